@@ -6,12 +6,19 @@ five angles -- one "step" = one full spectrum (trx_run: CIA + line sweep +
 optical depth + intensities + flux) with the line list, grids and Voigt table
 already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  metric = wavenumber-points x layers / s where
 "layers" is the number of layers the reference's lazy sweep needs for this
 input (deepest toomuch crossing), as in BASELINE.md.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds
+everything else: the steady-state and device-spectrum riders, the event-timed kernel
+breakdown and roofline, cold-start / multi-handle / batch / CLI figures, the CPU baseline,
+the N>1 secondary measurements and the --rehearse check.  --dump-outputs DIR writes the
+spectrum of the last timed step to DIR/spectrum.npy (float64; a fixed sample of it, with
+DIR/spectrum_index.npy, where the whole would exceed 60 MB).
 """
 from __future__ import annotations
 
@@ -20,6 +27,7 @@ import datetime
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -71,7 +79,15 @@ def parse():
     ap.add_argument("--comm-single", action="store_true",
                     help="N=1 only: run through a 1-rank RCCL communicator (the code path every rank of an N>1 job takes)")
     ap.add_argument("--cpu-lines", type=int, default=0, help="lines of the CPU-baseline sample (0 = full workload)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (riders, kernel breakdown, roofline, cold start, "
+                         "handles, batch, CLI, CPU baseline, N>1 extras, --rehearse check); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the spectrum of the last timed step to DIR/spectrum.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def kernel_source_hash():
@@ -160,6 +176,11 @@ def measured_valu(kernel, key=DEMO_KEY, family=True):
     return None
 
 
+WORKDIRS = []          # the workload directories of this process alone (removed before it exits)
+DUMP_MAX_BYTES = 60_000_000           # --dump-outputs writes at most this much (plus the .npy headers)
+DUMP_SAMPLE = 1 << 21                 # values in the sample of a larger spectrum (16 MiB, and as much for their indices)
+
+
 def make_workload(args, tag, nlines, verb=2, wnhigh=None, unique=True):
     from transit_amd import synth
     d = os.path.join(tempfile.gettempdir(), "transit_bench_%s_%d_%d_%s" % (
@@ -168,12 +189,30 @@ def make_workload(args, tag, nlines, verb=2, wnhigh=None, unique=True):
         d += "_3sp"
     if not unique and os.path.exists(os.path.join(d, "case.cfg")):
         return d
+    if unique:
+        WORKDIRS.append(d)
     dbs = synth.three_species_dbs(nlines // 3, args.wnlow, wnhigh or args.wnhigh) if getattr(args, "species", 1) == 3 else None
     synth.make_case(d, nlines=nlines, dbs=dbs, wnlow=args.wnlow, wnhigh=wnhigh or args.wnhigh, wndelt=args.wndelt,
                     wnosamp=args.wnosamp,
                     nlayers=args.layers, solution=args.solution, toomuch=10.0, ethresh=1e-50, nwidth=20.0,
                     raygrid="0 20 40 60 80", ncia=args.ncia, seed=1234, extra={"verb": verb})
     return d
+
+
+def dump_outputs(dirname, spectrum):
+    """--dump-outputs: what the timed call hands its caller (the spectrum) as DIR/spectrum.npy, float64.  Where
+    the whole would exceed DUMP_MAX_BYTES, a fixed sample (seeded, sorted indices in DIR/spectrum_index.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    spec = np.ascontiguousarray(spectrum, dtype=np.float64)
+    index = os.path.join(dirname, "spectrum_index.npy")
+    if spec.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(dirname, "spectrum.npy"), spec)
+        if os.path.exists(index):
+            os.remove(index)
+        return
+    idx = np.sort(np.random.default_rng(1234).choice(spec.size, size=DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(dirname, "spectrum.npy"), spec[idx])
+    np.save(index, idx.astype(np.float64))
 
 
 def cpu_baseline(args, gpu_spectrum_full):
@@ -389,6 +428,22 @@ def main():
         # device memory for the gather (trx_run_device + trx_gather).  The other form rides along (ms_device_spectrum).
         timed = step_host if world == 1 else step
         ms_step = time_steps(timed, fence, warmup, steps, reduce_max if world > 1 else None)
+        # what the timed call handed back in its last step (N > 1: the slices stitched, complete on rank 0)
+        if world == 1:
+            spectrum = host_spec.copy()
+        else:
+            g = gathered.cpu().numpy()
+            spectrum = np.concatenate([g[k * mpad: k * mpad + (h - l)] for k, (l, h) in enumerate(bounds)])
+        out = dict(P=P, eng=eng, ms_step=ms_step, spectrum=spectrum, nwn=nwn, bounds=bounds, t_first_create=t_first_create,
+                   opts=opts, dir=d, static=st)
+        if not args.full:
+            # the headline's "layers": how deep the rays of this input go (one more run, after the timed region)
+            r = eng.run(P.atm, opts, debug=("last",))
+            out["layers_needed"] = int(reduce_max(int(r["last"].max()) + 1)) if world > 1 else int(r["last"].max()) + 1
+            if not keep:
+                eng.close()
+                out["eng"] = None
+            return out
         # rider: the same step timed over at least 200 more steps right behind the timed region (no further
         # warm-up).  The headline keeps the driver's K and W; with K = 20 its 7 ms sit on a device whose
         # clocks are still on their way up (5 warm-up steps are 2 ms of GPU work): 0.362 ms per step
@@ -426,10 +481,8 @@ def main():
             full = spec_local[: hi - lo].cpu().numpy()
             if not np.array_equal(full, host_spec):
                 raise SystemExit("bench: trx_run and trx_run_device returned different spectra")
-        out = dict(P=P, eng=eng, stats=stats, ms_step=ms_step, ms_steady=ms_steady, steady_steps=steady_steps or steps,
-                   ms_device_spectrum=ms_device_spectrum,
-                   layers_needed=layers_needed, full=full, nwn=nwn,
-                   bounds=bounds, t_first_create=t_first_create, opts=opts, dir=d, static=st)
+        out.update(stats=stats, ms_steady=ms_steady, steady_steps=steady_steps or steps, ms_device_spectrum=ms_device_spectrum,
+                   layers_needed=layers_needed, full=full)
         if not keep:
             eng.close()
             out["eng"] = None
@@ -437,17 +490,59 @@ def main():
 
     # ---- headline: the CH4-demo run.  N>1: that ONE run split N ways (BASELINE.json's metric: strong
     # scaling) unless --scaling weak (one demo-sized slice per GPU, the band and the line list grown
-    # N-fold); either way the other mode is measured too and reported under config.
+    # N-fold); either way, with --full, the other mode is measured too and reported under config.
     grow = world if (args.scaling == "weak" and world > 1) else 1
     wnhigh = args.wnlow + grow * (args.wnhigh - args.wnlow)
     d = shared_case("demo", grow * args.lines, wnhigh=wnhigh)
     M = sharded_run(d, args.steps, args.warmup, keep=True)
-    P, eng, stats, ms_step, layers_needed, full, nwn = (M[k] for k in ("P", "eng", "stats", "ms_step", "layers_needed", "full", "nwn"))
+    P, eng, ms_step, layers_needed, nwn = (M[k] for k in ("P", "eng", "ms_step", "layers_needed", "nwn"))
     opts, st = M["opts"], M["static"]
     lo, hi = M["bounds"][rank]
     nlayer = P.nlayer
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, M["spectrum"])
 
-    extras = {"ms_create_first_in_process": 1e3 * M["t_first_create"]}
+    def finish():
+        eng.close()
+        if comm is not None:
+            tdist.destroy_comm(comm)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        for wd in WORKDIRS:
+            shutil.rmtree(wd, ignore_errors=True)
+
+    head = {
+        "metric": "wavenumber-points*layers/sec (CH4 2-4um emission spectrum)",
+        "value": nwn * layers_needed / (ms_step * 1e-3),
+        "unit": "wavenumber-points*layers/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+        "timed_call": "trx_run: atmosphere from host memory, spectrum back to host memory (SURVEY 8(d) t_run)" if world == 1
+                      else "trx_run_device + trx_gather: the slices stay in device memory for the one ncclAllGather",
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "%s%s: %g-%g cm-1 @%g cm-1, wnosamp %d, %s, "
+                               "%s, H2-H2%s CIA" % (
+                                   baseline_config(args, grow),
+                                   " -- BASELINE configs[1] with band and line list x%d: one demo-sized slice per GPU" % grow if grow > 1 else "",
+                                   args.wnlow, wnhigh, args.wndelt, args.wnosamp,
+                                   "H2O + CH4 + CO lines" if args.species == 3 else "CH4 lines",
+                                   "eclipse, 5 angles" if args.solution == "eclipse" else "transit (slant paths)",
+                                   " + H2-He" if args.ncia > 1 else ""),
+                   "n_wn": nwn, "n_layers": nlayer, "layers_needed": layers_needed, "n_lines": int(st.nlines),
+                   "parallelism": "wn-shard x%d, bins split by cost %s, one trx_gather per spectrum" % (
+                       world, [h - l for l, h in M["bounds"]]) if world > 1 else "one GPU",
+                   "ms_create_first_in_process": 1e3 * M["t_first_create"]},
+    }
+    if not args.full:
+        head["config"]["secondary"] = "not measured in this run: bench.py --full"
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        finish()
+        return
+
+    stats, full = M["stats"], M["full"]
+    extras = {}
     if world > 1:
         # what every rank paid, so that a SCALE line explains itself: the event-timed kernels of ITS shard (walks, combine /
         # accumulate, optical depth), the device time of a whole run and the host's time in the call, per spectrum
@@ -626,31 +721,13 @@ def main():
         valu_frac = (valu * 4.0 / (kern[dom] / dlaunch * 1e-3 * 1024 * 2.4e9)) if (valu and kern[dom] > 0) else None
         tr_pair, traffic_file = measured_traffic(prof_k, wkey) if world == 1 else (None, None)
         traffic, traffic_raw = tr_pair if tr_pair else (None, None)
-        out = {
-            "metric": "wavenumber-points*layers/sec (CH4 2-4um emission spectrum)",
-            "value": nwn * layers_needed / (ms_step * 1e-3),
-            "unit": "wavenumber-points*layers/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+        out = dict(head, **{
             "ms_per_step_steady": M["ms_steady"], "steady_steps": M["steady_steps"],
-            "timed_call": "trx_run: atmosphere from host memory, spectrum back to host memory (SURVEY 8(d) t_run)" if world == 1
-                          else "trx_run_device + trx_gather: the slices stay in device memory for the one ncclAllGather",
             "ms_per_step_device_spectrum": M["ms_device_spectrum"],
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s%s: %g-%g cm-1 @%g cm-1, wnosamp %d, %s, "
-                                   "%s, H2-H2%s CIA" % (
-                                       baseline_config(args, grow),
-                                       " -- BASELINE configs[1] with band and line list x%d: one demo-sized slice per GPU" % grow if grow > 1 else "",
-                                       args.wnlow, wnhigh, args.wndelt, args.wnosamp,
-                                       "H2O + CH4 + CO lines" if args.species == 3 else "CH4 lines",
-                                       "eclipse, 5 angles" if args.solution == "eclipse" else "transit (slant paths)",
-                                       " + H2-He" if args.ncia > 1 else ""),
-                       "n_wn": nwn, "n_layers": nlayer, "layers_needed": layers_needed, "layers_swept": R,
-                       "n_lines": int(st.nlines), "n_groups": stats["ngroups"], "n_kmax_candidates": stats["ncandidates"],
+            "config": dict(head["config"], **{
+                       "layers_swept": R, "n_groups": stats["ngroups"], "n_kmax_candidates": stats["ncandidates"],
                        "sum_bins": stats["sum_bins"],
                        "voigt_grid": "%dx%d" % (st.ndop, st.nlor), "table_floats": stats["table_floats"],
-                       "parallelism": "wn-shard x%d, bins split by cost %s, one trx_gather per spectrum" % (
-                           world, [h - l for l, h in M["bounds"]]) if world > 1 else "one GPU",
                        "layer_chunk": args.layer_chunk or "auto: the previous run's depth in equal steps (<= 64 layers where "
                                                           "the line walk applies, one lane per layer)",
                        "steps_per_run": launches, "walk_steps_per_run": wsteps,
@@ -673,7 +750,7 @@ def main():
                        "ms_host_cia": stats["ms_cia"], "ms_host_total_profiled_run": stats["ms_host_total"],
                        "b_alg_run_bytes": b_alg_run, "b_min_run_bytes": b_min_run,
                        "whole_run_alg_GBs": b_alg_run / (ms_step * 1e-3) / 1e9,
-                       "line_layer_bins_per_s": world * stats["sum_bins"] / (ms_step * 1e-3)},
+                       "line_layer_bins_per_s": world * stats["sum_bins"] / (ms_step * 1e-3)}),
             "roofline": {"bound": "hbm (distance, not the binding roof)", "kernel": dom_label, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach / HBM_PEAK_GBS,
                          "kernels": walk_forms if dom == "k_line_walk" else None,
@@ -697,7 +774,7 @@ def main():
                                  "layers) and ~42 (eight-bin frames, k_line_walk_lanes) vector instructions per line and step, most at the fp64 "
                                  "rate of one per 4 clocks and SIMD, and the deep step's row gathers are one L2 request per (group, layer) -- valu_issue_frac = SQ_INSTS_VALU x 4 clocks / "
                                  "(launch time x 1024 SIMDs x 2.4 GHz); counters and probes in profiles/, DESIGN.md section 4"},
-        }
+        })
         out["config"].update(extras)
         if "k_accumulate" in dom and ach > HBM_PEAK_GBS:
             # wide-profile regime (fine grids): neighbouring lines read the same profile rows, staged in
@@ -728,12 +805,7 @@ def main():
             except Exception as e:          # the baseline must never sink the measurement
                 out["cpu_baseline"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
-    eng.close()
-    if comm is not None:
-        tdist.destroy_comm(comm)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

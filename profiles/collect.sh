@@ -14,7 +14,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --no-cpu-baseline --no-extras $WORKLOAD"
+BENCH="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras $WORKLOAD"
 run() {     # run NAME ARGS... -- one profiled bench run, its CSVs copied out
   local name=$1; shift
   rm -rf /tmp/prof_$name

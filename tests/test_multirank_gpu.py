@@ -33,7 +33,7 @@ def test_bench_multirank_code_path_rehearsal():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "2", "--rehearse", "--no-extras", "--lines", "30000",
+           "--gpus", "2", "--steps", "3", "--warmup", "2", "--rehearse", "--full", "--no-extras", "--lines", "30000",
            "--layers", "40", "--wnhigh", "2700"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
@@ -58,7 +58,7 @@ def test_bench_secondary_measurements_are_guarded():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", TRANSIT_BENCH_EXTRAS_BUDGET_S="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "2", "--rehearse", "--lines", "30000", "--layers", "40", "--wnhigh", "2700"]
+           "--gpus", "2", "--steps", "3", "--warmup", "2", "--rehearse", "--full", "--lines", "30000", "--layers", "40", "--wnhigh", "2700"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
