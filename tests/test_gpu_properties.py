@@ -549,3 +549,28 @@ def test_threaded_create_gives_the_single_thread_groups(tmp_path, osamp, wndelt)
     assert np.array_equal(res[0][0], res[1][0])
     if osamp == 1:
         assert res[0][2] > 10_000          # the dense list does co-add
+
+
+def test_stats_describe_the_last_run_not_a_per_molecule_sweep():
+    """trx_stats' walk counters are "of the last run" (include/transit_hip.h): a per-molecule sweep on the
+    same handle in between (trx_sweep_permol, which walks the lines too) changes none of them."""
+    P = golden("eclipse_small").problem
+    walk = ("walk_steps", "walk_records", "walk_record_lanes", "walk_form_steps", "walk_form_layers", "walk_form_record_lanes")
+    eng = Engine(P.static)
+    try:
+        eng.run(P.atm, P.opts)
+        eng.run(P.atm, P.opts)                   # hinted: what the next hinted run repeats
+        first = eng.stats()
+        assert first["walk_steps"] > 0
+        iso_slot = np.zeros(P.static.niso, dtype=np.int32)        # (one line database: one molecule slot)
+        o = eng.sweep_permol(P.nlayer, P.atm.temp, P.atm.density, P.atm.zpart, P.opts.ethresh, 1,
+                             iso_slot.ctypes.data_as(_abi.c_int32_p))
+        assert (o != 0).any()
+        between = eng.stats()
+        eng.run(P.atm, P.opts)
+        second = eng.stats()
+    finally:
+        eng.close()
+    for k in walk:
+        assert between[k] == first[k], (k, first[k], between[k])
+        assert second[k] == first[k], (k, first[k], second[k])

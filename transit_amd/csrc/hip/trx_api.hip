@@ -1250,7 +1250,8 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
   int rc = walk_plan(h, nb, st, P, pl);
   if (rc) return rc;
   DevBuf &part = h->d_part[parity & 1];
-  h->stats.walk_steps++; h->stats.walk_records += pl->records; h->stats.walk_record_lanes += pl->records * nc;
+  // (trx_stats describes the last trx_run: a per-molecule sweep (trx_sweep_permol) walks too but is not counted)
+  if (!M.permol) { h->stats.walk_steps++; h->stats.walk_records += pl->records; h->stats.walk_record_lanes += pl->records * nc; }
   const size_t pbytes = sizeof(double) * kWalkLayers * (size_t)std::max<int64_t>(pl->records, 1);
   if (part.bytes < pbytes) {
     HIPCHK(h, hipStreamSynchronize(st));                 // an earlier step may still be using the old buffer
@@ -1274,7 +1275,12 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
   A.part = part.as<double>(); A.counters = M.prof ? h->d_counters.as<unsigned long long>() : nullptr;
   A.flags = h->d_flags.as<int>(); A.last = M.skip_done ? h->d_last.as<int>() : nullptr; A.eager = M.eager;
   // a shard launches only the ranges that can reach it: per isotope block the groups whose cells
-  // lie within Rc + 1 cells of [lo, hi) are one run of consecutive ranges (cnt_ge look-up)
+  // lie within Rc + 1 cells of [lo, hi) are one run of consecutive ranges (cnt_ge look-up).  A range
+  // reaches the bins of its whole span (the plan's blo..bhi: its lowest cell - Rc to its highest + Rc + 1),
+  // and the combine reads its records there: so a range whose groups sit on both sides of the window,
+  // none inside, is launched too (it writes the zeros; skipped, the combine would add whatever the record
+  // buffer held).  Groups below cell 0 (the grid's first line when it lies just below the band) count
+  // as in reach of a window that starts within Rc + 1 cells of the bottom.
   unsigned nw = (unsigned)h->nwaves;
   A.nseg = 0;
   if (h->windowed() && h->niso <= kWalkSegs && nw > 0) {
@@ -1285,9 +1291,11 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
       const int gb0 = h->h_gblock[b], gb1 = h->h_gblock[b + 1];
       if (gb0 == gb1) continue;
       const int32_t *cg = &h->h_cntge[(size_t)b * (h->nwn + 1)];
-      const int ga = cg[khi + 1], gz = cg[klo];                 // groups of the block (descending cells) with cell in [klo, khi]
-      if (gz <= ga) continue;
+      // groups of the block (descending cells) with cell in [klo, khi]: [ga, gz)
+      const int ga = cg[khi + 1], gz = h->lo - Rc - 1 <= 0 ? gb1 - gb0 : cg[klo];
+      // the ranges holding a group on each side of ga and of gz - 1: empty only where the window falls between two ranges
       const int wa = h->h_wbase[b] + ga / h->ngw, wz = h->h_wbase[b] + (gz + h->ngw - 1) / h->ngw;
+      if (wz <= wa) continue;
       A.seg_w0[ns] = wa; A.seg_cum[ns] = cum; cum += wz - wa; ns++;
     }
     A.seg_cum[ns] = cum; A.nseg = ns;
@@ -1304,7 +1312,7 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
   const bool lanes = lanes_prod && !M.prof, packed = packed_prod && !M.prof;
   const int form_prod = lanes_prod ? 1 : packed_prod ? 2 : 0, form = lanes ? 1 : packed ? 2 : 0;
   if (form_out) *form_out = form_prod;
-  h->stats.walk_form_steps[form_prod]++; h->stats.walk_form_layers[form_prod] += nc; h->stats.walk_form_record_lanes[form_prod] += pl->records * nc;
+  if (!M.permol) { h->stats.walk_form_steps[form_prod]++; h->stats.walk_form_layers[form_prod] += nc; h->stats.walk_form_record_lanes[form_prod] += pl->records * nc; }
   if (sp && sp->begin(form == 1 ? Spans::kWalkLanes : form == 2 ? Spans::kWalkPacked : Spans::kWalk, st)) return fail(h, TRX_E_HIP, "event");
   if (lanes) {
     // one range per wave (round 4 measured 2, 3, 4 ranges per wave at the demo size: 0.257 / 0.283 / 0.276 ms for the
