@@ -3,6 +3,8 @@
     libtransit_host.so  g++    host side: options, file formats, samplings
     libtransit_hip.so   hipcc  --offload-arch=gfx950: the kernels + the C ABI
     transit_hip         g++    CLI driver linking both (drop-in for `transit`)
+    libtransit.so       g++    the reference's library interface (include/transit_lib.h)
+                               over both, exporting its ten functions only
 
 Everything lands in transit_amd/lib/ (git-ignored, shipped to the GPU box with
 the tree).  hipcc cross-compiles gfx950 without a GPU.
@@ -66,15 +68,41 @@ def build_hip(force: bool = False) -> str:
     return out
 
 
+# the per-spectrum host code the CLI and the library share (messages, opacity-grid build, debug buffers, writers)
+OUTPUTS_SOURCES = ["host/transit_outputs.cpp"]
+OUTPUTS_DEPS = ["host/transit_outputs.cpp", "host/transit_outputs.h"]
+
+
+def _host_deps():
+    return ([os.path.join(CSRC, d) for d in OUTPUTS_DEPS] + [lib_path("libtransit_host.so"), lib_path("libtransit_hip.so")]
+            + [os.path.join(ROOT, "include", h) for h in ("transit_host.h", "transit_hip.h")])
+
+
 def build_cli(force: bool = False) -> str:
     out = lib_path("transit_hip")
     src = os.path.join(CSRC, "host", "transit_main.cpp")
     if not os.path.exists(src):
         return ""
-    deps = [src, lib_path("libtransit_host.so"), lib_path("libtransit_hip.so")]
+    deps = [src] + _host_deps()
     if force or _newer(out, deps):
-        _run([CXX, "-O2", "-std=c++17", "-Wall", "-pthread", "-o", out, src, "-I", os.path.join(ROOT, "include"),
+        _run([CXX, "-O2", "-std=c++17", "-Wall", "-pthread", "-o", out, src,
+              *[os.path.join(CSRC, s) for s in OUTPUTS_SOURCES], "-I", os.path.join(ROOT, "include"),
               "-L", LIB, "-ltransit_host", "-ltransit_hip", "-Wl,-rpath,$ORIGIN"])
+    return out
+
+
+def build_lib(force: bool = False) -> str:
+    """libtransit.so: transit_init / run_transit / free_memory ... (include/transit_lib.h).  Hidden
+    visibility and a version script: its only defined dynamic symbols are the header's ten functions."""
+    out = lib_path("libtransit.so")
+    src = os.path.join(CSRC, "host", "transit_lib.cpp")
+    vscript = os.path.join(CSRC, "host", "transit_lib.map")
+    deps = [src, vscript, os.path.join(ROOT, "include", "transit_lib.h")] + _host_deps()
+    if force or _newer(out, deps):
+        _run([CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-fvisibility=hidden",
+              "-fvisibility-inlines-hidden", "-o", out, src, *[os.path.join(CSRC, s) for s in OUTPUTS_SOURCES],
+              "-I", os.path.join(ROOT, "include"), "-L", LIB, "-ltransit_host", "-ltransit_hip",
+              "-Wl,--version-script=" + vscript, "-Wl,--no-undefined", "-Wl,-rpath,$ORIGIN"])
     return out
 
 
@@ -82,6 +110,7 @@ def build_all(force: bool = False):
     build_host(force)
     build_hip(force)
     build_cli(force)
+    build_lib(force)
 
 
 if __name__ == "__main__":

@@ -25,6 +25,7 @@
 
 #include "transit_hip.h"
 #include "transit_host.h"
+#include "transit_outputs.h"
 
 static double now_s()
 { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -36,7 +37,8 @@ struct Rank {
   trx_static st{};                   // this rank's copy: shard, device, communicator
   trx_handle *h = nullptr;
   int rc = TRX_OK; std::string err;
-  std::vector<double> slice, tau, e, ecs, intens, er, es, ec; std::vector<int64_t> last; std::vector<uint8_t> comp;
+  std::vector<double> slice;
+  trr::Buffers buf;                  // this shard's debug arrays
   trx_stats stats{};
 };
 
@@ -72,14 +74,8 @@ int main(int argc, char **argv)
   int rc = trh_load((int)args.size(), args.data(), &P, err, sizeof(err));
   if (rc == 1) return EXIT_SUCCESS;                       // --help / --version (argum.c:582-607)
   if (rc != TRX_OK) { std::fprintf(stderr, "transit_hip: %s (%s)\n", err, trx_strerror(rc)); return EXIT_FAILURE; }
-  const char *verb = trh_option(P, "verb");
-  const int verblevel = verb ? std::atoi(verb) : 2;
-  if (verblevel >= 2)                                     // TOUT_WARN is level 2, TOUT_INFO level 3 (flags_tr.h:181-185)
-    for (const char *m = trh_messages(P); m && *m; ) {
-      const char *e = std::strchr(m, '\n'); const size_t n = e ? (size_t)(e - m) : std::strlen(m);
-      if (m[0] == 'W' || verblevel >= 3) std::fprintf(stderr, "transit_hip: %s: %.*s\n", m[0] == 'W' ? "warning" : "note", (int)(n > 3 ? n - 3 : 0), m + 3);
-      m = e ? e + 1 : m + n;
-    }
+  const int verblevel = trr::verb_level(P);
+  trr::print_messages(P, verblevel, "transit_hip");
   if (verblevel > 3) std::printf("Check point: 00 - 04 inputs read and sampled:  dt = %.4f sec.\n\n", now_s() - t0);
 
   const int64_t nwn = trh_nwn(P);
@@ -88,44 +84,16 @@ int main(int argc, char **argv)
 
   // --opacityfile names a file that does not exist yet: build the grid on ONE GPU
   // (calcopacity, opacity.c:282-427), write it, and go on with it as the reference does
-  t0 = now_s();
-  if (trh_needs_opacity_build(P)) {
-    trx_handle *h = nullptr;
-    rc = trx_create(trh_static(P), &h);
-    if (rc != TRX_OK) { std::fprintf(stderr, "transit_hip: trx_create failed: %s\n", trx_strerror(rc)); trh_free(P); return EXIT_FAILURE; }
-    int32_t nv = 0, nslot = 0; const double *gt, *gd, *gz; const int32_t *gs;
-    trh_grid_request(P, &nv, &gt, &gd, &gz, &nslot, &gs);
-    std::vector<double> grid((size_t)nv * nslot * nwn);
-    rc = trx_sweep_permol(h, nv, gt, gd, gz, trh_opts(P)->ethresh, nslot, gs, grid.data());
-    if (rc == TRX_OK) rc = trh_install_opacity(P, grid.data());
-    if (rc != TRX_OK) {
-      std::fprintf(stderr, "transit_hip: opacity-grid build failed: %s (%s)\n", trx_strerror(rc), trx_last_error(h));
-      trx_destroy(h); trh_free(P); return EXIT_FAILURE;
-    }
-    if (verblevel > 3) std::printf("Check point: 00 - 05 opacity grid (%d states x %d molecules):  dt = %.4f sec.\n\n", nv, nslot, now_s() - t0);
-    trx_destroy(h);
+  {
+    std::string oerr;
+    if (trr::build_opacity_grid(P, verblevel, oerr) != TRX_OK) { std::fprintf(stderr, "transit_hip: %s\n", oerr.c_str()); trh_free(P); return EXIT_FAILURE; }
   }
   if (trh_option(P, "justOpacity")) { trh_free(P); return EXIT_SUCCESS; }   // transit.c:133-136
 
   // ---- what the run has to hand back
-  const bool want_toomuch = trh_option(P, "outtoomuch") != nullptr;
-  const char *sf = trh_option(P, "savefiles");
-  const bool want_dumps = sf && std::strncmp(sf, "yes", 3) == 0;                // argum.c:461-470
-  const bool det_tau = trh_wants_detail(P, 0), det_ext = trh_wants_detail(P, 1), det_cia = trh_wants_detail(P, 2);
-  const bool want_intens = trh_option(P, "outintens") != nullptr && trh_opts(P)->solution == TRX_SOL_ECLIPSE;
-  // --saveext: the extinction of an earlier run back in (restfile_extinct, tau.c:155-156), this run's out (tau.c:340-341)
-  const bool want_saveext = trh_option(P, "saveext") != nullptr;
-  std::vector<double> ext_in; std::vector<uint8_t> ext_flags;
-  bool restored = false;
-  if (want_saveext) {
-    ext_in.resize((size_t)nwn * nr); ext_flags.assign((size_t)nr, 0);
-    restored = trh_saveext_read(P, ext_in.data(), ext_flags.data()) == TRX_OK;
-    if (!restored && verblevel >= 2) std::fprintf(stderr, "transit_hip: note: no extinction restored from '%s'\n", trh_option(P, "saveext"));
-  }
-  const bool need_tau = want_toomuch || want_dumps || det_tau || det_ext, need_e = want_dumps || det_ext || want_saveext, need_ecs = want_dumps || det_cia;
-  const int nang = trh_opts(P)->nangles;
-  if (want_dumps && trh_write_sample(P, nullptr) != TRX_OK)                     // makesample.c:598-599
-    std::fprintf(stderr, "transit_hip: cannot write the sampling file\n");
+  const trr::Plan plan = trr::plan_outputs(P);
+  trr::Saved saved;
+  trr::before_spectrum(P, plan, verblevel, "transit_hip", saved);
 
   // ---- shards, devices, communicator
   std::vector<int64_t> bounds((size_t)ngpus + 1);
@@ -195,25 +163,16 @@ int main(int argc, char **argv)
     if (k == fail_rank) { r.rc = TRX_E_HIP; r.err = "trx_run (TRANSIT_HIP_FAIL_RANK)"; return; }
     if ((r.rc = trx_create(&r.st, &r.h)) != TRX_OK) { r.err = "trx_create"; return; }
     const int64_t n = bounds[k + 1] - bounds[k];
-    if (restored) {                                        // this shard's columns of the restored rows
+    if (saved.restored) {                                  // this shard's columns of the restored rows
       std::vector<double> part((size_t)n * nr);
-      for (int l = 0; l < nr; l++) std::memcpy(&part[(size_t)l * n], &ext_in[(size_t)l * nwn + bounds[k]], sizeof(double) * (size_t)n);
-      if ((r.rc = trx_restore_extinction(r.h, nr, part.data(), ext_flags.data())) != TRX_OK) { r.err = "trx_restore_extinction"; return; }
+      for (int l = 0; l < nr; l++) std::memcpy(&part[(size_t)l * n], &saved.e[(size_t)l * nwn + bounds[k]], sizeof(double) * (size_t)n);
+      if ((r.rc = trx_restore_extinction(r.h, nr, part.data(), saved.flags.data())) != TRX_OK) { r.err = "trx_restore_extinction"; return; }
     }
     r.slice.assign((size_t)count, 0.0);
     trx_debug dbg{};
-    if (need_tau) { r.tau.resize((size_t)n * nr); r.last.resize((size_t)n); dbg.tau = r.tau.data(); dbg.last = r.last.data(); }
-    if (need_e) { r.e.resize((size_t)n * nr); dbg.e = r.e.data(); }
-    if (want_saveext) { r.comp.assign((size_t)nr, 0); dbg.computed = r.comp.data(); }
-    if (need_ecs) { r.ecs.resize((size_t)n * nr); dbg.e_cs = r.ecs.data(); }
-    if (want_intens) { r.intens.resize((size_t)n * nang); dbg.intens = r.intens.data(); }
     trx_opts opts = *trh_opts(P);
-    if (want_dumps) {                                      // the dump writers redo the reference's laziness from `last`
-      opts.eager = 1;
-      r.er.resize((size_t)n * nr); r.es.resize((size_t)n * nr); r.ec.resize((size_t)n * nr);
-      dbg.er = r.er.data(); dbg.e_scat = r.es.data(); dbg.e_cloud = r.ec.data();
-    }
-    r.rc = trx_run(r.h, trh_atm(P), &opts, r.slice.data(), (dbg.tau || dbg.e || dbg.e_cs || dbg.intens) ? &dbg : nullptr);
+    const bool any = r.buf.attach(plan, n, dbg, opts);
+    r.rc = trx_run(r.h, trh_atm(P), &opts, r.slice.data(), any ? &dbg : nullptr);
     if (r.rc != TRX_OK) { r.err = std::string("trx_run: ") + trx_last_error(r.h); return; }
     trx_get_stats(r.h, &r.stats);
   };
@@ -238,41 +197,27 @@ int main(int argc, char **argv)
   std::vector<double> spectrum((size_t)nwn);
   for (int k = 0; k < ngpus; k++)
     std::memcpy(&spectrum[(size_t)bounds[k]], &gathered[(size_t)k * count], sizeof(double) * (size_t)(bounds[k + 1] - bounds[k]));
-  std::vector<double> tau, e, ecs, intens, er, es, ec; std::vector<int64_t> last;
-  if (want_dumps) { er.resize((size_t)nwn * nr); es.resize((size_t)nwn * nr); ec.resize((size_t)nwn * nr); }
-  if (need_tau) { tau.resize((size_t)nwn * nr); last.resize((size_t)nwn); }
-  if (need_e) e.resize((size_t)nwn * nr);
-  if (need_ecs) ecs.resize((size_t)nwn * nr);
-  if (want_intens) intens.resize((size_t)nwn * nang);
+  trr::Buffers full;                                       // the shards' debug arrays joined: whole-grid layouts
+  trx_debug fdbg{}; trx_opts fopts = *trh_opts(P);
+  full.attach(plan, nwn, fdbg, fopts);
   for (int k = 0; k < ngpus; k++) {                       // debug layouts: tau [wn][height], e/e_cs [layer][wn], intens [angle][wn]
-    const Rank &r = R[(size_t)k];
+    const trr::Buffers &r = R[(size_t)k].buf;
     const int64_t lo = bounds[k], n = bounds[k + 1] - bounds[k];
-    if (need_tau) { std::memcpy(&tau[(size_t)lo * nr], r.tau.data(), sizeof(double) * (size_t)n * nr); std::memcpy(&last[(size_t)lo], r.last.data(), sizeof(int64_t) * (size_t)n); }
+    if (plan.need_tau) { std::memcpy(&full.tau[(size_t)lo * nr], r.tau.data(), sizeof(double) * (size_t)n * nr); std::memcpy(&full.last[(size_t)lo], r.last.data(), sizeof(int64_t) * (size_t)n); }
     for (int l = 0; l < nr; l++) {
-      if (need_e) std::memcpy(&e[(size_t)l * nwn + lo], &r.e[(size_t)l * n], sizeof(double) * (size_t)n);
-      if (need_ecs) std::memcpy(&ecs[(size_t)l * nwn + lo], &r.ecs[(size_t)l * n], sizeof(double) * (size_t)n);
-      if (want_dumps) {
-        std::memcpy(&er[(size_t)l * nwn + lo], &r.er[(size_t)l * n], sizeof(double) * (size_t)n);
-        std::memcpy(&es[(size_t)l * nwn + lo], &r.es[(size_t)l * n], sizeof(double) * (size_t)n);
-        std::memcpy(&ec[(size_t)l * nwn + lo], &r.ec[(size_t)l * n], sizeof(double) * (size_t)n);
+      if (plan.need_e) std::memcpy(&full.e[(size_t)l * nwn + lo], &r.e[(size_t)l * n], sizeof(double) * (size_t)n);
+      if (plan.need_ecs) std::memcpy(&full.ecs[(size_t)l * nwn + lo], &r.ecs[(size_t)l * n], sizeof(double) * (size_t)n);
+      if (plan.dumps) {
+        std::memcpy(&full.er[(size_t)l * nwn + lo], &r.er[(size_t)l * n], sizeof(double) * (size_t)n);
+        std::memcpy(&full.es[(size_t)l * nwn + lo], &r.es[(size_t)l * n], sizeof(double) * (size_t)n);
+        std::memcpy(&full.ec[(size_t)l * nwn + lo], &r.ec[(size_t)l * n], sizeof(double) * (size_t)n);
       }
     }
-    for (int a = 0; a < nang && want_intens; a++) std::memcpy(&intens[(size_t)a * nwn + lo], &r.intens[(size_t)a * n], sizeof(double) * (size_t)n);
+    for (int a = 0; a < plan.nang && plan.intens; a++) std::memcpy(&full.intens[(size_t)a * nwn + lo], &r.intens[(size_t)a * n], sizeof(double) * (size_t)n);
   }
-  if (want_saveext) {
-    // a layer is in the file when EVERY shard swept it or it came out of the file already (whose row it keeps)
-    std::vector<uint8_t> flags((size_t)nr, 1);
-    for (int l = 0; l < nr; l++) {
-      for (auto &r : R) flags[(size_t)l] &= r.comp[(size_t)l];
-      if (restored && ext_flags[(size_t)l]) { flags[(size_t)l] = 1; std::memcpy(&e[(size_t)l * nwn], &ext_in[(size_t)l * nwn], sizeof(double) * (size_t)nwn); }
-      if (!flags[(size_t)l]) std::fill(e.begin() + (size_t)l * nwn, e.begin() + (size_t)(l + 1) * nwn, 0.0);
-    }
-    if (trh_saveext_write(P, e.data(), flags.data()) != TRX_OK) std::fprintf(stderr, "transit_hip: cannot write the extinction savefile\n");
-  }
-  if (need_e && need_tau) {                                // the run may have swept deeper than the deepest ray: give the rows
-    int64_t deep = 0;                                      // below it back the zeros the reference's lazy sweep leaves there
-    for (int64_t w = 0; w < nwn; w++) deep = std::max(deep, last[(size_t)w]);
-    std::fill(e.begin(), e.begin() + (size_t)(nr - 1 - deep) * nwn, 0.0);
+  if (plan.saveext) {                                      // a layer counts as swept when EVERY shard swept it
+    std::fill(full.comp.begin(), full.comp.end(), 1);
+    for (auto &r : R) for (int l = 0; l < nr; l++) full.comp[(size_t)l] &= r.buf.comp[(size_t)l];
   }
   if (verblevel > 3) {
     long long inr = 0, nadd = 0, swept = 0; double dev_ms = 0;
@@ -282,16 +227,7 @@ int main(int argc, char **argv)
                 ngpus, ngpus > 1 ? "s" : "", trh_opts(P)->solution == TRX_SOL_ECLIPSE ? "intensities + flux" : "modulation",
                 now_s() - t0, inr, nadd, swept, nr, dev_ms);
   }
-  if (want_toomuch) trh_write_toomuch(P, tau.data(), last.data(), nullptr);
-  if (want_intens) trh_write_intens(P, intens.data(), nullptr);
-  if (want_dumps && (trh_write_dumps_masked(P, e.data(), ecs.data(), tau.data(), last.data(), nullptr) != TRX_OK ||
-                     trh_write_ext_dumps(P, e.data(), ecs.data(), last.data(), er.data(), es.data(), ec.data(), nullptr) != TRX_OK))
-    std::fprintf(stderr, "transit_hip: cannot write the savefiles dumps\n");
-  if ((det_tau && trh_write_detail(P, 0, tau.data()) != TRX_OK) || (det_ext && trh_write_detail(P, 1, e.data()) != TRX_OK) ||
-      (det_cia && trh_write_detail(P, 2, ecs.data()) != TRX_OK))
-    std::fprintf(stderr, "transit_hip: cannot write a detail file\n");
-  rc = trh_write_spectrum(P, spectrum.data(), nullptr);
-  if (rc != TRX_OK) std::fprintf(stderr, "transit_hip: cannot write the spectrum file\n");
+  rc = trr::write_outputs(P, plan, saved, spectrum.data(), full, "transit_hip");
   if (verblevel > 3) std::printf("Check point: 00 - 15 outputs written:  wall since start = %.4f sec.\n", now_s() - t_start);
   cleanup(false);
   return rc == TRX_OK ? EXIT_SUCCESS : EXIT_FAILURE;
