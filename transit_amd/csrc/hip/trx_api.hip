@@ -109,6 +109,7 @@ struct trx_handle {
   bool no_binrec = false;                            // TRX_NO_BINREC: k_ray_tail finds a bin's records through the ranges' numbers (A/B, tests)
   int xcd_map = 1;                                   // blocks -> ranges by XCD (xcd_block): bit 0 k_line_walk_lanes, bit 1 k_line_walk (measured: slower there).  TRX_XCD_MAP, A/B
   bool lanes_walk = true, lanes_force = false; int max_gcount = 0; DevBuf d_linebase, d_rinfo;   // (TRX_LANES_WALK=2: also on sparse lists, tests)
+  int lanes_parts_most = 4;                          // k_line_walk_lanes: at most this many lanes per layer in phase 2 (TRX_LANES_PARTS, tests)
   bool no_row_copy = false, no_rows32 = false;
   bool row_staging = true;          // osamp == 1: wide profiles through k_accumulate_rows (TRX_NO_ROW_STAGING at create: tests compare the two forms)
   // lines
@@ -312,6 +313,7 @@ void test_switches(trx_handle *h)
   if (const char *e = std::getenv("TRX_XCD_MAP")) h->xcd_map = std::atoi(e);
   h->no_binrec = std::getenv("TRX_NO_BINREC") != nullptr;
   if (const char *e = std::getenv("TRX_LANES_WALK")) { h->lanes_walk = std::atoi(e) != 0; h->lanes_force = std::atoi(e) == 2; }      // k_line_walk_lanes never / also on sparse lists (test_gpu_lanes)
+  if (const char *e = std::getenv("TRX_LANES_PARTS")) h->lanes_parts_most = std::max(2, std::min(4, std::atoi(e)));      // ... with at most 2, 3 or 4 lanes per layer (test_gpu_lanes_parts)
   if (const char *e = std::getenv("TRX_RAY_TAIL")) h->ray_tail = std::atoi(e) != 0;            // the step kernels instead of k_ray_tail (test_gpu_tail)
   if (const char *e = std::getenv("TRX_CIA_SUMS")) h->cia_sums = std::atoi(e) != 0;
   if (const char *e = std::getenv("TRX_CIA_SEGMENTS")) h->cia_segments = std::atoi(e) != 0;  // the CIA splines' second derivatives in one sweep per table (test_gpu_cia_window)
@@ -490,7 +492,9 @@ int build_table(trx_handle *h, const trx_static *s)
         if (nq > 0 && 32 * nq < (1LL << 24) && s->osamp < (1 << 24) && 4 * tot32 < (1LL << 32) && !h->no_rows32) {
           DevBuf d_joff32;
           if ((rc = upload(h, d_joff32, joff32)) || (rc = upload(h, h->d_wp32, c32))) return rc;
-          if ((rc = ensure(h, h->d_tabW32, sizeof(float) * (size_t)tot32))) return rc;
+          // (and kLanesRowSlack floats behind: the last lane of a layer holding fewer bins than the others reads on past the row)
+          if ((rc = ensure(h, h->d_tabW32, sizeof(float) * ((size_t)tot32 + kLanesRowSlack)))) return rc;
+          HIPCHK(h, hipMemsetAsync(h->d_tabW32.as<float>() + tot32, 0, sizeof(float) * kLanesRowSlack, h->stream));
           for (size_t j0 = 0; j0 < jobs.size(); j0 += 32768) {
             const int nj = (int)std::min<size_t>(32768, jobs.size() - j0);
             hipLaunchKernelGGL(k_table_rows32, dim3(16, nj), dim3(256), 0, h->stream, d_jobs.as<ProfileJob>() + j0,
@@ -1321,11 +1325,23 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
     LanesExtra X{h->d_linebase.as<double>()};
     A.xcd_map = h->xcd_map & 1;
     if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG)
-      log_msg(TRX_LOG_DEBUG, "walk: lanes = lines, " + std::to_string(nc) + " layers, " + std::to_string(nb) + "-bin frames");
+      log_msg(TRX_LOG_DEBUG, "walk: lanes = lines, " + std::to_string(nc) + " layers, " + std::to_string(nb) + "-bin frames, " +
+                             std::to_string(lanes_parts(nc, h->lanes_parts_most)) + " lanes per layer");
     const dim3 grid((nw + kLanesWaves - 1) / kLanesWaves), block(64 * kLanesWaves);
     const size_t lds = lanes_lds_bytes(nc, h->ndop);
-    if (nb == 8) hipLaunchKernelGGL((k_line_walk_lanes<8, 5>), grid, block, lds, st, A, X);       // (blocks of 5 groups: a batch's ~28 are 6 blocks, an even number; 4: 102.2 us, 5: 101.2, 6: 103.6, round 5)
-    else         hipLaunchKernelGGL((k_line_walk_lanes<16, 2>), grid, block, lds, st, A, X);      // (blocks of 2 groups -- 8 floats per group and lane, 112 registers: 169.5 us; 3 / 4: 130 / 150 registers, 171.0 / 172.6, round 5)
+    // (blocks of 5 groups at 8 bins: a batch's ~28 are 6 blocks, an even number; 4: 102.2 us, 5: 101.2, 6: 103.6, round 5.
+    // Blocks of 2 at 16 bins -- with two lanes per layer 8 floats per group and lane, 112 registers: 169.5 us; 3 / 4:
+    // 130 / 150 registers, 171.0 / 172.6, round 5.)  Lanes per layer in phase 2: lanes_parts
+    const int parts = lanes_parts(nc, h->lanes_parts_most);
+    if (nb == 8) {
+      if (parts == 4)      hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 4>), grid, block, lds, st, A, X);
+      else if (parts == 3) hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 3>), grid, block, lds, st, A, X);
+      else                 hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 2>), grid, block, lds, st, A, X);
+    } else {
+      if (parts == 4)      hipLaunchKernelGGL((k_line_walk_lanes<16, 2, 4>), grid, block, lds, st, A, X);
+      else if (parts == 3) hipLaunchKernelGGL((k_line_walk_lanes<16, 2, 3>), grid, block, lds, st, A, X);
+      else                 hipLaunchKernelGGL((k_line_walk_lanes<16, 2, 2>), grid, block, lds, st, A, X);
+    }
   }
   else if (packed) {
     const int S = 64 / nc;

@@ -18,10 +18,11 @@
 //             [phase][profile][8 floats] for frames of 8 bins: the profile's offset + phase x slab).  Per
 //             (GROUP, layer): the weight kk (0 below the threshold) and that offset go to LDS -- 12 bytes,
 //             in the row of the group's RANK among the batch's groups (members of a group write a spare row).
-//   phase 2   lanes = (layer, half of the frame) exactly as k_line_walk<NB, false, 2>: the frame of NB
-//             accumulators slides down with the groups' cells, a bin that leaves it becomes one entry of
-//             the range's partial record -- but a group now costs a lane two LDS reads, one 16- or
-//             32-byte load and NB/2 multiply-adds.  Groups that share a cell (a dense list has hundreds
+//   phase 2   lanes = (layer, part of the frame), P = 2, 3 or 4 lanes per layer (lanes_parts: by the step's
+//             layer count), the frame logic of k_line_walk<NB, false, 2>: the frame of NB accumulators
+//             slides down with the groups' cells, a bin that leaves it becomes one entry of the range's
+//             partial record -- a group costs a lane two LDS reads, one load of its part's bins and
+//             NB/P (rounded up) multiply-adds.  Groups that share a cell (a dense list has hundreds
 //             per cell) are taken D at a time, consecutive ranks: their row segments are requested together,
 //             one block ahead of the block being added.  Two register sets take turns; WHICH of them is in
 //             flight when a batch ends is part of the control flow (the loop exists once per parity), so
@@ -50,15 +51,24 @@ constexpr int kLanesMaxGroup = 16;     // members of the longest co-added group 
 constexpr int kLanesMaxLayers = 32;
 constexpr int kLanesLayK = 12;         // doubles per layer record
 constexpr int kLanesBases = 4;         // base points of the rebased exponential a batch's table holds (more: computed per line)
+constexpr int kLanesRowSlack = 8;     // floats behind the compact rows: a layer's last lane of phase 2 with fewer bins than the others reads (and never writes out) past its row
 constexpr int kLanesRows = kLanesBatch + 2;      // rows of the two per-(group, layer) tables: the batch's groups by rank, a row of zeros (what a block's empty places read), a spare row (what the members of a group write)
 
 struct LanesExtra {
   const double *wbase;                 // [nlines] wavenumber of the line's base point (rebased exponential)
 };
 
-// per wave: kk [rows][ne] doubles, at [rows][ne] words, the layers' records (ne: layers rounded up to even), exp(ct * base point) [bases][ne], the groups' cells [batch] words
-__host__ __device__ inline int lanes_at_doubles(int ne) { return ((kLanesRows * ne / 2) + 1) & ~1; }      // (the offsets' words, a whole number of 16-byte units)
-__host__ __device__ inline int lanes_wave_doubles(int nc) { const int ne = (nc + 1) & ~1; return kLanesRows * ne + lanes_at_doubles(ne) + kLanesLayK * ne + kLanesBases * ne + kLanesBatch / 2; }
+// lanes per layer in phase 2 for a step of nc layers: 2 bins each while 4 lanes per layer fit the wave, then 3 (bins
+// 3/3/2), then 2 (4 bins); `most` caps it (TRX_LANES_PARTS, tests)
+__host__ __device__ inline int lanes_parts(int nc, int most = 4) { return min(most, nc <= 16 ? 4 : nc <= 21 ? 3 : 2); }
+
+// per wave: kk [rows][ns] doubles, at [rows][ns] words, the layers' records [nc], exp(ct * base point) [bases][ns], the
+// groups' cells [batch] words.  ns = nc rounded up to ODD: phase 1 stores a (group, layer) entry per lane, the lanes of one
+// store a row apart -- an odd row stride puts 16 consecutive rows' doubles (ds_write_b64) and 32 rows' words (ds_write_b32)
+// on distinct banks (an even one, 18 at 17 layers, had two rows on a bank)
+__host__ __device__ inline int lanes_stride(int nc) { return nc | 1; }
+__host__ __device__ inline int lanes_at_doubles(int ns) { return ((kLanesRows * ns + 1) / 2 + 1) & ~1; }      // (the offsets' words, a whole number of 16-byte units)
+__host__ __device__ inline int lanes_wave_doubles(int nc) { const int ns = lanes_stride(nc); return kLanesRows * ns + lanes_at_doubles(ns) + kLanesLayK * nc + kLanesBases * ns + kLanesBatch / 2; }
 __host__ __device__ inline size_t lanes_lds_bytes(int nc, int ndop) { return (size_t)kLanesWaves * 8 * (size_t)lanes_wave_doubles(nc) + 8 * (size_t)(ndop + 1); }
 
 // lane i <- lane i + 1 of the wave (DPP wave_shl:1; lane 63 gets 0)
@@ -69,12 +79,23 @@ __device__ __forceinline__ double wave_shl1(double v)
   return __hiloint2double(hi, lo);
 }
 
-template <int NB, int D>                                     // D: groups per block (two blocks in flight)
+// a frame's carry: what the lane one below holds (a layer's part 0 takes 0 instead)
+template <int P>
+__device__ __forceinline__ double carry_up(double v)
+{
+  // quad_perm [1,0,3,2] (the pair's other lane); row_shr:1 (a layer's four lanes never straddle a row of 16); wave_shr:1 (three lanes do)
+  return dpp_f64<P == 2 ? 0xB1 : P == 4 ? 0x111 : 0x138>(v);
+}
+
+template <int NB, int D, int P>                              // D: groups per block (two blocks in flight); P: lanes per layer in phase 2
 __global__ __launch_bounds__(64 * kLanesWaves)
 void k_line_walk_lanes(WalkArgs A, LanesExtra X)
 {
-  constexpr int Rc = NB / 2 - 1, NS = NB / 2, LPL = 2, BL = kLanesBatch;
+  // phase 2's lane (layer, part) holds NS consecutive bins of the frame from part * NS; the last part holds the NL left
+  // (3/3/2 for P = 3); its slots from NL on add what lies past the frame's row and are never written out
+  constexpr int Rc = NB / 2 - 1, NS = (NB + P - 1) / P, NL = NB - (P - 1) * NS, BL = kLanesBatch;
   static_assert(NB == 8 || NB == 16, "frames of 8 or 16 bins");
+  static_assert(P >= 2 && P <= 4 && NL >= 1 && NL <= NS, "2 to 4 lanes per layer");
   if (!A.eager && A.flags[0] == 0) return;
   __shared__ double s_e2[64];
   extern __shared__ double s_dyn[];
@@ -84,12 +105,12 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   // for together; the closed-ray test runs under them)
   const double e2_mine = threadIdx.x < 64 ? A.e2tab[threadIdx.x] : 0.0;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int nc = A.nc, ne = (nc + 1) & ~1;                   // (ne: layers rounded up to even -- a lane pair of phase 1 takes two)
-  double *s_kk = s_dyn + (size_t)wv * lanes_wave_doubles(nc);                // [rows][ne]
-  uint32_t *s_at = (uint32_t *)(s_kk + kLanesRows * ne);                      // [rows][ne]
-  double (*LK)[kLanesLayK] = (double (*)[kLanesLayK])(s_kk + kLanesRows * ne + lanes_at_doubles(ne));     // [ne] the layers' records
-  double *s_E0 = s_kk + kLanesRows * ne + lanes_at_doubles(ne) + kLanesLayK * ne;            // [kLanesBases][ne] exp(ct * base point)
-  int *s_cellr = (int *)(s_E0 + kLanesBases * ne);                            // [BL] cell of the batch's group of rank r
+  const int nc = A.nc, ns = lanes_stride(nc);                // (ns: the tables' row stride, odd)
+  double *s_kk = s_dyn + (size_t)wv * lanes_wave_doubles(nc);                // [rows][ns]
+  uint32_t *s_at = (uint32_t *)(s_kk + kLanesRows * ns);                      // [rows][ns]
+  double (*LK)[kLanesLayK] = (double (*)[kLanesLayK])(s_kk + kLanesRows * ns + lanes_at_doubles(ns));     // [nc] the layers' records
+  double *s_E0 = s_kk + kLanesRows * ns + lanes_at_doubles(ns) + kLanesLayK * nc;            // [kLanesBases][ns] exp(ct * base point)
+  int *s_cellr = (int *)(s_E0 + kLanesBases * ns);                            // [BL] cell of the batch's group of rank r
 
   // ---- the wave's range (wave-uniform: scalar loads)
   const int nlaunch = A.nseg > 0 ? A.seg_cum[A.nseg] : A.P.nwaves;
@@ -111,9 +132,8 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   if (threadIdx.x < 64) s_e2[threadIdx.x] = e2_mine;
   // the layers' scalars of the range's isotope block (lane c = layer c): in flight under the closed-ray test
   struct LayerScalars { double ad, ct, f, dens, kmax, wcut; int il, idst, idop0; } pre{};
-  if (have && lane < ne) {
-    const int cl = min(lane, nc - 1);                        // (the odd layer out: a copy of the last one, its results are never read)
-    const int r = A.r_top - cl, ri = r * A.niso + r_b;
+  if (have && lane < nc) {
+    const int r = A.r_top - lane, ri = r * A.niso + r_b;
     pre.ad = A.Y.alphad[ri]; pre.il = A.Y.ilor[ri]; pre.idst = A.sticky_idop[ri];
     pre.ct = A.Y.negc_over_t[r]; pre.f = A.Y.strength_f[ri]; pre.dens = A.permol ? 1.0 : A.Y.density[ri];
     pre.kmax = A.kmax[(long long)r * A.nmx + (A.nmx == 1 ? 0 : A.iso_mx[r_b])]; pre.wcut = A.wcut[ri]; pre.idop0 = A.Y.idop0[ri];
@@ -128,12 +148,12 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   if (!open) return;
 
   // ---- phase 2's lane: layer li, part of the frame (slots part*NS ...)
-  const int li = lane >> 1, part = lane & 1;
+  const int li = lane / P, part = lane - li * P;
   const bool valid = li < nc;
   const int lic = valid ? li : 0;
   const bool r32 = NB == 8 && A.tabw32 != nullptr;           // compact 32-byte rows (frames of 8 bins): offset = profile's + phase * slab, no borrow term
   const char *tabw_base = r32 ? (const char *)A.tabw32 : (const char *)A.tabw - 4 * (Rc + 1);     // (wave-uniform; a lane adds its part's 4 * NS * part)
-  const unsigned part_off = 4u * NS * (unsigned)part;
+  const unsigned part_off = 4u * NS * (unsigned)part;       // (4-byte aligned: a part of 3 bins reads 12 bytes)
   const double *s_kk_lane = s_kk + lic; const uint32_t *s_at_lane = s_at + lic;
   double acc[NS];
 #pragma unroll
@@ -151,16 +171,16 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
     int sh = jc - cell;
     if (sh >= NB) {
 #pragma unroll
-      for (int k = 0; k < NS; k++) { flush(k, acc[k], true); acc[k] = 0.0; }
+      for (int k = 0; k < NS; k++) { flush(k, acc[k], k < NL || part != P - 1); acc[k] = 0.0; }
       fill_zero(cell + Rc + 2, jc - Rc - 1);
       jc = cell;
     } else {
       for (; sh > 0; sh--) {
-        flush(NS - 1, acc[NS - 1], part == LPL - 1);
-        const double carry = dpp_f64<0xB1>(acc[NS - 1]);          // quad_perm [1,0,3,2]: the pair's other lane
+        flush(NL - 1, acc[NL - 1], part == P - 1);           // (the frame's top bin: the last part's slot NL - 1)
+        const double carry = carry_up<P>(acc[NS - 1]);
 #pragma unroll
         for (int k = NS - 1; k > 0; k--) acc[k] = acc[k - 1];
-        acc[0] = part == 1 ? carry : 0.0;
+        acc[0] = part != 0 ? carry : 0.0;
         jc--;
       }
     }
@@ -169,7 +189,7 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   // two blocks of up to D groups of one cell: one is being fetched while the other is added.  A set is consumed exactly
   // once per produce (and once, all zeros, before the first one): nothing below tests whether its loads have landed
   // except the multiply-adds that use them
-  struct alignas(16) Row { float v[NS]; };
+  struct alignas(NS % 4 == 0 ? 16 : NS % 2 == 0 ? 8 : 4) Row { float v[NS]; };     // (16-, 8- or 12-byte loads)
   double bk_kk[2][D]; Row bk_row[2][D];
   int bn[2] = {0, 0}, bcell[2] = {0, 0};                     // per set: groups in it, their cell
 #pragma unroll
@@ -190,13 +210,13 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   };
 
   // (rows BL, BL + 1 of the two tables: the weight 0 and the offset 0 -- what a block's empty places read; what a group's members write)
-  if (lane < ne) { s_kk[BL * ne + lane] = 0.0; s_at[BL * ne + lane] = 0u; s_at[(BL + 1) * ne + lane] = 0u; }
+  if (lane < nc) { s_kk[BL * ns + lane] = 0.0; s_at[BL * ns + lane] = 0u; s_at[(BL + 1) * ns + lane] = 0u; }
 
   // ---- the layers' records (lane c = layer c of the step): constants of (layer, isotope), the Doppler
   // index at the range's first line and its profile.  Doubles 0 ct, 1 f, 2 density, 3 threshold, 4 wcut,
   // 5 alphad, 6 lower end of the current Doppler index' interval; words from double 7: index, ilor;
   // from 8: {centre + 4, row bytes, ps % osamp, -} of the current profile; from 10: of the sticky one
-  if (lane < ne) {
+  if (lane < nc) {
     double *K = LK[lane];
     K[0] = pre.ct; K[1] = pre.f; K[2] = pre.dens;
     K[3] = A.ethresh * pre.kmax; K[4] = pre.wcut; K[5] = pre.ad;
@@ -231,8 +251,8 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   bn[1] = 0; bcell[1] = cell0;
 #pragma unroll
   for (int u = 0; u < D; u++) {
-    bk_kk[1][u] = s_kk_lane[BL * ne];
-    __builtin_memcpy(&bk_row[1][u], tabw_base + (s_at_lane[BL * ne] + part_off + 32u * u), sizeof(Row));     // (D loads, not one and its copies: any bytes of the table will do under a weight of 0)
+    bk_kk[1][u] = s_kk_lane[BL * ns];
+    __builtin_memcpy(&bk_row[1][u], tabw_base + (s_at_lane[BL * ns] + part_off + 32u * u), 4 * NS);     // (D loads, not one and its copies: any bytes of the table will do under a weight of 0)
   }
 
   for (int l = l0; l < l1; ) {
@@ -240,6 +260,8 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
     // lines x 2 sets of layers, or -- the last lines of the range -- 16 x 4 or 8 x 8: an iteration of the
     // layer loop then serves 4 or 8 layers of the few lines that are left
     int lg; geometry(l, lg);
+    int ncb = nc;                                             // (recomputed per batch, not held: `lane < nc` kept across the loop was
+    asm volatile("" : "+s"(ncb));                             // the one SGPR pair over the budget at three lanes per layer)
     const int BLx = 1 << lg, nsets = 64 >> lg;
     const int t1 = lane & (BLx - 1), h1 = lane >> lg;
     const int n0 = min(BLx, l1 - l);
@@ -261,7 +283,7 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
     for (unsigned m = (unsigned)__ballot(is_anchor && t1 > 0 && prev_cell != v_cell) & lowm; m; m &= m - 1u)
       bstart_r |= 1u << __builtin_popcount(amask & ((1u << __builtin_ctz(m)) - 1u));
     if (is_anchor && h1 == 0) s_cellr[rank] = v_cell;
-    const int rowk = (is_anchor ? rank : BL + 1) * ne;        // where this lane's (group, layer) entries go
+    const int rowk = (is_anchor ? rank : BL + 1) * ns;        // where this lane's (group, layer) entries go
     int len = 1;
     { const unsigned e = ends >> t1; if (is_anchor && e) len = __builtin_ctz(e) + 1; }
     int kmax_len = 1;
@@ -278,24 +300,25 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
       unsigned lm = leaders; int j = 0;
       if (e0_prev >= 0 && !(__builtin_amdgcn_readfirstlane(meta) & 4)) {
         // the batch's first line goes on from the base point the batch before ended on: its row of the table is that one
-        if (e0_prev != 0 && lane < ne) s_E0[lane] = s_E0[e0_prev * ne + lane];
+        if (e0_prev != 0 && lane < ncb) s_E0[lane] = s_E0[e0_prev * ns + lane];
         lm &= lm - 1u; j = 1;
       }
       for (; j < nlead; j++) {
         const int tl = __builtin_ctz(lm); lm &= lm - 1u;
         const double wbj = readlane_f64(wb, tl);
-        if (lane < ne) s_E0[j * ne + lane] = exp_neg(LK[lane][0] * wbj, s_e2);
+        if (lane < ncb) s_E0[j * ns + lane] = exp_neg(LK[lane][0] * wbj, s_e2);
       }
       e0_prev = nlead - 1;
     } else e0_prev = -1;
     // does some layer's Doppler index step inside this batch?  (lines descend: the last line decides)
     bool step = false;
-    { const double wl = readlane_f64(wavn, n - 1); if (lane < ne) step = LK[lane][5] * wl < LK[lane][6]; }
+    { const double wl = readlane_f64(wavn, n - 1); if (lane < ncb) step = LK[lane][5] * wl < LK[lane][6]; }
     const bool slow = __any(step);
     __builtin_amdgcn_wave_barrier();
     auto layer = [&](int c2, auto E0TAB, auto SLOW, auto CLAMP) {
-      // (two sets of layers -- a full batch -- never pass the last layer, ne is even; four or eight sets do: they repeat it, the same values to the same places)
-      const int c = decltype(CLAMP)::value ? min(c2 + h1, ne - 1) : c2 + h1;
+      // (two sets of layers -- a full batch -- pass the last layer only where nc is odd; four or eight sets do: they repeat
+      // it, the same values to the same places)
+      const int c = decltype(CLAMP)::value ? min(c2 + h1, nc - 1) : c2 + h1;
       double *K = LK[c];
       struct alignas(16) D2 { double a, b; }; struct alignas(16) I4 { int x, y, z, w; };
       const D2 k01 = *(const D2 *)(K + 0), k23 = *(const D2 *)(K + 2);
@@ -305,7 +328,7 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
       const double e1 = exp_neg(ct * elow, s_e2, c24);
       const double t0 = ct * wb;
       double E0;
-      if constexpr (decltype(E0TAB)::value) E0 = s_E0[bid * ne + c]; else E0 = exp_neg(t0, s_e2, c24);
+      if constexpr (decltype(E0TAB)::value) E0 = s_E0[bid * ns + c]; else E0 = exp_neg(t0, s_e2, c24);
       const double q = __builtin_fma(-E0, exp_small(__builtin_fma(ct, wavn, -t0), c24), 1.0);
       const double s = gf * e1 * q;
       // ---- the group's sum on its anchor's lane, members in line order (extinction.c:449-462).  The second member
@@ -331,7 +354,7 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
         if (idx != cur_i) { const WalkProfile wp = A.walkprof[idx * A.nlor + KI[1]]; pc.x = r32 ? (int)A.wp32[idx * A.nlor + KI[1]] : (int)wp.centre4 + 4; pc.y = wp.rowb; pc.z = wp.psr; }
         const int ncur = __shfl(idx, (n - 1) + (h1 << lg), 64);
         __builtin_amdgcn_wave_barrier();
-        if (t1 == 0 && c2 + h1 < ne && ncur != cur_i) {      // the next batch starts from the last line's index
+        if (t1 == 0 && c2 + h1 < nc && ncur != cur_i) {      // the next batch starts from the last line's index
           const WalkProfile wp = A.walkprof[ncur * A.nlor + KI[1]];
           K[6] = s_thr[ncur]; KI[0] = ncur; KI[2] = r32 ? (int)A.wp32[ncur * A.nlor + KI[1]] : (int)wp.centre4 + 4; KI[3] = wp.rowb; KI[4] = wp.psr;
         }
@@ -347,10 +370,10 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
       s_kk[rowk + c] = kk; s_at[rowk + c] = at;
     };
     using T = std::true_type; using F = std::false_type;
-    if (slow)             for (int c2 = 0; c2 < ne; c2 += nsets) layer(c2, F{}, T{}, T{});
-    else if (!e0_tab)     for (int c2 = 0; c2 < ne; c2 += nsets) layer(c2, F{}, F{}, T{});
-    else if (nsets != 2)  for (int c2 = 0; c2 < ne; c2 += nsets) layer(c2, T{}, F{}, T{});
-    else                  for (int c2 = 0; c2 < ne; c2 += 2)     layer(c2, T{}, F{}, F{});
+    if (slow)                       for (int c2 = 0; c2 < nc; c2 += nsets) layer(c2, F{}, T{}, T{});
+    else if (!e0_tab)               for (int c2 = 0; c2 < nc; c2 += nsets) layer(c2, F{}, F{}, T{});
+    else if (nsets != 2 || (nc & 1)) for (int c2 = 0; c2 < nc; c2 += nsets) layer(c2, T{}, F{}, T{});
+    else                            for (int c2 = 0; c2 < nc; c2 += 2)     layer(c2, T{}, F{}, F{});
     __builtin_amdgcn_wave_barrier();
 
     // ---- the next batch's lines: requested here, they arrive under phase 2
@@ -376,9 +399,9 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
       bcell[s] = __builtin_amdgcn_readlane(c_rank, min(j, BL - 1)); bn[s] = cnt;
 #pragma unroll
       for (int u = 0; u < D; u++) {
-        const int row = (u < cnt ? j + u : BL) * ne;          // (an empty place: weight 0, offset 0)
+        const int row = (u < cnt ? j + u : BL) * ns;          // (an empty place: weight 0, offset 0)
         bk_kk[s][u] = s_kk_lane[row];
-        __builtin_memcpy(&bk_row[s][u], tabw_base + (s_at_lane[row] + part_off), sizeof(Row));
+        __builtin_memcpy(&bk_row[s][u], tabw_base + (s_at_lane[row] + part_off), 4 * NS);
       }
       j += cnt;
     };
@@ -395,7 +418,7 @@ void k_line_walk_lanes(WalkArgs A, LanesExtra X)
   // the block still in flight, then the range's last bins
   consume(std::integral_constant<int, 1>{});
 #pragma unroll
-  for (int k = 0; k < NS; k++) flush(k, acc[k], true);
+  for (int k = 0; k < NS; k++) flush(k, acc[k], k < NL || part != P - 1);
   fill_zero(blo, jc - Rc - 1);
 }
 
