@@ -276,6 +276,43 @@ int  trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const 
 int  trx_batch_ways(const trx_batch *b);
 void trx_batch_destroy(trx_batch *b);
 
+/* Band integrals on the device: the spectrum reduced to an instrument's channels (filter curves, top-hat
+ * bins, a Gaussian line-spread function at pixel centres) without handing the whole spectrum back.
+ *
+ * A band is a weight w_i per coarse bin i of the whole grid (i = 0 .. nwn-1, nu_i = wn_i + i*wn_d):
+ *   TRX_BAND_WEIGHTS  bins first .. first+n-1, w_{first+k} = weights[k] (finite; copied at trx_set_bands)
+ *   TRX_BAND_GAUSS    sigma = fwhm / (2 sqrt(2 ln 2)); bins i_lo = ceil((centre - cut*sigma - wn_i)/wn_d) to
+ *                     i_hi = floor((centre + cut*sigma - wn_i)/wn_d), clipped to [0, nwn) (computed on the host in
+ *                     double; an empty range is allowed); w_i = exp(-((nu_i - centre)/sigma)^2 / 2), evaluated on
+ *                     the device
+ * A run gives sums[b][0] = sum of w_i S_i and sums[b][1] = sum of w_i over the band's bins in this handle's shard
+ * [wn_lo, wn_hi); the band's value is sums[b][0] / sums[b][1].  A sharded job adds the ranks' sums in rank order
+ * (e.g. trx_gather_host of the [nbands][2] partials); a band with no bin in the shard gives exactly (0, 0).
+ * The sums have no atomics: the bits of a band's pair depend on the spectrum, the band and the shard only -- not on
+ * the other bands of the set, the launch, the batch way that ran it or the handle's depth hint.
+ *
+ * trx_set_bands copies the set to the device (nbands = 0: clear it).  It returns TRX_E_ARG, naming the band in
+ * trx_last_error, for nbands < 0, an unknown kind, n < 1, first < 0, first + n > nwn, a NULL or non-finite weight,
+ * a non-finite centre, fwhm or cut, fwhm <= 0 or cut <= 0; a refused set leaves the previous one in force.
+ * trx_run_bands is trx_run plus the band sums: spectrum may be NULL (then the spectrum stays on the device), and
+ * when it is given it holds the bits trx_run gives.  It returns TRX_E_ARG with no set installed or sums NULL.
+ * trx_batch_set_bands installs the same set on every handle of the batch, or on none (its reason through
+ * trx_last_error(NULL)); trx_run_batch_bands is trx_run_batch with sums[j] ([nbands][2]) for spectra[j]. */
+typedef enum { TRX_BAND_WEIGHTS = 0, TRX_BAND_GAUSS = 1 } trx_band_kind;
+typedef struct {
+  int32_t kind, pad;        /* trx_band_kind; pad is ignored                                       */
+  int64_t first, n;         /* WEIGHTS: global coarse bins first .. first+n-1 of the whole grid     */
+  const double *weights;    /* WEIGHTS: [n], finite                                                 */
+  double centre, fwhm, cut; /* GAUSS: cm-1, cm-1 (> 0), half-width in sigmas (> 0)                  */
+} trx_band;
+int  trx_set_bands(trx_handle *h, int32_t nbands, const trx_band *bands);
+int  trx_run_bands(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                   double *spectrum /* [wn_hi-wn_lo], host; may be NULL */, double *sums /* [nbands][2] */,
+                   trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_bands(trx_batch *b, int32_t nbands, const trx_band *bands);
+int  trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                         double *const *sums /* [k] -> [nbands][2] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

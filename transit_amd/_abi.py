@@ -75,6 +75,14 @@ class TrxDebug(C.Structure):
                 ("er", c_double_p), ("e_scat", c_double_p), ("e_cloud", c_double_p)]
 
 
+BAND_WEIGHTS, BAND_GAUSS = 0, 1
+
+
+class TrxBand(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("first", C.c_int64), ("n", C.c_int64),
+                ("weights", c_double_p), ("centre", C.c_double), ("fwhm", C.c_double), ("cut", C.c_double)]
+
+
 class TrxStats(C.Structure):
     _fields_ = [
         ("nlines_inrange", C.c_int64), ("ngroups", C.c_int64), ("nadd", C.c_int64),
@@ -117,4 +125,19 @@ def bind_engine_api(lib, prefix: str = "trx_"):
     f("sweep_permol").argtypes = [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, C.c_double,
                                   C.c_int32, c_int32_p, c_double_p]
     f("sweep_permol").restype = C.c_int
+    return lib
+
+
+def bind_bands_api(lib):
+    """argtypes/restypes of the band entry points (trx_set_bands, trx_run_bands and their batch forms)."""
+    lib.trx_set_bands.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxBand)]
+    lib.trx_set_bands.restype = C.c_int
+    lib.trx_run_bands.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, c_double_p,
+                                  C.POINTER(TrxDebug)]
+    lib.trx_run_bands.restype = C.c_int
+    lib.trx_batch_set_bands.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxBand)]
+    lib.trx_batch_set_bands.restype = C.c_int
+    lib.trx_run_batch_bands.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
+                                        C.POINTER(c_double_p)]
+    lib.trx_run_batch_bands.restype = C.c_int
     return lib

@@ -36,6 +36,7 @@
 #include "trx_rows.hip.h"
 #include "trx_tail.hip.h"
 #include "trx_lanes.hip.h"
+#include "trx_bands.hip.h"
 #include "../trx_groups.h"
 
 using namespace trx;
@@ -53,6 +54,14 @@ struct DevBuf {
 struct DevView {
   void *p = nullptr;
   template <class T> T *as() const { return (T *)p; }
+};
+
+// a band set installed by trx_set_bands (trx_bands.hip.h), as this handle's shard sees it
+struct BandSet {
+  int32_t nbands = 0; int64_t npieces = 0;
+  DevBuf d_bands, d_pieces, d_w, d_part;             // BandDev[nbands], BandPiece[npieces], WEIGHTS' in-shard weights, [npieces][2]
+  void *h_out = nullptr, *h_out_dev = nullptr;       // pinned [nbands][2]: k_band_sums stores the run's sums here
+  ~BandSet() { if (h_out) (void)hipHostFree(h_out); }
 };
 
 }  // namespace
@@ -156,6 +165,7 @@ struct trx_handle {
   void *h_spec = nullptr; size_t h_spec_bytes = 0;     // pinned staging of the spectrum (trx_run hands over pageable memory)
   void *h_spec_dev = nullptr, *h_small_dev = nullptr;  // the device's addresses of the pinned blocks (asked for once per allocation, not per run)
   void *h_tailblk = nullptr, *h_tailblk_dev = nullptr; size_t h_tailblk_bytes = 0;   // pinned: what each block of k_ray_tail adds to the run's flags (vertical rays: the host adds them up)
+  std::unique_ptr<BandSet> bands;                      // trx_set_bands (null: none)
 };
 
 namespace {
@@ -2064,7 +2074,10 @@ static int run_finish(trx_handle *h, const trx_atm *a, const trx_opts *o, trx_de
   return TRX_OK;
 }
 
-static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg)
+// bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
+// spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
+static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg,
+                    const BandSet *bs = nullptr)
 {
   if (!h || !a || !o) return TRX_E_ARG;
   const auto t_host0 = std::chrono::steady_clock::now();
@@ -2517,7 +2530,7 @@ static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
     tail_mode = ok && steps >= 1;
   }
   // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  const bool tail_direct = tail_mode && h->tail_direct, tail_spec = tail_direct && spectrum && !d_spectrum;
+  const bool tail_direct = tail_mode && h->tail_direct, tail_spec = tail_direct && spectrum && !d_spectrum && !bs;
   // (any run that hands its spectrum to pageable host memory stages it in the handle's pinned buffer when it is small:
   // the copy command into pageable memory is staged by the runtime anyway, 25 us behind the copy of the flags at configs[2])
   const bool stage_spec = spectrum && !d_spectrum && nsh <= (1 << 20);
@@ -2718,6 +2731,19 @@ static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
     else
       hipLaunchKernelGGL(k_modulation, dim3((unsigned)((nsh + kModWaves - 1) / kModWaves)), dim3(64 * kModWaves), 0, st, M);
   }
+  // ---- band integrals of this pass's spectrum (trx_bands.hip.h), behind it on its queue.  A pass that resumes
+  // deeper queues them again behind its own spectrum: the sums the host reads are the last pass's.
+  if (bs && bs->nbands > 0) {
+    BandArgs BA{};
+    BA.spec = d_out; BA.bands = bs->d_bands.as<BandDev>(); BA.pieces = bs->d_pieces.as<BandPiece>();
+    BA.w = bs->d_w.as<double>(); BA.part = bs->d_part.as<double>(); BA.out = (double *)bs->h_out_dev;
+    BA.npieces = bs->npieces; BA.lo = h->lo; BA.nbands = bs->nbands; BA.wn_i = h->wn_i; BA.wn_d = h->wn_d;
+    if (!BA.spec || !BA.bands || !BA.part || !BA.out || (bs->npieces > 0 && !BA.pieces))
+      return fail(h, TRX_E_HIP, "internal: incomplete arguments for the band kernels (not launched)");
+    if (bs->npieces > 0)
+      hipLaunchKernelGGL(k_band_pieces, dim3((unsigned)((bs->npieces + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
+    hipLaunchKernelGGL(k_band_sums, dim3((unsigned)((bs->nbands + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
+  }
   HIPCHK(h, hipGetLastError());
   if (prof) HIPCHK(h, hipEventRecord(ev.b, tst));
 
@@ -2725,7 +2751,8 @@ static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   {   // one copy into pinned memory: flags, status and (profiled runs) the counters
     const size_t nb = count ? 128 + 24 * (size_t)nr : 128;
     if (!(tail_direct && !resumed)) HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small.p, nb, hipMemcpyDeviceToHost, st));
-    if (spectrum && !(tail_spec && !resumed)) HIPCHK(h, hipMemcpyAsync(stage_spec ? h->h_spec : (void *)spectrum, d_out, sizeof(double) * nsh, hipMemcpyDeviceToHost, st));
+    // (on the spectrum's queue: a band run's tail may have run on the side queue)
+    if (spectrum && !(tail_spec && !resumed)) HIPCHK(h, hipMemcpyAsync(stage_spec ? h->h_spec : (void *)spectrum, d_out, sizeof(double) * nsh, hipMemcpyDeviceToHost, tst));
     lap("spectrum+copies");
   }
   t_host_queued = std::chrono::steady_clock::now();
@@ -2837,6 +2864,93 @@ int trx_run_device(trx_handle *h, const trx_atm *a, const trx_opts *o, void *d_s
   return run_once(h, a, o, nullptr, d_spectrum, dbg);
 }
 
+// ---- band integrals (trx_bands.hip.h) -------------------------------------------------------------
+// The set as h's shard sees it, checked whole before anything is replaced: ranges on the host in double
+// (the header's rule), each band's in-shard bins cut into pieces of kBandPiece from its first in-shard bin.
+static int make_band_set(trx_handle *h, int32_t nbands, const trx_band *bands, std::unique_ptr<BandSet> &out)
+{
+  out.reset();
+  if (nbands < 0) return fail(h, TRX_E_ARG, "bands: nbands < 0");
+  if (nbands > 0 && !bands) return fail(h, TRX_E_ARG, "bands: NULL band array");
+  const int64_t nwn = h->nwn, lo = h->lo, hi = h->hi;
+  std::vector<BandDev> bd((size_t)nbands);
+  std::vector<BandPiece> pieces;
+  std::vector<double> w;
+  const double fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
+  for (int32_t b = 0; b < nbands; b++) {
+    const trx_band &B = bands[b];
+    const std::string name = "band " + std::to_string(b) + ": ";
+    BandDev &D = bd[(size_t)b];
+    D.kind = B.kind;
+    int64_t first = 0, last = 0;                         // [first, last) of the whole grid
+    if (B.kind == TRX_BAND_WEIGHTS) {
+      if (B.n < 1) return fail(h, TRX_E_ARG, name + "n < 1");
+      if (B.first < 0) return fail(h, TRX_E_ARG, name + "first < 0");
+      if (B.first > nwn - B.n) return fail(h, TRX_E_ARG, name + "first + n > nwn");
+      if (!B.weights) return fail(h, TRX_E_ARG, name + "NULL weights");
+      for (int64_t k = 0; k < B.n; k++)
+        if (!std::isfinite(B.weights[k])) return fail(h, TRX_E_ARG, name + "weight " + std::to_string(k) + " is not finite");
+      first = B.first; last = B.first + B.n;
+    } else if (B.kind == TRX_BAND_GAUSS) {
+      if (!std::isfinite(B.centre) || !std::isfinite(B.fwhm) || !std::isfinite(B.cut))
+        return fail(h, TRX_E_ARG, name + "centre, fwhm and cut must be finite");
+      if (!(B.fwhm > 0)) return fail(h, TRX_E_ARG, name + "fwhm <= 0");
+      if (!(B.cut > 0)) return fail(h, TRX_E_ARG, name + "cut <= 0");
+      D.centre = B.centre; D.sigma = B.fwhm / fwhm_sigma;
+      const double a = std::ceil((B.centre - B.cut * D.sigma - h->wn_i) / h->wn_d);
+      const double z = std::floor((B.centre + B.cut * D.sigma - h->wn_i) / h->wn_d) + 1.0;
+      // (clipped to [0, nwn] in double: no conversion of a value out of int64's range)
+      first = a <= 0 ? 0 : a >= (double)nwn ? nwn : (int64_t)a;
+      last = z <= 0 ? 0 : z >= (double)nwn ? nwn : (int64_t)z;
+      last = std::max(first, last);
+    } else return fail(h, TRX_E_ARG, name + "unknown kind " + std::to_string(B.kind));
+    const int64_t s = std::max(first, lo), e = std::min(last, hi);
+    D.s = s - lo; D.piece0 = (int64_t)pieces.size(); D.npieces = 0; D.woff = (int64_t)w.size();
+    if (e <= s) { D.s = 0; continue; }                   // no bin in this shard: (0, 0)
+    if (B.kind == TRX_BAND_WEIGHTS) w.insert(w.end(), B.weights + (s - first), B.weights + (e - first));
+    for (int64_t q = s; q < e; q += kBandPiece) {
+      BandPiece P{};
+      P.start = q - lo; P.band = b; P.len = (int32_t)std::min<int64_t>(kBandPiece, e - q);
+      pieces.push_back(P);
+    }
+    D.npieces = (int64_t)pieces.size() - D.piece0;
+  }
+  if (nbands == 0) return TRX_OK;                       // (clear)
+  std::unique_ptr<BandSet> S(new (std::nothrow) BandSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "bands: out of host memory");
+  S->nbands = nbands; S->npieces = (int64_t)pieces.size();
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload_raw(h, S->d_bands, bd.data(), bd.size())) || (rc = upload_raw(h, S->d_pieces, pieces.data(), pieces.size())) ||
+      (rc = upload_raw(h, S->d_w, w.data(), w.size())) || (rc = ensure(h, S->d_part, sizeof(double) * 2 * (size_t)S->npieces)))
+    return rc;
+  HIPCHK(h, hipHostMalloc(&S->h_out, sizeof(double) * 2 * (size_t)nbands, hipHostMallocDefault));
+  HIPCHK(h, hipHostGetDevicePointer(&S->h_out_dev, S->h_out, 0));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
+  out = std::move(S);
+  return TRX_OK;
+}
+
+int trx_set_bands(trx_handle *h, int32_t nbands, const trx_band *bands)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<BandSet> S;
+  const int rc = make_band_set(h, nbands, bands, S);
+  if (rc) return rc;
+  h->bands = std::move(S);
+  return TRX_OK;
+}
+
+int trx_run_bands(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, double *sums, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  if (!h->bands) return fail(h, TRX_E_ARG, "trx_run_bands: no band set installed (trx_set_bands)");
+  if (!sums) return fail(h, TRX_E_ARG, "trx_run_bands: sums is NULL");
+  const int rc = run_once(h, a, o, spectrum, nullptr, dbg, h->bands.get());
+  if (rc == TRX_OK) std::memcpy(sums, h->bands->h_out, sizeof(double) * 2 * (size_t)h->bands->nbands);
+  return rc;
+}
+
 // ---- several atmospheres per call -----------------------------------------------------------------
 // A retrieval driver runs many chains over one line list (the reference: one run_transit per atmosphere,
 // transit.c:118-122, one process each).  One spectrum leaves the device idle between its kernels and while
@@ -2852,6 +2966,7 @@ struct trx_batch {
   // the call being served (under mu)
   uint64_t epoch = 0; bool quit = false;
   int32_t k = 0; const trx_atm *atm = nullptr; const trx_opts *opts = nullptr; double *const *spectra = nullptr;
+  double *const *sums = nullptr;                     // trx_run_batch_bands: the band sums instead of the spectra
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -2895,7 +3010,8 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
         for (;;) {
           const int32_t j = b->next.fetch_add(1);
           if (j >= b->k) break;
-          const int rc = trx_run(b->hs[(size_t)i], b->atm + j, b->opts, b->spectra[j], nullptr);
+          const int rc = b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
+                                 : trx_run(b->hs[(size_t)i], b->atm + j, b->opts, b->spectra[j], nullptr);
           if (rc != TRX_OK) {
             std::lock_guard<std::mutex> lk(b->mu);
             if (b->rc == TRX_OK) { b->rc = rc; b->err = "atmosphere " + std::to_string(j) + ": " + b->hs[(size_t)i]->err; }
@@ -2912,14 +3028,12 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
   return TRX_OK;
 }
 
-int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra)
+// one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
+static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums)
 {
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !spectra))) return TRX_E_ARG;
-  for (int32_t j = 0; j < k; j++) if (!spectra[j]) return TRX_E_ARG;
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
-  b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra;
+  b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -2927,6 +3041,37 @@ int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *o
   b->cv_done.wait(lk, [&] { return b->busy == 0; });
   if (b->rc != TRX_OK) g_comm_err = b->err;                // trx_last_error(NULL)
   return b->rc;
+}
+
+int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !spectra))) return TRX_E_ARG;
+  for (int32_t j = 0; j < k; j++) if (!spectra[j]) return TRX_E_ARG;
+  return batch_call(b, k, atm, opts, spectra, nullptr);
+}
+
+// every handle of the batch gets the same set, or none does: all sets are built before any is installed
+int trx_batch_set_bands(trx_batch *b, int32_t nbands, const trx_band *bands)
+{
+  g_comm_err.clear();
+  if (!b) return TRX_E_ARG;
+  std::vector<std::unique_ptr<BandSet>> sets(b->hs.size());
+  for (size_t i = 0; i < b->hs.size(); i++) {
+    const int rc = make_band_set(b->hs[i], nbands, bands, sets[i]);
+    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
+  }
+  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->bands = std::move(sets[i]);
+  return TRX_OK;
+}
+
+int trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *sums)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums))) { g_comm_err = "trx_run_batch_bands: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_bands: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) if (!sums[j]) { g_comm_err = "trx_run_batch_bands: sums[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  return batch_call(b, k, atm, opts, nullptr, sums);
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

@@ -14,6 +14,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _abi
+from . import bands as _bands
 from .build import lib_path
 
 
@@ -198,6 +199,7 @@ def hip_library():
         lib.trx_run_device.argtypes = [C.c_void_p, C.POINTER(_abi.TrxAtm), C.POINTER(_abi.TrxOpts),
                                        C.c_void_p, C.POINTER(_abi.TrxDebug)]
         lib.trx_run_device.restype = C.c_int
+        _abi.bind_bands_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -226,6 +228,26 @@ class Engine(CEngine):
         rc = self._lib.trx_run_device(self._h, C.byref(atm), C.byref(opts), C.c_void_p(d_spectrum_ptr), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_device", self._last_error())
+
+    def set_bands(self, bands):
+        """trx_set_bands: install a band set (a list of transit_amd.bands.Band; empty: clear it)."""
+        arr = _bands.to_c(bands)
+        rc = self._lib.trx_set_bands(self._h, len(bands), arr)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_bands", self._last_error())
+        self.nbands = len(bands)
+
+    def run_bands(self, atm, opts, spectrum: bool = False):
+        """trx_run_bands: the band sums [nbands, 2] of this shard -- and, with spectrum=True, (sums, spectrum),
+        the spectrum bit for bit what run() gives."""
+        sums = np.zeros((getattr(self, "nbands", 0), 2))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_bands(self._h, C.byref(atm), C.byref(opts),
+                                     spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                     sums.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_bands", self._last_error())
+        return (sums, spec) if spectrum else sums
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -268,6 +290,28 @@ class Batch:
         rc = self._lib.trx_run_batch(self._b, k, arr, C.byref(opts), ptrs)
         if rc != 0:
             raise EngineError(rc, "trx_run_batch", (self._lib.trx_last_error(None) or b"").decode(errors="replace"))
+        return out
+
+    def _err(self) -> str:
+        return (self._lib.trx_last_error(None) or b"").decode(errors="replace")
+
+    def set_bands(self, bands):
+        """trx_batch_set_bands: the same band set on every handle of the batch, or on none."""
+        arr = _bands.to_c(bands)
+        rc = self._lib.trx_batch_set_bands(self._b, len(bands), arr)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_bands", self._err())
+        self.nbands = len(bands)
+
+    def run_bands(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
+        """trx_run_batch_bands: [K, nbands, 2], each atmosphere's sums what Engine.run_bands gives, bit for bit."""
+        k = len(atms)
+        out = np.zeros((k, getattr(self, "nbands", 0), 2))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        ptrs = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_bands(self._b, k, arr, C.byref(opts), ptrs)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_bands", self._err())
         return out
 
     def close(self):
