@@ -34,9 +34,12 @@ def _split(rng, total, parts):
     return [int(v) for v in np.diff(np.concatenate([[0], cuts, [total]]))]
 
 
-def _linedbs(rng, nlines, lo, hi):
+def _linedbs(rng, nlines, lo, hi, empty_db=False):
+    """empty_db: the last of at least two databases has no line at all."""
     niso = int(rng.choice(ISOTOPES))
     ndb = min(int(rng.integers(1, 4)), niso)
+    if empty_db:
+        ndb = max(ndb, 2)
     per_db = _split(rng, niso, ndb)
     mols = list(rng.choice(MOLECULES, ndb, replace=False))
     # lines per isotope: a random share, a quarter of the isotopes (never all of a database) without any
@@ -46,6 +49,8 @@ def _linedbs(rng, nlines, lo, hi):
         if not w[k0:k0 + n].any():
             w[k0] = 1.0
         k0 += n
+    if empty_db:
+        w[niso - per_db[-1]:] = 0.0
     counts = rng.multinomial(nlines, w / w.sum())
     dbs, k0 = [], 0
     for j, (mol, n) in enumerate(zip(mols, per_db)):
@@ -96,7 +101,7 @@ def random_case(seed):
 
 def summary(kw):
     """The case in one line (assertion messages): everything but the line lists, which are told by size."""
-    d = {k: v for k, v in kw.items() if k != "dbs"}
+    d = {k: v for k, v in kw.items() if k not in ("dbs", "atm")}
     d["isotopes"] = [len(db.isotopes) for db in kw["dbs"]]
     d["lines"] = sum(len(w) for db in kw["dbs"] for w in db.wl)
     return d
@@ -127,3 +132,69 @@ def reference_binary(kw):
     uninitialised mean density, defined only in the build with zero-initialised locals (oracle/Makefile)."""
     cloud = kw.get("extra", {}).get("cloud", "")
     return "transit_zinit" if cloud and not cloud.startswith("ext") else "transit"
+
+
+# ---- opacity-grid problems (test_gpu_grid_random.py, test_random_grid_reference.py) ---------------------
+# The per-molecule sweep (trx_sweep_permol) walks nv = nlayer x ntemp states in steps of up to 64 walking or 12
+# two-kernel states, in the order v = layer * ntemp + temperature, from the last state down.  The short forms
+# run only on a short step: k_line_walk_packed for <= 10 states, k_line_walk_lanes for <= 32 with 8+-bin
+# frames on a dense list.  Each seed draws one class of state counts (GRID_NV_CLASSES); one state colder
+# than kWalkMinTemp (~387 K) sends the whole sweep to the two-kernel form.
+GRID_NV_CLASSES = ["around64", "mod64_1_10", "mod64_11_32", "around128", "mod64_11_32", "mod64_1_10", "around64", "over2000"]
+
+
+def _grid_shape(rng, cls):
+    """(nlayer, ntemp) with nlayer in 3..70 and ntemp in 2..30 whose product falls in the class."""
+    ok = {"around64": lambda nv: nv in (63, 64, 65), "around128": lambda nv: nv in (128, 129),
+          "mod64_1_10": lambda nv: nv > 64 and 1 <= nv % 64 <= 10,
+          "mod64_11_32": lambda nv: nv > 64 and 11 <= nv % 64 <= 32,
+          "over2000": lambda nv: nv >= 2000}[cls]
+    pairs = [(nl, nt) for nl in range(3, 71) for nt in range(2, 31) if ok(nl * nt)]
+    nl, nt = pairs[int(rng.integers(0, len(pairs)))]
+    return nl, nt
+
+
+def random_grid_case(seed):
+    """synth.make_case keywords of one opacity-grid problem (extra: opacityfile, tlow, thigh, tempdelt): the
+    grid spans 70..3000 K (the synthetic TLI's range), the atmosphere lies inside it.  One whole molecule slot
+    without lines in the band on every seed == 3 (mod 8)."""
+    rng = np.random.default_rng(5000 + seed)
+    cls = GRID_NV_CLASSES[seed % len(GRID_NV_CLASSES)]
+    nlayers, ntemp = _grid_shape(rng, cls)
+    # grid temperatures: integer nodes, so that tlow + k * tempdelt is exact and ends on thigh
+    cold = rng.random() < 0.25                       # a grid reaching below kWalkMinTemp: no state walks
+    lo_min = 70 if cold else 390
+    tempdelt = int(rng.integers(1, max(2, (3000 - lo_min) // (ntemp - 1)) + 1))
+    tlow = int(rng.integers(lo_min, 3000 - (ntemp - 1) * tempdelt + 1))
+    if cold:
+        tlow = int(rng.integers(70, 381))
+        tempdelt = min(tempdelt, (3000 - tlow) // (ntemp - 1))
+    thigh = tlow + (ntemp - 1) * tempdelt
+    # the atmosphere: inside [tlow, thigh), and inside the CIA tables where it has any (from 400 K, with
+    # the second table from 800 K: synth.make_case)
+    a_lo, a_hi = tlow + 0.05 * (thigh - tlow), thigh - 0.05 * (thigh - tlow)
+    ncia = int(rng.integers(0, 3))
+    cia_lo = [0.0, 400.0, 800.0][ncia]
+    if a_lo < cia_lo:
+        if a_hi > cia_lo + 20.0 and rng.random() < 0.5:
+            a_lo = cia_lo + 1.0
+        else:
+            ncia = 0
+    t_top, t_bottom = (float(v) for v in rng.uniform(a_lo, a_hi, 2))
+    atm = synth.demo_atmosphere(nlayers, p_bottom=float(rng.choice([100.0, 10.0])), t_bottom=t_bottom, t_top=t_top)
+    dense = rng.random() < 0.3                       # ngroups >= 8 nwn: k_line_walk_lanes runs unforced
+    wnlow = float(rng.choice([400.0, 2500.0, 4000.0, 9000.0]))
+    width = 2.0 if dense else float(rng.choice([2.0, 7.0, 20.0, 40.0]))
+    wndelt = float(rng.choice([1.0, 0.5])) if dense else float(rng.choice([1.0, 0.5, 0.1, 0.02]))
+    osamp = int(rng.choice([1, 2, 7, 60, 2160])) if wndelt >= 0.5 else int(rng.choice([1, 2, 5]))
+    nlines = 5000 if dense else int(rng.choice([17, 300, 2000, 5000]))
+    if cls == "over2000":                            # (the oracle sweeps every state: keep the band short)
+        width, wndelt = min(width, 7.0), max(wndelt, 0.1)
+        osamp = min(osamp, 60) if wndelt < 0.5 else osamp
+    line_margin = float(rng.choice([0.0, 1.5]))
+    ethresh = float(rng.choice([1e-50, 1e-8, 1e-5, 1e-3]))
+    dbs = _linedbs(rng, nlines, wnlow - line_margin, wnlow + width + line_margin, empty_db=seed % 8 == 3)
+    extra = {"opacityfile": "opac.dat", "tlow": tlow, "thigh": thigh, "tempdelt": tempdelt}
+    return dict(wnlow=wnlow, wnhigh=wnlow + width, wndelt=wndelt, wnosamp=osamp, nlayers=nlayers,
+                solution="eclipse" if rng.random() < 0.6 else "transit", toomuch=float(rng.choice([0.5, 10.0])),
+                ethresh=ethresh, ncia=ncia, line_margin=line_margin, atm=atm, dbs=dbs, extra=extra)

@@ -559,7 +559,7 @@ def test_stats_describe_the_last_run_not_a_per_molecule_sweep():
     eng = Engine(P.static)
     try:
         eng.run(P.atm, P.opts)
-        eng.run(P.atm, P.opts)                   # hinted: what the next hinted run repeats
+        hinted = eng.run(P.atm, P.opts)["spectrum"]          # hinted: what the next hinted run repeats
         first = eng.stats()
         assert first["walk_steps"] > 0
         iso_slot = np.zeros(P.static.niso, dtype=np.int32)        # (one line database: one molecule slot)
@@ -567,10 +567,11 @@ def test_stats_describe_the_last_run_not_a_per_molecule_sweep():
                              iso_slot.ctypes.data_as(_abi.c_int32_p))
         assert (o != 0).any()
         between = eng.stats()
-        eng.run(P.atm, P.opts)
+        after = eng.run(P.atm, P.opts)["spectrum"]
         second = eng.stats()
     finally:
         eng.close()
+    assert np.array_equal(after, hinted)          # (and the sweep leaves nothing behind that moves the next spectrum)
     for k in walk:
         assert between[k] == first[k], (k, first[k], between[k])
         assert second[k] == first[k], (k, first[k], second[k])

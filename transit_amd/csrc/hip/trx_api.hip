@@ -2841,9 +2841,14 @@ int trx_sweep_permol(trx_handle *h, int32_t nv, const double *temp, const double
     SweepMode M{};
     M.eager = true; M.ethresh = ethresh; M.nmx = nslot; M.d_iso_mx = h->d_iso_mx.as<int32_t>();
     M.permol = true; M.d_e = h->d_pm.as<double>(); M.d_kmax = h->d_kmax.as<double>(); M.d_sticky = h->d_sticky.as<int>();
-    if (nb) rc = walk_chunk(h, Y, d_wcut, nb, r_top, nc, M, nullptr, 0, nullptr, nullptr);
+    int form = -1;
+    if (nb) rc = walk_chunk(h, Y, d_wcut, nb, r_top, nc, M, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &form);
     else    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, r_top, nc, sg_layers, M, nullptr);
     if (rc) return rc;
+    // (trx_stats does not count sweeps: the step plan goes to the log, one line per step -- tests read it)
+    if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG)
+      log_msg(TRX_LOG_DEBUG, std::string("sweep step: form ") + (form == 1 ? "lanes" : form == 2 ? "packed" : form == 0 ? "walk" : "two-kernel") +
+                             ", states " + std::to_string(nc) + ", frame bins " + std::to_string(nb));
     r_top -= nc;
   }
   HIPCHK(h, hipGetLastError());
