@@ -313,6 +313,43 @@ int  trx_batch_set_bands(trx_batch *b, int32_t nbands, const trx_band *bands);
 int  trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
                          double *const *sums /* [k] -> [nbands][2] */);
 
+/* Contribution functions on the device: where in the atmosphere each band of the installed set comes from, one
+ * number per (band, layer), from the run's own optical depths -- the optical depths never leave the device.
+ *
+ * Heights are counted as the optical-depth arrays count them: i = 0 is the top layer, height i is atmosphere layer
+ * r = nlayer-1-i, `last` is the ray's last height (trx_debug.last).  Per wavenumber bin j:
+ *   eclipse geometry   t_a,i = exp(-tau_i / cos(angle_a)),  area_a = sin^2(grid_{a+1}) - sin^2(grid_a) (eclipse.c:262-276),
+ *                      B_i = the Planck function at layer nlayer-1-i (eclipse.c:154)
+ *                        g_i = pi * sum_a area_a * t_a,i                     i = 0 .. last
+ *                        d_i = g_i - g_{i+1}                                 i = 0 .. last-1
+ *                        W_0 = d_0 / 2,  W_i = (d_{i-1} + d_i) / 2 (0 < i < last),  W_last = d_{last-1} / 2 + g_last
+ *                        (last = 0: W_0 = g_0);  W_i = 0 for i > last
+ *                        F_i = B_i * W_i
+ *                      This is the reference's quadrature (eclipse_intens: B[last] dtau[last] - integ_trapz(dtau, B,
+ *                      last+1), then flux()) regrouped by node: sum_i F_i is the flux of bin j, every term is >= 0.
+ *   transit geometry   F_i = exp(-tau_i) for i <= last, 0 below (what modulation1 integrates, slantpath.c:374-386),
+ *                      whatever modlevel.
+ * contrib[b][r] = sum over the band's bins j in this handle's shard of w_j * F_{nlayer-1-r}(j), rows in the
+ * ATMOSPHERE's layer order (bottom first, like trx_atm), the weights w_j exactly those of the band sums.  Eclipse:
+ * sum_r contrib[b][r] = sums[b][0] up to summation rounding.  Transit: contrib[b][r] / sums[b][1] is the band-averaged
+ * transmittance at layer r's impact parameter.
+ *
+ * A sharded job adds the ranks' rows in rank order, like the band sums (e.g. trx_gather_host of the nbands*nlayer
+ * partials); a band with no bin in the shard gives a row of exact zeros.  No atomics: a row's bits depend on the
+ * optical depths, the band and the shard only -- not on the other bands of the set, the launch, the batch way, the
+ * handle's depth hint or the kernels that made the optical depths.
+ *
+ * trx_run_contrib is trx_run_bands plus contrib: spectrum (when asked for) and sums hold the bits trx_run_bands
+ * gives.  TRX_E_ARG (reason in trx_last_error) with no set installed, sums NULL or contrib NULL.  A run that fails
+ * leaves contrib undefined.  trx_run_batch_contrib is trx_run_batch_bands with contrib[j] ([nbands][atm[j].nlayer])
+ * next to sums[j]. */
+int  trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                     double *spectrum /* [wn_hi-wn_lo], host; may be NULL */, double *sums /* [nbands][2] */,
+                     double *contrib /* [nbands][a->nlayer] */, trx_debug *dbg /* may be NULL */);
+int  trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                           double *const *sums /* [k] -> [nbands][2] */,
+                           double *const *contrib /* [k] -> [nbands][atm[j].nlayer] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

@@ -141,3 +141,14 @@ def bind_bands_api(lib):
                                         C.POINTER(c_double_p)]
     lib.trx_run_batch_bands.restype = C.c_int
     return lib
+
+
+def bind_contrib_api(lib):
+    """argtypes/restypes of the contribution-function entry points (trx_run_contrib, trx_run_batch_contrib)."""
+    lib.trx_run_contrib.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, c_double_p,
+                                    c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_contrib.restype = C.c_int
+    lib.trx_run_batch_contrib.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
+                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_contrib.restype = C.c_int
+    return lib

@@ -37,6 +37,7 @@
 #include "trx_tail.hip.h"
 #include "trx_lanes.hip.h"
 #include "trx_bands.hip.h"
+#include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 
 using namespace trx;
@@ -166,6 +167,9 @@ struct trx_handle {
   void *h_spec_dev = nullptr, *h_small_dev = nullptr;  // the device's addresses of the pinned blocks (asked for once per allocation, not per run)
   void *h_tailblk = nullptr, *h_tailblk_dev = nullptr; size_t h_tailblk_bytes = 0;   // pinned: what each block of k_ray_tail adds to the run's flags (vertical rays: the host adds them up)
   std::unique_ptr<BandSet> bands;                      // trx_set_bands (null: none)
+  // trx_run_contrib (trx_contrib.hip.h): sub-piece rows [npieces * kContribSplit][nlayer] and the pinned result [nbands][nlayer], sized on
+  // first use and when the set or nlayer grows
+  DevBuf d_cpart; void *h_contrib = nullptr, *h_contrib_dev = nullptr; size_t h_contrib_bytes = 0;
 };
 
 namespace {
@@ -1873,6 +1877,7 @@ void trx_destroy(trx_handle *h)
   if (h->h_in) (void)hipHostFree(h->h_in);
   if (h->h_spec) (void)hipHostFree(h->h_spec);
   if (h->h_tailblk) (void)hipHostFree(h->h_tailblk);
+  if (h->h_contrib) (void)hipHostFree(h->h_contrib);
   delete h;
 }
 
@@ -2076,8 +2081,9 @@ static int run_finish(trx_handle *h, const trx_atm *a, const trx_opts *o, trx_de
 
 // bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
 // spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
+// contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
 static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg,
-                    const BandSet *bs = nullptr)
+                    const BandSet *bs = nullptr, bool contrib = false)
 {
   if (!h || !a || !o) return TRX_E_ARG;
   const auto t_host0 = std::chrono::steady_clock::now();
@@ -2743,6 +2749,28 @@ static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
     if (bs->npieces > 0)
       hipLaunchKernelGGL(k_band_pieces, dim3((unsigned)((bs->npieces + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
     hipLaunchKernelGGL(k_band_sums, dim3((unsigned)((bs->nbands + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
+    // ---- and the contribution functions of this pass's optical depths (trx_contrib.hip.h), behind them
+    if (contrib) {
+      ContribArgs CA{};
+      if (vertical) emis_args(CA.E);
+      else {                                             // (transit geometry: the grid, tau and last; no angles)
+        CA.E.nr = nr; CA.E.nang = 0; CA.E.nsh = nsh; CA.E.lo = h->lo; CA.E.wn_i = h->wn_i; CA.E.wn_d = h->wn_d; CA.E.wn_fct = o->wn_fct;
+        CA.E.tau = h->d_tau.as<double>(); CA.E.last = h->d_last.as<int>(); CA.E.temp = d_tempk; CA.E.e2tab = h->d_e2tab.as<double>();
+      }
+      CA.bands = BA.bands; CA.pieces = BA.pieces; CA.w = BA.w; CA.part = h->d_cpart.as<double>(); CA.out = (double *)h->h_contrib_dev;
+      CA.npieces = bs->npieces; CA.nbands = bs->nbands; CA.vertical = vertical ? 1 : 0;
+      const size_t rows = sizeof(double) * (size_t)nr;
+      if (!CA.E.tau || !CA.E.last || !CA.E.temp || !CA.E.e2tab || !CA.bands || !CA.part || !CA.out || (bs->npieces > 0 && !CA.pieces) ||
+          (vertical && (CA.E.nang < 1 || CA.E.nang > kMaxAngles)) || h->d_tau.bytes < rows * (size_t)nsh || h->d_last.bytes < sizeof(int) * (size_t)nsh ||
+          h->d_cpart.bytes < rows * (size_t)bs->npieces * kContribSplit || h->h_contrib_bytes < rows * (size_t)bs->nbands)
+        return fail(h, TRX_E_HIP, "internal: incomplete arguments for the contribution kernels (not launched)");
+      if (bs->npieces > 0) {
+        const dim3 cgrid((unsigned)(bs->npieces * kContribSplit), (unsigned)((nr + kContribHeights - 1) / kContribHeights));
+        if (CA.E.nang <= 8) hipLaunchKernelGGL(k_contrib_pieces<8>, cgrid, dim3(64 * kContribWaves), 0, tst, CA);
+        else                hipLaunchKernelGGL(k_contrib_pieces<kMaxAngles>, cgrid, dim3(64 * kContribWaves), 0, tst, CA);
+      }
+      hipLaunchKernelGGL(k_contrib_sums, dim3((unsigned)(((int64_t)bs->nbands * nr + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, CA);
+    }
   }
   HIPCHK(h, hipGetLastError());
   if (prof) HIPCHK(h, hipEventRecord(ev.b, tst));
@@ -2956,6 +2984,34 @@ int trx_run_bands(trx_handle *h, const trx_atm *a, const trx_opts *o, double *sp
   return rc;
 }
 
+// ---- contribution functions per band and layer (trx_contrib.hip.h) --------------------------------
+int trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, double *sums, double *contrib, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  if (!h->bands) return fail(h, TRX_E_ARG, "trx_run_contrib: no band set installed (trx_set_bands)");
+  if (!sums) return fail(h, TRX_E_ARG, "trx_run_contrib: sums is NULL");
+  if (!contrib) return fail(h, TRX_E_ARG, "trx_run_contrib: contrib is NULL");
+  if (!a || !o) return TRX_E_ARG;
+  if (a->nlayer < 1) return fail(h, TRX_E_ARG, "trx_run_contrib: nlayer < 1");
+  const BandSet *bs = h->bands.get();
+  const size_t nr = (size_t)a->nlayer, out_bytes = sizeof(double) * nr * (size_t)bs->nbands;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = ensure(h, h->d_cpart, sizeof(double) * nr * (size_t)bs->npieces * kContribSplit); if (rc) return rc; }
+  if (h->h_contrib_bytes < out_bytes) {
+    if (h->h_contrib) (void)hipHostFree(h->h_contrib);
+    h->h_contrib = nullptr; h->h_contrib_dev = nullptr; h->h_contrib_bytes = 0;
+    HIPCHK(h, hipHostMalloc(&h->h_contrib, out_bytes, hipHostMallocDefault));
+    h->h_contrib_bytes = out_bytes;
+    HIPCHK(h, hipHostGetDevicePointer(&h->h_contrib_dev, h->h_contrib, 0));
+  }
+  const int rc = run_once(h, a, o, spectrum, nullptr, dbg, bs, true);
+  if (rc == TRX_OK) {
+    std::memcpy(sums, bs->h_out, sizeof(double) * 2 * (size_t)bs->nbands);
+    std::memcpy(contrib, h->h_contrib, out_bytes);
+  }
+  return rc;
+}
+
 // ---- several atmospheres per call -----------------------------------------------------------------
 // A retrieval driver runs many chains over one line list (the reference: one run_transit per atmosphere,
 // transit.c:118-122, one process each).  One spectrum leaves the device idle between its kernels and while
@@ -2972,6 +3028,7 @@ struct trx_batch {
   uint64_t epoch = 0; bool quit = false;
   int32_t k = 0; const trx_atm *atm = nullptr; const trx_opts *opts = nullptr; double *const *spectra = nullptr;
   double *const *sums = nullptr;                     // trx_run_batch_bands: the band sums instead of the spectra
+  double *const *contrib = nullptr;                  // trx_run_batch_contrib: and the contribution functions
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -3015,7 +3072,8 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
         for (;;) {
           const int32_t j = b->next.fetch_add(1);
           if (j >= b->k) break;
-          const int rc = b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
+          const int rc = b->contrib ? trx_run_contrib(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
+                       : b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
                                  : trx_run(b->hs[(size_t)i], b->atm + j, b->opts, b->spectra[j], nullptr);
           if (rc != TRX_OK) {
             std::lock_guard<std::mutex> lk(b->mu);
@@ -3034,11 +3092,12 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 }
 
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
-static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums)
+static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
+                      double *const *contrib = nullptr)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
-  b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums;
+  b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3077,6 +3136,18 @@ int trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm, const trx_o
   if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_bands: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
   for (int32_t j = 0; j < k; j++) if (!sums[j]) { g_comm_err = "trx_run_batch_bands: sums[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   return batch_call(b, k, atm, opts, nullptr, sums);
+}
+
+int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *sums, double *const *contrib)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums || !contrib))) { g_comm_err = "trx_run_batch_contrib: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_contrib: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) {
+    if (!sums[j]) { g_comm_err = "trx_run_batch_contrib: sums[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+    if (!contrib[j]) { g_comm_err = "trx_run_batch_contrib: contrib[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  }
+  return batch_call(b, k, atm, opts, nullptr, sums, contrib);
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

@@ -200,6 +200,7 @@ def hip_library():
                                        C.c_void_p, C.POINTER(_abi.TrxDebug)]
         lib.trx_run_device.restype = C.c_int
         _abi.bind_bands_api(lib)
+        _abi.bind_contrib_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -248,6 +249,21 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_bands", self._last_error())
         return (sums, spec) if spectrum else sums
+
+    def run_contrib(self, atm, opts, spectrum: bool = False):
+        """trx_run_contrib: (sums [nbands, 2], contrib [nbands, nlayer]) of this shard -- the band sums run_bands gives
+        and the contribution function (eclipse) or transmittance profile (transit) of every band, rows in the
+        atmosphere's layer order; with spectrum=True, (sums, contrib, spectrum)."""
+        nb = getattr(self, "nbands", 0)
+        sums = np.zeros((nb, 2))
+        contrib = np.zeros((nb, int(atm.nlayer)))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_contrib(self._h, C.byref(atm), C.byref(opts),
+                                       spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                       sums.ctypes.data_as(_abi.c_double_p), contrib.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_contrib", self._last_error())
+        return (sums, contrib, spec) if spectrum else (sums, contrib)
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -313,6 +329,23 @@ class Batch:
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_bands", self._err())
         return out
+
+    def run_contrib(self, atms, opts: _abi.TrxOpts):
+        """trx_run_batch_contrib: ([K, nbands, 2], [K, nbands, nlayer]), each atmosphere's pair what
+        Engine.run_contrib gives, bit for bit (the atmospheres of one call share nlayer here)."""
+        k = len(atms)
+        nb = getattr(self, "nbands", 0)
+        nl = int(atms[0].nlayer) if k else 0
+        if any(int(a.nlayer) != nl for a in atms):
+            raise ValueError("Batch.run_contrib: atmospheres of different nlayer; call it once per nlayer")
+        sums, contrib = np.zeros((k, nb, 2)), np.zeros((k, nb, nl))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        ps = (_abi.c_double_p * max(k, 1))(*[sums[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        pc = (_abi.c_double_p * max(k, 1))(*[contrib[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_contrib(self._b, k, arr, C.byref(opts), ps, pc)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_contrib", self._err())
+        return sums, contrib
 
     def close(self):
         if self._b:
