@@ -42,3 +42,21 @@ def test_threaded_grouping_is_the_sequential_loop(tmp_path):
     out = subprocess.run([exe, "40"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout
     assert " 0 differ" in out.stdout
+
+
+def test_step_plan_holds_what_its_consumers_rely_on(tmp_path):
+    """The step plan of a run (transit_amd/csrc/trx_plan.h) on seeded random frame profiles, hints,
+    layer_chunk values, eager and opacity-grid modes (tests/plan_check.cpp): the steps of a pass tile the
+    layers from the top; every step is one kind, its frame the widest of its layers; layers per step within
+    the kind's cap, layer_chunk and the strength buffers; three layers in the first step; last_step on the
+    pass's last step alone; a pass planned whole == planned step by step; the tail predicate == one or two
+    walk steps to the hint."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "plan_check")
+    subprocess.run([gxx, "-O2", "-Wall", "-I", os.path.join(ROOT, "transit_amd", "csrc"),
+                    "-o", exe, os.path.join(ROOT, "tests", "plan_check.cpp")], check=True)
+    out = subprocess.run([exe, "20000"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout
+    assert "20000 cases, 0 differ" in out.stdout

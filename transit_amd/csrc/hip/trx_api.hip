@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
-#include <functional>
 
 #include <algorithm>
 #include <chrono>
@@ -39,6 +38,7 @@
 #include "trx_bands.hip.h"
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
+#include "../trx_plan.h"
 
 using namespace trx;
 
@@ -51,6 +51,13 @@ struct DevBuf {
   template <class T> T *as() const { return (T *)p; }
 };
 
+// pinned host memory the device reads and writes in place (dev: its address there, asked for once per allocation, not per run)
+struct PinnedBuf {
+  void *p = nullptr, *dev = nullptr; size_t bytes = 0;
+  ~PinnedBuf() { release(); }
+  void release() { if (p) { (void)hipHostFree(p); p = dev = nullptr; bytes = 0; } }
+};
+
 // view into another allocation (same accessors as DevBuf, owns nothing)
 struct DevView {
   void *p = nullptr;
@@ -61,8 +68,7 @@ struct DevView {
 struct BandSet {
   int32_t nbands = 0; int64_t npieces = 0;
   DevBuf d_bands, d_pieces, d_w, d_part;             // BandDev[nbands], BandPiece[npieces], WEIGHTS' in-shard weights, [npieces][2]
-  void *h_out = nullptr, *h_out_dev = nullptr;       // pinned [nbands][2]: k_band_sums stores the run's sums here
-  ~BandSet() { if (h_out) (void)hipHostFree(h_out); }
+  PinnedBuf h_out;                                   // [nbands][2]: k_band_sums stores the run's sums here
 };
 
 }  // namespace
@@ -145,31 +151,32 @@ struct trx_handle {
   std::vector<Cia> cia;
   DevBuf d_cia_ws;
   // per-run workspaces (grown on demand)
-  int ws_nr = 0, ws_chunk = 0;
   DevBuf d_SG, d_idop8, d_sticky, d_part3;
   // per-run inputs: packed into ONE pinned host block and copied with ONE transfer
   // (layer scalars, ray geometry, impact parameters, CIA density products)
-  DevBuf d_in; void *h_in = nullptr; size_t h_in_bytes = 0; const double *h_in_dev = nullptr;      // (h_in_dev: the pinned block as the device sees it)
+  DevBuf d_in; PinnedBuf h_in;
   DevBuf d_pm_f64, d_pm_i32;         // the same scalars of a per-molecule sweep (trx_sweep_permol)
   // what the host reads back after a run, in ONE device block and one pinned host block:
   // flags (8 ints, byte 0), status (4 ints, byte 64), counters (3 per layer, byte 128)
   DevBuf d_xf;                        // scattering / cloud wavenumber factors [2][nsh] + 3 constants
-  DevBuf d_small; DevView d_flags, d_status, d_counters; void *h_small = nullptr; size_t h_small_bytes = 0;
+  DevBuf d_small; DevView d_flags, d_status, d_counters; PinnedBuf h_small;
   DevBuf d_e, d_ecs, d_er, d_tau, d_last, d_intens, d_spec, d_acc, d_geom;
   // opacity grid (optional)
   bool has_grid = false; long og_nmol = 0, og_ntemp = 0, og_nlayer = 0, og_nwave = 0;
-  std::vector<double> og_temp; std::vector<int32_t> og_molidx; DevBuf d_og_o, d_og_layer, d_og_itemp, d_iso_mx, d_pm, d_kmaxpm;
+  std::vector<double> og_temp; std::vector<int32_t> og_molidx; DevBuf d_og_o, d_og_layer, d_og_itemp, d_iso_mx, d_pm;
   trx_stats stats{};
   std::vector<double> run_f64, run_geom, run_ipv; std::vector<int32_t> run_i32;      // per-run host arrays (kept: no allocation per run)
+  std::vector<int> run_frame; std::vector<unsigned char> run_wide;      // [layer] walk_frame_bins, and the plan's "very wide" mark (trx_plan.h)
+  std::vector<PlanStep> run_plan;                                        // the steps of the pass being queued
+  std::vector<double> run_og_layer; std::vector<int> run_og_itemp;       // opacity grid: the layers' weights and temperature brackets (Run::grid_weights)
   int hint_layers = 0;       // layers the previous run needed (deepest toomuch crossing + 1)
   DevBuf d_e_saved; std::vector<uint8_t> saved;          // trx_restore_extinction: [nlayer][nsh] and the flags (empty: none)
-  void *h_spec = nullptr; size_t h_spec_bytes = 0;     // pinned staging of the spectrum (trx_run hands over pageable memory)
-  void *h_spec_dev = nullptr, *h_small_dev = nullptr;  // the device's addresses of the pinned blocks (asked for once per allocation, not per run)
-  void *h_tailblk = nullptr, *h_tailblk_dev = nullptr; size_t h_tailblk_bytes = 0;   // pinned: what each block of k_ray_tail adds to the run's flags (vertical rays: the host adds them up)
+  PinnedBuf h_spec;          // staging of the spectrum (trx_run hands over pageable memory)
+  PinnedBuf h_tailblk;       // what each block of k_ray_tail adds to the run's flags (vertical rays: the host adds them up)
   std::unique_ptr<BandSet> bands;                      // trx_set_bands (null: none)
   // trx_run_contrib (trx_contrib.hip.h): sub-piece rows [npieces * kContribSplit][nlayer] and the pinned result [nbands][nlayer], sized on
   // first use and when the set or nlayer grows
-  DevBuf d_cpart; void *h_contrib = nullptr, *h_contrib_dev = nullptr; size_t h_contrib_bytes = 0;
+  DevBuf d_cpart; PinnedBuf h_contrib;
 };
 
 namespace {
@@ -215,22 +222,25 @@ int ensure(trx_handle *h, DevBuf &b, size_t bytes)
   return TRX_OK;
 }
 
+// grow-only, with exactly the size asked for
+int ensure_pinned(trx_handle *h, PinnedBuf &b, size_t bytes)
+{
+  if (b.bytes >= bytes) return TRX_OK;
+  b.release();
+  HIPCHK(h, hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+  b.bytes = bytes;
+  HIPCHK(h, hipHostGetDevicePointer(&b.dev, b.p, 0));
+  return TRX_OK;
+}
+
 // the small read-back block for nlay layers (device + pinned host mirror)
 int ensure_small(trx_handle *h, int nlay)
 {
   const size_t bytes = 128 + 24 * (size_t)nlay;
-  int rc = ensure(h, h->d_small, bytes);
-  if (rc) return rc;
+  if (const int rc = ensure(h, h->d_small, bytes)) return rc;
   char *base = (char *)h->d_small.p;
   h->d_flags.p = base; h->d_status.p = base + 64; h->d_counters.p = base + 128;
-  if (h->h_small_bytes < bytes) {
-    if (h->h_small) (void)hipHostFree(h->h_small);
-    h->h_small = nullptr; h->h_small_bytes = 0;
-    HIPCHK(h, hipHostMalloc(&h->h_small, bytes, hipHostMallocDefault));
-    h->h_small_bytes = bytes;
-    HIPCHK(h, hipHostGetDevicePointer(&h->h_small_dev, h->h_small, 0));
-  }
-  return TRX_OK;
+  return ensure_pinned(h, h->h_small, bytes);
 }
 
 template <class T>
@@ -1239,7 +1249,7 @@ void launch_walk(const WalkArgs &A, bool prof, unsigned nwaves, hipStream_t st)
 // walks sit back to back on their queue whatever else this step still has to queue).
 struct PendingCombine {
   bool valid = false;
-  CombineArgs C{}; hipStream_t sc = nullptr, st_walk = nullptr; hipEvent_t ev_walk = nullptr, ev_done = nullptr; bool cross = false;
+  CombineArgs C{}; hipStream_t sc = nullptr; hipEvent_t ev_walk = nullptr, ev_done = nullptr; bool cross = false;
 };
 
 int launch_combine(trx_handle *h, PendingCombine &pc, Spans *sp)
@@ -1376,7 +1386,7 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
   }
   if (sp && sp->end(st)) return fail(h, TRX_E_HIP, "event");
   PendingCombine pc;
-  pc.valid = true; pc.sc = st_comb ? st_comb : st; pc.st_walk = st; pc.cross = st_comb != nullptr && ev_walk != nullptr;
+  pc.valid = true; pc.sc = st_comb ? st_comb : st; pc.cross = st_comb != nullptr && ev_walk != nullptr;
   pc.ev_walk = ev_walk; pc.ev_done = ev_done;
   if (pc.cross) HIPCHK(h, hipEventRecord(ev_walk, st));
   CombineArgs &C = pc.C;
@@ -1867,18 +1877,8 @@ void trx_destroy(trx_handle *h)
   for (auto e : h->ev_ac) (void)hipEventDestroy(e);
   for (auto e : h->ev_cb) (void)hipEventDestroy(e);
   if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-  if (h->ev_inputs) (void)hipEventDestroy(h->ev_inputs);
-  if (h->ev_run_a) (void)hipEventDestroy(h->ev_run_a);
-  if (h->ev_run_b) (void)hipEventDestroy(h->ev_run_b);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->ev_walk1) (void)hipEventDestroy(h->ev_walk1);
-  if (h->ev_cia) (void)hipEventDestroy(h->ev_cia);
-  if (h->h_small) (void)hipHostFree(h->h_small);
-  if (h->h_in) (void)hipHostFree(h->h_in);
-  if (h->h_spec) (void)hipHostFree(h->h_spec);
-  if (h->h_tailblk) (void)hipHostFree(h->h_tailblk);
-  if (h->h_contrib) (void)hipHostFree(h->h_contrib);
-  delete h;
+  for (hipEvent_t e : {h->ev_inputs, h->ev_run_a, h->ev_run_b, h->ev_join, h->ev_walk1, h->ev_cia}) if (e) (void)hipEventDestroy(e);
+  delete h;                      // (the queues are idle: its device and pinned buffers go with it)
 }
 
 int trx_get_stats(const trx_handle *h, trx_stats *out)
@@ -1911,11 +1911,8 @@ int trx_width_grids(const trx_handle *h, double *adop, double *alor)
   return TRX_OK;
 }
 
-namespace {
-}  // namespace
-
-// ---- a run in three parts: what it is given (run_check, run_host_inputs), what it queues (run_once),
-// ---- what it hands back (run_finish)
+// ---- a run: what it is given (run_check), its state and the phases that queue it (Run), what it hands
+// ---- back (Run::finish); run_once is the sequence of the phases
 static int run_check(trx_handle *h, const trx_atm *a, const trx_opts *o)
 {
   const int nr = a->nlayer;
@@ -1932,13 +1929,263 @@ static int run_check(trx_handle *h, const trx_atm *a, const trx_opts *o)
   return TRX_OK;
 }
 
+namespace {
+
+// the rest of a step behind its extinction: its combine, the CIA kernels ahead of the first optical depth, the optical depth itself
+struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swept = 0; hipStream_t st_tau = nullptr; PendingCombine pc; };
+
+// bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
+// spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
+// contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
+struct Run {
+  // ---- what the run is given
+  trx_handle *const h; const trx_atm *const a; const trx_opts *const o;
+  double *const spectrum; void *const d_spectrum; trx_debug *const dbg; const BandSet *const bs; const bool contrib;
+  const std::chrono::steady_clock::time_point t_host0;
+
+  // ---- its shape and modes
+  const int nr = a->nlayer; const int64_t nsh = h->nsh; const hipStream_t st = h->stream;
+  const bool eager = o->eager != 0, prof = o->profile != 0, count = o->profile >= 2;
+  const bool vertical = o->solution == TRX_SOL_ECLIPSE, extras_on = o->scat_flag != 0 || o->cloud_flag != 0;
+  // Two streams: the line sweep of step c+1 (saturates the machine) runs on the main stream while the
+  // optical depth of step c (a latency chain on a few waves) is integrated on stream4.
+  const bool pipelined = !h->has_grid;
+  // A handle remembers how deep the previous spectrum went (hint_layers) and plans its steps to
+  // end exactly there; the run returns at that depth and goes on only if rays are still open.
+  const bool stop_at_hint_ok = !h->has_grid && !eager && h->hint_layers > 0 && h->hint_layers <= nr;
+  // (any run that hands its spectrum to pageable host memory stages it in the handle's pinned buffer when it is small:
+  // the copy command into pageable memory is staged by the runtime anyway, 25 us behind the copy of the flags at configs[2])
+  const bool stage_spec = spectrum && !d_spectrum && nsh <= (1 << 20);
+
+  // ---- the input block (layout): its parts and their offsets, in doubles
+  // [layer scalars f64 | ray geometry | impact parameters | CIA density products | layer scalars i32]
+  LayerHost LH{h->run_f64, h->run_i32};
+  int gstride = 0; size_t mw_doubles = 0, n_geom_all = 0, nli = 0, n_f64 = 0, n_geom = 0, n_ip = 0, n_cd = 0, n_i32 = 0;
+  size_t off_geom = 0, off_ip = 0, off_cd = 0, off_i32 = 0, in_bytes = 0;
+
+  // ---- the front end (layout, front_maxima)
+  // (the start-up pass rides along with k_layer_max only where it is small next to it: a few
+  // thousand threads striding over 10^7 rays took 20 ms at configs[4])
+  const bool ride_along = nsh <= 65536;
+  bool early_front = false; double *kmax_run = nullptr; RunInit RI{};      // (early_front: layer maxima launched from the pinned block, ahead of the host's prologue)
+
+  // ---- the block in device memory (front_inputs), the spectrum's target, what the plan reads (workspaces)
+  LayerDev Y{}; const double *d_wcut = nullptr; const int32_t *d_npre = nullptr;
+  const double *d_press = nullptr, *d_tempk = nullptr, *d_mdens = nullptr, *d_nH = nullptr, *d_scatpol = nullptr, *d_rad = nullptr;
+  const double *d_gw = nullptr, *d_gh0 = nullptr, *d_mw = nullptr, *d_mh0 = nullptr, *d_pw = nullptr, *d_ipv = nullptr, *d_ciadens = nullptr;
+  double *d_out = nullptr; PlanInput P{};
+
+  // ---- the queues
+  // Streams.  The front end (inputs, layer maxima), the walks and everything that follows the
+  // LAST walk of the plan -- its combine, optical depth, the spectrum, the copies back -- sit on
+  // ONE queue: that chain is the critical path, and a hop between queues costs it ~30 us of
+  // signalling.  The combines and optical depths of the earlier steps go to a second queue, where
+  // they overlap the next step's walk.
+  const hipStream_t st_early = pipelined ? h->stream4 : st;
+  hipStream_t tst = nullptr;                   // the spectrum's queue
+  bool early_dirty = false;                    // work queued on st_early that st has not waited for
+  bool early_behind_inputs = false;            // the side queue has waited for this run's input copy
+  bool cia_queued = false;
+
+  // ---- the ray tail (plan_first_pass; all false once the run has resumed)
+  bool tail_mode = false;                      // the pass ends in k_ray_tail
+  // tail_direct, tail_spec: it stores flags / the spectrum straight into pinned host memory
+  // two_queues, tail_on_side: its second walk may go / has gone to the side queue, the tail behind it
+  bool tail_direct = false, tail_spec = false, two_queues = false, tail_on_side = false;
+  TailArgs TA{}; int tail_nct = 0;
+  const size_t tail_blocks = (size_t)((nsh + kTailRays - 1) / kTailRays);
+
+  // ---- progress
+  int r_top = nr - 1, nchunks = 0, nwalks = 0; bool resumed = false;
+  SideWork pending;                            // a step's side work, queued behind the next step's walk
+  std::vector<uint8_t> layer_walked;           // [nr] (layout) layers swept by walk steps: 1 + the form that took them (stats)
+
+  // ---- what comes back (results)
+  int flags[8] = {}, status[4] = {}; double ms_cia = 0;
+  std::vector<unsigned long long> counters;    // [3 * nr] (layout)
+  Spans spans; Spans *const sp = prof ? &spans : nullptr;
+  std::chrono::steady_clock::time_point t_host_prep = t_host0, t_host_queued = t_host0, t_lap = t_host0;
+  const bool lap_on = log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG; std::string laps;
+
+  // an error return must not leave work of this run in flight (the next run would overwrite its inputs underneath it)
+  bool in_flight = false;
+  ~Run() { if (in_flight) { (void)hipStreamSynchronize(h->stream4); (void)hipStreamSynchronize(h->stream2); (void)hipStreamSynchronize(h->stream); } }
+
+  void lap(const char *what) {
+    if (!lap_on) return;
+    const auto n = std::chrono::steady_clock::now();
+    char b[64]; std::snprintf(b, sizeof b, " %s %.0f", what, 1e3 * std::chrono::duration<double, std::milli>(n - t_lap).count());
+    laps += b; t_lap = n;
+  }
+  // kernel arguments
+  void model_args(TauArgs &T) const; void tau_args(TauArgs &T, int r_top_, int nc_) const; void emis_args(EmisArgs &E) const; void mod_args(ModArgs &M) const;
+  // launches: the instantiation and the grid of a kernel family in one place
+  void launch_tau(const TauArgs &T, hipStream_t q) const; void launch_ray_tail() const;
+  void launch_run_init() const
+  { hipLaunchKernelGGL(k_run_init, dim3((unsigned)std::min<long long>((std::max<long long>(nsh, 3LL * nr) + 255) / 256, 65536)), dim3(256), 0, st, RI); }
+  // the phases, in the order run_once calls them
+  int layout(); int front_maxima(); void host_inputs();            // (host_inputs: within front_maxima)
+  int workspaces(); int front_inputs(); int grid_weights();        // (grid_weights: within front_inputs)
+  int plan_first_pass(); int pass(); int resume(); int finish();
+  // what a pass is made of: its steps ...
+  int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
+  int side_work(SideWork &S); int queue_cia(); int join_early();
+  // ... the spectrum of what they swept, the way back
+  int spectrum_kernel(); int ray_tail(); int band_kernels(); int results();
+};
+
+// scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
+// wavenumber factors the optical-depth kernels multiply the layer parts with (k_extras_factors)
+void Run::model_args(TauArgs &T) const
+{
+  T.nr = nr; T.nsh = nsh; T.lo = h->lo; T.wn_i = h->wn_i; T.wn_d = h->wn_d; T.wn_fct = o->wn_fct;
+  T.scat_flag = o->scat_flag; T.cloud_flag = o->cloud_flag; T.nmol = h->nmol;
+  T.scat_pref = std::pow(10.0, o->scat_logext) * kE0H2;
+  T.press = d_press; T.temp = d_tempk; T.scat_pol = d_scatpol;
+  T.cloud_top = o->cloud_top; T.cloud_bot = o->cloud_bot; T.cloud_ext = o->cloud_ext; T.cloud_gamma = o->cloud_gamma;
+  T.cloud_Q = o->cloud_Q; T.cloud_r = o->cloud_r; T.cloud_sig = o->cloud_sig; T.cloud_refwn = o->cloud_refwn;
+  T.mdens = d_mdens; T.nH = d_nH;
+  if (extras_on) { T.xf_scat = h->d_xf.as<double>(); T.xf_cloud = T.xf_scat + nsh; T.xf_const = T.xf_cloud + nsh; }
+}
+
+void Run::tau_args(TauArgs &T, int r_top_, int nc_) const
+{
+  T.solution = o->solution; T.rad_fct = a->rad_fct; T.toomuch = o->toomuch;
+  T.r_top = r_top_; T.nc = nc_; T.rad = d_rad; T.e = h->d_e.as<double>(); T.ecs = h->d_ecs.as<double>();
+  T.er = h->d_er.as<double>(); T.tau = h->d_tau.as<double>(); T.last = h->d_last.as<int>();
+  T.er_all = (dbg != nullptr || eager) ? 1 : 0;
+  T.gw = d_gw; T.gstride = gstride; T.gh0 = d_gh0;
+  model_args(T);
+  T.flags = h->d_flags.as<int>(); T.eager = eager;
+  T.pw = d_pw; T.acc = h->d_acc.as<double>(); T.lay = vertical ? d_pw + 6 * (size_t)nr : nullptr;
+  T.hrs = d_pw + 4 * (size_t)nr; T.hr0 = T.hrs + nr; T.status = h->d_status.as<int>();
+}
+
+void Run::emis_args(EmisArgs &E) const
+{
+  E.nr = nr; E.nang = o->nangles; E.nsh = nsh; E.lo = h->lo; E.wn_i = h->wn_i; E.wn_d = h->wn_d; E.wn_fct = o->wn_fct;
+  E.tau = h->d_tau.as<double>(); E.last = h->d_last.as<int>(); E.temp = d_tempk;
+  std::vector<double> grid(o->nangles + 1);                    // eclipse.c:262-269
+  grid[0] = 0.0 * kDeg; grid[o->nangles] = 90.0 * kDeg;
+  for (int i = 1; i < o->nangles; i++) grid[i] = (o->angles_deg[i-1] + o->angles_deg[i]) * kDeg / 2.0;
+  for (int i = 0; i < o->nangles; i++) {
+    E.cosang[i] = std::cos(o->angles_deg[i] * kDeg);
+    E.area[i] = std::pow(std::sin(grid[i+1]), 2.0) - std::pow(std::sin(grid[i]), 2.0);
+    E.rcos[i] = checked_reciprocal(h, E.cosang[i]);
+  }
+  E.intens = h->d_intens.as<double>(); E.flux = d_out; E.e2tab = h->d_e2tab.as<double>();
+}
+
+void Run::mod_args(ModArgs &M) const
+{
+  M.nr = nr; M.modlevel = o->modlevel; M.transparent = o->transparent; M.nsh = nsh; M.toomuch = o->toomuch;
+  M.ip_fct = a->rad_fct; M.srad = o->starrad_cm; M.tau = h->d_tau.as<double>(); M.last = h->d_last.as<int>();
+  M.ip = d_ipv; M.gw = d_mw; M.gstride = gstride; M.gh0 = d_mh0; M.out = d_out; M.status = h->d_status.as<int>();
+}
+
+void Run::launch_tau(const TauArgs &T, hipStream_t q) const
+{
+  if (vertical) {
+    // small shards: one wave per block spreads the (latency-bound) chains over more CUs
+    const bool small = nsh <= 64 * 1024;
+    const dim3 grid((unsigned)std::min<int64_t>((nsh + (small ? 63 : 255)) / (small ? 64 : 256), kTauMaxBlocks)), block(small ? 64 : 256);
+    void (*const k[2][2])(TauArgs) = {{k_optical_depth_vertical<false, false>, k_optical_depth_vertical<false, true>},       // [small][extras]
+                                      {k_optical_depth_vertical<true, false>, k_optical_depth_vertical<true, true>}};
+    hipLaunchKernelGGL(k[small][extras_on], grid, block, 0, q, T);
+    return;
+  }
+  const dim3 grid((unsigned)std::min<int64_t>((nsh + kTauW - 1) / kTauW, kTauMaxBlocks));
+  hipLaunchKernelGGL(extras_on ? k_optical_depth<true> : k_optical_depth<false>, grid, dim3(256), 0, q, T);
+}
+
+void Run::launch_ray_tail() const
+{
+  void (*const k[2][3])(TailArgs) = {{k_ray_tail<0, false>, k_ray_tail<8, false>, k_ray_tail<kMaxAngles, false>},       // [extras][slant rays, <= 8 angles, more]
+                                     {k_ray_tail<0, true>, k_ray_tail<8, true>, k_ray_tail<kMaxAngles, true>}};
+  hipLaunchKernelGGL(k[extras_on][!vertical ? 0 : o->nangles <= 8 ? 1 : 2], dim3((unsigned)tail_blocks), dim3(kTailThreads), 0, tst, TA);
+}
+
+// ---- the input block's layout and what is sized by the run's shape alone
+int Run::layout()
+{
+  int rc;
+  // ray geometry: Simpson weights per start layer (eclipse.c:82-96, slantpath.c:76-95)
+  // (eclipse geometry uses tabulated weights for its one three-point ray only: rows of one pair,
+  // no modulation table -- 9 KB instead of 330 KB to build, copy and ship per run at 100 layers)
+  gstride = vertical ? 4 : 4 * (nr / 2 + 1);
+  mw_doubles = vertical ? 0 : (size_t)(nr + 1) * gstride;
+  n_geom_all = (size_t)(nr + 1) * gstride + mw_doubles + 2 * (size_t)(nr + 1) + 4 * (size_t)nr + 2 * (size_t)nr +
+               (vertical ? (size_t)kVertLay * nr : 0);       // (vertical rays: the chain's per-layer constants behind the rest)
+  nli = (size_t)nr * std::max(h->niso, 1);
+  n_f64 = 7 * nli + 8 * (size_t)nr; n_geom = vertical ? n_geom_all : 1; n_ip = (size_t)nr; n_cd = (size_t)nr * h->cia.size(); n_i32 = 4 * nli;
+  off_geom = n_f64; off_ip = off_geom + n_geom; off_cd = off_ip + n_ip; off_i32 = off_cd + n_cd;
+  in_bytes = (8 * off_i32 + 4 * n_i32 + 8 + 15) & ~(size_t)15;
+  if ((rc = ensure_pinned(h, h->h_in, in_bytes)) || (rc = ensure(h, h->d_in, in_bytes)) || (rc = ensure_small(h, nr)) ||
+      (rc = ensure(h, h->d_last, sizeof(int) * nsh)) || (rc = ensure(h, h->d_acc, sizeof(double) * 2 * nsh)) ||
+      (rc = ensure(h, h->d_sticky, sizeof(int) * nli)))
+    return rc;
+  // the layer maxima of consecutive runs alternate between two arrays: the run's start-up pass
+  // (which rides along with k_layer_max) zeroes the NEXT run's
+  const size_t had = h->d_kmax.bytes;
+  if ((rc = ensure(h, h->d_kmax, sizeof(double) * 2 * (size_t)nr))) return rc;
+  if (h->d_kmax.bytes != had || !h->kmax_clean || h->kmax_nr != nr) {
+    HIPCHK(h, hipMemsetAsync(h->d_kmax.p, 0, sizeof(double) * 2 * (size_t)nr, st));
+    h->kmax_parity = 0; h->kmax_nr = nr;
+  }
+  h->kmax_clean = false;               // until this run has got through (an error return leaves the halves in doubt)
+  kmax_run = h->d_kmax.as<double>() + (size_t)h->kmax_parity * nr;
+  RI.last = h->d_last.as<int>(); RI.nsh = nsh; RI.acc = h->d_acc.as<double>();
+  RI.counters = h->d_counters.as<unsigned long long>(); RI.ncounters = 3 * nr;
+  RI.kmax = h->d_kmax.as<double>() + (size_t)(h->kmax_parity ^ 1) * nr; RI.nkmax = nr;
+  RI.status = h->d_status.as<int>(); RI.flags = h->d_flags.as<int>(); RI.rays = (int)std::min<int64_t>(nsh, 0x7fffffff);
+  h->kmax_parity ^= 1;
+  counters.assign(3 * (size_t)nr, 0); layer_walked.assign((size_t)nr, 0);
+  in_flight = true;
+  return TRX_OK;
+}
+
+// ---- the device's first kernel, ahead of the host's prologue.  The strongest line of every layer (k_layer_max) needs
+// -c/T and SIGCTE*ratio/(m*Z) only: they go into the pinned block first, the kernel reads them THERE (a few hundred
+// doubles over the host link, once per block) and runs while the host computes widths, table indices, frames and ray
+// geometry -- 12 us that used to lie in front of the device's first instruction.  The rest of the block reaches device
+// memory by extra blocks of the next kernel (k_sticky_index, which reads its own few inputs from the pinned block too):
+// no copy engine, no wait of a kernel for a copy's completion signal.  (Opacity-grid runs and runs without lines have
+// no such kernels: the block is copied as before.)
+int Run::front_maxima()
+{
+  int rc;
+  early_front = !h->has_grid && h->ngroups > 0 && h->h_in.dev != nullptr;
+  if (early_front) {
+    double *hin = (double *)h->h_in.p;
+    for (int r = 0; r < nr; r++) {
+      if (!(a->temp[r] > 0)) return fail(h, TRX_E_ARG, "non-positive layer temperature");
+      hin[r] = layer_negct(a->temp[r]);
+      for (int i = 0; i < h->niso; i++) hin[(size_t)nr + (size_t)r * h->niso + i] = layer_strength(h, i, a->zpart[(size_t)i * nr + r]);
+    }
+    if (!ride_along) launch_run_init();
+    LayerDev Yp{}; Yp.negc_over_t = (const double *)h->h_in.dev; Yp.strength_f = Yp.negc_over_t + nr;
+    bool rode = false;
+    if ((rc = launch_layer_max(h, Yp, nr, a->temp, 1, nullptr, st, kmax_run, ride_along ? &RI : nullptr, &rode))) return rc;
+    lap("max");
+  }
+  // ---- layer prologue (extinction.c:364-395)
+  if ((rc = prep_layers(h, nr, a->temp, a->density, a->zpart, 8 * (size_t)nr, LH))) return rc;
+  lap("layers");
+  h->walk_temp_ok = true;
+  for (int r = 0; r < nr; r++) if (a->temp[r] < kWalkMinTemp) h->walk_temp_ok = false;
+  host_inputs();
+  lap("rays");
+  if (LH.f64.size() != n_f64 || h->run_geom.size() != n_geom || h->run_ipv.size() != n_ip || LH.i32.size() != n_i32)
+    return fail(h, TRX_E_HIP, "internal: the input block's layout");
+  return TRX_OK;
+}
+
 // the host's share of a run's inputs beyond prep_layers: the layer scalars of the scattering / cloud
 // models, the vertical rays' Simpson weights and per-layer chain constants, the impact parameters
-static void run_host_inputs(trx_handle *h, const trx_atm *a, LayerHost &LH, bool vertical, int gstride, size_t mw_doubles,
-                            size_t n_geom_all, std::vector<double> &geom, std::vector<double> &ipv)
+void Run::host_inputs()
 {
-  const int nr = a->nlayer, nmol = h->nmol;
-  std::vector<double> &f64 = LH.f64;
+  const int nmol = h->nmol;
+  std::vector<double> &f64 = LH.f64, &geom = h->run_geom, &ipv = h->run_ipv;
   // layer-only scalars of the scattering / cloud models (tau.c:193-214, extinction.c:617-621)
   double *press = &f64[LH.extra_off], *tempk = press + nr, *mdens = tempk + nr, *nH = mdens + nr,
          *scat_pol = nH + nr, *radv = scat_pol + nr;
@@ -1958,89 +2205,553 @@ static void run_host_inputs(trx_handle *h, const trx_atm *a, LayerHost &LH, bool
     mdens[r] = md * mm; scat_pol[r] = sp;
   }
 
-  geom.assign(vertical ? n_geom_all : 1, 0.0);                    // (transit: device-built, k_slant_geometry)
-  {
+  geom.assign(vertical ? n_geom_all : 1, 0.0);                    // (transit: device-built, k_slant_geometry -- nothing to prepare or ship here)
+  if (vertical) {
     std::vector<double> sx(nr + 1);
-    if (vertical) {
-      double *gw = &geom[0], *gh0 = gw + (size_t)(nr + 1) * gstride;
-      double *pw = gh0 + (nr + 1) + mw_doubles + (nr + 1);    // pair weights by starting layer (vertical rays)
-      // only the two-point ray (start layer nr-2) integrates with tabulated weights (eclipse.c:68-80);
-      // all others run on the pair weights below
-      const int rs = nr - 2;
-      const double r3[3] = {a->radius[rs], (a->radius[rs] + a->radius[rs+1]) / 2.0, a->radius[rs+1]};
-      sx[0] = 0.0;
-      for (int i = 1; i < 3; i++) sx[i] = sx[i-1] + (r3[i] - r3[i-1]);
-      simpson_weights(sx.data(), 3, gw + (size_t)rs * gstride, gh0 + rs);
-      for (int k = 0; k + 2 < nr; k++) { double h0; simpson_weights(a->radius + k, 3, pw + 4 * (size_t)k, &h0); }
-      // what the chain of bottom-point parabolas and Simpson sums needs per layer (VertLayer, trx_kernels.hip.h):
-      // the same IEEE operations the kernels used to repeat in every block
-      double *lay = pw + 6 * (size_t)nr;
-      for (int rs = 0; rs < nr; rs++) {
-        double *L = lay + (size_t)kVertLay * rs;
-        if (rs + 1 < nr) {
-          const double step = a->radius[rs + 1] - a->radius[rs];
-          L[0] = step; L[1] = a->radius[rs] / step; L[2] = 2.0 * step * step;
-          L[8] = 1.0 / step; L[9] = 1.0 / L[2]; L[10] = L[1] + 1.5;
-        }
-        for (int q = 0; q < 4; q++) L[3 + q] = pw[4 * (size_t)rs + q];
-        L[7] = a->radius[rs]; L[11] = a->radius[rs] * a->radius[rs];
+    double *gw = &geom[0], *gh0 = gw + (size_t)(nr + 1) * gstride;
+    double *pw = gh0 + (nr + 1) + mw_doubles + (nr + 1);    // pair weights by starting layer (vertical rays)
+    // only the two-point ray (start layer nr-2) integrates with tabulated weights (eclipse.c:68-80);
+    // all others run on the pair weights below
+    const int rs = nr - 2;
+    const double r3[3] = {a->radius[rs], (a->radius[rs] + a->radius[rs+1]) / 2.0, a->radius[rs+1]};
+    sx[0] = 0.0;
+    for (int i = 1; i < 3; i++) sx[i] = sx[i-1] + (r3[i] - r3[i-1]);
+    simpson_weights(sx.data(), 3, gw + (size_t)rs * gstride, gh0 + rs);
+    for (int k = 0; k + 2 < nr; k++) { double h0; simpson_weights(a->radius + k, 3, pw + 4 * (size_t)k, &h0); }
+    // what the chain of bottom-point parabolas and Simpson sums needs per layer (VertLayer, trx_kernels.hip.h):
+    // the same IEEE operations the kernels used to repeat in every block
+    double *lay = pw + 6 * (size_t)nr;
+    for (int rs = 0; rs < nr; rs++) {
+      double *L = lay + (size_t)kVertLay * rs;
+      if (rs + 1 < nr) {
+        const double step = a->radius[rs + 1] - a->radius[rs];
+        L[0] = step; L[1] = a->radius[rs] / step; L[2] = 2.0 * step * step;
+        L[8] = 1.0 / step; L[9] = 1.0 / L[2]; L[10] = L[1] + 1.5;
       }
-    } else {
-      // transit geometry: built on the device (k_slant_geometry), nothing to prepare or ship here
+      for (int q = 0; q < 4; q++) L[3 + q] = pw[4 * (size_t)rs + q];
+      L[7] = a->radius[rs]; L[11] = a->radius[rs] * a->radius[rs];
     }
   }
   ipv.resize((size_t)nr);
   for (int i = 0; i < nr; i++) ipv[i] = a->radius[nr - 1 - i];
+}
 
+// ---- workspaces, and what the step plan reads (trx_plan.h)
+int Run::workspaces()
+{
+  int rc;
+  // Layers per step.  The walk (narrow profiles) takes up to 64 layers, one per lane; its cost
+  // hardly depends on how many lanes are busy, so its steps are as large as the plan allows.
+  // The two-kernel form keeps a strength buffer per layer in flight: at most kMaxChunk, and
+  // 8 where the profiles are wide.  Optical depths are integrated in sub-steps of at most tau_cap layers.
+  const int user_chunk = o->layer_chunk > 0 ? std::max(3, o->layer_chunk) : 0;
+  bool any_wide = false;                      // some layer needs the two-kernel form
+  h->run_frame.resize((size_t)nr); h->run_wide.resize((size_t)nr);
+  for (int r = 0; r < nr; r++) {
+    h->run_frame[r] = walk_frame_bins(h, LH.psmax, r);
+    h->run_wide[r] = (2 * layer_psmax(h, LH.psmax, r)) / h->osamp + 1 >= 64;
+    any_wide = any_wide || h->run_frame[r] == 0;
+  }
+  const size_t gr_b = (size_t)std::max<int64_t>(h->ngroups, 1);
+  P.sg_layers = any_wide ? (user_chunk ? std::min(user_chunk, kMaxChunk) : kMaxChunk) : 1;
+  P.frame = h->run_frame.data(); P.very_wide = h->run_wide.data(); P.nr = nr; P.hint_layers = h->hint_layers; P.user_chunk = user_chunk;
+  P.eager = eager; P.has_grid = h->has_grid; P.stop_at_hint_ok = stop_at_hint_ok; P.walk_cap = kWalkLayers; P.chunk_cap = kMaxChunk;
+  if ((rc = ensure(h, h->d_SG, sizeof(double) * gr_b * P.sg_layers)) || (rc = ensure(h, h->d_idop8, gr_b * P.sg_layers)) ||
+      (rc = ensure(h, h->d_e, sizeof(double) * nr * nsh)) || (rc = ensure(h, h->d_er, sizeof(double) * nr * nsh)) ||
+      (rc = ensure(h, h->d_tau, sizeof(double) * nr * nsh)) ||
+      (rc = ensure(h, h->d_intens, sizeof(double) * kMaxAngles * nsh)) || (rc = ensure(h, h->d_spec, sizeof(double) * nsh)))
+    return rc;
+  if (pipelined)
+    while ((int)h->ev_ac.size() < nr + 1) {
+      hipEvent_t e1, e2;
+      if (hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess) return fail(h, TRX_E_HIP, "event");
+      h->ev_ac.push_back(e1); h->ev_cb.push_back(e2);
+    }
+  if (count && any_wide && (rc = ensure(h, h->d_part3, 24 * (size_t)kMaxChunk * ((((size_t)((nsh + kTileBins - 1) / kTileBins) + 3) / 4) + kXcds * kAccumXcdGroup))))
+    return rc;
+  return ensure(h, h->d_ecs, sizeof(double) * (size_t)nr * nsh);
+}
+
+// ---- the block filled and (no early front end) copied, the device's view of it; then the front kernels behind it
+int Run::front_inputs()
+{
+  int rc;
+  double *hin = (double *)h->h_in.p;
+  // (-c/T and the strength factors are in place already where the layer maxima were launched from them -- the same
+  // values: they are not written a second time under a kernel that may be reading them)
+  const size_t skip = early_front ? (size_t)nr + nli : 0;
+  std::memcpy(hin + skip, LH.f64.data() + skip, 8 * (n_f64 - skip));
+  std::memcpy(hin + off_geom, h->run_geom.data(), 8 * n_geom);
+  std::memcpy(hin + off_ip, h->run_ipv.data(), 8 * n_ip);
+  cia_densities(h, a, hin + off_cd);
+  std::memcpy(hin + off_i32, LH.i32.data(), 4 * n_i32);
+  lap("block");
+  t_host_prep = std::chrono::steady_clock::now();
+  lap("prep");
+  if (!early_front) { HIPCHK(h, hipMemcpyAsync(h->d_in.p, h->h_in.p, in_bytes, hipMemcpyHostToDevice, st)); lap("h2d"); }
+  // With lines, every element of e the path reads is written first (the accumulation kernels
+  // store every bin of a swept layer) and zeros only matter in the dumps.  Without any
+  // in-range line (empty list, all lines outside the band, a CIA-only run) no kernel writes
+  // e, but the optical-depth kernels still read it: it must be zero then.
+  if (dbg || eager || (h->ngroups == 0 && !h->has_grid)) HIPCHK(h, hipMemsetAsync(h->d_e.p, 0, sizeof(double) * nr * nsh, st));
+  if (dbg || eager) HIPCHK(h, hipMemsetAsync(h->d_tau.p, 0, sizeof(double) * nr * nsh, st));
+
+  const double *df = h->d_in.as<double>();
+  layer_dev(df, (const int32_t *)(df + off_i32), LH, nr, Y, d_wcut, d_npre);
+  d_press = df + LH.extra_off; d_tempk = d_press + nr; d_mdens = d_tempk + nr; d_nH = d_mdens + nr; d_scatpol = d_nH + nr; d_rad = d_scatpol + nr;
+  // (ray geometry: part of the input block in eclipse geometry, a device-built buffer of its own in transit geometry)
+  if (!vertical && (rc = ensure(h, h->d_geom, sizeof(double) * n_geom_all))) return rc;
+  d_gw = vertical ? df + off_geom : h->d_geom.as<double>(); d_gh0 = d_gw + (size_t)(nr + 1) * gstride;
+  d_mw = d_gh0 + (nr + 1); d_mh0 = d_mw + mw_doubles; d_pw = d_mh0 + (nr + 1);
+  d_ipv = df + off_ip; d_ciadens = df + off_cd;
+  if (h->has_grid && (rc = grid_weights())) return rc;
+  // ---- the sticky Doppler index of every layer (with the block's copy into device memory riding along), or -- no early
+  // front end -- both front kernels behind the copy command.  The event marks the place of the main queue behind which
+  // the inputs are in device memory: the CIA queue waits for it when its kernels are queued (behind the first walk's
+  // launch, not on the host's way to the device's first kernel), the side queue in front of its first work of the run.
+  if (early_front) {
+    // (what k_sticky_index itself reads of the block, it reads from the pinned copy: nothing of a grid can wait for the
+    // copy blocks of the same grid)
+    const double *pf = (const double *)h->h_in.dev;
+    LayerDev Yp{}; const double *p_wcut; const int32_t *p_npre;
+    layer_dev(pf, (const int32_t *)(pf + off_i32), LH, nr, Yp, p_wcut, p_npre);
+    if ((rc = launch_sticky(h, Yp, p_npre, nr, 1, nullptr, o->ethresh, st, kmax_run, pf, h->d_in.p, in_bytes))) return rc;
+  } else {
+    if (!ride_along) launch_run_init();
+    bool rode = false;
+    if (!h->has_grid &&
+        (rc = layer_maxima_and_sticky(h, Y, d_npre, nr, a->temp, 1, nullptr, o->ethresh, st, kmax_run, ride_along ? &RI : nullptr, &rode))) return rc;
+    if (ride_along && !rode) launch_run_init();      // no line kernel to ride along with (opacity-grid mode, no in-range line)
+  }
+  HIPCHK(h, hipEventRecord(h->ev_inputs, st));
+  lap("kmax");
+  return extras_on ? ensure(h, h->d_xf, sizeof(double) * (2 * (size_t)nsh + 8)) : TRX_OK;
+}
+
+// ---- opacity grid: temperature bracket and weights per layer (extinction.c:549-574)
+int Run::grid_weights()
+{
+  if (h->og_nlayer != nr) return fail(h, TRX_E_ARG, "opacity grid has a different number of layers");
+  const int nt = (int)h->og_ntemp, nm = (int)h->og_nmol;
+  // (handle-kept like run_f64: the copies read them from the queue -- they must outlive this function -- and no allocation per run)
+  std::vector<double> &og_layer = h->run_og_layer; std::vector<int> &og_itemp = h->run_og_itemp;
+  og_layer.assign((size_t)(3 + nm) * nr, 0.0); og_itemp.assign((size_t)nr, 0);
+  for (int r = 0; r < nr; r++) {
+    const double temp = a->temp[r];
+    if (temp < h->og_temp[0] || !(temp < h->og_temp[nt - 1])) return fail(h, TRX_E_RANGE, "layer temperature outside the opacity grid");
+    int it = nearest_index(h->og_temp.data(), temp, 0, nt);
+    if (temp < h->og_temp[it]) it--;
+    og_itemp[r] = it;
+    og_layer[r] = h->og_temp[it + 1] - temp; og_layer[nr + r] = temp - h->og_temp[it];
+    og_layer[2 * (size_t)nr + r] = h->og_temp[it + 1] - h->og_temp[it];
+    for (int m = 0; m < nm; m++) og_layer[(size_t)(3 + m) * nr + r] = a->density[(size_t)h->og_molidx[m] * nr + r];
+  }
+  const int rc = upload(h, h->d_og_layer, og_layer);
+  return rc ? rc : upload(h, h->d_og_itemp, og_itemp);
+}
+
+
+// ---- the first pass planned (trx_plan.h), and with it whether the run ends in the ray tail (trx_tail.hip.h): a hinted
+// run whose plan is one or two walk steps from the top ends in ONE kernel behind its walks -- no side
+// queue, no combine / optical depth / emission launches.
+int Run::plan_first_pass()
+{
+  int rc;
+  // (the run's two timing events live with the handle: creating and destroying a pair per run was
+  // ~10 us of host time, which a small shard waits for)
+  if (!h->ev_run_a) { HIPCHK(h, hipEventCreate(&h->ev_run_a)); HIPCHK(h, hipEventCreate(&h->ev_run_b)); }
+  // (device time of the run, trx_stats.ms_run_total: profiled runs only -- an event record is a
+  // packet of its own between the spectrum kernel and the copy back)
+  if (prof) HIPCHK(h, hipEventRecord(h->ev_run_a, st));
+  h->stats.walk_steps = 0; h->stats.walk_records = 0; h->stats.walk_record_lanes = 0;
+  for (int k = 0; k < 3; k++) h->stats.walk_form_steps[k] = h->stats.walk_form_layers[k] = h->stats.walk_form_record_lanes[k] = 0;
+  if (!h->has_grid && lap_on) {
+    std::string ln = "run: walk frame (bins) per layer, top first; 0 = two-kernel form:";
+    for (int r = nr - 1; r >= 0; r--) ln += " " + std::to_string(h->run_frame[r]);
+    log_msg(TRX_LOG_DEBUG, ln);
+  }
+  d_out = d_spectrum ? (double *)d_spectrum : h->d_spec.as<double>();
+  plan_pass(P, r_top, stop_at_hint_ok, h->run_plan);
+  tail_mode = h->ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
+              nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays && plan_is_tail(h->run_plan, kTailSteps);
+  // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
+  tail_direct = tail_mode && h->tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs;
+  if ((tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
+  // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
+  // into a pinned array, one entry per block, and the HOST adds it up behind the kernel (results).  The device-side sum was three
+  // dependent device-scope atomics per block and, for the last block to arrive, four more round trips and a system-scope
+  // fence: the kernel's last wave ended 5 us behind its last emission -- and every one of those fences writes back and
+  // invalidates the L2 under the emission waves (8 us of emission with them, 3 without).  The run's status (slant
+  // rays: what the reference exits on) goes into four slots behind the blocks' entries, one per code.
+  if (tail_direct && (rc = ensure_pinned(h, h->h_tailblk, 8 * tail_blocks + 16))) return rc;
+  two_queues = h->two_queues && tail_direct && pipelined;      // (tail_direct: nothing behind the tail on the main queue)
+  return TRX_OK;
+}
+
+int Run::join_early()
+{
+  if (!early_dirty) return TRX_OK;
+  if (hipEventRecord(h->ev_join, st_early) != hipSuccess || hipStreamWaitEvent(st, h->ev_join, 0) != hipSuccess) return fail(h, TRX_E_HIP, "event");
+  early_dirty = false;
+  return TRX_OK;
+}
+
+// CIA extinction (device), on a second stream: only the first optical-depth kernel needs
+// e_cs, so the (latency-bound) spline kernels overlap the first sweep step.  Queued right
+// after that step's kernels, which are what the GPU is waiting for.
+int Run::queue_cia()
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  if (hipStreamWaitEvent(h->stream2, h->ev_inputs, 0) != hipSuccess) return fail(h, TRX_E_HIP, "event");
+  if (extras_on) {        // (ahead of the first optical depth like everything on this queue)
+    TauArgs X{};
+    model_args(X);
+    hipLaunchKernelGGL(k_extras_factors, dim3((unsigned)((nsh + 255) / 256)), dim3(256), 0, h->stream2, X,
+                       h->d_xf.as<double>(), h->d_xf.as<double>() + nsh, h->d_xf.as<double>() + 2 * nsh);
+  }
+  if (!vertical) {        // the slant rays' geometry, ahead of the CIA kernels: both are waited for by the first optical depth
+    SlantGeomArgs G{};
+    G.rad = d_rad; G.nr = nr; G.fct = a->rad_fct; G.gstride = gstride;
+    G.gw = const_cast<double *>(d_gw); G.gh0 = const_cast<double *>(d_gh0); G.mw = const_cast<double *>(d_mw); G.mh0 = const_cast<double *>(d_mh0);
+    G.hrs = const_cast<double *>(d_pw) + 4 * (size_t)nr; G.hr0 = G.hrs + nr;
+    hipLaunchKernelGGL(k_slant_geometry, dim3((unsigned)(nr + nr - 2)), dim3(64), 0, h->stream2, G);
+  }
+  if (const int rcc = cia_device(h, a, o, d_tempk, d_ciadens, h->stream2)) return rcc;
+  if (hipEventRecord(h->ev_cia, h->stream2) != hipSuccess) return fail(h, TRX_E_HIP, "event");
+  ms_cia = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  cia_queued = true;
+  return TRX_OK;
+}
+
+int Run::side_work(SideWork &S)
+{
+  // The side queue's first work of a run waits for the inputs explicitly.  (Every step kind of today queues it behind
+  // an event recorded on the main queue after the copy -- a walk's, a sweep's -- but that is a rule nothing states.)
+  if (S.st_tau != st && !early_behind_inputs) { HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_inputs, 0)); early_behind_inputs = true; }
+  int rc = launch_combine(h, S.pc, sp);
+  if (rc) return rc;
+  if (S.first) {
+    if ((rc = queue_cia())) return rc;
+    lap("cia");
+    HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_cia, 0));
+  }
+  if (S.st_tau == st) { if ((rc = join_early())) return rc; }       // the optical depths of the earlier steps
+  else early_dirty = true;
+  if (!h->saved.empty())        // layers restored from an earlier run (trx_restore_extinction): their rows as they were saved
+    for (int c = 0; c < S.nc; c++) {
+      const int r = S.r_top - c;
+      if (h->saved[(size_t)r])
+        HIPCHK(h, hipMemcpyAsync(h->d_e.as<double>() + (size_t)r * nsh, h->d_e_saved.as<double>() + (size_t)r * nsh, sizeof(double) * (size_t)nsh,
+                                 hipMemcpyDeviceToDevice, S.st_tau));
+    }
+  if (prof && spans.begin(Spans::kTau, S.st_tau)) return fail(h, TRX_E_HIP, "event");
+  const int tau_cap = vertical ? kMaxChunk : kTauH;
+  for (int done = 0; done < S.nc; ) {          // optical depth in sub-steps of at most tau_cap layers
+    int nt = std::min(tau_cap, S.nc - done);
+    if (S.swept == 0 && done == 0) nt = std::min(S.nc, std::max(nt, 3));
+    TauArgs T{};
+    tau_args(T, S.r_top - done, nt);
+    launch_tau(T, S.st_tau);
+    done += nt;
+  }
+  if (prof && spans.end(S.st_tau)) return fail(h, TRX_E_HIP, "event");
+  return TRX_OK;
+}
+
+int Run::grid_step(const PlanStep &s)
+{
+  if (prof && spans.begin(Spans::kSweep, st)) return fail(h, TRX_E_HIP, "event");
+  GridArgs Gd{};
+  Gd.o = h->d_og_o.as<double>(); Gd.nt = (int)h->og_ntemp; Gd.nm = (int)h->og_nmol; Gd.nr = nr;
+  Gd.nwave = h->og_nwave; Gd.lo = h->lo; Gd.nsh = nsh; Gd.r_top = s.r_top; Gd.nc = s.nc; Gd.itemp = h->d_og_itemp.as<int>();
+  Gd.w_lo = h->d_og_layer.as<double>(); Gd.w_hi = Gd.w_lo + nr; Gd.dg = Gd.w_hi + nr; Gd.dens = Gd.dg + nr;
+  Gd.e = h->d_e.as<double>(); Gd.flags = h->d_flags.as<int>(); Gd.eager = eager;
+  hipLaunchKernelGGL(k_grid_extinction, dim3((unsigned)((nsh + 255) / 256), (unsigned)s.nc), dim3(256), 0, st, Gd);
+  if (prof && spans.end(st)) return fail(h, TRX_E_HIP, "event");
+  return TRX_OK;
+}
+
+// the extinction of a step's layers from the lines: a walk (for the tail, or with its combine handed to S), or the two-kernel form
+int Run::line_step(const PlanStep &s, SideWork &S, bool &walked)
+{
+  int rc = TRX_OK, form = 0;
+  SweepMode M{};
+  M.eager = eager; M.prof = count; M.ethresh = o->ethresh;
+  M.skip_done = (!eager && !(dbg && dbg->e));
+  M.d_e = h->d_e.as<double>(); M.d_kmax = kmax_run; M.d_sticky = h->d_sticky.as<int>();
+  M.st = st;
+  bool all_saved = !h->saved.empty();
+  for (int c = 0; c < s.nc && all_saved; c++) all_saved = h->saved[(size_t)(s.r_top - c)] != 0;
+  if (h->ngroups > 0 && !all_saved) {
+    if (s.nb && tail_mode) {
+      // (no combine of its own: its records wait for the tail, each step in its own buffer)
+      // Two walks of one run do not depend on each other, and a walk alone leaves a third of the device idle for
+      // the last third of its time: waves of one launch start together and end apart -- the oldest wave of a SIMD is
+      // served first, a step's ~13 600 ranges are under two generations of resident waves, and the kernel behind it
+      // on the queue cannot start before the last wave has ended (in-kernel clocks, round 5: 7168 waves in flight
+      // for the first 60 us of k_line_walk<2>, then 5000, 3900, 3000, 2200, 1200, 370 at 5 us steps).  The plan's
+      // second walk therefore goes to the side queue, behind the event that marks the inputs, and fills what the
+      // first one leaves; the tail follows it THERE (same queue: no signal between them) and waits for the first
+      // walk's event, long satisfied by then.  Demo: 0.269 -> 0.251 ms, the same bits.
+      // ev_walk1 is recorded once, behind the main queue's first walk (step), and is all the tail on the side queue
+      // waits for: that covers every walk of the main queue only while the side queue takes every walk but the first.
+      static_assert(kTailSteps == 2, "the side-queue tail waits for ev_walk1 alone: the main queue may carry exactly one walk ahead of it");
+      const bool side_walk = two_queues && nchunks == 1;
+      if (side_walk) { HIPCHK(h, hipStreamWaitEvent(h->stream4, h->ev_inputs, 0)); M.st = h->stream4; tail_on_side = true; }
+      rc = walk_chunk(h, Y, d_wcut, s.nb, s.r_top, s.nc, M, sp, nwalks, nullptr, nullptr, nullptr, nullptr, &S.pc, &form);
+      if (!rc) {
+        TailStep &TS = TA.S[TA.nsteps++];
+        TS.P = S.pc.C.P; TS.part = S.pc.C.part; TS.nc = s.nc;
+        TA.skip = S.pc.C.last;
+        S.pc.valid = false;
+      }
+      nwalks++;
+    }
+    else if (s.nb) {
+      rc = walk_chunk(h, Y, d_wcut, s.nb, s.r_top, s.nc, M, sp, nwalks, S.st_tau != st ? S.st_tau : nullptr, h->ev_ac[nchunks],
+                      nwalks >= 2 ? h->ev_cb[(nwalks - 2) % h->ev_cb.size()] : nullptr, h->ev_cb[nwalks % h->ev_cb.size()], &S.pc, &form);
+      nwalks++;
+    }
+    else    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s.r_top, s.nc, P.sg_layers, M, sp);
+    if (rc) return rc;
+    walked = s.nb != 0;
+    if (walked) for (int c = 0; c < s.nc; c++) layer_walked[(size_t)(s.r_top - c)] = (uint8_t)(1 + form);
+  }
+  if (S.st_tau != st && !walked) {     // the optical depth of this step follows its extinction
+    HIPCHK(h, hipEventRecord(h->ev_ac[nchunks], st));
+    HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_ac[nchunks], 0));
+  }
+  return TRX_OK;
+}
+
+// ---- one top-down step of layers (tau.c:235-290)
+int Run::step(const PlanStep &s)
+{
+  int rc;
+  SideWork S; bool walked = false;
+  S.first = nchunks == 0; S.r_top = s.r_top; S.nc = s.nc; S.swept = nr - 1 - s.r_top;
+  S.st_tau = (pipelined && !s.last_step) ? st_early : st;
+  if ((rc = h->has_grid ? grid_step(s) : line_step(s, S, walked))) return rc;
+  lap("sweep");
+  if (tail_mode) {
+    // the CIA kernels go to their queue behind the first walk (what the device is waiting for) -- ahead of a second
+    // walk on the side queue too: next to TWO walks they take three times as long, and configs[3]'s two tables then
+    // end after the walks.  With two queues the main one waits for them behind its walk and marks the place: one
+    // event for the tail to wait for.
+    if (!cia_queued) {
+      if ((rc = queue_cia())) return rc;
+      if (two_queues && !s.last_step) { HIPCHK(h, hipStreamWaitEvent(st, h->ev_cia, 0)); HIPCHK(h, hipEventRecord(h->ev_walk1, st)); }
+      lap("cia");
+    }
+  } else {
+    // The rest of the step -- its combine, the CIA kernels ahead of the first optical depth, the
+    // optical depth itself -- goes to the side queue for every step but the plan's last, and is
+    // QUEUED only after the next step's walk: the walks then sit back to back on the main queue
+    // however long the host takes over the rest (small shards are host-bound otherwise).
+    if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
+    S.active = true;
+    // (walk steps only: with the two-kernel form's long steps the later queueing of an optical
+    // depth measurably delays the stop information the next step's tile skipping reads --
+    // configs[4] 0.223 -> 0.246 s)
+    if (S.st_tau != st && walked) pending = S;
+    else if ((rc = side_work(S))) return rc;
+    lap("tau");
+  }
+  r_top -= s.nc; nchunks++;
+  return TRX_OK;
+}
+
+// ---- the ray tail: every address it reads or writes is checked on the host before the launch
+int Run::ray_tail()
+{
+  int rc;
+  if (tail_on_side) { tst = h->stream4; HIPCHK(h, hipStreamWaitEvent(tst, h->ev_walk1, 0)); }
+  else {
+    if (!cia_queued && (rc = queue_cia())) return rc;
+    HIPCHK(h, hipStreamWaitEvent(st, h->ev_cia, 0));
+  }
+  TA.niso = h->niso; TA.gblock = h->d_gblock.as<int32_t>(); TA.e = h->d_e.as<double>();
+  for (int b = 0; b < h->niso && b < 64; b++) if (h->h_gblock[b] != h->h_gblock[b + 1]) TA.blocks |= 1ull << b;
+  int nct = 0; for (int k = 0; k < TA.nsteps; k++) nct += TA.S[k].nc;
+  tau_args(TA.T, nr - 1, nct);
+  if (vertical) emis_args(TA.E); else mod_args(TA.M);
+  if (tail_direct) {              // spectrum and flags straight into pinned host memory: no copy commands behind the kernel
+    if (tail_spec) (vertical ? TA.E.flux : TA.M.out) = (double *)h->h_spec.dev;
+    TA.host_flags = (int *)h->h_small.dev;
+    TA.host_blocks = (int *)h->h_tailblk.dev;
+    std::memset((char *)h->h_tailblk.p + 8 * tail_blocks, 0, 16);
+    if (!vertical) TA.M.status_slots = TA.host_blocks + 2 * tail_blocks;
+    tail_nct = nct;
+  }
+  // (a null or stale address here is a wild access of a whole grid: round 3's one memory fault -- a work-in-progress
+  // tail storing the spectrum through a pinned buffer that no branch had allocated yet -- was exactly this kind)
+  bool ok = TA.nsteps >= 1 && TA.nsteps <= kTailSteps && nct >= 3 && nct <= kTailLayers && TA.gblock && TA.e &&
+            TA.T.ecs && TA.T.er && TA.T.tau && TA.T.last && TA.T.flags && TA.T.status && TA.T.rad &&
+            (vertical ? (TA.T.acc && TA.T.lay && TA.T.gw && TA.E.flux && TA.E.intens && TA.E.temp && TA.E.e2tab)
+                      : (TA.T.hrs && TA.T.hr0 && TA.T.gw && TA.M.out && TA.M.ip && TA.M.gw && TA.M.gh0 && TA.M.status)) &&
+            (!extras_on || (TA.T.xf_scat && TA.T.xf_cloud)) && (!tail_direct || (TA.host_flags && TA.host_blocks));
+  for (int k = 0; k < TA.nsteps && ok; k++)
+    ok = TA.S[k].part && TA.S[k].nc >= 1 && TA.S[k].nc <= kWalkLayers && TA.S[k].P.blo && TA.S[k].P.bhi && TA.S[k].P.off && TA.S[k].P.wbase;
+  if (!ok) return fail(h, TRX_E_HIP, "internal: incomplete arguments for the ray tail (not launched)");
+  if (prof && spans.begin(Spans::kTau, tst)) return fail(h, TRX_E_HIP, "event");
+  launch_ray_tail();
+  if (prof && spans.end(tst)) return fail(h, TRX_E_HIP, "event");
+  if (lap_on) log_msg(TRX_LOG_DEBUG, "run: ray tail over " + std::to_string(TA.nsteps) + " walk steps, " + std::to_string(nct) + " layers");
+  return TRX_OK;
+}
+
+// ---- the spectrum of the layers swept so far: the ray tail, or emission, or modulation
+int Run::spectrum_kernel()
+{
+  if (const int rc = join_early()) return rc;
+  if (resumed) HIPCHK(h, hipMemsetAsync(h->d_status.p, 0, 16, st));       // (a resumed run computes the spectrum a second time)
+  tst = st;
+  if (tail_mode) return ray_tail();
+  const bool rows = h->nwn > kEmisRowsAbove;       // (by the job's grid, not the shard: all shards of a job add in the same order)
+  const dim3 grows((unsigned)((nsh + 255) / 256));
+  if (vertical) {
+    EmisArgs E{};
+    emis_args(E);
+    if (rows) hipLaunchKernelGGL(k_emission_rows, grows, dim3(256), 0, st, E);
+    else      hipLaunchKernelGGL(k_emission, dim3((unsigned)((nsh + kEmisWaves - 1) / kEmisWaves)), dim3(64 * kEmisWaves), 0, st, E);
+  } else {
+    ModArgs M{};
+    mod_args(M);
+    if (rows) hipLaunchKernelGGL(k_modulation_rows, grows, dim3(256), 0, st, M);
+    else      hipLaunchKernelGGL(k_modulation, dim3((unsigned)((nsh + kModWaves - 1) / kModWaves)), dim3(64 * kModWaves), 0, st, M);
+  }
+  return TRX_OK;
+}
+
+// ---- band integrals of this pass's spectrum (trx_bands.hip.h), behind it on its queue.  A pass that resumes
+// deeper queues them again behind its own spectrum: the sums the host reads are the last pass's.
+int Run::band_kernels()
+{
+  if (!bs || bs->nbands <= 0) return TRX_OK;
+  BandArgs BA{};
+  BA.spec = d_out; BA.bands = bs->d_bands.as<BandDev>(); BA.pieces = bs->d_pieces.as<BandPiece>();
+  BA.w = bs->d_w.as<double>(); BA.part = bs->d_part.as<double>(); BA.out = (double *)bs->h_out.dev;
+  BA.npieces = bs->npieces; BA.lo = h->lo; BA.nbands = bs->nbands; BA.wn_i = h->wn_i; BA.wn_d = h->wn_d;
+  if (!BA.spec || !BA.bands || !BA.part || !BA.out || (bs->npieces > 0 && !BA.pieces))
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the band kernels (not launched)");
+  if (bs->npieces > 0)
+    hipLaunchKernelGGL(k_band_pieces, dim3((unsigned)((bs->npieces + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
+  hipLaunchKernelGGL(k_band_sums, dim3((unsigned)((bs->nbands + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
+  // ---- and the contribution functions of this pass's optical depths (trx_contrib.hip.h), behind them
+  if (!contrib) return TRX_OK;
+  ContribArgs CA{};
+  if (vertical) emis_args(CA.E);
+  else {                                             // (transit geometry: the grid, tau and last; no angles)
+    CA.E.nr = nr; CA.E.nang = 0; CA.E.nsh = nsh; CA.E.lo = h->lo; CA.E.wn_i = h->wn_i; CA.E.wn_d = h->wn_d; CA.E.wn_fct = o->wn_fct;
+    CA.E.tau = h->d_tau.as<double>(); CA.E.last = h->d_last.as<int>(); CA.E.temp = d_tempk; CA.E.e2tab = h->d_e2tab.as<double>();
+  }
+  CA.bands = BA.bands; CA.pieces = BA.pieces; CA.w = BA.w; CA.part = h->d_cpart.as<double>(); CA.out = (double *)h->h_contrib.dev;
+  CA.npieces = bs->npieces; CA.nbands = bs->nbands; CA.vertical = vertical ? 1 : 0;
+  const size_t rows = sizeof(double) * (size_t)nr;
+  if (!CA.E.tau || !CA.E.last || !CA.E.temp || !CA.E.e2tab || !CA.bands || !CA.part || !CA.out || (bs->npieces > 0 && !CA.pieces) ||
+      (vertical && (CA.E.nang < 1 || CA.E.nang > kMaxAngles)) || h->d_tau.bytes < rows * (size_t)nsh || h->d_last.bytes < sizeof(int) * (size_t)nsh ||
+      h->d_cpart.bytes < rows * (size_t)bs->npieces * kContribSplit || h->h_contrib.bytes < rows * (size_t)bs->nbands)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the contribution kernels (not launched)");
+  if (bs->npieces > 0) {
+    const dim3 cgrid((unsigned)(bs->npieces * kContribSplit), (unsigned)((nr + kContribHeights - 1) / kContribHeights));
+    hipLaunchKernelGGL(CA.E.nang <= 8 ? k_contrib_pieces<8> : k_contrib_pieces<kMaxAngles>, cgrid, dim3(64 * kContribWaves), 0, tst, CA);
+  }
+  hipLaunchKernelGGL(k_contrib_sums, dim3((unsigned)(((int64_t)bs->nbands * nr + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, CA);
+  return TRX_OK;
+}
+
+// ---- results back: the copies, the wait, and (direct tail) the flags summed on the host
+int Run::results()
+{
+  HIPCHK(h, hipGetLastError());
+  if (prof) HIPCHK(h, hipEventRecord(h->ev_run_b, tst));
+  // one copy into pinned memory: flags, status and (profiled runs) the counters
+  if (!tail_direct) HIPCHK(h, hipMemcpyAsync(h->h_small.p, h->d_small.p, count ? 128 + 24 * (size_t)nr : 128, hipMemcpyDeviceToHost, st));
+  // (on the spectrum's queue: a band run's tail may have run on the side queue)
+  if (spectrum && !tail_spec) HIPCHK(h, hipMemcpyAsync(stage_spec ? h->h_spec.p : (void *)spectrum, d_out, sizeof(double) * nsh, hipMemcpyDeviceToHost, tst));
+  lap("spectrum+copies");
+  t_host_queued = std::chrono::steady_clock::now();
+  if (tail_on_side) HIPCHK(h, hipStreamSynchronize(h->stream4));      // (the tail has waited for the main queue's walk: nothing is left there)
+  HIPCHK(h, hipStreamSynchronize(st));
+  // the tail stored the spectrum into the handle's pinned buffer, or the copy command did
+  if (spectrum && (tail_spec || stage_spec)) std::memcpy(spectrum, h->h_spec.p, sizeof(double) * (size_t)nsh);
+  if (tail_direct) {
+    // the flags as tau_publish leaves them after the plan's last step (all of them zero but the rays' number
+    // when the tail started: it covers the run from its first layer), from the blocks' entries.  (d_flags on the
+    // device keeps its start-of-run values: resume() sends these there before any kernel reads them.)
+    const int32_t *tb = (const int32_t *)h->h_tailblk.p;
+    int still = 0, deep = 0;
+    for (size_t b = 0; b < tail_blocks; b++) { still += tb[2 * b]; deep = std::max(deep, tb[2 * b + 1]); }
+    const int f[8] = {still, 0, tail_nct, 0, deep, 0, 0, 0};
+    std::memcpy(h->h_small.p, f, sizeof f);
+    int st4[4] = {0, 0, 0, 0};
+    for (int code = 1; code < 4; code++) if (tb[2 * tail_blocks + code]) st4[0] = code;      // (vertical rays raise none)
+    std::memcpy((char *)h->h_small.p + 64, st4, 16);
+  }
+  std::memcpy(flags, h->h_small.p, sizeof(flags));
+  std::memcpy(status, (const char *)h->h_small.p + 64, sizeof(status));
+  if (count) std::memcpy(counters.data(), (const char *)h->h_small.p + 128, 24 * (size_t)nr);      // (else: zero, as made)
+  return TRX_OK;
+}
+
+// ---- one pass: the planned steps (h->run_plan) from r_top down, the spectrum of what they swept, its way back
+int Run::pass()
+{
+  int rc;
+  for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
+  if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
+  return (rc = spectrum_kernel()) || (rc = band_kernels()) ? rc : results();
+}
+
+// Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
+// bottom, with the step kernels and no hint -- once; the second pass has nothing to resume to.
+int Run::resume()
+{
+  // (the step kernels that go on from here read the flags on the device: where the host has added them up, they go there first)
+  if (tail_direct) HIPCHK(h, hipMemcpyAsync(h->d_flags.p, h->h_small.p, 32, hipMemcpyHostToDevice, st));
+  tail_mode = tail_direct = tail_spec = tail_on_side = false;
+  resumed = true; h->hint_layers = P.hint_layers = 0;
+  plan_pass(P, r_top, false, h->run_plan);
+  return pass();
 }
 
 // what a run hands back: the handle's statistics and depth hint, the debug copies, the status raised on the device
-struct RunOutcome {
-  int flags[8], status[4];
-  const std::vector<unsigned long long> *counters; const std::vector<uint8_t> *layer_walked;
-  Spans *spans; hipEvent_t ev_a, ev_b;                    // profiled runs (null: not profiled)
-  int nchunks; double ms_cia;
-  std::chrono::steady_clock::time_point t_host0, t_host_prep, t_host_queued; const std::string *laps;
-};
-
-static int run_finish(trx_handle *h, const trx_atm *a, const trx_opts *o, trx_debug *dbg, const RunOutcome &Q,
-                      const std::function<void(TauArgs &)> &model_args)
+int Run::finish()
 {
-  const int nr = a->nlayer; const int64_t nsh = h->nsh;
-  hipStream_t st = h->stream;
   int rc;
   trx_stats &S = h->stats;
-  S.layers_swept = Q.flags[2];
-  h->hint_layers = Q.flags[4];
+  S.layers_swept = flags[2];
+  h->hint_layers = flags[4];
   S.neval = S.nskip = S.sum_bins = S.sum_bins_walk = S.walk_layers = 0;
   S.walk_form_bins[0] = S.walk_form_bins[1] = S.walk_form_bins[2] = 0;
   for (int r = 0; r < nr; r++) {
-    S.sum_bins += (int64_t)(*Q.counters)[3*r]; S.neval += (int64_t)(*Q.counters)[3*r+1]; S.nskip += (int64_t)(*Q.counters)[3*r+2];
-    if (const int fw = (*Q.layer_walked)[(size_t)r]) { S.walk_layers++; S.sum_bins_walk += (int64_t)(*Q.counters)[3*r]; S.walk_form_bins[fw - 1] += (int64_t)(*Q.counters)[3*r]; }
+    S.sum_bins += (int64_t)counters[3*r]; S.neval += (int64_t)counters[3*r+1]; S.nskip += (int64_t)counters[3*r+2];
+    if (const int fw = layer_walked[(size_t)r]) { S.walk_layers++; S.sum_bins_walk += (int64_t)counters[3*r]; S.walk_form_bins[fw - 1] += (int64_t)counters[3*r]; }
   }
-  float ms = 0; if (Q.spans) (void)hipEventElapsedTime(&ms, Q.ev_a, Q.ev_b); S.ms_run_total = ms;
-  S.ms_cia = Q.ms_cia;
-  S.ms_host_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - Q.t_host0).count();
-  if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG) {
+  float ms = 0; if (prof) (void)hipEventElapsedTime(&ms, h->ev_run_a, h->ev_run_b); S.ms_run_total = ms;
+  S.ms_cia = ms_cia;
+  S.ms_host_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+  if (lap_on) {
     char b[160];
     std::snprintf(b, sizeof b, "run: host %.0f us preparing inputs, %.0f us queueing, %.0f us waiting for the device",
-                  1e3 * std::chrono::duration<double, std::milli>(Q.t_host_prep - Q.t_host0).count(),
-                  1e3 * std::chrono::duration<double, std::milli>(Q.t_host_queued - Q.t_host_prep).count(),
-                  1e3 * (S.ms_host_total - std::chrono::duration<double, std::milli>(Q.t_host_queued - Q.t_host0).count()));
-    log_msg(TRX_LOG_DEBUG, std::string(b) + "; queueing by phase (us):" + *Q.laps);
+                  1e3 * std::chrono::duration<double, std::milli>(t_host_prep - t_host0).count(),
+                  1e3 * std::chrono::duration<double, std::milli>(t_host_queued - t_host_prep).count(),
+                  1e3 * (S.ms_host_total - std::chrono::duration<double, std::milli>(t_host_queued - t_host0).count()));
+    log_msg(TRX_LOG_DEBUG, std::string(b) + "; queueing by phase (us):" + laps);
   }
   S.ms_k_sweep = S.ms_k_walk = S.ms_k_accum = S.ms_tau = S.ms_sweep = 0; S.sweep_launches = 0;
   S.ms_k_walk_form[0] = S.ms_k_walk_form[1] = S.ms_k_walk_form[2] = 0; S.ms_walk_span = 0;
-  if (Q.spans) {
+  if (prof) {
     // every launch counts (also the ~4 us gated ones after all rays stopped), so that
     // sum / launches is the average a kernel trace reports
     double t[Spans::kKinds] = {0, 0, 0, 0, 0, 0};
-    Q.spans->sum(t);
+    spans.sum(t);
     S.ms_k_walk_form[0] = t[Spans::kWalk]; S.ms_k_walk_form[1] = t[Spans::kWalkLanes]; S.ms_k_walk_form[2] = t[Spans::kWalkPacked];
     S.ms_k_sweep = t[Spans::kSweep]; S.ms_k_walk = t[Spans::kWalk] + t[Spans::kWalkLanes] + t[Spans::kWalkPacked]; S.ms_k_accum = t[Spans::kAccum]; S.ms_tau = t[Spans::kTau];
-    S.sweep_launches = Q.nchunks;
+    S.sweep_launches = nchunks;
     S.ms_sweep = S.ms_k_sweep + S.ms_k_walk + S.ms_k_accum;
-    S.ms_walk_span = Q.spans->walk_span();
+    S.ms_walk_span = spans.walk_span();
   }
 
   if (dbg) {
@@ -2064,7 +2775,6 @@ static int run_finish(trx_handle *h, const trx_atm *a, const trx_opts *o, trx_de
       DevBuf d_x;
       if ((rc = ensure(h, d_x, sizeof(double) * 2 * (size_t)nr * nsh))) return rc;
       TauArgs T{};
-      T.nr = nr; T.nsh = nsh; T.lo = h->lo; T.wn_i = h->wn_i; T.wn_d = h->wn_d; T.wn_fct = o->wn_fct;
       model_args(T);
       double *xs = d_x.as<double>(), *xc = xs + (size_t)nr * nsh;
       hipLaunchKernelGGL(k_extras_dump, dim3((unsigned)((nsh + 255) / 256), (unsigned)nr), dim3(256), 0, st, T, xs, xc);
@@ -2073,756 +2783,29 @@ static int run_finish(trx_handle *h, const trx_atm *a, const trx_opts *o, trx_de
       if (dbg->e_cloud) HIPCHK(h, hipMemcpy(dbg->e_cloud, xc, sizeof(double) * nr * nsh, hipMemcpyDeviceToHost));
     }
   }
-  if (Q.status[0] == 1) return fail(h, TRX_E_NOTREACHED, "optical depth never reached toomuch (modlevel -1)");
-  if (Q.status[0] == 2) return fail(h, TRX_E_ARG, "fewer than three points for the radial integration");
-  if (Q.status[0] == 3) return fail(h, TRX_E_RANGE, "closest approach of a ray lies below the bottom layer (slantpath.c:39-44)");
+  if (status[0] == 1) return fail(h, TRX_E_NOTREACHED, "optical depth never reached toomuch (modlevel -1)");
+  if (status[0] == 2) return fail(h, TRX_E_ARG, "fewer than three points for the radial integration");
+  if (status[0] == 3) return fail(h, TRX_E_RANGE, "closest approach of a ray lies below the bottom layer (slantpath.c:39-44)");
   return TRX_OK;
 }
 
-// bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
-// spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
-// contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
+}  // namespace
+
 static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg,
                     const BandSet *bs = nullptr, bool contrib = false)
 {
-  if (!h || !a || !o) return TRX_E_ARG;
   const auto t_host0 = std::chrono::steady_clock::now();
-  auto t_host_queued = t_host0;
-  const int nr = a->nlayer, nmol = h->nmol;
-  const int64_t nsh = h->nsh;
-  { const int rcc = run_check(h, a, o); if (rcc) return rcc; }
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  const bool eager = o->eager != 0, prof = o->profile != 0, count = o->profile >= 2;
-  // A handle remembers how deep the previous spectrum went (hint_layers) and plans its steps to
-  // end exactly there; the run returns at that depth and goes on only if rays are still open.
-  const bool stop_at_hint_ok = !h->has_grid && !eager && h->hint_layers > 0 && h->hint_layers <= nr;
+  if (!h || !a || !o) return TRX_E_ARG;
   int rc;
-
-  hipStream_t st_sweep = st;
-  const auto t_host_first = std::chrono::steady_clock::now();
-  const bool lap_on = log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG;
-  std::string laps; auto t_lap = t_host_first;
-  auto lap = [&](const char *what) {
-    if (!lap_on) return;
-    const auto n = std::chrono::steady_clock::now();
-    char b[64]; std::snprintf(b, sizeof b, " %s %.0f", what, 1e3 * std::chrono::duration<double, std::milli>(n - t_lap).count());
-    laps += b; t_lap = n;
-  };
-  // ---- ray geometry: Simpson weights per start layer (eclipse.c:82-96, slantpath.c:76-95)
-  // (eclipse geometry uses tabulated weights for its one three-point ray only: rows of one pair,
-  // no modulation table -- 9 KB instead of 330 KB to build, copy and ship per run at 100 layers)
-  const bool vertical = o->solution == TRX_SOL_ECLIPSE;
-  const int gstride = vertical ? 4 : 4 * (nr / 2 + 1);
-  const size_t mw_doubles = vertical ? 0 : (size_t)(nr + 1) * gstride;
-  const size_t n_geom_all = (size_t)(nr + 1) * gstride + mw_doubles + 2 * (size_t)(nr + 1) + 4 * (size_t)nr + 2 * (size_t)nr +
-                            (vertical ? (size_t)kVertLay * nr : 0);       // (vertical rays: the chain's per-layer constants behind the rest)
-  // ---- per-run inputs: one pinned block (its layout is the run's shape alone)
-  // [layer scalars f64 | ray geometry | impact parameters | CIA density products | layer scalars i32]
-  const size_t nli = (size_t)nr * std::max(h->niso, 1);
-  const size_t n_f64 = 7 * nli + 8 * (size_t)nr, n_geom = vertical ? n_geom_all : 1, n_ip = (size_t)nr, n_cd = (size_t)nr * h->cia.size(), n_i32 = 4 * nli;
-  const size_t off_geom = n_f64, off_ip = off_geom + n_geom, off_cd = off_ip + n_ip, off_i32 = off_cd + n_cd;    // in doubles
-  const size_t in_bytes = (8 * off_i32 + 4 * n_i32 + 8 + 15) & ~(size_t)15;
-  if (h->h_in_bytes < in_bytes) {
-    if (h->h_in) (void)hipHostFree(h->h_in);
-    h->h_in = nullptr; h->h_in_bytes = 0; h->h_in_dev = nullptr;
-    HIPCHK(h, hipHostMalloc(&h->h_in, in_bytes, hipHostMallocDefault));
-    h->h_in_bytes = in_bytes;
-    void *dp = nullptr;
-    HIPCHK(h, hipHostGetDevicePointer(&dp, h->h_in, 0));
-    h->h_in_dev = (const double *)dp;
-  }
-  if ((rc = ensure(h, h->d_in, in_bytes)) || (rc = ensure_small(h, nr)) ||
-      (rc = ensure(h, h->d_last, sizeof(int) * nsh)) || (rc = ensure(h, h->d_acc, sizeof(double) * 2 * nsh)) ||
-      (rc = ensure(h, h->d_sticky, sizeof(int) * nli)))
+  if ((rc = run_check(h, a, o))) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  Run R{h, a, o, spectrum, d_spectrum, dbg, bs, contrib, t_host0};       // (behind run_check: its members are made from the run's shape)
+  if ((rc = R.layout()) || (rc = R.front_maxima()) || (rc = R.workspaces()) || (rc = R.front_inputs()) || (rc = R.plan_first_pass()) || (rc = R.pass()))
     return rc;
-  // the layer maxima of consecutive runs alternate between two arrays: the run's start-up pass
-  // (which rides along with k_layer_max) zeroes the NEXT run's
-  {
-    const size_t had = h->d_kmax.bytes;
-    if ((rc = ensure(h, h->d_kmax, sizeof(double) * 2 * (size_t)nr))) return rc;
-    if (h->d_kmax.bytes != had || !h->kmax_clean || h->kmax_nr != nr) {
-      HIPCHK(h, hipMemsetAsync(h->d_kmax.p, 0, sizeof(double) * 2 * (size_t)nr, st_sweep));
-      h->kmax_parity = 0; h->kmax_nr = nr;
-    }
-    h->kmax_clean = false;               // until this run has got through (an error return leaves the halves in doubt)
-  }
-  double *kmax_run = h->d_kmax.as<double>() + (size_t)h->kmax_parity * nr;
-  RunInit R{};
-  R.last = h->d_last.as<int>(); R.nsh = nsh; R.acc = h->d_acc.as<double>();
-  R.counters = h->d_counters.as<unsigned long long>(); R.ncounters = 3 * nr;
-  R.kmax = h->d_kmax.as<double>() + (size_t)(h->kmax_parity ^ 1) * nr; R.nkmax = nr;
-  R.status = h->d_status.as<int>(); R.flags = h->d_flags.as<int>(); R.rays = (int)std::min<int64_t>(nsh, 0x7fffffff);
-  h->kmax_parity ^= 1;
-  // an error return below must not leave work of this run in flight (the next run would overwrite its inputs underneath it)
-  struct Drain {
-    trx_handle *h; bool armed = true;
-    ~Drain() { if (armed) { (void)hipStreamSynchronize(h->stream4); (void)hipStreamSynchronize(h->stream2); (void)hipStreamSynchronize(h->stream); } }
-  } drain{h};
-  // ---- the device's first kernel, ahead of the host's prologue.  The strongest line of every layer (k_layer_max) needs
-  // -c/T and SIGCTE*ratio/(m*Z) only: they go into the pinned block first, the kernel reads them THERE (a few hundred
-  // doubles over the host link, once per block) and runs while the host computes widths, table indices, frames and ray
-  // geometry -- 12 us that used to lie in front of the device's first instruction.  The rest of the block reaches device
-  // memory by extra blocks of the next kernel (k_sticky_index, which reads its own few inputs from the pinned block too):
-  // no copy engine, no wait of a kernel for a copy's completion signal.  (Opacity-grid runs and runs without lines have
-  // no such kernels: the block is copied as before.)
-  // (the start-up pass rides along with k_layer_max only where it is small next to it: a few
-  // thousand threads striding over 10^7 rays took 20 ms at configs[4])
-  const bool ride_along = nsh <= 65536;
-  const bool early_front = !h->has_grid && h->ngroups > 0 && h->h_in_dev != nullptr;
-  bool init_done = false;
-  if (early_front) {
-    double *hin = (double *)h->h_in;
-    for (int r = 0; r < nr; r++) {
-      if (!(a->temp[r] > 0)) return fail(h, TRX_E_ARG, "non-positive layer temperature");
-      hin[r] = layer_negct(a->temp[r]);
-      for (int i = 0; i < h->niso; i++) hin[(size_t)nr + (size_t)r * h->niso + i] = layer_strength(h, i, a->zpart[(size_t)i * nr + r]);
-    }
-    if (!ride_along) {
-      hipLaunchKernelGGL(k_run_init, dim3((unsigned)std::min<long long>((std::max<long long>(nsh, 3LL * nr) + 255) / 256, 65536)), dim3(256), 0, st_sweep, R);
-      init_done = true;
-    }
-    LayerDev Yp{}; Yp.negc_over_t = h->h_in_dev; Yp.strength_f = h->h_in_dev + nr;
-    bool rode = false;
-    if ((rc = launch_layer_max(h, Yp, nr, a->temp, 1, nullptr, st_sweep, kmax_run, ride_along ? &R : nullptr, &rode))) return rc;
-    init_done = init_done || rode;
-    lap("max");
-  }
-
-  // ---- layer prologue (extinction.c:364-395) --------------------------------
-  LayerHost LH(h->run_f64, h->run_i32);
-  if ((rc = prep_layers(h, nr, a->temp, a->density, a->zpart, 8 * (size_t)nr, LH))) return rc;
-  lap("layers");
-  h->walk_temp_ok = true;
-  for (int r = 0; r < nr; r++) if (a->temp[r] < kWalkMinTemp) h->walk_temp_ok = false;
-  std::vector<double> &f64 = LH.f64;
-  const int32_t *psmax = LH.psmax;
-  // Layers per step.  The walk (narrow profiles) takes up to 64 layers, one per lane; its cost
-  // hardly depends on how many lanes are busy, so its steps are as large as the plan allows.
-  // The two-kernel form keeps a strength buffer per layer in flight: at most kMaxChunk, and
-  // 8 where the profiles are wide (a tile only learns between steps that its rays stopped).
-  // Optical depths are integrated in sub-steps of at most tau_cap layers.
-  const int tau_cap = o->solution == TRX_SOL_TRANSIT ? kTauH : kMaxChunk;
-  const int user_chunk = o->layer_chunk > 0 ? std::max(3, o->layer_chunk) : 0;
-  std::vector<double> &geom = h->run_geom, &ipv = h->run_ipv;
-  run_host_inputs(h, a, LH, vertical, gstride, mw_doubles, n_geom_all, geom, ipv);
-  lap("rays");
-  if (f64.size() != n_f64 || geom.size() != n_geom || ipv.size() != n_ip || LH.i32.size() != n_i32)
-    return fail(h, TRX_E_HIP, "internal: the input block's layout");
-
-  double ms_cia = 0;
-
-  // ---- workspaces -------------------------------------------------------------
-  // Two streams: the line sweep of step c+1 (saturates the machine) runs on stream4 while the
-  // optical depth of step c (a latency chain on a few waves) is integrated on the main stream.
-  const bool pipelined = !h->has_grid;
-  bool any_wide = false;                      // some layer needs the two-kernel form
-  for (int r = 0; r < nr && !any_wide; r++) any_wide = walk_frame_bins(h, psmax, r) == 0;
-  const size_t gr_b = (size_t)std::max<int64_t>(h->ngroups, 1);
-  const int sg_layers = any_wide ? (user_chunk ? std::min(user_chunk, kMaxChunk) : kMaxChunk) : 1;
-  if ((rc = ensure(h, h->d_SG, sizeof(double) * gr_b * sg_layers)) || (rc = ensure(h, h->d_idop8, gr_b * sg_layers)) ||
-      (rc = ensure(h, h->d_e, sizeof(double) * nr * nsh)) || (rc = ensure(h, h->d_er, sizeof(double) * nr * nsh)) ||
-      (rc = ensure(h, h->d_tau, sizeof(double) * nr * nsh)) ||
-      (rc = ensure(h, h->d_intens, sizeof(double) * kMaxAngles * nsh)) || (rc = ensure(h, h->d_spec, sizeof(double) * nsh)))
-    return rc;
-  if (pipelined)
-    while ((int)h->ev_ac.size() < nr + 1) {
-      hipEvent_t e1, e2;
-      if (hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess) return fail(h, TRX_E_HIP, "event");
-      h->ev_ac.push_back(e1); h->ev_cb.push_back(e2);
-    }
-  if (count && any_wide && (rc = ensure(h, h->d_part3, 24 * (size_t)kMaxChunk * ((((size_t)((nsh + kTileBins - 1) / kTileBins) + 3) / 4) + kXcds * kAccumXcdGroup))))
-    return rc;
-  if ((rc = ensure(h, h->d_ecs, sizeof(double) * (size_t)nr * nsh))) return rc;
-  {
-    double *hin = (double *)h->h_in;
-    // (-c/T and the strength factors are in place already where the layer maxima were launched from them -- the same
-    // values: they are not written a second time under a kernel that may be reading them)
-    const size_t skip = early_front ? (size_t)nr + nli : 0;
-    std::memcpy(hin + skip, f64.data() + skip, 8 * (n_f64 - skip));
-    std::memcpy(hin + off_geom, geom.data(), 8 * n_geom);
-    std::memcpy(hin + off_ip, ipv.data(), 8 * n_ip);
-    cia_densities(h, a, hin + off_cd);
-    std::memcpy(hin + off_i32, LH.i32.data(), 4 * n_i32);
-  }
-  lap("block");
-  // the whole front end of a run goes to the stream the line sweep runs on (the main stream
-  // joins it at the first optical depth): no cross-stream hop before the first sweep kernel
-  // Streams.  The front end (inputs, layer maxima), the walks and everything that follows the
-  // LAST walk of the plan -- its combine, optical depth, the spectrum, the copies back -- sit on
-  // ONE queue: that chain is the critical path, and a hop between queues costs it ~30 us of
-  // signalling.  The combines and optical depths of the earlier steps go to a second queue, where
-  // they overlap the next step's walk.
-  hipStream_t st_early = pipelined ? h->stream4 : st;
-  bool early_dirty = false;                    // work queued on st_early that st has not waited for
-  auto join_early = [&]() -> int {
-    if (!early_dirty) return TRX_OK;
-    if (hipEventRecord(h->ev_join, st_early) != hipSuccess || hipStreamWaitEvent(st, h->ev_join, 0) != hipSuccess) return fail(h, TRX_E_HIP, "event");
-    early_dirty = false;
-    return TRX_OK;
-  };
-  const auto t_host_prep = std::chrono::steady_clock::now();
-  lap("prep");
-  if (!early_front) { HIPCHK(h, hipMemcpyAsync(h->d_in.p, h->h_in, in_bytes, hipMemcpyHostToDevice, st_sweep)); lap("h2d"); }
-  // With lines, every element of e the path reads is written first (the accumulation kernels
-  // store every bin of a swept layer) and zeros only matter in the dumps.  Without any
-  // in-range line (empty list, all lines outside the band, a CIA-only run) no kernel writes
-  // e, but the optical-depth kernels still read it: it must be zero then.
-  if (dbg || eager || (h->ngroups == 0 && !h->has_grid))
-    HIPCHK(h, hipMemsetAsync(h->d_e.p, 0, sizeof(double) * nr * nsh, st_sweep));
-  if (dbg || eager)
-    HIPCHK(h, hipMemsetAsync(h->d_tau.p, 0, sizeof(double) * nr * nsh, st_sweep));
-
-  const double *df = h->d_in.as<double>();
-  LayerDev Y{}; const double *d_wcut; const int32_t *d_npre;
-  layer_dev(df, (const int32_t *)(df + off_i32), LH, nr, Y, d_wcut, d_npre);
-  const double *d_press = df + LH.extra_off, *d_tempk = d_press + nr, *d_mdens = d_tempk + nr, *d_nH = d_mdens + nr,
-               *d_scatpol = d_nH + nr, *d_rad = d_scatpol + nr;
-  // (ray geometry: part of the input block in eclipse geometry, a device-built buffer of its own in transit geometry)
-  if (!vertical && (rc = ensure(h, h->d_geom, sizeof(double) * n_geom_all))) return rc;
-  const double *d_gw = vertical ? df + off_geom : h->d_geom.as<double>(), *d_gh0 = d_gw + (size_t)(nr + 1) * gstride,
-               *d_mw = d_gh0 + (nr + 1), *d_mh0 = d_mw + mw_doubles, *d_pw = d_mh0 + (nr + 1);
-  const double *d_ipv = df + off_ip, *d_ciadens = df + off_cd;
-
-  // ---- opacity grid: temperature bracket and weights per layer (extinction.c:549-574) ----
-  std::vector<double> og_layer; std::vector<int> og_itemp;
-  if (h->has_grid) {
-    if (h->og_nlayer != nr) return fail(h, TRX_E_ARG, "opacity grid has a different number of layers");
-    const int nt = (int)h->og_ntemp, nm = (int)h->og_nmol;
-    og_layer.assign((size_t)(3 + nm) * nr, 0.0); og_itemp.assign(nr, 0);
-    for (int r = 0; r < nr; r++) {
-      const double temp = a->temp[r];
-      if (temp < h->og_temp[0] || !(temp < h->og_temp[nt - 1])) return fail(h, TRX_E_RANGE, "layer temperature outside the opacity grid");
-      int it = nearest_index(h->og_temp.data(), temp, 0, nt);
-      if (temp < h->og_temp[it]) it--;
-      og_itemp[r] = it;
-      og_layer[r] = h->og_temp[it + 1] - temp; og_layer[nr + r] = temp - h->og_temp[it];
-      og_layer[2 * (size_t)nr + r] = h->og_temp[it + 1] - h->og_temp[it];
-      for (int m = 0; m < nm; m++) og_layer[(size_t)(3 + m) * nr + r] = a->density[(size_t)h->og_molidx[m] * nr + r];
-    }
-    if ((rc = upload(h, h->d_og_layer, og_layer)) || (rc = upload(h, h->d_og_itemp, og_itemp))) return rc;
-  }
-
-  // ---- the sticky Doppler index of every layer (with the block's copy into device memory riding along), or -- no early
-  // front end -- both front kernels behind the copy command.  The event marks the place of the main queue behind which
-  // the inputs are in device memory: the CIA queue waits for it when its kernels are queued (behind the first walk's
-  // launch, not on the host's way to the device's first kernel), the side queue in front of its first work of the run.
-  if (early_front) {
-    // (what k_sticky_index itself reads of the block, it reads from the pinned copy: nothing of a grid can wait for the
-    // copy blocks of the same grid)
-    const double *pf = h->h_in_dev;
-    LayerDev Yp{}; const double *p_wcut; const int32_t *p_npre;
-    layer_dev(pf, (const int32_t *)(pf + off_i32), LH, nr, Yp, p_wcut, p_npre);
-    if ((rc = launch_sticky(h, Yp, p_npre, nr, 1, nullptr, o->ethresh, st_sweep, kmax_run, h->h_in_dev, h->d_in.p, in_bytes))) return rc;
-  } else {
-    if (!ride_along) {
-      hipLaunchKernelGGL(k_run_init, dim3((unsigned)std::min<long long>((std::max<long long>(nsh, 3LL * nr) + 255) / 256, 65536)), dim3(256), 0, st_sweep, R);
-      init_done = true;
-    }
-    bool rode = false;
-    if (!h->has_grid &&
-        (rc = layer_maxima_and_sticky(h, Y, d_npre, nr, a->temp, 1, nullptr, o->ethresh, st_sweep, kmax_run, ride_along ? &R : nullptr, &rode))) return rc;
-    if (!init_done && !rode)               // no line kernel to ride along with (opacity-grid mode, no in-range line)
-      hipLaunchKernelGGL(k_run_init, dim3((unsigned)std::min<long long>((std::max<long long>(nsh, 3LL * nr) + 255) / 256, 65536)), dim3(256), 0, st_sweep, R);
-  }
-  HIPCHK(h, hipEventRecord(h->ev_inputs, st_sweep));
-  lap("kmax");
-  // CIA extinction (device), on a second stream: only the first optical-depth kernel needs
-  // e_cs, so the (latency-bound) spline kernels overlap the first sweep step.  Queued right
-  // after that step's kernels, which are what the GPU is waiting for.
-  // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
-  // wavenumber factors the optical-depth kernels multiply the layer parts with (k_extras_factors)
-  const bool extras_on = o->scat_flag != 0 || o->cloud_flag != 0;
-  if (extras_on && (rc = ensure(h, h->d_xf, sizeof(double) * (2 * (size_t)nsh + 8)))) return rc;
-  auto model_args = [&](TauArgs &T) {
-    T.scat_flag = o->scat_flag; T.cloud_flag = o->cloud_flag; T.nmol = nmol;
-    T.scat_pref = std::pow(10.0, o->scat_logext) * kE0H2;
-    T.press = d_press; T.temp = d_tempk; T.scat_pol = d_scatpol;
-    T.cloud_top = o->cloud_top; T.cloud_bot = o->cloud_bot; T.cloud_ext = o->cloud_ext; T.cloud_gamma = o->cloud_gamma;
-    T.cloud_Q = o->cloud_Q; T.cloud_r = o->cloud_r; T.cloud_sig = o->cloud_sig; T.cloud_refwn = o->cloud_refwn;
-    T.mdens = d_mdens; T.nH = d_nH;
-    if (extras_on) { T.xf_scat = h->d_xf.as<double>(); T.xf_cloud = T.xf_scat + nsh; T.xf_const = T.xf_cloud + nsh; }
-  };
-  auto queue_cia = [&]() -> int {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (hipStreamWaitEvent(h->stream2, h->ev_inputs, 0) != hipSuccess) return fail(h, TRX_E_HIP, "event");
-    if (extras_on) {        // (ahead of the first optical depth like everything on this queue)
-      TauArgs X{};
-      X.nr = nr; X.nsh = nsh; X.lo = h->lo; X.wn_i = h->wn_i; X.wn_d = h->wn_d; X.wn_fct = o->wn_fct;
-      model_args(X);
-      hipLaunchKernelGGL(k_extras_factors, dim3((unsigned)((nsh + 255) / 256)), dim3(256), 0, h->stream2, X,
-                         h->d_xf.as<double>(), h->d_xf.as<double>() + nsh, h->d_xf.as<double>() + 2 * nsh);
-    }
-    if (!vertical) {        // the slant rays' geometry, ahead of the CIA kernels: both are waited for by the first optical depth
-      SlantGeomArgs G{};
-      G.rad = d_rad; G.nr = nr; G.fct = a->rad_fct; G.gstride = gstride;
-      G.gw = const_cast<double *>(d_gw); G.gh0 = const_cast<double *>(d_gh0); G.mw = const_cast<double *>(d_mw); G.mh0 = const_cast<double *>(d_mh0);
-      G.hrs = const_cast<double *>(d_pw) + 4 * (size_t)nr; G.hr0 = G.hrs + nr;
-      hipLaunchKernelGGL(k_slant_geometry, dim3((unsigned)(nr + nr - 2)), dim3(64), 0, h->stream2, G);
-    }
-    const int rcc = cia_device(h, a, o, d_tempk, d_ciadens, h->stream2);
-    if (rcc) return rcc;
-    if (hipEventRecord(h->ev_cia, h->stream2) != hipSuccess) return fail(h, TRX_E_HIP, "event");
-    ms_cia = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return TRX_OK;
-  };
-
-  // ---- events -----------------------------------------------------------------
-  Spans spans;
-  // (the run's two timing events live with the handle: creating and destroying a pair per run was
-  // ~10 us of host time, which a small shard waits for)
-  struct { hipEvent_t a, b; } ev{h->ev_run_a, h->ev_run_b};
-  if (!ev.a) {
-    HIPCHK(h, hipEventCreate(&h->ev_run_a)); HIPCHK(h, hipEventCreate(&h->ev_run_b));
-    ev.a = h->ev_run_a; ev.b = h->ev_run_b;
-  }
-  // (device time of the run, trx_stats.ms_run_total: profiled runs only -- an event record is a
-  // packet of its own between the spectrum kernel and the copy back)
-  if (prof) HIPCHK(h, hipEventRecord(ev.a, st));
-
-  h->stats.walk_steps = 0; h->stats.walk_records = 0; h->stats.walk_record_lanes = 0;
-  for (int k = 0; k < 3; k++) h->stats.walk_form_steps[k] = h->stats.walk_form_layers[k] = h->stats.walk_form_record_lanes[k] = 0;
-  std::vector<uint8_t> layer_walked((size_t)nr, 0);         // layers swept by walk steps: 1 + the form that took them (stats)
-  if (!h->has_grid && log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG) {
-    std::string ln = "run: walk frame (bins) per layer, top first; 0 = two-kernel form:";
-    for (int r = nr - 1; r >= 0; r--) ln += " " + std::to_string(walk_frame_bins(h, psmax, r));
-    log_msg(TRX_LOG_DEBUG, ln);
-  }
-  // ---- top-down sweep in steps of layers (tau.c:235-290) ----
-  int nchunks = 0, nwalks = 0, r_top = nr - 1;
-  bool stop_at_hint = stop_at_hint_ok, resumed = false;
-  int flags_host[8] = {0, 0, 0, 0, 0, 0, 0, 0}, status_host[4] = {0, 0, 0, 0};
-  std::vector<unsigned long long> counters(3 * (size_t)nr);
-  double *d_out = d_spectrum ? (double *)d_spectrum : h->d_spec.as<double>();
-  auto tau_args = [&](TauArgs &T, int r_top_, int nc_) {
-    T.nr = nr; T.solution = o->solution; T.nsh = nsh; T.lo = h->lo;
-    T.wn_i = h->wn_i; T.wn_d = h->wn_d; T.wn_fct = o->wn_fct; T.rad_fct = a->rad_fct; T.toomuch = o->toomuch;
-    T.r_top = r_top_; T.nc = nc_; T.rad = d_rad; T.e = h->d_e.as<double>(); T.ecs = h->d_ecs.as<double>();
-    T.er = h->d_er.as<double>(); T.tau = h->d_tau.as<double>(); T.last = h->d_last.as<int>();
-    T.er_all = (dbg != nullptr || eager) ? 1 : 0;
-    T.gw = d_gw; T.gstride = gstride; T.gh0 = d_gh0;
-    model_args(T);
-    T.flags = h->d_flags.as<int>(); T.eager = eager;
-    T.pw = d_pw; T.acc = h->d_acc.as<double>(); T.lay = vertical ? d_pw + 6 * (size_t)nr : nullptr;
-    T.hrs = d_pw + 4 * (size_t)nr; T.hr0 = T.hrs + nr; T.status = h->d_status.as<int>();
-  };
-  auto emis_args = [&](EmisArgs &E) {
-    E.nr = nr; E.nang = o->nangles; E.nsh = nsh; E.lo = h->lo; E.wn_i = h->wn_i; E.wn_d = h->wn_d; E.wn_fct = o->wn_fct;
-    E.tau = h->d_tau.as<double>(); E.last = h->d_last.as<int>(); E.temp = d_tempk;
-    std::vector<double> grid(o->nangles + 1);                    // eclipse.c:262-269
-    grid[0] = 0.0 * kDeg; grid[o->nangles] = 90.0 * kDeg;
-    for (int i = 1; i < o->nangles; i++) grid[i] = (o->angles_deg[i-1] + o->angles_deg[i]) * kDeg / 2.0;
-    for (int i = 0; i < o->nangles; i++) {
-      E.cosang[i] = std::cos(o->angles_deg[i] * kDeg);
-      E.area[i] = std::pow(std::sin(grid[i+1]), 2.0) - std::pow(std::sin(grid[i]), 2.0);
-      E.rcos[i] = checked_reciprocal(h, E.cosang[i]);
-    }
-    E.intens = h->d_intens.as<double>(); E.flux = d_out; E.e2tab = h->d_e2tab.as<double>();
-  };
-  auto mod_args = [&](ModArgs &M) {
-    M.nr = nr; M.modlevel = o->modlevel; M.transparent = o->transparent; M.nsh = nsh; M.toomuch = o->toomuch;
-    M.ip_fct = a->rad_fct; M.srad = o->starrad_cm; M.tau = h->d_tau.as<double>(); M.last = h->d_last.as<int>();
-    M.ip = d_ipv; M.gw = d_mw; M.gstride = gstride; M.gh0 = d_mh0; M.out = d_out; M.status = h->d_status.as<int>();
-  };
-  struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swept = 0; hipStream_t st_tau = nullptr; PendingCombine pc; };
-  SideWork pending;
-  bool early_behind_inputs = false;            // the side queue has waited for this run's input copy
-  auto run_side = [&](SideWork &S) -> int {
-    // The side queue's first work of a run waits for the inputs explicitly.  (Every step kind of today queues it behind
-    // an event recorded on the main queue after the copy -- a walk's, a sweep's -- but that is a rule nothing states.)
-    if (S.st_tau != st && !early_behind_inputs) { HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_inputs, 0)); early_behind_inputs = true; }
-    int rc = launch_combine(h, S.pc, prof ? &spans : nullptr);
-    if (rc) return rc;
-    if (S.first) {
-      if ((rc = queue_cia())) return rc;
-      lap("cia");
-      HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_cia, 0));
-    }
-    if (S.st_tau == st) { if ((rc = join_early())) return rc; }       // the optical depths of the earlier steps
-    else early_dirty = true;
-    if (!h->saved.empty())        // layers restored from an earlier run (trx_restore_extinction): their rows as they were saved
-      for (int c = 0; c < S.nc; c++) {
-        const int r = S.r_top - c;
-        if (h->saved[(size_t)r])
-          HIPCHK(h, hipMemcpyAsync(h->d_e.as<double>() + (size_t)r * nsh, h->d_e_saved.as<double>() + (size_t)r * nsh, sizeof(double) * (size_t)nsh,
-                                   hipMemcpyDeviceToDevice, S.st_tau));
-      }
-    if (prof && spans.begin(Spans::kTau, S.st_tau)) return fail(h, TRX_E_HIP, "event");
-    for (int done = 0; done < S.nc; ) {          // optical depth in sub-steps of at most tau_cap layers
-      int nt = std::min(tau_cap, S.nc - done);
-      if (S.swept == 0 && done == 0) nt = std::min(S.nc, std::max(nt, 3));
-      TauArgs T{};
-      tau_args(T, S.r_top - done, nt);
-      if (o->solution == TRX_SOL_ECLIPSE) {
-        // small shards: one wave per block spreads the (latency-bound) chains over more CUs
-        const bool small = nsh <= 64 * 1024, extras = o->scat_flag != 0 || o->cloud_flag != 0;
-        const dim3 grid((unsigned)std::min<int64_t>((nsh + (small ? 63 : 255)) / (small ? 64 : 256), kTauMaxBlocks)), block(small ? 64 : 256);
-        if (small && extras)       hipLaunchKernelGGL((k_optical_depth_vertical<true, true>), grid, block, 0, S.st_tau, T);
-        else if (small)            hipLaunchKernelGGL((k_optical_depth_vertical<true, false>), grid, block, 0, S.st_tau, T);
-        else if (extras)           hipLaunchKernelGGL((k_optical_depth_vertical<false, true>), grid, block, 0, S.st_tau, T);
-        else                       hipLaunchKernelGGL((k_optical_depth_vertical<false, false>), grid, block, 0, S.st_tau, T);
-      } else if (o->scat_flag != 0 || o->cloud_flag != 0)
-        hipLaunchKernelGGL(k_optical_depth<true>, dim3((unsigned)std::min<int64_t>((nsh + kTauW - 1) / kTauW, kTauMaxBlocks)),
-                           dim3(256), 0, S.st_tau, T);
-      else
-        hipLaunchKernelGGL(k_optical_depth<false>, dim3((unsigned)std::min<int64_t>((nsh + kTauW - 1) / kTauW, kTauMaxBlocks)),
-                           dim3(256), 0, S.st_tau, T);
-      done += nt;
-    }
-    if (prof && spans.end(S.st_tau)) return fail(h, TRX_E_HIP, "event");
-    return TRX_OK;
-  };
-  // Step plan.  Layers still to go: down to the previous spectrum's depth when it is known
-  // (retrieval loops re-run near-identical atmospheres), else to the bottom.  The step takes
-  // the layers of ONE kind from r_top down -- walk or two-kernel form -- up to that kind's cap,
-  // in equal parts when more than one step is needed.
-  auto plan_step = [&](int r_top, bool stop_at_hint, int &nb, int &nc, bool &last_step) {
-    const int swept = nr - 1 - r_top;
-    int togo = r_top + 1;
-    if (!eager && h->hint_layers > swept) togo = std::min(togo, h->hint_layers - swept);
-    nb = 0;
-    if (h->has_grid) nc = std::min(togo, user_chunk ? user_chunk : kMaxChunk);
-    else {
-      nb = walk_frame_bins(h, psmax, r_top);
-      int run = 1;                                 // consecutive layers of the same kind below r_top
-      while (run < togo && (walk_frame_bins(h, psmax, r_top - run) == 0) == (nb == 0)) run++;
-      int cap = nb ? kWalkLayers : kMaxChunk;
-      if (!nb && (2 * layer_psmax(h, psmax, std::max(0, r_top - run + 1))) / h->osamp + 1 >= 64) cap = 8;
-      if (user_chunk) cap = std::min(cap, user_chunk);
-      else if (!nb && !stop_at_hint_ok) cap = std::min(cap, 12);      // depth unknown, expensive layers: small steps
-      const int steps = (run + cap - 1) / cap;
-      nc = (run + steps - 1) / steps;
-      if (nb && steps > 1 && !user_chunk) {
-        // A walk step costs what its WIDEST layer's frame costs, whatever the number of layers
-        // (<= 64, one per lane), and frames grow with depth.  So this step takes the layers it
-        // cannot leave to the later steps, and then as many more as share their frame: the wide
-        // frames further down are paid for by as few lanes as possible.
-        const int must = run - (steps - 1) * cap;
-        int f = 0;
-        for (int c = 0; c < must; c++) f = std::max(f, walk_frame_bins(h, psmax, r_top - c));
-        nc = must;
-        while (nc < cap && nc < run && walk_frame_bins(h, psmax, r_top - nc) <= f) nc++;
-      }
-      if (nb) for (int c = 1; c < nc; c++) nb = std::max(nb, walk_frame_bins(h, psmax, r_top - c));
-    }
-    if (swept == 0) nc = std::max(nc, 3);          // the first step holds the 2- and 3-point rays (eclipse.c:65-80)
-    nc = std::min(nc, r_top + 1);
-    if (nb && swept == 0) for (int c = 1; c < nc; c++) {          // (a widened first step stays one kind)
-      const int v = walk_frame_bins(h, psmax, r_top - c);
-      if (v == 0) { nb = 0; break; }
-      nb = std::max(nb, v);
-    }
-    if (!nb && !h->has_grid && nc > sg_layers) nc = sg_layers;
-    // the plan's last step (bottom reached, or the depth the previous spectrum needed): its
-    // combine and optical depth stay on the walk's queue
-    last_step = r_top - nc < 0 || (stop_at_hint && nr - 1 - (r_top - nc) >= h->hint_layers);
-  };
-  // ---- the ray tail (trx_tail.hip.h): a hinted eclipse run whose plan is one or two walk steps from
-  // the top ends in ONE kernel behind its walks -- no side queue, no combine / optical depth /
-  // emission launches.  Decided from the plan, which a hinted run knows beforehand.
-  bool tail_mode = false;
-  TailArgs TA{};
-  if (h->ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
-      nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays) {
-    int r = nr - 1, steps = 0; bool ok = true;
-    for (; r >= 0 && ok; ) {
-      int nb_, nc_; bool last_;
-      plan_step(r, true, nb_, nc_, last_);
-      if (!nb_ || ++steps > kTailSteps) ok = false;
-      r -= nc_;
-      if (nr - 1 - r >= h->hint_layers) break;
-    }
-    tail_mode = ok && steps >= 1;
-  }
-  // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  const bool tail_direct = tail_mode && h->tail_direct, tail_spec = tail_direct && spectrum && !d_spectrum && !bs;
-  // (any run that hands its spectrum to pageable host memory stages it in the handle's pinned buffer when it is small:
-  // the copy command into pageable memory is staged by the runtime anyway, 25 us behind the copy of the flags at configs[2])
-  const bool stage_spec = spectrum && !d_spectrum && nsh <= (1 << 20);
-  if ((tail_spec || stage_spec) && h->h_spec_bytes < sizeof(double) * (size_t)nsh) {
-    if (h->h_spec) (void)hipHostFree(h->h_spec);
-    h->h_spec = nullptr; h->h_spec_bytes = 0;
-    HIPCHK(h, hipHostMalloc(&h->h_spec, sizeof(double) * (size_t)nsh, hipHostMallocDefault));
-    h->h_spec_bytes = sizeof(double) * (size_t)nsh;
-    HIPCHK(h, hipHostGetDevicePointer(&h->h_spec_dev, h->h_spec, 0));
-  }
-  // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
-  // into a pinned array, one entry per block, and the HOST adds it up behind the kernel.  The device-side sum was three
-  // dependent device-scope atomics per block and, for the last block to arrive, four more round trips and a system-scope
-  // fence: the kernel's last wave ended 5 us behind its last emission -- and every one of those fences writes back and
-  // invalidates the L2 under the emission waves (8 us of emission with them, 3 without).  The run's status (slant
-  // rays: what the reference exits on) goes into four slots behind the blocks' entries, one per code.
-  const size_t tail_blocks = (size_t)((nsh + kTailRays - 1) / kTailRays);
-  const bool tail_hostsum = tail_direct;
-  if (tail_hostsum && h->h_tailblk_bytes < 8 * tail_blocks + 16) {
-    if (h->h_tailblk) (void)hipHostFree(h->h_tailblk);
-    h->h_tailblk = nullptr; h->h_tailblk_bytes = 0;
-    HIPCHK(h, hipHostMalloc(&h->h_tailblk, 8 * tail_blocks + 16, hipHostMallocDefault));
-    h->h_tailblk_bytes = 8 * tail_blocks + 16;
-    HIPCHK(h, hipHostGetDevicePointer(&h->h_tailblk_dev, h->h_tailblk, 0));
-  }
-  int tail_nct = 0;
-  const bool two_queues = h->two_queues && tail_direct && pipelined;      // (tail_direct: nothing behind the tail on the main queue)
-  bool tail_on_side = false, cia_queued = false;
-  for (;;) {
-  {
-  for (; r_top >= 0; ) {
-    const int swept = nr - 1 - r_top;
-    int nb = 0, nc = 0; bool last_step = false;
-    plan_step(r_top, stop_at_hint, nb, nc, last_step);
-    hipStream_t st_tau = (pipelined && !last_step) ? st_early : st;
-    SideWork S;
-    bool step_walked = false;
-    S.first = nchunks == 0; S.r_top = r_top; S.nc = nc; S.swept = swept; S.st_tau = st_tau;
-    if (h->has_grid) {
-      if (prof && spans.begin(Spans::kSweep, st)) return fail(h, TRX_E_HIP, "event");
-      GridArgs Gd{};
-      Gd.o = h->d_og_o.as<double>(); Gd.nt = (int)h->og_ntemp; Gd.nm = (int)h->og_nmol; Gd.nr = nr;
-      Gd.nwave = h->og_nwave; Gd.lo = h->lo; Gd.nsh = nsh; Gd.r_top = r_top; Gd.nc = nc;
-      Gd.itemp = h->d_og_itemp.as<int>();
-      Gd.w_lo = h->d_og_layer.as<double>(); Gd.w_hi = Gd.w_lo + nr; Gd.dg = Gd.w_hi + nr; Gd.dens = Gd.dg + nr;
-      Gd.e = h->d_e.as<double>(); Gd.flags = h->d_flags.as<int>(); Gd.eager = eager;
-      hipLaunchKernelGGL(k_grid_extinction, dim3((unsigned)((nsh + 255) / 256), (unsigned)nc), dim3(256), 0, st, Gd);
-      if (prof && spans.end(st)) return fail(h, TRX_E_HIP, "event");
-    } else {
-      SweepMode M{};
-      bool walked = false; int form = 0;
-      M.eager = eager; M.prof = count; M.ethresh = o->ethresh;
-      M.skip_done = (!eager && !(dbg && dbg->e)); M.nmx = 1; M.d_iso_mx = nullptr; M.permol = false;
-      M.d_e = h->d_e.as<double>(); M.d_kmax = kmax_run; M.d_sticky = h->d_sticky.as<int>();
-      M.st = st_sweep;
-      bool all_saved = !h->saved.empty();
-      for (int c = 0; c < nc && all_saved; c++) all_saved = h->saved[(size_t)(r_top - c)] != 0;
-      if (h->ngroups > 0 && !all_saved) {
-        if (nb && tail_mode && !resumed) {
-          // (no combine of its own: its records wait for the tail, each step in its own buffer)
-          // Two walks of one run do not depend on each other, and a walk alone leaves a third of the device idle for
-          // the last third of its time: waves of one launch start together and end apart -- the oldest wave of a SIMD is
-          // served first, a step's ~13 600 ranges are under two generations of resident waves, and the kernel behind it
-          // on the queue cannot start before the last wave has ended (in-kernel clocks, round 5: 7168 waves in flight
-          // for the first 60 us of k_line_walk<2>, then 5000, 3900, 3000, 2200, 1200, 370 at 5 us steps).  The plan's
-          // second walk therefore goes to the side queue, behind the event that marks the inputs, and fills what the
-          // first one leaves; the tail follows it THERE (same queue: no signal between them) and waits for the first
-          // walk's event, long satisfied by then.  Demo: 0.269 -> 0.251 ms, the same bits.
-          const bool side_walk = two_queues && nchunks == 1;
-          if (side_walk) { HIPCHK(h, hipStreamWaitEvent(h->stream4, h->ev_inputs, 0)); M.st = h->stream4; tail_on_side = true; }
-          rc = walk_chunk(h, Y, d_wcut, nb, r_top, nc, M, prof ? &spans : nullptr, nwalks, nullptr, nullptr, nullptr, nullptr, &S.pc, &form);
-          if (!rc) {
-            TailStep &TS = TA.S[TA.nsteps++];
-            TS.P = S.pc.C.P; TS.part = S.pc.C.part; TS.nc = nc;
-            TA.skip = S.pc.C.last;
-            S.pc.valid = false;
-          }
-          nwalks++;
-        }
-        else if (nb) {
-          rc = walk_chunk(h, Y, d_wcut, nb, r_top, nc, M, prof ? &spans : nullptr, nwalks, st_tau != st ? st_tau : nullptr, h->ev_ac[nchunks],
-                          nwalks >= 2 ? h->ev_cb[(nwalks - 2) % h->ev_cb.size()] : nullptr, h->ev_cb[nwalks % h->ev_cb.size()], &S.pc, &form);
-          nwalks++;
-        }
-        else    rc = sweep_chunk(h, Y, d_wcut, psmax, r_top, nc, sg_layers, M, prof ? &spans : nullptr);
-        if (rc) return rc;
-        walked = nb != 0;
-        step_walked = walked;
-        if (walked) for (int c = 0; c < nc; c++) layer_walked[(size_t)(r_top - c)] = (uint8_t)(1 + form);
-      }
-      if (st_tau != st && !walked) {     // the optical depth of this step follows its extinction
-        HIPCHK(h, hipEventRecord(h->ev_ac[nchunks], st));
-        HIPCHK(h, hipStreamWaitEvent(st_tau, h->ev_ac[nchunks], 0));
-      }
-    }
-    lap("sweep");
-    if (tail_mode && !resumed) {
-      // the CIA kernels go to their queue behind the first walk (what the device is waiting for) -- ahead of a second
-      // walk on the side queue too: next to TWO walks they take three times as long, and configs[3]'s two tables then
-      // end after the walks.  With two queues the main one waits for them behind its walk and marks the place: one
-      // event for the tail to wait for.
-      if (!cia_queued) {
-        if ((rc = queue_cia())) return rc;
-        cia_queued = true;
-        if (two_queues && !last_step) { HIPCHK(h, hipStreamWaitEvent(st, h->ev_cia, 0)); HIPCHK(h, hipEventRecord(h->ev_walk1, st)); }
-        lap("cia");
-      }
-      r_top -= nc; nchunks++;
-      if (nr - 1 - r_top >= h->hint_layers) break;
-      continue;
-    }
-    // The rest of the step -- its combine, the CIA kernels ahead of the first optical depth, the
-    // optical depth itself -- goes to the side queue for every step but the plan's last, and is
-    // QUEUED only after the next step's walk: the walks then sit back to back on the main queue
-    // however long the host takes over the rest (small shards are host-bound otherwise).
-    if (pending.active) { if ((rc = run_side(pending))) return rc; pending.active = false; }
-    S.active = true;
-    // (walk steps only: with the two-kernel form's long steps the later queueing of an optical
-    // depth measurably delays the stop information the next step's tile skipping reads --
-    // configs[4] 0.223 -> 0.246 s)
-    if (st_tau != st && step_walked) pending = S;
-    else if ((rc = run_side(S))) return rc;
-    lap("tau");
-    r_top -= nc; nchunks++;
-    // the previous spectrum stopped here: compute the spectrum now and look at the outcome
-    // on the host (which this call waits for anyway) instead of queueing gated no-op steps
-    if (stop_at_hint && nr - 1 - r_top >= h->hint_layers) break;
-  }
-
-  if (pending.active) { if ((rc = run_side(pending))) return rc; pending.active = false; }
-
-  // ---- spectrum ---------------------------------------------------------------
-  if ((rc = join_early())) return rc;
-  if (resumed) HIPCHK(h, hipMemsetAsync(h->d_status.p, 0, 16, st));       // (a resumed run computes the spectrum a second time)
-  hipStream_t tst = st;                          // the tail's queue
-  if (tail_mode && !resumed) {
-    if (tail_on_side) { tst = h->stream4; HIPCHK(h, hipStreamWaitEvent(tst, h->ev_walk1, 0)); }
-    else {
-      if (!cia_queued) { if ((rc = queue_cia())) return rc; cia_queued = true; }
-      HIPCHK(h, hipStreamWaitEvent(st, h->ev_cia, 0));
-    }
-    TA.niso = h->niso; TA.gblock = h->d_gblock.as<int32_t>(); TA.e = h->d_e.as<double>();
-    for (int b = 0; b < h->niso && b < 64; b++) if (h->h_gblock[b] != h->h_gblock[b + 1]) TA.blocks |= 1ull << b;
-    int nct = 0;
-    for (int k = 0; k < TA.nsteps; k++) nct += TA.S[k].nc;
-    tau_args(TA.T, nr - 1, nct);
-    if (vertical) emis_args(TA.E); else mod_args(TA.M);
-    if (tail_direct) {              // spectrum and flags straight into pinned host memory: no copy commands behind the kernel
-      if (tail_spec) (vertical ? TA.E.flux : TA.M.out) = (double *)h->h_spec_dev;
-      TA.host_flags = (int *)h->h_small_dev;
-      if (tail_hostsum) {
-        TA.host_blocks = (int *)h->h_tailblk_dev;
-        std::memset((char *)h->h_tailblk + 8 * tail_blocks, 0, 16);
-        if (!vertical) TA.M.status_slots = TA.host_blocks + 2 * tail_blocks;
-      }
-      tail_nct = nct;
-    }
-    // Every address the tail reads or writes, checked on the host before the launch: a null or stale one
-    // here is a wild access of a whole grid (round 3's one memory fault -- a work-in-progress tail storing
-    // the spectrum through a pinned buffer that no branch had allocated yet -- was exactly this kind).
-    {
-      bool ok = TA.nsteps >= 1 && TA.nsteps <= kTailSteps && nct >= 3 && nct <= kTailLayers && TA.gblock && TA.e &&
-                TA.T.ecs && TA.T.er && TA.T.tau && TA.T.last && TA.T.flags && TA.T.status && TA.T.rad &&
-                (vertical ? (TA.T.acc && TA.T.lay && TA.T.gw && TA.E.flux && TA.E.intens && TA.E.temp && TA.E.e2tab)
-                          : (TA.T.hrs && TA.T.hr0 && TA.T.gw && TA.M.out && TA.M.ip && TA.M.gw && TA.M.gh0 && TA.M.status)) &&
-                (!extras_on || (TA.T.xf_scat && TA.T.xf_cloud)) && (!tail_direct || TA.host_flags) && (!tail_hostsum || TA.host_blocks);
-      for (int k = 0; k < TA.nsteps && ok; k++)
-        ok = TA.S[k].part && TA.S[k].nc >= 1 && TA.S[k].nc <= kWalkLayers && TA.S[k].P.blo && TA.S[k].P.bhi && TA.S[k].P.off && TA.S[k].P.wbase;
-      if (!ok) return fail(h, TRX_E_HIP, "internal: incomplete arguments for the ray tail (not launched)");
-    }
-    const dim3 tgrid((unsigned)((nsh + kTailRays - 1) / kTailRays)), tblock(kTailThreads);
-    if (prof && spans.begin(Spans::kTau, tst)) return fail(h, TRX_E_HIP, "event");
-    if (!vertical) {
-      if (extras_on) hipLaunchKernelGGL((k_ray_tail<0, true>), tgrid, tblock, 0, tst, TA);
-      else           hipLaunchKernelGGL((k_ray_tail<0, false>), tgrid, tblock, 0, tst, TA);
-    } else if (extras_on) {
-      if (o->nangles <= 8) hipLaunchKernelGGL((k_ray_tail<8, true>), tgrid, tblock, 0, tst, TA);
-      else                 hipLaunchKernelGGL((k_ray_tail<kMaxAngles, true>), tgrid, tblock, 0, tst, TA);
-    } else {
-      if (o->nangles <= 8) hipLaunchKernelGGL((k_ray_tail<8, false>), tgrid, tblock, 0, tst, TA);
-      else                 hipLaunchKernelGGL((k_ray_tail<kMaxAngles, false>), tgrid, tblock, 0, tst, TA);
-    }
-    if (prof && spans.end(tst)) return fail(h, TRX_E_HIP, "event");
-    if (lap_on) log_msg(TRX_LOG_DEBUG, "run: ray tail over " + std::to_string(TA.nsteps) + " walk steps, " + std::to_string(nct) + " layers");
-  }
-  else if (o->solution == TRX_SOL_ECLIPSE) {
-    EmisArgs E{};
-    emis_args(E);
-    if (h->nwn > kEmisRowsAbove)       // (by the job's grid, not the shard: all shards of a job add in the same order)
-      hipLaunchKernelGGL(k_emission_rows, dim3((unsigned)((nsh + 255) / 256)), dim3(256), 0, st, E);
-    else
-      hipLaunchKernelGGL(k_emission, dim3((unsigned)((nsh + kEmisWaves - 1) / kEmisWaves)), dim3(64 * kEmisWaves), 0, st, E);
-  } else {
-    ModArgs M{};
-    mod_args(M);
-    if (h->nwn > kEmisRowsAbove)
-      hipLaunchKernelGGL(k_modulation_rows, dim3((unsigned)((nsh + 255) / 256)), dim3(256), 0, st, M);
-    else
-      hipLaunchKernelGGL(k_modulation, dim3((unsigned)((nsh + kModWaves - 1) / kModWaves)), dim3(64 * kModWaves), 0, st, M);
-  }
-  // ---- band integrals of this pass's spectrum (trx_bands.hip.h), behind it on its queue.  A pass that resumes
-  // deeper queues them again behind its own spectrum: the sums the host reads are the last pass's.
-  if (bs && bs->nbands > 0) {
-    BandArgs BA{};
-    BA.spec = d_out; BA.bands = bs->d_bands.as<BandDev>(); BA.pieces = bs->d_pieces.as<BandPiece>();
-    BA.w = bs->d_w.as<double>(); BA.part = bs->d_part.as<double>(); BA.out = (double *)bs->h_out_dev;
-    BA.npieces = bs->npieces; BA.lo = h->lo; BA.nbands = bs->nbands; BA.wn_i = h->wn_i; BA.wn_d = h->wn_d;
-    if (!BA.spec || !BA.bands || !BA.part || !BA.out || (bs->npieces > 0 && !BA.pieces))
-      return fail(h, TRX_E_HIP, "internal: incomplete arguments for the band kernels (not launched)");
-    if (bs->npieces > 0)
-      hipLaunchKernelGGL(k_band_pieces, dim3((unsigned)((bs->npieces + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
-    hipLaunchKernelGGL(k_band_sums, dim3((unsigned)((bs->nbands + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
-    // ---- and the contribution functions of this pass's optical depths (trx_contrib.hip.h), behind them
-    if (contrib) {
-      ContribArgs CA{};
-      if (vertical) emis_args(CA.E);
-      else {                                             // (transit geometry: the grid, tau and last; no angles)
-        CA.E.nr = nr; CA.E.nang = 0; CA.E.nsh = nsh; CA.E.lo = h->lo; CA.E.wn_i = h->wn_i; CA.E.wn_d = h->wn_d; CA.E.wn_fct = o->wn_fct;
-        CA.E.tau = h->d_tau.as<double>(); CA.E.last = h->d_last.as<int>(); CA.E.temp = d_tempk; CA.E.e2tab = h->d_e2tab.as<double>();
-      }
-      CA.bands = BA.bands; CA.pieces = BA.pieces; CA.w = BA.w; CA.part = h->d_cpart.as<double>(); CA.out = (double *)h->h_contrib_dev;
-      CA.npieces = bs->npieces; CA.nbands = bs->nbands; CA.vertical = vertical ? 1 : 0;
-      const size_t rows = sizeof(double) * (size_t)nr;
-      if (!CA.E.tau || !CA.E.last || !CA.E.temp || !CA.E.e2tab || !CA.bands || !CA.part || !CA.out || (bs->npieces > 0 && !CA.pieces) ||
-          (vertical && (CA.E.nang < 1 || CA.E.nang > kMaxAngles)) || h->d_tau.bytes < rows * (size_t)nsh || h->d_last.bytes < sizeof(int) * (size_t)nsh ||
-          h->d_cpart.bytes < rows * (size_t)bs->npieces * kContribSplit || h->h_contrib_bytes < rows * (size_t)bs->nbands)
-        return fail(h, TRX_E_HIP, "internal: incomplete arguments for the contribution kernels (not launched)");
-      if (bs->npieces > 0) {
-        const dim3 cgrid((unsigned)(bs->npieces * kContribSplit), (unsigned)((nr + kContribHeights - 1) / kContribHeights));
-        if (CA.E.nang <= 8) hipLaunchKernelGGL(k_contrib_pieces<8>, cgrid, dim3(64 * kContribWaves), 0, tst, CA);
-        else                hipLaunchKernelGGL(k_contrib_pieces<kMaxAngles>, cgrid, dim3(64 * kContribWaves), 0, tst, CA);
-      }
-      hipLaunchKernelGGL(k_contrib_sums, dim3((unsigned)(((int64_t)bs->nbands * nr + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, CA);
-    }
-  }
-  HIPCHK(h, hipGetLastError());
-  if (prof) HIPCHK(h, hipEventRecord(ev.b, tst));
-
-  // ---- results back -----------------------------------------------------------
-  {   // one copy into pinned memory: flags, status and (profiled runs) the counters
-    const size_t nb = count ? 128 + 24 * (size_t)nr : 128;
-    if (!(tail_direct && !resumed)) HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small.p, nb, hipMemcpyDeviceToHost, st));
-    // (on the spectrum's queue: a band run's tail may have run on the side queue)
-    if (spectrum && !(tail_spec && !resumed)) HIPCHK(h, hipMemcpyAsync(stage_spec ? h->h_spec : (void *)spectrum, d_out, sizeof(double) * nsh, hipMemcpyDeviceToHost, tst));
-    lap("spectrum+copies");
-  }
-  t_host_queued = std::chrono::steady_clock::now();
-  }
-  {
-    const bool staged = spectrum && ((tail_spec && !resumed) || stage_spec);       // the tail stored the spectrum into the handle's pinned buffer, or the copy command did
-    if (tail_on_side && !resumed) HIPCHK(h, hipStreamSynchronize(h->stream4));      // (the tail has waited for the main queue's walk: nothing is left there)
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (staged) std::memcpy(spectrum, h->h_spec, sizeof(double) * (size_t)nsh);
-    if (tail_hostsum && !resumed) {
-      // the flags as tau_publish leaves them after the plan's last step (all of them zero but the rays' number
-      // when the tail started: it covers the run from its first layer), from the blocks' entries
-      const int32_t *tb = (const int32_t *)h->h_tailblk;
-      int still = 0, deep = 0;
-      for (size_t b = 0; b < tail_blocks; b++) { still += tb[2 * b]; deep = std::max(deep, tb[2 * b + 1]); }
-      const int f[8] = {still, 0, tail_nct, 0, deep, 0, 0, 0};
-      std::memcpy(h->h_small, f, sizeof f);
-      int st4[4] = {0, 0, 0, 0};
-      for (int code = 1; code < 4; code++) if (tb[2 * tail_blocks + code]) st4[0] = code;      // (vertical rays raise none)
-      std::memcpy((char *)h->h_small + 64, st4, 16);
-    }
-    std::memcpy(flags_host, h->h_small, sizeof(flags_host));
-    std::memcpy(status_host, (const char *)h->h_small + 64, sizeof(status_host));
-    if (count) std::memcpy(counters.data(), (const char *)h->h_small + 128, 24 * (size_t)nr);
-    else std::fill(counters.begin(), counters.end(), 0ull);
-  }
-  // rays still descending below the expected depth (the atmosphere changed): go on from there
-  if (stop_at_hint && flags_host[0] > 0 && r_top >= 0) {
-    // (the step kernels that go on from here read the flags on the device: where the host has added them up, they go there first)
-    if (tail_hostsum && !resumed) HIPCHK(h, hipMemcpyAsync(h->d_flags.p, h->h_small, 32, hipMemcpyHostToDevice, st));
-    stop_at_hint = false; resumed = true; h->hint_layers = 0; continue;
-  }
-  break;
-  }
-
-  drain.armed = false;                     // everything was joined into the main stream and waited for
+  if (R.stop_at_hint_ok && R.flags[0] > 0 && R.r_top >= 0 && (rc = R.resume())) return rc;
+  R.in_flight = false;                     // everything was joined into the main stream and waited for
   h->kmax_clean = true;
-  RunOutcome Q{};
-  std::memcpy(Q.flags, flags_host, sizeof Q.flags); std::memcpy(Q.status, status_host, sizeof Q.status);
-  Q.counters = &counters; Q.layer_walked = &layer_walked; Q.spans = prof ? &spans : nullptr; Q.ev_a = ev.a; Q.ev_b = ev.b;
-  Q.nchunks = nchunks; Q.ms_cia = ms_cia; Q.t_host0 = t_host0; Q.t_host_prep = t_host_prep; Q.t_host_queued = t_host_queued; Q.laps = &laps;
-  return run_finish(h, a, o, dbg, Q, model_args);
+  return R.finish();
 }
 
 int trx_sweep_permol(trx_handle *h, int32_t nv, const double *temp, const double *density, const double *zpart,
@@ -2955,10 +2938,9 @@ static int make_band_set(trx_handle *h, int32_t nbands, const trx_band *bands, s
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   if ((rc = upload_raw(h, S->d_bands, bd.data(), bd.size())) || (rc = upload_raw(h, S->d_pieces, pieces.data(), pieces.size())) ||
-      (rc = upload_raw(h, S->d_w, w.data(), w.size())) || (rc = ensure(h, S->d_part, sizeof(double) * 2 * (size_t)S->npieces)))
+      (rc = upload_raw(h, S->d_w, w.data(), w.size())) || (rc = ensure(h, S->d_part, sizeof(double) * 2 * (size_t)S->npieces)) ||
+      (rc = ensure_pinned(h, S->h_out, sizeof(double) * 2 * (size_t)nbands)))
     return rc;
-  HIPCHK(h, hipHostMalloc(&S->h_out, sizeof(double) * 2 * (size_t)nbands, hipHostMallocDefault));
-  HIPCHK(h, hipHostGetDevicePointer(&S->h_out_dev, S->h_out, 0));
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
   out = std::move(S);
   return TRX_OK;
@@ -2968,8 +2950,7 @@ int trx_set_bands(trx_handle *h, int32_t nbands, const trx_band *bands)
 {
   if (!h) return TRX_E_ARG;
   std::unique_ptr<BandSet> S;
-  const int rc = make_band_set(h, nbands, bands, S);
-  if (rc) return rc;
+  if (const int rc = make_band_set(h, nbands, bands, S)) return rc;
   h->bands = std::move(S);
   return TRX_OK;
 }
@@ -2980,7 +2961,7 @@ int trx_run_bands(trx_handle *h, const trx_atm *a, const trx_opts *o, double *sp
   if (!h->bands) return fail(h, TRX_E_ARG, "trx_run_bands: no band set installed (trx_set_bands)");
   if (!sums) return fail(h, TRX_E_ARG, "trx_run_bands: sums is NULL");
   const int rc = run_once(h, a, o, spectrum, nullptr, dbg, h->bands.get());
-  if (rc == TRX_OK) std::memcpy(sums, h->bands->h_out, sizeof(double) * 2 * (size_t)h->bands->nbands);
+  if (rc == TRX_OK) std::memcpy(sums, h->bands->h_out.p, sizeof(double) * 2 * (size_t)h->bands->nbands);
   return rc;
 }
 
@@ -2996,18 +2977,12 @@ int trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   const BandSet *bs = h->bands.get();
   const size_t nr = (size_t)a->nlayer, out_bytes = sizeof(double) * nr * (size_t)bs->nbands;
   HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = ensure(h, h->d_cpart, sizeof(double) * nr * (size_t)bs->npieces * kContribSplit); if (rc) return rc; }
-  if (h->h_contrib_bytes < out_bytes) {
-    if (h->h_contrib) (void)hipHostFree(h->h_contrib);
-    h->h_contrib = nullptr; h->h_contrib_dev = nullptr; h->h_contrib_bytes = 0;
-    HIPCHK(h, hipHostMalloc(&h->h_contrib, out_bytes, hipHostMallocDefault));
-    h->h_contrib_bytes = out_bytes;
-    HIPCHK(h, hipHostGetDevicePointer(&h->h_contrib_dev, h->h_contrib, 0));
-  }
-  const int rc = run_once(h, a, o, spectrum, nullptr, dbg, bs, true);
+  int rc;
+  if ((rc = ensure(h, h->d_cpart, sizeof(double) * nr * (size_t)bs->npieces * kContribSplit)) || (rc = ensure_pinned(h, h->h_contrib, out_bytes))) return rc;
+  rc = run_once(h, a, o, spectrum, nullptr, dbg, bs, true);
   if (rc == TRX_OK) {
-    std::memcpy(sums, bs->h_out, sizeof(double) * 2 * (size_t)bs->nbands);
-    std::memcpy(contrib, h->h_contrib, out_bytes);
+    std::memcpy(sums, bs->h_out.p, sizeof(double) * 2 * (size_t)bs->nbands);
+    std::memcpy(contrib, h->h_contrib.p, out_bytes);
   }
   return rc;
 }

@@ -371,7 +371,7 @@ void k_ray_tail(TailArgs A)
 
   }
 
-  // ---- results.  Waves 0..6: the emission of their ray (k_emission: lanes = heights; this run's
+  // ---- results.  Waves 0..kTailRays-1: the emission of their ray (k_emission: lanes = heights; this run's
   // optical depths from LDS); the chain wave: the rays' state and the run's flags; everybody: er and tau.
   int pub_still = 0, pub_deep = 0;                                    // (chain wave) what this block adds to the run's flags
   auto outcome = [&](int t, int &last, int &done, bool &still) {      // of ray t, from the first stopping layer
