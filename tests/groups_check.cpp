@@ -1,7 +1,8 @@
 // groups_check -- the threaded host loops of trx_create (transit_amd/csrc/trx_groups.h) against
 // one-thread loops written out here: co-added groups (extinction.c:445-462) and the per-key
 // counts, on line lists that are sparse, as dense as the fine grid, much denser than it, made of
-// many small isotope blocks, partly out of range, and with ties.  Prints "<cases> cases, <bad> differ".
+// many small isotope blocks, partly out of range, and with ties; the reductions over parts (parallel_flags,
+// parallel_minmax) against plain loops; groups_per_range at its thresholds.  Prints "<cases> cases, <bad> differ".
 #include <cstdio>
 #include <random>
 #include "trx_groups.h"
@@ -22,6 +23,38 @@ static Plain plain_groups(int64_t n, const int16_t *isoid, const double *wavn, c
     P.iso.push_back(isoid[f]); P.wv.push_back(w);
   }
   return P;
+}
+
+// the reductions of trx_create over parts of the list == one plain loop, whatever the parts
+static void check_reductions(std::mt19937_64 &rng, int &cases, int &bad)
+{
+  for (int r = 0; r < 60; r++) {
+    const int64_t n = (int64_t)(rng() % 5000);
+    std::vector<double> v((size_t)n); std::vector<uint8_t> use((size_t)n); std::vector<int> fl((size_t)n);
+    for (int64_t i = 0; i < n; i++) { v[(size_t)i] = (double)(rng() % 100000) - 50000.0; use[(size_t)i] = r % 3 == 0 ? 0 : rng() % 4 != 0; fl[(size_t)i] = rng() % 97 == 0 ? 1 + (int)(rng() % 3) : 0; }
+    int want_f = 0; double lo = HUGE_VAL, hi = -HUGE_VAL; int mx = 0;
+    for (int64_t i = 0; i < n; i++) { want_f |= fl[(size_t)i]; mx = std::max(mx, fl[(size_t)i]); if (use[(size_t)i]) { lo = std::min(lo, v[(size_t)i]); hi = std::max(hi, v[(size_t)i]); } }
+    for (int nth : {1, 2, 3, 16})
+      for (int64_t grain : {(int64_t)65536, (int64_t)64, (int64_t)1}) {
+        cases++;
+        const int got_f = trx::parallel_flags(n, nth, [&](int64_t i0, int64_t i1) { int b = 0; for (int64_t i = i0; i < i1; i++) b |= fl[(size_t)i]; return b; }, grain);
+        const trx::MinMax<double> m = trx::parallel_minmax<double>(n, nth, HUGE_VAL, -HUGE_VAL, [&](int64_t i, bool &u) { u = use[(size_t)i]; return v[(size_t)i]; }, grain);
+        const int got_mx = trx::parallel_minmax<int>(n, nth, 0, 0, [&](int64_t i, bool &) { return fl[(size_t)i]; }, grain).hi;
+        if (got_f != want_f || m.lo != lo || m.hi != hi || got_mx != mx) { bad++; std::printf("reductions differ: round %d n %lld threads %d grain %lld\n", r, (long long)n, nth, (long long)grain); }
+      }
+  }
+  // groups per range: 32, then up to 64 past 16384 ranges, then up to 512 past 131072
+  const struct { int64_t ng; int want; } at[] = {{0, 32}, {1, 32}, {32LL * 16385 - 1, 32}, {32LL * 16385, 64}, {64LL * 131073 - 1, 64}, {64LL * 131073, 128},
+      {128LL * 131073 - 1, 128}, {128LL * 131073, 256}, {256LL * 131073 - 1, 256}, {256LL * 131073, 512}, {2000000000LL, 512}};
+  for (const auto &a : at) { cases++; if (trx::groups_per_range(a.ng) != a.want) { bad++; std::printf("groups_per_range(%lld) = %d, not %d\n", (long long)a.ng, trx::groups_per_range(a.ng), a.want); } }
+  for (int r = 0; r < 2000; r++) {
+    const int64_t ng = (int64_t)(rng() % (1ULL << (10 + r % 22)));
+    int w = 32;
+    if (ng / 32 > 16384) w = 64;
+    while (w >= 64 && w < 512 && ng / w > 131072) w *= 2;
+    cases++;
+    if (trx::groups_per_range(ng) != w) { bad++; std::printf("groups_per_range(%lld) = %d, not %d\n", (long long)ng, trx::groups_per_range(ng), w); }
+  }
 }
 
 int main(int argc, char **argv)
@@ -83,6 +116,7 @@ int main(int argc, char **argv)
       if (cases > 4000 * (r + 1)) break;
     }
   }
+  check_reductions(rng, cases, bad);
   std::printf("%d cases, %d differ\n", cases, bad);
   return bad != 0;
 }

@@ -4,6 +4,7 @@ import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,3 +61,50 @@ def test_step_plan_holds_what_its_consumers_rely_on(tmp_path):
     out = subprocess.run([exe, "20000"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout
     assert "20000 cases, 0 differ" in out.stdout
+
+
+@pytest.fixture(scope="module")
+def table_check(tmp_path_factory):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path_factory.mktemp("table_check") / "table_check")
+    subprocess.run([gxx, "-O2", "-Wall", "-I", os.path.join(ROOT, "transit_amd", "csrc"),
+                    "-o", exe, os.path.join(ROOT, "tests", "table_check.cpp")], check=True)
+    return exe
+
+
+def test_table_layouts_hold_what_their_readers_rely_on(table_check):
+    """The Voigt table's plan and the layouts of its three copies (transit_amd/csrc/trx_table.h) on seeded random
+    grids (tests/table_check.cpp): profiles tile the table; aliases share everything with the entry a Doppler row
+    above; rows of distinct jobs are disjoint in every copy; the walk's rows, descriptors and the compact rows are
+    what the kernels assume; the limits that switch a copy off; the nearest-index thresholds against
+    nearest_index itself."""
+    out = subprocess.run([table_check, "2000"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout
+    assert "2000 cases, 0 differ" in out.stdout
+
+
+@pytest.mark.parametrize("case", ["eclipse_small", "coadd_thresh", "midres_os4", "highres_fine"])
+def test_table_plan_is_the_oracles(table_check, case):
+    """psize, poff, the total and both width grids of trx_table.h's plan == the oracle's table, exactly: goldens
+    with osamp 2160, 24, 4 and 1, which between them hold rows of every class and 1270 aliases of 3600 entries."""
+    import oracle_lib as ol
+    from cases import GOLDEN
+    from transit_amd.host import Problem
+    P = Problem.from_cfg(os.path.join(GOLDEN, case, "case.cfg"))
+    st = P.static
+    args = [st.ndop, st.nlor, repr(st.dmin), repr(st.dmax), repr(st.lmin), repr(st.lmax), repr(st.timesalpha),
+            repr(st.wn_d), st.osamp, st.nown]
+    out = subprocess.run([table_check, "grid"] + [str(a) for a in args], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout
+    got = {ln.split()[0]: ln.split()[1:] for ln in out.stdout.splitlines()}
+    ora = ol.OracleEngine(st)
+    ps, off, tab = ora.table()
+    adop, alor = ora.width_grids()
+    ora.close()
+    assert int(got["total"][0]) == tab.size
+    assert np.array_equal(np.array(got["psize"], dtype=np.int64), ps.ravel())
+    assert np.array_equal(np.array(got["poff"], dtype=np.int64), off.ravel())
+    assert np.array_equal(np.array([float.fromhex(x) for x in got["adop"]]), adop)
+    assert np.array_equal(np.array([float.fromhex(x) for x in got["alor"]]), alor)

@@ -39,6 +39,7 @@
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 #include "../trx_plan.h"
+#include "../trx_table.h"
 
 using namespace trx;
 
@@ -69,6 +70,31 @@ struct BandSet {
   int32_t nbands = 0; int64_t npieces = 0;
   DevBuf d_bands, d_pieces, d_w, d_part;             // BandDev[nbands], BandPiece[npieces], WEIGHTS' in-shard weights, [npieces][2]
   PinnedBuf h_out;                                   // [nbands][2]: k_band_sums stores the run's sums here
+};
+
+// The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
+// alone, before any stage.  Each selects between two forms of the same computation that give the same
+// bits (the tests named compare them side by side); none is needed in production, none changes a result.
+// (The A/B switches of forms that lost -- run graphs, the range size, tile-size tuning beyond what a
+// test forces -- are gone with those forms.)
+struct Switches {
+  bool no_row_copy = false;         // TRX_NO_ROW_COPY: wide frames without the walk's row copy (test_gpu_properties)
+  bool no_rows32 = false;           // TRX_NO_ROWS32: k_line_walk_lanes<8> on the 64-byte rows (test_gpu_lanes)
+  bool row_staging = true;          // osamp == 1: wide profiles through k_accumulate_rows (TRX_NO_ROW_STAGING: k_accumulate_wide; test_gpu_rows)
+  long long row_m8_from = 768;      // ... profile width (bins) from which a layer's tiles are 512 bins (TRX_ROWS_M8_FROM: test_gpu_rows, measurements)
+  bool packed_walk = true; int packed_max_layers = 10;   // steps of few layers walk several ranges per wave (TRX_NO_PACKED_WALK: never; TRX_PACKED_MAX_LAYERS: up to N layers, 1..32; test_gpu_packed)
+  int xcd_map = 1;                  // TRX_XCD_MAP: blocks -> ranges by XCD (xcd_block): bit 0 k_line_walk_lanes, bit 1 k_line_walk (measured: slower there)
+  bool no_binrec = false;           // TRX_NO_BINREC: k_ray_tail finds a bin's records through the ranges' numbers (A/B, tests)
+  // steps of at most 32 layers with frames of 8+ bins: lanes = lines for the strengths (trx_lanes.hip.h)
+  bool lanes_walk = true, lanes_force = false;      // TRX_LANES_WALK=0: the one-range / packed forms; =2: also on sparse lists (test_gpu_lanes)
+  int lanes_parts_most = 4;         // TRX_LANES_PARTS: k_line_walk_lanes with at most 2, 3 or 4 lanes per layer in phase 2 (test_gpu_lanes_parts)
+  bool ray_tail = true;             // hinted eclipse runs end in k_ray_tail (TRX_RAY_TAIL=0: the step kernels; test_gpu_tail, measurements)
+  bool cia_sums = true;             // the CIA splines' second derivatives as sums per row (TRX_CIA_SUMS=0: the sweeps of k_cia_layers; tests)
+  bool cia_segments = true;         // k_cia_layers in pieces of 128 rows (TRX_CIA_SEGMENTS=0: one sweep per table; test_gpu_cia_window)
+  bool cia_window = true;           // the CIA spline solved for the table rows a run needs (TRX_CIA_WINDOW=0: the whole table; test_gpu_cia_window)
+  bool two_queues = true;           // the second walk of a hinted run on a queue of its own, next to the first (TRX_TWO_QUEUES=0: behind it; A/B, tests)
+  bool tail_direct = true;          // ... which writes spectrum and flags straight into pinned host memory (TRX_TAIL_DIRECT=0: copy commands)
+  bool shard_frames = true;         // frames sized for the Doppler indices the lines in reach can take (TRX_SHARD_FRAMES=0: for the isotope's whole wavenumber range; test_gpu_shard_frames)
 };
 
 }  // namespace
@@ -110,24 +136,9 @@ struct trx_handle {
   // the walk's copy: phase-major rows of whole cache lines (walk_row_layout), one WalkProfile per table entry
   DevBuf d_tabW, d_walkprof; const float *tabW = nullptr; bool tabw_ok = false;
   DevBuf d_tabW32, d_wp32; const float *tabW32 = nullptr; unsigned slab32 = 0;      // compact 32-byte rows for frames of 8 bins (k_table_rows32)
-  long long row_m8_from = 768;      // profile width (bins) from which a layer's tiles are 512 bins (TRX_ROWS_M8_FROM: measurements)
   std::vector<std::pair<double, double>> recip_ok;     // divisors whose reciprocal quotient_rn may use (checked_reciprocal)
-  bool shard_frames = true;                              // frames sized for the Doppler indices the lines in reach can take (TRX_SHARD_FRAMES=0: for the isotope's whole wavenumber range)
-  bool cia_window = true;                                // the CIA spline solved for the table rows a run needs, not the whole table (TRX_CIA_WINDOW=0)
-  bool cia_sums = true;                                  // the CIA splines' second derivatives as sums per row (TRX_CIA_SUMS=0: the sweeps of k_cia_layers; tests)
-  bool cia_segments = true;                              // k_cia_layers in pieces of 128 rows (TRX_CIA_SEGMENTS=0: one sweep per table; tests)
-  bool two_queues = true;                                // the second walk of such a run on a queue of its own, next to the first (TRX_TWO_QUEUES=0: behind it)
-  bool tail_direct = true;                               // ... which writes spectrum and flags straight into pinned host memory (TRX_TAIL_DIRECT=0: copy commands)
-  bool ray_tail = true;                                  // hinted eclipse runs end in k_ray_tail (TRX_RAY_TAIL=0: the step kernels; tests, measurements)
-  bool packed_walk = true; int packed_max_layers = 10;   // steps of few layers walk several ranges per wave (TRX_NO_PACKED_WALK, TRX_PACKED_MAX_LAYERS: tests, measurements)
-  // steps of at most 32 layers with frames of 8+ bins: lanes = lines for the strengths (trx_lanes.hip.h; TRX_LANES_WALK=0:
-  // the one-range / packed forms)
-  bool no_binrec = false;                            // TRX_NO_BINREC: k_ray_tail finds a bin's records through the ranges' numbers (A/B, tests)
-  int xcd_map = 1;                                   // blocks -> ranges by XCD (xcd_block): bit 0 k_line_walk_lanes, bit 1 k_line_walk (measured: slower there).  TRX_XCD_MAP, A/B
-  bool lanes_walk = true, lanes_force = false; int max_gcount = 0; DevBuf d_linebase, d_rinfo;   // (TRX_LANES_WALK=2: also on sparse lists, tests)
-  int lanes_parts_most = 4;                          // k_line_walk_lanes: at most this many lanes per layer in phase 2 (TRX_LANES_PARTS, tests)
-  bool no_row_copy = false, no_rows32 = false;
-  bool row_staging = true;          // osamp == 1: wide profiles through k_accumulate_rows (TRX_NO_ROW_STAGING at create: tests compare the two forms)
+  int max_gcount = 0; DevBuf d_linebase, d_rinfo;      // the largest co-added group; what k_line_walk_lanes reads per line and per range (trx_lanes.hip.h)
+  Switches sw;
   // lines
   int64_t nlines = 0, ngroups = 0, nadd = 0, ninrange = 0;
   DevBuf d_lgroup, d_wavn, d_elow, d_gf, d_iso, d_inr, d_gfirst, d_gcount, d_giown, d_giso, d_gwavn, d_gblock, d_cntge, d_cntsub;
@@ -264,278 +275,166 @@ int upload(trx_handle *h, DevBuf &b, const std::vector<T> &v)
 template <class T>
 int upload(trx_handle *h, DevBuf &b, const HostBuf<T> &v) { return upload_raw(h, b, v.data(), v.size()); }
 
-// pu/src/iomisc.c:1064-1083 (logspace)
-void logspace(double lo, double hi, int n, std::vector<double> &out)
+// The one place the handle's switches are read (struct Switches); trx_create calls it before any stage.
+void read_switches(Switches &w)
 {
-  out.resize(n + 1);
-  const double l0 = std::log10(lo), l1 = std::log10(hi);
-  const double step = (l1 - l0) / (n - 1.0);
-  for (int i = 0; i < n; i++) out[i] = std::pow(10, l0 + i * step);
-  out[n] = HUGE_VAL;   // the reference searches with hi = n (extinction.c:393-394)
+  auto set = [](const char *name) { return std::getenv(name) != nullptr; };
+  auto num = [](const char *name, long long otherwise) { const char *e = std::getenv(name); return e ? std::atoll(e) : otherwise; };
+  auto clamped = [&](const char *name, int lo, int hi, int otherwise) { return (int)std::max<long long>(lo, std::min<long long>(hi, num(name, otherwise))); };
+  w.no_row_copy = set("TRX_NO_ROW_COPY");
+  w.no_rows32 = set("TRX_NO_ROWS32");
+  w.row_staging = !set("TRX_NO_ROW_STAGING");
+  w.row_m8_from = num("TRX_ROWS_M8_FROM", w.row_m8_from);
+  w.packed_walk = !set("TRX_NO_PACKED_WALK");
+  w.packed_max_layers = clamped("TRX_PACKED_MAX_LAYERS", 1, 32, w.packed_max_layers);
+  w.xcd_map = (int)num("TRX_XCD_MAP", w.xcd_map);
+  w.no_binrec = set("TRX_NO_BINREC");
+  const long long lanes = num("TRX_LANES_WALK", 1);
+  w.lanes_walk = lanes != 0; w.lanes_force = lanes == 2;
+  w.lanes_parts_most = clamped("TRX_LANES_PARTS", 2, 4, w.lanes_parts_most);
+  w.ray_tail = num("TRX_RAY_TAIL", 1) != 0;
+  w.cia_sums = num("TRX_CIA_SUMS", 1) != 0;
+  w.cia_segments = num("TRX_CIA_SEGMENTS", 1) != 0;
+  w.cia_window = num("TRX_CIA_WINDOW", 1) != 0;
+  w.two_queues = num("TRX_TWO_QUEUES", 1) != 0;
+  w.tail_direct = num("TRX_TAIL_DIRECT", 1) != 0;
+  w.shard_frames = num("TRX_SHARD_FRAMES", 1) != 0;
 }
 
-// ---- Voigt table plan: opacity.c:219-277 + extinction.c:8-57 ---------------
-int plan_table(trx_handle *h, const trx_static *s, std::vector<ProfileJob> &jobs)
+// ---- the Voigt table: plan and layouts in ../trx_table.h; here the uploads and the kernels ----
+struct TableBuild { TablePlan P; DevBuf d_jobs; };      // (d_jobs: read by every table kernel, alive until build_table's last synchronisation)
+
+// fn(first job, jobs) over the jobs in batches of 32768 (gridDim.y)
+template <class F>
+void for_job_batches(const std::vector<ProfileJob> &jobs, F fn)
 {
-  const int nd = s->ndop, nl = s->nlor;
-  logspace((double)s->dmin, (double)s->dmax, nd, h->adop);
-  logspace((double)s->lmin, (double)s->lmax, nl, h->alor);
-  h->psize.assign((size_t)nd * nl, 0); h->poff.assign((size_t)nd * nl, 0);
-  const double dwn = s->wn_d / s->osamp;
-  int64_t total = 0, bins = 0;
-  for (int i = 0; i < nd; i++)
-    for (int j = 0; j < nl; j++) {
-      const size_t k = (size_t)i * nl + j;
-      if (h->adop[i] * 10.0 < h->alor[j] && i != 0) {         // opacity.c:262-265
-        h->psize[k] = h->psize[k - nl]; h->poff[k] = h->poff[k - nl];
-        continue;
-      }
-      const float dop = (float)h->adop[i], lor = (float)h->alor[j];   // extinction.c:11-12
-      double big = dop; if (big < lor) big = lor;
-      const double wv = big * s->timesalpha;
-      int nv = 2 * (long)(wv / dwn + 0.5) + 1;
-      if (nv < 2) nv = 3;
-      if (nv > 2 * (int)s->nown) nv = 2 * (int)s->nown + 1;
-      if (nv < 0) return fail(h, TRX_E_ARG, "negative Voigt profile size");
-      ProfileJob J{};
-      J.off = total; J.nv = nv; J.alphaL = lor; J.alphaD = dop;
-      J.half = dwn * (long)(nv / 2);
-      const bool quick = nv > 99999;                            // voigt.c:109, extinction.c:51
-      // voigt.c:399-433
-      double step = 2.0 * J.half / (nv - 1);
-      int npts = 50; double sub = J.alphaD / (npts - 1);
-      if (step < sub || quick) { sub = step; J.regime = quick ? 0 : 1; J.m = 1; }
-      else {
-        npts = (int)(step / sub) + 1;
-        if (npts & 1) npts++;
-        J.m = npts; J.regime = 2;
-        const long long tot = (long long)nv * npts + 1;
-        if (tot > 2000000000LL) return fail(h, TRX_E_UNSUPPORTED, "Voigt sub-sampling exceeds int range");
-        sub = 2.0 * J.half / (double)(tot - 1);
-      }
-      J.sub = sub; J.first_bin = bins;
-      jobs.push_back(J);
-      h->psize[k] = nv / 2; h->poff[k] = total;
-      total += nv; bins += nv;
-    }
-  h->tab_n = total;
+  for (size_t j0 = 0; j0 < jobs.size(); j0 += 32768) fn(j0, (int)std::min<size_t>(32768, jobs.size() - j0));
+}
+
+// the plan into the handle; the thresholds of the two width grids
+int plan_into_handle(trx_handle *h, const trx_static *s, TableBuild &B)
+{
+  const char *text = "";
+  const TablePlanError pe = plan_table(*s, B.P, &text);
+  if (pe != kTablePlanOk) return fail(h, pe == kTablePlanArg ? TRX_E_ARG : TRX_E_UNSUPPORTED, text);
+  h->adop = B.P.adop; h->alor = B.P.alor; h->psize = B.P.psize; h->poff = B.P.poff; h->tab_n = B.P.tab_n;
+  h->psizeT = std::move(B.P.psizeT); h->psize_mono = B.P.psize_mono;
+  // the steps of the nearest-index function (index_steps): the Doppler grid's go to the kernels (index_from) and must
+  // exist; the Lorentz grid's serve the host's prologue (prep_layers), and a grid that fails the check keeps nearest_index
+  if (!index_steps(h->adop.data(), s->ndop, h->dopthr)) return fail(h, TRX_E_ARG, "Doppler-width grid is not strictly increasing");
+  if (!index_steps(h->alor.data(), s->nlor, h->lorthr)) h->lorthr.clear();
   return TRX_OK;
 }
 
-// Environment variables read at trx_create -- ALL of them, in one place.  Each selects between two forms
-// of the same computation that give the same bits (the tests named compare them side by side); none is
-// needed in production, none changes a result.  (The A/B switches of forms that lost -- run graphs, the
-// range size, tile-size tuning beyond what a test forces -- are gone with those forms.)
-void test_switches(trx_handle *h)
+// constants, the job list, the zeroed table and the entry arrays, in the order they have always gone up
+int upload_table_inputs(trx_handle *h, const trx_static *s, TableBuild &B)
 {
-  h->no_row_copy = std::getenv("TRX_NO_ROW_COPY") != nullptr;              // wide frames without the row copy (test_gpu_properties)
-  h->no_rows32 = std::getenv("TRX_NO_ROWS32") != nullptr;                  // k_line_walk_lanes<8> on the 64-byte rows (test_gpu_lanes)
-  h->row_staging = !std::getenv("TRX_NO_ROW_STAGING");                      // k_accumulate_wide instead of k_accumulate_rows (test_gpu_rows)
-  if (const char *v = std::getenv("TRX_ROWS_M8_FROM")) h->row_m8_from = std::atoll(v);      // ... and its tile size per layer (test_gpu_rows)
-  h->packed_walk = !std::getenv("TRX_NO_PACKED_WALK");                      // k_line_walk_packed never / for steps of up to N layers (test_gpu_packed)
-  if (const char *v = std::getenv("TRX_PACKED_MAX_LAYERS")) h->packed_max_layers = std::max(1, std::min(32, std::atoi(v)));
-  if (const char *e = std::getenv("TRX_XCD_MAP")) h->xcd_map = std::atoi(e);
-  h->no_binrec = std::getenv("TRX_NO_BINREC") != nullptr;
-  if (const char *e = std::getenv("TRX_LANES_WALK")) { h->lanes_walk = std::atoi(e) != 0; h->lanes_force = std::atoi(e) == 2; }      // k_line_walk_lanes never / also on sparse lists (test_gpu_lanes)
-  if (const char *e = std::getenv("TRX_LANES_PARTS")) h->lanes_parts_most = std::max(2, std::min(4, std::atoi(e)));      // ... with at most 2, 3 or 4 lanes per layer (test_gpu_lanes_parts)
-  if (const char *e = std::getenv("TRX_RAY_TAIL")) h->ray_tail = std::atoi(e) != 0;            // the step kernels instead of k_ray_tail (test_gpu_tail)
-  if (const char *e = std::getenv("TRX_CIA_SUMS")) h->cia_sums = std::atoi(e) != 0;
-  if (const char *e = std::getenv("TRX_CIA_SEGMENTS")) h->cia_segments = std::atoi(e) != 0;  // the CIA splines' second derivatives in one sweep per table (test_gpu_cia_window)
-  if (const char *e = std::getenv("TRX_TWO_QUEUES")) h->two_queues = std::atoi(e) != 0;       // the walks of a hinted run one behind the other (A/B, tests)
-  if (const char *e = std::getenv("TRX_TAIL_DIRECT")) h->tail_direct = std::atoi(e) != 0;      // ... copy commands instead of stores into pinned memory
-  if (const char *e = std::getenv("TRX_CIA_WINDOW")) h->cia_window = std::atoi(e) != 0;        // the CIA spline over the whole table (test_gpu_cia_window)
-  if (const char *e = std::getenv("TRX_SHARD_FRAMES")) h->shard_frames = std::atoi(e) != 0;    // a shard with the list's frames (test_gpu_shard_frames)
-}
-
-int build_table(trx_handle *h, const trx_static *s)
-{
-  std::vector<ProfileJob> jobs;
-  int rc = plan_table(h, s, jobs);
-  if (rc) return rc;
+  int rc;
   // series coefficients 1/(n!(2n+1)), voigt.c:45-108
   double coef[64]; long double fact = 1.0L;
   for (int n = 0; n < 64; n++) { if (n > 0) fact *= (long double)n; coef[n] = (double)(1.0L / (fact * (long double)(2 * n + 1))); }
   HIPCHK(h, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_voigt_coef), coef, sizeof(coef), 0, hipMemcpyHostToDevice, h->stream));
-  DevBuf d_jobs;
-  if ((rc = upload(h, d_jobs, jobs))) return rc;
-  // (behind the table: kWalkMaxFrame cells of zeros, where the walk's lanes read what a slot does not reach)
-  // (and kRowTail more: k_accumulate_rows stages whole 256-float pieces of a row, trx_rows.hip.h)
-  const size_t tab_alloc = (size_t)h->tab_n + 2 * kTabPad + (size_t)kWalkMaxFrame * (size_t)std::min<int64_t>(s->osamp, 1 << 21) + kRowTail;
+  if ((rc = upload(h, B.d_jobs, B.P.jobs))) return rc;
+  const size_t tab_alloc = table_alloc_floats(h->tab_n, s->osamp);
   if ((rc = ensure(h, h->d_tab, sizeof(float) * tab_alloc))) return rc;
   HIPCHK(h, hipMemsetAsync(h->d_tab.p, 0, sizeof(float) * tab_alloc, h->stream));
   h->tab = h->d_tab.as<float>() + kTabPad;
-  std::vector<int32_t> ps32(h->psize.begin(), h->psize.end());
-  if ((rc = upload(h, h->d_psize, ps32))) return rc;
-  if ((rc = upload(h, h->d_poff, h->poff))) return rc;
-  if ((rc = upload(h, h->d_adop, h->adop))) return rc;
-  {
-    // exact steps of the nearest-index function on the Doppler grid (index_from in the
-    // kernels): thr[k] = smallest double v with nearest_index(adop, v, 0, ndop) >= k,
-    // found by bisection on the bit patterns of the (positive) doubles
-    const int nd = s->ndop;
-    std::vector<double> thr((size_t)nd + 1);
-    thr[0] = -HUGE_VAL; thr[nd] = HUGE_VAL;
-    auto idx = [&](double v) { return nearest_index(h->adop.data(), v, 0, nd); };
-    for (int k = 1; k < nd; k++) {
-      uint64_t a, b; double x;
-      std::memcpy(&a, &h->adop[k - 1], 8); std::memcpy(&b, &h->adop[k], 8);      // idx(a) < k <= idx(b)
-      while (b - a > 1) {
-        const uint64_t m = a + (b - a) / 2;
-        std::memcpy(&x, &m, 8);
-        if (idx(x) >= k) b = m; else a = m;
-      }
-      std::memcpy(&thr[k], &b, 8);
-      if (idx(thr[k]) != k || idx(std::nextafter(thr[k], 0.0)) != k - 1)
-        return fail(h, TRX_E_ARG, "Doppler-width grid is not strictly increasing");
-    }
-    if ((rc = upload(h, h->d_dopthr, thr))) return rc;
-    h->dopthr = thr;
-    {   // the Lorentz grid's steps, for the host's prologue (prep_layers): the same bisection; a grid that fails the check keeps nearest_index
-      const int nl = s->nlor;
-      std::vector<double> lt((size_t)nl + 1);
-      lt[0] = -HUGE_VAL; lt[nl] = HUGE_VAL;
-      auto lidx = [&](double v) { return nearest_index(h->alor.data(), v, 0, nl); };
-      bool ok = true;
-      for (int k = 1; k < nl && ok; k++) {
-        uint64_t a, b; double x;
-        if (!(h->alor[k - 1] > 0) || !(h->alor[k] > h->alor[k - 1])) { ok = false; break; }
-        std::memcpy(&a, &h->alor[k - 1], 8); std::memcpy(&b, &h->alor[k], 8);
-        while (b - a > 1) {
-          const uint64_t m = a + (b - a) / 2;
-          std::memcpy(&x, &m, 8);
-          if (lidx(x) >= k) b = m; else a = m;
-        }
-        std::memcpy(&lt[k], &b, 8);
-        ok = lidx(lt[k]) == k && lidx(std::nextafter(lt[k], 0.0)) == k - 1;
-      }
-      if (ok) h->lorthr = lt; else h->lorthr.clear();
-    }
-    h->psizeT.resize((size_t)nd * h->nlor); h->psize_mono = true;
-    for (int d = 0; d < nd; d++)
-      for (int l = 0; l < h->nlor; l++) {
-        h->psizeT[(size_t)l * nd + d] = h->psize[(size_t)d * h->nlor + l];
-        if (d > 0 && h->psize[(size_t)d * h->nlor + l] < h->psize[(size_t)(d - 1) * h->nlor + l]) h->psize_mono = false;
-      }
-    std::vector<double> e2(64);                       // 2^(j/64) for exp_neg (kernels)
-    for (int j = 0; j < 64; j++) e2[j] = (double)exp2l((long double)j / 64.0L);
-    if ((rc = upload(h, h->d_e2tab, e2))) return rc;
-  }
-  hipEvent_t e0, e1;
-  HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-  HIPCHK(h, hipEventRecord(e0, h->stream));
+  if ((rc = upload(h, h->d_psize, h->psize)) || (rc = upload(h, h->d_poff, h->poff)) || (rc = upload(h, h->d_adop, h->adop)) ||
+      (rc = upload(h, h->d_dopthr, h->dopthr))) return rc;
+  std::vector<double> e2(64);                       // 2^(j/64) for exp_neg (kernels)
+  for (int j = 0; j < 64; j++) e2[j] = (double)exp2l((long double)j / 64.0L);
+  return upload(h, h->d_e2tab, e2);                 // (pageable: the copy has left e2 when the call returns)
+}
+
+void table_kernels(trx_handle *h, const TableBuild &B)
+{
   const int m_limit = 64;
-  for (size_t j0 = 0; j0 < jobs.size(); j0 += 32768) {
-    const int nj = (int)std::min<size_t>(32768, jobs.size() - j0);
+  const std::vector<ProfileJob> &jobs = B.P.jobs;
+  for_job_batches(jobs, [&](size_t j0, int nj) {
     int maxnv = 0; bool any_wave = false;
     for (int j = 0; j < nj; j++) { maxnv = std::max(maxnv, jobs[j0 + j].nv); any_wave |= (jobs[j0 + j].regime == 2 && jobs[j0 + j].m > m_limit); }
     const int gx = std::max(1, std::min(64, (maxnv + 255) / 256));
-    hipLaunchKernelGGL(k_voigt_bins, dim3(gx, nj), dim3(256), 0, h->stream,
-                       d_jobs.as<ProfileJob>() + j0, h->tab, m_limit);
+    hipLaunchKernelGGL(k_voigt_bins, dim3(gx, nj), dim3(256), 0, h->stream, B.d_jobs.as<ProfileJob>() + j0, h->tab, m_limit);
     if (any_wave)
       hipLaunchKernelGGL(k_voigt_bins_wave, dim3(std::max(1, std::min(256, maxnv)), nj), dim3(64), 0, h->stream,
-                         d_jobs.as<ProfileJob>() + j0, h->tab, m_limit);
-  }
-  // phase-major copy for the wide-profile kernel (identical layout when osamp == 1)
-  if (s->osamp == 1) { h->tabT = h->tab; h->poffT = h->d_poff.as<long long>(); }
-  else {
-    std::vector<long long> joffT(jobs.size()), poffT((size_t)s->ndop * s->nlor, 0);
-    long long totT = 0;
-    for (size_t j = 0; j < jobs.size(); j++) { joffT[j] = totT; totT += (long long)s->osamp * ((jobs[j].nv - 1) / s->osamp + 1); }
-    {   // table entries -> job (aliases share the job of the row above)
-      size_t j = 0;
-      for (int i = 0; i < s->ndop; i++)
-        for (int k = 0; k < s->nlor; k++) {
-          const size_t e = (size_t)i * s->nlor + k;
-          if (h->adop[i] * 10.0 < h->alor[k] && i != 0) poffT[e] = poffT[e - s->nlor];
-          else poffT[e] = joffT[j++];
-        }
-    }
-    DevBuf d_joffT;
-    if ((rc = upload(h, d_joffT, joffT)) || (rc = upload(h, h->d_poffT, poffT))) return rc;
-    if ((rc = ensure(h, h->d_tabT, sizeof(float) * ((size_t)totT + 2 * kTabPad)))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_tabT.p, 0, sizeof(float) * ((size_t)totT + 2 * kTabPad), h->stream));
-    for (size_t j0 = 0; j0 < jobs.size(); j0 += 32768) {
-      const int nj = (int)std::min<size_t>(32768, jobs.size() - j0);
-      hipLaunchKernelGGL(k_table_phase_major, dim3(32, nj), dim3(256), 0, h->stream, d_jobs.as<ProfileJob>() + j0,
-                         d_joffT.as<long long>() + j0, h->tab, h->d_tabT.as<float>() + kTabPad, s->osamp, 0);
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->tabT = h->d_tabT.as<float>() + kTabPad; h->poffT = h->d_poffT.as<long long>();
-  }
-  // The walk's copy (trx_walk.hip.h): phase-major rows, each between zeros (walk_row_layout) -- the
-  // bins of a frame are CONSECUTIVE entries of one row, and what a narrow profile does not reach
-  // is zero by position (the pad behind a row is also the pad in front of the next).  One
-  // descriptor per table entry.  32-bit byte offsets: no copy when it would pass 4 GB (walk_chunk).
-  {
-    std::vector<long long> joffW(jobs.size());
-    long long totW = 0;
-    for (size_t j = 0; j < jobs.size(); j++) {
-      int front, stride; walk_row_layout((jobs[j].nv - 1) / s->osamp + 1, front, stride);
-      joffW[j] = totW; totW += (long long)s->osamp * stride;
-    }
-    test_switches(h);
-    h->tabw_ok = 4 * (totW + 2 * (long long)kTabPad) < (1LL << 32) && !h->no_row_copy;
-    if (h->tabw_ok) {
-      std::vector<WalkProfile> desc((size_t)s->ndop * s->nlor);
-      size_t j = 0;
-      for (int i = 0; i < s->ndop; i++)
-        for (int k = 0; k < s->nlor; k++) {
-          const size_t e = (size_t)i * s->nlor + k;
-          if (h->adop[i] * 10.0 < h->alor[k] && i != 0) { desc[e] = desc[e - s->nlor]; continue; }
-          const long long ps = h->psize[e], K = (2 * ps) / s->osamp + 1;
-          int front, stride; walk_row_layout((int)K, front, stride);
-          desc[e].centre4 = (uint32_t)(4 * (joffW[j++] + front + ps / s->osamp));
-          desc[e].rowb = (int32_t)(4 * stride);
-          desc[e].psr = (int32_t)(ps % s->osamp);
-          desc[e].ps = (int32_t)ps;
-        }
-      DevBuf d_joffW;
-      if ((rc = upload(h, d_joffW, joffW)) || (rc = upload(h, h->d_walkprof, desc))) return rc;
-      if ((rc = ensure(h, h->d_tabW, sizeof(float) * ((size_t)totW + 2 * kTabPad)))) return rc;
-      HIPCHK(h, hipMemsetAsync(h->d_tabW.p, 0, sizeof(float) * ((size_t)totW + 2 * kTabPad), h->stream));
-      for (size_t j0 = 0; j0 < jobs.size(); j0 += 32768) {
-        const int nj = (int)std::min<size_t>(32768, jobs.size() - j0);
-        hipLaunchKernelGGL(k_table_phase_major, dim3(32, nj), dim3(256), 0, h->stream, d_jobs.as<ProfileJob>() + j0,
-                           d_joffW.as<long long>() + j0, h->tab, h->d_tabW.as<float>() + kTabPad, s->osamp, 1);
-      }
-      // compact rows (32 bytes) of the profiles with at most 8 entries per row: what k_line_walk_lanes<8> gathers
-      {
-        std::vector<long long> joff32(jobs.size(), -1);
-        std::vector<uint32_t> c32((size_t)s->ndop * s->nlor, 0xffffffffu);
-        long long nq = 0; size_t jj = 0;                 // profiles with compact rows: [phase][profile][8 floats]
-        for (int i = 0; i < s->ndop; i++)
-          for (int k = 0; k < s->nlor; k++) {
-            const size_t e = (size_t)i * s->nlor + k;
-            if (h->adop[i] * 10.0 < h->alor[k] && i != 0) { c32[e] = c32[e - s->nlor]; continue; }
-            const long long ps = h->psize[e], K = (2 * ps) / s->osamp + 1;
-            if (K <= 8) { joff32[jj] = 8 * nq; c32[e] = (uint32_t)(32 * nq); nq++; }
-            jj++;
-          }
-        const long long tot32 = nq * 8 * (long long)s->osamp;
-        // (a slab below 2^24 bytes and the phase below 2^24: the kernel's 24-bit multiply; the whole below 4 GB)
-        if (nq > 0 && 32 * nq < (1LL << 24) && s->osamp < (1 << 24) && 4 * tot32 < (1LL << 32) && !h->no_rows32) {
-          DevBuf d_joff32;
-          if ((rc = upload(h, d_joff32, joff32)) || (rc = upload(h, h->d_wp32, c32))) return rc;
-          // (and kLanesRowSlack floats behind: the last lane of a layer holding fewer bins than the others reads on past the row)
-          if ((rc = ensure(h, h->d_tabW32, sizeof(float) * ((size_t)tot32 + kLanesRowSlack)))) return rc;
-          HIPCHK(h, hipMemsetAsync(h->d_tabW32.as<float>() + tot32, 0, sizeof(float) * kLanesRowSlack, h->stream));
-          for (size_t j0 = 0; j0 < jobs.size(); j0 += 32768) {
-            const int nj = (int)std::min<size_t>(32768, jobs.size() - j0);
-            hipLaunchKernelGGL(k_table_rows32, dim3(16, nj), dim3(256), 0, h->stream, d_jobs.as<ProfileJob>() + j0,
-                               d_joffW.as<long long>() + j0, d_joff32.as<long long>() + j0, h->d_tabW.as<float>() + kTabPad, h->d_tabW32.as<float>(), s->osamp, 8 * nq);
-          }
-          h->slab32 = (unsigned)(32 * nq);
-          HIPCHK(h, hipStreamSynchronize(h->stream));
-          h->tabW32 = h->d_tabW32.as<float>();
-        }
-      }
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      h->tabW = h->d_tabW.as<float>() + kTabPad;
-    }
-  }
+                         B.d_jobs.as<ProfileJob>() + j0, h->tab, m_limit);
+  });
+}
+
+// phase-major copy for the wide-profile kernel (osamp == 1: the table itself has that layout)
+int phase_major_copy(trx_handle *h, const trx_static *s, const TableBuild &B)
+{
+  if (s->osamp == 1) { h->tabT = h->tab; h->poffT = h->d_poff.as<long long>(); return TRX_OK; }
+  const PhaseMajorLayout T = phase_major_layout(B.P, s->osamp);
+  const size_t bytes = sizeof(float) * ((size_t)T.totT + 2 * kTabPad);
+  DevBuf d_joffT;
+  int rc;
+  if ((rc = upload(h, d_joffT, T.joffT)) || (rc = upload(h, h->d_poffT, T.poffT)) || (rc = ensure(h, h->d_tabT, bytes))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->d_tabT.p, 0, bytes, h->stream));
+  for_job_batches(B.P.jobs, [&](size_t j0, int nj) {
+    hipLaunchKernelGGL(k_table_phase_major, dim3(32, nj), dim3(256), 0, h->stream, B.d_jobs.as<ProfileJob>() + j0,
+                       d_joffT.as<long long>() + j0, h->tab, h->d_tabT.as<float>() + kTabPad, s->osamp, 0);
+  });
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // d_joffT and T die here
+  h->tabT = h->d_tabT.as<float>() + kTabPad; h->poffT = h->d_poffT.as<long long>();
+  return TRX_OK;
+}
+
+// compact 32-byte rows, gathered from the walk's rows (d_joffW: where those are)
+int compact_rows(trx_handle *h, const trx_static *s, const TableBuild &B, const DevBuf &d_joffW)
+{
+  const CompactLayout C = compact_layout(B.P, s->osamp);
+  if (!compact_rows_fit(C.nq, C.tot32, s->osamp) || h->sw.no_rows32) return TRX_OK;
+  DevBuf d_joff32;
+  int rc;
+  // (and kLanesRowSlack floats behind: the last lane of a layer holding fewer bins than the others reads on past the row)
+  if ((rc = upload(h, d_joff32, C.joff32)) || (rc = upload(h, h->d_wp32, C.c32)) ||
+      (rc = ensure(h, h->d_tabW32, sizeof(float) * ((size_t)C.tot32 + kLanesRowSlack)))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->d_tabW32.as<float>() + C.tot32, 0, sizeof(float) * kLanesRowSlack, h->stream));
+  for_job_batches(B.P.jobs, [&](size_t j0, int nj) {
+    hipLaunchKernelGGL(k_table_rows32, dim3(16, nj), dim3(256), 0, h->stream, B.d_jobs.as<ProfileJob>() + j0, d_joffW.as<long long>() + j0,
+                       d_joff32.as<long long>() + j0, h->d_tabW.as<float>() + kTabPad, h->d_tabW32.as<float>(), s->osamp, 8 * C.nq);
+  });
+  h->slab32 = (unsigned)(32 * C.nq);
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // d_joff32 and C die here
+  h->tabW32 = h->d_tabW32.as<float>();
+  return TRX_OK;
+}
+
+// the walk's rows and their descriptors, then the compact rows made from them
+int walk_rows(trx_handle *h, const trx_static *s, const TableBuild &B)
+{
+  const WalkLayout W = walk_layout(B.P, s->osamp);
+  h->tabw_ok = walk_rows_fit(W.totW) && !h->sw.no_row_copy;
+  if (!h->tabw_ok) return TRX_OK;
+  const size_t bytes = sizeof(float) * ((size_t)W.totW + 2 * kTabPad);
+  DevBuf d_joffW;
+  int rc;
+  if ((rc = upload(h, d_joffW, W.joffW)) || (rc = upload(h, h->d_walkprof, W.prof)) || (rc = ensure(h, h->d_tabW, bytes))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->d_tabW.p, 0, bytes, h->stream));
+  for_job_batches(B.P.jobs, [&](size_t j0, int nj) {
+    hipLaunchKernelGGL(k_table_phase_major, dim3(32, nj), dim3(256), 0, h->stream, B.d_jobs.as<ProfileJob>() + j0,
+                       d_joffW.as<long long>() + j0, h->tab, h->d_tabW.as<float>() + kTabPad, s->osamp, 1);
+  });
+  if ((rc = compact_rows(h, s, B, d_joffW))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // d_joffW and W die here
+  h->tabW = h->d_tabW.as<float>() + kTabPad;
+  return TRX_OK;
+}
+
+int build_table(trx_handle *h, const trx_static *s)
+{
+  TableBuild B;
+  int rc;
+  if ((rc = plan_into_handle(h, s, B)) || (rc = upload_table_inputs(h, s, B))) return rc;
+  hipEvent_t e0, e1;                               // ms_create_table: the table kernels and the three copies
+  HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
+  HIPCHK(h, hipEventRecord(e0, h->stream));
+  table_kernels(h, B);
+  if ((rc = phase_major_copy(h, s, B)) || (rc = walk_rows(h, s, B))) return rc;
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(e1, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // B.d_jobs dies at return
   float ms = 0; HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   h->stats.ms_create_table = ms;
@@ -544,211 +443,237 @@ int build_table(trx_handle *h, const trx_static *s)
 }
 
 // ---- line list preparation (the threaded host loops: ../trx_groups.h) -------
-int prepare_lines(trx_handle *h, const trx_static *s)
-{
-  const int64_t n = s->nlines;
+// what the stages of prepare_lines hand to one another (host arrays: they die with it, after the uploads' synchronisation)
+struct LinePrep {
+  int64_t n = 0; int nth = 1;
+  double wn0 = 0, odwn = 0, own_last = 0;          // the fine grid: first point, step, last point
   StageTimer T;
-  const int nth = create_threads();
-  const double wn0 = s->wn_i, odwn = s->wn_d / s->osamp;
-  const double own_last = wn0 + (double)(s->nown - 1) * odwn;
-  if (n > 2000000000LL) return fail(h, TRX_E_UNSUPPORTED, "more than 2^31 lines per handle");
-  // the three arrays that go up as they are leave now, on a thread of their own, under the grouping
-  const double *elow = s->elow, *gf = s->gf;
-  int rc_raw = TRX_OK;
-  std::thread raw_up([&]() {
-    (void)hipSetDevice(h->device);
-    if ((rc_raw = upload_raw(h, h->d_elow, elow, (size_t)n)) || (rc_raw = upload_raw(h, h->d_gf, gf, (size_t)n)) ||
-        (rc_raw = upload_raw(h, h->d_iso, s->isoid, (size_t)n))) return;
-  });
-  struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } raw_join{raw_up};
-  HostBuf<double> wavn; wavn.alloc((size_t)n);
-  HostBuf<uint8_t> inr; inr.alloc((size_t)n);
-  {
-    std::vector<int64_t> cnt((size_t)nth + 1, 0); std::vector<int> bad((size_t)nth + 1, 0);
-    parallel_parts(n, nth, [&](int t, int64_t i0, int64_t i1) {
-      int64_t c = 0;
-      for (int64_t i = i0; i < i1; i++) {
-        if (s->isoid[i] < 0 || s->isoid[i] >= s->niso) { bad[t] = 1; continue; }
-        wavn[i] = 1.0 / (s->wl_um[i] * kTliWfct);
-        inr[i] = !(wavn[i] < wn0 || wavn[i] > own_last);             // extinction.c:410
-        c += inr[i];
-      }
-      cnt[t] = c;
-    });
-    for (int t = 0; t <= nth; t++) { if (bad[t]) return fail(h, TRX_E_ARG, "isotope id out of range"); h->ninrange += cnt[t]; }
-  }
-  T.lap("wavn + range flags");
-  // TLI order: isotope blocks in ascending id, wavelength ascending inside a
-  // block (pylineread.py:369-383); the gather kernel relies on it.
-  {
-    std::vector<int> bad((size_t)nth + 1, 0);
-    parallel_parts(n, nth, [&](int t, int64_t i0, int64_t i1) {
-      for (int64_t i = std::max<int64_t>(i0, 1); i < i1; i++) {
-        if (s->isoid[i] < s->isoid[i-1]) bad[t] |= 1;
-        else if (s->isoid[i] == s->isoid[i-1] && wavn[i] > wavn[i-1]) bad[t] |= 2;
-      }
-    });
-    int any = 0;
-    for (int t = 0; t <= nth; t++) any |= bad[t];
-    if (any & 1) return fail(h, TRX_E_ORDER, "isotope blocks are not in ascending order");
-    if (any & 2) return fail(h, TRX_E_ORDER, "wavelengths are not ascending inside an isotope block");
-  }
-  T.lap("order check");
-  // co-added groups (extinction.c:445-462), grouped in pieces side by side (trx_groups.h)
+  HostBuf<double> wavn; HostBuf<uint8_t> inr;      // [n] wavenumber, in-range flag
   LineGroups LG;
-  group_lines(n, s->isoid, wavn.data(), inr.data(), s->niso, wn0, odwn, nth, LG);
-  HostBuf<int32_t> &gfirst = LG.first, &gcount = LG.count, &giown = LG.iown; HostBuf<int16_t> &giso = LG.iso; HostBuf<double> &gwavn = LG.wavn;
-  h->iso_wmin = LG.iso_wmin; h->iso_wmax = LG.iso_wmax; h->nadd += LG.nadd;
-  T.lap("grouping");
-  h->nlines = n; h->ngroups = (int64_t)gfirst.size();
-  // isotope blocks (groups are in line order: the first group of every isotope by bisection) and
-  // the coarse-bin index over them
-  std::vector<int32_t> gblock(s->niso + 1, 0);
-  for (int b = 0; b <= s->niso; b++) gblock[b] = (int32_t)(std::lower_bound(giso.data(), giso.data() + giso.size(), (int16_t)b) - giso.data());
-  {
-    std::vector<int> bad((size_t)nth + 1, 0);
-    parallel_parts((int64_t)giown.size(), nth, [&](int t, int64_t g0, int64_t g1) {
-      for (int64_t g = std::max<int64_t>(g0, 1); g < g1; g++) if (giso[g] == giso[g-1] && giown[g] > giown[g-1]) bad[t] = 1;
-    });
-    for (int t = 0; t <= nth; t++) if (bad[t]) return fail(h, TRX_E_ORDER, "fine-grid indices are not descending inside an isotope block");
-  }
-  HostBuf<int32_t> cntge; cntge.alloc((size_t)s->niso * (s->nwn + 1));
-  for (int b = 0; b < s->niso; b++) {
-    const long long osamp = s->osamp, kmaxc = s->nwn - 1;
-    count_ge(giown.data(), gblock[b], gblock[b + 1], s->nwn, [=](int32_t io) { return std::min<long long>(io / osamp, kmaxc); },
-             &cntge[(size_t)b * (s->nwn + 1)], nth);
-  }
-  T.lap("cnt_ge");
-  // the same counts at F sub-buckets per coarse cell (key iown*F/osamp): k_accumulate sizes its
-  // windows with them, so that it does not stream whole cells of groups that lie between the
-  // reach of two bins.  F = 1 (the table above) when the fine grid is no finer or the table
-  // would be large.
-  HostBuf<int32_t> cntsub;
-  {
-    int F = (int)std::min<long long>(16, s->osamp);
-    while (F > 1 && (size_t)s->niso * (size_t)F * (size_t)s->nwn * 4 > ((size_t)64 << 20)) F /= 2;
-    h->sub_f = F;
-    if (F > 1) {
-      const size_t stride = (size_t)F * s->nwn + 1;
-      cntsub.alloc((size_t)s->niso * stride);
-      for (int b = 0; b < s->niso; b++) {
-        const long long osamp = s->osamp, kmaxs = (long long)stride - 2, FF = F;
-        count_ge(giown.data(), gblock[b], gblock[b + 1], (long long)stride - 1,
-                 [=](int32_t io) { return std::min<long long>((long long)io * FF / osamp, kmaxs); }, &cntsub[(size_t)b * stride], nth);
-      }
-    }
-  }
+  std::vector<int32_t> gblock;                     // [niso + 1] first group of every isotope block
+  HostBuf<int32_t> cntge, cntsub, lgroup, gimod, gidiv;
+};
 
-  HostBuf<int32_t> lgroup; lgroup.alloc((size_t)n);
-  parallel_parts(n, nth, [&](int, int64_t i0, int64_t i1) { std::fill(lgroup.begin() + i0, lgroup.begin() + i1, -1); });
-  HostBuf<int32_t> gimod, gidiv; gimod.alloc(giown.size()); gidiv.alloc(giown.size());
-  parallel_parts((int64_t)giown.size(), nth, [&](int, int64_t g0, int64_t g1) {
-    for (int64_t g = g0; g < g1; g++) { lgroup[(size_t)gfirst[g]] = (int32_t)g; gimod[g] = giown[g] % s->osamp; gidiv[g] = giown[g] / s->osamp; }
+// wavenumbers and range flags
+int line_wavenumbers(trx_handle *h, const trx_static *s, LinePrep &Q)
+{
+  Q.wavn.alloc((size_t)Q.n); Q.inr.alloc((size_t)Q.n);
+  std::atomic<int64_t> inrange{0};
+  const int bad = parallel_flags(Q.n, Q.nth, [&](int64_t i0, int64_t i1) {
+    int64_t c = 0; int b = 0;
+    for (int64_t i = i0; i < i1; i++) {
+      if (s->isoid[i] < 0 || s->isoid[i] >= s->niso) { b = 1; continue; }
+      Q.wavn[i] = 1.0 / (s->wl_um[i] * kTliWfct);
+      Q.inr[i] = !(Q.wavn[i] < Q.wn0 || Q.wavn[i] > Q.own_last);             // extinction.c:410
+      c += Q.inr[i];
+    }
+    inrange += c;
+    return b;
   });
-  T.lap("cnt_sub, lgroup, gimod");
-  int rc;
-  // ---- the walk's view of the list (k_line_walk): one 32-byte record per line, and line
-  // ranges of ngw consecutive groups per isotope block
-  // (32-bit byte offsets into the widened table: 8*tab_n + 64*osamp must stay below 2^32)
-  h->walk_ok = s->osamp < (1 << 21) && h->tab_n < ((int64_t)1 << 28) && !gfirst.empty();
-  if (h->walk_ok) {
-    // Groups per range: ~2 rounds of resident waves (the hardware balances the rounds).  Taken from
-    // the WHOLE list, not from what reaches this shard: the range size is part of the order of the
-    // sums, and a shard's spectrum must be the same bits as the unsharded one.  (Shorter ranges for
-    // small shards were measured: 1/8 of the demo 0.267 -> 0.259 ms with 32, slower with 16.)
-    // Lists of more than a million groups get MORE ranges of 64 groups, not longer ones (up to 2^17
-    // ranges: their partial records are ~50 MB per step and buffer): a rank of an N-way job walks 1/N
-    // of them, and a range is one wave's serial work -- with 512-group ranges one shard of eight of an
-    // 8*10^6-line list had 1 700 waves for 1 024 SIMDs (its 2-bin walk 226 us instead of 108).
-    int ngw = 32;
-    while (ngw < 64 && (int64_t)gfirst.size() / ngw > 16384) ngw *= 2;
-    while (ngw < 512 && (int64_t)gfirst.size() / ngw > 131072) ngw *= 2;
-    h->ngw = ngw;
-    h->h_wbase.assign(s->niso + 1, 0);
-    for (int b = 0; b < s->niso; b++) h->h_wbase[b + 1] = h->h_wbase[b] + (gblock[b + 1] - gblock[b] + ngw - 1) / ngw;
-    h->nwaves = h->h_wbase[s->niso];
-    if ((rc = upload(h, h->d_wbase, h->h_wbase))) return rc;
+  if (bad) return fail(h, TRX_E_ARG, "isotope id out of range");
+  h->ninrange += inrange;
+  Q.T.lap("wavn + range flags");
+  return TRX_OK;
+}
+
+// TLI order: isotope blocks in ascending id, wavelength ascending inside a
+// block (pylineread.py:369-383); the gather kernel relies on it.
+int check_line_order(trx_handle *h, const trx_static *s, LinePrep &Q)
+{
+  const int any = parallel_flags(Q.n, Q.nth, [&](int64_t i0, int64_t i1) {
+    int b = 0;
+    for (int64_t i = std::max<int64_t>(i0, 1); i < i1; i++) {
+      if (s->isoid[i] < s->isoid[i-1]) b |= 1;
+      else if (s->isoid[i] == s->isoid[i-1] && Q.wavn[i] > Q.wavn[i-1]) b |= 2;
+    }
+    return b;
+  });
+  if (any & 1) return fail(h, TRX_E_ORDER, "isotope blocks are not in ascending order");
+  if (any & 2) return fail(h, TRX_E_ORDER, "wavelengths are not ascending inside an isotope block");
+  Q.T.lap("order check");
+  return TRX_OK;
+}
+
+// co-added groups (extinction.c:445-462), grouped in pieces side by side (trx_groups.h), and their isotope blocks
+int group_and_check(trx_handle *h, const trx_static *s, LinePrep &Q)
+{
+  LineGroups &G = Q.LG;
+  group_lines(Q.n, s->isoid, Q.wavn.data(), Q.inr.data(), s->niso, Q.wn0, Q.odwn, Q.nth, G);
+  h->iso_wmin = G.iso_wmin; h->iso_wmax = G.iso_wmax; h->nadd += G.nadd;
+  Q.T.lap("grouping");
+  h->nlines = Q.n; h->ngroups = (int64_t)G.first.size();
+  // (groups are in line order: the first group of every isotope by bisection)
+  Q.gblock.assign(s->niso + 1, 0);
+  for (int b = 0; b <= s->niso; b++) Q.gblock[b] = (int32_t)(std::lower_bound(G.iso.data(), G.iso.data() + G.iso.size(), (int16_t)b) - G.iso.data());
+  const int bad = parallel_flags((int64_t)G.iown.size(), Q.nth, [&](int64_t g0, int64_t g1) {
+    int b = 0;
+    for (int64_t g = std::max<int64_t>(g0, 1); g < g1; g++) if (G.iso[g] == G.iso[g-1] && G.iown[g] > G.iown[g-1]) b = 1;
+    return b;
+  });
+  if (bad) return fail(h, TRX_E_ORDER, "fine-grid indices are not descending inside an isotope block");
+  return TRX_OK;
+}
+
+// the coarse-bin index over the blocks' groups (cntge), and the same counts at F sub-buckets per
+// coarse cell (cntsub, key iown*F/osamp): k_accumulate sizes its windows with them, so that it does
+// not stream whole cells of groups that lie between the reach of two bins.  F = 1 (cntge itself)
+// when the fine grid is no finer or the table would be large.
+void count_tables(trx_handle *h, const trx_static *s, LinePrep &Q)
+{
+  const int32_t *giown = Q.LG.iown.data();
+  const long long osamp = s->osamp;
+  Q.cntge.alloc((size_t)s->niso * (s->nwn + 1));
+  for (int b = 0; b < s->niso; b++) {
+    const long long kmaxc = s->nwn - 1;
+    count_ge(giown, Q.gblock[b], Q.gblock[b + 1], s->nwn, [=](int32_t io) { return std::min<long long>(io / osamp, kmaxc); },
+             &Q.cntge[(size_t)b * (s->nwn + 1)], Q.nth);
   }
-  raw_up.join();
-  if (rc_raw) return rc_raw;
-  if ((rc = upload(h, h->d_wavn, wavn)) || (rc = upload(h, h->d_inr, inr)) || (rc = upload(h, h->d_lgroup, lgroup)) || (rc = upload(h, h->d_gfirst, gfirst)) ||
-      (rc = upload(h, h->d_gcount, gcount)) || (rc = upload(h, h->d_giown, giown)) || (rc = upload(h, h->d_giso, giso)) ||
-      (rc = upload(h, h->d_gwavn, gwavn)) || (rc = upload(h, h->d_gimod, gimod)) || (rc = upload(h, h->d_gidiv, gidiv)) || (rc = upload(h, h->d_gblock, gblock)) || (rc = upload(h, h->d_cntge, cntge)) ||
-      (rc = upload(h, h->d_cntsub, cntsub)))
+  Q.T.lap("cnt_ge");
+  int F = (int)std::min<long long>(16, s->osamp);
+  while (F > 1 && (size_t)s->niso * (size_t)F * (size_t)s->nwn * 4 > ((size_t)64 << 20)) F /= 2;
+  h->sub_f = F;
+  if (F == 1) return;
+  const size_t stride = (size_t)F * s->nwn + 1;
+  Q.cntsub.alloc((size_t)s->niso * stride);
+  for (int b = 0; b < s->niso; b++) {
+    const long long kmaxs = (long long)stride - 2, FF = F;
+    count_ge(giown, Q.gblock[b], Q.gblock[b + 1], (long long)stride - 1,
+             [=](int32_t io) { return std::min<long long>((long long)io * FF / osamp, kmaxs); }, &Q.cntsub[(size_t)b * stride], Q.nth);
+  }
+}
+
+// a line's group (anchors only), a group's fine-grid index as cell and phase
+void group_indices(const trx_static *s, LinePrep &Q)
+{
+  const LineGroups &G = Q.LG;
+  Q.lgroup.alloc((size_t)Q.n);
+  parallel_parts(Q.n, Q.nth, [&](int, int64_t i0, int64_t i1) { std::fill(Q.lgroup.begin() + i0, Q.lgroup.begin() + i1, -1); });
+  Q.gimod.alloc(G.iown.size()); Q.gidiv.alloc(G.iown.size());
+  parallel_parts((int64_t)G.iown.size(), Q.nth, [&](int, int64_t g0, int64_t g1) {
+    for (int64_t g = g0; g < g1; g++) { Q.lgroup[(size_t)G.first[g]] = (int32_t)g; Q.gimod[g] = G.iown[g] % s->osamp; Q.gidiv[g] = G.iown[g] / s->osamp; }
+  });
+  Q.T.lap("cnt_sub, lgroup, gimod");
+}
+
+// the walk's view of the list (k_line_walk): line ranges of ngw consecutive groups per isotope block
+// (32-bit byte offsets into the widened table: 8*tab_n + 64*osamp must stay below 2^32)
+int walk_ranges(trx_handle *h, const trx_static *s, const LinePrep &Q)
+{
+  h->walk_ok = s->osamp < (1 << 21) && h->tab_n < ((int64_t)1 << 28) && !Q.LG.first.empty();
+  if (!h->walk_ok) return TRX_OK;
+  const int ngw = h->ngw = groups_per_range((int64_t)Q.LG.first.size());
+  h->h_wbase.assign(s->niso + 1, 0);
+  for (int b = 0; b < s->niso; b++) h->h_wbase[b + 1] = h->h_wbase[b] + (Q.gblock[b + 1] - Q.gblock[b] + ngw - 1) / ngw;
+  h->nwaves = h->h_wbase[s->niso];
+  return upload(h, h->d_wbase, h->h_wbase);
+}
+
+// everything else goes up; the host keeps what the per-run prologue reads
+int upload_lines(trx_handle *h, LinePrep &Q)
+{
+  LineGroups &G = Q.LG;
+  int rc;
+  if ((rc = upload(h, h->d_wavn, Q.wavn)) || (rc = upload(h, h->d_inr, Q.inr)) || (rc = upload(h, h->d_lgroup, Q.lgroup)) ||
+      (rc = upload(h, h->d_gfirst, G.first)) || (rc = upload(h, h->d_gcount, G.count)) || (rc = upload(h, h->d_giown, G.iown)) ||
+      (rc = upload(h, h->d_giso, G.iso)) || (rc = upload(h, h->d_gwavn, G.wavn)) || (rc = upload(h, h->d_gimod, Q.gimod)) ||
+      (rc = upload(h, h->d_gidiv, Q.gidiv)) || (rc = upload(h, h->d_gblock, Q.gblock)) || (rc = upload(h, h->d_cntge, Q.cntge)) ||
+      (rc = upload(h, h->d_cntsub, Q.cntsub)))
     return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));    // host vectors die at return
-  T.lap("uploads + sync");
-  h->h_gwavn = std::move(gwavn); h->h_gblock = gblock; h->h_cntge = std::move(cntge); h->h_gfirst = std::move(gfirst); h->h_gcount = std::move(gcount);
-  T.lap("host copies");
+  HIPCHK(h, hipStreamSynchronize(h->stream));    // the host arrays may go now
+  Q.T.lap("uploads + sync");
+  h->h_gwavn = std::move(G.wavn); h->h_gblock = Q.gblock; h->h_cntge = std::move(Q.cntge); h->h_gfirst = std::move(G.first); h->h_gcount = std::move(G.count);
+  Q.T.lap("host copies");
   LinesDev &L = h->L;
-  L.nlines = n; L.wavn = h->d_wavn.as<double>(); L.elow = h->d_elow.as<double>(); L.gf = h->d_gf.as<double>();
+  L.nlines = Q.n; L.wavn = h->d_wavn.as<double>(); L.elow = h->d_elow.as<double>(); L.gf = h->d_gf.as<double>();
   L.iso = h->d_iso.as<int16_t>(); L.inrange = h->d_inr.as<uint8_t>(); L.lgroup = h->d_lgroup.as<int32_t>();
   L.ngroups = h->ngroups; L.gfirst = h->d_gfirst.as<int32_t>(); L.gcount = h->d_gcount.as<int32_t>();
   L.giown = h->d_giown.as<int32_t>(); L.giso = h->d_giso.as<int16_t>(); L.gwavn = h->d_gwavn.as<double>();
   L.gblock = h->d_gblock.as<int32_t>(); L.cnt_ge = h->d_cntge.as<int32_t>();
-  if (h->walk_ok) {   // the walk's records (trx_walk.hip.h), built where the arrays already are
-    if ((rc = ensure(h, h->d_walk, sizeof(WalkLine) * ((size_t)n + 1))) || (rc = ensure(h, h->d_linebase, sizeof(double) * ((size_t)n + 1)))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_linebase.p, 0, sizeof(double) * ((size_t)n + 1), h->stream));
-    {
-      std::vector<int> mg((size_t)nth + 1, 0);
-      parallel_parts((int64_t)h->h_gcount.size(), nth, [&](int t, int64_t g0, int64_t g1) {
-        int m = 0;
-        for (int64_t g = g0; g < g1; g++) m = std::max(m, (int)h->h_gcount[(size_t)g]);
-        mg[t] = m;
-      });
-      h->max_gcount = *std::max_element(mg.begin(), mg.end());
-    }
-    hipLaunchKernelGGL(k_walk_records, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, h->stream, (long long)n, L.wavn, L.elow, L.gf,
-                       L.lgroup, L.giown, s->osamp, h->d_walk.as<WalkLine>());
-    hipLaunchKernelGGL(k_walk_marks, dim3((unsigned)((h->nwaves + 63) / 64)), dim3(64), 0, h->stream, h->nwaves, h->ngw, s->niso,
-                       h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), h->d_linebase.as<double>());
-    if ((rc = ensure(h, h->d_rinfo, sizeof(RangeInfo) * (size_t)std::max(h->nwaves, 1)))) return rc;
-    hipLaunchKernelGGL(k_range_info, dim3((unsigned)((h->nwaves + 255) / 256)), dim3(256), 0, h->stream, h->nwaves, h->ngw, s->niso,
-                       h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), h->d_rinfo.as<RangeInfo>());
-  }
-  h->stats.nlines_inrange = h->ninrange; h->stats.ngroups = h->ngroups; h->stats.nadd = h->nadd;
-  // ---- candidates for the layer maximum: lines no other line of their isotope dominates
-  // (trx_walk.hip.h).  Falls back to "every line" when the filter would not pay.
+  return TRX_OK;
+}
+
+// the walk's records (trx_walk.hip.h): one 32-byte record per line, built where the arrays already are
+int walk_records(trx_handle *h, const trx_static *s, const LinePrep &Q)
+{
+  const int64_t n = Q.n; const LinesDev &L = h->L;
+  int rc;
+  if ((rc = ensure(h, h->d_walk, sizeof(WalkLine) * ((size_t)n + 1))) || (rc = ensure(h, h->d_linebase, sizeof(double) * ((size_t)n + 1)))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->d_linebase.p, 0, sizeof(double) * ((size_t)n + 1), h->stream));
+  h->max_gcount = parallel_minmax<int>((int64_t)h->h_gcount.size(), Q.nth, 0, 0, [&](int64_t g, bool &) { return (int)h->h_gcount[(size_t)g]; }).hi;
+  hipLaunchKernelGGL(k_walk_records, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, h->stream, (long long)n, L.wavn, L.elow, L.gf,
+                     L.lgroup, L.giown, s->osamp, h->d_walk.as<WalkLine>());
+  hipLaunchKernelGGL(k_walk_marks, dim3((unsigned)((h->nwaves + 63) / 64)), dim3(64), 0, h->stream, h->nwaves, h->ngw, s->niso,
+                     h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), h->d_linebase.as<double>());
+  if ((rc = ensure(h, h->d_rinfo, sizeof(RangeInfo) * (size_t)std::max(h->nwaves, 1)))) return rc;
+  hipLaunchKernelGGL(k_range_info, dim3((unsigned)((h->nwaves + 255) / 256)), dim3(256), 0, h->stream, h->nwaves, h->ngw, s->niso,
+                     h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), h->d_rinfo.as<RangeInfo>());
+  return TRX_OK;
+}
+
+// candidates for the layer maximum: lines no other line of their isotope dominates
+// (trx_walk.hip.h).  Falls back to "every line" when the filter would not pay.
+int line_candidates(trx_handle *h, const trx_static *s, const LinePrep &Q)
+{
+  const int64_t n = Q.n; const LinesDev &L = h->L;
   h->ncand = -1;
-  if (h->ninrange > 4096 && s->niso > 0) {
-    double emin = HUGE_VAL, emax = -HUGE_VAL;
-    {
-      std::vector<double> lo((size_t)nth + 1, HUGE_VAL), hi((size_t)nth + 1, -HUGE_VAL);
-      parallel_parts(n, nth, [&](int t, int64_t i0, int64_t i1) {
-        double a = HUGE_VAL, b = -HUGE_VAL;
-        for (int64_t i = i0; i < i1; i++) if (inr[i]) { a = std::min(a, elow[i]); b = std::max(b, elow[i]); }
-        lo[t] = a; hi[t] = b;
-      });
-      for (int t = 0; t <= nth; t++) { emin = std::min(emin, lo[t]); emax = std::max(emax, hi[t]); }
-    }
-    CandGeom Gm{};
-    Gm.e_min = emin; Gm.e_scale = emax > emin ? kCandGrid / (emax - emin) : 0.0;
-    Gm.w_min = wn0;  Gm.w_scale = own_last > wn0 ? kCandGrid / (own_last - wn0) : 0.0;
-    const int cap = (int)std::max<int64_t>(4096, n / 8);
-    DevBuf d_M, d_n;
-    const size_t mbytes = sizeof(unsigned long long) * (size_t)s->niso * kCandGrid * kCandGrid;
-    if ((rc = ensure(h, d_M, mbytes)) || (rc = ensure(h, d_n, sizeof(int))) || (rc = ensure(h, h->d_cand, sizeof(int32_t) * (size_t)cap))) return rc;
-    HIPCHK(h, hipMemsetAsync(d_M.p, 0, mbytes, h->stream));
-    HIPCHK(h, hipMemsetAsync(d_n.p, 0, sizeof(int), h->stream));
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_cand_cellmax, dim3(nb), dim3(256), 0, h->stream, (long long)n, L.wavn, L.elow, L.gf, L.iso, L.inrange, Gm, d_M.as<unsigned long long>());
-    hipLaunchKernelGGL(k_cand_prefix, dim3((unsigned)s->niso), dim3(kCandGrid), 0, h->stream, d_M.as<unsigned long long>());
-    hipLaunchKernelGGL(k_cand_select, dim3(nb), dim3(256), 0, h->stream, (long long)n, L.wavn, L.elow, L.gf, L.iso, L.inrange, Gm,
-                       d_M.as<unsigned long long>(), h->d_cand.as<int32_t>(), d_n.as<int>(), cap);
-    int nc = 0;
-    HIPCHK(h, hipMemcpyAsync(&nc, d_n.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipGetLastError());
-    if (nc > 0 && nc <= cap) {
-      h->ncand = nc;
-      if ((rc = ensure(h, h->d_candrec, sizeof(CandLine) * (size_t)nc))) return rc;
-      hipLaunchKernelGGL(k_cand_pack, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, nc, h->d_cand.as<int32_t>(),
-                         L.wavn, L.elow, L.gf, L.iso, L.inrange, h->d_candrec.as<CandLine>());
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-  }
+  if (!(h->ninrange > 4096 && s->niso > 0)) return TRX_OK;
+  const MinMax<double> e = parallel_minmax<double>(n, Q.nth, HUGE_VAL, -HUGE_VAL, [&](int64_t i, bool &use) { use = Q.inr[i]; return s->elow[i]; });
+  CandGeom Gm{};
+  Gm.e_min = e.lo; Gm.e_scale = e.hi > e.lo ? kCandGrid / (e.hi - e.lo) : 0.0;
+  Gm.w_min = Q.wn0;  Gm.w_scale = Q.own_last > Q.wn0 ? kCandGrid / (Q.own_last - Q.wn0) : 0.0;
+  const int cap = (int)std::max<int64_t>(4096, n / 8);
+  DevBuf d_M, d_n;
+  const size_t mbytes = sizeof(unsigned long long) * (size_t)s->niso * kCandGrid * kCandGrid;
+  int rc;
+  if ((rc = ensure(h, d_M, mbytes)) || (rc = ensure(h, d_n, sizeof(int))) || (rc = ensure(h, h->d_cand, sizeof(int32_t) * (size_t)cap))) return rc;
+  HIPCHK(h, hipMemsetAsync(d_M.p, 0, mbytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_n.p, 0, sizeof(int), h->stream));
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_cand_cellmax, dim3(nb), dim3(256), 0, h->stream, (long long)n, L.wavn, L.elow, L.gf, L.iso, L.inrange, Gm, d_M.as<unsigned long long>());
+  hipLaunchKernelGGL(k_cand_prefix, dim3((unsigned)s->niso), dim3(kCandGrid), 0, h->stream, d_M.as<unsigned long long>());
+  hipLaunchKernelGGL(k_cand_select, dim3(nb), dim3(256), 0, h->stream, (long long)n, L.wavn, L.elow, L.gf, L.iso, L.inrange, Gm,
+                     d_M.as<unsigned long long>(), h->d_cand.as<int32_t>(), d_n.as<int>(), cap);
+  int nc = 0;
+  HIPCHK(h, hipMemcpyAsync(&nc, d_n.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipGetLastError());
+  if (!(nc > 0 && nc <= cap)) return TRX_OK;
+  h->ncand = nc;
+  if ((rc = ensure(h, h->d_candrec, sizeof(CandLine) * (size_t)nc))) return rc;
+  hipLaunchKernelGGL(k_cand_pack, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, nc, h->d_cand.as<int32_t>(),
+                     L.wavn, L.elow, L.gf, L.iso, L.inrange, h->d_candrec.as<CandLine>());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return TRX_OK;
+}
+
+int prepare_lines(trx_handle *h, const trx_static *s)
+{
+  LinePrep Q;
+  const int64_t n = Q.n = s->nlines;
+  Q.nth = create_threads();
+  Q.wn0 = s->wn_i; Q.odwn = s->wn_d / s->osamp; Q.own_last = Q.wn0 + (double)(s->nown - 1) * Q.odwn;
+  if (n > 2000000000LL) return fail(h, TRX_E_UNSUPPORTED, "more than 2^31 lines per handle");
+  // the three arrays that go up as they are leave now, on a thread of their own, under the grouping
+  int rc_raw = TRX_OK;
+  std::thread raw_up([&]() {
+    (void)hipSetDevice(h->device);
+    if ((rc_raw = upload_raw(h, h->d_elow, s->elow, (size_t)n)) || (rc_raw = upload_raw(h, h->d_gf, s->gf, (size_t)n)) ||
+        (rc_raw = upload_raw(h, h->d_iso, s->isoid, (size_t)n))) return;
+  });
+  struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } raw_join{raw_up};
+  int rc;
+  if ((rc = line_wavenumbers(h, s, Q)) || (rc = check_line_order(h, s, Q)) || (rc = group_and_check(h, s, Q))) return rc;
+  count_tables(h, s, Q);
+  group_indices(s, Q);
+  if ((rc = walk_ranges(h, s, Q))) return rc;
+  raw_up.join();
+  if (rc_raw) return rc_raw;
+  if ((rc = upload_lines(h, Q))) return rc;
+  if (h->walk_ok && (rc = walk_records(h, s, Q))) return rc;
+  h->stats.nlines_inrange = h->ninrange; h->stats.ngroups = h->ngroups; h->stats.nadd = h->nadd;
+  if ((rc = line_candidates(h, s, Q))) return rc;
   h->stats.ncandidates = h->ncand;
-  T.lap("candidates");
+  Q.T.lap("candidates");
   return TRX_OK;
 }
 
@@ -782,9 +707,9 @@ int cia_device(trx_handle *h, const trx_atm *a, const trx_opts *o, const double 
   int rc;
   // (per table of a batch: the table at the layers' temperatures, its second derivatives, and the sweeps' scratch -- one
   // piece per segment of k_cia_layers, each with room for its rows and both margins)
-  const int seg_rows = h->cia_segments ? 128 : 1 << 30;
-  const size_t seg_vrows = h->cia_segments ? (size_t)seg_rows + 2 * kCiaMargin + 8 : nwmax;
-  const size_t seg_cap = h->cia_segments ? (nwmax + (size_t)seg_rows - 1) / (size_t)seg_rows : 1;
+  const int seg_rows = h->sw.cia_segments ? 128 : 1 << 30;
+  const size_t seg_vrows = h->sw.cia_segments ? (size_t)seg_rows + 2 * kCiaMargin + 8 : nwmax;
+  const size_t seg_cap = h->sw.cia_segments ? (nwmax + (size_t)seg_rows - 1) / (size_t)seg_rows : 1;
   const size_t cia_job_doubles = (2 * nwmax + seg_cap * seg_vrows) * (size_t)nr;
   if ((rc = ensure(h, h->d_cia_ws, sizeof(double) * cia_job_doubles * std::min<size_t>(kCiaBatch, h->cia.size())))) return rc;
   auto wn_at = [&](long long i) { return o->wn_fct * (h->wn_i + (double)(h->lo + i) * h->wn_d); };
@@ -812,7 +737,7 @@ int cia_device(trx_handle *h, const trx_atm *a, const trx_opts *o, const double 
       for (int t = 0; t < B.n && !sums; t++) {
         const long nw = B.J[t].C.nwave;
         const long need_a = B.J[t].ia == 0 ? 0 : B.J[t].ia + kCiaMargin, need_b = B.J[t].iz == nw - 1 ? nw - 1 : B.J[t].iz - kCiaMargin;
-        if (h->cia_segments && need_b >= need_a) nseg = std::max<unsigned>(nseg, (unsigned)((need_b - need_a + seg_rows) / seg_rows));
+        if (h->sw.cia_segments && need_b >= need_a) nseg = std::max<unsigned>(nseg, (unsigned)((need_b - need_a + seg_rows) / seg_rows));
       }
       if (!sums)
         hipLaunchKernelGGL(k_cia_layers, dim3((unsigned)((ljl - fjl + 63) / 64), (unsigned)B.n, nseg), dim3(64), 0, cst, B, nr, seg_rows,
@@ -845,12 +770,12 @@ int cia_device(trx_handle *h, const trx_atm *a, const trx_opts *o, const double 
     CiaJob &J = B.J[B.n];
     J.C = CiaDev{(int)c.wn.size(), (int)c.temp.size(), c.d_wn.as<double>(), c.d_temp.as<double>(), c.d_cs.as<double>(),
                  c.d_zt.as<double>(), c.d_uw.as<double>(), c.d_ruw.as<double>(), c.d_rh.as<double>(),
-                 (h->cia_sums && !c.wf.empty()) ? c.d_wf.as<double>() : nullptr, (h->cia_sums && !c.wf.empty()) ? c.d_wb.as<double>() : nullptr};
+                 (h->sw.cia_sums && !c.wf.empty()) ? c.d_wf.as<double>() : nullptr, (h->sw.cia_sums && !c.wf.empty()) ? c.d_wb.as<double>() : nullptr};
     J.fj = fj; J.lj = lj; J.fi = fi; J.li = li;
     {   // table rows the wavenumber spline is solved for: those the run's wavenumbers bracket, a margin to spare (k_cia_layers)
       const int nw = (int)c.wn.size();
       J.ia = 0; J.iz = nw - 1;
-      if (h->cia_window && nw > 4 * kCiaMargin) {
+      if (h->sw.cia_window && nw > 4 * kCiaMargin) {
         const double xa = wn_at(fi), xb = wn_at(li - 1);
         const int ra = (int)(std::upper_bound(c.wn.begin(), c.wn.end(), xa) - c.wn.begin()) - 1;      // last row at or below the first wavenumber
         const int rb = (int)(std::lower_bound(c.wn.begin(), c.wn.end(), xb) - c.wn.begin());          // first row at or above the last one
@@ -1071,7 +996,7 @@ int prep_layers(trx_handle *h, int nr, const double *temp_k, const double *densi
       // Doppler widths grow with the wavenumber: on a band that spans a factor of ten the widest
       // profile of the list is several times the widest one a low-wavenumber shard meets, and in the
       // deep layers (no anchor reaches wcut) every line takes the ONE profile of the index at wn_i.
-      if (h->shard_frames && has_lines) {
+      if (h->sw.shard_frames && has_lines) {
         double lo_w = h->iso_wmin[i], hi_w = h->iso_wmax[i];
         if (h->windowed()) {
           const double reach = ((double)pm + h->osamp) * (h->wn_d / h->osamp) + h->wn_d;
@@ -1107,7 +1032,8 @@ int prep_layers(trx_handle *h, int nr, const double *temp_k, const double *densi
         const double *pa = gb + cg[std::min<long long>(std::max<long long>(kc + 2, 0), h->nwn)];
         const double *pz = gb + cg[std::min<long long>(std::max<long long>(kc - 2, 0), h->nwn)];
         // (the cut moves a little from a layer to the next: the search starts at the layer above's answer and doubles its
-        // step -- the lines it touches are the ones the layer above left in the cache; the same partition point)
+        // step -- the lines it touches are the ones the layer above left in the cache; the same partition point.  A step is
+        // tested against what is left of [lo, hi) before the pointer is formed: none points outside the array)
         const double *lo = pa, *hi = pz;                       // [lo, hi): all of [gb, lo) >= wc, all of [hi, ..) < wc
         const long g0 = h->guess_npre[i];
         if (g0 >= 0 && gb + g0 >= pa && gb + g0 <= pz) {
@@ -1115,10 +1041,10 @@ int prep_layers(trx_handle *h, int nr, const double *temp_k, const double *densi
           long stepw = 1;
           if (p < pz && *p >= wc) {                            // the answer lies above p
             lo = p + 1;
-            while (lo < hi) { const double *q = lo + stepw - 1; if (q >= hi) break; if (*q >= wc) { lo = q + 1; stepw *= 2; } else { hi = q; break; } }
+            while (lo < hi) { if (stepw > hi - lo) break; const double *q = lo + stepw - 1; if (*q >= wc) { lo = q + 1; stepw *= 2; } else { hi = q; break; } }
           } else {                                             // at or below p
             hi = p;
-            while (lo < hi) { const double *q = hi - stepw; if (q < lo) break; if (*q >= wc) { lo = q + 1; break; } else { hi = q; stepw *= 2; } }
+            while (lo < hi) { if (stepw > hi - lo) break; const double *q = hi - stepw; if (*q >= wc) { lo = q + 1; break; } else { hi = q; stepw *= 2; } }
           }
         }
         const long np = (long)(std::partition_point(lo, hi, [wc](double w) { return w >= wc; }) - gb);
@@ -1216,7 +1142,7 @@ int walk_plan(trx_handle *h, int nb, hipStream_t st, WalkPlan &P, trx_handle::Pl
   if (!pl->built && with_binw && (rc = ensure(h, pl->binw, 8 * (size_t)nbinw))) return rc;
   P.binw = with_binw ? pl->binw.as<int32_t>() : nullptr;
   // (and the bin's record in each of its first 64 ranges, for k_ray_tail: 256 bytes per bin and isotope, small shards only)
-  const bool with_binrec = with_binw && nbinw <= (1LL << 17) && !h->no_binrec;
+  const bool with_binrec = with_binw && nbinw <= (1LL << 17) && !h->sw.no_binrec;
   if (!pl->built && with_binrec && (rc = ensure(h, pl->binrec, 256 * (size_t)nbinw))) return rc;
   P.binrec = with_binrec ? pl->binrec.as<int32_t>() : nullptr;
   if (!pl->built) {
@@ -1299,7 +1225,7 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
   A.table = h->tab; A.zero_index = h->tab_n;
   A.tabw = h->tabW; A.walkprof = h->d_walkprof.as<WalkProfile>();
   A.tabw32 = h->tabW32; A.wp32 = h->tabW32 ? h->d_wp32.as<uint32_t>() : nullptr; A.slab32 = h->slab32;
-  A.xcd_map = h->xcd_map & 2;                        // (bit 1: k_line_walk, bit 0: k_line_walk_lanes)
+  A.xcd_map = h->sw.xcd_map & 2;                        // (bit 1: k_line_walk, bit 0: k_line_walk_lanes)
   A.part = part.as<double>(); A.counters = M.prof ? h->d_counters.as<unsigned long long>() : nullptr;
   A.flags = h->d_flags.as<int>(); A.last = M.skip_done ? h->d_last.as<int>() : nullptr; A.eager = M.eager;
   // a shard launches only the ranges that can reach it: per isotope block the groups whose cells
@@ -1331,10 +1257,10 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
     if (ns == 0) { A.nseg = 1; A.seg_w0[0] = 0; A.seg_cum[0] = 0; A.seg_cum[1] = 0; }     // nothing reaches: no wave does anything
   }
   // steps of few layers with wide frames on a dense list: lanes = lines for the strengths (trx_lanes.hip.h)
-  const bool lanes_prod = nw > 0 && A.tabw != nullptr && nb >= 8 && nc <= kLanesMaxLayers && h->lanes_walk &&
-                          h->max_gcount <= kLanesMaxGroup && (h->ngroups >= 8 * h->nwn || h->lanes_force);
+  const bool lanes_prod = nw > 0 && A.tabw != nullptr && nb >= 8 && nc <= kLanesMaxLayers && h->sw.lanes_walk &&
+                          h->max_gcount <= kLanesMaxGroup && (h->ngroups >= 8 * h->nwn || h->sw.lanes_force);
   // steps of few layers: several ranges per wave (k_line_walk_packed: an instruction serves S lines)
-  const bool packed_prod = !lanes_prod && nw > 0 && A.tabw != nullptr && nc <= h->packed_max_layers && h->packed_walk;
+  const bool packed_prod = !lanes_prod && nw > 0 && A.tabw != nullptr && nc <= h->sw.packed_max_layers && h->sw.packed_walk;
   // (a counting run -- instrumented k_line_walk for every step -- books its layers under the form the production run
   // takes for them: its per-layer counters are what prices each form's bytes, bench.py)
   const bool lanes = lanes_prod && !M.prof, packed = packed_prod && !M.prof;
@@ -1347,16 +1273,16 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
     // spectrum's two walks against 0.239 -- the last lines of a range already get lanes = (line, 4 or 8 layer sets);
     // the kernel no longer has that form)
     LanesExtra X{h->d_linebase.as<double>()};
-    A.xcd_map = h->xcd_map & 1;
+    A.xcd_map = h->sw.xcd_map & 1;
     if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG)
       log_msg(TRX_LOG_DEBUG, "walk: lanes = lines, " + std::to_string(nc) + " layers, " + std::to_string(nb) + "-bin frames, " +
-                             std::to_string(lanes_parts(nc, h->lanes_parts_most)) + " lanes per layer");
+                             std::to_string(lanes_parts(nc, h->sw.lanes_parts_most)) + " lanes per layer");
     const dim3 grid((nw + kLanesWaves - 1) / kLanesWaves), block(64 * kLanesWaves);
     const size_t lds = lanes_lds_bytes(nc, h->ndop);
     // (blocks of 5 groups at 8 bins: a batch's ~28 are 6 blocks, an even number; 4: 102.2 us, 5: 101.2, 6: 103.6, round 5.
     // Blocks of 2 at 16 bins -- with two lanes per layer 8 floats per group and lane, 112 registers: 169.5 us; 3 / 4:
     // 130 / 150 registers, 171.0 / 172.6, round 5.)  Lanes per layer in phase 2: lanes_parts
-    const int parts = lanes_parts(nc, h->lanes_parts_most);
+    const int parts = lanes_parts(nc, h->sw.lanes_parts_most);
     if (nb == 8) {
       if (parts == 4)      hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 4>), grid, block, lds, st, A, X);
       else if (parts == 3) hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 3>), grid, block, lds, st, A, X);
@@ -1464,10 +1390,10 @@ int sweep_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, const in
       const unsigned wtiles = (unsigned)((nsh + 64 * kWideM - 1) / (64 * kWideM));
       // no oversampling: every group of a profile reads the same row -- staged in LDS (trx_rows.hip.h);
       // layers whose profiles are much wider than a tile take tiles of 512 bins, the others of 256
-      if (h->osamp == 1 && h->row_staging) {
+      if (h->osamp == 1 && h->sw.row_staging) {
         unsigned m8 = 0;
         for (int c = 0; c < nc; c++)
-          if (((wide_mask >> c) & 1u) && 2 * layer_psmax(h, psmax, r_top - c) + 1 >= h->row_m8_from) m8 |= 1u << c;
+          if (((wide_mask >> c) & 1u) && 2 * layer_psmax(h, psmax, r_top - c) + 1 >= h->sw.row_m8_from) m8 |= 1u << c;
         auto launch = [&](unsigned mask, int m) {
           if (!mask) return;
           W.layer_mask = mask;
@@ -1702,10 +1628,11 @@ void trx_set_log(trx_log_fn fn, void *user, int max_level)
   s.fn = fn; s.user = user; s.max_level = max_level;
 }
 
-int trx_create(const trx_static *s, trx_handle **out)
+namespace {
+
+// the checks that need no handle, in the order callers rely on (which code each bad argument returns)
+int check_static(const trx_static *s)
 {
-  if (!s || !out) return TRX_E_ARG;
-  *out = nullptr;
   if (s->abi_version != TRX_ABI_VERSION) return TRX_E_ARG;
   if (s->nwn < 2 || s->osamp < 1 || s->nown != (s->nwn - 1) * s->osamp + 1) return TRX_E_ARG;
   if (s->ndop < 2 || s->nlor < 2 || s->ndop > kMaxDop) return TRX_E_UNSUPPORTED;
@@ -1715,54 +1642,64 @@ int trx_create(const trx_static *s, trx_handle **out)
   if (s->nown > 2000000000LL) return TRX_E_UNSUPPORTED;     // iown/beg_j are int in the reference too
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || s->device < 0 || s->device >= ndev) return TRX_E_NODEVICE;
-  trx_handle *h = new (std::nothrow) trx_handle();
-  if (!h) return TRX_E_NOMEM;
-  h->device = s->device;
-  int rc = TRX_OK;
-  auto bail = [&](int code) { trx_destroy(h); return code; };
-  if (hipSetDevice(h->device) != hipSuccess) return bail(TRX_E_NODEVICE);
+  return TRX_OK;
+}
+
+// ---- the queues.  Three streams that really overlap: the runtime hands out hardware queues round-robin, and with
+// other streams in the process (an RCCL communicator, the caller's own) two of ours can land on
+// ONE queue -- the CIA kernels then ran after the walks instead of under them, +0.11 ms per
+// spectrum.  So every new stream is probed against the ones it must overlap and replaced (the
+// next creation gets the next queue) until it does; after 12 tries it is taken as it is.
+// (d_flag: 16 ints of device memory; a kernel on `a` waits for one on `b`: only two queues get through that)
+bool streams_overlap(int *d_flag, hipStream_t a, hipStream_t b)
+{
+  int saw = 0; int *d_saw = d_flag + 8;
+  if (hipMemsetAsync(d_flag, 0, 64, a) != hipSuccess || hipStreamSynchronize(a) != hipSuccess) return true;
+  hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(1), 0, a, (volatile int *)d_flag, d_saw);
+  hipLaunchKernelGGL(k_probe_set, dim3(1), dim3(1), 0, b, (volatile int *)d_flag);
+  if (hipStreamSynchronize(a) != hipSuccess || hipStreamSynchronize(b) != hipSuccess) return true;
+  if (hipMemcpy(&saw, d_saw, sizeof saw, hipMemcpyDeviceToHost) != hipSuccess) return true;
+  return saw != 0;
+}
+
+int concurrent_stream(int *d_flag, hipStream_t *out, hipStream_t with1, hipStream_t with2)
+{
+  std::vector<hipStream_t> rejected;
+  int code = TRX_OK;
+  for (int attempt = 0; attempt < 12; attempt++) {
+    hipStream_t s2 = nullptr;
+    if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) { code = TRX_E_HIP; break; }
+    if (attempt == 11 || (streams_overlap(d_flag, with1, s2) && (!with2 || streams_overlap(d_flag, with2, s2)))) { *out = s2; break; }
+    rejected.push_back(s2);                  // kept alive until the end: destroying it would free its slot for the next try
+  }
+  for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
+  return code;
+}
+
+int create_queues(trx_handle *h)
+{
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return TRX_E_HIP;
   {
-    // Three streams that really overlap: the runtime hands out hardware queues round-robin, and with
-    // other streams in the process (an RCCL communicator, the caller's own) two of ours can land on
-    // ONE queue -- the CIA kernels then ran after the walks instead of under them, +0.11 ms per
-    // spectrum.  So every new stream is probed against the ones it must overlap and replaced (the
-    // next creation gets the next queue) until it does; after 12 tries it is taken as it is.
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(TRX_E_HIP);
     DevBuf probe;
-    if ((rc = ensure(h, probe, 64))) return bail(rc);
-    int *d_flag = probe.as<int>(), *d_saw = d_flag + 8;
-    auto overlaps = [&](hipStream_t a, hipStream_t b) -> bool {
-      int saw = 0;
-      if (hipMemsetAsync(d_flag, 0, 64, a) != hipSuccess || hipStreamSynchronize(a) != hipSuccess) return true;
-      hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(1), 0, a, (volatile int *)d_flag, d_saw);
-      hipLaunchKernelGGL(k_probe_set, dim3(1), dim3(1), 0, b, (volatile int *)d_flag);
-      if (hipStreamSynchronize(a) != hipSuccess || hipStreamSynchronize(b) != hipSuccess) return true;
-      if (hipMemcpy(&saw, d_saw, sizeof saw, hipMemcpyDeviceToHost) != hipSuccess) return true;
-      return saw != 0;
-    };
-    auto concurrent_stream = [&](hipStream_t *out, hipStream_t with1, hipStream_t with2) -> int {
-      std::vector<hipStream_t> rejected;
-      int code = TRX_OK;
-      for (int attempt = 0; attempt < 12; attempt++) {
-        hipStream_t s2 = nullptr;
-        if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) { code = TRX_E_HIP; break; }
-        if (attempt == 11 || (overlaps(with1, s2) && (!with2 || overlaps(with2, s2)))) { *out = s2; break; }
-        rejected.push_back(s2);                  // kept alive until the end: destroying it would free its slot for the next try
-      }
-      for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
-      return code;
-    };
-    if ((rc = concurrent_stream(&h->stream4, h->stream, nullptr)) || (rc = concurrent_stream(&h->stream2, h->stream, h->stream4))) return bail(rc);
+    int rc;
+    if ((rc = ensure(h, probe, 64)) || (rc = concurrent_stream(probe.as<int>(), &h->stream4, h->stream, nullptr)) ||
+        (rc = concurrent_stream(probe.as<int>(), &h->stream2, h->stream, h->stream4))) return rc;
   }
   if (hipEventCreateWithFlags(&h->ev_walk1, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_inputs, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_cia, hipEventDisableTiming) != hipSuccess) return bail(TRX_E_HIP);
+      hipEventCreateWithFlags(&h->ev_cia, hipEventDisableTiming) != hipSuccess) return TRX_E_HIP;
+  return TRX_OK;
+}
+
+// grids, communicator, isotopes and molecules: host copies and the pair constants of the layer prologue
+int species_constants(trx_handle *h, const trx_static *s)
+{
   h->wn_i = s->wn_i; h->wn_d = s->wn_d; h->osamp = s->osamp; h->odwn = s->wn_d / s->osamp;
   h->nwn = s->nwn; h->nown = s->nown; h->lo = s->wn_lo; h->hi = s->wn_hi; h->nsh = s->wn_hi - s->wn_lo;
   h->niso = s->niso; h->nmol = s->nmol; h->ndop = s->ndop; h->nlor = s->nlor;
   h->comm = s->comm; h->nranks = s->comm ? std::max(1, s->nranks) : 1; h->rank = s->rank;
-  if (h->comm && !rccl().ok()) return bail(TRX_E_UNSUPPORTED);
+  if (h->comm && !rccl().ok()) return TRX_E_UNSUPPORTED;
   h->iso_mass.assign(s->iso_mass, s->iso_mass + s->niso);
   h->iso_sqrtm.resize(s->niso);
   for (int i = 0; i < s->niso; i++) h->iso_sqrtm[i] = std::sqrt(h->iso_mass[i]);
@@ -1772,98 +1709,141 @@ int trx_create(const trx_static *s, trx_handle **out)
   h->mol_radius.assign(s->mol_radius, s->mol_radius + s->nmol);
   if (s->mol_pol) h->mol_pol.assign(s->mol_pol, s->mol_pol + s->nmol); else h->mol_pol.assign(s->nmol, 0.0);
   if (s->mol_is_h2) h->mol_is_h2.assign(s->mol_is_h2, s->mol_is_h2 + s->nmol); else h->mol_is_h2.assign(s->nmol, 0);
-  for (int i = 0; i < s->niso; i++) if (s->iso_imol[i] < 0 || s->iso_imol[i] >= s->nmol) return bail(TRX_E_ARG);
+  for (int i = 0; i < s->niso; i++) if (s->iso_imol[i] < 0 || s->iso_imol[i] >= s->nmol) return TRX_E_ARG;
   h->pair_csd.assign((size_t)s->niso * s->nmol, 0.0); h->pair_sqrt.assign((size_t)s->niso * s->nmol, 0.0);
   for (int i = 0; i < s->niso; i++)
     for (int j = 0; j < s->nmol; j++) {
       h->pair_csd[(size_t)i * s->nmol + j] = h->mol_radius[j] + h->mol_radius[h->iso_imol[i]];
       h->pair_sqrt[(size_t)i * s->nmol + j] = std::sqrt(1 / h->iso_mass[i] + 1 / h->mol_mass[j]);
     }
-  for (int k = 0; k < s->ncia; k++) {
-    const trx_cia &c = s->cia[k];
-    if (c.nspec < 1 || c.nspec > 2 || c.nwave < 3 || c.ntemp < 3) return bail(TRX_E_ARG);
-    trx_handle::Cia t; t.nspec = c.nspec; t.mol[0] = c.mol[0]; t.mol[1] = c.mol[1];
-    t.wn.assign(c.wn, c.wn + c.nwave); t.temp.assign(c.temp, c.temp + c.ntemp);
-    t.cs.assign(c.cs, c.cs + (size_t)c.nwave * c.ntemp);
-    // table-only halves of the two natural splines (spline_init, pu/src/spline.c:186-206):
-    // second derivatives along T of every row, and the pivots of the wavenumber sweep
-    {
-      const size_t nw = (size_t)c.nwave, nt = (size_t)c.ntemp;
-      std::vector<double> u(std::max(nw, nt)), v(std::max(nw, nt));
-      t.zt.resize(nw * nt);
-      for (size_t i = 0; i < nw; i++)
-        spline_second_derivs(t.zt.data() + i * nt, t.temp.data(), t.cs.data() + i * nt, (long)nt, u.data(), v.data());
-      std::vector<double> zdummy(nw), ydummy(nw, 0.0);
-      t.uw.assign(nw, 0.0);
-      spline_second_derivs(zdummy.data(), t.wn.data(), ydummy.data(), (long)nw, t.uw.data(), v.data());
-      t.ruw.assign(nw, 0.0);                 // reciprocal pivots: the per-layer sweeps multiply instead of dividing
-      for (size_t i = 0; i < (size_t)nw; i++) if (t.uw[i] != 0.0) t.ruw[i] = 1.0 / t.uw[i];
-      t.rh.assign(nw, 0.0);                  // reciprocal spacings 1/(wn[i+1]-wn[i])
-      for (size_t i = 0; i + 1 < (size_t)nw; i++) t.rh[i] = 1.0 / (t.wn[i + 1] - t.wn[i]);
-      // weights of the sums that stand for the two sweeps (k_cia_v, k_cia_z): products of the sweeps' row-to-row factors,
-      // kept where kCiaTerms of them leave less than 2^-60 everywhere in the table
-      if (nw >= 8) {
-        const size_t K = kCiaTerms;
-        std::vector<double> wf(nw * K, 0.0), wb(nw * K, 0.0);
-        double worst = 0.0;
-        for (size_t i = 1; i + 1 < nw; i++) {
-          double p = 1.0;                                   // forward: (-1)^k c[i] c[i-1] .. c[i-k+1], c[m] = h[m-1] / u[m-1] (m >= 2)
-          for (size_t k = 0; k <= K; k++) {
-            if (i < 1 + k) break;                           // row i - k < 1
-            if (k < K) wf[i * K + k] = p; else worst = std::fmax(worst, std::fabs(p));
-            const size_t m = i - k;                         // next factor: -c[m]
-            if (m < 2) break;
-            p *= -((t.wn[m] - t.wn[m - 1]) * t.ruw[m - 1]);
-          }
-          p = 1.0;                                          // backward: (-1)^k d[i] .. d[i+k-1] / u[i+k], d[m] = h[m] / u[m]
-          for (size_t k = 0; k <= K; k++) {
-            const size_t m = i + k;
-            if (m + 1 >= nw) break;                         // row i + k > n - 2
-            if (k < K) wb[i * K + k] = p * t.ruw[m]; else worst = std::fmax(worst, std::fabs(p));
-            p *= -((t.wn[m + 1] - t.wn[m]) * t.ruw[m]);
-          }
-        }
-        if (worst < 0x1p-60) { t.wf = std::move(wf); t.wb = std::move(wb); }
-        if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG) {
-          char msg[160];
-          std::snprintf(msg, sizeof msg, "create: CIA table %d (%zu rows): second derivatives by %s (term %d of the row sums at most %.1e of the first)",
-                        k, nw, t.wf.empty() ? "the two sweeps" : "sums per row", kCiaTerms, worst);
-          log_msg(TRX_LOG_DEBUG, msg);
-        }
-      }
+  return TRX_OK;
+}
+
+// Weights of the sums that stand for the two sweeps of a CIA table's wavenumber spline (k_cia_v, k_cia_z): products of
+// the sweeps' row-to-row factors, kCiaTerms of them per row.  What the sums leave out starts with a product of kCiaTerms
+// factors; the weights are kept where the largest such product in the table (`worst`) is below 2^-60, else the sweeps run.
+void cia_sum_weights(trx_handle::Cia &t, int k)
+{
+  const size_t nw = t.wn.size(), K = kCiaTerms;
+  std::vector<double> wf(nw * K, 0.0), wb(nw * K, 0.0);
+  double worst = 0.0;
+  for (size_t i = 1; i + 1 < nw; i++) {
+    double p = 1.0;                                   // forward: (-1)^k c[i] c[i-1] .. c[i-k+1], c[m] = h[m-1] / u[m-1] (m >= 2)
+    for (size_t k = 0; k <= K; k++) {
+      if (i < 1 + k) break;                           // row i - k < 1
+      if (k < K) wf[i * K + k] = p; else worst = std::fmax(worst, std::fabs(p));
+      const size_t m = i - k;                         // next factor: -c[m]
+      if (m < 2) break;
+      p *= -((t.wn[m] - t.wn[m - 1]) * t.ruw[m - 1]);
     }
-    h->cia.push_back(std::move(t));
+    p = 1.0;                                          // backward: (-1)^k d[i] .. d[i+k-1] / u[i+k], d[m] = h[m] / u[m]
+    for (size_t k = 0; k <= K; k++) {
+      const size_t m = i + k;
+      if (m + 1 >= nw) break;                         // row i + k > n - 2
+      if (k < K) wb[i * K + k] = p * t.ruw[m]; else worst = std::fmax(worst, std::fabs(p));
+      p *= -((t.wn[m + 1] - t.wn[m]) * t.ruw[m]);
+    }
   }
-  if (s->ogrid) {
-    const trx_opacity_grid *g = s->ogrid;
-    if (g->nmol < 1 || g->ntemp < 2 || g->nlayer < 1 || g->nwave != s->nwn || !g->o || !g->temp || !g->mol_index) return bail(TRX_E_ARG);
-    for (long m = 0; m < g->nmol; m++) if (g->mol_index[m] < 0 || g->mol_index[m] >= s->nmol) return bail(TRX_E_ARG);
-    h->has_grid = true; h->og_nmol = g->nmol; h->og_ntemp = g->ntemp; h->og_nlayer = g->nlayer; h->og_nwave = g->nwave;
-    h->og_temp.assign(g->temp, g->temp + g->ntemp); h->og_temp.push_back(HUGE_VAL);   // searched with hi = Ntemp (extinction.c:562)
-    h->og_molidx.assign(g->mol_index, g->mol_index + g->nmol);
-    const size_t no = (size_t)g->nlayer * g->ntemp * g->nmol * g->nwave;
-    if ((rc = ensure(h, h->d_og_o, sizeof(double) * no))) return bail(rc);
-    if (hipMemcpy(h->d_og_o.p, g->o, sizeof(double) * no, hipMemcpyHostToDevice) != hipSuccess) return bail(TRX_E_HIP);
+  if (worst < 0x1p-60) { t.wf = std::move(wf); t.wb = std::move(wb); }
+  if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "create: CIA table %d (%zu rows): second derivatives by %s (the largest product of %d row-to-row factors, the first the sums leave out: %.1e)",
+                  k, nw, t.wf.empty() ? "the two sweeps" : "sums per row", kCiaTerms, worst);
+    log_msg(TRX_LOG_DEBUG, msg);
   }
+}
+
+// one CIA table: host copies and the table-only halves of the two natural splines (spline_init,
+// pu/src/spline.c:186-206) -- second derivatives along T of every row, and the pivots of the wavenumber sweep
+int prepare_cia_table(const trx_cia &c, int k, trx_handle::Cia &t)
+{
+  if (c.nspec < 1 || c.nspec > 2 || c.nwave < 3 || c.ntemp < 3) return TRX_E_ARG;
+  t.nspec = c.nspec; t.mol[0] = c.mol[0]; t.mol[1] = c.mol[1];
+  t.wn.assign(c.wn, c.wn + c.nwave); t.temp.assign(c.temp, c.temp + c.ntemp);
+  t.cs.assign(c.cs, c.cs + (size_t)c.nwave * c.ntemp);
+  const size_t nw = (size_t)c.nwave, nt = (size_t)c.ntemp;
+  std::vector<double> u(std::max(nw, nt)), v(std::max(nw, nt));
+  t.zt.resize(nw * nt);
+  for (size_t i = 0; i < nw; i++)
+    spline_second_derivs(t.zt.data() + i * nt, t.temp.data(), t.cs.data() + i * nt, (long)nt, u.data(), v.data());
+  std::vector<double> zdummy(nw), ydummy(nw, 0.0);
+  t.uw.assign(nw, 0.0);
+  spline_second_derivs(zdummy.data(), t.wn.data(), ydummy.data(), (long)nw, t.uw.data(), v.data());
+  t.ruw.assign(nw, 0.0);                 // reciprocal pivots: the per-layer sweeps multiply instead of dividing
+  for (size_t i = 0; i < nw; i++) if (t.uw[i] != 0.0) t.ruw[i] = 1.0 / t.uw[i];
+  t.rh.assign(nw, 0.0);                  // reciprocal spacings 1/(wn[i+1]-wn[i])
+  for (size_t i = 0; i + 1 < nw; i++) t.rh[i] = 1.0 / (t.wn[i + 1] - t.wn[i]);
+  if (nw >= 8) cia_sum_weights(t, k);
+  return TRX_OK;
+}
+
+int upload_cia(trx_handle *h)
+{
+  int rc;
   for (auto &c : h->cia)
     if ((rc = upload(h, c.d_wn, c.wn)) || (rc = upload(h, c.d_temp, c.temp)) || (rc = upload(h, c.d_cs, c.cs)) ||
         (rc = upload(h, c.d_zt, c.zt)) || (rc = upload(h, c.d_uw, c.uw)) || (rc = upload(h, c.d_ruw, c.ruw)) || (rc = upload(h, c.d_rh, c.rh)) ||
-        (!c.wf.empty() && ((rc = upload(h, c.d_wf, c.wf)) || (rc = upload(h, c.d_wb, c.wb))))) return bail(rc);
-  // the handle does not survive a failed create, so its error text cannot be asked for later:
-  // without a message callback it goes to stderr
-  auto say = [&]() { if (!log_sink().fn) std::fprintf(stderr, "trx_create: %s\n", h->err.c_str()); };
-  StageTimer TC;
-  if ((rc = build_table(h, s)) != TRX_OK) { *out = nullptr; say(); return bail(rc); }
-  TC.lap("Voigt table (plan+kernels+sync)");
-  if ((rc = prepare_lines(h, s)) != TRX_OK) { say(); return bail(rc); }
-  {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "trx_create: %lld lines (%lld in range, %lld co-added groups), %lld wavenumbers [%lld,%lld), "
-                  "Voigt table %dx%d = %lld floats, %zu CIA tables", (long long)s->nlines, (long long)h->stats.nlines_inrange,
-                  (long long)h->ngroups, (long long)s->nwn, (long long)h->lo, (long long)h->hi, s->ndop, s->nlor,
-                  (long long)h->tab_n, h->cia.size());
-    log_msg(TRX_LOG_INFO, buf);
+        (!c.wf.empty() && ((rc = upload(h, c.d_wf, c.wf)) || (rc = upload(h, c.d_wb, c.wb))))) return rc;
+  return TRX_OK;
+}
+
+int opacity_grid(trx_handle *h, const trx_static *s)
+{
+  const trx_opacity_grid *g = s->ogrid;
+  if (!g) return TRX_OK;
+  if (g->nmol < 1 || g->ntemp < 2 || g->nlayer < 1 || g->nwave != s->nwn || !g->o || !g->temp || !g->mol_index) return TRX_E_ARG;
+  for (long m = 0; m < g->nmol; m++) if (g->mol_index[m] < 0 || g->mol_index[m] >= s->nmol) return TRX_E_ARG;
+  h->has_grid = true; h->og_nmol = g->nmol; h->og_ntemp = g->ntemp; h->og_nlayer = g->nlayer; h->og_nwave = g->nwave;
+  h->og_temp.assign(g->temp, g->temp + g->ntemp); h->og_temp.push_back(HUGE_VAL);   // searched with hi = Ntemp (extinction.c:562)
+  h->og_molidx.assign(g->mol_index, g->mol_index + g->nmol);
+  const size_t no = (size_t)g->nlayer * g->ntemp * g->nmol * g->nwave;
+  if (const int rc = ensure(h, h->d_og_o, sizeof(double) * no)) return rc;
+  if (hipMemcpy(h->d_og_o.p, g->o, sizeof(double) * no, hipMemcpyHostToDevice) != hipSuccess) return TRX_E_HIP;
+  return TRX_OK;
+}
+
+// the stages of trx_create behind the handle's allocation, in order; the first that fails ends it
+int create_stages(trx_handle *h, const trx_static *s)
+{
+  int rc;
+  if (hipSetDevice(h->device) != hipSuccess) return TRX_E_NODEVICE;
+  if ((rc = create_queues(h)) || (rc = species_constants(h, s))) return rc;
+  for (int k = 0; k < s->ncia; k++) {
+    trx_handle::Cia t;
+    if ((rc = prepare_cia_table(s->cia[k], k, t))) return rc;
+    h->cia.push_back(std::move(t));
   }
+  if ((rc = opacity_grid(h, s)) || (rc = upload_cia(h))) return rc;
+  StageTimer TC;
+  if ((rc = build_table(h, s))) return rc;
+  TC.lap("Voigt table (plan+kernels+sync)");
+  return prepare_lines(h, s);
+}
+
+}  // namespace
+
+int trx_create(const trx_static *s, trx_handle **out)
+{
+  if (!s || !out) return TRX_E_ARG;
+  *out = nullptr;
+  if (const int rc = check_static(s)) return rc;
+  trx_handle *h = new (std::nothrow) trx_handle();
+  if (!h) return TRX_E_NOMEM;
+  h->device = s->device;
+  read_switches(h->sw);
+  if (const int rc = create_stages(h, s)) {
+    // the handle does not survive a failed create, so its error text cannot be asked for later:
+    // without a message callback it goes to stderr
+    if (!log_sink().fn && !h->err.empty()) std::fprintf(stderr, "trx_create: %s\n", h->err.c_str());
+    trx_destroy(h);
+    return rc;
+  }
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "trx_create: %lld lines (%lld in range, %lld co-added groups), %lld wavenumbers [%lld,%lld), "
+                "Voigt table %dx%d = %lld floats, %zu CIA tables", (long long)s->nlines, (long long)h->stats.nlines_inrange,
+                (long long)h->ngroups, (long long)s->nwn, (long long)h->lo, (long long)h->hi, s->ndop, s->nlor,
+                (long long)h->tab_n, h->cia.size());
+  log_msg(TRX_LOG_INFO, buf);
   *out = h;
   return TRX_OK;
 }
@@ -2373,10 +2353,10 @@ int Run::plan_first_pass()
   }
   d_out = d_spectrum ? (double *)d_spectrum : h->d_spec.as<double>();
   plan_pass(P, r_top, stop_at_hint_ok, h->run_plan);
-  tail_mode = h->ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
+  tail_mode = h->sw.ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
               nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays && plan_is_tail(h->run_plan, kTailSteps);
   // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  tail_direct = tail_mode && h->tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs;
+  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs;
   if ((tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
   // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
   // into a pinned array, one entry per block, and the HOST adds it up behind the kernel (results).  The device-side sum was three
@@ -2385,7 +2365,7 @@ int Run::plan_first_pass()
   // invalidates the L2 under the emission waves (8 us of emission with them, 3 without).  The run's status (slant
   // rays: what the reference exits on) goes into four slots behind the blocks' entries, one per code.
   if (tail_direct && (rc = ensure_pinned(h, h->h_tailblk, 8 * tail_blocks + 16))) return rc;
-  two_queues = h->two_queues && tail_direct && pipelined;      // (tail_direct: nothing behind the tail on the main queue)
+  two_queues = h->sw.two_queues && tail_direct && pipelined;      // (tail_direct: nothing behind the tail on the main queue)
   return TRX_OK;
 }
 

@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../trx_numerics.h"
+
 namespace trx {
 
 constexpr int kMaxChunk   = 32;    // layers swept per top-down step (upper bound)
@@ -70,6 +72,40 @@ struct LayerDev {
 struct SweepWindow {
   int windowed, osamp;
   long long lo, hi, nwn;            // shard [lo, hi) of nwn coarse bins
+};
+
+// ---- the Voigt table's copies: what their layouts (../trx_table.h) share with the kernels ----
+constexpr int kWalkMaxFrame = 16;    // bins of the widest frame (k_line_walk<16>)
+
+// (trx_rows.hip.h)
+constexpr int kRowSpan = 256;                 // cells between the first and the last group of a run, at most
+constexpr int kRowMaxT = 512;                 // bins of the larger tile
+constexpr int kRowTail = kRowMaxT + kRowSpan + 8;   // zero floats the table carries behind its last profile
+
+// The walk's rows (trx_walk.hip.h): every row is a whole number of 64-byte lines, its K entries
+// behind `front` zeros and in front of at least as many -- the bins of a frame are consecutive
+// entries of ONE row, inside ONE or two cache lines, and what a narrow profile does not reach is
+// zero by position.  Profiles of up to 8 entries per row: 4 zeros, the entries, zeros to 16 floats
+// (a frame of 8 bins = one aligned 64-byte line); up to 16 entries: 8 zeros, the entries, zeros to
+// 32 floats; wider ones (no frame reads them) the same with whole lines.
+TRX_HD void walk_row_layout(int K, int &front, int &stride)
+{
+  if (K <= 8) { front = 4; stride = 16; }
+  else if (K <= 16) { front = 8; stride = 32; }
+  else { front = 8; stride = (K + 16 + 15) & ~15; }
+}
+
+// The walk's copy of the Voigt table ("tabW", built by trx_create): per profile `osamp` rows, row
+// `ph` holding the entries q = osamp*kk + ph, kk = 0..K-1, between zeros (walk_row_layout:
+// rows are whole 64-byte lines).  The bins of a frame sit a whole cell apart: they are
+// CONSECUTIVE entries of one row, one or two wide loads per lane instead of a load per bin, inside
+// one cache line for frames of up to 8 bins, and where a profile does not reach the entries are
+// zero by position (kTabPad zeros around the whole).
+struct alignas(16) WalkProfile {
+  uint32_t centre4;                  // byte offset of (row 0, kk = ps / osamp)
+  int32_t rowb;                      // bytes per row (walk_row_layout)
+  int32_t psr;                       // ps % osamp
+  int32_t ps;                        // half-width in table samples
 };
 
 }  // namespace trx

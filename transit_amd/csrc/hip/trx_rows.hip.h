@@ -24,9 +24,6 @@
 
 namespace trx {
 
-constexpr int kRowSpan = 256;                 // cells between the first and the last group of a run, at most
-constexpr int kRowMaxT = 512;                 // bins of the larger tile
-constexpr int kRowTail = kRowMaxT + kRowSpan + 8;   // zero floats the table carries behind its last profile
 static_assert(kRowMaxT <= kTabPad, "a tile's first bin lies at most T - 1 floats in front of a row");
 
 // bytes of dynamic LDS of a 4-wave block whose lanes own M bins each

@@ -355,20 +355,6 @@ constexpr int kWalkSegs = 16;        // isotope blocks whose reaching ranges a l
 constexpr double kRebaseSpan = 0.03125;     // cm-1
 constexpr double kWalkMinTemp = 1.4387752 * kRebaseSpan * 256.0 * 1.05;
 
-constexpr int kWalkMaxFrame = 16;    // bins of the widest frame (k_line_walk<16>)
-
-// The walk's copy of the Voigt table ("tabW", built by trx_create): per profile `osamp` rows, row
-// `ph` holding the entries q = osamp*kk + ph, kk = 0..K-1, between zeros (walk_row_layout,
-// trx_kernels.hip.h: rows are whole 64-byte lines).  The bins of a frame sit a whole cell apart: they are
-// CONSECUTIVE entries of one row, one or two wide loads per lane instead of a load per bin, inside
-// one cache line for frames of up to 8 bins, and where a profile does not reach the entries are
-// zero by position (kTabPad zeros around the whole).
-struct alignas(16) WalkProfile {
-  uint32_t centre4;                  // byte offset of (row 0, kk = ps / osamp)
-  int32_t rowb;                      // bytes per row (walk_row_layout)
-  int32_t psr;                       // ps % osamp
-  int32_t ps;                        // half-width in table samples
-};
 // frames of at least this many bins read tabW (the narrower ones: a load per bin from the table itself)
 constexpr int kWalkRowsFrom = 4;
 

@@ -48,6 +48,51 @@ void parallel_parts(int64_t n, int parts, F f, int64_t grain = 65536)
   for (auto &x : th) x.join();
 }
 
+// the parts' flags OR-ed together: f(begin, end) -> int
+template <class F>
+int parallel_flags(int64_t n, int parts, F f, int64_t grain = 65536)
+{
+  std::vector<int> part((size_t)std::max(parts, 1), 0);
+  parallel_parts(n, parts, [&](int t, int64_t i0, int64_t i1) { part[(size_t)t] = f(i0, i1); }, grain);
+  int any = 0;
+  for (int x : part) any |= x;
+  return any;
+}
+
+// smallest and largest of what f(i, use) gives over [0, n); use = false leaves element i out
+// (nothing used: lo = +max, hi = lowest of T)
+template <class T> struct MinMax { T lo, hi; };
+template <class T, class F>
+MinMax<T> parallel_minmax(int64_t n, int parts, T most, T least, F f, int64_t grain = 65536)
+{
+  std::vector<MinMax<T>> part((size_t)std::max(parts, 1), MinMax<T>{most, least});
+  parallel_parts(n, parts, [&](int t, int64_t i0, int64_t i1) {
+    MinMax<T> m{most, least};
+    for (int64_t i = i0; i < i1; i++) { bool use = true; const T v = f(i, use); if (use) { m.lo = std::min(m.lo, v); m.hi = std::max(m.hi, v); } }
+    part[(size_t)t] = m;
+  }, grain);
+  MinMax<T> r{most, least};
+  for (const MinMax<T> &m : part) { r.lo = std::min(r.lo, m.lo); r.hi = std::max(r.hi, m.hi); }
+  return r;
+}
+
+// Groups per range of the walk: ~2 rounds of resident waves (the hardware balances the rounds).  Taken from
+// the WHOLE list, not from what reaches a shard: the range size is part of the order of the
+// sums, and a shard's spectrum must be the same bits as the unsharded one.  (Shorter ranges for
+// small shards were measured: 1/8 of the demo 0.267 -> 0.259 ms with 32, slower with 16.)
+// Lists of more than a million groups get MORE ranges of 64 groups, not longer ones (up to 2^17
+// ranges: their partial records are ~50 MB per step and buffer): a rank of an N-way job walks 1/N
+// of them, and a range is one wave's serial work -- with 512-group ranges one shard of eight of an
+// 8*10^6-line list had 1 700 waves for 1 024 SIMDs (its 2-bin walk 226 us instead of 108).
+// So: 32, then up to 64 past 16384 ranges, then up to 512 past 131072.
+inline int groups_per_range(int64_t ngroups)
+{
+  int ngw = 32;
+  while (ngw < 64 && ngroups / ngw > 16384) ngw *= 2;
+  while (ngw < 512 && ngroups / ngw > 131072) ngw *= 2;
+  return ngw;
+}
+
 // cnt[k] = number of the block's groups with key >= k, k = 0..nkey (keys descend along the block)
 template <class Key>
 void count_ge(const int32_t *giown, int g0, int g1, long long nkey, Key key, int32_t *cnt, int nth, int64_t grain = 65536)
