@@ -350,6 +350,57 @@ int  trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */
                            double *const *sums /* [k] -> [nbands][2] */,
                            double *const *contrib /* [k] -> [nbands][atm[j].nlayer] */);
 
+/* Detector pixels at Doppler shifts on the device: the last step of a high-resolution cross-correlation retrieval --
+ * the spectrum shifted to the planet's velocity at each exposure, convolved with the spectrograph's Gaussian
+ * line-spread function and sampled at the detector's pixel centres -- without handing the spectrum back, and without
+ * a band per (pixel, shift) pair: the pixel set is installed once, the shifts come with every run, ranges and weights
+ * are made on the device.
+ *
+ * shift[v] = nu_observed / nu_rest: 1 at rest, below 1 for a receding source.  The pair out[v][p] is exactly the pair
+ * of the band TRX_BAND_GAUSS{centre = centre_p / shift_v, fwhm = fwhm_p / shift_v, cut} under the rules of
+ * trx_set_bands above:
+ *   centre' = centre_p / shift_v,  fwhm' = fwhm_p / shift_v,  sigma = fwhm' / (2 sqrt(2 ln 2))
+ *   i_lo = ceil((centre' - cut*sigma - wn_i)/wn_d),  i_hi = floor((centre' + cut*sigma - wn_i)/wn_d),
+ *   clipped to [0, nwn) and then to the shard (an empty range is allowed)
+ *   w_i = exp(-((nu_i - centre')/sigma)^2 / 2)
+ *   out[v][p] = (sum of w_i S_i, sum of w_i) over those bins; the pixel's value is out[v][p][0] / out[v][p][1].
+ * The two divisions and the range expressions are IEEE double with every operation rounded once (no fused
+ * multiply-add, on the device either): the range of a pair is the same integers as the equivalent band's.  The
+ * weight is the expression the band kernel evaluates (one device function serves both): the two paths differ in the
+ * order of their sums only.
+ *
+ * No atomics: the bits of a pair depend on the spectrum, that pixel, that shift and the shard only -- not on the other
+ * pixels or shifts of the call, the launch, the batch way that ran it or the handle's depth hint.  (A window of fewer
+ * than 192 in-shard bins is added by one lane in ascending bin order; a longer one by a wave, lane l adding its bins
+ * l, l + 64, ... in that order, then a fixed butterfly over the lanes.)  A sharded job adds the ranks' pairs in rank
+ * order, as for bands; a pair with no bin in the shard is exactly (+0, +0).
+ *
+ * trx_set_pixels copies the set to the device (px NULL or npix = 0: clear it).  It returns TRX_E_ARG, the reason in
+ * trx_last_error (naming "pixel N" where one pixel is at fault), for npix < 0, a NULL array, a non-finite or <= 0
+ * centre or fwhm, a non-finite or <= 0 cut; a refused set leaves the previous one in force.
+ * trx_run_pixels is trx_run plus the pairs: spectrum may be NULL (then the spectrum stays on the device), and when it
+ * is given it holds the bits trx_run gives.  TRX_E_ARG with no set installed, nshift < 1, shift or out NULL, a
+ * non-finite or <= 0 shift (naming "shift N").  A run that fails leaves out undefined.  trx_run, trx_run_bands and
+ * trx_run_contrib on a handle with pixels installed are unchanged.
+ * trx_batch_set_pixels installs the same set on every handle of the batch, or on none (its reason through
+ * trx_last_error(NULL)); trx_run_batch_pixels is trx_run_batch with atmosphere j's own shifts shift[j] ([nshift]) and
+ * its pairs out[j] ([nshift][npix][2]). */
+typedef struct {
+  int64_t npix;
+  const double *centre;     /* [npix] pixel centres, cm-1, OBSERVED frame; finite, > 0; any order         */
+  const double *fwhm;       /* [npix] line-spread FWHM at that pixel, cm-1, observed frame; finite, > 0   */
+  double cut;               /* half-width of the window in sigmas; finite, > 0                            */
+} trx_pixels;
+int  trx_set_pixels(trx_handle *h, const trx_pixels *px);
+int  trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                    double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                    int32_t nshift, const double *shift /* [nshift] */,
+                    double *out /* [nshift][npix][2], host */, trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_pixels(trx_batch *b, const trx_pixels *px);
+int  trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                          int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
+                          double *const *out /* [k] -> [nshift][npix][2] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

@@ -83,6 +83,10 @@ class TrxBand(C.Structure):
                 ("weights", c_double_p), ("centre", C.c_double), ("fwhm", C.c_double), ("cut", C.c_double)]
 
 
+class TrxPixels(C.Structure):
+    _fields_ = [("npix", C.c_int64), ("centre", c_double_p), ("fwhm", c_double_p), ("cut", C.c_double)]
+
+
 class TrxStats(C.Structure):
     _fields_ = [
         ("nlines_inrange", C.c_int64), ("ngroups", C.c_int64), ("nadd", C.c_int64),
@@ -151,4 +155,19 @@ def bind_contrib_api(lib):
     lib.trx_run_batch_contrib.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
                                           C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_contrib.restype = C.c_int
+    return lib
+
+
+def bind_pixels_api(lib):
+    """argtypes/restypes of the detector-pixel entry points (trx_set_pixels, trx_run_pixels and their batch forms)."""
+    lib.trx_set_pixels.argtypes = [C.c_void_p, C.POINTER(TrxPixels)]
+    lib.trx_set_pixels.restype = C.c_int
+    lib.trx_run_pixels.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                   c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_pixels.restype = C.c_int
+    lib.trx_batch_set_pixels.argtypes = [C.c_void_p, C.POINTER(TrxPixels)]
+    lib.trx_batch_set_pixels.restype = C.c_int
+    lib.trx_run_batch_pixels.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
+                                         C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_pixels.restype = C.c_int
     return lib

@@ -36,6 +36,7 @@
 #include "trx_tail.hip.h"
 #include "trx_lanes.hip.h"
 #include "trx_bands.hip.h"
+#include "trx_pixels.hip.h"
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 #include "../trx_plan.h"
@@ -71,6 +72,14 @@ struct BandSet {
   DevBuf d_bands, d_pieces, d_w, d_part;             // BandDev[nbands], BandPiece[npieces], WEIGHTS' in-shard weights, [npieces][2]
   PinnedBuf h_out;                                   // [nbands][2]: k_band_sums stores the run's sums here
 };
+
+// a pixel set installed by trx_set_pixels (trx_pixels.hip.h): the arrays as given -- ranges and weights are made on the device, per run
+struct PixelSet {
+  int64_t npix = 0; double cut = 0;
+  DevBuf d_centre, d_fwhm;                           // [npix] each
+};
+// a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift
+struct PixelRun { const PixelSet *set; int32_t nshift; };
 
 // The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
 // alone, before any stage.  Each selects between two forms of the same computation that give the same
@@ -188,6 +197,8 @@ struct trx_handle {
   // trx_run_contrib (trx_contrib.hip.h): sub-piece rows [npieces * kContribSplit][nlayer] and the pinned result [nbands][nlayer], sized on
   // first use and when the set or nlayer grows
   DevBuf d_cpart; PinnedBuf h_contrib;
+  std::unique_ptr<PixelSet> pixels;                    // trx_set_pixels (null: none)
+  DevBuf d_pixshift, d_pixout;                         // trx_run_pixels: the run's shifts [nshift] and its pairs [nshift][npix][2], grown on demand
 };
 
 namespace {
@@ -1917,10 +1928,12 @@ struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swe
 // bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
 // spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
 // contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
+// px: a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it
 struct Run {
   // ---- what the run is given
   trx_handle *const h; const trx_atm *const a; const trx_opts *const o;
   double *const spectrum; void *const d_spectrum; trx_debug *const dbg; const BandSet *const bs; const bool contrib;
+  const PixelRun *const px;
   const std::chrono::steady_clock::time_point t_host0;
 
   // ---- its shape and modes
@@ -2011,7 +2024,7 @@ struct Run {
   int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
   int side_work(SideWork &S); int queue_cia(); int join_early();
   // ... the spectrum of what they swept, the way back
-  int spectrum_kernel(); int ray_tail(); int band_kernels(); int results();
+  int spectrum_kernel(); int ray_tail(); int band_kernels(); int pixel_kernels(); int results();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2356,7 +2369,7 @@ int Run::plan_first_pass()
   tail_mode = h->sw.ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
               nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays && plan_is_tail(h->run_plan, kTailSteps);
   // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs;
+  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs && !px;
   if ((tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
   // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
   // into a pinned array, one entry per block, and the HOST adds it up behind the kernel (results).  The device-side sum was three
@@ -2641,6 +2654,29 @@ int Run::band_kernels()
   return TRX_OK;
 }
 
+// ---- the detector pixels of this pass's spectrum at the run's shifts (trx_pixels.hip.h), behind it on its queue like
+// the band kernels; a pass that resumes deeper queues it again behind its own spectrum.
+int Run::pixel_kernels()
+{
+  if (!px) return TRX_OK;
+  const PixelSet &S = *px->set;
+  PixArgs PA{};
+  PA.spec = d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
+  PA.shift = h->d_pixshift.as<double>(); PA.out = h->d_pixout.as<double>();
+  PA.npix = S.npix; PA.npairs = S.npix * (int64_t)px->nshift;
+  PA.nwn = h->nwn; PA.lo = h->lo; PA.hi = h->hi; PA.cut = S.cut; PA.fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
+  PA.wn_i = h->wn_i; PA.wn_d = h->wn_d;
+  const int64_t blocks = (PA.npairs + kPixBlock - 1) / kPixBlock;
+  // (every address the kernel reads or writes: the spectrum over [0, hi - lo) = [0, nsh), the set's arrays, the shifts, the pairs)
+  if (!PA.spec || !PA.centre || !PA.fwhm || !PA.shift || !PA.out || S.npix < 1 || px->nshift < 1 || h->hi - h->lo != nsh ||
+      S.d_centre.bytes < sizeof(double) * (size_t)S.npix || S.d_fwhm.bytes < sizeof(double) * (size_t)S.npix ||
+      h->d_pixshift.bytes < sizeof(double) * (size_t)px->nshift || h->d_pixout.bytes < sizeof(double) * 2 * (size_t)PA.npairs ||
+      blocks < 1 || blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the pixel kernel (not launched)");
+  hipLaunchKernelGGL(k_pixel_pairs, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
+  return TRX_OK;
+}
+
 // ---- results back: the copies, the wait, and (direct tail) the flags summed on the host
 int Run::results()
 {
@@ -2681,7 +2717,7 @@ int Run::pass()
   int rc;
   for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
   if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-  return (rc = spectrum_kernel()) || (rc = band_kernels()) ? rc : results();
+  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = pixel_kernels()) ? rc : results();
 }
 
 // Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
@@ -2772,14 +2808,14 @@ int Run::finish()
 }  // namespace
 
 static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg,
-                    const BandSet *bs = nullptr, bool contrib = false)
+                    const BandSet *bs = nullptr, bool contrib = false, const PixelRun *px = nullptr)
 {
   const auto t_host0 = std::chrono::steady_clock::now();
   if (!h || !a || !o) return TRX_E_ARG;
   int rc;
   if ((rc = run_check(h, a, o))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  Run R{h, a, o, spectrum, d_spectrum, dbg, bs, contrib, t_host0};       // (behind run_check: its members are made from the run's shape)
+  Run R{h, a, o, spectrum, d_spectrum, dbg, bs, contrib, px, t_host0};       // (behind run_check: its members are made from the run's shape)
   if ((rc = R.layout()) || (rc = R.front_maxima()) || (rc = R.workspaces()) || (rc = R.front_inputs()) || (rc = R.plan_first_pass()) || (rc = R.pass()))
     return rc;
   if (R.stop_at_hint_ok && R.flags[0] > 0 && R.r_top >= 0 && (rc = R.resume())) return rc;
@@ -2967,6 +3003,62 @@ int trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   return rc;
 }
 
+// ---- detector pixels at Doppler shifts (trx_pixels.hip.h) ------------------------------------------
+// The set, checked whole before anything is replaced; the device gets the arrays as they are.
+static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<PixelSet> &out)
+{
+  out.reset();
+  if (!px || px->npix == 0) return TRX_OK;              // (clear)
+  if (px->npix < 0) return fail(h, TRX_E_ARG, "pixels: npix < 0");
+  if (!px->centre || !px->fwhm) return fail(h, TRX_E_ARG, "pixels: NULL centre or fwhm array");
+  if (!std::isfinite(px->cut) || !(px->cut > 0)) return fail(h, TRX_E_ARG, "pixels: cut must be finite and > 0");
+  if (px->npix > 0x7fffffffLL) return fail(h, TRX_E_ARG, "pixels: npix above 2^31 - 1");
+  for (int64_t p = 0; p < px->npix; p++) {
+    if (!std::isfinite(px->centre[p]) || !(px->centre[p] > 0)) return fail(h, TRX_E_ARG, "pixel " + std::to_string(p) + ": centre must be finite and > 0");
+    if (!std::isfinite(px->fwhm[p]) || !(px->fwhm[p] > 0)) return fail(h, TRX_E_ARG, "pixel " + std::to_string(p) + ": fwhm must be finite and > 0");
+  }
+  std::unique_ptr<PixelSet> S(new (std::nothrow) PixelSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "pixels: out of host memory");
+  S->npix = px->npix; S->cut = px->cut;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload_raw(h, S->d_centre, px->centre, (size_t)px->npix)) || (rc = upload_raw(h, S->d_fwhm, px->fwhm, (size_t)px->npix))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
+  out = std::move(S);
+  return TRX_OK;
+}
+
+int trx_set_pixels(trx_handle *h, const trx_pixels *px)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<PixelSet> S;
+  if (const int rc = make_pixel_set(h, px, S)) return rc;
+  h->pixels = std::move(S);
+  return TRX_OK;
+}
+
+int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                   double *out, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  if (!h->pixels) return fail(h, TRX_E_ARG, "trx_run_pixels: no pixel set installed (trx_set_pixels)");
+  if (nshift < 1) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift < 1");
+  if (!shift) return fail(h, TRX_E_ARG, "trx_run_pixels: shift is NULL");
+  if (!out) return fail(h, TRX_E_ARG, "trx_run_pixels: out is NULL");
+  for (int32_t v = 0; v < nshift; v++)
+    if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, "trx_run_pixels: shift " + std::to_string(v) + " must be finite and > 0");
+  const PixelRun PR{h->pixels.get(), nshift};
+  if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift * npix above what one launch takes");
+  const size_t out_bytes = sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
+  if ((rc = ensure(h, h->d_pixout, out_bytes)) || (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift))) return rc;
+  if ((rc = run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR))) return rc;
+  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, out_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
 // ---- several atmospheres per call -----------------------------------------------------------------
 // A retrieval driver runs many chains over one line list (the reference: one run_transit per atmosphere,
 // transit.c:118-122, one process each).  One spectrum leaves the device idle between its kernels and while
@@ -2984,6 +3076,7 @@ struct trx_batch {
   int32_t k = 0; const trx_atm *atm = nullptr; const trx_opts *opts = nullptr; double *const *spectra = nullptr;
   double *const *sums = nullptr;                     // trx_run_batch_bands: the band sums instead of the spectra
   double *const *contrib = nullptr;                  // trx_run_batch_contrib: and the contribution functions
+  int32_t nshift = 0; const double *const *shifts = nullptr; double *const *pix = nullptr;      // trx_run_batch_pixels: the pixel pairs instead
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -3027,7 +3120,8 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
         for (;;) {
           const int32_t j = b->next.fetch_add(1);
           if (j >= b->k) break;
-          const int rc = b->contrib ? trx_run_contrib(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
+          const int rc = b->pix ? trx_run_pixels(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
+                       : b->contrib ? trx_run_contrib(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
                        : b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
                                  : trx_run(b->hs[(size_t)i], b->atm + j, b->opts, b->spectra[j], nullptr);
           if (rc != TRX_OK) {
@@ -3048,11 +3142,12 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
 static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
-                      double *const *contrib = nullptr)
+                      double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
   b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
+  b->nshift = nshift; b->shifts = shifts; b->pix = pix;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3103,6 +3198,34 @@ int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx
     if (!contrib[j]) { g_comm_err = "trx_run_batch_contrib: contrib[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   }
   return batch_call(b, k, atm, opts, nullptr, sums, contrib);
+}
+
+// every handle of the batch gets the same pixel set, or none does
+int trx_batch_set_pixels(trx_batch *b, const trx_pixels *px)
+{
+  g_comm_err.clear();
+  if (!b) return TRX_E_ARG;
+  std::vector<std::unique_ptr<PixelSet>> sets(b->hs.size());
+  for (size_t i = 0; i < b->hs.size(); i++) {
+    const int rc = make_pixel_set(b->hs[i], px, sets[i]);
+    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
+  }
+  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->pixels = std::move(sets[i]);
+  return TRX_OK;
+}
+
+int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
+                         double *const *out)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !out))) { g_comm_err = "trx_run_batch_pixels: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->pixels) { g_comm_err = "trx_run_batch_pixels: no pixel set installed (trx_batch_set_pixels)"; return TRX_E_ARG; }
+  if (nshift < 1) { g_comm_err = "trx_run_batch_pixels: nshift < 1"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) {
+    if (!shift[j]) { g_comm_err = "trx_run_batch_pixels: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+    if (!out[j]) { g_comm_err = "trx_run_batch_pixels: out[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  }
+  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, out);
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

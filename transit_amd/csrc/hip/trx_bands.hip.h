@@ -49,6 +49,15 @@ struct BandArgs {
   double wn_i, wn_d;
 };
 
+// the weight of global bin g under a Gaussian (centre, sigma): what TRX_BAND_GAUSS defines.  The pixel kernel
+// (trx_pixels.hip.h) calls it too: the two paths differ in the order of their sums only.
+__device__ __forceinline__ double gauss_weight(double wn_i, double wn_d, int64_t g, double centre, double sigma)
+{
+  const double nu = wn_i + (double)g * wn_d;
+  const double x = (nu - centre) / sigma;
+  return exp(-0.5 * (x * x));
+}
+
 __global__ __launch_bounds__(64 * kBandWaves) void k_band_pieces(BandArgs A)
 {
   const int lane = (int)(threadIdx.x & 63);
@@ -63,9 +72,7 @@ __global__ __launch_bounds__(64 * kBandWaves) void k_band_pieces(BandArgs A)
       const int t = k * 64 + lane;
       if (t < P.len) {
         const int64_t j = P.start + t;
-        const double nu = A.wn_i + (double)(A.lo + j) * A.wn_d;
-        const double x = (nu - B.centre) / B.sigma;
-        const double w = exp(-0.5 * (x * x));
+        const double w = gauss_weight(A.wn_i, A.wn_d, A.lo + j, B.centre, B.sigma);
         s += w * A.spec[j]; sw += w;
       }
     }

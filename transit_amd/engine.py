@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _abi
 from . import bands as _bands
+from . import pixels as _pixels
 from .build import lib_path
 
 
@@ -201,6 +202,7 @@ def hip_library():
         lib.trx_run_device.restype = C.c_int
         _abi.bind_bands_api(lib)
         _abi.bind_contrib_api(lib)
+        _abi.bind_pixels_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -264,6 +266,28 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_contrib", self._last_error())
         return (sums, contrib, spec) if spectrum else (sums, contrib)
+
+    def set_pixels(self, pixels):
+        """trx_set_pixels: install a detector (a transit_amd.pixels.Pixels; None or an empty one: clear it)."""
+        n = len(pixels) if pixels is not None else 0
+        rc = self._lib.trx_set_pixels(self._h, C.byref(_pixels.to_c(pixels)) if n else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_pixels", self._last_error())
+        self.npix = n
+
+    def run_pixels(self, atm, opts, shifts, spectrum: bool = False):
+        """trx_run_pixels: the pairs [nshift, npix, 2] of this shard at the Doppler shifts given (nu_observed / nu_rest)
+        -- and, with spectrum=True, (pairs, spectrum), the spectrum bit for bit what run() gives."""
+        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        out = np.zeros((sh.size, getattr(self, "npix", 0), 2))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_pixels(self._h, C.byref(atm), C.byref(opts),
+                                      spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                      int(sh.size), sh.ctypes.data_as(_abi.c_double_p),
+                                      out.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_pixels", self._last_error())
+        return (out, spec) if spectrum else out
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -346,6 +370,30 @@ class Batch:
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_contrib", self._err())
         return sums, contrib
+
+    def set_pixels(self, pixels):
+        """trx_batch_set_pixels: the same detector on every handle of the batch, or on none."""
+        n = len(pixels) if pixels is not None else 0
+        rc = self._lib.trx_batch_set_pixels(self._b, C.byref(_pixels.to_c(pixels)) if n else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_pixels", self._err())
+        self.npix = n
+
+    def run_pixels(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
+        """trx_run_batch_pixels: [K, nshift, npix, 2] for shifts of shape [K][nshift] (atmosphere j at its own shifts),
+        each atmosphere's pairs what Engine.run_pixels gives, bit for bit."""
+        k = len(atms)
+        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        if sh.ndim != 2 or sh.shape[0] != k:
+            raise ValueError("Batch.run_pixels: shifts of shape [K][nshift], one row per atmosphere")
+        out = np.zeros((k, sh.shape[1], getattr(self, "npix", 0), 2))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        ps = (_abi.c_double_p * max(k, 1))(*[sh[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_pixels(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_pixels", self._err())
+        return out
 
     def close(self):
         if self._b:
