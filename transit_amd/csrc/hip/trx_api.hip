@@ -103,6 +103,7 @@ struct Switches {
   bool cia_window = true;           // the CIA spline solved for the table rows a run needs (TRX_CIA_WINDOW=0: the whole table; test_gpu_cia_window)
   bool two_queues = true;           // the second walk of a hinted run on a queue of its own, next to the first (TRX_TWO_QUEUES=0: behind it; A/B, tests)
   bool tail_direct = true;          // ... which writes spectrum and flags straight into pinned host memory (TRX_TAIL_DIRECT=0: copy commands)
+  bool range_reach = true;          // k_line_walk tests a group's reach against its RANGE's widest profile and leaves a range out of all reach with zeros at its start (TRX_RANGE_REACH=0: the step's bound, every range walked; needs TablePlan::psize_mono; test_gpu_walk_reach, A/B)
   bool shard_frames = true;         // frames sized for the Doppler indices the lines in reach can take (TRX_SHARD_FRAMES=0: for the isotope's whole wavenumber range; test_gpu_shard_frames)
 };
 
@@ -309,6 +310,7 @@ void read_switches(Switches &w)
   w.cia_window = num("TRX_CIA_WINDOW", 1) != 0;
   w.two_queues = num("TRX_TWO_QUEUES", 1) != 0;
   w.tail_direct = num("TRX_TAIL_DIRECT", 1) != 0;
+  w.range_reach = num("TRX_RANGE_REACH", 1) != 0;
   w.shard_frames = num("TRX_SHARD_FRAMES", 1) != 0;
 }
 
@@ -617,7 +619,7 @@ int walk_records(trx_handle *h, const trx_static *s, const LinePrep &Q)
                      h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), h->d_linebase.as<double>());
   if ((rc = ensure(h, h->d_rinfo, sizeof(RangeInfo) * (size_t)std::max(h->nwaves, 1)))) return rc;
   hipLaunchKernelGGL(k_range_info, dim3((unsigned)((h->nwaves + 255) / 256)), dim3(256), 0, h->stream, h->nwaves, h->ngw, s->niso,
-                     h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), h->d_rinfo.as<RangeInfo>());
+                     h->d_wbase.as<int32_t>(), L.gblock, L.gfirst, L.gcount, h->d_walk.as<WalkLine>(), s->osamp, h->d_rinfo.as<RangeInfo>());
   return TRX_OK;
 }
 
@@ -1229,6 +1231,7 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, i
   A.lines = h->d_walk.as<WalkLine>(); A.rinfo = h->d_rinfo.as<RangeInfo>(); A.gfirst = h->d_gfirst.as<int32_t>(); A.gcount = h->d_gcount.as<int32_t>();
   A.gblock = h->d_gblock.as<int32_t>(); A.P = P;
   A.niso = h->niso; A.nlor = h->nlor; A.ndop = h->ndop; A.osamp = h->osamp; A.lo = h->lo; A.hi = h->hi;
+  A.wn_i = h->wn_i; A.odwn = h->odwn; A.range_reach = h->sw.range_reach && h->psize_mono;      // (a table whose profiles narrow somewhere as the Doppler index rises keeps the step's bound)
   A.r_top = r_top; A.nc = nc; A.Y = Y; A.wcut = d_wcut; A.kmax = M.d_kmax; A.ethresh = M.ethresh;
   A.nmx = M.nmx; A.iso_mx = M.d_iso_mx; A.permol = M.permol; A.sticky_idop = M.d_sticky;
   A.dthr = h->d_dopthr.as<double>(); A.e2tab = h->d_e2tab.as<double>();

@@ -95,6 +95,75 @@ TRX_HD void walk_row_layout(int K, int &front, int &stride)
   else { front = 8; stride = (K + 16 + 15) & ~15; }
 }
 
+// ---- how far a line range of the walk can reach (k_line_walk; checked on the host by tests/reach_check.cpp) ----
+// A group whose anchor sits at fine-grid phase imod of its cell (0 <= imod < osamp) touches a bin only when a
+// lane's profile half-size ps has imod <= ps (the cell's own bin) or osamp - imod <= ps (the bin above).  The
+// step's bound psm_s (LayerDev::psmax, wave maximum) is the widest profile of the isotope's WHOLE wavenumber
+// range; a range of 32-512 groups takes far narrower ones where widths are Doppler-dominated (width ~ wavenumber).
+//
+// Can a lane take the sticky profile somewhere in the range?  Only on an anchor below its wcut.  Anchors lie no
+// lower than half a fine-grid step below their grid point (iown is the NEAREST point, trx_groups.h) and the
+// range's lowest anchor is in cell1: the grid point one fine step below that cell's lower edge is below every
+// anchor of the range.  (wn_i + k*odwn as group_lines forms it; a contraction to one rounding moves it by an
+// ulp, against half a step of margin.)
+TRX_HD bool walk_may_stick(double wn_i, double odwn, int osamp, int cell1, double wcut)
+{
+  return wn_i + ((double)cell1 * (double)osamp - 1.0) * odwn < wcut;
+}
+
+// One lane's bound: ps_first is the half-size at the Doppler index of the range's FIRST anchor -- wavenumbers
+// descend along a range, the index only falls, and on a table with TablePlan::psize_mono no profile is wider
+// than the one an index above it: every "own" profile of the range is at most ps_first.  The sticky profile
+// (possibly the block's widest: deep, Lorentz-dominated layers) counts only where the lane can take it.
+TRX_HD int walk_lane_reach(int ps_first, int ps_sticky, bool may_stick)
+{
+  const int st = may_stick ? ps_sticky : 0;
+  return ps_first > st ? ps_first : st;
+}
+
+// The range's bound from the wave maximum of its valid lanes' bounds (idle lanes enter as 0): never above the
+// step's, and the step's alone where the table is not monotone or the switch (TRX_RANGE_REACH=0) says so.
+TRX_HD int walk_range_reach(int psm_s, int lanes_max, bool use_range)
+{
+  return use_range && lanes_max < psm_s ? lanes_max : psm_s;
+}
+
+// A group at phase imod is out of reach of every bin under bound `reach`: strictly inside the zone
+// (reach, osamp - reach).  (reach >= osamp / 2: the zone is empty.)
+TRX_HD bool walk_group_out_of_reach(int imod, int osamp, int reach)
+{
+  return imod > reach && imod < osamp - reach;
+}
+
+// The same test as the walk makes it per group: the slots of a frame of NB bins (slot k = bin cell - Rc + k,
+// Rc = NB/2 - 1, at fine distance |(k - Rc)*osamp - imod|) within `reach` = psq*osamp + psr of the anchor.
+// 0 exactly when walk_group_out_of_reach.
+TRX_HD unsigned walk_cand_slots(int NB, int imod, int osamp, int reach, int psq, int psr)
+{
+  if (NB == 2) return (imod <= reach ? 1u : 0u) | (osamp - imod <= reach ? 2u : 0u);
+  const int Rc = NB / 2 - 1;
+  const int klo = Rc - psq + (imod > psr ? 1 : 0), khi = Rc + psq + (imod + psr >= osamp ? 1 : 0);
+  return ((2u << khi) - 1u) & ~((1u << klo) - 1u);   // (0 <= klo, khi < NB by the choice of NB; klo = khi + 1: none)
+}
+
+// RangeInfo::pad: the smallest and the largest phase of a range's anchors, 16 bits each -- for ranges whose
+// anchors share ONE cell, on grids with osamp < 65536.  Any other range gets kRangeNoExit: smallest phase 0,
+// which is inside no zone (reach >= 0), so such a range is always walked.
+constexpr int32_t kRangeNoExit = 0;
+TRX_HD int32_t walk_range_phases(bool one_cell, int osamp, int imod_min, int imod_max)
+{
+  if (!one_cell || osamp >= 65536) return kRangeNoExit;
+  return (int32_t)((uint32_t)imod_min | ((uint32_t)imod_max << 16));
+}
+
+// Every group of the range is out of reach (walk_group_out_of_reach for its extreme phases, hence for all):
+// the range adds nothing to any bin and its records are zeros.
+TRX_HD bool walk_range_out_of_reach(int32_t phases, int osamp, int reach)
+{
+  const int lo = (int)((uint32_t)phases & 0xffffu), hi = (int)((uint32_t)phases >> 16);
+  return walk_group_out_of_reach(lo, osamp, reach) && walk_group_out_of_reach(hi, osamp, reach);
+}
+
 // The walk's copy of the Voigt table ("tabW", built by trx_create): per profile `osamp` rows, row
 // `ph` holding the entries q = osamp*kk + ph, kk = 0..K-1, between zeros (walk_row_layout:
 // rows are whole 64-byte lines).  The bins of a frame sit a whole cell apart: they are

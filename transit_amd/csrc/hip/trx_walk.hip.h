@@ -401,12 +401,12 @@ void k_walk_marks(int nwaves, int ngw, int niso, const int32_t *__restrict__ wba
 
 // what a wave needs to know about its range before it can ask for anything else (k_line_walk_lanes: one load
 // instead of a chain of five through wbase, gblock, gfirst, gcount and the first line's record)
-struct alignas(32) RangeInfo { int32_t l0, l1, b, cell0; double wavn0; int32_t cell1, pad; };      // cell0 / cell1: of the first / last group
+struct alignas(32) RangeInfo { int32_t l0, l1, b, cell0; double wavn0; int32_t cell1, phases; };      // cell0 / cell1: of the first / last group; phases: walk_range_phases (trx_device.h)
 
 __global__ __launch_bounds__(256)
 void k_range_info(int nwaves, int ngw, int niso, const int32_t *__restrict__ wbase, const int32_t *__restrict__ gblock,
                   const int32_t *__restrict__ gfirst, const int32_t *__restrict__ gcount, const WalkLine *__restrict__ lines,
-                  RangeInfo *__restrict__ out)
+                  int osamp, RangeInfo *__restrict__ out)
 {
   const int w = blockIdx.x * 256 + threadIdx.x;
   if (w >= nwaves) return;
@@ -416,6 +416,11 @@ void k_range_info(int nwaves, int ngw, int niso, const int32_t *__restrict__ wba
   RangeInfo R{};
   R.l0 = gfirst[g0]; R.l1 = gfirst[g1 - 1] + gcount[g1 - 1]; R.b = b;
   R.cell0 = lines[R.l0].cell; R.wavn0 = lines[R.l0].wavn; R.cell1 = lines[gfirst[g1 - 1]].cell;
+  // the extreme fine-grid phases of the range's anchors, for the walk's whole-range exit (ranges inside one cell)
+  int imin = osamp, imax = 0;
+  if (R.cell0 == R.cell1)
+    for (int g = g0; g < g1; g++) { const int im = lines[gfirst[g]].meta >> 3; imin = min(imin, im); imax = max(imax, im); }
+  R.phases = walk_range_phases(R.cell0 == R.cell1, osamp, imin, imax);
   out[w] = R;
 }
 
@@ -436,6 +441,9 @@ struct WalkArgs {
   const int32_t *gfirst, *gcount, *gblock;
   WalkPlan P;
   int niso, nlor, ndop, osamp;
+  double wn_i, odwn;                // the fine grid: first point and step (walk_may_stick)
+  int range_reach;                  // k_line_walk bounds a group's reach per RANGE and leaves ranges out of all reach at once
+                                    // (0: the step's bound alone -- TRX_RANGE_REACH=0, or a table without TablePlan::psize_mono)
   long long lo, hi;                 // shard [lo, hi)
   int r_top, nc;
   LayerDev Y; const double *wcut;   // [layer][iso]
@@ -528,6 +536,9 @@ void k_line_walk(WalkArgs A)
   const int li = LPL == 1 ? lane : (lane >> 1), part = LPL == 1 ? 0 : (lane & 1);
   const bool valid = li < A.nc;
   const int r = A.r_top - (valid ? li : 0), ri = r * A.niso + b;
+  // widest profile any lane of this step can use for this isotope: wave-uniform bound for the bin
+  // loop (idle lanes stay out of the maximum)
+  const int psm_l = valid ? A.Y.psmax[ri] : 0;
   const int mx = A.nmx == 1 ? 0 : A.iso_mx[b];
   const double ct = valid ? A.Y.negc_over_t[r] : 0.0;      // idle lanes: strength 0
   const double f = A.Y.strength_f[ri], dens = A.permol ? 1.0 : A.Y.density[ri];
@@ -535,24 +546,49 @@ void k_line_walk(WalkArgs A)
   const double wc = A.wcut[ri], ad = A.Y.alphad[ri];
   const int il = A.Y.ilor[ri];
   const int idst = A.sticky_idop[ri];
+  const int idop0 = A.Y.idop0[ri];
+
+  // bins of the interval that no frame position covers (a jump over empty or skipped cells, the
+  // tail below the last evaluated group) still get their record: zeros
+  auto fill_zero = [&](int ja, int jb) {                   // bins ja..jb inclusive
+    ja = max(ja, blo); jb = min(jb, bhi);
+    if (valid && part == 0) for (int j = ja; j <= jb; j++) A.part[(rec0 + (j - blo)) * kWalkLayers + li] = 0.0;
+  };
+
+  // The whole range out of reach: its anchors share one cell and every one sits further than the widest
+  // profile from both of the cell's edges (RangeInfo::phases, trx_device.h).  No group would be evaluated, the
+  // frame would never move and the epilogue would write zeros for blo..bhi: written here, and the wave is gone
+  // -- first by the step's bound, known one load after the range's record (the layer scalars above are on
+  // their way but nothing waits for them), then by the range's own bound below.  (Counting runs walk on.)
+  const int psm_s = __builtin_amdgcn_readfirstlane(wave_max_i(psm_l));
+  const bool range_reach = !PROF && A.range_reach != 0;   // wave-uniform
+  const int phases = __builtin_amdgcn_readfirstlane(RI.phases), cell1 = __builtin_amdgcn_readfirstlane(RI.cell1);
+  if (range_reach && walk_range_out_of_reach(phases, A.osamp, psm_s)) { fill_zero(blo, bhi); return; }
+
   const int ps_st = A.psize[idst * A.nlor + il];
   const unsigned vo_st = (unsigned)(A.poff[idst * A.nlor + il] + ps_st);     // table index of the sticky profile's centre
-  // widest profile any lane of this step can use for this isotope: wave-uniform bound for the bin
-  // loop, split into whole cells and the rest (psm_s = psq*osamp + psr)
-  const int psm_s = __builtin_amdgcn_readfirstlane(wave_max_i(valid ? A.Y.psmax[ri] : 0));
-  const int psq = psm_s / A.osamp, psr = psm_s - psq * A.osamp;
   const int lo32 = (int)A.lo, hi32 = (int)A.hi;            // (the grid has < 2^31 bins: trx_create)
   // every bin this range can reach lies inside the shard: no clipping of the slot masks
-  const bool interior = __builtin_amdgcn_readfirstlane(RI.cell1) - Rc >= lo32 && __builtin_amdgcn_readfirstlane(RI.cell0) + Rc + 1 < hi32;
+  const bool interior = cell1 - Rc >= lo32 && __builtin_amdgcn_readfirstlane(RI.cell0) + Rc + 1 < hi32;
 
   // Doppler index of the first anchor, then followed downwards (wavenumbers descend => it never rises)
-  int lo_i = index_from(s_thr, ad * RI.wavn0, A.Y.idop0[ri]);
+  int lo_i = index_from(s_thr, ad * RI.wavn0, idop0);
   double thr_lo = s_thr[lo_i];
   int ps_cur = A.psize[lo_i * A.nlor + il];
   unsigned vo_cur = 4u * (unsigned)(A.poff[lo_i * A.nlor + il] + ps_cur);   // byte offset of the profile centre
   const unsigned vo_st8 = 4u * vo_st;
   WalkProfile wp_cur{}, wp_st{};
   if (ROWS) { wp_cur = A.walkprof[lo_i * A.nlor + il]; wp_st = A.walkprof[idst * A.nlor + il]; }
+
+  // The range's own bound (walk_lane_reach, trx_device.h): no lane takes a wider own profile in this range than
+  // the one it starts with, nor the sticky one unless the range dips below its wcut.  Wave-uniform and fixed for
+  // the range, so every member of a group sees the bound its anchor saw; split into whole cells and the rest
+  // (psm = psq*osamp + psr).  A group it leaves out would have added kk * 0 in every lane -- the sums keep their
+  // bits as long as kk is finite, which the step's bound has always relied on.
+  const int reach_l = valid ? walk_lane_reach(ps_cur, ps_st, walk_may_stick(A.wn_i, A.odwn, A.osamp, cell1, wc)) : 0;
+  const int psm = walk_range_reach(psm_s, range_reach ? __builtin_amdgcn_readfirstlane(wave_max_i(reach_l)) : psm_s, range_reach);
+  if (range_reach && walk_range_out_of_reach(phases, A.osamp, psm)) { fill_zero(blo, bhi); return; }
+  const int psq = psm / A.osamp, psr = psm - psq * A.osamp;
 
   double acc[NS];
 #pragma unroll
@@ -563,13 +599,6 @@ void k_line_walk(WalkArgs A)
   auto flush = [&](int k, double v, bool mine = true) {    // bin of this lane's slot k leaves the frame
     const int j = jc - Rc + part * NS + k;
     if (valid && mine && j >= blo && j <= bhi) A.part[(rec0 + (j - blo)) * kWalkLayers + li] = v;     // (idle lanes: nobody reads their entries)
-  };
-
-  // bins of the interval that no frame position covers (a jump over empty or skipped cells, the
-  // tail below the last evaluated group) still get their record: zeros
-  auto fill_zero = [&](int ja, int jb) {                   // bins ja..jb inclusive
-    ja = max(ja, blo); jb = min(jb, bhi);
-    if (valid && part == 0) for (int j = ja; j <= jb; j++) A.part[(rec0 + (j - blo)) * kWalkLayers + li] = 0.0;
   };
 
   double pk = 0.0;                   // strength of the group so far (0 between groups)
@@ -620,14 +649,10 @@ void k_line_walk(WalkArgs A)
       E0 = exp_neg(t0, s_e2, c24); c0 = -t0;
     }
     if (L_meta & 1) {
-      // slots some layer of this step can reach from this group: |(k - Rc)*osamp - imod| <= psm_s
-      // and the bin inside the shard.  All wave-uniform integer arithmetic.
+      // slots some layer of this step can reach from this group: |(k - Rc)*osamp - imod| <= psm (the
+      // range's bound) and the bin inside the shard.  All wave-uniform integer arithmetic.
       cell = L_cell; imod = L_meta >> 3; wav_a = L_wavn;
-      if (NB == 2) cand = (imod <= psm_s ? 1u : 0u) | (A.osamp - imod <= psm_s ? 2u : 0u);
-      else {
-        const int klo = Rc - psq + (imod > psr ? 1 : 0), khi = Rc + psq + (imod + psr >= A.osamp ? 1 : 0);
-        cand = ((2u << khi) - 1u) & ~((1u << klo) - 1u);   // (0 <= klo <= khi < NB by the choice of NB)
-      }
+      cand = walk_cand_slots(NB, imod, A.osamp, psm, psq, psr);
       if (!interior) {
 #pragma unroll
         for (int k = 0; k < NB; k++) { const int j = cell - Rc + k; if (j < lo32 || j >= hi32) cand &= ~(1u << k); }
