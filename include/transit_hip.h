@@ -401,6 +401,67 @@ int  trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */,
                           int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
                           double *const *out /* [k] -> [nshift][npix][2] */);
 
+/* Cross-correlation moments of the detector pixels against observed data, on the device: what a driver reduces the
+ * [nshift][npix][2] matrix of trx_run_pixels to -- per exposure and spectral order a correlation coefficient, a
+ * log-likelihood or a chi-square, all functions of seven weighted sums over the order's pixels -- without handing the
+ * matrix back: the observed set is installed once over the pixel set, a run returns [nexp][nseg][TRX_NMOMENT] doubles.
+ *
+ * An exposure is a shift of the run (nshift = nexp); a segment s is the pixels [seg_first[s], seg_first[s+1]) of the
+ * installed pixel set.  For exposure v and pixel p, (a, b) = out[v][p] is exactly the pair trx_run_pixels gives for
+ * that shift and pixel (the same kernel, the same bits), f = data[v][p], w = weight[v][p] (1 without weights).
+ *   a pixel CONTRIBUTES when b > 0 and w > 0
+ *   its model value is g = gain_p * (a / b): one division, one product, each rounded once (no fused multiply-add)
+ * and over the contributing pixels of segment s
+ *   mom[v][s][0] = n, their number (as a double)     mom[v][s][4] = sum of w f
+ *   mom[v][s][1] = sum of w                          mom[v][s][5] = sum of w f g
+ *   mom[v][s][2] = sum of w g                        mom[v][s][6] = sum of w f^2
+ *   mom[v][s][3] = sum of w g^2
+ * with the terms (w g) g, (w f) g and (w f) f, every product rounded once.  A segment with no contributing pixel gives
+ * seven exact +0.
+ *
+ * The order of the sums is fixed: one wavefront adds a (v, s) row, lane l the segment's pixels first + l,
+ * first + l + 64, ... in that order, then the fixed butterfly over the 64 lanes that the long pixel windows use.  No
+ * atomics: the bits of a row depend on the spectrum, that segment's pixels, data and weights, that shift and nothing
+ * else -- not on the other segments or exposures of the call, the launch, the batch way that ran it or the handle's
+ * depth hint.  (A segment is one wave's work whatever its length: nexp * nseg is the parallel axis.)
+ *
+ * The observed set belongs to the pixel set it was installed over: trx_set_observed without a pixel set is TRX_E_ARG,
+ * a successful trx_set_pixels (a clearing one included) drops the observed set, a refused one leaves both in force.
+ * trx_set_observed copies seg_first, data, weight and gain to the device (ob NULL or nexp = 0: clear it).  It returns
+ * TRX_E_ARG, the reason in trx_last_error, for nexp < 0, nseg < 1, a NULL seg_first or data, seg_first[0] != 0, a
+ * decreasing entry, seg_first[nseg] != npix, nexp * nseg above 2^31 - 1, a non-finite datum or a negative or
+ * non-finite weight (naming "exposure N pixel M"), a non-finite gain (naming "pixel M"); a refused set leaves the
+ * previous one in force.
+ * trx_run_moments is trx_run_pixels plus the reduction: spectrum may be NULL, and when it is given it holds the bits
+ * trx_run gives; only mom is copied back, the pairs stay in device memory.  TRX_E_ARG with no observed set installed,
+ * nshift != nexp, shift or mom NULL, a non-finite or <= 0 shift (naming "shift N").  The moments are not linear in the
+ * pairs, so the partial pairs of shards cannot be reduced rank by rank: on a handle whose shard is not the whole grid
+ * (wn_lo != 0 or wn_hi != nwn) it returns TRX_E_UNSUPPORTED -- such a job takes trx_run_pixels, adds the ranks' pairs
+ * (trx_gather_host) and reduces them itself.  A run that fails leaves mom undefined.  trx_run, trx_run_bands,
+ * trx_run_contrib and trx_run_pixels on a handle with an observed set installed are unchanged.
+ * trx_batch_set_observed installs the same set on every handle of the batch, or on none (its reason through
+ * trx_last_error(NULL)); trx_run_batch_moments is trx_run_batch with atmosphere j's own shifts shift[j] ([nshift]) and
+ * its moments mom[j] ([nexp][nseg][TRX_NMOMENT]). */
+#define TRX_NMOMENT 7
+typedef struct {
+  int32_t nexp, nseg;        /* exposures (= the shifts of a run), segments (orders / detectors)            */
+  const int64_t *seg_first;  /* [nseg+1] segment s = pixels [seg_first[s], seg_first[s+1]) of the installed  */
+                             /* pixel set; seg_first[0] = 0, non-decreasing (an empty segment is allowed),   */
+                             /* seg_first[nseg] = npix                                                       */
+  const double *data;        /* [nexp][npix] observed value f, finite                                        */
+  const double *weight;      /* [nexp][npix] w >= 0, finite (1/sigma^2; 0 masks a pixel); NULL: all 1        */
+  const double *gain;        /* [npix] finite factor on the model value (e.g. (Rp/Rs)^2 / Fstar); NULL: 1    */
+} trx_observed;
+int  trx_set_observed(trx_handle *h, const trx_observed *ob);
+int  trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                     double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                     int32_t nshift, const double *shift /* [nshift], nshift = nexp */,
+                     double *mom /* [nexp][nseg][TRX_NMOMENT], host */, trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_observed(trx_batch *b, const trx_observed *ob);
+int  trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                           int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
+                           double *const *mom /* [k] -> [nexp][nseg][TRX_NMOMENT] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

@@ -87,6 +87,14 @@ class TrxPixels(C.Structure):
     _fields_ = [("npix", C.c_int64), ("centre", c_double_p), ("fwhm", c_double_p), ("cut", C.c_double)]
 
 
+NMOMENT = 7
+
+
+class TrxObserved(C.Structure):
+    _fields_ = [("nexp", C.c_int32), ("nseg", C.c_int32), ("seg_first", c_int64_p), ("data", c_double_p),
+                ("weight", c_double_p), ("gain", c_double_p)]
+
+
 class TrxStats(C.Structure):
     _fields_ = [
         ("nlines_inrange", C.c_int64), ("ngroups", C.c_int64), ("nadd", C.c_int64),
@@ -170,4 +178,19 @@ def bind_pixels_api(lib):
     lib.trx_run_batch_pixels.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_pixels.restype = C.c_int
+    return lib
+
+
+def bind_moments_api(lib):
+    """argtypes/restypes of the moment entry points (trx_set_observed, trx_run_moments and their batch forms)."""
+    lib.trx_set_observed.argtypes = [C.c_void_p, C.POINTER(TrxObserved)]
+    lib.trx_set_observed.restype = C.c_int
+    lib.trx_run_moments.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                    c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_moments.restype = C.c_int
+    lib.trx_batch_set_observed.argtypes = [C.c_void_p, C.POINTER(TrxObserved)]
+    lib.trx_batch_set_observed.restype = C.c_int
+    lib.trx_run_batch_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
+                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_moments.restype = C.c_int
     return lib

@@ -37,6 +37,7 @@
 #include "trx_lanes.hip.h"
 #include "trx_bands.hip.h"
 #include "trx_pixels.hip.h"
+#include "trx_moments.hip.h"
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 #include "../trx_plan.h"
@@ -78,8 +79,13 @@ struct PixelSet {
   int64_t npix = 0; double cut = 0;
   DevBuf d_centre, d_fwhm;                           // [npix] each
 };
-// a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift
-struct PixelRun { const PixelSet *set; int32_t nshift; };
+// an observed set installed by trx_set_observed over the pixel set (trx_moments.hip.h): the arrays as given
+struct ObservedSet {
+  int32_t nexp = 0, nseg = 0; int64_t npix = 0;
+  DevBuf d_seg, d_data, d_weight, d_gain;            // [nseg + 1], [nexp][npix], the same or none, [npix] or none
+};
+// a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments)
+struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; };
 
 // The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
 // alone, before any stage.  Each selects between two forms of the same computation that give the same
@@ -200,6 +206,8 @@ struct trx_handle {
   DevBuf d_cpart; PinnedBuf h_contrib;
   std::unique_ptr<PixelSet> pixels;                    // trx_set_pixels (null: none)
   DevBuf d_pixshift, d_pixout;                         // trx_run_pixels: the run's shifts [nshift] and its pairs [nshift][npix][2], grown on demand
+  std::unique_ptr<ObservedSet> observed;               // trx_set_observed (null: none); belongs to `pixels`
+  DevBuf d_mom;                                        // trx_run_moments: [nexp][nseg][TRX_NMOMENT], grown on demand
 };
 
 namespace {
@@ -1931,7 +1939,8 @@ struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swe
 // bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
 // spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
 // contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
-// px: a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it
+// px: a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it,
+// and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that
 struct Run {
   // ---- what the run is given
   trx_handle *const h; const trx_atm *const a; const trx_opts *const o;
@@ -2027,7 +2036,7 @@ struct Run {
   int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
   int side_work(SideWork &S); int queue_cia(); int join_early();
   // ... the spectrum of what they swept, the way back
-  int spectrum_kernel(); int ray_tail(); int band_kernels(); int pixel_kernels(); int results();
+  int spectrum_kernel(); int ray_tail(); int band_kernels(); int pixel_kernels(); int moment_kernels(); int results();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2680,6 +2689,29 @@ int Run::pixel_kernels()
   return TRX_OK;
 }
 
+// ---- the moments of those pairs against the observed set (trx_moments.hip.h), behind the pixel kernel on its queue;
+// a pass that resumes deeper queues both again.
+int Run::moment_kernels()
+{
+  if (!px || !px->obs) return TRX_OK;
+  const ObservedSet &O = *px->obs;
+  MomArgs MA{};
+  MA.pairs = h->d_pixout.as<double2>(); MA.data = O.d_data.as<double>(); MA.weight = O.d_weight.as<double>(); MA.gain = O.d_gain.as<double>();
+  MA.seg_first = O.d_seg.as<int64_t>(); MA.mom = h->d_mom.as<double>();
+  MA.npix = O.npix; MA.nseg = O.nseg; MA.nrows = (int64_t)O.nexp * O.nseg;
+  const int64_t blocks = (MA.nrows + kMomWaves - 1) / kMomWaves;
+  const size_t cells = sizeof(double) * (size_t)O.nexp * (size_t)O.npix;
+  // (every address the kernel reads or writes: pairs, data and weights over [nexp][npix] -- the segments lie in [0, npix),
+  // checked when the set was made --, the gains, the segment bounds, the rows)
+  if (!MA.pairs || !MA.data || !MA.seg_first || !MA.mom || O.nexp < 1 || O.nseg < 1 || O.npix != px->set->npix || O.nexp != px->nshift ||
+      h->d_pixout.bytes < 2 * cells || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
+      (MA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
+      h->d_mom.bytes < sizeof(double) * TRX_NMOMENT * (size_t)MA.nrows || blocks < 1 || blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the moment kernel (not launched)");
+  hipLaunchKernelGGL(k_pixel_moments, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
+  return TRX_OK;
+}
+
 // ---- results back: the copies, the wait, and (direct tail) the flags summed on the host
 int Run::results()
 {
@@ -2720,7 +2752,7 @@ int Run::pass()
   int rc;
   for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
   if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = pixel_kernels()) ? rc : results();
+  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = pixel_kernels()) || (rc = moment_kernels()) ? rc : results();
 }
 
 // Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
@@ -3031,13 +3063,35 @@ static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<P
   return TRX_OK;
 }
 
+// (the observed set belongs to the pixel set it was installed over: it goes with it)
+static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->pixels = std::move(S); h->observed.reset(); }
+
 int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 {
   if (!h) return TRX_E_ARG;
   std::unique_ptr<PixelSet> S;
   if (const int rc = make_pixel_set(h, px, S)) return rc;
-  h->pixels = std::move(S);
+  install_pixel_set(h, S);
   return TRX_OK;
+}
+
+// a pixel run for `who` (trx_run_pixels; obs: trx_run_moments): the pairs are in h->d_pixout, the moments in h->d_mom, when it returns
+static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                     const ObservedSet *obs, trx_debug *dbg)
+{
+  const std::string w(who);
+  for (int32_t v = 0; v < nshift; v++)
+    if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, w + ": shift " + std::to_string(v) + " must be finite and > 0");
+  const PixelRun PR{h->pixels.get(), nshift, obs};
+  if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, w + ": nshift * npix above what one launch takes");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
+  if ((rc = ensure(h, h->d_pixout, sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix)) ||
+      (obs && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
+      (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift)))
+    return rc;
+  return run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR);
 }
 
 int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
@@ -3048,17 +3102,73 @@ int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *s
   if (nshift < 1) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift < 1");
   if (!shift) return fail(h, TRX_E_ARG, "trx_run_pixels: shift is NULL");
   if (!out) return fail(h, TRX_E_ARG, "trx_run_pixels: out is NULL");
-  for (int32_t v = 0; v < nshift; v++)
-    if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, "trx_run_pixels: shift " + std::to_string(v) + " must be finite and > 0");
-  const PixelRun PR{h->pixels.get(), nshift};
-  if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift * npix above what one launch takes");
-  const size_t out_bytes = sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix;
+  if (const int rc = pixel_run(h, "trx_run_pixels", a, o, spectrum, nshift, shift, nullptr, dbg)) return rc;
+  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, sizeof(double) * 2 * (size_t)nshift * (size_t)h->pixels->npix, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
+// ---- cross-correlation moments of the pixels against observed data (trx_moments.hip.h) -------------
+// The set, checked whole before anything is replaced; the device gets the arrays as they are.
+static int make_observed_set(trx_handle *h, const trx_observed *ob, std::unique_ptr<ObservedSet> &out)
+{
+  out.reset();
+  if (!ob || ob->nexp == 0) return TRX_OK;              // (clear)
+  if (!h->pixels) return fail(h, TRX_E_ARG, "observed: no pixel set installed (trx_set_pixels)");
+  const int64_t npix = h->pixels->npix;
+  if (ob->nexp < 0) return fail(h, TRX_E_ARG, "observed: nexp < 0");
+  if (ob->nseg < 1) return fail(h, TRX_E_ARG, "observed: nseg < 1");
+  if (!ob->seg_first || !ob->data) return fail(h, TRX_E_ARG, "observed: NULL seg_first or data array");
+  if (ob->seg_first[0] != 0) return fail(h, TRX_E_ARG, "observed: seg_first[0] must be 0");
+  for (int32_t s = 0; s < ob->nseg; s++)
+    if (ob->seg_first[s + 1] < ob->seg_first[s]) return fail(h, TRX_E_ARG, "observed: seg_first decreases at segment " + std::to_string(s));
+  if (ob->seg_first[ob->nseg] != npix) return fail(h, TRX_E_ARG, "observed: seg_first[nseg] must be the pixel set's npix (" + std::to_string(npix) + ")");
+  if ((int64_t)ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, "observed: nexp * nseg above 2^31 - 1");
+  auto where = [npix](size_t k) { return "exposure " + std::to_string(k / (size_t)npix) + " pixel " + std::to_string(k % (size_t)npix); };
+  const size_t cells = (size_t)ob->nexp * (size_t)npix;
+  for (size_t k = 0; k < cells; k++) {
+    if (!std::isfinite(ob->data[k])) return fail(h, TRX_E_ARG, "observed: " + where(k) + ": datum must be finite");
+    if (ob->weight && (!std::isfinite(ob->weight[k]) || !(ob->weight[k] >= 0))) return fail(h, TRX_E_ARG, "observed: " + where(k) + ": weight must be finite and >= 0");
+  }
+  if (ob->gain)
+    for (int64_t p = 0; p < npix; p++)
+      if (!std::isfinite(ob->gain[p])) return fail(h, TRX_E_ARG, "observed: pixel " + std::to_string(p) + ": gain must be finite");
+  std::unique_ptr<ObservedSet> S(new (std::nothrow) ObservedSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "observed: out of host memory");
+  S->nexp = ob->nexp; S->nseg = ob->nseg; S->npix = npix;
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
-  // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
-  if ((rc = ensure(h, h->d_pixout, out_bytes)) || (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift))) return rc;
-  if ((rc = run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR))) return rc;
-  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, out_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  if ((rc = upload_raw(h, S->d_seg, ob->seg_first, (size_t)ob->nseg + 1)) || (rc = upload_raw(h, S->d_data, ob->data, cells)) ||
+      (ob->weight && (rc = upload_raw(h, S->d_weight, ob->weight, cells))) || (ob->gain && (rc = upload_raw(h, S->d_gain, ob->gain, (size_t)npix))))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
+  out = std::move(S);
+  return TRX_OK;
+}
+
+int trx_set_observed(trx_handle *h, const trx_observed *ob)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<ObservedSet> S;
+  if (const int rc = make_observed_set(h, ob, S)) return rc;
+  h->observed = std::move(S);
+  return TRX_OK;
+}
+
+int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                    double *mom, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  // (the moments are not linear in the pairs: the partial pairs of a shard say nothing about them)
+  if (h->windowed())
+    return fail(h, TRX_E_UNSUPPORTED, "trx_run_moments: this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
+                                      "(trx_gather_host) and reduce them on the host");
+  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "trx_run_moments: no observed set installed (trx_set_observed)");
+  const ObservedSet *ob = h->observed.get();
+  if (nshift != ob->nexp) return fail(h, TRX_E_ARG, "trx_run_moments: nshift " + std::to_string(nshift) + " is not the observed set's nexp " + std::to_string(ob->nexp));
+  if (!shift) return fail(h, TRX_E_ARG, "trx_run_moments: shift is NULL");
+  if (!mom) return fail(h, TRX_E_ARG, "trx_run_moments: mom is NULL");
+  if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, nshift, shift, ob, dbg)) return rc;
+  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
@@ -3080,6 +3190,7 @@ struct trx_batch {
   double *const *sums = nullptr;                     // trx_run_batch_bands: the band sums instead of the spectra
   double *const *contrib = nullptr;                  // trx_run_batch_contrib: and the contribution functions
   int32_t nshift = 0; const double *const *shifts = nullptr; double *const *pix = nullptr;      // trx_run_batch_pixels: the pixel pairs instead
+  double *const *mom = nullptr;                      // trx_run_batch_moments: the moments instead (shifts as for pix)
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -3123,7 +3234,8 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
         for (;;) {
           const int32_t j = b->next.fetch_add(1);
           if (j >= b->k) break;
-          const int rc = b->pix ? trx_run_pixels(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
+          const int rc = b->mom ? trx_run_moments(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
+                       : b->pix ? trx_run_pixels(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
                        : b->contrib ? trx_run_contrib(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
                        : b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
                                  : trx_run(b->hs[(size_t)i], b->atm + j, b->opts, b->spectra[j], nullptr);
@@ -3145,12 +3257,13 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
 static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
-                      double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr)
+                      double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr,
+                      double *const *mom = nullptr)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
   b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
-  b->nshift = nshift; b->shifts = shifts; b->pix = pix;
+  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3213,7 +3326,7 @@ int trx_batch_set_pixels(trx_batch *b, const trx_pixels *px)
     const int rc = make_pixel_set(b->hs[i], px, sets[i]);
     if (rc) { g_comm_err = b->hs[i]->err; return rc; }
   }
-  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->pixels = std::move(sets[i]);
+  for (size_t i = 0; i < b->hs.size(); i++) install_pixel_set(b->hs[i], sets[i]);
   return TRX_OK;
 }
 
@@ -3229,6 +3342,33 @@ int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_
     if (!out[j]) { g_comm_err = "trx_run_batch_pixels: out[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   }
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, out);
+}
+
+// every handle of the batch gets the same observed set, or none does
+int trx_batch_set_observed(trx_batch *b, const trx_observed *ob)
+{
+  g_comm_err.clear();
+  if (!b) return TRX_E_ARG;
+  std::vector<std::unique_ptr<ObservedSet>> sets(b->hs.size());
+  for (size_t i = 0; i < b->hs.size(); i++) {
+    const int rc = make_observed_set(b->hs[i], ob, sets[i]);
+    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
+  }
+  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->observed = std::move(sets[i]);
+  return TRX_OK;
+}
+
+int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
+                          double *const *mom)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_moments: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) {
+    if (!shift[j]) { g_comm_err = "trx_run_batch_moments: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+    if (!mom[j]) { g_comm_err = "trx_run_batch_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  }
+  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom);
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

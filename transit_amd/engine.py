@@ -203,6 +203,7 @@ def hip_library():
         _abi.bind_bands_api(lib)
         _abi.bind_contrib_api(lib)
         _abi.bind_pixels_api(lib)
+        _abi.bind_moments_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -274,6 +275,7 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_set_pixels", self._last_error())
         self.npix = n
+        self.mom_shape = (0, 0)
 
     def run_pixels(self, atm, opts, shifts, spectrum: bool = False):
         """trx_run_pixels: the pairs [nshift, npix, 2] of this shard at the Doppler shifts given (nu_observed / nu_rest)
@@ -288,6 +290,29 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_pixels", self._last_error())
         return (out, spec) if spectrum else out
+
+    def set_observed(self, observed):
+        """trx_set_observed: install the observed exposures (a transit_amd.xcor.Observed; None: clear them) over the
+        pixel set in force.  set_pixels drops them."""
+        rc = self._lib.trx_set_observed(self._h, C.byref(observed.to_c()) if observed is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_observed", self._last_error())
+        self.mom_shape = (observed.nexp, observed.nseg) if observed is not None else (0, 0)
+
+    def run_moments(self, atm, opts, shifts, spectrum: bool = False):
+        """trx_run_moments: the moments [nexp, nseg, 7] of the pixels at the exposures' Doppler shifts against the
+        observed set (transit_amd.xcor) -- and, with spectrum=True, (moments, spectrum), the spectrum bit for bit what
+        run() gives.  The pixel pairs stay on the device."""
+        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        mom = np.zeros(getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_moments(self._h, C.byref(atm), C.byref(opts),
+                                       spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                       int(sh.size), sh.ctypes.data_as(_abi.c_double_p),
+                                       mom.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_moments", self._last_error())
+        return (mom, spec) if spectrum else mom
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -378,6 +403,7 @@ class Batch:
         if rc != 0:
             raise EngineError(rc, "trx_batch_set_pixels", self._err())
         self.npix = n
+        self.mom_shape = (0, 0)
 
     def run_pixels(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_pixels: [K, nshift, npix, 2] for shifts of shape [K][nshift] (atmosphere j at its own shifts),
@@ -393,6 +419,29 @@ class Batch:
         rc = self._lib.trx_run_batch_pixels(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_pixels", self._err())
+        return out
+
+    def set_observed(self, observed):
+        """trx_batch_set_observed: the same observed set on every handle of the batch, or on none."""
+        rc = self._lib.trx_batch_set_observed(self._b, C.byref(observed.to_c()) if observed is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_observed", self._err())
+        self.mom_shape = (observed.nexp, observed.nseg) if observed is not None else (0, 0)
+
+    def run_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
+        """trx_run_batch_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp] (atmosphere j at its own shifts),
+        each atmosphere's moments what Engine.run_moments gives, bit for bit."""
+        k = len(atms)
+        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        if sh.ndim != 2 or sh.shape[0] != k:
+            raise ValueError("Batch.run_moments: shifts of shape [K][nexp], one row per atmosphere")
+        out = np.zeros((k,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        ps = (_abi.c_double_p * max(k, 1))(*[sh[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_moments", self._err())
         return out
 
     def close(self):

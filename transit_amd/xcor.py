@@ -1,0 +1,179 @@
+"""Host side of the moment runs, Engine.set_observed / Engine.run_moments and their Batch forms (trx_set_observed /
+trx_run_moments, include/transit_hip.h): a high-resolution cross-correlation retrieval's comparison of the detector
+pixels with the observed exposures, order by order, from seven weighted sums per (exposure, segment).
+
+For exposure v and pixel p, (a, b) is the pixel run's pair, f the datum, w its weight (1 without weights).  A pixel
+contributes when b > 0 and w > 0; its model value is g = gain_p * (a / b).  Over the contributing pixels of a segment
+
+    mom[v, s] = (n, sum w, sum w g, sum w g^2, sum w f, sum w f g, sum w f^2)
+
+    Observed(seg_first, data, weight=None, gain=None)    an observed set; to_c() its trx_observed
+    segments(lengths)                                    seg_first from the segments' lengths
+    reference(pairs, obs)                                the definition in numpy, sums by math.fsum
+    abs_reference(pairs, obs)                            the same with |f| and |g|: the scale of a sum's rounding error
+    chi2(mom, a=1, b=0)                                  sum w (f - a g - b)^2 per (v, s)
+    ccf(mom)                                             the weighted Pearson coefficient of f and g per (v, s)
+    loglike_bl19(mom, scale=1)                           the Brogi & Line (2019) log-likelihood per (v, s)
+    chi2_sum, ccf_sum, loglike_bl19_sum                  the same added over all (v, s)
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _abi
+
+NMOMENT = _abi.NMOMENT
+N, W, WG, WGG, WF, WFG, WFF = range(NMOMENT)
+
+
+def segments(lengths) -> np.ndarray:
+    """seg_first ([nseg + 1], int64) of segments of the given lengths, laid end to end from pixel 0."""
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if np.any(n < 0):
+        raise ValueError("segments: a negative length")
+    return np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+
+
+@dataclass
+class Observed:
+    """One trx_observed: segment bounds [nseg + 1], data [nexp, npix] (finite), weights [nexp, npix] (finite, >= 0;
+    None: all 1) and gain [npix] (finite; None: 1)."""
+    seg_first: np.ndarray
+    data: np.ndarray
+    weight: Optional[np.ndarray] = None
+    gain: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        self.seg_first = np.ascontiguousarray(self.seg_first, dtype=np.int64).reshape(-1)
+        self.data = np.ascontiguousarray(self.data, dtype=np.float64)
+        if self.data.ndim != 2:
+            raise ValueError("Observed: data of shape [nexp][npix]")
+        if self.weight is not None:
+            self.weight = np.ascontiguousarray(self.weight, dtype=np.float64)
+            if self.weight.shape != self.data.shape:
+                raise ValueError("Observed: weight of the shape of data")
+        if self.gain is not None:
+            self.gain = np.ascontiguousarray(self.gain, dtype=np.float64).reshape(-1)
+            if self.gain.size != self.data.shape[1]:
+                raise ValueError("Observed: one gain per pixel")
+        if self.seg_first.size < 1:
+            raise ValueError("Observed: seg_first of nseg + 1 entries")
+
+    @property
+    def nexp(self) -> int:
+        return int(self.data.shape[0])
+
+    @property
+    def npix(self) -> int:
+        return int(self.data.shape[1])
+
+    @property
+    def nseg(self) -> int:
+        return int(self.seg_first.size) - 1
+
+    def to_c(self):
+        """The trx_observed of the set (the arrays stay owned by this object)."""
+        c = _abi.TrxObserved()
+        c.nexp, c.nseg = self.nexp, self.nseg
+        c.seg_first = self.seg_first.ctypes.data_as(_abi.c_int64_p)
+        c.data = self.data.ctypes.data_as(_abi.c_double_p)
+        c.weight = self.weight.ctypes.data_as(_abi.c_double_p) if self.weight is not None else None
+        c.gain = self.gain.ctypes.data_as(_abi.c_double_p) if self.gain is not None else None
+        return c
+
+
+def _moments(pairs, obs: Observed, absolute: bool) -> np.ndarray:
+    pairs = np.asarray(pairs, dtype=np.float64)
+    if pairs.shape != (obs.nexp, obs.npix, 2):
+        raise ValueError("pairs of shape [nexp][npix][2]")
+    a, b = pairs[..., 0], pairs[..., 1]
+    w = obs.weight if obs.weight is not None else np.ones_like(obs.data)
+    gain = obs.gain if obs.gain is not None else np.ones(obs.npix)
+    use = (b > 0) & (w > 0)
+    g = gain[None, :] * (a / np.where(use, b, 1.0))          # one division, one product, each rounded once
+    f = obs.data
+    if absolute:
+        g, f = np.abs(g), np.abs(f)
+    wg, wf = w * g, w * f
+    terms = (np.ones_like(w), w, wg, wg * g, wf, wf * g, wf * f)
+    out = np.zeros((obs.nexp, obs.nseg, NMOMENT))
+    for v in range(obs.nexp):
+        for s in range(obs.nseg):
+            k = np.arange(obs.seg_first[s], obs.seg_first[s + 1])
+            k = k[use[v, k]]
+            for c, t in enumerate(terms):
+                out[v, s, c] = math.fsum(t[v, k])
+    return out
+
+
+def reference(pairs, obs: Observed) -> np.ndarray:
+    """The definition: [nexp, nseg, 7] from the pixel pairs [nexp, npix, 2] of a run and the observed set -- the
+    terms in numpy (every operation rounded once, as on the device), the sums by math.fsum."""
+    return _moments(pairs, obs, False)
+
+
+def abs_reference(pairs, obs: Observed) -> np.ndarray:
+    """reference with |f| and |g|: the sums of the absolute terms, which the rounding error of a sum is relative to."""
+    return _moments(pairs, obs, True)
+
+
+def chi2(mom, a: float = 1.0, b: float = 0.0) -> np.ndarray:
+    """sum of w (f - a g - b)^2 over the contributing pixels, per (v, s):
+    m6 - 2a m5 - 2b m4 + a^2 m3 + 2ab m2 + b^2 m1."""
+    m = np.asarray(mom, dtype=np.float64)
+    return m[..., WFF] - 2 * a * m[..., WFG] - 2 * b * m[..., WF] + a * a * m[..., WGG] + 2 * a * b * m[..., WG] + b * b * m[..., W]
+
+
+def central(mom):
+    """(n, s_f^2, s_g^2, R, ok) per (v, s): the weighted mean-subtracted variances of f and g and their covariance,
+    sum w (x - <x>)(y - <y>) / sum w with <x> = sum w x / sum w; ok is False for a row with n < 2 or a variance that
+    is not positive (there the three are nan)."""
+    m = np.asarray(mom, dtype=np.float64)
+    n, sw = m[..., N], m[..., W]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mf, mg = m[..., WF] / sw, m[..., WG] / sw
+        sf2 = m[..., WFF] / sw - mf * mf
+        sg2 = m[..., WGG] / sw - mg * mg
+        r = m[..., WFG] / sw - mf * mg
+        ok = (n >= 2) & (sf2 > 0) & (sg2 > 0)
+    nan = np.full(m.shape[:-1], np.nan)
+    return n, np.where(ok, sf2, nan), np.where(ok, sg2, nan), np.where(ok, r, nan), ok
+
+
+def ccf(mom) -> np.ndarray:
+    """The weighted Pearson correlation coefficient of f and g per (v, s), R / sqrt(s_f^2 s_g^2); nan for a row with
+    fewer than two contributing pixels or a zero variance."""
+    _, sf2, sg2, r, ok = central(mom)
+    with np.errstate(invalid="ignore"):
+        return r / np.sqrt(sf2 * sg2)
+
+
+def loglike_bl19(mom, scale: float = 1.0) -> np.ndarray:
+    """The log-likelihood of Brogi & Line (2019) per (v, s): -n/2 log(s_f^2 - 2 scale R + scale^2 s_g^2); nan for a
+    row with fewer than two contributing pixels, a zero variance or an argument of the logarithm that is not
+    positive."""
+    n, sf2, sg2, r, ok = central(mom)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        arg = sf2 - 2 * scale * r + scale * scale * sg2
+        return np.where(arg > 0, -0.5 * n * np.log(np.where(arg > 0, arg, 1.0)), np.nan)
+
+
+def chi2_sum(mom, a: float = 1.0, b: float = 0.0) -> float:
+    """chi2 added over every (v, s)."""
+    return float(np.sum(chi2(mom, a, b)))
+
+
+def ccf_sum(mom) -> float:
+    """ccf added over the (v, s) rows that have one: rows for which ccf is nan (fewer than two contributing pixels,
+    a zero variance) are SKIPPED, not counted as zero."""
+    return float(np.nansum(ccf(mom)))
+
+
+def loglike_bl19_sum(mom, scale: float = 1.0) -> float:
+    """loglike_bl19 added over the (v, s) rows that have one: rows for which it is nan (fewer than two contributing
+    pixels, a zero variance) are SKIPPED."""
+    return float(np.nansum(loglike_bl19(mom, scale)))
