@@ -462,6 +462,61 @@ int  trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */
                            int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
                            double *const *mom /* [k] -> [nexp][nseg][TRX_NMOMENT] */);
 
+/* The detrending filter between the pixels and their moments, on the device.  Observed exposures are detrended before
+ * they are compared with a model -- per spectral order the leading components in time (airmass, throughput, tellurics)
+ * are fitted and taken out -- and the same operation has to be applied to the model, or the likelihood is biased: the
+ * model reprocessing of Brogi & Line (2019) in the linear form of Gibson et al. (2022), M' = M - U (U^+ M).  It is a
+ * small linear map along the EXPOSURE axis of every pixel column; with it installed the whole likelihood stays on the
+ * device: spectrum -> pixels -> filter -> moments.
+ *
+ * A filter belongs to the observed set it is installed over.  It has one ncomp (1 .. TRX_FILTER_MAX) for all segments
+ * and per segment s two matrices: fwd[s][j][v] ([nseg][ncomp][nexp]), the coefficients C, and back[s][v][j]
+ * ([nseg][nexp][ncomp]), the basis B; a segment that wants fewer components pads with zeros.  For pixel p of segment
+ * s and exposure v, (a, b) is the pair trx_run_pixels gives and g[v][p] = gain_p * (a / b) as in the moments.
+ *   column p is LIVE when b > 0 at every exposure
+ *   otherwise it is DEAD, and all its values are quiet NaN: the projection needs the whole column, so a pixel whose
+ *   window leaves the grid at some exposures cannot be filtered
+ * and for a live column
+ *   c_j      = sum over v = 0 .. nexp-1, in that order, of fwd[s][j][v] * g[v][p]        j = 0 .. ncomp-1
+ *   r_v      = sum over j = 0 .. ncomp-1, in that order, of back[s][v][j] * c_j
+ *   g'[v][p] = g[v][p] - r_v
+ * every product and sum rounded once (no fused multiply-add), both sums started from +0.  The weights take no part in
+ * the projection: a caller who wants a weighted fit folds them into fwd.
+ *
+ * The filtered moments are the seven sums of trx_run_moments with g' in place of g, over the pixels whose value is not
+ * NaN and whose w > 0: the same terms, roundings, lane order and butterfly.  A row with no such pixel gives seven exact
+ * +0.  No atomics: the bits of a value depend on its column's pairs and gain and on its segment's two matrices and
+ * ncomp -- not on other columns or segments, the launch, the batch way that ran it or the handle's depth hint.
+ *
+ * trx_set_filter copies both matrices to the device (f NULL or ncomp = 0: clear the filter).  It returns TRX_E_ARG, the
+ * reason in trx_last_error, with no observed set installed, for ncomp < 0 or > TRX_FILTER_MAX, a NULL fwd or back, a
+ * non-finite entry (naming "segment S"); a refused filter leaves the previous one in force.  A successful
+ * trx_set_observed (a clearing one included) drops the filter, a successful trx_set_pixels drops both.
+ * trx_run_filtered_moments is trx_run_moments plus the filter: spectrum may be NULL, and when it is given it holds the
+ * bits trx_run gives; values, when given, receives g' ([nexp][npix], NaN in dead columns) for inspection and tests --
+ * without it only mom is copied back.  TRX_E_ARG with no filter installed, for every refusal of trx_run_moments, or
+ * with mom NULL; TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.  A run that fails leaves values and
+ * mom undefined.  trx_run, trx_run_bands, trx_run_contrib, trx_run_pixels and trx_run_moments on a handle with a filter
+ * installed are unchanged, bit for bit.
+ * trx_batch_set_filter installs the same filter on every handle of the batch, or on none (its reason through
+ * trx_last_error(NULL)); trx_run_batch_filtered_moments deals the atmospheres exactly as trx_run_batch_moments does. */
+#define TRX_FILTER_MAX 16
+typedef struct {
+  int32_t ncomp, pad;        /* components, 1 .. TRX_FILTER_MAX (0: clear); pad: 0                           */
+  const double *fwd;         /* [nseg][ncomp][nexp] coefficients, finite                                     */
+  const double *back;        /* [nseg][nexp][ncomp] basis, finite                                            */
+} trx_filter;
+int  trx_set_filter(trx_handle *h, const trx_filter *f);
+int  trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                              double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                              int32_t nshift, const double *shift /* [nshift], nshift = nexp */,
+                              double *values /* [nexp][npix], host; may be NULL */,
+                              double *mom /* [nexp][nseg][TRX_NMOMENT], host */, trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_filter(trx_batch *b, const trx_filter *f);
+int  trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                                    int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
+                                    double *const *mom /* [k] -> [nexp][nseg][TRX_NMOMENT] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

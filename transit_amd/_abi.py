@@ -95,6 +95,13 @@ class TrxObserved(C.Structure):
                 ("weight", c_double_p), ("gain", c_double_p)]
 
 
+FILTER_MAX = 16
+
+
+class TrxFilter(C.Structure):
+    _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("fwd", c_double_p), ("back", c_double_p)]
+
+
 class TrxStats(C.Structure):
     _fields_ = [
         ("nlines_inrange", C.c_int64), ("ngroups", C.c_int64), ("nadd", C.c_int64),
@@ -193,4 +200,19 @@ def bind_moments_api(lib):
     lib.trx_run_batch_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                           C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_moments.restype = C.c_int
+    return lib
+
+
+def bind_filter_api(lib):
+    """argtypes/restypes of the filter entry points (trx_set_filter, trx_run_filtered_moments and their batch forms)."""
+    lib.trx_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]
+    lib.trx_set_filter.restype = C.c_int
+    lib.trx_run_filtered_moments.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32,
+                                             c_double_p, c_double_p, c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_filtered_moments.restype = C.c_int
+    lib.trx_batch_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]
+    lib.trx_batch_set_filter.restype = C.c_int
+    lib.trx_run_batch_filtered_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
+                                                   C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_filtered_moments.restype = C.c_int
     return lib

@@ -38,6 +38,7 @@
 #include "trx_bands.hip.h"
 #include "trx_pixels.hip.h"
 #include "trx_moments.hip.h"
+#include "trx_filter.hip.h"
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 #include "../trx_plan.h"
@@ -83,9 +84,17 @@ struct PixelSet {
 struct ObservedSet {
   int32_t nexp = 0, nseg = 0; int64_t npix = 0;
   DevBuf d_seg, d_data, d_weight, d_gain;            // [nseg + 1], [nexp][npix], the same or none, [npix] or none
+  std::vector<int64_t> seg;                          // [nseg + 1] on the host: trx_set_filter cuts its tiles from it
 };
-// a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments)
-struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; };
+// a filter installed by trx_set_filter over the observed set (trx_filter.hip.h): the matrices zero-padded to npad
+// components and exposure-major, and the tiles of the observed set's segments
+struct FilterSet {
+  int32_t ncomp = 0, npad = 0, nexp = 0, nseg = 0; int64_t npix = 0, ntiles = 0;
+  DevBuf d_fwd, d_back, d_tiles;                     // [nseg][nexp][npad] each, FilterTile[ntiles]
+};
+// a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
+// filt: with the filter between the pairs and the moments (trx_run_filtered_moments)
+struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; };
 
 // The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
 // alone, before any stage.  Each selects between two forms of the same computation that give the same
@@ -208,6 +217,8 @@ struct trx_handle {
   DevBuf d_pixshift, d_pixout;                         // trx_run_pixels: the run's shifts [nshift] and its pairs [nshift][npix][2], grown on demand
   std::unique_ptr<ObservedSet> observed;               // trx_set_observed (null: none); belongs to `pixels`
   DevBuf d_mom;                                        // trx_run_moments: [nexp][nseg][TRX_NMOMENT], grown on demand
+  std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
+  DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
 };
 
 namespace {
@@ -2036,7 +2047,7 @@ struct Run {
   int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
   int side_work(SideWork &S); int queue_cia(); int join_early();
   // ... the spectrum of what they swept, the way back
-  int spectrum_kernel(); int ray_tail(); int band_kernels(); int pixel_kernels(); int moment_kernels(); int results();
+  int spectrum_kernel(); int ray_tail(); int band_kernels(); int pixel_kernels(); int filter_kernels(); int moment_kernels(); int results();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2689,13 +2700,42 @@ int Run::pixel_kernels()
   return TRX_OK;
 }
 
-// ---- the moments of those pairs against the observed set (trx_moments.hip.h), behind the pixel kernel on its queue;
-// a pass that resumes deeper queues both again.
+// ---- the filter of those pairs along the exposure axis (trx_filter.hip.h), behind the pixel kernel on its queue and
+// ahead of the moment kernel, which then reads its values; a pass that resumes deeper queues all three again.
+int Run::filter_kernels()
+{
+  if (!px || !px->filt) return TRX_OK;
+  const FilterSet &F = *px->filt;
+  const ObservedSet *O = px->obs;
+  FilterArgs FA{};
+  FA.pairs = h->d_pixout.as<double2>(); FA.gain = O ? O->d_gain.as<double>() : nullptr;
+  FA.fwd = F.d_fwd.as<double>(); FA.back = F.d_back.as<double>(); FA.tiles = F.d_tiles.as<FilterTile>(); FA.val = h->d_pixval.as<double>();
+  FA.npix = F.npix; FA.ntiles = F.ntiles; FA.nexp = F.nexp;
+  const int64_t blocks = (FA.ntiles + kFiltWaves - 1) / kFiltWaves;
+  const size_t cells = sizeof(double) * (size_t)F.nexp * (size_t)F.npix, mat = sizeof(double) * (size_t)F.nseg * (size_t)F.nexp * (size_t)F.npad;
+  // (every address the kernel reads or writes: pairs and values over [nexp][npix] -- the tiles lie in [0, npix) and name
+  // segments below nseg, made so when the filter was --, the gains, the two padded matrices, the tiles)
+  if (!O || !FA.pairs || !FA.fwd || !FA.back || !FA.tiles || !FA.val || F.nexp < 1 || F.nseg < 1 || F.ncomp < 1 || F.ncomp > F.npad ||
+      (F.npad != 4 && F.npad != 8 && F.npad != 16) || F.npix != px->set->npix || F.nexp != px->nshift || F.npix != O->npix || F.nexp != O->nexp || F.nseg != O->nseg ||
+      h->d_pixout.bytes < 2 * cells || h->d_pixval.bytes < cells || F.d_fwd.bytes < mat || F.d_back.bytes < mat ||
+      (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) || F.d_tiles.bytes < sizeof(FilterTile) * (size_t)F.ntiles ||
+      blocks < 1 || blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the filter kernel (not launched)");
+  const dim3 grid((unsigned)blocks), block(64 * kFiltWaves);
+  if (F.npad == 4) hipLaunchKernelGGL(k_pixel_filter<4>, grid, block, 0, tst, FA);
+  else if (F.npad == 8) hipLaunchKernelGGL(k_pixel_filter<8>, grid, block, 0, tst, FA);
+  else hipLaunchKernelGGL(k_pixel_filter<16>, grid, block, 0, tst, FA);
+  return TRX_OK;
+}
+
+// ---- the moments of those pairs (of the filter's values: a filtered run) against the observed set (trx_moments.hip.h),
+// behind the pixel kernel on its queue; a pass that resumes deeper queues both again.
 int Run::moment_kernels()
 {
   if (!px || !px->obs) return TRX_OK;
   const ObservedSet &O = *px->obs;
   MomArgs MA{};
+  MA.val = px->filt ? h->d_pixval.as<double>() : nullptr;
   MA.pairs = h->d_pixout.as<double2>(); MA.data = O.d_data.as<double>(); MA.weight = O.d_weight.as<double>(); MA.gain = O.d_gain.as<double>();
   MA.seg_first = O.d_seg.as<int64_t>(); MA.mom = h->d_mom.as<double>();
   MA.npix = O.npix; MA.nseg = O.nseg; MA.nrows = (int64_t)O.nexp * O.nseg;
@@ -2706,9 +2746,11 @@ int Run::moment_kernels()
   if (!MA.pairs || !MA.data || !MA.seg_first || !MA.mom || O.nexp < 1 || O.nseg < 1 || O.npix != px->set->npix || O.nexp != px->nshift ||
       h->d_pixout.bytes < 2 * cells || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
       (MA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
-      h->d_mom.bytes < sizeof(double) * TRX_NMOMENT * (size_t)MA.nrows || blocks < 1 || blocks > 0x7fffffffLL)
+      h->d_mom.bytes < sizeof(double) * TRX_NMOMENT * (size_t)MA.nrows || blocks < 1 || blocks > 0x7fffffffLL ||
+      (px->filt && (!MA.val || h->d_pixval.bytes < cells)))
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the moment kernel (not launched)");
-  hipLaunchKernelGGL(k_pixel_moments, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
+  if (px->filt) hipLaunchKernelGGL(k_pixel_moments<true>, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
+  else hipLaunchKernelGGL(k_pixel_moments<false>, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
   return TRX_OK;
 }
 
@@ -2752,7 +2794,7 @@ int Run::pass()
   int rc;
   for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
   if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = pixel_kernels()) || (rc = moment_kernels()) ? rc : results();
+  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = pixel_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : results();
 }
 
 // Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
@@ -3063,8 +3105,9 @@ static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<P
   return TRX_OK;
 }
 
-// (the observed set belongs to the pixel set it was installed over: it goes with it)
-static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->pixels = std::move(S); h->observed.reset(); }
+// (the observed set belongs to the pixel set it was installed over, the filter to the observed set: they go with it)
+static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); }
+static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->observed = std::move(S); h->filter.reset(); }
 
 int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 {
@@ -3075,20 +3118,22 @@ int trx_set_pixels(trx_handle *h, const trx_pixels *px)
   return TRX_OK;
 }
 
-// a pixel run for `who` (trx_run_pixels; obs: trx_run_moments): the pairs are in h->d_pixout, the moments in h->d_mom, when it returns
+// a pixel run for `who` (trx_run_pixels; obs: trx_run_moments; filt: trx_run_filtered_moments): the pairs are in h->d_pixout, the
+// moments in h->d_mom, the filtered values in h->d_pixval, when it returns
 static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                     const ObservedSet *obs, trx_debug *dbg)
+                     const ObservedSet *obs, trx_debug *dbg, const FilterSet *filt = nullptr)
 {
   const std::string w(who);
   for (int32_t v = 0; v < nshift; v++)
     if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, w + ": shift " + std::to_string(v) + " must be finite and > 0");
-  const PixelRun PR{h->pixels.get(), nshift, obs};
+  const PixelRun PR{h->pixels.get(), nshift, obs, filt};
   if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, w + ": nshift * npix above what one launch takes");
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
   if ((rc = ensure(h, h->d_pixout, sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix)) ||
       (obs && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
+      (filt && (rc = ensure(h, h->d_pixval, sizeof(double) * (size_t)nshift * (size_t)PR.set->npix))) ||
       (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift)))
     return rc;
   return run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR);
@@ -3135,6 +3180,7 @@ static int make_observed_set(trx_handle *h, const trx_observed *ob, std::unique_
   std::unique_ptr<ObservedSet> S(new (std::nothrow) ObservedSet);
   if (!S) return fail(h, TRX_E_NOMEM, "observed: out of host memory");
   S->nexp = ob->nexp; S->nseg = ob->nseg; S->npix = npix;
+  try { S->seg.assign(ob->seg_first, ob->seg_first + ob->nseg + 1); } catch (...) { return fail(h, TRX_E_NOMEM, "observed: out of host memory"); }
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   if ((rc = upload_raw(h, S->d_seg, ob->seg_first, (size_t)ob->nseg + 1)) || (rc = upload_raw(h, S->d_data, ob->data, cells)) ||
@@ -3150,7 +3196,7 @@ int trx_set_observed(trx_handle *h, const trx_observed *ob)
   if (!h) return TRX_E_ARG;
   std::unique_ptr<ObservedSet> S;
   if (const int rc = make_observed_set(h, ob, S)) return rc;
-  h->observed = std::move(S);
+  install_observed_set(h, S);
   return TRX_OK;
 }
 
@@ -3169,6 +3215,84 @@ int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   if (!mom) return fail(h, TRX_E_ARG, "trx_run_moments: mom is NULL");
   if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, nshift, shift, ob, dbg)) return rc;
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
+// ---- the detrending filter between the pairs and the moments (trx_filter.hip.h) ---------------------
+// The filter, checked whole before anything is replaced.  The device gets the two matrices exposure-major and zero-padded
+// to the kernel's 4, 8 or 16 components, and the tiles of the observed set's segments: up to 64 consecutive pixels of one
+// segment each, a segment's tiles in pixel order.
+static int make_filter_set(trx_handle *h, const trx_filter *f, std::unique_ptr<FilterSet> &out)
+{
+  out.reset();
+  if (!f || f->ncomp == 0) return TRX_OK;               // (clear)
+  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "filter: no observed set installed (trx_set_observed)");
+  const ObservedSet &O = *h->observed;
+  if (f->ncomp < 0) return fail(h, TRX_E_ARG, "filter: ncomp < 0");
+  if (f->ncomp > TRX_FILTER_MAX) return fail(h, TRX_E_ARG, "filter: ncomp above TRX_FILTER_MAX (" + std::to_string(TRX_FILTER_MAX) + ")");
+  if (!f->fwd || !f->back) return fail(h, TRX_E_ARG, "filter: NULL fwd or back array");
+  const size_t nc = (size_t)f->ncomp, ne = (size_t)O.nexp, per = nc * ne;
+  for (int32_t s = 0; s < O.nseg; s++)
+    for (size_t k = 0; k < per; k++) {
+      if (!std::isfinite(f->fwd[(size_t)s * per + k])) return fail(h, TRX_E_ARG, "filter: segment " + std::to_string(s) + ": fwd entry must be finite");
+      if (!std::isfinite(f->back[(size_t)s * per + k])) return fail(h, TRX_E_ARG, "filter: segment " + std::to_string(s) + ": back entry must be finite");
+    }
+  std::unique_ptr<FilterSet> S(new (std::nothrow) FilterSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "filter: out of host memory");
+  S->ncomp = f->ncomp; S->npad = f->ncomp <= 4 ? 4 : f->ncomp <= 8 ? 8 : 16;
+  S->nexp = O.nexp; S->nseg = O.nseg; S->npix = O.npix;
+  std::vector<double> fw, bk; std::vector<FilterTile> tiles;
+  try {
+    const size_t np = (size_t)S->npad;
+    fw.assign((size_t)O.nseg * ne * np, 0.0); bk.assign((size_t)O.nseg * ne * np, 0.0);
+    for (size_t s = 0; s < (size_t)O.nseg; s++)
+      for (size_t v = 0; v < ne; v++)
+        for (size_t j = 0; j < nc; j++) {
+          fw[(s * ne + v) * np + j] = f->fwd[(s * nc + j) * ne + v];
+          bk[(s * ne + v) * np + j] = f->back[(s * ne + v) * nc + j];
+        }
+    for (int32_t s = 0; s < O.nseg; s++)
+      for (int64_t p = O.seg[(size_t)s]; p < O.seg[(size_t)s + 1]; p += 64)
+        tiles.push_back(FilterTile{p, s, (int32_t)std::min<int64_t>(64, O.seg[(size_t)s + 1] - p)});
+  } catch (...) { return fail(h, TRX_E_NOMEM, "filter: out of host memory"); }
+  S->ntiles = (int64_t)tiles.size();
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload_raw(h, S->d_fwd, fw.data(), fw.size())) || (rc = upload_raw(h, S->d_back, bk.data(), bk.size())) ||
+      (rc = upload_raw(h, S->d_tiles, tiles.data(), tiles.size())))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
+  out = std::move(S);
+  return TRX_OK;
+}
+
+int trx_set_filter(trx_handle *h, const trx_filter *f)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<FilterSet> S;
+  if (const int rc = make_filter_set(h, f, S)) return rc;
+  h->filter = std::move(S);
+  return TRX_OK;
+}
+
+int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                             double *values, double *mom, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  // (as for trx_run_moments: neither the filtered values' live flags nor the moments follow from a shard's partial pairs)
+  if (h->windowed())
+    return fail(h, TRX_E_UNSUPPORTED, "trx_run_filtered_moments: this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
+                                      "(trx_gather_host) and filter and reduce them on the host");
+  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: no observed set installed (trx_set_observed)");
+  if (!h->filter) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: no filter installed (trx_set_filter)");
+  const ObservedSet *ob = h->observed.get();
+  if (nshift != ob->nexp) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: nshift " + std::to_string(nshift) + " is not the observed set's nexp " + std::to_string(ob->nexp));
+  if (!shift) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: shift is NULL");
+  if (!mom) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: mom is NULL");
+  if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, nshift, shift, ob, dbg, h->filter.get())) return rc;
+  // (the run has been waited for)
+  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));
+  if (values) HIPCHK(h, hipMemcpy(values, h->d_pixval.p, sizeof(double) * (size_t)ob->nexp * (size_t)ob->npix, hipMemcpyDeviceToHost));
   return TRX_OK;
 }
 
@@ -3191,6 +3315,7 @@ struct trx_batch {
   double *const *contrib = nullptr;                  // trx_run_batch_contrib: and the contribution functions
   int32_t nshift = 0; const double *const *shifts = nullptr; double *const *pix = nullptr;      // trx_run_batch_pixels: the pixel pairs instead
   double *const *mom = nullptr;                      // trx_run_batch_moments: the moments instead (shifts as for pix)
+  bool filtered = false;                             // trx_run_batch_filtered_moments: ... through the filter
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -3234,7 +3359,8 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
         for (;;) {
           const int32_t j = b->next.fetch_add(1);
           if (j >= b->k) break;
-          const int rc = b->mom ? trx_run_moments(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
+          const int rc = b->mom && b->filtered ? trx_run_filtered_moments(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], nullptr, b->mom[j], nullptr)
+                       : b->mom ? trx_run_moments(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
                        : b->pix ? trx_run_pixels(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
                        : b->contrib ? trx_run_contrib(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
                        : b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
@@ -3258,12 +3384,12 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
 static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
                       double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr,
-                      double *const *mom = nullptr)
+                      double *const *mom = nullptr, bool filtered = false)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
   b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
-  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom;
+  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3354,7 +3480,7 @@ int trx_batch_set_observed(trx_batch *b, const trx_observed *ob)
     const int rc = make_observed_set(b->hs[i], ob, sets[i]);
     if (rc) { g_comm_err = b->hs[i]->err; return rc; }
   }
-  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->observed = std::move(sets[i]);
+  for (size_t i = 0; i < b->hs.size(); i++) install_observed_set(b->hs[i], sets[i]);
   return TRX_OK;
 }
 
@@ -3369,6 +3495,34 @@ int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx
     if (!mom[j]) { g_comm_err = "trx_run_batch_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   }
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom);
+}
+
+// every handle of the batch gets the same filter, or none does
+int trx_batch_set_filter(trx_batch *b, const trx_filter *f)
+{
+  g_comm_err.clear();
+  if (!b) return TRX_E_ARG;
+  std::vector<std::unique_ptr<FilterSet>> sets(b->hs.size());
+  for (size_t i = 0; i < b->hs.size(); i++) {
+    const int rc = make_filter_set(b->hs[i], f, sets[i]);
+    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
+  }
+  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->filter = std::move(sets[i]);
+  return TRX_OK;
+}
+
+int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
+                                   double *const *mom)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_filtered_moments: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_filtered_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_moments: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) {
+    if (!shift[j]) { g_comm_err = "trx_run_batch_filtered_moments: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+    if (!mom[j]) { g_comm_err = "trx_run_batch_filtered_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  }
+  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom, true);
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

@@ -21,6 +21,10 @@
 //                    coalesced; a wave issues the loads of kMomTrips trips of 64 pixels before it adds the first
 //                    (a lane past the segment's end reads the segment's last pixel again and adds nothing).
 //
+//   k_pixel_moments<true>   the same sums over the FILTERED values of the run (trx_filter.hip.h, trx_run_filtered_moments):
+//                    the model value is val[v][p] as it stands, a pixel contributes when that is not NaN and w > 0;
+//                    24 bytes per pixel.  <false> is the form above.
+//
 // No atomics: the bits of a row depend on the pairs, data and weights of that exposure over that segment's pixels and
 // on their gains -- not on the other segments or exposures of the call, the launch, the handle that ran it or the
 // run's step plan.
@@ -37,6 +41,7 @@ constexpr int kMomTrips = 4;                          // trips of 64 pixels whos
 
 struct MomArgs {
   const double2 *pairs;     // [nexp][npix] (a, b): d_pixout of this run
+  const double *val;        // [nexp][npix] k_pixel_moments<true>: the filtered values of this run (trx_filter.hip.h), NaN = none
   const double *data;       // [nexp][npix]
   const double *weight;     // [nexp][npix], or null: all 1
   const double *gain;       // [npix], or null: all 1
@@ -46,6 +51,9 @@ struct MomArgs {
   int32_t nseg;
 };
 
+// kValues: the model value of a pixel is val[v][p] as it stands (gain and division are in it already), and the pixel
+// contributes when that is not NaN and w > 0; the terms, their order and the butterfly are the same
+template <bool kValues>
 __global__ __launch_bounds__(64 * kMomWaves) void k_pixel_moments(MomArgs A)
 {
 #pragma clang fp contract(off)
@@ -65,15 +73,15 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_pixel_moments(MomArgs A)
       const int64_t q = p0 + 64 * t + lane;
       in[t] = q < last;
       const int64_t p = in[t] ? q : last - 1;
-      ab[t] = A.pairs[base + p];
+      if constexpr (kValues) { ab[t].x = A.val[base + p]; ab[t].y = 1.0; g0[t] = 1.0; }
+      else { ab[t] = A.pairs[base + p]; g0[t] = A.gain ? A.gain[p] : 1.0; }
       f[t] = A.data[base + p];
       w[t] = A.weight ? A.weight[base + p] : 1.0;
-      g0[t] = A.gain ? A.gain[p] : 1.0;
     }
 #pragma unroll
     for (int t = 0; t < kMomTrips; t++)
-      if (in[t] && ab[t].y > 0.0 && w[t] > 0.0) {
-        const double g = g0[t] * (ab[t].x / ab[t].y);
+      if (in[t] && (kValues ? ab[t].x == ab[t].x : ab[t].y > 0.0) && w[t] > 0.0) {
+        const double g = kValues ? ab[t].x : g0[t] * (ab[t].x / ab[t].y);
         const double wg = w[t] * g, wf = w[t] * f[t];
         n += 1.0; sw += w[t]; swg += wg; swgg += wg * g; swf += wf; swfg += wf * g; swff += wf * f[t];
       }

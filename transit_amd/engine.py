@@ -204,6 +204,7 @@ def hip_library():
         _abi.bind_contrib_api(lib)
         _abi.bind_pixels_api(lib)
         _abi.bind_moments_api(lib)
+        _abi.bind_filter_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -313,6 +314,32 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_moments", self._last_error())
         return (mom, spec) if spectrum else mom
+
+    def set_filter(self, filt):
+        """trx_set_filter: install a detrending filter (a transit_amd.xcor.Filter; None: clear it) over the observed
+        set in force.  set_observed and set_pixels drop it."""
+        rc = self._lib.trx_set_filter(self._h, C.byref(filt.to_c()) if filt is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_filter", self._last_error())
+
+    def run_filtered_moments(self, atm, opts, shifts, spectrum: bool = False, values: bool = False):
+        """trx_run_filtered_moments: the moments [nexp, nseg, 7] of the FILTERED pixels (transit_amd.xcor) against the
+        observed set; with spectrum=True and/or values=True a tuple (moments[, spectrum][, values]) -- the spectrum
+        bit for bit what run() gives, the values [nexp, npix] the filtered model g' (NaN in dead columns).  Without
+        values=True neither the pairs nor the values leave the device."""
+        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        mom = np.zeros(getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        spec = np.zeros(self.nwn) if spectrum else None
+        val = np.zeros((mom.shape[0], getattr(self, "npix", 0))) if values else None
+        rc = self._lib.trx_run_filtered_moments(self._h, C.byref(atm), C.byref(opts),
+                                                spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                                int(sh.size), sh.ctypes.data_as(_abi.c_double_p),
+                                                val.ctypes.data_as(_abi.c_double_p) if val is not None else None,
+                                                mom.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_filtered_moments", self._last_error())
+        out = (mom,) + ((spec,) if spectrum else ()) + ((val,) if values else ())
+        return out if len(out) > 1 else mom
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -442,6 +469,28 @@ class Batch:
         rc = self._lib.trx_run_batch_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_moments", self._err())
+        return out
+
+    def set_filter(self, filt):
+        """trx_batch_set_filter: the same filter on every handle of the batch, or on none."""
+        rc = self._lib.trx_batch_set_filter(self._b, C.byref(filt.to_c()) if filt is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_filter", self._err())
+
+    def run_filtered_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
+        """trx_run_batch_filtered_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp], each atmosphere's moments
+        what Engine.run_filtered_moments gives, bit for bit."""
+        k = len(atms)
+        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        if sh.ndim != 2 or sh.shape[0] != k:
+            raise ValueError("Batch.run_filtered_moments: shifts of shape [K][nexp], one row per atmosphere")
+        out = np.zeros((k,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        ps = (_abi.c_double_p * max(k, 1))(*[sh[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_filtered_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_filtered_moments", self._err())
         return out
 
     def close(self):

@@ -15,6 +15,21 @@ contributes when b > 0 and w > 0; its model value is g = gain_p * (a / b).  Over
     ccf(mom)                                             the weighted Pearson coefficient of f and g per (v, s)
     loglike_bl19(mom, scale=1)                           the Brogi & Line (2019) log-likelihood per (v, s)
     chi2_sum, ccf_sum, loglike_bl19_sum                  the same added over all (v, s)
+
+The detrending filter (Engine.set_filter / Engine.run_filtered_moments; trx_set_filter / trx_run_filtered_moments): per
+segment s a coefficient matrix fwd[s] ([ncomp, nexp]) and a basis back[s] ([nexp, ncomp]) act along the exposure axis
+of every pixel column.  A column is live when b > 0 at every exposure, otherwise dead and all NaN; for a live column
+
+    c_j = sum_v fwd[s][j][v] g[v][p]      r_v = sum_j back[s][v][j] c_j      g'[v][p] = g[v][p] - r_v
+
+and the filtered moments are the seven sums with g' in place of g over the pixels with a value and w > 0.
+
+    Filter(fwd, back)                                    a filter; to_c() its trx_filter
+    svd_filter(data, seg_first, ncomp)                   back = U, fwd = U^T: each segment's leading left singular vectors
+    filter_reference(pairs, obs, filt)                   g' by the definition, in np.longdouble and rounded; dead columns NaN
+    filter_abs_reference(pairs, obs, filt)               |g| + |back| (|fwd| |g|): the scale of a value's rounding error
+    reference_values(values, obs)                        the moments from a value matrix [nexp, npix], sums by math.fsum
+    abs_reference_values(values, obs)                    the same with |f| and |values|
 """
 from __future__ import annotations
 
@@ -86,15 +101,27 @@ class Observed:
         return c
 
 
-def _moments(pairs, obs: Observed, absolute: bool) -> np.ndarray:
+def _model(pairs, obs: Observed):
+    """(g, b > 0): the model values gain_p * (a / b) -- one division, one product, each rounded once -- where b > 0
+    (0 elsewhere), and where that is"""
     pairs = np.asarray(pairs, dtype=np.float64)
     if pairs.shape != (obs.nexp, obs.npix, 2):
         raise ValueError("pairs of shape [nexp][npix][2]")
     a, b = pairs[..., 0], pairs[..., 1]
-    w = obs.weight if obs.weight is not None else np.ones_like(obs.data)
     gain = obs.gain if obs.gain is not None else np.ones(obs.npix)
-    use = (b > 0) & (w > 0)
-    g = gain[None, :] * (a / np.where(use, b, 1.0))          # one division, one product, each rounded once
+    on = b > 0
+    return np.where(on, gain[None, :] * (a / np.where(on, b, 1.0)), 0.0), on
+
+
+def _moments(pairs, obs: Observed, absolute: bool) -> np.ndarray:
+    g, on = _model(pairs, obs)
+    return _sums(g, on, obs, absolute)
+
+
+def _sums(g, has, obs: Observed, absolute: bool) -> np.ndarray:
+    """the seven sums per (v, s) of the model values g over the pixels that have one (has) and w > 0"""
+    w = obs.weight if obs.weight is not None else np.ones_like(obs.data)
+    use = has & (w > 0)
     f = obs.data
     if absolute:
         g, f = np.abs(g), np.abs(f)
@@ -177,3 +204,108 @@ def loglike_bl19_sum(mom, scale: float = 1.0) -> float:
     """loglike_bl19 added over the (v, s) rows that have one: rows for which it is nan (fewer than two contributing
     pixels, a zero variance) are SKIPPED."""
     return float(np.nansum(loglike_bl19(mom, scale)))
+
+
+@dataclass
+class Filter:
+    """One trx_filter: the coefficients fwd [nseg, ncomp, nexp] and the basis back [nseg, nexp, ncomp] (finite; a
+    segment that wants fewer components pads with zeros)."""
+    fwd: np.ndarray
+    back: np.ndarray
+
+    def __post_init__(self):
+        self.fwd = np.ascontiguousarray(self.fwd, dtype=np.float64)
+        self.back = np.ascontiguousarray(self.back, dtype=np.float64)
+        if self.fwd.ndim != 3 or self.back.ndim != 3:
+            raise ValueError("Filter: fwd of shape [nseg][ncomp][nexp], back of shape [nseg][nexp][ncomp]")
+        if self.back.shape != (self.fwd.shape[0], self.fwd.shape[2], self.fwd.shape[1]):
+            raise ValueError("Filter: back of the shape of fwd with its last two axes exchanged")
+
+    @property
+    def nseg(self) -> int:
+        return int(self.fwd.shape[0])
+
+    @property
+    def ncomp(self) -> int:
+        return int(self.fwd.shape[1])
+
+    @property
+    def nexp(self) -> int:
+        return int(self.fwd.shape[2])
+
+    def to_c(self):
+        """The trx_filter of the filter (the arrays stay owned by this object)."""
+        c = _abi.TrxFilter()
+        c.ncomp, c.pad = self.ncomp, 0
+        c.fwd = self.fwd.ctypes.data_as(_abi.c_double_p)
+        c.back = self.back.ctypes.data_as(_abi.c_double_p)
+        return c
+
+
+def svd_filter(data, seg_first, ncomp: int) -> Filter:
+    """The filter that takes the leading ncomp principal components in time out of every segment: per segment the
+    leading left singular vectors U ([nexp, ncomp]) of data[:, segment], back = U and fwd = U^T.  A segment with fewer
+    singular vectors than ncomp (an empty one: none) pads with zeros."""
+    data = np.asarray(data, dtype=np.float64)
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    nexp, nseg = data.shape[0], seg.size - 1
+    back = np.zeros((nseg, nexp, ncomp))
+    for s in range(nseg):
+        if seg[s + 1] > seg[s]:
+            u = np.linalg.svd(data[:, seg[s]:seg[s + 1]], full_matrices=False)[0][:, :ncomp]
+            back[s, :, :u.shape[1]] = u
+    return Filter(np.ascontiguousarray(back.transpose(0, 2, 1)), back)
+
+
+def _check_filter(obs: Observed, filt: Filter):
+    if (filt.nseg, filt.nexp) != (obs.nseg, obs.nexp):
+        raise ValueError("filter of the observed set's nseg and nexp")
+
+
+def filter_reference(pairs, obs: Observed, filt: Filter) -> np.ndarray:
+    """The definition: g' [nexp, npix] from the pixel pairs [nexp, npix, 2] of a run -- g in numpy as the moments take
+    it, the projection in np.longdouble, rounded to double at the end; a column with b <= 0 at any exposure is NaN."""
+    _check_filter(obs, filt)
+    g, on = _model(pairs, obs)
+    live = np.all(on, axis=0)
+    out = np.full(g.shape, np.nan)
+    gl = g.astype(np.longdouble)
+    for s in range(obs.nseg):
+        k = np.arange(obs.seg_first[s], obs.seg_first[s + 1])
+        k = k[live[k]]
+        c = filt.fwd[s].astype(np.longdouble) @ gl[:, k]
+        out[:, k] = (gl[:, k] - filt.back[s].astype(np.longdouble) @ c).astype(np.float64)
+    return out
+
+
+def filter_abs_reference(pairs, obs: Observed, filt: Filter) -> np.ndarray:
+    """|g| + |back| (|fwd| |g|) [nexp, npix]: what the rounding error of a filtered value is relative to (NaN in the
+    dead columns)."""
+    _check_filter(obs, filt)
+    g, on = _model(pairs, obs)
+    live = np.all(on, axis=0)
+    out = np.full(g.shape, np.nan)
+    for s in range(obs.nseg):
+        k = np.arange(obs.seg_first[s], obs.seg_first[s + 1])
+        k = k[live[k]]
+        out[:, k] = np.abs(g[:, k]) + np.abs(filt.back[s]) @ (np.abs(filt.fwd[s]) @ np.abs(g[:, k]))
+    return out
+
+
+def _values(values, obs: Observed):
+    values = np.asarray(values, dtype=np.float64)
+    if values.shape != (obs.nexp, obs.npix):
+        raise ValueError("values of shape [nexp][npix]")
+    has = ~np.isnan(values)
+    return np.where(has, values, 0.0), has
+
+
+def reference_values(values, obs: Observed) -> np.ndarray:
+    """The moments [nexp, nseg, 7] of a matrix of model values [nexp, npix] (gain and division in them already, NaN:
+    no value) against the observed set: the terms and the sums of reference()."""
+    return _sums(*_values(values, obs), obs, False)
+
+
+def abs_reference_values(values, obs: Observed) -> np.ndarray:
+    """reference_values with |f| and |values|."""
+    return _sums(*_values(values, obs), obs, True)
