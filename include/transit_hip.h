@@ -517,6 +517,71 @@ int  trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm 
                                     int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
                                     double *const *mom /* [k] -> [nexp][nseg][TRX_NMOMENT] */);
 
+/* Rotational broadening of the spectrum on the device, between the spectrum and the detector pixels: the planet's own
+ * velocity broadening -- the rotation kernel of v sin i with linear limb darkening -- that a high-resolution retrieval
+ * applies before the instrument's line-spread function.  Its width is a fitted parameter (it changes with every
+ * likelihood call) and its profile is not a Gaussian, so it cannot be folded into the pixel set's fwhm; with it
+ * installed the chain spectrum -> broadening -> pixels -> filter -> moments stays on the device.  (An extra GAUSSIAN
+ * velocity broadening needs none of this: it is exact through the pixels' fwhm, added in quadrature.)
+ *
+ * The grid is nu_i = wn_i + i*wn_d, i = 0 .. nwn-1, as for bands.  A broadening is {kind = TRX_BROADEN_ROTATION,
+ * beta = v sin i / c, limb = the linear limb-darkening coefficient in [0, 1]}.  For output bin i, every operation
+ * IEEE double rounded once, and without fused multiply-add where marked # (the integers h_i are then the same on host
+ * and device):
+ *   nu_i = wn_i + (double)i * wn_d        #
+ *   d_i  = nu_i * beta                    #   half-width in cm-1 (first order in beta)
+ *   h_i  = floor(d_i / wn_d)              #   half-width in bins; non-decreasing in i
+ *   h_i == 0:  B_i = S_i exactly (a copy)
+ *   else
+ *     w_0 = c1 + c2,   c1 = 2 (1 - limb),  c2 = (pi / 2) limb
+ *     num = w_0 * S_i,  den = w_0
+ *     for k = 1 .. h_i, ascending:
+ *         x = ((double)k * wn_d) / d_i ;  t = max(0, 1 - x*x) ;  w = c1 * sqrt(t) + c2 * t
+ *         s = (S_{i-k} if i-k >= 0 else +0) + (S_{i+k} if i+k < nwn else +0)
+ *         m = the number of those two bins inside the grid (0, 1 or 2)
+ *         num += w * s ;  den += w * m
+ *     B_i = num / den
+ * This is Gray's rotation profile sampled at the bin centres and renormalised by the weights actually used: at the
+ * grid's ends the window is one-sided, as the pixel windows are clipped there.  No atomics: the bits of B_i depend on S
+ * over [i - h_i, i + h_i], on beta and on limb only -- not on the launch, the batch way that ran it or the handle's
+ * depth hint.
+ *
+ * trx_set_broadening stores the two scalars (nothing is copied to the device); br NULL or kind TRX_BROADEN_NONE clears
+ * it.  The broadening stays in force until it is replaced or cleared and is independent of the pixel, observed and
+ * filter sets: trx_set_pixels does not drop it.  It returns TRX_E_ARG, the reason in trx_last_error, for an unknown
+ * kind, a non-finite or <= 0 beta, a non-finite limb or one outside [0, 1], a handle with wn_i <= 0 or wn_d <= 0, and
+ * for h_{nwn-1} > TRX_BROADEN_MAX_HALF (the error names the half-width); TRX_E_UNSUPPORTED on a handle whose shard is
+ * not the whole grid (the window needs neighbours across the shard's edge: such a job gathers the spectrum and
+ * broadens it itself, as it already does for the moments).  A refused call leaves the previous broadening in force.
+ *
+ * trx_run_broadened is trx_run plus B: spectrum may be NULL, and when it is given it holds the bits trx_run gives --
+ * never the broadened spectrum.  TRX_E_ARG with no broadening installed or broadened NULL.  A run that fails leaves
+ * broadened undefined.
+ * With a broadening installed, trx_run_pixels, trx_run_moments and trx_run_filtered_moments (and their batch forms)
+ * sample B in place of S: every pair is exactly what the pixel kernel gives when its spectrum is the buffer
+ * trx_run_broadened returns -- the same kernel, unchanged.  trx_run, trx_run_device, trx_run_bands, trx_run_contrib and
+ * trx_sweep_permol are unchanged bit for bit whatever is installed, and with nothing installed every entry point is.
+ *
+ * trx_batch_set_broadening: a retrieval's walkers carry a v sin i each, so br[j] belongs to atmosphere j of the
+ * following batch pixel, moment, filtered-moment and broadened runs; n = 1: the same broadening for every atmosphere;
+ * n = 0: clear it.  All n entries are checked before any is kept, or none is (the reason through
+ * trx_last_error(NULL)).  Such a run of k atmospheres with n != 1 and n != k returns TRX_E_ARG.  trx_run_batch,
+ * trx_run_batch_bands and trx_run_batch_contrib ignore the broadening.  trx_run_batch_broadened is trx_run_batch with
+ * broadened[j] ([nwn]) in place of the spectra. */
+typedef enum { TRX_BROADEN_NONE = 0, TRX_BROADEN_ROTATION = 1 } trx_broaden_kind;
+typedef struct {
+  int32_t kind, pad;         /* trx_broaden_kind; pad is ignored                                             */
+  double beta, limb;         /* v sin i / c (finite, > 0); limb-darkening coefficient, finite, in [0, 1]     */
+} trx_broadening;
+#define TRX_BROADEN_MAX_HALF 2048          /* largest h_i a handle accepts */
+int  trx_set_broadening(trx_handle *h, const trx_broadening *br);
+int  trx_run_broadened(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                       double *spectrum /* [nwn], host; may be NULL */, double *broadened /* [nwn], host */,
+                       trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_broadening(trx_batch *b, int32_t n, const trx_broadening *br /* [n] */);
+int  trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                             double *const *broadened /* [k] -> [nwn] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

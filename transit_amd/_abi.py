@@ -102,6 +102,14 @@ class TrxFilter(C.Structure):
     _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("fwd", c_double_p), ("back", c_double_p)]
 
 
+BROADEN_NONE, BROADEN_ROTATION = 0, 1
+BROADEN_MAX_HALF = 2048
+
+
+class TrxBroadening(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("beta", C.c_double), ("limb", C.c_double)]
+
+
 class TrxStats(C.Structure):
     _fields_ = [
         ("nlines_inrange", C.c_int64), ("ngroups", C.c_int64), ("nadd", C.c_int64),
@@ -215,4 +223,19 @@ def bind_filter_api(lib):
     lib.trx_run_batch_filtered_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                                    C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_filtered_moments.restype = C.c_int
+    return lib
+
+
+def bind_broaden_api(lib):
+    """argtypes/restypes of the broadening entry points (trx_set_broadening, trx_run_broadened and their batch forms)."""
+    lib.trx_set_broadening.argtypes = [C.c_void_p, C.POINTER(TrxBroadening)]
+    lib.trx_set_broadening.restype = C.c_int
+    lib.trx_run_broadened.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, c_double_p,
+                                      C.POINTER(TrxDebug)]
+    lib.trx_run_broadened.restype = C.c_int
+    lib.trx_batch_set_broadening.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxBroadening)]
+    lib.trx_batch_set_broadening.restype = C.c_int
+    lib.trx_run_batch_broadened.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
+                                            C.POINTER(c_double_p)]
+    lib.trx_run_batch_broadened.restype = C.c_int
     return lib

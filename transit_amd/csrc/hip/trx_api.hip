@@ -39,10 +39,12 @@
 #include "trx_pixels.hip.h"
 #include "trx_moments.hip.h"
 #include "trx_filter.hip.h"
+#include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 #include "../trx_plan.h"
 #include "../trx_table.h"
+#include "../trx_broaden.h"
 
 using namespace trx;
 
@@ -95,6 +97,9 @@ struct FilterSet {
 // a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
 // filt: with the filter between the pairs and the moments (trx_run_filtered_moments)
 struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; };
+// a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
+// the largest -- which sizes the kernel's tile
+struct Broadening { double beta = 0, limb = 0; int hmax = 0; };
 
 // The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
 // alone, before any stage.  Each selects between two forms of the same computation that give the same
@@ -219,6 +224,8 @@ struct trx_handle {
   DevBuf d_mom;                                        // trx_run_moments: [nexp][nseg][TRX_NMOMENT], grown on demand
   std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
   DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
+  bool broad_on = false; Broadening broad;             // trx_set_broadening (broad_on false: none); independent of the sets above
+  DevBuf d_broad;                                      // the broadened spectrum [nwn] of a broadened or pixel run, grown on demand
 };
 
 namespace {
@@ -1952,11 +1959,13 @@ struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swe
 // contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
 // px: a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it,
 // and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that
+// br: the broadening of a broadened run (trx_run_broadened) or of a pixel run on a handle with one installed -- the spectrum
+// stays on the device as for bs, the kernel of trx_broaden.hip.h follows it, and the pixel kernel reads what that one wrote
 struct Run {
   // ---- what the run is given
   trx_handle *const h; const trx_atm *const a; const trx_opts *const o;
   double *const spectrum; void *const d_spectrum; trx_debug *const dbg; const BandSet *const bs; const bool contrib;
-  const PixelRun *const px;
+  const PixelRun *const px; const Broadening *const br;
   const std::chrono::steady_clock::time_point t_host0;
 
   // ---- its shape and modes
@@ -2047,7 +2056,7 @@ struct Run {
   int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
   int side_work(SideWork &S); int queue_cia(); int join_early();
   // ... the spectrum of what they swept, the way back
-  int spectrum_kernel(); int ray_tail(); int band_kernels(); int pixel_kernels(); int filter_kernels(); int moment_kernels(); int results();
+  int spectrum_kernel(); int ray_tail(); int band_kernels(); int broaden_kernel(); int pixel_kernels(); int filter_kernels(); int moment_kernels(); int results();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2392,7 +2401,7 @@ int Run::plan_first_pass()
   tail_mode = h->sw.ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
               nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays && plan_is_tail(h->run_plan, kTailSteps);
   // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs && !px;
+  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs && !px && !br;
   if ((tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
   // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
   // into a pinned array, one entry per block, and the HOST adds it up behind the kernel (results).  The device-side sum was three
@@ -2677,6 +2686,28 @@ int Run::band_kernels()
   return TRX_OK;
 }
 
+// ---- the rotational broadening of this pass's spectrum (trx_broaden.hip.h), behind it on its queue and ahead of the pixel
+// kernel, which then reads d_broad; a pass that resumes deeper queues it again behind its own spectrum.
+int Run::broaden_kernel()
+{
+  if (!br) return TRX_OK;
+  BroadArgs BA{};
+  BA.spec = d_out; BA.out = h->d_broad.as<double>(); BA.nwn = h->nwn;
+  BA.wn_i = h->wn_i; BA.wn_d = h->wn_d; BA.beta = br->beta; BA.W = broaden_weights(br->limb); BA.hmax = br->hmax;
+  const int64_t blocks = (BA.nwn + kBroadBlock - 1) / kBroadBlock;
+  const size_t lds = sizeof(double) * ((size_t)kBroadBlock + 2 * (size_t)(br->hmax > 0 ? br->hmax : 0));
+  // (every address the kernel reads or writes: the spectrum and the broadened one over [0, nwn) = [0, nsh) -- the whole grid,
+  // or trx_set_broadening would have refused --, and a tile of at most kBroadBlock + 2 hmax doubles of LDS)
+  double d_last;
+  if (!BA.spec || !BA.out || h->windowed() || nsh != h->nwn || h->d_broad.bytes < sizeof(double) * (size_t)nsh ||
+      (!d_spectrum && h->d_spec.bytes < sizeof(double) * (size_t)nsh) || !(BA.wn_i > 0) || !(BA.wn_d > 0) || !(BA.beta > 0) ||
+      br->hmax < 0 || br->hmax > TRX_BROADEN_MAX_HALF || broaden_half(BA.wn_i, BA.wn_d, BA.beta, BA.nwn - 1, d_last) != (double)br->hmax ||
+      blocks < 1 || blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the broadening kernel (not launched)");
+  hipLaunchKernelGGL(k_broaden, dim3((unsigned)blocks), dim3(kBroadBlock), lds, tst, BA);
+  return TRX_OK;
+}
+
 // ---- the detector pixels of this pass's spectrum at the run's shifts (trx_pixels.hip.h), behind it on its queue like
 // the band kernels; a pass that resumes deeper queues it again behind its own spectrum.
 int Run::pixel_kernels()
@@ -2684,7 +2715,7 @@ int Run::pixel_kernels()
   if (!px) return TRX_OK;
   const PixelSet &S = *px->set;
   PixArgs PA{};
-  PA.spec = d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
+  PA.spec = br ? h->d_broad.as<double>() : d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
   PA.shift = h->d_pixshift.as<double>(); PA.out = h->d_pixout.as<double>();
   PA.npix = S.npix; PA.npairs = S.npix * (int64_t)px->nshift;
   PA.nwn = h->nwn; PA.lo = h->lo; PA.hi = h->hi; PA.cut = S.cut; PA.fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
@@ -2794,7 +2825,7 @@ int Run::pass()
   int rc;
   for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
   if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = pixel_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : results();
+  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = broaden_kernel()) || (rc = pixel_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : results();
 }
 
 // Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
@@ -2885,14 +2916,14 @@ int Run::finish()
 }  // namespace
 
 static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg,
-                    const BandSet *bs = nullptr, bool contrib = false, const PixelRun *px = nullptr)
+                    const BandSet *bs = nullptr, bool contrib = false, const PixelRun *px = nullptr, const Broadening *br = nullptr)
 {
   const auto t_host0 = std::chrono::steady_clock::now();
   if (!h || !a || !o) return TRX_E_ARG;
   int rc;
   if ((rc = run_check(h, a, o))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  Run R{h, a, o, spectrum, d_spectrum, dbg, bs, contrib, px, t_host0};       // (behind run_check: its members are made from the run's shape)
+  Run R{h, a, o, spectrum, d_spectrum, dbg, bs, contrib, px, br, t_host0};       // (behind run_check: its members are made from the run's shape)
   if ((rc = R.layout()) || (rc = R.front_maxima()) || (rc = R.workspaces()) || (rc = R.front_inputs()) || (rc = R.plan_first_pass()) || (rc = R.pass()))
     return rc;
   if (R.stop_at_hint_ok && R.flags[0] > 0 && R.r_top >= 0 && (rc = R.resume())) return rc;
@@ -3134,9 +3165,11 @@ static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx
   if ((rc = ensure(h, h->d_pixout, sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix)) ||
       (obs && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
       (filt && (rc = ensure(h, h->d_pixval, sizeof(double) * (size_t)nshift * (size_t)PR.set->npix))) ||
+      (h->broad_on && (rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn))) ||
       (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift)))
     return rc;
-  return run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR);
+  // (with a broadening installed the pixels sample the broadened spectrum)
+  return run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR, h->broad_on ? &h->broad : nullptr);
 }
 
 int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
@@ -3296,6 +3329,50 @@ int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
   return TRX_OK;
 }
 
+// ---- rotational broadening between the spectrum and the pixels (trx_broaden.hip.h) ------------------
+// The broadening as h would keep it, checked whole before anything is replaced: on = false for a clearing call.
+static int make_broadening(trx_handle *h, const trx_broadening *br, bool &on, Broadening &out)
+{
+  on = false; out = Broadening{};
+  if (!br || br->kind == TRX_BROADEN_NONE) return TRX_OK;      // (clear)
+  if (br->kind != TRX_BROADEN_ROTATION) return fail(h, TRX_E_ARG, "broadening: unknown kind " + std::to_string(br->kind));
+  if (!std::isfinite(br->beta) || !(br->beta > 0)) return fail(h, TRX_E_ARG, "broadening: beta must be finite and > 0");
+  if (!std::isfinite(br->limb) || !(br->limb >= 0) || !(br->limb <= 1)) return fail(h, TRX_E_ARG, "broadening: limb must be finite and in [0, 1]");
+  if (!(h->wn_i > 0) || !(h->wn_d > 0)) return fail(h, TRX_E_ARG, "broadening: the handle's grid needs wn_i > 0 and wn_d > 0");
+  // (the window needs neighbours across the shard's edge)
+  if (h->windowed())
+    return fail(h, TRX_E_UNSUPPORTED, "broadening: this handle's shard is not the whole grid; gather the spectrum (trx_gather_host) and broaden it on the host");
+  double d;
+  const double half = broaden_half(h->wn_i, h->wn_d, br->beta, h->nwn - 1, d);
+  if (!(half <= (double)TRX_BROADEN_MAX_HALF)) {
+    char b[160]; std::snprintf(b, sizeof b, "broadening: half-width of %.0f bins at the grid's last bin is above TRX_BROADEN_MAX_HALF (%d)", half, TRX_BROADEN_MAX_HALF);
+    return fail(h, TRX_E_ARG, b);
+  }
+  on = true; out.beta = br->beta; out.limb = br->limb; out.hmax = (int)half;
+  return TRX_OK;
+}
+
+int trx_set_broadening(trx_handle *h, const trx_broadening *br)
+{
+  if (!h) return TRX_E_ARG;
+  bool on; Broadening B;
+  if (const int rc = make_broadening(h, br, on, B)) return rc;
+  h->broad_on = on; h->broad = B;
+  return TRX_OK;
+}
+
+int trx_run_broadened(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, double *broadened, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  if (!h->broad_on) return fail(h, TRX_E_ARG, "trx_run_broadened: no broadening installed (trx_set_broadening)");
+  if (!broadened) return fail(h, TRX_E_ARG, "trx_run_broadened: broadened is NULL");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (const int rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn)) return rc;
+  if (const int rc = run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, nullptr, &h->broad)) return rc;
+  HIPCHK(h, hipMemcpy(broadened, h->d_broad.p, sizeof(double) * (size_t)h->nwn, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
 // ---- several atmospheres per call -----------------------------------------------------------------
 // A retrieval driver runs many chains over one line list (the reference: one run_transit per atmosphere,
 // transit.c:118-122, one process each).  One spectrum leaves the device idle between its kernels and while
@@ -3316,6 +3393,10 @@ struct trx_batch {
   int32_t nshift = 0; const double *const *shifts = nullptr; double *const *pix = nullptr;      // trx_run_batch_pixels: the pixel pairs instead
   double *const *mom = nullptr;                      // trx_run_batch_moments: the moments instead (shifts as for pix)
   bool filtered = false;                             // trx_run_batch_filtered_moments: ... through the filter
+  double *const *broadened = nullptr;                // trx_run_batch_broadened: the broadened spectra instead
+  // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none); a worker installs its
+  // atmosphere's entry on its own handle ahead of a pixel, moment, filtered-moment or broadened run
+  std::vector<trx_broadening> broad;
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -3359,15 +3440,22 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
         for (;;) {
           const int32_t j = b->next.fetch_add(1);
           if (j >= b->k) break;
-          const int rc = b->mom && b->filtered ? trx_run_filtered_moments(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], nullptr, b->mom[j], nullptr)
-                       : b->mom ? trx_run_moments(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
-                       : b->pix ? trx_run_pixels(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
-                       : b->contrib ? trx_run_contrib(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
-                       : b->sums ? trx_run_bands(b->hs[(size_t)i], b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
-                                 : trx_run(b->hs[(size_t)i], b->atm + j, b->opts, b->spectra[j], nullptr);
+          trx_handle *const hj = b->hs[(size_t)i];
+          int rc = TRX_OK;
+          // (a pixel or broadened run: this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
+          if (b->pix || b->mom || b->broadened)
+            rc = trx_set_broadening(hj, b->broad.empty() ? nullptr : &b->broad[b->broad.size() == 1 ? 0 : (size_t)j]);
+          if (rc == TRX_OK)
+            rc = b->broadened ? trx_run_broadened(hj, b->atm + j, b->opts, nullptr, b->broadened[j], nullptr)
+               : b->mom && b->filtered ? trx_run_filtered_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], nullptr, b->mom[j], nullptr)
+               : b->mom ? trx_run_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
+               : b->pix ? trx_run_pixels(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
+               : b->contrib ? trx_run_contrib(hj, b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
+               : b->sums ? trx_run_bands(hj, b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
+                         : trx_run(hj, b->atm + j, b->opts, b->spectra[j], nullptr);
           if (rc != TRX_OK) {
             std::lock_guard<std::mutex> lk(b->mu);
-            if (b->rc == TRX_OK) { b->rc = rc; b->err = "atmosphere " + std::to_string(j) + ": " + b->hs[(size_t)i]->err; }
+            if (b->rc == TRX_OK) { b->rc = rc; b->err = "atmosphere " + std::to_string(j) + ": " + hj->err; }
             b->next.store(b->k);                           // (the others finish the spectrum they are on and stop)
           }
         }
@@ -3384,12 +3472,12 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
 static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
                       double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr,
-                      double *const *mom = nullptr, bool filtered = false)
+                      double *const *mom = nullptr, bool filtered = false, double *const *broadened = nullptr)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
   b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
-  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered;
+  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered; b->broadened = broadened;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3442,6 +3530,45 @@ int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   return batch_call(b, k, atm, opts, nullptr, sums, contrib);
 }
 
+// the batch's broadenings, one for all atmospheres or one each: all entries are checked before any is kept, or none is
+int trx_batch_set_broadening(trx_batch *b, int32_t n, const trx_broadening *br)
+{
+  g_comm_err.clear();
+  if (!b || b->hs.empty()) return TRX_E_ARG;
+  if (n < 0 || (n > 0 && !br)) { g_comm_err = "trx_batch_set_broadening: n < 0 or a NULL array"; return TRX_E_ARG; }
+  std::vector<trx_broadening> keep;
+  try { keep.assign(br, br + n); } catch (...) { g_comm_err = "trx_batch_set_broadening: out of host memory"; return TRX_E_NOMEM; }
+  // (the handles are made from one description: what the first accepts, all accept)
+  for (int32_t j = 0; j < n; j++) {
+    bool on; Broadening B;
+    const int rc = make_broadening(b->hs[0], &keep[(size_t)j], on, B);
+    if (rc) { g_comm_err = "entry " + std::to_string(j) + ": " + b->hs[0]->err; return rc; }
+    if (!on) { g_comm_err = "trx_batch_set_broadening: entry " + std::to_string(j) + " is of kind TRX_BROADEN_NONE (n = 0 clears)"; return TRX_E_ARG; }
+  }
+  b->broad = std::move(keep);
+  if (n == 0) for (trx_handle *h : b->hs) { h->broad_on = false; h->broad = Broadening{}; }
+  return TRX_OK;
+}
+
+// a pixel or broadened run of k atmospheres takes one broadening for all, one each, or none
+static int batch_broadening_fits(trx_batch *b, int32_t k, const char *who)
+{
+  const size_t n = b->broad.size();
+  if (n <= 1 || n == (size_t)k || k == 0) return TRX_OK;
+  g_comm_err = std::string(who) + ": " + std::to_string(n) + " broadenings installed (trx_batch_set_broadening) for " + std::to_string(k) + " atmospheres";
+  return TRX_E_ARG;
+}
+
+int trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *broadened)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !broadened))) { g_comm_err = "trx_run_batch_broadened: bad argument"; return TRX_E_ARG; }
+  if (b->broad.empty()) { g_comm_err = "trx_run_batch_broadened: no broadening installed (trx_batch_set_broadening)"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) if (!broadened[j]) { g_comm_err = "trx_run_batch_broadened: broadened[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_broadened")) return rc;
+  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, false, broadened);
+}
+
 // every handle of the batch gets the same pixel set, or none does
 int trx_batch_set_pixels(trx_batch *b, const trx_pixels *px)
 {
@@ -3467,6 +3594,7 @@ int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_
     if (!shift[j]) { g_comm_err = "trx_run_batch_pixels: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
     if (!out[j]) { g_comm_err = "trx_run_batch_pixels: out[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   }
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_pixels")) return rc;
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, out);
 }
 
@@ -3494,6 +3622,7 @@ int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx
     if (!shift[j]) { g_comm_err = "trx_run_batch_moments: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
     if (!mom[j]) { g_comm_err = "trx_run_batch_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   }
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_moments")) return rc;
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom);
 }
 
@@ -3522,6 +3651,7 @@ int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, 
     if (!shift[j]) { g_comm_err = "trx_run_batch_filtered_moments: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
     if (!mom[j]) { g_comm_err = "trx_run_batch_filtered_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
   }
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_moments")) return rc;
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom, true);
 }
 

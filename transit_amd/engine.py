@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _abi
 from . import bands as _bands
+from . import broaden as _broaden
 from . import pixels as _pixels
 from .build import lib_path
 
@@ -205,6 +206,7 @@ def hip_library():
         _abi.bind_pixels_api(lib)
         _abi.bind_moments_api(lib)
         _abi.bind_filter_api(lib)
+        _abi.bind_broaden_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -340,6 +342,25 @@ class Engine(CEngine):
             raise EngineError(rc, "trx_run_filtered_moments", self._last_error())
         out = (mom,) + ((spec,) if spectrum else ()) + ((val,) if values else ())
         return out if len(out) > 1 else mom
+
+    def set_broadening(self, b):
+        """trx_set_broadening: install a rotational broadening (a transit_amd.broaden.Rotation; None: clear it).  The
+        pixel, moment and filtered-moment runs then sample the broadened spectrum; set_pixels does not drop it."""
+        rc = self._lib.trx_set_broadening(self._h, C.byref(_broaden.to_c(b)) if b is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_broadening", self._last_error())
+
+    def run_broadened(self, atm, opts, spectrum: bool = False):
+        """trx_run_broadened: the broadened spectrum [nwn] -- and, with spectrum=True, (broadened, spectrum), the
+        spectrum bit for bit what run() gives (never the broadened one)."""
+        out = np.zeros(self.nwn)
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_broadened(self._h, C.byref(atm), C.byref(opts),
+                                         spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                         out.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_broadened", self._last_error())
+        return (out, spec) if spectrum else out
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -491,6 +512,28 @@ class Batch:
         rc = self._lib.trx_run_batch_filtered_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_filtered_moments", self._err())
+        return out
+
+    def set_broadening(self, b):
+        """trx_batch_set_broadening: one transit_amd.broaden.Rotation for every atmosphere of the following pixel,
+        moment, filtered-moment and broadened runs, or a list with one per atmosphere (None or an empty list: clear);
+        all entries are accepted, or none is kept."""
+        bs = [] if b is None else list(b) if isinstance(b, (list, tuple)) else [b]
+        arr = (_abi.TrxBroadening * max(len(bs), 1))(*[_broaden.to_c(x) for x in bs])
+        rc = self._lib.trx_batch_set_broadening(self._b, len(bs), arr)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_broadening", self._err())
+
+    def run_broadened(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
+        """trx_run_batch_broadened: [K, nwn], each atmosphere's broadened spectrum what Engine.run_broadened gives with
+        that atmosphere's broadening, bit for bit."""
+        k = len(atms)
+        out = np.zeros((k, self.nwn))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_broadened(self._b, k, arr, C.byref(opts), po)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_broadened", self._err())
         return out
 
     def close(self):
