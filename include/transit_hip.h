@@ -582,6 +582,46 @@ int  trx_batch_set_broadening(trx_batch *b, int32_t n, const trx_broadening *br 
 int  trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
                              double *const *broadened /* [k] -> [nwn] */);
 
+/* The cross-correlation trail on the device: one model against EVERY exposure of the observed set at EVERY lag of a
+ * velocity grid -- CCF[lag][exposure], and the Kp-Vsys map a driver makes from it -- from one spectrum and one pass over
+ * the data.  (trx_run_moments answers the other question: one shift per exposure, the likelihood at one (Kp, Vsys).)
+ *
+ * lag[l] is a Doppler factor nu_observed / nu_rest, as shift[] is.  trail[l][v][s][:] are the seven moments of
+ * trx_run_moments for exposure v and segment s of the installed observed set -- its data, weights and gain -- with the
+ * model pair of pixel p the pair trx_run_pixels gives for the shift lag[l].  The contributing rule (b > 0 and w > 0), the
+ * terms (w g, (w g) g, w f, (w f) g, (w f) f, each rounded once, no fused multiply-add) and the order of the sums (lane k
+ * adds the segment's pixels first + k, first + k + 64, ..., then the same butterfly over the 64 lanes) are those of
+ * trx_run_moments, so
+ *   trail[l] is bit for bit what trx_run_moments returns on the same handle when all nexp shifts equal lag[l].
+ * It follows that
+ *   - there are no atomics;
+ *   - the bits of a row depend on the spectrum, that lag, and that exposure's data, weights and gains over that segment:
+ *     not on the other lags of the call (a repeated lag gives a repeated row), the tile of lags and exposures a row was
+ *     computed in, the launch, the batch way that ran it or the handle's depth hint;
+ *   - a row with no contributing pixel is seven exact +0;
+ *   - the sums cannot go through the matrix cores, whose order of addition is another.
+ *
+ * With a broadening installed the pairs sample the broadened spectrum, as in every other pixel run.  An installed FILTER
+ * IS IGNORED: the filter couples the exposures of a pixel column, and a trail's model is the same at all of them (the
+ * column is a constant) -- the trail's bits are the same with and without a filter on the handle.  A driver that detrends
+ * applies the filter to the data it installs.
+ *
+ * trx_run_trail is trx_run_pixels with nshift = nlag plus the reduction: spectrum may be NULL, and when it is given it
+ * holds the bits trx_run gives; only trail is copied back, the [nlag][npix] pairs stay in device memory.  TRX_E_ARG, the
+ * reason in trx_last_error, with no observed set installed, nlag < 1, lag or trail NULL, a non-finite or <= 0 lag
+ * (naming "lag N"), nlag * npix above what one pixel launch takes (2^31 - 1 blocks of 256 pairs), nlag * nexp * nseg
+ * above 2^31 - 1; TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid, for trx_run_moments' reason.  A run
+ * that fails leaves trail undefined.  Every other run on the handle is unchanged, bit for bit.
+ * trx_run_batch_trail is trx_run_batch with atmosphere j's own lags lag[j] ([nlag]) and its trail trail[j]; the batch's
+ * broadenings apply as in trx_run_batch_moments. */
+int  trx_run_trail(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                   double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                   int32_t nlag, const double *lag /* [nlag], nu_observed / nu_rest, as shift[] */,
+                   double *trail /* [nlag][nexp][nseg][TRX_NMOMENT], host */, trx_debug *dbg /* may be NULL */);
+int  trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                         int32_t nlag, const double *const *lag /* [k] -> [nlag] */,
+                         double *const *trail /* [k] -> [nlag][nexp][nseg][TRX_NMOMENT] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

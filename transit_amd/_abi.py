@@ -211,6 +211,17 @@ def bind_moments_api(lib):
     return lib
 
 
+def bind_trail_api(lib):
+    """argtypes/restypes of the trail entry points (trx_run_trail and its batch form)."""
+    lib.trx_run_trail.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                  c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_trail.restype = C.c_int
+    lib.trx_run_batch_trail.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
+                                        C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_trail.restype = C.c_int
+    return lib
+
+
 def bind_filter_api(lib):
     """argtypes/restypes of the filter entry points (trx_set_filter, trx_run_filtered_moments and their batch forms)."""
     lib.trx_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]

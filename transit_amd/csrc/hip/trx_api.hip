@@ -38,6 +38,7 @@
 #include "trx_bands.hip.h"
 #include "trx_pixels.hip.h"
 #include "trx_moments.hip.h"
+#include "trx_trail.hip.h"
 #include "trx_filter.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
@@ -95,8 +96,9 @@ struct FilterSet {
   DevBuf d_fwd, d_back, d_tiles;                     // [nseg][nexp][npad] each, FilterTile[ntiles]
 };
 // a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
-// filt: with the filter between the pairs and the moments (trx_run_filtered_moments)
-struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; };
+// filt: with the filter between the pairs and the moments (trx_run_filtered_moments); trail: the shifts are the lags of a
+// trail (trx_run_trail) -- every exposure of obs against every one of them (trx_trail.hip.h), never with a filter
+struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; };
 // a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
 // the largest -- which sizes the kernel's tile
 struct Broadening { double beta = 0, limb = 0; int hmax = 0; };
@@ -222,6 +224,7 @@ struct trx_handle {
   DevBuf d_pixshift, d_pixout;                         // trx_run_pixels: the run's shifts [nshift] and its pairs [nshift][npix][2], grown on demand
   std::unique_ptr<ObservedSet> observed;               // trx_set_observed (null: none); belongs to `pixels`
   DevBuf d_mom;                                        // trx_run_moments: [nexp][nseg][TRX_NMOMENT], grown on demand
+  DevBuf d_trail;                                      // trx_run_trail: [nlag][nexp][nseg][TRX_NMOMENT], grown on demand
   std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
   DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
   bool broad_on = false; Broadening broad;             // trx_set_broadening (broad_on false: none); independent of the sets above
@@ -1958,7 +1961,8 @@ struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swe
 // spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
 // contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
 // px: a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it,
-// and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that
+// and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that -- or (px->trail: trx_run_trail) the one of
+// trx_trail.hip.h
 // br: the broadening of a broadened run (trx_run_broadened) or of a pixel run on a handle with one installed -- the spectrum
 // stays on the device as for bs, the kernel of trx_broaden.hip.h follows it, and the pixel kernel reads what that one wrote
 struct Run {
@@ -2759,12 +2763,40 @@ int Run::filter_kernels()
   return TRX_OK;
 }
 
+// ---- the trail of those pairs -- one shift per LAG -- against every exposure of the observed set (trx_trail.hip.h)
+static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
+{
+  const ObservedSet &O = *px.obs;
+  constexpr int TL = kTrailLags, TV = kTrailExps;
+  TrailArgs TA{};
+  TA.pairs = h->d_pixout.as<double2>(); TA.data = O.d_data.as<double>(); TA.weight = O.d_weight.as<double>(); TA.gain = O.d_gain.as<double>();
+  TA.seg_first = O.d_seg.as<int64_t>(); TA.trail = h->d_trail.as<double>();
+  TA.npix = O.npix; TA.nlag = px.nshift; TA.nexp = O.nexp; TA.nseg = O.nseg;
+  TA.ntl = (px.nshift + TL - 1) / TL; TA.ntv = (O.nexp + TV - 1) / TV;
+  TA.nwaves = (int64_t)O.nseg * TA.ntl * TA.ntv; TA.xcd_map = 1;
+  const int64_t blocks = (TA.nwaves + kTrailWaves - 1) / kTrailWaves;
+  const int64_t rows = (int64_t)px.nshift * O.nexp * O.nseg;
+  const size_t cells = sizeof(double) * (size_t)O.nexp * (size_t)O.npix;
+  // (every address the kernel reads or writes: the pairs over [nlag][npix], data and weights over [nexp][npix] -- the segments
+  // lie in [0, npix), checked when the set was made, and a ragged tile's surplus indices are nlag - 1 and nexp - 1 --, the
+  // gains, the segment bounds, the rows of [nlag][nexp][nseg])
+  if (!TA.pairs || !TA.data || !TA.seg_first || !TA.trail || px.filt || px.nshift < 1 || O.nexp < 1 || O.nseg < 1 || O.npix < 1 || O.npix != px.set->npix ||
+      O.seg.size() != (size_t)O.nseg + 1 || O.seg.front() != 0 || O.seg.back() != O.npix || rows < 1 || rows > 0x7fffffffLL ||
+      h->d_pixout.bytes < sizeof(double) * 2 * (size_t)px.nshift * (size_t)O.npix || O.d_data.bytes < cells || (TA.weight && O.d_weight.bytes < cells) ||
+      (TA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
+      h->d_trail.bytes < sizeof(double) * TRX_NMOMENT * (size_t)rows || blocks < 1 || blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the trail kernel (not launched)");
+  hipLaunchKernelGGL((k_trail_moments<TL, TV>), dim3((unsigned)blocks), dim3(64 * kTrailWaves), 0, st, TA);
+  return TRX_OK;
+}
+
 // ---- the moments of those pairs (of the filter's values: a filtered run) against the observed set (trx_moments.hip.h),
-// behind the pixel kernel on its queue; a pass that resumes deeper queues both again.
+// behind the pixel kernel on its queue; a pass that resumes deeper queues both again.  (A trail run: its kernel instead.)
 int Run::moment_kernels()
 {
   if (!px || !px->obs) return TRX_OK;
   const ObservedSet &O = *px->obs;
+  if (px->trail) return launch_trail(h, *px, tst);
   MomArgs MA{};
   MA.val = px->filt ? h->d_pixval.as<double>() : nullptr;
   MA.pairs = h->d_pixout.as<double2>(); MA.data = O.d_data.as<double>(); MA.weight = O.d_weight.as<double>(); MA.gain = O.d_gain.as<double>();
@@ -3149,21 +3181,23 @@ int trx_set_pixels(trx_handle *h, const trx_pixels *px)
   return TRX_OK;
 }
 
-// a pixel run for `who` (trx_run_pixels; obs: trx_run_moments; filt: trx_run_filtered_moments): the pairs are in h->d_pixout, the
-// moments in h->d_mom, the filtered values in h->d_pixval, when it returns
+// a pixel run for `who` (trx_run_pixels; obs: trx_run_moments; filt: trx_run_filtered_moments; trail: trx_run_trail, the shifts
+// its lags): the pairs are in h->d_pixout, the moments in h->d_mom, the filtered values in h->d_pixval, the trail in
+// h->d_trail, when it returns
 static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                     const ObservedSet *obs, trx_debug *dbg, const FilterSet *filt = nullptr)
+                     const ObservedSet *obs, trx_debug *dbg, const FilterSet *filt = nullptr, bool trail = false)
 {
   const std::string w(who);
   for (int32_t v = 0; v < nshift; v++)
     if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, w + ": shift " + std::to_string(v) + " must be finite and > 0");
-  const PixelRun PR{h->pixels.get(), nshift, obs, filt};
+  const PixelRun PR{h->pixels.get(), nshift, obs, filt, trail};
   if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, w + ": nshift * npix above what one launch takes");
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
   if ((rc = ensure(h, h->d_pixout, sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix)) ||
-      (obs && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
+      (obs && !trail && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
+      (obs && trail && (rc = ensure(h, h->d_trail, sizeof(double) * TRX_NMOMENT * (size_t)nshift * (size_t)obs->nexp * (size_t)obs->nseg))) ||
       (filt && (rc = ensure(h, h->d_pixval, sizeof(double) * (size_t)nshift * (size_t)PR.set->npix))) ||
       (h->broad_on && (rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn))) ||
       (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift)))
@@ -3248,6 +3282,31 @@ int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   if (!mom) return fail(h, TRX_E_ARG, "trx_run_moments: mom is NULL");
   if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, nshift, shift, ob, dbg)) return rc;
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
+// ---- the cross-correlation trail: every exposure against every lag of a grid (trx_trail.hip.h) -----
+int trx_run_trail(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nlag, const double *lag,
+                  double *trail, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  // (as for trx_run_moments: the partial pairs of a shard say nothing about the moments)
+  if (h->windowed())
+    return fail(h, TRX_E_UNSUPPORTED, "trx_run_trail: this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
+                                      "(trx_gather_host) and reduce them on the host");
+  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "trx_run_trail: no observed set installed (trx_set_observed)");
+  const ObservedSet *ob = h->observed.get();
+  if (nlag < 1) return fail(h, TRX_E_ARG, "trx_run_trail: nlag < 1");
+  if (!lag) return fail(h, TRX_E_ARG, "trx_run_trail: lag is NULL");
+  if (!trail) return fail(h, TRX_E_ARG, "trx_run_trail: trail is NULL");
+  // (the counts first: a refused nlag is not an extent to read lag[] over)
+  if ((int64_t)nlag * ob->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, "trx_run_trail: nlag * npix above what one pixel launch takes");
+  if ((int64_t)nlag * ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, "trx_run_trail: nlag * nexp * nseg above 2^31 - 1");
+  for (int32_t l = 0; l < nlag; l++)
+    if (!std::isfinite(lag[l]) || !(lag[l] > 0)) return fail(h, TRX_E_ARG, "trx_run_trail: lag " + std::to_string(l) + " must be finite and > 0");
+  // (an installed filter takes no part: it couples the exposures, and a trail's model is the same at all of them)
+  if (const int rc = pixel_run(h, "trx_run_trail", a, o, spectrum, nlag, lag, ob, dbg, nullptr, true)) return rc;
+  HIPCHK(h, hipMemcpy(trail, h->d_trail.p, sizeof(double) * TRX_NMOMENT * (size_t)nlag * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
@@ -3393,6 +3452,7 @@ struct trx_batch {
   int32_t nshift = 0; const double *const *shifts = nullptr; double *const *pix = nullptr;      // trx_run_batch_pixels: the pixel pairs instead
   double *const *mom = nullptr;                      // trx_run_batch_moments: the moments instead (shifts as for pix)
   bool filtered = false;                             // trx_run_batch_filtered_moments: ... through the filter
+  double *const *trail = nullptr;                    // trx_run_batch_trail: the trails instead (shifts: the lags, nshift of them)
   double *const *broadened = nullptr;                // trx_run_batch_broadened: the broadened spectra instead
   // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none); a worker installs its
   // atmosphere's entry on its own handle ahead of a pixel, moment, filtered-moment or broadened run
@@ -3443,10 +3503,11 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
           trx_handle *const hj = b->hs[(size_t)i];
           int rc = TRX_OK;
           // (a pixel or broadened run: this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
-          if (b->pix || b->mom || b->broadened)
+          if (b->pix || b->mom || b->trail || b->broadened)
             rc = trx_set_broadening(hj, b->broad.empty() ? nullptr : &b->broad[b->broad.size() == 1 ? 0 : (size_t)j]);
           if (rc == TRX_OK)
             rc = b->broadened ? trx_run_broadened(hj, b->atm + j, b->opts, nullptr, b->broadened[j], nullptr)
+               : b->trail ? trx_run_trail(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->trail[j], nullptr)
                : b->mom && b->filtered ? trx_run_filtered_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], nullptr, b->mom[j], nullptr)
                : b->mom ? trx_run_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
                : b->pix ? trx_run_pixels(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
@@ -3472,12 +3533,12 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
 static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
                       double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr,
-                      double *const *mom = nullptr, bool filtered = false, double *const *broadened = nullptr)
+                      double *const *mom = nullptr, bool filtered = false, double *const *broadened = nullptr, double *const *trail = nullptr)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
   b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
-  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered; b->broadened = broadened;
+  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered; b->broadened = broadened; b->trail = trail;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3624,6 +3685,21 @@ int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   }
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_moments")) return rc;
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom);
+}
+
+int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nlag, const double *const *lag,
+                        double *const *trail)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !lag || !trail))) { g_comm_err = "trx_run_batch_trail: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_trail: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  if (nlag < 1) { g_comm_err = "trx_run_batch_trail: nlag < 1"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) {
+    if (!lag[j]) { g_comm_err = "trx_run_batch_trail: lag[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+    if (!trail[j]) { g_comm_err = "trx_run_batch_trail: trail[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  }
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_trail")) return rc;
+  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nlag, lag, nullptr, nullptr, false, nullptr, trail);
 }
 
 // every handle of the batch gets the same filter, or none does

@@ -205,6 +205,7 @@ def hip_library():
         _abi.bind_contrib_api(lib)
         _abi.bind_pixels_api(lib)
         _abi.bind_moments_api(lib)
+        _abi.bind_trail_api(lib)
         _abi.bind_filter_api(lib)
         _abi.bind_broaden_api(lib)
         lib.trx_device_count.restype = C.c_int
@@ -316,6 +317,22 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_moments", self._last_error())
         return (mom, spec) if spectrum else mom
+
+    def run_trail(self, atm, opts, lags, spectrum: bool = False):
+        """trx_run_trail: the trail [nlag, nexp, nseg, 7] -- the moments of every exposure of the observed set against
+        the model at every lag (nu_observed / nu_rest, as shifts are; transit_amd.xcor.lag_grid), row l bit for bit
+        run_moments(atm, opts, [lags[l]] * nexp) -- and, with spectrum=True, (trail, spectrum), the spectrum bit for bit
+        what run() gives.  An installed filter takes no part; the pixel pairs stay on the device."""
+        lg = np.ascontiguousarray(lags, dtype=np.float64).reshape(-1)
+        trail = np.zeros((lg.size,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_trail(self._h, C.byref(atm), C.byref(opts),
+                                     spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                     int(lg.size), lg.ctypes.data_as(_abi.c_double_p),
+                                     trail.ctypes.data_as(_abi.c_double_p), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_trail", self._last_error())
+        return (trail, spec) if spectrum else trail
 
     def set_filter(self, filt):
         """trx_set_filter: install a detrending filter (a transit_amd.xcor.Filter; None: clear it) over the observed
@@ -490,6 +507,22 @@ class Batch:
         rc = self._lib.trx_run_batch_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_moments", self._err())
+        return out
+
+    def run_trail(self, atms, opts: _abi.TrxOpts, lags) -> np.ndarray:
+        """trx_run_batch_trail: [K, nlag, nexp, nseg, 7] for lags of shape [K][nlag] (atmosphere j at its own lags), each
+        atmosphere's trail what Engine.run_trail gives, bit for bit."""
+        k = len(atms)
+        lg = np.ascontiguousarray(lags, dtype=np.float64)
+        if lg.ndim != 2 or lg.shape[0] != k:
+            raise ValueError("Batch.run_trail: lags of shape [K][nlag], one row per atmosphere")
+        out = np.zeros((k, lg.shape[1]) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        ps = (_abi.c_double_p * max(k, 1))(*[lg[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        rc = self._lib.trx_run_batch_trail(self._b, k, arr, C.byref(opts), int(lg.shape[1]), ps, po)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_trail", self._err())
         return out
 
     def set_filter(self, filt):

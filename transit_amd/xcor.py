@@ -16,6 +16,14 @@ contributes when b > 0 and w > 0; its model value is g = gain_p * (a / b).  Over
     loglike_bl19(mom, scale=1)                           the Brogi & Line (2019) log-likelihood per (v, s)
     chi2_sum, ccf_sum, loglike_bl19_sum                  the same added over all (v, s)
 
+The trail (Engine.run_trail / Batch.run_trail; trx_run_trail): the same seven sums for every exposure against the model at
+every lag of a velocity grid, trail[l, v, s] -- row l is the moments with lag l's pairs at all exposures.
+
+    trail_reference(pairs, obs)                          the definition over the pairs [nlag, npix, 2] of run_pixels(lags)
+    trail_abs_reference(pairs, obs)                      the same with |f| and |g|
+    lag_grid(v_lo, v_hi, step)                           (lag_kms, lags): velocities v_lo, v_lo + step, ... and pixels.shift of each
+    velocity_map(trail, lag_kms, v_planet, stat=ccf)     the statistic along each map cell's velocity track, added over exposures
+
 The detrending filter (Engine.set_filter / Engine.run_filtered_moments; trx_set_filter / trx_run_filtered_moments): per
 segment s a coefficient matrix fwd[s] ([ncomp, nexp]) and a basis back[s] ([nexp, ncomp]) act along the exposure axis
 of every pixel column.  A column is live when b > 0 at every exposure, otherwise dead and all NaN; for a live column
@@ -39,7 +47,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _abi
+from . import _abi, pixels as _pixels
 
 NMOMENT = _abi.NMOMENT
 N, W, WG, WGG, WF, WFG, WFF = range(NMOMENT)
@@ -204,6 +212,67 @@ def loglike_bl19_sum(mom, scale: float = 1.0) -> float:
     """loglike_bl19 added over the (v, s) rows that have one: rows for which it is nan (fewer than two contributing
     pixels, a zero variance) are SKIPPED."""
     return float(np.nansum(loglike_bl19(mom, scale)))
+
+
+def _trail(pairs, obs: Observed, absolute: bool) -> np.ndarray:
+    pairs = np.asarray(pairs, dtype=np.float64)
+    if pairs.ndim != 3 or pairs.shape[1:] != (obs.npix, 2):
+        raise ValueError("pairs of shape [nlag][npix][2]")
+    out = np.zeros((pairs.shape[0], obs.nexp, obs.nseg, NMOMENT))
+    for l in range(pairs.shape[0]):
+        out[l] = _moments(np.broadcast_to(pairs[l], (obs.nexp, obs.npix, 2)), obs, absolute)
+    return out
+
+
+def trail_reference(pairs, obs: Observed) -> np.ndarray:
+    """The definition of the trail: [nlag, nexp, nseg, 7] from the pixel pairs [nlag, npix, 2] of a run at the lags
+    and the observed set -- lag l is reference() with that lag's pairs at every exposure."""
+    return _trail(pairs, obs, False)
+
+
+def trail_abs_reference(pairs, obs: Observed) -> np.ndarray:
+    """trail_reference with |f| and |g| (abs_reference per lag)."""
+    return _trail(pairs, obs, True)
+
+
+def lag_grid(v_lo: float, v_hi: float, step: float):
+    """(lag_kms, lags): the velocities v_lo, v_lo + step, ... up to v_hi (km/s; v_hi included when a whole number of
+    steps away, to rounding) and the Doppler factor pixels.shift of each -- what run_trail takes."""
+    if not (step > 0) or not (v_hi >= v_lo):
+        raise ValueError("lag_grid: step > 0 and v_hi >= v_lo")
+    n = int(math.floor((v_hi - v_lo) / step * (1.0 + 1e-12) + 1e-9)) + 1
+    kms = v_lo + step * np.arange(n, dtype=np.float64)
+    return kms, np.array([_pixels.shift(v) for v in kms])
+
+
+def velocity_map(trail, lag_kms, v_planet, stat=ccf) -> np.ndarray:
+    """The detection map of a trail [nlag, nexp, nseg, 7] over lags at the velocities lag_kms ([nlag], increasing):
+    v_planet ([..., nexp]) is the planet's velocity at every exposure for every map cell, e.g.
+    vsys[None, :, None] + kp[:, None, None] * sin(2 pi phase).  stat (ccf, loglike_bl19, chi2, ...) is applied to the
+    trail and added over the segments -- rows it leaves undefined (nan) are SKIPPED, as the *_sum helpers skip them
+    -- which gives [nlag, nexp]; that is interpolated linearly in lag velocity at each exposure's velocity and added
+    over the exposures.  A cell with any velocity outside [lag_kms[0], lag_kms[-1]] is nan."""
+    trail = np.asarray(trail, dtype=np.float64)
+    kms = np.asarray(lag_kms, dtype=np.float64).reshape(-1)
+    vp = np.asarray(v_planet, dtype=np.float64)
+    if trail.ndim != 4 or trail.shape[0] != kms.size or trail.shape[3] != NMOMENT:
+        raise ValueError("velocity_map: trail of shape [nlag][nexp][nseg][7], one lag velocity per lag")
+    if kms.size > 1 and not np.all(np.diff(kms) > 0):
+        raise ValueError("velocity_map: lag_kms must increase")
+    if vp.ndim < 1 or vp.shape[-1] != trail.shape[1]:
+        raise ValueError("velocity_map: v_planet of shape [..., nexp]")
+    per = np.nansum(np.asarray(stat(trail), dtype=np.float64), axis=2)      # [nlag, nexp]
+    inside = (vp >= kms[0]) & (vp <= kms[-1])
+    out = np.zeros(vp.shape[:-1])
+    for v in range(trail.shape[1]):
+        x = np.where(inside[..., v], vp[..., v], kms[0])
+        if kms.size == 1:
+            out += per[0, v]
+            continue
+        k = np.clip(np.searchsorted(kms, x, side="right") - 1, 0, kms.size - 2)
+        t = (x - kms[k]) / (kms[k + 1] - kms[k])
+        out += per[k, v] + t * (per[k + 1, v] - per[k, v])
+    return np.where(np.all(inside, axis=-1), out, np.nan)
 
 
 @dataclass
