@@ -622,6 +622,75 @@ int  trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, 
                          int32_t nlag, const double *const *lag /* [k] -> [nlag] */,
                          double *const *trail /* [k] -> [nlag][nexp][nseg][TRX_NMOMENT] */);
 
+/* The Kp-Vsys detection map on the device, reduced from the trail: trx_run_trail followed, on the device, by the two
+ * products an observer looks at -- the CCF trail per[lag][exposure], a statistic of every trail row added over the
+ * segments (orders), and the map[Kp][Vsys], per interpolated along each cell's velocity track and added over the
+ * exposures.  Only the map ([nkp][nvsys] doubles) and, when asked for, per ([nlag][nexp]) are copied back; the
+ * [nlag][nexp][nseg][TRX_NMOMENT] trail stays in device memory.
+ *
+ * A trx_vmap is {stat, nlag, p0, p1, lag, lag_kms, nkp, nvsys, kp, vsys, orbit, offset}: lag[l] the lags as trx_run_trail
+ * takes them, lag_kms[l] their velocities (km/s, strictly increasing), kp[i] and vsys[j] the map's axes (km/s),
+ * orbit[v] what multiplies Kp at exposure v (sin(2 pi phase_v) for a circular orbit), offset[v] a velocity added at
+ * exposure v (the barycentric correction) or NULL.  nexp and nseg are the installed observed set's.  Every operation
+ * below is IEEE double, rounded once, no fused multiply-add; +, -, *, / and sqrt are correctly rounded on the device, so
+ * only log can differ from a host evaluation of the same lines.
+ *
+ * 1. The statistic of a row, stat(m) of its moments m0 .. m6 (n, sum w, sum w g, sum w g^2, sum w f, sum w f g, sum w f^2):
+ *      <f> = m4 / m1     <g> = m2 / m1
+ *      sf2 = m6 / m1 - <f> * <f>      sg2 = m3 / m1 - <g> * <g>      R = m5 / m1 - <f> * <g>
+ *      TRX_STAT_CCF           R / sqrt(sf2 * sg2)
+ *      TRX_STAT_LOGLIKE_BL19  (-0.5 * n) * log(arg),  arg = sf2 - (2 * p0) * R + (p0 * p0) * sg2        (p0: the scale)
+ *      TRX_STAT_CHI2          m6 - (2 p0) m5 - (2 p1) m4 + (p0 p0) m3 + ((2 p0) p1) m2 + (p1 p1) m1, added left to right
+ *                             (sum w (f - p0 g - p1)^2)
+ *    The first two are undefined (NaN) for n < 2, for sf2 <= 0 or sg2 <= 0 (or not a number), BL19 also for arg <= 0.
+ * 2. per[l][v] = the sum of stat(trail[l][v][s]) over s = 0 .. nseg-1 IN THAT ORDER, one addition each, from +0;
+ *    undefined rows are skipped (all skipped: +0).
+ * 3. Cell (i, j): for v = 0 .. nexp-1 in that order, x_v = (kp[i] * orbit[v] + vsys[j]) + offset[v] (the last addition
+ *    only with an offset),
+ *      k = clip(upper_bound(lag_kms, x_v) - 1, 0, nlag - 2)       (upper_bound: the number of lag_kms <= x_v)
+ *      t = (x_v - lag_kms[k]) / (lag_kms[k+1] - lag_kms[k])       (x_v == lag_kms[nlag-1]: k = nlag - 2, t = 1)
+ *      map[i][j] += per[k][v] + t * (per[k+1][v] - per[k][v])     (nlag == 1: += per[0][v])
+ *    from +0.  A cell with any x_v outside [lag_kms[0], lag_kms[nlag-1]], or not finite, is NaN.
+ * It follows that
+ *   - there are no atomics: per[l][v] depends on the trail rows (l, v, .) only, a cell on its kp, its vsys, orbit,
+ *     offset, lag_kms and per -- not on the other cells of the call, the launch, the batch way or the depth hint;
+ *   - map is, bit for bit, steps 3 applied on the host to the per the same call returned;
+ *   - per is steps 1-2 applied on the host to the trail trx_run_trail returns, bit for bit for CCF and CHI2 and to the
+ *     accuracy of log for LOGLIKE_BL19 (the device's within 3 ulp).
+ *
+ * Everything else is trx_run_trail's: a broadening applies, a filter is ignored, spectrum may be NULL and when given
+ * holds the bits trx_run gives, the device's trail buffer holds afterwards what trx_run_trail would have left there,
+ * and every other run on the handle is unchanged, bit for bit.  per may be NULL.
+ * TRX_E_ARG, the reason in trx_last_error, with nothing touched and the handle usable: every refusal of trx_run_trail
+ * (no observed set, nlag < 1, lag NULL, a lag that is not finite and > 0, the two products above their limits); vm or
+ * map NULL; an unknown stat; nkp < 1 or nvsys < 1; nkp * nvsys above 2^31 - 1; lag_kms, kp, vsys or orbit NULL; a
+ * non-finite p0 or p1; a non-finite kp, vsys, orbit or offset (naming e.g. "orbit N"); a lag_kms that is not finite and
+ * strictly increasing ("lag_kms N").  TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.
+ * trx_run_batch_velocity_map is trx_run_batch with ONE vm for all atmospheres, atmosphere j's map in map[j] and, with
+ * per not NULL, its statistic in per[j]; it also refuses a NULL map[j] or per[j].  The batch's broadenings apply as in
+ * trx_run_batch_trail. */
+#define TRX_STAT_CCF 1          /* the weighted Pearson coefficient                  */
+#define TRX_STAT_LOGLIKE_BL19 2 /* Brogi & Line (2019) log-likelihood, p0 = scale    */
+#define TRX_STAT_CHI2 3         /* chi-square of f against p0 g + p1                 */
+typedef struct {
+  int32_t stat, nlag;
+  double  p0, p1;
+  const double *lag;      /* [nlag] nu_observed / nu_rest, as trx_run_trail takes them       */
+  const double *lag_kms;  /* [nlag] the lags' velocities, strictly increasing                */
+  int32_t nkp, nvsys;
+  const double *kp;       /* [nkp]   km/s                                                     */
+  const double *vsys;     /* [nvsys] km/s                                                     */
+  const double *orbit;    /* [nexp]  what multiplies Kp at exposure v, e.g. sin(2 pi phase_v) */
+  const double *offset;   /* [nexp]  km/s added at exposure v (barycentric), or NULL: none    */
+} trx_vmap;
+int  trx_run_velocity_map(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                          double *spectrum /* [wn_hi-wn_lo], host; may be NULL */, const trx_vmap *vm,
+                          double *map /* [nkp][nvsys], host */, double *per /* [nlag][nexp], host; may be NULL */,
+                          trx_debug *dbg /* may be NULL */);
+int  trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                                const trx_vmap *vm /* one for all */, double *const *map /* [k] -> [nkp][nvsys] */,
+                                double *const *per /* NULL, or [k] -> [nlag][nexp] */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

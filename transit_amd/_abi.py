@@ -102,6 +102,15 @@ class TrxFilter(C.Structure):
     _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("fwd", c_double_p), ("back", c_double_p)]
 
 
+STAT_CCF, STAT_LOGLIKE_BL19, STAT_CHI2 = 1, 2, 3
+
+
+class TrxVmap(C.Structure):
+    _fields_ = [("stat", C.c_int32), ("nlag", C.c_int32), ("p0", C.c_double), ("p1", C.c_double),
+                ("lag", c_double_p), ("lag_kms", c_double_p), ("nkp", C.c_int32), ("nvsys", C.c_int32),
+                ("kp", c_double_p), ("vsys", c_double_p), ("orbit", c_double_p), ("offset", c_double_p)]
+
+
 BROADEN_NONE, BROADEN_ROTATION = 0, 1
 BROADEN_MAX_HALF = 2048
 
@@ -219,6 +228,17 @@ def bind_trail_api(lib):
     lib.trx_run_batch_trail.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                         C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_trail.restype = C.c_int
+    return lib
+
+
+def bind_vmap_api(lib):
+    """argtypes/restypes of the detection-map entry points (trx_run_velocity_map and its batch form)."""
+    lib.trx_run_velocity_map.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.POINTER(TrxVmap),
+                                         c_double_p, c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_velocity_map.restype = C.c_int
+    lib.trx_run_batch_velocity_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.POINTER(TrxVmap),
+                                               C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_velocity_map.restype = C.c_int
     return lib
 
 

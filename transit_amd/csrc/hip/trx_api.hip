@@ -39,6 +39,7 @@
 #include "trx_pixels.hip.h"
 #include "trx_moments.hip.h"
 #include "trx_trail.hip.h"
+#include "trx_vmap.hip.h"
 #include "trx_filter.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
@@ -46,6 +47,7 @@
 #include "../trx_plan.h"
 #include "../trx_table.h"
 #include "../trx_broaden.h"
+#include "../trx_vmap.h"
 
 using namespace trx;
 
@@ -225,6 +227,9 @@ struct trx_handle {
   std::unique_ptr<ObservedSet> observed;               // trx_set_observed (null: none); belongs to `pixels`
   DevBuf d_mom;                                        // trx_run_moments: [nexp][nseg][TRX_NMOMENT], grown on demand
   DevBuf d_trail;                                      // trx_run_trail: [nlag][nexp][nseg][TRX_NMOMENT], grown on demand
+  // trx_run_velocity_map (trx_vmap.hip.h), grown on demand: the call's arrays lag_kms, kp, vsys, orbit, offset end to end (their
+  // host copy: vm_in), the statistic [nlag][nexp] followed by its transpose [nexp][nlag], the map [nkp][nvsys]
+  DevBuf d_vm_in, d_vm_per, d_vm_map; std::vector<double> vm_in;
   std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
   DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
   bool broad_on = false; Broadening broad;             // trx_set_broadening (broad_on false: none); independent of the sets above
@@ -3286,27 +3291,117 @@ int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
 }
 
 // ---- the cross-correlation trail: every exposure against every lag of a grid (trx_trail.hip.h) -----
+// what a trail run refuses, for `who` (trx_run_trail, trx_run_velocity_map); out: where its result goes, named out_name
+static int trail_run_checks(trx_handle *h, const std::string &who, int32_t nlag, const double *lag, const void *out, const char *out_name)
+{
+  // (as for trx_run_moments: the partial pairs of a shard say nothing about the moments)
+  if (h->windowed())
+    return fail(h, TRX_E_UNSUPPORTED, who + ": this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
+                                      "(trx_gather_host) and reduce them on the host");
+  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, who + ": no observed set installed (trx_set_observed)");
+  const ObservedSet *ob = h->observed.get();
+  if (nlag < 1) return fail(h, TRX_E_ARG, who + ": nlag < 1");
+  if (!lag) return fail(h, TRX_E_ARG, who + ": lag is NULL");
+  if (!out) return fail(h, TRX_E_ARG, who + ": " + out_name + " is NULL");
+  // (the counts first: a refused nlag is not an extent to read lag[] over)
+  if ((int64_t)nlag * ob->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, who + ": nlag * npix above what one pixel launch takes");
+  if ((int64_t)nlag * ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, who + ": nlag * nexp * nseg above 2^31 - 1");
+  for (int32_t l = 0; l < nlag; l++)
+    if (!std::isfinite(lag[l]) || !(lag[l] > 0)) return fail(h, TRX_E_ARG, who + ": lag " + std::to_string(l) + " must be finite and > 0");
+  return TRX_OK;
+}
+
 int trx_run_trail(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nlag, const double *lag,
                   double *trail, trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  // (as for trx_run_moments: the partial pairs of a shard say nothing about the moments)
-  if (h->windowed())
-    return fail(h, TRX_E_UNSUPPORTED, "trx_run_trail: this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
-                                      "(trx_gather_host) and reduce them on the host");
-  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "trx_run_trail: no observed set installed (trx_set_observed)");
+  if (const int rc = trail_run_checks(h, "trx_run_trail", nlag, lag, trail, "trail")) return rc;
   const ObservedSet *ob = h->observed.get();
-  if (nlag < 1) return fail(h, TRX_E_ARG, "trx_run_trail: nlag < 1");
-  if (!lag) return fail(h, TRX_E_ARG, "trx_run_trail: lag is NULL");
-  if (!trail) return fail(h, TRX_E_ARG, "trx_run_trail: trail is NULL");
-  // (the counts first: a refused nlag is not an extent to read lag[] over)
-  if ((int64_t)nlag * ob->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, "trx_run_trail: nlag * npix above what one pixel launch takes");
-  if ((int64_t)nlag * ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, "trx_run_trail: nlag * nexp * nseg above 2^31 - 1");
-  for (int32_t l = 0; l < nlag; l++)
-    if (!std::isfinite(lag[l]) || !(lag[l] > 0)) return fail(h, TRX_E_ARG, "trx_run_trail: lag " + std::to_string(l) + " must be finite and > 0");
   // (an installed filter takes no part: it couples the exposures, and a trail's model is the same at all of them)
   if (const int rc = pixel_run(h, "trx_run_trail", a, o, spectrum, nlag, lag, ob, dbg, nullptr, true)) return rc;
   HIPCHK(h, hipMemcpy(trail, h->d_trail.p, sizeof(double) * TRX_NMOMENT * (size_t)nlag * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
+// ---- the Kp-Vsys map of that trail, reduced on the device (trx_vmap.hip.h) --------------------------
+// what a map run refuses on top of a trail run's refusals, for `who`
+static int velocity_map_checks(trx_handle *h, const std::string &who, const trx_vmap *vm, const void *map)
+{
+  if (!vm) return fail(h, TRX_E_ARG, who + ": vm is NULL");
+  if (const int rc = trail_run_checks(h, who, vm->nlag, vm->lag, map, "map")) return rc;
+  const int32_t nexp = h->observed->nexp;
+  if (vm->stat != TRX_STAT_CCF && vm->stat != TRX_STAT_LOGLIKE_BL19 && vm->stat != TRX_STAT_CHI2)
+    return fail(h, TRX_E_ARG, who + ": unknown stat " + std::to_string(vm->stat));
+  if (vm->nkp < 1 || vm->nvsys < 1) return fail(h, TRX_E_ARG, who + ": nkp < 1 or nvsys < 1");
+  if ((int64_t)vm->nkp * vm->nvsys > 0x7fffffffLL) return fail(h, TRX_E_ARG, who + ": nkp * nvsys above 2^31 - 1");
+  if (!vm->lag_kms) return fail(h, TRX_E_ARG, who + ": lag_kms is NULL");
+  if (!vm->kp) return fail(h, TRX_E_ARG, who + ": kp is NULL");
+  if (!vm->vsys) return fail(h, TRX_E_ARG, who + ": vsys is NULL");
+  if (!vm->orbit) return fail(h, TRX_E_ARG, who + ": orbit is NULL");
+  if (!std::isfinite(vm->p0)) return fail(h, TRX_E_ARG, who + ": p0 must be finite");
+  if (!std::isfinite(vm->p1)) return fail(h, TRX_E_ARG, who + ": p1 must be finite");
+  auto finite = [&](const char *name, const double *x, int32_t n) {
+    for (int32_t k = 0; k < n; k++)
+      if (!std::isfinite(x[k])) return fail(h, TRX_E_ARG, who + ": " + name + " " + std::to_string(k) + " must be finite");
+    return (int)TRX_OK;
+  };
+  int rc;
+  if ((rc = finite("kp", vm->kp, vm->nkp)) || (rc = finite("vsys", vm->vsys, vm->nvsys)) || (rc = finite("orbit", vm->orbit, nexp)) ||
+      (vm->offset && (rc = finite("offset", vm->offset, nexp))))
+    return rc;
+  for (int32_t l = 0; l < vm->nlag; l++)
+    if (!std::isfinite(vm->lag_kms[l]) || (l > 0 && !(vm->lag_kms[l] > vm->lag_kms[l - 1])))
+      return fail(h, TRX_E_ARG, who + ": lag_kms " + std::to_string(l) + " must be finite and above the one before it (strictly increasing)");
+  return TRX_OK;
+}
+
+int trx_run_velocity_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, double *per,
+                         trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const std::string who("trx_run_velocity_map");
+  if (const int rc = velocity_map_checks(h, who, vm, map)) return rc;
+  const ObservedSet *ob = h->observed.get();
+  const size_t nlag = (size_t)vm->nlag, nexp = (size_t)ob->nexp, nkp = (size_t)vm->nkp, nvsys = (size_t)vm->nvsys;
+  // the call's arrays end to end, as the device gets them
+  const size_t at_kp = nlag, at_vsys = at_kp + nkp, at_orbit = at_vsys + nvsys, at_offset = at_orbit + nexp, nin = at_offset + (vm->offset ? nexp : 0);
+  try {
+    h->vm_in.resize(nin);
+  } catch (...) { return fail(h, TRX_E_NOMEM, who + ": out of host memory"); }
+  std::copy(vm->lag_kms, vm->lag_kms + nlag, h->vm_in.begin());
+  std::copy(vm->kp, vm->kp + nkp, h->vm_in.begin() + (std::ptrdiff_t)at_kp);
+  std::copy(vm->vsys, vm->vsys + nvsys, h->vm_in.begin() + (std::ptrdiff_t)at_vsys);
+  std::copy(vm->orbit, vm->orbit + nexp, h->vm_in.begin() + (std::ptrdiff_t)at_orbit);
+  if (vm->offset) std::copy(vm->offset, vm->offset + nexp, h->vm_in.begin() + (std::ptrdiff_t)at_offset);
+  // the trail of the lags into d_trail, as trx_run_trail leaves it; it stays there
+  if (const int rc = pixel_run(h, who.c_str(), a, o, spectrum, vm->nlag, vm->lag, ob, dbg, nullptr, true)) return rc;
+  const size_t rows = nlag * nexp, cells = nkp * nvsys;
+  int rc;
+  if ((rc = ensure(h, h->d_vm_per, sizeof(double) * 2 * rows)) || (rc = ensure(h, h->d_vm_map, sizeof(double) * cells)) ||
+      (rc = upload_raw(h, h->d_vm_in, h->vm_in.data(), nin)))
+    return rc;
+  // (the run has been waited for: the two kernels follow the upload on the main queue)
+  const double *in = h->d_vm_in.as<double>();
+  TrailStatArgs SA{};
+  SA.trail = h->d_trail.as<double>(); SA.per_lv = h->d_vm_per.as<double>(); SA.per_vl = SA.per_lv + rows;
+  SA.nrows = (int64_t)rows; SA.nlag = vm->nlag; SA.nexp = ob->nexp; SA.nseg = ob->nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
+  VelMapArgs MA{};
+  MA.per_vl = SA.per_vl; MA.lag_kms = in; MA.kp = in + at_kp; MA.vsys = in + at_vsys; MA.orbit = in + at_orbit; MA.offset = vm->offset ? in + at_offset : nullptr;
+  MA.map = h->d_vm_map.as<double>(); MA.ncells = (int64_t)cells; MA.nlag = vm->nlag; MA.nexp = ob->nexp; MA.nvsys = vm->nvsys;
+  const int64_t sblocks = (SA.nrows + kVmapWaves - 1) / kVmapWaves, mblocks = (MA.ncells + kVmapWaves - 1) / kVmapWaves;
+  // (every address the kernels read or write: the trail rows [nlag][nexp][nseg], the statistic twice over [nlag][nexp], the
+  // call's arrays -- a cell's lag indices lie in [0, nlag - 1], vmap_locate --, the cells)
+  if (!SA.trail || !SA.per_lv || !in || !MA.map || rows < 1 || cells < 1 || ob->nseg < 1 ||
+      h->d_trail.bytes < sizeof(double) * TRX_NMOMENT * rows * (size_t)ob->nseg || h->d_vm_per.bytes < sizeof(double) * 2 * rows ||
+      h->d_vm_in.bytes < sizeof(double) * nin || h->d_vm_map.bytes < sizeof(double) * cells ||
+      sblocks < 1 || sblocks > 0x7fffffffLL || mblocks < 1 || mblocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the map kernels (not launched)");
+  hipLaunchKernelGGL(k_trail_stat, dim3((unsigned)sblocks), dim3(64 * kVmapWaves), 0, h->stream, SA);
+  hipLaunchKernelGGL(k_velocity_map, dim3((unsigned)mblocks), dim3(64 * kVmapWaves), 0, h->stream, MA);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(map, h->d_vm_map.p, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (per) HIPCHK(h, hipMemcpyAsync(per, h->d_vm_per.p, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return TRX_OK;
 }
 
@@ -3454,6 +3549,8 @@ struct trx_batch {
   bool filtered = false;                             // trx_run_batch_filtered_moments: ... through the filter
   double *const *trail = nullptr;                    // trx_run_batch_trail: the trails instead (shifts: the lags, nshift of them)
   double *const *broadened = nullptr;                // trx_run_batch_broadened: the broadened spectra instead
+  // trx_run_batch_velocity_map: the maps instead, one trx_vmap for all atmospheres; vm_per: and the statistics, or null
+  const trx_vmap *vm = nullptr; double *const *vm_map = nullptr; double *const *vm_per = nullptr;
   // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none); a worker installs its
   // atmosphere's entry on its own handle ahead of a pixel, moment, filtered-moment or broadened run
   std::vector<trx_broadening> broad;
@@ -3503,10 +3600,11 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
           trx_handle *const hj = b->hs[(size_t)i];
           int rc = TRX_OK;
           // (a pixel or broadened run: this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
-          if (b->pix || b->mom || b->trail || b->broadened)
+          if (b->pix || b->mom || b->trail || b->broadened || b->vm)
             rc = trx_set_broadening(hj, b->broad.empty() ? nullptr : &b->broad[b->broad.size() == 1 ? 0 : (size_t)j]);
           if (rc == TRX_OK)
-            rc = b->broadened ? trx_run_broadened(hj, b->atm + j, b->opts, nullptr, b->broadened[j], nullptr)
+            rc = b->vm ? trx_run_velocity_map(hj, b->atm + j, b->opts, nullptr, b->vm, b->vm_map[j], b->vm_per ? b->vm_per[j] : nullptr, nullptr)
+               : b->broadened ? trx_run_broadened(hj, b->atm + j, b->opts, nullptr, b->broadened[j], nullptr)
                : b->trail ? trx_run_trail(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->trail[j], nullptr)
                : b->mom && b->filtered ? trx_run_filtered_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], nullptr, b->mom[j], nullptr)
                : b->mom ? trx_run_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
@@ -3533,12 +3631,14 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 // one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
 static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
                       double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr,
-                      double *const *mom = nullptr, bool filtered = false, double *const *broadened = nullptr, double *const *trail = nullptr)
+                      double *const *mom = nullptr, bool filtered = false, double *const *broadened = nullptr, double *const *trail = nullptr,
+                      const trx_vmap *vm = nullptr, double *const *vm_map = nullptr, double *const *vm_per = nullptr)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
   b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
   b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered; b->broadened = broadened; b->trail = trail;
+  b->vm = vm; b->vm_map = vm_map; b->vm_per = vm_per;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3700,6 +3800,23 @@ int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_o
   }
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_trail")) return rc;
   return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nlag, lag, nullptr, nullptr, false, nullptr, trail);
+}
+
+int trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map,
+                               double *const *per)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = "trx_run_batch_velocity_map: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_velocity_map: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  for (int32_t j = 0; j < k; j++) {
+    if (!map[j]) { g_comm_err = "trx_run_batch_velocity_map: map[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+    if (per && !per[j]) { g_comm_err = "trx_run_batch_velocity_map: per[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  }
+  // (the handles are made from one description and carry one observed set: what the first refuses, all refuse)
+  if (k > 0)
+    if (const int rc = velocity_map_checks(b->hs[0], "trx_run_batch_velocity_map", vm, map[0])) { g_comm_err = b->hs[0]->err; return rc; }
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_velocity_map")) return rc;
+  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, false, nullptr, nullptr, vm, map, per);
 }
 
 // every handle of the batch gets the same filter, or none does

@@ -206,6 +206,7 @@ def hip_library():
         _abi.bind_pixels_api(lib)
         _abi.bind_moments_api(lib)
         _abi.bind_trail_api(lib)
+        _abi.bind_vmap_api(lib)
         _abi.bind_filter_api(lib)
         _abi.bind_broaden_api(lib)
         lib.trx_device_count.restype = C.c_int
@@ -333,6 +334,23 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_trail", self._last_error())
         return (trail, spec) if spectrum else trail
+
+    def run_velocity_map(self, atm, opts, vm, per: bool = False, spectrum: bool = False):
+        """trx_run_velocity_map: the Kp-Vsys map [nkp, nvsys] of a transit_amd.xcor.VelocityMap -- run_trail at vm.lag and,
+        on the device, xcor.trail_statistic and xcor.map_from_per of it; the trail stays there.  With per=True and/or
+        spectrum=True a tuple (map[, per][, spectrum]): per [nlag, nexp] the statistic the map was made from (the map is
+        xcor.map_from_per(per, vm) bit for bit), the spectrum bit for bit what run() gives."""
+        m = np.zeros((vm.nkp, vm.nvsys))
+        pr = np.zeros((vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_velocity_map(self._h, C.byref(atm), C.byref(opts),
+                                            spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
+                                            C.byref(vm.to_c()), m.ctypes.data_as(_abi.c_double_p),
+                                            pr.ctypes.data_as(_abi.c_double_p) if pr is not None else None, None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_velocity_map", self._last_error())
+        out = (m,) + ((pr,) if per else ()) + ((spec,) if spectrum else ())
+        return out if len(out) > 1 else m
 
     def set_filter(self, filt):
         """trx_set_filter: install a detrending filter (a transit_amd.xcor.Filter; None: clear it) over the observed
@@ -524,6 +542,21 @@ class Batch:
         if rc != 0:
             raise EngineError(rc, "trx_run_batch_trail", self._err())
         return out
+
+    def run_velocity_map(self, atms, opts: _abi.TrxOpts, vm, per: bool = False):
+        """trx_run_batch_velocity_map: the maps [K, nkp, nvsys] of one transit_amd.xcor.VelocityMap for all atmospheres
+        -- with per=True, (maps, per [K, nlag, nexp]) --, each atmosphere's what Engine.run_velocity_map gives, bit for
+        bit."""
+        k = len(atms)
+        m = np.zeros((k, vm.nkp, vm.nvsys))
+        pr = np.zeros((k, vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        pm = (_abi.c_double_p * max(k, 1))(*[m[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
+        pp = (_abi.c_double_p * max(k, 1))(*[pr[j].ctypes.data_as(_abi.c_double_p) for j in range(k)]) if per else None
+        rc = self._lib.trx_run_batch_velocity_map(self._b, k, arr, C.byref(opts), C.byref(vm.to_c()), pm, pp)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_batch_velocity_map", self._err())
+        return (m, pr) if per else m
 
     def set_filter(self, filt):
         """trx_batch_set_filter: the same filter on every handle of the batch, or on none."""

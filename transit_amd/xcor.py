@@ -24,6 +24,16 @@ every lag of a velocity grid, trail[l, v, s] -- row l is the moments with lag l'
     lag_grid(v_lo, v_hi, step)                           (lag_kms, lags): velocities v_lo, v_lo + step, ... and pixels.shift of each
     velocity_map(trail, lag_kms, v_planet, stat=ccf)     the statistic along each map cell's velocity track, added over exposures
 
+The detection map on the device (Engine.run_velocity_map / Batch.run_velocity_map; trx_run_velocity_map): the trail
+reduced there to per[l, v] = the statistic of the rows (l, v, .) added over the segments IN ORDER, and to the Kp-Vsys
+map, per interpolated along each cell's velocity track and added over the exposures in order.
+
+    VelocityMap(lag_kms, kp, vsys, orbit, offset=None, stat="ccf", scale=1, a=1, b=0)     a trx_vmap; to_c()
+    trail_statistic(trail, vm)                           per [nlag, nexp]: the definition in numpy, segments added in order
+    map_from_per(per, vm)                                the map [nkp, nvsys] from per: the definition in numpy
+    map_reference(trail, vm)                             map_from_per(trail_statistic(trail, vm), vm)
+    per_bound(trail, vm), map_bound(trail, vm)           how far two double evaluations of per / of a cell can lie apart
+
 The detrending filter (Engine.set_filter / Engine.run_filtered_moments; trx_set_filter / trx_run_filtered_moments): per
 segment s a coefficient matrix fwd[s] ([ncomp, nexp]) and a basis back[s] ([nexp, ncomp]) act along the exposure axis
 of every pixel column.  A column is live when b > 0 at every exposure, otherwise dead and all NaN; for a live column
@@ -273,6 +283,191 @@ def velocity_map(trail, lag_kms, v_planet, stat=ccf) -> np.ndarray:
         t = (x - kms[k]) / (kms[k + 1] - kms[k])
         out += per[k, v] + t * (per[k + 1, v] - per[k, v])
     return np.where(np.all(inside, axis=-1), out, np.nan)
+
+
+STATS = {"ccf": _abi.STAT_CCF, "loglike_bl19": _abi.STAT_LOGLIKE_BL19, "chi2": _abi.STAT_CHI2}
+
+
+@dataclass
+class VelocityMap:
+    """One trx_vmap: the lag grid lag_kms ([nlag] km/s, strictly increasing; lag, their Doppler factors pixels.shift,
+    is filled in), the map's axes kp ([nkp]) and vsys ([nvsys]) in km/s, orbit ([nexp]: what multiplies Kp at every
+    exposure, sin(2 pi phase) for a circular orbit), offset ([nexp] km/s added at every exposure, or None) and the
+    statistic: "ccf", "loglike_bl19" (scale) or "chi2" (a, b)."""
+    lag_kms: np.ndarray
+    kp: np.ndarray
+    vsys: np.ndarray
+    orbit: np.ndarray
+    offset: Optional[np.ndarray] = None
+    stat: str = "ccf"
+    scale: float = 1.0
+    a: float = 1.0
+    b: float = 0.0
+    lag: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        flat = lambda x: np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        self.lag_kms, self.kp, self.vsys, self.orbit = flat(self.lag_kms), flat(self.kp), flat(self.vsys), flat(self.orbit)
+        if self.offset is not None:
+            self.offset = flat(self.offset)
+            if self.offset.size != self.orbit.size:
+                raise ValueError("VelocityMap: one offset per exposure")
+        if self.stat not in STATS:
+            raise ValueError("VelocityMap: stat is one of %s" % ", ".join(sorted(STATS)))
+        self.lag = np.array([_pixels.shift(v) for v in self.lag_kms]) if self.lag is None else flat(self.lag)
+        if self.lag.size != self.lag_kms.size:
+            raise ValueError("VelocityMap: one lag per lag velocity")
+
+    @property
+    def nlag(self) -> int:
+        return int(self.lag_kms.size)
+
+    @property
+    def nkp(self) -> int:
+        return int(self.kp.size)
+
+    @property
+    def nvsys(self) -> int:
+        return int(self.vsys.size)
+
+    @property
+    def nexp(self) -> int:
+        return int(self.orbit.size)
+
+    @property
+    def params(self):
+        """(p0, p1) of the trx_vmap: (scale, 0) for loglike_bl19, (a, b) for chi2, (0, 0) for ccf"""
+        return {"ccf": (0.0, 0.0), "loglike_bl19": (float(self.scale), 0.0), "chi2": (float(self.a), float(self.b))}[self.stat]
+
+    def statistic(self, mom) -> np.ndarray:
+        """the statistic of moments [..., 7]: ccf, loglike_bl19 or chi2 with this map's parameters"""
+        return {"ccf": lambda m: ccf(m), "loglike_bl19": lambda m: loglike_bl19(m, float(self.scale)),
+                "chi2": lambda m: chi2(m, float(self.a), float(self.b))}[self.stat](mom)
+
+    def to_c(self):
+        """The trx_vmap of the map (the arrays stay owned by this object)."""
+        c = _abi.TrxVmap()
+        c.stat, c.nlag = STATS[self.stat], self.nlag
+        c.p0, c.p1 = self.params
+        c.lag = self.lag.ctypes.data_as(_abi.c_double_p)
+        c.lag_kms = self.lag_kms.ctypes.data_as(_abi.c_double_p)
+        c.nkp, c.nvsys = self.nkp, self.nvsys
+        c.kp = self.kp.ctypes.data_as(_abi.c_double_p)
+        c.vsys = self.vsys.ctypes.data_as(_abi.c_double_p)
+        c.orbit = self.orbit.ctypes.data_as(_abi.c_double_p)
+        c.offset = self.offset.ctypes.data_as(_abi.c_double_p) if self.offset is not None else None
+        return c
+
+
+def _check_trail(trail, vm: VelocityMap) -> np.ndarray:
+    trail = np.asarray(trail, dtype=np.float64)
+    if trail.ndim != 4 or trail.shape[0] != vm.nlag or trail.shape[1] != vm.nexp or trail.shape[3] != NMOMENT:
+        raise ValueError("trail of shape [nlag][nexp][nseg][7] with the map's nlag and nexp")
+    return trail
+
+
+def trail_statistic(trail, vm: VelocityMap) -> np.ndarray:
+    """per [nlag, nexp] by the definition of trx_run_velocity_map: the map's statistic of every trail row, added over
+    the segments s = 0, 1, ... IN THAT ORDER, one addition each, from +0; rows the statistic leaves undefined (nan) are
+    skipped.  (velocity_map adds them with np.nansum, whose order is pairwise: the same sum to rounding.)"""
+    st = np.asarray(vm.statistic(_check_trail(trail, vm)), dtype=np.float64)
+    per = np.zeros(st.shape[:2])
+    for s in range(st.shape[2]):
+        with np.errstate(invalid="ignore"):
+            per = np.where(np.isnan(st[:, :, s]), per, per + st[:, :, s])
+    return per
+
+
+def _tracks(vm: VelocityMap) -> np.ndarray:
+    """x [nkp, nvsys, nexp]: (kp * orbit + vsys) + offset, the last addition only with an offset"""
+    x = vm.kp[:, None, None] * vm.orbit[None, None, :] + vm.vsys[None, :, None]
+    return x + vm.offset[None, None, :] if vm.offset is not None else x
+
+
+def _locate(kms, x):
+    """(inside, k, t) of the velocities x on the grid kms: trx_run_velocity_map's step 3 (outside: k = 0, t = 0)"""
+    with np.errstate(invalid="ignore"):
+        inside = (x >= kms[0]) & (x <= kms[-1])
+    if kms.size < 2:
+        return inside, np.zeros(x.shape, dtype=np.int64), np.zeros(x.shape)
+    xi = np.where(inside, x, kms[0])
+    k = np.clip(np.searchsorted(kms, xi, side="right") - 1, 0, kms.size - 2)
+    t = (xi - kms[k]) / (kms[k + 1] - kms[k])
+    return inside, k, np.where(inside, t, 0.0)
+
+
+def map_from_per(per, vm: VelocityMap) -> np.ndarray:
+    """The map [nkp, nvsys] from per [nlag, nexp] by the definition of trx_run_velocity_map: exposure after exposure,
+    per[k, v] + t * (per[k + 1, v] - per[k, v]) at the cell's velocity, added in that order from +0; a cell with a
+    velocity outside the lag grid, or not finite, is nan.  Engine.run_velocity_map's map is this of its per, bit for
+    bit."""
+    per = np.asarray(per, dtype=np.float64)
+    if per.shape != (vm.nlag, vm.nexp):
+        raise ValueError("per of shape [nlag][nexp]")
+    inside, k, t = _locate(vm.lag_kms, _tracks(vm))
+    out = np.zeros((vm.nkp, vm.nvsys))
+    for v in range(vm.nexp):
+        if vm.nlag < 2:
+            out = out + per[0, v]
+            continue
+        kv, tv = k[..., v], t[..., v]
+        with np.errstate(invalid="ignore"):
+            out = out + (per[kv, v] + tv * (per[kv + 1, v] - per[kv, v]))
+    return np.where(np.all(inside, axis=-1), out, np.nan)
+
+
+def map_reference(trail, vm: VelocityMap) -> np.ndarray:
+    """The map of a trail by the definition, all in numpy: map_from_per(trail_statistic(trail, vm), vm)."""
+    return map_from_per(trail_statistic(trail, vm), vm)
+
+
+_EPS = 2.0 ** -52
+
+
+def _abs_rows(trail, vm: VelocityMap) -> np.ndarray:
+    """A [nlag, nexp]: the sum over the segments of |statistic| (undefined rows: nothing)"""
+    return np.nansum(np.abs(np.asarray(vm.statistic(_check_trail(trail, vm)), dtype=np.float64)), axis=2)
+
+
+def per_bound(trail, vm: VelocityMap) -> np.ndarray:
+    """[nlag, nexp]: how far per of the device may lie from trail_statistic of the same trail -- the row part of
+    map_bound.  Both add the same nseg terms in the same order, so only the terms can differ.  A ccf or chi2 term uses
+    +, -, *, / and sqrt alone, all correctly rounded on either side: the same bits, and 4 * 2^-52 * A, A the sum of the
+    |terms| of the row, is a safety net.  A loglike_bl19 term is (-n/2) log(arg) with the same arg on both sides; the
+    device's log is within 3 ulp and numpy's within 1, the product rounds once on each side: 5 * 2^-52 |term| at the
+    most; nseg additions of terms that differ give partial sums that differ, each rounded: nseg * 2^-52 * A more."""
+    a = _abs_rows(trail, vm)
+    nseg = np.asarray(trail).shape[2]
+    return (5 + nseg if vm.stat == "loglike_bl19" else 4) * _EPS * a
+
+
+def map_bound(trail, vm: VelocityMap) -> np.ndarray:
+    """[nkp, nvsys] (nan where the cell is): how far two double evaluations of a map cell from one trail can lie apart
+    when each adds the segments in ANY order (trail_statistic in index order, velocity_map pairwise, the device in
+    index order) and the exposures in index order.  With A[l, v] the sum of the |statistics| of the rows (l, v, .) and
+    S = sum over v of A[k_v, v] + A[k_v + 1, v] -- the absolute terms that enter the cell:
+
+      - per: each side's statistic of a row is within c * 2^-53 |term| of the exact one (c = 4: ccf and chi2 are at most
+        a dozen correctly rounded operations but agree bit for bit in practice; c = 5 for loglike_bl19, see per_bound),
+        and a sum of nseg terms in any order is within (nseg - 1) 2^-53 A of the exact sum of its terms: two sides lie
+        at most (c + nseg) 2^-52 A apart.  The interpolation passes a difference of the two rows on with weights
+        1 - t and t in [0, 1]: at most (c + nseg) 2^-52 (A[k] + A[k+1]) per exposure;
+      - the term per[k] + t (per[k+1] - per[k]): t from two operations, then a difference, a product and a sum, each
+        within 2^-53 of a magnitude of at most |per[k]| + |per[k+1]| <= A[k] + A[k+1]: 5 * 2^-53 per side;
+      - the sum of nexp terms in order: (nexp - 1) 2^-53 of the sum of the |terms| per side, each |term| at most
+        max(|per[k]|, |per[k+1]|).
+
+    Together (c + nseg + 5 + nexp) 2^-52 S, to first order in 2^-52 -- below the (nseg + nexp + 16) 2^-52 S that the
+    interface promises at the most."""
+    trail = _check_trail(trail, vm)
+    a = _abs_rows(trail, vm)
+    nseg = trail.shape[2]
+    inside, k, _ = _locate(vm.lag_kms, _tracks(vm))
+    s = np.zeros((vm.nkp, vm.nvsys))
+    for v in range(vm.nexp):
+        s += a[0, v] if vm.nlag < 2 else a[k[..., v], v] + a[k[..., v] + 1, v]
+    c = 5 if vm.stat == "loglike_bl19" else 4
+    return np.where(np.all(inside, axis=-1), (c + nseg + 5 + vm.nexp) * _EPS * s, np.nan)
 
 
 @dataclass
