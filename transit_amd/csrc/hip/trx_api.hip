@@ -23,6 +23,7 @@
 #include <cstring>
 #include <atomic>
 #include <condition_variable>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -104,6 +105,21 @@ struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = 
 // a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
 // the largest -- which sizes the kernel's tile
 struct Broadening { double beta = 0, limb = 0; int hmax = 0; };
+// what a run makes behind its spectrum (run_once, Run): nothing (trx_run, trx_run_device), or
+struct Products {
+  // a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
+  // spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
+  const BandSet *bs = nullptr;
+  // a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
+  bool contrib = false;
+  // a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it,
+  // and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that -- or (px->trail: trx_run_trail) the one of
+  // trx_trail.hip.h
+  const PixelRun *px = nullptr;
+  // the broadening of a broadened run (trx_run_broadened) or of a pixel run on a handle with one installed -- the spectrum
+  // stays on the device as for bs, the kernel of trx_broaden.hip.h follows it, and the pixel kernel reads what that one wrote
+  const Broadening *br = nullptr;
+};
 
 // The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
 // alone, before any stage.  Each selects between two forms of the same computation that give the same
@@ -1962,19 +1978,10 @@ namespace {
 // the rest of a step behind its extinction: its combine, the CIA kernels ahead of the first optical depth, the optical depth itself
 struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swept = 0; hipStream_t st_tau = nullptr; PendingCombine pc; };
 
-// bs: a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
-// spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
-// contrib: a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
-// px: a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it,
-// and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that -- or (px->trail: trx_run_trail) the one of
-// trx_trail.hip.h
-// br: the broadening of a broadened run (trx_run_broadened) or of a pixel run on a handle with one installed -- the spectrum
-// stays on the device as for bs, the kernel of trx_broaden.hip.h follows it, and the pixel kernel reads what that one wrote
 struct Run {
   // ---- what the run is given
   trx_handle *const h; const trx_atm *const a; const trx_opts *const o;
-  double *const spectrum; void *const d_spectrum; trx_debug *const dbg; const BandSet *const bs; const bool contrib;
-  const PixelRun *const px; const Broadening *const br;
+  double *const spectrum; void *const d_spectrum; trx_debug *const dbg; const Products want;
   const std::chrono::steady_clock::time_point t_host0;
 
   // ---- its shape and modes
@@ -2065,7 +2072,9 @@ struct Run {
   int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
   int side_work(SideWork &S); int queue_cia(); int join_early();
   // ... the spectrum of what they swept, the way back
-  int spectrum_kernel(); int ray_tail(); int band_kernels(); int broaden_kernel(); int pixel_kernels(); int filter_kernels(); int moment_kernels(); int results();
+  int spectrum_kernel(); int ray_tail(); int results();
+  // ... and what the run makes of that spectrum (want), behind it on its queue
+  int product_kernels(); int band_kernels(); int broaden_kernel(); int pixel_kernels(); int filter_kernels(); int moment_kernels();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2410,7 +2419,7 @@ int Run::plan_first_pass()
   tail_mode = h->sw.ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
               nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays && plan_is_tail(h->run_plan, kTailSteps);
   // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !bs && !px && !br;
+  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !want.bs && !want.px && !want.br;
   if ((tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
   // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
   // into a pinned array, one entry per block, and the HOST adds it up behind the kernel (results).  The device-side sum was three
@@ -2662,6 +2671,7 @@ int Run::spectrum_kernel()
 // deeper queues them again behind its own spectrum: the sums the host reads are the last pass's.
 int Run::band_kernels()
 {
+  const BandSet *const bs = want.bs;
   if (!bs || bs->nbands <= 0) return TRX_OK;
   BandArgs BA{};
   BA.spec = d_out; BA.bands = bs->d_bands.as<BandDev>(); BA.pieces = bs->d_pieces.as<BandPiece>();
@@ -2673,7 +2683,7 @@ int Run::band_kernels()
     hipLaunchKernelGGL(k_band_pieces, dim3((unsigned)((bs->npieces + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
   hipLaunchKernelGGL(k_band_sums, dim3((unsigned)((bs->nbands + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
   // ---- and the contribution functions of this pass's optical depths (trx_contrib.hip.h), behind them
-  if (!contrib) return TRX_OK;
+  if (!want.contrib) return TRX_OK;
   ContribArgs CA{};
   if (vertical) emis_args(CA.E);
   else {                                             // (transit geometry: the grid, tau and last; no angles)
@@ -2699,6 +2709,7 @@ int Run::band_kernels()
 // kernel, which then reads d_broad; a pass that resumes deeper queues it again behind its own spectrum.
 int Run::broaden_kernel()
 {
+  const Broadening *const br = want.br;
   if (!br) return TRX_OK;
   BroadArgs BA{};
   BA.spec = d_out; BA.out = h->d_broad.as<double>(); BA.nwn = h->nwn;
@@ -2721,10 +2732,11 @@ int Run::broaden_kernel()
 // the band kernels; a pass that resumes deeper queues it again behind its own spectrum.
 int Run::pixel_kernels()
 {
+  const PixelRun *const px = want.px;
   if (!px) return TRX_OK;
   const PixelSet &S = *px->set;
   PixArgs PA{};
-  PA.spec = br ? h->d_broad.as<double>() : d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
+  PA.spec = want.br ? h->d_broad.as<double>() : d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
   PA.shift = h->d_pixshift.as<double>(); PA.out = h->d_pixout.as<double>();
   PA.npix = S.npix; PA.npairs = S.npix * (int64_t)px->nshift;
   PA.nwn = h->nwn; PA.lo = h->lo; PA.hi = h->hi; PA.cut = S.cut; PA.fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
@@ -2744,6 +2756,7 @@ int Run::pixel_kernels()
 // ahead of the moment kernel, which then reads its values; a pass that resumes deeper queues all three again.
 int Run::filter_kernels()
 {
+  const PixelRun *const px = want.px;
   if (!px || !px->filt) return TRX_OK;
   const FilterSet &F = *px->filt;
   const ObservedSet *O = px->obs;
@@ -2799,6 +2812,7 @@ static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
 // behind the pixel kernel on its queue; a pass that resumes deeper queues both again.  (A trail run: its kernel instead.)
 int Run::moment_kernels()
 {
+  const PixelRun *const px = want.px;
   if (!px || !px->obs) return TRX_OK;
   const ObservedSet &O = *px->obs;
   if (px->trail) return launch_trail(h, *px, tst);
@@ -2856,13 +2870,22 @@ int Run::results()
   return TRX_OK;
 }
 
+// ---- what the run makes of this pass's spectrum (want), all of it on the spectrum's queue.  The order is a dependency:
+// the bands and contributions read the spectrum and the optical depths only, but the broadening writes d_broad, which the
+// pixels then sample; the filter reads the pixels' pairs; the moments (or the trail) read the pairs or the filter's values.
+int Run::product_kernels()
+{
+  int rc;
+  return (rc = band_kernels()) || (rc = broaden_kernel()) || (rc = pixel_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : TRX_OK;
+}
+
 // ---- one pass: the planned steps (h->run_plan) from r_top down, the spectrum of what they swept, its way back
 int Run::pass()
 {
   int rc;
   for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
   if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-  return (rc = spectrum_kernel()) || (rc = band_kernels()) || (rc = broaden_kernel()) || (rc = pixel_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : results();
+  return (rc = spectrum_kernel()) || (rc = product_kernels()) ? rc : results();
 }
 
 // Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
@@ -2952,15 +2975,14 @@ int Run::finish()
 
 }  // namespace
 
-static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg,
-                    const BandSet *bs = nullptr, bool contrib = false, const PixelRun *px = nullptr, const Broadening *br = nullptr)
+static int run_once(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, void *d_spectrum, trx_debug *dbg, const Products &want)
 {
   const auto t_host0 = std::chrono::steady_clock::now();
   if (!h || !a || !o) return TRX_E_ARG;
   int rc;
   if ((rc = run_check(h, a, o))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  Run R{h, a, o, spectrum, d_spectrum, dbg, bs, contrib, px, br, t_host0};       // (behind run_check: its members are made from the run's shape)
+  Run R{h, a, o, spectrum, d_spectrum, dbg, want, t_host0};       // (behind run_check: its members are made from the run's shape)
   if ((rc = R.layout()) || (rc = R.front_maxima()) || (rc = R.workspaces()) || (rc = R.front_inputs()) || (rc = R.plan_first_pass()) || (rc = R.pass()))
     return rc;
   if (R.stop_at_hint_ok && R.flags[0] > 0 && R.r_top >= 0 && (rc = R.resume())) return rc;
@@ -3032,13 +3054,13 @@ int trx_sweep_permol(trx_handle *h, int32_t nv, const double *temp, const double
 int trx_run(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, trx_debug *dbg)
 {
   if (!spectrum) return TRX_E_ARG;
-  return run_once(h, a, o, spectrum, nullptr, dbg);
+  return run_once(h, a, o, spectrum, nullptr, dbg, Products{});
 }
 
 int trx_run_device(trx_handle *h, const trx_atm *a, const trx_opts *o, void *d_spectrum, trx_debug *dbg)
 {
   if (!d_spectrum) return TRX_E_ARG;
-  return run_once(h, a, o, nullptr, d_spectrum, dbg);
+  return run_once(h, a, o, nullptr, d_spectrum, dbg, Products{});
 }
 
 // ---- band integrals (trx_bands.hip.h) -------------------------------------------------------------
@@ -3107,12 +3129,14 @@ static int make_band_set(trx_handle *h, int32_t nbands, const trx_band *bands, s
   return TRX_OK;
 }
 
+static void install_band_set(trx_handle *h, std::unique_ptr<BandSet> &S) { h->bands = std::move(S); }
+
 int trx_set_bands(trx_handle *h, int32_t nbands, const trx_band *bands)
 {
   if (!h) return TRX_E_ARG;
   std::unique_ptr<BandSet> S;
   if (const int rc = make_band_set(h, nbands, bands, S)) return rc;
-  h->bands = std::move(S);
+  install_band_set(h, S);
   return TRX_OK;
 }
 
@@ -3121,7 +3145,8 @@ int trx_run_bands(trx_handle *h, const trx_atm *a, const trx_opts *o, double *sp
   if (!h) return TRX_E_ARG;
   if (!h->bands) return fail(h, TRX_E_ARG, "trx_run_bands: no band set installed (trx_set_bands)");
   if (!sums) return fail(h, TRX_E_ARG, "trx_run_bands: sums is NULL");
-  const int rc = run_once(h, a, o, spectrum, nullptr, dbg, h->bands.get());
+  Products want; want.bs = h->bands.get();
+  const int rc = run_once(h, a, o, spectrum, nullptr, dbg, want);
   if (rc == TRX_OK) std::memcpy(sums, h->bands->h_out.p, sizeof(double) * 2 * (size_t)h->bands->nbands);
   return rc;
 }
@@ -3140,7 +3165,8 @@ int trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   if ((rc = ensure(h, h->d_cpart, sizeof(double) * nr * (size_t)bs->npieces * kContribSplit)) || (rc = ensure_pinned(h, h->h_contrib, out_bytes))) return rc;
-  rc = run_once(h, a, o, spectrum, nullptr, dbg, bs, true);
+  Products want; want.bs = bs; want.contrib = true;
+  rc = run_once(h, a, o, spectrum, nullptr, dbg, want);
   if (rc == TRX_OK) {
     std::memcpy(sums, bs->h_out.p, sizeof(double) * 2 * (size_t)bs->nbands);
     std::memcpy(contrib, h->h_contrib.p, out_bytes);
@@ -3186,29 +3212,30 @@ int trx_set_pixels(trx_handle *h, const trx_pixels *px)
   return TRX_OK;
 }
 
-// a pixel run for `who` (trx_run_pixels; obs: trx_run_moments; filt: trx_run_filtered_moments; trail: trx_run_trail, the shifts
-// its lags): the pairs are in h->d_pixout, the moments in h->d_mom, the filtered values in h->d_pixval, the trail in
-// h->d_trail, when it returns
-static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                     const ObservedSet *obs, trx_debug *dbg, const FilterSet *filt = nullptr, bool trail = false)
+// the pixel run PR for `who` (trx_run_pixels; PR.obs: trx_run_moments; PR.filt: trx_run_filtered_moments; PR.trail: trx_run_trail,
+// the shifts its lags) at PR.nshift shifts: the pairs are in h->d_pixout, the moments in h->d_mom, the filtered values in
+// h->d_pixval, the trail in h->d_trail, when it returns
+static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, const PixelRun &PR, const double *shift,
+                     trx_debug *dbg)
 {
   const std::string w(who);
+  const int32_t nshift = PR.nshift; const ObservedSet *const obs = PR.obs;
   for (int32_t v = 0; v < nshift; v++)
     if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, w + ": shift " + std::to_string(v) + " must be finite and > 0");
-  const PixelRun PR{h->pixels.get(), nshift, obs, filt, trail};
   if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, w + ": nshift * npix above what one launch takes");
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
   if ((rc = ensure(h, h->d_pixout, sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix)) ||
-      (obs && !trail && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
-      (obs && trail && (rc = ensure(h, h->d_trail, sizeof(double) * TRX_NMOMENT * (size_t)nshift * (size_t)obs->nexp * (size_t)obs->nseg))) ||
-      (filt && (rc = ensure(h, h->d_pixval, sizeof(double) * (size_t)nshift * (size_t)PR.set->npix))) ||
+      (obs && !PR.trail && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
+      (obs && PR.trail && (rc = ensure(h, h->d_trail, sizeof(double) * TRX_NMOMENT * (size_t)nshift * (size_t)obs->nexp * (size_t)obs->nseg))) ||
+      (PR.filt && (rc = ensure(h, h->d_pixval, sizeof(double) * (size_t)nshift * (size_t)PR.set->npix))) ||
       (h->broad_on && (rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn))) ||
       (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift)))
     return rc;
   // (with a broadening installed the pixels sample the broadened spectrum)
-  return run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, &PR, h->broad_on ? &h->broad : nullptr);
+  Products want; want.px = &PR; if (h->broad_on) want.br = &h->broad;
+  return run_once(h, a, o, spectrum, nullptr, dbg, want);
 }
 
 int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
@@ -3219,7 +3246,7 @@ int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *s
   if (nshift < 1) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift < 1");
   if (!shift) return fail(h, TRX_E_ARG, "trx_run_pixels: shift is NULL");
   if (!out) return fail(h, TRX_E_ARG, "trx_run_pixels: out is NULL");
-  if (const int rc = pixel_run(h, "trx_run_pixels", a, o, spectrum, nshift, shift, nullptr, dbg)) return rc;
+  if (const int rc = pixel_run(h, "trx_run_pixels", a, o, spectrum, PixelRun{h->pixels.get(), nshift}, shift, dbg)) return rc;
   HIPCHK(h, hipMemcpy(out, h->d_pixout.p, sizeof(double) * 2 * (size_t)nshift * (size_t)h->pixels->npix, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
@@ -3272,20 +3299,35 @@ int trx_set_observed(trx_handle *h, const trx_observed *ob)
   return TRX_OK;
 }
 
+// What a run against the observed set refuses for `who`, in this order: a shard of the grid, no observed set, (Filtered) no
+// filter, the count -- one shift per exposure, or (Trail) at least one lag --, the NULL arrays: in (named shift, or lag) and
+// out (named out_name).
+enum class ObservedRun { Moments, Filtered, Trail };
+static int observed_run_checks(trx_handle *h, const std::string &who, ObservedRun kind, int32_t n, const void *in, const void *out, const char *out_name)
+{
+  const bool lags = kind == ObservedRun::Trail;
+  // (the moments are not linear in the pairs: the partial pairs of a shard say nothing about them -- nor about the filtered
+  // values' live flags)
+  if (h->windowed())
+    return fail(h, TRX_E_UNSUPPORTED, who + ": this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs (trx_gather_host) and " +
+                                      (kind == ObservedRun::Filtered ? "filter and reduce" : "reduce") + " them on the host");
+  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, who + ": no observed set installed (trx_set_observed)");
+  if (kind == ObservedRun::Filtered && !h->filter) return fail(h, TRX_E_ARG, who + ": no filter installed (trx_set_filter)");
+  const int32_t nexp = h->observed->nexp;
+  if (lags && n < 1) return fail(h, TRX_E_ARG, who + ": nlag < 1");
+  if (!lags && n != nexp) return fail(h, TRX_E_ARG, who + ": nshift " + std::to_string(n) + " is not the observed set's nexp " + std::to_string(nexp));
+  if (!in) return fail(h, TRX_E_ARG, who + ": " + (lags ? "lag" : "shift") + " is NULL");
+  if (!out) return fail(h, TRX_E_ARG, who + ": " + out_name + " is NULL");
+  return TRX_OK;
+}
+
 int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
                     double *mom, trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  // (the moments are not linear in the pairs: the partial pairs of a shard say nothing about them)
-  if (h->windowed())
-    return fail(h, TRX_E_UNSUPPORTED, "trx_run_moments: this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
-                                      "(trx_gather_host) and reduce them on the host");
-  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "trx_run_moments: no observed set installed (trx_set_observed)");
+  if (const int rc = observed_run_checks(h, "trx_run_moments", ObservedRun::Moments, nshift, shift, mom, "mom")) return rc;
   const ObservedSet *ob = h->observed.get();
-  if (nshift != ob->nexp) return fail(h, TRX_E_ARG, "trx_run_moments: nshift " + std::to_string(nshift) + " is not the observed set's nexp " + std::to_string(ob->nexp));
-  if (!shift) return fail(h, TRX_E_ARG, "trx_run_moments: shift is NULL");
-  if (!mom) return fail(h, TRX_E_ARG, "trx_run_moments: mom is NULL");
-  if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, nshift, shift, ob, dbg)) return rc;
+  if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, PixelRun{h->pixels.get(), nshift, ob}, shift, dbg)) return rc;
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
@@ -3294,15 +3336,8 @@ int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
 // what a trail run refuses, for `who` (trx_run_trail, trx_run_velocity_map); out: where its result goes, named out_name
 static int trail_run_checks(trx_handle *h, const std::string &who, int32_t nlag, const double *lag, const void *out, const char *out_name)
 {
-  // (as for trx_run_moments: the partial pairs of a shard say nothing about the moments)
-  if (h->windowed())
-    return fail(h, TRX_E_UNSUPPORTED, who + ": this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
-                                      "(trx_gather_host) and reduce them on the host");
-  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, who + ": no observed set installed (trx_set_observed)");
+  if (const int rc = observed_run_checks(h, who, ObservedRun::Trail, nlag, lag, out, out_name)) return rc;
   const ObservedSet *ob = h->observed.get();
-  if (nlag < 1) return fail(h, TRX_E_ARG, who + ": nlag < 1");
-  if (!lag) return fail(h, TRX_E_ARG, who + ": lag is NULL");
-  if (!out) return fail(h, TRX_E_ARG, who + ": " + out_name + " is NULL");
   // (the counts first: a refused nlag is not an extent to read lag[] over)
   if ((int64_t)nlag * ob->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, who + ": nlag * npix above what one pixel launch takes");
   if ((int64_t)nlag * ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, who + ": nlag * nexp * nseg above 2^31 - 1");
@@ -3318,7 +3353,8 @@ int trx_run_trail(trx_handle *h, const trx_atm *a, const trx_opts *o, double *sp
   if (const int rc = trail_run_checks(h, "trx_run_trail", nlag, lag, trail, "trail")) return rc;
   const ObservedSet *ob = h->observed.get();
   // (an installed filter takes no part: it couples the exposures, and a trail's model is the same at all of them)
-  if (const int rc = pixel_run(h, "trx_run_trail", a, o, spectrum, nlag, lag, ob, dbg, nullptr, true)) return rc;
+  PixelRun PR{h->pixels.get(), nlag, ob}; PR.trail = true;
+  if (const int rc = pixel_run(h, "trx_run_trail", a, o, spectrum, PR, lag, dbg)) return rc;
   HIPCHK(h, hipMemcpy(trail, h->d_trail.p, sizeof(double) * TRX_NMOMENT * (size_t)nlag * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
@@ -3374,7 +3410,8 @@ int trx_run_velocity_map(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   std::copy(vm->orbit, vm->orbit + nexp, h->vm_in.begin() + (std::ptrdiff_t)at_orbit);
   if (vm->offset) std::copy(vm->offset, vm->offset + nexp, h->vm_in.begin() + (std::ptrdiff_t)at_offset);
   // the trail of the lags into d_trail, as trx_run_trail leaves it; it stays there
-  if (const int rc = pixel_run(h, who.c_str(), a, o, spectrum, vm->nlag, vm->lag, ob, dbg, nullptr, true)) return rc;
+  PixelRun PR{h->pixels.get(), vm->nlag, ob}; PR.trail = true;
+  if (const int rc = pixel_run(h, who.c_str(), a, o, spectrum, PR, vm->lag, dbg)) return rc;
   const size_t rows = nlag * nexp, cells = nkp * nvsys;
   int rc;
   if ((rc = ensure(h, h->d_vm_per, sizeof(double) * 2 * rows)) || (rc = ensure(h, h->d_vm_map, sizeof(double) * cells)) ||
@@ -3453,12 +3490,14 @@ static int make_filter_set(trx_handle *h, const trx_filter *f, std::unique_ptr<F
   return TRX_OK;
 }
 
+static void install_filter_set(trx_handle *h, std::unique_ptr<FilterSet> &S) { h->filter = std::move(S); }
+
 int trx_set_filter(trx_handle *h, const trx_filter *f)
 {
   if (!h) return TRX_E_ARG;
   std::unique_ptr<FilterSet> S;
   if (const int rc = make_filter_set(h, f, S)) return rc;
-  h->filter = std::move(S);
+  install_filter_set(h, S);
   return TRX_OK;
 }
 
@@ -3466,17 +3505,9 @@ int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
                              double *values, double *mom, trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  // (as for trx_run_moments: neither the filtered values' live flags nor the moments follow from a shard's partial pairs)
-  if (h->windowed())
-    return fail(h, TRX_E_UNSUPPORTED, "trx_run_filtered_moments: this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs "
-                                      "(trx_gather_host) and filter and reduce them on the host");
-  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: no observed set installed (trx_set_observed)");
-  if (!h->filter) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: no filter installed (trx_set_filter)");
+  if (const int rc = observed_run_checks(h, "trx_run_filtered_moments", ObservedRun::Filtered, nshift, shift, mom, "mom")) return rc;
   const ObservedSet *ob = h->observed.get();
-  if (nshift != ob->nexp) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: nshift " + std::to_string(nshift) + " is not the observed set's nexp " + std::to_string(ob->nexp));
-  if (!shift) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: shift is NULL");
-  if (!mom) return fail(h, TRX_E_ARG, "trx_run_filtered_moments: mom is NULL");
-  if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, nshift, shift, ob, dbg, h->filter.get())) return rc;
+  if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, PixelRun{h->pixels.get(), nshift, ob, h->filter.get()}, shift, dbg)) return rc;
   // (the run has been waited for)
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));
   if (values) HIPCHK(h, hipMemcpy(values, h->d_pixval.p, sizeof(double) * (size_t)ob->nexp * (size_t)ob->npix, hipMemcpyDeviceToHost));
@@ -3522,7 +3553,8 @@ int trx_run_broadened(trx_handle *h, const trx_atm *a, const trx_opts *o, double
   if (!broadened) return fail(h, TRX_E_ARG, "trx_run_broadened: broadened is NULL");
   HIPCHK(h, hipSetDevice(h->device));
   if (const int rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn)) return rc;
-  if (const int rc = run_once(h, a, o, spectrum, nullptr, dbg, nullptr, false, nullptr, &h->broad)) return rc;
+  Products want; want.br = &h->broad;
+  if (const int rc = run_once(h, a, o, spectrum, nullptr, dbg, want)) return rc;
   HIPCHK(h, hipMemcpy(broadened, h->d_broad.p, sizeof(double) * (size_t)h->nwn, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
@@ -3535,28 +3567,48 @@ int trx_run_broadened(trx_handle *h, const trx_atm *a, const trx_opts *o, double
 // thread of its own, and deals the K atmospheres of a call to them.  Every spectrum is what trx_run gives
 // for its atmosphere, bit for bit -- it IS a trx_run, on whichever handle was free (a run's sums do not
 // depend on the handle's history: the depth hint only changes the step plan).
+extern "C++" {      // (BatchJob's constructor and batch_install are templates: they cannot have C linkage)
+// one call's job, "run atmosphere j on handle h": a callable of its trx_run_batch_* function, held by address -- it lives on
+// the stack of that function, which waits inside batch_call until every worker is done with it.  Nothing is allocated,
+// nothing can throw.
+struct BatchJob {
+  const void *call = nullptr; int (*run)(const void *call, trx_handle *h, int32_t j) = nullptr;
+  BatchJob() = default;
+  template <class F>
+  BatchJob(const F &f) : call(&f), run([](const void *c, trx_handle *h, int32_t j) { return (*static_cast<const F *>(c))(h, j); }) {}
+  int operator()(trx_handle *h, int32_t j) const { return run(call, h, j); }
+};
+
 struct trx_batch {
   std::vector<trx_handle *> hs;
   std::vector<std::thread> workers;
   std::mutex mu; std::condition_variable cv_work, cv_done;
-  // the call being served (under mu)
+  // the call being served (under mu): k atmospheres, the job that runs one of them, and whether a worker installs the
+  // atmosphere's broadening on its handle first (a pixel, moment, filtered-moment, trail, map or broadened run)
   uint64_t epoch = 0; bool quit = false;
-  int32_t k = 0; const trx_atm *atm = nullptr; const trx_opts *opts = nullptr; double *const *spectra = nullptr;
-  double *const *sums = nullptr;                     // trx_run_batch_bands: the band sums instead of the spectra
-  double *const *contrib = nullptr;                  // trx_run_batch_contrib: and the contribution functions
-  int32_t nshift = 0; const double *const *shifts = nullptr; double *const *pix = nullptr;      // trx_run_batch_pixels: the pixel pairs instead
-  double *const *mom = nullptr;                      // trx_run_batch_moments: the moments instead (shifts as for pix)
-  bool filtered = false;                             // trx_run_batch_filtered_moments: ... through the filter
-  double *const *trail = nullptr;                    // trx_run_batch_trail: the trails instead (shifts: the lags, nshift of them)
-  double *const *broadened = nullptr;                // trx_run_batch_broadened: the broadened spectra instead
-  // trx_run_batch_velocity_map: the maps instead, one trx_vmap for all atmospheres; vm_per: and the statistics, or null
-  const trx_vmap *vm = nullptr; double *const *vm_map = nullptr; double *const *vm_per = nullptr;
-  // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none); a worker installs its
-  // atmosphere's entry on its own handle ahead of a pixel, moment, filtered-moment or broadened run
+  int32_t k = 0; BatchJob job; bool wants_broadening = false;
+  // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none)
   std::vector<trx_broadening> broad;
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
+
+// every handle of the batch gets the same set, or none does: all sets are built (make) before any is installed (install);
+// the failing handle's text goes to trx_last_error(NULL)
+template <class Set, class Make>
+static int batch_install(trx_batch *b, Make make, void (*install)(trx_handle *, std::unique_ptr<Set> &))
+{
+  g_comm_err.clear();
+  if (!b) return TRX_E_ARG;
+  std::vector<std::unique_ptr<Set>> sets(b->hs.size());
+  for (size_t i = 0; i < b->hs.size(); i++) {
+    const int rc = make(b->hs[i], sets[i]);
+    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
+  }
+  for (size_t i = 0; i < b->hs.size(); i++) install(b->hs[i], sets[i]);
+  return TRX_OK;
+}
+}  // extern "C++"
 
 int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 {
@@ -3599,19 +3651,10 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
           if (j >= b->k) break;
           trx_handle *const hj = b->hs[(size_t)i];
           int rc = TRX_OK;
-          // (a pixel or broadened run: this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
-          if (b->pix || b->mom || b->trail || b->broadened || b->vm)
+          // (this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
+          if (b->wants_broadening)
             rc = trx_set_broadening(hj, b->broad.empty() ? nullptr : &b->broad[b->broad.size() == 1 ? 0 : (size_t)j]);
-          if (rc == TRX_OK)
-            rc = b->vm ? trx_run_velocity_map(hj, b->atm + j, b->opts, nullptr, b->vm, b->vm_map[j], b->vm_per ? b->vm_per[j] : nullptr, nullptr)
-               : b->broadened ? trx_run_broadened(hj, b->atm + j, b->opts, nullptr, b->broadened[j], nullptr)
-               : b->trail ? trx_run_trail(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->trail[j], nullptr)
-               : b->mom && b->filtered ? trx_run_filtered_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], nullptr, b->mom[j], nullptr)
-               : b->mom ? trx_run_moments(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->mom[j], nullptr)
-               : b->pix ? trx_run_pixels(hj, b->atm + j, b->opts, nullptr, b->nshift, b->shifts[j], b->pix[j], nullptr)
-               : b->contrib ? trx_run_contrib(hj, b->atm + j, b->opts, nullptr, b->sums[j], b->contrib[j], nullptr)
-               : b->sums ? trx_run_bands(hj, b->atm + j, b->opts, nullptr, b->sums[j], nullptr)
-                         : trx_run(hj, b->atm + j, b->opts, b->spectra[j], nullptr);
+          if (rc == TRX_OK) rc = b->job(hj, j);
           if (rc != TRX_OK) {
             std::lock_guard<std::mutex> lk(b->mu);
             if (b->rc == TRX_OK) { b->rc = rc; b->err = "atmosphere " + std::to_string(j) + ": " + hj->err; }
@@ -3628,24 +3671,31 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
   return TRX_OK;
 }
 
-// one call of the batch: spectra (trx_run) or band sums (trx_run_bands) of k atmospheres
-static int batch_call(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra, double *const *sums,
-                      double *const *contrib = nullptr, int32_t nshift = 0, const double *const *shifts = nullptr, double *const *pix = nullptr,
-                      double *const *mom = nullptr, bool filtered = false, double *const *broadened = nullptr, double *const *trail = nullptr,
-                      const trx_vmap *vm = nullptr, double *const *vm_map = nullptr, double *const *vm_per = nullptr)
+// one call of the batch: `job` for each of k atmospheres on whichever handle is free; returns when every worker is done
+static int batch_call(trx_batch *b, int32_t k, bool wants_broadening, const BatchJob &job)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
-  b->k = k; b->atm = atm; b->opts = opts; b->spectra = spectra; b->sums = sums; b->contrib = contrib;
-  b->nshift = nshift; b->shifts = shifts; b->pix = pix; b->mom = mom; b->filtered = filtered; b->broadened = broadened; b->trail = trail;
-  b->vm = vm; b->vm_map = vm_map; b->vm_per = vm_per;
+  b->k = k; b->job = job; b->wants_broadening = wants_broadening;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
   b->cv_work.notify_all();
   b->cv_done.wait(lk, [&] { return b->busy == 0; });
+  b->job = BatchJob{};                                     // (the caller's callable goes when this returns)
   if (b->rc != TRX_OK) g_comm_err = b->err;                // trx_last_error(NULL)
   return b->rc;
+}
+
+// a NULL row among the k rows of the arrays named: by atmosphere, then in the order given (an array that is NULL itself is
+// an optional one the caller left out)
+struct BatchRows { const char *name; const double *const *rows; };
+static int batch_rows_check(const char *who, int32_t k, std::initializer_list<BatchRows> arrays)
+{
+  for (int32_t j = 0; j < k; j++)
+    for (const BatchRows &A : arrays)
+      if (A.rows && !A.rows[j]) { g_comm_err = std::string(who) + ": " + A.name + "[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  return TRX_OK;
 }
 
 int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra)
@@ -3653,21 +3703,12 @@ int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *o
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !spectra))) return TRX_E_ARG;
   for (int32_t j = 0; j < k; j++) if (!spectra[j]) return TRX_E_ARG;
-  return batch_call(b, k, atm, opts, spectra, nullptr);
+  return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run(h, atm + j, opts, spectra[j], nullptr); });
 }
 
-// every handle of the batch gets the same set, or none does: all sets are built before any is installed
 int trx_batch_set_bands(trx_batch *b, int32_t nbands, const trx_band *bands)
 {
-  g_comm_err.clear();
-  if (!b) return TRX_E_ARG;
-  std::vector<std::unique_ptr<BandSet>> sets(b->hs.size());
-  for (size_t i = 0; i < b->hs.size(); i++) {
-    const int rc = make_band_set(b->hs[i], nbands, bands, sets[i]);
-    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
-  }
-  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->bands = std::move(sets[i]);
-  return TRX_OK;
+  return batch_install<BandSet>(b, [=](trx_handle *h, std::unique_ptr<BandSet> &S) { return make_band_set(h, nbands, bands, S); }, install_band_set);
 }
 
 int trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *sums)
@@ -3675,8 +3716,8 @@ int trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm, const trx_o
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums))) { g_comm_err = "trx_run_batch_bands: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_bands: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) if (!sums[j]) { g_comm_err = "trx_run_batch_bands: sums[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  return batch_call(b, k, atm, opts, nullptr, sums);
+  if (const int rc = batch_rows_check("trx_run_batch_bands", k, {{"sums", sums}})) return rc;
+  return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run_bands(h, atm + j, opts, nullptr, sums[j], nullptr); });
 }
 
 int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *sums, double *const *contrib)
@@ -3684,11 +3725,8 @@ int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums || !contrib))) { g_comm_err = "trx_run_batch_contrib: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_contrib: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) {
-    if (!sums[j]) { g_comm_err = "trx_run_batch_contrib: sums[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-    if (!contrib[j]) { g_comm_err = "trx_run_batch_contrib: contrib[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  }
-  return batch_call(b, k, atm, opts, nullptr, sums, contrib);
+  if (const int rc = batch_rows_check("trx_run_batch_contrib", k, {{"sums", sums}, {"contrib", contrib}})) return rc;
+  return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run_contrib(h, atm + j, opts, nullptr, sums[j], contrib[j], nullptr); });
 }
 
 // the batch's broadenings, one for all atmospheres or one each: all entries are checked before any is kept, or none is
@@ -3725,23 +3763,14 @@ int trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm, const t
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !broadened))) { g_comm_err = "trx_run_batch_broadened: bad argument"; return TRX_E_ARG; }
   if (b->broad.empty()) { g_comm_err = "trx_run_batch_broadened: no broadening installed (trx_batch_set_broadening)"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) if (!broadened[j]) { g_comm_err = "trx_run_batch_broadened: broadened[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
+  if (const int rc = batch_rows_check("trx_run_batch_broadened", k, {{"broadened", broadened}})) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_broadened")) return rc;
-  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, false, broadened);
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_broadened(h, atm + j, opts, nullptr, broadened[j], nullptr); });
 }
 
-// every handle of the batch gets the same pixel set, or none does
 int trx_batch_set_pixels(trx_batch *b, const trx_pixels *px)
 {
-  g_comm_err.clear();
-  if (!b) return TRX_E_ARG;
-  std::vector<std::unique_ptr<PixelSet>> sets(b->hs.size());
-  for (size_t i = 0; i < b->hs.size(); i++) {
-    const int rc = make_pixel_set(b->hs[i], px, sets[i]);
-    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
-  }
-  for (size_t i = 0; i < b->hs.size(); i++) install_pixel_set(b->hs[i], sets[i]);
-  return TRX_OK;
+  return batch_install<PixelSet>(b, [=](trx_handle *h, std::unique_ptr<PixelSet> &S) { return make_pixel_set(h, px, S); }, install_pixel_set);
 }
 
 int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
@@ -3751,26 +3780,14 @@ int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !out))) { g_comm_err = "trx_run_batch_pixels: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->pixels) { g_comm_err = "trx_run_batch_pixels: no pixel set installed (trx_batch_set_pixels)"; return TRX_E_ARG; }
   if (nshift < 1) { g_comm_err = "trx_run_batch_pixels: nshift < 1"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) {
-    if (!shift[j]) { g_comm_err = "trx_run_batch_pixels: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-    if (!out[j]) { g_comm_err = "trx_run_batch_pixels: out[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  }
+  if (const int rc = batch_rows_check("trx_run_batch_pixels", k, {{"shift", shift}, {"out", out}})) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_pixels")) return rc;
-  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, out);
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_pixels(h, atm + j, opts, nullptr, nshift, shift[j], out[j], nullptr); });
 }
 
-// every handle of the batch gets the same observed set, or none does
 int trx_batch_set_observed(trx_batch *b, const trx_observed *ob)
 {
-  g_comm_err.clear();
-  if (!b) return TRX_E_ARG;
-  std::vector<std::unique_ptr<ObservedSet>> sets(b->hs.size());
-  for (size_t i = 0; i < b->hs.size(); i++) {
-    const int rc = make_observed_set(b->hs[i], ob, sets[i]);
-    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
-  }
-  for (size_t i = 0; i < b->hs.size(); i++) install_observed_set(b->hs[i], sets[i]);
-  return TRX_OK;
+  return batch_install<ObservedSet>(b, [=](trx_handle *h, std::unique_ptr<ObservedSet> &S) { return make_observed_set(h, ob, S); }, install_observed_set);
 }
 
 int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
@@ -3779,12 +3796,9 @@ int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_moments: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) {
-    if (!shift[j]) { g_comm_err = "trx_run_batch_moments: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-    if (!mom[j]) { g_comm_err = "trx_run_batch_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  }
+  if (const int rc = batch_rows_check("trx_run_batch_moments", k, {{"shift", shift}, {"mom", mom}})) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_moments")) return rc;
-  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom);
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_moments(h, atm + j, opts, nullptr, nshift, shift[j], mom[j], nullptr); });
 }
 
 int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nlag, const double *const *lag,
@@ -3794,12 +3808,9 @@ int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_o
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !lag || !trail))) { g_comm_err = "trx_run_batch_trail: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_trail: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
   if (nlag < 1) { g_comm_err = "trx_run_batch_trail: nlag < 1"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) {
-    if (!lag[j]) { g_comm_err = "trx_run_batch_trail: lag[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-    if (!trail[j]) { g_comm_err = "trx_run_batch_trail: trail[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  }
+  if (const int rc = batch_rows_check("trx_run_batch_trail", k, {{"lag", lag}, {"trail", trail}})) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_trail")) return rc;
-  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nlag, lag, nullptr, nullptr, false, nullptr, trail);
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_trail(h, atm + j, opts, nullptr, nlag, lag[j], trail[j], nullptr); });
 }
 
 int trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map,
@@ -3808,29 +3819,17 @@ int trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm, cons
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = "trx_run_batch_velocity_map: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_velocity_map: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) {
-    if (!map[j]) { g_comm_err = "trx_run_batch_velocity_map: map[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-    if (per && !per[j]) { g_comm_err = "trx_run_batch_velocity_map: per[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  }
+  if (const int rc = batch_rows_check("trx_run_batch_velocity_map", k, {{"map", map}, {"per", per}})) return rc;
   // (the handles are made from one description and carry one observed set: what the first refuses, all refuse)
   if (k > 0)
     if (const int rc = velocity_map_checks(b->hs[0], "trx_run_batch_velocity_map", vm, map[0])) { g_comm_err = b->hs[0]->err; return rc; }
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_velocity_map")) return rc;
-  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, false, nullptr, nullptr, vm, map, per);
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_velocity_map(h, atm + j, opts, nullptr, vm, map[j], per ? per[j] : nullptr, nullptr); });
 }
 
-// every handle of the batch gets the same filter, or none does
 int trx_batch_set_filter(trx_batch *b, const trx_filter *f)
 {
-  g_comm_err.clear();
-  if (!b) return TRX_E_ARG;
-  std::vector<std::unique_ptr<FilterSet>> sets(b->hs.size());
-  for (size_t i = 0; i < b->hs.size(); i++) {
-    const int rc = make_filter_set(b->hs[i], f, sets[i]);
-    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
-  }
-  for (size_t i = 0; i < b->hs.size(); i++) b->hs[i]->filter = std::move(sets[i]);
-  return TRX_OK;
+  return batch_install<FilterSet>(b, [=](trx_handle *h, std::unique_ptr<FilterSet> &S) { return make_filter_set(h, f, S); }, install_filter_set);
 }
 
 int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
@@ -3840,12 +3839,9 @@ int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, 
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_filtered_moments: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_filtered_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
   if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_moments: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
-  for (int32_t j = 0; j < k; j++) {
-    if (!shift[j]) { g_comm_err = "trx_run_batch_filtered_moments: shift[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-    if (!mom[j]) { g_comm_err = "trx_run_batch_filtered_moments: mom[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  }
+  if (const int rc = batch_rows_check("trx_run_batch_filtered_moments", k, {{"shift", shift}, {"mom", mom}})) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_moments")) return rc;
-  return batch_call(b, k, atm, opts, nullptr, nullptr, nullptr, nshift, shift, nullptr, mom, true);
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_moments(h, atm + j, opts, nullptr, nshift, shift[j], nullptr, mom[j], nullptr); });
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

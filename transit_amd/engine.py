@@ -227,6 +227,11 @@ def hip_library():
     return _hip
 
 
+def _dp(x):
+    """the double pointer of an array, or None for None (an output the caller does not want)"""
+    return x.ctypes.data_as(_abi.c_double_p) if x is not None else None
+
+
 class Engine(CEngine):
     """MI355X engine: one handle = one GPU = one wavenumber shard."""
 
@@ -251,9 +256,7 @@ class Engine(CEngine):
         the spectrum bit for bit what run() gives."""
         sums = np.zeros((getattr(self, "nbands", 0), 2))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_bands(self._h, C.byref(atm), C.byref(opts),
-                                     spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                     sums.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_bands(self._h, C.byref(atm), C.byref(opts), _dp(spec), _dp(sums), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_bands", self._last_error())
         return (sums, spec) if spectrum else sums
@@ -266,9 +269,7 @@ class Engine(CEngine):
         sums = np.zeros((nb, 2))
         contrib = np.zeros((nb, int(atm.nlayer)))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_contrib(self._h, C.byref(atm), C.byref(opts),
-                                       spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                       sums.ctypes.data_as(_abi.c_double_p), contrib.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_contrib(self._h, C.byref(atm), C.byref(opts), _dp(spec), _dp(sums), _dp(contrib), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_contrib", self._last_error())
         return (sums, contrib, spec) if spectrum else (sums, contrib)
@@ -288,10 +289,7 @@ class Engine(CEngine):
         sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
         out = np.zeros((sh.size, getattr(self, "npix", 0), 2))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_pixels(self._h, C.byref(atm), C.byref(opts),
-                                      spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                      int(sh.size), sh.ctypes.data_as(_abi.c_double_p),
-                                      out.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_pixels(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(out), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_pixels", self._last_error())
         return (out, spec) if spectrum else out
@@ -311,10 +309,7 @@ class Engine(CEngine):
         sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
         mom = np.zeros(getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_moments(self._h, C.byref(atm), C.byref(opts),
-                                       spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                       int(sh.size), sh.ctypes.data_as(_abi.c_double_p),
-                                       mom.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_moments(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(mom), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_moments", self._last_error())
         return (mom, spec) if spectrum else mom
@@ -327,10 +322,7 @@ class Engine(CEngine):
         lg = np.ascontiguousarray(lags, dtype=np.float64).reshape(-1)
         trail = np.zeros((lg.size,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_trail(self._h, C.byref(atm), C.byref(opts),
-                                     spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                     int(lg.size), lg.ctypes.data_as(_abi.c_double_p),
-                                     trail.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_trail(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(lg.size), _dp(lg), _dp(trail), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_trail", self._last_error())
         return (trail, spec) if spectrum else trail
@@ -343,10 +335,7 @@ class Engine(CEngine):
         m = np.zeros((vm.nkp, vm.nvsys))
         pr = np.zeros((vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_velocity_map(self._h, C.byref(atm), C.byref(opts),
-                                            spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                            C.byref(vm.to_c()), m.ctypes.data_as(_abi.c_double_p),
-                                            pr.ctypes.data_as(_abi.c_double_p) if pr is not None else None, None)
+        rc = self._lib.trx_run_velocity_map(self._h, C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m), _dp(pr), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_velocity_map", self._last_error())
         out = (m,) + ((pr,) if per else ()) + ((spec,) if spectrum else ())
@@ -368,11 +357,8 @@ class Engine(CEngine):
         mom = np.zeros(getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
         spec = np.zeros(self.nwn) if spectrum else None
         val = np.zeros((mom.shape[0], getattr(self, "npix", 0))) if values else None
-        rc = self._lib.trx_run_filtered_moments(self._h, C.byref(atm), C.byref(opts),
-                                                spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                                int(sh.size), sh.ctypes.data_as(_abi.c_double_p),
-                                                val.ctypes.data_as(_abi.c_double_p) if val is not None else None,
-                                                mom.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_filtered_moments(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(val),
+                                                _dp(mom), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_filtered_moments", self._last_error())
         out = (mom,) + ((spec,) if spectrum else ()) + ((val,) if values else ())
@@ -390,9 +376,7 @@ class Engine(CEngine):
         spectrum bit for bit what run() gives (never the broadened one)."""
         out = np.zeros(self.nwn)
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_broadened(self._h, C.byref(atm), C.byref(opts),
-                                         spec.ctypes.data_as(_abi.c_double_p) if spec is not None else None,
-                                         out.ctypes.data_as(_abi.c_double_p), None)
+        rc = self._lib.trx_run_broadened(self._h, C.byref(atm), C.byref(opts), _dp(spec), _dp(out), None)
         if rc != 0:
             raise EngineError(rc, "trx_run_broadened", self._last_error())
         return (out, spec) if spectrum else out
@@ -406,6 +390,19 @@ class Engine(CEngine):
         rc = self._lib.trx_gather(self._h, C.c_void_p(d_slice_ptr), C.c_void_p(d_all_ptr), int(count))
         if rc != 0:
             raise EngineError(rc, "trx_gather", self._last_error())
+
+
+def _rows(a):
+    """one double pointer per row of a [K, ...] (None: no array; K = 0: one unused entry, ctypes has no empty array)"""
+    return (_abi.c_double_p * max(len(a), 1))(*[_dp(row) for row in a]) if a is not None else None
+
+
+def _per_atmosphere(who: str, what: str, x, k: int) -> np.ndarray:
+    """x as [K][n] doubles, one row per atmosphere; what: "shifts of shape [K][nshift]", for the refusal"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != k:
+        raise ValueError("Batch.%s: %s, one row per atmosphere" % (who, what))
+    return a
 
 
 class Batch:
@@ -428,20 +425,23 @@ class Batch:
         self.nwn = int(static.wn_hi - static.wn_lo)
         rc = lib.trx_batch_create(C.byref(static), int(ways), C.byref(self._b))
         if rc != 0:
-            raise EngineError(rc, "trx_batch_create", (lib.trx_last_error(None) or b"").decode(errors="replace"))
-
-    def run(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
-        k = len(atms)
-        out = np.zeros((k, self.nwn))
-        arr = (_abi.TrxAtm * k)(*atms)
-        ptrs = (_abi.c_double_p * k)(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch(self._b, k, arr, C.byref(opts), ptrs)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch", (self._lib.trx_last_error(None) or b"").decode(errors="replace"))
-        return out
+            raise EngineError(rc, "trx_batch_create", self._err())
 
     def _err(self) -> str:
         return (self._lib.trx_last_error(None) or b"").decode(errors="replace")
+
+    def _call(self, name: str, atms, opts: _abi.TrxOpts, *args):
+        """the batch function `name` over the atmospheres: args are what follows opts in its C signature"""
+        k = len(atms)
+        arr = (_abi.TrxAtm * max(k, 1))(*atms)
+        rc = getattr(self._lib, name)(self._b, k, arr, C.byref(opts), *args)
+        if rc != 0:
+            raise EngineError(rc, name, self._err())
+
+    def run(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
+        out = np.zeros((len(atms), self.nwn))
+        self._call("trx_run_batch", atms, opts, _rows(out))
+        return out
 
     def set_bands(self, bands):
         """trx_batch_set_bands: the same band set on every handle of the batch, or on none."""
@@ -453,13 +453,8 @@ class Batch:
 
     def run_bands(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
         """trx_run_batch_bands: [K, nbands, 2], each atmosphere's sums what Engine.run_bands gives, bit for bit."""
-        k = len(atms)
-        out = np.zeros((k, getattr(self, "nbands", 0), 2))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        ptrs = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_bands(self._b, k, arr, C.byref(opts), ptrs)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_bands", self._err())
+        out = np.zeros((len(atms), getattr(self, "nbands", 0), 2))
+        self._call("trx_run_batch_bands", atms, opts, _rows(out))
         return out
 
     def run_contrib(self, atms, opts: _abi.TrxOpts):
@@ -471,12 +466,7 @@ class Batch:
         if any(int(a.nlayer) != nl for a in atms):
             raise ValueError("Batch.run_contrib: atmospheres of different nlayer; call it once per nlayer")
         sums, contrib = np.zeros((k, nb, 2)), np.zeros((k, nb, nl))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        ps = (_abi.c_double_p * max(k, 1))(*[sums[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        pc = (_abi.c_double_p * max(k, 1))(*[contrib[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_contrib(self._b, k, arr, C.byref(opts), ps, pc)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_contrib", self._err())
+        self._call("trx_run_batch_contrib", atms, opts, _rows(sums), _rows(contrib))
         return sums, contrib
 
     def set_pixels(self, pixels):
@@ -491,17 +481,9 @@ class Batch:
     def run_pixels(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_pixels: [K, nshift, npix, 2] for shifts of shape [K][nshift] (atmosphere j at its own shifts),
         each atmosphere's pairs what Engine.run_pixels gives, bit for bit."""
-        k = len(atms)
-        sh = np.ascontiguousarray(shifts, dtype=np.float64)
-        if sh.ndim != 2 or sh.shape[0] != k:
-            raise ValueError("Batch.run_pixels: shifts of shape [K][nshift], one row per atmosphere")
-        out = np.zeros((k, sh.shape[1], getattr(self, "npix", 0), 2))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        ps = (_abi.c_double_p * max(k, 1))(*[sh[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_pixels(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_pixels", self._err())
+        sh = _per_atmosphere("run_pixels", "shifts of shape [K][nshift]", shifts, len(atms))
+        out = np.zeros((len(atms), sh.shape[1], getattr(self, "npix", 0), 2))
+        self._call("trx_run_batch_pixels", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
     def set_observed(self, observed):
@@ -514,48 +496,26 @@ class Batch:
     def run_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp] (atmosphere j at its own shifts),
         each atmosphere's moments what Engine.run_moments gives, bit for bit."""
-        k = len(atms)
-        sh = np.ascontiguousarray(shifts, dtype=np.float64)
-        if sh.ndim != 2 or sh.shape[0] != k:
-            raise ValueError("Batch.run_moments: shifts of shape [K][nexp], one row per atmosphere")
-        out = np.zeros((k,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        ps = (_abi.c_double_p * max(k, 1))(*[sh[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_moments", self._err())
+        sh = _per_atmosphere("run_moments", "shifts of shape [K][nexp]", shifts, len(atms))
+        out = np.zeros((len(atms),) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        self._call("trx_run_batch_moments", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
     def run_trail(self, atms, opts: _abi.TrxOpts, lags) -> np.ndarray:
         """trx_run_batch_trail: [K, nlag, nexp, nseg, 7] for lags of shape [K][nlag] (atmosphere j at its own lags), each
         atmosphere's trail what Engine.run_trail gives, bit for bit."""
-        k = len(atms)
-        lg = np.ascontiguousarray(lags, dtype=np.float64)
-        if lg.ndim != 2 or lg.shape[0] != k:
-            raise ValueError("Batch.run_trail: lags of shape [K][nlag], one row per atmosphere")
-        out = np.zeros((k, lg.shape[1]) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        ps = (_abi.c_double_p * max(k, 1))(*[lg[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_trail(self._b, k, arr, C.byref(opts), int(lg.shape[1]), ps, po)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_trail", self._err())
+        lg = _per_atmosphere("run_trail", "lags of shape [K][nlag]", lags, len(atms))
+        out = np.zeros((len(atms), lg.shape[1]) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        self._call("trx_run_batch_trail", atms, opts, int(lg.shape[1]), _rows(lg), _rows(out))
         return out
 
     def run_velocity_map(self, atms, opts: _abi.TrxOpts, vm, per: bool = False):
         """trx_run_batch_velocity_map: the maps [K, nkp, nvsys] of one transit_amd.xcor.VelocityMap for all atmospheres
         -- with per=True, (maps, per [K, nlag, nexp]) --, each atmosphere's what Engine.run_velocity_map gives, bit for
         bit."""
-        k = len(atms)
-        m = np.zeros((k, vm.nkp, vm.nvsys))
-        pr = np.zeros((k, vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        pm = (_abi.c_double_p * max(k, 1))(*[m[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        pp = (_abi.c_double_p * max(k, 1))(*[pr[j].ctypes.data_as(_abi.c_double_p) for j in range(k)]) if per else None
-        rc = self._lib.trx_run_batch_velocity_map(self._b, k, arr, C.byref(opts), C.byref(vm.to_c()), pm, pp)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_velocity_map", self._err())
+        m = np.zeros((len(atms), vm.nkp, vm.nvsys))
+        pr = np.zeros((len(atms), vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
+        self._call("trx_run_batch_velocity_map", atms, opts, C.byref(vm.to_c()), _rows(m), _rows(pr))
         return (m, pr) if per else m
 
     def set_filter(self, filt):
@@ -567,17 +527,9 @@ class Batch:
     def run_filtered_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_filtered_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp], each atmosphere's moments
         what Engine.run_filtered_moments gives, bit for bit."""
-        k = len(atms)
-        sh = np.ascontiguousarray(shifts, dtype=np.float64)
-        if sh.ndim != 2 or sh.shape[0] != k:
-            raise ValueError("Batch.run_filtered_moments: shifts of shape [K][nexp], one row per atmosphere")
-        out = np.zeros((k,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        ps = (_abi.c_double_p * max(k, 1))(*[sh[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_filtered_moments(self._b, k, arr, C.byref(opts), int(sh.shape[1]), ps, po)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_filtered_moments", self._err())
+        sh = _per_atmosphere("run_filtered_moments", "shifts of shape [K][nexp]", shifts, len(atms))
+        out = np.zeros((len(atms),) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        self._call("trx_run_batch_filtered_moments", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
     def set_broadening(self, b):
@@ -593,13 +545,8 @@ class Batch:
     def run_broadened(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
         """trx_run_batch_broadened: [K, nwn], each atmosphere's broadened spectrum what Engine.run_broadened gives with
         that atmosphere's broadening, bit for bit."""
-        k = len(atms)
-        out = np.zeros((k, self.nwn))
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        po = (_abi.c_double_p * max(k, 1))(*[out[j].ctypes.data_as(_abi.c_double_p) for j in range(k)])
-        rc = self._lib.trx_run_batch_broadened(self._b, k, arr, C.byref(opts), po)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_batch_broadened", self._err())
+        out = np.zeros((len(atms), self.nwn))
+        self._call("trx_run_batch_broadened", atms, opts, _rows(out))
         return out
 
     def close(self):
