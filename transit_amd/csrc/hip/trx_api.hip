@@ -49,6 +49,7 @@
 #include "../trx_table.h"
 #include "../trx_broaden.h"
 #include "../trx_vmap.h"
+#include "../trx_products.h"
 
 using namespace trx;
 
@@ -100,8 +101,9 @@ struct FilterSet {
 };
 // a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
 // filt: with the filter between the pairs and the moments (trx_run_filtered_moments); trail: the shifts are the lags of a
-// trail (trx_run_trail) -- every exposure of obs against every one of them (trx_trail.hip.h), never with a filter
-struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; };
+// trail (trx_run_trail) -- every exposure of obs against every one of them (trx_trail.hip.h), never with a filter; ext: the
+// extents of its buffers (../trx_products.h), which pixel_run works out, grows them to and leaves here for the guards and copies
+struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; PixelExtents ext{}; };
 // a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
 // the largest -- which sizes the kernel's tile
 struct Broadening { double beta = 0, limb = 0; int hmax = 0; };
@@ -2693,9 +2695,10 @@ int Run::band_kernels()
   CA.bands = BA.bands; CA.pieces = BA.pieces; CA.w = BA.w; CA.part = h->d_cpart.as<double>(); CA.out = (double *)h->h_contrib.dev;
   CA.npieces = bs->npieces; CA.nbands = bs->nbands; CA.vertical = vertical ? 1 : 0;
   const size_t rows = sizeof(double) * (size_t)nr;
+  const ContribExtents CX = contrib_extents(nr, bs->npieces, bs->nbands);
   if (!CA.E.tau || !CA.E.last || !CA.E.temp || !CA.E.e2tab || !CA.bands || !CA.part || !CA.out || (bs->npieces > 0 && !CA.pieces) ||
       (vertical && (CA.E.nang < 1 || CA.E.nang > kMaxAngles)) || h->d_tau.bytes < rows * (size_t)nsh || h->d_last.bytes < sizeof(int) * (size_t)nsh ||
-      h->d_cpart.bytes < rows * (size_t)bs->npieces * kContribSplit || h->h_contrib.bytes < rows * (size_t)bs->nbands)
+      h->d_cpart.bytes < CX.cpart_bytes || h->h_contrib.bytes < CX.out_bytes)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the contribution kernels (not launched)");
   if (bs->npieces > 0) {
     const dim3 cgrid((unsigned)(bs->npieces * kContribSplit), (unsigned)((nr + kContribHeights - 1) / kContribHeights));
@@ -2719,7 +2722,7 @@ int Run::broaden_kernel()
   // (every address the kernel reads or writes: the spectrum and the broadened one over [0, nwn) = [0, nsh) -- the whole grid,
   // or trx_set_broadening would have refused --, and a tile of at most kBroadBlock + 2 hmax doubles of LDS)
   double d_last;
-  if (!BA.spec || !BA.out || h->windowed() || nsh != h->nwn || h->d_broad.bytes < sizeof(double) * (size_t)nsh ||
+  if (!BA.spec || !BA.out || h->windowed() || nsh != h->nwn || h->d_broad.bytes < broadened_bytes(nsh) ||
       (!d_spectrum && h->d_spec.bytes < sizeof(double) * (size_t)nsh) || !(BA.wn_i > 0) || !(BA.wn_d > 0) || !(BA.beta > 0) ||
       br->hmax < 0 || br->hmax > TRX_BROADEN_MAX_HALF || broaden_half(BA.wn_i, BA.wn_d, BA.beta, BA.nwn - 1, d_last) != (double)br->hmax ||
       blocks < 1 || blocks > 0x7fffffffLL)
@@ -2734,18 +2737,19 @@ int Run::pixel_kernels()
 {
   const PixelRun *const px = want.px;
   if (!px) return TRX_OK;
-  const PixelSet &S = *px->set;
+  const PixelSet &S = *px->set; const PixelExtents &X = px->ext;
   PixArgs PA{};
   PA.spec = want.br ? h->d_broad.as<double>() : d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
   PA.shift = h->d_pixshift.as<double>(); PA.out = h->d_pixout.as<double>();
   PA.npix = S.npix; PA.npairs = S.npix * (int64_t)px->nshift;
   PA.nwn = h->nwn; PA.lo = h->lo; PA.hi = h->hi; PA.cut = S.cut; PA.fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
   PA.wn_i = h->wn_i; PA.wn_d = h->wn_d;
-  const int64_t blocks = (PA.npairs + kPixBlock - 1) / kPixBlock;
-  // (every address the kernel reads or writes: the spectrum over [0, hi - lo) = [0, nsh), the set's arrays, the shifts, the pairs)
-  if (!PA.spec || !PA.centre || !PA.fwhm || !PA.shift || !PA.out || S.npix < 1 || px->nshift < 1 || h->hi - h->lo != nsh ||
+  const int64_t blocks = X.blocks;
+  // (every address the kernel reads or writes: the spectrum over [0, hi - lo) = [0, nsh), the set's arrays, the shifts, the pairs
+  // -- by the extents pixel_run grew the buffers to, which are this launch's: X.pairs)
+  if (!PA.spec || !PA.centre || !PA.fwhm || !PA.shift || !PA.out || S.npix < 1 || px->nshift < 1 || h->hi - h->lo != nsh || X.pairs != PA.npairs ||
       S.d_centre.bytes < sizeof(double) * (size_t)S.npix || S.d_fwhm.bytes < sizeof(double) * (size_t)S.npix ||
-      h->d_pixshift.bytes < sizeof(double) * (size_t)px->nshift || h->d_pixout.bytes < sizeof(double) * 2 * (size_t)PA.npairs ||
+      h->d_pixshift.bytes < X.shift_bytes || h->d_pixout.bytes < X.pair_bytes ||
       blocks < 1 || blocks > 0x7fffffffLL)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the pixel kernel (not launched)");
   hipLaunchKernelGGL(k_pixel_pairs, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
@@ -2758,19 +2762,19 @@ int Run::filter_kernels()
 {
   const PixelRun *const px = want.px;
   if (!px || !px->filt) return TRX_OK;
-  const FilterSet &F = *px->filt;
+  const FilterSet &F = *px->filt; const PixelExtents &X = px->ext;
   const ObservedSet *O = px->obs;
   FilterArgs FA{};
   FA.pairs = h->d_pixout.as<double2>(); FA.gain = O ? O->d_gain.as<double>() : nullptr;
   FA.fwd = F.d_fwd.as<double>(); FA.back = F.d_back.as<double>(); FA.tiles = F.d_tiles.as<FilterTile>(); FA.val = h->d_pixval.as<double>();
   FA.npix = F.npix; FA.ntiles = F.ntiles; FA.nexp = F.nexp;
   const int64_t blocks = (FA.ntiles + kFiltWaves - 1) / kFiltWaves;
-  const size_t cells = sizeof(double) * (size_t)F.nexp * (size_t)F.npix, mat = sizeof(double) * (size_t)F.nseg * (size_t)F.nexp * (size_t)F.npad;
+  const size_t mat = sizeof(double) * (size_t)F.nseg * (size_t)F.nexp * (size_t)F.npad;
   // (every address the kernel reads or writes: pairs and values over [nexp][npix] -- the tiles lie in [0, npix) and name
   // segments below nseg, made so when the filter was --, the gains, the two padded matrices, the tiles)
   if (!O || !FA.pairs || !FA.fwd || !FA.back || !FA.tiles || !FA.val || F.nexp < 1 || F.nseg < 1 || F.ncomp < 1 || F.ncomp > F.npad ||
       (F.npad != 4 && F.npad != 8 && F.npad != 16) || F.npix != px->set->npix || F.nexp != px->nshift || F.npix != O->npix || F.nexp != O->nexp || F.nseg != O->nseg ||
-      h->d_pixout.bytes < 2 * cells || h->d_pixval.bytes < cells || F.d_fwd.bytes < mat || F.d_back.bytes < mat ||
+      X.pairs != (int64_t)F.nexp * F.npix || h->d_pixout.bytes < X.pair_bytes || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes || F.d_fwd.bytes < mat || F.d_back.bytes < mat ||
       (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) || F.d_tiles.bytes < sizeof(FilterTile) * (size_t)F.ntiles ||
       blocks < 1 || blocks > 0x7fffffffLL)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the filter kernel (not launched)");
@@ -2784,7 +2788,7 @@ int Run::filter_kernels()
 // ---- the trail of those pairs -- one shift per LAG -- against every exposure of the observed set (trx_trail.hip.h)
 static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
 {
-  const ObservedSet &O = *px.obs;
+  const ObservedSet &O = *px.obs; const PixelExtents &X = px.ext;
   constexpr int TL = kTrailLags, TV = kTrailExps;
   TrailArgs TA{};
   TA.pairs = h->d_pixout.as<double2>(); TA.data = O.d_data.as<double>(); TA.weight = O.d_weight.as<double>(); TA.gain = O.d_gain.as<double>();
@@ -2793,16 +2797,16 @@ static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
   TA.ntl = (px.nshift + TL - 1) / TL; TA.ntv = (O.nexp + TV - 1) / TV;
   TA.nwaves = (int64_t)O.nseg * TA.ntl * TA.ntv; TA.xcd_map = 1;
   const int64_t blocks = (TA.nwaves + kTrailWaves - 1) / kTrailWaves;
-  const int64_t rows = (int64_t)px.nshift * O.nexp * O.nseg;
+  const int64_t rows = X.rows;
   const size_t cells = sizeof(double) * (size_t)O.nexp * (size_t)O.npix;
   // (every address the kernel reads or writes: the pairs over [nlag][npix], data and weights over [nexp][npix] -- the segments
   // lie in [0, npix), checked when the set was made, and a ragged tile's surplus indices are nlag - 1 and nexp - 1 --, the
   // gains, the segment bounds, the rows of [nlag][nexp][nseg])
   if (!TA.pairs || !TA.data || !TA.seg_first || !TA.trail || px.filt || px.nshift < 1 || O.nexp < 1 || O.nseg < 1 || O.npix < 1 || O.npix != px.set->npix ||
       O.seg.size() != (size_t)O.nseg + 1 || O.seg.front() != 0 || O.seg.back() != O.npix || rows < 1 || rows > 0x7fffffffLL ||
-      h->d_pixout.bytes < sizeof(double) * 2 * (size_t)px.nshift * (size_t)O.npix || O.d_data.bytes < cells || (TA.weight && O.d_weight.bytes < cells) ||
+      X.pairs != (int64_t)px.nshift * O.npix || h->d_pixout.bytes < X.pair_bytes || O.d_data.bytes < cells || (TA.weight && O.d_weight.bytes < cells) ||
       (TA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
-      h->d_trail.bytes < sizeof(double) * TRX_NMOMENT * (size_t)rows || blocks < 1 || blocks > 0x7fffffffLL)
+      X.trail_bytes < 1 || h->d_trail.bytes < X.trail_bytes || blocks < 1 || blocks > 0x7fffffffLL)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the trail kernel (not launched)");
   hipLaunchKernelGGL((k_trail_moments<TL, TV>), dim3((unsigned)blocks), dim3(64 * kTrailWaves), 0, st, TA);
   return TRX_OK;
@@ -2814,7 +2818,7 @@ int Run::moment_kernels()
 {
   const PixelRun *const px = want.px;
   if (!px || !px->obs) return TRX_OK;
-  const ObservedSet &O = *px->obs;
+  const ObservedSet &O = *px->obs; const PixelExtents &X = px->ext;
   if (px->trail) return launch_trail(h, *px, tst);
   MomArgs MA{};
   MA.val = px->filt ? h->d_pixval.as<double>() : nullptr;
@@ -2826,10 +2830,10 @@ int Run::moment_kernels()
   // (every address the kernel reads or writes: pairs, data and weights over [nexp][npix] -- the segments lie in [0, npix),
   // checked when the set was made --, the gains, the segment bounds, the rows)
   if (!MA.pairs || !MA.data || !MA.seg_first || !MA.mom || O.nexp < 1 || O.nseg < 1 || O.npix != px->set->npix || O.nexp != px->nshift ||
-      h->d_pixout.bytes < 2 * cells || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
+      X.pairs != (int64_t)O.nexp * O.npix || h->d_pixout.bytes < X.pair_bytes || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
       (MA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
-      h->d_mom.bytes < sizeof(double) * TRX_NMOMENT * (size_t)MA.nrows || blocks < 1 || blocks > 0x7fffffffLL ||
-      (px->filt && (!MA.val || h->d_pixval.bytes < cells)))
+      X.rows != MA.nrows || h->d_mom.bytes < X.mom_bytes || blocks < 1 || blocks > 0x7fffffffLL ||
+      (px->filt && (!MA.val || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes)))
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the moment kernel (not launched)");
   if (px->filt) hipLaunchKernelGGL(k_pixel_moments<true>, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
   else hipLaunchKernelGGL(k_pixel_moments<false>, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
@@ -3063,65 +3067,33 @@ int trx_run_device(trx_handle *h, const trx_atm *a, const trx_opts *o, void *d_s
   return run_once(h, a, o, nullptr, d_spectrum, dbg, Products{});
 }
 
+// ---- the run products: their checks, layouts and extents are ../trx_products.h's; here they meet the handle and the device
+// what that header's checks need to know of h
+static ProductState product_state(const trx_handle *h)
+{
+  ProductState S;
+  S.windowed = h->windowed(); S.wn_i = h->wn_i; S.wn_d = h->wn_d; S.nwn = h->nwn; S.lo = h->lo; S.hi = h->hi;
+  if (h->pixels) S.npix = h->pixels->npix;
+  if (h->observed) { S.nexp = h->observed->nexp; S.nseg = h->observed->nseg; S.seg = h->observed->seg.data(); }
+  S.filter = h->filter != nullptr;
+  return S;
+}
+
 // ---- band integrals (trx_bands.hip.h) -------------------------------------------------------------
-// The set as h's shard sees it, checked whole before anything is replaced: ranges on the host in double
-// (the header's rule), each band's in-shard bins cut into pieces of kBandPiece from its first in-shard bin.
+// The set as h's shard sees it (band_layout), checked whole before anything is replaced.
 static int make_band_set(trx_handle *h, int32_t nbands, const trx_band *bands, std::unique_ptr<BandSet> &out)
 {
   out.reset();
-  if (nbands < 0) return fail(h, TRX_E_ARG, "bands: nbands < 0");
-  if (nbands > 0 && !bands) return fail(h, TRX_E_ARG, "bands: NULL band array");
-  const int64_t nwn = h->nwn, lo = h->lo, hi = h->hi;
-  std::vector<BandDev> bd((size_t)nbands);
-  std::vector<BandPiece> pieces;
-  std::vector<double> w;
-  const double fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
-  for (int32_t b = 0; b < nbands; b++) {
-    const trx_band &B = bands[b];
-    const std::string name = "band " + std::to_string(b) + ": ";
-    BandDev &D = bd[(size_t)b];
-    D.kind = B.kind;
-    int64_t first = 0, last = 0;                         // [first, last) of the whole grid
-    if (B.kind == TRX_BAND_WEIGHTS) {
-      if (B.n < 1) return fail(h, TRX_E_ARG, name + "n < 1");
-      if (B.first < 0) return fail(h, TRX_E_ARG, name + "first < 0");
-      if (B.first > nwn - B.n) return fail(h, TRX_E_ARG, name + "first + n > nwn");
-      if (!B.weights) return fail(h, TRX_E_ARG, name + "NULL weights");
-      for (int64_t k = 0; k < B.n; k++)
-        if (!std::isfinite(B.weights[k])) return fail(h, TRX_E_ARG, name + "weight " + std::to_string(k) + " is not finite");
-      first = B.first; last = B.first + B.n;
-    } else if (B.kind == TRX_BAND_GAUSS) {
-      if (!std::isfinite(B.centre) || !std::isfinite(B.fwhm) || !std::isfinite(B.cut))
-        return fail(h, TRX_E_ARG, name + "centre, fwhm and cut must be finite");
-      if (!(B.fwhm > 0)) return fail(h, TRX_E_ARG, name + "fwhm <= 0");
-      if (!(B.cut > 0)) return fail(h, TRX_E_ARG, name + "cut <= 0");
-      D.centre = B.centre; D.sigma = B.fwhm / fwhm_sigma;
-      const double a = std::ceil((B.centre - B.cut * D.sigma - h->wn_i) / h->wn_d);
-      const double z = std::floor((B.centre + B.cut * D.sigma - h->wn_i) / h->wn_d) + 1.0;
-      // (clipped to [0, nwn] in double: no conversion of a value out of int64's range)
-      first = a <= 0 ? 0 : a >= (double)nwn ? nwn : (int64_t)a;
-      last = z <= 0 ? 0 : z >= (double)nwn ? nwn : (int64_t)z;
-      last = std::max(first, last);
-    } else return fail(h, TRX_E_ARG, name + "unknown kind " + std::to_string(B.kind));
-    const int64_t s = std::max(first, lo), e = std::min(last, hi);
-    D.s = s - lo; D.piece0 = (int64_t)pieces.size(); D.npieces = 0; D.woff = (int64_t)w.size();
-    if (e <= s) { D.s = 0; continue; }                   // no bin in this shard: (0, 0)
-    if (B.kind == TRX_BAND_WEIGHTS) w.insert(w.end(), B.weights + (s - first), B.weights + (e - first));
-    for (int64_t q = s; q < e; q += kBandPiece) {
-      BandPiece P{};
-      P.start = q - lo; P.band = b; P.len = (int32_t)std::min<int64_t>(kBandPiece, e - q);
-      pieces.push_back(P);
-    }
-    D.npieces = (int64_t)pieces.size() - D.piece0;
-  }
+  std::string msg; BandLayout L;
+  if (const int rc = band_layout(product_state(h), nbands, bands, L, msg)) return fail(h, rc, msg);
   if (nbands == 0) return TRX_OK;                       // (clear)
   std::unique_ptr<BandSet> S(new (std::nothrow) BandSet);
   if (!S) return fail(h, TRX_E_NOMEM, "bands: out of host memory");
-  S->nbands = nbands; S->npieces = (int64_t)pieces.size();
+  S->nbands = nbands; S->npieces = (int64_t)L.pieces.size();
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
-  if ((rc = upload_raw(h, S->d_bands, bd.data(), bd.size())) || (rc = upload_raw(h, S->d_pieces, pieces.data(), pieces.size())) ||
-      (rc = upload_raw(h, S->d_w, w.data(), w.size())) || (rc = ensure(h, S->d_part, sizeof(double) * 2 * (size_t)S->npieces)) ||
+  if ((rc = upload(h, S->d_bands, L.bands)) || (rc = upload(h, S->d_pieces, L.pieces)) ||
+      (rc = upload(h, S->d_w, L.w)) || (rc = ensure(h, S->d_part, sizeof(double) * 2 * (size_t)S->npieces)) ||
       (rc = ensure_pinned(h, S->h_out, sizeof(double) * 2 * (size_t)nbands)))
     return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
@@ -3161,15 +3133,15 @@ int trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   if (!a || !o) return TRX_E_ARG;
   if (a->nlayer < 1) return fail(h, TRX_E_ARG, "trx_run_contrib: nlayer < 1");
   const BandSet *bs = h->bands.get();
-  const size_t nr = (size_t)a->nlayer, out_bytes = sizeof(double) * nr * (size_t)bs->nbands;
+  const ContribExtents X = contrib_extents(a->nlayer, bs->npieces, bs->nbands);
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
-  if ((rc = ensure(h, h->d_cpart, sizeof(double) * nr * (size_t)bs->npieces * kContribSplit)) || (rc = ensure_pinned(h, h->h_contrib, out_bytes))) return rc;
+  if ((rc = ensure(h, h->d_cpart, X.cpart_bytes)) || (rc = ensure_pinned(h, h->h_contrib, X.out_bytes))) return rc;
   Products want; want.bs = bs; want.contrib = true;
   rc = run_once(h, a, o, spectrum, nullptr, dbg, want);
   if (rc == TRX_OK) {
     std::memcpy(sums, bs->h_out.p, sizeof(double) * 2 * (size_t)bs->nbands);
-    std::memcpy(contrib, h->h_contrib.p, out_bytes);
+    std::memcpy(contrib, h->h_contrib.p, X.out_bytes);
   }
   return rc;
 }
@@ -3180,14 +3152,8 @@ static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<P
 {
   out.reset();
   if (!px || px->npix == 0) return TRX_OK;              // (clear)
-  if (px->npix < 0) return fail(h, TRX_E_ARG, "pixels: npix < 0");
-  if (!px->centre || !px->fwhm) return fail(h, TRX_E_ARG, "pixels: NULL centre or fwhm array");
-  if (!std::isfinite(px->cut) || !(px->cut > 0)) return fail(h, TRX_E_ARG, "pixels: cut must be finite and > 0");
-  if (px->npix > 0x7fffffffLL) return fail(h, TRX_E_ARG, "pixels: npix above 2^31 - 1");
-  for (int64_t p = 0; p < px->npix; p++) {
-    if (!std::isfinite(px->centre[p]) || !(px->centre[p] > 0)) return fail(h, TRX_E_ARG, "pixel " + std::to_string(p) + ": centre must be finite and > 0");
-    if (!std::isfinite(px->fwhm[p]) || !(px->fwhm[p] > 0)) return fail(h, TRX_E_ARG, "pixel " + std::to_string(p) + ": fwhm must be finite and > 0");
-  }
+  std::string msg;
+  if (const int rc = pixel_set_checks(px, msg)) return fail(h, rc, msg);
   std::unique_ptr<PixelSet> S(new (std::nothrow) PixelSet);
   if (!S) return fail(h, TRX_E_NOMEM, "pixels: out of host memory");
   S->npix = px->npix; S->cut = px->cut;
@@ -3214,24 +3180,20 @@ int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 
 // the pixel run PR for `who` (trx_run_pixels; PR.obs: trx_run_moments; PR.filt: trx_run_filtered_moments; PR.trail: trx_run_trail,
 // the shifts its lags) at PR.nshift shifts: the pairs are in h->d_pixout, the moments in h->d_mom, the filtered values in
-// h->d_pixval, the trail in h->d_trail, when it returns
-static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, const PixelRun &PR, const double *shift,
+// h->d_pixval, the trail in h->d_trail, when it returns -- each over its extent in PR.ext
+static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, PixelRun &PR, const double *shift,
                      trx_debug *dbg)
 {
-  const std::string w(who);
-  const int32_t nshift = PR.nshift; const ObservedSet *const obs = PR.obs;
-  for (int32_t v = 0; v < nshift; v++)
-    if (!std::isfinite(shift[v]) || !(shift[v] > 0)) return fail(h, TRX_E_ARG, w + ": shift " + std::to_string(v) + " must be finite and > 0");
-  if ((int64_t)nshift * PR.set->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, w + ": nshift * npix above what one launch takes");
+  std::string msg;
+  if (const int rc = pixel_run_checks(who, PR.nshift, PR.set->npix, shift, msg)) return fail(h, rc, msg);
+  const PixelExtents &X = PR.ext = pixel_extents(PR.set->npix, PR.nshift, PR.obs ? PR.obs->nexp : 0, PR.obs ? PR.obs->nseg : 0, PR.filt != nullptr, PR.trail);
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
-  if ((rc = ensure(h, h->d_pixout, sizeof(double) * 2 * (size_t)nshift * (size_t)PR.set->npix)) ||
-      (obs && !PR.trail && (rc = ensure(h, h->d_mom, sizeof(double) * TRX_NMOMENT * (size_t)obs->nexp * (size_t)obs->nseg))) ||
-      (obs && PR.trail && (rc = ensure(h, h->d_trail, sizeof(double) * TRX_NMOMENT * (size_t)nshift * (size_t)obs->nexp * (size_t)obs->nseg))) ||
-      (PR.filt && (rc = ensure(h, h->d_pixval, sizeof(double) * (size_t)nshift * (size_t)PR.set->npix))) ||
-      (h->broad_on && (rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn))) ||
-      (rc = upload_raw(h, h->d_pixshift, shift, (size_t)nshift)))
+  if ((rc = ensure(h, h->d_pixout, X.pair_bytes)) || (X.mom_bytes && (rc = ensure(h, h->d_mom, X.mom_bytes))) ||
+      (X.trail_bytes && (rc = ensure(h, h->d_trail, X.trail_bytes))) || (X.val_bytes && (rc = ensure(h, h->d_pixval, X.val_bytes))) ||
+      (h->broad_on && (rc = ensure(h, h->d_broad, broadened_bytes(h->nwn)))) ||
+      (rc = upload_raw(h, h->d_pixshift, shift, (size_t)PR.nshift)))
     return rc;
   // (with a broadening installed the pixels sample the broadened spectrum)
   Products want; want.px = &PR; if (h->broad_on) want.br = &h->broad;
@@ -3246,8 +3208,9 @@ int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *s
   if (nshift < 1) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift < 1");
   if (!shift) return fail(h, TRX_E_ARG, "trx_run_pixels: shift is NULL");
   if (!out) return fail(h, TRX_E_ARG, "trx_run_pixels: out is NULL");
-  if (const int rc = pixel_run(h, "trx_run_pixels", a, o, spectrum, PixelRun{h->pixels.get(), nshift}, shift, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, sizeof(double) * 2 * (size_t)nshift * (size_t)h->pixels->npix, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  PixelRun PR{h->pixels.get(), nshift};
+  if (const int rc = pixel_run(h, "trx_run_pixels", a, o, spectrum, PR, shift, dbg)) return rc;
+  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, PR.ext.pair_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
@@ -3257,25 +3220,10 @@ static int make_observed_set(trx_handle *h, const trx_observed *ob, std::unique_
 {
   out.reset();
   if (!ob || ob->nexp == 0) return TRX_OK;              // (clear)
-  if (!h->pixels) return fail(h, TRX_E_ARG, "observed: no pixel set installed (trx_set_pixels)");
+  std::string msg;
+  if (const int rc = observed_set_checks(product_state(h), ob, msg)) return fail(h, rc, msg);
   const int64_t npix = h->pixels->npix;
-  if (ob->nexp < 0) return fail(h, TRX_E_ARG, "observed: nexp < 0");
-  if (ob->nseg < 1) return fail(h, TRX_E_ARG, "observed: nseg < 1");
-  if (!ob->seg_first || !ob->data) return fail(h, TRX_E_ARG, "observed: NULL seg_first or data array");
-  if (ob->seg_first[0] != 0) return fail(h, TRX_E_ARG, "observed: seg_first[0] must be 0");
-  for (int32_t s = 0; s < ob->nseg; s++)
-    if (ob->seg_first[s + 1] < ob->seg_first[s]) return fail(h, TRX_E_ARG, "observed: seg_first decreases at segment " + std::to_string(s));
-  if (ob->seg_first[ob->nseg] != npix) return fail(h, TRX_E_ARG, "observed: seg_first[nseg] must be the pixel set's npix (" + std::to_string(npix) + ")");
-  if ((int64_t)ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, "observed: nexp * nseg above 2^31 - 1");
-  auto where = [npix](size_t k) { return "exposure " + std::to_string(k / (size_t)npix) + " pixel " + std::to_string(k % (size_t)npix); };
   const size_t cells = (size_t)ob->nexp * (size_t)npix;
-  for (size_t k = 0; k < cells; k++) {
-    if (!std::isfinite(ob->data[k])) return fail(h, TRX_E_ARG, "observed: " + where(k) + ": datum must be finite");
-    if (ob->weight && (!std::isfinite(ob->weight[k]) || !(ob->weight[k] >= 0))) return fail(h, TRX_E_ARG, "observed: " + where(k) + ": weight must be finite and >= 0");
-  }
-  if (ob->gain)
-    for (int64_t p = 0; p < npix; p++)
-      if (!std::isfinite(ob->gain[p])) return fail(h, TRX_E_ARG, "observed: pixel " + std::to_string(p) + ": gain must be finite");
   std::unique_ptr<ObservedSet> S(new (std::nothrow) ObservedSet);
   if (!S) return fail(h, TRX_E_NOMEM, "observed: out of host memory");
   S->nexp = ob->nexp; S->nseg = ob->nseg; S->npix = npix;
@@ -3299,95 +3247,56 @@ int trx_set_observed(trx_handle *h, const trx_observed *ob)
   return TRX_OK;
 }
 
-// What a run against the observed set refuses for `who`, in this order: a shard of the grid, no observed set, (Filtered) no
-// filter, the count -- one shift per exposure, or (Trail) at least one lag --, the NULL arrays: in (named shift, or lag) and
-// out (named out_name).
-enum class ObservedRun { Moments, Filtered, Trail };
-static int observed_run_checks(trx_handle *h, const std::string &who, ObservedRun kind, int32_t n, const void *in, const void *out, const char *out_name)
-{
-  const bool lags = kind == ObservedRun::Trail;
-  // (the moments are not linear in the pairs: the partial pairs of a shard say nothing about them -- nor about the filtered
-  // values' live flags)
-  if (h->windowed())
-    return fail(h, TRX_E_UNSUPPORTED, who + ": this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs (trx_gather_host) and " +
-                                      (kind == ObservedRun::Filtered ? "filter and reduce" : "reduce") + " them on the host");
-  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, who + ": no observed set installed (trx_set_observed)");
-  if (kind == ObservedRun::Filtered && !h->filter) return fail(h, TRX_E_ARG, who + ": no filter installed (trx_set_filter)");
-  const int32_t nexp = h->observed->nexp;
-  if (lags && n < 1) return fail(h, TRX_E_ARG, who + ": nlag < 1");
-  if (!lags && n != nexp) return fail(h, TRX_E_ARG, who + ": nshift " + std::to_string(n) + " is not the observed set's nexp " + std::to_string(nexp));
-  if (!in) return fail(h, TRX_E_ARG, who + ": " + (lags ? "lag" : "shift") + " is NULL");
-  if (!out) return fail(h, TRX_E_ARG, who + ": " + out_name + " is NULL");
-  return TRX_OK;
-}
-
 int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
                     double *mom, trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  if (const int rc = observed_run_checks(h, "trx_run_moments", ObservedRun::Moments, nshift, shift, mom, "mom")) return rc;
-  const ObservedSet *ob = h->observed.get();
-  if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, PixelRun{h->pixels.get(), nshift, ob}, shift, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  std::string msg;
+  if (const int rc = observed_run_checks(product_state(h), "trx_run_moments", ObservedRun::Moments, nshift, shift, mom, "mom", msg)) return fail(h, rc, msg);
+  PixelRun PR{h->pixels.get(), nshift, h->observed.get()};
+  if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, PR, shift, dbg)) return rc;
+  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
 // ---- the cross-correlation trail: every exposure against every lag of a grid (trx_trail.hip.h) -----
-// what a trail run refuses, for `who` (trx_run_trail, trx_run_velocity_map); out: where its result goes, named out_name
-static int trail_run_checks(trx_handle *h, const std::string &who, int32_t nlag, const double *lag, const void *out, const char *out_name)
-{
-  if (const int rc = observed_run_checks(h, who, ObservedRun::Trail, nlag, lag, out, out_name)) return rc;
-  const ObservedSet *ob = h->observed.get();
-  // (the counts first: a refused nlag is not an extent to read lag[] over)
-  if ((int64_t)nlag * ob->npix > 0x7fffffffLL * kPixBlock) return fail(h, TRX_E_ARG, who + ": nlag * npix above what one pixel launch takes");
-  if ((int64_t)nlag * ob->nexp * ob->nseg > 0x7fffffffLL) return fail(h, TRX_E_ARG, who + ": nlag * nexp * nseg above 2^31 - 1");
-  for (int32_t l = 0; l < nlag; l++)
-    if (!std::isfinite(lag[l]) || !(lag[l] > 0)) return fail(h, TRX_E_ARG, who + ": lag " + std::to_string(l) + " must be finite and > 0");
-  return TRX_OK;
-}
-
 int trx_run_trail(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nlag, const double *lag,
                   double *trail, trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  if (const int rc = trail_run_checks(h, "trx_run_trail", nlag, lag, trail, "trail")) return rc;
-  const ObservedSet *ob = h->observed.get();
+  std::string msg;
+  if (const int rc = trail_run_checks(product_state(h), "trx_run_trail", nlag, lag, trail, "trail", msg)) return fail(h, rc, msg);
   // (an installed filter takes no part: it couples the exposures, and a trail's model is the same at all of them)
-  PixelRun PR{h->pixels.get(), nlag, ob}; PR.trail = true;
+  PixelRun PR{h->pixels.get(), nlag, h->observed.get()}; PR.trail = true;
   if (const int rc = pixel_run(h, "trx_run_trail", a, o, spectrum, PR, lag, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(trail, h->d_trail.p, sizeof(double) * TRX_NMOMENT * (size_t)nlag * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  HIPCHK(h, hipMemcpy(trail, h->d_trail.p, PR.ext.trail_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
 // ---- the Kp-Vsys map of that trail, reduced on the device (trx_vmap.hip.h) --------------------------
-// what a map run refuses on top of a trail run's refusals, for `who`
-static int velocity_map_checks(trx_handle *h, const std::string &who, const trx_vmap *vm, const void *map)
+// the statistic of PR's trail (in h->d_trail, the run waited for) and the map of it, behind the upload of the call's arrays
+// on the main queue: X their extents, the arrays at X.at_* of h->d_vm_in
+static int launch_velocity_map(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const VmapExtents &X)
 {
-  if (!vm) return fail(h, TRX_E_ARG, who + ": vm is NULL");
-  if (const int rc = trail_run_checks(h, who, vm->nlag, vm->lag, map, "map")) return rc;
-  const int32_t nexp = h->observed->nexp;
-  if (vm->stat != TRX_STAT_CCF && vm->stat != TRX_STAT_LOGLIKE_BL19 && vm->stat != TRX_STAT_CHI2)
-    return fail(h, TRX_E_ARG, who + ": unknown stat " + std::to_string(vm->stat));
-  if (vm->nkp < 1 || vm->nvsys < 1) return fail(h, TRX_E_ARG, who + ": nkp < 1 or nvsys < 1");
-  if ((int64_t)vm->nkp * vm->nvsys > 0x7fffffffLL) return fail(h, TRX_E_ARG, who + ": nkp * nvsys above 2^31 - 1");
-  if (!vm->lag_kms) return fail(h, TRX_E_ARG, who + ": lag_kms is NULL");
-  if (!vm->kp) return fail(h, TRX_E_ARG, who + ": kp is NULL");
-  if (!vm->vsys) return fail(h, TRX_E_ARG, who + ": vsys is NULL");
-  if (!vm->orbit) return fail(h, TRX_E_ARG, who + ": orbit is NULL");
-  if (!std::isfinite(vm->p0)) return fail(h, TRX_E_ARG, who + ": p0 must be finite");
-  if (!std::isfinite(vm->p1)) return fail(h, TRX_E_ARG, who + ": p1 must be finite");
-  auto finite = [&](const char *name, const double *x, int32_t n) {
-    for (int32_t k = 0; k < n; k++)
-      if (!std::isfinite(x[k])) return fail(h, TRX_E_ARG, who + ": " + name + " " + std::to_string(k) + " must be finite");
-    return (int)TRX_OK;
-  };
-  int rc;
-  if ((rc = finite("kp", vm->kp, vm->nkp)) || (rc = finite("vsys", vm->vsys, vm->nvsys)) || (rc = finite("orbit", vm->orbit, nexp)) ||
-      (vm->offset && (rc = finite("offset", vm->offset, nexp))))
-    return rc;
-  for (int32_t l = 0; l < vm->nlag; l++)
-    if (!std::isfinite(vm->lag_kms[l]) || (l > 0 && !(vm->lag_kms[l] > vm->lag_kms[l - 1])))
-      return fail(h, TRX_E_ARG, who + ": lag_kms " + std::to_string(l) + " must be finite and above the one before it (strictly increasing)");
+  const ObservedSet *ob = PR.obs;
+  const double *in = h->d_vm_in.as<double>();
+  TrailStatArgs SA{};
+  SA.trail = h->d_trail.as<double>(); SA.per_lv = h->d_vm_per.as<double>(); SA.per_vl = SA.per_lv + X.rows;
+  SA.nrows = (int64_t)X.rows; SA.nlag = vm->nlag; SA.nexp = ob->nexp; SA.nseg = ob->nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
+  VelMapArgs MA{};
+  MA.per_vl = SA.per_vl; MA.lag_kms = in; MA.kp = in + X.at_kp; MA.vsys = in + X.at_vsys; MA.orbit = in + X.at_orbit; MA.offset = vm->offset ? in + X.at_offset : nullptr;
+  MA.map = h->d_vm_map.as<double>(); MA.ncells = (int64_t)X.cells; MA.nlag = vm->nlag; MA.nexp = ob->nexp; MA.nvsys = vm->nvsys;
+  const int64_t sblocks = (SA.nrows + kVmapWaves - 1) / kVmapWaves, mblocks = (MA.ncells + kVmapWaves - 1) / kVmapWaves;
+  // (every address the kernels read or write: the trail rows [nlag][nexp][nseg], the statistic twice over [nlag][nexp], the
+  // call's arrays -- a cell's lag indices lie in [0, nlag - 1], vmap_locate --, the cells)
+  if (!SA.trail || !SA.per_lv || !in || !MA.map || X.rows < 1 || X.cells < 1 || ob->nseg < 1 ||
+      PR.ext.rows != SA.nrows * ob->nseg || h->d_trail.bytes < PR.ext.trail_bytes || h->d_vm_per.bytes < X.per2_bytes ||
+      h->d_vm_in.bytes < X.in_bytes || h->d_vm_map.bytes < X.map_bytes ||
+      sblocks < 1 || sblocks > 0x7fffffffLL || mblocks < 1 || mblocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the map kernels (not launched)");
+  hipLaunchKernelGGL(k_trail_stat, dim3((unsigned)sblocks), dim3(64 * kVmapWaves), 0, h->stream, SA);
+  hipLaunchKernelGGL(k_velocity_map, dim3((unsigned)mblocks), dim3(64 * kVmapWaves), 0, h->stream, MA);
+  HIPCHK(h, hipGetLastError());
   return TRX_OK;
 }
 
@@ -3395,96 +3304,41 @@ int trx_run_velocity_map(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
                          trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  const std::string who("trx_run_velocity_map");
-  if (const int rc = velocity_map_checks(h, who, vm, map)) return rc;
-  const ObservedSet *ob = h->observed.get();
-  const size_t nlag = (size_t)vm->nlag, nexp = (size_t)ob->nexp, nkp = (size_t)vm->nkp, nvsys = (size_t)vm->nvsys;
-  // the call's arrays end to end, as the device gets them
-  const size_t at_kp = nlag, at_vsys = at_kp + nkp, at_orbit = at_vsys + nvsys, at_offset = at_orbit + nexp, nin = at_offset + (vm->offset ? nexp : 0);
-  try {
-    h->vm_in.resize(nin);
-  } catch (...) { return fail(h, TRX_E_NOMEM, who + ": out of host memory"); }
-  std::copy(vm->lag_kms, vm->lag_kms + nlag, h->vm_in.begin());
-  std::copy(vm->kp, vm->kp + nkp, h->vm_in.begin() + (std::ptrdiff_t)at_kp);
-  std::copy(vm->vsys, vm->vsys + nvsys, h->vm_in.begin() + (std::ptrdiff_t)at_vsys);
-  std::copy(vm->orbit, vm->orbit + nexp, h->vm_in.begin() + (std::ptrdiff_t)at_orbit);
-  if (vm->offset) std::copy(vm->offset, vm->offset + nexp, h->vm_in.begin() + (std::ptrdiff_t)at_offset);
+  const char *const who = "trx_run_velocity_map";
+  std::string msg;
+  if (const int rc = velocity_map_checks(product_state(h), who, vm, map, msg)) return fail(h, rc, msg);
+  const VmapExtents X = vmap_extents(*vm, h->observed->nexp);
+  if (const int rc = vmap_pack(who, *vm, X, h->vm_in, msg)) return fail(h, rc, msg);
   // the trail of the lags into d_trail, as trx_run_trail leaves it; it stays there
-  PixelRun PR{h->pixels.get(), vm->nlag, ob}; PR.trail = true;
-  if (const int rc = pixel_run(h, who.c_str(), a, o, spectrum, PR, vm->lag, dbg)) return rc;
-  const size_t rows = nlag * nexp, cells = nkp * nvsys;
+  PixelRun PR{h->pixels.get(), vm->nlag, h->observed.get()}; PR.trail = true;
+  if (const int rc = pixel_run(h, who, a, o, spectrum, PR, vm->lag, dbg)) return rc;
   int rc;
-  if ((rc = ensure(h, h->d_vm_per, sizeof(double) * 2 * rows)) || (rc = ensure(h, h->d_vm_map, sizeof(double) * cells)) ||
-      (rc = upload_raw(h, h->d_vm_in, h->vm_in.data(), nin)))
-    return rc;
   // (the run has been waited for: the two kernels follow the upload on the main queue)
-  const double *in = h->d_vm_in.as<double>();
-  TrailStatArgs SA{};
-  SA.trail = h->d_trail.as<double>(); SA.per_lv = h->d_vm_per.as<double>(); SA.per_vl = SA.per_lv + rows;
-  SA.nrows = (int64_t)rows; SA.nlag = vm->nlag; SA.nexp = ob->nexp; SA.nseg = ob->nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
-  VelMapArgs MA{};
-  MA.per_vl = SA.per_vl; MA.lag_kms = in; MA.kp = in + at_kp; MA.vsys = in + at_vsys; MA.orbit = in + at_orbit; MA.offset = vm->offset ? in + at_offset : nullptr;
-  MA.map = h->d_vm_map.as<double>(); MA.ncells = (int64_t)cells; MA.nlag = vm->nlag; MA.nexp = ob->nexp; MA.nvsys = vm->nvsys;
-  const int64_t sblocks = (SA.nrows + kVmapWaves - 1) / kVmapWaves, mblocks = (MA.ncells + kVmapWaves - 1) / kVmapWaves;
-  // (every address the kernels read or write: the trail rows [nlag][nexp][nseg], the statistic twice over [nlag][nexp], the
-  // call's arrays -- a cell's lag indices lie in [0, nlag - 1], vmap_locate --, the cells)
-  if (!SA.trail || !SA.per_lv || !in || !MA.map || rows < 1 || cells < 1 || ob->nseg < 1 ||
-      h->d_trail.bytes < sizeof(double) * TRX_NMOMENT * rows * (size_t)ob->nseg || h->d_vm_per.bytes < sizeof(double) * 2 * rows ||
-      h->d_vm_in.bytes < sizeof(double) * nin || h->d_vm_map.bytes < sizeof(double) * cells ||
-      sblocks < 1 || sblocks > 0x7fffffffLL || mblocks < 1 || mblocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the map kernels (not launched)");
-  hipLaunchKernelGGL(k_trail_stat, dim3((unsigned)sblocks), dim3(64 * kVmapWaves), 0, h->stream, SA);
-  hipLaunchKernelGGL(k_velocity_map, dim3((unsigned)mblocks), dim3(64 * kVmapWaves), 0, h->stream, MA);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(map, h->d_vm_map.p, sizeof(double) * cells, hipMemcpyDeviceToHost, h->stream));
-  if (per) HIPCHK(h, hipMemcpyAsync(per, h->d_vm_per.p, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = ensure(h, h->d_vm_per, X.per2_bytes)) || (rc = ensure(h, h->d_vm_map, X.map_bytes)) || (rc = upload(h, h->d_vm_in, h->vm_in)) ||
+      (rc = launch_velocity_map(h, PR, vm, X)))
+    return rc;
+  HIPCHK(h, hipMemcpyAsync(map, h->d_vm_map.p, X.map_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (per) HIPCHK(h, hipMemcpyAsync(per, h->d_vm_per.p, X.per_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return TRX_OK;
 }
 
 // ---- the detrending filter between the pairs and the moments (trx_filter.hip.h) ---------------------
-// The filter, checked whole before anything is replaced.  The device gets the two matrices exposure-major and zero-padded
-// to the kernel's 4, 8 or 16 components, and the tiles of the observed set's segments: up to 64 consecutive pixels of one
-// segment each, a segment's tiles in pixel order.
+// The filter, checked whole before anything is replaced; the device gets filter_layout's matrices and tiles.
 static int make_filter_set(trx_handle *h, const trx_filter *f, std::unique_ptr<FilterSet> &out)
 {
   out.reset();
   if (!f || f->ncomp == 0) return TRX_OK;               // (clear)
-  if (!h->pixels || !h->observed) return fail(h, TRX_E_ARG, "filter: no observed set installed (trx_set_observed)");
-  const ObservedSet &O = *h->observed;
-  if (f->ncomp < 0) return fail(h, TRX_E_ARG, "filter: ncomp < 0");
-  if (f->ncomp > TRX_FILTER_MAX) return fail(h, TRX_E_ARG, "filter: ncomp above TRX_FILTER_MAX (" + std::to_string(TRX_FILTER_MAX) + ")");
-  if (!f->fwd || !f->back) return fail(h, TRX_E_ARG, "filter: NULL fwd or back array");
-  const size_t nc = (size_t)f->ncomp, ne = (size_t)O.nexp, per = nc * ne;
-  for (int32_t s = 0; s < O.nseg; s++)
-    for (size_t k = 0; k < per; k++) {
-      if (!std::isfinite(f->fwd[(size_t)s * per + k])) return fail(h, TRX_E_ARG, "filter: segment " + std::to_string(s) + ": fwd entry must be finite");
-      if (!std::isfinite(f->back[(size_t)s * per + k])) return fail(h, TRX_E_ARG, "filter: segment " + std::to_string(s) + ": back entry must be finite");
-    }
+  const ProductState P = product_state(h);
+  std::string msg; FilterLayout L;
+  if (const int rc = filter_set_checks(P, f, msg)) return fail(h, rc, msg);
   std::unique_ptr<FilterSet> S(new (std::nothrow) FilterSet);
   if (!S) return fail(h, TRX_E_NOMEM, "filter: out of host memory");
-  S->ncomp = f->ncomp; S->npad = f->ncomp <= 4 ? 4 : f->ncomp <= 8 ? 8 : 16;
-  S->nexp = O.nexp; S->nseg = O.nseg; S->npix = O.npix;
-  std::vector<double> fw, bk; std::vector<FilterTile> tiles;
-  try {
-    const size_t np = (size_t)S->npad;
-    fw.assign((size_t)O.nseg * ne * np, 0.0); bk.assign((size_t)O.nseg * ne * np, 0.0);
-    for (size_t s = 0; s < (size_t)O.nseg; s++)
-      for (size_t v = 0; v < ne; v++)
-        for (size_t j = 0; j < nc; j++) {
-          fw[(s * ne + v) * np + j] = f->fwd[(s * nc + j) * ne + v];
-          bk[(s * ne + v) * np + j] = f->back[(s * ne + v) * nc + j];
-        }
-    for (int32_t s = 0; s < O.nseg; s++)
-      for (int64_t p = O.seg[(size_t)s]; p < O.seg[(size_t)s + 1]; p += 64)
-        tiles.push_back(FilterTile{p, s, (int32_t)std::min<int64_t>(64, O.seg[(size_t)s + 1] - p)});
-  } catch (...) { return fail(h, TRX_E_NOMEM, "filter: out of host memory"); }
-  S->ntiles = (int64_t)tiles.size();
+  if (const int rc = filter_layout(P, f, L, msg)) return fail(h, rc, msg);
+  S->ncomp = f->ncomp; S->npad = L.npad; S->nexp = P.nexp; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size();
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
-  if ((rc = upload_raw(h, S->d_fwd, fw.data(), fw.size())) || (rc = upload_raw(h, S->d_back, bk.data(), bk.size())) ||
-      (rc = upload_raw(h, S->d_tiles, tiles.data(), tiles.size())))
-    return rc;
+  if ((rc = upload(h, S->d_fwd, L.fwd)) || (rc = upload(h, S->d_back, L.back)) || (rc = upload(h, S->d_tiles, L.tiles))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
   out = std::move(S);
   return TRX_OK;
@@ -3505,12 +3359,13 @@ int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
                              double *values, double *mom, trx_debug *dbg)
 {
   if (!h) return TRX_E_ARG;
-  if (const int rc = observed_run_checks(h, "trx_run_filtered_moments", ObservedRun::Filtered, nshift, shift, mom, "mom")) return rc;
-  const ObservedSet *ob = h->observed.get();
-  if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, PixelRun{h->pixels.get(), nshift, ob, h->filter.get()}, shift, dbg)) return rc;
+  std::string msg;
+  if (const int rc = observed_run_checks(product_state(h), "trx_run_filtered_moments", ObservedRun::Filtered, nshift, shift, mom, "mom", msg)) return fail(h, rc, msg);
+  PixelRun PR{h->pixels.get(), nshift, h->observed.get(), h->filter.get()};
+  if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, PR, shift, dbg)) return rc;
   // (the run has been waited for)
-  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, sizeof(double) * TRX_NMOMENT * (size_t)ob->nexp * (size_t)ob->nseg, hipMemcpyDeviceToHost));
-  if (values) HIPCHK(h, hipMemcpy(values, h->d_pixval.p, sizeof(double) * (size_t)ob->nexp * (size_t)ob->npix, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));
+  if (values) HIPCHK(h, hipMemcpy(values, h->d_pixval.p, PR.ext.val_bytes, hipMemcpyDeviceToHost));
   return TRX_OK;
 }
 
@@ -3520,20 +3375,9 @@ static int make_broadening(trx_handle *h, const trx_broadening *br, bool &on, Br
 {
   on = false; out = Broadening{};
   if (!br || br->kind == TRX_BROADEN_NONE) return TRX_OK;      // (clear)
-  if (br->kind != TRX_BROADEN_ROTATION) return fail(h, TRX_E_ARG, "broadening: unknown kind " + std::to_string(br->kind));
-  if (!std::isfinite(br->beta) || !(br->beta > 0)) return fail(h, TRX_E_ARG, "broadening: beta must be finite and > 0");
-  if (!std::isfinite(br->limb) || !(br->limb >= 0) || !(br->limb <= 1)) return fail(h, TRX_E_ARG, "broadening: limb must be finite and in [0, 1]");
-  if (!(h->wn_i > 0) || !(h->wn_d > 0)) return fail(h, TRX_E_ARG, "broadening: the handle's grid needs wn_i > 0 and wn_d > 0");
-  // (the window needs neighbours across the shard's edge)
-  if (h->windowed())
-    return fail(h, TRX_E_UNSUPPORTED, "broadening: this handle's shard is not the whole grid; gather the spectrum (trx_gather_host) and broaden it on the host");
-  double d;
-  const double half = broaden_half(h->wn_i, h->wn_d, br->beta, h->nwn - 1, d);
-  if (!(half <= (double)TRX_BROADEN_MAX_HALF)) {
-    char b[160]; std::snprintf(b, sizeof b, "broadening: half-width of %.0f bins at the grid's last bin is above TRX_BROADEN_MAX_HALF (%d)", half, TRX_BROADEN_MAX_HALF);
-    return fail(h, TRX_E_ARG, b);
-  }
-  on = true; out.beta = br->beta; out.limb = br->limb; out.hmax = (int)half;
+  std::string msg; int hmax = 0;
+  if (const int rc = broadening_checks(product_state(h), br, hmax, msg)) return fail(h, rc, msg);
+  on = true; out.beta = br->beta; out.limb = br->limb; out.hmax = hmax;
   return TRX_OK;
 }
 
@@ -3552,10 +3396,10 @@ int trx_run_broadened(trx_handle *h, const trx_atm *a, const trx_opts *o, double
   if (!h->broad_on) return fail(h, TRX_E_ARG, "trx_run_broadened: no broadening installed (trx_set_broadening)");
   if (!broadened) return fail(h, TRX_E_ARG, "trx_run_broadened: broadened is NULL");
   HIPCHK(h, hipSetDevice(h->device));
-  if (const int rc = ensure(h, h->d_broad, sizeof(double) * (size_t)h->nwn)) return rc;
+  if (const int rc = ensure(h, h->d_broad, broadened_bytes(h->nwn))) return rc;
   Products want; want.br = &h->broad;
   if (const int rc = run_once(h, a, o, spectrum, nullptr, dbg, want)) return rc;
-  HIPCHK(h, hipMemcpy(broadened, h->d_broad.p, sizeof(double) * (size_t)h->nwn, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  HIPCHK(h, hipMemcpy(broadened, h->d_broad.p, broadened_bytes(h->nwn), hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
@@ -3687,17 +3531,6 @@ static int batch_call(trx_batch *b, int32_t k, bool wants_broadening, const Batc
   return b->rc;
 }
 
-// a NULL row among the k rows of the arrays named: by atmosphere, then in the order given (an array that is NULL itself is
-// an optional one the caller left out)
-struct BatchRows { const char *name; const double *const *rows; };
-static int batch_rows_check(const char *who, int32_t k, std::initializer_list<BatchRows> arrays)
-{
-  for (int32_t j = 0; j < k; j++)
-    for (const BatchRows &A : arrays)
-      if (A.rows && !A.rows[j]) { g_comm_err = std::string(who) + ": " + A.name + "[" + std::to_string(j) + "] is NULL"; return TRX_E_ARG; }
-  return TRX_OK;
-}
-
 int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra)
 {
   g_comm_err.clear();
@@ -3716,7 +3549,7 @@ int trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm, const trx_o
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums))) { g_comm_err = "trx_run_batch_bands: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_bands: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_bands", k, {{"sums", sums}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_bands", k, {{"sums", sums}}, g_comm_err)) return rc;
   return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run_bands(h, atm + j, opts, nullptr, sums[j], nullptr); });
 }
 
@@ -3725,7 +3558,7 @@ int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums || !contrib))) { g_comm_err = "trx_run_batch_contrib: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_contrib: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_contrib", k, {{"sums", sums}, {"contrib", contrib}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_contrib", k, {{"sums", sums}, {"contrib", contrib}}, g_comm_err)) return rc;
   return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run_contrib(h, atm + j, opts, nullptr, sums[j], contrib[j], nullptr); });
 }
 
@@ -3763,7 +3596,7 @@ int trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm, const t
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !broadened))) { g_comm_err = "trx_run_batch_broadened: bad argument"; return TRX_E_ARG; }
   if (b->broad.empty()) { g_comm_err = "trx_run_batch_broadened: no broadening installed (trx_batch_set_broadening)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_broadened", k, {{"broadened", broadened}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_broadened", k, {{"broadened", broadened}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_broadened")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_broadened(h, atm + j, opts, nullptr, broadened[j], nullptr); });
 }
@@ -3780,7 +3613,7 @@ int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !out))) { g_comm_err = "trx_run_batch_pixels: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->pixels) { g_comm_err = "trx_run_batch_pixels: no pixel set installed (trx_batch_set_pixels)"; return TRX_E_ARG; }
   if (nshift < 1) { g_comm_err = "trx_run_batch_pixels: nshift < 1"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_pixels", k, {{"shift", shift}, {"out", out}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_pixels", k, {{"shift", shift}, {"out", out}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_pixels")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_pixels(h, atm + j, opts, nullptr, nshift, shift[j], out[j], nullptr); });
 }
@@ -3796,7 +3629,7 @@ int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_moments: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_moments", k, {{"shift", shift}, {"mom", mom}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_moments")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_moments(h, atm + j, opts, nullptr, nshift, shift[j], mom[j], nullptr); });
 }
@@ -3808,7 +3641,7 @@ int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_o
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !lag || !trail))) { g_comm_err = "trx_run_batch_trail: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_trail: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
   if (nlag < 1) { g_comm_err = "trx_run_batch_trail: nlag < 1"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_trail", k, {{"lag", lag}, {"trail", trail}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_trail", k, {{"lag", lag}, {"trail", trail}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_trail")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_trail(h, atm + j, opts, nullptr, nlag, lag[j], trail[j], nullptr); });
 }
@@ -3819,10 +3652,10 @@ int trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm, cons
   g_comm_err.clear();
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = "trx_run_batch_velocity_map: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_velocity_map: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_velocity_map", k, {{"map", map}, {"per", per}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_velocity_map", k, {{"map", map}, {"per", per}}, g_comm_err)) return rc;
   // (the handles are made from one description and carry one observed set: what the first refuses, all refuse)
   if (k > 0)
-    if (const int rc = velocity_map_checks(b->hs[0], "trx_run_batch_velocity_map", vm, map[0])) { g_comm_err = b->hs[0]->err; return rc; }
+    if (const int rc = velocity_map_checks(product_state(b->hs[0]), "trx_run_batch_velocity_map", vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_velocity_map")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_velocity_map(h, atm + j, opts, nullptr, vm, map[j], per ? per[j] : nullptr, nullptr); });
 }
@@ -3839,7 +3672,7 @@ int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, 
   if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_filtered_moments: bad argument"; return TRX_E_ARG; }
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_filtered_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
   if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_moments: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_filtered_moments", k, {{"shift", shift}, {"mom", mom}})) return rc;
+  if (const int rc = batch_rows_check("trx_run_batch_filtered_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_moments")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_moments(h, atm + j, opts, nullptr, nshift, shift[j], nullptr, mom[j], nullptr); });
 }

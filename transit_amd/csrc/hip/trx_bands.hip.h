@@ -21,22 +21,9 @@
 
 namespace trx {
 
-constexpr int kBandLaneBins = 16;                     // bins per lane of a piece
-constexpr int kBandPiece = 64 * kBandLaneBins;        // bins per piece
 constexpr int kBandWaves = 4;                         // waves per block of both kernels
 
-// one band as a shard sees it (trx_set_bands builds it on the host)
-struct BandDev {
-  int32_t kind, pad;        // TRX_BAND_WEIGHTS / TRX_BAND_GAUSS
-  int64_t s;                // first in-shard bin, local to the shard
-  int64_t woff;             // WEIGHTS: index of that bin's weight in BandArgs::w
-  int64_t piece0, npieces;  // its pieces: piece0 .. piece0 + npieces - 1 (none: no bin in the shard)
-  double centre, sigma;     // GAUSS: cm-1
-};
-struct BandPiece {
-  int64_t start;            // local bin of the piece's first bin
-  int32_t band, len;        // 1 <= len <= kBandPiece
-};
+// (kBandLaneBins, kBandPiece, BandDev, BandPiece: trx_device.h)
 struct BandArgs {
   const double *spec;       // [nsh] the run's spectrum (device)
   const BandDev *bands;     // [nbands]

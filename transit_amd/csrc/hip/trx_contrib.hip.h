@@ -34,9 +34,7 @@
 
 namespace trx {
 
-constexpr int kContribWaves = 4;                                  // waves per block: one bin per lane
-constexpr int kContribSplit = kBandPiece / (64 * kContribWaves);  // sub-pieces (blocks) per piece
-constexpr int kContribHeights = 16;                               // heights per block
+constexpr int kContribHeights = 16;                               // heights per block (kContribWaves, kContribSplit: trx_device.h)
 
 struct ContribArgs {
   EmisArgs E;               // eclipse: angles, area weights, temperatures, e2tab; both: nr, nsh, lo, grid, tau, last

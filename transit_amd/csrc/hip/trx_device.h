@@ -177,4 +177,32 @@ struct alignas(16) WalkProfile {
   int32_t ps;                        // half-width in table samples
 };
 
+// ---- the run products: what their host layouts (../trx_products.h) share with the kernels ----
+// (trx_bands.hip.h)
+constexpr int kBandLaneBins = 16;                     // bins per lane of a piece
+constexpr int kBandPiece = 64 * kBandLaneBins;        // bins per piece
+
+// one band as a shard sees it (trx_set_bands builds it on the host)
+struct BandDev {
+  int32_t kind, pad;        // TRX_BAND_WEIGHTS / TRX_BAND_GAUSS
+  int64_t s;                // first in-shard bin, local to the shard
+  int64_t woff;             // WEIGHTS: index of that bin's weight in BandArgs::w
+  int64_t piece0, npieces;  // its pieces: piece0 .. piece0 + npieces - 1 (none: no bin in the shard)
+  double centre, sigma;     // GAUSS: cm-1
+};
+struct BandPiece {
+  int64_t start;            // local bin of the piece's first bin
+  int32_t band, len;        // 1 <= len <= kBandPiece
+};
+
+// (trx_contrib.hip.h)
+constexpr int kContribWaves = 4;                                  // waves per block: one bin per lane
+constexpr int kContribSplit = kBandPiece / (64 * kContribWaves);  // sub-pieces (blocks) per piece
+
+// (trx_pixels.hip.h)
+constexpr int kPixBlock = 256;                        // lanes (pairs) per block: whole waves
+
+// (trx_filter.hip.h)
+struct FilterTile { int64_t first; int32_t seg, count; };      // pixels [first, first + count) of segment seg, 1 <= count <= 64
+
 }  // namespace trx

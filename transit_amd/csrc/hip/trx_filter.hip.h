@@ -30,13 +30,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "transit_hip.h"
+#include "trx_device.h"
 
 namespace trx {
 
 constexpr int kFiltWaves = 4;                         // tiles (waves) per block
 constexpr int kFiltTrips = 4;                         // exposures whose loads a wave has in flight at once
-
-struct FilterTile { int64_t first; int32_t seg, count; };      // pixels [first, first + count) of segment seg, 1 <= count <= 64
 
 struct FilterArgs {
   const double2 *pairs;     // [nexp][npix] (a, b): d_pixout of this run

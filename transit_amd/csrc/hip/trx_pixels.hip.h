@@ -26,7 +26,7 @@
 
 namespace trx {
 
-constexpr int kPixBlock = 256;                        // lanes (pairs) per block: whole waves
+// (kPixBlock, the lanes (pairs) per block: trx_device.h)
 constexpr int kPixWaveFrom = 192;                     // in-shard window length from which the wave adds a pair
 
 struct PixArgs {
