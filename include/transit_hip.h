@@ -691,6 +691,61 @@ int  trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm /* [
                                 const trx_vmap *vm /* one for all */, double *const *map /* [k] -> [nkp][nvsys] */,
                                 double *const *per /* NULL, or [k] -> [nlag][nexp] */);
 
+/* The high-pass of the model pixels along each order, on the device, between the pixels and everything that reads them.
+ * Observed exposures are continuum-normalised before they are compared with a model: per spectral order a smooth
+ * function along the PIXEL axis -- in practice a running Gaussian or boxcar mean -- is taken out, and the model has to
+ * go through the same high-pass, or its broadband slope biases every statistic (the moments remove a weighted mean per
+ * order only).  With it installed the chain spectrum -> broadening -> pixels -> high-pass -> filter -> moments / trail /
+ * map stays on the device.
+ *
+ * A high-pass belongs to the observed set it is installed over; the segments are that set's.  It is a symmetric tap
+ * table taps[0 .. half]: every tap finite and >= 0, taps[0] > 0, taps[k] the weight at a distance of k pixels,
+ * 0 <= half <= TRX_HIGHPASS_MAX_HALF.  For a row r (a shift, or a lag of a trail), segment s = [first, last) and pixel
+ * p in it, with (a, b) the pair trx_run_pixels gives for that row and pixel:
+ *   live_q = b[r][q] > 0
+ *   g_q    = gain_q * (a[r][q] / b[r][q])            (gain 1 without a gain array)
+ *   num_p  = sum of taps[|k|] * g_{p+k}
+ *   den_p  = sum of taps[|k|]
+ *   g'_p   = g_p - num_p / den_p
+ *   - both sums run over k = -half .. +half IN THAT ORDER and start from +0; a term whose q = p + k lies outside
+ *     [first, last) or is not live is skipped;
+ *   - every product, sum, the division and the subtraction are rounded once (no fused multiply-add);
+ *   - a pixel that is not live is DEAD: quiet NaN in values, and nothing downstream counts it;
+ *   - a non-finite g propagates as IEEE arithmetic gives; den_p >= taps[0] > 0 for a live p;
+ *   - half = 0 gives g' = g - (t g) / t: +0 at every live pixel when taps[0] is a power of two (1 in a Gaussian or a
+ *     boxcar table), for which the product and the quotient are exact.
+ * Only + - * / and no atomics: the bits of a value depend on its row's pairs over its window, the gains and the taps --
+ * not on other rows or segments, the launch, the batch way that ran it or the handle's depth hint.
+ *
+ * trx_set_highpass copies the taps (hp NULL or hp->taps NULL: clear it).  It returns TRX_E_ARG, the reason in
+ * trx_last_error, with no observed set installed, half < 0 or above TRX_HIGHPASS_MAX_HALF, a non-finite or negative
+ * tap (naming "tap N"), taps[0] not above 0; a refused one leaves the previous high-pass in force.  A successful
+ * trx_set_observed (a clearing one included) or trx_set_pixels drops it, as they drop the filter; it is independent of
+ * the broadening and of the filter.
+ * trx_run_highpassed is trx_run_pixels plus the high-pass, for any nshift >= 1 (rows are independent): spectrum may be
+ * NULL, and when it is given it holds the bits trx_run gives; values[r][p] = g'_p of row r, NaN where dead.  TRX_E_ARG
+ * with no observed set or no high-pass installed, nshift < 1, shift or values NULL, a non-finite or <= 0 shift (naming
+ * "shift N"), nshift * npix above what one pixel launch takes; TRX_E_UNSUPPORTED on a handle whose shard is not the
+ * whole grid, for trx_run_moments' reason.  A run that fails leaves values undefined.
+ * WITH A HIGH-PASS INSTALLED trx_run_moments, trx_run_filtered_moments, trx_run_trail and trx_run_velocity_map (and
+ * their batch forms) take g' where they took g and skip the dead pixels: the same kernels, the same order of every sum,
+ * so trail[l] stays bit for bit trx_run_moments with all shifts equal to lag[l] on the same handle.  trx_run,
+ * trx_run_bands, trx_run_contrib, trx_run_pixels, trx_run_broadened and trx_sweep_permol are unchanged bit for bit, as
+ * is every run on a handle without a high-pass.
+ * trx_batch_set_highpass installs the same high-pass on every handle of the batch, or on none (its reason through
+ * trx_last_error(NULL)). */
+#define TRX_HIGHPASS_MAX_HALF 1024
+typedef struct {
+  int32_t half, pad;         /* taps[0 .. half]; pad is ignored                                              */
+  const double *taps;        /* [half + 1] finite, >= 0, taps[0] > 0                                         */
+} trx_highpass;
+int  trx_set_highpass(trx_handle *h, const trx_highpass *hp);
+int  trx_run_highpassed(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                        double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                        int32_t nshift, const double *shift /* [nshift] */,
+                        double *values /* [nshift][npix], host; NaN = dead */, trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

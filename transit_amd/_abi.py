@@ -102,6 +102,13 @@ class TrxFilter(C.Structure):
     _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("fwd", c_double_p), ("back", c_double_p)]
 
 
+HIGHPASS_MAX_HALF = 1024
+
+
+class TrxHighpass(C.Structure):
+    _fields_ = [("half", C.c_int32), ("pad", C.c_int32), ("taps", c_double_p)]
+
+
 STAT_CCF, STAT_LOGLIKE_BL19, STAT_CHI2 = 1, 2, 3
 
 
@@ -254,6 +261,18 @@ def bind_filter_api(lib):
     lib.trx_run_batch_filtered_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                                    C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_filtered_moments.restype = C.c_int
+    return lib
+
+
+def bind_highpass_api(lib):
+    """argtypes/restypes of the high-pass entry points (trx_set_highpass, trx_run_highpassed, trx_batch_set_highpass)."""
+    lib.trx_set_highpass.argtypes = [C.c_void_p, C.POINTER(TrxHighpass)]
+    lib.trx_set_highpass.restype = C.c_int
+    lib.trx_run_highpassed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32,
+                                       c_double_p, c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_highpassed.restype = C.c_int
+    lib.trx_batch_set_highpass.argtypes = [C.c_void_p, C.POINTER(TrxHighpass)]
+    lib.trx_batch_set_highpass.restype = C.c_int
     return lib
 
 

@@ -42,6 +42,7 @@
 #include "trx_trail.hip.h"
 #include "trx_vmap.hip.h"
 #include "trx_filter.hip.h"
+#include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
@@ -99,11 +100,22 @@ struct FilterSet {
   int32_t ncomp = 0, npad = 0, nexp = 0, nseg = 0; int64_t npix = 0, ntiles = 0;
   DevBuf d_fwd, d_back, d_tiles;                     // [nseg][nexp][npad] each, FilterTile[ntiles]
 };
+// a high-pass installed by trx_set_highpass over the observed set (trx_highpass.hip.h): the taps, their full-window sum and
+// the tiles of the observed set's segments; obs: that set (it goes when the set does), whose gains the kernel reads
+struct HighPassSet {
+  int32_t half = 0, nseg = 0; int64_t npix = 0, ntiles = 0; double den_full = 0; const ObservedSet *obs = nullptr;
+  DevBuf d_taps, d_tiles;                            // [half + 1], HpTile[ntiles]
+};
 // a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
 // filt: with the filter between the pairs and the moments (trx_run_filtered_moments); trail: the shifts are the lags of a
 // trail (trx_run_trail) -- every exposure of obs against every one of them (trx_trail.hip.h), never with a filter; ext: the
-// extents of its buffers (../trx_products.h), which pixel_run works out, grows them to and leaves here for the guards and copies
-struct PixelRun { const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; PixelExtents ext{}; };
+// extents of its buffers (../trx_products.h), which pixel_run works out, grows them to and leaves here for the guards and copies;
+// hp: with the high-pass between the pairs and whatever reads them (pixel_run sets it for every run with obs on a handle that
+// has one; trx_run_highpassed itself), hpx the extents of that
+struct PixelRun {
+  const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; PixelExtents ext{};
+  const HighPassSet *hp = nullptr; HighpassExtents hpx{};
+};
 // a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
 // the largest -- which sizes the kernel's tile
 struct Broadening { double beta = 0, limb = 0; int hmax = 0; };
@@ -250,6 +262,10 @@ struct trx_handle {
   DevBuf d_vm_in, d_vm_per, d_vm_map; std::vector<double> vm_in;
   std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
   DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
+  std::unique_ptr<HighPassSet> highpass;               // trx_set_highpass (null: none); belongs to `observed`
+  // the high-passed pairs [nshift][npix][2] of a run with a high-pass, (g', 1) or (0, 0), grown on demand: what the filter, the
+  // moments and the trail then read in place of d_pixout; trx_run_highpassed copies them to h_pixhp whole
+  DevBuf d_pixhp; PinnedBuf h_pixhp;
   bool broad_on = false; Broadening broad;             // trx_set_broadening (broad_on false: none); independent of the sets above
   DevBuf d_broad;                                      // the broadened spectrum [nwn] of a broadened or pixel run, grown on demand
 };
@@ -2076,7 +2092,7 @@ struct Run {
   // ... the spectrum of what they swept, the way back
   int spectrum_kernel(); int ray_tail(); int results();
   // ... and what the run makes of that spectrum (want), behind it on its queue
-  int product_kernels(); int band_kernels(); int broaden_kernel(); int pixel_kernels(); int filter_kernels(); int moment_kernels();
+  int product_kernels(); int band_kernels(); int broaden_kernel(); int pixel_kernels(); int highpass_kernels(); int filter_kernels(); int moment_kernels();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2756,6 +2772,33 @@ int Run::pixel_kernels()
   return TRX_OK;
 }
 
+// ---- the high-pass of those pairs along the pixel axis (trx_highpass.hip.h), behind the pixel kernel on its queue and ahead
+// of the filter, the moments and the trail, which then read d_pixhp; a pass that resumes deeper queues it again.
+int Run::highpass_kernels()
+{
+  const PixelRun *const px = want.px;
+  if (!px || !px->hp) return TRX_OK;
+  const HighPassSet &F = *px->hp; const PixelExtents &X = px->ext; const HighpassExtents &HX = px->hpx;
+  const ObservedSet *O = F.obs;
+  HpArgs HA{};
+  HA.pairs = h->d_pixout.as<double2>(); HA.gain = O ? O->d_gain.as<double>() : nullptr; HA.taps = F.d_taps.as<double>();
+  HA.tiles = F.d_tiles.as<HpTile>(); HA.out = h->d_pixhp.as<double2>();
+  HA.npix = F.npix; HA.ntiles = F.ntiles; HA.den_full = F.den_full; HA.half = F.half;
+  const HighpassExtents want_x = highpass_extents(F.npix, px->nshift, F.ntiles, F.half);
+  // (every address the kernel reads or writes: pairs in and out over [nshift][npix] -- the tiles lie in [0, npix) within their
+  // segments' bounds, made so from the observed set's when the high-pass was --, the gains, the taps [half + 1], the tiles,
+  // and (count + 2 half) * 2 doubles of LDS, count <= kHpTile)
+  if (!O || O != h->observed.get() || (px->obs && px->obs != O) || !HA.pairs || !HA.taps || !HA.tiles || !HA.out || F.half < 0 || F.half > TRX_HIGHPASS_MAX_HALF ||
+      F.npix < 1 || F.npix != px->set->npix || F.npix != O->npix || F.nseg != O->nseg || px->nshift < 1 || F.ntiles < 1 ||
+      X.pairs != (int64_t)px->nshift * F.npix || HX.pairs != X.pairs || HX.blocks != want_x.blocks || HX.pair_bytes != want_x.pair_bytes || HX.lds_bytes != want_x.lds_bytes ||
+      h->d_pixout.bytes < X.pair_bytes || h->d_pixhp.bytes < HX.pair_bytes || (HA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) ||
+      F.d_taps.bytes < sizeof(double) * ((size_t)F.half + 1) || F.d_tiles.bytes < sizeof(HpTile) * (size_t)F.ntiles ||
+      HX.lds_bytes > 65536 || HX.blocks < 1 || HX.blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the high-pass kernel (not launched)");
+  hipLaunchKernelGGL(k_pixel_highpass, dim3((unsigned)HX.blocks), dim3(kHpBlock), HX.lds_bytes, tst, HA);
+  return TRX_OK;
+}
+
 // ---- the filter of those pairs along the exposure axis (trx_filter.hip.h), behind the pixel kernel on its queue and
 // ahead of the moment kernel, which then reads its values; a pass that resumes deeper queues all three again.
 int Run::filter_kernels()
@@ -2765,7 +2808,8 @@ int Run::filter_kernels()
   const FilterSet &F = *px->filt; const PixelExtents &X = px->ext;
   const ObservedSet *O = px->obs;
   FilterArgs FA{};
-  FA.pairs = h->d_pixout.as<double2>(); FA.gain = O ? O->d_gain.as<double>() : nullptr;
+  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
+  FA.pairs = px->hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = O && !px->hp ? O->d_gain.as<double>() : nullptr;
   FA.fwd = F.d_fwd.as<double>(); FA.back = F.d_back.as<double>(); FA.tiles = F.d_tiles.as<FilterTile>(); FA.val = h->d_pixval.as<double>();
   FA.npix = F.npix; FA.ntiles = F.ntiles; FA.nexp = F.nexp;
   const int64_t blocks = (FA.ntiles + kFiltWaves - 1) / kFiltWaves;
@@ -2774,7 +2818,7 @@ int Run::filter_kernels()
   // segments below nseg, made so when the filter was --, the gains, the two padded matrices, the tiles)
   if (!O || !FA.pairs || !FA.fwd || !FA.back || !FA.tiles || !FA.val || F.nexp < 1 || F.nseg < 1 || F.ncomp < 1 || F.ncomp > F.npad ||
       (F.npad != 4 && F.npad != 8 && F.npad != 16) || F.npix != px->set->npix || F.nexp != px->nshift || F.npix != O->npix || F.nexp != O->nexp || F.nseg != O->nseg ||
-      X.pairs != (int64_t)F.nexp * F.npix || h->d_pixout.bytes < X.pair_bytes || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes || F.d_fwd.bytes < mat || F.d_back.bytes < mat ||
+      X.pairs != (int64_t)F.nexp * F.npix || h->d_pixout.bytes < X.pair_bytes || (px->hp && (px->hpx.pairs != X.pairs || h->d_pixhp.bytes < px->hpx.pair_bytes)) || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes || F.d_fwd.bytes < mat || F.d_back.bytes < mat ||
       (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) || F.d_tiles.bytes < sizeof(FilterTile) * (size_t)F.ntiles ||
       blocks < 1 || blocks > 0x7fffffffLL)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the filter kernel (not launched)");
@@ -2791,7 +2835,9 @@ static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
   const ObservedSet &O = *px.obs; const PixelExtents &X = px.ext;
   constexpr int TL = kTrailLags, TV = kTrailExps;
   TrailArgs TA{};
-  TA.pairs = h->d_pixout.as<double2>(); TA.data = O.d_data.as<double>(); TA.weight = O.d_weight.as<double>(); TA.gain = O.d_gain.as<double>();
+  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
+  TA.pairs = px.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); TA.gain = px.hp ? nullptr : O.d_gain.as<double>();
+  TA.data = O.d_data.as<double>(); TA.weight = O.d_weight.as<double>();
   TA.seg_first = O.d_seg.as<int64_t>(); TA.trail = h->d_trail.as<double>();
   TA.npix = O.npix; TA.nlag = px.nshift; TA.nexp = O.nexp; TA.nseg = O.nseg;
   TA.ntl = (px.nshift + TL - 1) / TL; TA.ntv = (O.nexp + TV - 1) / TV;
@@ -2804,7 +2850,7 @@ static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
   // gains, the segment bounds, the rows of [nlag][nexp][nseg])
   if (!TA.pairs || !TA.data || !TA.seg_first || !TA.trail || px.filt || px.nshift < 1 || O.nexp < 1 || O.nseg < 1 || O.npix < 1 || O.npix != px.set->npix ||
       O.seg.size() != (size_t)O.nseg + 1 || O.seg.front() != 0 || O.seg.back() != O.npix || rows < 1 || rows > 0x7fffffffLL ||
-      X.pairs != (int64_t)px.nshift * O.npix || h->d_pixout.bytes < X.pair_bytes || O.d_data.bytes < cells || (TA.weight && O.d_weight.bytes < cells) ||
+      X.pairs != (int64_t)px.nshift * O.npix || h->d_pixout.bytes < X.pair_bytes || (px.hp && (px.hpx.pairs != X.pairs || h->d_pixhp.bytes < px.hpx.pair_bytes)) || O.d_data.bytes < cells || (TA.weight && O.d_weight.bytes < cells) ||
       (TA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
       X.trail_bytes < 1 || h->d_trail.bytes < X.trail_bytes || blocks < 1 || blocks > 0x7fffffffLL)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the trail kernel (not launched)");
@@ -2822,7 +2868,9 @@ int Run::moment_kernels()
   if (px->trail) return launch_trail(h, *px, tst);
   MomArgs MA{};
   MA.val = px->filt ? h->d_pixval.as<double>() : nullptr;
-  MA.pairs = h->d_pixout.as<double2>(); MA.data = O.d_data.as<double>(); MA.weight = O.d_weight.as<double>(); MA.gain = O.d_gain.as<double>();
+  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
+  MA.pairs = px->hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); MA.gain = px->hp ? nullptr : O.d_gain.as<double>();
+  MA.data = O.d_data.as<double>(); MA.weight = O.d_weight.as<double>();
   MA.seg_first = O.d_seg.as<int64_t>(); MA.mom = h->d_mom.as<double>();
   MA.npix = O.npix; MA.nseg = O.nseg; MA.nrows = (int64_t)O.nexp * O.nseg;
   const int64_t blocks = (MA.nrows + kMomWaves - 1) / kMomWaves;
@@ -2830,7 +2878,7 @@ int Run::moment_kernels()
   // (every address the kernel reads or writes: pairs, data and weights over [nexp][npix] -- the segments lie in [0, npix),
   // checked when the set was made --, the gains, the segment bounds, the rows)
   if (!MA.pairs || !MA.data || !MA.seg_first || !MA.mom || O.nexp < 1 || O.nseg < 1 || O.npix != px->set->npix || O.nexp != px->nshift ||
-      X.pairs != (int64_t)O.nexp * O.npix || h->d_pixout.bytes < X.pair_bytes || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
+      X.pairs != (int64_t)O.nexp * O.npix || h->d_pixout.bytes < X.pair_bytes || (px->hp && (px->hpx.pairs != X.pairs || h->d_pixhp.bytes < px->hpx.pair_bytes)) || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
       (MA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
       X.rows != MA.nrows || h->d_mom.bytes < X.mom_bytes || blocks < 1 || blocks > 0x7fffffffLL ||
       (px->filt && (!MA.val || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes)))
@@ -2876,11 +2924,12 @@ int Run::results()
 
 // ---- what the run makes of this pass's spectrum (want), all of it on the spectrum's queue.  The order is a dependency:
 // the bands and contributions read the spectrum and the optical depths only, but the broadening writes d_broad, which the
-// pixels then sample; the filter reads the pixels' pairs; the moments (or the trail) read the pairs or the filter's values.
+// pixels then sample; the high-pass reads the pixels' pairs and writes its own, which stand in for them from there on; the
+// filter reads the pairs; the moments (or the trail) read the pairs or the filter's values.
 int Run::product_kernels()
 {
   int rc;
-  return (rc = band_kernels()) || (rc = broaden_kernel()) || (rc = pixel_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : TRX_OK;
+  return (rc = band_kernels()) || (rc = broaden_kernel()) || (rc = pixel_kernels()) || (rc = highpass_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : TRX_OK;
 }
 
 // ---- one pass: the planned steps (h->run_plan) from r_top down, the spectrum of what they swept, its way back
@@ -3075,7 +3124,7 @@ static ProductState product_state(const trx_handle *h)
   S.windowed = h->windowed(); S.wn_i = h->wn_i; S.wn_d = h->wn_d; S.nwn = h->nwn; S.lo = h->lo; S.hi = h->hi;
   if (h->pixels) S.npix = h->pixels->npix;
   if (h->observed) { S.nexp = h->observed->nexp; S.nseg = h->observed->nseg; S.seg = h->observed->seg.data(); }
-  S.filter = h->filter != nullptr;
+  S.filter = h->filter != nullptr; S.highpass = h->highpass != nullptr;
   return S;
 }
 
@@ -3165,9 +3214,10 @@ static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<P
   return TRX_OK;
 }
 
-// (the observed set belongs to the pixel set it was installed over, the filter to the observed set: they go with it)
-static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); }
-static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->observed = std::move(S); h->filter.reset(); }
+// (the observed set belongs to the pixel set it was installed over, the filter and the high-pass to the observed set: they go
+// with it -- the high-pass first, which points into the observed set)
+static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->highpass.reset(); h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); }
+static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->highpass.reset(); h->observed = std::move(S); h->filter.reset(); }
 
 int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 {
@@ -3179,19 +3229,24 @@ int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 }
 
 // the pixel run PR for `who` (trx_run_pixels; PR.obs: trx_run_moments; PR.filt: trx_run_filtered_moments; PR.trail: trx_run_trail,
-// the shifts its lags) at PR.nshift shifts: the pairs are in h->d_pixout, the moments in h->d_mom, the filtered values in
-// h->d_pixval, the trail in h->d_trail, when it returns -- each over its extent in PR.ext
+// the shifts its lags; PR.hp: trx_run_highpassed) at PR.nshift shifts: the pairs are in h->d_pixout, the moments in h->d_mom,
+// the filtered values in h->d_pixval, the trail in h->d_trail, when it returns -- each over its extent in PR.ext --, the
+// high-passed pairs (a run with PR.hp, given or taken from the handle here) in h->d_pixhp over PR.hpx
 static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, PixelRun &PR, const double *shift,
                      trx_debug *dbg)
 {
   std::string msg;
   if (const int rc = pixel_run_checks(who, PR.nshift, PR.set->npix, shift, msg)) return fail(h, rc, msg);
   const PixelExtents &X = PR.ext = pixel_extents(PR.set->npix, PR.nshift, PR.obs ? PR.obs->nexp : 0, PR.obs ? PR.obs->nseg : 0, PR.filt != nullptr, PR.trail);
+  // (every run against the observed set takes the high-pass installed over it)
+  if (PR.obs && h->highpass) PR.hp = h->highpass.get();
+  if (PR.hp) PR.hpx = highpass_extents(PR.hp->npix, PR.nshift, PR.hp->ntiles, PR.hp->half);
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
   if ((rc = ensure(h, h->d_pixout, X.pair_bytes)) || (X.mom_bytes && (rc = ensure(h, h->d_mom, X.mom_bytes))) ||
       (X.trail_bytes && (rc = ensure(h, h->d_trail, X.trail_bytes))) || (X.val_bytes && (rc = ensure(h, h->d_pixval, X.val_bytes))) ||
+      (PR.hp && (rc = ensure(h, h->d_pixhp, PR.hpx.pair_bytes))) ||
       (h->broad_on && (rc = ensure(h, h->d_broad, broadened_bytes(h->nwn)))) ||
       (rc = upload_raw(h, h->d_pixshift, shift, (size_t)PR.nshift)))
     return rc;
@@ -3366,6 +3421,56 @@ int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
   // (the run has been waited for)
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));
   if (values) HIPCHK(h, hipMemcpy(values, h->d_pixval.p, PR.ext.val_bytes, hipMemcpyDeviceToHost));
+  return TRX_OK;
+}
+
+// ---- the high-pass between the pairs and whatever reads them (trx_highpass.hip.h) -------------------
+// The high-pass, checked whole before anything is replaced; the device gets highpass_layout's taps and tiles.
+static int make_highpass_set(trx_handle *h, const trx_highpass *hp, std::unique_ptr<HighPassSet> &out)
+{
+  out.reset();
+  if (!hp || !hp->taps) return TRX_OK;                  // (clear)
+  const ProductState P = product_state(h);
+  std::string msg; HighpassLayout L;
+  if (const int rc = highpass_set_checks(P, hp, msg)) return fail(h, rc, msg);
+  std::unique_ptr<HighPassSet> S(new (std::nothrow) HighPassSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "highpass: out of host memory");
+  if (const int rc = highpass_layout(P, hp, L, msg)) return fail(h, rc, msg);
+  S->half = L.half; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size(); S->den_full = L.den_full; S->obs = h->observed.get();
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload(h, S->d_taps, L.taps)) || (rc = upload(h, S->d_tiles, L.tiles))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
+  out = std::move(S);
+  return TRX_OK;
+}
+
+static void install_highpass_set(trx_handle *h, std::unique_ptr<HighPassSet> &S) { h->highpass = std::move(S); }
+
+int trx_set_highpass(trx_handle *h, const trx_highpass *hp)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<HighPassSet> S;
+  if (const int rc = make_highpass_set(h, hp, S)) return rc;
+  install_highpass_set(h, S);
+  return TRX_OK;
+}
+
+int trx_run_highpassed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                       double *values, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  std::string msg;
+  if (const int rc = observed_run_checks(product_state(h), "trx_run_highpassed", ObservedRun::Highpassed, nshift, shift, values, "values", msg)) return fail(h, rc, msg);
+  // (no moments: the observed set only lends the high-pass its segments and gains)
+  PixelRun PR{h->pixels.get(), nshift}; PR.hp = h->highpass.get();
+  if (const int rc = pixel_run(h, "trx_run_highpassed", a, o, spectrum, PR, shift, dbg)) return rc;
+  // (the run has been waited for) the pairs whole -- into pinned memory grown once the run's checks have passed its size --,
+  // then their first components: (g', 1) is g', (0, 0) is a dead pixel
+  if (const int rc = ensure_pinned(h, h->h_pixhp, PR.hpx.pair_bytes)) return rc;
+  HIPCHK(h, hipMemcpy(h->h_pixhp.p, h->d_pixhp.p, PR.hpx.pair_bytes, hipMemcpyDeviceToHost));
+  const double *const ab = (const double *)h->h_pixhp.p; const double nan = __builtin_nan("");
+  for (int64_t k = 0; k < PR.hpx.pairs; k++) values[k] = ab[2 * k + 1] > 0.0 ? ab[2 * k] : nan;
   return TRX_OK;
 }
 
@@ -3658,6 +3763,11 @@ int trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm, cons
     if (const int rc = velocity_map_checks(product_state(b->hs[0]), "trx_run_batch_velocity_map", vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_velocity_map")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_velocity_map(h, atm + j, opts, nullptr, vm, map[j], per ? per[j] : nullptr, nullptr); });
+}
+
+int trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp)
+{
+  return batch_install<HighPassSet>(b, [=](trx_handle *h, std::unique_ptr<HighPassSet> &S) { return make_highpass_set(h, hp, S); }, install_highpass_set);
 }
 
 int trx_batch_set_filter(trx_batch *b, const trx_filter *f)

@@ -205,4 +205,11 @@ constexpr int kPixBlock = 256;                        // lanes (pairs) per block
 // (trx_filter.hip.h)
 struct FilterTile { int64_t first; int32_t seg, count; };      // pixels [first, first + count) of segment seg, 1 <= count <= 64
 
+// (trx_highpass.hip.h)
+constexpr int kHpBlock = 256;                         // lanes per block: whole waves
+constexpr int kHpOuts = 2;                            // outputs a lane keeps in registers: pixels lane, lane + kHpBlock of the tile
+constexpr int kHpTile = kHpBlock * kHpOuts;           // pixels per tile
+// pixels [first, first + count) of the segment [seg_first, seg_last), 1 <= count <= kHpTile
+struct HpTile { int64_t first, seg_first, seg_last; int32_t count, pad; };
+
 }  // namespace trx

@@ -1,5 +1,5 @@
-// trx_products.h -- the host side of the run products (bands, contributions, pixels, moments, filter, trail, velocity map,
-// broadening; include/transit_hip.h): what their calls refuse, the layouts the device gets, and the extents of a run's
+// trx_products.h -- the host side of the run products (bands, contributions, pixels, moments, filter, high-pass, trail,
+// velocity map, broadening; include/transit_hip.h): what their calls refuse, the layouts the device gets, and the extents of a run's
 // buffers.  Plain C++ (no HIP), pure arithmetic over the public structs: trx_api.hip checks with it, uploads what it lays
 // out and grows, guards and copies by its extents; tests/products_check.cpp runs the same source on the CPU over
 // exact-size buffers.  A check returns a TRX_* code and leaves the refusal's text in `msg`; the caller logs it.
@@ -14,6 +14,7 @@
 #include "transit_hip.h"
 #include "hip/trx_device.h"
 #include "trx_broaden.h"
+#include "trx_highpass.h"
 #include "trx_numerics.h"
 
 namespace trx {
@@ -25,6 +26,7 @@ struct ProductState {
   int64_t npix = 0;                                    // the pixel set's (0: none installed)
   int32_t nexp = 0, nseg = 0; const int64_t *seg = nullptr;      // the observed set's, seg its [nseg + 1] host bounds (null: none)
   bool filter = false;                                 // a filter is installed
+  bool highpass = false;                               // a high-pass is installed
 };
 
 inline int refuse(std::string &msg, int code, std::string text) { msg = std::move(text); return code; }
@@ -171,9 +173,9 @@ inline int observed_set_checks(const ProductState &S, const trx_observed *ob, st
 }
 
 // What a run against the observed set refuses for `who`, in this order: a shard of the grid, no observed set, (Filtered) no
-// filter, the count -- one shift per exposure, or (Trail) at least one lag --, the NULL arrays: in (named shift, or lag) and
-// out (named out_name).
-enum class ObservedRun { Moments, Filtered, Trail };
+// filter, (Highpassed) no high-pass, the count -- one shift per exposure, or (Trail) at least one lag, or (Highpassed) at
+// least one shift: its rows are independent --, the NULL arrays: in (named shift, or lag) and out (named out_name).
+enum class ObservedRun { Moments, Filtered, Trail, Highpassed };
 inline int observed_run_checks(const ProductState &S, const char *who, ObservedRun kind, int32_t n, const void *in, const void *out, const char *out_name,
                                std::string &msg)
 {
@@ -183,11 +185,13 @@ inline int observed_run_checks(const ProductState &S, const char *who, ObservedR
   // values' live flags)
   if (S.windowed)
     return no(TRX_E_UNSUPPORTED, std::string("this handle's shard is not the whole grid; take trx_run_pixels, add the ranks' pairs (trx_gather_host) and ") +
-                                 (kind == ObservedRun::Filtered ? "filter and reduce" : "reduce") + " them on the host");
+                                 (kind == ObservedRun::Filtered ? "filter and reduce" : kind == ObservedRun::Highpassed ? "high-pass" : "reduce") + " them on the host");
   if (S.npix < 1 || !S.seg) return no(TRX_E_ARG, "no observed set installed (trx_set_observed)");
   if (kind == ObservedRun::Filtered && !S.filter) return no(TRX_E_ARG, "no filter installed (trx_set_filter)");
+  if (kind == ObservedRun::Highpassed && !S.highpass) return no(TRX_E_ARG, "no high-pass installed (trx_set_highpass)");
   if (lags && n < 1) return no(TRX_E_ARG, "nlag < 1");
-  if (!lags && n != S.nexp) return no(TRX_E_ARG, "nshift " + std::to_string(n) + " is not the observed set's nexp " + std::to_string(S.nexp));
+  if (kind == ObservedRun::Highpassed && n < 1) return no(TRX_E_ARG, "nshift < 1");
+  if (!lags && kind != ObservedRun::Highpassed && n != S.nexp) return no(TRX_E_ARG, "nshift " + std::to_string(n) + " is not the observed set's nexp " + std::to_string(S.nexp));
   if (!in) return no(TRX_E_ARG, std::string(lags ? "lag" : "shift") + " is NULL");
   if (!out) return no(TRX_E_ARG, std::string(out_name) + " is NULL");
   return TRX_OK;
@@ -307,6 +311,49 @@ inline int filter_layout(const ProductState &S, const trx_filter *f, FilterLayou
         L.tiles.push_back(FilterTile{p, s, (int32_t)std::min<int64_t>(64, S.seg[(size_t)s + 1] - p)});
   } catch (...) { return refuse(msg, TRX_E_NOMEM, "filter: out of host memory"); }
   return TRX_OK;
+}
+
+// ---- the high-pass along the pixel axis (hip/trx_highpass.hip.h) ------------------------------------
+// a high-pass that is not a clearing call (hp and hp->taps non-null)
+inline int highpass_set_checks(const ProductState &S, const trx_highpass *hp, std::string &msg)
+{
+  if (S.npix < 1 || !S.seg) return refuse(msg, TRX_E_ARG, "highpass: no observed set installed (trx_set_observed)");
+  if (hp->half < 0) return refuse(msg, TRX_E_ARG, "highpass: half < 0");
+  if (hp->half > TRX_HIGHPASS_MAX_HALF) return refuse(msg, TRX_E_ARG, "highpass: half above TRX_HIGHPASS_MAX_HALF (" + std::to_string(TRX_HIGHPASS_MAX_HALF) + ")");
+  for (int32_t k = 0; k <= hp->half; k++)
+    if (!std::isfinite(hp->taps[k]) || !(hp->taps[k] >= 0)) return refuse(msg, TRX_E_ARG, "highpass: tap " + std::to_string(k) + " must be finite and >= 0");
+  if (!(hp->taps[0] > 0)) return refuse(msg, TRX_E_ARG, "highpass: tap 0 must be > 0");
+  return TRX_OK;
+}
+
+// What the device gets of a checked high-pass over the observed set of S: the taps, the full-window denominator
+// (highpass_full_den: the sum in the kernel's order) and the tiles of the set's segments: up to kHpTile consecutive pixels
+// of one segment each, with that segment's bounds, a segment's tiles in pixel order.
+struct HighpassLayout { int32_t half = 0; double den_full = 0; std::vector<double> taps; std::vector<HpTile> tiles; };
+inline int highpass_layout(const ProductState &S, const trx_highpass *hp, HighpassLayout &L, std::string &msg)
+{
+  try {
+    L.half = hp->half; L.taps.assign(hp->taps, hp->taps + hp->half + 1); L.tiles.clear();
+    L.den_full = highpass_full_den(L.half, L.taps.data());
+    for (int32_t s = 0; s < S.nseg; s++) {
+      const int64_t a = S.seg[(size_t)s], z = S.seg[(size_t)s + 1];
+      for (int64_t p = a; p < z; p += kHpTile) L.tiles.push_back(HpTile{p, a, z, (int32_t)std::min<int64_t>(kHpTile, z - p), 0});
+    }
+  } catch (...) { return refuse(msg, TRX_E_NOMEM, "highpass: out of host memory"); }
+  return TRX_OK;
+}
+
+// The extents of a high-pass over nshift rows of npix pixels with ntiles tiles: the pair buffer [nshift][npix][2] the kernel
+// writes (d_pixhp) -- and a highpassed run copies to pinned memory whole --, its values [nshift][npix], the kernel's blocks
+// (one per row and tile) and the LDS of one: g and the flags over a tile and its two halos.
+struct HighpassExtents { int64_t pairs = 0, blocks = 0; size_t pair_bytes = 0, val_bytes = 0, lds_bytes = 0; };
+inline HighpassExtents highpass_extents(int64_t npix, int32_t nshift, int64_t ntiles, int32_t half)
+{
+  HighpassExtents X;
+  X.pairs = (int64_t)nshift * npix; X.blocks = (int64_t)nshift * ntiles;
+  X.pair_bytes = sizeof(double) * 2 * (size_t)X.pairs; X.val_bytes = sizeof(double) * (size_t)X.pairs;
+  X.lds_bytes = sizeof(double) * 2 * ((size_t)kHpTile + 2 * (size_t)half);
+  return X;
 }
 
 // ---- rotational broadening (hip/trx_broaden.hip.h) -------------------------------------------------

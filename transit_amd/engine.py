@@ -208,6 +208,7 @@ def hip_library():
         _abi.bind_trail_api(lib)
         _abi.bind_vmap_api(lib)
         _abi.bind_filter_api(lib)
+        _abi.bind_highpass_api(lib)
         _abi.bind_broaden_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
@@ -363,6 +364,26 @@ class Engine(CEngine):
             raise EngineError(rc, "trx_run_filtered_moments", self._last_error())
         out = (mom,) + ((spec,) if spectrum else ()) + ((val,) if values else ())
         return out if len(out) > 1 else mom
+
+    def set_highpass(self, hp):
+        """trx_set_highpass: install a high-pass along the pixel axis (a transit_amd.xcor.HighPass; None: clear it) over
+        the observed set in force.  run_moments, run_filtered_moments, run_trail and run_velocity_map then take the
+        high-passed model; set_observed and set_pixels drop it."""
+        rc = self._lib.trx_set_highpass(self._h, C.byref(hp.to_c()) if hp is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_highpass", self._last_error())
+
+    def run_highpassed(self, atm, opts, shifts, spectrum: bool = False):
+        """trx_run_highpassed: the high-passed model values [nshift, npix] (transit_amd.xcor.highpass_reference of
+        run_pixels' pairs, bit for bit; NaN where the pixel is dead) at any number of shifts -- and, with
+        spectrum=True, (values, spectrum), the spectrum bit for bit what run() gives."""
+        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        val = np.zeros((sh.size, getattr(self, "npix", 0)))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_highpassed(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(val), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_highpassed", self._last_error())
+        return (val, spec) if spectrum else val
 
     def set_broadening(self, b):
         """trx_set_broadening: install a rotational broadening (a transit_amd.broaden.Rotation; None: clear it).  The
@@ -523,6 +544,12 @@ class Batch:
         rc = self._lib.trx_batch_set_filter(self._b, C.byref(filt.to_c()) if filt is not None else None)
         if rc != 0:
             raise EngineError(rc, "trx_batch_set_filter", self._err())
+
+    def set_highpass(self, hp):
+        """trx_batch_set_highpass: the same high-pass on every handle of the batch, or on none."""
+        rc = self._lib.trx_batch_set_highpass(self._b, C.byref(hp.to_c()) if hp is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_highpass", self._err())
 
     def run_filtered_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_filtered_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp], each atmosphere's moments

@@ -48,6 +48,22 @@ and the filtered moments are the seven sums with g' in place of g over the pixel
     filter_abs_reference(pairs, obs, filt)               |g| + |back| (|fwd| |g|): the scale of a value's rounding error
     reference_values(values, obs)                        the moments from a value matrix [nexp, npix], sums by math.fsum
     abs_reference_values(values, obs)                    the same with |f| and |values|
+
+The high-pass along the pixel axis (Engine.set_highpass / Engine.run_highpassed; trx_set_highpass / trx_run_highpassed):
+a symmetric tap table taps[0 .. half] (finite, >= 0, taps[0] > 0) over the observed set's segments.  For a row of pairs
+and a live pixel p (b > 0) of a segment, over the live pixels p + k of that segment, k = -half .. half in that order,
+
+    g'_p = g_p - (sum taps[|k|] g_{p+k}) / (sum taps[|k|])
+
+every operation rounded once; a dead pixel is NaN.  With it installed run_moments, run_filtered_moments, run_trail and
+run_velocity_map take g' where they took g.
+
+    HighPass(taps)                                       a high-pass; to_c() its trx_highpass
+    gaussian_highpass(sigma_pix, cut=3.0)                taps exp(-k^2 / (2 sigma^2)), half = floor(cut * sigma)
+    boxcar_highpass(width)                               width equal taps (width odd)
+    highpass_reference(pairs, obs, hp)                   g' [n, npix] by the definition, bit for bit the device's; dead NaN
+    highpass_pairs(values)                               the pairs (g', 1) / (0, 0) of such values: what reference,
+                                                         trail_reference and filter_reference take with a gain-free set
 """
 from __future__ import annotations
 
@@ -573,3 +589,84 @@ def reference_values(values, obs: Observed) -> np.ndarray:
 def abs_reference_values(values, obs: Observed) -> np.ndarray:
     """reference_values with |f| and |values|."""
     return _sums(*_values(values, obs), obs, True)
+
+
+@dataclass
+class HighPass:
+    """One trx_highpass: the symmetric tap table taps[0 .. half] (finite, >= 0, taps[0] > 0), taps[k] the weight at a
+    distance of k pixels."""
+    taps: np.ndarray
+
+    def __post_init__(self):
+        self.taps = np.ascontiguousarray(self.taps, dtype=np.float64).reshape(-1)
+        if self.taps.size < 1:
+            raise ValueError("HighPass: at least taps[0]")
+
+    @property
+    def half(self) -> int:
+        return int(self.taps.size) - 1
+
+    def to_c(self):
+        """The trx_highpass of the table (the array stays owned by this object)."""
+        c = _abi.TrxHighpass()
+        c.half, c.pad = self.half, 0
+        c.taps = self.taps.ctypes.data_as(_abi.c_double_p)
+        return c
+
+
+def gaussian_highpass(sigma_pix: float, cut: float = 3.0) -> HighPass:
+    """A running Gaussian mean of sigma_pix pixels cut at cut sigmas: taps exp(-k^2 / (2 sigma^2)), half = floor(cut * sigma)."""
+    if not (sigma_pix > 0) or not (cut > 0):
+        raise ValueError("gaussian_highpass: sigma_pix > 0 and cut > 0")
+    k = np.arange(int(math.floor(cut * sigma_pix)) + 1, dtype=np.float64)
+    return HighPass(np.exp(-(k * k) / (2.0 * sigma_pix * sigma_pix)))
+
+
+def boxcar_highpass(width: int) -> HighPass:
+    """A running mean over width pixels (odd): width equal taps, half = (width - 1) / 2."""
+    if width < 1 or width % 2 != 1:
+        raise ValueError("boxcar_highpass: an odd width >= 1")
+    return HighPass(np.ones((width - 1) // 2 + 1))
+
+
+def highpass_reference(pairs, obs: Observed, hp: HighPass) -> np.ndarray:
+    """The definition: g' [n, npix] from the pixel pairs [n, npix, 2] of a run at n shifts (or lags), the observed set's
+    segments and gain, and the taps -- vectorised over the pixels with a loop over k = -half .. half; a skipped term (its
+    pixel outside the segment or dead) is added as taps * 0, which leaves a sum that started from +0 as it is, bit for
+    bit.  NaN where the pixel is dead.  Engine.run_highpassed gives these bits."""
+    pairs = np.asarray(pairs, dtype=np.float64)
+    if pairs.ndim != 3 or pairs.shape[1:] != (obs.npix, 2):
+        raise ValueError("pairs of shape [n][npix][2]")
+    a, b = pairs[..., 0], pairs[..., 1]
+    gain = obs.gain if obs.gain is not None else np.ones(obs.npix)
+    on = b > 0
+    with np.errstate(all="ignore"):
+        g = np.where(on, gain[None, :] * (a / np.where(on, b, 1.0)), 0.0)
+    live = on.astype(np.float64)
+    out = np.full(g.shape, np.nan)
+    n, half = g.shape[0], hp.half
+    for s in range(obs.nseg):
+        first, last = int(obs.seg_first[s]), int(obs.seg_first[s + 1])
+        if last <= first:
+            continue
+        m = last - first
+        gz, lz = np.zeros((n, m + 2 * half)), np.zeros((n, m + 2 * half))
+        gz[:, half:half + m], lz[:, half:half + m] = g[:, first:last], live[:, first:last]
+        num, den = np.zeros((n, m)), np.zeros((n, m))
+        with np.errstate(all="ignore"):
+            for k in range(-half, half + 1):
+                t = hp.taps[abs(k)]
+                num = num + t * gz[:, half + k:half + k + m]
+                den = den + t * lz[:, half + k:half + k + m]
+            v = g[:, first:last] - num / den
+        out[:, first:last] = np.where(on[:, first:last], v, np.nan)
+    return out
+
+
+def highpass_pairs(values) -> np.ndarray:
+    """The pairs [n, npix, 2] the device keeps of high-passed values [n, npix]: (g', 1) for a live pixel, (0, 0) for a dead
+    one (NaN).  reference, trail_reference and filter_reference of them with a gain-free copy of the observed set are the
+    runs with the high-pass installed."""
+    values = np.asarray(values, dtype=np.float64)
+    has = ~np.isnan(values)
+    return np.stack([np.where(has, values, 0.0), has.astype(np.float64)], axis=-1)
