@@ -604,7 +604,8 @@ int  trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm /* [k] 
  * With a broadening installed the pairs sample the broadened spectrum, as in every other pixel run.  An installed FILTER
  * IS IGNORED: the filter couples the exposures of a pixel column, and a trail's model is the same at all of them (the
  * column is a constant) -- the trail's bits are the same with and without a filter on the handle.  A driver that detrends
- * applies the filter to the data it installs.
+ * applies the filter to the data it installs -- or takes trx_run_filtered_map, which applies it to every map cell's
+ * own model matrix.
  *
  * trx_run_trail is trx_run_pixels with nshift = nlag plus the reduction: spectrum may be NULL, and when it is given it
  * holds the bits trx_run gives; only trail is copied back, the [nlag][npix] pairs stay in device memory.  TRX_E_ARG, the
@@ -745,6 +746,59 @@ int  trx_run_highpassed(trx_handle *h, const trx_atm *a, const trx_opts *o,
                         int32_t nshift, const double *shift /* [nshift] */,
                         double *values /* [nshift][npix], host; NaN = dead */, trx_debug *dbg /* may be NULL */);
 int  trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp);
+
+/* The Kp-Vsys detection map with the detrending filter applied to every cell's own model matrix, from one spectrum.
+ * trx_run_trail and trx_run_velocity_map ignore an installed filter, because a trail's model is the same at all
+ * exposures; in a map cell it is not -- at exposure v it sits at the cell's own velocity kp * orbit[v] + vsys -- and the
+ * reprocessed model M' = M - U (U^+ M) (Brogi & Line 2019; Gibson et al. 2022) differs from cell to cell.  This call
+ * does for every cell what trx_run_filtered_moments does for one velocity hypothesis, from ONE spectrum and ONE pixel
+ * pass at the lags; only the map ([nkp][nvsys] doubles) and, when asked for, the lag table are copied back.
+ *
+ * vm is the trx_vmap of trx_run_velocity_map; nexp, nseg, the data, weights and gains are the installed observed set's,
+ * the matrices the installed filter's.  Every operation below is IEEE double, rounded once, no fused multiply-add.
+ *
+ * 1. The rows.  G[l][p] is the pair trx_run_pixels gives for the shift vm->lag[l] and pixel p.  With a broadening
+ *    installed the pairs sample the broadened spectrum; with a high-pass installed G[l][p] is that row's high-passed
+ *    pair (g', 1) / (0, 0), as every observed run takes it.  This is one pixel pass of nlag rows, exactly the one
+ *    trx_run_trail makes; the trail kernel does not run, and the device's trail buffer is not written.
+ * 2. The track of a cell.  For cell (i, j) and exposure v, x_v = (kp[i] * orbit[v] + vsys[j]) + offset[v] (the last
+ *    addition only with an offset), and with k and t of x_v as in step 3 of trx_run_velocity_map the cell takes the
+ *    NEAREST lag, not an interpolation:
+ *      k_v = k + (t > 0.5 ? 1 : 0)            (a tie goes to the lower lag; nlag == 1: k_v = 0)
+ *    lag_index[i][j][v] = k_v.  If any x_v is outside [lag_kms[0], lag_kms[nlag-1]] or not finite, the whole cell is NaN
+ *    in map, and its lag_index entries are -1 at the offending exposures and the nearest index elsewhere.  (Nearest, so
+ *    that every cell is an existing product at shifts the caller can name, point 6; a driver makes it as fine as it wants
+ *    with the lag step.)
+ * 3. The cell's model matrix M[v][p] = G[k_v][p].  For each pixel column this is the filter of trx_set_filter unchanged:
+ *    the column is LIVE when b > 0 at every one of the cell's rows k_v; c_j is taken over v ascending and r_v over j
+ *    ascending, both from +0; g' = g - r_v; a DEAD column is NaN.  A column can be live in one cell and dead in another.
+ * 4. The cell's moments.  For every (v, s) the seven sums of trx_run_filtered_moments over g' against exposure v's data
+ *    and weights: the same terms, the same lane order (first + l, first + l + 64, ...), the same butterfly.
+ * 5. The cell's value.  per_v = the sum over s = 0 .. nseg-1 IN THAT ORDER, from +0, of stat(mom[v][s]) (step 1 of
+ *    trx_run_velocity_map), undefined rows skipped; map[i][j] = the sum over v = 0 .. nexp-1 IN THAT ORDER, from +0, of
+ *    per_v.
+ * 6. It follows that, for a cell inside the lag grid,
+ *   - its moments are bit for bit what trx_run_filtered_moments returns on the same handle with shift[v] = lag[k_v];
+ *   - map[i][j] is point 5 applied on the host to those moments, in the same bits for CCF and CHI2 and to the accuracy
+ *     of the device's log (within 3 ulp) for LOGLIKE_BL19;
+ *   - there are no atomics: a cell's bits do not depend on the other cells of the call, the chunk of cells it was
+ *     computed in, the launch, the batch way or the handle's depth hint.
+ *
+ * spectrum may be NULL, and when it is given it holds the bits trx_run gives; lag_index may be NULL.  trx_run_trail,
+ * trx_run_velocity_map and every other run on the handle are unchanged, bit for bit.  A run that fails leaves map and
+ * lag_index undefined.
+ * TRX_E_ARG, the reason in trx_last_error, with nothing touched and the handle usable: every refusal of
+ * trx_run_velocity_map under this call's name; no filter installed; nkp * nvsys * nexp above 2^31 - 1.
+ * TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.
+ * trx_run_batch_filtered_map is trx_run_batch with ONE vm for all atmospheres and atmosphere j's map in map[j]; it also
+ * refuses a NULL map[j].  The batch's broadenings apply as in trx_run_batch_velocity_map. */
+int  trx_run_filtered_map(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                          double *spectrum /* [wn_hi-wn_lo], host; may be NULL */, const trx_vmap *vm,
+                          double *map /* [nkp][nvsys], host */,
+                          int32_t *lag_index /* [nkp][nvsys][nexp], host; may be NULL */,
+                          trx_debug *dbg /* may be NULL */);
+int  trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                                const trx_vmap *vm /* one for all */, double *const *map /* [k] -> [nkp][nvsys] */);
 
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)

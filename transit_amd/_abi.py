@@ -249,6 +249,20 @@ def bind_vmap_api(lib):
     return lib
 
 
+CELLMAP_CHUNK = 64      # kCellMapChunk (csrc/hip/trx_device.h): the most cells of a filtered map that go through the device at once
+
+
+def bind_cellmap_api(lib):
+    """argtypes/restypes of the filtered-map entry points (trx_run_filtered_map and its batch form)."""
+    lib.trx_run_filtered_map.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.POINTER(TrxVmap),
+                                         c_double_p, c_int32_p, C.POINTER(TrxDebug)]
+    lib.trx_run_filtered_map.restype = C.c_int
+    lib.trx_run_batch_filtered_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.POINTER(TrxVmap),
+                                               C.POINTER(c_double_p)]
+    lib.trx_run_batch_filtered_map.restype = C.c_int
+    return lib
+
+
 def bind_filter_api(lib):
     """argtypes/restypes of the filter entry points (trx_set_filter, trx_run_filtered_moments and their batch forms)."""
     lib.trx_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]

@@ -41,6 +41,7 @@
 #include "trx_moments.hip.h"
 #include "trx_trail.hip.h"
 #include "trx_vmap.hip.h"
+#include "trx_cellmap.hip.h"
 #include "trx_filter.hip.h"
 #include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
@@ -260,6 +261,10 @@ struct trx_handle {
   // trx_run_velocity_map (trx_vmap.hip.h), grown on demand: the call's arrays lag_kms, kp, vsys, orbit, offset end to end (their
   // host copy: vm_in), the statistic [nlag][nexp] followed by its transpose [nexp][nlag], the map [nkp][nvsys]
   DevBuf d_vm_in, d_vm_per, d_vm_map; std::vector<double> vm_in;
+  // trx_run_filtered_map (trx_cellmap.hip.h), grown on demand: the call's arrays in d_vm_in as above, the nearest-lag table
+  // [nkp * nvsys][nexp] int32, one chunk's filtered values [chunk][nexp][npix] and moments [chunk][nexp][nseg][TRX_NMOMENT],
+  // the map [nkp][nvsys]
+  DevBuf d_cm_index, d_cm_val, d_cm_mom, d_cm_map;
   std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
   DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
   std::unique_ptr<HighPassSet> highpass;               // trx_set_highpass (null: none); belongs to `observed`
@@ -3474,6 +3479,101 @@ int trx_run_highpassed(trx_handle *h, const trx_atm *a, const trx_opts *o, doubl
   return TRX_OK;
 }
 
+// ---- the Kp-Vsys map with the filter applied to every cell's own model matrix (trx_cellmap.hip.h) ---
+// The map of PR's rows (the pairs of the lags in h->d_pixout, or h->d_pixhp with a high-pass; the run waited for), behind the
+// upload of the call's arrays on the main queue: the index table once, then chunk after chunk the filter, the moments and the
+// statistic.  VX: the extents of the call's arrays at VX.at_* of h->d_vm_in; CX: those of the cell buffers.
+static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const VmapExtents &VX, const CellMapExtents &CX)
+{
+  const ObservedSet *O = h->observed.get(); const FilterSet *F = h->filter.get();
+  const double *in = h->d_vm_in.as<double>();
+  if (!O || !F || !in) return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
+  const int32_t nlag = vm->nlag, nexp = O->nexp, nseg = O->nseg;
+  const int64_t npix = O->npix;
+  CellTrackArgs TA{};
+  TA.lag_kms = in; TA.kp = in + VX.at_kp; TA.vsys = in + VX.at_vsys; TA.orbit = in + VX.at_orbit; TA.offset = vm->offset ? in + VX.at_offset : nullptr;
+  TA.index = h->d_cm_index.as<int32_t>(); TA.ntracks = CX.tracks; TA.nlag = nlag; TA.nexp = nexp; TA.nvsys = vm->nvsys;
+  // (every address the kernel reads or writes: the call's arrays -- a track's cell below nkp * nvsys, its exposure below
+  // nexp --, the bisection inside lag_kms [nlag], the table over [cells][nexp])
+  if (!TA.index || nlag < 1 || nexp < 1 || vm->nvsys < 1 || vm->nkp < 1 || CX.cells != (int64_t)vm->nkp * vm->nvsys || (int64_t)VX.cells != CX.cells ||
+      CX.tracks != CX.cells * nexp || CX.tracks > 0x7fffffffLL || h->d_vm_in.bytes < VX.in_bytes || VX.at_kp != (size_t)nlag ||
+      VX.at_offset - VX.at_orbit != (size_t)nexp || h->d_cm_index.bytes < CX.index_bytes || CX.index_bytes < sizeof(int32_t) * (size_t)CX.tracks ||
+      CX.track_blocks < 1 || CX.track_blocks > 0x7fffffffLL || CX.track_blocks * kCellTrackBlock < CX.tracks)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell track kernel (not launched)");
+  hipLaunchKernelGGL(k_cell_tracks, dim3((unsigned)CX.track_blocks), dim3(kCellTrackBlock), 0, h->stream, TA);
+
+  CellFilterArgs FA{};
+  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
+  FA.pairs = PR.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = PR.hp ? nullptr : O->d_gain.as<double>();
+  FA.fwd = F->d_fwd.as<double>(); FA.back = F->d_back.as<double>(); FA.tiles = F->d_tiles.as<FilterTile>(); FA.val = h->d_cm_val.as<double>();
+  FA.npix = npix; FA.ntiles = F->ntiles; FA.nexp = nexp;
+  CellMomArgs MA{};
+  MA.val = FA.val; MA.data = O->d_data.as<double>(); MA.weight = O->d_weight.as<double>(); MA.seg_first = O->d_seg.as<int64_t>();
+  MA.mom = h->d_cm_mom.as<double>(); MA.npix = npix; MA.nexp = nexp; MA.nseg = nseg;
+  CellStatArgs SA{};
+  SA.mom = MA.mom; SA.nexp = nexp; SA.nseg = nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
+  const size_t mat = sizeof(double) * (size_t)F->nseg * (size_t)F->nexp * (size_t)F->npad;
+  const size_t obs_cells = sizeof(double) * (size_t)nexp * (size_t)npix;
+  // (every address the three kernels read or write, for the largest chunk: the pairs over [nlag][npix] -- a table entry the
+  // filter follows lies in [0, nlag - 1], vmap_nearest, and a cell with a -1 is left out by all three --, the tiles in
+  // [0, npix) naming segments below nseg, made so when the filter was, the gains, the two padded matrices; the values over
+  // [chunk][nexp][npix]; data and weights over [nexp][npix], the segments in [0, npix), checked when the set was made; the
+  // moment rows over [chunk][nexp][nseg]; the chunk's cells of the map)
+  if (!FA.pairs || !FA.fwd || !FA.back || !FA.tiles || !FA.val || !MA.data || !MA.seg_first || !MA.mom || !h->d_cm_map.p ||
+      F->nexp != nexp || F->nseg != nseg || F->npix != npix || npix < 1 || nseg < 1 || npix != PR.set->npix || F->ncomp < 1 || F->ncomp > F->npad ||
+      (F->npad != 4 && F->npad != 8 && F->npad != 16) || F->ntiles < 1 || PR.nshift != nlag || PR.filt || PR.trail || PR.obs ||
+      PR.ext.pairs != (int64_t)nlag * npix || h->d_pixout.bytes < PR.ext.pair_bytes || (PR.hp && (PR.hpx.pairs != PR.ext.pairs || h->d_pixhp.bytes < PR.hpx.pair_bytes)) ||
+      F->d_fwd.bytes < mat || F->d_back.bytes < mat || F->d_tiles.bytes < sizeof(FilterTile) * (size_t)F->ntiles ||
+      (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)npix) || O->d_data.bytes < obs_cells || (MA.weight && O->d_weight.bytes < obs_cells) ||
+      O->d_seg.bytes < sizeof(int64_t) * ((size_t)nseg + 1) || O->seg.size() != (size_t)nseg + 1 || O->seg.front() != 0 || O->seg.back() != npix ||
+      CX.chunk < 1 || CX.nchunks < 1 || CX.last_chunk < 1 || CX.last_chunk > CX.chunk || (CX.nchunks - 1) * CX.chunk + CX.last_chunk != CX.cells ||
+      CX.rows != CX.chunk * nexp * nseg || CX.rows > 0x7fffffffLL ||
+      CX.val_bytes < obs_cells * (size_t)CX.chunk || h->d_cm_val.bytes < CX.val_bytes ||
+      CX.mom_bytes < sizeof(double) * TRX_NMOMENT * (size_t)CX.rows || h->d_cm_mom.bytes < CX.mom_bytes ||
+      CX.map_bytes < sizeof(double) * (size_t)CX.cells || h->d_cm_map.bytes < CX.map_bytes ||
+      (CX.chunk * F->ntiles + kFiltWaves - 1) / kFiltWaves > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
+  for (int64_t q = 0; q < CX.nchunks; q++) {
+    const int64_t cell0 = q * CX.chunk, n = q + 1 < CX.nchunks ? CX.chunk : CX.last_chunk;      // cells [cell0, cell0 + n)
+    FA.index = MA.index = SA.index = TA.index + cell0 * nexp;
+    FA.nwaves = n * F->ntiles; MA.nrows = n * nexp * nseg;
+    SA.map = h->d_cm_map.as<double>() + cell0; SA.ncells = n;
+    const dim3 fgrid((unsigned)((FA.nwaves + kFiltWaves - 1) / kFiltWaves)), fblock(64 * kFiltWaves);
+    if (F->npad == 4) hipLaunchKernelGGL(k_cell_filter<4>, fgrid, fblock, 0, h->stream, FA);
+    else if (F->npad == 8) hipLaunchKernelGGL(k_cell_filter<8>, fgrid, fblock, 0, h->stream, FA);
+    else hipLaunchKernelGGL(k_cell_filter<16>, fgrid, fblock, 0, h->stream, FA);
+    hipLaunchKernelGGL(k_cell_moments, dim3((unsigned)((MA.nrows + kMomWaves - 1) / kMomWaves)), dim3(64 * kMomWaves), 0, h->stream, MA);
+    hipLaunchKernelGGL(k_cell_stat, dim3((unsigned)((n + kCellStatWaves - 1) / kCellStatWaves)), dim3(64 * kCellStatWaves), 0, h->stream, SA);
+  }
+  HIPCHK(h, hipGetLastError());
+  return TRX_OK;
+}
+
+int trx_run_filtered_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, int32_t *lag_index,
+                         trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_run_filtered_map";
+  std::string msg;
+  if (const int rc = filtered_map_checks(product_state(h), who, vm, map, msg)) return fail(h, rc, msg);
+  const ObservedSet *O = h->observed.get();
+  const VmapExtents VX = vmap_extents(*vm, O->nexp);
+  const CellMapExtents CX = cell_map_extents((int64_t)vm->nkp * vm->nvsys, O->nexp, O->nseg, O->npix);
+  if (const int rc = vmap_pack(who, *vm, VX, h->vm_in, msg)) return fail(h, rc, msg);
+  // one pixel pass of nlag rows, the one trx_run_trail makes -- no moments, no trail; the high-pass when one is installed
+  PixelRun PR{h->pixels.get(), vm->nlag}; PR.hp = h->highpass.get();
+  if (const int rc = pixel_run(h, who, a, o, spectrum, PR, vm->lag, dbg)) return rc;
+  int rc;
+  // (the run has been waited for: the kernels follow the upload on the main queue)
+  if ((rc = ensure(h, h->d_cm_index, CX.index_bytes)) || (rc = ensure(h, h->d_cm_val, CX.val_bytes)) || (rc = ensure(h, h->d_cm_mom, CX.mom_bytes)) ||
+      (rc = ensure(h, h->d_cm_map, CX.map_bytes)) || (rc = upload(h, h->d_vm_in, h->vm_in)) || (rc = launch_filtered_map(h, PR, vm, VX, CX)))
+    return rc;
+  HIPCHK(h, hipMemcpyAsync(map, h->d_cm_map.p, CX.map_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (lag_index) HIPCHK(h, hipMemcpyAsync(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return TRX_OK;
+}
+
 // ---- rotational broadening between the spectrum and the pixels (trx_broaden.hip.h) ------------------
 // The broadening as h would keep it, checked whole before anything is replaced: on = false for a clearing call.
 static int make_broadening(trx_handle *h, const trx_broadening *br, bool &on, Broadening &out)
@@ -3785,6 +3885,20 @@ int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, 
   if (const int rc = batch_rows_check("trx_run_batch_filtered_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_moments")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_moments(h, atm + j, opts, nullptr, nshift, shift[j], nullptr, mom[j], nullptr); });
+}
+
+int trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = "trx_run_batch_filtered_map: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_filtered_map: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_map: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
+  if (const int rc = batch_rows_check("trx_run_batch_filtered_map", k, {{"map", map}}, g_comm_err)) return rc;
+  // (the handles are made from one description and carry one observed set and one filter: what the first refuses, all refuse)
+  if (k > 0)
+    if (const int rc = filtered_map_checks(product_state(b->hs[0]), "trx_run_batch_filtered_map", vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_map")) return rc;
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_map(h, atm + j, opts, nullptr, vm, map[j], nullptr, nullptr); });
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

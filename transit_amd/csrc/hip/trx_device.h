@@ -212,4 +212,10 @@ constexpr int kHpTile = kHpBlock * kHpOuts;           // pixels per tile
 // pixels [first, first + count) of the segment [seg_first, seg_last), 1 <= count <= kHpTile
 struct HpTile { int64_t first, seg_first, seg_last; int32_t count, pad; };
 
+// (trx_cellmap.hip.h) a filtered map goes through its cells in chunks: at most kCellMapChunk cells, and fewer where the
+// chunk's filtered values [chunk][nexp][npix] would be above kCellMapValBytes -- never fewer than one
+constexpr int kCellMapChunk = 64;
+constexpr uint64_t kCellMapValBytes = (uint64_t)1 << 30;
+constexpr int kCellTrackBlock = 256;                  // lanes ((cell, exposure) pairs) per block of k_cell_tracks
+
 }  // namespace trx

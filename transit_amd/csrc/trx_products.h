@@ -1,5 +1,5 @@
 // trx_products.h -- the host side of the run products (bands, contributions, pixels, moments, filter, high-pass, trail,
-// velocity map, broadening; include/transit_hip.h): what their calls refuse, the layouts the device gets, and the extents of a run's
+// velocity map, filtered map, broadening; include/transit_hip.h): what their calls refuse, the layouts the device gets, and the extents of a run's
 // buffers.  Plain C++ (no HIP), pure arithmetic over the public structs: trx_api.hip checks with it, uploads what it lays
 // out and grows, guards and copies by its extents; tests/products_check.cpp runs the same source on the CPU over
 // exact-size buffers.  A check returns a TRX_* code and leaves the refusal's text in `msg`; the caller logs it.
@@ -353,6 +353,48 @@ inline HighpassExtents highpass_extents(int64_t npix, int32_t nshift, int64_t nt
   X.pairs = (int64_t)nshift * npix; X.blocks = (int64_t)nshift * ntiles;
   X.pair_bytes = sizeof(double) * 2 * (size_t)X.pairs; X.val_bytes = sizeof(double) * (size_t)X.pairs;
   X.lds_bytes = sizeof(double) * 2 * ((size_t)kHpTile + 2 * (size_t)half);
+  return X;
+}
+
+// ---- the Kp-Vsys map with the filter applied per cell (hip/trx_cellmap.hip.h) -----------------------
+// what a filtered map refuses for `who`: every refusal of a map run, then no filter, then more index entries than int32 counts
+inline int filtered_map_checks(const ProductState &S, const char *who, const trx_vmap *vm, const void *map, std::string &msg)
+{
+  if (const int rc = velocity_map_checks(S, who, vm, map, msg)) return rc;
+  if (!S.filter) return refuse(msg, TRX_E_ARG, std::string(who) + ": no filter installed (trx_set_filter)");
+  if ((int64_t)vm->nkp * vm->nvsys * S.nexp > 0x7fffffffLL) return refuse(msg, TRX_E_ARG, std::string(who) + ": nkp * nvsys * nexp above 2^31 - 1");
+  return TRX_OK;
+}
+
+// A filtered map's buffers.  The cells go through the filter and the moments in chunks: `chunk` cells at a time -- cell_cap
+// at the most, fewer where the chunk's values would be above val_cap bytes or its moment rows above 2^31 - 1, never fewer
+// than one --, `nchunks` of them, the last with last_chunk cells.  The index table [cells][nexp] int32 and the map [cells]
+// are the whole call's; the values [chunk][nexp][npix] and the moments [chunk][nexp][nseg][TRX_NMOMENT] are one chunk's.
+struct CellMapExtents {
+  int64_t cells = 0, chunk = 0, nchunks = 0, last_chunk = 0;
+  int64_t tracks = 0, track_blocks = 0;                // cells * nexp, and k_cell_tracks' blocks of kCellTrackBlock of them
+  int64_t rows = 0;                                    // moment rows of a full chunk: chunk * nexp * nseg
+  size_t index_bytes = 0, val_bytes = 0, mom_bytes = 0, map_bytes = 0;
+};
+inline CellMapExtents cell_map_extents(int64_t cells, int32_t nexp, int32_t nseg, int64_t npix, int64_t cell_cap = kCellMapChunk,
+                                       uint64_t val_cap = kCellMapValBytes)
+{
+  CellMapExtents X;
+  const uint64_t cell_val = sizeof(double) * (uint64_t)nexp * (uint64_t)npix;      // one cell's values
+  const int64_t cell_rows = (int64_t)nexp * nseg;
+  X.cells = cells;
+  X.chunk = std::min(cells, cell_cap);
+  if (cell_val > 0) X.chunk = std::min<int64_t>(X.chunk, (int64_t)std::min<uint64_t>(val_cap / cell_val, 0x7fffffffULL));
+  if (cell_rows > 0) X.chunk = std::min<int64_t>(X.chunk, 0x7fffffffLL / cell_rows);
+  X.chunk = std::max<int64_t>(X.chunk, 1);
+  X.nchunks = (cells + X.chunk - 1) / X.chunk;
+  X.last_chunk = cells - (X.nchunks - 1) * X.chunk;
+  X.tracks = cells * nexp; X.track_blocks = (X.tracks + kCellTrackBlock - 1) / kCellTrackBlock;
+  X.rows = X.chunk * cell_rows;
+  X.index_bytes = sizeof(int32_t) * (size_t)X.tracks;
+  X.val_bytes = (size_t)cell_val * (size_t)X.chunk;
+  X.mom_bytes = sizeof(double) * TRX_NMOMENT * (size_t)X.rows;
+  X.map_bytes = sizeof(double) * (size_t)cells;
   return X;
 }
 

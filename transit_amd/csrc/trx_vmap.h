@@ -1,7 +1,8 @@
 // trx_vmap.h -- the arithmetic of the Kp-Vsys detection map (trx_run_velocity_map, include/transit_hip.h): the statistic
 // of one trail row, the place of a velocity on the lag grid and one exposure's interpolated term.  Plain host/device
-// functions: k_trail_stat and k_velocity_map (hip/trx_vmap.hip.h) call them per lane, tests/vmap_check.cpp runs the same
-// source on the CPU.  Every operation is an IEEE double operation rounded once -- no fused multiply-add -- in the order
+// functions: k_trail_stat and k_velocity_map (hip/trx_vmap.hip.h) and k_cell_tracks and k_cell_stat (hip/trx_cellmap.hip.h,
+// trx_run_filtered_map) call them per lane, tests/vmap_check.cpp and tests/cellmap_check.cpp run the same source on the
+// CPU.  Every operation is an IEEE double operation rounded once -- no fused multiply-add -- in the order
 // transit_amd/xcor.py (central, ccf, loglike_bl19, chi2, map_from_per) writes it, so that +, -, *, / and sqrt give numpy's
 // bits on either side; only log is the platform's.
 #pragma once
@@ -78,6 +79,15 @@ TRX_HD bool vmap_locate(const double *kms, int32_t nlag, double x, int32_t &k, d
   if (k > nlag - 2) k = nlag - 2;
   t = (x - kms[k]) / (kms[k + 1] - kms[k]);
   return true;
+}
+
+// The lag NEAREST to x on that grid (trx_run_filtered_map): vmap_locate's k, or k + 1 when t > 0.5 -- a tie goes to the
+// lower lag; nlag == 1: 0.  -1 for an x vmap_locate refuses.  In [0, nlag - 1] otherwise.
+TRX_HD int32_t vmap_nearest(const double *kms, int32_t nlag, double x)
+{
+  int32_t k; double t;
+  if (!vmap_locate(kms, nlag, x, k, t)) return -1;
+  return k + (t > 0.5 ? 1 : 0);
 }
 
 // one exposure's term of a cell from the statistic at the two lags around its velocity

@@ -208,6 +208,7 @@ def hip_library():
         _abi.bind_trail_api(lib)
         _abi.bind_vmap_api(lib)
         _abi.bind_filter_api(lib)
+        _abi.bind_cellmap_api(lib)
         _abi.bind_highpass_api(lib)
         _abi.bind_broaden_api(lib)
         lib.trx_device_count.restype = C.c_int
@@ -364,6 +365,23 @@ class Engine(CEngine):
             raise EngineError(rc, "trx_run_filtered_moments", self._last_error())
         out = (mom,) + ((spec,) if spectrum else ()) + ((val,) if values else ())
         return out if len(out) > 1 else mom
+
+    def run_filtered_map(self, atm, opts, vm, lag_index: bool = False, spectrum: bool = False):
+        """trx_run_filtered_map: the Kp-Vsys map [nkp, nvsys] of a transit_amd.xcor.VelocityMap with the installed filter
+        applied to every cell's own model matrix -- the cell takes at every exposure the lag nearest to its velocity
+        (xcor.nearest_lags), and its value is xcor.cell_value of run_filtered_moments at those lags; a cell with a
+        velocity outside the lag grid is NaN.  With lag_index=True and/or spectrum=True a tuple
+        (map[, lag_index][, spectrum]): lag_index [nkp, nvsys, nexp] int32 the lags taken (-1: outside), the spectrum
+        bit for bit what run() gives.  One spectrum and one pixel pass, whatever the number of cells."""
+        m = np.zeros((vm.nkp, vm.nvsys))
+        idx = np.zeros((vm.nkp, vm.nvsys, getattr(self, "mom_shape", (0, 0))[0]), dtype=np.int32) if lag_index else None
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_filtered_map(self._h, C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m),
+                                            idx.ctypes.data_as(_abi.c_int32_p) if lag_index else None, None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_filtered_map", self._last_error())
+        out = (m,) + ((idx,) if lag_index else ()) + ((spec,) if spectrum else ())
+        return out if len(out) > 1 else m
 
     def set_highpass(self, hp):
         """trx_set_highpass: install a high-pass along the pixel axis (a transit_amd.xcor.HighPass; None: clear it) over
@@ -558,6 +576,13 @@ class Batch:
         out = np.zeros((len(atms),) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
         self._call("trx_run_batch_filtered_moments", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
+
+    def run_filtered_map(self, atms, opts: _abi.TrxOpts, vm) -> np.ndarray:
+        """trx_run_batch_filtered_map: the maps [K, nkp, nvsys] of one transit_amd.xcor.VelocityMap for all atmospheres,
+        each atmosphere's what Engine.run_filtered_map gives, bit for bit."""
+        m = np.zeros((len(atms), vm.nkp, vm.nvsys))
+        self._call("trx_run_batch_filtered_map", atms, opts, C.byref(vm.to_c()), _rows(m))
+        return m
 
     def set_broadening(self, b):
         """trx_batch_set_broadening: one transit_amd.broaden.Rotation for every atmosphere of the following pixel,

@@ -49,6 +49,16 @@ and the filtered moments are the seven sums with g' in place of g over the pixel
     reference_values(values, obs)                        the moments from a value matrix [nexp, npix], sums by math.fsum
     abs_reference_values(values, obs)                    the same with |f| and |values|
 
+The detection map with the filter applied to every cell's own model matrix (Engine.run_filtered_map /
+Batch.run_filtered_map; trx_run_filtered_map): a cell takes at every exposure the row of the lag NEAREST to its velocity,
+that matrix goes through the filter and the moments above, and the cell is the statistic added over the segments and
+then over the exposures, both in order.
+
+    nearest_lags(vm)                                     [nkp, nvsys, nexp]: the lag every cell takes at every exposure, -1 outside
+    cell_value(mom, vm)                                  a cell from its moments [nexp, nseg, 7]
+    cell_bound(mom, vm)                                  how far two double evaluations of cell_value can lie apart
+    filtered_map_reference(pairs, obs, filt, vm)         the whole definition in numpy from run_pixels(lags)' pairs
+
 The high-pass along the pixel axis (Engine.set_highpass / Engine.run_highpassed; trx_set_highpass / trx_run_highpassed):
 a symmetric tap table taps[0 .. half] (finite, >= 0, taps[0] > 0) over the observed set's segments.  For a row of pairs
 and a live pixel p (b > 0) of a segment, over the live pixels p + k of that segment, k = -half .. half in that order,
@@ -589,6 +599,73 @@ def reference_values(values, obs: Observed) -> np.ndarray:
 def abs_reference_values(values, obs: Observed) -> np.ndarray:
     """reference_values with |f| and |values|."""
     return _sums(*_values(values, obs), obs, True)
+
+
+def nearest_lags(vm: VelocityMap) -> np.ndarray:
+    """[nkp, nvsys, nexp] int: the lag NEAREST to every cell's velocity at every exposure, as trx_run_filtered_map takes
+    it -- _locate's k, or k + 1 when t > 0.5 (a tie goes to the lower lag; one lag: 0) -- and -1 where the velocity is
+    outside the lag grid or not finite.  Built on _tracks and _locate, whose operations are the device's: the same
+    index on either side, ties included."""
+    inside, k, t = _locate(vm.lag_kms, _tracks(vm))
+    return np.where(inside, k + (t > 0.5), -1).astype(np.int64)
+
+
+def cell_value(mom, vm: VelocityMap) -> float:
+    """Point 5 of trx_run_filtered_map on a cell's moments [nexp, nseg, 7]: per exposure the map's statistic of the rows
+    added over the segments s = 0, 1, ... IN THAT ORDER from +0, undefined rows (nan) skipped; then those sums added over
+    the exposures in order from +0."""
+    mom = np.asarray(mom, dtype=np.float64)
+    if mom.ndim != 3 or mom.shape[0] != vm.nexp or mom.shape[2] != NMOMENT:
+        raise ValueError("mom of shape [nexp][nseg][7] with the map's nexp")
+    st = np.asarray(vm.statistic(mom), dtype=np.float64)
+    per = np.zeros(mom.shape[0])
+    for s in range(mom.shape[1]):
+        with np.errstate(invalid="ignore"):
+            per = np.where(np.isnan(st[:, s]), per, per + st[:, s])
+    out = 0.0
+    for v in range(mom.shape[0]):
+        out = out + float(per[v])
+    return out
+
+
+def cell_bound(mom, vm: VelocityMap) -> float:
+    """How far two double evaluations of point 5 (cell_value on the host, k_cell_stat on the device) of the SAME moments
+    [nexp, nseg, 7] can lie apart: map_bound's t = 0, single-row case.  With A_v the sum over the segments of
+    |statistic| of the rows (v, .) and S the sum of the A_v:
+
+      - each side's statistic of a row is within c * 2^-53 |term| of the exact one (c = 4 for ccf and chi2, a dozen
+        correctly rounded operations that agree bit for bit in practice; c = 5 for loglike_bl19, see per_bound), and a
+        sum of nseg terms is within (nseg - 1) 2^-53 A_v of the exact sum of its terms: two sides lie at most
+        (c + nseg) 2^-52 A_v apart in per_v;
+      - there is no interpolation: the cell takes one row per exposure, and per_v enters the sum as it stands;
+      - the sum of nexp terms in order: (nexp - 1) 2^-53 of the sum of the |per_v| <= S per side.
+
+    Together (c + nseg + nexp) 2^-52 S, to first order in 2^-52."""
+    mom = np.asarray(mom, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        s = float(np.nansum(np.abs(np.asarray(vm.statistic(mom), dtype=np.float64))))
+    c = 5 if vm.stat == "loglike_bl19" else 4
+    return (c + mom.shape[1] + mom.shape[0]) * _EPS * s
+
+
+def filtered_map_reference(pairs_at_lags, obs: Observed, filt: Filter, vm: VelocityMap) -> np.ndarray:
+    """The definition of trx_run_filtered_map in numpy: the map [nkp, nvsys] from the pixel pairs [nlag, npix, 2] of
+    run_pixels at vm.lag.  Cell (i, j) takes at exposure v the row nearest_lags(vm)[i, j, v]; that matrix goes through
+    filter_reference and reference_values as a filtered run's does, and cell_value gives the cell.  A cell with a
+    velocity outside the lag grid is nan.  (With a high-pass: highpass_pairs of highpass_reference of the pairs, and a
+    gain-free copy of the observed set.)"""
+    pairs = np.asarray(pairs_at_lags, dtype=np.float64)
+    if pairs.shape != (vm.nlag, obs.npix, 2):
+        raise ValueError("pairs of shape [nlag][npix][2] with the map's nlag")
+    if vm.nexp != obs.nexp:
+        raise ValueError("a map of the observed set's nexp")
+    idx = nearest_lags(vm)
+    out = np.full((vm.nkp, vm.nvsys), np.nan)
+    for i in range(vm.nkp):
+        for j in range(vm.nvsys):
+            if np.all(idx[i, j] >= 0):
+                out[i, j] = cell_value(reference_values(filter_reference(pairs[idx[i, j]], obs, filt), obs), vm)
+    return out
 
 
 @dataclass
