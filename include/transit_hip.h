@@ -592,7 +592,8 @@ int  trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm /* [k] 
  * terms (w g, (w g) g, w f, (w f) g, (w f) f, each rounded once, no fused multiply-add) and the order of the sums (lane k
  * adds the segment's pixels first + k, first + k + 64, ..., then the same butterfly over the 64 lanes) are those of
  * trx_run_moments, so
- *   trail[l] is bit for bit what trx_run_moments returns on the same handle when all nexp shifts equal lag[l].
+ *   trail[l] is bit for bit what trx_run_moments returns on the same handle when all nexp shifts equal lag[l]
+ *   (on a handle without an exposure table: the trail ignores one, trx_set_exposures).
  * It follows that
  *   - there are no atomics;
  *   - the bits of a row depend on the spectrum, that lag, and that exposure's data, weights and gains over that segment:
@@ -730,7 +731,8 @@ int  trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm /* [
  * whole grid, for trx_run_moments' reason.  A run that fails leaves values undefined.
  * WITH A HIGH-PASS INSTALLED trx_run_moments, trx_run_filtered_moments, trx_run_trail and trx_run_velocity_map (and
  * their batch forms) take g' where they took g and skip the dead pixels: the same kernels, the same order of every sum,
- * so trail[l] stays bit for bit trx_run_moments with all shifts equal to lag[l] on the same handle.  trx_run,
+ * so trail[l] stays bit for bit trx_run_moments with all shifts equal to lag[l] on the same handle (on a handle without
+ * an exposure table).  trx_run,
  * trx_run_bands, trx_run_contrib, trx_run_pixels, trx_run_broadened and trx_sweep_permol are unchanged bit for bit, as
  * is every run on a handle without a high-pass.
  * trx_batch_set_highpass installs the same high-pass on every handle of the batch, or on none (its reason through
@@ -778,7 +780,8 @@ int  trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp);
  *    trx_run_velocity_map), undefined rows skipped; map[i][j] = the sum over v = 0 .. nexp-1 IN THAT ORDER, from +0, of
  *    per_v.
  * 6. It follows that, for a cell inside the lag grid,
- *   - its moments are bit for bit what trx_run_filtered_moments returns on the same handle with shift[v] = lag[k_v];
+ *   - its moments are bit for bit what trx_run_filtered_moments returns on the same handle with shift[v] = lag[k_v]
+ *     (on a handle without an exposure table: the map ignores one, trx_set_exposures);
  *   - map[i][j] is point 5 applied on the host to those moments, in the same bits for CCF and CHI2 and to the accuracy
  *     of the device's log (within 3 ulp) for LOGLIKE_BL19;
  *   - there are no atomics: a cell's bits do not depend on the other cells of the call, the chunk of cells it was
@@ -799,6 +802,70 @@ int  trx_run_filtered_map(trx_handle *h, const trx_atm *a, const trx_opts *o,
                           trx_debug *dbg /* may be NULL */);
 int  trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
                                 const trx_vmap *vm /* one for all */, double *const *map /* [k] -> [nkp][nvsys] */);
+
+/* The exposure table on the device: the two parts of a time series' forward model that differ from exposure to exposure
+ * and must act on the pixels BEFORE the filter, which mixes the exposures of a column.
+ *   scale[v]  the model's amplitude at exposure v: the light curve in transit (0 out of transit), the phase function in
+ *             emission.  (trx_observed.gain is per pixel only.)
+ *   smear[v]  eta_v = dv / (2 c), the HALF-width of the change of the planet's Doppler factor over exposure v, relative:
+ *             the lines are smeared by a box in velocity whose width differs from exposure to exposure.
+ * The table belongs to the observed set: row v of the pixel matrix is exposure v.  For exposure v (shift s, eta = smear[v],
+ * c = scale[v]) and pixel p, every operation IEEE double, rounded once, no fused multiply-add:
+ *   eta == 0:  the pair is exactly the pair trx_run_pixels gives for (s, p): the same range, the same Gaussian weight, the
+ *              same lane and wave order.
+ *   eta > 0:   centre' = centre_p / s ; fwhm' = fwhm_p / s ; sigma = fwhm' / (2 sqrt(2 ln 2))       (as trx_run_pixels)
+ *              d = centre' * eta                 the box's half-width in cm-1, first order in eta as the broadening is in beta
+ *              r = cut * sigma + d
+ *              i_lo = ceil((centre' - r - wn_i) / wn_d) ; i_hi = floor((centre' + r - wn_i) / wn_d), clipped to [0, nwn)
+ *              and then to the shard, as trx_run_pixels clips (a NaN edge: no bin)
+ *              q = sigma * sqrt(2)               (the host's double sqrt(2.0))
+ *              x = nu_i - centre' ; W_i = erf((x + d) / q) - erf((x - d) / q)
+ *              (a, b) = (sum of W_i S_i, sum of W_i)
+ *              W is the box of half-width d convolved with the Gaussian, unnormalised: the value is a / b.  The order of
+ *              the sums is trx_run_pixels' rule applied to THIS window's in-shard length: fewer than 192 bins, one lane,
+ *              bins ascending; otherwise the wave, lane l adding bins l, l + 64, ..., then the fixed butterfly.
+ *   scale:     a is replaced by c * a, one product; b is untouched, so the contributing, live and dead rules of the
+ *              moments, the filter and the high-pass do not move.  c = 0 makes the model 0 at that exposure, not the pixel
+ *              dead.  A pair with no bin in the shard is exactly (+0, +0), whatever c.
+ * No atomics: the bits of a pair depend on the spectrum, its pixel, its shift, its own eta and c, and the shard -- not on
+ * the rest of the table, the other rows, the launch, the batch way that ran it or the handle's depth hint.
+ *
+ * WHERE THE TABLE ACTS: in the runs whose rows are exposures.  trx_run_exposed returns these pairs; trx_run_moments and
+ * trx_run_filtered_moments (and their batch forms) take them where they took the plain pairs, with the high-pass and the
+ * filter behind them unchanged.  WHERE IT IS IGNORED: in trx_run_pixels, trx_run_highpassed, trx_run_trail,
+ * trx_run_velocity_map and trx_run_filtered_map a row is a shift or a lag, not an exposure; their bits are the same with
+ * and without a table on the handle, as the trail's are with and without a filter.  Every run on a handle without a table is
+ * unchanged, bit for bit.
+ *
+ * trx_set_exposures keeps the two arrays on the host (no device work, no synchronisation: the table changes with every
+ * likelihood call, as v sin i does); a run uploads them with its shifts, ahead of its kernels.  ex NULL or nexp == 0 clears
+ * it.  A successful trx_set_observed or trx_set_pixels drops it, clearing calls included; a refused one keeps it.  It is
+ * independent of the broadening, the filter and the high-pass.  TRX_E_ARG, the reason in trx_last_error, the previous table
+ * in force and the handle usable: no observed set; nexp < 0 or not the observed set's; both arrays NULL; a non-finite
+ * scale; a smear that is not finite, negative or above TRX_SMEAR_MAX (both naming "exposure N").
+ * trx_run_exposed is trx_run_pixels with the table: spectrum may be NULL, and when it is given it holds the bits trx_run
+ * gives.  TRX_E_ARG with no observed set or no table installed, nshift not the set's nexp, shift or out NULL, a non-finite
+ * or <= 0 shift (naming "shift N").  It works on a handle whose shard is not the whole grid: the pairs are linear in the
+ * bins, and the ranks add theirs in rank order.  (The moment runs stay TRX_E_UNSUPPORTED there.)
+ * trx_batch_set_exposures follows trx_batch_set_broadening: ex[j] belongs to atmosphere j of the following batch exposed,
+ * moment and filtered-moment runs; n = 1: one table for all; n = 0: clear.  All entries are checked before any is kept, and
+ * the arrays are copied.  Such a run of k atmospheres with n != 1 and n != k returns TRX_E_ARG (n = 0: the moment runs go
+ * without a table; trx_run_batch_exposed refuses). */
+#define TRX_SMEAR_MAX 0.01
+typedef struct {
+  int32_t nexp, pad;         /* = the installed observed set's nexp; pad is ignored                          */
+  const double *scale;       /* [nexp] finite factor on the model at exposure v, or NULL: 1                  */
+  const double *smear;       /* [nexp] eta_v >= 0, finite, <= TRX_SMEAR_MAX, or NULL: 0                      */
+} trx_exposures;             /* 24 bytes */
+int  trx_set_exposures(trx_handle *h, const trx_exposures *ex);
+int  trx_run_exposed(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                     double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                     int32_t nshift, const double *shift /* [nshift], nshift = nexp */,
+                     double *out /* [nexp][npix][2], host */, trx_debug *dbg /* may be NULL */);
+int  trx_batch_set_exposures(trx_batch *b, int32_t n, const trx_exposures *ex /* [n] */);
+int  trx_run_batch_exposed(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                           int32_t nshift, const double *const *shift /* [k] -> [nexp] */,
+                           double *const *out /* [k] -> [nexp][npix][2] */);
 
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)

@@ -126,6 +126,13 @@ class TrxBroadening(C.Structure):
     _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("beta", C.c_double), ("limb", C.c_double)]
 
 
+SMEAR_MAX = 0.01
+
+
+class TrxExposures(C.Structure):
+    _fields_ = [("nexp", C.c_int32), ("pad", C.c_int32), ("scale", c_double_p), ("smear", c_double_p)]
+
+
 class TrxStats(C.Structure):
     _fields_ = [
         ("nlines_inrange", C.c_int64), ("ngroups", C.c_int64), ("nadd", C.c_int64),
@@ -302,4 +309,19 @@ def bind_broaden_api(lib):
     lib.trx_run_batch_broadened.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
                                             C.POINTER(c_double_p)]
     lib.trx_run_batch_broadened.restype = C.c_int
+    return lib
+
+
+def bind_exposures_api(lib):
+    """argtypes/restypes of the exposure-table entry points (trx_set_exposures, trx_run_exposed and their batch forms)."""
+    lib.trx_set_exposures.argtypes = [C.c_void_p, C.POINTER(TrxExposures)]
+    lib.trx_set_exposures.restype = C.c_int
+    lib.trx_run_exposed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                    c_double_p, C.POINTER(TrxDebug)]
+    lib.trx_run_exposed.restype = C.c_int
+    lib.trx_batch_set_exposures.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxExposures)]
+    lib.trx_batch_set_exposures.restype = C.c_int
+    lib.trx_run_batch_exposed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
+                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
+    lib.trx_run_batch_exposed.restype = C.c_int
     return lib

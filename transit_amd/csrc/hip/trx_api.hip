@@ -52,6 +52,7 @@
 #include "../trx_broaden.h"
 #include "../trx_vmap.h"
 #include "../trx_products.h"
+#include "../trx_exposures.h"
 
 using namespace trx;
 
@@ -107,15 +108,24 @@ struct HighPassSet {
   int32_t half = 0, nseg = 0; int64_t npix = 0, ntiles = 0; double den_full = 0; const ObservedSet *obs = nullptr;
   DevBuf d_taps, d_tiles;                            // [half + 1], HpTile[ntiles]
 };
+// an exposure table installed by trx_set_exposures over the observed set (trx_pixels.hip.h, ../trx_exposures.h): the two
+// arrays as given, on the host -- a run uploads them with its shifts (an array the caller left out is empty)
+struct ExposureSet {
+  int32_t nexp = 0;
+  std::vector<double> scale, smear;                  // [nexp] each, or empty
+};
 // a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
 // filt: with the filter between the pairs and the moments (trx_run_filtered_moments); trail: the shifts are the lags of a
 // trail (trx_run_trail) -- every exposure of obs against every one of them (trx_trail.hip.h), never with a filter; ext: the
 // extents of its buffers (../trx_products.h), which pixel_run works out, grows them to and leaves here for the guards and copies;
 // hp: with the high-pass between the pairs and whatever reads them (pixel_run sets it for every run with obs on a handle that
-// has one; trx_run_highpassed itself), hpx the extents of that
+// has one; trx_run_highpassed itself), hpx the extents of that; ex: the rows are exposures and take the handle's exposure
+// table (trx_run_exposed, and trx_run_moments and trx_run_filtered_moments on a handle with one), already in h->d_exscale
+// and h->d_exsmear
 struct PixelRun {
   const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; PixelExtents ext{};
   const HighPassSet *hp = nullptr; HighpassExtents hpx{};
+  const ExposureSet *ex = nullptr;
 };
 // a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
 // the largest -- which sizes the kernel's tile
@@ -273,6 +283,8 @@ struct trx_handle {
   DevBuf d_pixhp; PinnedBuf h_pixhp;
   bool broad_on = false; Broadening broad;             // trx_set_broadening (broad_on false: none); independent of the sets above
   DevBuf d_broad;                                      // the broadened spectrum [nwn] of a broadened or pixel run, grown on demand
+  std::unique_ptr<ExposureSet> exposures;              // trx_set_exposures (null: none); belongs to `observed`
+  DevBuf d_exscale, d_exsmear;                         // the table's arrays [nexp] each, uploaded by every run that takes it, grown on demand
 };
 
 namespace {
@@ -2773,7 +2785,22 @@ int Run::pixel_kernels()
       h->d_pixshift.bytes < X.shift_bytes || h->d_pixout.bytes < X.pair_bytes ||
       blocks < 1 || blocks > 0x7fffffffLL)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the pixel kernel (not launched)");
-  hipLaunchKernelGGL(k_pixel_pairs, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
+  const ExposureSet *const ex = px->ex;
+  if (!ex) {
+    hipLaunchKernelGGL(k_pixel_pairs, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
+    return TRX_OK;
+  }
+  // the rows are exposures: the table's arrays, one entry per row (pixel_run sent them ahead with the shifts)
+  const ExposureExtents EX = exposure_extents(ex->nexp);
+  if (!ex->scale.empty()) PA.scale = h->d_exscale.as<double>();
+  if (!ex->smear.empty()) PA.smear = h->d_exsmear.as<double>();
+  PA.sqrt2 = std::sqrt(2.0);
+  // (every further address the kernel reads: scale and smear over [0, nshift) = [0, nexp))
+  if (ex != h->exposures.get() || ex->nexp != px->nshift || (ex->scale.empty() && ex->smear.empty()) ||
+      (!ex->scale.empty() && (ex->scale.size() != (size_t)ex->nexp || !PA.scale || h->d_exscale.bytes < EX.scale_bytes)) ||
+      (!ex->smear.empty() && (ex->smear.size() != (size_t)ex->nexp || !PA.smear || h->d_exsmear.bytes < EX.smear_bytes)))
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the exposed pixel kernel (not launched)");
+  hipLaunchKernelGGL(k_pixel_pairs_exposed, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
   return TRX_OK;
 }
 
@@ -3129,7 +3156,7 @@ static ProductState product_state(const trx_handle *h)
   S.windowed = h->windowed(); S.wn_i = h->wn_i; S.wn_d = h->wn_d; S.nwn = h->nwn; S.lo = h->lo; S.hi = h->hi;
   if (h->pixels) S.npix = h->pixels->npix;
   if (h->observed) { S.nexp = h->observed->nexp; S.nseg = h->observed->nseg; S.seg = h->observed->seg.data(); }
-  S.filter = h->filter != nullptr; S.highpass = h->highpass != nullptr;
+  S.filter = h->filter != nullptr; S.highpass = h->highpass != nullptr; S.exposures = h->exposures != nullptr;
   return S;
 }
 
@@ -3219,10 +3246,10 @@ static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<P
   return TRX_OK;
 }
 
-// (the observed set belongs to the pixel set it was installed over, the filter and the high-pass to the observed set: they go
-// with it -- the high-pass first, which points into the observed set)
-static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->highpass.reset(); h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); }
-static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->highpass.reset(); h->observed = std::move(S); h->filter.reset(); }
+// (the observed set belongs to the pixel set it was installed over, the filter, the high-pass and the exposure table to the
+// observed set: they go with it -- the high-pass first, which points into the observed set)
+static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->highpass.reset(); h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); h->exposures.reset(); }
+static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->highpass.reset(); h->observed = std::move(S); h->filter.reset(); h->exposures.reset(); }
 
 int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 {
@@ -3254,6 +3281,9 @@ static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx
       (PR.hp && (rc = ensure(h, h->d_pixhp, PR.hpx.pair_bytes))) ||
       (h->broad_on && (rc = ensure(h, h->d_broad, broadened_bytes(h->nwn)))) ||
       (rc = upload_raw(h, h->d_pixshift, shift, (size_t)PR.nshift)))
+    return rc;
+  // (the exposure table with them: it changes from call to call, as the shifts do)
+  if (PR.ex && ((!PR.ex->scale.empty() && (rc = upload(h, h->d_exscale, PR.ex->scale))) || (!PR.ex->smear.empty() && (rc = upload(h, h->d_exsmear, PR.ex->smear)))))
     return rc;
   // (with a broadening installed the pixels sample the broadened spectrum)
   Products want; want.px = &PR; if (h->broad_on) want.br = &h->broad;
@@ -3313,9 +3343,50 @@ int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *
   if (!h) return TRX_E_ARG;
   std::string msg;
   if (const int rc = observed_run_checks(product_state(h), "trx_run_moments", ObservedRun::Moments, nshift, shift, mom, "mom", msg)) return fail(h, rc, msg);
-  PixelRun PR{h->pixels.get(), nshift, h->observed.get()};
+  PixelRun PR{h->pixels.get(), nshift, h->observed.get()}; PR.ex = h->exposures.get();
   if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, PR, shift, dbg)) return rc;
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
+  return TRX_OK;
+}
+
+// ---- the exposure table: a scale and a Doppler smear per exposure, in the pixel stage (trx_pixels.hip.h) ----
+// The table as h would keep it, checked whole before anything is replaced (null: a clearing call); the arrays stay on the host.
+static int make_exposure_set(trx_handle *h, const trx_exposures *ex, std::unique_ptr<ExposureSet> &out)
+{
+  out.reset();
+  if (!ex || ex->nexp == 0) return TRX_OK;              // (clear)
+  std::string msg;
+  if (const int rc = exposure_set_checks(product_state(h), ex, msg)) return fail(h, rc, msg);
+  std::unique_ptr<ExposureSet> S(new (std::nothrow) ExposureSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "exposures: out of host memory");
+  S->nexp = ex->nexp;
+  try {
+    if (ex->scale) S->scale.assign(ex->scale, ex->scale + ex->nexp);
+    if (ex->smear) S->smear.assign(ex->smear, ex->smear + ex->nexp);
+  } catch (...) { return fail(h, TRX_E_NOMEM, "exposures: out of host memory"); }
+  out = std::move(S);
+  return TRX_OK;
+}
+
+int trx_set_exposures(trx_handle *h, const trx_exposures *ex)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<ExposureSet> S;
+  if (const int rc = make_exposure_set(h, ex, S)) return rc;
+  h->exposures = std::move(S);
+  return TRX_OK;
+}
+
+int trx_run_exposed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                    double *out, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  std::string msg;
+  if (const int rc = exposed_run_checks(product_state(h), "trx_run_exposed", nshift, shift, out, msg)) return fail(h, rc, msg);
+  // (the pairs alone: no moments, and no high-pass -- a run of the pixel stage, as trx_run_pixels is)
+  PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
+  if (const int rc = pixel_run(h, "trx_run_exposed", a, o, spectrum, PR, shift, dbg)) return rc;
+  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, PR.ext.pair_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
   return TRX_OK;
 }
 
@@ -3421,7 +3492,7 @@ int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o,
   if (!h) return TRX_E_ARG;
   std::string msg;
   if (const int rc = observed_run_checks(product_state(h), "trx_run_filtered_moments", ObservedRun::Filtered, nshift, shift, mom, "mom", msg)) return fail(h, rc, msg);
-  PixelRun PR{h->pixels.get(), nshift, h->observed.get(), h->filter.get()};
+  PixelRun PR{h->pixels.get(), nshift, h->observed.get(), h->filter.get()}; PR.ex = h->exposures.get();
   if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, PR, shift, dbg)) return rc;
   // (the run has been waited for)
   HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));
@@ -3638,6 +3709,10 @@ struct trx_batch {
   int32_t k = 0; BatchJob job; bool wants_broadening = false;
   // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none)
   std::vector<trx_broadening> broad;
+  // trx_batch_set_exposures: one table for all atmospheres or one per atmosphere (empty: none), the arrays copied; a worker
+  // installs the atmosphere's on its handle first where the call's rows are exposures (wants_exposures: an exposed, moment
+  // or filtered-moment run)
+  std::vector<ExposureSet> expo; bool wants_exposures = false;
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
 };
@@ -3703,6 +3778,15 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
           // (this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
           if (b->wants_broadening)
             rc = trx_set_broadening(hj, b->broad.empty() ? nullptr : &b->broad[b->broad.size() == 1 ? 0 : (size_t)j]);
+          // (and its exposure table -- checked whole by trx_batch_set_exposures; none: cleared)
+          if (rc == TRX_OK && b->wants_exposures) {
+            if (b->expo.empty()) rc = trx_set_exposures(hj, nullptr);
+            else {
+              const ExposureSet &E = b->expo[b->expo.size() == 1 ? 0 : (size_t)j];
+              const trx_exposures ex{E.nexp, 0, E.scale.empty() ? nullptr : E.scale.data(), E.smear.empty() ? nullptr : E.smear.data()};
+              rc = trx_set_exposures(hj, &ex);
+            }
+          }
           if (rc == TRX_OK) rc = b->job(hj, j);
           if (rc != TRX_OK) {
             std::lock_guard<std::mutex> lk(b->mu);
@@ -3721,11 +3805,11 @@ int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
 }
 
 // one call of the batch: `job` for each of k atmospheres on whichever handle is free; returns when every worker is done
-static int batch_call(trx_batch *b, int32_t k, bool wants_broadening, const BatchJob &job)
+static int batch_call(trx_batch *b, int32_t k, bool wants_broadening, const BatchJob &job, bool wants_exposures = false)
 {
   if (k == 0) return TRX_OK;
   std::unique_lock<std::mutex> lk(b->mu);
-  b->k = k; b->job = job; b->wants_broadening = wants_broadening;
+  b->k = k; b->job = job; b->wants_broadening = wants_broadening; b->wants_exposures = wants_exposures;
   b->next.store(0); b->rc = TRX_OK; b->err.clear();
   b->busy = (int32_t)b->workers.size();
   b->epoch++;
@@ -3808,7 +3892,9 @@ int trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm, const t
 
 int trx_batch_set_pixels(trx_batch *b, const trx_pixels *px)
 {
-  return batch_install<PixelSet>(b, [=](trx_handle *h, std::unique_ptr<PixelSet> &S) { return make_pixel_set(h, px, S); }, install_pixel_set);
+  const int rc = batch_install<PixelSet>(b, [=](trx_handle *h, std::unique_ptr<PixelSet> &S) { return make_pixel_set(h, px, S); }, install_pixel_set);
+  if (rc == TRX_OK) b->expo.clear();                      // (the exposure tables go with the observed set)
+  return rc;
 }
 
 int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
@@ -3825,7 +3911,51 @@ int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_
 
 int trx_batch_set_observed(trx_batch *b, const trx_observed *ob)
 {
-  return batch_install<ObservedSet>(b, [=](trx_handle *h, std::unique_ptr<ObservedSet> &S) { return make_observed_set(h, ob, S); }, install_observed_set);
+  const int rc = batch_install<ObservedSet>(b, [=](trx_handle *h, std::unique_ptr<ObservedSet> &S) { return make_observed_set(h, ob, S); }, install_observed_set);
+  if (rc == TRX_OK) b->expo.clear();                      // (the exposure tables go with the observed set)
+  return rc;
+}
+
+// the batch's exposure tables, one for all atmospheres or one each: all entries are checked before any is kept, or none is
+int trx_batch_set_exposures(trx_batch *b, int32_t n, const trx_exposures *ex)
+{
+  g_comm_err.clear();
+  if (!b || b->hs.empty()) return TRX_E_ARG;
+  if (n < 0 || (n > 0 && !ex)) { g_comm_err = "trx_batch_set_exposures: n < 0 or a NULL array"; return TRX_E_ARG; }
+  std::vector<ExposureSet> keep;
+  // (the handles are made from one description and carry one observed set: what the first accepts, all accept)
+  for (int32_t j = 0; j < n; j++) {
+    std::unique_ptr<ExposureSet> S;
+    const int rc = make_exposure_set(b->hs[0], ex + j, S);
+    if (rc) { g_comm_err = "entry " + std::to_string(j) + ": " + b->hs[0]->err; return rc; }
+    if (!S) { g_comm_err = "trx_batch_set_exposures: entry " + std::to_string(j) + " has nexp 0 (n = 0 clears)"; return TRX_E_ARG; }
+    try { keep.push_back(std::move(*S)); } catch (...) { g_comm_err = "trx_batch_set_exposures: out of host memory"; return TRX_E_NOMEM; }
+  }
+  b->expo = std::move(keep);
+  if (n == 0) for (trx_handle *h : b->hs) h->exposures.reset();
+  return TRX_OK;
+}
+
+// a run of k atmospheres whose rows are exposures takes one table for all, one each, or none
+static int batch_exposures_fit(trx_batch *b, int32_t k, const char *who)
+{
+  const size_t n = b->expo.size();
+  if (n <= 1 || n == (size_t)k || k == 0) return TRX_OK;
+  g_comm_err = std::string(who) + ": " + std::to_string(n) + " exposure tables installed (trx_batch_set_exposures) for " + std::to_string(k) + " atmospheres";
+  return TRX_E_ARG;
+}
+
+int trx_run_batch_exposed(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
+                          double *const *out)
+{
+  g_comm_err.clear();
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !out))) { g_comm_err = "trx_run_batch_exposed: bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_exposed: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  if (b->expo.empty()) { g_comm_err = "trx_run_batch_exposed: no exposure table installed (trx_batch_set_exposures)"; return TRX_E_ARG; }
+  if (const int rc = batch_rows_check("trx_run_batch_exposed", k, {{"shift", shift}, {"out", out}}, g_comm_err)) return rc;
+  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_exposed")) return rc;
+  if (const int rc = batch_exposures_fit(b, k, "trx_run_batch_exposed")) return rc;
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_exposed(h, atm + j, opts, nullptr, nshift, shift[j], out[j], nullptr); }, true);
 }
 
 int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
@@ -3836,7 +3966,8 @@ int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx
   if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
   if (const int rc = batch_rows_check("trx_run_batch_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_moments")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_moments(h, atm + j, opts, nullptr, nshift, shift[j], mom[j], nullptr); });
+  if (const int rc = batch_exposures_fit(b, k, "trx_run_batch_moments")) return rc;
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_moments(h, atm + j, opts, nullptr, nshift, shift[j], mom[j], nullptr); }, true);
 }
 
 int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nlag, const double *const *lag,
@@ -3884,7 +4015,8 @@ int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, 
   if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_moments: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
   if (const int rc = batch_rows_check("trx_run_batch_filtered_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_moments")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_moments(h, atm + j, opts, nullptr, nshift, shift[j], nullptr, mom[j], nullptr); });
+  if (const int rc = batch_exposures_fit(b, k, "trx_run_batch_filtered_moments")) return rc;
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_moments(h, atm + j, opts, nullptr, nshift, shift[j], nullptr, mom[j], nullptr); }, true);
 }
 
 int trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map)

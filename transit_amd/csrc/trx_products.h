@@ -27,6 +27,7 @@ struct ProductState {
   int32_t nexp = 0, nseg = 0; const int64_t *seg = nullptr;      // the observed set's, seg its [nseg + 1] host bounds (null: none)
   bool filter = false;                                 // a filter is installed
   bool highpass = false;                               // a high-pass is installed
+  bool exposures = false;                              // an exposure table is installed (trx_exposures.h)
 };
 
 inline int refuse(std::string &msg, int code, std::string text) { msg = std::move(text); return code; }

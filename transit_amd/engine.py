@@ -211,6 +211,7 @@ def hip_library():
         _abi.bind_cellmap_api(lib)
         _abi.bind_highpass_api(lib)
         _abi.bind_broaden_api(lib)
+        _abi.bind_exposures_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -420,6 +421,28 @@ class Engine(CEngine):
             raise EngineError(rc, "trx_run_broadened", self._last_error())
         return (out, spec) if spectrum else out
 
+    def set_exposures(self, ex):
+        """trx_set_exposures: install an exposure table (a transit_amd.exposures.Exposures; None or an empty one: clear
+        it) over the observed set in force: a scale and a Doppler-smear half-width per exposure.  run_exposed, run_moments
+        and run_filtered_moments then take it; set_observed and set_pixels drop it.  No device work: cheap per likelihood
+        call."""
+        n = len(ex) if ex is not None else 0
+        rc = self._lib.trx_set_exposures(self._h, C.byref(ex.to_c()) if n else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_exposures", self._last_error())
+
+    def run_exposed(self, atm, opts, shifts, spectrum: bool = False):
+        """trx_run_exposed: the pairs [nexp, npix, 2] of this shard at the exposures' Doppler shifts with the installed
+        exposure table (transit_amd.exposures.reference) -- and, with spectrum=True, (pairs, spectrum), the spectrum bit
+        for bit what run() gives."""
+        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        out = np.zeros((sh.size, getattr(self, "npix", 0), 2))
+        spec = np.zeros(self.nwn) if spectrum else None
+        rc = self._lib.trx_run_exposed(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(out), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_exposed", self._last_error())
+        return (out, spec) if spectrum else out
+
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
         memory) into d_all in rank order, ncclAllGather over the handle's communicator (a device
@@ -599,6 +622,24 @@ class Batch:
         that atmosphere's broadening, bit for bit."""
         out = np.zeros((len(atms), self.nwn))
         self._call("trx_run_batch_broadened", atms, opts, _rows(out))
+        return out
+
+    def set_exposures(self, ex):
+        """trx_batch_set_exposures: one transit_amd.exposures.Exposures for every atmosphere of the following exposed,
+        moment and filtered-moment runs, or a list with one per atmosphere (None or an empty list: clear); all entries
+        are accepted, or none is kept.  The arrays are copied."""
+        xs = [] if ex is None else list(ex) if isinstance(ex, (list, tuple)) else [ex]
+        arr = (_abi.TrxExposures * max(len(xs), 1))(*[x.to_c() for x in xs])
+        rc = self._lib.trx_batch_set_exposures(self._b, len(xs), arr)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_exposures", self._err())
+
+    def run_exposed(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
+        """trx_run_batch_exposed: [K, nexp, npix, 2] for shifts of shape [K][nexp] (atmosphere j at its own shifts and
+        with its own table), each atmosphere's pairs what Engine.run_exposed gives, bit for bit."""
+        sh = _per_atmosphere("run_exposed", "shifts of shape [K][nexp]", shifts, len(atms))
+        out = np.zeros((len(atms), sh.shape[1], getattr(self, "npix", 0), 2))
+        self._call("trx_run_batch_exposed", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
     def close(self):
