@@ -517,6 +517,51 @@ int  trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm 
                                     int32_t nshift, const double *const *shift /* [k] -> [nshift] */,
                                     double *const *mom /* [k] -> [nexp][nseg][TRX_NMOMENT] */);
 
+/* The WEIGHTED detrending filter: the filter slot's second kind.  The plain filter projects every pixel column of a
+ * segment with the same coefficients; the detrending applied to real data (SYSREM, PCA with masks) is a WEIGHTED fit
+ * per column, and the model has to go through the same operation (Gibson et al. 2022):
+ *   M' = M - U (U^T L U)^-1 U^T L M,    L = diag of the column's own weights
+ * A weighted filter has one ncomp (1 .. TRX_FILTER_MAX) and per segment s the time vectors U = basis[s] ([nexp][ncomp]);
+ * a segment that wants fewer components must not pad with zeros (a zero vector is a singular pivot).  The weights are the
+ * observed set's weight[v][p] (NULL: all 1).  For pixel p of segment s, g[v] = gain_p * (a / b) as in the plain filter,
+ * w[v] = weight[v][p], n = ncomp.  Every operation is IEEE double rounded once, no fused multiply-add; sums start from
+ * +0 and run in the order written.
+ *
+ * At install, once per column:
+ *   for j = 0 .. n-1, k = 0 .. j:   N_jk = sum over v ascending of (U[v][j] * w[v]) * U[v][k]
+ *   for j = 0 .. n-1:
+ *     for k = 0 .. j-1:  s = N_jk;  for m = 0 .. k-1: s = s - T_jm * L_km;   T_jk = s;  L_jk = s / D_k
+ *     D_j = N_jj;        for k = 0 .. j-1: D_j = D_j - T_jk * L_jk
+ *     pivot j is SINGULAR if not (D_j > TRX_WFILTER_PIVOT * N_jj)             (N_jj = 0 and NaN included)
+ * Per run:
+ *   y_j = sum over v ascending of (U[v][j] * w[v]) * g[v]
+ *   z_j = y_j - (sum over k < j, k ascending, of L_jk * z_k);   q_j = z_j / D_j            j ascending
+ *   c_j = q_j - (sum over k > j, k ascending, of L_kj * c_k)                               j descending
+ *   r_v = sum over j ascending of U[v][j] * c_j;                g'[v] = g[v] - r_v
+ * A column is LIVE when b > 0 at every exposure (the plain filter's rule) AND no pivot was singular; any other column is
+ * DEAD and all its values are quiet NaN.  The pivot rule makes dead a column with fewer positive weights than
+ * components, a column masked at every exposure, and a column whose basis is degenerate under its weights.  The moments
+ * skip NaN values: such a column contributes nothing.  The kernels pad the components to 4, 8 or 16; a padded component
+ * takes no part in a pivot and changes no bit.  The bits of a value depend on its column's pairs, gain and weights and on
+ * its segment's basis and ncomp only.
+ *
+ * The weighted filter occupies the handle's ONE filter slot: trx_set_weighted_filter replaces a plain filter,
+ * trx_set_filter a weighted one; f NULL or ncomp = 0 clears the slot; trx_set_observed and trx_set_pixels drop it as
+ * they drop the plain one.  nsingular, when given, receives the number of columns, over all npix, with a singular pivot
+ * (0 for a clearing call).  With it installed trx_run_filtered_moments, trx_run_filtered_map and their batch forms run
+ * the weighted kernels where they ran the plain ones: same signatures, refusals and outputs, the same input pairs (after
+ * the exposure table and the high-pass where those are installed).  Every other entry point is unchanged, bit for bit.
+ * TRX_E_ARG, the reason in trx_last_error, the previous filter of either kind left in force: no observed set installed,
+ * ncomp < 0 or > TRX_FILTER_MAX, a NULL basis, a non-finite basis entry (naming "segment S").
+ * trx_batch_set_weighted_filter installs it on every handle of the batch, or on none (trx_last_error(NULL)). */
+#define TRX_WFILTER_PIVOT 0x1p-26           /* a pivot at or below this share of its diagonal entry: singular */
+typedef struct {
+  int32_t ncomp, pad;        /* components, 1 .. TRX_FILTER_MAX (0: clear); pad: 0                       */
+  const double *basis;       /* [nseg][nexp][ncomp], finite: the time vectors U of every segment          */
+} trx_wfilter;               /* 16 bytes */
+int  trx_set_weighted_filter(trx_handle *h, const trx_wfilter *f, int64_t *nsingular /* may be NULL */);
+int  trx_batch_set_weighted_filter(trx_batch *b, const trx_wfilter *f);
+
 /* Rotational broadening of the spectrum on the device, between the spectrum and the detector pixels: the planet's own
  * velocity broadening -- the rotation kernel of v sin i with linear limb darkening -- that a high-resolution retrieval
  * applies before the instrument's line-spread function.  Its width is a fitted parameter (it changes with every

@@ -102,6 +102,13 @@ class TrxFilter(C.Structure):
     _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("fwd", c_double_p), ("back", c_double_p)]
 
 
+WFILTER_PIVOT = 2.0 ** -26      # TRX_WFILTER_PIVOT: a pivot at or below this share of its diagonal entry is singular
+
+
+class TrxWfilter(C.Structure):
+    _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("basis", c_double_p)]
+
+
 HIGHPASS_MAX_HALF = 1024
 
 
@@ -279,6 +286,10 @@ def bind_filter_api(lib):
     lib.trx_run_filtered_moments.restype = C.c_int
     lib.trx_batch_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]
     lib.trx_batch_set_filter.restype = C.c_int
+    lib.trx_set_weighted_filter.argtypes = [C.c_void_p, C.POINTER(TrxWfilter), C.POINTER(C.c_int64)]
+    lib.trx_set_weighted_filter.restype = C.c_int
+    lib.trx_batch_set_weighted_filter.argtypes = [C.c_void_p, C.POINTER(TrxWfilter)]
+    lib.trx_batch_set_weighted_filter.restype = C.c_int
     lib.trx_run_batch_filtered_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                                    C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_filtered_moments.restype = C.c_int

@@ -43,6 +43,7 @@
 #include "trx_vmap.hip.h"
 #include "trx_cellmap.hip.h"
 #include "trx_filter.hip.h"
+#include "trx_wfilter.hip.h"
 #include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
@@ -53,6 +54,7 @@
 #include "../trx_vmap.h"
 #include "../trx_products.h"
 #include "../trx_exposures.h"
+#include "../trx_wfilter.h"
 
 using namespace trx;
 
@@ -101,6 +103,10 @@ struct ObservedSet {
 struct FilterSet {
   int32_t ncomp = 0, npad = 0, nexp = 0, nseg = 0; int64_t npix = 0, ntiles = 0;
   DevBuf d_fwd, d_back, d_tiles;                     // [nseg][nexp][npad] each, FilterTile[ntiles]
+  // a weighted filter (trx_set_weighted_filter, trx_wfilter.hip.h): its padded basis in d_back (d_fwd stays empty), and
+  // every column's factor [nfac][npix] and pivot flag [npix], made by k_wfilter_factor when it was installed
+  bool weighted = false; int32_t nfac = 0;
+  DevBuf d_fac, d_live;
 };
 // a high-pass installed by trx_set_highpass over the observed set (trx_highpass.hip.h): the taps, their full-window sum and
 // the tiles of the observed set's segments; obs: that set (it goes when the set does), whose gains the kernel reads
@@ -2831,12 +2837,51 @@ int Run::highpass_kernels()
   return TRX_OK;
 }
 
+// ---- the weighted filter of those pairs (trx_wfilter.hip.h), where the plain one runs
+// what the weighted kernels read of the set F over the observed set O, whole: the padded basis, the tiles, every column's
+// factor and flag, the weights
+static bool wfilter_set_complete(const FilterSet &F, const ObservedSet &O)
+{
+  const WfilterExtents WX = wfilter_extents(F.npix, F.nexp, F.nseg, F.ncomp, F.npad, F.ntiles, kFiltWaves);
+  return F.weighted && F.d_back.p && F.d_tiles.p && F.d_fac.p && F.d_live.p && F.nexp >= 1 && F.nseg >= 1 && F.ncomp >= 1 && F.ncomp <= F.npad &&
+         (F.npad == 4 || F.npad == 8 || F.npad == 16) && F.npix >= 1 && F.ntiles >= 1 && F.npix == O.npix && F.nexp == O.nexp && F.nseg == O.nseg &&
+         F.nfac == WX.nfac && F.d_back.bytes >= WX.basis_bytes && F.d_fac.bytes >= WX.fac_bytes && F.d_live.bytes >= WX.live_bytes &&
+         F.d_tiles.bytes >= sizeof(FilterTile) * (size_t)F.ntiles &&
+         (!O.d_weight.p || O.d_weight.bytes >= sizeof(double) * (size_t)O.nexp * (size_t)O.npix);
+}
+
+static int launch_wfilter(trx_handle *h, const PixelRun &px, hipStream_t st)
+{
+  const FilterSet &F = *px.filt; const PixelExtents &X = px.ext;
+  const ObservedSet *O = px.obs;
+  WfilterArgs FA{};
+  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
+  FA.pairs = px.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = O && !px.hp ? O->d_gain.as<double>() : nullptr;
+  FA.weight = O ? O->d_weight.as<double>() : nullptr; FA.basis = F.d_back.as<double>(); FA.fac = F.d_fac.as<double>(); FA.live = F.d_live.as<int32_t>();
+  FA.tiles = F.d_tiles.as<FilterTile>(); FA.val = h->d_pixval.as<double>();
+  FA.npix = F.npix; FA.ntiles = F.ntiles; FA.nexp = F.nexp; FA.ncomp = F.ncomp;
+  const int64_t blocks = (FA.ntiles + kFiltWaves - 1) / kFiltWaves;
+  // (every address the kernel reads or writes: pairs and values over [nexp][npix] -- the tiles lie in [0, npix) and name
+  // segments below nseg, made so when the filter was --, the gains, and the set's own arrays: wfilter_set_complete)
+  if (!O || !FA.pairs || !FA.val || !wfilter_set_complete(F, *O) || F.npix != px.set->npix || F.nexp != px.nshift ||
+      X.pairs != (int64_t)F.nexp * F.npix || h->d_pixout.bytes < X.pair_bytes || (px.hp && (px.hpx.pairs != X.pairs || h->d_pixhp.bytes < px.hpx.pair_bytes)) ||
+      X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes || (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) ||
+      blocks < 1 || blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the weighted filter kernel (not launched)");
+  const dim3 grid((unsigned)blocks), block(64 * kFiltWaves);
+  if (F.npad == 4) hipLaunchKernelGGL(k_pixel_wfilter<4>, grid, block, 0, st, FA);
+  else if (F.npad == 8) hipLaunchKernelGGL(k_pixel_wfilter<8>, grid, block, 0, st, FA);
+  else hipLaunchKernelGGL(k_pixel_wfilter<16>, grid, block, 0, st, FA);
+  return TRX_OK;
+}
+
 // ---- the filter of those pairs along the exposure axis (trx_filter.hip.h), behind the pixel kernel on its queue and
 // ahead of the moment kernel, which then reads its values; a pass that resumes deeper queues all three again.
 int Run::filter_kernels()
 {
   const PixelRun *const px = want.px;
   if (!px || !px->filt) return TRX_OK;
+  if (px->filt->weighted) return launch_wfilter(h, *px, tst);
   const FilterSet &F = *px->filt; const PixelExtents &X = px->ext;
   const ObservedSet *O = px->obs;
   FilterArgs FA{};
@@ -3486,6 +3531,62 @@ int trx_set_filter(trx_handle *h, const trx_filter *f)
   return TRX_OK;
 }
 
+// The weighted filter (trx_wfilter.hip.h), checked whole before anything is replaced: the device gets wfilter_layout's basis
+// and tiles, k_wfilter_factor makes every column's factor and flag from them and the observed set's weights, and the flags
+// come back once for the count of the singular columns.
+static int make_wfilter_set(trx_handle *h, const trx_wfilter *f, std::unique_ptr<FilterSet> &out, int64_t *nsingular)
+{
+  out.reset();
+  if (nsingular) *nsingular = 0;
+  if (!f || f->ncomp == 0) return TRX_OK;               // (clear)
+  const ProductState P = product_state(h);
+  std::string msg; WfilterLayout L;
+  if (const int rc = wfilter_set_checks(P, f, msg)) return fail(h, rc, msg);
+  std::unique_ptr<FilterSet> S(new (std::nothrow) FilterSet);
+  if (!S) return fail(h, TRX_E_NOMEM, "weighted filter: out of host memory");
+  if (const int rc = wfilter_layout(P, f, L, msg)) return fail(h, rc, msg);
+  S->weighted = true;
+  S->ncomp = f->ncomp; S->npad = L.npad; S->nexp = P.nexp; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size();
+  const WfilterExtents WX = wfilter_extents(S->npix, S->nexp, S->nseg, S->ncomp, S->npad, S->ntiles, kFiltWaves);
+  S->nfac = WX.nfac;
+  std::vector<int32_t> live;
+  try { live.assign((size_t)S->npix, 0); } catch (...) { return fail(h, TRX_E_NOMEM, "weighted filter: out of host memory"); }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload(h, S->d_back, L.basis)) || (rc = upload(h, S->d_tiles, L.tiles)) || (rc = ensure(h, S->d_fac, WX.fac_bytes)) ||
+      (rc = ensure(h, S->d_live, WX.live_bytes)))
+    return rc;
+  // (a pixel outside every tile -- none: the segments cover [0, npix) -- would keep a zero factor and a zero flag)
+  HIPCHK(h, hipMemsetAsync(S->d_fac.p, 0, WX.fac_bytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(S->d_live.p, 0, WX.live_bytes, h->stream));
+  const ObservedSet *O = h->observed.get();
+  WfilterFactorArgs A{};
+  A.weight = O ? O->d_weight.as<double>() : nullptr; A.basis = S->d_back.as<double>(); A.tiles = S->d_tiles.as<FilterTile>();
+  A.fac = S->d_fac.as<double>(); A.live = S->d_live.as<int32_t>(); A.npix = S->npix; A.ntiles = S->ntiles; A.nexp = S->nexp; A.ncomp = S->ncomp;
+  // (every address the kernel reads or writes: wfilter_set_complete -- the segments cover [0, npix): at least one tile)
+  if (!O || !wfilter_set_complete(*S, *O) || WX.blocks < 1 || WX.blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the weighted filter's factor kernel (not launched)");
+  const dim3 grid((unsigned)WX.blocks), block(64 * kFiltWaves);
+  if (S->npad == 4) hipLaunchKernelGGL(k_wfilter_factor<4>, grid, block, 0, h->stream, A);
+  else if (S->npad == 8) hipLaunchKernelGGL(k_wfilter_factor<8>, grid, block, 0, h->stream, A);
+  else hipLaunchKernelGGL(k_wfilter_factor<16>, grid, block, 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(live.data(), S->d_live.p, WX.live_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
+  if (nsingular) for (int32_t x : live) *nsingular += x ? 0 : 1;
+  out = std::move(S);
+  return TRX_OK;
+}
+
+int trx_set_weighted_filter(trx_handle *h, const trx_wfilter *f, int64_t *nsingular)
+{
+  if (!h) return TRX_E_ARG;
+  std::unique_ptr<FilterSet> S;
+  if (const int rc = make_wfilter_set(h, f, S, nsingular)) return rc;
+  install_filter_set(h, S);
+  return TRX_OK;
+}
+
 int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
                              double *values, double *mom, trx_debug *dbg)
 {
@@ -3578,6 +3679,11 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
   FA.pairs = PR.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = PR.hp ? nullptr : O->d_gain.as<double>();
   FA.fwd = F->d_fwd.as<double>(); FA.back = F->d_back.as<double>(); FA.tiles = F->d_tiles.as<FilterTile>(); FA.val = h->d_cm_val.as<double>();
   FA.npix = npix; FA.ntiles = F->ntiles; FA.nexp = nexp;
+  // (a weighted filter: k_cell_wfilter in k_cell_filter's place, over the same pairs, tiles, index rows and values)
+  const bool wt = F->weighted;
+  WfilterArgs WA{};
+  WA.pairs = FA.pairs; WA.gain = FA.gain; WA.weight = O->d_weight.as<double>(); WA.basis = FA.back; WA.fac = F->d_fac.as<double>();
+  WA.live = F->d_live.as<int32_t>(); WA.tiles = FA.tiles; WA.val = FA.val; WA.npix = npix; WA.ntiles = F->ntiles; WA.nexp = nexp; WA.ncomp = F->ncomp;
   CellMomArgs MA{};
   MA.val = FA.val; MA.data = O->d_data.as<double>(); MA.weight = O->d_weight.as<double>(); MA.seg_first = O->d_seg.as<int64_t>();
   MA.mom = h->d_cm_mom.as<double>(); MA.npix = npix; MA.nexp = nexp; MA.nseg = nseg;
@@ -3590,11 +3696,12 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
   // [0, npix) naming segments below nseg, made so when the filter was, the gains, the two padded matrices; the values over
   // [chunk][nexp][npix]; data and weights over [nexp][npix], the segments in [0, npix), checked when the set was made; the
   // moment rows over [chunk][nexp][nseg]; the chunk's cells of the map)
-  if (!FA.pairs || !FA.fwd || !FA.back || !FA.tiles || !FA.val || !MA.data || !MA.seg_first || !MA.mom || !h->d_cm_map.p ||
+  if ((wt ? !wfilter_set_complete(*F, *O) : !FA.fwd || F->d_fwd.bytes < mat) ||
+      !FA.pairs || !FA.back || !FA.tiles || !FA.val || !MA.data || !MA.seg_first || !MA.mom || !h->d_cm_map.p ||
       F->nexp != nexp || F->nseg != nseg || F->npix != npix || npix < 1 || nseg < 1 || npix != PR.set->npix || F->ncomp < 1 || F->ncomp > F->npad ||
       (F->npad != 4 && F->npad != 8 && F->npad != 16) || F->ntiles < 1 || PR.nshift != nlag || PR.filt || PR.trail || PR.obs ||
       PR.ext.pairs != (int64_t)nlag * npix || h->d_pixout.bytes < PR.ext.pair_bytes || (PR.hp && (PR.hpx.pairs != PR.ext.pairs || h->d_pixhp.bytes < PR.hpx.pair_bytes)) ||
-      F->d_fwd.bytes < mat || F->d_back.bytes < mat || F->d_tiles.bytes < sizeof(FilterTile) * (size_t)F->ntiles ||
+      F->d_back.bytes < mat || F->d_tiles.bytes < sizeof(FilterTile) * (size_t)F->ntiles ||
       (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)npix) || O->d_data.bytes < obs_cells || (MA.weight && O->d_weight.bytes < obs_cells) ||
       O->d_seg.bytes < sizeof(int64_t) * ((size_t)nseg + 1) || O->seg.size() != (size_t)nseg + 1 || O->seg.front() != 0 || O->seg.back() != npix ||
       CX.chunk < 1 || CX.nchunks < 1 || CX.last_chunk < 1 || CX.last_chunk > CX.chunk || (CX.nchunks - 1) * CX.chunk + CX.last_chunk != CX.cells ||
@@ -3608,9 +3715,15 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
     const int64_t cell0 = q * CX.chunk, n = q + 1 < CX.nchunks ? CX.chunk : CX.last_chunk;      // cells [cell0, cell0 + n)
     FA.index = MA.index = SA.index = TA.index + cell0 * nexp;
     FA.nwaves = n * F->ntiles; MA.nrows = n * nexp * nseg;
+    WA.index = FA.index; WA.nwaves = FA.nwaves;
     SA.map = h->d_cm_map.as<double>() + cell0; SA.ncells = n;
     const dim3 fgrid((unsigned)((FA.nwaves + kFiltWaves - 1) / kFiltWaves)), fblock(64 * kFiltWaves);
-    if (F->npad == 4) hipLaunchKernelGGL(k_cell_filter<4>, fgrid, fblock, 0, h->stream, FA);
+    if (wt) {
+      if (F->npad == 4) hipLaunchKernelGGL(k_cell_wfilter<4>, fgrid, fblock, 0, h->stream, WA);
+      else if (F->npad == 8) hipLaunchKernelGGL(k_cell_wfilter<8>, fgrid, fblock, 0, h->stream, WA);
+      else hipLaunchKernelGGL(k_cell_wfilter<16>, fgrid, fblock, 0, h->stream, WA);
+    }
+    else if (F->npad == 4) hipLaunchKernelGGL(k_cell_filter<4>, fgrid, fblock, 0, h->stream, FA);
     else if (F->npad == 8) hipLaunchKernelGGL(k_cell_filter<8>, fgrid, fblock, 0, h->stream, FA);
     else hipLaunchKernelGGL(k_cell_filter<16>, fgrid, fblock, 0, h->stream, FA);
     hipLaunchKernelGGL(k_cell_moments, dim3((unsigned)((MA.nrows + kMomWaves - 1) / kMomWaves)), dim3(64 * kMomWaves), 0, h->stream, MA);
@@ -4004,6 +4117,11 @@ int trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp)
 int trx_batch_set_filter(trx_batch *b, const trx_filter *f)
 {
   return batch_install<FilterSet>(b, [=](trx_handle *h, std::unique_ptr<FilterSet> &S) { return make_filter_set(h, f, S); }, install_filter_set);
+}
+
+int trx_batch_set_weighted_filter(trx_batch *b, const trx_wfilter *f)
+{
+  return batch_install<FilterSet>(b, [=](trx_handle *h, std::unique_ptr<FilterSet> &S) { return make_wfilter_set(h, f, S, nullptr); }, install_filter_set);
 }
 
 int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,

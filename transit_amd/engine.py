@@ -351,6 +351,17 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_set_filter", self._last_error())
 
+    def set_weighted_filter(self, wf) -> int:
+        """trx_set_weighted_filter: install a weighted detrending filter (a transit_amd.xcor.WeightedFilter; None: clear
+        the slot) over the observed set in force, in the slot set_filter fills: every pixel column is projected by least
+        squares under its own weights.  Returns the number of columns the pivot rule makes dead.  run_filtered_moments
+        and run_filtered_map then take it where they took the plain filter."""
+        nsing = C.c_int64(0)
+        rc = self._lib.trx_set_weighted_filter(self._h, C.byref(wf.to_c()) if wf is not None else None, C.byref(nsing))
+        if rc != 0:
+            raise EngineError(rc, "trx_set_weighted_filter", self._last_error())
+        return int(nsing.value)
+
     def run_filtered_moments(self, atm, opts, shifts, spectrum: bool = False, values: bool = False):
         """trx_run_filtered_moments: the moments [nexp, nseg, 7] of the FILTERED pixels (transit_amd.xcor) against the
         observed set; with spectrum=True and/or values=True a tuple (moments[, spectrum][, values]) -- the spectrum
@@ -585,6 +596,12 @@ class Batch:
         rc = self._lib.trx_batch_set_filter(self._b, C.byref(filt.to_c()) if filt is not None else None)
         if rc != 0:
             raise EngineError(rc, "trx_batch_set_filter", self._err())
+
+    def set_weighted_filter(self, wf):
+        """trx_batch_set_weighted_filter: the same weighted filter on every handle of the batch, or on none."""
+        rc = self._lib.trx_batch_set_weighted_filter(self._b, C.byref(wf.to_c()) if wf is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_batch_set_weighted_filter", self._err())
 
     def set_highpass(self, hp):
         """trx_batch_set_highpass: the same high-pass on every handle of the batch, or on none."""

@@ -49,6 +49,21 @@ and the filtered moments are the seven sums with g' in place of g over the pixel
     reference_values(values, obs)                        the moments from a value matrix [nexp, npix], sums by math.fsum
     abs_reference_values(values, obs)                    the same with |f| and |values|
 
+The weighted filter (Engine.set_weighted_filter; trx_set_weighted_filter), the filter slot's second kind: every pixel column
+is projected by least squares under its OWN weights w[v] = weight[v][p], with its segment's time vectors U = basis[s]
+([nexp, ncomp]): g' = g - U (U^T diag(w) U)^-1 U^T diag(w) g.  The column's normal matrix is factorised (L D L^T) when the
+filter is installed; a pivot at or below 2^-26 of its diagonal entry is singular and the column dead (NaN), as is a column
+with b <= 0 at any exposure.  The operations and their order are stated in include/transit_hip.h.
+
+    WeightedFilter(basis)                                a weighted filter; to_c() its trx_wfilter
+    svd_basis(data, seg_first, ncomp)                    the back of svd_filter: each segment's leading left singular vectors
+    sysrem_basis(data, weight, seg_first, ncomp, niter)  SYSREM's time vectors (Tamuz et al. 2005), normalised
+    weighted_factor(obs, wf)                             (L, D, live) of every column: the install step, bit for bit the device's
+    weighted_pivots(obs, wf)                             every pivot's share D_j / N_jj of its diagonal entry
+    weighted_filter_reference(pairs, obs, wf)            g' [nexp, npix] in double in the definition's order: bit for bit the device's
+    weighted_filter_exact(pairs, obs, wf)                the same projection in np.longdouble, rounded at the end
+    weighted_filter_bound(pairs, obs, wf)                how far a double evaluation can lie from the exact projection
+
 The detection map with the filter applied to every cell's own model matrix (Engine.run_filtered_map /
 Batch.run_filtered_map; trx_run_filtered_map): a cell takes at every exposure the row of the lag NEAREST to its velocity,
 that matrix goes through the filter and the moments above, and the cell is the statistic added over the segments and
@@ -648,12 +663,246 @@ def cell_bound(mom, vm: VelocityMap) -> float:
     return (c + mom.shape[1] + mom.shape[0]) * _EPS * s
 
 
-def filtered_map_reference(pairs_at_lags, obs: Observed, filt: Filter, vm: VelocityMap) -> np.ndarray:
+@dataclass
+class WeightedFilter:
+    """One trx_wfilter: the time vectors basis [nseg, nexp, ncomp] (finite) of every segment.  The weights of the
+    projection are the observed set's."""
+    basis: np.ndarray
+
+    def __post_init__(self):
+        self.basis = np.ascontiguousarray(self.basis, dtype=np.float64)
+        if self.basis.ndim != 3:
+            raise ValueError("WeightedFilter: basis of shape [nseg][nexp][ncomp]")
+
+    @property
+    def nseg(self) -> int:
+        return int(self.basis.shape[0])
+
+    @property
+    def nexp(self) -> int:
+        return int(self.basis.shape[1])
+
+    @property
+    def ncomp(self) -> int:
+        return int(self.basis.shape[2])
+
+    def to_c(self):
+        """The trx_wfilter of the filter (the array stays owned by this object)."""
+        c = _abi.TrxWfilter()
+        c.ncomp, c.pad = self.ncomp, 0
+        c.basis = self.basis.ctypes.data_as(_abi.c_double_p)
+        return c
+
+
+def svd_basis(data, seg_first, ncomp: int) -> np.ndarray:
+    """[nseg, nexp, ncomp]: each segment's leading left singular vectors, the `back` of svd_filter.  A segment with fewer
+    singular vectors than ncomp keeps zero vectors there -- singular pivots under a weighted filter."""
+    return svd_filter(data, seg_first, ncomp).back
+
+
+def sysrem_basis(data, weight, seg_first, ncomp: int, niter: int = 10) -> np.ndarray:
+    """[nseg, nexp, ncomp]: the time vectors of SYSREM (Tamuz, Mazeh & Zucker 2005) per segment, one component after
+    another.  With r the segment's residuals [nexp, n] (the data at first) and w their weights (None: all 1), a
+    component starts from a = 1 and alternates, niter times,
+
+        c_p = sum_v w r a / sum_v w a^2        a_v = sum_p w r c / sum_p w c^2        (0 where the denominator is 0)
+
+    then a is normalised to unit length (c takes the factor), kept as the component, and a c^T leaves the residuals."""
+    data = np.asarray(data, dtype=np.float64)
+    w_all = np.ones_like(data) if weight is None else np.asarray(weight, dtype=np.float64)
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    nexp, nseg = data.shape[0], seg.size - 1
+    out = np.zeros((nseg, nexp, ncomp))
+
+    def ratio(num, den):
+        return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+
+    for s in range(nseg):
+        r, w = data[:, seg[s]:seg[s + 1]].copy(), w_all[:, seg[s]:seg[s + 1]]
+        if r.shape[1] == 0:
+            continue
+        for i in range(ncomp):
+            a = np.ones(nexp)
+            c = np.zeros(r.shape[1])
+            for _ in range(niter):
+                c = ratio(np.sum(w * r * a[:, None], axis=0), np.sum(w * (a * a)[:, None], axis=0))
+                a = ratio(np.sum(w * r * c[None, :], axis=1), np.sum(w * (c * c)[None, :], axis=1))
+            norm = float(np.sqrt(np.sum(a * a)))
+            if norm > 0:
+                a, c = a / norm, c * norm
+            out[s, :, i] = a
+            r -= a[:, None] * c[None, :]
+    return out
+
+
+def _check_wfilter(obs: Observed, wf: WeightedFilter):
+    if (wf.nseg, wf.nexp) != (obs.nseg, obs.nexp):
+        raise ValueError("weighted filter of the observed set's nseg and nexp")
+
+
+def _wf_factor(obs: Observed, wf: WeightedFilter, dtype):
+    """(L [n, n, npix], D [n, npix], N_jj [n, npix]): the definition's install step in `dtype`, vectorised over the
+    columns, every operation in its order"""
+    _check_wfilter(obs, wf)
+    n, npix = wf.ncomp, obs.npix
+    w = (obs.weight if obs.weight is not None else np.ones_like(obs.data)).astype(dtype)
+    N = np.zeros((n, n, npix), dtype=dtype)
+    for s in range(obs.nseg):
+        k = slice(int(obs.seg_first[s]), int(obs.seg_first[s + 1]))
+        U = wf.basis[s].astype(dtype)
+        for j in range(n):
+            for i in range(j + 1):
+                acc = np.zeros(k.stop - k.start, dtype=dtype)
+                for v in range(obs.nexp):
+                    acc = acc + (U[v, j] * w[v, k]) * U[v, i]
+                N[j, i, k] = acc
+    T, L, D = np.zeros_like(N), np.zeros_like(N), np.zeros((n, npix), dtype=dtype)
+    with np.errstate(all="ignore"):
+        for j in range(n):
+            for i in range(j):
+                t = N[j, i].copy()
+                for m in range(i):
+                    t = t - T[j, m] * L[i, m]
+                T[j, i] = t
+                L[j, i] = t / D[i]
+            d = N[j, j].copy()
+            for i in range(j):
+                d = d - T[j, i] * L[j, i]
+            D[j] = d
+    return L, D, np.stack([N[j, j] for j in range(n)]) if n else np.zeros((0, npix), dtype=dtype)
+
+
+def _wf_apply(g, obs: Observed, wf: WeightedFilter, L, D, dtype):
+    """g' [nexp, npix] in `dtype` from g: the definition's run step, vectorised over the columns"""
+    n = wf.ncomp
+    w = (obs.weight if obs.weight is not None else np.ones_like(obs.data)).astype(dtype)
+    g = g.astype(dtype)
+    out = np.zeros(g.shape, dtype=dtype)
+    with np.errstate(all="ignore"):
+        for s in range(obs.nseg):
+            k = slice(int(obs.seg_first[s]), int(obs.seg_first[s + 1]))
+            U = wf.basis[s].astype(dtype)
+            y = []
+            for j in range(n):
+                acc = np.zeros(k.stop - k.start, dtype=dtype)
+                for v in range(obs.nexp):
+                    acc = acc + (U[v, j] * w[v, k]) * g[v, k]
+                y.append(acc)
+            z = []
+            for j in range(n):
+                t = np.zeros(k.stop - k.start, dtype=dtype)
+                for i in range(j):
+                    t = t + L[j, i, k] * z[i]
+                z.append(y[j] - t)
+            q = [z[j] / D[j, k] for j in range(n)]
+            c = [None] * n
+            for j in range(n - 1, -1, -1):
+                t = np.zeros(k.stop - k.start, dtype=dtype)
+                for i in range(j + 1, n):
+                    t = t + L[i, j, k] * c[i]
+                c[j] = q[j] - t
+            for v in range(obs.nexp):
+                r = np.zeros(k.stop - k.start, dtype=dtype)
+                for j in range(n):
+                    r = r + U[v, j] * c[j]
+                out[v, k] = g[v, k] - r
+    return out
+
+
+def weighted_pivots(obs: Observed, wf: WeightedFilter) -> np.ndarray:
+    """[npix, ncomp]: every pivot's share D_j / N_jj of its diagonal entry in the mirror (nan for N_jj = 0): a pivot is
+    singular when this is not above _abi.WFILTER_PIVOT"""
+    _, D, njj = _wf_factor(obs, wf, np.float64)
+    with np.errstate(all="ignore"):
+        return (D / njj).T
+
+
+def weighted_factor(obs: Observed, wf: WeightedFilter):
+    """(L [npix, ncomp, ncomp], D [npix, ncomp], live [npix]): every column's factor of trx_set_weighted_filter, the
+    definition's install step in numpy double in exactly its order -- the mirror of k_wfilter_factor, bit for bit.  L is
+    strictly lower triangular (the unit diagonal is implied); live: no pivot of the column is singular,
+    D_j > 2^-26 N_jj for every j.  What follows a singular pivot in L and D is whatever the arithmetic gives."""
+    L, D, njj = _wf_factor(obs, wf, np.float64)
+    with np.errstate(all="ignore"):
+        live = np.all(D > _abi.WFILTER_PIVOT * njj, axis=0) if wf.ncomp else np.ones(obs.npix, dtype=bool)
+    return np.ascontiguousarray(L.transpose(2, 0, 1)), np.ascontiguousarray(D.T), live
+
+
+def weighted_filter_reference(pairs, obs: Observed, wf: WeightedFilter) -> np.ndarray:
+    """g' [nexp, npix] of the weighted filter from the pixel pairs [nexp, npix, 2] of a run: the definition's run step in
+    numpy double in exactly its order, from weighted_factor's factor -- the mirror of k_pixel_wfilter, bit for bit.  A
+    column with b <= 0 at any exposure or with a singular pivot is NaN.  How far it can lie from the exact projection of
+    the same g: weighted_filter_bound."""
+    g, on = _model(pairs, obs)
+    L, D, live = weighted_factor(obs, wf)
+    out = _wf_apply(g, obs, wf, L.transpose(1, 2, 0), D.T, np.float64)
+    return np.where((live & np.all(on, axis=0))[None, :], out, np.nan)
+
+
+def weighted_filter_bound(pairs, obs: Observed, wf: WeightedFilter) -> np.ndarray:
+    """[nexp, npix]: how far a double evaluation of the definition (weighted_filter_reference, the device) can lie from
+    the exact weighted projection of the same g (weighted_filter_exact stands for it), NaN in the dead columns.  For one
+    column, with u = 2^-53, n = ncomp, N = U^T diag(w) U, y = U^T diag(w) g, c = N^-1 y, |.| taken entry by entry, to
+    first order in u:
+
+      - y_j: every term is two products, and nexp of them are added from +0:
+            |dy_j| <= (nexp + 1) u Ya_j,          Ya_j = sum_v |U_vj| w_v |g_v|;
+        in the same way |dN_jk| <= (nexp + 1) u Na_jk, Na_jk = sum_v |U_vj| w_v |U_vk|;
+      - the factor and the two triangular solves: the computed c solves (N + dN + E) c = y + dy with
+        |E| <= (3 n + 1) u |L| |D| |L^T|, the bound of a Cholesky solve (Higham, Accuracy and Stability of Numerical
+        Algorithms, theorems 10.3 and 10.4; with R = D^1/2 L^T this is |R^T| |R|: a row of the factor takes at most n
+        products and a division, each solve as many), and by Cauchy-Schwarz over the columns of R
+            (|R^T| |R|)_jk <= S_jk = sqrt(N_jj N_kk);
+      - so |dc| <= |N^-1| ((nexp + 1) u Ya + ((nexp + 1) u Na + (3 n + 1) u S) |c|);
+      - r_v = sum_j U_vj c_j, n products added from +0, and one subtraction:
+            |dg'_v| <= sum_j |U_vj| |dc_j| + n u sum_j |U_vj| |c_j| + u |g'_v|.
+
+    Doubled, for the terms of second order (the pivot rule keeps N far from singular in a live column).  N^-1 and c are
+    taken from numpy's inverse in double, whose own error is of second order here."""
+    _check_wfilter(obs, wf)
+    g, on = _model(pairs, obs)
+    live = weighted_factor(obs, wf)[2] & np.all(on, axis=0)
+    w = obs.weight if obs.weight is not None else np.ones_like(obs.data)
+    n, nexp, u = wf.ncomp, obs.nexp, 2.0 ** -53
+    out = np.full(g.shape, np.nan)
+    for s in range(obs.nseg):
+        k = np.arange(obs.seg_first[s], obs.seg_first[s + 1])
+        k = k[live[k]]
+        if k.size == 0:
+            continue
+        U, aU = wf.basis[s], np.abs(wf.basis[s])
+        N = np.einsum("vj,vp,vi->pji", U, w[:, k], U)
+        Na = np.einsum("vj,vp,vi->pji", aU, w[:, k], aU)
+        y, Ya = np.einsum("vj,vp->pj", U, w[:, k] * g[:, k]), np.einsum("vj,vp->pj", aU, w[:, k] * np.abs(g[:, k]))
+        Ninv = np.linalg.inv(N)
+        c = np.einsum("pji,pi->pj", Ninv, y)
+        d = np.sqrt(np.einsum("pjj->pj", N))
+        S = d[:, :, None] * d[:, None, :]
+        rhs = (nexp + 1) * u * Ya + np.einsum("pji,pi->pj", (nexp + 1) * u * Na + (3 * n + 1) * u * S, np.abs(c))
+        dc = np.einsum("pji,pi->pj", np.abs(Ninv), rhs)
+        gp = g[:, k] - U @ c.T
+        out[:, k] = 2.0 * (aU @ dc.T + n * u * (aU @ np.abs(c).T) + u * np.abs(gp))
+    return out
+
+
+def weighted_filter_exact(pairs, obs: Observed, wf: WeightedFilter) -> np.ndarray:
+    """The same least-squares projection with the factor and the solve in np.longdouble, rounded to double at the end; g
+    as the moments take it, the dead columns (NaN) the mirror's."""
+    g, on = _model(pairs, obs)
+    live = weighted_factor(obs, wf)[2] & np.all(on, axis=0)
+    L, D, _ = _wf_factor(obs, wf, np.longdouble)
+    out = _wf_apply(g, obs, wf, L, D, np.longdouble).astype(np.float64)
+    return np.where(live[None, :], out, np.nan)
+
+
+def filtered_map_reference(pairs_at_lags, obs: Observed, filt, vm: VelocityMap) -> np.ndarray:
     """The definition of trx_run_filtered_map in numpy: the map [nkp, nvsys] from the pixel pairs [nlag, npix, 2] of
     run_pixels at vm.lag.  Cell (i, j) takes at exposure v the row nearest_lags(vm)[i, j, v]; that matrix goes through
-    filter_reference and reference_values as a filtered run's does, and cell_value gives the cell.  A cell with a
+    filter_reference (a WeightedFilter: weighted_filter_reference) and reference_values as a filtered run's does, and
+    cell_value gives the cell.  A cell with a
     velocity outside the lag grid is nan.  (With a high-pass: highpass_pairs of highpass_reference of the pairs, and a
     gain-free copy of the observed set.)"""
+    values = weighted_filter_reference if isinstance(filt, WeightedFilter) else filter_reference
     pairs = np.asarray(pairs_at_lags, dtype=np.float64)
     if pairs.shape != (vm.nlag, obs.npix, 2):
         raise ValueError("pairs of shape [nlag][npix][2] with the map's nlag")
@@ -664,7 +913,7 @@ def filtered_map_reference(pairs_at_lags, obs: Observed, filt: Filter, vm: Veloc
     for i in range(vm.nkp):
         for j in range(vm.nvsys):
             if np.all(idx[i, j] >= 0):
-                out[i, j] = cell_value(reference_values(filter_reference(pairs[idx[i, j]], obs, filt), obs), vm)
+                out[i, j] = cell_value(reference_values(values(pairs[idx[i, j]], obs, filt), obs), vm)
     return out
 
 
