@@ -826,7 +826,8 @@ int  trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp);
  *    per_v.
  * 6. It follows that, for a cell inside the lag grid,
  *   - its moments are bit for bit what trx_run_filtered_moments returns on the same handle with shift[v] = lag[k_v]
- *     (on a handle without an exposure table: the map ignores one, trx_set_exposures);
+ *     (on a handle without an exposure table: the map ignores one, trx_set_exposures; trx_run_exposed_map is the map
+ *     that takes it);
  *   - map[i][j] is point 5 applied on the host to those moments, in the same bits for CCF and CHI2 and to the accuracy
  *     of the device's log (within 3 ulp) for LOGLIKE_BL19;
  *   - there are no atomics: a cell's bits do not depend on the other cells of the call, the chunk of cells it was
@@ -879,7 +880,8 @@ int  trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm /* [
  * trx_run_filtered_moments (and their batch forms) take them where they took the plain pairs, with the high-pass and the
  * filter behind them unchanged.  WHERE IT IS IGNORED: in trx_run_pixels, trx_run_highpassed, trx_run_trail,
  * trx_run_velocity_map and trx_run_filtered_map a row is a shift or a lag, not an exposure; their bits are the same with
- * and without a table on the handle, as the trail's are with and without a filter.  Every run on a handle without a table is
+ * and without a table on the handle, as the trail's are with and without a filter.  (The map whose rows are (lag, exposure)
+ * pairs, and which therefore takes the table, is trx_run_exposed_map below.)  Every run on a handle without a table is
  * unchanged, bit for bit.
  *
  * trx_set_exposures keeps the two arrays on the host (no device work, no synchronisation: the table changes with every
@@ -893,7 +895,7 @@ int  trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm /* [
  * or <= 0 shift (naming "shift N").  It works on a handle whose shard is not the whole grid: the pairs are linear in the
  * bins, and the ranks add theirs in rank order.  (The moment runs stay TRX_E_UNSUPPORTED there.)
  * trx_batch_set_exposures follows trx_batch_set_broadening: ex[j] belongs to atmosphere j of the following batch exposed,
- * moment and filtered-moment runs; n = 1: one table for all; n = 0: clear.  All entries are checked before any is kept, and
+ * moment, filtered-moment and exposed-map runs; n = 1: one table for all; n = 0: clear.  All entries are checked before any is kept, and
  * the arrays are copied.  Such a run of k atmospheres with n != 1 and n != k returns TRX_E_ARG (n = 0: the moment runs go
  * without a table; trx_run_batch_exposed refuses). */
 #define TRX_SMEAR_MAX 0.01
@@ -911,6 +913,58 @@ int  trx_batch_set_exposures(trx_batch *b, int32_t n, const trx_exposures *ex /*
 int  trx_run_batch_exposed(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
                            int32_t nshift, const double *const *shift /* [k] -> [nexp] */,
                            double *const *out /* [k] -> [nexp][npix][2] */);
+
+/* The detrended Kp-Vsys map UNDER THE EXPOSURE TABLE, from one spectrum: trx_run_filtered_map with the model of exposure v
+ * scaled by scale[v] and smeared by smear[v] BEFORE the filter, which mixes the exposures of a column.  This is the map for
+ * a transit series with out-of-transit frames (scale[v] = 0 there) and for planets whose lines smear by several km/s per
+ * exposure; trx_run_filtered_map ignores the table because its pixel rows are lags, and a lag has no exposure.  Here a pixel
+ * row is a PAIR (lag, exposure), and the pixel pass makes exactly the pairs the call's cells need.
+ *
+ * vm is the trx_vmap of trx_run_velocity_map; nexp, nseg, the data, weights and gains are the installed observed set's, the
+ * filter (of either kind) and the table the installed ones.  Every operation is IEEE double, rounded once, no fused
+ * multiply-add.
+ *
+ * 1. The tracks.  Step 2 of trx_run_filtered_map, unchanged: x_v, the nearest lag k_v, lag_index[i][j][v] = k_v.  A cell with
+ *    any x_v outside the lag grid or not finite is OUTSIDE: NaN in map, -1 in lag_index at the offending exposures.
+ * 2. The row spans.  Over the cells that are not outside, for every exposure v: lo_v = min k_v, hi_v = max k_v,
+ *    n_v = hi_v - lo_v + 1 (n_v = 0 when no cell is inside); base_v = n_0 + ... + n_{v-1}; R = the sum of the n_v, returned in
+ *    *nrows.  Row r = base_v + (l - lo_v) is the pair (lag l, exposure v).  The spans are dense on purpose -- no compaction,
+ *    integer min and max only --, so nothing depends on the order the cells are looked at in.
+ * 3. The rows.  G[r][p] is exactly the pair trx_run_exposed gives on this handle for exposure v and pixel p when
+ *    shift[v] = vm->lag[l]: ONE launch of the exposed pixel kernel over R rows with shift_r = lag[l], smear_r = smear[v],
+ *    scale_r = scale[v]; an array the table leaves out (NULL) stays out.  With a broadening installed the rows sample the
+ *    broadened spectrum; with a high-pass installed G[r] is that row's high-passed pair.
+ * 4. The cell.  M[v][p] = G[base_v + k_v - lo_v][p]; then points 3 - 5 of trx_run_filtered_map word for word: the installed
+ *    filter with its live and dead rule over the cell's own rows, the moments, the statistic added over the segments and
+ *    then over the exposures.  The same kernels run, reading a row table where they read the lag table.
+ * 5. It follows that, for a cell inside the lag grid,
+ *   - its moments are bit for bit what trx_run_filtered_moments returns on the same handle, table installed, with
+ *     shift[v] = lag[k_v];
+ *   - map[i][j] is point 5 of trx_run_filtered_map applied on the host to those moments: the same bits for CCF and CHI2, the
+ *     accuracy of the device's log (within 3 ulp) for LOGLIKE_BL19;
+ *   - with a table of scale all 1 and smear all 0 (or either NULL) map and lag_index are bit for bit trx_run_filtered_map's;
+ *   - there are no atomics: a cell's bits do not depend on the other cells of the call, the spans, the row numbers, the
+ *     chunk, the launch, the batch way or the handle's depth hint.
+ * 6. It leaves no trace: the handle's table, what its buffers mean to later calls, the trail buffer and every other entry
+ *    point are unchanged, bit for bit; trx_run_filtered_map, trx_run_trail and trx_run_velocity_map keep ignoring the table.
+ * 7. R = 0 (every cell outside): no pixel, filter or moment kernel runs, map is all NaN, and spectrum, when given, still
+ *    holds trx_run's bits.
+ *
+ * spectrum, lag_index and nrows may be NULL.  A run that fails leaves map, lag_index and *nrows undefined.
+ * TRX_E_ARG, the reason in trx_last_error, no output touched and the handle usable: every refusal of trx_run_filtered_map
+ * under this call's name; no exposure table installed; R * npix above what one pixel launch takes; R * npix * 16 bytes of
+ * pairs above 2^33 (kExposedMapPairBytes -- with a high-pass a second buffer of that size stands beside the first; a design
+ * limit, not a measurement: a driver above it splits the orders or coarsens the lags), naming R and the bytes.
+ * TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.
+ * trx_run_batch_exposed_map is trx_run_batch_filtered_map with the batch's tables as trx_run_batch_exposed takes them: one
+ * for all atmospheres or one each (n != 1 and n != k: TRX_E_ARG), none installed: TRX_E_ARG; a NULL map[j] is refused. */
+int  trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                         double *spectrum /* [wn_hi-wn_lo], host; may be NULL */, const trx_vmap *vm,
+                         double *map /* [nkp][nvsys], host */,
+                         int32_t *lag_index /* [nkp][nvsys][nexp], host; may be NULL */,
+                         int64_t *nrows /* R; may be NULL */, trx_debug *dbg /* may be NULL */);
+int  trx_run_batch_exposed_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
+                               const trx_vmap *vm /* one for all */, double *const *map /* [k] -> [nkp][nvsys] */);
 
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)

@@ -277,6 +277,20 @@ def bind_cellmap_api(lib):
     return lib
 
 
+EXPOSED_MAP_PAIR_BYTES = 1 << 33      # kExposedMapPairBytes (csrc/hip/trx_device.h): the most bytes of pixel pairs [R][npix][2] an exposed map makes
+
+
+def bind_expmap_api(lib):
+    """argtypes/restypes of the exposed-map entry points (trx_run_exposed_map and its batch form)."""
+    lib.trx_run_exposed_map.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.POINTER(TrxVmap),
+                                        c_double_p, c_int32_p, C.POINTER(C.c_int64), C.POINTER(TrxDebug)]
+    lib.trx_run_exposed_map.restype = C.c_int
+    lib.trx_run_batch_exposed_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.POINTER(TrxVmap),
+                                              C.POINTER(c_double_p)]
+    lib.trx_run_batch_exposed_map.restype = C.c_int
+    return lib
+
+
 def bind_filter_api(lib):
     """argtypes/restypes of the filter entry points (trx_set_filter, trx_run_filtered_moments and their batch forms)."""
     lib.trx_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]

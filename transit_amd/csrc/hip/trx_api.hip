@@ -42,6 +42,7 @@
 #include "trx_trail.hip.h"
 #include "trx_vmap.hip.h"
 #include "trx_cellmap.hip.h"
+#include "trx_expmap.hip.h"
 #include "trx_filter.hip.h"
 #include "trx_wfilter.hip.h"
 #include "trx_highpass.hip.h"
@@ -54,6 +55,7 @@
 #include "../trx_vmap.h"
 #include "../trx_products.h"
 #include "../trx_exposures.h"
+#include "../trx_expmap.h"
 #include "../trx_wfilter.h"
 
 using namespace trx;
@@ -127,11 +129,12 @@ struct ExposureSet {
 // hp: with the high-pass between the pairs and whatever reads them (pixel_run sets it for every run with obs on a handle that
 // has one; trx_run_highpassed itself), hpx the extents of that; ex: the rows are exposures and take the handle's exposure
 // table (trx_run_exposed, and trx_run_moments and trx_run_filtered_moments on a handle with one), already in h->d_exscale
-// and h->d_exsmear
+// and h->d_exsmear; ex_rows: ex is the call's own set of one entry per ROW of a map under the table (trx_run_exposed_map:
+// nexp = nshift rows, each a lag at an exposure), not the handle's
 struct PixelRun {
   const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; PixelExtents ext{};
   const HighPassSet *hp = nullptr; HighpassExtents hpx{};
-  const ExposureSet *ex = nullptr;
+  const ExposureSet *ex = nullptr; bool ex_rows = false;
 };
 // a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
 // the largest -- which sizes the kernel's tile
@@ -281,6 +284,9 @@ struct trx_handle {
   // [nkp * nvsys][nexp] int32, one chunk's filtered values [chunk][nexp][npix] and moments [chunk][nexp][nseg][TRX_NMOMENT],
   // the map [nkp][nvsys]
   DevBuf d_cm_index, d_cm_val, d_cm_mom, d_cm_map;
+  // trx_run_exposed_map (trx_expmap.hip.h), grown on demand: the spans [nexp][2] int32 of the call's exposures (their host
+  // copy: em_span), the first row [nexp] int64 of each, the row table [nkp * nvsys][nexp] int32 beside the lag table
+  DevBuf d_em_span, d_em_base, d_em_row; std::vector<int32_t> em_span;
   std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
   DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
   std::unique_ptr<HighPassSet> highpass;               // trx_set_highpass (null: none); belongs to `observed`
@@ -2802,7 +2808,8 @@ int Run::pixel_kernels()
   if (!ex->smear.empty()) PA.smear = h->d_exsmear.as<double>();
   PA.sqrt2 = std::sqrt(2.0);
   // (every further address the kernel reads: scale and smear over [0, nshift) = [0, nexp))
-  if (ex != h->exposures.get() || ex->nexp != px->nshift || (ex->scale.empty() && ex->smear.empty()) ||
+  // (the set is the handle's -- or the rows' own of an exposed map, which never has obs, filt or trail)
+  if ((px->ex_rows ? px->obs || px->filt || px->trail : ex != h->exposures.get()) || ex->nexp != px->nshift || (ex->scale.empty() && ex->smear.empty()) ||
       (!ex->scale.empty() && (ex->scale.size() != (size_t)ex->nexp || !PA.scale || h->d_exscale.bytes < EX.scale_bytes)) ||
       (!ex->smear.empty() && (ex->smear.size() != (size_t)ex->nexp || !PA.smear || h->d_exsmear.bytes < EX.smear_bytes)))
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the exposed pixel kernel (not launched)");
@@ -3652,16 +3659,14 @@ int trx_run_highpassed(trx_handle *h, const trx_atm *a, const trx_opts *o, doubl
 }
 
 // ---- the Kp-Vsys map with the filter applied to every cell's own model matrix (trx_cellmap.hip.h) ---
-// The map of PR's rows (the pairs of the lags in h->d_pixout, or h->d_pixhp with a high-pass; the run waited for), behind the
-// upload of the call's arrays on the main queue: the index table once, then chunk after chunk the filter, the moments and the
-// statistic.  VX: the extents of the call's arrays at VX.at_* of h->d_vm_in; CX: those of the cell buffers.
-static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const VmapExtents &VX, const CellMapExtents &CX)
+// the index table of the call's cells (k_cell_tracks) into h->d_cm_index, behind the upload of the call's arrays on the main
+// queue.  VX: the extents of the call's arrays at VX.at_* of h->d_vm_in; CX: those of the cell buffers.
+static int launch_cell_tracks(trx_handle *h, const trx_vmap *vm, const VmapExtents &VX, const CellMapExtents &CX)
 {
-  const ObservedSet *O = h->observed.get(); const FilterSet *F = h->filter.get();
+  const ObservedSet *O = h->observed.get();
   const double *in = h->d_vm_in.as<double>();
-  if (!O || !F || !in) return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
-  const int32_t nlag = vm->nlag, nexp = O->nexp, nseg = O->nseg;
-  const int64_t npix = O->npix;
+  if (!O || !in) return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell track kernel (not launched)");
+  const int32_t nlag = vm->nlag, nexp = O->nexp;
   CellTrackArgs TA{};
   TA.lag_kms = in; TA.kp = in + VX.at_kp; TA.vsys = in + VX.at_vsys; TA.orbit = in + VX.at_orbit; TA.offset = vm->offset ? in + VX.at_offset : nullptr;
   TA.index = h->d_cm_index.as<int32_t>(); TA.ntracks = CX.tracks; TA.nlag = nlag; TA.nexp = nexp; TA.nvsys = vm->nvsys;
@@ -3673,7 +3678,20 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
       CX.track_blocks < 1 || CX.track_blocks > 0x7fffffffLL || CX.track_blocks * kCellTrackBlock < CX.tracks)
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell track kernel (not launched)");
   hipLaunchKernelGGL(k_cell_tracks, dim3((unsigned)CX.track_blocks), dim3(kCellTrackBlock), 0, h->stream, TA);
+  return TRX_OK;
+}
 
+// chunk after chunk the filter, the moments and the statistic of the cells, each cell's rows of PR's pairs named by its
+// entries of `table` [cells][nexp]: the lag table (trx_run_filtered_map: nrow = nlag rows) or the row table of an exposed
+// map (nrow = R rows), every entry -1 or in [0, nrow)
+static int launch_cell_chunks(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const CellMapExtents &CX, const DevBuf &table, int64_t nrow)
+{
+  const ObservedSet *O = h->observed.get(); const FilterSet *F = h->filter.get();
+  if (!O || !F || !table.p || table.bytes < CX.index_bytes || CX.index_bytes < sizeof(int32_t) * (size_t)CX.tracks)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
+  const int32_t nexp = O->nexp, nseg = O->nseg;
+  const int64_t npix = O->npix;
+  const int32_t *const index = table.as<int32_t>();
   CellFilterArgs FA{};
   // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
   FA.pairs = PR.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = PR.hp ? nullptr : O->d_gain.as<double>();
@@ -3691,16 +3709,16 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
   SA.mom = MA.mom; SA.nexp = nexp; SA.nseg = nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
   const size_t mat = sizeof(double) * (size_t)F->nseg * (size_t)F->nexp * (size_t)F->npad;
   const size_t obs_cells = sizeof(double) * (size_t)nexp * (size_t)npix;
-  // (every address the three kernels read or write, for the largest chunk: the pairs over [nlag][npix] -- a table entry the
-  // filter follows lies in [0, nlag - 1], vmap_nearest, and a cell with a -1 is left out by all three --, the tiles in
+  // (every address the three kernels read or write, for the largest chunk: the pairs over [nrow][npix] -- a table entry the
+  // filter follows lies in [0, nrow - 1], vmap_nearest or exposed_map_row, and a cell with a -1 is left out by all three --, the tiles in
   // [0, npix) naming segments below nseg, made so when the filter was, the gains, the two padded matrices; the values over
   // [chunk][nexp][npix]; data and weights over [nexp][npix], the segments in [0, npix), checked when the set was made; the
   // moment rows over [chunk][nexp][nseg]; the chunk's cells of the map)
   if ((wt ? !wfilter_set_complete(*F, *O) : !FA.fwd || F->d_fwd.bytes < mat) ||
       !FA.pairs || !FA.back || !FA.tiles || !FA.val || !MA.data || !MA.seg_first || !MA.mom || !h->d_cm_map.p ||
       F->nexp != nexp || F->nseg != nseg || F->npix != npix || npix < 1 || nseg < 1 || npix != PR.set->npix || F->ncomp < 1 || F->ncomp > F->npad ||
-      (F->npad != 4 && F->npad != 8 && F->npad != 16) || F->ntiles < 1 || PR.nshift != nlag || PR.filt || PR.trail || PR.obs ||
-      PR.ext.pairs != (int64_t)nlag * npix || h->d_pixout.bytes < PR.ext.pair_bytes || (PR.hp && (PR.hpx.pairs != PR.ext.pairs || h->d_pixhp.bytes < PR.hpx.pair_bytes)) ||
+      (F->npad != 4 && F->npad != 8 && F->npad != 16) || F->ntiles < 1 || nrow < 1 || PR.nshift != nrow || PR.filt || PR.trail || PR.obs ||
+      PR.ext.pairs != nrow * npix || h->d_pixout.bytes < PR.ext.pair_bytes || (PR.hp && (PR.hpx.pairs != PR.ext.pairs || h->d_pixhp.bytes < PR.hpx.pair_bytes)) ||
       F->d_back.bytes < mat || F->d_tiles.bytes < sizeof(FilterTile) * (size_t)F->ntiles ||
       (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)npix) || O->d_data.bytes < obs_cells || (MA.weight && O->d_weight.bytes < obs_cells) ||
       O->d_seg.bytes < sizeof(int64_t) * ((size_t)nseg + 1) || O->seg.size() != (size_t)nseg + 1 || O->seg.front() != 0 || O->seg.back() != npix ||
@@ -3713,7 +3731,7 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
   for (int64_t q = 0; q < CX.nchunks; q++) {
     const int64_t cell0 = q * CX.chunk, n = q + 1 < CX.nchunks ? CX.chunk : CX.last_chunk;      // cells [cell0, cell0 + n)
-    FA.index = MA.index = SA.index = TA.index + cell0 * nexp;
+    FA.index = MA.index = SA.index = index + cell0 * nexp;
     FA.nwaves = n * F->ntiles; MA.nrows = n * nexp * nseg;
     WA.index = FA.index; WA.nwaves = FA.nwaves;
     SA.map = h->d_cm_map.as<double>() + cell0; SA.ncells = n;
@@ -3731,6 +3749,14 @@ static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap
   }
   HIPCHK(h, hipGetLastError());
   return TRX_OK;
+}
+
+// The map of PR's rows (the pairs of the lags in h->d_pixout, or h->d_pixhp with a high-pass; the run waited for), behind the
+// upload of the call's arrays on the main queue: the index table once, then the chunks, which follow that table.
+static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const VmapExtents &VX, const CellMapExtents &CX)
+{
+  if (const int rc = launch_cell_tracks(h, vm, VX, CX)) return rc;
+  return launch_cell_chunks(h, PR, vm, CX, h->d_cm_index, vm->nlag);
 }
 
 int trx_run_filtered_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, int32_t *lag_index,
@@ -3755,6 +3781,101 @@ int trx_run_filtered_map(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   HIPCHK(h, hipMemcpyAsync(map, h->d_cm_map.p, CX.map_bytes, hipMemcpyDeviceToHost, h->stream));
   if (lag_index) HIPCHK(h, hipMemcpyAsync(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return TRX_OK;
+}
+
+// ---- the Kp-Vsys map under the exposure table: its pixel rows are (lag, exposure) pairs (trx_expmap.hip.h) ----
+// the spans of the lags the inside cells take at every exposure (k_cell_spans), behind k_cell_tracks on the main queue, read
+// back into h->em_span [nexp][2]: the queue is waited for
+static int launch_cell_spans(trx_handle *h, const CellMapExtents &CX, const ExposedMapExtents &EX, int32_t nexp)
+{
+  CellSpanArgs SA{};
+  SA.index = h->d_cm_index.as<int32_t>(); SA.span = h->d_em_span.as<int32_t>(); SA.ncells = CX.cells; SA.nexp = nexp;
+  // (every address the kernel reads or writes: the index table over [cells][nexp], the spans over [nexp][2])
+  if (!SA.index || !SA.span || nexp < 1 || CX.cells < 1 || CX.tracks != CX.cells * nexp || h->d_cm_index.bytes < CX.index_bytes ||
+      CX.index_bytes < sizeof(int32_t) * (size_t)CX.tracks || EX.span_bytes < sizeof(int32_t) * 2 * (size_t)nexp || h->d_em_span.bytes < EX.span_bytes ||
+      EX.span_blocks < 1 || EX.span_blocks > 0x7fffffffLL || EX.span_blocks * kCellSpanWaves < nexp)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell span kernel (not launched)");
+  try { h->em_span.assign(2 * (size_t)nexp, 0); } catch (...) { return fail(h, TRX_E_NOMEM, "trx_run_exposed_map: out of host memory"); }
+  hipLaunchKernelGGL(k_cell_spans, dim3((unsigned)EX.span_blocks), dim3(64 * kCellSpanWaves), 0, h->stream, SA);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(h->em_span.data(), h->d_em_span.p, EX.span_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return TRX_OK;
+}
+
+// the row table of the call's cells (k_cell_rows) into h->d_em_row from the lag table, the spans on the device and the rows'
+// bases L.base, which go up first
+static int launch_cell_rows(trx_handle *h, const CellMapExtents &CX, const ExposedMapExtents &EX, int32_t nexp, const ExposedMapRows &L)
+{
+  if (const int rc = upload(h, h->d_em_base, L.base)) return rc;
+  CellRowArgs RA{};
+  RA.index = h->d_cm_index.as<int32_t>(); RA.span = h->d_em_span.as<int32_t>(); RA.base = h->d_em_base.as<int64_t>(); RA.row = h->d_em_row.as<int32_t>();
+  RA.ntracks = CX.tracks; RA.nexp = nexp;
+  // (every address the kernel reads or writes: the two tables over [cells][nexp], the spans over [nexp][2], the bases over
+  // [nexp] of the [nexp + 1] there are; a row it writes is below base[nexp] = R, an int32 count)
+  if (!RA.index || !RA.span || !RA.base || !RA.row || nexp < 1 || CX.tracks != CX.cells * nexp || CX.tracks < 1 || CX.tracks > 0x7fffffffLL ||
+      h->d_cm_index.bytes < CX.index_bytes || EX.row_bytes < sizeof(int32_t) * (size_t)CX.tracks || h->d_em_row.bytes < EX.row_bytes ||
+      h->d_em_span.bytes < EX.span_bytes || L.base.size() != (size_t)nexp + 1 || h->d_em_base.bytes < sizeof(int64_t) * ((size_t)nexp + 1) ||
+      L.base.back() != L.R || L.R != EX.rows || L.R < 1 || L.R > 0x7fffffffLL ||
+      CX.track_blocks < 1 || CX.track_blocks > 0x7fffffffLL || CX.track_blocks * kCellTrackBlock < CX.tracks)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell row kernel (not launched)");
+  hipLaunchKernelGGL(k_cell_rows, dim3((unsigned)CX.track_blocks), dim3(kCellTrackBlock), 0, h->stream, RA);
+  return TRX_OK;
+}
+
+int trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, int32_t *lag_index,
+                        int64_t *nrows, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_run_exposed_map";
+  std::string msg;
+  if (const int rc = exposed_map_checks(product_state(h), who, vm, map, msg)) return fail(h, rc, msg);
+  if (!a || !o) return TRX_E_ARG;
+  const ObservedSet *O = h->observed.get(); const ExposureSet *T = h->exposures.get();
+  const int32_t nexp = O->nexp;
+  const VmapExtents VX = vmap_extents(*vm, nexp);
+  const CellMapExtents CX = cell_map_extents((int64_t)vm->nkp * vm->nvsys, nexp, O->nseg, O->npix);
+  ExposedMapExtents EX;
+  // (the two tables' extents do not depend on R: no row refuses nothing)
+  if (const int rc = exposed_map_extents(who, 0, O->npix, CX.cells, nexp, EX, msg)) return fail(h, rc, msg);
+  if (const int rc = vmap_pack(who, *vm, VX, h->vm_in, msg)) return fail(h, rc, msg);
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  // the tracks and the spans AHEAD of the pixel pass: they say which (lag, exposure) rows it has to make
+  if ((rc = ensure(h, h->d_cm_index, CX.index_bytes)) || (rc = ensure(h, h->d_em_span, EX.span_bytes)) || (rc = ensure(h, h->d_em_row, EX.row_bytes)) ||
+      (rc = upload(h, h->d_vm_in, h->vm_in)) || (rc = launch_cell_tracks(h, vm, VX, CX)) || (rc = launch_cell_spans(h, CX, EX, nexp)))
+    return rc;
+  ExposedMapRows L;
+  if ((rc = exposed_map_bases(who, h->em_span.data(), nexp, vm->nlag, L, msg)) || (rc = exposed_map_extents(who, L.R, O->npix, CX.cells, nexp, EX, msg)))
+    return fail(h, rc, msg);
+  if (L.R == 0) {
+    // no cell inside the lag grid: the spectrum alone -- no pixel, filter or moment kernel --, and a map of NaN
+    if ((rc = run_once(h, a, o, spectrum, nullptr, dbg, Products{}))) return rc;
+    const double nan = __builtin_nan("");
+    for (int64_t c = 0; c < CX.cells; c++) map[c] = nan;
+    if (lag_index) HIPCHK(h, hipMemcpy(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost));
+    if (nrows) *nrows = 0;
+    return TRX_OK;
+  }
+  if ((rc = exposed_map_row_arrays(who, h->em_span.data(), nexp, vm->lag, T->scale.empty() ? nullptr : T->scale.data(),
+                                   T->smear.empty() ? nullptr : T->smear.data(), L, msg)))
+    return fail(h, rc, msg);
+  // one pixel pass of R rows with a table of their own -- row r's shift, smear and scale --, not the handle's: no moments,
+  // no trail; the high-pass when one is installed
+  ExposureSet rows; rows.nexp = (int32_t)L.R; rows.scale = std::move(L.scale); rows.smear = std::move(L.smear);
+  PixelRun PR{h->pixels.get(), (int32_t)L.R}; PR.hp = h->highpass.get(); PR.ex = &rows; PR.ex_rows = true;
+  // (a call that fails leaves no copy from this call's own arrays -- the rows', the bases -- in flight when they go)
+  auto failed = [&](int code) { (void)hipStreamSynchronize(h->stream); return code; };
+  if ((rc = pixel_run(h, who, a, o, spectrum, PR, L.shift.data(), dbg))) return failed(rc);
+  // (the run has been waited for: the kernels follow on the main queue, the cells' rows named by the row table)
+  if ((rc = ensure(h, h->d_cm_val, CX.val_bytes)) || (rc = ensure(h, h->d_cm_mom, CX.mom_bytes)) || (rc = ensure(h, h->d_cm_map, CX.map_bytes)) ||
+      (rc = launch_cell_rows(h, CX, EX, nexp, L)) || (rc = launch_cell_chunks(h, PR, vm, CX, h->d_em_row, L.R)))
+    return failed(rc);
+  HIPCHK(h, hipMemcpyAsync(map, h->d_cm_map.p, CX.map_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (lag_index) HIPCHK(h, hipMemcpyAsync(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (nrows) *nrows = L.R;
   return TRX_OK;
 }
 
@@ -3823,8 +3944,8 @@ struct trx_batch {
   // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none)
   std::vector<trx_broadening> broad;
   // trx_batch_set_exposures: one table for all atmospheres or one per atmosphere (empty: none), the arrays copied; a worker
-  // installs the atmosphere's on its handle first where the call's rows are exposures (wants_exposures: an exposed, moment
-  // or filtered-moment run)
+  // installs the atmosphere's on its handle first where the call's rows are exposures (wants_exposures: an exposed, moment,
+  // filtered-moment or exposed-map run)
   std::vector<ExposureSet> expo; bool wants_exposures = false;
   std::atomic<int32_t> next{0};
   int32_t busy = 0; int rc = TRX_OK; std::string err;
@@ -4149,6 +4270,24 @@ int trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm, cons
     if (const int rc = filtered_map_checks(product_state(b->hs[0]), "trx_run_batch_filtered_map", vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
   if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_map")) return rc;
   return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_map(h, atm + j, opts, nullptr, vm, map[j], nullptr, nullptr); });
+}
+
+int trx_run_batch_exposed_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map)
+{
+  g_comm_err.clear();
+  const char *const who = "trx_run_batch_exposed_map";
+  if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = std::string(who) + ": bad argument"; return TRX_E_ARG; }
+  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = std::string(who) + ": no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
+  if (!b->hs[0]->filter) { g_comm_err = std::string(who) + ": no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
+  if (b->expo.empty()) { g_comm_err = std::string(who) + ": no exposure table installed (trx_batch_set_exposures)"; return TRX_E_ARG; }
+  if (const int rc = batch_rows_check(who, k, {{"map", map}}, g_comm_err)) return rc;
+  // (the handles are made from one description and carry one observed set and one filter: what the first refuses, all refuse;
+  // the tables are the batch's, installed per atmosphere by the workers)
+  if (k > 0)
+    if (const int rc = filtered_map_checks(product_state(b->hs[0]), who, vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
+  if (const int rc = batch_broadening_fits(b, k, who)) return rc;
+  if (const int rc = batch_exposures_fit(b, k, who)) return rc;
+  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_exposed_map(h, atm + j, opts, nullptr, vm, map[j], nullptr, nullptr, nullptr); }, true);
 }
 
 int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }

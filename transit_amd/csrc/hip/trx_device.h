@@ -218,4 +218,10 @@ constexpr int kCellMapChunk = 64;
 constexpr uint64_t kCellMapValBytes = (uint64_t)1 << 30;
 constexpr int kCellTrackBlock = 256;                  // lanes ((cell, exposure) pairs) per block of k_cell_tracks
 
+// (trx_expmap.hip.h) an exposed map's pixel rows are (lag, exposure) pairs: their pairs [R][npix][2] may take
+// kExposedMapPairBytes at the most -- a design limit, not a measurement: with a high-pass a second buffer of that size
+// stands beside the first, and the two stay under 16 GiB of the card's memory
+constexpr uint64_t kExposedMapPairBytes = (uint64_t)1 << 33;
+constexpr int kCellSpanWaves = 4;                     // exposures (waves) per block of k_cell_spans
+
 }  // namespace trx

@@ -212,6 +212,7 @@ def hip_library():
         _abi.bind_highpass_api(lib)
         _abi.bind_broaden_api(lib)
         _abi.bind_exposures_api(lib)
+        _abi.bind_expmap_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -434,8 +435,8 @@ class Engine(CEngine):
 
     def set_exposures(self, ex):
         """trx_set_exposures: install an exposure table (a transit_amd.exposures.Exposures; None or an empty one: clear
-        it) over the observed set in force: a scale and a Doppler-smear half-width per exposure.  run_exposed, run_moments
-        and run_filtered_moments then take it; set_observed and set_pixels drop it.  No device work: cheap per likelihood
+        it) over the observed set in force: a scale and a Doppler-smear half-width per exposure.  run_exposed, run_moments,
+        run_filtered_moments and run_exposed_map then take it; set_observed and set_pixels drop it.  No device work: cheap per likelihood
         call."""
         n = len(ex) if ex is not None else 0
         rc = self._lib.trx_set_exposures(self._h, C.byref(ex.to_c()) if n else None)
@@ -453,6 +454,25 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_run_exposed", self._last_error())
         return (out, spec) if spectrum else out
+
+    def run_exposed_map(self, atm, opts, vm, lag_index: bool = False, nrows: bool = False, spectrum: bool = False):
+        """trx_run_exposed_map: run_filtered_map UNDER the installed exposure table -- the model of exposure v scaled and
+        smeared before the filter.  The Kp-Vsys map [nkp, nvsys] of a transit_amd.xcor.VelocityMap: a cell's value is
+        xcor.cell_value of run_filtered_moments (table installed) at the lags nearest to its velocity; a cell with a
+        velocity outside the lag grid is NaN.  With lag_index=True, nrows=True and/or spectrum=True a tuple
+        (map[, lag_index][, nrows][, spectrum]): lag_index [nkp, nvsys, nexp] int32 the lags taken (-1: outside), nrows
+        the (lag, exposure) pixel rows the call made (xcor.exposed_map_rows(vm)[3]), the spectrum bit for bit what run()
+        gives.  One spectrum and one pixel pass, whatever the number of cells."""
+        m = np.zeros((vm.nkp, vm.nvsys))
+        idx = np.zeros((vm.nkp, vm.nvsys, getattr(self, "mom_shape", (0, 0))[0]), dtype=np.int32) if lag_index else None
+        spec = np.zeros(self.nwn) if spectrum else None
+        nr = C.c_int64(-1)
+        rc = self._lib.trx_run_exposed_map(self._h, C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m),
+                                           idx.ctypes.data_as(_abi.c_int32_p) if lag_index else None, C.byref(nr), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_run_exposed_map", self._last_error())
+        out = (m,) + ((idx,) if lag_index else ()) + ((int(nr.value),) if nrows else ()) + ((spec,) if spectrum else ())
+        return out if len(out) > 1 else m
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
@@ -658,6 +678,14 @@ class Batch:
         out = np.zeros((len(atms), sh.shape[1], getattr(self, "npix", 0), 2))
         self._call("trx_run_batch_exposed", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
+
+    def run_exposed_map(self, atms, opts: _abi.TrxOpts, vm) -> np.ndarray:
+        """trx_run_batch_exposed_map: the maps [K, nkp, nvsys] of one transit_amd.xcor.VelocityMap for all atmospheres
+        under the batch's exposure tables (one for all, or atmosphere j with its own), each atmosphere's what
+        Engine.run_exposed_map gives, bit for bit."""
+        m = np.zeros((len(atms), vm.nkp, vm.nvsys))
+        self._call("trx_run_batch_exposed_map", atms, opts, C.byref(vm.to_c()), _rows(m))
+        return m
 
     def close(self):
         if self._b:

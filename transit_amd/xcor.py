@@ -74,6 +74,12 @@ then over the exposures, both in order.
     cell_bound(mom, vm)                                  how far two double evaluations of cell_value can lie apart
     filtered_map_reference(pairs, obs, filt, vm)         the whole definition in numpy from run_pixels(lags)' pairs
 
+The same map under the exposure table (Engine.run_exposed_map / Batch.run_exposed_map; trx_run_exposed_map): a pixel row
+is a pair (lag, exposure), so that the table's scale and smear act on the model before the filter.
+
+    exposed_map_rows(vm)                                 (lo, hi, base, R): the span of lags per exposure, the rows' bases, their number
+    exposed_map_reference(pairs_lv, obs, filt, vm, hp)   the whole definition in numpy from run_exposed's pairs per lag
+
 The high-pass along the pixel axis (Engine.set_highpass / Engine.run_highpassed; trx_set_highpass / trx_run_highpassed):
 a symmetric tap table taps[0 .. half] (finite, >= 0, taps[0] > 0) over the observed set's segments.  For a row of pairs
 and a live pixel p (b > 0) of a segment, over the live pixels p + k of that segment, k = -half .. half in that order,
@@ -914,6 +920,49 @@ def filtered_map_reference(pairs_at_lags, obs: Observed, filt, vm: VelocityMap) 
         for j in range(vm.nvsys):
             if np.all(idx[i, j] >= 0):
                 out[i, j] = cell_value(reference_values(values(pairs[idx[i, j]], obs, filt), obs), vm)
+    return out
+
+
+def exposed_map_rows(vm: VelocityMap):
+    """(lo, hi, base, R) of trx_run_exposed_map: over the cells inside the lag grid, per exposure v the least and the largest
+    lag the cells take (lo[v], hi[v]; 2^31 - 1 and -1 where no cell is inside), base[v] = n_0 + ... + n_{v-1} with
+    n_v = hi[v] - lo[v] + 1 (0 for such an exposure), and R the sum of the n_v: the pixel rows the call makes, row
+    base[v] + (l - lo[v]) the pair (lag l, exposure v)."""
+    idx = nearest_lags(vm).reshape(-1, vm.nexp)
+    idx = idx[np.all(idx >= 0, axis=1)]
+    if idx.shape[0] == 0:
+        lo, hi = np.full(vm.nexp, 2 ** 31 - 1, dtype=np.int64), np.full(vm.nexp, -1, dtype=np.int64)
+    else:
+        lo, hi = idx.min(axis=0).astype(np.int64), idx.max(axis=0).astype(np.int64)
+    n = np.where(hi >= lo, hi - lo + 1, 0)
+    base = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+    return lo, hi, base, int(np.sum(n))
+
+
+def exposed_map_reference(pairs_lv, obs: Observed, filt, vm: VelocityMap, hp=None) -> np.ndarray:
+    """The definition of trx_run_exposed_map in numpy: the map [nkp, nvsys] from pairs_lv [nlag, nexp, npix, 2], with
+    pairs_lv[l][v] the pair row run_exposed gives for exposure v at the shift vm.lag[l] (the table's scale and smear in
+    it).  Cell (i, j) takes at exposure v the row pairs_lv[nearest_lags(vm)[i, j, v], v]; that matrix goes through the
+    high-pass when one is given (highpass_pairs of highpass_reference, and a gain-free copy of the observed set from
+    there on), filter_reference (a WeightedFilter: weighted_filter_reference) and reference_values as a filtered run's
+    does, and cell_value gives the cell.  A cell with a velocity outside the lag grid is nan."""
+    values = weighted_filter_reference if isinstance(filt, WeightedFilter) else filter_reference
+    pairs = np.asarray(pairs_lv, dtype=np.float64)
+    if pairs.shape != (vm.nlag, obs.nexp, obs.npix, 2):
+        raise ValueError("pairs of shape [nlag][nexp][npix][2] with the map's nlag")
+    if vm.nexp != obs.nexp:
+        raise ValueError("a map of the observed set's nexp")
+    behind = Observed(obs.seg_first, obs.data, obs.weight) if hp is not None else obs
+    idx = nearest_lags(vm)
+    ve = np.arange(obs.nexp)
+    out = np.full((vm.nkp, vm.nvsys), np.nan)
+    for i in range(vm.nkp):
+        for j in range(vm.nvsys):
+            if np.all(idx[i, j] >= 0):
+                m = pairs[idx[i, j], ve]
+                if hp is not None:
+                    m = highpass_pairs(highpass_reference(m, obs, hp))
+                out[i, j] = cell_value(reference_values(values(m, behind, filt), behind), vm)
     return out
 
 
