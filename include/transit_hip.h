@@ -966,6 +966,68 @@ int  trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o,
 int  trx_run_batch_exposed_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k] */, const trx_opts *o,
                                const trx_vmap *vm /* one for all */, double *const *map /* [k] -> [nkp][nvsys] */);
 
+/* Detrending the observed exposures THEMSELVES on the device, with model injection: the step of an injection-recovery
+ * test that ran on the host.  One call multiplies a model into the raw exposures (optional), runs SYSREM (Tamuz, Mazeh &
+ * Zucker 2005) on them per segment, leaves the residuals installed as the observed set's data and the weighted filter of
+ * the fitted time vectors in the filter slot.  trx_run_filtered_moments, trx_run_filtered_map and trx_run_exposed_map
+ * after it are the recovery, unchanged.
+ *
+ * Every operation is IEEE double rounded once, no fused multiply-add; sums start from +0 and run in the order written.
+ * F is the data as trx_set_observed installed them -- the RAW set, never the result of an earlier detrend call --, w the
+ * set's weights (1 without), gain the set's gain.
+ * 0. f0 = F.
+ * 1. Injection (inject = 1).  (a, b)[v][p] is the pair trx_run_moments forms on this handle ahead of the high-pass for
+ *    shift[v]: trx_run_exposed's with an exposure table installed, trx_run_pixels' without, behind the broadening where
+ *    one is installed -- one spectrum and one pixel pass of the same kernels, the same bits.  Where b > 0:
+ *      g = gain_p * (a / b);  m = p0 * g;  m = m + p1;  f0[v][p] = F[v][p] * m       (the "p0 g + p1" of TRX_STAT_CHI2)
+ *    where b <= 0: f0[v][p] = F[v][p].  The high-pass and the filter take no part.  With inject = 0, a, o, shift and
+ *    spectrum are not looked at and no spectrum is computed.
+ * 2. SYSREM per segment s over its pixels [first, last), r = f0.  For component i = 0 .. ncomp-1: a_v = 1 for all v, then
+ *    niter times
+ *      column step, per pixel p:    num = sum over v ascending of (w[v][p] * r[v][p]) * a_v
+ *                                   den = sum over v ascending of (w[v][p] * a_v) * a_v
+ *                                   c_p = num / den if den > 0, else +0
+ *      row step, per exposure v:    num = sum over p of (w * r) * c_p;   den = sum over p of (w * c_p) * c_p
+ *                                   a_v = num / den if den > 0, else +0
+ *    the row sums in the order of the moments: lane l of 64 adds the pixels first + l, first + l + 64, ... in that order,
+ *    then the 64 lane sums go through the butterfly (every lane adds its partner lane ^ 32, 16, 8, 4, 2, 1).  Then the close:
+ *      n2 = sum over v ascending of a_v * a_v;  t = sqrt(n2);  if t > 0: a_v = a_v / t and c_p = c_p * t
+ *      U[s][v][i] = a_v;  coef[i][p] = c_p;  r[v][p] = r[v][p] - a_v * c_p
+ *    An empty segment, or one masked everywhere, gives zero vectors.  The bits of a segment's result depend on that
+ *    segment's f0 and w, ncomp and niter only -- not on other segments, the launch or the handle's depth hint; there are no
+ *    atomics.  sqrt is the device's, correctly rounded.
+ * 3. U is copied to the host; a non-finite entry is TRX_E_ARG ("component I of segment S is not finite") with nothing
+ *    installed.  Otherwise, at once and only after every kernel has finished, the observed set's data become r and the
+ *    filter slot takes the weighted filter of U through trx_set_weighted_filter's path (the same factor kernel and pivot
+ *    rule, nsingular as there), replacing a filter of either kind.  The weights, gain, segments, high-pass, exposure table,
+ *    broadening and pixel set stay installed.  basis, coef and data, where given, receive U, coef and r.
+ * 4. From raw, always: the handle keeps F on the device -- the first call moves it aside, later calls read it --, so a call
+ *    with the same arguments gives the same bits however many detrend calls came before.  dt NULL or ncomp = 0 is the UNDO:
+ *    data <- F, the filter slot cleared, TRX_OK even if nothing had been detrended (nsingular, when given, 0).
+ *    trx_set_observed and trx_set_pixels drop everything as they do for the set.
+ * 5. TRX_E_ARG, the reason in trx_last_error, nothing touched -- data, filter and outputs as they were --, checked in this
+ *    order: no observed set; ncomp < 0 or > TRX_FILTER_MAX; niter < 1 or > TRX_SYSREM_MAX_ITER; inject not 0 or 1;
+ *    pad != 0; with inject = 1: a non-finite p0 or p1, a NULL a, o or shift, nshift != nexp, a bad shift ("shift N"),
+ *    nexp * npix above what one pixel launch takes.  TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.  The
+ *    residuals are built in a buffer of their own and swapped in at step 3: a call that fails later (TRX_E_HIP,
+ *    TRX_E_NOMEM) also leaves the previous data and filter in force.
+ * Not here: a batch form (a driver takes basis and data from one handle and installs them on a trx_batch through
+ * trx_batch_set_observed and trx_batch_set_weighted_filter), high-passing the data, per-order normalisation or division by
+ * a column's scatter, PCA/SVD on the device, shards. */
+#define TRX_SYSREM_MAX_ITER 64
+typedef struct {
+  int32_t ncomp, niter;      /* components 1 .. TRX_FILTER_MAX (0: undo); alternations per component, 1 .. TRX_SYSREM_MAX_ITER */
+  int32_t inject, pad;       /* 0: detrend the raw data; 1: inject the model first; pad: 0 */
+  double  p0, p1;            /* injected exposure: f0 = F * (p0 g + p1) */
+} trx_detrend;               /* 32 bytes */
+int  trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                          double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                          int32_t nshift, const double *shift /* [nexp]; inject = 1 only */, const trx_detrend *dt,
+                          double *basis /* [nseg][nexp][ncomp], host; may be NULL */,
+                          double *coef /* [ncomp][npix], host; may be NULL */,
+                          double *data /* [nexp][npix]: the residuals now installed, host; may be NULL */,
+                          int64_t *nsingular /* may be NULL */, trx_debug *dbg /* may be NULL */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

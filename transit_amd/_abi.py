@@ -109,6 +109,14 @@ class TrxWfilter(C.Structure):
     _fields_ = [("ncomp", C.c_int32), ("pad", C.c_int32), ("basis", c_double_p)]
 
 
+SYSREM_MAX_ITER = 64            # TRX_SYSREM_MAX_ITER: the most alternations per component of trx_detrend_observed
+
+
+class TrxDetrend(C.Structure):
+    _fields_ = [("ncomp", C.c_int32), ("niter", C.c_int32), ("inject", C.c_int32), ("pad", C.c_int32),
+                ("p0", C.c_double), ("p1", C.c_double)]
+
+
 HIGHPASS_MAX_HALF = 1024
 
 
@@ -349,4 +357,13 @@ def bind_exposures_api(lib):
     lib.trx_run_batch_exposed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
                                           C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.trx_run_batch_exposed.restype = C.c_int
+    return lib
+
+
+def bind_sysrem_api(lib):
+    """argtypes/restypes of the detrending entry point (trx_detrend_observed)."""
+    lib.trx_detrend_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                         C.POINTER(TrxDetrend), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int64),
+                                         C.POINTER(TrxDebug)]
+    lib.trx_detrend_observed.restype = C.c_int
     return lib

@@ -45,6 +45,7 @@
 #include "trx_expmap.hip.h"
 #include "trx_filter.hip.h"
 #include "trx_wfilter.hip.h"
+#include "trx_sysrem.hip.h"
 #include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
@@ -57,6 +58,7 @@
 #include "../trx_exposures.h"
 #include "../trx_expmap.h"
 #include "../trx_wfilter.h"
+#include "../trx_sysrem.h"
 
 using namespace trx;
 
@@ -99,6 +101,9 @@ struct ObservedSet {
   int32_t nexp = 0, nseg = 0; int64_t npix = 0;
   DevBuf d_seg, d_data, d_weight, d_gain;            // [nseg + 1], [nexp][npix], the same or none, [npix] or none
   std::vector<int64_t> seg;                          // [nseg + 1] on the host: trx_set_filter cuts its tiles from it
+  // trx_detrend_observed (trx_sysrem.hip.h): the data as trx_set_observed installed them, moved aside by the first detrend
+  // call -- d_data then holds a call's residuals -- and moved back by the undo (empty: d_data is the raw set)
+  DevBuf d_raw;
 };
 // a filter installed by trx_set_filter over the observed set (trx_filter.hip.h): the matrices zero-padded to npad
 // components and exposure-major, and the tiles of the observed set's segments
@@ -297,6 +302,10 @@ struct trx_handle {
   DevBuf d_broad;                                      // the broadened spectrum [nwn] of a broadened or pixel run, grown on demand
   std::unique_ptr<ExposureSet> exposures;              // trx_set_exposures (null: none); belongs to `observed`
   DevBuf d_exscale, d_exsmear;                         // the table's arrays [nexp] each, uploaded by every run that takes it, grown on demand
+  // trx_detrend_observed (trx_sysrem.hip.h), grown on demand: the residuals [nexp][npix] a call builds (swapped with the
+  // observed set's data when it succeeds), the time vector [nseg][nexp], the column vector [npix], coef [ncomp][npix],
+  // U [nseg][nexp][ncomp] (its host copy: sr_basis) and the tiles of the set's segments
+  DevBuf d_sr_r, d_sr_a, d_sr_c, d_sr_coef, d_sr_basis, d_sr_tiles; std::vector<double> sr_basis;
 };
 
 namespace {
@@ -3876,6 +3885,111 @@ int trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o, doub
   if (lag_index) HIPCHK(h, hipMemcpyAsync(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (nrows) *nrows = L.R;
+  return TRX_OK;
+}
+
+// ---- detrending the observed set itself: model injection and SYSREM (trx_sysrem.hip.h) --------------
+static void move_buf(DevBuf &to, DevBuf &from) { to.release(); to.p = from.p; to.bytes = from.bytes; from.p = nullptr; from.bytes = 0; }
+
+// the SYSREM kernels of dt over the residuals in h->d_sr_r, on the main queue: X the call's extents, ntiles the tiles in h->d_sr_tiles
+static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend *dt, const SysremExtents &X, int64_t ntiles)
+{
+  SysremArgs A{};
+  A.r = h->d_sr_r.as<double>(); A.weight = O->d_weight.as<double>(); A.tiles = h->d_sr_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
+  A.a = h->d_sr_a.as<double>(); A.c = h->d_sr_c.as<double>(); A.coef = h->d_sr_coef.as<double>(); A.basis = h->d_sr_basis.as<double>();
+  A.npix = O->npix; A.ntiles = ntiles; A.nrows = X.rows; A.nexp = O->nexp; A.nseg = O->nseg; A.ncomp = dt->ncomp;
+  // (every address the kernels read or write: the residuals and the weights [nexp][npix], the tiles -- which cover [0, npix) --,
+  // the bounds [nseg + 1], a [nseg][nexp], c [npix], coef [ncomp][npix], U [nseg][nexp][ncomp])
+  if (!A.r || !A.tiles || !A.seg_first || !A.a || !A.c || !A.coef || !A.basis || A.npix < 1 || A.nexp < 1 || A.nseg < 1 || ntiles < 1 ||
+      h->d_sr_r.bytes < X.r_bytes || (A.weight && O->d_weight.bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
+      O->d_seg.bytes < sizeof(int64_t) * ((size_t)O->nseg + 1) || h->d_sr_a.bytes < X.a_bytes || h->d_sr_c.bytes < X.c_bytes ||
+      h->d_sr_coef.bytes < X.coef_bytes || h->d_sr_basis.bytes < X.basis_bytes ||
+      X.tile_blocks < 1 || X.tile_blocks > 0x7fffffffLL || X.row_blocks < 1 || X.row_blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the SYSREM kernels (not launched)");
+  // (an empty segment has no tile: its vectors stay zero)
+  HIPCHK(h, hipMemsetAsync(A.basis, 0, X.basis_bytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(A.coef, 0, X.coef_bytes, h->stream));
+  const dim3 tgrid((unsigned)X.tile_blocks), tblock(64 * kFiltWaves), rgrid((unsigned)X.row_blocks), rblock(64 * kMomWaves);
+  for (int32_t i = 0; i < dt->ncomp; i++) {
+    A.comp = i;
+    for (int32_t k = 0; k < dt->niter; k++) {
+      SysremArgs C = A;
+      if (k == 0) C.a = nullptr;                       // (a component starts from a = 1)
+      hipLaunchKernelGGL(k_sysrem_cols, tgrid, tblock, 0, h->stream, C);
+      hipLaunchKernelGGL(k_sysrem_rows, rgrid, rblock, 0, h->stream, A);
+    }
+    hipLaunchKernelGGL(k_sysrem_close, tgrid, tblock, 0, h->stream, A);
+    hipLaunchKernelGGL(k_sysrem_subtract, tgrid, tblock, 0, h->stream, A);
+  }
+  HIPCHK(h, hipGetLastError());
+  return TRX_OK;
+}
+
+int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                         const trx_detrend *dt, double *basis, double *coef, double *data, int64_t *nsingular, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_detrend_observed";
+  const ProductState P = product_state(h);
+  std::string msg;
+  if (const int rc = detrend_checks(P, dt, a, o, nshift, shift, msg)) return fail(h, rc, msg);
+  ObservedSet *const O = h->observed.get();
+  HIPCHK(h, hipSetDevice(h->device));
+  if (detrend_is_undo(dt)) {
+    // (the buffer of the residuals is kept for the next call when the handle has none)
+    if (O->d_raw.p) {
+      DevBuf old; move_buf(old, O->d_data); move_buf(O->d_data, O->d_raw);
+      if (!h->d_sr_r.p) move_buf(h->d_sr_r, old);
+    }
+    h->filter.reset();
+    if (nsingular) *nsingular = 0;
+    return TRX_OK;
+  }
+  std::vector<FilterTile> tiles;
+  if (const int rc = sysrem_tiles(P, tiles, msg)) return fail(h, rc, msg);
+  const int64_t ntiles = (int64_t)tiles.size();
+  const SysremExtents X = sysrem_extents(O->npix, O->nexp, O->nseg, dt->ncomp, dt->niter, ntiles, kPixBlock, kFiltWaves, kMomWaves);
+  try { h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
+  // the pairs of the injection: the pixel stage alone, as trx_run_exposed (or, without a table, trx_run_pixels) runs it -- no
+  // moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for
+  if (dt->inject) {
+    PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
+    if (const int rc = pixel_run(h, who, a, o, spectrum, PR, shift, dbg)) return rc;
+    if (PR.ext.pairs != X.cells || h->d_pixout.bytes < PR.ext.pair_bytes) return fail(h, TRX_E_HIP, "internal: the injection's pairs are not the observed set's size");
+  }
+  int rc;
+  if ((rc = ensure(h, h->d_sr_r, X.r_bytes)) || (rc = ensure(h, h->d_sr_a, X.a_bytes)) || (rc = ensure(h, h->d_sr_c, X.c_bytes)) ||
+      (rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = ensure(h, h->d_sr_basis, X.basis_bytes)) || (rc = upload(h, h->d_sr_tiles, tiles)))
+    return rc;
+  // step 0 and 1: the raw data, or the injected data, into the call's own buffer
+  const DevBuf &raw = O->d_raw.p ? O->d_raw : O->d_data;
+  if (!raw.p || raw.bytes < X.r_bytes) return fail(h, TRX_E_HIP, "internal: the observed set's data are not its size");
+  if (dt->inject) {
+    SysremInjectArgs IA{};
+    IA.pairs = h->d_pixout.as<double2>(); IA.raw = raw.as<double>(); IA.gain = O->d_gain.as<double>(); IA.r = h->d_sr_r.as<double>();
+    IA.npix = O->npix; IA.cells = X.cells; IA.p0 = dt->p0; IA.p1 = dt->p1;
+    if ((IA.gain && O->d_gain.bytes < X.c_bytes) || X.elem_blocks < 1 || X.elem_blocks > 0x7fffffffLL)
+      return fail(h, TRX_E_HIP, "internal: incomplete arguments for the injection kernel (not launched)");
+    hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)X.elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
+    HIPCHK(h, hipGetLastError());
+  } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, X.r_bytes, hipMemcpyDeviceToDevice, h->stream));
+  // step 2
+  if ((rc = launch_sysrem(h, O, dt, X, ntiles))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->sr_basis.data(), h->d_sr_basis.p, X.basis_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished; the tiles' staging vector may go)
+  // step 3: the weighted filter of U as trx_set_weighted_filter makes it -- it reads the set's weights, not its data --, the
+  // outputs, and only then the swap
+  if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, dt->ncomp, msg))) return fail(h, rc, msg);
+  const trx_wfilter wf{dt->ncomp, 0, h->sr_basis.data()};
+  std::unique_ptr<FilterSet> S; int64_t nsing = 0;
+  if ((rc = make_wfilter_set(h, &wf, S, &nsing))) return rc;
+  if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, X.coef_bytes, hipMemcpyDeviceToHost));
+  if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, X.r_bytes, hipMemcpyDeviceToHost));
+  if (basis) std::memcpy(basis, h->sr_basis.data(), X.basis_bytes);
+  if (!O->d_raw.p) { move_buf(O->d_raw, O->d_data); move_buf(O->d_data, h->d_sr_r); }
+  else { std::swap(O->d_data.p, h->d_sr_r.p); std::swap(O->d_data.bytes, h->d_sr_r.bytes); }
+  install_filter_set(h, S);
+  if (nsingular) *nsingular = nsing;
   return TRX_OK;
 }
 

@@ -1,0 +1,162 @@
+// trx_sysrem.hip.h -- detrending the observed exposures themselves on the device (trx_detrend_observed,
+// include/transit_hip.h): the injection of the model into the raw data and SYSREM (Tamuz, Mazeh & Zucker 2005) per
+// segment, one component after another.  The arithmetic is ../trx_sysrem.h's, the same source a CPU program runs.
+//
+// The residuals r [nexp][npix] start as the raw data (or the injected data) in a buffer of their own.  Per component the
+// time vector a [nseg][nexp] starts at 1 and alternates niter times with the column vector c [npix]:
+//
+//   k_sysrem_inject    element-wise over [nexp][npix]: r = F * (p0 g + p1) where the run's pair has b > 0, F elsewhere.
+//   k_sysrem_cols      the column step.  One lane per pixel column, one wavefront per tile of filter_layout's tile table
+//                    (<= 64 pixels of one segment), kFiltWaves tiles per block.  v ascends, the loads of w and r of
+//                    kSysTrips exposures issued before the first add (a trip past the last exposure reads the last one
+//                    again and adds nothing); a_v is wave-uniform (a null a: every a_v = 1, a component's first step).
+//   k_sysrem_rows      the row step.  k_pixel_moments' structure: one wavefront per row (v, s), kMomWaves rows per
+//                    block; lane l adds the segment's pixels first + l, first + l + 64, ... in that order, kMomTrips
+//                    trips in flight (a lane past the end reads the last pixel again and adds nothing), then wave_sum's
+//                    butterfly.  nexp * nseg is the parallel axis.
+//   k_sysrem_close     one wavefront per tile: the norm t of its segment's a (every tile of a segment computes the same
+//                    t from the same a, which the kernel does not change), the scaled c into coef[i][p], and -- the
+//                    segment's first tile -- the scaled a into U[s][v][i].
+//   k_sysrem_subtract  one wavefront per tile: r[v][p] = r[v][p] - U[s][v][i] * coef[i][p].
+//
+// No LDS, no atomics; cross-lane work goes through wave_sum only.  The bits of a segment's result depend on that segment's
+// data and weights, ncomp and niter -- not on other segments, the launch or the handle.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "transit_hip.h"
+#include "trx_device.h"
+#include "trx_kernels.hip.h"
+#include "trx_filter.hip.h"
+#include "trx_moments.hip.h"
+#include "../trx_sysrem.h"
+
+namespace trx {
+
+constexpr int kSysTrips = 8;                          // exposures whose loads a column kernel's wave has in flight at once
+
+struct SysremInjectArgs {
+  const double2 *pairs;     // [nexp][npix] (a, b) of the run
+  const double *raw;        // [nexp][npix] F
+  const double *gain;       // [npix], or null: all 1
+  double *r;                // [nexp][npix]
+  int64_t npix, cells;      // cells = nexp * npix
+  double p0, p1;
+};
+
+struct SysremArgs {
+  double *r;                // [nexp][npix] the residuals
+  const double *weight;     // [nexp][npix], or null: all 1
+  const FilterTile *tiles;  // [ntiles]
+  const int64_t *seg_first; // [nseg + 1]
+  double *a;                // [nseg][nexp]; k_sysrem_cols: null = all 1
+  double *c;                // [npix]
+  double *coef;             // [ncomp][npix]
+  double *basis;            // U [nseg][nexp][ncomp]
+  int64_t npix, ntiles, nrows;      // nrows = nexp * nseg
+  int32_t nexp, nseg, ncomp, comp;  // comp: the component being fitted
+};
+
+__global__ __launch_bounds__(kPixBlock) void k_sysrem_inject(SysremInjectArgs A)
+{
+  const int64_t k = (int64_t)blockIdx.x * kPixBlock + threadIdx.x;
+  if (k >= A.cells) return;
+  const int64_t p = k % A.npix;
+  const double2 ab = A.pairs[k];
+  A.r[k] = sysrem_inject(A.raw[k], ab.x, ab.y, A.gain ? A.gain[p] : 1.0, A.p0, A.p1);
+}
+
+__global__ __launch_bounds__(64 * kFiltWaves) void k_sysrem_cols(SysremArgs A)
+{
+#pragma clang fp contract(off)
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (tile >= A.ntiles) return;
+  const FilterTile T = A.tiles[tile];
+  if (lane >= T.count) return;
+  const int64_t p = T.first + lane;
+  const int nexp = A.nexp;
+  const double *const a = A.a ? A.a + (int64_t)T.seg * nexp : nullptr;
+  double num = 0.0, den = 0.0;
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    double w[kSysTrips], r[kSysTrips];
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++) {
+      const int64_t at = (int64_t)min(v0 + t, nexp - 1) * A.npix + p;
+      r[t] = A.r[at];
+      w[t] = A.weight ? A.weight[at] : 1.0;
+    }
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) sysrem_col_term(w[t], r[t], a ? a[v0 + t] : 1.0, num, den);
+  }
+  A.c[p] = sysrem_ratio(num, den);
+}
+
+__global__ __launch_bounds__(64 * kMomWaves) void k_sysrem_rows(SysremArgs A)
+{
+#pragma clang fp contract(off)
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t row = (int64_t)blockIdx.x * kMomWaves + (threadIdx.x >> 6);
+  if (row >= A.nrows) return;                          // (a whole wave: the butterfly below has all its lanes)
+  const int64_t v = row / A.nseg, s = row - v * A.nseg;
+  const int64_t first = A.seg_first[s], last = A.seg_first[s + 1];
+  const int64_t base = v * A.npix;
+  double num = 0.0, den = 0.0;
+  for (int64_t p0 = first; p0 < last; p0 += 64 * kMomTrips) {
+    double r[kMomTrips], w[kMomTrips], c[kMomTrips]; bool in[kMomTrips];
+#pragma unroll
+    for (int t = 0; t < kMomTrips; t++) {
+      const int64_t q = p0 + 64 * t + lane;
+      in[t] = q < last;
+      const int64_t p = in[t] ? q : last - 1;
+      r[t] = A.r[base + p];
+      w[t] = A.weight ? A.weight[base + p] : 1.0;
+      c[t] = A.c[p];
+    }
+#pragma unroll
+    for (int t = 0; t < kMomTrips; t++)
+      if (in[t]) sysrem_row_term(w[t], r[t], c[t], num, den);
+  }
+  num = wave_sum(num); den = wave_sum(den);
+  if (lane == 0) A.a[s * A.nexp + v] = sysrem_ratio(num, den);
+}
+
+__global__ __launch_bounds__(64 * kFiltWaves) void k_sysrem_close(SysremArgs A)
+{
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (tile >= A.ntiles) return;
+  const FilterTile T = A.tiles[tile];
+  const int nexp = A.nexp;
+  const double *const a = A.a + (int64_t)T.seg * nexp;
+  const double t = sysrem_norm(a, nexp);
+  if (T.first == A.seg_first[T.seg])
+    for (int v = lane; v < nexp; v += 64) A.basis[((int64_t)T.seg * nexp + v) * A.ncomp + A.comp] = sysrem_close_a(a[v], t);
+  if (lane >= T.count) return;
+  const int64_t p = T.first + lane;
+  A.coef[(int64_t)A.comp * A.npix + p] = sysrem_close_c(A.c[p], t);
+}
+
+__global__ __launch_bounds__(64 * kFiltWaves) void k_sysrem_subtract(SysremArgs A)
+{
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (tile >= A.ntiles) return;
+  const FilterTile T = A.tiles[tile];
+  if (lane >= T.count) return;
+  const int64_t p = T.first + lane;
+  const int nexp = A.nexp;
+  const double *const U = A.basis + (int64_t)T.seg * nexp * A.ncomp + A.comp;
+  const double c = A.coef[(int64_t)A.comp * A.npix + p];
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    double r[kSysTrips];
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++) r[t] = A.r[(int64_t)min(v0 + t, nexp - 1) * A.npix + p];
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) A.r[(int64_t)(v0 + t) * A.npix + p] = sysrem_subtract(r[t], U[(int64_t)(v0 + t) * A.ncomp], c);
+  }
+}
+
+}  // namespace trx

@@ -213,6 +213,7 @@ def hip_library():
         _abi.bind_broaden_api(lib)
         _abi.bind_exposures_api(lib)
         _abi.bind_expmap_api(lib)
+        _abi.bind_sysrem_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -234,6 +235,15 @@ def hip_library():
 def _dp(x):
     """the double pointer of an array, or None for None (an output the caller does not want)"""
     return x.ctypes.data_as(_abi.c_double_p) if x is not None else None
+
+
+class Detrended:
+    """What Engine.detrend_observed returns: basis [nseg, nexp, ncomp] the fitted time vectors U, coef [ncomp, npix] their
+    column vectors, data [nexp, npix] the residuals now installed as the observed data (None after the undo), nsingular the
+    columns the installed weighted filter's pivot rule makes dead, spectrum the injection run's spectrum (None without)."""
+
+    def __init__(self, basis, coef, data, nsingular, spectrum=None):
+        self.basis, self.coef, self.data, self.nsingular, self.spectrum = basis, coef, data, nsingular, spectrum
 
 
 class Engine(CEngine):
@@ -473,6 +483,35 @@ class Engine(CEngine):
             raise EngineError(rc, "trx_run_exposed_map", self._last_error())
         out = (m,) + ((idx,) if lag_index else ()) + ((int(nr.value),) if nrows else ()) + ((spec,) if spectrum else ())
         return out if len(out) > 1 else m
+
+    def detrend_observed(self, ncomp: int, niter: int = 10, inject=None, outputs: bool = True) -> "Detrended":
+        """trx_detrend_observed: SYSREM on the observed exposures themselves, on the device, always from the RAW data of
+        set_observed -- ncomp components of niter alternations per segment (xcor.sysrem_reference, bit for bit).  inject:
+        None, or (atm, opts, shifts, p0, p1): the model of this handle's pixel stage at the exposures' shifts is multiplied
+        into the raw data first, f0 = F * (p0 g + p1) (xcor.inject_reference of run_exposed's pairs, or run_pixels' without
+        a table).  The residuals become the observed data and the weighted filter of the fitted basis the filter;
+        run_filtered_moments, run_filtered_map and run_exposed_map then are the recovery.  ncomp = 0 is the undo: the raw
+        data back, the filter slot cleared.  Returns a Detrended: basis [nseg, nexp, ncomp], coef [ncomp, npix], data
+        [nexp, npix] (the residuals now installed), nsingular, and spectrum (None without an injection).  outputs=False
+        leaves basis, coef and data on the device (None in the result): the loop of an injection-recovery test needs
+        only the map that follows."""
+        nexp, nseg = getattr(self, "mom_shape", (0, 0))
+        npix = getattr(self, "npix", 0)
+        dt = _abi.TrxDetrend(int(ncomp), int(niter), 0 if inject is None else 1, 0, 0.0, 0.0)
+        atm = opts = sh = spec = None
+        if inject is not None:
+            atm, opts, shifts, dt.p0, dt.p1 = inject
+            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+            spec = np.zeros(self.nwn)
+        n = max(int(ncomp), 0) if outputs else 0
+        basis, coef, data = np.zeros((nseg, nexp, n)), np.zeros((n, npix)), np.zeros((nexp, npix))
+        nsing = C.c_int64(0)
+        rc = self._lib.trx_detrend_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
+                                            _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), C.byref(dt),
+                                            _dp(basis) if n else None, _dp(coef) if n else None, _dp(data) if n else None, C.byref(nsing), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_detrend_observed", self._last_error())
+        return Detrended(basis if n else None, coef if n else None, data if n else None, int(nsing.value), spec)
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device

@@ -64,6 +64,16 @@ with b <= 0 at any exposure.  The operations and their order are stated in inclu
     weighted_filter_exact(pairs, obs, wf)                the same projection in np.longdouble, rounded at the end
     weighted_filter_bound(pairs, obs, wf)                how far a double evaluation can lie from the exact projection
 
+Detrending the observed exposures themselves on the device (Engine.detrend_observed; trx_detrend_observed): a model is
+multiplied into the RAW data (optional), SYSREM runs on them per segment, the residuals become the observed data and the
+weighted filter of the fitted basis the filter.  The operations and their order are stated in include/transit_hip.h; the
+mirrors here follow them bit for bit, the row sums included (64 lane sums, then the wave's butterfly).
+
+    wave_sum(lanes)                                      the butterfly over 64 lane sums [..., 64]: partner lane ^ 32, 16, 8, 4, 2, 1
+    row_sum(terms)                                       the sum of terms [..., n] in the device's order: lanes, then wave_sum
+    inject_reference(pairs, obs, p0, p1)                 f0 = F * (p0 g + p1) where b > 0, F elsewhere
+    sysrem_reference(data, weight, seg_first, ncomp, niter)      (basis, coef, resid): the mirror of the device's SYSREM
+
 The detection map with the filter applied to every cell's own model matrix (Engine.run_filtered_map /
 Batch.run_filtered_map; trx_run_filtered_map): a cell takes at every exposure the row of the lag NEAREST to its velocity,
 that matrix goes through the filter and the moments above, and the cell is the statistic added over the segments and
@@ -739,6 +749,85 @@ def sysrem_basis(data, weight, seg_first, ncomp: int, niter: int = 10) -> np.nda
             out[s, :, i] = a
             r -= a[:, None] * c[None, :]
     return out
+
+
+_LANE = np.arange(64)
+
+
+def wave_sum(lanes) -> np.ndarray:
+    """The wave's butterfly sum of 64 lane values (the last axis, [..., 64]): every lane adds its partner lane ^ 32, then
+    ^ 16, 8, 4, 2, 1 -- the order of the device's wave_sum.  Returns lane 0's total (all lanes hold the same bits)."""
+    x = np.asarray(lanes, dtype=np.float64)
+    if x.shape[-1] != 64:
+        raise ValueError("wave_sum: 64 lanes on the last axis")
+    for o in (32, 16, 8, 4, 2, 1):
+        x = x + x[..., _LANE ^ o]
+    return x[..., 0]
+
+
+def row_sum(terms) -> np.ndarray:
+    """The sum of terms [..., n] along the last axis in the order of the device's row kernels (k_pixel_moments,
+    k_sysrem_rows): lane l adds the terms l, l + 64, l + 128, ... in that order from +0, then wave_sum."""
+    t = np.asarray(terms, dtype=np.float64)
+    acc = np.zeros(t.shape[:-1] + (64,))
+    for k in range(0, t.shape[-1], 64):
+        chunk = t[..., k:k + 64]
+        acc[..., :chunk.shape[-1]] = acc[..., :chunk.shape[-1]] + chunk
+    return wave_sum(acc)
+
+
+def inject_reference(pairs, obs: Observed, p0: float, p1: float) -> np.ndarray:
+    """[nexp, npix]: the injected exposures of trx_detrend_observed from the pixel pairs [nexp, npix, 2] of a run and the
+    RAW observed set: where b > 0, g = gain_p * (a / b), m = p0 * g, m = m + p1, f0 = F * m; F's bits elsewhere."""
+    g, on = _model(pairs, obs)
+    m = np.float64(p0) * g
+    m = m + np.float64(p1)
+    return np.where(on, obs.data * m, obs.data)
+
+
+def _ratio(num, den):
+    return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+
+
+def sysrem_reference(data, weight, seg_first, ncomp: int, niter: int = 10):
+    """(basis [nseg, nexp, ncomp], coef [ncomp, npix], resid [nexp, npix]): SYSREM per segment as trx_detrend_observed
+    defines it (include/transit_hip.h), in numpy double in exactly its order -- the mirror of k_sysrem_cols,
+    k_sysrem_rows, k_sysrem_close and k_sysrem_subtract, bit for bit.  The column sums run over v ascending, the row sums
+    are row_sum's, the norm's sum runs over v ascending and its root is np.sqrt.  sysrem_basis is the same algorithm with
+    numpy's own summation order."""
+    resid = np.array(data, dtype=np.float64)
+    if resid.ndim != 2:
+        raise ValueError("sysrem_reference: data of shape [nexp][npix]")
+    w_all = np.ones_like(resid) if weight is None else np.asarray(weight, dtype=np.float64)
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    nexp, npix, nseg = resid.shape[0], resid.shape[1], seg.size - 1
+    basis, coef = np.zeros((nseg, nexp, ncomp)), np.zeros((ncomp, npix))
+    with np.errstate(all="ignore"):
+        for s in range(nseg):
+            k = slice(int(seg[s]), int(seg[s + 1]))
+            r, w = resid[:, k], w_all[:, k]
+            n = r.shape[1]
+            if n == 0:
+                continue
+            for i in range(ncomp):
+                a, c = np.ones(nexp), np.zeros(n)
+                for _ in range(niter):
+                    num, den = np.zeros(n), np.zeros(n)
+                    for v in range(nexp):
+                        num = num + (w[v] * r[v]) * a[v]
+                        den = den + (w[v] * a[v]) * a[v]
+                    c = _ratio(num, den)
+                    a = _ratio(row_sum((w * r) * c[None, :]), row_sum((w * c[None, :]) * c[None, :]))
+                n2 = np.float64(0.0)
+                for v in range(nexp):
+                    n2 = n2 + a[v] * a[v]
+                t = np.sqrt(n2)
+                if t > 0:
+                    a, c = a / t, c * t
+                basis[s, :, i] = a
+                coef[i, k] = c
+                r -= a[:, None] * c[None, :]
+    return basis, coef, resid
 
 
 def _check_wfilter(obs: Observed, wf: WeightedFilter):
