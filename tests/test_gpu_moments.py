@@ -7,7 +7,8 @@ The case is test_gpu_pixels' (40 000 lines, 6001 bins, 60 layers), the pixel set
 (one in A, one in B) are moved off the grid, to 2400 and 2700 cm-1: their pairs have b = 0 and count in no moment.
 Segment lengths [1, 63, 64, 65, 200, 0, 7, 400]: one lane, a wave less one, a wave, a wave plus one, several
 strides, an empty segment, a short one, the longest; 7 exposures x 8 segments = 56 waves, the last block ragged.
-(A second segmentation, [300, 200, 300], has a segment with windows of both forms in it.)
+(A second segmentation, [300, 200, 300], has a segment with windows of both forms in it.)  The exposure and the order axis
+-- 64, 65 and 130 exposures, 64, 65 and 130 segments -- are test_gpu_many_exposures.py's.
 
 Tolerance of the accuracy checks, per moment, relative to xcor.abs_reference (the same sum over |terms|):
 (n_max + 16) * 2^-52 with n_max the longest segment -- the worst case of a double sum of n terms, (n - 1) * 2^-53

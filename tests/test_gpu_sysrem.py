@@ -6,7 +6,8 @@ The case is test_gpu_wfilter's: tp.make("eclipse", 20 000 lines, 6001 bins), the
 (b = 0 at every exposure), the segments [1, 63, 64, 65, 200, 0, 7, 400], 7 exposures, and a set of 12 exposures for 9
 components.  The data are sysrem_cases.data_set (smooth trends plus seeded noise) at the model's scale; the edge weights are
 sysrem_cases.edge_weights: 5 % single masked entries, a column masked at every exposure and an exposure masked over a whole
-segment.
+segment.  The exposure and the order axis -- 64, 65 and 130 exposures with up to 16 components, 64, 65 and 130 segments --
+are test_gpu_many_exposures.py's.
 
 One refusal of the header's list cannot be reached on a device -- nexp * npix above what one pixel launch takes needs more
 than 5e11 pairs --; tests/sysrem_check.cpp holds its text on the host."""

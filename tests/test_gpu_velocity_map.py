@@ -9,7 +9,8 @@ the 4 rows of a block), and two observed sets: tm.observed() with the segments [
 test_gpu_trail.end_to_end_map.  The map is Kp = 40, 70, 100, 130, 160, 190, 250 by Vsys = -12 .. 12 in steps of 6: with
 sin(2 pi 0.06) = 0.36812 the Kp = 250 row is outside the lag grid everywhere (92.0 + |Vsys| > 81), the Kp = 190 row at
 Vsys = +-12 only (81.9), everything else inside; the middle exposure has orbit = 0 and sits on lag nodes.  A second grid
-of 13 x 11 = 143 cells is more than one block and ends in a ragged one.
+of 13 x 11 = 143 cells is more than one block and ends in a ragged one.  More than one trip of a wave over the exposures
+(k_velocity_map) and over the segments (k_trail_stat) -- 64, 65 and 130 of either -- is test_gpu_many_exposures.py's.
 
 THE CONTRACT: map is bit for bit xcor.map_from_per of the per the same call returned; per is xcor.trail_statistic of
 run_trail's trail within xcor.per_bound -- in the same bits for ccf and chi2, whose rows use only correctly rounded
