@@ -1028,6 +1028,50 @@ int  trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o,
                           double *data /* [nexp][npix]: the residuals now installed, host; may be NULL */,
                           int64_t *nsingular /* may be NULL */, trx_debug *dbg /* may be NULL */);
 
+/* Weighing the observed set by the scatter of its pixel columns, on the device: the step of a detection pipeline between
+ * SYSREM and the map.  One call reads the data the handle holds, forms every column's variance in time and every
+ * segment's median variance, masks the columns whose variance stands out of their segment's, writes the new weights and
+ * factorises the installed weighted filter again against them.  The data are not divided: the weights carry the step.
+ *
+ * Every operation is IEEE double rounded once, no fused multiply-add; sums start from +0 and run in the order written.
+ * r is the data currently installed -- the residuals after trx_detrend_observed, the raw set otherwise --, W the weights
+ * as trx_set_observed installed them (1 everywhere without) -- NEVER the result of an earlier weigh call.
+ * 1. Column pass, per pixel p, v ascending over the entries with W[v][p] > 0:  n their count;  s = sum of r;
+ *    mean = s / (double)n;  q = sum of d * d with d = r - mean (a second pass, the same order);  var_p = q / (double)(n - 1).
+ *    The column is LIVE if n >= min_live, var_p > 0 and var_p is finite; otherwise var_p = +0.
+ * 2. Segment median, per segment over its m live columns: med_s is the lower median of their var, the value of rank
+ *    (m - 1) / 2 in ascending var, ties by ascending p; m = 0: med_s = +0.  (Found by counting -- exact, order-free, no
+ *    atomics.)
+ * 3. Keep rule:  lim = clip * clip;  lim = lim * med_s;  p is KEPT if it is live and (clip == 0 or var_p <= lim).
+ *    nmasked is the number of live columns the clip removed.
+ * 4. New weights:  TRX_SCATTER_VARIANCE: w'[v][p] = 1.0 / var_p (divided once per column) where W[v][p] > 0 and p is kept,
+ *    +0 elsewhere;  TRX_SCATTER_MASK: w'[v][p] = W[v][p] where p is kept, +0 elsewhere.
+ * 5. At once and only after every kernel has finished, w' -- built in a buffer of its own -- becomes the observed set's
+ *    weights; the handle keeps W aside on the device.  If the filter slot holds a WEIGHTED filter, its factor and pivot
+ *    flags are made again from its own basis against w' (trx_set_weighted_filter's kernel and pivot rule; nsingular as
+ *    there, 0 without a weighted filter) in new buffers and swapped in with the weights.  A plain filter, the high-pass,
+ *    exposure table, broadening, gain, data and pixel set stay as they are.  variance, median and weight, where given,
+ *    receive var, med and w'.
+ * 6. The undo, and "from raw": sc NULL or kind = TRX_SCATTER_NONE puts W back in force and factorises the weighted filter
+ *    again against it; TRX_OK even if nothing had been weighed; nmasked 0, and variance, median and weight are not written.
+ *    trx_detrend_observed's SYSREM and filter factor always read W, and a successful detrend call (its undo included)
+ *    leaves W as the weights in force -- a failed one the weights as they were --: detrend, weigh, detrend gives the second
+ *    detrend the bits of a fresh one.  trx_set_weighted_filter after a weigh factorises against the weights in force.
+ *    trx_set_observed and trx_set_pixels drop everything.
+ * 7. TRX_E_ARG, the reason in trx_last_error, nothing touched, checked in this order: no observed set; kind outside 0 .. 2;
+ *    min_live < 2 or above nexp; clip non-finite, negative or in (0, 1) (a non-NULL sc is checked whole, whatever its
+ *    kind).  TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.  A call that fails later (TRX_E_HIP,
+ *    TRX_E_NOMEM) leaves the previous weights and filter in force.
+ * Not here: a batch form, shards, dividing the data, sigma-clipping single entries. */
+#define TRX_SCATTER_NONE     0   /* undo: the weights as trx_set_observed installed them */
+#define TRX_SCATTER_VARIANCE 1   /* w' = 1 / var_p on the kept columns' live entries      */
+#define TRX_SCATTER_MASK     2   /* w' = W on the kept columns, 0 on the others           */
+typedef struct { int32_t kind, min_live; double clip; } trx_scatter;      /* 16 bytes */
+int  trx_weigh_observed(trx_handle *h, const trx_scatter *sc,
+                        double *variance /* [npix], host; may be NULL */, double *median /* [nseg], host; may be NULL */,
+                        double *weight /* [nexp][npix], host; may be NULL */,
+                        int64_t *nmasked /* may be NULL */, int64_t *nsingular /* may be NULL */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

@@ -117,6 +117,13 @@ class TrxDetrend(C.Structure):
                 ("p0", C.c_double), ("p1", C.c_double)]
 
 
+SCATTER_NONE, SCATTER_VARIANCE, SCATTER_MASK = 0, 1, 2      # TRX_SCATTER_*: the kinds of trx_weigh_observed
+
+
+class TrxScatter(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("min_live", C.c_int32), ("clip", C.c_double)]
+
+
 HIGHPASS_MAX_HALF = 1024
 
 
@@ -366,4 +373,12 @@ def bind_sysrem_api(lib):
                                          C.POINTER(TrxDetrend), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int64),
                                          C.POINTER(TrxDebug)]
     lib.trx_detrend_observed.restype = C.c_int
+    return lib
+
+
+def bind_scatter_api(lib):
+    """argtypes/restypes of the column-scatter entry point (trx_weigh_observed)."""
+    lib.trx_weigh_observed.argtypes = [C.c_void_p, C.POINTER(TrxScatter), c_double_p, c_double_p, c_double_p,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.trx_weigh_observed.restype = C.c_int
     return lib

@@ -46,6 +46,7 @@
 #include "trx_filter.hip.h"
 #include "trx_wfilter.hip.h"
 #include "trx_sysrem.hip.h"
+#include "trx_scatter.hip.h"
 #include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
@@ -59,6 +60,7 @@
 #include "../trx_expmap.h"
 #include "../trx_wfilter.h"
 #include "../trx_sysrem.h"
+#include "../trx_scatter.h"
 
 using namespace trx;
 
@@ -104,6 +106,11 @@ struct ObservedSet {
   // trx_detrend_observed (trx_sysrem.hip.h): the data as trx_set_observed installed them, moved aside by the first detrend
   // call -- d_data then holds a call's residuals -- and moved back by the undo (empty: d_data is the raw set)
   DevBuf d_raw;
+  // trx_weigh_observed (trx_scatter.hip.h): weighed = d_weight holds a weigh call's result and d_wraw the weights as
+  // trx_set_observed installed them -- empty where the set had none: all 1 --, moved aside by the first weigh call and moved
+  // back by its undo and by trx_detrend_observed (not weighed: d_weight is W, d_wraw is empty)
+  DevBuf d_wraw; bool weighed = false;
+  const DevBuf &raw_weight() const { return weighed ? d_wraw : d_weight; }
 };
 // a filter installed by trx_set_filter over the observed set (trx_filter.hip.h): the matrices zero-padded to npad
 // components and exposure-major, and the tiles of the observed set's segments
@@ -306,6 +313,10 @@ struct trx_handle {
   // observed set's data when it succeeds), the time vector [nseg][nexp], the column vector [npix], coef [ncomp][npix],
   // U [nseg][nexp][ncomp] (its host copy: sr_basis) and the tiles of the set's segments
   DevBuf d_sr_r, d_sr_a, d_sr_c, d_sr_coef, d_sr_basis, d_sr_tiles; std::vector<double> sr_basis;
+  // trx_weigh_observed (trx_scatter.hip.h), grown on demand: the weights [nexp][npix] a call builds (swapped with the observed
+  // set's when it succeeds), the variances [npix], the medians [nseg], the columns' flags [npix] and the tiles; the factor
+  // and the pivot flags a call makes for the installed weighted filter (swapped with the filter's)
+  DevBuf d_sc_w, d_sc_var, d_sc_med, d_sc_flag, d_sc_tiles, d_sc_fac, d_sc_live;
 };
 
 namespace {
@@ -3547,10 +3558,47 @@ int trx_set_filter(trx_handle *h, const trx_filter *f)
   return TRX_OK;
 }
 
+// Every column's factor and pivot flag of the weighted filter S over the observed set O against `weight` ([nexp][npix] of
+// weight_bytes, or null: all 1), into fac and live (grown to size): k_wfilter_factor from S's own basis and tiles, which are
+// on the device.  The flags come back once for the count of the singular columns.  trx_set_weighted_filter installs with
+// it; trx_weigh_observed makes an installed filter's factor again against other weights, in buffers of its own.
+static int factor_wfilter(trx_handle *h, const FilterSet &S, const ObservedSet *O, const double *weight, size_t weight_bytes, DevBuf &fac, DevBuf &live,
+                          int64_t *nsingular)
+{
+  if (nsingular) *nsingular = 0;
+  const WfilterExtents WX = wfilter_extents(S.npix, S.nexp, S.nseg, S.ncomp, S.npad, S.ntiles, kFiltWaves);
+  std::vector<int32_t> flags;
+  try { flags.assign((size_t)S.npix, 0); } catch (...) { return fail(h, TRX_E_NOMEM, "weighted filter: out of host memory"); }
+  int rc;
+  if ((rc = ensure(h, fac, WX.fac_bytes)) || (rc = ensure(h, live, WX.live_bytes))) return rc;
+  // (a pixel outside every tile -- none: the segments cover [0, npix) -- would keep a zero factor and a zero flag)
+  HIPCHK(h, hipMemsetAsync(fac.p, 0, WX.fac_bytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(live.p, 0, WX.live_bytes, h->stream));
+  WfilterFactorArgs A{};
+  A.weight = weight; A.basis = S.d_back.as<double>(); A.tiles = S.d_tiles.as<FilterTile>();
+  A.fac = fac.as<double>(); A.live = live.as<int32_t>(); A.npix = S.npix; A.ntiles = S.ntiles; A.nexp = S.nexp; A.ncomp = S.ncomp;
+  // (every address the kernel reads or writes: the padded basis, the tiles -- the segments cover [0, npix): at least one --,
+  // the weights, the factor and the flags)
+  if (!O || !S.weighted || !A.basis || !A.tiles || S.nexp < 1 || S.nseg < 1 || S.ncomp < 1 || S.ncomp > S.npad || (S.npad != 4 && S.npad != 8 && S.npad != 16) ||
+      S.npix < 1 || S.ntiles < 1 || S.npix != O->npix || S.nexp != O->nexp || S.nseg != O->nseg || S.nfac != WX.nfac || S.d_back.bytes < WX.basis_bytes ||
+      S.d_tiles.bytes < sizeof(FilterTile) * (size_t)S.ntiles || (weight && weight_bytes < sizeof(double) * (size_t)S.nexp * (size_t)S.npix) ||
+      fac.bytes < WX.fac_bytes || live.bytes < WX.live_bytes || WX.blocks < 1 || WX.blocks > 0x7fffffffLL)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the weighted filter's factor kernel (not launched)");
+  const dim3 grid((unsigned)WX.blocks), block(64 * kFiltWaves);
+  if (S.npad == 4) hipLaunchKernelGGL(k_wfilter_factor<4>, grid, block, 0, h->stream, A);
+  else if (S.npad == 8) hipLaunchKernelGGL(k_wfilter_factor<8>, grid, block, 0, h->stream, A);
+  else hipLaunchKernelGGL(k_wfilter_factor<16>, grid, block, 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(flags.data(), live.p, WX.live_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vector goes when this returns)
+  if (nsingular) for (int32_t x : flags) *nsingular += x ? 0 : 1;
+  return TRX_OK;
+}
+
 // The weighted filter (trx_wfilter.hip.h), checked whole before anything is replaced: the device gets wfilter_layout's basis
-// and tiles, k_wfilter_factor makes every column's factor and flag from them and the observed set's weights, and the flags
-// come back once for the count of the singular columns.
-static int make_wfilter_set(trx_handle *h, const trx_wfilter *f, std::unique_ptr<FilterSet> &out, int64_t *nsingular)
+// and tiles, and factor_wfilter makes every column's factor and flag from them and the weights w -- null: the observed
+// set's weights in force (trx_set_weighted_filter); trx_detrend_observed gives the weights as trx_set_observed installed them.
+static int make_wfilter_set(trx_handle *h, const trx_wfilter *f, std::unique_ptr<FilterSet> &out, int64_t *nsingular, const DevBuf *w = nullptr)
 {
   out.reset();
   if (nsingular) *nsingular = 0;
@@ -3563,33 +3611,14 @@ static int make_wfilter_set(trx_handle *h, const trx_wfilter *f, std::unique_ptr
   if (const int rc = wfilter_layout(P, f, L, msg)) return fail(h, rc, msg);
   S->weighted = true;
   S->ncomp = f->ncomp; S->npad = L.npad; S->nexp = P.nexp; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size();
-  const WfilterExtents WX = wfilter_extents(S->npix, S->nexp, S->nseg, S->ncomp, S->npad, S->ntiles, kFiltWaves);
-  S->nfac = WX.nfac;
-  std::vector<int32_t> live;
-  try { live.assign((size_t)S->npix, 0); } catch (...) { return fail(h, TRX_E_NOMEM, "weighted filter: out of host memory"); }
+  S->nfac = wfilter_extents(S->npix, S->nexp, S->nseg, S->ncomp, S->npad, S->ntiles, kFiltWaves).nfac;
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
-  if ((rc = upload(h, S->d_back, L.basis)) || (rc = upload(h, S->d_tiles, L.tiles)) || (rc = ensure(h, S->d_fac, WX.fac_bytes)) ||
-      (rc = ensure(h, S->d_live, WX.live_bytes)))
-    return rc;
-  // (a pixel outside every tile -- none: the segments cover [0, npix) -- would keep a zero factor and a zero flag)
-  HIPCHK(h, hipMemsetAsync(S->d_fac.p, 0, WX.fac_bytes, h->stream));
-  HIPCHK(h, hipMemsetAsync(S->d_live.p, 0, WX.live_bytes, h->stream));
+  if ((rc = upload(h, S->d_back, L.basis)) || (rc = upload(h, S->d_tiles, L.tiles))) return rc;
   const ObservedSet *O = h->observed.get();
-  WfilterFactorArgs A{};
-  A.weight = O ? O->d_weight.as<double>() : nullptr; A.basis = S->d_back.as<double>(); A.tiles = S->d_tiles.as<FilterTile>();
-  A.fac = S->d_fac.as<double>(); A.live = S->d_live.as<int32_t>(); A.npix = S->npix; A.ntiles = S->ntiles; A.nexp = S->nexp; A.ncomp = S->ncomp;
-  // (every address the kernel reads or writes: wfilter_set_complete -- the segments cover [0, npix): at least one tile)
-  if (!O || !wfilter_set_complete(*S, *O) || WX.blocks < 1 || WX.blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the weighted filter's factor kernel (not launched)");
-  const dim3 grid((unsigned)WX.blocks), block(64 * kFiltWaves);
-  if (S->npad == 4) hipLaunchKernelGGL(k_wfilter_factor<4>, grid, block, 0, h->stream, A);
-  else if (S->npad == 8) hipLaunchKernelGGL(k_wfilter_factor<8>, grid, block, 0, h->stream, A);
-  else hipLaunchKernelGGL(k_wfilter_factor<16>, grid, block, 0, h->stream, A);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(live.data(), S->d_live.p, WX.live_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
-  if (nsingular) for (int32_t x : live) *nsingular += x ? 0 : 1;
+  if (!w && O) w = &O->d_weight;
+  // (factor_wfilter waits for the queue: the staging vectors may go when it returns)
+  if ((rc = factor_wfilter(h, *S, O, w ? w->as<double>() : nullptr, w ? w->bytes : 0, S->d_fac, S->d_live, nsingular))) return rc;
   out = std::move(S);
   return TRX_OK;
 }
@@ -3890,18 +3919,29 @@ int trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o, doub
 
 // ---- detrending the observed set itself: model injection and SYSREM (trx_sysrem.hip.h) --------------
 static void move_buf(DevBuf &to, DevBuf &from) { to.release(); to.p = from.p; to.bytes = from.bytes; from.p = nullptr; from.bytes = 0; }
+static void swap_buf(DevBuf &a, DevBuf &b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
+
+// the weights as trx_set_observed installed them back in force (trx_weigh_observed's undo, and every successful
+// trx_detrend_observed); a weigh call's buffer is kept for the next one when the handle has none
+static void restore_raw_weights(trx_handle *h, ObservedSet *O)
+{
+  if (!O->weighed) return;
+  DevBuf old; move_buf(old, O->d_weight); move_buf(O->d_weight, O->d_wraw);
+  if (!h->d_sc_w.p) move_buf(h->d_sc_w, old);
+  O->weighed = false;
+}
 
 // the SYSREM kernels of dt over the residuals in h->d_sr_r, on the main queue: X the call's extents, ntiles the tiles in h->d_sr_tiles
 static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend *dt, const SysremExtents &X, int64_t ntiles)
 {
   SysremArgs A{};
-  A.r = h->d_sr_r.as<double>(); A.weight = O->d_weight.as<double>(); A.tiles = h->d_sr_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
+  A.r = h->d_sr_r.as<double>(); A.weight = O->raw_weight().as<double>(); A.tiles = h->d_sr_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
   A.a = h->d_sr_a.as<double>(); A.c = h->d_sr_c.as<double>(); A.coef = h->d_sr_coef.as<double>(); A.basis = h->d_sr_basis.as<double>();
   A.npix = O->npix; A.ntiles = ntiles; A.nrows = X.rows; A.nexp = O->nexp; A.nseg = O->nseg; A.ncomp = dt->ncomp;
   // (every address the kernels read or write: the residuals and the weights [nexp][npix], the tiles -- which cover [0, npix) --,
   // the bounds [nseg + 1], a [nseg][nexp], c [npix], coef [ncomp][npix], U [nseg][nexp][ncomp])
   if (!A.r || !A.tiles || !A.seg_first || !A.a || !A.c || !A.coef || !A.basis || A.npix < 1 || A.nexp < 1 || A.nseg < 1 || ntiles < 1 ||
-      h->d_sr_r.bytes < X.r_bytes || (A.weight && O->d_weight.bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
+      h->d_sr_r.bytes < X.r_bytes || (A.weight && O->raw_weight().bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
       O->d_seg.bytes < sizeof(int64_t) * ((size_t)O->nseg + 1) || h->d_sr_a.bytes < X.a_bytes || h->d_sr_c.bytes < X.c_bytes ||
       h->d_sr_coef.bytes < X.coef_bytes || h->d_sr_basis.bytes < X.basis_bytes ||
       X.tile_blocks < 1 || X.tile_blocks > 0x7fffffffLL || X.row_blocks < 1 || X.row_blocks > 0x7fffffffLL)
@@ -3941,6 +3981,7 @@ int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
       DevBuf old; move_buf(old, O->d_data); move_buf(O->d_data, O->d_raw);
       if (!h->d_sr_r.p) move_buf(h->d_sr_r, old);
     }
+    restore_raw_weights(h, O);
     h->filter.reset();
     if (nsingular) *nsingular = 0;
     return TRX_OK;
@@ -3977,18 +4018,85 @@ int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   if ((rc = launch_sysrem(h, O, dt, X, ntiles))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->sr_basis.data(), h->d_sr_basis.p, X.basis_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished; the tiles' staging vector may go)
-  // step 3: the weighted filter of U as trx_set_weighted_filter makes it -- it reads the set's weights, not its data --, the
-  // outputs, and only then the swap
+  // step 3: the weighted filter of U as trx_set_weighted_filter makes it -- it reads the set's weights as trx_set_observed
+  // installed them, not its data --, the outputs, and only then the swap, which puts those weights back in force
   if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, dt->ncomp, msg))) return fail(h, rc, msg);
   const trx_wfilter wf{dt->ncomp, 0, h->sr_basis.data()};
   std::unique_ptr<FilterSet> S; int64_t nsing = 0;
-  if ((rc = make_wfilter_set(h, &wf, S, &nsing))) return rc;
+  if ((rc = make_wfilter_set(h, &wf, S, &nsing, &O->raw_weight()))) return rc;
   if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, X.coef_bytes, hipMemcpyDeviceToHost));
   if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, X.r_bytes, hipMemcpyDeviceToHost));
   if (basis) std::memcpy(basis, h->sr_basis.data(), X.basis_bytes);
   if (!O->d_raw.p) { move_buf(O->d_raw, O->d_data); move_buf(O->d_data, h->d_sr_r); }
   else { std::swap(O->d_data.p, h->d_sr_r.p); std::swap(O->d_data.bytes, h->d_sr_r.bytes); }
+  restore_raw_weights(h, O);
   install_filter_set(h, S);
+  if (nsingular) *nsingular = nsing;
+  return TRX_OK;
+}
+
+// ---- weighing the observed set by its columns' scatter (trx_scatter.hip.h) --------------------------
+int trx_weigh_observed(trx_handle *h, const trx_scatter *sc, double *variance, double *median, double *weight, int64_t *nmasked, int64_t *nsingular)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_weigh_observed";
+  const ProductState P = product_state(h);
+  std::string msg;
+  if (const int rc = scatter_checks(P, sc, msg)) return fail(h, rc, msg);
+  ObservedSet *const O = h->observed.get();
+  FilterSet *const F = h->filter && h->filter->weighted ? h->filter.get() : nullptr;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc; int64_t nsing = 0;
+  if (scatter_is_undo(sc)) {
+    const DevBuf &W = O->raw_weight();
+    if (F && (rc = factor_wfilter(h, *F, O, W.as<double>(), W.bytes, h->d_sc_fac, h->d_sc_live, &nsing))) return rc;
+    restore_raw_weights(h, O);
+    if (F) { swap_buf(F->d_fac, h->d_sc_fac); swap_buf(F->d_live, h->d_sc_live); }
+    if (nmasked) *nmasked = 0;
+    if (nsingular) *nsingular = nsing;
+    return TRX_OK;
+  }
+  std::vector<FilterTile> tiles; std::vector<int32_t> flags;
+  if ((rc = scatter_tiles(P, kScatBlock, tiles, msg))) return fail(h, rc, msg);
+  const int64_t ntiles = (int64_t)tiles.size();
+  const ScatterExtents X = scatter_extents(O->npix, O->nexp, O->nseg, ntiles, kScatBlock);
+  try { flags.assign((size_t)O->npix, 0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
+  if ((rc = ensure(h, h->d_sc_w, X.w_bytes)) || (rc = ensure(h, h->d_sc_var, X.var_bytes)) || (rc = ensure(h, h->d_sc_med, X.med_bytes)) ||
+      (rc = ensure(h, h->d_sc_flag, X.flag_bytes)) || (rc = upload(h, h->d_sc_tiles, tiles)))
+    return rc;
+  const DevBuf &W = O->raw_weight();
+  ScatterArgs A{};
+  A.r = O->d_data.as<double>(); A.weight = W.as<double>(); A.tiles = h->d_sc_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
+  A.var = h->d_sc_var.as<double>(); A.med = h->d_sc_med.as<double>(); A.out = h->d_sc_w.as<double>(); A.flag = h->d_sc_flag.as<int32_t>();
+  A.npix = O->npix; A.ntiles = ntiles; A.nexp = O->nexp; A.kind = sc->kind; A.min_live = sc->min_live; A.clip = sc->clip;
+  // (every address the kernels read or write: the data and the weights [nexp][npix], the tiles -- which cover [0, npix) and
+  // name segments below nseg --, the bounds [nseg + 1], var and the flags [npix], med [nseg], w' [nexp][npix])
+  if (!A.r || !A.tiles || !A.seg_first || !A.var || !A.med || !A.out || !A.flag || A.npix < 1 || A.nexp < 2 || O->nseg < 1 || !X.grid_ok ||
+      O->d_data.bytes < X.w_bytes || (A.weight && W.bytes < X.w_bytes) || h->d_sc_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
+      O->d_seg.bytes < sizeof(int64_t) * ((size_t)O->nseg + 1) || h->d_sc_var.bytes < X.var_bytes || h->d_sc_med.bytes < X.med_bytes ||
+      h->d_sc_w.bytes < X.w_bytes || h->d_sc_flag.bytes < X.flag_bytes)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the scatter kernels (not launched)");
+  // (an empty segment has no tile, a segment without a live column no lane that stores: their medians stay +0)
+  HIPCHK(h, hipMemsetAsync(A.med, 0, X.med_bytes, h->stream));
+  hipLaunchKernelGGL(k_scatter_cols, dim3((unsigned)X.col_blocks), dim3(kScatBlock), 0, h->stream, A);
+  hipLaunchKernelGGL(k_scatter_median, dim3((unsigned)X.tile_blocks), dim3(kScatBlock), 0, h->stream, A);
+  hipLaunchKernelGGL(k_scatter_weights, dim3((unsigned)X.tile_blocks), dim3(kScatBlock), 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(flags.data(), h->d_sc_flag.p, X.flag_bytes, hipMemcpyDeviceToHost, h->stream));
+  // the installed weighted filter's factor against w', in the handle's own buffers (factor_wfilter waits for the queue: every
+  // kernel has finished, the staging vectors may go)
+  if (F) { if ((rc = factor_wfilter(h, *F, O, A.out, h->d_sc_w.bytes, h->d_sc_fac, h->d_sc_live, &nsing))) return rc; }
+  else HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (variance) HIPCHK(h, hipMemcpy(variance, h->d_sc_var.p, X.var_bytes, hipMemcpyDeviceToHost));
+  if (median) HIPCHK(h, hipMemcpy(median, h->d_sc_med.p, X.med_bytes, hipMemcpyDeviceToHost));
+  if (weight) HIPCHK(h, hipMemcpy(weight, h->d_sc_w.p, X.w_bytes, hipMemcpyDeviceToHost));
+  // the swap: W aside on the first call (empty where the set had no weights), w' in force, the new factor in the filter
+  if (!O->weighed) { move_buf(O->d_wraw, O->d_weight); move_buf(O->d_weight, h->d_sc_w); O->weighed = true; }
+  else swap_buf(O->d_weight, h->d_sc_w);
+  if (F) { swap_buf(F->d_fac, h->d_sc_fac); swap_buf(F->d_live, h->d_sc_live); }
+  int64_t nm = 0;
+  for (int32_t x : flags) nm += x == kScatClipped ? 1 : 0;
+  if (nmasked) *nmasked = nm;
   if (nsingular) *nsingular = nsing;
   return TRX_OK;
 }

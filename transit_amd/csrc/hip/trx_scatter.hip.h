@@ -1,0 +1,158 @@
+// trx_scatter.hip.h -- weighing the observed set by the scatter of its pixel columns on the device (trx_weigh_observed,
+// include/transit_hip.h): every column's variance in time, every segment's median variance, and the new weights -- the
+// inverse variance of the columns kept, or a mask of them.  The arithmetic is ../trx_scatter.h's, the same source a CPU
+// program runs.
+//
+//   k_scatter_cols     one lane per pixel column, kScatBlock columns per block, a wave's loads coalesced.  Two passes over
+//                    the exposures, v ascending, the loads of the weight and the datum of kSysTrips exposures issued
+//                    before the first add (a trip past the last exposure reads the last one again and adds nothing): the
+//                    count and the sum, then the squares about the mean.  Writes var[p]: > 0 for a live column, +0 for a
+//                    dead one.
+//   k_scatter_median   one block per tile of scatter_tiles (<= kScatBlock columns of one segment), a wave owning 64 of the
+//                    tile's columns as candidates.  The block stages the segment's variances through LDS, kScatLds at a
+//                    time (padded to a multiple of kScatTrip), a dead column's +0 as +infinity -- every lane of the block takes every trip of that loop, the
+//                    two barriers in it are block-uniform --, and every lane counts the staged values ahead of its own
+//                    candidate (all lanes read the same LDS word: a broadcast).  The live columns are counted as they are
+//                    staged: a ballot per wave, the waves' totals added through LDS -- integers, exact in any order.  The
+//                    one live lane of the segment whose rank is (m - 1) / 2 stores med[s]; med is zeroed before the launch,
+//                    which is the answer of an empty segment (no tile) and of one without a live column (no lane stores).
+//   k_scatter_weights  one block per tile, one lane per column: the keep rule and 1 / var once, then the column's new
+//                    weights for every exposure (kSysTrips loads of W in flight) and the column's flag.
+//
+// No atomics, no scratch; LDS in k_scatter_median alone (kScatLds doubles and a count per wave).  The bits of a segment's result depend on that
+// segment's data and weights and on the call's parameters -- not on other segments, the launch or the handle.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "transit_hip.h"
+#include "trx_device.h"
+#include "trx_sysrem.hip.h"
+#include "../trx_scatter.h"
+
+namespace trx {
+
+struct ScatterArgs {
+  const double *r;          // [nexp][npix] the data installed
+  const double *weight;     // W [nexp][npix] as trx_set_observed installed it, or null: all 1
+  const FilterTile *tiles;  // [ntiles], scatter_tiles'
+  const int64_t *seg_first; // [nseg + 1]
+  double *var;              // [npix]
+  double *med;              // [nseg]
+  double *out;              // w' [nexp][npix]
+  int32_t *flag;            // [npix]: kScatDead, kScatKept, kScatClipped
+  int64_t npix, ntiles;
+  int32_t nexp, kind, min_live;
+  double clip;
+};
+
+// one column's variance; HASW: the set has weights (without: every W is 1, nothing is loaded for it).  A template, not a test
+// per load: the loads of a trip must all be issued before the first is waited for
+template <bool HASW>
+__device__ __forceinline__ double scatter_column(const ScatterArgs &A, int64_t p)
+{
+#pragma clang fp contract(off)
+  const int nexp = A.nexp;
+  int32_t n = 0; double s = 0.0;
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    double w[kSysTrips], r[kSysTrips];
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++) {
+      const int64_t at = (int64_t)min(v0 + t, nexp - 1) * A.npix + p;
+      r[t] = A.r[at];
+      w[t] = HASW ? A.weight[at] : 1.0;
+    }
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) scatter_sum_term(w[t], r[t], n, s);
+  }
+  double q = 0.0;
+  if (scatter_enough(n, A.min_live)) {
+    const double mean = scatter_mean(s, n);
+    for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+      double w[kSysTrips], r[kSysTrips];
+#pragma unroll
+      for (int t = 0; t < kSysTrips; t++) {
+        const int64_t at = (int64_t)min(v0 + t, nexp - 1) * A.npix + p;
+        r[t] = A.r[at];
+        w[t] = HASW ? A.weight[at] : 1.0;
+      }
+#pragma unroll
+      for (int t = 0; t < kSysTrips; t++)
+        if (v0 + t < nexp) scatter_square_term(w[t], r[t], mean, q);
+    }
+  }
+  return scatter_variance(q, n, A.min_live);
+}
+
+__global__ __launch_bounds__(kScatBlock) void k_scatter_cols(ScatterArgs A)
+{
+  const int64_t p = (int64_t)blockIdx.x * kScatBlock + threadIdx.x;
+  if (p >= A.npix) return;
+  A.var[p] = A.weight ? scatter_column<true>(A, p) : scatter_column<false>(A, p);
+}
+
+static_assert(kScatLds % kScatTrip == 0 && kScatBlock % 64 == 0, "a padded trip fits the staging array; whole waves");
+
+__global__ __launch_bounds__(kScatBlock) void k_scatter_median(ScatterArgs A)
+{
+  __shared__ double staged[kScatLds];
+  __shared__ long long live_of_wave[kScatBlock / 64];
+  const int lane = (int)threadIdx.x;
+  const FilterTile T = A.tiles[blockIdx.x];            // (the grid is the tile table: ntiles blocks)
+  const int64_t first = A.seg_first[T.seg], last = A.seg_first[T.seg + 1];
+  const bool mine = lane < T.count;
+  const int64_t p = T.first + (mine ? lane : 0);       // (a lane past the tile's end counts for the tile's first column and stores nothing)
+  const double varp = A.var[p];
+  long long live = 0, rank = 0;                        // live: the live columns this lane's WAVE has staged (wave-uniform)
+  for (int64_t q0 = first; q0 < last; q0 += kScatLds) {
+    const int nq = last - q0 < kScatLds ? (int)(last - q0) : kScatLds;
+    const int pj = scatter_place(p, q0);
+    __syncthreads();                                   // (the trip before has been read by every lane)
+    const int npad = scatter_padded(nq);               // (<= kScatLds: kScatTrip divides it)
+    for (int j0 = 0; j0 < npad; j0 += kScatBlock) {    // (block-uniform: every lane takes every trip, the ballot has whole waves)
+      const int j = j0 + lane;
+      const double x = j < nq ? A.var[q0 + j] : 0.0;   // (the padding is staged as a dead column: ahead of nothing)
+      if (j < npad) staged[j] = scatter_staged(x);
+      live += __popcll(__ballot(x > 0.0));
+    }
+    __syncthreads();
+    int ahead = 0;
+    for (int j0 = 0; j0 < npad; j0 += kScatTrip) {
+      double x[kScatTrip];
+#pragma unroll
+      for (int t = 0; t < kScatTrip; t++) x[t] = staged[j0 + t];
+#pragma unroll
+      for (int t = 0; t < kScatTrip; t++) scatter_rank_term(x[t], j0 + t, varp, pj, ahead);
+    }
+    rank += ahead;
+  }
+  if ((lane & 63) == 0) live_of_wave[lane >> 6] = live;
+  __syncthreads();
+  long long m = 0;
+  for (int k = 0; k < kScatBlock / 64; k++) m += live_of_wave[k];
+  if (mine && scatter_is_median(varp, m, rank)) A.med[T.seg] = varp;
+}
+
+__global__ __launch_bounds__(kScatBlock) void k_scatter_weights(ScatterArgs A)
+{
+#pragma clang fp contract(off)
+  const int lane = (int)threadIdx.x;
+  const FilterTile T = A.tiles[blockIdx.x];
+  if (lane >= T.count) return;
+  const int64_t p = T.first + lane;
+  const int nexp = A.nexp;
+  const double var = A.var[p];
+  const bool keep = scatter_keep(var, A.med[T.seg], A.clip);
+  const double inv = scatter_inverse(var, keep);
+  A.flag[p] = scatter_flag(var, keep);
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    double w[kSysTrips];
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++) w[t] = A.weight ? A.weight[(int64_t)min(v0 + t, nexp - 1) * A.npix + p] : 1.0;
+#pragma unroll
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) A.out[(int64_t)(v0 + t) * A.npix + p] = scatter_weight(A.kind, w[t], keep, inv);
+  }
+}
+
+}  // namespace trx

@@ -214,6 +214,7 @@ def hip_library():
         _abi.bind_exposures_api(lib)
         _abi.bind_expmap_api(lib)
         _abi.bind_sysrem_api(lib)
+        _abi.bind_scatter_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -244,6 +245,16 @@ class Detrended:
 
     def __init__(self, basis, coef, data, nsingular, spectrum=None):
         self.basis, self.coef, self.data, self.nsingular, self.spectrum = basis, coef, data, nsingular, spectrum
+
+
+class Weighed:
+    """What Engine.weigh_observed returns: variance [npix] every column's variance in time (+0: a dead column), median [nseg]
+    every segment's median variance, weight [nexp, npix] the weights now in force (all three None after the undo or with
+    outputs=False), nmasked the live columns the clip removed, nsingular the columns the installed weighted filter's pivot
+    rule makes dead under the new weights (0 without a weighted filter)."""
+
+    def __init__(self, variance, median, weight, nmasked, nsingular):
+        self.variance, self.median, self.weight, self.nmasked, self.nsingular = variance, median, weight, nmasked, nsingular
 
 
 class Engine(CEngine):
@@ -512,6 +523,28 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_detrend_observed", self._last_error())
         return Detrended(basis if n else None, coef if n else None, data if n else None, int(nsing.value), spec)
+
+    def weigh_observed(self, kind: int, clip: float = 0.0, min_live: int = 2, outputs: bool = True) -> "Weighed":
+        """trx_weigh_observed: the column-scatter weights of the observed set, on the device, from the data installed (the
+        residuals of detrend_observed, or the raw set) and ALWAYS from the weights as set_observed installed them
+        (xcor.scatter_reference, bit for bit).  kind: _abi.SCATTER_VARIANCE (w' = 1 / var_p on the kept columns' live
+        entries), SCATTER_MASK (w' = W on the kept columns) or SCATTER_NONE, the undo: set_observed's weights back in force.
+        clip: 0 (none) or >= 1: a live column is kept if var_p <= clip^2 times its segment's median variance; min_live: the
+        entries a live column needs.  The new weights become the observed set's, and an installed weighted filter is
+        factorised again against them; run_filtered_moments, run_filtered_map and run_exposed_map then run under them.
+        Returns a Weighed: variance [npix], median [nseg], weight [nexp, npix], nmasked, nsingular.  outputs=False leaves the
+        three arrays on the device (None in the result)."""
+        nexp, nseg = getattr(self, "mom_shape", (0, 0))
+        npix = getattr(self, "npix", 0)
+        sc = _abi.TrxScatter(int(kind), int(min_live), float(clip))
+        give = bool(outputs) and int(kind) != _abi.SCATTER_NONE
+        var, med, w = np.zeros(npix), np.zeros(nseg), np.zeros((nexp, npix))
+        nm, nsing = C.c_int64(0), C.c_int64(0)
+        rc = self._lib.trx_weigh_observed(self._h, C.byref(sc), _dp(var) if give else None, _dp(med) if give else None,
+                                          _dp(w) if give else None, C.byref(nm), C.byref(nsing))
+        if rc != 0:
+            raise EngineError(rc, "trx_weigh_observed", self._last_error())
+        return Weighed(var if give else None, med if give else None, w if give else None, int(nm.value), int(nsing.value))
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device

@@ -830,6 +830,59 @@ def sysrem_reference(data, weight, seg_first, ncomp: int, niter: int = 10):
     return basis, coef, resid
 
 
+SCATTER_NONE, SCATTER_VARIANCE, SCATTER_MASK = 0, 1, 2    # TRX_SCATTER_*: the kinds of trx_weigh_observed
+
+
+def scatter_reference(data, weight, seg_first, kind: int, clip: float = 0.0, min_live: int = 2):
+    """(var [npix], med [nseg], keep [npix] bool, w' [nexp, npix]): the column-scatter weights as trx_weigh_observed
+    defines them (include/transit_hip.h), in numpy double in exactly its order -- the mirror of k_scatter_cols,
+    k_scatter_median and k_scatter_weights, bit for bit.  data: the data installed (the residuals of a detrend, or the raw
+    set); weight: the weights as set_observed installed them, None = all 1.  Per column over the entries with W > 0, v
+    ascending: n, s = sum r, mean = s / n, q = sum (r - mean)^2, var = q / (n - 1) where n >= min_live and var is positive
+    and finite, else +0 (dead).  med: the lower median of a segment's live var (rank (m - 1) // 2, ascending var, ties by
+    ascending pixel; +0 without a live column).  keep: live and (clip == 0 or var <= (clip * clip) * med).  w': kind
+    SCATTER_VARIANCE: 1 / var where W > 0 and kept; SCATTER_MASK: W where kept; +0 elsewhere.  The live columns the clip
+    removed (nmasked) are (var > 0) & ~keep."""
+    r = np.asarray(data, dtype=np.float64)
+    if r.ndim != 2:
+        raise ValueError("scatter_reference: data of shape [nexp][npix]")
+    if kind not in (SCATTER_VARIANCE, SCATTER_MASK):
+        raise ValueError("scatter_reference: kind SCATTER_VARIANCE or SCATTER_MASK")
+    W = np.ones_like(r) if weight is None else np.asarray(weight, dtype=np.float64)
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    nexp, npix, nseg = r.shape[0], r.shape[1], seg.size - 1
+    on = W > 0
+    with np.errstate(all="ignore"):
+        n, s = np.zeros(npix, dtype=np.int64), np.zeros(npix)
+        for v in range(nexp):
+            n = n + on[v]
+            s = np.where(on[v], s + r[v], s)
+        enough = n >= min_live
+        mean = s / np.where(enough, n, 1).astype(np.float64)
+        q = np.zeros(npix)
+        for v in range(nexp):
+            d = r[v] - mean
+            q = np.where(on[v], q + d * d, q)
+        var = q / np.where(enough, n - 1, 1).astype(np.float64)
+        var = np.where(enough & (var > 0) & np.isfinite(var), var, 0.0)
+        live = var > 0
+        med = np.zeros(nseg)
+        for k in range(nseg):
+            a, b = int(seg[k]), int(seg[k + 1])
+            x = var[a:b][live[a:b]]                                  # (in ascending pixel order)
+            if x.size:
+                med[k] = x[np.argsort(x, kind="stable")[(x.size - 1) // 2]]
+        lim = np.float64(clip) * np.float64(clip)
+        lim = lim * np.repeat(med, np.diff(seg))
+        keep = live & ((clip == 0) | (var <= lim))
+        inv = 1.0 / np.where(keep, var, 1.0)
+    if kind == SCATTER_VARIANCE:
+        out = np.where(on & keep[None, :], inv[None, :], 0.0)
+    else:
+        out = np.where(keep[None, :], W, 0.0)
+    return var, med, keep, out
+
+
 def _check_wfilter(obs: Observed, wf: WeightedFilter):
     if (wf.nseg, wf.nexp) != (obs.nseg, obs.nexp):
         raise ValueError("weighted filter of the observed set's nseg and nexp")
