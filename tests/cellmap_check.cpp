@@ -9,43 +9,13 @@
 //   cellmap_check nearest FILE    FILE: "nlag n", then the doubles (C99 hex, nan, inf) of lag_kms [nlag] and x [n]; prints
 //                                 vmap_nearest of every x, one per line
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <initializer_list>
-#include <limits>
-#include <memory>
-#include <string>
 
 #include "trx_products.h"
 #include "trx_vmap.h"
+#include "check_common.h"
 
 using namespace trx;
-
-static int g_checks = 0, g_bad = 0;
-#define CHECK(cond) do { g_checks++; if (!(cond)) { g_bad++; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
-
-// an exact-size heap array
-template <class T>
-struct Heap {
-  std::unique_ptr<T[]> p; size_t n;
-  explicit Heap(size_t n_, T fill = T()) : p(new T[n_]), n(n_) { for (size_t i = 0; i < n; i++) p[i] = fill; }
-  Heap(std::initializer_list<T> v) : p(new T[v.size()]), n(v.size()) { size_t i = 0; for (const T &x : v) p[i++] = x; }
-  T *get() const { return p.get(); }
-  T &operator[](size_t i) const { return p[i]; }
-};
-
-static void refused(int rc, const std::string &msg, int want_rc, const char *want, int line)
-{
-  g_checks++;
-  if (rc == want_rc && msg == want) return;
-  g_bad++;
-  std::printf("FAILED line %d: got (%d, \"%s\"), want (%d, \"%s\")\n", line, rc, msg.c_str(), want_rc, want);
-}
-#define REFUSED(call, want_rc, want) do { std::string msg; const int rc_ = (call); refused(rc_, msg, want_rc, want, __LINE__); } while (0)
-#define ACCEPTED(call) do { std::string msg = "untouched"; const int rc_ = (call); refused(rc_, msg, TRX_OK, "untouched", __LINE__); } while (0)
-
-static const double kNaN = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
 
 // ---- the refusal table: a map run's refusals under this call's name, then its own two ---------------
 static void refusals()
@@ -200,17 +170,6 @@ static void extents()
   CHECK(X.chunk == 2 && X.rows == 2LL * 32768 * 32767 && X.rows <= 0x7fffffffLL);
   X = cell_map_extents(1000, 46340, 46340, 1);
   CHECK(X.chunk == 1 && X.nchunks == 1000);
-}
-
-static std::unique_ptr<double[]> read_doubles(FILE *f, size_t n)
-{
-  std::unique_ptr<double[]> a(new double[n]);          // exact size: the sanitizer guards both ends
-  char word[64];
-  for (size_t k = 0; k < n; k++) {
-    if (std::fscanf(f, "%63s", word) != 1) { std::fprintf(stderr, "cellmap_check: the file ends early\n"); std::exit(2); }
-    a[k] = std::strtod(word, nullptr);
-  }
-  return a;
 }
 
 int main(int argc, char **argv)

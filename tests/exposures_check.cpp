@@ -7,45 +7,17 @@
 //                                <centre> <sigma> <d> <first> <last>" for its edge cases (doubles as %a) and "ok <checks>"
 //   exposures_check range FILE   FILE: lines "wn_i wn_d nwn cut centre_obs fwhm_obs shift eta"; prints the same lines for them
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
 
 #include "transit_hip.h"
 #include "trx_exposures.h"
+#include "check_common.h"
 
 using namespace trx;
 
 static_assert(sizeof(trx_exposures) == 24, "trx_exposures is 24 bytes");
 static_assert(TRX_OK == 0 && TRX_E_ARG == -1, "the codes the tests of the interface pin");
 
-static int g_checks = 0, g_bad = 0;
-#define CHECK(cond) do { g_checks++; if (!(cond)) { g_bad++; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
-
-// an exact-size heap array
-template <class T>
-struct Heap {
-  std::unique_ptr<T[]> p; size_t n;
-  explicit Heap(size_t n_, T fill = T()) : p(new T[n_]), n(n_) { for (size_t i = 0; i < n; i++) p[i] = fill; }
-  Heap(std::initializer_list<T> v) : p(new T[v.size()]), n(v.size()) { size_t i = 0; for (const T &x : v) p[i++] = x; }
-  T *get() const { return p.get(); }
-  T &operator[](size_t i) const { return p[i]; }
-};
-
-static void refused(int rc, const std::string &msg, int want_rc, const char *want, int line)
-{
-  g_checks++;
-  if (rc == want_rc && msg == want) return;
-  g_bad++;
-  std::printf("FAILED line %d: got (%d, \"%s\"), want (%d, \"%s\")\n", line, rc, msg.c_str(), want_rc, want);
-}
-#define REFUSED(call, want_rc, want) do { std::string msg; const int rc_ = (call); refused(rc_, msg, want_rc, want, __LINE__); } while (0)
-#define ACCEPTED(call) do { std::string msg = "untouched"; const int rc_ = (call); refused(rc_, msg, TRX_OK, "untouched", __LINE__); } while (0)
-
-static const double kNaN = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
 static const double kFwhmSigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
 
 // a whole-grid handle of 5000 bins with a pixel set of 6 pixels and an observed set of 3 exposures by 2 segments

@@ -1,5 +1,6 @@
 // products_check.cpp -- the host side of the run products (transit_amd/csrc/trx_products.h) without a device: the refusal
-// table against literal texts, the band and filter layouts' invariants, the extents of hand-worked shapes.  Stand-alone
+// table against literal texts, the band and filter layouts' invariants, the extents of hand-worked shapes -- and the launch
+// conditions of trx_launch.h over plain structs, its buffer transitions over a counting fake.  Stand-alone
 // (tests/test_products_host.py builds it under -fsanitize=address,undefined); every array handed to the header is a heap
 // allocation of exactly the stated length, so a read past an extent is a sanitizer report.
 //
@@ -7,45 +8,17 @@
 //                               its GAUSS bands (doubles as %a) and "ok <checks>" at the end
 //   products_check gauss FILE   FILE: lines "wn_i wn_d nwn centre fwhm cut"; prints the same lines for them
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
 #include <vector>
 
 #include "transit_hip.h"
 #include "trx_products.h"
+#include "trx_launch.h"
+#include "check_common.h"
 
 using namespace trx;
 
 static_assert(TRX_OK == 0 && TRX_E_ARG == -1 && TRX_E_UNSUPPORTED == -6, "the codes the tests of the interface pin");
-
-static int g_checks = 0, g_bad = 0;
-#define CHECK(cond) do { g_checks++; if (!(cond)) { g_bad++; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
-
-// an exact-size heap array (n = 0: a zero-length allocation, not to be read at all)
-template <class T>
-struct Heap {
-  std::unique_ptr<T[]> p; size_t n;
-  explicit Heap(size_t n_, T fill = T()) : p(new T[n_]), n(n_) { for (size_t i = 0; i < n; i++) p[i] = fill; }
-  Heap(std::initializer_list<T> v) : p(new T[v.size()]), n(v.size()) { size_t i = 0; for (const T &x : v) p[i++] = x; }
-  T *get() const { return p.get(); }
-  T &operator[](size_t i) const { return p[i]; }
-};
-
-static void refused(int rc, const std::string &msg, int want_rc, const char *want, int line)
-{
-  g_checks++;
-  if (rc == want_rc && msg == want) return;
-  g_bad++;
-  std::printf("FAILED line %d: got (%d, \"%s\"), want (%d, \"%s\")\n", line, rc, msg.c_str(), want_rc, want);
-}
-#define REFUSED(call, want_rc, want) do { std::string msg; const int rc_ = (call); refused(rc_, msg, want_rc, want, __LINE__); } while (0)
-#define ACCEPTED(call) do { std::string msg = "untouched"; const int rc_ = (call); refused(rc_, msg, TRX_OK, "untouched", __LINE__); } while (0)
-
-static const double kNaN = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
 
 // a whole-grid handle of 5000 bins with a pixel set of 6 pixels, an observed set of 3 exposures by 2 segments and a filter
 struct Installed {
@@ -611,6 +584,223 @@ static void extents()
   CHECK(broadened_bytes(5000) == 40000 && broadened_bytes(1) == 8);
 }
 
+// ---- the launch conditions (transit_amd/csrc/trx_launch.h) -------------------------------------------
+// the sets as plain structs: a buffer is a pointer that is never followed and a byte count
+struct PlainBuf { void *p = nullptr; size_t bytes = 0; void release() { p = nullptr; bytes = 0; } };
+struct PlainObs {
+  int32_t nexp = 0, nseg = 0; int64_t npix = 0; std::vector<int64_t> seg;
+  PlainBuf d_seg, d_gain; InForce<PlainBuf> d_data, d_weight;
+};
+struct PlainFilt {
+  int32_t ncomp = 0, npad = 0, nexp = 0, nseg = 0; int64_t npix = 0, ntiles = 0; bool weighted = false; int32_t nfac = 0;
+  PlainBuf d_fwd, d_back, d_tiles, d_fac, d_live;
+};
+static char g_there;                                     // what a non-null pointer points at
+static PlainBuf of(size_t bytes) { return PlainBuf{&g_there, bytes}; }
+
+// the smallest shapes with every branch: 2 exposures, 2 segments -- the first empty --, 3 pixels; a filter of 3 components
+// padded to 4 with the one tile of the second segment
+static PlainObs whole_obs(bool weights, bool gain)
+{
+  PlainObs O; O.nexp = 2; O.nseg = 2; O.npix = 3; O.seg = {0, 0, 3};
+  O.d_seg = of(24); O.d_data.now = of(48);
+  if (weights) O.d_weight.now = of(48);
+  if (gain) O.d_gain = of(24);
+  return O;
+}
+static PlainFilt whole_filt(bool weighted)
+{
+  PlainFilt F; F.ncomp = 3; F.npad = 4; F.nexp = 2; F.nseg = 2; F.npix = 3; F.ntiles = 1; F.weighted = weighted;
+  F.d_back = of(128); F.d_tiles = of(sizeof(FilterTile));
+  if (weighted) { F.nfac = 6; F.d_fac = of(144); F.d_live = of(12); } else F.d_fwd = of(128);
+  return F;
+}
+
+static void grid_conditions()
+{
+  int64_t blocks = -1;
+  CHECK(!blocks_for(0, 4, &blocks) && blocks == 0);
+  CHECK(blocks_for(1, 4, &blocks) && blocks == 1);
+  CHECK(blocks_for(5, 4, &blocks) && blocks == 2);
+  CHECK(blocks_for(0x7fffffffLL * 4, 4, &blocks) && blocks == 0x7fffffffLL);
+  CHECK(!blocks_for(0x7fffffffLL * 4 + 1, 4, &blocks) && blocks == 0x80000000LL);
+  CHECK(!grid_ok(0) && grid_ok(1) && grid_ok(0x7fffffffLL) && !grid_ok(0x80000000LL) && !grid_ok(-1));
+  for (int32_t npad = -1; npad <= 33; npad++) CHECK(npad_ok(npad) == (npad == 4 || npad == 8 || npad == 16));
+}
+
+static void observed_set_conditions()
+{
+  for (const bool weights : {false, true})
+    for (const bool gain : {false, true}) {
+      const PlainObs O = whole_obs(weights, gain);
+      CHECK(observed_set_whole(O, O.d_weight.now, true) && observed_set_whole(O, O.d_weight.now, false));
+      // one defect each: refused whether or not the data are read, unless the defect is the data's
+      auto refused_with = [&](void (*spoil)(PlainObs &), bool data_only = false) {
+        PlainObs B = whole_obs(weights, gain); spoil(B);
+        CHECK(!observed_set_whole(B, B.d_weight.now, true) && observed_set_whole(B, B.d_weight.now, false) == data_only);
+      };
+      refused_with([](PlainObs &B) { B.d_seg.p = nullptr; });
+      refused_with([](PlainObs &B) { B.d_seg.bytes--; });
+      refused_with([](PlainObs &B) { B.d_data.now.p = nullptr; }, true);
+      refused_with([](PlainObs &B) { B.d_data.now.bytes--; }, true);
+      refused_with([](PlainObs &B) { B.nexp++; }, !weights);           // (the data, and the weights where there are any, are one exposure short)
+      refused_with([](PlainObs &B) { B.nexp = 0; });
+      refused_with([](PlainObs &B) { B.nseg++; });
+      refused_with([](PlainObs &B) { B.nseg--; });
+      refused_with([](PlainObs &B) { B.npix++; });
+      refused_with([](PlainObs &B) { B.npix--; });
+      refused_with([](PlainObs &B) { B.seg.front() = 1; });
+      refused_with([](PlainObs &B) { B.seg.back() = 2; });
+      if (weights) refused_with([](PlainObs &B) { B.d_weight.now.bytes--; });
+      if (gain) refused_with([](PlainObs &B) { B.d_gain.bytes--; });
+      // the weights a caller names are the ones held against the extent: the raw ones of a weighed set
+      PlainObs W = whole_obs(weights, gain);
+      PlainBuf fresh = of(47);
+      W.d_weight.adopt(fresh);
+      CHECK(!observed_set_whole(W, W.d_weight.now, true) && observed_set_whole(W, W.d_weight.raw(), true));
+    }
+}
+
+static void filter_set_conditions()
+{
+  for (const bool weighted : {false, true}) {
+    auto whole = [&](const PlainFilt &F, const PlainObs &O) { return weighted ? wfilter_set_complete(F, O) : filter_set_whole(F, O); };
+    const PlainObs O = whole_obs(true, true);
+    CHECK(whole(whole_filt(weighted), O) && whole(whole_filt(weighted), whole_obs(false, false)));
+    CHECK(!(weighted ? filter_set_whole(whole_filt(true), O) : wfilter_set_complete(whole_filt(false), O)));      // (the other kind's predicate)
+    auto refused_with = [&](void (*spoil)(PlainFilt &)) { PlainFilt B = whole_filt(weighted); spoil(B); CHECK(!whole(B, O)); };
+    refused_with([](PlainFilt &B) { B.d_back.p = nullptr; });
+    refused_with([](PlainFilt &B) { B.d_back.bytes--; });
+    refused_with([](PlainFilt &B) { B.d_tiles.p = nullptr; });
+    refused_with([](PlainFilt &B) { B.d_tiles.bytes--; });
+    refused_with([](PlainFilt &B) { B.weighted = !B.weighted; });
+    refused_with([](PlainFilt &B) { B.nexp++; });
+    refused_with([](PlainFilt &B) { B.nexp--; });
+    refused_with([](PlainFilt &B) { B.nseg++; });
+    refused_with([](PlainFilt &B) { B.nseg--; });
+    refused_with([](PlainFilt &B) { B.npix++; });
+    refused_with([](PlainFilt &B) { B.npix--; });
+    refused_with([](PlainFilt &B) { B.ncomp = 0; });
+    refused_with([](PlainFilt &B) { B.ncomp = 5; B.nfac = 15; B.d_fac.bytes = 1 << 20; });      // ncomp > npad
+    refused_with([](PlainFilt &B) { B.ntiles = 0; });
+    // a padded count no kernel is made for, behind buffers that would hold it
+    for (const int32_t npad : {0, 3, 5, 12, 32}) {
+      PlainFilt B = whole_filt(weighted); B.npad = npad; B.d_fwd.bytes = B.d_back.bytes = 1 << 20;
+      if (npad < B.ncomp) { B.ncomp = 1; B.nfac = 1; }
+      CHECK(!whole(B, O));
+      B.npad = 16; CHECK(whole(B, O));                                       // (the count alone refused it)
+    }
+    if (weighted) {
+      refused_with([](PlainFilt &B) { B.d_fac.p = nullptr; });
+      refused_with([](PlainFilt &B) { B.d_fac.bytes--; });
+      refused_with([](PlainFilt &B) { B.d_live.p = nullptr; });
+      refused_with([](PlainFilt &B) { B.d_live.bytes--; });
+      refused_with([](PlainFilt &B) { B.nfac++; });
+      PlainObs S = whole_obs(true, true); S.d_weight.now.bytes--;
+      CHECK(!wfilter_set_complete(whole_filt(true), S));                      // the weights in force, one byte short
+      // what the factor kernel reads is whole without a factor, and with other weights in force
+      PlainFilt B = whole_filt(true); B.d_fac = B.d_live = PlainBuf{};
+      const WfilterExtents WX = wfilter_extents(B.npix, B.nexp, B.nseg, B.ncomp, B.npad, B.ntiles, 4);
+      CHECK(wfilter_basis_whole(B, S, WX) && !wfilter_set_complete(B, O));
+      CHECK(WX.nfac == 6 && WX.basis_bytes == 128 && WX.fac_bytes == 144 && WX.live_bytes == 12 && WX.blocks == 1);
+    } else {
+      refused_with([](PlainFilt &B) { B.d_fwd.p = nullptr; });
+      refused_with([](PlainFilt &B) { B.d_fwd.bytes--; });
+    }
+  }
+}
+
+static void pair_source_conditions()
+{
+  const PixelExtents X = pixel_extents(3, 2, 0, 0, false, false);
+  const HighpassExtents HX = highpass_extents(3, 2, 1, 1);
+  static char out_there, hp_there, gain_there;
+  const PlainBuf out{&out_there, X.pair_bytes}, hp{&hp_there, HX.pair_bytes}, gain{&gain_there, 24}, none{};
+  CHECK(X.pair_bytes == 96 && HX.pair_bytes == 96 && HX.pairs == X.pairs);
+  // without a high-pass: the pixel kernel's pairs and the gains that apply
+  PairSource P = pair_source(X, (const HighpassExtents *)nullptr, out, none, &gain, 3);
+  CHECK(P.pairs == &out_there && P.gain == &gain_there && P.whole);
+  P = pair_source(X, (const HighpassExtents *)nullptr, out, none, (const PlainBuf *)nullptr, 3);
+  CHECK(P.pairs == &out_there && !P.gain && P.whole);
+  P = pair_source(X, (const HighpassExtents *)nullptr, out, none, &none, 3);      // (a set without gains)
+  CHECK(P.pairs == &out_there && !P.gain && P.whole);
+  // with one: its pairs and no gain -- the high-pass applied it
+  P = pair_source(X, &HX, out, hp, &gain, 3);
+  CHECK(P.pairs == &hp_there && !P.gain && P.whole);
+  // one defect each
+  auto whole_with = [&](const HighpassExtents *hx, PlainBuf o, PlainBuf h, PlainBuf g, int64_t npix = 3) { return pair_source(X, hx, o, h, &g, npix).whole; };
+  auto shorter = [](PlainBuf b) { b.bytes--; return b; };
+  auto null_of = [](PlainBuf b) { b.p = nullptr; return b; };
+  CHECK(!whole_with(nullptr, null_of(out), hp, gain) && !whole_with(nullptr, shorter(out), hp, gain) && !whole_with(nullptr, out, hp, shorter(gain)));
+  CHECK(whole_with(nullptr, out, null_of(hp), gain) && whole_with(nullptr, out, shorter(hp), gain));      // (not read without a high-pass)
+  CHECK(!whole_with(&HX, out, null_of(hp), gain) && !whole_with(&HX, out, shorter(hp), gain) && !whole_with(&HX, shorter(out), hp, gain));
+  CHECK(whole_with(&HX, out, hp, shorter(gain)));                                                         // (not read behind a high-pass)
+  HighpassExtents other = HX; other.pairs++;
+  CHECK(!whole_with(&other, out, hp, gain));
+  CHECK(!whole_with(nullptr, out, hp, gain, 0) && !whole_with(nullptr, out, hp, gain, 4));                // (the gains are npix long)
+}
+
+// a buffer that owns a heap block and counts: a leak or a double release is a count that is off, and a sanitizer report
+struct CountedBuf {
+  void *p = nullptr; size_t bytes = 0;
+  static int live, released;
+  CountedBuf() = default;
+  explicit CountedBuf(size_t n) : p(std::malloc(n)), bytes(n) { live++; }
+  CountedBuf(const CountedBuf &) = delete;
+  CountedBuf &operator=(const CountedBuf &) = delete;
+  ~CountedBuf() { release(); }
+  void release() { if (p) { std::free(p); p = nullptr; bytes = 0; live--; released++; } }
+};
+int CountedBuf::live = 0, CountedBuf::released = 0;
+
+static void in_force_transitions()
+{
+  auto empty = [](const CountedBuf &b) { return !b.p && b.bytes == 0; };
+  {  // adopt, adopt, restore: the raw version aside, then the two calls' buffers swap, then the raw one back
+    InForce<CountedBuf> S; CountedBuf raw(8), one(16), two(24), spare;
+    const void *const A = raw.p, *const B = one.p, *const C = two.p;
+    exchange_buf(S.now, raw);
+    CHECK(S.raw().p == A && !S.adopted);
+    S.adopt(one);
+    CHECK(S.now.p == B && S.now.bytes == 16 && S.raw().p == A && S.raw().bytes == 8 && S.adopted && empty(one));
+    S.adopt(two);
+    CHECK(S.now.p == C && S.raw().p == A && two.p == B && two.bytes == 16 && S.adopted);
+    S.restore(spare);
+    CHECK(S.now.p == A && S.now.bytes == 8 && S.raw().p == A && !S.adopted && empty(S.aside) && spare.p == C && spare.bytes == 24);
+    CHECK(CountedBuf::live == 3 && CountedBuf::released == 0);              // raw in force, `one` in two, `two` in spare
+  }
+  CHECK(CountedBuf::live == 0 && CountedBuf::released == 3);
+  {  // restore without adopt: nothing moves
+    InForce<CountedBuf> S; CountedBuf raw(8), spare;
+    const void *const A = raw.p;
+    exchange_buf(S.now, raw);
+    S.restore(spare);
+    CHECK(S.now.p == A && S.raw().p == A && !S.adopted && empty(spare) && empty(S.aside) && CountedBuf::live == 1);
+  }
+  CHECK(CountedBuf::live == 0 && CountedBuf::released == 4);
+  {  // a set without weights: the empty raw version goes aside and comes back
+    InForce<CountedBuf> S; CountedBuf one(16), spare;
+    const void *const B = one.p;
+    S.adopt(one);
+    CHECK(S.now.p == B && S.adopted && empty(S.raw()) && empty(one));
+    S.restore(spare);
+    CHECK(empty(S.now) && empty(S.raw()) && !S.adopted && spare.p == B && CountedBuf::live == 1);
+    S.adopt(spare);                                                       // (and again, from the spare)
+    CHECK(S.now.p == B && empty(S.raw()) && empty(spare) && CountedBuf::live == 1);
+  }
+  CHECK(CountedBuf::live == 0 && CountedBuf::released == 5);
+  {  // restore with a spare that is taken: the buffer that was in force is released, not leaked
+    InForce<CountedBuf> S; CountedBuf raw(8), one(16), spare(32);
+    const void *const A = raw.p, *const D = spare.p;
+    exchange_buf(S.now, raw);
+    S.adopt(one);
+    S.restore(spare);
+    CHECK(S.now.p == A && !S.adopted && empty(S.aside) && spare.p == D && spare.bytes == 32);
+    CHECK(CountedBuf::live == 2 && CountedBuf::released == 6);
+  }
+  CHECK(CountedBuf::live == 0 && CountedBuf::released == 8);
+}
+
 int main(int argc, char **argv)
 {
   if (argc == 3 && !std::strcmp(argv[1], "gauss")) {
@@ -625,6 +815,7 @@ int main(int argc, char **argv)
   band_refusals(); pixel_refusals(); observed_refusals(); observed_run_refusals(); trail_refusals(); map_refusals(); filter_refusals();
   broadening_refusals(); batch_rows_refusals();
   band_layouts(); filter_layouts(); extents();
+  grid_conditions(); observed_set_conditions(); filter_set_conditions(); pair_source_conditions(); in_force_transitions();
   std::printf("%s %d\n", g_bad ? "bad" : "ok", g_checks);
   return g_bad ? 1 : 0;
 }

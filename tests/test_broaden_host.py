@@ -4,11 +4,12 @@ block by block over exact-size tiles under -fsanitize=address,undefined."""
 import math
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+import host_check
 
 from transit_amd import broaden, pixels
 
@@ -145,14 +146,7 @@ def test_a_double_walk_in_the_kernels_order_is_inside_the_bound():
 
 
 def build_check(tmp, short):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp / ("broaden_check_%d" % short))
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-DBROADEN_TILE_SHORT=%d" % short, "-I", os.path.join(ROOT, "transit_amd", "csrc"),
-                    "-o", exe, os.path.join(ROOT, "tests", "broaden_check.cpp")], check=True)
-    return exe
+    return host_check.build_check("broaden_check", tmp, public_headers=False, defines=["BROADEN_TILE_SHORT=%d" % short], exe_name="broaden_check_%d" % short)
 
 
 def test_kernel_arithmetic_on_exact_tiles_under_sanitizers(tmp_path):

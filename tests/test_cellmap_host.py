@@ -4,11 +4,12 @@ vmap_nearest (transit_amd/csrc/trx_vmap.h), filtered_map_checks and cell_map_ext
 -- on the CPU through tests/cellmap_check.cpp, a stand-alone program over exact-size buffers under
 -fsanitize=address,undefined."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 from transit_amd import _abi, xcor
 
@@ -18,14 +19,7 @@ EPS = 2.0 ** -52
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("cellmap_check") / "cellmap_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "cellmap_check.cpp")], check=True)
-    return exe
+    return build_check("cellmap_check", tmp_path_factory.mktemp("cellmap_check"))
 
 
 def test_refusals_and_extents_under_sanitizers(check_exe):

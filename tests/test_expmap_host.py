@@ -4,11 +4,12 @@ side the library compiles -- exposed_map_checks, the spans, bases and row arrays
 exposed_map_extents (transit_amd/csrc/trx_expmap.h) -- on the CPU through tests/expmap_check.cpp, a stand-alone program
 over exact-size buffers under -fsanitize=address,undefined."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 from test_cellmap_host import hand_case
 from transit_amd import _abi, xcor
@@ -19,14 +20,7 @@ EMPTY = (2 ** 31 - 1, -1)
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("expmap_check") / "expmap_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "expmap_check.cpp")], check=True)
-    return exe
+    return build_check("expmap_check", tmp_path_factory.mktemp("expmap_check"))
 
 
 def test_refusals_rows_and_extents_under_sanitizers(check_exe):

@@ -6,11 +6,12 @@ the ABI: the struct's size and the four exported symbols."""
 import ctypes
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 from transit_amd import _abi, bands, build, exposures, pixels
 
@@ -19,14 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("exposures_check") / "exposures_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "exposures_check.cpp")], check=True)
-    return exe
+    return build_check("exposures_check", tmp_path_factory.mktemp("exposures_check"))
 
 
 @pytest.fixture(scope="module")

@@ -3,11 +3,12 @@ transit_amd/csrc/trx_highpass.h (the arithmetic k_pixel_highpass runs per lane) 
 transit_amd/csrc/trx_products.h, built with -ffp-contract=off under -fsanitize=address,undefined over exact-size heap
 arrays -- and transit_amd.xcor's statement of the same definition, which the program's values must equal in every bit."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 from transit_amd import xcor
 
@@ -17,14 +18,7 @@ TILE = 512                                             # kHpTile (the program as
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("highpass_check") / "highpass_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "highpass_check.cpp")], check=True)
-    return exe
+    return build_check("highpass_check", tmp_path_factory.mktemp("highpass_check"))
 
 
 def test_refusals_layout_and_extents_under_sanitizers(check_exe):

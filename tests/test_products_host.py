@@ -2,11 +2,12 @@
 extents of transit_amd/csrc/trx_products.h through tests/products_check.cpp, a stand-alone program over exact-size heap
 arrays under -fsanitize=address,undefined -- and the GAUSS range rule it holds against bands.gauss_range, its Python mirror."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 from transit_amd import bands
 
@@ -15,14 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("products_check") / "products_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "products_check.cpp")], check=True)
-    return exe
+    return build_check("products_check", tmp_path_factory.mktemp("products_check"))
 
 
 @pytest.fixture(scope="module")

@@ -7,11 +7,12 @@ None = weights 1, the median against np.sort, the variance against np.var); and 
 the exported symbol and the kernels in the code object."""
 import ctypes
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 import scatter_cases as cs
 from transit_amd import _abi, build, xcor
@@ -22,14 +23,7 @@ same_bits = cs.same_bits
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("scatter_check") / "scatter_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "scatter_check.cpp")], check=True)
-    return exe
+    return build_check("scatter_check", tmp_path_factory.mktemp("scatter_check"))
 
 
 def test_refusals_extents_tiles_and_known_sets_under_sanitizers(check_exe):

@@ -6,11 +6,12 @@ agreement with xcor.sysrem_basis, the injection's fixed points); and the ABI: th
 symbol and the kernels in the code object."""
 import ctypes
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
@@ -20,14 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("sysrem_check") / "sysrem_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "sysrem_check.cpp")], check=True)
-    return exe
+    return build_check("sysrem_check", tmp_path_factory.mktemp("sysrem_check"))
 
 
 def test_refusals_extents_tiles_and_known_sets_under_sanitizers(check_exe):

@@ -4,11 +4,12 @@ map_bound) against cases worked by hand and against the older xcor.velocity_map,
 under -fsanitize=address,undefined."""
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 from transit_amd import xcor
 
@@ -165,13 +166,7 @@ def test_map_reference_against_velocity_map(stat):
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("vmap_check") / "vmap_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "vmap_check.cpp")], check=True)
-    return exe
+    return build_check("vmap_check", tmp_path_factory.mktemp("vmap_check"), public_headers=False)
 
 
 def run_check(exe, path, trail, vm):

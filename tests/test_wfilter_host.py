@@ -6,11 +6,12 @@ projection in long double within xcor.weighted_filter_bound (derived in its docs
 vector; and the ABI: the struct's size, the pivot constant and the exported symbols."""
 import ctypes
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from host_check import build_check
 
 import wfilter_cases as wc
 from transit_amd import _abi, build, xcor
@@ -22,14 +23,7 @@ MASKED, SHORT, EXACT = 70, 75, 80                # edge columns, in the last seg
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("wfilter_check") / "wfilter_check")
-    subprocess.run([gxx, "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "transit_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "wfilter_check.cpp")], check=True)
-    return exe
+    return build_check("wfilter_check", tmp_path_factory.mktemp("wfilter_check"))
 
 
 def test_refusals_extents_layout_and_known_columns_under_sanitizers(check_exe):

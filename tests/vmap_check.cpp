@@ -9,24 +9,11 @@
 // [nlag][nexp][nseg][7], lag_kms [nlag], kp [nkp], vsys [nvsys], orbit [nexp] and, with has_offset, offset [nexp].
 // Prints "per" and nlag * nexp doubles in hex, one per line, then "map" and nkp * nvsys.
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
 
 #include "trx_vmap.h"
+#include "check_common.h"
 
 using namespace trx;
-
-static std::unique_ptr<double[]> read_doubles(FILE *f, size_t n)
-{
-  std::unique_ptr<double[]> a(new double[n]);          // exact size: the sanitizer guards both ends
-  char word[64];
-  for (size_t k = 0; k < n; k++) {
-    if (std::fscanf(f, "%63s", word) != 1) { std::fprintf(stderr, "vmap_check: the file ends early\n"); std::exit(2); }
-    a[k] = std::strtod(word, nullptr);
-  }
-  return a;
-}
 
 int main(int argc, char **argv)
 {

@@ -12,42 +12,12 @@
 //                                 must agree in every bit -- and prints per column "col p live" and then its nfac factor
 //                                 entries and its nexp values as C99 hex
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <initializer_list>
-#include <limits>
-#include <memory>
-#include <string>
 
 #include "trx_wfilter.h"
+#include "check_common.h"
 
 using namespace trx;
-
-static int g_checks = 0, g_bad = 0;
-#define CHECK(cond) do { g_checks++; if (!(cond)) { g_bad++; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
-
-// an exact-size heap array
-template <class T>
-struct Heap {
-  std::unique_ptr<T[]> p; size_t n;
-  explicit Heap(size_t n_, T fill = T()) : p(new T[n_]), n(n_) { for (size_t i = 0; i < n; i++) p[i] = fill; }
-  Heap(std::initializer_list<T> v) : p(new T[v.size()]), n(v.size()) { size_t i = 0; for (const T &x : v) p[i++] = x; }
-  T *get() const { return p.get(); }
-  T &operator[](size_t i) const { return p[i]; }
-};
-
-static void refused(int rc, const std::string &msg, int want_rc, const char *want, int line)
-{
-  g_checks++;
-  if (rc == want_rc && msg == want) return;
-  g_bad++;
-  std::printf("FAILED line %d: got (%d, \"%s\"), want (%d, \"%s\")\n", line, rc, msg.c_str(), want_rc, want);
-}
-#define REFUSED(call, want_rc, want) do { std::string msg; const int rc_ = (call); refused(rc_, msg, want_rc, want, __LINE__); } while (0)
-#define ACCEPTED(call) do { std::string msg = "untouched"; const int rc_ = (call); refused(rc_, msg, TRX_OK, "untouched", __LINE__); } while (0)
-
-static const double kNaN = std::numeric_limits<double>::quiet_NaN(), kInf = std::numeric_limits<double>::infinity();
 
 static bool same_bits(double a, double b) { return !std::memcmp(&a, &b, sizeof a) || (a != a && b != b); }
 
@@ -237,17 +207,6 @@ static void known()
   Heap<double> one{0.0, 0.0, 0.0,  0.0, 0.0, 0.0,  2.0, 2.0, 2.0,  0.0, 0.0, 0.0};
   R = run_set(S, T, one.get(), g.get());
   CHECK(R.live[0] == 0 && R.live[1] == 0 && R.live[2] == 0);
-}
-
-static std::unique_ptr<double[]> read_doubles(FILE *f, size_t n)
-{
-  std::unique_ptr<double[]> a(new double[n]);          // exact size: the sanitizer guards both ends
-  char word[64];
-  for (size_t k = 0; k < n; k++) {
-    if (std::fscanf(f, "%63s", word) != 1) { std::fprintf(stderr, "wfilter_check: the file ends early\n"); std::exit(2); }
-    a[k] = std::strtod(word, nullptr);
-  }
-  return a;
 }
 
 int main(int argc, char **argv)

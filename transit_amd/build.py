@@ -11,6 +11,7 @@ the tree).  hipcc cross-compiles gfx950 without a GPU.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -25,7 +26,8 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 CXX = os.environ.get("CXX") or "g++"
 
 HIP_SOURCES = ["hip/trx_api.hip"]
-HIP_DEPS = ["hip/trx_kernels.hip.h", "hip/trx_walk.hip.h", "hip/trx_rows.hip.h", "hip/trx_tail.hip.h", "hip/trx_lanes.hip.h", "hip/trx_bands.hip.h", "hip/trx_contrib.hip.h", "hip/trx_pixels.hip.h", "hip/trx_moments.hip.h", "hip/trx_trail.hip.h", "hip/trx_vmap.hip.h", "hip/trx_cellmap.hip.h", "hip/trx_expmap.hip.h", "hip/trx_filter.hip.h", "hip/trx_wfilter.hip.h", "hip/trx_sysrem.hip.h", "hip/trx_scatter.hip.h", "hip/trx_highpass.hip.h", "hip/trx_broaden.hip.h", "hip/trx_device.h", "trx_numerics.h", "trx_groups.h", "trx_plan.h", "trx_table.h", "trx_broaden.h", "trx_highpass.h", "trx_vmap.h", "trx_products.h", "trx_exposures.h", "trx_expmap.h", "trx_wfilter.h", "trx_sysrem.h", "trx_scatter.h"]
+# every header the one translation unit can include: whatever lies beside it or one level up
+HIP_DEPS = sorted(os.path.relpath(p, CSRC) for pat in ("*.h", "hip/*.h") for p in glob.glob(os.path.join(CSRC, pat)))
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
              "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-pthread"]
 

@@ -11,6 +11,9 @@
 //   * the plan of a run: layers per step, streams, events, the exchanges of a sharded job.
 // Everything per (line x layer), per (group x layer x bin) and per
 // (wavenumber x layer) runs in the kernels of trx_kernels.hip.h.
+//
+// One translation unit in four files: the handle and its helpers (trx_handle.hip.h), here the handle's creation and the run
+// path, then the run products (trx_api_products.hip.h) and the batch layer (trx_api_batch.hip.h), included at the end.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -61,348 +64,13 @@
 #include "../trx_wfilter.h"
 #include "../trx_sysrem.h"
 #include "../trx_scatter.h"
+#include "../trx_launch.h"
 
 using namespace trx;
 
-namespace {
-
-struct DevBuf {
-  void *p = nullptr; size_t bytes = 0;
-  ~DevBuf() { release(); }
-  void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
-  template <class T> T *as() const { return (T *)p; }
-};
-
-// pinned host memory the device reads and writes in place (dev: its address there, asked for once per allocation, not per run)
-struct PinnedBuf {
-  void *p = nullptr, *dev = nullptr; size_t bytes = 0;
-  ~PinnedBuf() { release(); }
-  void release() { if (p) { (void)hipHostFree(p); p = dev = nullptr; bytes = 0; } }
-};
-
-// view into another allocation (same accessors as DevBuf, owns nothing)
-struct DevView {
-  void *p = nullptr;
-  template <class T> T *as() const { return (T *)p; }
-};
-
-// a band set installed by trx_set_bands (trx_bands.hip.h), as this handle's shard sees it
-struct BandSet {
-  int32_t nbands = 0; int64_t npieces = 0;
-  DevBuf d_bands, d_pieces, d_w, d_part;             // BandDev[nbands], BandPiece[npieces], WEIGHTS' in-shard weights, [npieces][2]
-  PinnedBuf h_out;                                   // [nbands][2]: k_band_sums stores the run's sums here
-};
-
-// a pixel set installed by trx_set_pixels (trx_pixels.hip.h): the arrays as given -- ranges and weights are made on the device, per run
-struct PixelSet {
-  int64_t npix = 0; double cut = 0;
-  DevBuf d_centre, d_fwhm;                           // [npix] each
-};
-// an observed set installed by trx_set_observed over the pixel set (trx_moments.hip.h): the arrays as given
-struct ObservedSet {
-  int32_t nexp = 0, nseg = 0; int64_t npix = 0;
-  DevBuf d_seg, d_data, d_weight, d_gain;            // [nseg + 1], [nexp][npix], the same or none, [npix] or none
-  std::vector<int64_t> seg;                          // [nseg + 1] on the host: trx_set_filter cuts its tiles from it
-  // trx_detrend_observed (trx_sysrem.hip.h): the data as trx_set_observed installed them, moved aside by the first detrend
-  // call -- d_data then holds a call's residuals -- and moved back by the undo (empty: d_data is the raw set)
-  DevBuf d_raw;
-  // trx_weigh_observed (trx_scatter.hip.h): weighed = d_weight holds a weigh call's result and d_wraw the weights as
-  // trx_set_observed installed them -- empty where the set had none: all 1 --, moved aside by the first weigh call and moved
-  // back by its undo and by trx_detrend_observed (not weighed: d_weight is W, d_wraw is empty)
-  DevBuf d_wraw; bool weighed = false;
-  const DevBuf &raw_weight() const { return weighed ? d_wraw : d_weight; }
-};
-// a filter installed by trx_set_filter over the observed set (trx_filter.hip.h): the matrices zero-padded to npad
-// components and exposure-major, and the tiles of the observed set's segments
-struct FilterSet {
-  int32_t ncomp = 0, npad = 0, nexp = 0, nseg = 0; int64_t npix = 0, ntiles = 0;
-  DevBuf d_fwd, d_back, d_tiles;                     // [nseg][nexp][npad] each, FilterTile[ntiles]
-  // a weighted filter (trx_set_weighted_filter, trx_wfilter.hip.h): its padded basis in d_back (d_fwd stays empty), and
-  // every column's factor [nfac][npix] and pivot flag [npix], made by k_wfilter_factor when it was installed
-  bool weighted = false; int32_t nfac = 0;
-  DevBuf d_fac, d_live;
-};
-// a high-pass installed by trx_set_highpass over the observed set (trx_highpass.hip.h): the taps, their full-window sum and
-// the tiles of the observed set's segments; obs: that set (it goes when the set does), whose gains the kernel reads
-struct HighPassSet {
-  int32_t half = 0, nseg = 0; int64_t npix = 0, ntiles = 0; double den_full = 0; const ObservedSet *obs = nullptr;
-  DevBuf d_taps, d_tiles;                            // [half + 1], HpTile[ntiles]
-};
-// an exposure table installed by trx_set_exposures over the observed set (trx_pixels.hip.h, ../trx_exposures.h): the two
-// arrays as given, on the host -- a run uploads them with its shifts (an array the caller left out is empty)
-struct ExposureSet {
-  int32_t nexp = 0;
-  std::vector<double> scale, smear;                  // [nexp] each, or empty
-};
-// a pixel run (trx_run_pixels): the set and the run's shifts, already in h->d_pixshift; obs: a moment run (trx_run_moments);
-// filt: with the filter between the pairs and the moments (trx_run_filtered_moments); trail: the shifts are the lags of a
-// trail (trx_run_trail) -- every exposure of obs against every one of them (trx_trail.hip.h), never with a filter; ext: the
-// extents of its buffers (../trx_products.h), which pixel_run works out, grows them to and leaves here for the guards and copies;
-// hp: with the high-pass between the pairs and whatever reads them (pixel_run sets it for every run with obs on a handle that
-// has one; trx_run_highpassed itself), hpx the extents of that; ex: the rows are exposures and take the handle's exposure
-// table (trx_run_exposed, and trx_run_moments and trx_run_filtered_moments on a handle with one), already in h->d_exscale
-// and h->d_exsmear; ex_rows: ex is the call's own set of one entry per ROW of a map under the table (trx_run_exposed_map:
-// nexp = nshift rows, each a lag at an exposure), not the handle's
-struct PixelRun {
-  const PixelSet *set; int32_t nshift; const ObservedSet *obs = nullptr; const FilterSet *filt = nullptr; bool trail = false; PixelExtents ext{};
-  const HighPassSet *hp = nullptr; HighpassExtents hpx{};
-  const ExposureSet *ex = nullptr; bool ex_rows = false;
-};
-// a broadening installed by trx_set_broadening (trx_broaden.hip.h): two scalars, and the half-width of the grid's last bin --
-// the largest -- which sizes the kernel's tile
-struct Broadening { double beta = 0, limb = 0; int hmax = 0; };
-// what a run makes behind its spectrum (run_once, Run): nothing (trx_run, trx_run_device), or
-struct Products {
-  // a band run (trx_run_bands) -- the spectrum goes to h->d_spec like trx_run_device's, the band kernels follow the
-  // spectrum kernel on its queue, and the host copy of the spectrum (when asked for) is the plain copy command
-  const BandSet *bs = nullptr;
-  // a contribution run (trx_run_contrib) -- the kernels of trx_contrib.hip.h follow the band kernels
-  bool contrib = false;
-  // a pixel run (trx_run_pixels) -- the spectrum stays on the device as for bs, the kernel of trx_pixels.hip.h follows it,
-  // and (px->obs: trx_run_moments) the kernel of trx_moments.hip.h follows that -- or (px->trail: trx_run_trail) the one of
-  // trx_trail.hip.h
-  const PixelRun *px = nullptr;
-  // the broadening of a broadened run (trx_run_broadened) or of a pixel run on a handle with one installed -- the spectrum
-  // stays on the device as for bs, the kernel of trx_broaden.hip.h follows it, and the pixel kernel reads what that one wrote
-  const Broadening *br = nullptr;
-};
-
-// The handle's test switches: environment variables read at trx_create -- ALL of them, by read_switches
-// alone, before any stage.  Each selects between two forms of the same computation that give the same
-// bits (the tests named compare them side by side); none is needed in production, none changes a result.
-// (The A/B switches of forms that lost -- run graphs, the range size, tile-size tuning beyond what a
-// test forces -- are gone with those forms.)
-struct Switches {
-  bool no_row_copy = false;         // TRX_NO_ROW_COPY: wide frames without the walk's row copy (test_gpu_properties)
-  bool no_rows32 = false;           // TRX_NO_ROWS32: k_line_walk_lanes<8> on the 64-byte rows (test_gpu_lanes)
-  bool row_staging = true;          // osamp == 1: wide profiles through k_accumulate_rows (TRX_NO_ROW_STAGING: k_accumulate_wide; test_gpu_rows)
-  long long row_m8_from = 768;      // ... profile width (bins) from which a layer's tiles are 512 bins (TRX_ROWS_M8_FROM: test_gpu_rows, measurements)
-  bool packed_walk = true; int packed_max_layers = 10;   // steps of few layers walk several ranges per wave (TRX_NO_PACKED_WALK: never; TRX_PACKED_MAX_LAYERS: up to N layers, 1..32; test_gpu_packed)
-  int xcd_map = 1;                  // TRX_XCD_MAP: blocks -> ranges by XCD (xcd_block): bit 0 k_line_walk_lanes, bit 1 k_line_walk (measured: slower there)
-  bool no_binrec = false;           // TRX_NO_BINREC: k_ray_tail finds a bin's records through the ranges' numbers (A/B, tests)
-  // steps of at most 32 layers with frames of 8+ bins: lanes = lines for the strengths (trx_lanes.hip.h)
-  bool lanes_walk = true, lanes_force = false;      // TRX_LANES_WALK=0: the one-range / packed forms; =2: also on sparse lists (test_gpu_lanes)
-  int lanes_parts_most = 4;         // TRX_LANES_PARTS: k_line_walk_lanes with at most 2, 3 or 4 lanes per layer in phase 2 (test_gpu_lanes_parts)
-  bool ray_tail = true;             // hinted eclipse runs end in k_ray_tail (TRX_RAY_TAIL=0: the step kernels; test_gpu_tail, measurements)
-  bool cia_sums = true;             // the CIA splines' second derivatives as sums per row (TRX_CIA_SUMS=0: the sweeps of k_cia_layers; tests)
-  bool cia_segments = true;         // k_cia_layers in pieces of 128 rows (TRX_CIA_SEGMENTS=0: one sweep per table; test_gpu_cia_window)
-  bool cia_window = true;           // the CIA spline solved for the table rows a run needs (TRX_CIA_WINDOW=0: the whole table; test_gpu_cia_window)
-  bool two_queues = true;           // the second walk of a hinted run on a queue of its own, next to the first (TRX_TWO_QUEUES=0: behind it; A/B, tests)
-  bool tail_direct = true;          // ... which writes spectrum and flags straight into pinned host memory (TRX_TAIL_DIRECT=0: copy commands)
-  bool range_reach = true;          // k_line_walk tests a group's reach against its RANGE's widest profile and leaves a range out of all reach with zeros at its start (TRX_RANGE_REACH=0: the step's bound, every range walked; needs TablePlan::psize_mono; test_gpu_walk_reach, A/B)
-  bool shard_frames = true;         // frames sized for the Doppler indices the lines in reach can take (TRX_SHARD_FRAMES=0: for the isotope's whole wavenumber range; test_gpu_shard_frames)
-};
-
-}  // namespace
-
-struct trx_handle {
-  int device = 0;
-  hipStream_t stream = nullptr, stream2 = nullptr;   // stream2: CIA kernels, overlapped with the first sweep step
-  // stream4: the line sweep of step c+1 runs while `stream` integrates the optical depth of
-  // step c; ev_ac[c] = extinction of step c complete
-  hipStream_t stream4 = nullptr;
-  std::vector<hipEvent_t> ev_ac, ev_cb;      // ev_cb[c] = partial records of step c consumed
-  hipEvent_t ev_walk1 = nullptr;                     // the first walk of a two-queue run (and the CIA kernels) are done
-  hipEvent_t ev_inputs = nullptr, ev_cia = nullptr, ev_join = nullptr, ev_run_a = nullptr, ev_run_b = nullptr;
-  std::string err;
-
-  // grids
-  double wn_i = 0, wn_d = 0, odwn = 0; int64_t nwn = 0, nown = 0, lo = 0, hi = 0, nsh = 0; int osamp = 1;
-  // isotopes / molecules (host copies)
-  int niso = 0, nmol = 0;
-  std::vector<double> iso_mass, iso_ratio, mol_mass, mol_radius, mol_pol;
-  std::vector<double> pair_csd, pair_sqrt;          // [niso][nmol]: r_mol + r_iso's molecule, sqrt(1/m_iso + 1/m_mol) (extinction.c:376-380)
-  std::vector<int32_t> iso_imol, mol_is_h2;
-  std::vector<double> iso_wmin, iso_wmax;          // anchor wavenumber range per isotope
-  // Voigt table
-  int ndop = 0, nlor = 0;
-  std::vector<double> adop, alor;                   // +1 sentinel
-  std::vector<int32_t> psizeT; bool psize_mono = false;   // psize as [nlor][ndop] (prep_layers); no profile narrower than the one a Doppler index below it
-  std::vector<double> dopthr;                       // steps of the nearest-index function on adop (build_table; dop_index)
-  std::vector<double> lorthr;                       // the same on alor (empty: the grid did not pass the check -- nearest_index is called)
-  std::vector<int> guess_dop, guess_lor, guess_a0, guess_a1;      // [niso] where prep_layers found the layer above (its walks start there)
-  std::vector<long> guess_npre;                     // [niso] and the layer above's count of groups at or above the refresh cut
-  std::vector<double> iso_sqrtm;                    // sqrt(iso_mass)
-  std::vector<double> dens_over_m;                  // [nmol] scratch of prep_layers
-  std::vector<int32_t> psize; std::vector<long long> poff; int64_t tab_n = 0;
-  DevBuf d_adop, d_dopthr, d_e2tab, d_psize, d_poff, d_tab, d_tabT, d_poffT, d_gimod, d_gidiv;
-  // both tables carry kTabPad zero floats in front and behind: k_accumulate_wide reads whole
-  // 4-float lane segments around a profile row and masks what lies outside the row
-  float *tab = nullptr; const float *tabT = nullptr; const long long *poffT = nullptr;
-  // the walk's copy: phase-major rows of whole cache lines (walk_row_layout), one WalkProfile per table entry
-  DevBuf d_tabW, d_walkprof; const float *tabW = nullptr; bool tabw_ok = false;
-  DevBuf d_tabW32, d_wp32; const float *tabW32 = nullptr; unsigned slab32 = 0;      // compact 32-byte rows for frames of 8 bins (k_table_rows32)
-  std::vector<std::pair<double, double>> recip_ok;     // divisors whose reciprocal quotient_rn may use (checked_reciprocal)
-  int max_gcount = 0; DevBuf d_linebase, d_rinfo;      // the largest co-added group; what k_line_walk_lanes reads per line and per range (trx_lanes.hip.h)
-  Switches sw;
-  // lines
-  int64_t nlines = 0, ngroups = 0, nadd = 0, ninrange = 0;
-  DevBuf d_lgroup, d_wavn, d_elow, d_gf, d_iso, d_inr, d_gfirst, d_gcount, d_giown, d_giso, d_gwavn, d_gblock, d_cntge, d_cntsub;
-  int sub_f = 1;                        // sub-buckets per coarse cell of d_cntsub (1: it is d_cntge)
-  LinesDev L{};
-  HostBuf<double> h_gwavn; std::vector<int32_t> h_gblock; HostBuf<int32_t> h_cntge, h_gfirst, h_gcount;   // host copies for the per-run prologue
-  void *comm = nullptr; int nranks = 1, rank = 0;          // RCCL communicator: only trx_gather uses it
-  bool windowed() const { return lo > 0 || hi < nwn; }    // a shard sweeps only the lines that can reach it
-  // candidates for the layer maximum (k_cand_*): indices into the line arrays; -1 = use every line
-  DevBuf d_cand, d_candrec; int64_t ncand = -1;             // candidate line indices / their packed line data
-  DevBuf d_kmax;                                            // [2][layer] (runs alternate; k_layer_max) / [layer][nmx] (per-molecule sweeps)
-  int kmax_parity = 0, kmax_nr = 0; bool kmax_clean = false;   // clean: the half the next run will use is zero
-  // the walk (k_line_walk): one record per line, line ranges of ngw groups, plans per profile reach
-  DevBuf d_walk, d_wbase, d_part[2];   // partial records: consecutive steps alternate
-  std::vector<int32_t> h_wbase; int nwaves = 0, ngw = 0; bool walk_ok = false;
-  bool walk_temp_ok = true;         // this run's layers are all warmer than kWalkMinTemp
-  struct Plan { bool built = false; DevBuf blo, bhi, off, binw, binrec; int64_t records = 0; };
-  Plan plan[4];                                             // NB = 2, 4, 8, 16 bins per frame
-  // CIA (host copies)
-  struct Cia { int nspec; int mol[2]; std::vector<double> wn, temp, cs, zt, uw, ruw, rh, wf, wb; DevBuf d_wn, d_temp, d_cs, d_zt, d_uw, d_ruw, d_rh, d_wf, d_wb; };      // wf, wb: weights of k_cia_v / k_cia_z (empty: the sweeps)
-  std::vector<Cia> cia;
-  DevBuf d_cia_ws;
-  // per-run workspaces (grown on demand)
-  DevBuf d_SG, d_idop8, d_sticky, d_part3;
-  // per-run inputs: packed into ONE pinned host block and copied with ONE transfer
-  // (layer scalars, ray geometry, impact parameters, CIA density products)
-  DevBuf d_in; PinnedBuf h_in;
-  DevBuf d_pm_f64, d_pm_i32;         // the same scalars of a per-molecule sweep (trx_sweep_permol)
-  // what the host reads back after a run, in ONE device block and one pinned host block:
-  // flags (8 ints, byte 0), status (4 ints, byte 64), counters (3 per layer, byte 128)
-  DevBuf d_xf;                        // scattering / cloud wavenumber factors [2][nsh] + 3 constants
-  DevBuf d_small; DevView d_flags, d_status, d_counters; PinnedBuf h_small;
-  DevBuf d_e, d_ecs, d_er, d_tau, d_last, d_intens, d_spec, d_acc, d_geom;
-  // opacity grid (optional)
-  bool has_grid = false; long og_nmol = 0, og_ntemp = 0, og_nlayer = 0, og_nwave = 0;
-  std::vector<double> og_temp; std::vector<int32_t> og_molidx; DevBuf d_og_o, d_og_layer, d_og_itemp, d_iso_mx, d_pm;
-  trx_stats stats{};
-  std::vector<double> run_f64, run_geom, run_ipv; std::vector<int32_t> run_i32;      // per-run host arrays (kept: no allocation per run)
-  std::vector<int> run_frame; std::vector<unsigned char> run_wide;      // [layer] walk_frame_bins, and the plan's "very wide" mark (trx_plan.h)
-  std::vector<PlanStep> run_plan;                                        // the steps of the pass being queued
-  std::vector<double> run_og_layer; std::vector<int> run_og_itemp;       // opacity grid: the layers' weights and temperature brackets (Run::grid_weights)
-  int hint_layers = 0;       // layers the previous run needed (deepest toomuch crossing + 1)
-  DevBuf d_e_saved; std::vector<uint8_t> saved;          // trx_restore_extinction: [nlayer][nsh] and the flags (empty: none)
-  PinnedBuf h_spec;          // staging of the spectrum (trx_run hands over pageable memory)
-  PinnedBuf h_tailblk;       // what each block of k_ray_tail adds to the run's flags (vertical rays: the host adds them up)
-  std::unique_ptr<BandSet> bands;                      // trx_set_bands (null: none)
-  // trx_run_contrib (trx_contrib.hip.h): sub-piece rows [npieces * kContribSplit][nlayer] and the pinned result [nbands][nlayer], sized on
-  // first use and when the set or nlayer grows
-  DevBuf d_cpart; PinnedBuf h_contrib;
-  std::unique_ptr<PixelSet> pixels;                    // trx_set_pixels (null: none)
-  DevBuf d_pixshift, d_pixout;                         // trx_run_pixels: the run's shifts [nshift] and its pairs [nshift][npix][2], grown on demand
-  std::unique_ptr<ObservedSet> observed;               // trx_set_observed (null: none); belongs to `pixels`
-  DevBuf d_mom;                                        // trx_run_moments: [nexp][nseg][TRX_NMOMENT], grown on demand
-  DevBuf d_trail;                                      // trx_run_trail: [nlag][nexp][nseg][TRX_NMOMENT], grown on demand
-  // trx_run_velocity_map (trx_vmap.hip.h), grown on demand: the call's arrays lag_kms, kp, vsys, orbit, offset end to end (their
-  // host copy: vm_in), the statistic [nlag][nexp] followed by its transpose [nexp][nlag], the map [nkp][nvsys]
-  DevBuf d_vm_in, d_vm_per, d_vm_map; std::vector<double> vm_in;
-  // trx_run_filtered_map (trx_cellmap.hip.h), grown on demand: the call's arrays in d_vm_in as above, the nearest-lag table
-  // [nkp * nvsys][nexp] int32, one chunk's filtered values [chunk][nexp][npix] and moments [chunk][nexp][nseg][TRX_NMOMENT],
-  // the map [nkp][nvsys]
-  DevBuf d_cm_index, d_cm_val, d_cm_mom, d_cm_map;
-  // trx_run_exposed_map (trx_expmap.hip.h), grown on demand: the spans [nexp][2] int32 of the call's exposures (their host
-  // copy: em_span), the first row [nexp] int64 of each, the row table [nkp * nvsys][nexp] int32 beside the lag table
-  DevBuf d_em_span, d_em_base, d_em_row; std::vector<int32_t> em_span;
-  std::unique_ptr<FilterSet> filter;                   // trx_set_filter (null: none); belongs to `observed`
-  DevBuf d_pixval;                                     // trx_run_filtered_moments: the filtered values [nexp][npix], grown on demand
-  std::unique_ptr<HighPassSet> highpass;               // trx_set_highpass (null: none); belongs to `observed`
-  // the high-passed pairs [nshift][npix][2] of a run with a high-pass, (g', 1) or (0, 0), grown on demand: what the filter, the
-  // moments and the trail then read in place of d_pixout; trx_run_highpassed copies them to h_pixhp whole
-  DevBuf d_pixhp; PinnedBuf h_pixhp;
-  bool broad_on = false; Broadening broad;             // trx_set_broadening (broad_on false: none); independent of the sets above
-  DevBuf d_broad;                                      // the broadened spectrum [nwn] of a broadened or pixel run, grown on demand
-  std::unique_ptr<ExposureSet> exposures;              // trx_set_exposures (null: none); belongs to `observed`
-  DevBuf d_exscale, d_exsmear;                         // the table's arrays [nexp] each, uploaded by every run that takes it, grown on demand
-  // trx_detrend_observed (trx_sysrem.hip.h), grown on demand: the residuals [nexp][npix] a call builds (swapped with the
-  // observed set's data when it succeeds), the time vector [nseg][nexp], the column vector [npix], coef [ncomp][npix],
-  // U [nseg][nexp][ncomp] (its host copy: sr_basis) and the tiles of the set's segments
-  DevBuf d_sr_r, d_sr_a, d_sr_c, d_sr_coef, d_sr_basis, d_sr_tiles; std::vector<double> sr_basis;
-  // trx_weigh_observed (trx_scatter.hip.h), grown on demand: the weights [nexp][npix] a call builds (swapped with the observed
-  // set's when it succeeds), the variances [npix], the medians [nseg], the columns' flags [npix] and the tiles; the factor
-  // and the pivot flags a call makes for the installed weighted filter (swapped with the filter's)
-  DevBuf d_sc_w, d_sc_var, d_sc_med, d_sc_flag, d_sc_tiles, d_sc_fac, d_sc_live;
-};
+#include "trx_handle.hip.h"
 
 namespace {
-
-// process-wide message sink (trx_set_log): the reference's tr_output()/verblevel pair
-struct LogSink { trx_log_fn fn = nullptr; void *user = nullptr; int max_level = 0; };
-LogSink &log_sink() { static LogSink s; return s; }
-void log_msg(int level, const std::string &msg)
-{
-  const LogSink s = log_sink();
-  if (s.fn && level <= s.max_level) s.fn(level, msg.c_str(), s.user);
-}
-
-// stage timer of trx_create: logs "create: <stage> x.xx ms" at TRX_LOG_DEBUG
-struct StageTimer {
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void lap(const char *what) {
-    const auto n = std::chrono::steady_clock::now();
-    if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG) {
-      char b[128]; std::snprintf(b, sizeof b, "create: %-28s %8.2f ms", what, std::chrono::duration<double, std::milli>(n - t).count());
-      log_msg(TRX_LOG_DEBUG, b);
-    }
-    t = n;
-  }
-};
-
-int fail(trx_handle *h, int code, const std::string &msg)
-{ if (h) h->err = msg; log_msg(TRX_LOG_ERROR, msg); return code; }
-
-#define HIPCHK(h, call)                                                              \
-  do { hipError_t e_ = (call);                                                       \
-       if (e_ != hipSuccess)                                                         \
-         return fail(h, e_ == hipErrorOutOfMemory ? TRX_E_NOMEM : TRX_E_HIP,         \
-                     std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-int ensure(trx_handle *h, DevBuf &b, size_t bytes)
-{
-  if (bytes == 0) bytes = 8;
-  if (b.bytes >= bytes) return TRX_OK;
-  b.release();
-  HIPCHK(h, hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
-  return TRX_OK;
-}
-
-// grow-only, with exactly the size asked for
-int ensure_pinned(trx_handle *h, PinnedBuf &b, size_t bytes)
-{
-  if (b.bytes >= bytes) return TRX_OK;
-  b.release();
-  HIPCHK(h, hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
-  b.bytes = bytes;
-  HIPCHK(h, hipHostGetDevicePointer(&b.dev, b.p, 0));
-  return TRX_OK;
-}
-
-// the small read-back block for nlay layers (device + pinned host mirror)
-int ensure_small(trx_handle *h, int nlay)
-{
-  const size_t bytes = 128 + 24 * (size_t)nlay;
-  if (const int rc = ensure(h, h->d_small, bytes)) return rc;
-  char *base = (char *)h->d_small.p;
-  h->d_flags.p = base; h->d_status.p = base + 64; h->d_counters.p = base + 128;
-  return ensure_pinned(h, h->h_small, bytes);
-}
-
-template <class T>
-int upload_raw(trx_handle *h, DevBuf &b, const T *p, size_t n)
-{
-  int rc = ensure(h, b, n * sizeof(T));
-  if (rc) return rc;
-  if (n) HIPCHK(h, hipMemcpyAsync(b.p, p, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  return TRX_OK;
-}
-
-template <class T>
-int upload(trx_handle *h, DevBuf &b, const std::vector<T> &v)
-{
-  int rc = ensure(h, b, v.size() * sizeof(T));
-  if (rc) return rc;
-  if (!v.empty()) HIPCHK(h, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  return TRX_OK;
-}
-
-template <class T>
-int upload(trx_handle *h, DevBuf &b, const HostBuf<T> &v) { return upload_raw(h, b, v.data(), v.size()); }
 
 // The one place the handle's switches are read (struct Switches); trx_create calls it before any stage.
 void read_switches(Switches &w)
@@ -2141,7 +1809,7 @@ struct Run {
   // ... the spectrum of what they swept, the way back
   int spectrum_kernel(); int ray_tail(); int results();
   // ... and what the run makes of that spectrum (want), behind it on its queue
-  int product_kernels(); int band_kernels(); int broaden_kernel(); int pixel_kernels(); int highpass_kernels(); int filter_kernels(); int moment_kernels();
+  int product_kernels();
 };
 
 // scattering / cloud models: the parameters of tau.c:193-214, extinction.c:587-693, and the per-ray
@@ -2734,264 +2402,6 @@ int Run::spectrum_kernel()
   return TRX_OK;
 }
 
-// ---- band integrals of this pass's spectrum (trx_bands.hip.h), behind it on its queue.  A pass that resumes
-// deeper queues them again behind its own spectrum: the sums the host reads are the last pass's.
-int Run::band_kernels()
-{
-  const BandSet *const bs = want.bs;
-  if (!bs || bs->nbands <= 0) return TRX_OK;
-  BandArgs BA{};
-  BA.spec = d_out; BA.bands = bs->d_bands.as<BandDev>(); BA.pieces = bs->d_pieces.as<BandPiece>();
-  BA.w = bs->d_w.as<double>(); BA.part = bs->d_part.as<double>(); BA.out = (double *)bs->h_out.dev;
-  BA.npieces = bs->npieces; BA.lo = h->lo; BA.nbands = bs->nbands; BA.wn_i = h->wn_i; BA.wn_d = h->wn_d;
-  if (!BA.spec || !BA.bands || !BA.part || !BA.out || (bs->npieces > 0 && !BA.pieces))
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the band kernels (not launched)");
-  if (bs->npieces > 0)
-    hipLaunchKernelGGL(k_band_pieces, dim3((unsigned)((bs->npieces + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
-  hipLaunchKernelGGL(k_band_sums, dim3((unsigned)((bs->nbands + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, BA);
-  // ---- and the contribution functions of this pass's optical depths (trx_contrib.hip.h), behind them
-  if (!want.contrib) return TRX_OK;
-  ContribArgs CA{};
-  if (vertical) emis_args(CA.E);
-  else {                                             // (transit geometry: the grid, tau and last; no angles)
-    CA.E.nr = nr; CA.E.nang = 0; CA.E.nsh = nsh; CA.E.lo = h->lo; CA.E.wn_i = h->wn_i; CA.E.wn_d = h->wn_d; CA.E.wn_fct = o->wn_fct;
-    CA.E.tau = h->d_tau.as<double>(); CA.E.last = h->d_last.as<int>(); CA.E.temp = d_tempk; CA.E.e2tab = h->d_e2tab.as<double>();
-  }
-  CA.bands = BA.bands; CA.pieces = BA.pieces; CA.w = BA.w; CA.part = h->d_cpart.as<double>(); CA.out = (double *)h->h_contrib.dev;
-  CA.npieces = bs->npieces; CA.nbands = bs->nbands; CA.vertical = vertical ? 1 : 0;
-  const size_t rows = sizeof(double) * (size_t)nr;
-  const ContribExtents CX = contrib_extents(nr, bs->npieces, bs->nbands);
-  if (!CA.E.tau || !CA.E.last || !CA.E.temp || !CA.E.e2tab || !CA.bands || !CA.part || !CA.out || (bs->npieces > 0 && !CA.pieces) ||
-      (vertical && (CA.E.nang < 1 || CA.E.nang > kMaxAngles)) || h->d_tau.bytes < rows * (size_t)nsh || h->d_last.bytes < sizeof(int) * (size_t)nsh ||
-      h->d_cpart.bytes < CX.cpart_bytes || h->h_contrib.bytes < CX.out_bytes)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the contribution kernels (not launched)");
-  if (bs->npieces > 0) {
-    const dim3 cgrid((unsigned)(bs->npieces * kContribSplit), (unsigned)((nr + kContribHeights - 1) / kContribHeights));
-    hipLaunchKernelGGL(CA.E.nang <= 8 ? k_contrib_pieces<8> : k_contrib_pieces<kMaxAngles>, cgrid, dim3(64 * kContribWaves), 0, tst, CA);
-  }
-  hipLaunchKernelGGL(k_contrib_sums, dim3((unsigned)(((int64_t)bs->nbands * nr + kBandWaves - 1) / kBandWaves)), dim3(64 * kBandWaves), 0, tst, CA);
-  return TRX_OK;
-}
-
-// ---- the rotational broadening of this pass's spectrum (trx_broaden.hip.h), behind it on its queue and ahead of the pixel
-// kernel, which then reads d_broad; a pass that resumes deeper queues it again behind its own spectrum.
-int Run::broaden_kernel()
-{
-  const Broadening *const br = want.br;
-  if (!br) return TRX_OK;
-  BroadArgs BA{};
-  BA.spec = d_out; BA.out = h->d_broad.as<double>(); BA.nwn = h->nwn;
-  BA.wn_i = h->wn_i; BA.wn_d = h->wn_d; BA.beta = br->beta; BA.W = broaden_weights(br->limb); BA.hmax = br->hmax;
-  const int64_t blocks = (BA.nwn + kBroadBlock - 1) / kBroadBlock;
-  const size_t lds = sizeof(double) * ((size_t)kBroadBlock + 2 * (size_t)(br->hmax > 0 ? br->hmax : 0));
-  // (every address the kernel reads or writes: the spectrum and the broadened one over [0, nwn) = [0, nsh) -- the whole grid,
-  // or trx_set_broadening would have refused --, and a tile of at most kBroadBlock + 2 hmax doubles of LDS)
-  double d_last;
-  if (!BA.spec || !BA.out || h->windowed() || nsh != h->nwn || h->d_broad.bytes < broadened_bytes(nsh) ||
-      (!d_spectrum && h->d_spec.bytes < sizeof(double) * (size_t)nsh) || !(BA.wn_i > 0) || !(BA.wn_d > 0) || !(BA.beta > 0) ||
-      br->hmax < 0 || br->hmax > TRX_BROADEN_MAX_HALF || broaden_half(BA.wn_i, BA.wn_d, BA.beta, BA.nwn - 1, d_last) != (double)br->hmax ||
-      blocks < 1 || blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the broadening kernel (not launched)");
-  hipLaunchKernelGGL(k_broaden, dim3((unsigned)blocks), dim3(kBroadBlock), lds, tst, BA);
-  return TRX_OK;
-}
-
-// ---- the detector pixels of this pass's spectrum at the run's shifts (trx_pixels.hip.h), behind it on its queue like
-// the band kernels; a pass that resumes deeper queues it again behind its own spectrum.
-int Run::pixel_kernels()
-{
-  const PixelRun *const px = want.px;
-  if (!px) return TRX_OK;
-  const PixelSet &S = *px->set; const PixelExtents &X = px->ext;
-  PixArgs PA{};
-  PA.spec = want.br ? h->d_broad.as<double>() : d_out; PA.centre = S.d_centre.as<double>(); PA.fwhm = S.d_fwhm.as<double>();
-  PA.shift = h->d_pixshift.as<double>(); PA.out = h->d_pixout.as<double>();
-  PA.npix = S.npix; PA.npairs = S.npix * (int64_t)px->nshift;
-  PA.nwn = h->nwn; PA.lo = h->lo; PA.hi = h->hi; PA.cut = S.cut; PA.fwhm_sigma = 2.0 * std::sqrt(2.0 * std::log(2.0));
-  PA.wn_i = h->wn_i; PA.wn_d = h->wn_d;
-  const int64_t blocks = X.blocks;
-  // (every address the kernel reads or writes: the spectrum over [0, hi - lo) = [0, nsh), the set's arrays, the shifts, the pairs
-  // -- by the extents pixel_run grew the buffers to, which are this launch's: X.pairs)
-  if (!PA.spec || !PA.centre || !PA.fwhm || !PA.shift || !PA.out || S.npix < 1 || px->nshift < 1 || h->hi - h->lo != nsh || X.pairs != PA.npairs ||
-      S.d_centre.bytes < sizeof(double) * (size_t)S.npix || S.d_fwhm.bytes < sizeof(double) * (size_t)S.npix ||
-      h->d_pixshift.bytes < X.shift_bytes || h->d_pixout.bytes < X.pair_bytes ||
-      blocks < 1 || blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the pixel kernel (not launched)");
-  const ExposureSet *const ex = px->ex;
-  if (!ex) {
-    hipLaunchKernelGGL(k_pixel_pairs, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
-    return TRX_OK;
-  }
-  // the rows are exposures: the table's arrays, one entry per row (pixel_run sent them ahead with the shifts)
-  const ExposureExtents EX = exposure_extents(ex->nexp);
-  if (!ex->scale.empty()) PA.scale = h->d_exscale.as<double>();
-  if (!ex->smear.empty()) PA.smear = h->d_exsmear.as<double>();
-  PA.sqrt2 = std::sqrt(2.0);
-  // (every further address the kernel reads: scale and smear over [0, nshift) = [0, nexp))
-  // (the set is the handle's -- or the rows' own of an exposed map, which never has obs, filt or trail)
-  if ((px->ex_rows ? px->obs || px->filt || px->trail : ex != h->exposures.get()) || ex->nexp != px->nshift || (ex->scale.empty() && ex->smear.empty()) ||
-      (!ex->scale.empty() && (ex->scale.size() != (size_t)ex->nexp || !PA.scale || h->d_exscale.bytes < EX.scale_bytes)) ||
-      (!ex->smear.empty() && (ex->smear.size() != (size_t)ex->nexp || !PA.smear || h->d_exsmear.bytes < EX.smear_bytes)))
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the exposed pixel kernel (not launched)");
-  hipLaunchKernelGGL(k_pixel_pairs_exposed, dim3((unsigned)blocks), dim3(kPixBlock), 0, tst, PA);
-  return TRX_OK;
-}
-
-// ---- the high-pass of those pairs along the pixel axis (trx_highpass.hip.h), behind the pixel kernel on its queue and ahead
-// of the filter, the moments and the trail, which then read d_pixhp; a pass that resumes deeper queues it again.
-int Run::highpass_kernels()
-{
-  const PixelRun *const px = want.px;
-  if (!px || !px->hp) return TRX_OK;
-  const HighPassSet &F = *px->hp; const PixelExtents &X = px->ext; const HighpassExtents &HX = px->hpx;
-  const ObservedSet *O = F.obs;
-  HpArgs HA{};
-  HA.pairs = h->d_pixout.as<double2>(); HA.gain = O ? O->d_gain.as<double>() : nullptr; HA.taps = F.d_taps.as<double>();
-  HA.tiles = F.d_tiles.as<HpTile>(); HA.out = h->d_pixhp.as<double2>();
-  HA.npix = F.npix; HA.ntiles = F.ntiles; HA.den_full = F.den_full; HA.half = F.half;
-  const HighpassExtents want_x = highpass_extents(F.npix, px->nshift, F.ntiles, F.half);
-  // (every address the kernel reads or writes: pairs in and out over [nshift][npix] -- the tiles lie in [0, npix) within their
-  // segments' bounds, made so from the observed set's when the high-pass was --, the gains, the taps [half + 1], the tiles,
-  // and (count + 2 half) * 2 doubles of LDS, count <= kHpTile)
-  if (!O || O != h->observed.get() || (px->obs && px->obs != O) || !HA.pairs || !HA.taps || !HA.tiles || !HA.out || F.half < 0 || F.half > TRX_HIGHPASS_MAX_HALF ||
-      F.npix < 1 || F.npix != px->set->npix || F.npix != O->npix || F.nseg != O->nseg || px->nshift < 1 || F.ntiles < 1 ||
-      X.pairs != (int64_t)px->nshift * F.npix || HX.pairs != X.pairs || HX.blocks != want_x.blocks || HX.pair_bytes != want_x.pair_bytes || HX.lds_bytes != want_x.lds_bytes ||
-      h->d_pixout.bytes < X.pair_bytes || h->d_pixhp.bytes < HX.pair_bytes || (HA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) ||
-      F.d_taps.bytes < sizeof(double) * ((size_t)F.half + 1) || F.d_tiles.bytes < sizeof(HpTile) * (size_t)F.ntiles ||
-      HX.lds_bytes > 65536 || HX.blocks < 1 || HX.blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the high-pass kernel (not launched)");
-  hipLaunchKernelGGL(k_pixel_highpass, dim3((unsigned)HX.blocks), dim3(kHpBlock), HX.lds_bytes, tst, HA);
-  return TRX_OK;
-}
-
-// ---- the weighted filter of those pairs (trx_wfilter.hip.h), where the plain one runs
-// what the weighted kernels read of the set F over the observed set O, whole: the padded basis, the tiles, every column's
-// factor and flag, the weights
-static bool wfilter_set_complete(const FilterSet &F, const ObservedSet &O)
-{
-  const WfilterExtents WX = wfilter_extents(F.npix, F.nexp, F.nseg, F.ncomp, F.npad, F.ntiles, kFiltWaves);
-  return F.weighted && F.d_back.p && F.d_tiles.p && F.d_fac.p && F.d_live.p && F.nexp >= 1 && F.nseg >= 1 && F.ncomp >= 1 && F.ncomp <= F.npad &&
-         (F.npad == 4 || F.npad == 8 || F.npad == 16) && F.npix >= 1 && F.ntiles >= 1 && F.npix == O.npix && F.nexp == O.nexp && F.nseg == O.nseg &&
-         F.nfac == WX.nfac && F.d_back.bytes >= WX.basis_bytes && F.d_fac.bytes >= WX.fac_bytes && F.d_live.bytes >= WX.live_bytes &&
-         F.d_tiles.bytes >= sizeof(FilterTile) * (size_t)F.ntiles &&
-         (!O.d_weight.p || O.d_weight.bytes >= sizeof(double) * (size_t)O.nexp * (size_t)O.npix);
-}
-
-static int launch_wfilter(trx_handle *h, const PixelRun &px, hipStream_t st)
-{
-  const FilterSet &F = *px.filt; const PixelExtents &X = px.ext;
-  const ObservedSet *O = px.obs;
-  WfilterArgs FA{};
-  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
-  FA.pairs = px.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = O && !px.hp ? O->d_gain.as<double>() : nullptr;
-  FA.weight = O ? O->d_weight.as<double>() : nullptr; FA.basis = F.d_back.as<double>(); FA.fac = F.d_fac.as<double>(); FA.live = F.d_live.as<int32_t>();
-  FA.tiles = F.d_tiles.as<FilterTile>(); FA.val = h->d_pixval.as<double>();
-  FA.npix = F.npix; FA.ntiles = F.ntiles; FA.nexp = F.nexp; FA.ncomp = F.ncomp;
-  const int64_t blocks = (FA.ntiles + kFiltWaves - 1) / kFiltWaves;
-  // (every address the kernel reads or writes: pairs and values over [nexp][npix] -- the tiles lie in [0, npix) and name
-  // segments below nseg, made so when the filter was --, the gains, and the set's own arrays: wfilter_set_complete)
-  if (!O || !FA.pairs || !FA.val || !wfilter_set_complete(F, *O) || F.npix != px.set->npix || F.nexp != px.nshift ||
-      X.pairs != (int64_t)F.nexp * F.npix || h->d_pixout.bytes < X.pair_bytes || (px.hp && (px.hpx.pairs != X.pairs || h->d_pixhp.bytes < px.hpx.pair_bytes)) ||
-      X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes || (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) ||
-      blocks < 1 || blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the weighted filter kernel (not launched)");
-  const dim3 grid((unsigned)blocks), block(64 * kFiltWaves);
-  if (F.npad == 4) hipLaunchKernelGGL(k_pixel_wfilter<4>, grid, block, 0, st, FA);
-  else if (F.npad == 8) hipLaunchKernelGGL(k_pixel_wfilter<8>, grid, block, 0, st, FA);
-  else hipLaunchKernelGGL(k_pixel_wfilter<16>, grid, block, 0, st, FA);
-  return TRX_OK;
-}
-
-// ---- the filter of those pairs along the exposure axis (trx_filter.hip.h), behind the pixel kernel on its queue and
-// ahead of the moment kernel, which then reads its values; a pass that resumes deeper queues all three again.
-int Run::filter_kernels()
-{
-  const PixelRun *const px = want.px;
-  if (!px || !px->filt) return TRX_OK;
-  if (px->filt->weighted) return launch_wfilter(h, *px, tst);
-  const FilterSet &F = *px->filt; const PixelExtents &X = px->ext;
-  const ObservedSet *O = px->obs;
-  FilterArgs FA{};
-  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
-  FA.pairs = px->hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = O && !px->hp ? O->d_gain.as<double>() : nullptr;
-  FA.fwd = F.d_fwd.as<double>(); FA.back = F.d_back.as<double>(); FA.tiles = F.d_tiles.as<FilterTile>(); FA.val = h->d_pixval.as<double>();
-  FA.npix = F.npix; FA.ntiles = F.ntiles; FA.nexp = F.nexp;
-  const int64_t blocks = (FA.ntiles + kFiltWaves - 1) / kFiltWaves;
-  const size_t mat = sizeof(double) * (size_t)F.nseg * (size_t)F.nexp * (size_t)F.npad;
-  // (every address the kernel reads or writes: pairs and values over [nexp][npix] -- the tiles lie in [0, npix) and name
-  // segments below nseg, made so when the filter was --, the gains, the two padded matrices, the tiles)
-  if (!O || !FA.pairs || !FA.fwd || !FA.back || !FA.tiles || !FA.val || F.nexp < 1 || F.nseg < 1 || F.ncomp < 1 || F.ncomp > F.npad ||
-      (F.npad != 4 && F.npad != 8 && F.npad != 16) || F.npix != px->set->npix || F.nexp != px->nshift || F.npix != O->npix || F.nexp != O->nexp || F.nseg != O->nseg ||
-      X.pairs != (int64_t)F.nexp * F.npix || h->d_pixout.bytes < X.pair_bytes || (px->hp && (px->hpx.pairs != X.pairs || h->d_pixhp.bytes < px->hpx.pair_bytes)) || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes || F.d_fwd.bytes < mat || F.d_back.bytes < mat ||
-      (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)F.npix) || F.d_tiles.bytes < sizeof(FilterTile) * (size_t)F.ntiles ||
-      blocks < 1 || blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the filter kernel (not launched)");
-  const dim3 grid((unsigned)blocks), block(64 * kFiltWaves);
-  if (F.npad == 4) hipLaunchKernelGGL(k_pixel_filter<4>, grid, block, 0, tst, FA);
-  else if (F.npad == 8) hipLaunchKernelGGL(k_pixel_filter<8>, grid, block, 0, tst, FA);
-  else hipLaunchKernelGGL(k_pixel_filter<16>, grid, block, 0, tst, FA);
-  return TRX_OK;
-}
-
-// ---- the trail of those pairs -- one shift per LAG -- against every exposure of the observed set (trx_trail.hip.h)
-static int launch_trail(trx_handle *h, const PixelRun &px, hipStream_t st)
-{
-  const ObservedSet &O = *px.obs; const PixelExtents &X = px.ext;
-  constexpr int TL = kTrailLags, TV = kTrailExps;
-  TrailArgs TA{};
-  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
-  TA.pairs = px.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); TA.gain = px.hp ? nullptr : O.d_gain.as<double>();
-  TA.data = O.d_data.as<double>(); TA.weight = O.d_weight.as<double>();
-  TA.seg_first = O.d_seg.as<int64_t>(); TA.trail = h->d_trail.as<double>();
-  TA.npix = O.npix; TA.nlag = px.nshift; TA.nexp = O.nexp; TA.nseg = O.nseg;
-  TA.ntl = (px.nshift + TL - 1) / TL; TA.ntv = (O.nexp + TV - 1) / TV;
-  TA.nwaves = (int64_t)O.nseg * TA.ntl * TA.ntv; TA.xcd_map = 1;
-  const int64_t blocks = (TA.nwaves + kTrailWaves - 1) / kTrailWaves;
-  const int64_t rows = X.rows;
-  const size_t cells = sizeof(double) * (size_t)O.nexp * (size_t)O.npix;
-  // (every address the kernel reads or writes: the pairs over [nlag][npix], data and weights over [nexp][npix] -- the segments
-  // lie in [0, npix), checked when the set was made, and a ragged tile's surplus indices are nlag - 1 and nexp - 1 --, the
-  // gains, the segment bounds, the rows of [nlag][nexp][nseg])
-  if (!TA.pairs || !TA.data || !TA.seg_first || !TA.trail || px.filt || px.nshift < 1 || O.nexp < 1 || O.nseg < 1 || O.npix < 1 || O.npix != px.set->npix ||
-      O.seg.size() != (size_t)O.nseg + 1 || O.seg.front() != 0 || O.seg.back() != O.npix || rows < 1 || rows > 0x7fffffffLL ||
-      X.pairs != (int64_t)px.nshift * O.npix || h->d_pixout.bytes < X.pair_bytes || (px.hp && (px.hpx.pairs != X.pairs || h->d_pixhp.bytes < px.hpx.pair_bytes)) || O.d_data.bytes < cells || (TA.weight && O.d_weight.bytes < cells) ||
-      (TA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
-      X.trail_bytes < 1 || h->d_trail.bytes < X.trail_bytes || blocks < 1 || blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the trail kernel (not launched)");
-  hipLaunchKernelGGL((k_trail_moments<TL, TV>), dim3((unsigned)blocks), dim3(64 * kTrailWaves), 0, st, TA);
-  return TRX_OK;
-}
-
-// ---- the moments of those pairs (of the filter's values: a filtered run) against the observed set (trx_moments.hip.h),
-// behind the pixel kernel on its queue; a pass that resumes deeper queues both again.  (A trail run: its kernel instead.)
-int Run::moment_kernels()
-{
-  const PixelRun *const px = want.px;
-  if (!px || !px->obs) return TRX_OK;
-  const ObservedSet &O = *px->obs; const PixelExtents &X = px->ext;
-  if (px->trail) return launch_trail(h, *px, tst);
-  MomArgs MA{};
-  MA.val = px->filt ? h->d_pixval.as<double>() : nullptr;
-  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
-  MA.pairs = px->hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); MA.gain = px->hp ? nullptr : O.d_gain.as<double>();
-  MA.data = O.d_data.as<double>(); MA.weight = O.d_weight.as<double>();
-  MA.seg_first = O.d_seg.as<int64_t>(); MA.mom = h->d_mom.as<double>();
-  MA.npix = O.npix; MA.nseg = O.nseg; MA.nrows = (int64_t)O.nexp * O.nseg;
-  const int64_t blocks = (MA.nrows + kMomWaves - 1) / kMomWaves;
-  const size_t cells = sizeof(double) * (size_t)O.nexp * (size_t)O.npix;
-  // (every address the kernel reads or writes: pairs, data and weights over [nexp][npix] -- the segments lie in [0, npix),
-  // checked when the set was made --, the gains, the segment bounds, the rows)
-  if (!MA.pairs || !MA.data || !MA.seg_first || !MA.mom || O.nexp < 1 || O.nseg < 1 || O.npix != px->set->npix || O.nexp != px->nshift ||
-      X.pairs != (int64_t)O.nexp * O.npix || h->d_pixout.bytes < X.pair_bytes || (px->hp && (px->hpx.pairs != X.pairs || h->d_pixhp.bytes < px->hpx.pair_bytes)) || O.d_data.bytes < cells || (MA.weight && O.d_weight.bytes < cells) ||
-      (MA.gain && O.d_gain.bytes < sizeof(double) * (size_t)O.npix) || O.d_seg.bytes < sizeof(int64_t) * ((size_t)O.nseg + 1) ||
-      X.rows != MA.nrows || h->d_mom.bytes < X.mom_bytes || blocks < 1 || blocks > 0x7fffffffLL ||
-      (px->filt && (!MA.val || X.val_bytes < 1 || h->d_pixval.bytes < X.val_bytes)))
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the moment kernel (not launched)");
-  if (px->filt) hipLaunchKernelGGL(k_pixel_moments<true>, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
-  else hipLaunchKernelGGL(k_pixel_moments<false>, dim3((unsigned)blocks), dim3(64 * kMomWaves), 0, tst, MA);
-  return TRX_OK;
-}
-
 // ---- results back: the copies, the wait, and (direct tail) the flags summed on the host
 int Run::results()
 {
@@ -3024,16 +2434,6 @@ int Run::results()
   std::memcpy(status, (const char *)h->h_small.p + 64, sizeof(status));
   if (count) std::memcpy(counters.data(), (const char *)h->h_small.p + 128, 24 * (size_t)nr);      // (else: zero, as made)
   return TRX_OK;
-}
-
-// ---- what the run makes of this pass's spectrum (want), all of it on the spectrum's queue.  The order is a dependency:
-// the bands and contributions read the spectrum and the optical depths only, but the broadening writes d_broad, which the
-// pixels then sample; the high-pass reads the pixels' pairs and writes its own, which stand in for them from there on; the
-// filter reads the pairs; the moments (or the trail) read the pairs or the filter's values.
-int Run::product_kernels()
-{
-  int rc;
-  return (rc = band_kernels()) || (rc = broaden_kernel()) || (rc = pixel_kernels()) || (rc = highpass_kernels()) || (rc = filter_kernels()) || (rc = moment_kernels()) ? rc : TRX_OK;
 }
 
 // ---- one pass: the planned steps (h->run_plan) from r_top down, the spectrum of what they swept, its way back
@@ -3220,1308 +2620,7 @@ int trx_run_device(trx_handle *h, const trx_atm *a, const trx_opts *o, void *d_s
   return run_once(h, a, o, nullptr, d_spectrum, dbg, Products{});
 }
 
-// ---- the run products: their checks, layouts and extents are ../trx_products.h's; here they meet the handle and the device
-// what that header's checks need to know of h
-static ProductState product_state(const trx_handle *h)
-{
-  ProductState S;
-  S.windowed = h->windowed(); S.wn_i = h->wn_i; S.wn_d = h->wn_d; S.nwn = h->nwn; S.lo = h->lo; S.hi = h->hi;
-  if (h->pixels) S.npix = h->pixels->npix;
-  if (h->observed) { S.nexp = h->observed->nexp; S.nseg = h->observed->nseg; S.seg = h->observed->seg.data(); }
-  S.filter = h->filter != nullptr; S.highpass = h->highpass != nullptr; S.exposures = h->exposures != nullptr;
-  return S;
-}
-
-// ---- band integrals (trx_bands.hip.h) -------------------------------------------------------------
-// The set as h's shard sees it (band_layout), checked whole before anything is replaced.
-static int make_band_set(trx_handle *h, int32_t nbands, const trx_band *bands, std::unique_ptr<BandSet> &out)
-{
-  out.reset();
-  std::string msg; BandLayout L;
-  if (const int rc = band_layout(product_state(h), nbands, bands, L, msg)) return fail(h, rc, msg);
-  if (nbands == 0) return TRX_OK;                       // (clear)
-  std::unique_ptr<BandSet> S(new (std::nothrow) BandSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "bands: out of host memory");
-  S->nbands = nbands; S->npieces = (int64_t)L.pieces.size();
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload(h, S->d_bands, L.bands)) || (rc = upload(h, S->d_pieces, L.pieces)) ||
-      (rc = upload(h, S->d_w, L.w)) || (rc = ensure(h, S->d_part, sizeof(double) * 2 * (size_t)S->npieces)) ||
-      (rc = ensure_pinned(h, S->h_out, sizeof(double) * 2 * (size_t)nbands)))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
-  out = std::move(S);
-  return TRX_OK;
-}
-
-static void install_band_set(trx_handle *h, std::unique_ptr<BandSet> &S) { h->bands = std::move(S); }
-
-int trx_set_bands(trx_handle *h, int32_t nbands, const trx_band *bands)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<BandSet> S;
-  if (const int rc = make_band_set(h, nbands, bands, S)) return rc;
-  install_band_set(h, S);
-  return TRX_OK;
-}
-
-int trx_run_bands(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, double *sums, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  if (!h->bands) return fail(h, TRX_E_ARG, "trx_run_bands: no band set installed (trx_set_bands)");
-  if (!sums) return fail(h, TRX_E_ARG, "trx_run_bands: sums is NULL");
-  Products want; want.bs = h->bands.get();
-  const int rc = run_once(h, a, o, spectrum, nullptr, dbg, want);
-  if (rc == TRX_OK) std::memcpy(sums, h->bands->h_out.p, sizeof(double) * 2 * (size_t)h->bands->nbands);
-  return rc;
-}
-
-// ---- contribution functions per band and layer (trx_contrib.hip.h) --------------------------------
-int trx_run_contrib(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, double *sums, double *contrib, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  if (!h->bands) return fail(h, TRX_E_ARG, "trx_run_contrib: no band set installed (trx_set_bands)");
-  if (!sums) return fail(h, TRX_E_ARG, "trx_run_contrib: sums is NULL");
-  if (!contrib) return fail(h, TRX_E_ARG, "trx_run_contrib: contrib is NULL");
-  if (!a || !o) return TRX_E_ARG;
-  if (a->nlayer < 1) return fail(h, TRX_E_ARG, "trx_run_contrib: nlayer < 1");
-  const BandSet *bs = h->bands.get();
-  const ContribExtents X = contrib_extents(a->nlayer, bs->npieces, bs->nbands);
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = ensure(h, h->d_cpart, X.cpart_bytes)) || (rc = ensure_pinned(h, h->h_contrib, X.out_bytes))) return rc;
-  Products want; want.bs = bs; want.contrib = true;
-  rc = run_once(h, a, o, spectrum, nullptr, dbg, want);
-  if (rc == TRX_OK) {
-    std::memcpy(sums, bs->h_out.p, sizeof(double) * 2 * (size_t)bs->nbands);
-    std::memcpy(contrib, h->h_contrib.p, X.out_bytes);
-  }
-  return rc;
-}
-
-// ---- detector pixels at Doppler shifts (trx_pixels.hip.h) ------------------------------------------
-// The set, checked whole before anything is replaced; the device gets the arrays as they are.
-static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<PixelSet> &out)
-{
-  out.reset();
-  if (!px || px->npix == 0) return TRX_OK;              // (clear)
-  std::string msg;
-  if (const int rc = pixel_set_checks(px, msg)) return fail(h, rc, msg);
-  std::unique_ptr<PixelSet> S(new (std::nothrow) PixelSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "pixels: out of host memory");
-  S->npix = px->npix; S->cut = px->cut;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload_raw(h, S->d_centre, px->centre, (size_t)px->npix)) || (rc = upload_raw(h, S->d_fwhm, px->fwhm, (size_t)px->npix))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
-  out = std::move(S);
-  return TRX_OK;
-}
-
-// (the observed set belongs to the pixel set it was installed over, the filter, the high-pass and the exposure table to the
-// observed set: they go with it -- the high-pass first, which points into the observed set)
-static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->highpass.reset(); h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); h->exposures.reset(); }
-static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->highpass.reset(); h->observed = std::move(S); h->filter.reset(); h->exposures.reset(); }
-
-int trx_set_pixels(trx_handle *h, const trx_pixels *px)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<PixelSet> S;
-  if (const int rc = make_pixel_set(h, px, S)) return rc;
-  install_pixel_set(h, S);
-  return TRX_OK;
-}
-
-// the pixel run PR for `who` (trx_run_pixels; PR.obs: trx_run_moments; PR.filt: trx_run_filtered_moments; PR.trail: trx_run_trail,
-// the shifts its lags; PR.hp: trx_run_highpassed) at PR.nshift shifts: the pairs are in h->d_pixout, the moments in h->d_mom,
-// the filtered values in h->d_pixval, the trail in h->d_trail, when it returns -- each over its extent in PR.ext --, the
-// high-passed pairs (a run with PR.hp, given or taken from the handle here) in h->d_pixhp over PR.hpx
-static int pixel_run(trx_handle *h, const char *who, const trx_atm *a, const trx_opts *o, double *spectrum, PixelRun &PR, const double *shift,
-                     trx_debug *dbg)
-{
-  std::string msg;
-  if (const int rc = pixel_run_checks(who, PR.nshift, PR.set->npix, shift, msg)) return fail(h, rc, msg);
-  const PixelExtents &X = PR.ext = pixel_extents(PR.set->npix, PR.nshift, PR.obs ? PR.obs->nexp : 0, PR.obs ? PR.obs->nseg : 0, PR.filt != nullptr, PR.trail);
-  // (every run against the observed set takes the high-pass installed over it)
-  if (PR.obs && h->highpass) PR.hp = h->highpass.get();
-  if (PR.hp) PR.hpx = highpass_extents(PR.hp->npix, PR.nshift, PR.hp->ntiles, PR.hp->half);
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  // (the shifts go ahead of the run's own inputs on its main queue; every queue of the run waits for those)
-  if ((rc = ensure(h, h->d_pixout, X.pair_bytes)) || (X.mom_bytes && (rc = ensure(h, h->d_mom, X.mom_bytes))) ||
-      (X.trail_bytes && (rc = ensure(h, h->d_trail, X.trail_bytes))) || (X.val_bytes && (rc = ensure(h, h->d_pixval, X.val_bytes))) ||
-      (PR.hp && (rc = ensure(h, h->d_pixhp, PR.hpx.pair_bytes))) ||
-      (h->broad_on && (rc = ensure(h, h->d_broad, broadened_bytes(h->nwn)))) ||
-      (rc = upload_raw(h, h->d_pixshift, shift, (size_t)PR.nshift)))
-    return rc;
-  // (the exposure table with them: it changes from call to call, as the shifts do)
-  if (PR.ex && ((!PR.ex->scale.empty() && (rc = upload(h, h->d_exscale, PR.ex->scale))) || (!PR.ex->smear.empty() && (rc = upload(h, h->d_exsmear, PR.ex->smear)))))
-    return rc;
-  // (with a broadening installed the pixels sample the broadened spectrum)
-  Products want; want.px = &PR; if (h->broad_on) want.br = &h->broad;
-  return run_once(h, a, o, spectrum, nullptr, dbg, want);
-}
-
-int trx_run_pixels(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                   double *out, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  if (!h->pixels) return fail(h, TRX_E_ARG, "trx_run_pixels: no pixel set installed (trx_set_pixels)");
-  if (nshift < 1) return fail(h, TRX_E_ARG, "trx_run_pixels: nshift < 1");
-  if (!shift) return fail(h, TRX_E_ARG, "trx_run_pixels: shift is NULL");
-  if (!out) return fail(h, TRX_E_ARG, "trx_run_pixels: out is NULL");
-  PixelRun PR{h->pixels.get(), nshift};
-  if (const int rc = pixel_run(h, "trx_run_pixels", a, o, spectrum, PR, shift, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, PR.ext.pair_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
-  return TRX_OK;
-}
-
-// ---- cross-correlation moments of the pixels against observed data (trx_moments.hip.h) -------------
-// The set, checked whole before anything is replaced; the device gets the arrays as they are.
-static int make_observed_set(trx_handle *h, const trx_observed *ob, std::unique_ptr<ObservedSet> &out)
-{
-  out.reset();
-  if (!ob || ob->nexp == 0) return TRX_OK;              // (clear)
-  std::string msg;
-  if (const int rc = observed_set_checks(product_state(h), ob, msg)) return fail(h, rc, msg);
-  const int64_t npix = h->pixels->npix;
-  const size_t cells = (size_t)ob->nexp * (size_t)npix;
-  std::unique_ptr<ObservedSet> S(new (std::nothrow) ObservedSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "observed: out of host memory");
-  S->nexp = ob->nexp; S->nseg = ob->nseg; S->npix = npix;
-  try { S->seg.assign(ob->seg_first, ob->seg_first + ob->nseg + 1); } catch (...) { return fail(h, TRX_E_NOMEM, "observed: out of host memory"); }
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload_raw(h, S->d_seg, ob->seg_first, (size_t)ob->nseg + 1)) || (rc = upload_raw(h, S->d_data, ob->data, cells)) ||
-      (ob->weight && (rc = upload_raw(h, S->d_weight, ob->weight, cells))) || (ob->gain && (rc = upload_raw(h, S->d_gain, ob->gain, (size_t)npix))))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the caller's arrays may go once this returns)
-  out = std::move(S);
-  return TRX_OK;
-}
-
-int trx_set_observed(trx_handle *h, const trx_observed *ob)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<ObservedSet> S;
-  if (const int rc = make_observed_set(h, ob, S)) return rc;
-  install_observed_set(h, S);
-  return TRX_OK;
-}
-
-int trx_run_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                    double *mom, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  std::string msg;
-  if (const int rc = observed_run_checks(product_state(h), "trx_run_moments", ObservedRun::Moments, nshift, shift, mom, "mom", msg)) return fail(h, rc, msg);
-  PixelRun PR{h->pixels.get(), nshift, h->observed.get()}; PR.ex = h->exposures.get();
-  if (const int rc = pixel_run(h, "trx_run_moments", a, o, spectrum, PR, shift, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
-  return TRX_OK;
-}
-
-// ---- the exposure table: a scale and a Doppler smear per exposure, in the pixel stage (trx_pixels.hip.h) ----
-// The table as h would keep it, checked whole before anything is replaced (null: a clearing call); the arrays stay on the host.
-static int make_exposure_set(trx_handle *h, const trx_exposures *ex, std::unique_ptr<ExposureSet> &out)
-{
-  out.reset();
-  if (!ex || ex->nexp == 0) return TRX_OK;              // (clear)
-  std::string msg;
-  if (const int rc = exposure_set_checks(product_state(h), ex, msg)) return fail(h, rc, msg);
-  std::unique_ptr<ExposureSet> S(new (std::nothrow) ExposureSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "exposures: out of host memory");
-  S->nexp = ex->nexp;
-  try {
-    if (ex->scale) S->scale.assign(ex->scale, ex->scale + ex->nexp);
-    if (ex->smear) S->smear.assign(ex->smear, ex->smear + ex->nexp);
-  } catch (...) { return fail(h, TRX_E_NOMEM, "exposures: out of host memory"); }
-  out = std::move(S);
-  return TRX_OK;
-}
-
-int trx_set_exposures(trx_handle *h, const trx_exposures *ex)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<ExposureSet> S;
-  if (const int rc = make_exposure_set(h, ex, S)) return rc;
-  h->exposures = std::move(S);
-  return TRX_OK;
-}
-
-int trx_run_exposed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                    double *out, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  std::string msg;
-  if (const int rc = exposed_run_checks(product_state(h), "trx_run_exposed", nshift, shift, out, msg)) return fail(h, rc, msg);
-  // (the pairs alone: no moments, and no high-pass -- a run of the pixel stage, as trx_run_pixels is)
-  PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
-  if (const int rc = pixel_run(h, "trx_run_exposed", a, o, spectrum, PR, shift, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(out, h->d_pixout.p, PR.ext.pair_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
-  return TRX_OK;
-}
-
-// ---- the cross-correlation trail: every exposure against every lag of a grid (trx_trail.hip.h) -----
-int trx_run_trail(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nlag, const double *lag,
-                  double *trail, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  std::string msg;
-  if (const int rc = trail_run_checks(product_state(h), "trx_run_trail", nlag, lag, trail, "trail", msg)) return fail(h, rc, msg);
-  // (an installed filter takes no part: it couples the exposures, and a trail's model is the same at all of them)
-  PixelRun PR{h->pixels.get(), nlag, h->observed.get()}; PR.trail = true;
-  if (const int rc = pixel_run(h, "trx_run_trail", a, o, spectrum, PR, lag, dbg)) return rc;
-  HIPCHK(h, hipMemcpy(trail, h->d_trail.p, PR.ext.trail_bytes, hipMemcpyDeviceToHost));      // (the run has been waited for)
-  return TRX_OK;
-}
-
-// ---- the Kp-Vsys map of that trail, reduced on the device (trx_vmap.hip.h) --------------------------
-// the statistic of PR's trail (in h->d_trail, the run waited for) and the map of it, behind the upload of the call's arrays
-// on the main queue: X their extents, the arrays at X.at_* of h->d_vm_in
-static int launch_velocity_map(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const VmapExtents &X)
-{
-  const ObservedSet *ob = PR.obs;
-  const double *in = h->d_vm_in.as<double>();
-  TrailStatArgs SA{};
-  SA.trail = h->d_trail.as<double>(); SA.per_lv = h->d_vm_per.as<double>(); SA.per_vl = SA.per_lv + X.rows;
-  SA.nrows = (int64_t)X.rows; SA.nlag = vm->nlag; SA.nexp = ob->nexp; SA.nseg = ob->nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
-  VelMapArgs MA{};
-  MA.per_vl = SA.per_vl; MA.lag_kms = in; MA.kp = in + X.at_kp; MA.vsys = in + X.at_vsys; MA.orbit = in + X.at_orbit; MA.offset = vm->offset ? in + X.at_offset : nullptr;
-  MA.map = h->d_vm_map.as<double>(); MA.ncells = (int64_t)X.cells; MA.nlag = vm->nlag; MA.nexp = ob->nexp; MA.nvsys = vm->nvsys;
-  const int64_t sblocks = (SA.nrows + kVmapWaves - 1) / kVmapWaves, mblocks = (MA.ncells + kVmapWaves - 1) / kVmapWaves;
-  // (every address the kernels read or write: the trail rows [nlag][nexp][nseg], the statistic twice over [nlag][nexp], the
-  // call's arrays -- a cell's lag indices lie in [0, nlag - 1], vmap_locate --, the cells)
-  if (!SA.trail || !SA.per_lv || !in || !MA.map || X.rows < 1 || X.cells < 1 || ob->nseg < 1 ||
-      PR.ext.rows != SA.nrows * ob->nseg || h->d_trail.bytes < PR.ext.trail_bytes || h->d_vm_per.bytes < X.per2_bytes ||
-      h->d_vm_in.bytes < X.in_bytes || h->d_vm_map.bytes < X.map_bytes ||
-      sblocks < 1 || sblocks > 0x7fffffffLL || mblocks < 1 || mblocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the map kernels (not launched)");
-  hipLaunchKernelGGL(k_trail_stat, dim3((unsigned)sblocks), dim3(64 * kVmapWaves), 0, h->stream, SA);
-  hipLaunchKernelGGL(k_velocity_map, dim3((unsigned)mblocks), dim3(64 * kVmapWaves), 0, h->stream, MA);
-  HIPCHK(h, hipGetLastError());
-  return TRX_OK;
-}
-
-int trx_run_velocity_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, double *per,
-                         trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  const char *const who = "trx_run_velocity_map";
-  std::string msg;
-  if (const int rc = velocity_map_checks(product_state(h), who, vm, map, msg)) return fail(h, rc, msg);
-  const VmapExtents X = vmap_extents(*vm, h->observed->nexp);
-  if (const int rc = vmap_pack(who, *vm, X, h->vm_in, msg)) return fail(h, rc, msg);
-  // the trail of the lags into d_trail, as trx_run_trail leaves it; it stays there
-  PixelRun PR{h->pixels.get(), vm->nlag, h->observed.get()}; PR.trail = true;
-  if (const int rc = pixel_run(h, who, a, o, spectrum, PR, vm->lag, dbg)) return rc;
-  int rc;
-  // (the run has been waited for: the two kernels follow the upload on the main queue)
-  if ((rc = ensure(h, h->d_vm_per, X.per2_bytes)) || (rc = ensure(h, h->d_vm_map, X.map_bytes)) || (rc = upload(h, h->d_vm_in, h->vm_in)) ||
-      (rc = launch_velocity_map(h, PR, vm, X)))
-    return rc;
-  HIPCHK(h, hipMemcpyAsync(map, h->d_vm_map.p, X.map_bytes, hipMemcpyDeviceToHost, h->stream));
-  if (per) HIPCHK(h, hipMemcpyAsync(per, h->d_vm_per.p, X.per_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return TRX_OK;
-}
-
-// ---- the detrending filter between the pairs and the moments (trx_filter.hip.h) ---------------------
-// The filter, checked whole before anything is replaced; the device gets filter_layout's matrices and tiles.
-static int make_filter_set(trx_handle *h, const trx_filter *f, std::unique_ptr<FilterSet> &out)
-{
-  out.reset();
-  if (!f || f->ncomp == 0) return TRX_OK;               // (clear)
-  const ProductState P = product_state(h);
-  std::string msg; FilterLayout L;
-  if (const int rc = filter_set_checks(P, f, msg)) return fail(h, rc, msg);
-  std::unique_ptr<FilterSet> S(new (std::nothrow) FilterSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "filter: out of host memory");
-  if (const int rc = filter_layout(P, f, L, msg)) return fail(h, rc, msg);
-  S->ncomp = f->ncomp; S->npad = L.npad; S->nexp = P.nexp; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size();
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload(h, S->d_fwd, L.fwd)) || (rc = upload(h, S->d_back, L.back)) || (rc = upload(h, S->d_tiles, L.tiles))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
-  out = std::move(S);
-  return TRX_OK;
-}
-
-static void install_filter_set(trx_handle *h, std::unique_ptr<FilterSet> &S) { h->filter = std::move(S); }
-
-int trx_set_filter(trx_handle *h, const trx_filter *f)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<FilterSet> S;
-  if (const int rc = make_filter_set(h, f, S)) return rc;
-  install_filter_set(h, S);
-  return TRX_OK;
-}
-
-// Every column's factor and pivot flag of the weighted filter S over the observed set O against `weight` ([nexp][npix] of
-// weight_bytes, or null: all 1), into fac and live (grown to size): k_wfilter_factor from S's own basis and tiles, which are
-// on the device.  The flags come back once for the count of the singular columns.  trx_set_weighted_filter installs with
-// it; trx_weigh_observed makes an installed filter's factor again against other weights, in buffers of its own.
-static int factor_wfilter(trx_handle *h, const FilterSet &S, const ObservedSet *O, const double *weight, size_t weight_bytes, DevBuf &fac, DevBuf &live,
-                          int64_t *nsingular)
-{
-  if (nsingular) *nsingular = 0;
-  const WfilterExtents WX = wfilter_extents(S.npix, S.nexp, S.nseg, S.ncomp, S.npad, S.ntiles, kFiltWaves);
-  std::vector<int32_t> flags;
-  try { flags.assign((size_t)S.npix, 0); } catch (...) { return fail(h, TRX_E_NOMEM, "weighted filter: out of host memory"); }
-  int rc;
-  if ((rc = ensure(h, fac, WX.fac_bytes)) || (rc = ensure(h, live, WX.live_bytes))) return rc;
-  // (a pixel outside every tile -- none: the segments cover [0, npix) -- would keep a zero factor and a zero flag)
-  HIPCHK(h, hipMemsetAsync(fac.p, 0, WX.fac_bytes, h->stream));
-  HIPCHK(h, hipMemsetAsync(live.p, 0, WX.live_bytes, h->stream));
-  WfilterFactorArgs A{};
-  A.weight = weight; A.basis = S.d_back.as<double>(); A.tiles = S.d_tiles.as<FilterTile>();
-  A.fac = fac.as<double>(); A.live = live.as<int32_t>(); A.npix = S.npix; A.ntiles = S.ntiles; A.nexp = S.nexp; A.ncomp = S.ncomp;
-  // (every address the kernel reads or writes: the padded basis, the tiles -- the segments cover [0, npix): at least one --,
-  // the weights, the factor and the flags)
-  if (!O || !S.weighted || !A.basis || !A.tiles || S.nexp < 1 || S.nseg < 1 || S.ncomp < 1 || S.ncomp > S.npad || (S.npad != 4 && S.npad != 8 && S.npad != 16) ||
-      S.npix < 1 || S.ntiles < 1 || S.npix != O->npix || S.nexp != O->nexp || S.nseg != O->nseg || S.nfac != WX.nfac || S.d_back.bytes < WX.basis_bytes ||
-      S.d_tiles.bytes < sizeof(FilterTile) * (size_t)S.ntiles || (weight && weight_bytes < sizeof(double) * (size_t)S.nexp * (size_t)S.npix) ||
-      fac.bytes < WX.fac_bytes || live.bytes < WX.live_bytes || WX.blocks < 1 || WX.blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the weighted filter's factor kernel (not launched)");
-  const dim3 grid((unsigned)WX.blocks), block(64 * kFiltWaves);
-  if (S.npad == 4) hipLaunchKernelGGL(k_wfilter_factor<4>, grid, block, 0, h->stream, A);
-  else if (S.npad == 8) hipLaunchKernelGGL(k_wfilter_factor<8>, grid, block, 0, h->stream, A);
-  else hipLaunchKernelGGL(k_wfilter_factor<16>, grid, block, 0, h->stream, A);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(flags.data(), live.p, WX.live_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vector goes when this returns)
-  if (nsingular) for (int32_t x : flags) *nsingular += x ? 0 : 1;
-  return TRX_OK;
-}
-
-// The weighted filter (trx_wfilter.hip.h), checked whole before anything is replaced: the device gets wfilter_layout's basis
-// and tiles, and factor_wfilter makes every column's factor and flag from them and the weights w -- null: the observed
-// set's weights in force (trx_set_weighted_filter); trx_detrend_observed gives the weights as trx_set_observed installed them.
-static int make_wfilter_set(trx_handle *h, const trx_wfilter *f, std::unique_ptr<FilterSet> &out, int64_t *nsingular, const DevBuf *w = nullptr)
-{
-  out.reset();
-  if (nsingular) *nsingular = 0;
-  if (!f || f->ncomp == 0) return TRX_OK;               // (clear)
-  const ProductState P = product_state(h);
-  std::string msg; WfilterLayout L;
-  if (const int rc = wfilter_set_checks(P, f, msg)) return fail(h, rc, msg);
-  std::unique_ptr<FilterSet> S(new (std::nothrow) FilterSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "weighted filter: out of host memory");
-  if (const int rc = wfilter_layout(P, f, L, msg)) return fail(h, rc, msg);
-  S->weighted = true;
-  S->ncomp = f->ncomp; S->npad = L.npad; S->nexp = P.nexp; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size();
-  S->nfac = wfilter_extents(S->npix, S->nexp, S->nseg, S->ncomp, S->npad, S->ntiles, kFiltWaves).nfac;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload(h, S->d_back, L.basis)) || (rc = upload(h, S->d_tiles, L.tiles))) return rc;
-  const ObservedSet *O = h->observed.get();
-  if (!w && O) w = &O->d_weight;
-  // (factor_wfilter waits for the queue: the staging vectors may go when it returns)
-  if ((rc = factor_wfilter(h, *S, O, w ? w->as<double>() : nullptr, w ? w->bytes : 0, S->d_fac, S->d_live, nsingular))) return rc;
-  out = std::move(S);
-  return TRX_OK;
-}
-
-int trx_set_weighted_filter(trx_handle *h, const trx_wfilter *f, int64_t *nsingular)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<FilterSet> S;
-  if (const int rc = make_wfilter_set(h, f, S, nsingular)) return rc;
-  install_filter_set(h, S);
-  return TRX_OK;
-}
-
-int trx_run_filtered_moments(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                             double *values, double *mom, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  std::string msg;
-  if (const int rc = observed_run_checks(product_state(h), "trx_run_filtered_moments", ObservedRun::Filtered, nshift, shift, mom, "mom", msg)) return fail(h, rc, msg);
-  PixelRun PR{h->pixels.get(), nshift, h->observed.get(), h->filter.get()}; PR.ex = h->exposures.get();
-  if (const int rc = pixel_run(h, "trx_run_filtered_moments", a, o, spectrum, PR, shift, dbg)) return rc;
-  // (the run has been waited for)
-  HIPCHK(h, hipMemcpy(mom, h->d_mom.p, PR.ext.mom_bytes, hipMemcpyDeviceToHost));
-  if (values) HIPCHK(h, hipMemcpy(values, h->d_pixval.p, PR.ext.val_bytes, hipMemcpyDeviceToHost));
-  return TRX_OK;
-}
-
-// ---- the high-pass between the pairs and whatever reads them (trx_highpass.hip.h) -------------------
-// The high-pass, checked whole before anything is replaced; the device gets highpass_layout's taps and tiles.
-static int make_highpass_set(trx_handle *h, const trx_highpass *hp, std::unique_ptr<HighPassSet> &out)
-{
-  out.reset();
-  if (!hp || !hp->taps) return TRX_OK;                  // (clear)
-  const ProductState P = product_state(h);
-  std::string msg; HighpassLayout L;
-  if (const int rc = highpass_set_checks(P, hp, msg)) return fail(h, rc, msg);
-  std::unique_ptr<HighPassSet> S(new (std::nothrow) HighPassSet);
-  if (!S) return fail(h, TRX_E_NOMEM, "highpass: out of host memory");
-  if (const int rc = highpass_layout(P, hp, L, msg)) return fail(h, rc, msg);
-  S->half = L.half; S->nseg = P.nseg; S->npix = P.npix; S->ntiles = (int64_t)L.tiles.size(); S->den_full = L.den_full; S->obs = h->observed.get();
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload(h, S->d_taps, L.taps)) || (rc = upload(h, S->d_tiles, L.tiles))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging vectors go when this returns)
-  out = std::move(S);
-  return TRX_OK;
-}
-
-static void install_highpass_set(trx_handle *h, std::unique_ptr<HighPassSet> &S) { h->highpass = std::move(S); }
-
-int trx_set_highpass(trx_handle *h, const trx_highpass *hp)
-{
-  if (!h) return TRX_E_ARG;
-  std::unique_ptr<HighPassSet> S;
-  if (const int rc = make_highpass_set(h, hp, S)) return rc;
-  install_highpass_set(h, S);
-  return TRX_OK;
-}
-
-int trx_run_highpassed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                       double *values, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  std::string msg;
-  if (const int rc = observed_run_checks(product_state(h), "trx_run_highpassed", ObservedRun::Highpassed, nshift, shift, values, "values", msg)) return fail(h, rc, msg);
-  // (no moments: the observed set only lends the high-pass its segments and gains)
-  PixelRun PR{h->pixels.get(), nshift}; PR.hp = h->highpass.get();
-  if (const int rc = pixel_run(h, "trx_run_highpassed", a, o, spectrum, PR, shift, dbg)) return rc;
-  // (the run has been waited for) the pairs whole -- into pinned memory grown once the run's checks have passed its size --,
-  // then their first components: (g', 1) is g', (0, 0) is a dead pixel
-  if (const int rc = ensure_pinned(h, h->h_pixhp, PR.hpx.pair_bytes)) return rc;
-  HIPCHK(h, hipMemcpy(h->h_pixhp.p, h->d_pixhp.p, PR.hpx.pair_bytes, hipMemcpyDeviceToHost));
-  const double *const ab = (const double *)h->h_pixhp.p; const double nan = __builtin_nan("");
-  for (int64_t k = 0; k < PR.hpx.pairs; k++) values[k] = ab[2 * k + 1] > 0.0 ? ab[2 * k] : nan;
-  return TRX_OK;
-}
-
-// ---- the Kp-Vsys map with the filter applied to every cell's own model matrix (trx_cellmap.hip.h) ---
-// the index table of the call's cells (k_cell_tracks) into h->d_cm_index, behind the upload of the call's arrays on the main
-// queue.  VX: the extents of the call's arrays at VX.at_* of h->d_vm_in; CX: those of the cell buffers.
-static int launch_cell_tracks(trx_handle *h, const trx_vmap *vm, const VmapExtents &VX, const CellMapExtents &CX)
-{
-  const ObservedSet *O = h->observed.get();
-  const double *in = h->d_vm_in.as<double>();
-  if (!O || !in) return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell track kernel (not launched)");
-  const int32_t nlag = vm->nlag, nexp = O->nexp;
-  CellTrackArgs TA{};
-  TA.lag_kms = in; TA.kp = in + VX.at_kp; TA.vsys = in + VX.at_vsys; TA.orbit = in + VX.at_orbit; TA.offset = vm->offset ? in + VX.at_offset : nullptr;
-  TA.index = h->d_cm_index.as<int32_t>(); TA.ntracks = CX.tracks; TA.nlag = nlag; TA.nexp = nexp; TA.nvsys = vm->nvsys;
-  // (every address the kernel reads or writes: the call's arrays -- a track's cell below nkp * nvsys, its exposure below
-  // nexp --, the bisection inside lag_kms [nlag], the table over [cells][nexp])
-  if (!TA.index || nlag < 1 || nexp < 1 || vm->nvsys < 1 || vm->nkp < 1 || CX.cells != (int64_t)vm->nkp * vm->nvsys || (int64_t)VX.cells != CX.cells ||
-      CX.tracks != CX.cells * nexp || CX.tracks > 0x7fffffffLL || h->d_vm_in.bytes < VX.in_bytes || VX.at_kp != (size_t)nlag ||
-      VX.at_offset - VX.at_orbit != (size_t)nexp || h->d_cm_index.bytes < CX.index_bytes || CX.index_bytes < sizeof(int32_t) * (size_t)CX.tracks ||
-      CX.track_blocks < 1 || CX.track_blocks > 0x7fffffffLL || CX.track_blocks * kCellTrackBlock < CX.tracks)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell track kernel (not launched)");
-  hipLaunchKernelGGL(k_cell_tracks, dim3((unsigned)CX.track_blocks), dim3(kCellTrackBlock), 0, h->stream, TA);
-  return TRX_OK;
-}
-
-// chunk after chunk the filter, the moments and the statistic of the cells, each cell's rows of PR's pairs named by its
-// entries of `table` [cells][nexp]: the lag table (trx_run_filtered_map: nrow = nlag rows) or the row table of an exposed
-// map (nrow = R rows), every entry -1 or in [0, nrow)
-static int launch_cell_chunks(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const CellMapExtents &CX, const DevBuf &table, int64_t nrow)
-{
-  const ObservedSet *O = h->observed.get(); const FilterSet *F = h->filter.get();
-  if (!O || !F || !table.p || table.bytes < CX.index_bytes || CX.index_bytes < sizeof(int32_t) * (size_t)CX.tracks)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
-  const int32_t nexp = O->nexp, nseg = O->nseg;
-  const int64_t npix = O->npix;
-  const int32_t *const index = table.as<int32_t>();
-  CellFilterArgs FA{};
-  // (with a high-pass: its pairs (g', 1) or (0, 0), the gain in them already)
-  FA.pairs = PR.hp ? h->d_pixhp.as<double2>() : h->d_pixout.as<double2>(); FA.gain = PR.hp ? nullptr : O->d_gain.as<double>();
-  FA.fwd = F->d_fwd.as<double>(); FA.back = F->d_back.as<double>(); FA.tiles = F->d_tiles.as<FilterTile>(); FA.val = h->d_cm_val.as<double>();
-  FA.npix = npix; FA.ntiles = F->ntiles; FA.nexp = nexp;
-  // (a weighted filter: k_cell_wfilter in k_cell_filter's place, over the same pairs, tiles, index rows and values)
-  const bool wt = F->weighted;
-  WfilterArgs WA{};
-  WA.pairs = FA.pairs; WA.gain = FA.gain; WA.weight = O->d_weight.as<double>(); WA.basis = FA.back; WA.fac = F->d_fac.as<double>();
-  WA.live = F->d_live.as<int32_t>(); WA.tiles = FA.tiles; WA.val = FA.val; WA.npix = npix; WA.ntiles = F->ntiles; WA.nexp = nexp; WA.ncomp = F->ncomp;
-  CellMomArgs MA{};
-  MA.val = FA.val; MA.data = O->d_data.as<double>(); MA.weight = O->d_weight.as<double>(); MA.seg_first = O->d_seg.as<int64_t>();
-  MA.mom = h->d_cm_mom.as<double>(); MA.npix = npix; MA.nexp = nexp; MA.nseg = nseg;
-  CellStatArgs SA{};
-  SA.mom = MA.mom; SA.nexp = nexp; SA.nseg = nseg; SA.stat = vm->stat; SA.p0 = vm->p0; SA.p1 = vm->p1;
-  const size_t mat = sizeof(double) * (size_t)F->nseg * (size_t)F->nexp * (size_t)F->npad;
-  const size_t obs_cells = sizeof(double) * (size_t)nexp * (size_t)npix;
-  // (every address the three kernels read or write, for the largest chunk: the pairs over [nrow][npix] -- a table entry the
-  // filter follows lies in [0, nrow - 1], vmap_nearest or exposed_map_row, and a cell with a -1 is left out by all three --, the tiles in
-  // [0, npix) naming segments below nseg, made so when the filter was, the gains, the two padded matrices; the values over
-  // [chunk][nexp][npix]; data and weights over [nexp][npix], the segments in [0, npix), checked when the set was made; the
-  // moment rows over [chunk][nexp][nseg]; the chunk's cells of the map)
-  if ((wt ? !wfilter_set_complete(*F, *O) : !FA.fwd || F->d_fwd.bytes < mat) ||
-      !FA.pairs || !FA.back || !FA.tiles || !FA.val || !MA.data || !MA.seg_first || !MA.mom || !h->d_cm_map.p ||
-      F->nexp != nexp || F->nseg != nseg || F->npix != npix || npix < 1 || nseg < 1 || npix != PR.set->npix || F->ncomp < 1 || F->ncomp > F->npad ||
-      (F->npad != 4 && F->npad != 8 && F->npad != 16) || F->ntiles < 1 || nrow < 1 || PR.nshift != nrow || PR.filt || PR.trail || PR.obs ||
-      PR.ext.pairs != nrow * npix || h->d_pixout.bytes < PR.ext.pair_bytes || (PR.hp && (PR.hpx.pairs != PR.ext.pairs || h->d_pixhp.bytes < PR.hpx.pair_bytes)) ||
-      F->d_back.bytes < mat || F->d_tiles.bytes < sizeof(FilterTile) * (size_t)F->ntiles ||
-      (FA.gain && O->d_gain.bytes < sizeof(double) * (size_t)npix) || O->d_data.bytes < obs_cells || (MA.weight && O->d_weight.bytes < obs_cells) ||
-      O->d_seg.bytes < sizeof(int64_t) * ((size_t)nseg + 1) || O->seg.size() != (size_t)nseg + 1 || O->seg.front() != 0 || O->seg.back() != npix ||
-      CX.chunk < 1 || CX.nchunks < 1 || CX.last_chunk < 1 || CX.last_chunk > CX.chunk || (CX.nchunks - 1) * CX.chunk + CX.last_chunk != CX.cells ||
-      CX.rows != CX.chunk * nexp * nseg || CX.rows > 0x7fffffffLL ||
-      CX.val_bytes < obs_cells * (size_t)CX.chunk || h->d_cm_val.bytes < CX.val_bytes ||
-      CX.mom_bytes < sizeof(double) * TRX_NMOMENT * (size_t)CX.rows || h->d_cm_mom.bytes < CX.mom_bytes ||
-      CX.map_bytes < sizeof(double) * (size_t)CX.cells || h->d_cm_map.bytes < CX.map_bytes ||
-      (CX.chunk * F->ntiles + kFiltWaves - 1) / kFiltWaves > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell map kernels (not launched)");
-  for (int64_t q = 0; q < CX.nchunks; q++) {
-    const int64_t cell0 = q * CX.chunk, n = q + 1 < CX.nchunks ? CX.chunk : CX.last_chunk;      // cells [cell0, cell0 + n)
-    FA.index = MA.index = SA.index = index + cell0 * nexp;
-    FA.nwaves = n * F->ntiles; MA.nrows = n * nexp * nseg;
-    WA.index = FA.index; WA.nwaves = FA.nwaves;
-    SA.map = h->d_cm_map.as<double>() + cell0; SA.ncells = n;
-    const dim3 fgrid((unsigned)((FA.nwaves + kFiltWaves - 1) / kFiltWaves)), fblock(64 * kFiltWaves);
-    if (wt) {
-      if (F->npad == 4) hipLaunchKernelGGL(k_cell_wfilter<4>, fgrid, fblock, 0, h->stream, WA);
-      else if (F->npad == 8) hipLaunchKernelGGL(k_cell_wfilter<8>, fgrid, fblock, 0, h->stream, WA);
-      else hipLaunchKernelGGL(k_cell_wfilter<16>, fgrid, fblock, 0, h->stream, WA);
-    }
-    else if (F->npad == 4) hipLaunchKernelGGL(k_cell_filter<4>, fgrid, fblock, 0, h->stream, FA);
-    else if (F->npad == 8) hipLaunchKernelGGL(k_cell_filter<8>, fgrid, fblock, 0, h->stream, FA);
-    else hipLaunchKernelGGL(k_cell_filter<16>, fgrid, fblock, 0, h->stream, FA);
-    hipLaunchKernelGGL(k_cell_moments, dim3((unsigned)((MA.nrows + kMomWaves - 1) / kMomWaves)), dim3(64 * kMomWaves), 0, h->stream, MA);
-    hipLaunchKernelGGL(k_cell_stat, dim3((unsigned)((n + kCellStatWaves - 1) / kCellStatWaves)), dim3(64 * kCellStatWaves), 0, h->stream, SA);
-  }
-  HIPCHK(h, hipGetLastError());
-  return TRX_OK;
-}
-
-// The map of PR's rows (the pairs of the lags in h->d_pixout, or h->d_pixhp with a high-pass; the run waited for), behind the
-// upload of the call's arrays on the main queue: the index table once, then the chunks, which follow that table.
-static int launch_filtered_map(trx_handle *h, const PixelRun &PR, const trx_vmap *vm, const VmapExtents &VX, const CellMapExtents &CX)
-{
-  if (const int rc = launch_cell_tracks(h, vm, VX, CX)) return rc;
-  return launch_cell_chunks(h, PR, vm, CX, h->d_cm_index, vm->nlag);
-}
-
-int trx_run_filtered_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, int32_t *lag_index,
-                         trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  const char *const who = "trx_run_filtered_map";
-  std::string msg;
-  if (const int rc = filtered_map_checks(product_state(h), who, vm, map, msg)) return fail(h, rc, msg);
-  const ObservedSet *O = h->observed.get();
-  const VmapExtents VX = vmap_extents(*vm, O->nexp);
-  const CellMapExtents CX = cell_map_extents((int64_t)vm->nkp * vm->nvsys, O->nexp, O->nseg, O->npix);
-  if (const int rc = vmap_pack(who, *vm, VX, h->vm_in, msg)) return fail(h, rc, msg);
-  // one pixel pass of nlag rows, the one trx_run_trail makes -- no moments, no trail; the high-pass when one is installed
-  PixelRun PR{h->pixels.get(), vm->nlag}; PR.hp = h->highpass.get();
-  if (const int rc = pixel_run(h, who, a, o, spectrum, PR, vm->lag, dbg)) return rc;
-  int rc;
-  // (the run has been waited for: the kernels follow the upload on the main queue)
-  if ((rc = ensure(h, h->d_cm_index, CX.index_bytes)) || (rc = ensure(h, h->d_cm_val, CX.val_bytes)) || (rc = ensure(h, h->d_cm_mom, CX.mom_bytes)) ||
-      (rc = ensure(h, h->d_cm_map, CX.map_bytes)) || (rc = upload(h, h->d_vm_in, h->vm_in)) || (rc = launch_filtered_map(h, PR, vm, VX, CX)))
-    return rc;
-  HIPCHK(h, hipMemcpyAsync(map, h->d_cm_map.p, CX.map_bytes, hipMemcpyDeviceToHost, h->stream));
-  if (lag_index) HIPCHK(h, hipMemcpyAsync(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return TRX_OK;
-}
-
-// ---- the Kp-Vsys map under the exposure table: its pixel rows are (lag, exposure) pairs (trx_expmap.hip.h) ----
-// the spans of the lags the inside cells take at every exposure (k_cell_spans), behind k_cell_tracks on the main queue, read
-// back into h->em_span [nexp][2]: the queue is waited for
-static int launch_cell_spans(trx_handle *h, const CellMapExtents &CX, const ExposedMapExtents &EX, int32_t nexp)
-{
-  CellSpanArgs SA{};
-  SA.index = h->d_cm_index.as<int32_t>(); SA.span = h->d_em_span.as<int32_t>(); SA.ncells = CX.cells; SA.nexp = nexp;
-  // (every address the kernel reads or writes: the index table over [cells][nexp], the spans over [nexp][2])
-  if (!SA.index || !SA.span || nexp < 1 || CX.cells < 1 || CX.tracks != CX.cells * nexp || h->d_cm_index.bytes < CX.index_bytes ||
-      CX.index_bytes < sizeof(int32_t) * (size_t)CX.tracks || EX.span_bytes < sizeof(int32_t) * 2 * (size_t)nexp || h->d_em_span.bytes < EX.span_bytes ||
-      EX.span_blocks < 1 || EX.span_blocks > 0x7fffffffLL || EX.span_blocks * kCellSpanWaves < nexp)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell span kernel (not launched)");
-  try { h->em_span.assign(2 * (size_t)nexp, 0); } catch (...) { return fail(h, TRX_E_NOMEM, "trx_run_exposed_map: out of host memory"); }
-  hipLaunchKernelGGL(k_cell_spans, dim3((unsigned)EX.span_blocks), dim3(64 * kCellSpanWaves), 0, h->stream, SA);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(h->em_span.data(), h->d_em_span.p, EX.span_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return TRX_OK;
-}
-
-// the row table of the call's cells (k_cell_rows) into h->d_em_row from the lag table, the spans on the device and the rows'
-// bases L.base, which go up first
-static int launch_cell_rows(trx_handle *h, const CellMapExtents &CX, const ExposedMapExtents &EX, int32_t nexp, const ExposedMapRows &L)
-{
-  if (const int rc = upload(h, h->d_em_base, L.base)) return rc;
-  CellRowArgs RA{};
-  RA.index = h->d_cm_index.as<int32_t>(); RA.span = h->d_em_span.as<int32_t>(); RA.base = h->d_em_base.as<int64_t>(); RA.row = h->d_em_row.as<int32_t>();
-  RA.ntracks = CX.tracks; RA.nexp = nexp;
-  // (every address the kernel reads or writes: the two tables over [cells][nexp], the spans over [nexp][2], the bases over
-  // [nexp] of the [nexp + 1] there are; a row it writes is below base[nexp] = R, an int32 count)
-  if (!RA.index || !RA.span || !RA.base || !RA.row || nexp < 1 || CX.tracks != CX.cells * nexp || CX.tracks < 1 || CX.tracks > 0x7fffffffLL ||
-      h->d_cm_index.bytes < CX.index_bytes || EX.row_bytes < sizeof(int32_t) * (size_t)CX.tracks || h->d_em_row.bytes < EX.row_bytes ||
-      h->d_em_span.bytes < EX.span_bytes || L.base.size() != (size_t)nexp + 1 || h->d_em_base.bytes < sizeof(int64_t) * ((size_t)nexp + 1) ||
-      L.base.back() != L.R || L.R != EX.rows || L.R < 1 || L.R > 0x7fffffffLL ||
-      CX.track_blocks < 1 || CX.track_blocks > 0x7fffffffLL || CX.track_blocks * kCellTrackBlock < CX.tracks)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the cell row kernel (not launched)");
-  hipLaunchKernelGGL(k_cell_rows, dim3((unsigned)CX.track_blocks), dim3(kCellTrackBlock), 0, h->stream, RA);
-  return TRX_OK;
-}
-
-int trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, const trx_vmap *vm, double *map, int32_t *lag_index,
-                        int64_t *nrows, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  const char *const who = "trx_run_exposed_map";
-  std::string msg;
-  if (const int rc = exposed_map_checks(product_state(h), who, vm, map, msg)) return fail(h, rc, msg);
-  if (!a || !o) return TRX_E_ARG;
-  const ObservedSet *O = h->observed.get(); const ExposureSet *T = h->exposures.get();
-  const int32_t nexp = O->nexp;
-  const VmapExtents VX = vmap_extents(*vm, nexp);
-  const CellMapExtents CX = cell_map_extents((int64_t)vm->nkp * vm->nvsys, nexp, O->nseg, O->npix);
-  ExposedMapExtents EX;
-  // (the two tables' extents do not depend on R: no row refuses nothing)
-  if (const int rc = exposed_map_extents(who, 0, O->npix, CX.cells, nexp, EX, msg)) return fail(h, rc, msg);
-  if (const int rc = vmap_pack(who, *vm, VX, h->vm_in, msg)) return fail(h, rc, msg);
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  // the tracks and the spans AHEAD of the pixel pass: they say which (lag, exposure) rows it has to make
-  if ((rc = ensure(h, h->d_cm_index, CX.index_bytes)) || (rc = ensure(h, h->d_em_span, EX.span_bytes)) || (rc = ensure(h, h->d_em_row, EX.row_bytes)) ||
-      (rc = upload(h, h->d_vm_in, h->vm_in)) || (rc = launch_cell_tracks(h, vm, VX, CX)) || (rc = launch_cell_spans(h, CX, EX, nexp)))
-    return rc;
-  ExposedMapRows L;
-  if ((rc = exposed_map_bases(who, h->em_span.data(), nexp, vm->nlag, L, msg)) || (rc = exposed_map_extents(who, L.R, O->npix, CX.cells, nexp, EX, msg)))
-    return fail(h, rc, msg);
-  if (L.R == 0) {
-    // no cell inside the lag grid: the spectrum alone -- no pixel, filter or moment kernel --, and a map of NaN
-    if ((rc = run_once(h, a, o, spectrum, nullptr, dbg, Products{}))) return rc;
-    const double nan = __builtin_nan("");
-    for (int64_t c = 0; c < CX.cells; c++) map[c] = nan;
-    if (lag_index) HIPCHK(h, hipMemcpy(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost));
-    if (nrows) *nrows = 0;
-    return TRX_OK;
-  }
-  if ((rc = exposed_map_row_arrays(who, h->em_span.data(), nexp, vm->lag, T->scale.empty() ? nullptr : T->scale.data(),
-                                   T->smear.empty() ? nullptr : T->smear.data(), L, msg)))
-    return fail(h, rc, msg);
-  // one pixel pass of R rows with a table of their own -- row r's shift, smear and scale --, not the handle's: no moments,
-  // no trail; the high-pass when one is installed
-  ExposureSet rows; rows.nexp = (int32_t)L.R; rows.scale = std::move(L.scale); rows.smear = std::move(L.smear);
-  PixelRun PR{h->pixels.get(), (int32_t)L.R}; PR.hp = h->highpass.get(); PR.ex = &rows; PR.ex_rows = true;
-  // (a call that fails leaves no copy from this call's own arrays -- the rows', the bases -- in flight when they go)
-  auto failed = [&](int code) { (void)hipStreamSynchronize(h->stream); return code; };
-  if ((rc = pixel_run(h, who, a, o, spectrum, PR, L.shift.data(), dbg))) return failed(rc);
-  // (the run has been waited for: the kernels follow on the main queue, the cells' rows named by the row table)
-  if ((rc = ensure(h, h->d_cm_val, CX.val_bytes)) || (rc = ensure(h, h->d_cm_mom, CX.mom_bytes)) || (rc = ensure(h, h->d_cm_map, CX.map_bytes)) ||
-      (rc = launch_cell_rows(h, CX, EX, nexp, L)) || (rc = launch_cell_chunks(h, PR, vm, CX, h->d_em_row, L.R)))
-    return failed(rc);
-  HIPCHK(h, hipMemcpyAsync(map, h->d_cm_map.p, CX.map_bytes, hipMemcpyDeviceToHost, h->stream));
-  if (lag_index) HIPCHK(h, hipMemcpyAsync(lag_index, h->d_cm_index.p, CX.index_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (nrows) *nrows = L.R;
-  return TRX_OK;
-}
-
-// ---- detrending the observed set itself: model injection and SYSREM (trx_sysrem.hip.h) --------------
-static void move_buf(DevBuf &to, DevBuf &from) { to.release(); to.p = from.p; to.bytes = from.bytes; from.p = nullptr; from.bytes = 0; }
-static void swap_buf(DevBuf &a, DevBuf &b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
-
-// the weights as trx_set_observed installed them back in force (trx_weigh_observed's undo, and every successful
-// trx_detrend_observed); a weigh call's buffer is kept for the next one when the handle has none
-static void restore_raw_weights(trx_handle *h, ObservedSet *O)
-{
-  if (!O->weighed) return;
-  DevBuf old; move_buf(old, O->d_weight); move_buf(O->d_weight, O->d_wraw);
-  if (!h->d_sc_w.p) move_buf(h->d_sc_w, old);
-  O->weighed = false;
-}
-
-// the SYSREM kernels of dt over the residuals in h->d_sr_r, on the main queue: X the call's extents, ntiles the tiles in h->d_sr_tiles
-static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend *dt, const SysremExtents &X, int64_t ntiles)
-{
-  SysremArgs A{};
-  A.r = h->d_sr_r.as<double>(); A.weight = O->raw_weight().as<double>(); A.tiles = h->d_sr_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
-  A.a = h->d_sr_a.as<double>(); A.c = h->d_sr_c.as<double>(); A.coef = h->d_sr_coef.as<double>(); A.basis = h->d_sr_basis.as<double>();
-  A.npix = O->npix; A.ntiles = ntiles; A.nrows = X.rows; A.nexp = O->nexp; A.nseg = O->nseg; A.ncomp = dt->ncomp;
-  // (every address the kernels read or write: the residuals and the weights [nexp][npix], the tiles -- which cover [0, npix) --,
-  // the bounds [nseg + 1], a [nseg][nexp], c [npix], coef [ncomp][npix], U [nseg][nexp][ncomp])
-  if (!A.r || !A.tiles || !A.seg_first || !A.a || !A.c || !A.coef || !A.basis || A.npix < 1 || A.nexp < 1 || A.nseg < 1 || ntiles < 1 ||
-      h->d_sr_r.bytes < X.r_bytes || (A.weight && O->raw_weight().bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
-      O->d_seg.bytes < sizeof(int64_t) * ((size_t)O->nseg + 1) || h->d_sr_a.bytes < X.a_bytes || h->d_sr_c.bytes < X.c_bytes ||
-      h->d_sr_coef.bytes < X.coef_bytes || h->d_sr_basis.bytes < X.basis_bytes ||
-      X.tile_blocks < 1 || X.tile_blocks > 0x7fffffffLL || X.row_blocks < 1 || X.row_blocks > 0x7fffffffLL)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the SYSREM kernels (not launched)");
-  // (an empty segment has no tile: its vectors stay zero)
-  HIPCHK(h, hipMemsetAsync(A.basis, 0, X.basis_bytes, h->stream));
-  HIPCHK(h, hipMemsetAsync(A.coef, 0, X.coef_bytes, h->stream));
-  const dim3 tgrid((unsigned)X.tile_blocks), tblock(64 * kFiltWaves), rgrid((unsigned)X.row_blocks), rblock(64 * kMomWaves);
-  for (int32_t i = 0; i < dt->ncomp; i++) {
-    A.comp = i;
-    for (int32_t k = 0; k < dt->niter; k++) {
-      SysremArgs C = A;
-      if (k == 0) C.a = nullptr;                       // (a component starts from a = 1)
-      hipLaunchKernelGGL(k_sysrem_cols, tgrid, tblock, 0, h->stream, C);
-      hipLaunchKernelGGL(k_sysrem_rows, rgrid, rblock, 0, h->stream, A);
-    }
-    hipLaunchKernelGGL(k_sysrem_close, tgrid, tblock, 0, h->stream, A);
-    hipLaunchKernelGGL(k_sysrem_subtract, tgrid, tblock, 0, h->stream, A);
-  }
-  HIPCHK(h, hipGetLastError());
-  return TRX_OK;
-}
-
-int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
-                         const trx_detrend *dt, double *basis, double *coef, double *data, int64_t *nsingular, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  const char *const who = "trx_detrend_observed";
-  const ProductState P = product_state(h);
-  std::string msg;
-  if (const int rc = detrend_checks(P, dt, a, o, nshift, shift, msg)) return fail(h, rc, msg);
-  ObservedSet *const O = h->observed.get();
-  HIPCHK(h, hipSetDevice(h->device));
-  if (detrend_is_undo(dt)) {
-    // (the buffer of the residuals is kept for the next call when the handle has none)
-    if (O->d_raw.p) {
-      DevBuf old; move_buf(old, O->d_data); move_buf(O->d_data, O->d_raw);
-      if (!h->d_sr_r.p) move_buf(h->d_sr_r, old);
-    }
-    restore_raw_weights(h, O);
-    h->filter.reset();
-    if (nsingular) *nsingular = 0;
-    return TRX_OK;
-  }
-  std::vector<FilterTile> tiles;
-  if (const int rc = sysrem_tiles(P, tiles, msg)) return fail(h, rc, msg);
-  const int64_t ntiles = (int64_t)tiles.size();
-  const SysremExtents X = sysrem_extents(O->npix, O->nexp, O->nseg, dt->ncomp, dt->niter, ntiles, kPixBlock, kFiltWaves, kMomWaves);
-  try { h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
-  // the pairs of the injection: the pixel stage alone, as trx_run_exposed (or, without a table, trx_run_pixels) runs it -- no
-  // moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for
-  if (dt->inject) {
-    PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
-    if (const int rc = pixel_run(h, who, a, o, spectrum, PR, shift, dbg)) return rc;
-    if (PR.ext.pairs != X.cells || h->d_pixout.bytes < PR.ext.pair_bytes) return fail(h, TRX_E_HIP, "internal: the injection's pairs are not the observed set's size");
-  }
-  int rc;
-  if ((rc = ensure(h, h->d_sr_r, X.r_bytes)) || (rc = ensure(h, h->d_sr_a, X.a_bytes)) || (rc = ensure(h, h->d_sr_c, X.c_bytes)) ||
-      (rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = ensure(h, h->d_sr_basis, X.basis_bytes)) || (rc = upload(h, h->d_sr_tiles, tiles)))
-    return rc;
-  // step 0 and 1: the raw data, or the injected data, into the call's own buffer
-  const DevBuf &raw = O->d_raw.p ? O->d_raw : O->d_data;
-  if (!raw.p || raw.bytes < X.r_bytes) return fail(h, TRX_E_HIP, "internal: the observed set's data are not its size");
-  if (dt->inject) {
-    SysremInjectArgs IA{};
-    IA.pairs = h->d_pixout.as<double2>(); IA.raw = raw.as<double>(); IA.gain = O->d_gain.as<double>(); IA.r = h->d_sr_r.as<double>();
-    IA.npix = O->npix; IA.cells = X.cells; IA.p0 = dt->p0; IA.p1 = dt->p1;
-    if ((IA.gain && O->d_gain.bytes < X.c_bytes) || X.elem_blocks < 1 || X.elem_blocks > 0x7fffffffLL)
-      return fail(h, TRX_E_HIP, "internal: incomplete arguments for the injection kernel (not launched)");
-    hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)X.elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
-    HIPCHK(h, hipGetLastError());
-  } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, X.r_bytes, hipMemcpyDeviceToDevice, h->stream));
-  // step 2
-  if ((rc = launch_sysrem(h, O, dt, X, ntiles))) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->sr_basis.data(), h->d_sr_basis.p, X.basis_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished; the tiles' staging vector may go)
-  // step 3: the weighted filter of U as trx_set_weighted_filter makes it -- it reads the set's weights as trx_set_observed
-  // installed them, not its data --, the outputs, and only then the swap, which puts those weights back in force
-  if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, dt->ncomp, msg))) return fail(h, rc, msg);
-  const trx_wfilter wf{dt->ncomp, 0, h->sr_basis.data()};
-  std::unique_ptr<FilterSet> S; int64_t nsing = 0;
-  if ((rc = make_wfilter_set(h, &wf, S, &nsing, &O->raw_weight()))) return rc;
-  if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, X.coef_bytes, hipMemcpyDeviceToHost));
-  if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, X.r_bytes, hipMemcpyDeviceToHost));
-  if (basis) std::memcpy(basis, h->sr_basis.data(), X.basis_bytes);
-  if (!O->d_raw.p) { move_buf(O->d_raw, O->d_data); move_buf(O->d_data, h->d_sr_r); }
-  else { std::swap(O->d_data.p, h->d_sr_r.p); std::swap(O->d_data.bytes, h->d_sr_r.bytes); }
-  restore_raw_weights(h, O);
-  install_filter_set(h, S);
-  if (nsingular) *nsingular = nsing;
-  return TRX_OK;
-}
-
-// ---- weighing the observed set by its columns' scatter (trx_scatter.hip.h) --------------------------
-int trx_weigh_observed(trx_handle *h, const trx_scatter *sc, double *variance, double *median, double *weight, int64_t *nmasked, int64_t *nsingular)
-{
-  if (!h) return TRX_E_ARG;
-  const char *const who = "trx_weigh_observed";
-  const ProductState P = product_state(h);
-  std::string msg;
-  if (const int rc = scatter_checks(P, sc, msg)) return fail(h, rc, msg);
-  ObservedSet *const O = h->observed.get();
-  FilterSet *const F = h->filter && h->filter->weighted ? h->filter.get() : nullptr;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc; int64_t nsing = 0;
-  if (scatter_is_undo(sc)) {
-    const DevBuf &W = O->raw_weight();
-    if (F && (rc = factor_wfilter(h, *F, O, W.as<double>(), W.bytes, h->d_sc_fac, h->d_sc_live, &nsing))) return rc;
-    restore_raw_weights(h, O);
-    if (F) { swap_buf(F->d_fac, h->d_sc_fac); swap_buf(F->d_live, h->d_sc_live); }
-    if (nmasked) *nmasked = 0;
-    if (nsingular) *nsingular = nsing;
-    return TRX_OK;
-  }
-  std::vector<FilterTile> tiles; std::vector<int32_t> flags;
-  if ((rc = scatter_tiles(P, kScatBlock, tiles, msg))) return fail(h, rc, msg);
-  const int64_t ntiles = (int64_t)tiles.size();
-  const ScatterExtents X = scatter_extents(O->npix, O->nexp, O->nseg, ntiles, kScatBlock);
-  try { flags.assign((size_t)O->npix, 0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
-  if ((rc = ensure(h, h->d_sc_w, X.w_bytes)) || (rc = ensure(h, h->d_sc_var, X.var_bytes)) || (rc = ensure(h, h->d_sc_med, X.med_bytes)) ||
-      (rc = ensure(h, h->d_sc_flag, X.flag_bytes)) || (rc = upload(h, h->d_sc_tiles, tiles)))
-    return rc;
-  const DevBuf &W = O->raw_weight();
-  ScatterArgs A{};
-  A.r = O->d_data.as<double>(); A.weight = W.as<double>(); A.tiles = h->d_sc_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
-  A.var = h->d_sc_var.as<double>(); A.med = h->d_sc_med.as<double>(); A.out = h->d_sc_w.as<double>(); A.flag = h->d_sc_flag.as<int32_t>();
-  A.npix = O->npix; A.ntiles = ntiles; A.nexp = O->nexp; A.kind = sc->kind; A.min_live = sc->min_live; A.clip = sc->clip;
-  // (every address the kernels read or write: the data and the weights [nexp][npix], the tiles -- which cover [0, npix) and
-  // name segments below nseg --, the bounds [nseg + 1], var and the flags [npix], med [nseg], w' [nexp][npix])
-  if (!A.r || !A.tiles || !A.seg_first || !A.var || !A.med || !A.out || !A.flag || A.npix < 1 || A.nexp < 2 || O->nseg < 1 || !X.grid_ok ||
-      O->d_data.bytes < X.w_bytes || (A.weight && W.bytes < X.w_bytes) || h->d_sc_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
-      O->d_seg.bytes < sizeof(int64_t) * ((size_t)O->nseg + 1) || h->d_sc_var.bytes < X.var_bytes || h->d_sc_med.bytes < X.med_bytes ||
-      h->d_sc_w.bytes < X.w_bytes || h->d_sc_flag.bytes < X.flag_bytes)
-    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the scatter kernels (not launched)");
-  // (an empty segment has no tile, a segment without a live column no lane that stores: their medians stay +0)
-  HIPCHK(h, hipMemsetAsync(A.med, 0, X.med_bytes, h->stream));
-  hipLaunchKernelGGL(k_scatter_cols, dim3((unsigned)X.col_blocks), dim3(kScatBlock), 0, h->stream, A);
-  hipLaunchKernelGGL(k_scatter_median, dim3((unsigned)X.tile_blocks), dim3(kScatBlock), 0, h->stream, A);
-  hipLaunchKernelGGL(k_scatter_weights, dim3((unsigned)X.tile_blocks), dim3(kScatBlock), 0, h->stream, A);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(flags.data(), h->d_sc_flag.p, X.flag_bytes, hipMemcpyDeviceToHost, h->stream));
-  // the installed weighted filter's factor against w', in the handle's own buffers (factor_wfilter waits for the queue: every
-  // kernel has finished, the staging vectors may go)
-  if (F) { if ((rc = factor_wfilter(h, *F, O, A.out, h->d_sc_w.bytes, h->d_sc_fac, h->d_sc_live, &nsing))) return rc; }
-  else HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (variance) HIPCHK(h, hipMemcpy(variance, h->d_sc_var.p, X.var_bytes, hipMemcpyDeviceToHost));
-  if (median) HIPCHK(h, hipMemcpy(median, h->d_sc_med.p, X.med_bytes, hipMemcpyDeviceToHost));
-  if (weight) HIPCHK(h, hipMemcpy(weight, h->d_sc_w.p, X.w_bytes, hipMemcpyDeviceToHost));
-  // the swap: W aside on the first call (empty where the set had no weights), w' in force, the new factor in the filter
-  if (!O->weighed) { move_buf(O->d_wraw, O->d_weight); move_buf(O->d_weight, h->d_sc_w); O->weighed = true; }
-  else swap_buf(O->d_weight, h->d_sc_w);
-  if (F) { swap_buf(F->d_fac, h->d_sc_fac); swap_buf(F->d_live, h->d_sc_live); }
-  int64_t nm = 0;
-  for (int32_t x : flags) nm += x == kScatClipped ? 1 : 0;
-  if (nmasked) *nmasked = nm;
-  if (nsingular) *nsingular = nsing;
-  return TRX_OK;
-}
-
-// ---- rotational broadening between the spectrum and the pixels (trx_broaden.hip.h) ------------------
-// The broadening as h would keep it, checked whole before anything is replaced: on = false for a clearing call.
-static int make_broadening(trx_handle *h, const trx_broadening *br, bool &on, Broadening &out)
-{
-  on = false; out = Broadening{};
-  if (!br || br->kind == TRX_BROADEN_NONE) return TRX_OK;      // (clear)
-  std::string msg; int hmax = 0;
-  if (const int rc = broadening_checks(product_state(h), br, hmax, msg)) return fail(h, rc, msg);
-  on = true; out.beta = br->beta; out.limb = br->limb; out.hmax = hmax;
-  return TRX_OK;
-}
-
-int trx_set_broadening(trx_handle *h, const trx_broadening *br)
-{
-  if (!h) return TRX_E_ARG;
-  bool on; Broadening B;
-  if (const int rc = make_broadening(h, br, on, B)) return rc;
-  h->broad_on = on; h->broad = B;
-  return TRX_OK;
-}
-
-int trx_run_broadened(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, double *broadened, trx_debug *dbg)
-{
-  if (!h) return TRX_E_ARG;
-  if (!h->broad_on) return fail(h, TRX_E_ARG, "trx_run_broadened: no broadening installed (trx_set_broadening)");
-  if (!broadened) return fail(h, TRX_E_ARG, "trx_run_broadened: broadened is NULL");
-  HIPCHK(h, hipSetDevice(h->device));
-  if (const int rc = ensure(h, h->d_broad, broadened_bytes(h->nwn))) return rc;
-  Products want; want.br = &h->broad;
-  if (const int rc = run_once(h, a, o, spectrum, nullptr, dbg, want)) return rc;
-  HIPCHK(h, hipMemcpy(broadened, h->d_broad.p, broadened_bytes(h->nwn), hipMemcpyDeviceToHost));      // (the run has been waited for)
-  return TRX_OK;
-}
-
-// ---- several atmospheres per call -----------------------------------------------------------------
-// A retrieval driver runs many chains over one line list (the reference: one run_transit per atmosphere,
-// transit.c:118-122, one process each).  One spectrum leaves the device idle between its kernels and while
-// the host prepares and queues (about a fifth of a CH4-demo spectrum), and another
-// spectrum's kernels fit there: a batch keeps `ways` handles made from ONE description, each with a host
-// thread of its own, and deals the K atmospheres of a call to them.  Every spectrum is what trx_run gives
-// for its atmosphere, bit for bit -- it IS a trx_run, on whichever handle was free (a run's sums do not
-// depend on the handle's history: the depth hint only changes the step plan).
-extern "C++" {      // (BatchJob's constructor and batch_install are templates: they cannot have C linkage)
-// one call's job, "run atmosphere j on handle h": a callable of its trx_run_batch_* function, held by address -- it lives on
-// the stack of that function, which waits inside batch_call until every worker is done with it.  Nothing is allocated,
-// nothing can throw.
-struct BatchJob {
-  const void *call = nullptr; int (*run)(const void *call, trx_handle *h, int32_t j) = nullptr;
-  BatchJob() = default;
-  template <class F>
-  BatchJob(const F &f) : call(&f), run([](const void *c, trx_handle *h, int32_t j) { return (*static_cast<const F *>(c))(h, j); }) {}
-  int operator()(trx_handle *h, int32_t j) const { return run(call, h, j); }
-};
-
-struct trx_batch {
-  std::vector<trx_handle *> hs;
-  std::vector<std::thread> workers;
-  std::mutex mu; std::condition_variable cv_work, cv_done;
-  // the call being served (under mu): k atmospheres, the job that runs one of them, and whether a worker installs the
-  // atmosphere's broadening on its handle first (a pixel, moment, filtered-moment, trail, map or broadened run)
-  uint64_t epoch = 0; bool quit = false;
-  int32_t k = 0; BatchJob job; bool wants_broadening = false;
-  // trx_batch_set_broadening: one entry for all atmospheres or one per atmosphere (empty: none)
-  std::vector<trx_broadening> broad;
-  // trx_batch_set_exposures: one table for all atmospheres or one per atmosphere (empty: none), the arrays copied; a worker
-  // installs the atmosphere's on its handle first where the call's rows are exposures (wants_exposures: an exposed, moment,
-  // filtered-moment or exposed-map run)
-  std::vector<ExposureSet> expo; bool wants_exposures = false;
-  std::atomic<int32_t> next{0};
-  int32_t busy = 0; int rc = TRX_OK; std::string err;
-};
-
-// every handle of the batch gets the same set, or none does: all sets are built (make) before any is installed (install);
-// the failing handle's text goes to trx_last_error(NULL)
-template <class Set, class Make>
-static int batch_install(trx_batch *b, Make make, void (*install)(trx_handle *, std::unique_ptr<Set> &))
-{
-  g_comm_err.clear();
-  if (!b) return TRX_E_ARG;
-  std::vector<std::unique_ptr<Set>> sets(b->hs.size());
-  for (size_t i = 0; i < b->hs.size(); i++) {
-    const int rc = make(b->hs[i], sets[i]);
-    if (rc) { g_comm_err = b->hs[i]->err; return rc; }
-  }
-  for (size_t i = 0; i < b->hs.size(); i++) install(b->hs[i], sets[i]);
-  return TRX_OK;
-}
-}  // extern "C++"
-
-int trx_batch_create(const trx_static *st, int32_t ways, trx_batch **out)
-{
-  g_comm_err.clear();
-  if (!st || !out || ways < 1 || ways > TRX_BATCH_MAX_WAYS) { g_comm_err = "batch: bad argument (ways 1.." + std::to_string(TRX_BATCH_MAX_WAYS) + ")"; return TRX_E_ARG; }
-  *out = nullptr;
-  std::unique_ptr<trx_batch> B(new (std::nothrow) trx_batch);
-  if (!B) { g_comm_err = "batch: out of host memory"; return TRX_E_NOMEM; }
-  // (no C++ exception crosses the C boundary: a failed handle, allocation or thread start gives the handles back,
-  // joins the workers that did start and returns a code, its text through trx_last_error(NULL))
-  auto give_up = [&](int rc, const std::string &why) {
-    { std::lock_guard<std::mutex> lk(B->mu); B->quit = true; }
-    B->cv_work.notify_all();
-    for (std::thread &t : B->workers) if (t.joinable()) t.join();
-    for (trx_handle *x : B->hs) trx_destroy(x);
-    B->hs.clear(); B->workers.clear();
-    g_comm_err = why;
-    return rc;
-  };
-  for (int i = 0; i < ways; i++) {
-    trx_handle *h = nullptr;
-    const int rc = trx_create(st, &h);
-    if (rc != TRX_OK) return give_up(rc, "batch: handle " + std::to_string(i) + ": " + trx_strerror(rc));
-    try { B->hs.push_back(h); } catch (...) { trx_destroy(h); return give_up(TRX_E_NOMEM, "batch: out of host memory"); }
-  }
-  trx_batch *b = B.get();
-  try {
-  for (int i = 0; i < ways; i++)
-    b->workers.emplace_back([b, i]() {
-      uint64_t seen = 0;
-      for (;;) {
-        {
-          std::unique_lock<std::mutex> lk(b->mu);
-          b->cv_work.wait(lk, [&] { return b->quit || b->epoch != seen; });
-          if (b->quit) return;
-          seen = b->epoch;
-        }
-        for (;;) {
-          const int32_t j = b->next.fetch_add(1);
-          if (j >= b->k) break;
-          trx_handle *const hj = b->hs[(size_t)i];
-          int rc = TRX_OK;
-          // (this atmosphere's broadening first -- checked whole by trx_batch_set_broadening; none: cleared)
-          if (b->wants_broadening)
-            rc = trx_set_broadening(hj, b->broad.empty() ? nullptr : &b->broad[b->broad.size() == 1 ? 0 : (size_t)j]);
-          // (and its exposure table -- checked whole by trx_batch_set_exposures; none: cleared)
-          if (rc == TRX_OK && b->wants_exposures) {
-            if (b->expo.empty()) rc = trx_set_exposures(hj, nullptr);
-            else {
-              const ExposureSet &E = b->expo[b->expo.size() == 1 ? 0 : (size_t)j];
-              const trx_exposures ex{E.nexp, 0, E.scale.empty() ? nullptr : E.scale.data(), E.smear.empty() ? nullptr : E.smear.data()};
-              rc = trx_set_exposures(hj, &ex);
-            }
-          }
-          if (rc == TRX_OK) rc = b->job(hj, j);
-          if (rc != TRX_OK) {
-            std::lock_guard<std::mutex> lk(b->mu);
-            if (b->rc == TRX_OK) { b->rc = rc; b->err = "atmosphere " + std::to_string(j) + ": " + hj->err; }
-            b->next.store(b->k);                           // (the others finish the spectrum they are on and stop)
-          }
-        }
-        std::lock_guard<std::mutex> lk(b->mu);
-        if (--b->busy == 0) b->cv_done.notify_all();
-      }
-    });
-  } catch (const std::bad_alloc &) { return give_up(TRX_E_NOMEM, "batch: out of host memory");
-  } catch (const std::exception &e) { return give_up(TRX_E_HIP, std::string("batch: worker thread: ") + e.what()); }
-  *out = B.release();
-  return TRX_OK;
-}
-
-// one call of the batch: `job` for each of k atmospheres on whichever handle is free; returns when every worker is done
-static int batch_call(trx_batch *b, int32_t k, bool wants_broadening, const BatchJob &job, bool wants_exposures = false)
-{
-  if (k == 0) return TRX_OK;
-  std::unique_lock<std::mutex> lk(b->mu);
-  b->k = k; b->job = job; b->wants_broadening = wants_broadening; b->wants_exposures = wants_exposures;
-  b->next.store(0); b->rc = TRX_OK; b->err.clear();
-  b->busy = (int32_t)b->workers.size();
-  b->epoch++;
-  b->cv_work.notify_all();
-  b->cv_done.wait(lk, [&] { return b->busy == 0; });
-  b->job = BatchJob{};                                     // (the caller's callable goes when this returns)
-  if (b->rc != TRX_OK) g_comm_err = b->err;                // trx_last_error(NULL)
-  return b->rc;
-}
-
-int trx_run_batch(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *spectra)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !spectra))) return TRX_E_ARG;
-  for (int32_t j = 0; j < k; j++) if (!spectra[j]) return TRX_E_ARG;
-  return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run(h, atm + j, opts, spectra[j], nullptr); });
-}
-
-int trx_batch_set_bands(trx_batch *b, int32_t nbands, const trx_band *bands)
-{
-  return batch_install<BandSet>(b, [=](trx_handle *h, std::unique_ptr<BandSet> &S) { return make_band_set(h, nbands, bands, S); }, install_band_set);
-}
-
-int trx_run_batch_bands(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *sums)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums))) { g_comm_err = "trx_run_batch_bands: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_bands: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_bands", k, {{"sums", sums}}, g_comm_err)) return rc;
-  return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run_bands(h, atm + j, opts, nullptr, sums[j], nullptr); });
-}
-
-int trx_run_batch_contrib(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *sums, double *const *contrib)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !sums || !contrib))) { g_comm_err = "trx_run_batch_contrib: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->bands) { g_comm_err = "trx_run_batch_contrib: no band set installed (trx_batch_set_bands)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_contrib", k, {{"sums", sums}, {"contrib", contrib}}, g_comm_err)) return rc;
-  return batch_call(b, k, false, [=](trx_handle *h, int32_t j) { return trx_run_contrib(h, atm + j, opts, nullptr, sums[j], contrib[j], nullptr); });
-}
-
-// the batch's broadenings, one for all atmospheres or one each: all entries are checked before any is kept, or none is
-int trx_batch_set_broadening(trx_batch *b, int32_t n, const trx_broadening *br)
-{
-  g_comm_err.clear();
-  if (!b || b->hs.empty()) return TRX_E_ARG;
-  if (n < 0 || (n > 0 && !br)) { g_comm_err = "trx_batch_set_broadening: n < 0 or a NULL array"; return TRX_E_ARG; }
-  std::vector<trx_broadening> keep;
-  try { keep.assign(br, br + n); } catch (...) { g_comm_err = "trx_batch_set_broadening: out of host memory"; return TRX_E_NOMEM; }
-  // (the handles are made from one description: what the first accepts, all accept)
-  for (int32_t j = 0; j < n; j++) {
-    bool on; Broadening B;
-    const int rc = make_broadening(b->hs[0], &keep[(size_t)j], on, B);
-    if (rc) { g_comm_err = "entry " + std::to_string(j) + ": " + b->hs[0]->err; return rc; }
-    if (!on) { g_comm_err = "trx_batch_set_broadening: entry " + std::to_string(j) + " is of kind TRX_BROADEN_NONE (n = 0 clears)"; return TRX_E_ARG; }
-  }
-  b->broad = std::move(keep);
-  if (n == 0) for (trx_handle *h : b->hs) { h->broad_on = false; h->broad = Broadening{}; }
-  return TRX_OK;
-}
-
-// a pixel or broadened run of k atmospheres takes one broadening for all, one each, or none
-static int batch_broadening_fits(trx_batch *b, int32_t k, const char *who)
-{
-  const size_t n = b->broad.size();
-  if (n <= 1 || n == (size_t)k || k == 0) return TRX_OK;
-  g_comm_err = std::string(who) + ": " + std::to_string(n) + " broadenings installed (trx_batch_set_broadening) for " + std::to_string(k) + " atmospheres";
-  return TRX_E_ARG;
-}
-
-int trx_run_batch_broadened(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, double *const *broadened)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !broadened))) { g_comm_err = "trx_run_batch_broadened: bad argument"; return TRX_E_ARG; }
-  if (b->broad.empty()) { g_comm_err = "trx_run_batch_broadened: no broadening installed (trx_batch_set_broadening)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_broadened", k, {{"broadened", broadened}}, g_comm_err)) return rc;
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_broadened")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_broadened(h, atm + j, opts, nullptr, broadened[j], nullptr); });
-}
-
-int trx_batch_set_pixels(trx_batch *b, const trx_pixels *px)
-{
-  const int rc = batch_install<PixelSet>(b, [=](trx_handle *h, std::unique_ptr<PixelSet> &S) { return make_pixel_set(h, px, S); }, install_pixel_set);
-  if (rc == TRX_OK) b->expo.clear();                      // (the exposure tables go with the observed set)
-  return rc;
-}
-
-int trx_run_batch_pixels(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
-                         double *const *out)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !out))) { g_comm_err = "trx_run_batch_pixels: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->pixels) { g_comm_err = "trx_run_batch_pixels: no pixel set installed (trx_batch_set_pixels)"; return TRX_E_ARG; }
-  if (nshift < 1) { g_comm_err = "trx_run_batch_pixels: nshift < 1"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_pixels", k, {{"shift", shift}, {"out", out}}, g_comm_err)) return rc;
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_pixels")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_pixels(h, atm + j, opts, nullptr, nshift, shift[j], out[j], nullptr); });
-}
-
-int trx_batch_set_observed(trx_batch *b, const trx_observed *ob)
-{
-  const int rc = batch_install<ObservedSet>(b, [=](trx_handle *h, std::unique_ptr<ObservedSet> &S) { return make_observed_set(h, ob, S); }, install_observed_set);
-  if (rc == TRX_OK) b->expo.clear();                      // (the exposure tables go with the observed set)
-  return rc;
-}
-
-// the batch's exposure tables, one for all atmospheres or one each: all entries are checked before any is kept, or none is
-int trx_batch_set_exposures(trx_batch *b, int32_t n, const trx_exposures *ex)
-{
-  g_comm_err.clear();
-  if (!b || b->hs.empty()) return TRX_E_ARG;
-  if (n < 0 || (n > 0 && !ex)) { g_comm_err = "trx_batch_set_exposures: n < 0 or a NULL array"; return TRX_E_ARG; }
-  std::vector<ExposureSet> keep;
-  // (the handles are made from one description and carry one observed set: what the first accepts, all accept)
-  for (int32_t j = 0; j < n; j++) {
-    std::unique_ptr<ExposureSet> S;
-    const int rc = make_exposure_set(b->hs[0], ex + j, S);
-    if (rc) { g_comm_err = "entry " + std::to_string(j) + ": " + b->hs[0]->err; return rc; }
-    if (!S) { g_comm_err = "trx_batch_set_exposures: entry " + std::to_string(j) + " has nexp 0 (n = 0 clears)"; return TRX_E_ARG; }
-    try { keep.push_back(std::move(*S)); } catch (...) { g_comm_err = "trx_batch_set_exposures: out of host memory"; return TRX_E_NOMEM; }
-  }
-  b->expo = std::move(keep);
-  if (n == 0) for (trx_handle *h : b->hs) h->exposures.reset();
-  return TRX_OK;
-}
-
-// a run of k atmospheres whose rows are exposures takes one table for all, one each, or none
-static int batch_exposures_fit(trx_batch *b, int32_t k, const char *who)
-{
-  const size_t n = b->expo.size();
-  if (n <= 1 || n == (size_t)k || k == 0) return TRX_OK;
-  g_comm_err = std::string(who) + ": " + std::to_string(n) + " exposure tables installed (trx_batch_set_exposures) for " + std::to_string(k) + " atmospheres";
-  return TRX_E_ARG;
-}
-
-int trx_run_batch_exposed(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
-                          double *const *out)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !out))) { g_comm_err = "trx_run_batch_exposed: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_exposed: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (b->expo.empty()) { g_comm_err = "trx_run_batch_exposed: no exposure table installed (trx_batch_set_exposures)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_exposed", k, {{"shift", shift}, {"out", out}}, g_comm_err)) return rc;
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_exposed")) return rc;
-  if (const int rc = batch_exposures_fit(b, k, "trx_run_batch_exposed")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_exposed(h, atm + j, opts, nullptr, nshift, shift[j], out[j], nullptr); }, true);
-}
-
-int trx_run_batch_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
-                          double *const *mom)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_moments: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_moments")) return rc;
-  if (const int rc = batch_exposures_fit(b, k, "trx_run_batch_moments")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_moments(h, atm + j, opts, nullptr, nshift, shift[j], mom[j], nullptr); }, true);
-}
-
-int trx_run_batch_trail(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nlag, const double *const *lag,
-                        double *const *trail)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !lag || !trail))) { g_comm_err = "trx_run_batch_trail: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_trail: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (nlag < 1) { g_comm_err = "trx_run_batch_trail: nlag < 1"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_trail", k, {{"lag", lag}, {"trail", trail}}, g_comm_err)) return rc;
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_trail")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_trail(h, atm + j, opts, nullptr, nlag, lag[j], trail[j], nullptr); });
-}
-
-int trx_run_batch_velocity_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map,
-                               double *const *per)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = "trx_run_batch_velocity_map: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_velocity_map: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_velocity_map", k, {{"map", map}, {"per", per}}, g_comm_err)) return rc;
-  // (the handles are made from one description and carry one observed set: what the first refuses, all refuse)
-  if (k > 0)
-    if (const int rc = velocity_map_checks(product_state(b->hs[0]), "trx_run_batch_velocity_map", vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_velocity_map")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_velocity_map(h, atm + j, opts, nullptr, vm, map[j], per ? per[j] : nullptr, nullptr); });
-}
-
-int trx_batch_set_highpass(trx_batch *b, const trx_highpass *hp)
-{
-  return batch_install<HighPassSet>(b, [=](trx_handle *h, std::unique_ptr<HighPassSet> &S) { return make_highpass_set(h, hp, S); }, install_highpass_set);
-}
-
-int trx_batch_set_filter(trx_batch *b, const trx_filter *f)
-{
-  return batch_install<FilterSet>(b, [=](trx_handle *h, std::unique_ptr<FilterSet> &S) { return make_filter_set(h, f, S); }, install_filter_set);
-}
-
-int trx_batch_set_weighted_filter(trx_batch *b, const trx_wfilter *f)
-{
-  return batch_install<FilterSet>(b, [=](trx_handle *h, std::unique_ptr<FilterSet> &S) { return make_wfilter_set(h, f, S, nullptr); }, install_filter_set);
-}
-
-int trx_run_batch_filtered_moments(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, int32_t nshift, const double *const *shift,
-                                   double *const *mom)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !shift || !mom))) { g_comm_err = "trx_run_batch_filtered_moments: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_filtered_moments: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_moments: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_filtered_moments", k, {{"shift", shift}, {"mom", mom}}, g_comm_err)) return rc;
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_moments")) return rc;
-  if (const int rc = batch_exposures_fit(b, k, "trx_run_batch_filtered_moments")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_moments(h, atm + j, opts, nullptr, nshift, shift[j], nullptr, mom[j], nullptr); }, true);
-}
-
-int trx_run_batch_filtered_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map)
-{
-  g_comm_err.clear();
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = "trx_run_batch_filtered_map: bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = "trx_run_batch_filtered_map: no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (!b->hs[0]->filter) { g_comm_err = "trx_run_batch_filtered_map: no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check("trx_run_batch_filtered_map", k, {{"map", map}}, g_comm_err)) return rc;
-  // (the handles are made from one description and carry one observed set and one filter: what the first refuses, all refuse)
-  if (k > 0)
-    if (const int rc = filtered_map_checks(product_state(b->hs[0]), "trx_run_batch_filtered_map", vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
-  if (const int rc = batch_broadening_fits(b, k, "trx_run_batch_filtered_map")) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_filtered_map(h, atm + j, opts, nullptr, vm, map[j], nullptr, nullptr); });
-}
-
-int trx_run_batch_exposed_map(trx_batch *b, int32_t k, const trx_atm *atm, const trx_opts *opts, const trx_vmap *vm, double *const *map)
-{
-  g_comm_err.clear();
-  const char *const who = "trx_run_batch_exposed_map";
-  if (!b || k < 0 || (k > 0 && (!atm || !opts || !map))) { g_comm_err = std::string(who) + ": bad argument"; return TRX_E_ARG; }
-  if (b->hs.empty() || !b->hs[0]->observed) { g_comm_err = std::string(who) + ": no observed set installed (trx_batch_set_observed)"; return TRX_E_ARG; }
-  if (!b->hs[0]->filter) { g_comm_err = std::string(who) + ": no filter installed (trx_batch_set_filter)"; return TRX_E_ARG; }
-  if (b->expo.empty()) { g_comm_err = std::string(who) + ": no exposure table installed (trx_batch_set_exposures)"; return TRX_E_ARG; }
-  if (const int rc = batch_rows_check(who, k, {{"map", map}}, g_comm_err)) return rc;
-  // (the handles are made from one description and carry one observed set and one filter: what the first refuses, all refuse;
-  // the tables are the batch's, installed per atmosphere by the workers)
-  if (k > 0)
-    if (const int rc = filtered_map_checks(product_state(b->hs[0]), who, vm, map[0], g_comm_err)) return fail(b->hs[0], rc, g_comm_err);
-  if (const int rc = batch_broadening_fits(b, k, who)) return rc;
-  if (const int rc = batch_exposures_fit(b, k, who)) return rc;
-  return batch_call(b, k, true, [=](trx_handle *h, int32_t j) { return trx_run_exposed_map(h, atm + j, opts, nullptr, vm, map[j], nullptr, nullptr, nullptr); }, true);
-}
-
-int trx_batch_ways(const trx_batch *b) { return b ? (int)b->hs.size() : 0; }
-
-void trx_batch_destroy(trx_batch *b)
-{
-  if (!b) return;
-  { std::lock_guard<std::mutex> lk(b->mu); b->quit = true; }
-  b->cv_work.notify_all();
-  for (std::thread &t : b->workers) t.join();
-  for (trx_handle *h : b->hs) trx_destroy(h);
-  delete b;
-}
+#include "trx_api_products.hip.h"
+#include "trx_api_batch.hip.h"
 
 }  // extern "C"
