@@ -1072,6 +1072,40 @@ int  trx_weigh_observed(trx_handle *h, const trx_scatter *sc,
                         double *weight /* [nexp][npix], host; may be NULL */,
                         int64_t *nmasked /* may be NULL */, int64_t *nsingular /* may be NULL */);
 
+/* High-passing the observed set itself along the pixel axis, on the device: the data-side twin of trx_set_highpass.  The
+ * model of a run against the observed set goes through the installed high-pass; SYSREM's residuals (or the raw set) go
+ * through the SAME table with this call, so the two are compared like with like.  The documented order is
+ * trx_detrend_observed, trx_highpass_observed, trx_weigh_observed, the map.
+ *
+ * Every operation is IEEE double rounded once, no fused multiply-add; sums start from +0; no atomics.
+ * W is the weights as trx_set_observed installed them (1 everywhere without) -- the array trx_detrend_observed reads, NEVER
+ * a weigh call's result.  r is the data as the last successful trx_detrend_observed left them -- its residuals, or the raw
+ * set if the set is not detrended --, NEVER an earlier high-pass call's result: calling twice gives the bits of calling once.
+ * taps[0 .. half] is the high-pass installed on the handle.
+ * 1. An entry (v, q) is LIVE if W[v][q] > 0.  For a row v, a segment [first, last) and a live pixel p in it
+ *      r'[v][p] = r[v][p] - (sum of taps[|k|] * r[v][p+k]) / (sum of taps[|k|]),   k = -half .. half in that order,
+ *    over the q = p + k inside the segment and live: trx_set_highpass's formula with g = r and live = (W > 0).  A dead entry
+ *    gets r' = +0 (after SYSREM it holds an unweighted junk residual); ndead is their count.
+ * 2. At once and only after every kernel has finished, r' -- built in a buffer of its own -- becomes the observed set's
+ *    data; r is kept aside on the device.  Nothing else changes: the weights in force, a filter of either kind and its
+ *    factor, the high-pass, the exposure table, the broadening, the gain and the pixel set stay.  data, where given,
+ *    receives r'.
+ * 3. The undo: apply = 0 puts r back in force; TRX_OK even if nothing had been high-passed, and no high-pass need be
+ *    installed; ndead 0, data not written.
+ * 4. Every successful trx_detrend_observed, its undo included, discards the high-pass: detrend, high-pass, detrend gives the
+ *    second detrend the bits of a fresh one.  trx_weigh_observed reads the data in force -- r' after this call --, and its
+ *    undo does not touch the data; this call after a weigh neither reads nor changes the weights in force.
+ *    trx_set_highpass afterwards, with a new table or NULL, leaves the data as they are.  trx_set_observed and
+ *    trx_set_pixels drop everything.
+ * 5. TRX_E_ARG, the reason in trx_last_error, nothing touched, checked in this order: no observed set; apply not 0 or 1;
+ *    with apply = 1, no high-pass installed.  TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.  nexp * ntiles
+ *    above one launch's grid is refused before anything is launched.  A call that fails later (TRX_E_HIP, TRX_E_NOMEM)
+ *    leaves the previous data in force.
+ * Not here: a batch form, shards, a high-pass ahead of SYSREM, a table other than the installed one, clipping single entries. */
+int  trx_highpass_observed(trx_handle *h, int32_t apply /* 1: high-pass, 0: undo */,
+                           double *data /* [nexp][npix]: the data now installed, host; may be NULL */,
+                           int64_t *ndead /* may be NULL */);
+
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)
  * batched over nv independent thermodynamic states -- what calcopacity()

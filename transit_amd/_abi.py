@@ -382,3 +382,10 @@ def bind_scatter_api(lib):
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.trx_weigh_observed.restype = C.c_int
     return lib
+
+
+def bind_hpdata_api(lib):
+    """argtypes/restypes of the observed set's own high-pass (trx_highpass_observed)."""
+    lib.trx_highpass_observed.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.POINTER(C.c_int64)]
+    lib.trx_highpass_observed.restype = C.c_int
+    return lib

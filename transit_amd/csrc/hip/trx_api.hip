@@ -65,6 +65,7 @@
 #include "../trx_sysrem.h"
 #include "../trx_scatter.h"
 #include "../trx_launch.h"
+#include "../trx_hpdata.h"
 
 using namespace trx;
 

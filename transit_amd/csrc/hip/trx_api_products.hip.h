@@ -433,6 +433,7 @@ static int make_observed_set(trx_handle *h, const trx_observed *ob, std::unique_
   if (!S) return fail(h, TRX_E_NOMEM, "observed: out of host memory");
   S->nexp = ob->nexp; S->nseg = ob->nseg; S->npix = npix;
   try { S->seg.assign(ob->seg_first, ob->seg_first + ob->nseg + 1); } catch (...) { return fail(h, TRX_E_NOMEM, "observed: out of host memory"); }
+  if (ob->weight) for (size_t k = 0; k < cells; k++) S->ndead += ob->weight[k] > 0.0 ? 0 : 1;
   HIPCHK(h, hipSetDevice(h->device));
   int rc;
   if ((rc = upload_raw(h, S->d_seg, ob->seg_first, (size_t)ob->nseg + 1)) || (rc = upload_raw(h, S->d_data.now, ob->data, cells)) ||
@@ -989,6 +990,7 @@ int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   HIPCHK(h, hipSetDevice(h->device));
   if (detrend_is_undo(dt)) {
     // (the buffers of the residuals and of a weigh call's weights are kept for the next call when the handle has none)
+    O->d_data.uncover(h->d_hp_r);                       // (a high-pass over the data goes first: its buffer is kept for the next one)
     O->d_data.restore(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
     h->filter.reset();
     if (nsingular) *nsingular = 0;
@@ -1035,6 +1037,7 @@ int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, X.coef_bytes, hipMemcpyDeviceToHost));
   if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, X.r_bytes, hipMemcpyDeviceToHost));
   if (basis) std::memcpy(basis, h->sr_basis.data(), X.basis_bytes);
+  O->d_data.uncover(h->d_hp_r);                         // (as in the undo)
   O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
   install_filter_set(h, S);
   if (nsingular) *nsingular = nsing;
@@ -1103,6 +1106,47 @@ int trx_weigh_observed(trx_handle *h, const trx_scatter *sc, double *variance, d
   for (int32_t x : flags) nm += x == kScatClipped ? 1 : 0;
   if (nmasked) *nmasked = nm;
   if (nsingular) *nsingular = nsing;
+  return TRX_OK;
+}
+
+// ---- high-passing the observed set itself (k_data_highpass, trx_highpass.hip.h) ----------------------
+int trx_highpass_observed(trx_handle *h, int32_t apply, double *data, int64_t *ndead)
+{
+  if (!h) return TRX_E_ARG;
+  std::string msg;
+  if (const int rc = hpdata_checks(product_state(h), apply, msg)) return fail(h, rc, msg);
+  ObservedSet *const O = h->observed.get();
+  HIPCHK(h, hipSetDevice(h->device));
+  if (hpdata_is_undo(apply)) {
+    // (the buffer of the high-passed data is kept for the next call when the handle has none)
+    O->d_data.uncover(h->d_hp_r);
+    if (ndead) *ndead = 0;
+    return TRX_OK;
+  }
+  const HighPassSet &F = *h->highpass;
+  const HpDataExtents X = hpdata_extents(O->npix, O->nexp, F.ntiles, F.half);
+  if (const int rc = hpdata_launch_checks(X, msg)) return fail(h, rc, msg);
+  int rc;
+  if ((rc = ensure(h, h->d_hp_r, X.r_bytes))) return rc;
+  // r: what the last successful detrend left -- never an earlier high-pass's result --; W: as trx_set_observed installed them
+  const DevBuf &R = O->d_data.base(), &W = O->d_weight.raw();
+  HpDataArgs A{};
+  A.r = R.as<double>(); A.weight = W.as<double>(); A.taps = F.d_taps.as<double>(); A.tiles = F.d_tiles.as<HpTile>(); A.out = h->d_hp_r.as<double>();
+  A.npix = F.npix; A.ntiles = F.ntiles; A.den_full = F.den_full; A.half = F.half;
+  // (every address the kernel reads or writes: data in and out and the weights over [nexp][npix] -- the tiles lie in [0, npix)
+  // within their segments' bounds, made so from this observed set's when the high-pass was --, the taps [half + 1], the tiles,
+  // and (count + 2 half) * 2 doubles of LDS, count <= kHpTile; the output is a buffer of its own)
+  if (F.obs != O || !observed_set_whole(*O, W, true) || !A.r || R.bytes < X.r_bytes || (A.weight && W.bytes < X.r_bytes) || !A.taps || !A.tiles || !A.out ||
+      A.out == A.r || h->d_hp_r.bytes < X.r_bytes || F.half < 0 || F.half > TRX_HIGHPASS_MAX_HALF || F.npix != O->npix || F.nseg != O->nseg || F.ntiles < 1 ||
+      F.d_taps.bytes < sizeof(double) * ((size_t)F.half + 1) || F.d_tiles.bytes < sizeof(HpTile) * (size_t)F.ntiles || X.lds_bytes > 65536 || !grid_ok(X.blocks))
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the data high-pass kernel (not launched)");
+  hipLaunchKernelGGL(k_data_highpass, dim3((unsigned)X.blocks), dim3(kHpBlock), X.lds_bytes, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished)
+  if (data) HIPCHK(h, hipMemcpy(data, h->d_hp_r.p, X.r_bytes, hipMemcpyDeviceToHost));
+  // the swap: what was in force goes under on the first call, r' in force; the previous r' waits in d_hp_r for the next call
+  O->d_data.cover(h->d_hp_r);
+  if (ndead) *ndead = O->ndead;                         // (the weights as installed do not change: counted when they were)
   return TRX_OK;
 }
 

@@ -43,11 +43,13 @@ struct ObservedSet {
   int32_t nexp = 0, nseg = 0; int64_t npix = 0;
   DevBuf d_seg, d_gain;                              // [nseg + 1], [npix] or none
   std::vector<int64_t> seg;                          // [nseg + 1] on the host: trx_set_filter cuts its tiles from it
+  int64_t ndead = 0;                                 // entries whose weight as installed is not > 0 (none without weights)
   // the data [nexp][npix] and the weights, the same or none (all 1), in force (.now) and as trx_set_observed installed them
   // (.raw(), ../trx_launch.h).  trx_detrend_observed (trx_sysrem.hip.h) adopts a call's residuals as the data and its undo
   // restores them; trx_weigh_observed (trx_scatter.hip.h) adopts a call's weights, and its undo and every successful
-  // trx_detrend_observed restore them
-  InForce<DevBuf> d_data, d_weight;
+  // trx_detrend_observed restore them.  The data have a third level (../trx_hpdata.h): trx_highpass_observed covers what is
+  // in force with its high-passed version, its undo uncovers it, and every successful trx_detrend_observed discards it
+  DataInForce<DevBuf> d_data; InForce<DevBuf> d_weight;
 };
 // a filter installed by trx_set_filter over the observed set (trx_filter.hip.h): the matrices zero-padded to npad
 // components and exposure-major, and the tiles of the observed set's segments
@@ -254,6 +256,9 @@ struct trx_handle {
   // set's when it succeeds), the variances [npix], the medians [nseg], the columns' flags [npix] and the tiles; the factor
   // and the pivot flags a call makes for the installed weighted filter (swapped with the filter's)
   DevBuf d_sc_w, d_sc_var, d_sc_med, d_sc_flag, d_sc_tiles, d_sc_fac, d_sc_live;
+  // trx_highpass_observed (trx_highpass.hip.h), grown on demand: the high-passed data [nexp][npix] a call builds (swapped
+  // with the observed set's data when it succeeds; the previous call's, or an undone one, waits here for the next)
+  DevBuf d_hp_r;
 };
 
 namespace {

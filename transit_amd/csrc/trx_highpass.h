@@ -1,7 +1,8 @@
 // trx_highpass.h -- the arithmetic of the high-pass along the pixel axis (trx_set_highpass / trx_run_highpassed,
 // include/transit_hip.h): one staged entry of a row, the values of the pixels a lane owns, the full-window denominator.
-// Plain host/device functions: k_pixel_highpass (hip/trx_highpass.hip.h) calls them per lane over its tile in LDS,
-// tests/highpass_check.cpp runs the same source on the CPU over exact-size arrays.  Every operation is an IEEE double
+// Plain host/device functions: k_pixel_highpass and k_data_highpass (hip/trx_highpass.hip.h; the second high-passes the
+// observed set's own data, trx_highpass_observed) call them per lane over their tile in LDS, tests/highpass_check.cpp and
+// tests/hpdata_check.cpp run the same source on the CPU over exact-size arrays.  Every operation is an IEEE double
 // operation rounded once -- no fused multiply-add -- in the order transit_amd/xcor.py (highpass_reference) writes it.
 //
 // The definition skips the terms whose pixel is outside the segment or not live.  Here such a pixel is STAGED as
@@ -23,6 +24,16 @@ TRX_HD void highpass_stage(double a, double b, double gain, bool inside, double 
 #endif
   const bool live = inside && b > 0.0;
   g = live ? gain * (a / b) : 0.0;
+  m = live ? 1.0 : 0.0;
+}
+
+// the staged entry of one datum of the observed set (trx_highpass_observed): r its value -- a residual, or the raw datum --,
+// w its weight as trx_set_observed installed it (1 without weights), inside: the pixel lies in the segment of the tile that
+// stages it.  The value goes in as it is: no pair, no quotient, no gain
+TRX_HD void highpass_stage_datum(double r, double w, bool inside, double &g, double &m)
+{
+  const bool live = inside && w > 0.0;
+  g = live ? r : 0.0;
   m = live ? 1.0 : 0.0;
 }
 

@@ -215,6 +215,7 @@ def hip_library():
         _abi.bind_expmap_api(lib)
         _abi.bind_sysrem_api(lib)
         _abi.bind_scatter_api(lib)
+        _abi.bind_hpdata_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -255,6 +256,14 @@ class Weighed:
 
     def __init__(self, variance, median, weight, nmasked, nsingular):
         self.variance, self.median, self.weight, self.nmasked, self.nsingular = variance, median, weight, nmasked, nsingular
+
+
+class Highpassed:
+    """What Engine.highpass_observed returns: data [nexp, npix] the high-passed data now installed (+0 at the dead entries;
+    None after the undo or with outputs=False), ndead the entries whose weight as set_observed installed it is not > 0."""
+
+    def __init__(self, data, ndead):
+        self.data, self.ndead = data, ndead
 
 
 class Engine(CEngine):
@@ -545,6 +554,22 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_weigh_observed", self._last_error())
         return Weighed(var if give else None, med if give else None, w if give else None, int(nm.value), int(nsing.value))
+
+    def highpass_observed(self, apply: bool = True, outputs: bool = True) -> "Highpassed":
+        """trx_highpass_observed: the observed set's own data through the installed high-pass (set_highpass), on the device
+        -- from the data as the last detrend_observed left them (its residuals, or the raw set), never from an earlier
+        high-pass, and with live = (W > 0) of the weights as set_observed installed them (xcor.highpass_observed_reference,
+        bit for bit).  The result becomes the observed data; weights, filter, high-pass, exposure table and gain stay.
+        apply=False is the undo.  Every successful detrend_observed discards the high-pass: the order is detrend, high-pass,
+        weigh, map.  Returns a Highpassed: data [nexp, npix] and ndead.  outputs=False leaves the data on the device."""
+        nexp = getattr(self, "mom_shape", (0, 0))[0]
+        give = bool(outputs) and bool(apply)
+        data = np.zeros((nexp, getattr(self, "npix", 0))) if give else None
+        nd = C.c_int64(0)
+        rc = self._lib.trx_highpass_observed(self._h, 1 if apply else 0, _dp(data), C.byref(nd))
+        if rc != 0:
+            raise EngineError(rc, "trx_highpass_observed", self._last_error())
+        return Highpassed(data, int(nd.value))
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device

@@ -1180,6 +1180,22 @@ def highpass_reference(pairs, obs: Observed, hp: HighPass) -> np.ndarray:
     return out
 
 
+def highpass_observed_reference(data, weight, seg_first, hp: HighPass):
+    """(values [nexp, npix], ndead): the observed set's own data through the high-pass as trx_highpass_observed defines it
+    (include/transit_hip.h) -- the mirror of k_data_highpass, bit for bit.  data: the data the call reads (the residuals
+    of a detrend, or the raw set); weight: the weights as set_observed installed them (None: all 1).  It is
+    highpass_reference of the pairs (data, weight > 0) without a gain -- g = 1 * (r / 1) is r --, with +0 in place of NaN
+    at the dead entries; ndead is their count."""
+    data = np.asarray(data, dtype=np.float64)
+    if data.ndim != 2:
+        raise ValueError("data of shape [nexp][npix]")
+    live = np.ones(data.shape, dtype=bool) if weight is None else np.asarray(weight, dtype=np.float64) > 0
+    if live.shape != data.shape:
+        raise ValueError("weight of the data's shape")
+    v = highpass_reference(np.stack([data, live.astype(np.float64)], axis=-1), Observed(seg_first, data, None, None), hp)
+    return np.where(live, v, 0.0), int(np.count_nonzero(~live))
+
+
 def highpass_pairs(values) -> np.ndarray:
     """The pairs [n, npix, 2] the device keeps of high-passed values [n, npix]: (g', 1) for a live pixel, (0, 0) for a dead
     one (NaN).  reference, trail_reference and filter_reference of them with a gain-free copy of the observed set are the
