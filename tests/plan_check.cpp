@@ -7,7 +7,9 @@
 //   * the first step has three layers (the 2- and 3-point rays);
 //   * last_step marks the pass's last step and no other;
 //   * a pass planned whole is the pass planned step by step;
-//   * the tail predicate == one or two walk steps to the hint, counted here the plain way.
+//   * the tail predicate == one or two walk steps to the hint, counted here the plain way;
+//   * the per-molecule sweep's steps (plan_sweep_step) tile nv-1 .. 0, each of one kind, within its cap (walk_cap or the
+//     strength buffers' layers), its frame the widest of its layers: equal to the plain per-layer restatement.
 // Prints "<cases> cases, <bad> differ".
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +26,7 @@ int main(int argc, char **argv)
 {
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 20000;
   const int kWalkCap = 64, kChunkCap = 32, kTailSteps = 2;
-  std::mt19937_64 rng(20261);
+  std::mt19937_64 rng(20261), rng_sweep(20262);      // (the sweep's caps from a generator of their own: the runs' cases stay as they were)
   int cases = 0;
   for (int r = 0; r < rounds; r++, cases++) {
     const int nr = 3 + (int)(rng() % (r % 7 == 0 ? 300 : 120));
@@ -52,6 +54,33 @@ int main(int argc, char **argv)
     for (int i = 0; i < nr; i++) any_wide = any_wide || frame[i] == 0;
     in.sg_layers = any_wide ? (in.user_chunk ? std::min(in.user_chunk, kChunkCap) : kChunkCap) : 1;
     in.walk_cap = kWalkCap; in.chunk_cap = kChunkCap;
+
+    // the per-molecule sweep's steps against the plain per-layer restatement: a step takes layers while they are of
+    // r_top's kind and it is under its cap, and its frame is the widest met on the way
+    {
+      const int sg = 1 + (int)(rng_sweep() % 32), wcap = r % 3 == 0 ? 1 + (int)(rng_sweep() % kWalkCap) : kWalkCap;
+      size_t k = 0;
+      int at = nr - 1;
+      std::vector<unsigned char> taken((size_t)nr, 0);
+      for (; at >= 0; k++) {
+        const PlanStep s = plan_sweep_step(frame.data(), at, wcap, sg);
+        const bool walk = frame[at] != 0;
+        int nc = 0, widest = 0;
+        for (int i = at; i >= 0 && (frame[i] != 0) == walk && nc < (walk ? wcap : sg); i--) { nc++; widest = std::max(widest, frame[i]); }
+        EXPECT(s.r_top == at && s.nc == nc && s.nb == (walk ? widest : 0));
+        EXPECT(s.nc >= 1 && s.nc <= (s.nb ? wcap : sg) && s.r_top - s.nc >= -1);
+        for (int c = 0; c < s.nc && s.r_top - c >= 0; c++) {
+          EXPECT((frame[s.r_top - c] != 0) == (s.nb != 0) && frame[s.r_top - c] <= s.nb);      // one kind; the frame holds every layer's
+          EXPECT(!taken[(size_t)(s.r_top - c)]);
+          taken[(size_t)(s.r_top - c)] = 1;
+        }
+        EXPECT(s.last_step == (s.r_top - s.nc < 0));
+        if (s.nc < 1) break;
+        at -= s.nc;
+      }
+      k = 0;
+      for (int i = 0; i < nr; i++) EXPECT(taken[(size_t)i]);                                   // the steps tile nr-1 .. 0
+    }
 
     // a first pass (to the hint where the run stops there), and the pass of a run that resumed below the hint
     for (int second = 0; second < 2; second++) {

@@ -51,7 +51,8 @@ def test_step_plan_holds_what_its_consumers_rely_on(tmp_path):
     layers from the top; every step is one kind, its frame the widest of its layers; layers per step within
     the kind's cap, layer_chunk and the strength buffers; three layers in the first step; last_step on the
     pass's last step alone; a pass planned whole == planned step by step; the tail predicate == one or two
-    walk steps to the hint."""
+    walk steps to the hint; the per-molecule sweep's steps (plan_sweep_step) tile every layer, one kind each, within
+    the kind's cap, the frame the widest of the step's layers."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")

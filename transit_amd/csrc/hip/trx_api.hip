@@ -12,8 +12,9 @@
 // Everything per (line x layer), per (group x layer x bin) and per
 // (wavenumber x layer) runs in the kernels of trx_kernels.hip.h.
 //
-// One translation unit in four files: the handle and its helpers (trx_handle.hip.h), here the handle's creation and the run
-// path, then the run products (trx_api_products.hip.h) and the batch layer (trx_api_batch.hip.h), included at the end.
+// One translation unit in five files: the handle and its helpers (trx_handle.hip.h), here the handle's creation and the run
+// path, the launches of a sweep step (trx_api_sweep.hip.h) between the two, then the run products (trx_api_products.hip.h)
+// and the batch layer (trx_api_batch.hip.h), included at the end.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -55,6 +56,7 @@
 #include "trx_contrib.hip.h"
 #include "../trx_groups.h"
 #include "../trx_plan.h"
+#include "../trx_sweep.h"
 #include "../trx_table.h"
 #include "../trx_broaden.h"
 #include "../trx_vmap.h"
@@ -862,427 +864,8 @@ void layer_dev(const double *df, const int32_t *di, const LayerHost &LH, int nr,
   Y.idop0 = di; Y.ilor = di + nli; Y.psmax = Y.ilor + nli; d_npre = Y.psmax + nli;
 }
 
-// ---- per-kernel timing of a profiled run: (start, end) event pairs on the stream of the kernel ----
-struct Spans {
-  enum Kind { kSweep = 0, kWalk = 1, kAccum = 2, kTau = 3, kWalkLanes = 4, kWalkPacked = 5, kKinds = 6 };      // (kWalk: k_line_walk itself; the three walk forms add up to trx_stats.ms_k_walk)
-  struct Span { hipEvent_t a, b; int kind; };
-  std::vector<Span> v;
-  int begin(int kind, hipStream_t st) {
-    Span sp{nullptr, nullptr, kind};
-    if (hipEventCreate(&sp.a) != hipSuccess || hipEventCreate(&sp.b) != hipSuccess) return -1;
-    v.push_back(sp);
-    return hipEventRecord(sp.a, st) == hipSuccess ? 0 : -1;
-  }
-  int end(hipStream_t st) { return hipEventRecord(v.back().b, st) == hipSuccess ? 0 : -1; }
-  void sum(double out[kKinds]) const {
-    for (const Span &sp : v) { float t = 0; if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) out[sp.kind] += t; }
-  }
-  static bool is_walk(int k) { return k == kWalk || k == kWalkLanes || k == kWalkPacked; }
-  // first walk's start to last walk's end (the walks of one run may share the device on two queues)
-  double walk_span() const {
-    double best = 0;
-    for (const Span &x : v) if (is_walk(x.kind))
-      for (const Span &y : v) if (is_walk(y.kind)) { float t = 0; if (hipEventElapsedTime(&t, x.a, y.b) == hipSuccess && t > best) best = t; }
-    return best;
-  }
-  ~Spans() { for (Span &sp : v) { if (sp.a) (void)hipEventDestroy(sp.a); if (sp.b) (void)hipEventDestroy(sp.b); } }
-};
-
-// ---- one step of the line sweep ------------------------------------------------------------
-struct SweepMode {
-  bool eager = false, prof = false, skip_done = false, permol = false;
-  double ethresh = 0;
-  int nmx = 1; const int32_t *d_iso_mx = nullptr;   // output slot per isotope (per-molecule sweeps)
-  double *d_e = nullptr;                             // [layer][nmx][nsh]
-  const double *d_kmax = nullptr;                    // [layer][nmx] (k_layer_max)
-  const int *d_sticky = nullptr;                     // [layer][iso] (k_sticky_index)
-  hipStream_t st = nullptr;                          // null: the handle's stream
-};
-
-// widest profile (in fine-grid points) any isotope with lines can use in layer r
-long long layer_psmax(const trx_handle *h, const int32_t *psmax, int r)
-{
-  long long pm = 0;
-  for (int b = 0; b < h->niso; b++)
-    if (h->h_gblock[b] != h->h_gblock[b + 1]) pm = std::max<long long>(pm, psmax[(size_t)r * h->niso + b]);
-  return pm;
-}
-
-// Frame size of the walk for layer r (bins a line can reach = 2*Rc + 2 with Rc whole cells of
-// profile half-width), or 0 when its profiles are wider than the largest frame: the layer then
-// takes the two-kernel path.  A per-LAYER property, so that the path a layer takes -- and with
-// it the order of its sums -- does not depend on how the layers are grouped into steps.
-int walk_frame_bins(const trx_handle *h, const int32_t *psmax, int r)
-{
-  if (!h->walk_ok || !h->walk_temp_ok) return 0;
-  const long long rc = layer_psmax(h, psmax, r) / h->osamp;
-  // (The 16-bin frame -- profiles reaching 4-7 cells -- used to pay only on sparse lists: with a load
-  // per bin it cost 1.4 ms for the 9 such layers of configs[2] against ~0.4 ms in the two-kernel
-  // form.  Reading rows of the table copy, two lanes per layer, it is the cheaper one there too:
-  // 2.32 -> 2.26 ms.)
-  return rc <= 0 ? 2 : rc <= 1 ? 4 : rc <= 3 ? 8 : rc <= 7 ? 16 : 0;     // (tab_n >= Rc*osamp follows: a profile that wide is in the table)
-}
-
-// plan of the line ranges for a frame of nb bins (built once per handle and frame size)
-int walk_plan(trx_handle *h, int nb, hipStream_t st, WalkPlan &P, trx_handle::Plan *&pl)
-{
-  const int v = nb == 2 ? 0 : nb == 4 ? 1 : nb == 8 ? 2 : 3;
-  pl = &h->plan[v];
-  int rc;
-  if (!pl->built) {
-    const size_t nw = (size_t)std::max(h->nwaves, 1);
-    if ((rc = ensure(h, pl->blo, 4 * nw)) || (rc = ensure(h, pl->bhi, 4 * nw)) || (rc = ensure(h, pl->off, 8 * (nw + 1)))) return rc;
-  }
-  P.nwaves = h->nwaves; P.ngw = h->ngw; P.wbase = h->d_wbase.as<int32_t>();
-  P.blo = pl->blo.as<int32_t>(); P.bhi = pl->bhi.as<int32_t>(); P.off = pl->off.as<int64_t>();
-  // (the per-bin range table: 8 bytes per bin and isotope; above 2^24 entries the combine searches instead)
-  const long long nbinw = (long long)h->nsh * h->niso;
-  const bool with_binw = nbinw > 0 && nbinw <= (1LL << 24);
-  if (!pl->built && with_binw && (rc = ensure(h, pl->binw, 8 * (size_t)nbinw))) return rc;
-  P.binw = with_binw ? pl->binw.as<int32_t>() : nullptr;
-  // (and the bin's record in each of its first 64 ranges, for k_ray_tail: 256 bytes per bin and isotope, small shards only)
-  const bool with_binrec = with_binw && nbinw <= (1LL << 17) && !h->sw.no_binrec;
-  if (!pl->built && with_binrec && (rc = ensure(h, pl->binrec, 256 * (size_t)nbinw))) return rc;
-  P.binrec = with_binrec ? pl->binrec.as<int32_t>() : nullptr;
-  if (!pl->built) {
-    hipLaunchKernelGGL(k_wave_plan, dim3(1), dim3(256), 0, st, P, h->niso, h->d_gblock.as<int32_t>(), h->d_gidiv.as<int32_t>(),
-                       nb / 2 - 1, (long long)h->lo, (long long)h->hi);
-    if (with_binw)
-      hipLaunchKernelGGL(k_bin_ranges, dim3((unsigned)((nbinw + 255) / 256)), dim3(256), 0, st, P, h->niso, (long long)h->lo, (long long)h->nsh);
-    int64_t total = 0;
-    HIPCHK(h, hipMemcpyAsync(&total, P.off + h->nwaves, sizeof total, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));                 // once per handle and frame size
-    pl->records = total; pl->built = true;
-  }
-  if (pl->records >= (1LL << 31)) P.binrec = nullptr;      // (32-bit record numbers)
-  return TRX_OK;
-}
-
-template <int NB>
-void launch_walk(const WalkArgs &A, bool prof, unsigned nwaves, hipStream_t st)
-{
-  const dim3 grid((nwaves + kWalkWaves - 1) / kWalkWaves), block(64 * kWalkWaves);
-  if (prof) hipLaunchKernelGGL((k_line_walk<NB, true>), grid, block, 0, st, A);
-  else if constexpr (NB >= 8) {      // steps of at most 32 layers: two lanes per layer (trx_walk.hip.h)
-    if (A.nc <= 32) hipLaunchKernelGGL((k_line_walk<NB, false, 2>), grid, block, 0, st, A);
-    else            hipLaunchKernelGGL((k_line_walk<NB, false>), grid, block, 0, st, A);
-  }
-  else      hipLaunchKernelGGL((k_line_walk<NB, false>), grid, block, 0, st, A);
-}
-
-// A combine whose launch has been put off (the host queues the NEXT step's walk first, so that the
-// walks sit back to back on their queue whatever else this step still has to queue).
-struct PendingCombine {
-  bool valid = false;
-  CombineArgs C{}; hipStream_t sc = nullptr; hipEvent_t ev_walk = nullptr, ev_done = nullptr; bool cross = false;
-};
-
-int launch_combine(trx_handle *h, PendingCombine &pc, Spans *sp)
-{
-  if (!pc.valid) return TRX_OK;
-  pc.valid = false;
-  if (pc.cross) HIPCHK(h, hipStreamWaitEvent(pc.sc, pc.ev_walk, 0));
-  if (sp && sp->begin(Spans::kAccum, pc.sc)) return fail(h, TRX_E_HIP, "event");
-  hipLaunchKernelGGL(k_walk_combine, dim3((unsigned)((h->nsh + kCombineBins - 1) / kCombineBins)), dim3(64 * kCombineBins), 0, pc.sc, pc.C);
-  if (sp && sp->end(pc.sc)) return fail(h, TRX_E_HIP, "event");
-  if (pc.cross && pc.ev_done) HIPCHK(h, hipEventRecord(pc.ev_done, pc.sc));
-  return TRX_OK;
-}
-
-// The walk: layers r_top .. r_top-nc+1 (nc <= 64) in one kernel on M.st, then the combine of its
-// partial sums on st_comb (the stream the optical depth runs on; null: M.st).  Consecutive steps
-// alternate between two record buffers, so that the next step's walk does not wait for this
-// step's combine.
-int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, int nb, int r_top, int nc, const SweepMode &M, Spans *sp,
-               int parity, hipStream_t st_comb, hipEvent_t ev_walk, hipEvent_t ev_reuse = nullptr, hipEvent_t ev_done = nullptr,
-               PendingCombine *defer = nullptr /* non-null: the combine is handed back instead of launched */,
-               int *form_out = nullptr /* which kernel took the step: 0 k_line_walk, 1 k_line_walk_lanes, 2 k_line_walk_packed */)
-{
-  hipStream_t st = M.st ? M.st : h->stream;
-  WalkPlan P{}; trx_handle::Plan *pl = nullptr;
-  int rc = walk_plan(h, nb, st, P, pl);
-  if (rc) return rc;
-  DevBuf &part = h->d_part[parity & 1];
-  // (trx_stats describes the last trx_run: a per-molecule sweep (trx_sweep_permol) walks too but is not counted)
-  if (!M.permol) { h->stats.walk_steps++; h->stats.walk_records += pl->records; h->stats.walk_record_lanes += pl->records * nc; }
-  const size_t pbytes = sizeof(double) * kWalkLayers * (size_t)std::max<int64_t>(pl->records, 1);
-  if (part.bytes < pbytes) {
-    HIPCHK(h, hipStreamSynchronize(st));                 // an earlier step may still be using the old buffer
-    HIPCHK(h, hipStreamSynchronize(h->stream4));          // (combines of earlier steps run there)
-    if ((rc = ensure(h, part, pbytes))) return rc;
-  }
-  // this buffer's previous records (two steps ago) must have been combined
-  if (ev_reuse) HIPCHK(h, hipStreamWaitEvent(st, ev_reuse, 0));
-  WalkArgs A{};
-  A.lines = h->d_walk.as<WalkLine>(); A.rinfo = h->d_rinfo.as<RangeInfo>(); A.gfirst = h->d_gfirst.as<int32_t>(); A.gcount = h->d_gcount.as<int32_t>();
-  A.gblock = h->d_gblock.as<int32_t>(); A.P = P;
-  A.niso = h->niso; A.nlor = h->nlor; A.ndop = h->ndop; A.osamp = h->osamp; A.lo = h->lo; A.hi = h->hi;
-  A.wn_i = h->wn_i; A.odwn = h->odwn; A.range_reach = h->sw.range_reach && h->psize_mono;      // (a table whose profiles narrow somewhere as the Doppler index rises keeps the step's bound)
-  A.r_top = r_top; A.nc = nc; A.Y = Y; A.wcut = d_wcut; A.kmax = M.d_kmax; A.ethresh = M.ethresh;
-  A.nmx = M.nmx; A.iso_mx = M.d_iso_mx; A.permol = M.permol; A.sticky_idop = M.d_sticky;
-  A.dthr = h->d_dopthr.as<double>(); A.e2tab = h->d_e2tab.as<double>();
-  A.psize = h->d_psize.as<int32_t>(); A.poff = h->d_poff.as<long long>();
-  A.table = h->tab; A.zero_index = h->tab_n;
-  A.tabw = h->tabW; A.walkprof = h->d_walkprof.as<WalkProfile>();
-  A.tabw32 = h->tabW32; A.wp32 = h->tabW32 ? h->d_wp32.as<uint32_t>() : nullptr; A.slab32 = h->slab32;
-  A.xcd_map = h->sw.xcd_map & 2;                        // (bit 1: k_line_walk, bit 0: k_line_walk_lanes)
-  A.part = part.as<double>(); A.counters = M.prof ? h->d_counters.as<unsigned long long>() : nullptr;
-  A.flags = h->d_flags.as<int>(); A.last = M.skip_done ? h->d_last.as<int>() : nullptr; A.eager = M.eager;
-  // a shard launches only the ranges that can reach it: per isotope block the groups whose cells
-  // lie within Rc + 1 cells of [lo, hi) are one run of consecutive ranges (cnt_ge look-up).  A range
-  // reaches the bins of its whole span (the plan's blo..bhi: its lowest cell - Rc to its highest + Rc + 1),
-  // and the combine reads its records there: so a range whose groups sit on both sides of the window,
-  // none inside, is launched too (it writes the zeros; skipped, the combine would add whatever the record
-  // buffer held).  Groups below cell 0 (the grid's first line when it lies just below the band) count
-  // as in reach of a window that starts within Rc + 1 cells of the bottom.
-  unsigned nw = (unsigned)h->nwaves;
-  A.nseg = 0;
-  if (h->windowed() && h->niso <= kWalkSegs && nw > 0) {
-    const int Rc = nb / 2 - 1;
-    const long long klo = std::max<long long>(0, h->lo - Rc - 1), khi = std::min<long long>(h->nwn - 1, h->hi - 1 + Rc);
-    int cum = 0, ns = 0;
-    for (int b = 0; b < h->niso; b++) {
-      const int gb0 = h->h_gblock[b], gb1 = h->h_gblock[b + 1];
-      if (gb0 == gb1) continue;
-      const int32_t *cg = &h->h_cntge[(size_t)b * (h->nwn + 1)];
-      // groups of the block (descending cells) with cell in [klo, khi]: [ga, gz)
-      const int ga = cg[khi + 1], gz = h->lo - Rc - 1 <= 0 ? gb1 - gb0 : cg[klo];
-      // the ranges holding a group on each side of ga and of gz - 1: empty only where the window falls between two ranges
-      const int wa = h->h_wbase[b] + ga / h->ngw, wz = h->h_wbase[b] + (gz + h->ngw - 1) / h->ngw;
-      if (wz <= wa) continue;
-      A.seg_w0[ns] = wa; A.seg_cum[ns] = cum; cum += wz - wa; ns++;
-    }
-    A.seg_cum[ns] = cum; A.nseg = ns;
-    nw = (unsigned)cum;
-    if (ns == 0) { A.nseg = 1; A.seg_w0[0] = 0; A.seg_cum[0] = 0; A.seg_cum[1] = 0; }     // nothing reaches: no wave does anything
-  }
-  // steps of few layers with wide frames on a dense list: lanes = lines for the strengths (trx_lanes.hip.h)
-  const bool lanes_prod = nw > 0 && A.tabw != nullptr && nb >= 8 && nc <= kLanesMaxLayers && h->sw.lanes_walk &&
-                          h->max_gcount <= kLanesMaxGroup && (h->ngroups >= 8 * h->nwn || h->sw.lanes_force);
-  // steps of few layers: several ranges per wave (k_line_walk_packed: an instruction serves S lines)
-  const bool packed_prod = !lanes_prod && nw > 0 && A.tabw != nullptr && nc <= h->sw.packed_max_layers && h->sw.packed_walk;
-  // (a counting run -- instrumented k_line_walk for every step -- books its layers under the form the production run
-  // takes for them: its per-layer counters are what prices each form's bytes, bench.py)
-  const bool lanes = lanes_prod && !M.prof, packed = packed_prod && !M.prof;
-  const int form_prod = lanes_prod ? 1 : packed_prod ? 2 : 0, form = lanes ? 1 : packed ? 2 : 0;
-  if (form_out) *form_out = form_prod;
-  if (!M.permol) { h->stats.walk_form_steps[form_prod]++; h->stats.walk_form_layers[form_prod] += nc; h->stats.walk_form_record_lanes[form_prod] += pl->records * nc; }
-  if (sp && sp->begin(form == 1 ? Spans::kWalkLanes : form == 2 ? Spans::kWalkPacked : Spans::kWalk, st)) return fail(h, TRX_E_HIP, "event");
-  if (lanes) {
-    // one range per wave (round 4 measured 2, 3, 4 ranges per wave at the demo size: 0.257 / 0.283 / 0.276 ms for the
-    // spectrum's two walks against 0.239 -- the last lines of a range already get lanes = (line, 4 or 8 layer sets);
-    // the kernel no longer has that form)
-    LanesExtra X{h->d_linebase.as<double>()};
-    A.xcd_map = h->sw.xcd_map & 1;
-    if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG)
-      log_msg(TRX_LOG_DEBUG, "walk: lanes = lines, " + std::to_string(nc) + " layers, " + std::to_string(nb) + "-bin frames, " +
-                             std::to_string(lanes_parts(nc, h->sw.lanes_parts_most)) + " lanes per layer");
-    const dim3 grid((nw + kLanesWaves - 1) / kLanesWaves), block(64 * kLanesWaves);
-    const size_t lds = lanes_lds_bytes(nc, h->ndop);
-    // (blocks of 5 groups at 8 bins: a batch's ~28 are 6 blocks, an even number; 4: 102.2 us, 5: 101.2, 6: 103.6, round 5.
-    // Blocks of 2 at 16 bins -- with two lanes per layer 8 floats per group and lane, 112 registers: 169.5 us; 3 / 4:
-    // 130 / 150 registers, 171.0 / 172.6, round 5.)  Lanes per layer in phase 2: lanes_parts
-    const int parts = lanes_parts(nc, h->sw.lanes_parts_most);
-    if (nb == 8) {
-      if (parts == 4)      hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 4>), grid, block, lds, st, A, X);
-      else if (parts == 3) hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 3>), grid, block, lds, st, A, X);
-      else                 hipLaunchKernelGGL((k_line_walk_lanes<8, 5, 2>), grid, block, lds, st, A, X);
-    } else {
-      if (parts == 4)      hipLaunchKernelGGL((k_line_walk_lanes<16, 2, 4>), grid, block, lds, st, A, X);
-      else if (parts == 3) hipLaunchKernelGGL((k_line_walk_lanes<16, 2, 3>), grid, block, lds, st, A, X);
-      else                 hipLaunchKernelGGL((k_line_walk_lanes<16, 2, 2>), grid, block, lds, st, A, X);
-    }
-  }
-  else if (packed) {
-    const int S = 64 / nc;
-    const unsigned pw = (nw + (unsigned)S - 1) / (unsigned)S;
-    const dim3 grid((pw + kWalkWaves - 1) / kWalkWaves), block(64 * kWalkWaves);
-    if (nb <= 4)      hipLaunchKernelGGL(k_line_walk_packed<4>, grid, block, 0, st, A, S);      // (a 2-bin step in the 4-bin row form: the same values)
-    else if (nb == 8) hipLaunchKernelGGL(k_line_walk_packed<8>, grid, block, 0, st, A, S);
-    else              hipLaunchKernelGGL(k_line_walk_packed<16>, grid, block, 0, st, A, S);
-  }
-  else if (nw > 0) {
-    // (no row copy -- it would have passed 4 GB: the wide frames run their per-bin form, which is
-    // the counting instantiation with the counters switched off)
-    const bool per_bin = M.prof || (nb >= kWalkRowsFrom && A.tabw == nullptr);
-    if (nb == 2) launch_walk<2>(A, per_bin, nw, st);
-    else if (nb == 4) launch_walk<4>(A, per_bin, nw, st);
-    else if (nb == 8) launch_walk<8>(A, per_bin, nw, st);
-    else launch_walk<16>(A, per_bin, nw, st);
-  }
-  if (sp && sp->end(st)) return fail(h, TRX_E_HIP, "event");
-  PendingCombine pc;
-  pc.valid = true; pc.sc = st_comb ? st_comb : st; pc.cross = st_comb != nullptr && ev_walk != nullptr;
-  pc.ev_walk = ev_walk; pc.ev_done = ev_done;
-  if (pc.cross) HIPCHK(h, hipEventRecord(ev_walk, st));
-  CombineArgs &C = pc.C;
-  C.P = P; C.niso = h->niso; C.gblock = h->d_gblock.as<int32_t>(); C.lo = h->lo; C.nsh = h->nsh; C.r_top = r_top; C.nc = nc;
-  C.nmx = M.nmx; C.iso_mx = M.d_iso_mx; C.part = part.as<double>(); C.e = M.d_e;
-  C.flags = h->d_flags.as<int>(); C.last = A.last; C.eager = M.eager;
-  if (defer) { *defer = pc; return TRX_OK; }
-  return launch_combine(h, pc, sp);
-}
-
-// The two-kernel form (profiles wider than the walk's largest frame): strengths, accumulation.
-int sweep_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, const int32_t *psmax,
-                int r_top, int nc, int nc_max, const SweepMode &M, Spans *sp)
-{
-  hipStream_t st = M.st ? M.st : h->stream;
-  const int niso = h->niso; const int64_t nsh = h->nsh;
-  const int ntiles = (int)((nsh + kTileBins - 1) / kTileBins);
-  double *d_SG = h->d_SG.as<double>();
-  uint8_t *d_idop8 = h->d_idop8.as<uint8_t>();
-  // lines whose profiles can reach this shard in any layer of the step (contiguous per isotope block):
-  // their number here, for the launch; the runs themselves are found by the kernel (SweepWindow)
-  SweepWindow Wn{};
-  Wn.windowed = h->windowed() ? 1 : 0; Wn.osamp = h->osamp; Wn.lo = h->lo; Wn.hi = h->hi; Wn.nwn = h->nwn;
-  long long seg_lines = 0;
-  for (int b = 0; b < niso; b++) {
-    const int gb0 = h->h_gblock[b], gb1 = h->h_gblock[b + 1];
-    if (gb0 == gb1) continue;
-    int ga = gb0, gz = gb1;
-    if (h->windowed()) {
-      long long psm = 0;
-      for (int c = 0; c < nc; c++) psm = std::max<long long>(psm, psmax[(size_t)(r_top - c) * niso + b]);
-      const long long lo_f = (long long)h->osamp * h->lo - psm;
-      long long klo = lo_f > 0 ? lo_f / h->osamp : 0;
-      long long khi = ((long long)h->osamp * (h->hi - 1) + psm) / h->osamp;
-      if (khi > h->nwn - 1) khi = h->nwn - 1;
-      const int32_t *cg = &h->h_cntge[(size_t)b * (h->nwn + 1)];
-      ga = gb0 + cg[khi + 1]; gz = gb0 + cg[klo];
-    }
-    if (ga >= gz) continue;
-    seg_lines += ((long long)h->h_gfirst[gz - 1] + h->h_gcount[gz - 1]) - h->h_gfirst[ga];
-  }
-  constexpr unsigned kSpan = kXcds * kAccumXcdGroup;
-  const unsigned tblocks = (unsigned)(((ntiles + 3) / 4 + kSpan - 1) / kSpan * kSpan);   // multiple of 8*G: xcd_grouped_x()
-  if (sp && sp->begin(Spans::kSweep, st)) return fail(h, TRX_E_HIP, "event");
-  if (seg_lines > 0) {
-    hipLaunchKernelGGL(k_group_sweep, dim3((unsigned)((seg_lines + 255) / 256)), dim3(256), sizeof(long long) * (2 * (size_t)niso + 1), st,
-                       h->L, Y, Wn, niso, r_top, nc, h->d_dopthr.as<double>(), h->ndop, h->d_e2tab.as<double>(), d_wcut,
-                       d_SG, d_idop8, h->d_flags.as<int>(), (int)M.eager);
-  }
-  if (sp && (sp->end(st) || sp->begin(Spans::kAccum, st))) return fail(h, TRX_E_HIP, "event");
-  if (h->ngroups > 0) {
-    AccumArgs A{};
-    A.L = h->L; A.Y = Y; A.niso = niso; A.nlor = h->nlor; A.ndop = h->ndop; A.osamp = h->osamp;
-    A.nwn = h->nwn; A.lo = h->lo; A.nsh = nsh; A.r_top = r_top; A.nc = nc; A.ntiles = ntiles;
-    A.SG = d_SG; A.idop8 = d_idop8; A.sticky_idop = M.d_sticky;
-    A.kmaxc = M.d_kmax; A.ethresh = M.ethresh; A.nmx = M.nmx; A.iso_mx = M.d_iso_mx; A.permol = M.permol;
-    A.psize = h->d_psize.as<int32_t>(); A.poff = h->d_poff.as<long long>();
-    A.table = h->tab; A.e = M.d_e;
-    // (profiled runs count every group in the tile of its own coarse cell: whole-cell windows)
-    A.sub_f = M.prof ? 1 : h->sub_f; A.cnt_sub = A.sub_f > 1 ? h->d_cntsub.as<int32_t>() : h->d_cntge.as<int32_t>();
-    A.part = M.prof ? h->d_part3.as<unsigned long long>() : nullptr; A.part_stride = (int)tblocks;
-    A.flags = h->d_flags.as<int>(); A.eager = M.eager;
-    A.last = M.skip_done ? h->d_last.as<int>() : nullptr;
-    // layers whose profiles span >= 64 coarse bins go to the lanes-own-bins kernel
-    unsigned wide_mask = 0;
-    for (int c = 0; c < nc; c++)
-      if ((2 * layer_psmax(h, psmax, r_top - c)) / h->osamp + 1 >= 64) wide_mask |= 1u << c;   // measured: 16 or 32 here is 4x slower at configs[2] size, 128/256 no better
-    A.skip_mask = wide_mask;
-    if (M.prof) HIPCHK(h, hipMemsetAsync(h->d_part3.p, 0, 24 * (size_t)nc_max * tblocks, st));
-    if (wide_mask != (nc >= 32 ? 0xffffffffu : ((1u << nc) - 1u)))
-      hipLaunchKernelGGL(k_accumulate, dim3(tblocks, (unsigned)nc), dim3(256), 0, st, A);
-    if (wide_mask) {
-      WideArgs W{}; W.A = A; W.tabT = h->tabT; W.poffT = h->poffT;
-      W.gimod = h->d_gimod.as<int32_t>(); W.gidiv = h->d_gidiv.as<int32_t>(); W.layer_mask = wide_mask;
-      const unsigned wtiles = (unsigned)((nsh + 64 * kWideM - 1) / (64 * kWideM));
-      // no oversampling: every group of a profile reads the same row -- staged in LDS (trx_rows.hip.h);
-      // layers whose profiles are much wider than a tile take tiles of 512 bins, the others of 256
-      if (h->osamp == 1 && h->sw.row_staging) {
-        unsigned m8 = 0;
-        for (int c = 0; c < nc; c++)
-          if (((wide_mask >> c) & 1u) && 2 * layer_psmax(h, psmax, r_top - c) + 1 >= h->sw.row_m8_from) m8 |= 1u << c;
-        auto launch = [&](unsigned mask, int m) {
-          if (!mask) return;
-          W.layer_mask = mask;
-          const unsigned tiles = (unsigned)((nsh + 64 * m - 1) / (64 * m));
-          const dim3 grid((tiles + 3) / 4, (unsigned)nc);
-          const size_t lds = rows_lds_bytes(h->ndop, m);
-          if (M.prof) hipLaunchKernelGGL((k_accumulate_rows<true, 4>), grid, dim3(256), lds, st, W);      // (counting runs: one tile size)
-          else if (m == 8) hipLaunchKernelGGL((k_accumulate_rows<false, 8>), grid, dim3(256), lds, st, W);
-          else hipLaunchKernelGGL((k_accumulate_rows<false, 4>), grid, dim3(256), lds, st, W);
-        };
-        if (M.prof) launch(wide_mask, 4);
-        else { launch(wide_mask & ~m8, 4); launch(m8, 8); }
-      }
-      else hipLaunchKernelGGL(k_accumulate_wide, dim3((wtiles + 3) / 4, (unsigned)nc), dim3(256), 0, st, W);
-    }
-  }
-  if (sp && sp->end(st)) return fail(h, TRX_E_HIP, "event");
-  if (M.prof && h->ngroups > 0) {      // counters (profiling runs only; gated like the sweep itself)
-    for (int k = 0; k < 3; k++)
-      hipLaunchKernelGGL(k_sum_parts_gated, dim3((unsigned)nc), dim3(256), 0, st, h->d_part3.as<unsigned long long>(),
-                         (int)tblocks, 3, k, h->d_counters.as<unsigned long long>(), 3, r_top, h->d_flags.as<int>(), (int)M.eager);
-  }
-  return TRX_OK;
-}
-
-// Strongest single line and sticky Doppler index of ALL nv layers (states) at once: both depend
-// on the inputs only, not on how far the rays get, so they leave the per-step chain.
-// kmax: [nv][nmx], zero on entry.  init: the run's small buffers, initialised by an extra row of
-// blocks of the first launch (null: none); *init_done tells whether that happened.
-// Two launches, each usable on its own: trx_run queues the maxima BEFORE the rest of its host prologue
-// (they need -c/T and the strength factors only, which it hands over in pinned host memory).
-int launch_layer_max(trx_handle *h, const LayerDev &Y, int nv, const double *temp_k, int nmx, const int32_t *d_iso_mx,
-                     hipStream_t st, double *kmax, const RunInit *init = nullptr, bool *init_done = nullptr)
-{
-  if (init_done) *init_done = false;
-  if (h->ngroups == 0) return TRX_OK;
-  // the pruning argument needs c*nu/T well above the rounding of 1 - exp(-c*nu/T) (trx_walk.hip.h)
-  bool pruned = h->ncand > 0;
-  for (int r = 0; r < nv && pruned; r++) if (kExpCte * kTliEfct * h->wn_i / temp_k[r] < 1e-5) pruned = false;
-  const long long n = pruned ? h->ncand : h->nlines;
-  for (int r0 = 0; r0 < nv; r0 += 32768) {
-    const int nr = std::min(32768, nv - r0);
-    LayerDev Yr = Y; Yr.negc_over_t += r0; Yr.strength_f += (size_t)r0 * h->niso;
-    const unsigned ny = (unsigned)((nr + kLayerMaxGroup - 1) / kLayerMaxGroup);
-    const bool with_init = init && r0 == 0;
-    RunInit R{}; R.nsh = -1;
-    if (with_init) { R = *init; *init_done = true; }
-    // (at most kLayerMaxWaves waves per group of layers: beyond that a wave takes several chunks of candidates)
-    const int xwaves = (int)std::min<long long>((n + 64 * kLayerMaxLines - 1) / (64 * kLayerMaxLines), kLayerMaxWaves);
-    hipLaunchKernelGGL(k_layer_max, dim3((unsigned)((xwaves + kLayerMaxBlock - 1) / kLayerMaxBlock), ny + (with_init ? 1u : 0u)), dim3(64 * kLayerMaxBlock), sizeof(double) * (size_t)kLayerMaxGroup * (size_t)std::max(h->niso, 1), st,
-                       h->L, Yr, h->niso, nr, pruned ? h->d_candrec.as<CandLine>() : nullptr, n, h->d_e2tab.as<double>(), nmx, d_iso_mx,
-                       (unsigned long long *)(kmax + (size_t)r0 * nmx), R, with_init ? (int)ny : -1, xwaves);
-  }
-  return TRX_OK;
-}
-
-// (copy_*: the run's input block from pinned host memory into device memory, by extra blocks of the first launch)
-int launch_sticky(trx_handle *h, const LayerDev &Y, const int32_t *d_npre, int nv, int nmx, const int32_t *d_iso_mx, double ethresh,
-                  hipStream_t st, const double *kmax, const void *copy_src = nullptr, void *copy_dst = nullptr, size_t copy_bytes = 0)
-{
-  const long long n16 = (long long)(copy_bytes / 16);
-  if (h->ngroups == 0 && n16 == 0) return TRX_OK;
-  bool copied = n16 == 0;
-  for (int r0 = 0; r0 < nv || !copied; r0 += 4096) {               // one wave per (layer, isotope)
-    const int nr = h->ngroups == 0 ? 0 : std::max(0, std::min(4096, nv - r0));
-    const int nst = nr * h->niso;
-    const int ncp = copied ? 0 : (int)std::min<long long>((n16 + 63) / 64, 64);
-    if (nst + ncp == 0) break;
-    hipLaunchKernelGGL(k_sticky_index, dim3((unsigned)(nst + ncp)), dim3(64), 0, st,
-                       h->L, Y, h->niso, r0 + nr - 1, nr, kmax, nmx, d_iso_mx, ethresh, h->d_dopthr.as<double>(), h->ndop,
-                       h->d_e2tab.as<double>(), d_npre, h->d_sticky.as<int>(), h->d_flags.as<int>(), 1,
-                       copied ? nullptr : (const uint4 *)copy_src, copied ? nullptr : (uint4 *)copy_dst, copied ? 0LL : n16, nst);
-    copied = true;
-  }
-  HIPCHK(h, hipGetLastError());
-  return TRX_OK;
-}
-
-int layer_maxima_and_sticky(trx_handle *h, const LayerDev &Y, const int32_t *d_npre, int nv, const double *temp_k,
-                            int nmx, const int32_t *d_iso_mx, double ethresh, hipStream_t st, double *kmax,
-                            const RunInit *init = nullptr, bool *init_done = nullptr)
-{
-  int rc;
-  if (init_done) *init_done = false;
-  if ((rc = ensure(h, h->d_sticky, sizeof(int) * (size_t)nv * std::max(h->niso, 1)))) return rc;
-  if (h->ngroups == 0) return TRX_OK;
-  if ((rc = launch_layer_max(h, Y, nv, temp_k, nmx, d_iso_mx, st, kmax, init, init_done))) return rc;
-  return launch_sticky(h, Y, d_npre, nv, nmx, d_iso_mx, ethresh, st, kmax);
-}
+// ---- one step of the line sweep: Spans, walk_chunk, sweep_chunk, layer_maxima_and_sticky
+#include "trx_api_sweep.hip.h"
 
 }  // namespace
 
@@ -2024,13 +1607,8 @@ int Run::workspaces()
   // The two-kernel form keeps a strength buffer per layer in flight: at most kMaxChunk, and
   // 8 where the profiles are wide.  Optical depths are integrated in sub-steps of at most tau_cap layers.
   const int user_chunk = o->layer_chunk > 0 ? std::max(3, o->layer_chunk) : 0;
-  bool any_wide = false;                      // some layer needs the two-kernel form
   h->run_frame.resize((size_t)nr); h->run_wide.resize((size_t)nr);
-  for (int r = 0; r < nr; r++) {
-    h->run_frame[r] = walk_frame_bins(h, LH.psmax, r);
-    h->run_wide[r] = (2 * layer_psmax(h, LH.psmax, r)) / h->osamp + 1 >= 64;
-    any_wide = any_wide || h->run_frame[r] == 0;
-  }
+  const bool any_wide = layer_frames(h, LH.psmax, nr, h->run_frame.data(), h->run_wide.data());      // some layer needs the two-kernel form
   const size_t gr_b = (size_t)std::max<int64_t>(h->ngroups, 1);
   P.sg_layers = any_wide ? (user_chunk ? std::min(user_chunk, kMaxChunk) : kMaxChunk) : 1;
   P.frame = h->run_frame.data(); P.very_wide = h->run_wide.data(); P.nr = nr; P.hint_layers = h->hint_layers; P.user_chunk = user_chunk;
@@ -2254,7 +1832,8 @@ int Run::grid_step(const PlanStep &s)
 // the extinction of a step's layers from the lines: a walk (for the tail, or with its combine handed to S), or the two-kernel form
 int Run::line_step(const PlanStep &s, SideWork &S, bool &walked)
 {
-  int rc = TRX_OK, form = 0;
+  int rc = TRX_OK;
+  WalkResult W;
   SweepMode M{};
   M.eager = eager; M.prof = count; M.ethresh = o->ethresh;
   M.skip_done = (!eager && !(dbg && dbg->e));
@@ -2278,24 +1857,31 @@ int Run::line_step(const PlanStep &s, SideWork &S, bool &walked)
       static_assert(kTailSteps == 2, "the side-queue tail waits for ev_walk1 alone: the main queue may carry exactly one walk ahead of it");
       const bool side_walk = two_queues && nchunks == 1;
       if (side_walk) { HIPCHK(h, hipStreamWaitEvent(h->stream4, h->ev_inputs, 0)); M.st = h->stream4; tail_on_side = true; }
-      rc = walk_chunk(h, Y, d_wcut, s.nb, s.r_top, s.nc, M, sp, nwalks, nullptr, nullptr, nullptr, nullptr, &S.pc, &form);
+      WalkQueue Q;
+      Q.parity = nwalks; Q.defer = true;
+      rc = walk_chunk(h, Y, d_wcut, s, M, sp, Q, W);
       if (!rc) {
         TailStep &TS = TA.S[TA.nsteps++];
-        TS.P = S.pc.C.P; TS.part = S.pc.C.part; TS.nc = s.nc;
-        TA.skip = S.pc.C.last;
-        S.pc.valid = false;
+        TS.P = W.pc.C.P; TS.part = W.pc.C.part; TS.nc = s.nc;
+        TA.skip = W.pc.C.last;
       }
       nwalks++;
     }
     else if (s.nb) {
-      rc = walk_chunk(h, Y, d_wcut, s.nb, s.r_top, s.nc, M, sp, nwalks, S.st_tau != st ? S.st_tau : nullptr, h->ev_ac[nchunks],
-                      nwalks >= 2 ? h->ev_cb[(nwalks - 2) % h->ev_cb.size()] : nullptr, h->ev_cb[nwalks % h->ev_cb.size()], &S.pc, &form);
+      WalkQueue Q;
+      Q.parity = nwalks; Q.defer = true;
+      if (S.st_tau != st) Q.st_comb = S.st_tau;
+      Q.ev_walk = h->ev_ac[nchunks];
+      if (nwalks >= 2) Q.ev_reuse = h->ev_cb[(nwalks - 2) % h->ev_cb.size()];
+      Q.ev_done = h->ev_cb[nwalks % h->ev_cb.size()];
+      rc = walk_chunk(h, Y, d_wcut, s, M, sp, Q, W);
+      if (!rc) S.pc = W.pc;
       nwalks++;
     }
-    else    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s.r_top, s.nc, P.sg_layers, M, sp);
+    else    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s, P.sg_layers, M, sp);
     if (rc) return rc;
     walked = s.nb != 0;
-    if (walked) for (int c = 0; c < s.nc; c++) layer_walked[(size_t)(s.r_top - c)] = (uint8_t)(1 + form);
+    if (walked) for (int c = 0; c < s.nc; c++) layer_walked[(size_t)(s.r_top - c)] = (uint8_t)(1 + W.form);
   }
   if (S.st_tau != st && !walked) {     // the optical depth of this step follows its extinction
     HIPCHK(h, hipEventRecord(h->ev_ac[nchunks], st));
@@ -2568,9 +2154,8 @@ int trx_sweep_permol(trx_handle *h, int32_t nv, const double *temp, const double
   for (int r = 0; r < nv; r++) if (temp[r] < kWalkMinTemp) h->walk_temp_ok = false;
   const size_t gr_b = (size_t)std::max<int64_t>(h->ngroups, 1);
   std::vector<int32_t> slots(iso_slot, iso_slot + std::max(niso, 1));
-  bool any_wide = false;
-  for (int r = 0; r < nv && !any_wide; r++) any_wide = walk_frame_bins(h, LH.psmax, r) == 0;
-  const int sg_layers = any_wide ? 12 : 1;
+  const std::unique_ptr<int[]> frame(new int[(size_t)nv]);      // the walk's frame per state, filled as a run's (Run::workspaces)
+  const int sg_layers = layer_frames(h, LH.psmax, nv, frame.get(), nullptr) ? 12 : 1;
   if ((rc = ensure(h, h->d_SG, sizeof(double) * gr_b * sg_layers)) || (rc = ensure(h, h->d_idop8, gr_b * sg_layers)) ||
       (rc = ensure_small(h, nv)) ||
       (rc = ensure(h, h->d_pm, sizeof(double) * (size_t)nv * nslot * nsh)) ||
@@ -2585,23 +2170,19 @@ int trx_sweep_permol(trx_handle *h, int32_t nv, const double *temp, const double
   h->kmax_clean = false;
   if ((rc = layer_maxima_and_sticky(h, Y, d_npre, nv, temp, nslot, h->d_iso_mx.as<int32_t>(), ethresh, st, h->d_kmax.as<double>()))) return rc;
   for (int r_top = nv - 1; r_top >= 0 && h->ngroups > 0; ) {
-    int nb = walk_frame_bins(h, LH.psmax, r_top);
-    int nc = 1;
-    const int cap = nb ? kWalkLayers : sg_layers;
-    while (nc < cap && nc <= r_top && (walk_frame_bins(h, LH.psmax, r_top - nc) == 0) == (nb == 0)) nc++;
-    if (nb) for (int c = 1; c < nc; c++) nb = std::max(nb, walk_frame_bins(h, LH.psmax, r_top - c));
+    const PlanStep s = plan_sweep_step(frame.get(), r_top, kWalkLayers, sg_layers);
     SweepMode M{};
     M.eager = true; M.ethresh = ethresh; M.nmx = nslot; M.d_iso_mx = h->d_iso_mx.as<int32_t>();
     M.permol = true; M.d_e = h->d_pm.as<double>(); M.d_kmax = h->d_kmax.as<double>(); M.d_sticky = h->d_sticky.as<int>();
-    int form = -1;
-    if (nb) rc = walk_chunk(h, Y, d_wcut, nb, r_top, nc, M, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &form);
-    else    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, r_top, nc, sg_layers, M, nullptr);
+    WalkResult W;      // (form -1: the two-kernel form)
+    if (s.nb) rc = walk_chunk(h, Y, d_wcut, s, M, nullptr, WalkQueue{}, W);
+    else      rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s, sg_layers, M, nullptr);
     if (rc) return rc;
     // (trx_stats does not count sweeps: the step plan goes to the log, one line per step -- tests read it)
     if (log_sink().fn && log_sink().max_level >= TRX_LOG_DEBUG)
-      log_msg(TRX_LOG_DEBUG, std::string("sweep step: form ") + (form == 1 ? "lanes" : form == 2 ? "packed" : form == 0 ? "walk" : "two-kernel") +
-                             ", states " + std::to_string(nc) + ", frame bins " + std::to_string(nb));
-    r_top -= nc;
+      log_msg(TRX_LOG_DEBUG, std::string("sweep step: form ") + (W.form == 1 ? "lanes" : W.form == 2 ? "packed" : W.form == 0 ? "walk" : "two-kernel") +
+                             ", states " + std::to_string(s.nc) + ", frame bins " + std::to_string(s.nb));
+    r_top -= s.nc;
   }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(out, h->d_pm.p, sizeof(double) * (size_t)nv * nslot * nsh, hipMemcpyDeviceToHost, st));

@@ -79,6 +79,18 @@ inline void plan_pass(const PlanInput &in, int r_top, bool stop_at_hint, std::ve
   }
 }
 
+// The step of a per-molecule sweep (trx_sweep_permol): no hint, no first-step rule, every state to the bottom.
+// The states of ONE kind from r_top down -- walk or two-kernel form -- up to that kind's cap; a walk step's
+// frame is the widest of its states'.  frame: [nv] as PlanInput::frame.  (static: no new symbol of the library)
+static inline PlanStep plan_sweep_step(const int *frame, int r_top, int walk_cap, int sg_layers)
+{
+  int nb = frame[r_top], nc = 1;
+  const int cap = nb ? walk_cap : sg_layers;
+  while (nc < cap && nc <= r_top && (frame[r_top - nc] == 0) == (nb == 0)) nc++;
+  if (nb) for (int c = 1; c < nc; c++) nb = std::max(nb, frame[r_top - c]);
+  return PlanStep{r_top, nc, nb, r_top - nc < 0};
+}
+
 // a pass to the hint that the ray tail can end (trx_tail.hip.h): 1 to tail_steps steps, every one a walk
 inline bool plan_is_tail(const std::vector<PlanStep> &pass, int tail_steps)
 {
