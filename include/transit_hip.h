@@ -1013,7 +1013,7 @@ int  trx_run_batch_exposed_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k
  *    TRX_E_NOMEM) also leaves the previous data and filter in force.
  * Not here: a batch form (a driver takes basis and data from one handle and installs them on a trx_batch through
  * trx_batch_set_observed and trx_batch_set_weighted_filter), high-passing the data, per-order normalisation or division by
- * a column's scatter, PCA/SVD on the device, shards. */
+ * a column's scatter, shards.  A principal-component analysis in SYSREM's place is trx_pca_observed, below. */
 #define TRX_SYSREM_MAX_ITER 64
 typedef struct {
   int32_t ncomp, niter;      /* components 1 .. TRX_FILTER_MAX (0: undo); alternations per component, 1 .. TRX_SYSREM_MAX_ITER */
@@ -1027,6 +1027,62 @@ int  trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o,
                           double *coef /* [ncomp][npix], host; may be NULL */,
                           double *data /* [nexp][npix]: the residuals now installed, host; may be NULL */,
                           int64_t *nsingular /* may be NULL */, trx_debug *dbg /* may be NULL */);
+
+/* The same call with a PRINCIPAL-COMPONENT ANALYSIS IN TIME in SYSREM's place (de Kok et al. 2013): per segment the leading
+ * eigenvectors of the exposures x exposures Gram matrix of the data -- the left singular vectors of the exposures x pixels
+ * matrix -- are fitted and removed.  The injection (steps 0 and 1), the outcome and the undo (steps 3 and 4) are
+ * trx_detrend_observed's, through the same state: either call undoes either, and pca -> detrend or detrend -> pca gives
+ * the second call the bits of a fresh one.  Every operation is IEEE double rounded once, no fused multiply-add; sums start
+ * from +0 in the order written; there are no atomics.  Per segment s over its pixels [first, last), W the set's weights:
+ * 2a. Exposure v is LIVE in s if W[v][p] > 0 for some p of the segment.  Column p is WHOLE if W[v][p] > 0 for every v live
+ *     in s and at least one v is live; nwhole[s] counts them.  x[v][p] = f0[v][p] where p is whole and v live, +0 elsewhere.
+ *     PCA has no definition under scattered masks (zero-filled entries where the data are ~ 1 would dominate the Gram
+ *     matrix): whole-column and whole-exposure masks are exact, columns with holes take no part in the fit -- they still
+ *     get coefficients and residuals in 2d.  SYSREM (trx_detrend_observed) is the tool for scattered masks.
+ * 2b. G[v][u] = sum over p of x[v][p] * x[u][p] for u >= v, in the order of the moments: lane l of 64 adds the pixels
+ *     first + l, first + l + 64, ... from +0, then the butterfly with partner lane ^ 32, 16, 8, 4, 2, 1.  G[u][v] = G[v][u].
+ * 2c. Eigenvectors by cyclic Jacobi in a fixed parallel order, nsweep sweeps, no convergence test.  A = G, V = I, m = nexp
+ *     rounded up to even.  A sweep is the rounds t = 0 .. m-2 of the circle tournament: round t has the pair (m-1, t) and, for
+ *     k = 1 .. m/2-1, ((t+k) mod (m-1), (t-k) mod (m-1)), each ordered p < q; pairs with q >= nexp are dropped.  Every
+ *     rotation of a round takes its parameters from A as the round finds it.  apq = A[p][q]; apq == 0: the pair is skipped,
+ *     nothing of A or V rewritten; otherwise
+ *       theta = (A[q][q] - A[p][p]) / (2.0 * apq);  t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0))
+ *       c = 1.0 / sqrt(t * t + 1.0);  s = t * c
+ *     Column phase, every row i, both old values read first: A[i][p] <- c A[i][p] - s A[i][q], A[i][q] <- s A[i][p] + c A[i][q],
+ *     the same for V.  Then the row phase, every column j: A[p][j] <- c A[p][j] - s A[q][j], A[q][j] <- s A[p][j] + c A[q][j];
+ *     then A[p][q] = A[q][p] = +0.  Each product is rounded, then the sum or difference.  After the last sweep lambda_j =
+ *     A[j][j], offdiag[s] = max over p < q of |A[p][q]|; the j are ranked by descending lambda, ties by ascending j, a lambda
+ *     that is not > 0 and finite (NaN and +-inf included) ranking as 0; component
+ *     i is the column of V of rank i if its lambda is > 0 and finite, the zero vector otherwise; the entry of largest
+ *     magnitude, the first on ties, is made positive by negating the column (0 - x: a zero entry stays +0).  U[s][v][i] is that column, eigen[s][i] its
+ *     lambda (+0 for a zero vector).  An empty segment, or one without a whole column, has G = 0: every vector is zero (singular
+ *     pivots of the filter, counted by nsingular).
+ * 2d. Every column, the ones with holes included: coef[i][p] = sum over v ascending of U[s][v][i] * y[v][p], y = f0 where
+ *     W > 0, +0 elsewhere; r = f0, then for i ascending r[v][p] = r[v][p] - U[s][v][i] * coef[i][p].
+ * The Gram route squares the condition number: components whose singular value is below about 1e-8 of the largest are
+ * noise -- far below anything a detrend of <= TRX_FILTER_MAX components asks for.  offdiag against eigen[s][0] tells how
+ * far nsweep sweeps have converged: nothing is left after 8 sweeps at a dozen exposures; at 100 exposures 8 sweeps leave up to
+ * 3e-11 of eigen[s][0] where G's spectrum is crowded (fewer whole columns than exposures, or many close noise eigenvalues), 10
+ * to 12 sweeps reach rounding level; the leading components are converged long before.
+ * TRX_E_ARG, the reason in trx_last_error, nothing touched, checked in this order: no observed set; nexp above
+ * TRX_PCA_MAX_EXP; ncomp < 0, above TRX_FILTER_MAX or above nexp; nsweep < 1 or above TRX_PCA_MAX_SWEEP; then inject, pad and
+ * the injection's arguments as trx_detrend_observed has them.  TRX_E_UNSUPPORTED on a shard.  A later TRX_E_HIP or
+ * TRX_E_NOMEM leaves the previous data and filter in force.  pc NULL or ncomp = 0 is trx_detrend_observed's undo.
+ * Not here: a batch form, shards, centring or standardising the columns ahead of the PCA (trx_weigh_observed and the filter
+ * carry that), a sweep count driven by convergence, more than TRX_PCA_MAX_EXP exposures. */
+#define TRX_PCA_MAX_SWEEP 32
+#define TRX_PCA_MAX_EXP   128
+typedef struct {
+  int32_t ncomp, nsweep;     /* components 1 .. min(TRX_FILTER_MAX, nexp) (0: undo); Jacobi sweeps 1 .. TRX_PCA_MAX_SWEEP */
+  int32_t inject, pad;       /* as trx_detrend */
+  double  p0, p1;
+} trx_pca;                   /* 32 bytes */
+int  trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum /* as trx_detrend_observed */,
+                      int32_t nshift, const double *shift, const trx_pca *pc,
+                      double *basis /* [nseg][nexp][ncomp] */, double *coef /* [ncomp][npix] */,
+                      double *data /* [nexp][npix]: the residuals now installed */, double *eigen /* [nseg][ncomp] */,
+                      double *offdiag /* [nseg] */, int64_t *nwhole /* [nseg] */,
+                      int64_t *nsingular, trx_debug *dbg);      /* every output may be NULL */
 
 /* Weighing the observed set by the scatter of its pixel columns, on the device: the step of a detection pipeline between
  * SYSREM and the map.  One call reads the data the handle holds, forms every column's variance in time and every

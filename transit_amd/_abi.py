@@ -117,6 +117,15 @@ class TrxDetrend(C.Structure):
                 ("p0", C.c_double), ("p1", C.c_double)]
 
 
+PCA_MAX_SWEEP = 32              # TRX_PCA_MAX_SWEEP: the most Jacobi sweeps of trx_pca_observed
+PCA_MAX_EXP = 128               # TRX_PCA_MAX_EXP: the most exposures of a set trx_pca_observed takes
+
+
+class TrxPca(C.Structure):
+    _fields_ = [("ncomp", C.c_int32), ("nsweep", C.c_int32), ("inject", C.c_int32), ("pad", C.c_int32),
+                ("p0", C.c_double), ("p1", C.c_double)]
+
+
 SCATTER_NONE, SCATTER_VARIANCE, SCATTER_MASK = 0, 1, 2      # TRX_SCATTER_*: the kinds of trx_weigh_observed
 
 
@@ -373,6 +382,16 @@ def bind_sysrem_api(lib):
                                          C.POINTER(TrxDetrend), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int64),
                                          C.POINTER(TrxDebug)]
     lib.trx_detrend_observed.restype = C.c_int
+    return lib
+
+
+def bind_pca_api(lib):
+    """argtypes/restypes of the principal-component entry point (trx_pca_observed)."""
+    i64p = C.POINTER(C.c_int64)
+    lib.trx_pca_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                     C.POINTER(TrxPca), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, i64p, i64p,
+                                     C.POINTER(TrxDebug)]
+    lib.trx_pca_observed.restype = C.c_int
     return lib
 
 

@@ -50,6 +50,7 @@
 #include "trx_filter.hip.h"
 #include "trx_wfilter.hip.h"
 #include "trx_sysrem.hip.h"
+#include "trx_pca.hip.h"
 #include "trx_scatter.hip.h"
 #include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
@@ -65,6 +66,7 @@
 #include "../trx_expmap.h"
 #include "../trx_wfilter.h"
 #include "../trx_sysrem.h"
+#include "../trx_pca.h"
 #include "../trx_scatter.h"
 #include "../trx_launch.h"
 #include "../trx_hpdata.h"

@@ -978,6 +978,65 @@ static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend 
   return TRX_OK;
 }
 
+// steps 0 and 1 of a detrending call (who), on the main queue: the raw data, or the injected data, into h->d_sr_r.  With an
+// injection the pairs come from the pixel stage alone, as trx_run_exposed (or, without a table, trx_run_pixels) runs it -- no
+// moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for.  cells, r_bytes, c_bytes and
+// elem_blocks: the call's extents.
+static int detrend_fill(trx_handle *h, const char *who, const ObservedSet *O, bool inject, double p0, double p1, const trx_atm *a, const trx_opts *o,
+                        double *spectrum, int32_t nshift, const double *shift, trx_debug *dbg, int64_t cells, size_t r_bytes, size_t c_bytes, int64_t elem_blocks)
+{
+  if (inject) {
+    PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
+    if (const int rc = pixel_run(h, who, a, o, spectrum, PR, shift, dbg)) return rc;
+    if (PR.ext.pairs != cells || h->d_pixout.bytes < PR.ext.pair_bytes) return fail(h, TRX_E_HIP, "internal: the injection's pairs are not the observed set's size");
+  }
+  if (const int rc = ensure(h, h->d_sr_r, r_bytes)) return rc;
+  const DevBuf &raw = O->d_data.raw();
+  if (!raw.p || raw.bytes < r_bytes) return fail(h, TRX_E_HIP, "internal: the observed set's data are not its size");
+  if (inject) {
+    SysremInjectArgs IA{};
+    IA.pairs = h->d_pixout.as<double2>(); IA.raw = raw.as<double>(); IA.gain = O->d_gain.as<double>(); IA.r = h->d_sr_r.as<double>();
+    IA.npix = O->npix; IA.cells = cells; IA.p0 = p0; IA.p1 = p1;
+    if ((IA.gain && O->d_gain.bytes < c_bytes) || !grid_ok(elem_blocks))
+      return fail(h, TRX_E_HIP, "internal: incomplete arguments for the injection kernel (not launched)");
+    hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
+    HIPCHK(h, hipGetLastError());
+  } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, r_bytes, hipMemcpyDeviceToDevice, h->stream));
+  return TRX_OK;
+}
+
+// step 3 of a detrending call (who), every kernel finished and U [nseg][nexp][ncomp] in h->sr_basis: the weighted filter of U
+// as trx_set_weighted_filter makes it -- it reads the set's weights as trx_set_observed installed them, not its data --, the
+// outputs, and only then the swap, which puts those weights back in force
+static int detrend_install(trx_handle *h, const char *who, ObservedSet *O, int32_t ncomp, size_t basis_bytes, size_t coef_bytes, size_t r_bytes,
+                           double *basis, double *coef, double *data, int64_t *nsingular)
+{
+  std::string msg; int rc;
+  if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, ncomp, msg, who))) return fail(h, rc, msg);
+  const trx_wfilter wf{ncomp, 0, h->sr_basis.data()};
+  std::unique_ptr<FilterSet> S; int64_t nsing = 0;
+  if ((rc = make_wfilter_set(h, &wf, S, &nsing, &O->d_weight.raw()))) return rc;
+  if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, coef_bytes, hipMemcpyDeviceToHost));
+  if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, r_bytes, hipMemcpyDeviceToHost));
+  if (basis) std::memcpy(basis, h->sr_basis.data(), basis_bytes);
+  O->d_data.uncover(h->d_hp_r);                         // (as in the undo)
+  O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
+  install_filter_set(h, S);
+  if (nsingular) *nsingular = nsing;
+  return TRX_OK;
+}
+
+// the undo of either detrending call: the raw data back, the filter slot cleared
+static int detrend_undo(trx_handle *h, ObservedSet *O, int64_t *nsingular)
+{
+  // (the buffers of the residuals and of a weigh call's weights are kept for the next call when the handle has none)
+  O->d_data.uncover(h->d_hp_r);                         // (a high-pass over the data goes first: its buffer is kept for the next one)
+  O->d_data.restore(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
+  h->filter.reset();
+  if (nsingular) *nsingular = 0;
+  return TRX_OK;
+}
+
 int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
                          const trx_detrend *dt, double *basis, double *coef, double *data, int64_t *nsingular, trx_debug *dbg)
 {
@@ -988,60 +1047,109 @@ int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   if (const int rc = detrend_checks(P, dt, a, o, nshift, shift, msg)) return fail(h, rc, msg);
   ObservedSet *const O = h->observed.get();
   HIPCHK(h, hipSetDevice(h->device));
-  if (detrend_is_undo(dt)) {
-    // (the buffers of the residuals and of a weigh call's weights are kept for the next call when the handle has none)
-    O->d_data.uncover(h->d_hp_r);                       // (a high-pass over the data goes first: its buffer is kept for the next one)
-    O->d_data.restore(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
-    h->filter.reset();
-    if (nsingular) *nsingular = 0;
-    return TRX_OK;
-  }
+  if (detrend_is_undo(dt)) return detrend_undo(h, O, nsingular);
   std::vector<FilterTile> tiles;
   if (const int rc = sysrem_tiles(P, tiles, msg)) return fail(h, rc, msg);
   const int64_t ntiles = (int64_t)tiles.size();
   const SysremExtents X = sysrem_extents(O->npix, O->nexp, O->nseg, dt->ncomp, dt->niter, ntiles, kPixBlock, kFiltWaves, kMomWaves);
   try { h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
-  // the pairs of the injection: the pixel stage alone, as trx_run_exposed (or, without a table, trx_run_pixels) runs it -- no
-  // moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for
-  if (dt->inject) {
-    PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
-    if (const int rc = pixel_run(h, who, a, o, spectrum, PR, shift, dbg)) return rc;
-    if (PR.ext.pairs != X.cells || h->d_pixout.bytes < PR.ext.pair_bytes) return fail(h, TRX_E_HIP, "internal: the injection's pairs are not the observed set's size");
-  }
   int rc;
-  if ((rc = ensure(h, h->d_sr_r, X.r_bytes)) || (rc = ensure(h, h->d_sr_a, X.a_bytes)) || (rc = ensure(h, h->d_sr_c, X.c_bytes)) ||
+  // step 0 and 1: the raw data, or the injected data, into the call's own buffer
+  if ((rc = detrend_fill(h, who, O, dt->inject != 0, dt->p0, dt->p1, a, o, spectrum, nshift, shift, dbg, X.cells, X.r_bytes, X.c_bytes, X.elem_blocks)))
+    return rc;
+  if ((rc = ensure(h, h->d_sr_a, X.a_bytes)) || (rc = ensure(h, h->d_sr_c, X.c_bytes)) ||
       (rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = ensure(h, h->d_sr_basis, X.basis_bytes)) || (rc = upload(h, h->d_sr_tiles, tiles)))
     return rc;
-  // step 0 and 1: the raw data, or the injected data, into the call's own buffer
-  const DevBuf &raw = O->d_data.raw();
-  if (!raw.p || raw.bytes < X.r_bytes) return fail(h, TRX_E_HIP, "internal: the observed set's data are not its size");
-  if (dt->inject) {
-    SysremInjectArgs IA{};
-    IA.pairs = h->d_pixout.as<double2>(); IA.raw = raw.as<double>(); IA.gain = O->d_gain.as<double>(); IA.r = h->d_sr_r.as<double>();
-    IA.npix = O->npix; IA.cells = X.cells; IA.p0 = dt->p0; IA.p1 = dt->p1;
-    if ((IA.gain && O->d_gain.bytes < X.c_bytes) || !grid_ok(X.elem_blocks))
-      return fail(h, TRX_E_HIP, "internal: incomplete arguments for the injection kernel (not launched)");
-    hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)X.elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
-    HIPCHK(h, hipGetLastError());
-  } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, X.r_bytes, hipMemcpyDeviceToDevice, h->stream));
   // step 2
   if ((rc = launch_sysrem(h, O, dt, X, ntiles))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->sr_basis.data(), h->d_sr_basis.p, X.basis_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished; the tiles' staging vector may go)
-  // step 3: the weighted filter of U as trx_set_weighted_filter makes it -- it reads the set's weights as trx_set_observed
-  // installed them, not its data --, the outputs, and only then the swap, which puts those weights back in force
-  if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, dt->ncomp, msg))) return fail(h, rc, msg);
-  const trx_wfilter wf{dt->ncomp, 0, h->sr_basis.data()};
-  std::unique_ptr<FilterSet> S; int64_t nsing = 0;
-  if ((rc = make_wfilter_set(h, &wf, S, &nsing, &O->d_weight.raw()))) return rc;
-  if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, X.coef_bytes, hipMemcpyDeviceToHost));
-  if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, X.r_bytes, hipMemcpyDeviceToHost));
-  if (basis) std::memcpy(basis, h->sr_basis.data(), X.basis_bytes);
-  O->d_data.uncover(h->d_hp_r);                         // (as in the undo)
-  O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
-  install_filter_set(h, S);
-  if (nsingular) *nsingular = nsing;
-  return TRX_OK;
+  // step 3
+  return detrend_install(h, who, O, dt->ncomp, X.basis_bytes, X.coef_bytes, X.r_bytes, basis, coef, data, nsingular);
+}
+
+// ---- the principal components of the observed set in SYSREM's place (trx_pca.hip.h) ------------------
+// the PCA kernels of pc over the data in h->d_sr_r, on the main queue: X the call's extents, ntiles the tiles in h->d_sr_tiles
+static int launch_pca(trx_handle *h, const ObservedSet *O, const trx_pca *pc, const PcaExtents &X, int64_t ntiles)
+{
+  PcaArgs A{};
+  A.r = h->d_sr_r.as<double>(); A.weight = O->d_weight.raw().as<double>(); A.tiles = h->d_sr_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
+  A.live = h->d_pc_live.as<int32_t>(); A.whole = h->d_pc_whole.as<int32_t>(); A.G = h->d_pc_g.as<double>(); A.Vt = h->d_pc_v.as<double>();
+  A.coef = h->d_sr_coef.as<double>(); A.basis = h->d_sr_basis.as<double>(); A.eigen = h->d_pc_eigen.as<double>(); A.offdiag = h->d_pc_off.as<double>();
+  A.nwhole = h->d_pc_nwhole.as<int64_t>();
+  A.npix = O->npix; A.ntiles = ntiles; A.nrows = X.rows; A.gram_tiles = X.gram_tiles;
+  A.nexp = O->nexp; A.nseg = O->nseg; A.ncomp = pc->ncomp; A.nsweep = pc->nsweep; A.stride = X.stride;
+  // (every address the kernels read or write: the data and the weights [nexp][npix], the tiles -- which cover [0, npix) and
+  // name segments below nseg --, the bounds [nseg + 1], live [nseg][nexp], whole [npix], G and Vt [nseg][nexp][nexp], coef
+  // [ncomp][npix], U [nseg][nexp][ncomp], eigen [nseg][ncomp], offdiag and nwhole [nseg], and X.lds_bytes of LDS: A
+  // [nexp][stride] with the round's tables behind it)
+  if (!A.r || !A.tiles || !A.live || !A.whole || !A.G || !A.Vt || !A.coef || !A.basis || !A.eigen || !A.offdiag || !A.nwhole ||
+      !observed_set_whole(*O, O->d_weight.raw(), false) || ntiles < 1 || A.nexp > TRX_PCA_MAX_EXP || A.ncomp < 1 || A.ncomp > TRX_FILTER_MAX ||
+      A.ncomp > A.nexp || A.nsweep < 1 || A.nsweep > TRX_PCA_MAX_SWEEP || A.stride < A.nexp ||
+      h->d_sr_r.bytes < X.r_bytes || (A.weight && O->d_weight.raw().bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
+      h->d_pc_live.bytes < X.live_bytes || h->d_pc_whole.bytes < X.whole_bytes || h->d_pc_g.bytes < X.g_bytes || h->d_pc_v.bytes < X.g_bytes ||
+      h->d_sr_coef.bytes < X.coef_bytes || h->d_sr_basis.bytes < X.basis_bytes || h->d_pc_eigen.bytes < X.eigen_bytes ||
+      h->d_pc_off.bytes < X.offdiag_bytes || h->d_pc_nwhole.bytes < X.nwhole_bytes || !X.grid_ok)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the PCA kernels (not launched)");
+  // (the Jacobi block's LDS is dynamic and above the default limit of a launch at the larger sets: raised once per handle, to
+  // the most a workgroup may take -- X.grid_ok holds every call's own size under it)
+  if (!h->pc_lds_raised) {
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pca_jacobi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPcaLdsMost));
+    h->pc_lds_raised = true;
+  }
+  // (a launch that fails is named)
+  auto launched = [&](const char *kernel) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRX_OK : fail(h, TRX_E_HIP, std::string("trx_pca_observed: launch of ") + kernel + ": " + hipGetErrorString(e));
+  };
+  int rc;
+  hipLaunchKernelGGL(k_pca_live, dim3((unsigned)X.row_blocks), dim3(64 * kMomWaves), 0, h->stream, A);
+  if ((rc = launched("k_pca_live"))) return rc;
+  hipLaunchKernelGGL(k_pca_whole, dim3((unsigned)X.tile_blocks), dim3(64 * kFiltWaves), 0, h->stream, A);
+  if ((rc = launched("k_pca_whole"))) return rc;
+  hipLaunchKernelGGL(k_pca_gram, dim3((unsigned)X.gram_blocks), dim3(64 * kPcaGramWaves), 0, h->stream, A);
+  if ((rc = launched("k_pca_gram"))) return rc;
+  hipLaunchKernelGGL(k_pca_jacobi, dim3((unsigned)X.jacobi_blocks), dim3(kPcaBlock), X.lds_bytes, h->stream, A);
+  if ((rc = launched("k_pca_jacobi"))) return rc;
+  hipLaunchKernelGGL(k_pca_project, dim3((unsigned)X.tile_blocks), dim3(64 * kFiltWaves), 0, h->stream, A);
+  return launched("k_pca_project");
+}
+
+int trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift, const trx_pca *pc,
+                     double *basis, double *coef, double *data, double *eigen, double *offdiag, int64_t *nwhole, int64_t *nsingular, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_pca_observed";
+  const ProductState P = product_state(h);
+  std::string msg;
+  if (const int rc = pca_checks(P, pc, a, o, nshift, shift, msg)) return fail(h, rc, msg);
+  ObservedSet *const O = h->observed.get();
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pca_is_undo(pc)) return detrend_undo(h, O, nsingular);
+  std::vector<FilterTile> tiles;
+  if (const int rc = sysrem_tiles(P, tiles, msg)) return fail(h, rc, msg);
+  const int64_t ntiles = (int64_t)tiles.size();
+  const PcaExtents X = pca_extents(O->npix, O->nexp, O->nseg, pc->ncomp, ntiles, kPixBlock, kFiltWaves, kMomWaves);
+  try { h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
+  int rc;
+  // step 0 and 1, as trx_detrend_observed's
+  if ((rc = detrend_fill(h, who, O, pc->inject != 0, pc->p0, pc->p1, a, o, spectrum, nshift, shift, dbg, X.cells, X.r_bytes, X.c_bytes, X.elem_blocks)))
+    return rc;
+  if ((rc = ensure(h, h->d_pc_live, X.live_bytes)) || (rc = ensure(h, h->d_pc_whole, X.whole_bytes)) || (rc = ensure(h, h->d_pc_g, X.g_bytes)) ||
+      (rc = ensure(h, h->d_pc_v, X.g_bytes)) || (rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = ensure(h, h->d_sr_basis, X.basis_bytes)) ||
+      (rc = ensure(h, h->d_pc_eigen, X.eigen_bytes)) || (rc = ensure(h, h->d_pc_off, X.offdiag_bytes)) || (rc = ensure(h, h->d_pc_nwhole, X.nwhole_bytes)) ||
+      (rc = upload(h, h->d_sr_tiles, tiles)))
+    return rc;
+  // step 2
+  if ((rc = launch_pca(h, O, pc, X, ntiles))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->sr_basis.data(), h->d_sr_basis.p, X.basis_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished; the tiles' staging vector may go)
+  // the fit's own outputs (a non-finite U refuses with every output untouched), then step 3: the swap comes last
+  if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, pc->ncomp, msg, who))) return fail(h, rc, msg);
+  if (eigen) HIPCHK(h, hipMemcpy(eigen, h->d_pc_eigen.p, X.eigen_bytes, hipMemcpyDeviceToHost));
+  if (offdiag) HIPCHK(h, hipMemcpy(offdiag, h->d_pc_off.p, X.offdiag_bytes, hipMemcpyDeviceToHost));
+  if (nwhole) HIPCHK(h, hipMemcpy(nwhole, h->d_pc_nwhole.p, X.nwhole_bytes, hipMemcpyDeviceToHost));
+  return detrend_install(h, who, O, pc->ncomp, X.basis_bytes, X.coef_bytes, X.r_bytes, basis, coef, data, nsingular);
 }
 
 // ---- weighing the observed set by its columns' scatter (trx_scatter.hip.h) --------------------------

@@ -252,6 +252,11 @@ struct trx_handle {
   // observed set's data when it succeeds), the time vector [nseg][nexp], the column vector [npix], coef [ncomp][npix],
   // U [nseg][nexp][ncomp] (its host copy: sr_basis) and the tiles of the set's segments
   DevBuf d_sr_r, d_sr_a, d_sr_c, d_sr_coef, d_sr_basis, d_sr_tiles; std::vector<double> sr_basis;
+  // trx_pca_observed (trx_pca.hip.h), grown on demand beside the detrend's residuals, coef, U and tiles, which it shares: the
+  // live flags [nseg][nexp] and the whole flags [npix] (int32), the Gram matrices and the transposed eigenvector matrices
+  // [nseg][nexp][nexp] each, eigen [nseg][ncomp], offdiag [nseg] and nwhole [nseg] (int64)
+  DevBuf d_pc_live, d_pc_whole, d_pc_g, d_pc_v, d_pc_eigen, d_pc_off, d_pc_nwhole;
+  bool pc_lds_raised = false;                          // k_pca_jacobi's limit of dynamic LDS has been raised on this handle's device
   // trx_weigh_observed (trx_scatter.hip.h), grown on demand: the weights [nexp][npix] a call builds (swapped with the observed
   // set's when it succeeds), the variances [npix], the medians [nseg], the columns' flags [npix] and the tiles; the factor
   // and the pivot flags a call makes for the installed weighted filter (swapped with the filter's)

@@ -21,6 +21,28 @@ namespace trx {
 // Whether the call is the undo (dt NULL or ncomp = 0): the raw data back, the filter slot cleared.
 inline bool detrend_is_undo(const trx_detrend *dt) { return !dt || dt->ncomp == 0; }
 
+// What the injection's part of a detrending call refuses, and the shard after it: inject, pad, p0, p1, a, o, the shifts.  who:
+// the call that names itself in the text; mirror: the host routine the shard's refusal points to.
+inline int detrend_inject_checks(const char *who, const char *mirror, const ProductState &S, int32_t inject, int32_t pad, double p0, double p1,
+                                 const void *a, const void *o, int32_t nshift, const double *shift, std::string &msg)
+{
+  auto no = [&](int code, const std::string &what) { return refuse(msg, code, std::string(who) + ": " + what); };
+  if (inject != 0 && inject != 1) return no(TRX_E_ARG, "inject must be 0 or 1");
+  if (pad != 0) return no(TRX_E_ARG, "pad must be 0");
+  if (inject) {
+    if (!std::isfinite(p0)) return no(TRX_E_ARG, "p0 must be finite");
+    if (!std::isfinite(p1)) return no(TRX_E_ARG, "p1 must be finite");
+    if (!a) return no(TRX_E_ARG, "a is NULL");
+    if (!o) return no(TRX_E_ARG, "o is NULL");
+    if (!shift) return no(TRX_E_ARG, "shift is NULL");
+    if (nshift != S.nexp) return no(TRX_E_ARG, "nshift " + std::to_string(nshift) + " is not the observed set's nexp " + std::to_string(S.nexp));
+    if (const int rc = pixel_run_checks(who, nshift, S.npix, shift, msg)) return rc;
+  }
+  // (the injection's pairs are a run's: the partial pairs of a shard are not the model)
+  if (S.windowed) return no(TRX_E_UNSUPPORTED, std::string("this handle's shard is not the whole grid; detrend on the host (") + mirror + ")");
+  return TRX_OK;
+}
+
 // What trx_detrend_observed refuses, in the header's order.  The undo is checked for the observed set (and ncomp's sign)
 // alone; a call that detrends for everything.
 inline int detrend_checks(const ProductState &S, const trx_detrend *dt, const void *a, const void *o, int32_t nshift, const double *shift, std::string &msg)
@@ -34,20 +56,7 @@ inline int detrend_checks(const ProductState &S, const trx_detrend *dt, const vo
   if (dt->ncomp == 0) return TRX_OK;
   if (dt->niter < 1) return no(TRX_E_ARG, "niter < 1");
   if (dt->niter > TRX_SYSREM_MAX_ITER) return no(TRX_E_ARG, "niter above TRX_SYSREM_MAX_ITER (" + std::to_string(TRX_SYSREM_MAX_ITER) + ")");
-  if (dt->inject != 0 && dt->inject != 1) return no(TRX_E_ARG, "inject must be 0 or 1");
-  if (dt->pad != 0) return no(TRX_E_ARG, "pad must be 0");
-  if (dt->inject) {
-    if (!std::isfinite(dt->p0)) return no(TRX_E_ARG, "p0 must be finite");
-    if (!std::isfinite(dt->p1)) return no(TRX_E_ARG, "p1 must be finite");
-    if (!a) return no(TRX_E_ARG, "a is NULL");
-    if (!o) return no(TRX_E_ARG, "o is NULL");
-    if (!shift) return no(TRX_E_ARG, "shift is NULL");
-    if (nshift != S.nexp) return no(TRX_E_ARG, "nshift " + std::to_string(nshift) + " is not the observed set's nexp " + std::to_string(S.nexp));
-    if (const int rc = pixel_run_checks(who, nshift, S.npix, shift, msg)) return rc;
-  }
-  // (the injection's pairs are a run's: the partial pairs of a shard are not the model)
-  if (S.windowed) return no(TRX_E_UNSUPPORTED, "this handle's shard is not the whole grid; detrend on the host (xcor.sysrem_reference)");
-  return TRX_OK;
+  return detrend_inject_checks(who, "xcor.sysrem_reference", S, dt->inject, dt->pad, dt->p0, dt->p1, a, o, nshift, shift, msg);
 }
 
 // The tiles of the observed set's segments, filter_layout's: up to 64 consecutive pixels of one segment each, a segment's
@@ -89,14 +98,14 @@ inline SysremExtents sysrem_extents(int64_t npix, int32_t nexp, int32_t nseg, in
   return X;
 }
 
-// the first non-finite entry of U [nseg][nexp][ncomp] names the call's refusal
-inline int sysrem_basis_check(const double *U, int32_t nseg, int32_t nexp, int32_t ncomp, std::string &msg)
+// the first non-finite entry of U [nseg][nexp][ncomp] names the call's refusal (who: the call, trx_pca_observed's too)
+inline int sysrem_basis_check(const double *U, int32_t nseg, int32_t nexp, int32_t ncomp, std::string &msg, const char *who = "trx_detrend_observed")
 {
   for (int32_t s = 0; s < nseg; s++)
     for (int32_t v = 0; v < nexp; v++)
       for (int32_t i = 0; i < ncomp; i++)
         if (!std::isfinite(U[((size_t)s * (size_t)nexp + (size_t)v) * (size_t)ncomp + (size_t)i]))
-          return refuse(msg, TRX_E_ARG, "trx_detrend_observed: component " + std::to_string(i) + " of segment " + std::to_string(s) + " is not finite");
+          return refuse(msg, TRX_E_ARG, std::string(who) + ": component " + std::to_string(i) + " of segment " + std::to_string(s) + " is not finite");
   return TRX_OK;
 }
 

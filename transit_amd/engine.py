@@ -214,6 +214,7 @@ def hip_library():
         _abi.bind_exposures_api(lib)
         _abi.bind_expmap_api(lib)
         _abi.bind_sysrem_api(lib)
+        _abi.bind_pca_api(lib)
         _abi.bind_scatter_api(lib)
         _abi.bind_hpdata_api(lib)
         lib.trx_device_count.restype = C.c_int
@@ -242,10 +243,14 @@ def _dp(x):
 class Detrended:
     """What Engine.detrend_observed returns: basis [nseg, nexp, ncomp] the fitted time vectors U, coef [ncomp, npix] their
     column vectors, data [nexp, npix] the residuals now installed as the observed data (None after the undo), nsingular the
-    columns the installed weighted filter's pivot rule makes dead, spectrum the injection run's spectrum (None without)."""
+    columns the installed weighted filter's pivot rule makes dead, spectrum the injection run's spectrum (None without).
+    Engine.pca_observed returns one with three more: eigen [nseg, ncomp] the components' eigenvalues of the Gram matrix,
+    offdiag [nseg] the largest off-diagonal entry the sweeps left, nwhole [nseg] the columns that took part in the fit
+    (None from detrend_observed, after the undo and with outputs=False)."""
 
-    def __init__(self, basis, coef, data, nsingular, spectrum=None):
+    def __init__(self, basis, coef, data, nsingular, spectrum=None, eigen=None, offdiag=None, nwhole=None):
         self.basis, self.coef, self.data, self.nsingular, self.spectrum = basis, coef, data, nsingular, spectrum
+        self.eigen, self.offdiag, self.nwhole = eigen, offdiag, nwhole
 
 
 class Weighed:
@@ -532,6 +537,37 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_detrend_observed", self._last_error())
         return Detrended(basis if n else None, coef if n else None, data if n else None, int(nsing.value), spec)
+
+    def pca_observed(self, ncomp: int, nsweep: int = 8, inject=None, outputs: bool = True) -> "Detrended":
+        """trx_pca_observed: detrend_observed with a principal-component analysis in time in SYSREM's place, on the device,
+        always from the RAW data of set_observed -- per segment the ncomp leading eigenvectors of the Gram matrix of the
+        whole columns (those no live exposure masks) by nsweep Jacobi sweeps in a fixed order (xcor.pca_reference, bit for
+        bit), removed from every column.  inject, the outcome, outputs=False and the undo (ncomp = 0) are
+        detrend_observed's; either call undoes either.  Scattered masks keep a column out of the fit: SYSREM is the tool
+        for those.  Returns a Detrended with eigen [nseg, ncomp], offdiag [nseg] and nwhole [nseg] beside basis, coef and
+        data (all None after the undo or with outputs=False)."""
+        nexp, nseg = getattr(self, "mom_shape", (0, 0))
+        npix = getattr(self, "npix", 0)
+        pc = _abi.TrxPca(int(ncomp), int(nsweep), 0 if inject is None else 1, 0, 0.0, 0.0)
+        atm = opts = sh = spec = None
+        if inject is not None:
+            atm, opts, shifts, pc.p0, pc.p1 = inject
+            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+            spec = np.zeros(self.nwn)
+        n = max(int(ncomp), 0) if outputs else 0
+        basis, coef, data = np.zeros((nseg, nexp, n)), np.zeros((n, npix)), np.zeros((nexp, npix))
+        eigen, offdiag, nwhole = np.zeros((nseg, n)), np.zeros(nseg), np.zeros(nseg, dtype=np.int64)
+        nsing = C.c_int64(0)
+        rc = self._lib.trx_pca_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
+                                        _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), C.byref(pc),
+                                        _dp(basis) if n else None, _dp(coef) if n else None, _dp(data) if n else None,
+                                        _dp(eigen) if n else None, _dp(offdiag) if n else None,
+                                        nwhole.ctypes.data_as(C.POINTER(C.c_int64)) if n else None, C.byref(nsing), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_pca_observed", self._last_error())
+        if not n:
+            return Detrended(None, None, None, int(nsing.value), spec)
+        return Detrended(basis, coef, data, int(nsing.value), spec, eigen, offdiag, nwhole)
 
     def weigh_observed(self, kind: int, clip: float = 0.0, min_live: int = 2, outputs: bool = True) -> "Weighed":
         """trx_weigh_observed: the column-scatter weights of the observed set, on the device, from the data installed (the

@@ -74,6 +74,12 @@ mirrors here follow them bit for bit, the row sums included (64 lane sums, then 
     inject_reference(pairs, obs, p0, p1)                 f0 = F * (p0 g + p1) where b > 0, F elsewhere
     sysrem_reference(data, weight, seg_first, ncomp, niter)      (basis, coef, resid): the mirror of the device's SYSREM
 
+The same call with a principal-component analysis in time in SYSREM's place (Engine.pca_observed; trx_pca_observed): the
+Gram matrix of each segment's whole columns, its eigenvectors by a fixed number of Jacobi sweeps in a fixed parallel order.
+
+    jacobi_rounds(nexp)                                  the rounds of one sweep: lists of disjoint pairs (p, q), p < q < nexp
+    pca_reference(data, weight, seg_first, ncomp, nsweep)        (basis, coef, resid, eigen, offdiag, nwhole): the mirror
+
 The detection map with the filter applied to every cell's own model matrix (Engine.run_filtered_map /
 Batch.run_filtered_map; trx_run_filtered_map): a cell takes at every exposure the row of the lag NEAREST to its velocity,
 that matrix goes through the filter and the moments above, and the cell is the statistic added over the segments and
@@ -828,6 +834,109 @@ def sysrem_reference(data, weight, seg_first, ncomp: int, niter: int = 10):
                 coef[i, k] = c
                 r -= a[:, None] * c[None, :]
     return basis, coef, resid
+
+
+def jacobi_rounds(nexp: int):
+    """The rounds of one Jacobi sweep of trx_pca_observed over nexp exposures: the circle tournament of m = nexp rounded
+    up to even, round t = 0 .. m-2 holding the pair (m-1, t) and, for k = 1 .. m/2-1, ((t+k) mod (m-1), (t-k) mod (m-1)),
+    each ordered p < q, the pairs with q >= nexp (the dummy's) dropped.  A list of m - 1 lists of (p, q)."""
+    nexp = int(nexp)
+    if nexp < 1:
+        raise ValueError("jacobi_rounds: nexp >= 1")
+    m = nexp + (nexp & 1)
+    rounds = []
+    for t in range(m - 1):
+        pairs = [(m - 1, t)] + [((t + k) % (m - 1), (t - k) % (m - 1)) for k in range(1, m // 2)]
+        pairs = [(min(a, b), max(a, b)) for a, b in pairs]
+        rounds.append([(p, q) for p, q in pairs if q < nexp])
+    return rounds
+
+
+def _jacobi(G, nsweep: int, rounds):
+    """(A, V) after nsweep sweeps of the parallel-order Jacobi of trx_pca_observed on the symmetric G: every rotation of a
+    round takes its parameters from A as the round finds it, then the column phase (A and V), then the row phase (A)."""
+    A, V = G.copy(), np.eye(G.shape[0])
+    for _ in range(nsweep):
+        for pairs in rounds:
+            if not pairs:
+                continue
+            P, Q = np.array([p for p, _ in pairs]), np.array([q for _, q in pairs])
+            apq = A[P, Q]
+            on = apq != 0
+            if not on.any():
+                continue
+            P, Q, apq = P[on], Q[on], apq[on]
+            theta = (A[Q, Q] - A[P, P]) / (2.0 * apq)
+            t = np.where(theta >= 0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+            c = 1.0 / np.sqrt(t * t + 1.0)
+            s = t * c
+            for M in (A, V):
+                x, y = M[:, P].copy(), M[:, Q].copy()
+                M[:, P] = c * x - s * y
+                M[:, Q] = s * x + c * y
+            x, y = A[P, :].copy(), A[Q, :].copy()
+            A[P, :] = c[:, None] * x - s[:, None] * y
+            A[Q, :] = s[:, None] * x + c[:, None] * y
+            A[P, Q] = 0.0
+            A[Q, P] = 0.0
+    return A, V
+
+
+def pca_reference(data, weight, seg_first, ncomp: int, nsweep: int = 8):
+    """(basis [nseg, nexp, ncomp], coef [ncomp, npix], resid [nexp, npix], eigen [nseg, ncomp], offdiag [nseg], nwhole
+    [nseg] int64): the principal components in time per segment as trx_pca_observed defines them (include/transit_hip.h),
+    in numpy double in exactly its order -- the mirror of k_pca_live, k_pca_whole, k_pca_gram, k_pca_jacobi and
+    k_pca_project, bit for bit.  An exposure is live in a segment if any of its weights there is > 0, a column whole if
+    every live exposure's weight on it is; the Gram matrix of the whole columns' live entries is summed by row_sum, its
+    eigenvectors come from nsweep sweeps of jacobi_rounds, ranked by descending eigenvalue (ties by ascending index; one that is not > 0 and finite ranks as 0), the
+    entry of largest magnitude (the first on ties) made positive; an eigenvalue not > 0 or not finite gives the zero
+    vector.  The coefficients are sums over v ascending of U * y (y the data where W > 0, +0 elsewhere) on EVERY column,
+    the residuals f0 minus the components in ascending order."""
+    resid = np.array(data, dtype=np.float64)
+    if resid.ndim != 2:
+        raise ValueError("pca_reference: data of shape [nexp][npix]")
+    w_all = np.ones_like(resid) if weight is None else np.asarray(weight, dtype=np.float64)
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    nexp, npix, nseg = resid.shape[0], resid.shape[1], seg.size - 1
+    if not 0 <= ncomp <= nexp:
+        raise ValueError("pca_reference: ncomp in 0 .. nexp")
+    basis, coef = np.zeros((nseg, nexp, ncomp)), np.zeros((ncomp, npix))
+    eigen, offdiag, nwhole = np.zeros((nseg, ncomp)), np.zeros(nseg), np.zeros(nseg, dtype=np.int64)
+    rounds = jacobi_rounds(nexp)
+    upper = np.triu_indices(nexp, 1)
+    with np.errstate(all="ignore"):
+        for s in range(nseg):
+            k = slice(int(seg[s]), int(seg[s + 1]))
+            f0, on = resid[:, k], w_all[:, k] > 0
+            live = on.any(axis=1)
+            whole = on[live].all(axis=0) & live.any()
+            nwhole[s] = int(np.count_nonzero(whole))
+            x = np.where(whole[None, :] & live[:, None], f0, 0.0)
+            G = row_sum(x[:, None, :] * x[None, :, :])
+            A, V = _jacobi(G, nsweep, rounds)
+            lam = np.diagonal(A).copy()
+            off = np.abs(A[upper])
+            off = off[~np.isnan(off)]
+            offdiag[s] = off.max() if off.size else 0.0
+            valid = (lam > 0) & np.isfinite(lam)
+            order = np.argsort(-np.where(valid, lam, 0.0), kind="stable")
+            for i in range(ncomp):
+                j = int(order[i])
+                if not valid[j]:
+                    continue
+                col = V[:, j]
+                if col[int(np.argmax(np.abs(col)))] < 0:
+                    col = 0.0 - col                                  # (a zero entry stays +0)
+                basis[s, :, i], eigen[s, i] = col, lam[j]
+            U = basis[s]
+            y = np.where(on, f0, 0.0)
+            c = np.zeros((ncomp, f0.shape[1]))
+            for v in range(nexp):
+                c = c + U[v][:, None] * y[v][None, :]
+            coef[:, k] = c
+            for i in range(ncomp):
+                f0 -= U[:, i][:, None] * c[i][None, :]
+    return basis, coef, resid, eigen, offdiag, nwhole
 
 
 SCATTER_NONE, SCATTER_VARIANCE, SCATTER_MASK = 0, 1, 2    # TRX_SCATTER_*: the kinds of trx_weigh_observed
