@@ -58,6 +58,7 @@
 #include "../trx_groups.h"
 #include "../trx_plan.h"
 #include "../trx_sweep.h"
+#include "../trx_schedule.h"
 #include "../trx_table.h"
 #include "../trx_broaden.h"
 #include "../trx_vmap.h"
@@ -1296,8 +1297,11 @@ static int run_check(trx_handle *h, const trx_atm *a, const trx_opts *o)
 
 namespace {
 
-// the rest of a step behind its extinction: its combine, the CIA kernels ahead of the first optical depth, the optical depth itself
-struct SideWork { bool active = false, first = false; int r_top = 0, nc = 0, swept = 0; hipStream_t st_tau = nullptr; PendingCombine pc; };
+// the kernels' caps as the schedule reads them (trx_schedule.h)
+constexpr ScheduleCaps kScheduleCaps{kEmisRowsAbove, kTailRays, kTailSteps, 65536, kMaxChunk, kTauH};
+// (the side-queue tail waits for walk1 alone: the main queue may carry exactly one walk ahead of it -- tests/schedule_check.cpp
+// shows the tail unordered against a third walk)
+static_assert(kTailSteps == 2, "the side-queue tail waits for ev_walk1 alone: the main queue may carry exactly one walk ahead of it");
 
 struct Run {
   // ---- what the run is given
@@ -1337,29 +1341,27 @@ struct Run {
   const double *d_gw = nullptr, *d_gh0 = nullptr, *d_mw = nullptr, *d_mh0 = nullptr, *d_pw = nullptr, *d_ipv = nullptr, *d_ciadens = nullptr;
   double *d_out = nullptr; PlanInput P{};
 
-  // ---- the queues
-  // Streams.  The front end (inputs, layer maxima), the walks and everything that follows the
-  // LAST walk of the plan -- its combine, optical depth, the spectrum, the copies back -- sit on
-  // ONE queue: that chain is the critical path, and a hop between queues costs it ~30 us of
-  // signalling.  The combines and optical depths of the earlier steps go to a second queue, where
-  // they overlap the next step's walk.
-  const hipStream_t st_early = pipelined ? h->stream4 : st;
-  hipStream_t tst = nullptr;                   // the spectrum's queue
-  bool early_dirty = false;                    // work queued on st_early that st has not waited for
-  bool early_behind_inputs = false;            // the side queue has waited for this run's input copy
-  bool cia_queued = false;
+  // ---- the queues: which kernel of a pass goes where, behind which event, is the schedule's (trx_schedule.h); here
+  // its names become the handle's streams and events
+  hipStream_t tst = nullptr;                   // the spectrum's queue (pass)
+  hipStream_t queue(Queue q) const { return q == kQMain ? st : q == kQSide ? h->stream4 : h->stream2; }
+  hipEvent_t event(const QueueOp &op) const {
+    switch (op.ev) {
+      case kEvInputs: return h->ev_inputs; case kEvCia: return h->ev_cia; case kEvJoin: return h->ev_join; case kEvWalk1: return h->ev_walk1;
+      case kEvStepDone: return h->ev_ac[(size_t)op.idx]; case kEvRecordsFree: return h->ev_cb[(size_t)op.idx];
+      default: return nullptr;
+    }
+  }
 
   // ---- the ray tail (plan_first_pass; all false once the run has resumed)
-  bool tail_mode = false;                      // the pass ends in k_ray_tail
-  // tail_direct, tail_spec: it stores flags / the spectrum straight into pinned host memory
-  // two_queues, tail_on_side: its second walk may go / has gone to the side queue, the tail behind it
-  bool tail_direct = false, tail_spec = false, two_queues = false, tail_on_side = false;
+  TailChoice tail;
   TailArgs TA{}; int tail_nct = 0;
   const size_t tail_blocks = (size_t)((nsh + kTailRays - 1) / kTailRays);
 
   // ---- progress
-  int r_top = nr - 1, nchunks = 0, nwalks = 0; bool resumed = false;
-  SideWork pending;                            // a step's side work, queued behind the next step's walk
+  int r_top = nr - 1; bool resumed = false;
+  ScheduleState sched;                         // steps and walks queued so far, over both passes
+  CombineArgs comb[2];                         // a walk's combine, by record buffer, from its walk op to its combine op
   std::vector<uint8_t> layer_walked;           // [nr] (layout) layers swept by walk steps: 1 + the form that took them (stats)
 
   // ---- what comes back (results)
@@ -1389,11 +1391,12 @@ struct Run {
   int layout(); int front_maxima(); void host_inputs();            // (host_inputs: within front_maxima)
   int workspaces(); int front_inputs(); int grid_weights();        // (grid_weights: within front_inputs)
   int plan_first_pass(); int pass(); int resume(); int finish();
-  // what a pass is made of: its steps ...
-  int step(const PlanStep &s); int grid_step(const PlanStep &s); int line_step(const PlanStep &s, SideWork &S, bool &walked);
-  int side_work(SideWork &S); int queue_cia(); int join_early();
-  // ... the spectrum of what they swept, the way back
-  int spectrum_kernel(); int ray_tail(); int results();
+  // what a pass is made of: the ops of its schedule, issued one by one ...
+  int issue(const QueueOp &op); SweepMode sweep_mode(const QueueOp &op) const;
+  int walk(const QueueOp &op); int grid_step(const PlanStep &s); int cia_group(); int restore_rows(const QueueOp &op); int tau_substep(const QueueOp &op);
+  int spectrum_kernel(); int ray_tail();
+  // ... and the way back
+  int results(const PassEnd &end);
   // ... and what the run makes of that spectrum (want), behind it on its queue
   int product_kernels();
 };
@@ -1732,37 +1735,28 @@ int Run::plan_first_pass()
   }
   d_out = d_spectrum ? (double *)d_spectrum : h->d_spec.as<double>();
   plan_pass(P, r_top, stop_at_hint_ok, h->run_plan);
-  tail_mode = h->sw.ray_tail && stop_at_hint_ok && !count && h->ngroups > 0 && h->saved.empty() &&      // (profile 1: the same plan with events around its kernels)
-              nsh <= 65536 && h->nwn <= kEmisRowsAbove && nsh < 0x7fffffffLL / kTailRays && plan_is_tail(h->run_plan, kTailSteps);
-  // (flags into the pinned block the host reads; the spectrum into pinned memory too when the caller wants it on the host)
-  tail_direct = tail_mode && h->sw.tail_direct; tail_spec = tail_direct && spectrum && !d_spectrum && !want.bs && !want.px && !want.br;
-  if ((tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
+  TailIn ti;
+  ti.ray_tail = h->sw.ray_tail; ti.tail_direct = h->sw.tail_direct; ti.two_queues = h->sw.two_queues;
+  ti.stop_at_hint_ok = stop_at_hint_ok; ti.count = count; ti.has_lines = h->ngroups > 0; ti.no_saved = h->saved.empty(); ti.pipelined = pipelined;
+  ti.nsh = nsh; ti.nwn = h->nwn; ti.pass = &h->run_plan;
+  ti.host_spectrum = spectrum && !d_spectrum; ti.any_product = want.bs || want.px || want.br;
+  tail = tail_choice(ti, kScheduleCaps);
+  if ((tail.tail_spec || stage_spec) && (rc = ensure_pinned(h, h->h_spec, sizeof(double) * (size_t)nsh))) return rc;
   // Vertical rays: what the blocks of the tail add to the run's flags -- rays still open, deepest layer reached -- goes
   // into a pinned array, one entry per block, and the HOST adds it up behind the kernel (results).  The device-side sum was three
   // dependent device-scope atomics per block and, for the last block to arrive, four more round trips and a system-scope
   // fence: the kernel's last wave ended 5 us behind its last emission -- and every one of those fences writes back and
   // invalidates the L2 under the emission waves (8 us of emission with them, 3 without).  The run's status (slant
   // rays: what the reference exits on) goes into four slots behind the blocks' entries, one per code.
-  if (tail_direct && (rc = ensure_pinned(h, h->h_tailblk, 8 * tail_blocks + 16))) return rc;
-  two_queues = h->sw.two_queues && tail_direct && pipelined;      // (tail_direct: nothing behind the tail on the main queue)
-  return TRX_OK;
-}
-
-int Run::join_early()
-{
-  if (!early_dirty) return TRX_OK;
-  if (hipEventRecord(h->ev_join, st_early) != hipSuccess || hipStreamWaitEvent(st, h->ev_join, 0) != hipSuccess) return fail(h, TRX_E_HIP, "event");
-  early_dirty = false;
-  return TRX_OK;
+  return tail.tail_direct ? ensure_pinned(h, h->h_tailblk, 8 * tail_blocks + 16) : TRX_OK;
 }
 
 // CIA extinction (device), on a second stream: only the first optical-depth kernel needs
 // e_cs, so the (latency-bound) spline kernels overlap the first sweep step.  Queued right
 // after that step's kernels, which are what the GPU is waiting for.
-int Run::queue_cia()
+int Run::cia_group()
 {
   const auto t0 = std::chrono::steady_clock::now();
-  if (hipStreamWaitEvent(h->stream2, h->ev_inputs, 0) != hipSuccess) return fail(h, TRX_E_HIP, "event");
   if (extras_on) {        // (ahead of the first optical depth like everything on this queue)
     TauArgs X{};
     model_args(X);
@@ -1777,44 +1771,33 @@ int Run::queue_cia()
     hipLaunchKernelGGL(k_slant_geometry, dim3((unsigned)(nr + nr - 2)), dim3(64), 0, h->stream2, G);
   }
   if (const int rcc = cia_device(h, a, o, d_tempk, d_ciadens, h->stream2)) return rcc;
-  if (hipEventRecord(h->ev_cia, h->stream2) != hipSuccess) return fail(h, TRX_E_HIP, "event");
   ms_cia = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  cia_queued = true;
   return TRX_OK;
 }
 
-int Run::side_work(SideWork &S)
+// layers restored from an earlier run (trx_restore_extinction): their rows as they were saved
+int Run::restore_rows(const QueueOp &op)
 {
-  // The side queue's first work of a run waits for the inputs explicitly.  (Every step kind of today queues it behind
-  // an event recorded on the main queue after the copy -- a walk's, a sweep's -- but that is a rule nothing states.)
-  if (S.st_tau != st && !early_behind_inputs) { HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_inputs, 0)); early_behind_inputs = true; }
-  int rc = launch_combine(h, S.pc, sp);
-  if (rc) return rc;
-  if (S.first) {
-    if ((rc = queue_cia())) return rc;
-    lap("cia");
-    HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_cia, 0));
+  const PlanStep &s = h->run_plan[(size_t)op.step];
+  for (int c = 0; c < s.nc; c++) {
+    const int r = s.r_top - c;
+    if (h->saved[(size_t)r])
+      HIPCHK(h, hipMemcpyAsync(h->d_e.as<double>() + (size_t)r * nsh, h->d_e_saved.as<double>() + (size_t)r * nsh, sizeof(double) * (size_t)nsh,
+                               hipMemcpyDeviceToDevice, queue(op.q)));
   }
-  if (S.st_tau == st) { if ((rc = join_early())) return rc; }       // the optical depths of the earlier steps
-  else early_dirty = true;
-  if (!h->saved.empty())        // layers restored from an earlier run (trx_restore_extinction): their rows as they were saved
-    for (int c = 0; c < S.nc; c++) {
-      const int r = S.r_top - c;
-      if (h->saved[(size_t)r])
-        HIPCHK(h, hipMemcpyAsync(h->d_e.as<double>() + (size_t)r * nsh, h->d_e_saved.as<double>() + (size_t)r * nsh, sizeof(double) * (size_t)nsh,
-                                 hipMemcpyDeviceToDevice, S.st_tau));
-    }
-  if (prof && spans.begin(Spans::kTau, S.st_tau)) return fail(h, TRX_E_HIP, "event");
-  const int tau_cap = vertical ? kMaxChunk : kTauH;
-  for (int done = 0; done < S.nc; ) {          // optical depth in sub-steps of at most tau_cap layers
-    int nt = std::min(tau_cap, S.nc - done);
-    if (S.swept == 0 && done == 0) nt = std::min(S.nc, std::max(nt, 3));
-    TauArgs T{};
-    tau_args(T, S.r_top - done, nt);
-    launch_tau(T, S.st_tau);
-    done += nt;
-  }
-  if (prof && spans.end(S.st_tau)) return fail(h, TRX_E_HIP, "event");
+  return TRX_OK;
+}
+
+// one optical-depth sub-step; a profiled run brackets the sub-steps of a step together
+int Run::tau_substep(const QueueOp &op)
+{
+  const hipStream_t q = queue(op.q);
+  if (op.opens && prof && spans.begin(Spans::kTau, q)) return fail(h, TRX_E_HIP, "event");
+  TauArgs T{};
+  tau_args(T, op.r_top, op.nc);
+  launch_tau(T, q);
+  if (op.closes && prof && spans.end(q)) return fail(h, TRX_E_HIP, "event");
+  if (op.closes) lap("tau");
   return TRX_OK;
 }
 
@@ -1831,113 +1814,57 @@ int Run::grid_step(const PlanStep &s)
   return TRX_OK;
 }
 
-// the extinction of a step's layers from the lines: a walk (for the tail, or with its combine handed to S), or the two-kernel form
-int Run::line_step(const PlanStep &s, SideWork &S, bool &walked)
+SweepMode Run::sweep_mode(const QueueOp &op) const
 {
-  int rc = TRX_OK;
-  WalkResult W;
   SweepMode M{};
   M.eager = eager; M.prof = count; M.ethresh = o->ethresh;
   M.skip_done = (!eager && !(dbg && dbg->e));
   M.d_e = h->d_e.as<double>(); M.d_kmax = kmax_run; M.d_sticky = h->d_sticky.as<int>();
-  M.st = st;
-  bool all_saved = !h->saved.empty();
-  for (int c = 0; c < s.nc && all_saved; c++) all_saved = h->saved[(size_t)(s.r_top - c)] != 0;
-  if (h->ngroups > 0 && !all_saved) {
-    if (s.nb && tail_mode) {
-      // (no combine of its own: its records wait for the tail, each step in its own buffer)
-      // Two walks of one run do not depend on each other, and a walk alone leaves a third of the device idle for
-      // the last third of its time: waves of one launch start together and end apart -- the oldest wave of a SIMD is
-      // served first, a step's ~13 600 ranges are under two generations of resident waves, and the kernel behind it
-      // on the queue cannot start before the last wave has ended (in-kernel clocks, round 5: 7168 waves in flight
-      // for the first 60 us of k_line_walk<2>, then 5000, 3900, 3000, 2200, 1200, 370 at 5 us steps).  The plan's
-      // second walk therefore goes to the side queue, behind the event that marks the inputs, and fills what the
-      // first one leaves; the tail follows it THERE (same queue: no signal between them) and waits for the first
-      // walk's event, long satisfied by then.  Demo: 0.269 -> 0.251 ms, the same bits.
-      // ev_walk1 is recorded once, behind the main queue's first walk (step), and is all the tail on the side queue
-      // waits for: that covers every walk of the main queue only while the side queue takes every walk but the first.
-      static_assert(kTailSteps == 2, "the side-queue tail waits for ev_walk1 alone: the main queue may carry exactly one walk ahead of it");
-      const bool side_walk = two_queues && nchunks == 1;
-      if (side_walk) { HIPCHK(h, hipStreamWaitEvent(h->stream4, h->ev_inputs, 0)); M.st = h->stream4; tail_on_side = true; }
-      WalkQueue Q;
-      Q.parity = nwalks; Q.defer = true;
-      rc = walk_chunk(h, Y, d_wcut, s, M, sp, Q, W);
-      if (!rc) {
-        TailStep &TS = TA.S[TA.nsteps++];
-        TS.P = W.pc.C.P; TS.part = W.pc.C.part; TS.nc = s.nc;
-        TA.skip = W.pc.C.last;
-      }
-      nwalks++;
-    }
-    else if (s.nb) {
-      WalkQueue Q;
-      Q.parity = nwalks; Q.defer = true;
-      if (S.st_tau != st) Q.st_comb = S.st_tau;
-      Q.ev_walk = h->ev_ac[nchunks];
-      if (nwalks >= 2) Q.ev_reuse = h->ev_cb[(nwalks - 2) % h->ev_cb.size()];
-      Q.ev_done = h->ev_cb[nwalks % h->ev_cb.size()];
-      rc = walk_chunk(h, Y, d_wcut, s, M, sp, Q, W);
-      if (!rc) S.pc = W.pc;
-      nwalks++;
-    }
-    else    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s, P.sg_layers, M, sp);
-    if (rc) return rc;
-    walked = s.nb != 0;
-    if (walked) for (int c = 0; c < s.nc; c++) layer_walked[(size_t)(s.r_top - c)] = (uint8_t)(1 + W.form);
+  M.st = queue(op.q);
+  return M;
+}
+
+// a walk step's extinction as records: its combine is kept for the combine op, or (tail mode) its records wait for the tail
+int Run::walk(const QueueOp &op)
+{
+  const PlanStep &s = h->run_plan[(size_t)op.step];
+  WalkResult W;
+  if (const int rc = walk_chunk(h, Y, d_wcut, s, sweep_mode(op), sp, op.parity, W)) return rc;
+  if (tail.tail_mode) {
+    TailStep &TS = TA.S[TA.nsteps++];
+    TS.P = W.C.P; TS.part = W.C.part; TS.nc = s.nc;
+    TA.skip = W.C.last;
   }
-  if (S.st_tau != st && !walked) {     // the optical depth of this step follows its extinction
-    HIPCHK(h, hipEventRecord(h->ev_ac[nchunks], st));
-    HIPCHK(h, hipStreamWaitEvent(S.st_tau, h->ev_ac[nchunks], 0));
-  }
+  else comb[op.parity] = W.C;
+  for (int c = 0; c < s.nc; c++) layer_walked[(size_t)(s.r_top - c)] = (uint8_t)(1 + W.form);
   return TRX_OK;
 }
 
-// ---- one top-down step of layers (tau.c:235-290)
-int Run::step(const PlanStep &s)
+// ---- one op of the pass's schedule (trx_schedule.h), on the queue and behind the events it names
+int Run::issue(const QueueOp &op)
 {
-  int rc;
-  SideWork S; bool walked = false;
-  S.first = nchunks == 0; S.r_top = s.r_top; S.nc = s.nc; S.swept = nr - 1 - s.r_top;
-  S.st_tau = (pipelined && !s.last_step) ? st_early : st;
-  if ((rc = h->has_grid ? grid_step(s) : line_step(s, S, walked))) return rc;
-  lap("sweep");
-  if (tail_mode) {
-    // the CIA kernels go to their queue behind the first walk (what the device is waiting for) -- ahead of a second
-    // walk on the side queue too: next to TWO walks they take three times as long, and configs[3]'s two tables then
-    // end after the walks.  With two queues the main one waits for them behind its walk and marks the place: one
-    // event for the tail to wait for.
-    if (!cia_queued) {
-      if ((rc = queue_cia())) return rc;
-      if (two_queues && !s.last_step) { HIPCHK(h, hipStreamWaitEvent(st, h->ev_cia, 0)); HIPCHK(h, hipEventRecord(h->ev_walk1, st)); }
-      lap("cia");
-    }
-  } else {
-    // The rest of the step -- its combine, the CIA kernels ahead of the first optical depth, the
-    // optical depth itself -- goes to the side queue for every step but the plan's last, and is
-    // QUEUED only after the next step's walk: the walks then sit back to back on the main queue
-    // however long the host takes over the rest (small shards are host-bound otherwise).
-    if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-    S.active = true;
-    // (walk steps only: with the two-kernel form's long steps the later queueing of an optical
-    // depth measurably delays the stop information the next step's tile skipping reads --
-    // configs[4] 0.223 -> 0.246 s)
-    if (S.st_tau != st && walked) pending = S;
-    else if ((rc = side_work(S))) return rc;
-    lap("tau");
+  int rc = TRX_OK;
+  const PlanStep &s = h->run_plan[(size_t)op.step];
+  switch (op.kind) {
+    case kOpWait:     HIPCHK(h, hipStreamWaitEvent(queue(op.q), event(op), 0)); break;
+    case kOpRecord:   HIPCHK(h, hipEventRecord(event(op), queue(op.q))); break;
+    case kOpWalk:     rc = walk(op); lap("sweep"); break;
+    case kOpSweep:    rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s, P.sg_layers, sweep_mode(op), sp); lap("sweep"); break;
+    case kOpGrid:     rc = grid_step(s); lap("sweep"); break;
+    case kOpCombine:  rc = launch_combine(h, comb[op.parity], queue(op.q), sp); break;
+    case kOpCia:      rc = cia_group(); lap("cia"); break;
+    case kOpRestore:  rc = restore_rows(op); break;
+    case kOpTau:      rc = tau_substep(op); break;
+    case kOpTail:     rc = ray_tail(); break;
+    case kOpSpectrum: rc = spectrum_kernel(); break;
   }
-  r_top -= s.nc; nchunks++;
-  return TRX_OK;
+  return rc;
 }
 
 // ---- the ray tail: every address it reads or writes is checked on the host before the launch
 int Run::ray_tail()
 {
-  int rc;
-  if (tail_on_side) { tst = h->stream4; HIPCHK(h, hipStreamWaitEvent(tst, h->ev_walk1, 0)); }
-  else {
-    if (!cia_queued && (rc = queue_cia())) return rc;
-    HIPCHK(h, hipStreamWaitEvent(st, h->ev_cia, 0));
-  }
+  const bool tail_direct = tail.tail_direct, tail_spec = tail.tail_spec;
   TA.niso = h->niso; TA.gblock = h->d_gblock.as<int32_t>(); TA.e = h->d_e.as<double>();
   for (int b = 0; b < h->niso && b < 64; b++) if (h->h_gblock[b] != h->h_gblock[b + 1]) TA.blocks |= 1ull << b;
   int nct = 0; for (int k = 0; k < TA.nsteps; k++) nct += TA.S[k].nc;
@@ -1968,13 +1895,10 @@ int Run::ray_tail()
   return TRX_OK;
 }
 
-// ---- the spectrum of the layers swept so far: the ray tail, or emission, or modulation
+// ---- the spectrum of the layers swept so far, where no ray tail gives it: emission, or modulation
 int Run::spectrum_kernel()
 {
-  if (const int rc = join_early()) return rc;
   if (resumed) HIPCHK(h, hipMemsetAsync(h->d_status.p, 0, 16, st));       // (a resumed run computes the spectrum a second time)
-  tst = st;
-  if (tail_mode) return ray_tail();
   const bool rows = h->nwn > kEmisRowsAbove;       // (by the job's grid, not the shard: all shards of a job add in the same order)
   const dim3 grows((unsigned)((nsh + 255) / 256));
   if (vertical) {
@@ -1992,8 +1916,9 @@ int Run::spectrum_kernel()
 }
 
 // ---- results back: the copies, the wait, and (direct tail) the flags summed on the host
-int Run::results()
+int Run::results(const PassEnd &end)
 {
+  const bool tail_direct = tail.tail_direct, tail_spec = tail.tail_spec;
   HIPCHK(h, hipGetLastError());
   if (prof) HIPCHK(h, hipEventRecord(h->ev_run_b, tst));
   // one copy into pinned memory: flags, status and (profiled runs) the counters
@@ -2002,7 +1927,7 @@ int Run::results()
   if (spectrum && !tail_spec) HIPCHK(h, hipMemcpyAsync(stage_spec ? h->h_spec.p : (void *)spectrum, d_out, sizeof(double) * nsh, hipMemcpyDeviceToHost, tst));
   lap("spectrum+copies");
   t_host_queued = std::chrono::steady_clock::now();
-  if (tail_on_side) HIPCHK(h, hipStreamSynchronize(h->stream4));      // (the tail has waited for the main queue's walk: nothing is left there)
+  if (end.sync_side) HIPCHK(h, hipStreamSynchronize(h->stream4));     // (the tail has waited for the main queue's walk: nothing is left there)
   HIPCHK(h, hipStreamSynchronize(st));
   // the tail stored the spectrum into the handle's pinned buffer, or the copy command did
   if (spectrum && (tail_spec || stage_spec)) std::memcpy(spectrum, h->h_spec.p, sizeof(double) * (size_t)nsh);
@@ -2025,13 +1950,20 @@ int Run::results()
   return TRX_OK;
 }
 
-// ---- one pass: the planned steps (h->run_plan) from r_top down, the spectrum of what they swept, its way back
+// ---- one pass: the planned steps (h->run_plan) from r_top down and the spectrum of what they swept as a schedule
+// (trx_schedule.h; tests/schedule_check.cpp holds every consumer behind its producer), its ops issued in order, the
+// products behind the spectrum, the way back
 int Run::pass()
 {
   int rc;
-  for (const PlanStep &s : h->run_plan) if ((rc = step(s))) return rc;
-  if (pending.active) { if ((rc = side_work(pending))) return rc; pending.active = false; }
-  return (rc = spectrum_kernel()) || (rc = product_kernels()) ? rc : results();
+  ScheduleIn in;
+  in.pipelined = pipelined; in.has_grid = h->has_grid; in.vertical = vertical; in.has_lines = h->ngroups > 0;
+  in.tail = tail; in.saved = h->saved.empty() ? nullptr : h->saved.data(); in.nr = nr;
+  const PassEnd end = schedule_pass(h->run_plan, in, kScheduleCaps, sched, h->run_sched);
+  tst = queue(end.spectrum_q);
+  for (const QueueOp &op : h->run_sched) if ((rc = issue(op))) return rc;
+  r_top = h->run_plan.back().r_top - h->run_plan.back().nc;
+  return (rc = product_kernels()) ? rc : results(end);
 }
 
 // Rays still descending below the expected depth (the atmosphere changed): the run goes on from there to the
@@ -2039,8 +1971,8 @@ int Run::pass()
 int Run::resume()
 {
   // (the step kernels that go on from here read the flags on the device: where the host has added them up, they go there first)
-  if (tail_direct) HIPCHK(h, hipMemcpyAsync(h->d_flags.p, h->h_small.p, 32, hipMemcpyHostToDevice, st));
-  tail_mode = tail_direct = tail_spec = tail_on_side = false;
+  if (tail.tail_direct) HIPCHK(h, hipMemcpyAsync(h->d_flags.p, h->h_small.p, 32, hipMemcpyHostToDevice, st));
+  tail = TailChoice{};
   resumed = true; h->hint_layers = P.hint_layers = 0;
   plan_pass(P, r_top, false, h->run_plan);
   return pass();
@@ -2079,7 +2011,7 @@ int Run::finish()
     spans.sum(t);
     S.ms_k_walk_form[0] = t[Spans::kWalk]; S.ms_k_walk_form[1] = t[Spans::kWalkLanes]; S.ms_k_walk_form[2] = t[Spans::kWalkPacked];
     S.ms_k_sweep = t[Spans::kSweep]; S.ms_k_walk = t[Spans::kWalk] + t[Spans::kWalkLanes] + t[Spans::kWalkPacked]; S.ms_k_accum = t[Spans::kAccum]; S.ms_tau = t[Spans::kTau];
-    S.sweep_launches = nchunks;
+    S.sweep_launches = sched.steps;
     S.ms_sweep = S.ms_k_sweep + S.ms_k_walk + S.ms_k_accum;
     S.ms_walk_span = spans.walk_span();
   }
@@ -2177,7 +2109,7 @@ int trx_sweep_permol(trx_handle *h, int32_t nv, const double *temp, const double
     M.eager = true; M.ethresh = ethresh; M.nmx = nslot; M.d_iso_mx = h->d_iso_mx.as<int32_t>();
     M.permol = true; M.d_e = h->d_pm.as<double>(); M.d_kmax = h->d_kmax.as<double>(); M.d_sticky = h->d_sticky.as<int>();
     WalkResult W;      // (form -1: the two-kernel form)
-    if (s.nb) rc = walk_chunk(h, Y, d_wcut, s, M, nullptr, WalkQueue{}, W);
+    if (s.nb) { if (!(rc = walk_chunk(h, Y, d_wcut, s, M, nullptr, 0, W))) rc = launch_combine(h, W.C, st, nullptr); }
     else      rc = sweep_chunk(h, Y, d_wcut, LH.psmax, s, sg_layers, M, nullptr);
     if (rc) return rc;
     // (trx_stats does not count sweeps: the step plan goes to the log, one line per step -- tests read it)

@@ -1,5 +1,5 @@
 // trx_api_sweep.hip.h -- one step of the line sweep as kernel launches: the walk (walk_chunk: the range plan, the record
-// buffer, the arguments, the shard's window, the form, the launch, the combine) and the two-kernel form (sweep_chunk:
+// buffer, the arguments, the shard's window, the form, the launch; launch_combine: its combine) and the two-kernel form (sweep_chunk:
 // strengths, accumulation, the wide layers' kernels), the per-kernel timing of a profiled run (Spans), and the layer
 // maxima and sticky indices that leave the per-step chain.  What a launch DECIDES -- frames, windows, line counts, forms,
 // masks -- is ../trx_sweep.h's, plain C++ that tests/sweep_check.cpp runs on the CPU; here it is launched.  Part of the
@@ -116,36 +116,18 @@ void launch_walk(const WalkArgs &A, bool prof, unsigned nwaves, hipStream_t st)
   else      hipLaunchKernelGGL((k_line_walk<NB, false>), grid, block, 0, st, A);
 }
 
-// A combine whose launch has been put off (the host queues the NEXT step's walk first, so that the
-// walks sit back to back on their queue whatever else this step still has to queue).
-struct PendingCombine {
-  bool valid = false;
-  CombineArgs C{}; hipStream_t sc = nullptr; hipEvent_t ev_walk = nullptr, ev_done = nullptr; bool cross = false;
-};
-
-int launch_combine(trx_handle *h, PendingCombine &pc, Spans *sp)
+// the combine of a walk's partial sums, on the queue its optical depth follows on
+int launch_combine(trx_handle *h, const CombineArgs &C, hipStream_t q, Spans *sp)
 {
-  if (!pc.valid) return TRX_OK;
-  pc.valid = false;
-  if (pc.cross) HIPCHK(h, hipStreamWaitEvent(pc.sc, pc.ev_walk, 0));
-  if (sp && sp->begin(Spans::kAccum, pc.sc)) return fail(h, TRX_E_HIP, "event");
-  hipLaunchKernelGGL(k_walk_combine, dim3((unsigned)((h->nsh + kCombineBins - 1) / kCombineBins)), dim3(64 * kCombineBins), 0, pc.sc, pc.C);
-  if (sp && sp->end(pc.sc)) return fail(h, TRX_E_HIP, "event");
-  if (pc.cross && pc.ev_done) HIPCHK(h, hipEventRecord(pc.ev_done, pc.sc));
+  if (sp && sp->begin(Spans::kAccum, q)) return fail(h, TRX_E_HIP, "event");
+  hipLaunchKernelGGL(k_walk_combine, dim3((unsigned)((h->nsh + kCombineBins - 1) / kCombineBins)), dim3(64 * kCombineBins), 0, q, C);
+  if (sp && sp->end(q)) return fail(h, TRX_E_HIP, "event");
   return TRX_OK;
 }
 
-// How a walk step (walk_chunk) is queued, and what it hands back.
-struct WalkQueue {
-  int parity = 0;                      // which of the two record buffers
-  hipStream_t st_comb = nullptr;       // the combine's stream (null: the walk's)
-  hipEvent_t ev_walk = nullptr;        // recorded behind the walk, for a combine on another stream to wait for
-  hipEvent_t ev_reuse = nullptr;       // the walk waits for it: this buffer's previous records (two steps ago) have been combined
-  hipEvent_t ev_done = nullptr;        // recorded behind a combine on another stream
-  bool defer = false;                  // the combine is handed back (WalkResult::pc) instead of launched
-};
+// What a walk step (walk_chunk) hands back.
 struct WalkResult {
-  PendingCombine pc;                   // valid only where the combine was deferred
+  CombineArgs C{};                     // its combine, for the caller to launch (launch_combine) or to hand to the ray tail
   int form = -1;                       // which kernel the production run takes for the step (trx_sweep.h: WalkKind)
 };
 
@@ -228,17 +210,14 @@ void launch_walk_form(const trx_handle *h, WalkArgs &A, const WalkForm &F, unsig
   }
 }
 
-// the combine of a walk's partial sums, on the stream the optical depth runs on
-PendingCombine combine_of(const trx_handle *h, const WalkArgs &A, const SweepMode &M, const WalkQueue &Q, hipStream_t st)
+// the arguments of the combine of a walk's partial sums
+CombineArgs combine_of(const trx_handle *h, const WalkArgs &A, const SweepMode &M)
 {
-  PendingCombine pc;
-  pc.valid = true; pc.sc = Q.st_comb ? Q.st_comb : st; pc.cross = Q.st_comb != nullptr && Q.ev_walk != nullptr;
-  pc.ev_walk = Q.ev_walk; pc.ev_done = Q.ev_done;
-  CombineArgs &C = pc.C;
+  CombineArgs C{};
   C.P = A.P; C.niso = h->niso; C.gblock = h->d_gblock.as<int32_t>(); C.lo = h->lo; C.nsh = h->nsh; C.r_top = A.r_top; C.nc = A.nc;
   C.nmx = M.nmx; C.iso_mx = M.d_iso_mx; C.part = A.part; C.e = M.d_e;
   C.flags = h->d_flags.as<int>(); C.last = A.last; C.eager = M.eager;
-  return pc;
+  return C;
 }
 
 // what walk_form (trx_sweep.h) reads of the handle and the step
@@ -253,11 +232,11 @@ WalkFormIn walk_form_in(const trx_handle *h, const PlanStep &s, unsigned nw, boo
   return in;
 }
 
-// The walk: layers s.r_top .. s.r_top-s.nc+1 (nc <= 64) in one kernel on M.st, then the combine of its
-// partial sums on Q.st_comb.  Consecutive steps alternate between two record buffers, so that the next
-// step's walk does not wait for this step's combine.
+// The walk: layers s.r_top .. s.r_top-s.nc+1 (nc <= 64) in one kernel on M.st, into record buffer `parity`; the
+// combine of its partial sums is handed back (R.C).  Consecutive steps alternate between two record buffers, so that
+// the next step's walk does not wait for this step's combine.
 int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, const PlanStep &s, const SweepMode &M, Spans *sp,
-               const WalkQueue &Q, WalkResult &R)
+               int parity, WalkResult &R)
 {
   static_assert(kSweepSegs == kWalkSegs, "trx_sweep.h sizes the window for the kernels' segment count");
   constexpr WalkCaps kCaps{kLanesMaxLayers, kLanesMaxGroup, kWalkRowsFrom};
@@ -267,8 +246,7 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, const Pla
   if (rc) return rc;
   // (trx_stats describes the last trx_run: a per-molecule sweep (trx_sweep_permol) walks too but is not counted)
   if (!M.permol) { h->stats.walk_steps++; h->stats.walk_records += pl->records; h->stats.walk_record_lanes += pl->records * s.nc; }
-  if ((rc = record_buffer(h, *pl, Q.parity, st, part))) return rc;
-  if (Q.ev_reuse) HIPCHK(h, hipStreamWaitEvent(st, Q.ev_reuse, 0));
+  if ((rc = record_buffer(h, *pl, parity, st, part))) return rc;
   WalkArgs A = walk_args(h, Y, d_wcut, s, M, P, part->as<double>());
   const WalkWindow W = walk_window(group_view(h), s.nb, h->nwaves);
   A.nseg = W.nseg; std::copy(W.seg_w0, W.seg_w0 + kWalkSegs, A.seg_w0); std::copy(W.seg_cum, W.seg_cum + kWalkSegs + 1, A.seg_cum);
@@ -278,10 +256,8 @@ int walk_chunk(trx_handle *h, const LayerDev &Y, const double *d_wcut, const Pla
   if (sp && sp->begin(F.launched == kFormLanes ? Spans::kWalkLanes : F.launched == kFormPacked ? Spans::kWalkPacked : Spans::kWalk, st)) return fail(h, TRX_E_HIP, "event");
   launch_walk_form(h, A, F, W.nw, s.nb, st);
   if (sp && sp->end(st)) return fail(h, TRX_E_HIP, "event");
-  PendingCombine pc = combine_of(h, A, M, Q, st);
-  if (pc.cross) HIPCHK(h, hipEventRecord(Q.ev_walk, st));
-  if (Q.defer) { R.pc = pc; return TRX_OK; }
-  return launch_combine(h, pc, sp);
+  R.C = combine_of(h, A, M);
+  return TRX_OK;
 }
 
 // the accumulation kernels' arguments: the handle's tables, the step and the mode

@@ -214,6 +214,7 @@ struct trx_handle {
   std::vector<double> run_f64, run_geom, run_ipv; std::vector<int32_t> run_i32;      // per-run host arrays (kept: no allocation per run)
   std::vector<int> run_frame; std::vector<unsigned char> run_wide;      // [layer] walk_frame_bins, and the plan's "very wide" mark (trx_plan.h)
   std::vector<PlanStep> run_plan;                                        // the steps of the pass being queued
+  std::vector<QueueOp> run_sched;                                        // ... and its schedule (trx_schedule.h), issued op by op
   std::vector<double> run_og_layer; std::vector<int> run_og_itemp;       // opacity grid: the layers' weights and temperature brackets (Run::grid_weights)
   int hint_layers = 0;       // layers the previous run needed (deepest toomuch crossing + 1)
   DevBuf d_e_saved; std::vector<uint8_t> saved;          // trx_restore_extinction: [nlayer][nsh] and the flags (empty: none)
