@@ -1012,8 +1012,10 @@ int  trx_run_batch_exposed_map(trx_batch *b, int32_t k, const trx_atm *atm /* [k
  *    residuals are built in a buffer of their own and swapped in at step 3: a call that fails later (TRX_E_HIP,
  *    TRX_E_NOMEM) also leaves the previous data and filter in force.
  * Not here: a batch form (a driver takes basis and data from one handle and installs them on a trx_batch through
- * trx_batch_set_observed and trx_batch_set_weighted_filter), high-passing the data, per-order normalisation or division by
- * a column's scatter, shards.  A principal-component analysis in SYSREM's place is trx_pca_observed, below. */
+ * trx_batch_set_observed and trx_batch_set_weighted_filter), high-passing the data or division by a column's scatter,
+ * shards.  The per-order normalisation ahead of the fit is step 1b, the recipe of trx_set_normalise (below): with one
+ * installed f0 goes through it between steps 1 and 2; without one the call is what it was.  A principal-component analysis
+ * in SYSREM's place is trx_pca_observed, below. */
 #define TRX_SYSREM_MAX_ITER 64
 typedef struct {
   int32_t ncomp, niter;      /* components 1 .. TRX_FILTER_MAX (0: undo); alternations per component, 1 .. TRX_SYSREM_MAX_ITER */
@@ -1068,8 +1070,9 @@ int  trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o,
  * TRX_PCA_MAX_EXP; ncomp < 0, above TRX_FILTER_MAX or above nexp; nsweep < 1 or above TRX_PCA_MAX_SWEEP; then inject, pad and
  * the injection's arguments as trx_detrend_observed has them.  TRX_E_UNSUPPORTED on a shard.  A later TRX_E_HIP or
  * TRX_E_NOMEM leaves the previous data and filter in force.  pc NULL or ncomp = 0 is trx_detrend_observed's undo.
- * Not here: a batch form, shards, centring or standardising the columns ahead of the PCA (trx_weigh_observed and the filter
- * carry that), a sweep count driven by convergence, more than TRX_PCA_MAX_EXP exposures. */
+ * Not here: a batch form, shards, standardising the columns ahead of the PCA (trx_weigh_observed and the filter carry
+ * that), a sweep count driven by convergence, more than TRX_PCA_MAX_EXP exposures.  Centring the columns ahead of the PCA
+ * is step 1b, the recipe of trx_set_normalise (below), as in trx_detrend_observed. */
 #define TRX_PCA_MAX_SWEEP 32
 #define TRX_PCA_MAX_EXP   128
 typedef struct {
@@ -1118,7 +1121,7 @@ int  trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double
  *    min_live < 2 or above nexp; clip non-finite, negative or in (0, 1) (a non-NULL sc is checked whole, whatever its
  *    kind).  TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.  A call that fails later (TRX_E_HIP,
  *    TRX_E_NOMEM) leaves the previous weights and filter in force.
- * Not here: a batch form, shards, dividing the data, sigma-clipping single entries. */
+ * Not here: a batch form, shards, dividing the data.  Sigma-clipping single entries is trx_set_normalise's clip (below). */
 #define TRX_SCATTER_NONE     0   /* undo: the weights as trx_set_observed installed them */
 #define TRX_SCATTER_VARIANCE 1   /* w' = 1 / var_p on the kept columns' live entries      */
 #define TRX_SCATTER_MASK     2   /* w' = W on the kept columns, 0 on the others           */
@@ -1157,10 +1160,78 @@ int  trx_weigh_observed(trx_handle *h, const trx_scatter *sc,
  *    with apply = 1, no high-pass installed.  TRX_E_UNSUPPORTED on a handle whose shard is not the whole grid.  nexp * ntiles
  *    above one launch's grid is refused before anything is launched.  A call that fails later (TRX_E_HIP, TRX_E_NOMEM)
  *    leaves the previous data in force.
- * Not here: a batch form, shards, a high-pass ahead of SYSREM, a table other than the installed one, clipping single entries. */
+ * Not here: a batch form, shards, a high-pass ahead of SYSREM, a table other than the installed one.  Clipping single
+ * entries is trx_set_normalise's clip (below), ahead of the fit. */
 int  trx_highpass_observed(trx_handle *h, int32_t apply /* 1: high-pass, 0: undo */,
                            double *data /* [nexp][npix]: the data now installed, host; may be NULL */,
                            int64_t *ndead /* may be NULL */);
+
+/* Normalising the observed set on the device, ahead of SYSREM and PCA: the first step of every published pipeline, and
+ * STEP 1b of the detrending calls.  Each (exposure, segment) row is divided by its own continuum level -- a quantile of its
+ * live data --, each pixel column is divided by, or has subtracted, its mean in time, and single outlying entries are
+ * clipped.  The recipe sits in a slot on the handle (trx_set_normalise); with one installed trx_detrend_observed and
+ * trx_pca_observed run it on f0 in the call's own buffer between the injection (step 1) and the fit (step 2), so that an
+ * injection-recovery loop injects into the RAW data and normalises afterwards, as the pipeline under test does, without
+ * the data leaving the device.  trx_normalise_observed is "the detrend of zero components": steps 0, 1 and 1b alone.  The
+ * documented order is normalise, detrend or pca, high-pass, weigh, the map.
+ *
+ * Every operation is IEEE double rounded once, no fused multiply-add; sums start from +0 in the order written; no atomics.
+ * W is the weights as trx_set_observed installed them (1 without) -- never a weigh call's --; an entry is LIVE if W[v][p] > 0.
+ * 1. Row scale, per exposure v and segment s.  m is the number of live pixels of the row.  row_kind QUANTILE:
+ *      k = (int64) floor(quantile * (double)(m - 1));  scale[v][s] = the value of rank k (0-based, ascending) among the
+ *    row's live f0 (an exact selection; ties are equal values; quantile 0.5 is the lower median).  The row is GOOD if m >= 1
+ *    and scale > 0; otherwise scale = +0 (a scale of -0 included).  f1 = f0 / scale.  row_kind NONE: every row with a live
+ *    pixel is good, scale = 1.0 and f1 = f0.
+ * 2. Column centre, per pixel p, v ascending over the entries that are live in a good row: n their count, s the sum of f1,
+ *    c_p = s / (double)n.  The column is GOOD if n >= 1 and -- DIVIDE and RATIO: c_p > 0 and finite; SUBTRACT: c_p finite;
+ *    col_kind NONE: nothing more.  A column that is not good has c_p = +0.  f2 = f1 / c_p;  or t = f1 / c_p, t - 1.0;  or
+ *    f1 - c_p;  or f1.
+ * 3. Clip (clip > 0), per good column with n >= 2, one pass, not iterated, in trx_weigh_observed's arithmetic:
+ *      mean = (sum of f2) / (double)n;  q = sum of d * d with d = f2 - mean;  var = q / (double)(n - 1);
+ *      lim = clip * clip;  lim = lim * var;  an entry with d * d > lim becomes mean and counts in nclipped.
+ * 4. Every entry that is dead, in a bad row or in a bad column gets +0; nbad counts the LIVE entries among them.
+ * A segment's output bits depend only on that segment's f0 and W and on the recipe -- not on other segments, the launch or
+ * the handle.
+ *
+ * trx_set_normalise installs the recipe (nm NULL: clears it): host work only, nothing in force changes -- data, weights and
+ * filter stay --, the recipe acts from the next detrending call on.  trx_set_observed and trx_set_pixels drop it with
+ * everything else.  TRX_E_ARG, nothing touched, checked in this order: no observed set; row_kind outside 0 .. 1; col_kind
+ * outside 0 .. 3; quantile non-finite or outside [0, 1] (whatever row_kind is); clip non-finite, negative or in (0, 1);
+ * both kinds NONE and clip == 0 (a recipe that does nothing: pass NULL).  TRX_E_UNSUPPORTED on a shard.
+ *
+ * trx_normalise_observed runs steps 0, 1 and 1b with trx_detrend_observed's injection and its checks; at once and only after
+ * every kernel has finished the result -- built in the detrend's residual buffer -- becomes the observed data, the filter
+ * slot is cleared, the weights of trx_set_observed go back in force and a high-pass over the data is discarded.  It goes
+ * through the state of the other two calls: any of the three undoes any other, trx_detrend_observed with ncomp = 0 undoes
+ * it, and every call starts from the raw F.  data, rowscale and centre, where given, receive the data now installed,
+ * scale and c; nclipped and nbad the two counts.  A driver needs those once per data set: a row with rowscale == 0, or a
+ * column that turned bad, is to be masked in the weights of trx_set_observed, and so is a column whose centre is low (a
+ * deep telluric).  TRX_E_ARG, nothing touched, in this order: no observed set; no recipe installed; then inject and the
+ * injection's arguments as trx_detrend_observed has them.  TRX_E_UNSUPPORTED on a shard.  A later TRX_E_HIP or
+ * TRX_E_NOMEM leaves the data and the filter in force as they were.
+ * Not here: a change of the WEIGHTS (the call masks nothing: the driver does, above), a batch form, shards, an iterated
+ * clip, a polynomial continuum per row. */
+#define TRX_NORM_ROW_NONE      0
+#define TRX_NORM_ROW_QUANTILE  1   /* divide each (exposure, segment) row by its quantile */
+#define TRX_NORM_COL_NONE      0
+#define TRX_NORM_COL_DIVIDE    1   /* f / c_p        (about 1) */
+#define TRX_NORM_COL_RATIO     2   /* f / c_p - 1.0  (about 0) */
+#define TRX_NORM_COL_SUBTRACT  3   /* f - c_p        (about 0) */
+typedef struct {
+  int32_t row_kind, col_kind;
+  double  quantile;      /* in [0, 1]; 0.5: the lower median */
+  double  clip;          /* 0: none; otherwise >= 1: entries beyond clip sigma of their column are replaced */
+} trx_normalise;         /* 24 bytes */
+int  trx_set_normalise(trx_handle *h, const trx_normalise *nm /* NULL: clear */);
+int  trx_normalise_observed(trx_handle *h, const trx_atm *a, const trx_opts *o,
+                            double *spectrum /* [wn_hi-wn_lo], host; may be NULL */,
+                            int32_t nshift, const double *shift /* [nexp]; inject = 1 only */,
+                            int32_t inject, double p0, double p1,
+                            double *data /* [nexp][npix]: the data now installed, host; may be NULL */,
+                            double *rowscale /* [nexp][nseg], host; may be NULL */,
+                            double *centre /* [npix], host; may be NULL */,
+                            int64_t *nclipped /* may be NULL */, int64_t *nbad /* may be NULL */,
+                            trx_debug *dbg /* may be NULL */);
 
 /* The per-layer operator of the reference in its per-molecule form,
  *   computemolext(tr, kiso, temp, density, Z, permol = 1)   (extinction.c:282)

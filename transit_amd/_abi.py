@@ -133,6 +133,14 @@ class TrxScatter(C.Structure):
     _fields_ = [("kind", C.c_int32), ("min_live", C.c_int32), ("clip", C.c_double)]
 
 
+NORM_ROW_NONE, NORM_ROW_QUANTILE = 0, 1                     # TRX_NORM_ROW_*: the row kinds of trx_set_normalise
+NORM_COL_NONE, NORM_COL_DIVIDE, NORM_COL_RATIO, NORM_COL_SUBTRACT = 0, 1, 2, 3      # TRX_NORM_COL_*: its column kinds
+
+
+class TrxNormalise(C.Structure):
+    _fields_ = [("row_kind", C.c_int32), ("col_kind", C.c_int32), ("quantile", C.c_double), ("clip", C.c_double)]
+
+
 HIGHPASS_MAX_HALF = 1024
 
 
@@ -407,4 +415,16 @@ def bind_hpdata_api(lib):
     """argtypes/restypes of the observed set's own high-pass (trx_highpass_observed)."""
     lib.trx_highpass_observed.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.POINTER(C.c_int64)]
     lib.trx_highpass_observed.restype = C.c_int
+    return lib
+
+
+def bind_normalise_api(lib):
+    """argtypes/restypes of the normalisation entry points (trx_set_normalise, trx_normalise_observed)."""
+    i64p = C.POINTER(C.c_int64)
+    lib.trx_set_normalise.argtypes = [C.c_void_p, C.POINTER(TrxNormalise)]
+    lib.trx_set_normalise.restype = C.c_int
+    lib.trx_normalise_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                           C.c_int32, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p, i64p, i64p,
+                                           C.POINTER(TrxDebug)]
+    lib.trx_normalise_observed.restype = C.c_int
     return lib

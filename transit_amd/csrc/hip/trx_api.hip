@@ -52,6 +52,7 @@
 #include "trx_sysrem.hip.h"
 #include "trx_pca.hip.h"
 #include "trx_scatter.hip.h"
+#include "trx_normalise.hip.h"
 #include "trx_highpass.hip.h"
 #include "trx_broaden.hip.h"
 #include "trx_contrib.hip.h"
@@ -69,6 +70,7 @@
 #include "../trx_sysrem.h"
 #include "../trx_pca.h"
 #include "../trx_scatter.h"
+#include "../trx_normalise.h"
 #include "../trx_launch.h"
 #include "../trx_hpdata.h"
 

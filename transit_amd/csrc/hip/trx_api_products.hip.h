@@ -362,9 +362,10 @@ static int make_pixel_set(trx_handle *h, const trx_pixels *px, std::unique_ptr<P
 }
 
 // (the observed set belongs to the pixel set it was installed over, the filter, the high-pass and the exposure table to the
-// observed set: they go with it -- the high-pass first, which points into the observed set)
-static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->highpass.reset(); h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); h->exposures.reset(); }
-static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->highpass.reset(); h->observed = std::move(S); h->filter.reset(); h->exposures.reset(); }
+// observed set, and so does the recipe of trx_set_normalise: they go with it -- the high-pass first, which points into the
+// observed set)
+static void install_pixel_set(trx_handle *h, std::unique_ptr<PixelSet> &S) { h->highpass.reset(); h->pixels = std::move(S); h->observed.reset(); h->filter.reset(); h->exposures.reset(); h->norm_on = false; }
+static void install_observed_set(trx_handle *h, std::unique_ptr<ObservedSet> &S) { h->highpass.reset(); h->observed = std::move(S); h->filter.reset(); h->exposures.reset(); h->norm_on = false; }
 
 int trx_set_pixels(trx_handle *h, const trx_pixels *px)
 {
@@ -978,7 +979,40 @@ static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend 
   return TRX_OK;
 }
 
-// steps 0 and 1 of a detrending call (who), on the main queue: the raw data, or the injected data, into h->d_sr_r.  With an
+// step 1b of a detrending call (who), on the main queue behind steps 0 and 1: the recipe installed on h over f0 in h->d_sr_r,
+// in place (trx_normalise.hip.h); the row scales, the centres and the columns' counts are left in h->d_nm_*
+static int launch_normalise(trx_handle *h, const char *who, const ObservedSet *O)
+{
+  std::string msg; int rc;
+  if ((rc = sysrem_tiles(product_state(h), h->nm_tiles, msg, who))) return fail(h, rc, msg);
+  const int64_t ntiles = (int64_t)h->nm_tiles.size();
+  if (ntiles < 1) return fail(h, TRX_E_ARG, std::string(who) + ": the observed set has no pixel in any segment");
+  const NormExtents X = normalise_extents(O->npix, O->nexp, O->nseg, ntiles, kNormWaves);
+  if ((rc = ensure(h, h->d_nm_scale, X.scale_bytes)) || (rc = ensure(h, h->d_nm_centre, X.centre_bytes)) || (rc = ensure(h, h->d_nm_count, X.count_bytes)) ||
+      (rc = upload(h, h->d_nm_tiles, h->nm_tiles)))
+    return rc;
+  const DevBuf &W = O->d_weight.raw();
+  NormArgs A{};
+  A.r = h->d_sr_r.as<double>(); A.weight = W.as<double>(); A.tiles = h->d_nm_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
+  A.scale = h->d_nm_scale.as<double>(); A.centre = h->d_nm_centre.as<double>(); A.count = h->d_nm_count.as<int32_t>();
+  A.npix = O->npix; A.ntiles = ntiles; A.nexp = O->nexp; A.nseg = O->nseg;
+  A.row_kind = h->norm.row_kind; A.col_kind = h->norm.col_kind; A.quantile = h->norm.quantile; A.clip = h->norm.clip;
+  // (every address the kernels read or write: the data and the weights [nexp][npix], the tiles -- which cover [0, npix) and
+  // name segments below nseg --, the bounds [nseg + 1], scale [nexp][nseg] -- one block per row --, centre [npix], the counts
+  // [2][npix])
+  if (!A.r || !A.tiles || !A.scale || !A.centre || !A.count || !observed_set_whole(*O, W, false) || A.nexp < 1 || A.nseg < 1 || !X.grid_ok ||
+      h->d_sr_r.bytes < X.r_bytes || (A.weight && W.bytes < X.r_bytes) || h->d_nm_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
+      h->d_nm_scale.bytes < X.scale_bytes || h->d_nm_centre.bytes < X.centre_bytes || h->d_nm_count.bytes < X.count_bytes)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the normalise kernels (not launched)");
+  HIPCHK(h, hipMemsetAsync(A.scale, 0, X.scale_bytes, h->stream));
+  hipLaunchKernelGGL(k_norm_rowscale, dim3((unsigned)X.row_blocks), dim3(kNormBlock), 0, h->stream, A);
+  hipLaunchKernelGGL(k_norm_cols, dim3((unsigned)X.tile_blocks), dim3(64 * kNormWaves), 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  return TRX_OK;
+}
+
+// steps 0, 1 and -- with a recipe installed (trx_set_normalise) -- 1b of a detrending call (who), on the main queue.
+// Steps 0 and 1: the raw data, or the injected data, into h->d_sr_r.  With an
 // injection the pairs come from the pixel stage alone, as trx_run_exposed (or, without a table, trx_run_pixels) runs it -- no
 // moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for.  cells, r_bytes, c_bytes and
 // elem_blocks: the call's extents.
@@ -1002,7 +1036,8 @@ static int detrend_fill(trx_handle *h, const char *who, const ObservedSet *O, bo
     hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
     HIPCHK(h, hipGetLastError());
   } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, r_bytes, hipMemcpyDeviceToDevice, h->stream));
-  return TRX_OK;
+  // step 1b (without a recipe nothing is launched: the call's bits are what they were)
+  return h->norm_on ? launch_normalise(h, who, O) : TRX_OK;
 }
 
 // step 3 of a detrending call (who), every kernel finished and U [nseg][nexp][ncomp] in h->sr_basis: the weighted filter of U
@@ -1150,6 +1185,54 @@ int trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double 
   if (offdiag) HIPCHK(h, hipMemcpy(offdiag, h->d_pc_off.p, X.offdiag_bytes, hipMemcpyDeviceToHost));
   if (nwhole) HIPCHK(h, hipMemcpy(nwhole, h->d_pc_nwhole.p, X.nwhole_bytes, hipMemcpyDeviceToHost));
   return detrend_install(h, who, O, pc->ncomp, X.basis_bytes, X.coef_bytes, X.r_bytes, basis, coef, data, nsingular);
+}
+
+// ---- normalising the observed set: the recipe of step 1b and the detrend of zero components (trx_normalise.hip.h) ----
+int trx_set_normalise(trx_handle *h, const trx_normalise *nm)
+{
+  if (!h) return TRX_E_ARG;
+  std::string msg;
+  if (const int rc = normalise_set_checks(product_state(h), nm, msg)) return fail(h, rc, msg);
+  // (host work alone: the data, the weights and the filter in force stay; the next detrending call takes the recipe)
+  h->norm_on = nm != nullptr;
+  h->norm = nm ? *nm : trx_normalise{};
+  return TRX_OK;
+}
+
+int trx_normalise_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift,
+                           int32_t inject, double p0, double p1, double *data, double *rowscale, double *centre, int64_t *nclipped, int64_t *nbad,
+                           trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_normalise_observed";
+  const ProductState P = product_state(h);
+  std::string msg;
+  if (const int rc = normalise_checks(P, h->norm_on, inject, p0, p1, a, o, nshift, shift, msg)) return fail(h, rc, msg);
+  ObservedSet *const O = h->observed.get();
+  HIPCHK(h, hipSetDevice(h->device));
+  // (the extents steps 0 and 1 take are the detrend's; the fit's own, of one component here, are not used)
+  const SysremExtents X = sysrem_extents(O->npix, O->nexp, O->nseg, 1, 1, 1, kPixBlock, kFiltWaves, kMomWaves);
+  const NormExtents N = normalise_extents(O->npix, O->nexp, O->nseg, 1, kNormWaves);
+  try { h->nm_count.assign(N.count_bytes / sizeof(int32_t), 0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
+  int rc;
+  // steps 0, 1 and 1b, into the call's own buffer
+  if ((rc = detrend_fill(h, who, O, inject != 0, p0, p1, a, o, spectrum, nshift, shift, dbg, X.cells, X.r_bytes, X.c_bytes, X.elem_blocks))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->nm_count.data(), h->d_nm_count.p, N.count_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished)
+  if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, N.r_bytes, hipMemcpyDeviceToHost));
+  if (rowscale) HIPCHK(h, hipMemcpy(rowscale, h->d_nm_scale.p, N.scale_bytes, hipMemcpyDeviceToHost));
+  if (centre) HIPCHK(h, hipMemcpy(centre, h->d_nm_centre.p, N.centre_bytes, hipMemcpyDeviceToHost));
+  // the swap comes last, as detrend_install's: the data in force, the weights of trx_set_observed back, no filter
+  O->d_data.uncover(h->d_hp_r);
+  O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
+  h->filter.reset();
+  // (the counts are integers: per column on the device, over the columns here)
+  int64_t nc = 0, nb = 0;
+  const size_t npix = (size_t)O->npix;
+  for (size_t p = 0; p < npix; p++) { nc += h->nm_count[p]; nb += h->nm_count[npix + p]; }
+  if (nclipped) *nclipped = nc;
+  if (nbad) *nbad = nb;
+  return TRX_OK;
 }
 
 // ---- weighing the observed set by its columns' scatter (trx_scatter.hip.h) --------------------------

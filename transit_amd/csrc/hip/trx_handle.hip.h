@@ -265,6 +265,11 @@ struct trx_handle {
   // trx_highpass_observed (trx_highpass.hip.h), grown on demand: the high-passed data [nexp][npix] a call builds (swapped
   // with the observed set's data when it succeeds; the previous call's, or an undone one, waits here for the next)
   DevBuf d_hp_r;
+  // trx_set_normalise (trx_normalise.hip.h): the recipe of step 1b of the detrending calls (norm_on false: none); belongs to
+  // `observed`.  Grown on demand: the row scales [nexp][nseg], the centres [npix], the columns' two counts [2][npix] (int32;
+  // their host copy: nm_count) and the tiles (their staging vector: nm_tiles, which outlives the upload)
+  bool norm_on = false; trx_normalise norm{};
+  DevBuf d_nm_scale, d_nm_centre, d_nm_count, d_nm_tiles; std::vector<int32_t> nm_count; std::vector<FilterTile> nm_tiles;
 };
 
 namespace {

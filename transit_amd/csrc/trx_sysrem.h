@@ -60,15 +60,15 @@ inline int detrend_checks(const ProductState &S, const trx_detrend *dt, const vo
 }
 
 // The tiles of the observed set's segments, filter_layout's: up to 64 consecutive pixels of one segment each, a segment's
-// tiles in pixel order.  They give the column kernels their column -> segment map.
-inline int sysrem_tiles(const ProductState &S, std::vector<FilterTile> &tiles, std::string &msg)
+// tiles in pixel order.  They give the column kernels their column -> segment map (who: the call that names itself in a refusal).
+inline int sysrem_tiles(const ProductState &S, std::vector<FilterTile> &tiles, std::string &msg, const char *who = "trx_detrend_observed")
 {
   try {
     tiles.clear();
     for (int32_t s = 0; s < S.nseg; s++)
       for (int64_t p = S.seg[(size_t)s]; p < S.seg[(size_t)s + 1]; p += 64)
         tiles.push_back(FilterTile{p, s, (int32_t)std::min<int64_t>(64, S.seg[(size_t)s + 1] - p)});
-  } catch (...) { return refuse(msg, TRX_E_NOMEM, "trx_detrend_observed: out of host memory"); }
+  } catch (...) { return refuse(msg, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
   return TRX_OK;
 }
 

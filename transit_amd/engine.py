@@ -217,6 +217,7 @@ def hip_library():
         _abi.bind_pca_api(lib)
         _abi.bind_scatter_api(lib)
         _abi.bind_hpdata_api(lib)
+        _abi.bind_normalise_api(lib)
         lib.trx_device_count.restype = C.c_int
         lib.trx_abi_version.restype = C.c_int
         if lib.trx_abi_version() != _abi.ABI_VERSION:
@@ -269,6 +270,16 @@ class Highpassed:
 
     def __init__(self, data, ndead):
         self.data, self.ndead = data, ndead
+
+
+class Normalised:
+    """What Engine.normalise_observed returns: data [nexp, npix] the normalised data now installed (+0 at the dead entries and
+    in bad rows and columns), rowscale [nexp, nseg] every row's scale (+0: a bad row), centre [npix] every column's mean in
+    time (+0: a bad column) -- the three None with outputs=False --, nclipped the entries the clip replaced, nbad the live
+    entries that got +0, spectrum the injection run's spectrum (None without)."""
+
+    def __init__(self, data, rowscale, centre, nclipped, nbad, spectrum=None):
+        self.data, self.rowscale, self.centre, self.nclipped, self.nbad, self.spectrum = data, rowscale, centre, nclipped, nbad, spectrum
 
 
 class Engine(CEngine):
@@ -606,6 +617,43 @@ class Engine(CEngine):
         if rc != 0:
             raise EngineError(rc, "trx_highpass_observed", self._last_error())
         return Highpassed(data, int(nd.value))
+
+    def set_normalise(self, nm):
+        """trx_set_normalise: install the recipe of step 1b of the detrending calls (a transit_amd.xcor.Normalise; None:
+        clear it) over the observed set in force: every (exposure, segment) row divided by its quantile, every column
+        divided by or reduced by its mean in time, single entries clipped.  No device work, and nothing in force changes:
+        detrend_observed, pca_observed and normalise_observed take the recipe from their next call on, between the
+        injection and the fit.  set_observed and set_pixels drop it."""
+        rc = self._lib.trx_set_normalise(self._h, C.byref(nm.to_c()) if nm is not None else None)
+        if rc != 0:
+            raise EngineError(rc, "trx_set_normalise", self._last_error())
+
+    def normalise_observed(self, inject=None, outputs: bool = True) -> "Normalised":
+        """trx_normalise_observed: "the detrend of zero components" -- the installed recipe (set_normalise) over the RAW data
+        of set_observed, or over the injected data (inject as detrend_observed takes it), on the device
+        (xcor.normalise_reference, bit for bit).  The result becomes the observed data, the filter slot is cleared and the
+        weights of set_observed go back in force; detrend_observed(0) undoes it, and detrend_observed, pca_observed and this
+        call undo one another.  The weights are NOT changed: rows with rowscale == 0, bad columns and columns of a low
+        centre are for the driver to mask in set_observed.  Returns a Normalised: data [nexp, npix], rowscale [nexp, nseg],
+        centre [npix], nclipped, nbad and spectrum.  outputs=False leaves the three arrays on the device."""
+        nexp, nseg = getattr(self, "mom_shape", (0, 0))
+        npix = getattr(self, "npix", 0)
+        atm = opts = sh = spec = None
+        p0 = p1 = 0.0
+        if inject is not None:
+            atm, opts, shifts, p0, p1 = inject
+            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+            spec = np.zeros(self.nwn)
+        give = bool(outputs)
+        data, scale, centre = np.zeros((nexp, npix)), np.zeros((nexp, nseg)), np.zeros(npix)
+        nc, nb = C.c_int64(0), C.c_int64(0)
+        rc = self._lib.trx_normalise_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
+                                              _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), 0 if inject is None else 1,
+                                              float(p0), float(p1), _dp(data) if give else None, _dp(scale) if give else None,
+                                              _dp(centre) if give else None, C.byref(nc), C.byref(nb), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_normalise_observed", self._last_error())
+        return Normalised(data if give else None, scale if give else None, centre if give else None, int(nc.value), int(nb.value), spec)
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device

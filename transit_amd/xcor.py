@@ -80,6 +80,14 @@ Gram matrix of each segment's whole columns, its eigenvectors by a fixed number 
     jacobi_rounds(nexp)                                  the rounds of one sweep: lists of disjoint pairs (p, q), p < q < nexp
     pca_reference(data, weight, seg_first, ncomp, nsweep)        (basis, coef, resid, eigen, offdiag, nwhole): the mirror
 
+Normalising the observed set ahead of either (Engine.set_normalise / Engine.normalise_observed; trx_set_normalise /
+trx_normalise_observed): step 1b of the detrending calls, between the injection and the fit.  Every (exposure, segment) row
+is divided by a quantile of its live data, every column by (or less) its mean in time, single entries are clipped.
+
+    Normalise(row_kind, col_kind, quantile=0.5, clip=0.0)        a recipe; to_c() its trx_normalise
+    normalise_reference(f0, weight, seg_first, nm)               (data, rowscale, centre, nclipped, nbad): the mirror, the
+                                                                 quantile from a full sort of the live values
+
 The detection map with the filter applied to every cell's own model matrix (Engine.run_filtered_map /
 Batch.run_filtered_map; trx_run_filtered_map): a cell takes at every exposure the row of the lag NEAREST to its velocity,
 that matrix goes through the filter and the moments above, and the cell is the statistic added over the segments and
@@ -990,6 +998,108 @@ def scatter_reference(data, weight, seg_first, kind: int, clip: float = 0.0, min
     else:
         out = np.where(keep[None, :], W, 0.0)
     return var, med, keep, out
+
+
+NORM_ROW_NONE, NORM_ROW_QUANTILE = 0, 1                                                # TRX_NORM_ROW_*
+NORM_COL_NONE, NORM_COL_DIVIDE, NORM_COL_RATIO, NORM_COL_SUBTRACT = 0, 1, 2, 3         # TRX_NORM_COL_*
+
+
+@dataclass
+class Normalise:
+    """One trx_normalise, the recipe of step 1b of the detrending calls: row_kind NORM_ROW_NONE or NORM_ROW_QUANTILE (every
+    (exposure, segment) row divided by its quantile; 0.5: the lower median), col_kind NORM_COL_NONE, _DIVIDE (f / c, about
+    1), _RATIO (f / c - 1, about 0) or _SUBTRACT (f - c, about 0) with c the column's mean in time, clip 0 (none) or >= 1:
+    entries beyond clip sigma of their column are replaced by the column's mean."""
+    row_kind: int
+    col_kind: int
+    quantile: float = 0.5
+    clip: float = 0.0
+
+    def to_c(self):
+        """The trx_normalise of the recipe."""
+        return _abi.TrxNormalise(int(self.row_kind), int(self.col_kind), float(self.quantile), float(self.clip))
+
+
+def normalise_reference(f0, weight, seg_first, nm: Normalise):
+    """(data [nexp, npix], rowscale [nexp, nseg], centre [npix], nclipped, nbad): step 1b as trx_set_normalise defines it
+    (include/transit_hip.h), in numpy double in exactly its order -- the mirror of k_norm_rowscale and k_norm_cols, bit for
+    bit.  f0: the raw or the injected data; weight: the weights as set_observed installed them, None = all 1.  The row scale
+    is the entry of rank floor(quantile * (m - 1)) of a FULL SORT of the row's m live values (np.sort: not the device's
+    bisection); a row is good if m >= 1 and its scale is > 0 (+0 otherwise; 1.0 with NORM_ROW_NONE).  Per column over the
+    entries live in a good row, v ascending: n, s = sum f1, c = s / n; good as the column kind asks; f2 by the kind; with a
+    clip the mean and the squares of f2 about it in scatter_reference's arithmetic, an entry with d * d > (clip * clip) *
+    var replaced by the mean.  Dead entries, bad rows and bad columns are +0; nbad counts the live ones among them."""
+    f0 = np.asarray(f0, dtype=np.float64)
+    if f0.ndim != 2:
+        raise ValueError("normalise_reference: data of shape [nexp][npix]")
+    if nm.row_kind not in (NORM_ROW_NONE, NORM_ROW_QUANTILE) or nm.col_kind not in (NORM_COL_NONE, NORM_COL_DIVIDE, NORM_COL_RATIO, NORM_COL_SUBTRACT):
+        raise ValueError("normalise_reference: unknown row_kind or col_kind")
+    if not (0.0 <= nm.quantile <= 1.0) or not (nm.clip == 0 or (nm.clip >= 1 and math.isfinite(nm.clip))):
+        raise ValueError("normalise_reference: quantile in [0, 1], clip 0 or >= 1")
+    W = np.ones_like(f0) if weight is None else np.asarray(weight, dtype=np.float64)
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    nexp, npix, nseg = f0.shape[0], f0.shape[1], seg.size - 1
+    live = W > 0
+    scale = np.zeros((nexp, nseg))
+    for v in range(nexp):
+        for s in range(nseg):
+            a, b = int(seg[s]), int(seg[s + 1])
+            x = f0[v, a:b][live[v, a:b]]
+            if x.size == 0:
+                continue
+            if nm.row_kind == NORM_ROW_NONE:
+                scale[v, s] = 1.0
+                continue
+            k = int(np.floor(np.float64(nm.quantile) * np.float64(x.size - 1)))
+            q = np.sort(x)[k]
+            scale[v, s] = q if q > 0 else 0.0
+    col_scale = np.repeat(scale, np.diff(seg), axis=1)                # [nexp, npix]: every entry's row scale
+    on = live & (col_scale > 0)
+    with np.errstate(all="ignore"):
+        f1 = f0 / np.where(on, col_scale, 1.0) if nm.row_kind == NORM_ROW_QUANTILE else f0
+        n, s = np.zeros(npix, dtype=np.int64), np.zeros(npix)
+        for v in range(nexp):
+            n = n + on[v]
+            s = np.where(on[v], s + f1[v], s)
+        c = s / np.where(n >= 1, n, 1).astype(np.float64)
+        if nm.col_kind == NORM_COL_NONE:
+            good = n >= 1
+        elif nm.col_kind == NORM_COL_SUBTRACT:
+            good = (n >= 1) & np.isfinite(c)
+        else:
+            good = (n >= 1) & (c > 0) & np.isfinite(c)
+        c = np.where(good, c, 0.0)
+        safe = np.where(good, c, 1.0)
+        if nm.col_kind == NORM_COL_DIVIDE:
+            f2 = f1 / safe[None, :]
+        elif nm.col_kind == NORM_COL_RATIO:
+            t = f1 / safe[None, :]
+            f2 = t - 1.0
+        elif nm.col_kind == NORM_COL_SUBTRACT:
+            f2 = f1 - c[None, :]
+        else:
+            f2 = f1
+        keep = on & good[None, :]
+        nclipped = 0
+        if nm.clip > 0:
+            clips = good & (n >= 2)
+            s2 = np.zeros(npix)
+            for v in range(nexp):
+                s2 = np.where(keep[v], s2 + f2[v], s2)
+            mean = s2 / np.where(clips, n, 1).astype(np.float64)
+            q = np.zeros(npix)
+            for v in range(nexp):
+                d = f2[v] - mean
+                q = np.where(keep[v], q + d * d, q)
+            var = q / np.where(clips, n - 1, 1).astype(np.float64)
+            lim = np.float64(nm.clip) * np.float64(nm.clip)
+            lim = lim * var
+            d = f2 - mean[None, :]
+            hit = keep & clips[None, :] & (d * d > lim[None, :])
+            nclipped = int(np.count_nonzero(hit))
+            f2 = np.where(hit, mean[None, :], f2)
+    data = np.where(keep, f2, 0.0)
+    return data, scale, c, nclipped, int(np.count_nonzero(live & ~keep))
 
 
 def _check_wfilter(obs: Observed, wf: WeightedFilter):
