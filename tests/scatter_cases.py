@@ -72,9 +72,9 @@ def the_set(nexp: int, weighted: bool, scale: float = 1.0):
     return _SETS[key]
 
 
-def clip_margin(var, med, keep):
+def clip_margin(var, med, keep, seg=SEG):
     """(clipped columns, the smallest | var / (9 med) - 1 | over the live columns): how far the clip of 3 is from flipping"""
-    medp = np.repeat(med, np.diff(SEG))
+    medp = np.repeat(med, np.diff(seg))
     live = var > 0
     ratio = var[live] / medp[live]
     return tuple(int(p) for p in np.flatnonzero(live & ~keep)), float(np.min(np.abs(ratio / 9.0 - 1.0)))

@@ -1,8 +1,11 @@
 """The observed-set products on the device past 64 exposures and past 64 segments: moments, trail, Kp-Vsys map, plain and
-weighted filter, the per-cell maps and SYSREM (include/transit_hip.h) against transit_amd.xcor at the sets of many_cases.py.
+weighted filter, the per-cell maps, SYSREM, PCA, the scatter weights, the data-side high-pass and the normalisation
+(include/transit_hip.h) against transit_amd.xcor at the sets of many_cases.py.
 
-The other device tests of this chain run at 4 to 12 exposures and at most 12 segments: the pixel axis is theirs.  Here the
-pixel set and the segments stay test_gpu_moments' and the other two axes grow:
+The other device tests of this chain run at 4 to 12 exposures and at most 12 segments, on test_gpu_moments' 800 pixels in
+segments of at most 400; orders of a detector's length -- 1024, 1025 and 2049 pixels -- are tests/test_gpu_long_orders.py's,
+on many_cases.long_set under the same checkers.  Here the pixel set and the segments stay test_gpu_moments' and the other two
+axes grow:
   - 64, 65 and 130 exposures.  A wave takes the exposures 64 at a time in k_velocity_map and k_cell_stat (the in-order sum
     carried from trip to trip) and in k_sysrem_close's store of the basis; the column kernels take them 4 at a time
     (k_pixel_filter, k_cell_filter, k_pixel_wfilter, k_cell_wfilter, k_wfilter_factor) or 8 at a time (k_sysrem_cols,
@@ -11,22 +14,35 @@ pixel set and the segments stay test_gpu_moments' and the other two axes grow:
     65 and 130.  ncomp 4, 8 and 16 fill the kernels' register arrays with no zero-padded component, 3, 5 and 6 do not;
   - 64, 65 and 130 segments of 5 exposures: k_trail_stat takes the segments 64 at a time and skips undefined statistics,
     k_cell_stat's per-exposure loop over the segments is long.
+What runs on the two axes: moments, trail, velocity map, plain and weighted filter, filtered and exposed map, SYSREM (with
+and without injection) and, of the data-side calls, weigh_observed (raw and detrended data, both kinds, clip 3),
+highpass_observed (halves 5 and 70) and normalise_observed (MEDIAN_RATIO, and quantile 0.9 + divide + clip 3), all in their
+mirrors' bits; pca_observed at 64 and 65 exposures ((5, 8) and (16, 8); 130 is above TRX_PCA_MAX_EXP and refused) and on the
+orders sets, where the empty segments on both sides of index 64 and the dead segment give +0 medians, a zero basis without
+a sign bit, nwhole 0 and untouched data.
 
 No tolerance here is this file's own.  Every comparison is "the same bits" or one of the derived rules of the tests this
 file borrows its checkers from, evaluated at the set's nexp, ncomp and longest segment: test_gpu_moments.check_moments and
 test_gpu_trail.check_trail ((n_max + 16) * 2^-52 of the absolute sums), test_gpu_velocity_map.check_per (xcor.per_bound),
 test_gpu_filter.check_values and check_moments ((nexp + ncomp + 8) * 2^-52 of A), test_gpu_filtered_map.check_contract
 (xcor.cell_bound), the propagation of test_gpu_filtered_map's docstring for the maps against numpy alone, and
-test_gpu_sysrem.check_outputs (bits).  tests/test_many_cases_host.py holds the preconditions of the sets on the host."""
+test_gpu_sysrem.check_outputs, test_gpu_pca.check_outputs, test_gpu_scatter.check_outputs, test_gpu_normalise.check_normalised
+and test_gpu_hpdata's rule (bits).  tests/test_many_cases_host.py holds the preconditions of the sets on the host."""
 import numpy as np
 import pytest
 
+import hpdata_cases as hc
 import many_cases as mc
+import normalise_cases as nc
+import scatter_cases as cs
 import test_gpu_exposed_map as tem
 import test_gpu_filter as tf
 import test_gpu_filtered_map as tfm
 import test_gpu_moments as tm
+import test_gpu_normalise as tn
+import test_gpu_pca as tpc
 import test_gpu_pixels as tp
+import test_gpu_scatter as tsc
 import test_gpu_sysrem as ts
 import test_gpu_trail as tt
 import test_gpu_velocity_map as tv
@@ -34,11 +50,13 @@ import test_gpu_wfilter as twf
 import wfilter_cases as wc
 from test_gpu_batch import atmospheres
 from transit_amd import pixels, xcor
-from transit_amd.engine import Batch, Engine
+from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
 STATS = tv.STATS
+HP = hc.tables(70)["gauss"]
+RECIPES = [tn.MEDIAN_RATIO, xcor.Normalise(xcor.NORM_ROW_QUANTILE, xcor.NORM_COL_DIVIDE, 0.9, 3.0)]
 EPS = 2.0 ** -52
 LAGS = mc.LAGS
 OUTSIDE = np.zeros((3, 4), dtype=bool)
@@ -362,6 +380,105 @@ def test_sysrem_with_injection_and_what_it_installs(case, nexp):
     assert np.count_nonzero(np.isfinite(got[1]).all(axis=0)) > 600 and np.isnan(got[1][:, ms.masked_col]).all()
 
 
+# ---- many exposures: the data-side calls -------------------------------------------------------------------------------
+def weigh_raw_and_detrended(E, ob, ncomp, niter, what):
+    """weigh_observed on the raw data and on the residuals of detrend_observed(ncomp, niter), both kinds, clip 3: the mirror's
+    variance, median, weights, nmasked and nsingular; returns the results of the raw stage"""
+    raw = []
+    for stage in ("raw", "detrended"):
+        D = E.detrend_observed(ncomp, niter) if stage == "detrended" else None
+        data = D.data if D else ob.data
+        for kind in cs.KINDS:
+            mirror = xcor.scatter_reference(data, ob.weight, ob.seg_first, kind, 3.0, 2)
+            R = E.weigh_observed(kind, clip=3.0)
+            tsc.check_outputs(R, mirror, "%s, %s, kind %d" % (what, stage, kind))
+            assert R.nsingular == (tsc.nsingular_of(ob, data, mirror[3], D.basis) if D else 0), (what, stage, kind)
+            if not D:
+                raw.append(R)
+    return raw
+
+
+def highpass_raw_and_detrended(E, ob, ncomp, niter, what):
+    """highpass_observed on the raw data and on the residuals of detrend_observed(ncomp, niter), halves 5 and 70 under a
+    boxcar, a Gaussian and a random table: the mirror's bits and ndead"""
+    for stage in ("raw", "detrended"):
+        data = E.detrend_observed(ncomp, niter).data if stage == "detrended" else ob.data
+        for half in (5, 70):
+            for name, hp in hc.tables(half).items():
+                want, ndead = xcor.highpass_observed_reference(data, ob.weight, ob.seg_first, hp)
+                E.set_highpass(hp)
+                R = E.highpass_observed()
+                assert same_bits(R.data, want) and R.ndead == ndead == np.count_nonzero(ob.weight == 0), (what, stage, half, name)
+    E.set_highpass(None)
+
+
+def normalise_both_recipes(E, ob, what):
+    for nm in RECIPES:
+        E.set_normalise(nm)
+        N = E.normalise_observed()
+        tn.check_normalised(N, xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm), "%s, %s" % (what, nc.name(nm)))
+        assert np.isfinite(N.data).all()
+    E.set_normalise(None)
+
+
+@pytest.mark.parametrize("nexp", mc.NEXPS)
+def test_weigh_observed(case, nexp):
+    ms, px, ob = case.exposures(nexp)
+    E = case.handle(px, ob)
+    weigh_raw_and_detrended(E, ob, 3, 2, ms.name)
+    E.close()
+
+
+@pytest.mark.parametrize("nexp", mc.NEXPS)
+def test_highpass_observed(case, nexp):
+    ms, px, ob = case.exposures(nexp)
+    E = case.handle(px, ob)
+    highpass_raw_and_detrended(E, ob, 3, 2, ms.name)
+    E.close()
+
+
+@pytest.mark.parametrize("nexp", mc.NEXPS)
+def test_normalise_observed(case, nexp):
+    ms, px, ob = case.exposures(nexp)
+    E = case.handle(px, ob)
+    normalise_both_recipes(E, ob, ms.name)
+    E.close()
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("ncomp", [5, 16])
+@pytest.mark.parametrize("nexp", [64, 65])
+def test_pca(case, nexp, ncomp, weighted):
+    """with 5 % masked entries only 3 to 4 % of the columns are whole at these exposure counts: a segment without one has
+    nwhole 0 and a zero basis"""
+    ms, px, full = case.exposures(nexp)
+    ob = full if weighted else ms.observed(case.scale, weighted=False)
+    E = case.handle(px, ob)
+    what = "%s, PCA of %d components, %s" % (ms.name, ncomp, "edge weights" if weighted else "no weights")
+    mirror = xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, 8)
+    D = E.pca_observed(ncomp, 8)
+    tpc.check_outputs(D, mirror, ob, what)
+    nwhole = mirror[5]
+    assert np.array_equal(D.nwhole, nwhole) and (weighted or np.array_equal(nwhole, ms.lengths)), what
+    for s in range(ms.nseg):
+        if nwhole[s] == 0:
+            assert np.all(D.basis[s] == 0) and not np.signbit(D.basis[s]).any() and np.all(D.eigen[s] == 0), (what, s)
+        else:
+            assert np.any(D.basis[s, :, 0] != 0), (what, s)
+    assert nwhole[5] == 0 and nwhole[7] > 0, what
+    print("%s: the mirror's seven; nwhole %s, nsingular %d" % (what, D.nwhole, D.nsingular))
+    E.close()
+
+
+def test_pca_above_its_cap_is_refused(case):
+    ms, px, ob = case.exposures(130)
+    E = case.handle(px, ob)
+    with pytest.raises(EngineError) as ei:
+        E.pca_observed(5, 8)
+    assert ei.value.code == -1 and "nexp 130 is above TRX_PCA_MAX_EXP (128)" in str(ei.value)
+    E.close()
+
+
 # ---- many orders ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nseg", mc.NSEGS)
 def test_orders_moments_trail_and_velocity_map(case, nseg):
@@ -401,6 +518,75 @@ def test_orders_sysrem(case, nseg):
     assert np.all(np.any(D.basis[live, :, 0] != 0, axis=1))
     assert D.nsingular >= 1 + lengths[ms.dead_seg]
     print("%s: basis, coef, data and nsingular (%d) are the mirror's" % (ms.name, D.nsingular))
+    E.close()
+
+
+def orders_edges(ms, nseg):
+    """(the empty segments -- on both sides of index 64 where there is another side --, the dead segment's pixels)"""
+    empty = np.flatnonzero(np.array(ms.lengths) == 0)
+    assert empty.min() < 64 and (nseg < 130 or empty.max() > 64)
+    return empty, ms.segment(ms.dead_seg)
+
+
+@pytest.mark.parametrize("nseg", mc.NSEGS)
+def test_orders_pca(case, nseg):
+    ms, px, ob = case.orders(nseg)
+    E = case.handle(px, ob)
+    mirror = xcor.pca_reference(ob.data, ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 8)
+    D = E.pca_observed(mc.ORDERS_NCOMP, 8)
+    tpc.check_outputs(D, mirror, ob, ms.name)
+    empty, dead = orders_edges(ms, nseg)
+    for s in list(empty) + [ms.dead_seg]:
+        assert np.all(D.basis[s] == 0) and not np.signbit(D.basis[s]).any() and D.nwhole[s] == 0 and np.all(D.eigen[s] == 0) and D.offdiag[s] == 0, s
+    assert np.all(D.coef[:, dead] == 0) and np.array_equal(D.data[:, dead], ob.data[:, dead])
+    for s in np.flatnonzero(D.nwhole == 0):
+        assert np.all(D.basis[s] == 0) and not np.signbit(D.basis[s]).any(), s
+    assert np.count_nonzero(D.nwhole > 0) > nseg // 2 and np.all(np.any(D.basis[D.nwhole > 0][:, :, 0] != 0, axis=1))
+    print("%s: the mirror's seven; %d segments with whole columns, nsingular %d" % (ms.name, np.count_nonzero(D.nwhole > 0), D.nsingular))
+    E.close()
+
+
+@pytest.mark.parametrize("nseg", mc.NSEGS)
+def test_orders_weigh_observed(case, nseg):
+    ms, px, ob = case.orders(nseg)
+    E = case.handle(px, ob)
+    raw = weigh_raw_and_detrended(E, ob, mc.ORDERS_NCOMP, 10, ms.name)
+    empty, dead = orders_edges(ms, nseg)
+    for R in raw:
+        med = R.median[list(empty) + [ms.dead_seg]]
+        assert np.all(med == 0) and not np.signbit(med).any()
+        assert np.all(R.variance[dead] == 0) and np.all(R.weight[:, dead] == 0)
+        live = np.delete(np.arange(nseg), list(empty) + [ms.dead_seg])
+        assert np.count_nonzero(R.median[live] > 0) > nseg // 2
+    E.close()
+
+
+@pytest.mark.parametrize("nseg", mc.NSEGS)
+def test_orders_highpass_observed(case, nseg):
+    ms, px, ob = case.orders(nseg)
+    E = case.handle(px, ob)
+    highpass_raw_and_detrended(E, ob, mc.ORDERS_NCOMP, 10, ms.name)
+    E.set_highpass(HP)
+    R = E.highpass_observed()
+    empty, dead = orders_edges(ms, nseg)
+    assert np.all(R.data[:, dead] == 0) and not np.signbit(R.data[:, dead]).any()      # dead entries are +0
+    E.close()
+
+
+@pytest.mark.parametrize("nseg", mc.NSEGS)
+def test_orders_normalise_observed(case, nseg):
+    """the two recipes, then detrend_observed and pca_observed at ORDERS_NCOMP with MEDIAN_RATIO installed"""
+    ms, px, ob = case.orders(nseg)
+    E = case.handle(px, ob)
+    normalise_both_recipes(E, ob, ms.name)
+    E.set_normalise(tn.MEDIAN_RATIO)
+    norm = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, tn.MEDIAN_RATIO)
+    empty, dead = orders_edges(ms, nseg)
+    assert np.all(norm[1][:, list(empty) + [ms.dead_seg]] == 0) and np.all(norm[0][:, dead] == 0) and not np.signbit(norm[0][:, dead]).any()
+    D = E.detrend_observed(mc.ORDERS_NCOMP, 10)
+    ts.check_outputs(D, xcor.sysrem_reference(norm[0], ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 10), ob, ms.name)
+    D = E.pca_observed(mc.ORDERS_NCOMP, 8)
+    tpc.check_outputs(D, xcor.pca_reference(norm[0], ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 8), ob, ms.name)
     E.close()
 
 

@@ -15,6 +15,7 @@ import pytest
 from host_check import build_check
 
 import hpdata_cases as hc
+import many_cases as mc
 import scatter_cases as cs
 import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
@@ -39,6 +40,49 @@ def test_staging_refusals_extents_guard_and_data_levels_under_sanitizers(check_e
     assert not [line for line in lines if line.startswith("FAILED")]
 
 
+def mirror_is_the_composition(d, w, seg, hp, what):
+    """the mirror of one set under one table against the composition, bit for bit, and what follows from the definition;
+    returns (the mirror's data, the live entries alone in their window)"""
+    dead = np.zeros(d.shape, dtype=bool) if w is None else ~(w > 0)
+    got, ndead = xcor.highpass_observed_reference(d, w, seg, hp)
+    assert same_bits(got, hc.composition(d, w, seg, hp)), what
+    assert ndead == np.count_nonzero(dead) and (ndead > 0) == (w is not None), what
+    assert np.isfinite(got).all(), what
+    # a dead entry is +0; a live entry alone in its window is r - (t0 r) / t0 -- +0 wherever that quotient is exact --; every
+    # other live entry is not zero
+    assert np.all(got[dead] == 0) and not np.signbit(got[dead]).any(), what
+    lone = hc.alone(w, seg, hp, d.shape)
+    assert not (lone & dead).any(), what
+    assert same_bits(got[lone], d[lone] - (hp.taps[0] * d[lone]) / hp.taps[0]), what
+    assert np.all(got[~dead & ~lone] != 0), what
+    if hp.taps[0] == 1.0:
+        assert np.array_equal(got == 0, dead | lone), what
+    return got, lone
+
+
+_LONG = {}
+
+
+def long_data(weighted, stage):
+    """(set, data the high-pass reads, weights or None) of many_cases.long_set: raw, or after xcor.sysrem_reference(.., 3, 2)"""
+    ms = mc.long_set()[0]
+    w = ms.weight if weighted else None
+    if stage == "detrended" and weighted not in _LONG:
+        _LONG[weighted] = xcor.sysrem_reference(ms.data, w, ms.seg_first, 3, 2)[2]
+    return ms, (_LONG[weighted] if stage == "detrended" else ms.data), w
+
+
+@pytest.mark.parametrize("stage", hc.STAGES)
+@pytest.mark.parametrize("weighted", [False, True])
+def test_the_mirror_is_the_composition_on_the_long_orders(weighted, stage):
+    """segments of 1024, 1025 and 2049 pixels: two whole tiles of kHpTile; two and a tile of ONE pixel, whose window is all
+    halo; four and a tile of one pixel"""
+    ms, d, w = long_data(weighted, stage)
+    for half in mc.LONG_HALVES:
+        for name, hp in hc.tables(half).items():
+            mirror_is_the_composition(d, w, ms.seg_first, hp, "long orders, %s, %s, half %d, %s" % ("edge weights" if weighted else "no weights", stage, half, name))
+
+
 @pytest.mark.parametrize("nexp,weighted,stage,seg_name", SETS)
 def test_the_mirror_is_the_composition_bit_for_bit(nexp, weighted, stage, seg_name):
     d, w = hc.the_data(nexp, weighted, stage, seg_name)
@@ -49,19 +93,10 @@ def test_the_mirror_is_the_composition_bit_for_bit(nexp, weighted, stage, seg_na
     for half in hc.HALVES:
         for name, hp in hc.tables(half).items():
             what = "%d exposures, %s, %s, %s, half %d, %s" % (nexp, "edge weights" if weighted else "no weights", stage, seg_name, half, name)
-            got, ndead = xcor.highpass_observed_reference(d, w, seg, hp)
-            assert same_bits(got, hc.composition(d, w, seg, hp)), what
-            assert ndead == np.count_nonzero(dead) and (ndead > 0) == weighted, what
-            assert np.isfinite(got).all(), what
-            # a dead entry is +0; a live entry alone in its window is r - (t0 r) / t0 -- +0 wherever that quotient is exact --; every
-            # other live entry is not zero.  The one-pixel segment's live entries are alone at every half.
-            assert np.all(got[dead] == 0) and not np.signbit(got[dead]).any(), what
-            lone = hc.alone(w, seg, hp, d.shape)
-            assert lone[:, one][~dead[:, one]].all() and not (lone & dead).any(), what
-            assert same_bits(got[lone], d[lone] - (hp.taps[0] * d[lone]) / hp.taps[0]), what
-            assert np.all(got[~dead & ~lone] != 0), what
+            got, lone = mirror_is_the_composition(d, w, seg, hp, what)
+            # The one-pixel segment's live entries are alone at every half.
+            assert lone[:, one][~dead[:, one]].all(), what
             if hp.taps[0] == 1.0:
-                assert np.array_equal(got == 0, dead | lone), what
                 if not weighted and half >= 1:
                     only = np.zeros(d.shape, dtype=bool)
                     only[:, one] = True
@@ -101,6 +136,32 @@ def test_the_preconditions_of_the_sets(nexp):
     assert not a <= sc.MASKED_COL < b
 
 
+def walk_is_the_mirror(check_exe, tmp_path, d, w, seg, half, name):
+    """the program's walk of one set under one table against the mirror, bit for bit"""
+    nexp, npix, weighted = d.shape[0], d.shape[1], w is not None
+    hp = hc.tables(half)[name]
+    src, dst = tmp_path / ("in%d.bin" % half), tmp_path / ("out%d.bin" % half)
+    with open(src, "wb") as f:
+        f.write(np.array([nexp, npix, len(seg) - 1, half, int(weighted)], dtype=np.int64).tobytes())
+        f.write(np.asarray(seg, dtype=np.int64).tobytes())
+        f.write(hp.taps.tobytes())
+        if weighted:
+            f.write(np.ascontiguousarray(w).tobytes())
+        f.write(np.ascontiguousarray(d).tobytes())
+    out = subprocess.run([check_exe, "values", str(src), str(dst)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stderr == "", out.stdout[-2000:] + out.stderr[-4000:]
+    assert "FAILED" not in out.stdout and " 0 differ from the literal definition" in out.stdout
+    lines = {x[0]: x[1:] for x in (line.split() for line in out.stdout.splitlines())}
+    want, ndead = xcor.highpass_observed_reference(d, w, seg, hp)
+    got = np.fromfile(dst, dtype=np.float64).reshape(want.shape)
+    assert same_bits(got, want), (half, name)
+    assert int(lines["ndead"][0]) == ndead
+    waves, full = int(lines["waves"][0]), int(lines["waves"][2])      # ("waves N full M")
+    assert 0 <= full <= waves and (weighted or half == 0 or full < waves)      # (a window over a segment's edge is never full)
+    if half == 0 and not weighted:
+        assert full == waves
+
+
 @pytest.mark.parametrize("nexp,weighted,stage,seg_name", SETS)
 def test_the_programs_walk_is_the_mirror_bit_for_bit(check_exe, tmp_path, nexp, weighted, stage, seg_name):
     """every half; the three tables in turn, so that every table meets every half over the sets"""
@@ -109,27 +170,18 @@ def test_the_programs_walk_is_the_mirror_bit_for_bit(check_exe, tmp_path, nexp, 
     turn = SETS.index((nexp, weighted, stage, seg_name))
     for i, half in enumerate(hc.HALVES):
         name = ("boxcar", "gauss", "random")[(turn + i) % 3]
-        hp = hc.tables(half)[name]
-        src, dst = tmp_path / ("in%d.bin" % half), tmp_path / ("out%d.bin" % half)
-        with open(src, "wb") as f:
-            f.write(np.array([nexp, cs.NPIX, len(seg) - 1, half, int(weighted)], dtype=np.int64).tobytes())
-            f.write(np.asarray(seg, dtype=np.int64).tobytes())
-            f.write(hp.taps.tobytes())
-            if weighted:
-                f.write(np.ascontiguousarray(w).tobytes())
-            f.write(np.ascontiguousarray(d).tobytes())
-        out = subprocess.run([check_exe, "values", str(src), str(dst)], capture_output=True, text=True)
-        assert out.returncode == 0 and out.stderr == "", out.stdout[-2000:] + out.stderr[-4000:]
-        assert "FAILED" not in out.stdout and " 0 differ from the literal definition" in out.stdout
-        lines = {x[0]: x[1:] for x in (line.split() for line in out.stdout.splitlines())}
-        want, ndead = xcor.highpass_observed_reference(d, w, seg, hp)
-        got = np.fromfile(dst, dtype=np.float64).reshape(want.shape)
-        assert same_bits(got, want), (half, name)
-        assert int(lines["ndead"][0]) == ndead
-        waves, full = int(lines["waves"][0]), int(lines["waves"][2])      # ("waves N full M")
-        assert 0 <= full <= waves and (weighted or half == 0 or full < waves)      # (a window over a segment's edge is never full)
-        if half == 0 and not weighted:
-            assert full == waves
+        walk_is_the_mirror(check_exe, tmp_path, d, w, seg, half, name)
+
+
+@pytest.mark.parametrize("stage", hc.STAGES)
+@pytest.mark.parametrize("weighted", [False, True])
+def test_the_programs_walk_on_the_long_orders(check_exe, tmp_path, weighted, stage):
+    """k_data_highpass' own walk on the CPU over the long set: the tiles of one pixel of the 1025- and the 2049-pixel segment,
+    and a half of 600 > kHpTile over three and five tiles"""
+    ms, d, w = long_data(weighted, stage)
+    for half in mc.LONG_HALVES:
+        for name in hc.tables(half):
+            walk_is_the_mirror(check_exe, tmp_path, d, w, ms.seg_first, half, name)
 
 
 def test_the_mirror_refuses_what_it_does_not_define():

@@ -1,11 +1,17 @@
-"""The preconditions of test_gpu_many_exposures.py, checked with numpy alone: the sets of many_cases.py have the edges their
-docstring promises, on the sides of 64 it promises them, and the references the device tests compare with -- xcor.sysrem_reference
-at the (ncomp, niter) pairs used there, xcor.weighted_factor of its basis and of wfilter_cases.random_basis -- are finite and
-leave most columns live.  A failure on the device is then no problem of the inputs."""
+"""The preconditions of test_gpu_many_exposures.py and test_gpu_long_orders.py, checked with numpy alone: the sets of
+many_cases.py have the edges their docstring promises, on the sides of 64 it promises them, and the references the device tests
+compare with -- xcor.sysrem_reference at the (ncomp, niter) pairs used there, xcor.weighted_factor of its basis and of
+wfilter_cases.random_basis -- are finite and leave most columns live; the long set's planted ties straddle the median rank
+across staging trips, its clip of 3 removes exactly the planted columns with a margin, its masked entries sit at the
+high-pass tiles' borders, and PCA finds whole columns in every long segment.  A failure on the device is then no problem of
+the inputs.  (The host check programs run over the long set in test_scatter_host.py, test_sysrem_host.py, test_pca_host.py,
+test_normalise_host.py and test_hpdata_host.py, beside the sets they already read.)"""
 import numpy as np
 import pytest
 
 import many_cases as mc
+import scatter_cases as cs
+import sysrem_cases as sc
 import wfilter_cases as wc
 from transit_amd import xcor
 
@@ -61,7 +67,10 @@ def test_many_orders_sets_have_their_edges(nseg):
 def test_every_live_row_has_pixels(kind, n):
     """every non-empty segment has a non-zero count at every exposure, the masked exposure of its segment and the dead segment
     apart -- the off-grid pixels, which count nowhere, left out"""
-    ms = the_set(kind, n)
+    every_live_row_has_pixels(the_set(kind, n))
+
+
+def every_live_row_has_pixels(ms):
     on = np.ones(ms.npix, dtype=bool)
     on[list(ms.off_grid)] = False
     for s, length in enumerate(ms.lengths):
@@ -77,6 +86,11 @@ def test_every_live_row_has_pixels(kind, n):
 @pytest.mark.parametrize("kind,n", EXPOSURES + ORDERS, ids=ids(EXPOSURES + ORDERS))
 def test_one_cell_leaves_the_lag_grid_at_the_last_exposure_only(kind, n):
     ms = the_set(kind, n)
+    assert kind == "seg" or ms.nexp - 1 >= 63
+    one_cell_leaves_the_lag_grid(ms)
+
+
+def one_cell_leaves_the_lag_grid(ms):
     for offset in (ms.offset, None):
         vm = ms.the_map(offset=offset)
         assert (vm.nkp, vm.nvsys) == (3, 4) and 9 <= vm.nlag <= 11
@@ -85,7 +99,6 @@ def test_one_cell_leaves_the_lag_grid_at_the_last_exposure_only(kind, n):
         cells = np.argwhere(outside.any(axis=-1))
         assert cells.tolist() == [list(mc.OUTSIDE_CELL)]
         assert np.flatnonzero(outside[mc.OUTSIDE_CELL]).tolist() == [ms.nexp - 1]
-        assert kind == "seg" or ms.nexp - 1 >= 63
         # the inside cells take lags from both ends of the grid
         assert idx[~outside].min() == 0 and idx[~outside].max() == vm.nlag - 1
         assert np.array_equal(np.isnan(xcor.map_from_per(np.ones((vm.nlag, ms.nexp)), vm)), outside.any(axis=-1))
@@ -128,4 +141,140 @@ RANDOM = [("exp", n, c) for n in mc.NEXPS for c in (4, 5, 8, 16)] + [("seg", n, 
 def test_a_random_basis_leaves_columns_live(kind, n, ncomp):
     ms = the_set(kind, n)
     dead = check_factor(ms, ms.observed(), wc.random_basis(ms.nseg, ms.nexp, ncomp, seed=50 + ncomp), (kind, n, ncomp))
+    print("%s, a random basis of %d components: %d of %d columns dead" % (ms.name, ncomp, dead, ms.npix))
+
+
+def test_data_set_without_a_trends_factor_is_sysrem_cases_bit_for_bit():
+    """long_set scales data_set's trends; at the default factor of 1 the other sets keep sysrem_cases.data_set's bits"""
+    for nexp, seed in ((5, 3), (12, 52), (65, 165)):
+        assert mc.same_bits(mc.data_set(nexp, sc.NPIX, seed), sc.data_set(nexp, seed))
+        assert mc.same_bits(mc.data_set(nexp, sc.NPIX, seed, noise=0.0, nterms=2), sc.data_set(nexp, seed, noise=0.0, nterms=2))
+    assert not mc.same_bits(mc.data_set(12, sc.NPIX, 52, trends=mc.LONG_TRENDS), sc.data_set(12, 52))
+    assert mc.same_bits(mc.exposures_set(64).data, sc.data_set(64, 164))
+
+
+# ---- the long orders -------------------------------------------------------------------------------------------------
+def test_the_long_set_has_its_edges():
+    ms, pl = mc.long_set()
+    assert (ms.nexp, ms.nseg, ms.npix) == (12, 5, 4105) and ms.lengths == [1024, 1025, 0, 2049, 7]
+    assert ms.lengths[1] == mc.SCAT_TRIP + 1 and ms.lengths[3] == 2 * mc.SCAT_TRIP + 1 == 4 * mc.HP_TILE + 1
+    (p, centre), = ms.off_grid.items()
+    assert ms.seg_first[3] < p < ms.seg_first[4] - 1 and centre == 2700.0
+    w = ms.weight
+    assert w.shape == ms.data.shape == (12, 4105) and np.isfinite(ms.data).all() and ms.data.min() > 0
+    assert w.min() == 0.0 and w[w > 0].min() >= 0.5 and w.max() <= 2.0
+    assert 0.04 < np.count_nonzero(np.delete(w, ms.masked_exp, axis=0) == 0) / (11 * 4105) < 0.06      # 5 % single entries
+    assert ms.masked_seg == 1 and np.all(w[ms.masked_exp, ms.segment(1)] == 0) and ms.seg_first[0] <= ms.masked_col < ms.seg_first[1] and np.all(w[:, ms.masked_col] == 0)
+    assert ms.gain.min() >= 0.5 and ms.gain.max() <= 1.5
+    assert ms.velocity[0] == -40.0 and ms.velocity[-1] == 40.0 and np.all(np.diff(ms.shifts) < 0)
+    assert 3 in np.flatnonzero(ms.scale == 0) and 0.0 in ms.smear
+    every_live_row_has_pixels(ms)
+    one_cell_leaves_the_lag_grid(ms)
+    # the two sets differ in the tie columns alone
+    other, plo = mc.long_set(weighted=False)
+    differ = np.flatnonzero(np.any(other.data != ms.data, axis=0) | np.any(other.weight != w, axis=0))
+    assert set(differ) <= {c for _, a, b in pl.ties + plo.ties for c in (a, b, a - mc.SCAT_TRIP)} and plo.noisy == pl.noisy and plo.near == pl.near
+
+
+def test_the_long_sets_masked_entries_sit_at_the_high_pass_tiles_borders():
+    """a masked entry within HP_NEAR pixels below every kHpTile border of the long segments and one above it, the borders at the
+    segments' last pixel apart (the tiles of one pixel: the tie's copy and a noisy column); under both tie plantings"""
+    for weighted in (True, False):
+        ms, pl = mc.long_set(weighted)
+        borders = mc.hp_borders(ms.lengths)
+        assert [q - int(ms.seg_first[s]) for s, q in borders] == [512, 512, 1024, 512, 1024, 1536, 2048]
+        for s, q in borders:
+            last = q == ms.seg_first[s + 1] - 1
+            below = [(v, p) for v, p, b in pl.near if b == q and q - mc.HP_NEAR <= p < q]
+            above = [(v, p) for v, p, b in pl.near if b == q and q <= p <= q + mc.HP_NEAR]
+            assert len(below) == 1 and len(above) == (0 if last else 1), (s, q)
+            for v, p in below + above:
+                assert ms.weight[v, p] == 0 and (v, s) != (ms.masked_exp, ms.masked_seg) and p != ms.masked_col and ms.seg_first[s] <= p < ms.seg_first[s + 1]
+                assert np.count_nonzero(ms.weight[:, p] > 0) >= 8                    # (single entries, not a dead column)
+        assert len(pl.near) == 12 and mc.HP_NEAR in mc.LONG_HALVES      # a tile's halo crosses the border at every half >= HP_NEAR
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_the_long_sets_ties_straddle_the_median_rank_across_staging_trips(weighted):
+    ms, pl = mc.long_set(weighted)
+    seg, w = ms.seg_first, (ms.weight if weighted else None)
+    var, med, keep, _ = xcor.scatter_reference(ms.data, w, seg, xcor.SCATTER_VARIANCE, 0.0, 2)
+    assert [s for s, _, _ in pl.ties] == list(mc.LONG_TIE_SEGS) == [1, 3]
+    after = []
+    for s, a, b in pl.ties:
+        order = [int(p) for p in mc.ranked(var, seg, s)]
+        m = len(order)
+        r = (m - 1) // 2
+        assert a != b and mc.same_bits(ms.data[:, a], ms.data[:, b]) and mc.same_bits(ms.weight[:, a], ms.weight[:, b])
+        assert mc.same_bits(var[a], var[b]) and var[a] > 0 and np.count_nonzero(var[ms.segment(s)] == var[a]) == 2
+        assert order[r:r + 2] == sorted((a, b)) and mc.same_bits(med[s], var[a])     # the ranks r and r + 1, the lower pixel first
+        assert mc.trip_of(seg, s, a) != mc.trip_of(seg, s, b)
+        after.append(b > a)
+        if not weighted:
+            assert m == ms.lengths[s]
+    assert after == [True, False]                                # the copy after the original in one segment, before it in the other
+    s, a, b = pl.ties[0]
+    assert b == seg[s + 1] - 1 and mc.trip_of(seg, s, b) == 1    # the second trip's only value
+    s, a, b = pl.ties[1]
+    assert (mc.trip_of(seg, s, a), mc.trip_of(seg, s, b)) == (1, 0)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_the_long_sets_clip_of_three_removes_exactly_the_noisy_columns_with_a_margin(weighted):
+    """test_scatter_host's precondition at the long set: the planted columns are the ones removed, and no live column's var / med
+    lies within 5 % of 9"""
+    ms, pl = mc.long_set(weighted)
+    seg, w = ms.seg_first, (ms.weight if weighted else None)
+    assert all(any(seg[s] <= p < seg[s + 1] for p in pl.noisy) for s in mc.LONG_SEGS)
+    assert seg[4] - 1 in pl.noisy and seg[3] + 1024 in pl.noisy and seg[1] - 1 in pl.noisy and seg[1] + 1023 in pl.noisy
+    # the two stages of test_gpu_long_orders.test_weigh_observed: the raw data, and the residuals of 3 components of 2 alternations
+    # (after 10 alternations the components have taken some planted columns up: 6 or 7 of the 10 are clipped, at a margin of 0.044)
+    for stage, data in (("raw", ms.data), ("detrended", xcor.sysrem_reference(ms.data, w, seg, 3, 2)[2])):
+        for min_live in (2, ms.nexp):
+            for kind in cs.KINDS:
+                var, med, keep, _ = xcor.scatter_reference(data, w, seg, kind, 3.0, min_live)
+                clipped, margin = cs.clip_margin(var, med, keep, seg)
+                print("%s, %s, %s, min_live %d: clipped %s, nearest var / (9 med) is %.3f away from 1"
+                      % (ms.name, "edge weights" if weighted else "no weights", stage, min_live, clipped, margin))
+                want = tuple(p for p in sorted(pl.noisy) if var[p] > 0)
+                assert clipped == want and margin > 0.05, stage
+                if min_live == 2:
+                    assert want == tuple(sorted(pl.noisy)), stage
+
+
+def test_pca_finds_whole_columns_in_every_long_segment():
+    ms = mc.long_set()[0]
+    for ncomp in (3, 5):
+        basis, coef, resid, eigen, offdiag, nwhole = xcor.pca_reference(ms.data, ms.weight, ms.seg_first, ncomp, 8)
+        print("%s, %d components: nwhole %s" % (ms.name, ncomp, nwhole))
+        for s in mc.LONG_SEGS:
+            assert 100 < nwhole[s] < ms.lengths[s] and np.all(np.any(basis[s] != 0, axis=0)) and np.all(eigen[s] > 0)
+        assert nwhole[2] == 0 and np.all(basis[2] == 0) and 0 <= nwhole[4] <= 7
+        assert np.isfinite(basis).all() and np.isfinite(resid).all()
+
+
+LONG_SYSREM = [(3, 10, False), (3, 10, True), (16, 10, False), (16, 10, True), (8, 10, True), (5, 10, True)]
+
+
+@pytest.mark.parametrize("ncomp,niter,weighted", LONG_SYSREM)
+def test_the_sysrem_mirror_is_finite_on_the_long_set(ncomp, niter, weighted):
+    """16 components of 12 exposures leave no column live under a weighted filter -- the device's nsingular is then the whole set,
+    which the device test compares all the same --; up to 8 most columns stay live"""
+    ms = mc.long_set()[0]
+    ob = ms.observed(weighted=weighted)
+    basis, coef, resid = xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, ncomp, niter)
+    assert basis.shape == (ms.nseg, ms.nexp, ncomp) and np.isfinite(basis).all() and np.isfinite(coef).all() and np.isfinite(resid).all()
+    assert np.all(basis[2] == 0) and np.all(np.any(basis[[0, 1, 3, 4], :, 0] != 0, axis=1))
+    if weighted:
+        assert np.all(basis[ms.masked_seg, ms.masked_exp] == 0) and not np.signbit(basis[ms.masked_seg, ms.masked_exp]).any()
+    live = xcor.weighted_factor(ob, xcor.WeightedFilter(basis))[2]
+    print("%s, %d components of %d alternations, %s: %d of %d columns dead" % (ms.name, ncomp, niter, "weighted" if weighted else "no weights", np.count_nonzero(~live), ms.npix))
+    if ncomp <= 8:
+        assert np.count_nonzero(live) >= 0.75 * ms.npix and not (weighted and live[ms.masked_col])
+
+
+@pytest.mark.parametrize("ncomp", [6, 8])
+def test_a_random_basis_leaves_columns_live_on_the_long_set(ncomp):
+    ms = mc.long_set()[0]
+    dead = check_factor(ms, ms.observed(), wc.random_basis(ms.nseg, ms.nexp, ncomp, seed=50 + ncomp), ("long", ncomp))
     print("%s, a random basis of %d components: %d of %d columns dead" % (ms.name, ncomp, dead, ms.npix))

@@ -15,6 +15,7 @@ import pytest
 
 from host_check import build_check
 
+import many_cases as mc
 import normalise_cases as nc
 import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
@@ -82,6 +83,36 @@ def test_the_programs_outputs_are_the_mirrors_bit_for_bit(check_exe, tmp_path, w
             assert np.all((scale == 1.0) | (scale == 0.0)), what
         if nm.clip == 0:
             assert nclipped == 0, what
+
+
+LONG_RECIPES = [xcor.Normalise(xcor.NORM_ROW_QUANTILE, xcor.NORM_COL_RATIO, 0.5, 0.0), xcor.Normalise(xcor.NORM_ROW_QUANTILE, xcor.NORM_COL_DIVIDE, 0.9, 3.0)]
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nm", LONG_RECIPES, ids=nc.name)
+def test_the_programs_outputs_on_the_long_orders(check_exe, tmp_path, nm, weighted):
+    """many_cases.long_set under the two recipes of tests/test_gpu_long_orders.py: rows of 1024 and 1025 keys below the staging
+    capacity, of 2049 one above it; the quantile against a full sort, and the mirror's median against np.sort's lower middle"""
+    ms = mc.long_set()[0]
+    w = ms.weight if weighted else None
+    want = xcor.normalise_reference(ms.data, w, ms.seg_first, nm)
+    got = program(check_exe, tmp_path / "set.txt", ms.data, w, ms.seg_first, nm)
+    for g, m in zip(got[:3], want[:3]):
+        assert same_bits(g, m), nc.name(nm)
+    assert got[3:] == want[3:], nc.name(nm)
+    out, scale, centre, nclipped, nbad = want
+    live = np.ones_like(ms.data, dtype=bool) if w is None else w > 0
+    assert np.isfinite(out).all() and np.all(out[~live] == 0) and not np.signbit(out[~live]).any()
+    assert np.all(scale[:, 2] == 0) and np.all(scale[:, [0, 3, 4]] > 0) and (nm.clip > 0 or nclipped == 0)
+    assert (scale[ms.masked_exp, ms.masked_seg] == 0) == weighted and np.count_nonzero(scale[:, ms.masked_seg] > 0) == ms.nexp - int(weighted)
+    for v in range(ms.nexp):
+        for s in range(ms.nseg):
+            x = ms.data[v, ms.segment(s)][live[v, ms.segment(s)]]
+            if x.size == 0:
+                assert scale[v, s] == 0
+                continue
+            k = int(np.floor(nm.quantile * (x.size - 1)))
+            assert scale[v, s] == np.sort(x)[k] and (nm.quantile != 0.5 or k == (x.size - 1) // 2)
 
 
 def test_the_edge_set_has_its_edges():

@@ -14,6 +14,7 @@ import pytest
 
 from host_check import build_check
 
+import many_cases as mc
 import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
 
@@ -114,6 +115,28 @@ def test_the_programs_results_are_the_mirrors_bit_for_bit(check_exe, tmp_path, n
         assert np.array_equal(nwhole, sc.LENGTHS) and np.all(np.any(basis[[0, 1, 2, 3, 4, 6, 7], :, 0] != 0, axis=1))
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("ncomp", [3, 5])
+def test_the_programs_results_on_the_long_orders(check_exe, tmp_path, ncomp, weighted):
+    """many_cases.long_set at the (ncomp, nsweep) of tests/test_gpu_long_orders.py: Gram rows and live counts over 1024, 1025
+    and 2049 pixels"""
+    ms = mc.long_set()[0]
+    w = ms.weight if weighted else None
+    want = xcor.pca_reference(ms.data, w, ms.seg_first, ncomp, 8)
+    same_as_mirror(run_program(check_exe, tmp_path / "set.txt", ms.nexp, ncomp, 8, ms.seg_first, ms.data, w), want)
+    basis, coef, resid, eigen, offdiag, nwhole = want
+    assert np.all(basis[2] == 0) and not np.signbit(basis[2]).any() and np.all(eigen[2] == 0) and nwhole[2] == 0 and offdiag[2] == 0
+    assert np.isfinite(basis).all() and np.isfinite(resid).all() and np.isfinite(coef).all()
+    if weighted:
+        k = ms.segment(ms.masked_seg)
+        assert np.all(basis[ms.masked_seg, ms.masked_exp] == 0) and not np.signbit(basis[ms.masked_seg, ms.masked_exp]).any()
+        assert np.array_equal(resid[ms.masked_exp, k], ms.data[ms.masked_exp, k])
+        for s in mc.LONG_SEGS:
+            assert 0 < nwhole[s] < ms.lengths[s] and np.any(basis[s, :, 0] != 0)
+    else:
+        assert np.array_equal(nwhole, ms.lengths) and np.all(np.any(basis[[0, 1, 3, 4], :, 0] != 0, axis=1))
+
+
 def test_a_set_whose_every_column_has_a_hole(check_exe, tmp_path):
     nexp = 7
     data = sc.data_set(nexp, 3)
@@ -136,13 +159,13 @@ def test_weights_none_are_weights_one(nexp, ncomp, nsweep):
         assert sc.same_bits(a, b)
 
 
-def prototype_set(nexp=7, seed=2, noise=1e-3, fall=0.3):
+def prototype_set(nexp=7, seed=2, noise=1e-3, fall=0.3, npix=sc.NPIX):
     """test_sysrem_host.prototype_set's recipe without its weights: six rank-one terms of falling size plus noise"""
     rng = np.random.default_rng(seed)
-    d = np.zeros((nexp, sc.NPIX))
+    d = np.zeros((nexp, npix))
     for k in range(6):
-        sign = 1 if k == 0 else rng.choice([-1, 1], sc.NPIX)[None, :]
-        d += fall ** k * rng.uniform(0.5, 1.5, nexp)[:, None] * rng.uniform(0.5, 1.5, sc.NPIX)[None, :] * sign
+        sign = 1 if k == 0 else rng.choice([-1, 1], npix)[None, :]
+        d += fall ** k * rng.uniform(0.5, 1.5, nexp)[:, None] * rng.uniform(0.5, 1.5, npix)[None, :] * sign
     d += noise * rng.standard_normal(d.shape)
     return d
 
@@ -215,6 +238,31 @@ def test_the_mirror_against_svd_basis(nexp, ncomp):
         u = got[s][:, np.any(got[s] != 0, axis=0)]               # the non-zero vectors (all of them on the segments of >= 7 pixels)
         assert u.shape[1] == ncomp or s not in big
         assert u.shape[1] == 0 or np.max(np.abs(u.T @ u - np.eye(u.shape[1]))) < 1e-13
+    assert np.all(np.diff(eigen, axis=1) <= 0)
+
+
+@pytest.mark.parametrize("nexp", [7, 12])
+@pytest.mark.parametrize("ncomp", [1, 3, 5])
+def test_the_mirror_against_svd_basis_on_the_long_orders(nexp, ncomp):
+    """test_the_mirror_against_svd_basis' rules -- SVD_BOUND on the segments of >= 7 pixels, offdiag <= 1e-12 eigen[:, 0] after
+    8 sweeps, orthonormal vectors, descending eigenvalues -- at the lengths of many_cases.long_set: prototype_set's recipe
+    over 4105 pixels in segments of 1024, 1025, 0, 2049 and 7.  The Gram matrix's row sums take such a row in lanes of 17 and
+    of 33 terms; numpy's SVD knows nothing of either."""
+    seg = xcor.segments(mc.LONG_LENGTHS)
+    d = prototype_set(nexp, npix=int(seg[-1]))
+    got, _, _, eigen, offdiag, nwhole = xcor.pca_reference(d, None, seg, ncomp, 8)
+    want = signed(xcor.svd_basis(d, seg, ncomp))
+    big = [0, 1, 3, 4]
+    worst = float(np.abs(got - want)[big].max())
+    rel = offdiag / np.where(eigen[:, 0] > 0, eigen[:, 0], 1.0)
+    print("long orders, nexp %d, ncomp %d: largest |mirror - svd_basis| %.2e; offdiag / eigen[:, 0] per segment after 8 sweeps: %s"
+          % (nexp, ncomp, worst, np.array2string(rel, precision=2)))
+    assert np.array_equal(nwhole, mc.LONG_LENGTHS) and np.all(got[2] == 0)
+    assert worst < SVD_BOUND[ncomp]
+    assert np.all(rel <= 1e-12)
+    for s in big:
+        u = got[s]
+        assert np.all(np.any(u != 0, axis=0)) and np.max(np.abs(u.T @ u - np.eye(ncomp))) < 1e-13
     assert np.all(np.diff(eigen, axis=1) <= 0)
 
 

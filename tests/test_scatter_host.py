@@ -14,6 +14,7 @@ import pytest
 
 from host_check import build_check
 
+import many_cases as mc
 import scatter_cases as cs
 from transit_amd import _abi, build, xcor
 
@@ -48,18 +49,13 @@ def mirror(nexp, weighted, kind, clip, min_live):
     return _MIRROR[key]
 
 
-@pytest.mark.parametrize("full", [False, True])
-@pytest.mark.parametrize("clip", cs.CLIPS)
-@pytest.mark.parametrize("kind", cs.KINDS)
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("nexp", [7, 12])
-def test_the_programs_variances_medians_and_weights_are_the_mirrors_bit_for_bit(check_exe, tmp_path, nexp, weighted, kind, clip, full):
-    min_live = nexp if full else 2
-    data, w, (var, med, keep, out_w) = mirror(nexp, weighted, kind, clip, min_live)
-    path = tmp_path / "set.txt"
+def program_is_the_mirror(check_exe, path, data, w, seg, kind, clip, min_live, want):
+    """the program's var, med, w' and nmasked of one set under one call against the mirror's, bit for bit"""
+    var, med, keep, out_w = want
+    nexp = data.shape[0]
     with open(path, "w") as f:
-        f.write("%d %d %d %d %d %s\n%s\n" % (nexp, kind, min_live, len(cs.LENGTHS), int(weighted), float(clip).hex(), " ".join(str(int(x)) for x in cs.SEG)))
-        for arr in (data,) + ((w,) if weighted else ()):
+        f.write("%d %d %d %d %d %s\n%s\n" % (nexp, kind, min_live, len(seg) - 1, int(w is not None), float(clip).hex(), " ".join(str(int(x)) for x in seg)))
+        for arr in (data,) + ((w,) if w is not None else ()):
             f.write(" ".join(float(x).hex() for x in arr.reshape(-1)) + "\n")
     out = subprocess.run([check_exe, "set", str(path)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stderr == "", out.stdout[-2000:] + out.stderr[-4000:]
@@ -69,8 +65,19 @@ def test_the_programs_variances_medians_and_weights_are_the_mirrors_bit_for_bit(
     assert same_bits(got["var"], var)
     assert same_bits(got["med"], med)
     assert same_bits(got["w"].reshape(out_w.shape), out_w)
+    assert int(lines["nmasked"][0]) == np.count_nonzero((var > 0) & ~keep)
+
+
+@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("clip", cs.CLIPS)
+@pytest.mark.parametrize("kind", cs.KINDS)
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nexp", [7, 12])
+def test_the_programs_variances_medians_and_weights_are_the_mirrors_bit_for_bit(check_exe, tmp_path, nexp, weighted, kind, clip, full):
+    min_live = nexp if full else 2
+    data, w, (var, med, keep, out_w) = mirror(nexp, weighted, kind, clip, min_live)
+    program_is_the_mirror(check_exe, tmp_path / "set.txt", data, w, cs.SEG, kind, clip, min_live, (var, med, keep, out_w))
     live = var > 0
-    assert int(lines["nmasked"][0]) == np.count_nonzero(live & ~keep)
     # the edges: the empty segment's median is +0, the one-pixel segment's is its column's variance; the planted dead columns
     # (+0 where that column is dead)
     assert med[5] == 0 and not np.signbit(med[5]) and same_bits(med[0], var[0]) and (var[0] > 0 or (weighted and full))
@@ -156,6 +163,60 @@ def test_the_variance_against_numpys():
                 col = data[:, p] if w is None else data[w[:, p] > 0, p]
                 worst = max(worst, abs(var[p] - np.var(col, ddof=1)) / var[p])
     print("largest relative |mirror - np.var(ddof=1)|: %.2e" % worst)
+    assert worst < 1e-13
+
+
+# ---- the long orders of many_cases.long_set: 1024, 1025, 0, 2049 and 7 pixels -- one staging trip exactly, a second trip of
+# one value, three trips; the ties across trips, the noisy columns in the one-column tile and at the 1023 | 1024 border
+def long_mirror(weighted, kind, clip, min_live):
+    """(set, planted, weights or None, the mirror's four) of the long set whose ties are planted for this weighting"""
+    key = ("long", weighted, kind, clip, min_live)
+    if key not in _MIRROR:
+        ms, pl = mc.long_set(weighted)
+        w = ms.weight if weighted else None
+        _MIRROR[key] = (ms, pl, w, xcor.scatter_reference(ms.data, w, ms.seg_first, kind, clip, min_live))
+    return _MIRROR[key]
+
+
+@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("clip", cs.CLIPS)
+@pytest.mark.parametrize("kind", cs.KINDS)
+@pytest.mark.parametrize("weighted", [False, True])
+def test_the_programs_variances_medians_and_weights_on_the_long_orders(check_exe, tmp_path, weighted, kind, clip, full):
+    """the kernels' own source on the CPU, kScatLds = 1024 as on the device: the 1025- and the 2049-pixel segment take two and
+    three staging trips, the last of one value padded to kScatTrip; every (kind, clip, min_live) of the 800-pixel test"""
+    min_live = mc.LONG_NEXP if full else 2
+    ms, pl, w, want = long_mirror(weighted, kind, clip, min_live)
+    program_is_the_mirror(check_exe, tmp_path / "set.txt", ms.data, w, ms.seg_first, kind, clip, min_live, want)
+    var, med, keep, out_w = want
+    assert med[2] == 0 and not np.signbit(med[2]) and np.isfinite(var).all() and np.isfinite(out_w).all() and not np.signbit(out_w).any()
+    if min_live == 2:
+        for s, a, b in pl.ties:
+            assert same_bits(med[s], var[a]) and same_bits(var[a], var[b])
+    elif weighted:                                               # an exposure is masked over the whole 1025-pixel segment: no column of 12
+        assert med[ms.masked_seg] == 0 and not var[ms.segment(ms.masked_seg)].any()
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_the_median_is_the_sorted_live_variances_lower_middle_on_the_long_orders(weighted):
+    for min_live in (2, mc.LONG_NEXP):
+        ms, _, _, (var, med, _, _) = long_mirror(weighted, xcor.SCATTER_VARIANCE, 0.0, min_live)
+        for s in range(ms.nseg):
+            x = var[ms.segment(s)]
+            x = x[x > 0]
+            assert same_bits(med[s], np.sort(x)[(x.size - 1) // 2] if x.size else 0.0)
+
+
+def test_the_variance_against_numpys_on_the_long_orders():
+    """test_the_variance_against_numpys' rule -- 1e-13 of the variance -- over the 4105 columns of the long set, with and
+    without the weights"""
+    worst = 0.0
+    for weighted in (False, True):
+        ms, _, w, (var, _, _, _) = long_mirror(weighted, xcor.SCATTER_VARIANCE, 0.0, 2)
+        for p in np.flatnonzero(var > 0):
+            col = ms.data[:, p] if w is None else ms.data[w[:, p] > 0, p]
+            worst = max(worst, abs(var[p] - np.var(col, ddof=1)) / var[p])
+    print("long orders: largest relative |mirror - np.var(ddof=1)|: %.2e" % worst)
     assert worst < 1e-13
 
 

@@ -13,6 +13,7 @@ import pytest
 
 from host_check import build_check
 
+import many_cases as mc
 import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
 
@@ -47,16 +48,12 @@ def mirror(nexp, weighted, ncomp, niter):
     return _MIRROR[key]
 
 
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("niter", [1, 2, 10])
-@pytest.mark.parametrize("ncomp", [1, 3, 5])
-@pytest.mark.parametrize("nexp", [7, 12])
-def test_the_programs_vectors_and_residuals_are_the_mirrors_bit_for_bit(check_exe, tmp_path, nexp, ncomp, niter, weighted):
-    data, w, (basis, coef, resid) = mirror(nexp, weighted, ncomp, niter)
-    path = tmp_path / "set.txt"
+def program_is_the_mirror(check_exe, path, data, w, seg, ncomp, niter, want):
+    """the program's U, coef and residuals of one set against the mirror's, bit for bit"""
+    basis, coef, resid = want
     with open(path, "w") as f:
-        f.write("%d %d %d %d %d\n%s\n" % (nexp, ncomp, niter, len(sc.LENGTHS), int(weighted), " ".join(str(int(x)) for x in sc.SEG)))
-        for arr in (data,) + ((w,) if weighted else ()):
+        f.write("%d %d %d %d %d\n%s\n" % (data.shape[0], ncomp, niter, len(seg) - 1, int(w is not None), " ".join(str(int(x)) for x in seg)))
+        for arr in (data,) + ((w,) if w is not None else ()):
             f.write(" ".join(float(x).hex() for x in arr.reshape(-1)) + "\n")
     out = subprocess.run([check_exe, "set", str(path)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stderr == "", out.stdout[-2000:] + out.stderr[-4000:]
@@ -66,6 +63,34 @@ def test_the_programs_vectors_and_residuals_are_the_mirrors_bit_for_bit(check_ex
     assert sc.same_bits(got["U"].reshape(basis.shape), basis)
     assert sc.same_bits(got["coef"].reshape(coef.shape), coef)
     assert sc.same_bits(got["r"].reshape(resid.shape), resid)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("ncomp,niter", [(3, 10), (16, 10)])
+def test_the_programs_vectors_and_residuals_on_the_long_orders(check_exe, tmp_path, ncomp, niter, weighted):
+    """many_cases.long_set: rows of 1024, 1025 and 2049 pixels -- four row steps of 256, four and one lane, eight and one lane --
+    at the (ncomp, niter) of tests/test_gpu_long_orders.py"""
+    ms = mc.long_set()[0]
+    w = ms.weight if weighted else None
+    want = xcor.sysrem_reference(ms.data, w, ms.seg_first, ncomp, niter)
+    program_is_the_mirror(check_exe, tmp_path / "set.txt", ms.data, w, ms.seg_first, ncomp, niter, want)
+    basis, coef, resid = want
+    assert np.all(basis[2] == 0) and not np.signbit(basis[2]).any() and np.isfinite(basis).all() and np.isfinite(resid).all()
+    assert np.all(np.any(basis[[0, 1, 3, 4], :, 0] != 0, axis=1))
+    if weighted:
+        k = ms.segment(ms.masked_seg)
+        assert np.all(basis[ms.masked_seg, ms.masked_exp] == 0) and not np.signbit(basis[ms.masked_seg, ms.masked_exp]).any()
+        assert np.array_equal(resid[ms.masked_exp, k], ms.data[ms.masked_exp, k])
+        assert np.all(coef[:, ms.masked_col] == 0) and np.array_equal(resid[:, ms.masked_col], ms.data[:, ms.masked_col])
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("niter", [1, 2, 10])
+@pytest.mark.parametrize("ncomp", [1, 3, 5])
+@pytest.mark.parametrize("nexp", [7, 12])
+def test_the_programs_vectors_and_residuals_are_the_mirrors_bit_for_bit(check_exe, tmp_path, nexp, ncomp, niter, weighted):
+    data, w, (basis, coef, resid) = mirror(nexp, weighted, ncomp, niter)
+    program_is_the_mirror(check_exe, tmp_path / "set.txt", data, w, sc.SEG, ncomp, niter, (basis, coef, resid))
     # the edges: the empty segment's vectors are zero; under the edge weights the masked exposure's a_v is +0 and its
     # residuals are the data, and the masked column keeps its data and a zero coefficient
     assert np.all(basis[5] == 0) and not np.signbit(basis[5]).any()
@@ -113,13 +138,13 @@ def test_wave_sum_and_row_sum_orders():
     assert xcor.row_sum(np.zeros(0)) == 0.0 and xcor.row_sum(np.ones((3, 200))).tolist() == [200.0] * 3
 
 
-def prototype_set(seed=2, noise=1e-3, fall=0.3):
+def prototype_set(seed=2, noise=1e-3, fall=0.3, npix=sc.NPIX):
     """7 exposures over the shared segments: six rank-one terms of falling size plus noise, 5 % masked entries"""
     rng = np.random.default_rng(seed)
-    d = np.zeros((7, sc.NPIX))
+    d = np.zeros((7, npix))
     for k in range(6):
-        sign = 1 if k == 0 else rng.choice([-1, 1], sc.NPIX)[None, :]
-        d += fall ** k * rng.uniform(0.5, 1.5, 7)[:, None] * rng.uniform(0.5, 1.5, sc.NPIX)[None, :] * sign
+        sign = 1 if k == 0 else rng.choice([-1, 1], npix)[None, :]
+        d += fall ** k * rng.uniform(0.5, 1.5, 7)[:, None] * rng.uniform(0.5, 1.5, npix)[None, :] * sign
     d += noise * rng.standard_normal(d.shape)
     w = rng.uniform(0.5, 2.0, d.shape)
     w[rng.random(d.shape) < 0.05] = 0.0
@@ -142,6 +167,22 @@ def test_the_mirror_against_sysrem_basis(ncomp):
           % (ncomp, worst, float(diff[0, :, 0].max())))
     assert worst < 1e-11
     assert float(diff[0, :, 0].max()) < 1e-11
+
+
+@pytest.mark.parametrize("ncomp", [3, 5])
+def test_the_mirror_against_sysrem_basis_on_the_long_orders(ncomp):
+    """test_the_mirror_against_sysrem_basis' rule, 1e-11 on the segments of >= 7 pixels, at the lengths of many_cases.long_set:
+    prototype_set's recipe over 4105 pixels in segments of 1024, 1025, 0, 2049 and 7.  The mirror's row sums take such a row
+    in lanes of 17 and of 33 terms, numpy's pairwise: a mirror that dropped or doubled a row step would differ by order 1."""
+    seg = xcor.segments(mc.LONG_LENGTHS)
+    d, w = prototype_set(npix=int(seg[-1]))
+    got = xcor.sysrem_reference(d, w, seg, ncomp, 10)[0]
+    want = xcor.sysrem_basis(d, w, seg, ncomp, 10)
+    diff = np.abs(got - want)
+    worst = float(diff[[0, 1, 3, 4]].max())
+    print("long orders, ncomp %d: largest |mirror - sysrem_basis| on the segments of >= 7 pixels %.2e" % (ncomp, worst))
+    assert np.all(got[2] == 0) and np.all(want[2] == 0)
+    assert worst < 1e-11
 
 
 def test_injection_fixed_points():
