@@ -1087,6 +1087,54 @@ int  trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double
                       double *offdiag /* [nseg] */, int64_t *nwhole /* [nseg] */,
                       int64_t *nsingular, trx_debug *dbg);      /* every output may be NULL */
 
+/* The same call with a REGRESSION ON GIVEN TIME VECTORS in SYSREM's place: every pixel column is fitted by weighted least
+ * squares with vectors the caller already has -- 1, airmass and airmass^2 (Brogi et al. 2012), a basis frozen from an
+ * earlier trx_detrend_observed or another night, the vectors of a telluric-rich order for all orders --, optionally
+ * followed by a few SYSREM components on what is left.  It is trx_set_weighted_filter's projector applied to the data:
+ * one factor serves the data here and the model in every run after it, so the data went through exactly the operation
+ * the model goes through.  The injection (steps 0, 1 and 1b), the outcome and the undo (steps 3 and 4) are
+ * trx_detrend_observed's, through the same state.  Every operation is IEEE double rounded once, no fused multiply-add;
+ * sums start from +0 in the order written; there are no atomics.  W is the weights as trx_set_observed installed them
+ * (1 without), NEVER a weigh call's result.  Per segment s, U = vectors[s] ([nexp][nvec]), per pixel column p of it,
+ * w[v] = W[v][p]:
+ * 2a. The factor: the normal matrix N = U^T diag(w) U, its L D L^T factor and the pivot rule exactly as
+ *     trx_set_weighted_filter defines them (the same kernel, TRX_WFILTER_PIVOT).  nsingular_fit counts the columns with a
+ *     singular pivot: a column live at fewer than nvec exposures or masked everywhere, a segment whose vectors are
+ *     linearly dependent.
+ * 2b. The fit, for a column with no singular pivot:
+ *       y_j = sum over v ascending of (U[v][j] * w[v]) * f0[v][p]
+ *       c = that definition's forward and back solve of y;  coef[j][p] = c_j
+ *       r[v][p] = f0[v][p] - (sum over j ascending of U[v][j] * c_j)          every v, dead entries included
+ *     For a column with a singular pivot c_j = +0 for every j, the solve's result is not used and r = f0, as SYSREM's
+ *     den = 0 has it.  The bits of a column depend on its own f0 and w and on its segment's vectors and nvec only.
+ * 2c. nfit > 0: SYSREM of nfit components and niter alternations on r, step 2 of trx_detrend_observed unchanged, giving
+ *     U_fit[s][v][i] and coef[nvec + i][p].
+ * 3.  trx_detrend_observed's outcome with the merged basis B[s][v] = (vectors[s][v][0 .. nvec), U_fit[s][v][0 .. nfit)):
+ *     at once and only after every kernel has finished r becomes the observed data, the filter slot takes the weighted
+ *     filter of B through trx_set_weighted_filter's path against W (nsingular as there; with nfit = 0 the factor of 2a IS
+ *     the filter's, made once), the set's weights go back in force and a high-pass over the data is discarded.  basis,
+ *     coef and data, where given, receive B, coef and r.
+ * 4.  rg NULL or nvec = 0 is trx_detrend_observed's undo (nsingular_fit and nsingular, when given, 0).  Any of
+ *     trx_detrend_observed, trx_pca_observed, trx_normalise_observed and this call undoes any other, and every call starts
+ *     from F.
+ * TRX_E_ARG, the reason in trx_last_error, nothing touched, checked in this order: no observed set; nvec < 0 or above
+ * TRX_FILTER_MAX; nfit < 0; nvec + nfit above TRX_FILTER_MAX; with nfit > 0 niter < 1 or above TRX_SYSREM_MAX_ITER; a NULL
+ * vectors; a non-finite entry of it (naming "segment S"); then inject and the injection's arguments as
+ * trx_detrend_observed has them.  TRX_E_UNSUPPORTED on a shard.  A later TRX_E_HIP or TRX_E_NOMEM leaves the data, the
+ * weights and the filter in force as they were.
+ * Not here: a batch form, shards, a fit in log flux, vectors that differ from column to column. */
+typedef struct {
+  int32_t nvec, nfit;        /* given vectors 1 .. TRX_FILTER_MAX (0: undo); SYSREM components fitted after them, >= 0 */
+  int32_t niter, inject;     /* alternations per fitted component (read only if nfit > 0); as trx_detrend            */
+  double  p0, p1;            /* as trx_detrend */
+  const double *vectors;     /* [nseg][nexp][nvec], finite: trx_wfilter's basis layout */
+} trx_regress;               /* 40 bytes */
+int  trx_regress_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum /* as trx_detrend_observed */,
+                          int32_t nshift, const double *shift, const trx_regress *rg,
+                          double *basis /* [nseg][nexp][nvec+nfit] */, double *coef /* [nvec+nfit][npix] */,
+                          double *data /* [nexp][npix]: the residuals now installed */,
+                          int64_t *nsingular_fit, int64_t *nsingular, trx_debug *dbg);      /* every output may be NULL */
+
 /* Weighing the observed set by the scatter of its pixel columns, on the device: the step of a detection pipeline between
  * SYSREM and the map.  One call reads the data the handle holds, forms every column's variance in time and every
  * segment's median variance, masks the columns whose variance stands out of their segment's, writes the new weights and
@@ -1173,7 +1221,7 @@ int  trx_highpass_observed(trx_handle *h, int32_t apply /* 1: high-pass, 0: undo
  * trx_pca_observed run it on f0 in the call's own buffer between the injection (step 1) and the fit (step 2), so that an
  * injection-recovery loop injects into the RAW data and normalises afterwards, as the pipeline under test does, without
  * the data leaving the device.  trx_normalise_observed is "the detrend of zero components": steps 0, 1 and 1b alone.  The
- * documented order is normalise, detrend or pca, high-pass, weigh, the map.
+ * documented order is normalise, detrend, pca or regress, high-pass, weigh, the map.
  *
  * Every operation is IEEE double rounded once, no fused multiply-add; sums start from +0 in the order written; no atomics.
  * W is the weights as trx_set_observed installed them (1 without) -- never a weigh call's --; an entry is LIVE if W[v][p] > 0.

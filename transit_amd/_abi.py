@@ -126,6 +126,11 @@ class TrxPca(C.Structure):
                 ("p0", C.c_double), ("p1", C.c_double)]
 
 
+class TrxRegress(C.Structure):
+    _fields_ = [("nvec", C.c_int32), ("nfit", C.c_int32), ("niter", C.c_int32), ("inject", C.c_int32),
+                ("p0", C.c_double), ("p1", C.c_double), ("vectors", c_double_p)]
+
+
 SCATTER_NONE, SCATTER_VARIANCE, SCATTER_MASK = 0, 1, 2      # TRX_SCATTER_*: the kinds of trx_weigh_observed
 
 
@@ -400,6 +405,15 @@ def bind_pca_api(lib):
                                      C.POINTER(TrxPca), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, i64p, i64p,
                                      C.POINTER(TrxDebug)]
     lib.trx_pca_observed.restype = C.c_int
+    return lib
+
+
+def bind_regress_api(lib):
+    """argtypes/restypes of the regression entry point (trx_regress_observed)."""
+    i64p = C.POINTER(C.c_int64)
+    lib.trx_regress_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
+                                         C.POINTER(TrxRegress), c_double_p, c_double_p, c_double_p, i64p, i64p, C.POINTER(TrxDebug)]
+    lib.trx_regress_observed.restype = C.c_int
     return lib
 
 

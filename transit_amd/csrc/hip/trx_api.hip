@@ -51,6 +51,7 @@
 #include "trx_wfilter.hip.h"
 #include "trx_sysrem.hip.h"
 #include "trx_pca.hip.h"
+#include "trx_regress.hip.h"
 #include "trx_scatter.hip.h"
 #include "trx_normalise.hip.h"
 #include "trx_highpass.hip.h"
@@ -69,6 +70,7 @@
 #include "../trx_wfilter.h"
 #include "../trx_sysrem.h"
 #include "../trx_pca.h"
+#include "../trx_regress.h"
 #include "../trx_scatter.h"
 #include "../trx_normalise.h"
 #include "../trx_launch.h"

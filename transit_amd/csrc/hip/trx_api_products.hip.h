@@ -946,18 +946,20 @@ int trx_run_exposed_map(trx_handle *h, const trx_atm *a, const trx_opts *o, doub
 }
 
 // ---- detrending the observed set itself: model injection and SYSREM (trx_sysrem.hip.h) --------------
-// the SYSREM kernels of dt over the residuals in h->d_sr_r, on the main queue: X the call's extents, ntiles the tiles in h->d_sr_tiles
-static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend *dt, const SysremExtents &X, int64_t ntiles)
+// the SYSREM kernels of dt over the residuals in h->d_sr_r, on the main queue: X the call's extents, ntiles the tiles in h->d_sr_tiles;
+// coef_first: the row of h->d_sr_coef the first component's column vector goes to (trx_regress_observed: behind the given vectors')
+static int launch_sysrem(trx_handle *h, const ObservedSet *O, const trx_detrend *dt, const SysremExtents &X, int64_t ntiles, int32_t coef_first = 0)
 {
+  const size_t coef_at = sizeof(double) * (size_t)coef_first * (size_t)O->npix;
   SysremArgs A{};
   A.r = h->d_sr_r.as<double>(); A.weight = O->d_weight.raw().as<double>(); A.tiles = h->d_sr_tiles.as<FilterTile>(); A.seg_first = O->d_seg.as<int64_t>();
-  A.a = h->d_sr_a.as<double>(); A.c = h->d_sr_c.as<double>(); A.coef = h->d_sr_coef.as<double>(); A.basis = h->d_sr_basis.as<double>();
+  A.a = h->d_sr_a.as<double>(); A.c = h->d_sr_c.as<double>(); A.coef = h->d_sr_coef.p ? h->d_sr_coef.as<double>() + (size_t)coef_first * (size_t)O->npix : nullptr; A.basis = h->d_sr_basis.as<double>();
   A.npix = O->npix; A.ntiles = ntiles; A.nrows = X.rows; A.nexp = O->nexp; A.nseg = O->nseg; A.ncomp = dt->ncomp;
   // (every address the kernels read or write: the residuals and the weights [nexp][npix], the tiles -- which cover [0, npix) --,
   // the bounds [nseg + 1], a [nseg][nexp], c [npix], coef [ncomp][npix], U [nseg][nexp][ncomp])
-  if (!A.r || !A.tiles || !A.a || !A.c || !A.coef || !A.basis || !observed_set_whole(*O, O->d_weight.raw(), false) || ntiles < 1 ||
+  if (!A.r || !A.tiles || !A.a || !A.c || !A.coef || !A.basis || !observed_set_whole(*O, O->d_weight.raw(), false) || ntiles < 1 || coef_first < 0 ||
       h->d_sr_r.bytes < X.r_bytes || (A.weight && O->d_weight.raw().bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles ||
-      h->d_sr_a.bytes < X.a_bytes || h->d_sr_c.bytes < X.c_bytes || h->d_sr_coef.bytes < X.coef_bytes || h->d_sr_basis.bytes < X.basis_bytes ||
+      h->d_sr_a.bytes < X.a_bytes || h->d_sr_c.bytes < X.c_bytes || h->d_sr_coef.bytes < coef_at + X.coef_bytes || h->d_sr_basis.bytes < X.basis_bytes ||
       !grid_ok(X.tile_blocks) || !grid_ok(X.row_blocks))
     return fail(h, TRX_E_HIP, "internal: incomplete arguments for the SYSREM kernels (not launched)");
   // (an empty segment has no tile: its vectors stay zero)
@@ -1042,15 +1044,18 @@ static int detrend_fill(trx_handle *h, const char *who, const ObservedSet *O, bo
 
 // step 3 of a detrending call (who), every kernel finished and U [nseg][nexp][ncomp] in h->sr_basis: the weighted filter of U
 // as trx_set_weighted_filter makes it -- it reads the set's weights as trx_set_observed installed them, not its data --, the
-// outputs, and only then the swap, which puts those weights back in force
+// outputs, and only then the swap, which puts those weights back in force.  made: that filter where the call has made it
+// already, with made_nsingular its count (trx_regress_observed without fitted components: the factor its fit ran from)
 static int detrend_install(trx_handle *h, const char *who, ObservedSet *O, int32_t ncomp, size_t basis_bytes, size_t coef_bytes, size_t r_bytes,
-                           double *basis, double *coef, double *data, int64_t *nsingular)
+                           double *basis, double *coef, double *data, int64_t *nsingular, std::unique_ptr<FilterSet> *made = nullptr,
+                           int64_t made_nsingular = 0)
 {
   std::string msg; int rc;
   if ((rc = sysrem_basis_check(h->sr_basis.data(), O->nseg, O->nexp, ncomp, msg, who))) return fail(h, rc, msg);
   const trx_wfilter wf{ncomp, 0, h->sr_basis.data()};
-  std::unique_ptr<FilterSet> S; int64_t nsing = 0;
-  if ((rc = make_wfilter_set(h, &wf, S, &nsing, &O->d_weight.raw()))) return rc;
+  std::unique_ptr<FilterSet> S; int64_t nsing = made_nsingular;
+  if (made) S = std::move(*made);
+  else if ((rc = make_wfilter_set(h, &wf, S, &nsing, &O->d_weight.raw()))) return rc;
   if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, coef_bytes, hipMemcpyDeviceToHost));
   if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, r_bytes, hipMemcpyDeviceToHost));
   if (basis) std::memcpy(basis, h->sr_basis.data(), basis_bytes);
@@ -1185,6 +1190,87 @@ int trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double 
   if (offdiag) HIPCHK(h, hipMemcpy(offdiag, h->d_pc_off.p, X.offdiag_bytes, hipMemcpyDeviceToHost));
   if (nwhole) HIPCHK(h, hipMemcpy(nwhole, h->d_pc_nwhole.p, X.nwhole_bytes, hipMemcpyDeviceToHost));
   return detrend_install(h, who, O, pc->ncomp, X.basis_bytes, X.coef_bytes, X.r_bytes, basis, coef, data, nsingular);
+}
+
+// ---- regressing the observed set on given time vectors (trx_regress.hip.h) ----------------------------
+// step 2b of the call, on the main queue behind steps 0, 1 and 1b: every column of f0 in h->d_sr_r fitted with the vectors
+// and the factor of F -- the weighted filter of the given vectors against the set's weights as installed --, in place;
+// the coefficients into the first F.ncomp rows of h->d_sr_coef.  X the call's extents, ntiles the tiles in h->d_sr_tiles
+static int launch_regress(trx_handle *h, const ObservedSet *O, const FilterSet &F, const RegressExtents &X, int64_t ntiles)
+{
+  const DevBuf &W = O->d_weight.raw();
+  const WfilterExtents WX = wfilter_extents(F.npix, F.nexp, F.nseg, F.ncomp, F.npad, F.ntiles, kFiltWaves);
+  RegressArgs A{};
+  A.r = h->d_sr_r.as<double>(); A.weight = W.as<double>(); A.basis = F.d_back.as<double>(); A.fac = F.d_fac.as<double>(); A.live = F.d_live.as<int32_t>();
+  A.tiles = h->d_sr_tiles.as<FilterTile>(); A.coef = h->d_sr_coef.as<double>();
+  A.npix = O->npix; A.ntiles = ntiles; A.nexp = O->nexp; A.nvec = F.ncomp;
+  // (every address the kernel reads or writes: the data and the weights [nexp][npix], the tiles -- which cover [0, npix) and
+  // name segments below nseg --, the padded vectors [nseg][nexp][npad], the factor [nfac][npix] and the flags [npix] -- made
+  // against W, the weights the kernel reads --, coef [nvec][npix] of the [nvec + nfit][npix] there are)
+  if (!A.r || !A.tiles || !A.coef || !A.fac || !A.live || !observed_set_whole(*O, W, false) || !wfilter_basis_whole(F, *O, WX) || ntiles < 1 ||
+      F.ncomp < 1 || F.ncomp > X.ncomp || X.ncomp > TRX_FILTER_MAX || h->d_sr_r.bytes < X.r_bytes || X.r_bytes < sizeof(double) * (size_t)O->nexp * (size_t)O->npix ||
+      (A.weight && W.bytes < X.r_bytes) || h->d_sr_tiles.bytes < sizeof(FilterTile) * (size_t)ntiles || F.d_fac.bytes < WX.fac_bytes || F.d_live.bytes < WX.live_bytes ||
+      X.coef_fit_bytes != sizeof(double) * (size_t)F.ncomp * (size_t)O->npix || h->d_sr_coef.bytes < X.coef_bytes || X.coef_bytes < X.coef_fit_bytes ||
+      X.tile_blocks * kFiltWaves < ntiles || !X.grid_ok)
+    return fail(h, TRX_E_HIP, "internal: incomplete arguments for the regression kernel (not launched)");
+  LAUNCH_NPAD(k_regress_cols, F.npad, dim3((unsigned)X.tile_blocks), dim3(64 * kFiltWaves), h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  return TRX_OK;
+}
+
+int trx_regress_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double *spectrum, int32_t nshift, const double *shift, const trx_regress *rg,
+                         double *basis, double *coef, double *data, int64_t *nsingular_fit, int64_t *nsingular, trx_debug *dbg)
+{
+  if (!h) return TRX_E_ARG;
+  const char *const who = "trx_regress_observed";
+  const ProductState P = product_state(h);
+  std::string msg;
+  if (const int rc = regress_checks(P, rg, a, o, nshift, shift, msg)) return fail(h, rc, msg);
+  ObservedSet *const O = h->observed.get();
+  HIPCHK(h, hipSetDevice(h->device));
+  if (regress_is_undo(rg)) {
+    if (nsingular_fit) *nsingular_fit = 0;
+    return detrend_undo(h, O, nsingular);
+  }
+  std::vector<FilterTile> tiles;
+  if (const int rc = sysrem_tiles(P, tiles, msg, who)) return fail(h, rc, msg);
+  const int64_t ntiles = (int64_t)tiles.size();
+  const int32_t nvec = rg->nvec, nfit = rg->nfit;
+  const RegressExtents X = regress_extents(O->npix, O->nexp, O->nseg, nvec, nfit, ntiles, kFiltWaves);
+  // (the fitted components' own extents; those of steps 0 and 1 are the detrend's whatever nfit is)
+  const SysremExtents SX = sysrem_extents(O->npix, O->nexp, O->nseg, nfit, nfit > 0 ? rg->niter : 0, ntiles, kPixBlock, kFiltWaves, kMomWaves);
+  std::vector<double> fit;
+  try {
+    h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0);
+    fit.assign(SX.basis_bytes / sizeof(double), 0.0);
+  } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
+  int rc;
+  // steps 0, 1 and 1b, as trx_detrend_observed's
+  if ((rc = detrend_fill(h, who, O, rg->inject != 0, rg->p0, rg->p1, a, o, spectrum, nshift, shift, dbg, SX.cells, SX.r_bytes, SX.c_bytes, SX.elem_blocks)))
+    return rc;
+  // step 2a: the weighted filter of the given vectors against W -- its factor is the fit's (factor_wfilter waits for the queue)
+  const trx_wfilter wf{nvec, 0, rg->vectors};
+  std::unique_ptr<FilterSet> S; int64_t nsing_fit = 0;
+  if ((rc = make_wfilter_set(h, &wf, S, &nsing_fit, &O->d_weight.raw()))) return rc;
+  if (!S) return fail(h, TRX_E_HIP, "internal: the given vectors' filter was not made");
+  // step 2b
+  if ((rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = upload(h, h->d_sr_tiles, tiles)) || (rc = launch_regress(h, O, *S, X, ntiles))) return rc;
+  // step 2c: SYSREM on what is left
+  if (nfit > 0) {
+    const trx_detrend dt{nfit, rg->niter, 0, 0, 0.0, 0.0};
+    if ((rc = ensure(h, h->d_sr_a, SX.a_bytes)) || (rc = ensure(h, h->d_sr_c, SX.c_bytes)) || (rc = ensure(h, h->d_sr_basis, SX.basis_bytes)) ||
+        (rc = launch_sysrem(h, O, &dt, SX, ntiles, nvec)))
+      return rc;
+    HIPCHK(h, hipMemcpyAsync(fit.data(), h->d_sr_basis.p, SX.basis_bytes, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished; the tiles' staging vector may go)
+  regress_merge(rg->vectors, fit.data(), O->nseg, O->nexp, nvec, nfit, h->sr_basis.data());
+  // step 3: without fitted components the filter of step 2a is the one to install
+  int64_t nsing = 0;
+  if ((rc = detrend_install(h, who, O, X.ncomp, X.basis_bytes, X.coef_bytes, X.r_bytes, basis, coef, data, &nsing, nfit == 0 ? &S : nullptr, nsing_fit))) return rc;
+  if (nsingular_fit) *nsingular_fit = nsing_fit;
+  if (nsingular) *nsingular = nsing;
+  return TRX_OK;
 }
 
 // ---- normalising the observed set: the recipe of step 1b and the detrend of zero components (trx_normalise.hip.h) ----

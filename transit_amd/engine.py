@@ -215,6 +215,7 @@ def hip_library():
         _abi.bind_expmap_api(lib)
         _abi.bind_sysrem_api(lib)
         _abi.bind_pca_api(lib)
+        _abi.bind_regress_api(lib)
         _abi.bind_scatter_api(lib)
         _abi.bind_hpdata_api(lib)
         _abi.bind_normalise_api(lib)
@@ -247,11 +248,13 @@ class Detrended:
     columns the installed weighted filter's pivot rule makes dead, spectrum the injection run's spectrum (None without).
     Engine.pca_observed returns one with three more: eigen [nseg, ncomp] the components' eigenvalues of the Gram matrix,
     offdiag [nseg] the largest off-diagonal entry the sweeps left, nwhole [nseg] the columns that took part in the fit
-    (None from detrend_observed, after the undo and with outputs=False)."""
+    (None from detrend_observed, after the undo and with outputs=False).  Engine.regress_observed returns one with
+    nsingular_fit, the columns whose fit of the given vectors had a singular pivot (None from the other two calls); its basis
+    [nseg, nexp, nvec + nfit] holds the given vectors ahead of the fitted ones, its coef [nvec + nfit, npix] likewise."""
 
-    def __init__(self, basis, coef, data, nsingular, spectrum=None, eigen=None, offdiag=None, nwhole=None):
+    def __init__(self, basis, coef, data, nsingular, spectrum=None, eigen=None, offdiag=None, nwhole=None, nsingular_fit=None):
         self.basis, self.coef, self.data, self.nsingular, self.spectrum = basis, coef, data, nsingular, spectrum
-        self.eigen, self.offdiag, self.nwhole = eigen, offdiag, nwhole
+        self.eigen, self.offdiag, self.nwhole, self.nsingular_fit = eigen, offdiag, nwhole, nsingular_fit
 
 
 class Weighed:
@@ -579,6 +582,44 @@ class Engine(CEngine):
         if not n:
             return Detrended(None, None, None, int(nsing.value), spec)
         return Detrended(basis, coef, data, int(nsing.value), spec, eigen, offdiag, nwhole)
+
+    def regress_observed(self, vectors, nfit: int = 0, niter: int = 10, inject=None, outputs: bool = True) -> "Detrended":
+        """trx_regress_observed: detrend_observed with a weighted least-squares fit of GIVEN time vectors in SYSREM's place,
+        on the device, always from the RAW data of set_observed -- every pixel column regressed on its segment's vectors
+        under its own weights (xcor.regress_reference, bit for bit), then nfit SYSREM components of niter alternations on
+        what is left (xcor.sysrem_reference of those residuals).  vectors: [nseg, nexp, nvec], or [nexp, nvec] for all
+        segments (xcor.time_basis of the airmass, the basis of an earlier detrend_observed, ...); None or nvec = 0 is the
+        undo.  inject, the outcome and outputs=False are detrend_observed's; any of the detrending calls undoes any other.
+        The residuals become the observed data and the weighted filter of the merged basis the filter -- with nfit = 0 by
+        the very factor the fit used.  Returns a Detrended with nsingular_fit beside basis [nseg, nexp, nvec + nfit], coef
+        [nvec + nfit, npix], data, nsingular and spectrum."""
+        nexp, nseg = getattr(self, "mom_shape", (0, 0))
+        npix = getattr(self, "npix", 0)
+        vec = None
+        if vectors is not None:
+            vec = np.asarray(vectors, dtype=np.float64)
+            if vec.ndim == 2:
+                vec = np.broadcast_to(vec[None, :, :], (nseg,) + vec.shape)
+            if vec.ndim != 3 or (vec.shape[2] and vec.shape[:2] != (nseg, nexp)):
+                raise ValueError("Engine.regress_observed: vectors of shape [nseg][nexp][nvec] or [nexp][nvec]")
+            vec = np.ascontiguousarray(vec)
+        nvec = int(vec.shape[2]) if vec is not None else 0
+        rg = _abi.TrxRegress(nvec, int(nfit), int(niter), 0 if inject is None else 1, 0.0, 0.0, _dp(vec) if nvec else None)
+        atm = opts = sh = spec = None
+        if inject is not None:
+            atm, opts, shifts, rg.p0, rg.p1 = inject
+            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+            spec = np.zeros(self.nwn)
+        n = nvec + max(int(nfit), 0) if outputs and nvec else 0
+        basis, coef, data = np.zeros((nseg, nexp, n)), np.zeros((n, npix)), np.zeros((nexp, npix))
+        nfs, nsing = C.c_int64(0), C.c_int64(0)
+        rc = self._lib.trx_regress_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
+                                            _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), C.byref(rg),
+                                            _dp(basis) if n else None, _dp(coef) if n else None, _dp(data) if n else None,
+                                            C.byref(nfs), C.byref(nsing), None)
+        if rc != 0:
+            raise EngineError(rc, "trx_regress_observed", self._last_error())
+        return Detrended(basis if n else None, coef if n else None, data if n else None, int(nsing.value), spec, nsingular_fit=int(nfs.value))
 
     def weigh_observed(self, kind: int, clip: float = 0.0, min_live: int = 2, outputs: bool = True) -> "Weighed":
         """trx_weigh_observed: the column-scatter weights of the observed set, on the device, from the data installed (the

@@ -80,6 +80,13 @@ Gram matrix of each segment's whole columns, its eigenvectors by a fixed number 
     jacobi_rounds(nexp)                                  the rounds of one sweep: lists of disjoint pairs (p, q), p < q < nexp
     pca_reference(data, weight, seg_first, ncomp, nsweep)        (basis, coef, resid, eigen, offdiag, nwhole): the mirror
 
+The same call with a regression on GIVEN time vectors in SYSREM's place (Engine.regress_observed; trx_regress_observed):
+every pixel column fitted by weighted least squares with its segment's vectors -- the weighted filter's projector applied
+to the data --, then optionally a few SYSREM components on the residuals.
+
+    regress_reference(f0, weight, seg_first, vectors)    (coef, resid, nsingular): the mirror; a singular column keeps f0
+    time_basis(x, degree)                                [nexp, degree + 1]: the powers of the centred, scaled x (the airmass)
+
 Normalising the observed set ahead of either (Engine.set_normalise / Engine.normalise_observed; trx_set_normalise /
 trx_normalise_observed): step 1b of the detrending calls, between the injection and the fit.  Every (exposure, segment) row
 is divided by a quantile of its live data, every column by (or less) its mean in time, single entries are clipped.
@@ -1139,12 +1146,14 @@ def _wf_factor(obs: Observed, wf: WeightedFilter, dtype):
     return L, D, np.stack([N[j, j] for j in range(n)]) if n else np.zeros((0, npix), dtype=dtype)
 
 
-def _wf_apply(g, obs: Observed, wf: WeightedFilter, L, D, dtype):
-    """g' [nexp, npix] in `dtype` from g: the definition's run step, vectorised over the columns"""
+def _wf_fit(g, obs: Observed, wf: WeightedFilter, L, D, dtype, live=None):
+    """(c [n, npix], g' [nexp, npix]) in `dtype` from g: the definition's run step, vectorised over the columns -- the
+    coefficients of every column's solve and g less their combination of the vectors.  live [npix] (trx_regress_observed):
+    a column where it is False gets the coefficients +0, its solve's result unused"""
     n = wf.ncomp
     w = (obs.weight if obs.weight is not None else np.ones_like(obs.data)).astype(dtype)
     g = g.astype(dtype)
-    out = np.zeros(g.shape, dtype=dtype)
+    out, coef = np.zeros(g.shape, dtype=dtype), np.zeros((n, g.shape[1]), dtype=dtype)
     with np.errstate(all="ignore"):
         for s in range(obs.nseg):
             k = slice(int(obs.seg_first[s]), int(obs.seg_first[s + 1]))
@@ -1168,12 +1177,21 @@ def _wf_apply(g, obs: Observed, wf: WeightedFilter, L, D, dtype):
                 for i in range(j + 1, n):
                     t = t + L[i, j, k] * c[i]
                 c[j] = q[j] - t
+            for j in range(n):
+                if live is not None:
+                    c[j] = np.where(live[k], c[j], dtype(0.0))
+                coef[j, k] = c[j]
             for v in range(obs.nexp):
                 r = np.zeros(k.stop - k.start, dtype=dtype)
                 for j in range(n):
                     r = r + U[v, j] * c[j]
                 out[v, k] = g[v, k] - r
-    return out
+    return coef, out
+
+
+def _wf_apply(g, obs: Observed, wf: WeightedFilter, L, D, dtype):
+    """g' [nexp, npix] in `dtype` from g: the definition's run step, vectorised over the columns"""
+    return _wf_fit(g, obs, wf, L, D, dtype)[1]
 
 
 def weighted_pivots(obs: Observed, wf: WeightedFilter) -> np.ndarray:
@@ -1260,6 +1278,42 @@ def weighted_filter_exact(pairs, obs: Observed, wf: WeightedFilter) -> np.ndarra
     L, D, _ = _wf_factor(obs, wf, np.longdouble)
     out = _wf_apply(g, obs, wf, L, D, np.longdouble).astype(np.float64)
     return np.where(live[None, :], out, np.nan)
+
+
+def regress_reference(f0, weight, seg_first, vectors):
+    """(coef [nvec, npix], resid [nexp, npix], nsingular): every pixel column of f0 [nexp, npix] regressed on its segment's
+    time vectors ([nseg, nexp, nvec], or [nexp, nvec] for all segments) by weighted least squares under its own weights
+    (None: all 1), as trx_regress_observed defines it (include/transit_hip.h) -- the mirror of k_wfilter_factor and
+    k_regress_cols, bit for bit.  It is the weighted filter's install and run steps (_wf_factor, _wf_fit) with g = f0: a
+    column with a singular pivot gets the coefficients +0 and keeps f0; nsingular counts them."""
+    f0 = np.ascontiguousarray(f0, dtype=np.float64)
+    if f0.ndim != 2:
+        raise ValueError("regress_reference: f0 of shape [nexp][npix]")
+    seg = np.asarray(seg_first, dtype=np.int64).reshape(-1)
+    vec = np.asarray(vectors, dtype=np.float64)
+    if vec.ndim == 2:
+        vec = np.broadcast_to(vec[None, :, :], (seg.size - 1,) + vec.shape)
+    if vec.ndim != 3 or vec.shape[:2] != (seg.size - 1, f0.shape[0]) or not np.isfinite(vec).all():
+        raise ValueError("regress_reference: finite vectors of shape [nseg][nexp][nvec] or [nexp][nvec]")
+    obs, wf = Observed(seg, f0, weight), WeightedFilter(vec)
+    L, D, njj = _wf_factor(obs, wf, np.float64)
+    with np.errstate(all="ignore"):
+        live = np.all(D > _abi.WFILTER_PIVOT * njj, axis=0) if wf.ncomp else np.ones(obs.npix, dtype=bool)
+    coef, resid = _wf_fit(f0, obs, wf, L, D, np.float64, live)
+    return coef, resid, int(np.count_nonzero(~live))
+
+
+def time_basis(x, degree: int) -> np.ndarray:
+    """[nexp, degree + 1]: the powers 0 .. degree of t = (x - mean(x)) / max|x - mean(x)| -- of the airmass of every
+    exposure, say --, a well-conditioned set of vectors for regress_reference and Engine.regress_observed (a constant x
+    gives t = 0).  A convenience: the call takes any finite vectors."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    if degree < 0 or not np.isfinite(x).all():
+        raise ValueError("time_basis: finite x and degree >= 0")
+    d = x - np.mean(x)
+    span = np.max(np.abs(d)) if d.size else 0.0
+    t = d / span if span > 0 else np.zeros_like(d)
+    return np.stack([t ** k for k in range(degree + 1)], axis=1)
 
 
 def filtered_map_reference(pairs_at_lags, obs: Observed, filt, vm: VelocityMap) -> np.ndarray:
