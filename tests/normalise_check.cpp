@@ -189,20 +189,6 @@ static double row_scale(const trx_normalise &nm, const double *f, const double *
   return norm_scale(nm.row_kind, x, m);
 }
 
-// one column's pass over the exposures, the way norm_column_pass takes it (PASS 0: n and the sum of f1; 1: the sum of f2; 2: the squares)
-static void column_pass(int pass, const trx_normalise &nm, const double *r, const double *weight, const double *scale, int64_t npix, int nexp, int nseg,
-                        int64_t p, double c, double mean, int32_t &n, double &acc)
-{
-  for (int v = 0; v < nexp; v++) {
-    const int64_t at = (int64_t)v * npix + p;
-    const double w = weight ? weight[at] : 1.0, sc = scale[(int64_t)v * nseg];
-    const bool on = norm_on(w, sc);
-    if (pass == 0) norm_sum_term(on, on ? norm_row(nm.row_kind, r[at], sc) : 0.0, n, acc);
-    else if (pass == 1) { int32_t unused = 0; norm_sum_term(on, on ? norm_entry(nm.row_kind, nm.col_kind, r[at], sc, c) : 0.0, unused, acc); }
-    else norm_square_term(on, on ? norm_entry(nm.row_kind, nm.col_kind, r[at], sc, c) : 0.0, mean, acc);
-  }
-}
-
 // k_norm_rowscale and k_norm_cols over every row, tile and lane; data [nexp][npix], weight the same or null.  cap: the staging
 // capacity (kNormCap on the device; smaller here makes a short segment take the path that reads again)
 static SetResult run_set(const ProductState &S, const trx_normalise &nm, const double *data, const double *weight, int cap = kNormCap)
@@ -234,34 +220,8 @@ static SetResult run_set(const ProductState &S, const trx_normalise &nm, const d
         if (lane >= T.count) continue;
         const int64_t p = T.first + lane;
         const double *const scale = R.scale.get() + T.seg;
-        int32_t n = 0, unused = 0; double s = 0.0;
-        column_pass(0, nm, R.data.get(), weight, scale, npix, nexp, nseg, p, 0.0, 0.0, n, s);
-        bool good;
-        const double c = norm_centre(nm.col_kind, s, n, good);
-        const bool clips = norm_clips(nm.clip, n, good);
-        double mean = 0.0, lim = 0.0;
-        if (clips) {
-          double s2 = 0.0, q = 0.0;
-          column_pass(1, nm, R.data.get(), weight, scale, npix, nexp, nseg, p, c, 0.0, unused, s2);
-          mean = norm_mean(s2, n);
-          column_pass(2, nm, R.data.get(), weight, scale, npix, nexp, nseg, p, c, mean, unused, q);
-          lim = norm_limit(nm.clip, q, n);
-        }
-        int32_t nclip = 0, nbad = 0;
-        for (int v = 0; v < nexp; v++) {
-          const int64_t at = (int64_t)v * npix + p;
-          const double w = weight ? weight[at] : 1.0, sc = scale[(int64_t)v * nseg];
-          const bool on = norm_on(w, sc) && good;
-          double out = 0.0;
-          if (on) {
-            out = norm_entry(nm.row_kind, nm.col_kind, R.data[(size_t)at], sc, c);
-            if (clips && norm_clipped(out, mean, lim)) { out = mean; nclip++; }
-          } else if (w > 0.0) nbad++;
-          R.data[(size_t)at] = out;
-        }
-        R.centre[(size_t)p] = c;
-        count[(size_t)p] = nclip;
-        count[(size_t)(npix + p)] = nbad;
+        if (weight) norm_column<true>(R.data.get(), weight, scale, p, npix, nseg, nexp, nm.row_kind, nm.col_kind, nm.clip, R.centre[(size_t)p], count[(size_t)p], count[(size_t)(npix + p)]);
+        else norm_column<false>(R.data.get(), nullptr, scale, p, npix, nseg, nexp, nm.row_kind, nm.col_kind, nm.clip, R.centre[(size_t)p], count[(size_t)p], count[(size_t)(npix + p)]);
       }
     }
   for (int64_t p = 0; p < npix; p++) { R.nclipped += count[(size_t)p]; R.nbad += count[(size_t)(npix + p)]; }

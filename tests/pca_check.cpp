@@ -193,13 +193,7 @@ static SetResult run_set(const ProductState &S, int ncomp, int nsweep, const dou
   for (const FilterTile &T : tiles)
     for (int lane = 0; lane < T.count; lane++) {
       const int64_t p = T.first + lane;
-      bool any = false, all = true;
-      for (int v = 0; v < nexp; v++) {
-        if (!live[(size_t)((int64_t)T.seg * nexp + v)]) continue;
-        any = true;
-        if (weight && !(weight[(int64_t)v * npix + p] > 0.0)) all = false;
-      }
-      whole[(size_t)p] = any && all ? 1 : 0;
+      whole[(size_t)p] = pca_whole_column(live.get() + (int64_t)T.seg * nexp, weight ? weight + p : nullptr, weight != nullptr, npix, nexp) ? 1 : 0;
     }
   // k_pca_gram: one wave per tile of 4 x 4 entries, the lanes' sums through the butterfly
   const int nb = pca_gram_blocks(nexp), per = pca_gram_tiles(nexp);
@@ -288,21 +282,7 @@ static SetResult run_set(const ProductState &S, int ncomp, int nsweep, const dou
   for (const FilterTile &T : tiles)
     for (int lane = 0; lane < T.count; lane++) {
       const int64_t p = T.first + lane;
-      const double *const U = R.U.get() + (int64_t)T.seg * nexp * ncomp;
-      double c[TRX_FILTER_MAX];
-      for (int i = 0; i < TRX_FILTER_MAX; i++) c[i] = 0.0;
-      for (int v = 0; v < nexp; v++) {
-        const int64_t at = (int64_t)v * npix + p;
-        const double y = !weight || weight[at] > 0.0 ? r[at] : 0.0;
-        for (int i = 0; i < ncomp; i++) pca_coef_term(U[(int64_t)v * ncomp + i], y, c[i]);
-      }
-      for (int i = 0; i < ncomp; i++) R.coef[(size_t)((int64_t)i * npix + p)] = c[i];
-      for (int v = 0; v < nexp; v++) {
-        const int64_t at = (int64_t)v * npix + p;
-        double x = r[at];
-        for (int i = 0; i < ncomp; i++) x = sysrem_subtract(x, U[(int64_t)v * ncomp + i], c[i]);
-        r[at] = x;
-      }
+      pca_project_column(r + p, weight ? weight + p : nullptr, weight != nullptr, R.U.get() + (int64_t)T.seg * nexp * ncomp, R.coef.get() + p, npix, nexp, ncomp);
     }
   return R;
 }

@@ -165,14 +165,7 @@ static SetResult run_set(const ProductState &S, int nvec, const double *vec, con
         const int64_t p = T.first + lane;
         const double *const Us = U.get() + (int64_t)T.seg * nexp * NC;
         // the factor kernel: row after row of the normal matrix and of the factor
-        bool good = true;
-        for (int j = 0; j < nvec; j++) {
-          double Nrow[NC];
-          for (int k = 0; k < NC; k++) Nrow[k] = 0.0;
-          for (int v = 0; v < nexp; v++) wfilter_normal_term<NC>(Us + (int64_t)v * NC, weight ? weight[(int64_t)v * npix + p] : 1.0, j, Nrow);
-          good = wfilter_factor_row<NC>(j, Nrow, fac.get() + p, npix) && good;
-        }
-        live[(size_t)p] = good ? 1 : 0;
+        live[(size_t)p] = wfilter_factor_column<NC>(Us, weight ? weight + p : nullptr, weight != nullptr, fac.get() + p, npix, nexp, nvec) ? 1 : 0;
       }
     }
   // (the device has every factor before the first fit: two launches)
@@ -184,7 +177,7 @@ static SetResult run_set(const ProductState &S, int nvec, const double *vec, con
       for (int lane = 0; lane < 64; lane++) {
         if (lane >= T.count) continue;
         const int64_t p = T.first + lane;
-        regress_column<NC>(U.get() + (int64_t)T.seg * nexp * NC, weight ? weight + p : nullptr, R.data.get() + p, fac.get() + p, live[(size_t)p] != 0,
+        regress_column<NC>(U.get() + (int64_t)T.seg * nexp * NC, weight ? weight + p : nullptr, weight != nullptr, R.data.get() + p, fac.get() + p, live[(size_t)p] != 0,
                            R.coef.get() + p, npix, nexp, nvec);
       }
     }

@@ -131,13 +131,7 @@ static SetResult run_set(const ProductState &S, const trx_scatter &sc, const dou
     for (int lane = 0; lane < kScatBlock; lane++) {
       const int64_t p = blk * kScatBlock + lane;
       if (p >= npix) continue;
-      int32_t n = 0; double s = 0.0, q = 0.0;
-      for (int v = 0; v < nexp; v++) scatter_sum_term(weight ? weight[(int64_t)v * npix + p] : 1.0, data[(int64_t)v * npix + p], n, s);
-      if (scatter_enough(n, sc.min_live)) {
-        const double mean = scatter_mean(s, n);
-        for (int v = 0; v < nexp; v++) scatter_square_term(weight ? weight[(int64_t)v * npix + p] : 1.0, data[(int64_t)v * npix + p], mean, q);
-      }
-      R.var[(size_t)p] = scatter_variance(q, n, sc.min_live);
+      R.var[(size_t)p] = weight ? scatter_column<true>(data + p, weight + p, npix, nexp, sc.min_live) : scatter_column<false>(data + p, nullptr, npix, nexp, sc.min_live);
     }
   // the median kernel: one block per tile, the segment's variances staged `lds` at a time; the stores are counted: one per
   // segment with a live column, none elsewhere
@@ -184,12 +178,8 @@ static SetResult run_set(const ProductState &S, const trx_scatter &sc, const dou
     for (int lane = 0; lane < kScatBlock; lane++) {
       if (lane >= T.count) continue;
       const int64_t p = T.first + lane;
-      const double var = R.var[(size_t)p];
-      const bool keep = scatter_keep(var, R.med[(size_t)T.seg], sc.clip);
-      const double inv = scatter_inverse(var, keep);
-      R.flag[(size_t)p] = scatter_flag(var, keep);
-      for (int v = 0; v < nexp; v++)
-        R.w[(size_t)((int64_t)v * npix + p)] = scatter_weight(sc.kind, weight ? weight[(int64_t)v * npix + p] : 1.0, keep, inv);
+      scatter_weights_column(R.var[(size_t)p], R.med[(size_t)T.seg], sc.clip, sc.kind, weight ? weight + p : nullptr, weight != nullptr, R.w.get() + p,
+                             R.flag[(size_t)p], npix, nexp);
     }
   for (size_t p = 0; p < R.flag.n; p++) R.nmasked += R.flag[p] == kScatClipped ? 1 : 0;
   return R;

@@ -116,6 +116,9 @@ static void extents()
   SysremExtents X = sysrem_extents(800, 7, 8, 3, 10, 16, kElemBlock, kTileWaves, kRowWaves);
   CHECK(X.cells == 5600 && X.rows == 56 && X.elem_blocks == 22 && X.tile_blocks == 4 && X.row_blocks == 14 && X.launches == 66);
   CHECK(X.r_bytes == 8u * 5600 && X.a_bytes == 8u * 56 && X.c_bytes == 8u * 800 && X.coef_bytes == 8u * 3 * 800 && X.basis_bytes == 8u * 56 * 3);
+  // steps 0 and 1 alone: the same four numbers whatever the call fits
+  const FillExtents F = fill_extents(800, 7, kElemBlock);
+  CHECK(F.cells == X.cells && F.elem_blocks == X.elem_blocks && F.r_bytes == X.r_bytes && F.c_bytes == X.c_bytes);
   X = sysrem_extents(81920, 100, 40, 5, 10, 1280, kElemBlock, kTileWaves, kRowWaves);
   CHECK(X.cells == 8192000 && X.rows == 4000 && X.elem_blocks == 32000 && X.tile_blocks == 320 && X.row_blocks == 1000 && X.launches == 110);
   CHECK(X.r_bytes == (size_t)8 * 8192000 && X.coef_bytes == (size_t)8 * 5 * 81920 && X.basis_bytes == (size_t)8 * 4000 * 5);
@@ -146,6 +149,28 @@ static void extents()
   CHECK(ok);
 }
 
+// ---- the trip loop of trx_columns.h --------------------------------------------------------------------------
+// exposure_trips<K> over a heap array of exactly nexp doubles, nexp = 1 .. 2K + 1: load sees only exposures there are (the
+// array itself is read: a load outside it is a sanitizer report), use gets every exposure once, ascending, with what load
+// gave for that exposure; nothing at all for nexp = 0
+template <int K>
+static void trips()
+{
+  for (int nexp = 1; nexp <= 2 * K + 1; nexp++) {
+    Heap<double> col((size_t)nexp);
+    for (int v = 0; v < nexp; v++) col[(size_t)v] = 100.0 + v;
+    int loads = 0, uses = 0; bool inside = true, ordered = true, matched = true;
+    exposure_trips<K>(
+        nexp, [&](int v) { loads++; inside = inside && v >= 0 && v <= nexp - 1; return inside ? col.get()[v] : kNaN; },
+        [&](int v, double x) { ordered = ordered && v == uses; matched = matched && x == 100.0 + v; uses++; });
+    CHECK(inside && ordered && matched && uses == nexp && loads == (nexp + K - 1) / K * K);
+  }
+  int calls = 0;
+  exposure_trips<K>(0, [&](int) { calls++; return 0.0; }, [&](int, double) { calls++; });
+  exposure_trips<K>(-3, [&](int) { calls++; return 0.0; }, [&](int, double) { calls++; });
+  CHECK(calls == 0);
+}
+
 // ---- the whole set, the way the device walks it ---------------------------------------------------------
 struct SetResult { Heap<double> U, coef, r; };
 
@@ -171,9 +196,7 @@ static SetResult run_set(const ProductState &S, int ncomp, int niter, const doub
           if (lane >= T.count) continue;
           const int64_t p = T.first + lane;
           const double *const av = it ? a.get() + (int64_t)T.seg * nexp : nullptr;
-          double num = 0.0, den = 0.0;
-          for (int v = 0; v < nexp; v++) sysrem_col_term(weight ? weight[(int64_t)v * npix + p] : 1.0, r[(int64_t)v * npix + p], av ? av[v] : 1.0, num, den);
-          c[(size_t)p] = sysrem_ratio(num, den);
+          c[(size_t)p] = sysrem_column_step(r + p, weight ? weight + p : nullptr, weight != nullptr, av, npix, nexp);
         }
       launches++;
       // the row step: one wave per (v, s), lane sums over trips of 64 pixels, then the butterfly
@@ -212,9 +235,7 @@ static SetResult run_set(const ProductState &S, int ncomp, int niter, const doub
       for (int lane = 0; lane < 64; lane++) {
         if (lane >= T.count) continue;
         const int64_t p = T.first + lane;
-        const double *const U = R.U.get() + (int64_t)T.seg * nexp * ncomp + i;
-        const double cp = R.coef[(size_t)((int64_t)i * npix + p)];
-        for (int v = 0; v < nexp; v++) r[(int64_t)v * npix + p] = sysrem_subtract(r[(int64_t)v * npix + p], U[(int64_t)v * ncomp], cp);
+        sysrem_column_subtract(r + p, R.U.get() + (int64_t)T.seg * nexp * ncomp + i, ncomp, R.coef[(size_t)((int64_t)i * npix + p)], npix, nexp);
       }
     launches++;
   }
@@ -312,6 +333,9 @@ int main(int argc, char **argv)
   if (argc != 1) { std::fprintf(stderr, "usage: sysrem_check [set FILE]\n"); return 2; }
   refusals();
   extents();
+  trips<4>();
+  trips<8>();
+  CHECK(kSysTrips == 8 && kFiltTrips == 4);
   known();
   if (g_bad) { std::printf("FAILED %d of %d checks\n", g_bad, g_checks); return 1; }
   std::printf("ok %d\n", g_checks);

@@ -102,6 +102,21 @@ def test_every_recipe_corner_is_the_mirrors_bit_for_bit(case, which, nexp):
     E.close()
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nexp", [8, 9, 16, 17])
+def test_bits_about_a_whole_number_of_trips(case, nexp, weighted):
+    """the column kernel takes 8 exposures a trip (kSysTrips): one and two whole trips, and one exposure past each; a recipe
+    with a row quantile, a column mean and a clip takes every pass of it"""
+    nm = xcor.Normalise(Q, DIVIDE, 0.9, 3.0)
+    ob = case.observed(nexp, weighted)
+    E = case.handle(ob)
+    E.set_normalise(nm)
+    mirror = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm)
+    assert np.isfinite(mirror[0]).all()
+    check_normalised(E.normalise_observed(), mirror, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
+    E.close()
+
+
 # ---- 2. the detrending calls with a recipe installed -------------------------------------------------------------
 def nsingular_of(ob, basis):
     return int(np.count_nonzero(~xcor.weighted_factor(ob, xcor.WeightedFilter(basis))[2]))

@@ -109,6 +109,18 @@ def test_bits(case, nexp, weighted):
     E.close()
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nexp", [8, 9, 16, 17])
+def test_bits_about_a_whole_number_of_trips(case, nexp, weighted):
+    """the column kernels take 8 exposures a trip (kSysTrips): one and two whole trips, and one exposure past each"""
+    ob = case.observed(nexp, weighted)
+    E = case.handle(ob)
+    mirror = xcor.scatter_reference(ob.data, ob.weight, ob.seg_first, V, 3.0, 2)
+    assert np.isfinite(mirror[0]).all() and np.isfinite(mirror[3]).all()
+    check_outputs(E.weigh_observed(V, clip=3.0, min_live=2), mirror, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
+    E.close()
+
+
 # ---- 2. what is installed ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", cs.KINDS)
 def test_what_is_installed(case, kind):

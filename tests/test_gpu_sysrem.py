@@ -118,6 +118,16 @@ def test_bits_without_injection(case, nexp, ncomp, weighted):
     E.close()
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nexp", [8, 9, 16, 17])
+def test_bits_about_a_whole_number_of_trips(case, nexp, weighted):
+    """the column kernels take 8 exposures a trip (kSysTrips): one and two whole trips, and one exposure past each"""
+    ob = case.observed(nexp, weighted)
+    E = case.handle(ob)
+    check_outputs(E.detrend_observed(2, 2), case.mirror(nexp, weighted, 2, 2), ob, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
+    E.close()
+
+
 # ---- 2. bits with injection -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("setup", ["table", "pixels", "table and broadening"])
 def test_bits_with_injection(case, setup):

@@ -89,13 +89,7 @@ static void device_walk(const ProductState &S, const WfilterLayout &L, int ncomp
       if (lane >= T.count) continue;
       const int64_t p = T.first + lane;
       const double *const U = basis.get() + (int64_t)T.seg * nexp * NC;
-      bool good = true;
-      for (int j = 0; j < ncomp; j++) {
-        double Nrow[NC];
-        for (int k = 0; k < NC; k++) Nrow[k] = 0.0;
-        for (int v = 0; v < nexp; v++) wfilter_normal_term<NC>(U + (int64_t)v * NC, weight ? weight[(int64_t)v * npix + p] : 1.0, j, Nrow);
-        good = wfilter_factor_row<NC>(j, Nrow, fac + p, npix) && good;
-      }
+      const bool good = wfilter_factor_column<NC>(U, weight ? weight + p : nullptr, weight != nullptr, fac + p, npix, nexp, ncomp);
       live[p] = good ? 1 : 0;
       double y[NC];
       for (int j = 0; j < NC; j++) y[j] = 0.0;

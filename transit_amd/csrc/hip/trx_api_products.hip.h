@@ -1016,30 +1016,43 @@ static int launch_normalise(trx_handle *h, const char *who, const ObservedSet *O
 // steps 0, 1 and -- with a recipe installed (trx_set_normalise) -- 1b of a detrending call (who), on the main queue.
 // Steps 0 and 1: the raw data, or the injected data, into h->d_sr_r.  With an
 // injection the pairs come from the pixel stage alone, as trx_run_exposed (or, without a table, trx_run_pixels) runs it -- no
-// moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for.  cells, r_bytes, c_bytes and
-// elem_blocks: the call's extents.
-static int detrend_fill(trx_handle *h, const char *who, const ObservedSet *O, bool inject, double p0, double p1, const trx_atm *a, const trx_opts *o,
-                        double *spectrum, int32_t nshift, const double *shift, trx_debug *dbg, int64_t cells, size_t r_bytes, size_t c_bytes, int64_t elem_blocks)
+// moments, no high-pass, no filter; they are in h->d_pixout and the run has been waited for.
+// The caller's part of it: who it is, whether and how it injects, the run's arguments as it got them.
+struct FillCall {
+  const char *who; bool inject; double p0, p1;
+  const trx_atm *a; const trx_opts *o; double *spectrum; int32_t nshift; const double *shift; trx_debug *dbg;
+};
+static int detrend_fill(trx_handle *h, const ObservedSet *O, const FillCall &C)
 {
-  if (inject) {
-    PixelRun PR{h->pixels.get(), nshift}; PR.ex = h->exposures.get();
-    if (const int rc = pixel_run(h, who, a, o, spectrum, PR, shift, dbg)) return rc;
-    if (PR.ext.pairs != cells || h->d_pixout.bytes < PR.ext.pair_bytes) return fail(h, TRX_E_HIP, "internal: the injection's pairs are not the observed set's size");
+  const FillExtents X = fill_extents(O->npix, O->nexp, kPixBlock);
+  if (C.inject) {
+    PixelRun PR{h->pixels.get(), C.nshift}; PR.ex = h->exposures.get();
+    if (const int rc = pixel_run(h, C.who, C.a, C.o, C.spectrum, PR, C.shift, C.dbg)) return rc;
+    if (PR.ext.pairs != X.cells || h->d_pixout.bytes < PR.ext.pair_bytes) return fail(h, TRX_E_HIP, "internal: the injection's pairs are not the observed set's size");
   }
-  if (const int rc = ensure(h, h->d_sr_r, r_bytes)) return rc;
+  if (const int rc = ensure(h, h->d_sr_r, X.r_bytes)) return rc;
   const DevBuf &raw = O->d_data.raw();
-  if (!raw.p || raw.bytes < r_bytes) return fail(h, TRX_E_HIP, "internal: the observed set's data are not its size");
-  if (inject) {
+  if (!raw.p || raw.bytes < X.r_bytes) return fail(h, TRX_E_HIP, "internal: the observed set's data are not its size");
+  if (C.inject) {
     SysremInjectArgs IA{};
     IA.pairs = h->d_pixout.as<double2>(); IA.raw = raw.as<double>(); IA.gain = O->d_gain.as<double>(); IA.r = h->d_sr_r.as<double>();
-    IA.npix = O->npix; IA.cells = cells; IA.p0 = p0; IA.p1 = p1;
-    if ((IA.gain && O->d_gain.bytes < c_bytes) || !grid_ok(elem_blocks))
+    IA.npix = O->npix; IA.cells = X.cells; IA.p0 = C.p0; IA.p1 = C.p1;
+    if ((IA.gain && O->d_gain.bytes < X.c_bytes) || !grid_ok(X.elem_blocks))
       return fail(h, TRX_E_HIP, "internal: incomplete arguments for the injection kernel (not launched)");
-    hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
+    hipLaunchKernelGGL(k_sysrem_inject, dim3((unsigned)X.elem_blocks), dim3(kPixBlock), 0, h->stream, IA);
     HIPCHK(h, hipGetLastError());
-  } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, r_bytes, hipMemcpyDeviceToDevice, h->stream));
+  } else HIPCHK(h, hipMemcpyAsync(h->d_sr_r.p, raw.p, X.r_bytes, hipMemcpyDeviceToDevice, h->stream));
   // step 1b (without a recipe nothing is launched: the call's bits are what they were)
-  return h->norm_on ? launch_normalise(h, who, O) : TRX_OK;
+  return h->norm_on ? launch_normalise(h, C.who, O) : TRX_OK;
+}
+
+// The swap that ends a detrending call: the call's buffer in force as the data (a high-pass over them goes first, as in the
+// undo), the weights of trx_set_observed back, and S in the filter slot -- an empty S clears it.
+static void detrend_swap(trx_handle *h, ObservedSet *O, std::unique_ptr<FilterSet> &S)
+{
+  O->d_data.uncover(h->d_hp_r);
+  O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
+  install_filter_set(h, S);
 }
 
 // step 3 of a detrending call (who), every kernel finished and U [nseg][nexp][ncomp] in h->sr_basis: the weighted filter of U
@@ -1059,9 +1072,7 @@ static int detrend_install(trx_handle *h, const char *who, ObservedSet *O, int32
   if (coef) HIPCHK(h, hipMemcpy(coef, h->d_sr_coef.p, coef_bytes, hipMemcpyDeviceToHost));
   if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, r_bytes, hipMemcpyDeviceToHost));
   if (basis) std::memcpy(basis, h->sr_basis.data(), basis_bytes);
-  O->d_data.uncover(h->d_hp_r);                         // (as in the undo)
-  O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
-  install_filter_set(h, S);
+  detrend_swap(h, O, S);
   if (nsingular) *nsingular = nsing;
   return TRX_OK;
 }
@@ -1095,8 +1106,7 @@ int trx_detrend_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   try { h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
   int rc;
   // step 0 and 1: the raw data, or the injected data, into the call's own buffer
-  if ((rc = detrend_fill(h, who, O, dt->inject != 0, dt->p0, dt->p1, a, o, spectrum, nshift, shift, dbg, X.cells, X.r_bytes, X.c_bytes, X.elem_blocks)))
-    return rc;
+  if ((rc = detrend_fill(h, O, FillCall{who, dt->inject != 0, dt->p0, dt->p1, a, o, spectrum, nshift, shift, dbg}))) return rc;
   if ((rc = ensure(h, h->d_sr_a, X.a_bytes)) || (rc = ensure(h, h->d_sr_c, X.c_bytes)) ||
       (rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = ensure(h, h->d_sr_basis, X.basis_bytes)) || (rc = upload(h, h->d_sr_tiles, tiles)))
     return rc;
@@ -1173,8 +1183,7 @@ int trx_pca_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, double 
   try { h->sr_basis.assign(X.basis_bytes / sizeof(double), 0.0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
   int rc;
   // step 0 and 1, as trx_detrend_observed's
-  if ((rc = detrend_fill(h, who, O, pc->inject != 0, pc->p0, pc->p1, a, o, spectrum, nshift, shift, dbg, X.cells, X.r_bytes, X.c_bytes, X.elem_blocks)))
-    return rc;
+  if ((rc = detrend_fill(h, O, FillCall{who, pc->inject != 0, pc->p0, pc->p1, a, o, spectrum, nshift, shift, dbg}))) return rc;
   if ((rc = ensure(h, h->d_pc_live, X.live_bytes)) || (rc = ensure(h, h->d_pc_whole, X.whole_bytes)) || (rc = ensure(h, h->d_pc_g, X.g_bytes)) ||
       (rc = ensure(h, h->d_pc_v, X.g_bytes)) || (rc = ensure(h, h->d_sr_coef, X.coef_bytes)) || (rc = ensure(h, h->d_sr_basis, X.basis_bytes)) ||
       (rc = ensure(h, h->d_pc_eigen, X.eigen_bytes)) || (rc = ensure(h, h->d_pc_off, X.offdiag_bytes)) || (rc = ensure(h, h->d_pc_nwhole, X.nwhole_bytes)) ||
@@ -1237,7 +1246,7 @@ int trx_regress_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   const int64_t ntiles = (int64_t)tiles.size();
   const int32_t nvec = rg->nvec, nfit = rg->nfit;
   const RegressExtents X = regress_extents(O->npix, O->nexp, O->nseg, nvec, nfit, ntiles, kFiltWaves);
-  // (the fitted components' own extents; those of steps 0 and 1 are the detrend's whatever nfit is)
+  // (the fitted components' own extents: none of them is used where nfit = 0)
   const SysremExtents SX = sysrem_extents(O->npix, O->nexp, O->nseg, nfit, nfit > 0 ? rg->niter : 0, ntiles, kPixBlock, kFiltWaves, kMomWaves);
   std::vector<double> fit;
   try {
@@ -1246,8 +1255,7 @@ int trx_regress_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, dou
   } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
   int rc;
   // steps 0, 1 and 1b, as trx_detrend_observed's
-  if ((rc = detrend_fill(h, who, O, rg->inject != 0, rg->p0, rg->p1, a, o, spectrum, nshift, shift, dbg, SX.cells, SX.r_bytes, SX.c_bytes, SX.elem_blocks)))
-    return rc;
+  if ((rc = detrend_fill(h, O, FillCall{who, rg->inject != 0, rg->p0, rg->p1, a, o, spectrum, nshift, shift, dbg}))) return rc;
   // step 2a: the weighted filter of the given vectors against W -- its factor is the fit's (factor_wfilter waits for the queue)
   const trx_wfilter wf{nvec, 0, rg->vectors};
   std::unique_ptr<FilterSet> S; int64_t nsing_fit = 0;
@@ -1296,22 +1304,19 @@ int trx_normalise_observed(trx_handle *h, const trx_atm *a, const trx_opts *o, d
   if (const int rc = normalise_checks(P, h->norm_on, inject, p0, p1, a, o, nshift, shift, msg)) return fail(h, rc, msg);
   ObservedSet *const O = h->observed.get();
   HIPCHK(h, hipSetDevice(h->device));
-  // (the extents steps 0 and 1 take are the detrend's; the fit's own, of one component here, are not used)
-  const SysremExtents X = sysrem_extents(O->npix, O->nexp, O->nseg, 1, 1, 1, kPixBlock, kFiltWaves, kMomWaves);
   const NormExtents N = normalise_extents(O->npix, O->nexp, O->nseg, 1, kNormWaves);
   try { h->nm_count.assign(N.count_bytes / sizeof(int32_t), 0); } catch (...) { return fail(h, TRX_E_NOMEM, std::string(who) + ": out of host memory"); }
   int rc;
   // steps 0, 1 and 1b, into the call's own buffer
-  if ((rc = detrend_fill(h, who, O, inject != 0, p0, p1, a, o, spectrum, nshift, shift, dbg, X.cells, X.r_bytes, X.c_bytes, X.elem_blocks))) return rc;
+  if ((rc = detrend_fill(h, O, FillCall{who, inject != 0, p0, p1, a, o, spectrum, nshift, shift, dbg}))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->nm_count.data(), h->d_nm_count.p, N.count_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (every kernel has finished)
   if (data) HIPCHK(h, hipMemcpy(data, h->d_sr_r.p, N.r_bytes, hipMemcpyDeviceToHost));
   if (rowscale) HIPCHK(h, hipMemcpy(rowscale, h->d_nm_scale.p, N.scale_bytes, hipMemcpyDeviceToHost));
   if (centre) HIPCHK(h, hipMemcpy(centre, h->d_nm_centre.p, N.centre_bytes, hipMemcpyDeviceToHost));
   // the swap comes last, as detrend_install's: the data in force, the weights of trx_set_observed back, no filter
-  O->d_data.uncover(h->d_hp_r);
-  O->d_data.adopt(h->d_sr_r); O->d_weight.restore(h->d_sc_w);
-  h->filter.reset();
+  std::unique_ptr<FilterSet> none;
+  detrend_swap(h, O, none);
   // (the counts are integers: per column on the device, over the columns here)
   int64_t nc = 0, nb = 0;
   const size_t npix = (size_t)O->npix;

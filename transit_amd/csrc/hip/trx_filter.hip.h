@@ -31,11 +31,27 @@
 #include <stdint.h>
 #include "transit_hip.h"
 #include "trx_device.h"
+#include "../trx_columns.h"
 
 namespace trx {
 
-constexpr int kFiltWaves = 4;                         // tiles (waves) per block
-constexpr int kFiltTrips = 4;                         // exposures whose loads a wave has in flight at once
+constexpr int kFiltWaves = 4;                         // tiles (waves) per block (kFiltTrips: ../trx_columns.h)
+
+// The prologue of a kernel of one wavefront per tile, WAVES tiles per block, one lane per pixel column: column(T, p) with the
+// wave's tile T and the lane's column p; a wave past the last tile and a lane past its tile's end do nothing.  The wave's
+// number is a value the compiler knows to be the same in all its lanes: what follows from it -- the tile, its segment, the
+// addresses of the segment's matrices and vectors -- is read through scalar loads.  (The column is a callable and not a
+// returned flag: the two early returns stay two plain branches, as written out in a kernel.)
+template <int WAVES, class Column>
+__device__ __forceinline__ void tile_column(const FilterTile *tiles, int64_t ntiles, Column column)
+{
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t tile = (int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (tile >= ntiles) return;
+  const FilterTile T = tiles[tile];
+  if (lane >= T.count) return;
+  column(T, T.first + lane);
+}
 
 struct FilterArgs {
   const double2 *pairs;     // [nexp][npix] (a, b): d_pixout of this run

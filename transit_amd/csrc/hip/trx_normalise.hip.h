@@ -11,9 +11,10 @@
 //                    exact in any order.  Every lane of the block takes every trip of every loop: their counts come from the
 //                    segment's length alone, the barriers are block-uniform.  Lane 0 stores scale[v][s]; the array is zeroed
 //                    before the launch.  With row_kind NONE only the live entries are counted.
-//   k_norm_cols       one lane per pixel column, a wave per tile of <= 64 columns of one segment, in place in the call's
-//                    buffer: the sum of f1 = f0 / scale over the entries live in a good row (v ascending, the loads of
-//                    kSysTrips exposures issued before the first add), the centre, with a clip the mean and the squares of
+//   k_norm_cols       one lane per pixel column, a wave per tile of <= 64 columns of one segment (tile_column), in place in
+//                    the call's buffer.  The lane's column is norm_column of ../trx_normalise.h: the sum of f1 = f0 / scale
+//                    over the entries live in a good row (v ascending in trips of kSysTrips, exposure_trips' loop of
+//                    ../trx_columns.h written out there), the centre, with a clip the mean and the squares of
 //                    f2, then the pass that writes f2 -- the mean where the clip takes the entry, +0 where the entry is dead
 //                    or its row or column bad --, centre[p] and the column's two counts.  Every pass forms f1 and f2 again
 //                    from f0: the same operations, the same bits.
@@ -105,91 +106,13 @@ __global__ __launch_bounds__(kNormBlock) void k_norm_rowscale(NormArgs A)
   if (lane == 0) A.scale[row] = norm_scale(A.row_kind, x, m);
 }
 
-// one column, in place; HASW: the set has weights (without: every W is 1, nothing is loaded for it).  A template, not a test
-// per load: the loads of a trip must all be issued before the first is waited for.  PASS 0: n and the sum of f1; 1: the sum
-// of f2; 2: the squares of f2 about the mean
-template <bool HASW, int PASS>
-__device__ __forceinline__ void norm_column_pass(const NormArgs &A, int64_t p, const double *scale, double c, double mean, int32_t &n, double &acc)
-{
-#pragma clang fp contract(off)
-  const int nexp = A.nexp;
-  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-    double w[kSysTrips], r[kSysTrips], sc[kSysTrips];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++) {
-      const int v = min(v0 + t, nexp - 1);
-      const int64_t at = (int64_t)v * A.npix + p;
-      r[t] = A.r[at];
-      w[t] = HASW ? A.weight[at] : 1.0;
-      sc[t] = scale[(int64_t)v * A.nseg];
-    }
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++)
-      if (v0 + t < nexp) {
-        const bool on = norm_on(w[t], sc[t]);
-        // (an entry that takes no part is not divided: its scale may be +0)
-        if (PASS == 0) norm_sum_term(on, on ? norm_row(A.row_kind, r[t], sc[t]) : 0.0, n, acc);
-        else if (PASS == 1) { int32_t unused = 0; norm_sum_term(on, on ? norm_entry(A.row_kind, A.col_kind, r[t], sc[t], c) : 0.0, unused, acc); }
-        else norm_square_term(on, on ? norm_entry(A.row_kind, A.col_kind, r[t], sc[t], c) : 0.0, mean, acc);
-      }
-  }
-}
-
-template <bool HASW>
-__device__ __forceinline__ void norm_column(const NormArgs &A, int64_t p, int32_t seg)
-{
-#pragma clang fp contract(off)
-  const int nexp = A.nexp;
-  const double *const scale = A.scale + seg;           // scale[v * nseg] is this segment's at exposure v
-  int32_t n = 0; double s = 0.0;
-  norm_column_pass<HASW, 0>(A, p, scale, 0.0, 0.0, n, s);
-  bool good;
-  const double c = norm_centre(A.col_kind, s, n, good);
-  const bool clips = norm_clips(A.clip, n, good);
-  double mean = 0.0, lim = 0.0;
-  if (clips) {
-    int32_t unused = 0; double s2 = 0.0, q = 0.0;
-    norm_column_pass<HASW, 1>(A, p, scale, c, 0.0, unused, s2);
-    mean = norm_mean(s2, n);
-    norm_column_pass<HASW, 2>(A, p, scale, c, mean, unused, q);
-    lim = norm_limit(A.clip, q, n);
-  }
-  int32_t nclip = 0, nbad = 0;
-  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-    double w[kSysTrips], r[kSysTrips], sc[kSysTrips];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++) {
-      const int v = min(v0 + t, nexp - 1);
-      const int64_t at = (int64_t)v * A.npix + p;
-      r[t] = A.r[at];
-      w[t] = HASW ? A.weight[at] : 1.0;
-      sc[t] = scale[(int64_t)v * A.nseg];
-    }
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++)
-      if (v0 + t < nexp) {
-        const bool on = norm_on(w[t], sc[t]) && good;
-        double out = 0.0;
-        if (on) {
-          out = norm_entry(A.row_kind, A.col_kind, r[t], sc[t], c);
-          if (clips && norm_clipped(out, mean, lim)) { out = mean; nclip++; }
-        } else if (w[t] > 0.0) nbad++;
-        A.r[(int64_t)(v0 + t) * A.npix + p] = out;
-      }
-  }
-  A.centre[p] = c;
-  A.count[p] = nclip;
-  A.count[A.npix + p] = nbad;
-}
-
 __global__ __launch_bounds__(64 * kNormWaves) void k_norm_cols(NormArgs A)
 {
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t tile = (int64_t)blockIdx.x * kNormWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  if (A.weight) norm_column<true>(A, T.first + lane, T.seg); else norm_column<false>(A, T.first + lane, T.seg);
+  tile_column<kNormWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    const double *const scale = A.scale + T.seg;       // scale[v * nseg] is this segment's at exposure v
+    if (A.weight) norm_column<true>(A.r, A.weight, scale, p, A.npix, A.nseg, A.nexp, A.row_kind, A.col_kind, A.clip, A.centre[p], A.count[p], A.count[A.npix + p]);
+    else norm_column<false>(A.r, nullptr, scale, p, A.npix, A.nseg, A.nexp, A.row_kind, A.col_kind, A.clip, A.centre[p], A.count[p], A.count[A.npix + p]);
+  });
 }
 
 }  // namespace trx

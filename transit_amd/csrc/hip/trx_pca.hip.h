@@ -7,8 +7,9 @@
 //
 //   k_pca_live      k_sysrem_rows' structure: one wavefront per row (v, s), kMomWaves rows per block; the lanes look at the
 //                   segment's weights 64 at a time and leave at the first trip that finds one > 0.  live [nseg][nexp].
-//   k_pca_whole     one lane per pixel column, one wavefront per tile of the tile table, kFiltWaves tiles per block: v
-//                   ascends over the live exposures.  whole [npix].
+//   k_pca_whole     one lane per pixel column, one wavefront per tile of the tile table, kFiltWaves tiles per block
+//                   (tile_column); the lane's column is pca_whole_column of ../trx_pca.h: v ascends over the live exposures.
+//                   whole [npix].
 //   k_pca_gram      one wavefront per tile of kPcaGramTile x kPcaGramTile entries (v, u) of a segment's G, bv <= bu,
 //                   kPcaGramWaves tiles per block.  Lane l carries the 16 accumulators at its own pixels first + l, first +
 //                   l + 64, ..., 8 loads a step in place of 32, then one wave_sum butterfly per entry; lane 0 stores
@@ -20,8 +21,9 @@
 //                   and Vt, barrier, the row phase over (pair, column) items of A, barrier -- nsweep * (m - 1) rounds,
 //                   no convergence test.  Then the eigenvalues, offdiag, the ranks by counting, the sign, U and eigen;
 //                   the block also counts its segment's whole columns.
-//   k_pca_project   k_sysrem_subtract's tiling: one lane per pixel column; the coefficients of all components in
-//                   registers (v ascending), then the residuals in place (i ascending per entry).
+//   k_pca_project   k_sysrem_subtract's tiling: one lane per pixel column, pca_project_column of ../trx_pca.h; the
+//                   coefficients of all components in registers (v ascending), then the residuals in place (i ascending
+//                   per entry).
 //
 // No atomics; cross-lane work goes through wave_sum, wave_sum_ll and the block's barriers only.  The bits of a segment's
 // result depend on that segment's data and weights, ncomp and nsweep -- not on other segments, the launch or the handle.
@@ -75,20 +77,10 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_pca_live(PcaArgs A)
 
 __global__ __launch_bounds__(64 * kFiltWaves) void k_pca_whole(PcaArgs A)
 {
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  const int64_t p = T.first + lane;
-  const int32_t *const live = A.live + (int64_t)T.seg * A.nexp;
-  bool any = false, all = true;
-  for (int v = 0; v < A.nexp; v++) {
-    if (!live[v]) continue;
-    any = true;
-    if (A.weight && !(A.weight[(int64_t)v * A.npix + p] > 0.0)) all = false;
-  }
-  A.whole[p] = any && all ? 1 : 0;
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    const bool hasw = A.weight != nullptr;
+    A.whole[p] = pca_whole_column(A.live + (int64_t)T.seg * A.nexp, hasw ? A.weight + p : nullptr, hasw, A.npix, A.nexp) ? 1 : 0;
+  });
 }
 
 __global__ __launch_bounds__(64 * kPcaGramWaves) void k_pca_gram(PcaArgs A)
@@ -237,37 +229,10 @@ __global__ __launch_bounds__(kPcaBlock) void k_pca_jacobi(PcaArgs A)
 
 __global__ __launch_bounds__(64 * kFiltWaves) void k_pca_project(PcaArgs A)
 {
-#pragma clang fp contract(off)
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  const int64_t p = T.first + lane;
-  const int nexp = A.nexp, ncomp = A.ncomp;
-  const double *const U = A.basis + (int64_t)T.seg * nexp * ncomp;
-  double c[TRX_FILTER_MAX];
-#pragma unroll
-  for (int i = 0; i < TRX_FILTER_MAX; i++) c[i] = 0.0;
-  for (int v = 0; v < nexp; v++) {
-    const int64_t at = (int64_t)v * A.npix + p;
-    const double f = A.r[at];
-    const double y = !A.weight || A.weight[at] > 0.0 ? f : 0.0;
-#pragma unroll
-    for (int i = 0; i < TRX_FILTER_MAX; i++)
-      if (i < ncomp) pca_coef_term(U[(int64_t)v * ncomp + i], y, c[i]);
-  }
-#pragma unroll
-  for (int i = 0; i < TRX_FILTER_MAX; i++)
-    if (i < ncomp) A.coef[(int64_t)i * A.npix + p] = c[i];
-  for (int v = 0; v < nexp; v++) {
-    const int64_t at = (int64_t)v * A.npix + p;
-    double r = A.r[at];
-#pragma unroll
-    for (int i = 0; i < TRX_FILTER_MAX; i++)
-      if (i < ncomp) r = sysrem_subtract(r, U[(int64_t)v * ncomp + i], c[i]);
-    A.r[at] = r;
-  }
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    const bool hasw = A.weight != nullptr;
+    pca_project_column(A.r + p, hasw ? A.weight + p : nullptr, hasw, A.basis + (int64_t)T.seg * A.nexp * A.ncomp, A.coef + p, A.npix, A.nexp, A.ncomp);
+  });
 }
 
 }  // namespace trx

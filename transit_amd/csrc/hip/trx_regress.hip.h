@@ -11,7 +11,8 @@
 //                    and NC accumulators y in registers, the vectors through wave-uniform loads; then the solve, the
 //                    column's factor entries loaded as they are used (coalesced, each once per triangle); pass 2 walks v
 //                    again -- f0 once more, r_v from U and the coefficients, and the residual written over f0 in place.
-//                    Both passes issue the loads of kFiltTrips exposures before they use the first.  coef[j][p] is written
+//                    Both passes walk in exposure_trips' trips of kFiltTrips (../trx_columns.h); the prologue is
+//                    tile_column's.  coef[j][p] is written
 //                    between the passes.  A column with a singular pivot gets the coefficients +0 and keeps f0.
 //
 // No LDS, no cross-lane operation, no atomics: a lane past the tile's end loads and stores nothing.  The bits of a column's
@@ -44,16 +45,11 @@ struct RegressArgs {
 template <int NC>
 __global__ __launch_bounds__(64 * kFiltWaves) void k_regress_cols(RegressArgs A)
 {
-  const int lane = (int)(threadIdx.x & 63);
-  // (the wave's number, as a value the compiler knows to be the same in all its lanes: the tile, its segment and the
-  // vectors' address are read through scalar loads)
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  const int64_t p = T.first + lane;
-  regress_column<NC>(A.basis + (int64_t)T.seg * A.nexp * NC, A.weight ? A.weight + p : nullptr, A.r + p, A.fac + p, A.live[p] != 0, A.coef + p,
-                     A.npix, A.nexp, A.nvec);
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    const bool hasw = A.weight != nullptr;
+    regress_column<NC>(A.basis + (int64_t)T.seg * A.nexp * NC, hasw ? A.weight + p : nullptr, hasw, A.r + p, A.fac + p, A.live[p] != 0, A.coef + p,
+                       A.npix, A.nexp, A.nvec);
+  });
 }
 
 }  // namespace trx

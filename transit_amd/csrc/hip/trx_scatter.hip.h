@@ -3,9 +3,9 @@
 // inverse variance of the columns kept, or a mask of them.  The arithmetic is ../trx_scatter.h's, the same source a CPU
 // program runs.
 //
-//   k_scatter_cols     one lane per pixel column, kScatBlock columns per block, a wave's loads coalesced.  Two passes over
-//                    the exposures, v ascending, the loads of the weight and the datum of kSysTrips exposures issued
-//                    before the first add (a trip past the last exposure reads the last one again and adds nothing): the
+//   k_scatter_cols     one lane per pixel column, kScatBlock columns per block, a wave's loads coalesced.  The lane's column
+//                    is scatter_column of ../trx_scatter.h: two passes over the exposures, v ascending in trips of
+//                    kSysTrips (exposure_trips' loop of ../trx_columns.h, written out there): the
 //                    count and the sum, then the squares about the mean.  Writes var[p]: > 0 for a live column, +0 for a
 //                    dead one.
 //   k_scatter_median   one block per tile of scatter_tiles (<= kScatBlock columns of one segment), a wave owning 64 of the
@@ -16,8 +16,8 @@
 //                    staged: a ballot per wave, the waves' totals added through LDS -- integers, exact in any order.  The
 //                    one live lane of the segment whose rank is (m - 1) / 2 stores med[s]; med is zeroed before the launch,
 //                    which is the answer of an empty segment (no tile) and of one without a live column (no lane stores).
-//   k_scatter_weights  one block per tile, one lane per column: the keep rule and 1 / var once, then the column's new
-//                    weights for every exposure (kSysTrips loads of W in flight) and the column's flag.
+//   k_scatter_weights  one block per tile, one lane per column (scatter_weights_column): the keep rule and 1 / var once, then
+//                    the column's new weights for every exposure (exposure_trips' trips of kSysTrips) and the column's flag.
 //
 // No atomics, no scratch; LDS in k_scatter_median alone (kScatLds doubles and a count per wave).  The bits of a segment's result depend on that
 // segment's data and weights and on the call's parameters -- not on other segments, the launch or the handle.
@@ -45,50 +45,11 @@ struct ScatterArgs {
   double clip;
 };
 
-// one column's variance; HASW: the set has weights (without: every W is 1, nothing is loaded for it).  A template, not a test
-// per load: the loads of a trip must all be issued before the first is waited for
-template <bool HASW>
-__device__ __forceinline__ double scatter_column(const ScatterArgs &A, int64_t p)
-{
-#pragma clang fp contract(off)
-  const int nexp = A.nexp;
-  int32_t n = 0; double s = 0.0;
-  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-    double w[kSysTrips], r[kSysTrips];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++) {
-      const int64_t at = (int64_t)min(v0 + t, nexp - 1) * A.npix + p;
-      r[t] = A.r[at];
-      w[t] = HASW ? A.weight[at] : 1.0;
-    }
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++)
-      if (v0 + t < nexp) scatter_sum_term(w[t], r[t], n, s);
-  }
-  double q = 0.0;
-  if (scatter_enough(n, A.min_live)) {
-    const double mean = scatter_mean(s, n);
-    for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-      double w[kSysTrips], r[kSysTrips];
-#pragma unroll
-      for (int t = 0; t < kSysTrips; t++) {
-        const int64_t at = (int64_t)min(v0 + t, nexp - 1) * A.npix + p;
-        r[t] = A.r[at];
-        w[t] = HASW ? A.weight[at] : 1.0;
-      }
-#pragma unroll
-      for (int t = 0; t < kSysTrips; t++)
-        if (v0 + t < nexp) scatter_square_term(w[t], r[t], mean, q);
-    }
-  }
-  return scatter_variance(q, n, A.min_live);
-}
-
 __global__ __launch_bounds__(kScatBlock) void k_scatter_cols(ScatterArgs A)
 {
   const int64_t p = (int64_t)blockIdx.x * kScatBlock + threadIdx.x;
   if (p >= A.npix) return;
-  A.var[p] = A.weight ? scatter_column<true>(A, p) : scatter_column<false>(A, p);
+  A.var[p] = A.weight ? scatter_column<true>(A.r + p, A.weight + p, A.npix, A.nexp, A.min_live) : scatter_column<false>(A.r + p, nullptr, A.npix, A.nexp, A.min_live);
 }
 
 static_assert(kScatLds % kScatTrip == 0 && kScatBlock % 64 == 0, "a padded trip fits the staging array; whole waves");
@@ -135,24 +96,12 @@ __global__ __launch_bounds__(kScatBlock) void k_scatter_median(ScatterArgs A)
 
 __global__ __launch_bounds__(kScatBlock) void k_scatter_weights(ScatterArgs A)
 {
-#pragma clang fp contract(off)
   const int lane = (int)threadIdx.x;
   const FilterTile T = A.tiles[blockIdx.x];
   if (lane >= T.count) return;
   const int64_t p = T.first + lane;
-  const int nexp = A.nexp;
-  const double var = A.var[p];
-  const bool keep = scatter_keep(var, A.med[T.seg], A.clip);
-  const double inv = scatter_inverse(var, keep);
-  A.flag[p] = scatter_flag(var, keep);
-  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-    double w[kSysTrips];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++) w[t] = A.weight ? A.weight[(int64_t)min(v0 + t, nexp - 1) * A.npix + p] : 1.0;
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++)
-      if (v0 + t < nexp) A.out[(int64_t)(v0 + t) * A.npix + p] = scatter_weight(A.kind, w[t], keep, inv);
-  }
+  const bool hasw = A.weight != nullptr;
+  scatter_weights_column(A.var[p], A.med[T.seg], A.clip, A.kind, hasw ? A.weight + p : nullptr, hasw, A.out + p, A.flag[p], A.npix, A.nexp);
 }
 
 }  // namespace trx

@@ -7,9 +7,9 @@
 //
 //   k_sysrem_inject    element-wise over [nexp][npix]: r = F * (p0 g + p1) where the run's pair has b > 0, F elsewhere.
 //   k_sysrem_cols      the column step.  One lane per pixel column, one wavefront per tile of filter_layout's tile table
-//                    (<= 64 pixels of one segment), kFiltWaves tiles per block.  v ascends, the loads of w and r of
-//                    kSysTrips exposures issued before the first add (a trip past the last exposure reads the last one
-//                    again and adds nothing); a_v is wave-uniform (a null a: every a_v = 1, a component's first step).
+//                    (<= 64 pixels of one segment), kFiltWaves tiles per block (tile_column).  The lane's column is
+//                    sysrem_column_step of ../trx_sysrem.h: v ascends in exposure_trips' trips of kSysTrips
+//                    (../trx_columns.h); a_v is wave-uniform (a null a: every a_v = 1, a component's first step).
 //   k_sysrem_rows      the row step.  k_pixel_moments' structure: one wavefront per row (v, s), kMomWaves rows per
 //                    block; lane l adds the segment's pixels first + l, first + l + 64, ... in that order, kMomTrips
 //                    trips in flight (a lane past the end reads the last pixel again and adds nothing), then wave_sum's
@@ -17,7 +17,7 @@
 //   k_sysrem_close     one wavefront per tile: the norm t of its segment's a (every tile of a segment computes the same
 //                    t from the same a, which the kernel does not change), the scaled c into coef[i][p], and -- the
 //                    segment's first tile -- the scaled a into U[s][v][i].
-//   k_sysrem_subtract  one wavefront per tile: r[v][p] = r[v][p] - U[s][v][i] * coef[i][p].
+//   k_sysrem_subtract  one wavefront per tile: r[v][p] = r[v][p] - U[s][v][i] * coef[i][p] (sysrem_column_subtract, the same trips).
 //
 // No LDS, no atomics; cross-lane work goes through wave_sum only.  The bits of a segment's result depend on that segment's
 // data and weights, ncomp and niter -- not on other segments, the launch or the handle.
@@ -32,8 +32,6 @@
 #include "../trx_sysrem.h"
 
 namespace trx {
-
-constexpr int kSysTrips = 8;                          // exposures whose loads a column kernel's wave has in flight at once
 
 struct SysremInjectArgs {
   const double2 *pairs;     // [nexp][npix] (a, b) of the run
@@ -68,29 +66,10 @@ __global__ __launch_bounds__(kPixBlock) void k_sysrem_inject(SysremInjectArgs A)
 
 __global__ __launch_bounds__(64 * kFiltWaves) void k_sysrem_cols(SysremArgs A)
 {
-#pragma clang fp contract(off)
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  const int64_t p = T.first + lane;
-  const int nexp = A.nexp;
-  const double *const a = A.a ? A.a + (int64_t)T.seg * nexp : nullptr;
-  double num = 0.0, den = 0.0;
-  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-    double w[kSysTrips], r[kSysTrips];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++) {
-      const int64_t at = (int64_t)min(v0 + t, nexp - 1) * A.npix + p;
-      r[t] = A.r[at];
-      w[t] = A.weight ? A.weight[at] : 1.0;
-    }
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++)
-      if (v0 + t < nexp) sysrem_col_term(w[t], r[t], a ? a[v0 + t] : 1.0, num, den);
-  }
-  A.c[p] = sysrem_ratio(num, den);
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    const bool hasw = A.weight != nullptr;
+    A.c[p] = sysrem_column_step(A.r + p, hasw ? A.weight + p : nullptr, hasw, A.a ? A.a + (int64_t)T.seg * A.nexp : nullptr, A.npix, A.nexp);
+  });
 }
 
 __global__ __launch_bounds__(64 * kMomWaves) void k_sysrem_rows(SysremArgs A)
@@ -140,23 +119,9 @@ __global__ __launch_bounds__(64 * kFiltWaves) void k_sysrem_close(SysremArgs A)
 
 __global__ __launch_bounds__(64 * kFiltWaves) void k_sysrem_subtract(SysremArgs A)
 {
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  const int64_t p = T.first + lane;
-  const int nexp = A.nexp;
-  const double *const U = A.basis + (int64_t)T.seg * nexp * A.ncomp + A.comp;
-  const double c = A.coef[(int64_t)A.comp * A.npix + p];
-  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
-    double r[kSysTrips];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++) r[t] = A.r[(int64_t)min(v0 + t, nexp - 1) * A.npix + p];
-#pragma unroll
-    for (int t = 0; t < kSysTrips; t++)
-      if (v0 + t < nexp) A.r[(int64_t)(v0 + t) * A.npix + p] = sysrem_subtract(r[t], U[(int64_t)(v0 + t) * A.ncomp], c);
-  }
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    sysrem_column_subtract(A.r + p, A.basis + (int64_t)T.seg * A.nexp * A.ncomp + A.comp, A.ncomp, A.coef[(int64_t)A.comp * A.npix + p], A.npix, A.nexp);
+  });
 }
 
 }  // namespace trx

@@ -8,7 +8,9 @@
 // run solves with the factor.  The arithmetic is ../trx_wfilter.h's, the same source a CPU program runs.
 //
 //   k_wfilter_factor<NC>  at install.  One lane per pixel column, one wavefront per tile of the filter's tile table,
-//                    kFiltWaves tiles per block.  For row j = 0 .. ncomp-1 one pass over the exposures adds row j of the
+//                    kFiltWaves tiles per block (tile_column).  The lane's column is wfilter_factor_column of
+//                    ../trx_wfilter.h: for row j = 0 .. ncomp-1 one pass over the exposures (exposure_trips' trips of
+//                    kFiltTrips, ../trx_columns.h) adds row j of the
 //                    normal matrix (j + 1 accumulators in registers; the basis through wave-uniform loads, the weights
 //                    coalesced), then row j of the factor is made from it and from the rows below j, which the lane reads
 //                    back from where it stored them.  It writes fac[e][p] (component-major: coalesced) and live[p].
@@ -61,40 +63,18 @@ struct WfilterArgs {
 template <int NC>
 __global__ __launch_bounds__(64 * kFiltWaves) void k_wfilter_factor(WfilterFactorArgs A)
 {
-#pragma clang fp contract(off)
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  const int64_t p = T.first + lane;
-  const int nexp = A.nexp, n = A.ncomp;
-  const double *const U = A.basis + (int64_t)T.seg * nexp * NC;
-  double *const fac = A.fac + p;
-  bool good = true;
-  for (int j = 0; j < n; j++) {
-    double Nrow[NC];
-#pragma unroll
-    for (int k = 0; k < NC; k++) Nrow[k] = 0.0;
-    for (int v0 = 0; v0 < nexp; v0 += kFiltTrips) {
-      double w[kFiltTrips];
-#pragma unroll
-      for (int t = 0; t < kFiltTrips; t++) w[t] = A.weight ? A.weight[(int64_t)min(v0 + t, nexp - 1) * A.npix + p] : 1.0;
-#pragma unroll
-      for (int t = 0; t < kFiltTrips; t++)
-        if (v0 + t < nexp) wfilter_normal_term<NC>(U + (int64_t)(v0 + t) * NC, w[t], j, Nrow);
-    }
-    good = wfilter_factor_row<NC>(j, Nrow, fac, A.npix) && good;
-  }
-  A.live[p] = good ? 1 : 0;
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) {
+    const bool hasw = A.weight != nullptr;
+    const bool good = wfilter_factor_column<NC>(A.basis + (int64_t)T.seg * A.nexp * NC, hasw ? A.weight + p : nullptr, hasw, A.fac + p, A.npix, A.nexp, A.ncomp);
+    A.live[p] = good ? 1 : 0;
+  });
 }
 
-// one column of the run: CELL: exposure v's pair from row idx[v] of the pairs
+// one column p of the run: CELL: exposure v's pair from row idx[v] of the pairs
 template <int NC, bool CELL>
-__device__ __forceinline__ void wfilter_column(const WfilterArgs &A, const FilterTile &T, int lane, const int32_t *idx, double *val)
+__device__ __forceinline__ void wfilter_column(const WfilterArgs &A, const FilterTile &T, int64_t p, const int32_t *idx, double *val)
 {
 #pragma clang fp contract(off)
-  const int64_t p = T.first + lane;
   const int nexp = A.nexp;
   const double gn = A.gain ? A.gain[p] : 1.0;
   const double *const U = A.basis + (int64_t)T.seg * nexp * NC;
@@ -142,14 +122,7 @@ __device__ __forceinline__ void wfilter_column(const WfilterArgs &A, const Filte
 template <int NC>
 __global__ __launch_bounds__(64 * kFiltWaves) void k_pixel_wfilter(WfilterArgs A)
 {
-  const int lane = (int)(threadIdx.x & 63);
-  // (the wave's number, as a value the compiler knows to be the same in all its lanes: what follows from it -- the
-  // tile, its segment, the basis' address -- is read through scalar loads)
-  const int64_t tile = (int64_t)blockIdx.x * kFiltWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (tile >= A.ntiles) return;
-  const FilterTile T = A.tiles[tile];
-  if (lane >= T.count) return;
-  wfilter_column<NC, false>(A, T, lane, nullptr, A.val);
+  tile_column<kFiltWaves>(A.tiles, A.ntiles, [&](const FilterTile &T, int64_t p) { wfilter_column<NC, false>(A, T, p, nullptr, A.val); });
 }
 
 template <int NC>
@@ -165,7 +138,7 @@ __global__ __launch_bounds__(64 * kFiltWaves) void k_cell_wfilter(WfilterArgs A)
   if (out) return;
   const FilterTile T = A.tiles[tile];
   if (lane >= T.count) return;
-  wfilter_column<NC, true>(A, T, lane, idx, A.val + c * A.nexp * A.npix);
+  wfilter_column<NC, true>(A, T, T.first + lane, idx, A.val + c * A.nexp * A.npix);
 }
 
 }  // namespace trx

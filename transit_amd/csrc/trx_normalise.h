@@ -202,4 +202,104 @@ TRX_HD double norm_limit(double clip, double q, int32_t n)
 }
 TRX_HD bool norm_clipped(double f2, double mean, double lim) { return norm_dev2(f2, mean) > lim; }
 
+// ---- one column ---------------------------------------------------------------------------------------
+// what a trip loads of an exposure: the datum f0, its weight and its row's scale
+struct NormEntry { double f, w, sc; };
+
+// One column p: r the set's data (the column's entry v at r[v * stride + p]: the arrays whole and the column's number, not a
+// pointer per lane -- that form costs this kernel registers enough to lose a wave), w its weights the same way, scale the
+// column's segment's row scales (exposure v's at scale[v * sstride]).  HASW: the set has weights (without: every W is 1, nothing
+// is loaded for it, w is not read).  A template, decided once per launch: the loads of a trip must all be issued before the
+// first is waited for.  Every pass takes the exposures in trips of kSysTrips, written out here, exposure_trips' loop line for
+// line: through the helper the device compiler turns terms of a trip into branches of their own (trx_columns.h).  norm_trip
+// loads the trip that starts at v0.
+template <bool HASW>
+TRX_HD void norm_trip(const double *r, const double *w, const double *scale, int64_t p, int64_t stride, int64_t sstride, int nexp, int v0,
+                      NormEntry (&got)[kSysTrips])
+{
+  const int last = nexp - 1;
+#if defined(__clang__)
+#pragma unroll
+#endif
+  for (int t = 0; t < kSysTrips; t++) {
+    const int v = v0 + t < last ? v0 + t : last;
+    const int64_t at = (int64_t)v * stride + p;
+    got[t] = NormEntry{r[at], HASW ? w[at] : 1.0, scale[(int64_t)v * sstride]};
+  }
+}
+
+// PASS 0: n and the sum of f1; 1: the sum of f2; 2: the squares of f2 about the mean
+template <bool HASW, int PASS>
+TRX_HD void norm_column_pass(const double *r, const double *w, const double *scale, int64_t p, int64_t stride, int64_t sstride, int nexp, int32_t row_kind,
+                             int32_t col_kind, double c, double mean, int32_t &n, double &acc)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    NormEntry got[kSysTrips];
+    norm_trip<HASW>(r, w, scale, p, stride, sstride, nexp, v0, got);
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) {
+        const NormEntry &x = got[t];
+        const bool on = norm_on(x.w, x.sc);
+        // (an entry that takes no part is not divided: its scale may be +0)
+        if (PASS == 0) norm_sum_term(on, on ? norm_row(row_kind, x.f, x.sc) : 0.0, n, acc);
+        else if (PASS == 1) { int32_t unused = 0; norm_sum_term(on, on ? norm_entry(row_kind, col_kind, x.f, x.sc, c) : 0.0, unused, acc); }
+        else norm_square_term(on, on ? norm_entry(row_kind, col_kind, x.f, x.sc, c) : 0.0, mean, acc);
+      }
+  }
+}
+
+// The column in place: the sum of f1 over the entries that take part and the centre, with a clip the mean and the squares of
+// f2, then the pass that writes f2 -- the mean where the clip takes the entry, +0 where the entry is dead or its row or column
+// bad.  Every pass forms f1 and f2 again from f0: the same operations, the same bits.  centre: the column's centre; nclip, nbad:
+// the entries the clip replaced, the live entries that got +0
+template <bool HASW>
+TRX_HD void norm_column(double *r, const double *w, const double *scale, int64_t p, int64_t stride, int64_t sstride, int nexp, int32_t row_kind, int32_t col_kind,
+                        double clip, double &centre, int32_t &nclip_out, int32_t &nbad_out)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  int32_t n = 0; double s = 0.0;
+  norm_column_pass<HASW, 0>(r, w, scale, p, stride, sstride, nexp, row_kind, col_kind, 0.0, 0.0, n, s);
+  bool good;
+  const double c = norm_centre(col_kind, s, n, good);
+  const bool clips = norm_clips(clip, n, good);
+  double mean = 0.0, lim = 0.0;
+  if (clips) {
+    int32_t unused = 0; double s2 = 0.0, q = 0.0;
+    norm_column_pass<HASW, 1>(r, w, scale, p, stride, sstride, nexp, row_kind, col_kind, c, 0.0, unused, s2);
+    mean = norm_mean(s2, n);
+    norm_column_pass<HASW, 2>(r, w, scale, p, stride, sstride, nexp, row_kind, col_kind, c, mean, unused, q);
+    lim = norm_limit(clip, q, n);
+  }
+  int32_t nclip = 0, nbad = 0;
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    NormEntry got[kSysTrips];
+    norm_trip<HASW>(r, w, scale, p, stride, sstride, nexp, v0, got);
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) {
+        const NormEntry &x = got[t];
+        const bool on = norm_on(x.w, x.sc) && good;
+        double out = 0.0;
+        if (on) {
+          out = norm_entry(row_kind, col_kind, x.f, x.sc, c);
+          if (clips && norm_clipped(out, mean, lim)) { out = mean; nclip++; }
+        } else if (x.w > 0.0) nbad++;
+        r[(int64_t)(v0 + t) * stride + p] = out;
+      }
+  }
+  centre = c;
+  nclip_out = nclip;
+  nbad_out = nbad;
+}
+
 }  // namespace trx

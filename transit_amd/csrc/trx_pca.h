@@ -140,6 +140,59 @@ TRX_HD void pca_coef_term(double u, double y, double &c)
   c = c + m;
 }
 
+// ---- one column ---------------------------------------------------------------------------------------
+// Whether a column is whole: its segment has a live exposure (live [nexp]) and the column's weight is > 0 at every live one.
+// w: the column's weights (entry v at w[v * stride]), read only where hasw: the set has weights -- one answer for the whole
+// launch; without: every w is 1.
+TRX_HD bool pca_whole_column(const int32_t *live, const double *w, bool hasw, int64_t stride, int nexp)
+{
+  bool any = false, all = true;
+  for (int v = 0; v < nexp; v++) {
+    if (!live[v]) continue;
+    any = true;
+    if (hasw && !(w[(int64_t)v * stride] > 0.0)) all = false;
+  }
+  return any && all;
+}
+
+// The projection of one column on its segment's ncomp components U [nexp][ncomp]: the coefficients of all components (v
+// ascending; a masked entry counts as +0) to coef[i * stride], then the residuals in place in r (entry v at r[v * stride]; i
+// ascending per entry).  w, hasw: as above.
+TRX_HD void pca_project_column(double *r, const double *w, bool hasw, const double *U, double *coef, int64_t stride, int nexp, int ncomp)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double c[TRX_FILTER_MAX];
+#if defined(__clang__)
+#pragma unroll
+#endif
+  for (int i = 0; i < TRX_FILTER_MAX; i++) c[i] = 0.0;
+  for (int v = 0; v < nexp; v++) {
+    const double f = r[(int64_t)v * stride];
+    const double y = !hasw || w[(int64_t)v * stride] > 0.0 ? f : 0.0;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int i = 0; i < TRX_FILTER_MAX; i++)
+      if (i < ncomp) pca_coef_term(U[(int64_t)v * ncomp + i], y, c[i]);
+  }
+#if defined(__clang__)
+#pragma unroll
+#endif
+  for (int i = 0; i < TRX_FILTER_MAX; i++)
+    if (i < ncomp) coef[(int64_t)i * stride] = c[i];
+  for (int v = 0; v < nexp; v++) {
+    double x = r[(int64_t)v * stride];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int i = 0; i < TRX_FILTER_MAX; i++)
+      if (i < ncomp) x = sysrem_subtract(x, U[(int64_t)v * ncomp + i], c[i]);
+    r[(int64_t)v * stride] = x;
+  }
+}
+
 // ---- extents -----------------------------------------------------------------------------------------
 // The extents of a call of ncomp components over nexp exposures, nseg segments, npix pixels and ntiles tiles: the
 // residuals r [nexp][npix], coef [ncomp][npix], U [nseg][nexp][ncomp], the Gram matrices G and the transposed eigenvector
@@ -158,16 +211,15 @@ struct PcaExtents {
 inline PcaExtents pca_extents(int64_t npix, int32_t nexp, int32_t nseg, int32_t ncomp, int64_t ntiles, int elem_block, int tiles_per_block, int rows_per_block)
 {
   PcaExtents X;
-  X.cells = (int64_t)nexp * npix; X.rows = (int64_t)nexp * nseg;
-  X.elem_blocks = (X.cells + elem_block - 1) / elem_block;
+  const FillExtents F = fill_extents(npix, nexp, elem_block);
+  X.cells = F.cells; X.elem_blocks = F.elem_blocks; X.r_bytes = F.r_bytes; X.c_bytes = F.c_bytes;
+  X.rows = (int64_t)nexp * nseg;
   X.row_blocks = (X.rows + rows_per_block - 1) / rows_per_block;
   X.tile_blocks = (ntiles + tiles_per_block - 1) / tiles_per_block;
   X.gram_tiles = (int64_t)pca_gram_tiles(nexp) * nseg;
   X.gram_blocks = (X.gram_tiles + kPcaGramWaves - 1) / kPcaGramWaves;
   X.jacobi_blocks = nseg;
   X.stride = nexp | 1; X.npairs = pca_pairs(nexp); X.nrounds = pca_rounds(nexp);
-  X.r_bytes = sizeof(double) * (size_t)X.cells;
-  X.c_bytes = sizeof(double) * (size_t)npix;
   X.coef_bytes = sizeof(double) * (size_t)ncomp * (size_t)npix;
   X.basis_bytes = sizeof(double) * (size_t)X.rows * (size_t)ncomp;
   X.g_bytes = sizeof(double) * (size_t)X.rows * (size_t)nexp;

@@ -89,38 +89,25 @@ inline void regress_merge(const double *given, const double *fit, int32_t nseg, 
 
 // ---- one column ---------------------------------------------------------------------------------------
 // The fit of one column of n components: U its segment's padded vectors [nexp][NC], w the column's weights (entry v at
-// w[v * stride]; null: all 1), r its data f0 in and its residuals out (entry v at r[v * stride]), fac its factor (entry e at
+// w[v * stride]; without hasw: all 1), r its data f0 in and its residuals out (entry v at r[v * stride]), fac its factor (entry e at
 // fac[e * stride]), live whether no pivot of it was singular, coef its coefficients out (component j at coef[j * stride]).
 //   pass 1   y_j = sum over v ascending of (U[v][j] * w[v]) * f0[v]               (wfilter_rhs_term)
 //   solve    c = the factor's forward and back solve of y                        (wfilter_solve); a column with a singular
 //            pivot: c_j = +0 for every j, the solve's result is not used
 //   pass 2   r[v] = f0[v] - (sum over j ascending of U[v][j] * c_j), every v     (wfilter_value)
-// Both passes take kRegressTrips exposures at a time, their loads first -- a trip past the last exposure reads the last
-// one again and adds nothing --, then their terms in exposure order.
+// Both passes take the exposures in exposure_trips' trips of kRegressTrips (trx_columns.h).  w is read only where hasw: the set
+// has weights -- one answer for the whole launch, never a test of a lane's own pointer.
 template <int NC>
-TRX_HD void regress_column(const double *U, const double *w, double *r, const double *fac, bool live, double *coef, int64_t stride, int nexp, int n)
+TRX_HD void regress_column(const double *U, const double *w, bool hasw, double *r, const double *fac, bool live, double *coef, int64_t stride, int nexp, int n)
 {
   double y[NC];
 #if defined(__clang__)
 #pragma unroll
 #endif
   for (int j = 0; j < NC; j++) y[j] = 0.0;
-  for (int v0 = 0; v0 < nexp; v0 += kRegressTrips) {
-    double f[kRegressTrips], wv[kRegressTrips];
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int t = 0; t < kRegressTrips; t++) {
-      const int v = v0 + t < nexp ? v0 + t : nexp - 1;
-      f[t] = r[(int64_t)v * stride];
-      wv[t] = w ? w[(int64_t)v * stride] : 1.0;
-    }
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int t = 0; t < kRegressTrips; t++)
-      if (v0 + t < nexp) wfilter_rhs_term<NC>(U + (int64_t)(v0 + t) * NC, wv[t], f[t], y);
-  }
+  exposure_trips<kRegressTrips>(
+      nexp, [&](int v) { return WeightedEntry{r[(int64_t)v * stride], hasw ? w[(int64_t)v * stride] : 1.0}; },
+      [&](int v, const WeightedEntry &x) { wfilter_rhs_term<NC>(U + (int64_t)v * NC, x.w, x.f, y); });
   wfilter_solve<NC>(n, y, fac, stride);
 #if defined(__clang__)
 #pragma unroll
@@ -129,18 +116,15 @@ TRX_HD void regress_column(const double *U, const double *w, double *r, const do
     y[j] = live ? y[j] : 0.0;
     if (j < n) coef[(int64_t)j * stride] = y[j];
   }
-  for (int v0 = 0; v0 < nexp; v0 += kRegressTrips) {
-    double f[kRegressTrips];
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int t = 0; t < kRegressTrips; t++) f[t] = r[(int64_t)(v0 + t < nexp ? v0 + t : nexp - 1) * stride];
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int t = 0; t < kRegressTrips; t++)
-      if (v0 + t < nexp) r[(int64_t)(v0 + t) * stride] = wfilter_value<NC>(U + (int64_t)(v0 + t) * NC, y, f[t]);
-  }
+  exposure_trips<kRegressTrips>(
+      nexp, [&](int v) { return r[(int64_t)v * stride]; },
+      [&](int v, double f) { r[(int64_t)v * stride] = wfilter_value<NC>(U + (int64_t)v * NC, y, f); });
+}
+// the same for a caller that holds one column's weights or none (w null: all 1) -- a host caller: one column, one answer
+template <int NC>
+TRX_HD void regress_column(const double *U, const double *w, double *r, const double *fac, bool live, double *coef, int64_t stride, int nexp, int n)
+{
+  regress_column<NC>(U, w, w != nullptr, r, fac, live, coef, stride, nexp, n);
 }
 
 }  // namespace trx

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "transit_hip.h"
+#include "trx_columns.h"
 #include "trx_numerics.h"
 #include "trx_products.h"
 
@@ -159,6 +160,73 @@ TRX_HD double scatter_weight(int32_t kind, double W, bool keep, double inv)
   if (!keep) return 0.0;
   if (kind == TRX_SCATTER_VARIANCE) return W > 0.0 ? inv : 0.0;
   return W;
+}
+
+// ---- one column ---------------------------------------------------------------------------------------
+// One column's variance: r its data (entry v at r[v * stride]), w its weights the same way.  HASW: the set has weights
+// (without: every W is 1, nothing is loaded for it, w is not read).  A template, decided once per launch: the loads of a trip
+// must all be issued before the first is waited for.  Two passes in trips of kSysTrips: the count and the sum, then -- a column
+// of enough entries -- the squares about the mean.  The trips are written out here, exposure_trips' loop line for line: through
+// the helper the device compiler turns the first term of every trip into a branch of its own (trx_columns.h).
+template <bool HASW>
+TRX_HD double scatter_column(const double *r, const double *w, int64_t stride, int nexp, int32_t min_live)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int last = nexp - 1;
+  int32_t n = 0; double s = 0.0;
+  for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+    WeightedEntry got[kSysTrips];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int t = 0; t < kSysTrips; t++) {
+      const int64_t at = (int64_t)(v0 + t < last ? v0 + t : last) * stride;
+      got[t] = WeightedEntry{r[at], HASW ? w[at] : 1.0};
+    }
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int t = 0; t < kSysTrips; t++)
+      if (v0 + t < nexp) scatter_sum_term(got[t].w, got[t].f, n, s);
+  }
+  double q = 0.0;
+  if (scatter_enough(n, min_live)) {
+    const double mean = scatter_mean(s, n);
+    for (int v0 = 0; v0 < nexp; v0 += kSysTrips) {
+      WeightedEntry got[kSysTrips];
+#if defined(__clang__)
+#pragma unroll
+#endif
+      for (int t = 0; t < kSysTrips; t++) {
+        const int64_t at = (int64_t)(v0 + t < last ? v0 + t : last) * stride;
+        got[t] = WeightedEntry{r[at], HASW ? w[at] : 1.0};
+      }
+#if defined(__clang__)
+#pragma unroll
+#endif
+      for (int t = 0; t < kSysTrips; t++)
+        if (v0 + t < nexp) scatter_square_term(got[t].w, got[t].f, mean, q);
+    }
+  }
+  return scatter_variance(q, n, min_live);
+}
+
+// One column's new weights: the keep rule and 1 / var once, then out[v * stride] for every exposure from the column's own
+// weights w (read only where hasw: one answer for the whole launch; without: every W is 1), and the column's flag
+TRX_HD void scatter_weights_column(double var, double med, double clip, int32_t kind, const double *w, bool hasw, double *out, int32_t &flag, int64_t stride,
+                                   int nexp)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const bool keep = scatter_keep(var, med, clip);
+  const double inv = scatter_inverse(var, keep);
+  flag = scatter_flag(var, keep);
+  exposure_trips<kSysTrips>(
+      nexp, [&](int v) { return hasw ? w[(int64_t)v * stride] : 1.0; },
+      [&](int v, double W) { out[(int64_t)v * stride] = scatter_weight(kind, W, keep, inv); });
 }
 
 }  // namespace trx

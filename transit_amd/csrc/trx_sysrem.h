@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "transit_hip.h"
+#include "trx_columns.h"
 #include "trx_numerics.h"
 #include "trx_products.h"
 
@@ -72,6 +73,20 @@ inline int sysrem_tiles(const ProductState &S, std::vector<FilterTile> &tiles, s
   return TRX_OK;
 }
 
+// The extents of steps 0 and 1 of a detrending call -- the raw or the injected data into the call's buffer --, whatever the
+// call fits afterwards: the cells of [nexp][npix], the bytes of the residuals r and of a vector of one double per pixel (the
+// gains the injection reads; SYSREM's c), the blocks of the element-wise kernel (elem_block cells each).
+struct FillExtents { int64_t cells = 0, elem_blocks = 0; size_t r_bytes = 0, c_bytes = 0; };
+inline FillExtents fill_extents(int64_t npix, int32_t nexp, int elem_block)
+{
+  FillExtents X;
+  X.cells = (int64_t)nexp * npix;
+  X.elem_blocks = (X.cells + elem_block - 1) / elem_block;
+  X.r_bytes = sizeof(double) * (size_t)X.cells;
+  X.c_bytes = sizeof(double) * (size_t)npix;
+  return X;
+}
+
 // The extents of a detrend call of ncomp components and niter alternations over nexp exposures, nseg segments, npix pixels
 // and ntiles tiles: the residuals r [nexp][npix], the time vector a [nseg][nexp], the column vector c [npix], coef
 // [ncomp][npix] and U [nseg][nexp][ncomp]; the blocks of the element-wise kernel (elem_block cells each), of the column
@@ -85,14 +100,13 @@ inline SysremExtents sysrem_extents(int64_t npix, int32_t nexp, int32_t nseg, in
                                     int tiles_per_block, int rows_per_block)
 {
   SysremExtents X;
-  X.cells = (int64_t)nexp * npix; X.rows = (int64_t)nexp * nseg;
-  X.elem_blocks = (X.cells + elem_block - 1) / elem_block;
+  const FillExtents F = fill_extents(npix, nexp, elem_block);
+  X.cells = F.cells; X.elem_blocks = F.elem_blocks; X.r_bytes = F.r_bytes; X.c_bytes = F.c_bytes;
+  X.rows = (int64_t)nexp * nseg;
   X.tile_blocks = (ntiles + tiles_per_block - 1) / tiles_per_block;
   X.row_blocks = (X.rows + rows_per_block - 1) / rows_per_block;
   X.launches = (int64_t)ncomp * (2 * (int64_t)niter + 2);
-  X.r_bytes = sizeof(double) * (size_t)X.cells;
   X.a_bytes = sizeof(double) * (size_t)X.rows;
-  X.c_bytes = sizeof(double) * (size_t)npix;
   X.coef_bytes = sizeof(double) * (size_t)ncomp * (size_t)npix;
   X.basis_bytes = sizeof(double) * (size_t)X.rows * (size_t)ncomp;
   return X;
@@ -168,6 +182,31 @@ TRX_HD double sysrem_subtract(double r, double av, double c)
 #endif
   const double m = av * c;
   return r - m;
+}
+
+// ---- one column -------------------------------------------------------------------------------------
+// The column step of one column: r its residuals (entry v at r[v * stride]), w its weights the same way (read only where
+// hasw: the set has weights -- one answer for the whole launch, never a test of a lane's own pointer; without: every w is 1),
+// a its segment's time vector [nexp] (null: every a_v = 1, a component's first step).  v ascends, exposure_trips' way,
+// kSysTrips at a time.
+TRX_HD double sysrem_column_step(const double *r, const double *w, bool hasw, const double *a, int64_t stride, int nexp)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double num = 0.0, den = 0.0;
+  exposure_trips<kSysTrips>(
+      nexp, [&](int v) { return WeightedEntry{r[(int64_t)v * stride], hasw ? w[(int64_t)v * stride] : 1.0}; },
+      [&](int v, const WeightedEntry &x) { sysrem_col_term(x.w, x.f, a ? a[v] : 1.0, num, den); });
+  return sysrem_ratio(num, den);
+}
+
+// The subtract of one column, in place: r[v] = r[v] - U_v * c with U_v at U[v * ustride] (its segment's component), every v
+TRX_HD void sysrem_column_subtract(double *r, const double *U, int64_t ustride, double c, int64_t stride, int nexp)
+{
+  exposure_trips<kSysTrips>(
+      nexp, [&](int v) { return r[(int64_t)v * stride]; },
+      [&](int v, double f) { r[(int64_t)v * stride] = sysrem_subtract(f, U[(int64_t)v * ustride], c); });
 }
 
 // wave_sum's butterfly over 64 lane sums on the host: every lane adds its partner lane ^ 32, 16, 8, 4, 2, 1 in that order;

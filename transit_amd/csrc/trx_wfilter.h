@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "transit_hip.h"
+#include "trx_columns.h"
 #include "trx_numerics.h"
 #include "trx_products.h"
 
@@ -125,6 +126,32 @@ TRX_HD bool wfilter_factor_row(int j, const double (&Nrow)[NC], double *fac, int
     if (k < j) d = d - T[k] * Lr[k];
   fac[(int64_t)wfilter_at(j, j) * stride] = d;
   return d > TRX_WFILTER_PIVOT * njj;
+}
+
+// The factor of one column of n components: U its segment's padded vectors [nexp][NC], w the column's weights (entry v at
+// w[v * stride], read only where hasw: the set has weights -- one answer for the whole launch, never a test of a lane's own
+// pointer; without: every w is 1), fac its factor out (entry e at fac[e * stride]).  For row j = 0 .. n-1 one pass over the
+// exposures, in exposure_trips' trips of kFiltTrips, adds row j of the normal matrix; then row j of the factor is made from it
+// and from the rows below j.  Returns whether no pivot was singular.
+template <int NC>
+TRX_HD bool wfilter_factor_column(const double *U, const double *w, bool hasw, double *fac, int64_t stride, int nexp, int n)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  bool good = true;
+  for (int j = 0; j < n; j++) {
+    double Nrow[NC];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int k = 0; k < NC; k++) Nrow[k] = 0.0;
+    exposure_trips<kFiltTrips>(
+        nexp, [&](int v) { return hasw ? w[(int64_t)v * stride] : 1.0; },
+        [&](int v, double wv) { wfilter_normal_term<NC>(U + (int64_t)v * NC, wv, j, Nrow); });
+    good = wfilter_factor_row<NC>(j, Nrow, fac, stride) && good;
+  }
+  return good;
 }
 
 // The coefficients c from y (in place) by the column's factor of n components:
