@@ -49,3 +49,23 @@ def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
         sk.bind(("127.0.0.1", 0))
         return sk.getsockname()[1]
+
+
+SAVEFILES = (("tau.dat", "wavenumber"), ("CIA.dat", "wavenumber"), ("mol_extion.dat", "radius"),
+             ("total_extion.dat", "wavenumber"), ("cloud_extion.dat", "wavenumber"), ("scatt_extion.dat", "wavenumber"))
+
+
+def check_savefiles(got_dir, case, tol):
+    """The six dumps of `savefiles yes` against the reference's own: same text skeleton (header,
+    row keys, line count), same zeros (layers the reference's lazy sweep never reached; heights
+    past the toomuch cut), values to `tol`."""
+    for name, key in SAVEFILES:
+        ref_path = os.path.join(GOLDEN, case, name)
+        got_lines, ref_lines = open(os.path.join(got_dir, name)).read().split("\n"), open(ref_path).read().split("\n")
+        assert got_lines[:4] == ref_lines[:4], (name, got_lines[:4], ref_lines[:4])
+        assert len(got_lines) == len(ref_lines), (name, len(got_lines), len(ref_lines))
+        gk, gv = ol.read_rows_dump(os.path.join(got_dir, name), key)
+        rk, rv = ol.read_rows_dump(ref_path, key)
+        assert np.array_equal(gk, rk), (name, "row keys", gk.shape, rk.shape)
+        assert np.array_equal(gv == 0, rv == 0), (name, "zeros differ at", np.argwhere((gv == 0) != (rv == 0))[:4].tolist())
+        assert rel_err(gv, rv) < tol, (name, rel_err(gv, rv), tol)

@@ -9,7 +9,6 @@ composition the mirror is held against.
 import numpy as np
 
 import scatter_cases as cs
-import sysrem_cases as sc
 from transit_amd import xcor
 
 TILE = 512                                             # kHpTile
@@ -18,7 +17,6 @@ BORDER = 64 + TILE
 HALVES = (0, 1, 5, 70, 450)
 NEAR = 5                                               # a masked entry this close to BORDER on either side, in every weighted set
 STAGES = ("raw", "detrended")
-same_bits = sc.same_bits
 
 
 def tables(half, seed=0):

@@ -1,5 +1,5 @@
 """The sets the tests of the exposure, order and pixel axes share (test_many_cases_host.py, test_gpu_many_exposures.py,
-test_gpu_long_orders.py): observed sets of 64, 65 and 130 exposures over the 800 pixels of test_gpu_moments -- a wave of
+test_gpu_long_orders.py): observed sets of 64, 65 and 130 exposures over the 800 pixels of xcor_checks -- a wave of
 exposures, a wave plus one, two waves and a ragged third; 64 is a multiple of the filter kernels' 4 and of SYSREM's 8
 exposures per trip, 65 one past both --, sets of 5 exposures over 64, 65 and 130 short segments, and long_set: 12 exposures
 over orders of a detector's length, 1024, 1025 and 2049 pixels, with what it plants (see there).  Seeded numpy only; the pixel
@@ -21,7 +21,7 @@ from transit_amd.exposures import Exposures
 
 NEXPS = (64, 65, 130)
 NSEGS = (64, 65, 130)
-LENGTHS = [1, 63, 64, 65, 200, 0, 7, 400]        # test_gpu_moments' segments
+LENGTHS = [1, 63, 64, 65, 200, 0, 7, 400]        # xcor_checks' segments
 OFF_GRID = {250: 2400.0, 700: 2700.0}            # and its two off-grid pixels: pixel -> centre (cm-1)
 PATTERN = [3, 1, 0, 5, 2, 64, 1]                 # the many-orders sets' lengths, cycled
 ORDERS_NEXP = 5
@@ -140,7 +140,7 @@ _SETS = {}
 
 
 def exposures_set(nexp: int) -> ManySet:
-    """nexp exposures of test_gpu_moments' 800 pixels; the column 300 (of the 200-pixel segment) is masked at every exposure,
+    """nexp exposures of xcor_checks.pixel_set's 800 pixels; the column 300 (of the 200-pixel segment) is masked at every exposure,
     and one exposure over the whole 65-pixel segment: exposure 64 of 65, 127 of 130 -- on a wave's second and on its last
     trip over the exposures -- and, where no exposure has an index of 64 or more, 61 of 64"""
     if ("exp", nexp) not in _SETS:
@@ -303,7 +303,3 @@ def long_set(weighted: bool = True):
         _SETS["long", weighted] = (ms, Planted(ties, noisy, near, weighted))
     return _SETS["long", weighted]
 
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)])

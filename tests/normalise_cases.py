@@ -62,7 +62,3 @@ def the_set(nexp: int, weighted: bool):
         w[nexp - 1, SEG[MASKED_SEG]:SEG[MASKED_SEG + 1]] = 0.0
     return d, w
 
-
-def same_bits(a, b) -> bool:
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)]) and np.array_equal(np.isnan(a), np.isnan(b))

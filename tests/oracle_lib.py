@@ -83,3 +83,16 @@ def read_rows_dump(path, key):
         else:
             i += 1
     return np.array(heads), np.vstack(rows)
+
+
+def read_grid(path):
+    """(molecule ids, temperatures, pressures, wavenumbers, opacities [layer][temp][mol][wn]) of an opacity-grid file
+    (opacity.c:405-421)"""
+    with open(path, "rb") as f:
+        nmol, ntemp, nlayer, nwave = np.fromfile(f, dtype=np.int64, count=4)
+        ids = np.fromfile(f, dtype=np.int32, count=nmol)
+        temp = np.fromfile(f, dtype=np.float64, count=ntemp)
+        press = np.fromfile(f, dtype=np.float64, count=nlayer)
+        wns = np.fromfile(f, dtype=np.float64, count=nwave)
+        o = np.fromfile(f, dtype=np.float64).reshape(nlayer, ntemp, nmol, nwave)
+    return ids, temp, press, wns, o

@@ -4,10 +4,8 @@ that reads segment 0's everywhere --, planted singular columns, and a set whose 
 powers plus noise, for the end-to-end chain.  The data and the weights are sysrem_cases' and many_cases'."""
 import numpy as np
 
-import sysrem_cases as sc
 from transit_amd import xcor
 
-same_bits = sc.same_bits
 NVECS = [1, 3, 4, 5, 8, 9, 16]                    # below, at and above the kernels' padded counts 4, 8 and 16
 NEXP_16 = 17                                     # the exposures the sets of 16 vectors have: columns stay non-singular
 

@@ -20,7 +20,6 @@ CONSTANT_COL = 10
 NOISY_COLS = (437, 500, 611, 700, 790)
 TIE_SEGS = (3, 4)                                # the 65-pixel and the 200-pixel segment
 NOISE = 0.01
-same_bits = sc.same_bits
 
 KINDS = (xcor.SCATTER_VARIANCE, xcor.SCATTER_MASK)
 CLIPS = (0.0, 3.0)

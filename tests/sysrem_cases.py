@@ -33,7 +33,3 @@ def edge_weights(nexp: int, seed: int) -> np.ndarray:
     w[MASKED_EXP, SEG[MASKED_SEG]:SEG[MASKED_SEG + 1]] = 0.0
     return w
 
-
-def same_bits(a, b) -> bool:
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)]) and np.array_equal(np.isnan(a), np.isnan(b))

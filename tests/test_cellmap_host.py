@@ -11,6 +11,7 @@ import pytest
 
 from host_check import build_check
 
+import xcor_checks as xc
 from transit_amd import _abi, xcor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -96,20 +97,8 @@ def test_nearest_lags_of_a_map_marks_the_offending_exposures_only():
     assert xcor.nearest_lags(off).tolist() == [[[-1, -1]]]
 
 
-def hand_case():
-    """2 lags, 2 exposures, 2 segments of 2 pixels; lag 1's pixel 1 has no window on the grid.  The filter of segment 0 takes
-    the mean over the two exposures out (fwd = (1/2, 1/2), back = (1, 1)); that of segment 1 takes exposure 0's value
-    out of exposure 1 (fwd = (1, 0), back = (0, 1))."""
-    g = np.array([[1.0, 2.0, 3.0, 4.0], [2.0, 9.0, 1.0, 5.0]])
-    b = np.array([[1.0, 1.0, 1.0, 1.0], [1.0, 0.0, 1.0, 1.0]])
-    pairs = np.stack([g * b, b], axis=-1)
-    obs = xcor.Observed([0, 2, 4], [[1.0, 0.0, 2.0, 4.0], [0.0, 2.0, 1.0, 3.0]])
-    filt = xcor.Filter([[[0.5, 0.5]], [[1.0, 0.0]]], [[[1.0], [1.0]], [[0.0], [1.0]]])
-    return pairs, obs, filt
-
-
 def test_filtered_map_reference_by_hand():
-    pairs, obs, filt = hand_case()
+    pairs, obs, filt = xc.hand_case()
     vm = xcor.VelocityMap([-1.0, 1.0], [1.0, 0.0], [0.0, 1.5], [1.0, -1.0], stat="chi2", a=1.0, b=0.0)
     m = xcor.filtered_map_reference(pairs, obs, filt, vm)
     # cell (Kp 1, Vsys 0): M = (lag 1, lag 0) = ((2, dead, 1, 5), (1, 2, 3, 4)); column 1 is dead in THIS cell.

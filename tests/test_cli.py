@@ -116,7 +116,7 @@ def test_cli_detail_and_sampling_files_match_the_reference(tmp_path, case):
     ref = lambda f: os.path.join(GOLDEN, case, f)
     assert open(work / "sample.dat").read() == open(ref("sample.dat")).read()
     assert rel_err(ol.read_spectrum(work / "spectrum.dat")[:, 1], ol.read_spectrum(ref("spectrum.dat"))[:, 1]) < 2e-8
-    from test_options import check_savefiles
+    from cases import check_savefiles
     check_savefiles(str(work), case, 1e-8)                               # all six `savefiles` dumps
     for f in ("detail_tau.dat", "detail_ext.dat", "detail_cia.dat"):
         got, want = open(work / f).read().split("\n"), open(ref(f)).read().split("\n")

@@ -11,7 +11,7 @@ import pytest
 
 from host_check import build_check
 
-from test_cellmap_host import hand_case
+import xcor_checks as xc
 from transit_amd import _abi, xcor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,7 +118,7 @@ def exposed(pairs, scale):
 
 
 def test_exposed_map_reference_by_hand():
-    pairs, obs, filt = hand_case()
+    pairs, obs, filt = xc.hand_case()
     vm = xcor.VelocityMap([-1.0, 1.0], [1.0, 0.0], [0.0, 1.5], [1.0, -1.0], stat="chi2", a=1.0, b=0.0)
     m = xcor.exposed_map_reference(exposed(pairs, (1.0, 0.0)), obs, filt, vm)
     # the model is 0 at exposure 1, live where it was.

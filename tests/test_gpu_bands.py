@@ -12,62 +12,20 @@ import shutil
 import numpy as np
 import pytest
 
+import pixel_cases as pc
 from cases import GOLDEN
-from test_gpu_batch import atmospheres
-from transit_amd import _abi, bands, synth
+from transit_amd import _abi, bands
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
 
 pytestmark = pytest.mark.gpu
 
 
-def grid(P):
-    st = P.static
-    n = int(st.nwn)
-    return float(st.wn_i), float(st.wn_d), n, st.wn_i + np.arange(n) * st.wn_d
-
-
-def band_set(P, seed=0):
-    """top-hats tiling the grid, overlapping filter curves, Gaussians at R = 300 and 3000 (one with its edges on
-    grid points), a one-bin band, a whole-grid band, a band near the grid's start and a Gaussian off the grid"""
-    wn_i, wn_d, n, wn = grid(P)
-    rng = np.random.default_rng(seed)
-    lo, hi = wn[0] - wn_d / 2, wn[-1] + wn_d / 2
-    edges = np.linspace(lo, hi, 17)
-    out = [bands.tophat(wn, edges[k], edges[k + 1]) for k in range(16)]
-    for a, b in ((0.15, 0.55), (0.4, 0.8), (0.3, 0.95)):
-        fw = np.sort(rng.uniform(wn[0] + a * (wn[-1] - wn[0]), wn[0] + b * (wn[-1] - wn[0]), 29))
-        ft = np.sin(np.linspace(0.1, 3.0, fw.size)) ** 2 + 0.05
-        out.append(bands.filter_curve(wn, fw, ft))
-    span = wn[-1] - wn[0]
-    out += bands.resolving_power(wn[0] + span * np.linspace(0.03, 0.97, 9) + 0.37 * wn_d, 300.0)
-    out += bands.resolving_power(wn[0] + span * np.linspace(0.01, 0.99, 23) + 0.11 * wn_d, 3000.0)
-    sig = 2.0 * wn_d                                   # 4 sigmas = 8 bins exactly: both edges on grid points
-    out.append(bands.gauss(wn[n // 3], sig * bands.FWHM_PER_SIGMA, 4.0))
-    out.append(bands.weights(n // 2, [0.7]))           # one bin
-    out.append(bands.weights(0, 1.0 + 0.25 * np.sin(np.arange(n))))     # the whole grid
-    out.append(bands.weights(2, [1.0, 2.0, 3.0]))      # outside every shard but the first
-    out.append(bands.gauss(wn[0] - 50 * span, 1.0))    # no bin at all
-    return out
-
-
-def band_bins(P, b):
-    """(global bins, weights) of a band by the header's rule"""
-    wn_i, wn_d, n, wn = grid(P)
-    if b.kind == _abi.BAND_WEIGHTS:
-        return np.arange(b.first, b.first + b.weights.size), np.asarray(b.weights)
-    a, z = bands.gauss_range(wn_i, wn_d, n, b.centre, b.fwhm, b.cut)
-    i = np.arange(a, z)
-    sigma = b.fwhm / bands.FWHM_PER_SIGMA
-    x = ((wn_i + i * wn_d) - b.centre) / sigma
-    return i, np.exp(-0.5 * (x * x))
-
-
 def reference(P, bs, spec, lo=0):
     """math.fsum of the band sums over the spectrum of shard [lo, lo + len(spec))"""
     ref = np.zeros((len(bs), 2))
     for k, b in enumerate(bs):
-        i, w = band_bins(P, b)
+        i, w = pc.band_bins(P, b)
         m = (i >= lo) & (i < lo + spec.size)
         ref[k, 0] = math.fsum(w[m] * spec[i[m] - lo])
         ref[k, 1] = math.fsum(w[m])
@@ -86,32 +44,13 @@ def check_accuracy(P, bs, sums, spec, lo=0):
                 assert abs(g - r) <= tol * abs(r), (k, c, g, r, abs(g - r) / abs(r))
 
 
-def make(tmp_path, solution, **kw):
-    d = str(tmp_path / solution)
-    args = dict(nlines=100_000, wnlow=2500, wnhigh=2900, wndelt=1.0, wnosamp=2160, nlayers=100, solution=solution,
-                toomuch=10.0, ethresh=1e-50, seed=41, ncia=2 if solution == "transit" else 1)
-    args.update(kw)
-    synth.make_case(d, **args)
-    return Problem.from_cfg(os.path.join(d, "case.cfg"))
-
-
-def thinner(P, f):
-    """the problem's atmosphere with densities times f (f < 1: the rays go deeper)"""
-    a = P.atm
-    dens = np.ascontiguousarray(P.layer_arrays()["density"] * f)
-    b = _abi.TrxAtm()
-    C.memmove(C.byref(b), C.byref(a), C.sizeof(_abi.TrxAtm))
-    b.density = dens.ctypes.data_as(_abi.c_double_p)
-    return b, dens
-
-
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_band_runs_keep_the_spectrum_and_sum_it(tmp_path, solution):
-    P = make(tmp_path, solution)
-    bs = band_set(P)
+    P = pc.make_band_case(tmp_path, solution)
+    bs = pc.band_set(P)
     plain, banded = Engine(P.static), Engine(P.static)
     banded.set_bands(bs)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     for atm in (P.atm, P.atm, deep, P.atm):        # fresh, hinted, resuming deeper, hinted again
         ref = plain.run(atm, P.opts)["spectrum"]
         sums, spec = banded.run_bands(atm, P.opts, spectrum=True)
@@ -133,10 +72,10 @@ def test_band_runs_keep_the_spectrum_and_sum_it(tmp_path, solution):
 
 
 def test_batch_band_sums_are_the_single_handle_sums(tmp_path):
-    P = make(tmp_path, "eclipse", nlines=120_000, seed=33)
-    bs = band_set(P, seed=3)
+    P = pc.make_band_case(tmp_path, "eclipse", nlines=120_000, seed=33)
+    bs = pc.band_set(P, seed=3)
     K = 11
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     one = Engine(P.static)
     one.set_bands(bs)
     ref = np.stack([one.run_bands(atms[j], P.opts) for j in range(K)])
@@ -153,8 +92,8 @@ def test_batch_band_sums_are_the_single_handle_sums(tmp_path):
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_shards_combined_in_rank_order(tmp_path, solution):
-    P = make(tmp_path, solution, nlines=60_000, nlayers=80)
-    bs = band_set(P, seed=5)
+    P = pc.make_band_case(tmp_path, solution, nlines=60_000, nlayers=80)
+    bs = pc.band_set(P, seed=5)
     n = P.nwn
     whole = Engine(P.static)
     whole.set_bands(bs)
@@ -172,7 +111,7 @@ def test_shards_combined_in_rank_order(tmp_path, solution):
             E.close()
             check_accuracy(P, bs, s, sp, lo=cuts[r])
             for k, b in enumerate(bs):
-                i, _ = band_bins(P, b)
+                i, _ = pc.band_bins(P, b)
                 if not np.any((i >= cuts[r]) & (i < cuts[r + 1])):
                     assert s[k, 0] == 0 and s[k, 1] == 0 and not np.signbit(s[k, 0]), (r, k)
             parts.append(s)
@@ -186,8 +125,8 @@ def test_shards_combined_in_rank_order(tmp_path, solution):
 
 def test_large_grid_many_gaussians(tmp_path):
     """above kEmisRowsAbove bins (k_emission_rows): 10^4 Gaussians at R = 3000, bands of many pieces"""
-    P = make(tmp_path, "eclipse", nlines=100_000, wnlow=2500, wnhigh=2800, wndelt=0.001, wnosamp=1, nlayers=60)
-    wn_i, wn_d, n, wn = grid(P)
+    P = pc.make_band_case(tmp_path, "eclipse", nlines=100_000, wnlow=2500, wnhigh=2800, wndelt=0.001, wnosamp=1, nlayers=60)
+    wn_i, wn_d, n, wn = pc.grid(P)
     assert n > 65536 and n >= 3 * 10 ** 5
     bs = bands.resolving_power(np.linspace(wn[0] + 1.0, wn[-1] - 1.0, 10_000), 3000.0)
     bs += [bands.weights(0, 1.0 + 0.25 * np.cos(np.arange(n) * 1e-3)), bands.tophat(wn, 2600.0, 2700.0),
@@ -211,7 +150,7 @@ def test_opacity_grid_handle(tmp_path):
     builder.build_opacity_grid(P)
     builder.close()
     assert P.static.ogrid
-    bs = band_set(P, seed=7)
+    bs = pc.band_set(P, seed=7)
     plain, banded = Engine(P.static), Engine(P.static)
     banded.set_bands(bs)
     for _ in range(2):
@@ -224,7 +163,7 @@ def test_opacity_grid_handle(tmp_path):
 
 
 def test_refusals_keep_the_previous_set(tmp_path):
-    P = make(tmp_path, "eclipse", nlines=20_000, wnhigh=2600, nlayers=60)
+    P = pc.make_band_case(tmp_path, "eclipse", nlines=20_000, wnhigh=2600, nlayers=60)
     n = P.nwn
     E = Engine(P.static)
     with pytest.raises(EngineError) as ei:             # no set installed

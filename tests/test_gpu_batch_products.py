@@ -15,11 +15,8 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_velocity_map as tv
-from test_gpu_bands import grid
-from test_gpu_batch import atmospheres
+import pixel_cases as pc
+import xcor_checks as xc
 from transit_amd import _abi, bands, broaden, pixels, synth, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
@@ -92,24 +89,24 @@ def ctx(tmp_path_factory):
     synth.make_case(d, nlines=20_000, wnlow=2500, wnhigh=2600, wndelt=1.0, wnosamp=2160, nlayers=60,
                     solution="eclipse", toomuch=10.0, ethresh=1e-50, seed=5)
     P = Problem.from_cfg(os.path.join(d, "case.cfg"))
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     c = SimpleNamespace(P=P, nwn=n, nl=int(P.atm.nlayer))
-    c.atms, c.keep = atmospheres(P, K)
+    c.atms, c.keep = pc.atmospheres(P, K)
     centres = np.linspace(2510.0, 2590.0, NPIX // 2) + 0.37 * wn_d
-    c.px = tp.joined(pixels.resolving_power(centres, 1500.0, 4.0), pixels.resolving_power(centres, 400.0, 4.0))
+    c.px = pc.joined(pixels.resolving_power(centres, 1500.0, 4.0), pixels.resolving_power(centres, 400.0, 4.0))
     c.bands = [bands.tophat(wn, 2520.0, 2540.0), bands.gauss(2555.3, 6.0, 4.0), bands.weights(7, [1.0, 2.0, 3.0])]
     c.bl = [broaden.Rotation.from_beta(beta, limb) for beta, limb in zip(BETAS, (0.6, 0.0, 1.0))]
     halves = [int(broaden.half_widths(wn_i, wn_d, n, b.beta)[-1]) for b in c.bl]
     assert halves == [1, 2, 5] and max(halves) < _abi.BROADEN_MAX_HALF
-    c.shifts = np.stack([np.roll(tp.SHIFTS, j)[:NEXP] * (1.0 + 1e-6 * j) for j in range(K)])
+    c.shifts = np.stack([np.roll(pc.SHIFTS, j)[:NEXP] * (1.0 + 1e-6 * j) for j in range(K)])
     lag_kms, lags = xcor.lag_grid(-6.0, 6.0, 3.0)
     c.lags = np.stack([lags * (1.0 + 1e-6 * j) for j in range(K)])
-    c.vm = tv.the_map("loglike_bl19", lag_kms=lag_kms, kp=[10.0, 20.0, 30.0], vsys=[-2.0, -1.0, 0.0, 1.0],
+    c.vm = xc.the_map("loglike_bl19", lag_kms=lag_kms, kp=[10.0, 20.0, 30.0], vsys=[-2.0, -1.0, 0.0, 1.0],
                       orbit=np.sin(2 * np.pi * np.array([-0.02, 0.0, 0.02])), offset=[0.1, -0.2, 0.3])
     assert len(c.px) == NPIX and len(c.bands) == NBANDS and c.lags.shape == (K, NLAG) and (c.vm.nkp, c.vm.nvsys) == (3, 4)
     c.E = Engine(P.static)
     scale = float(np.mean(c.E.run(P.atm, P.opts)["spectrum"]))
-    c.ob = tm.observed(NPIX, scale, lengths=LENGTHS, nexp=NEXP)
+    c.ob = xc.observed(NPIX, scale, lengths=LENGTHS, nexp=NEXP)
     c.F = xcor.svd_filter(c.ob.data, c.ob.seg_first, 2)
     install(c.E, c)
     c.ref = {}

@@ -1,7 +1,7 @@
 """Rotational broadening of the spectrum on the device (trx_set_broadening / trx_run_broadened and the batch forms,
 include/transit_hip.h) against transit_amd.broaden, the numpy statement of the same definition.
 
-The case is test_gpu_pixels' (40 000 lines, 2500-2560 cm-1 at 0.01, 6001 bins = 24 blocks of the kernel, the last one
+The case is pixel_cases.make's (40 000 lines, 2500-2560 cm-1 at 0.01, 6001 bins = 24 blocks of the kernel, the last one
 ragged; 60 layers; both geometries).  The betas and what each is there for:
 
     1.037e-4    h = 25 -> 26    the half-width changes inside the grid
@@ -23,19 +23,16 @@ import shutil
 import numpy as np
 import pytest
 
-import test_gpu_filter as tf
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
+import pixel_cases as pc
+import xcor_checks as xc
 from cases import GOLDEN
-from test_gpu_bands import band_set, grid, thinner
-from test_gpu_batch import atmospheres
 from transit_amd import _abi, broaden, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
+SHIFTS = pc.SHIFTS
 BETAS = {"h25-26": 1.037e-4, "h325-333": 1.3037e-3, "h0-1": 3.95e-6, "h0": 2e-6}
 HALVES = {"h25-26": (25, 26), "h325-333": (325, 333), "h0-1": (0, 1), "h0": (0, 0)}
 LIMBS = (0.0, 0.6, 1.0)
@@ -50,13 +47,13 @@ def case(tmp_path_factory):
     def get(solution, **kw):
         key = (solution,) + tuple(sorted(kw.items()))
         if key not in made:
-            made[key] = tp.make(tmp_path_factory.mktemp("broaden"), solution, **kw)
+            made[key] = pc.make(tmp_path_factory.mktemp("broaden"), solution, **kw)
         return made[key]
 
     def reference(P, spec, b):
         key = (spec.tobytes(), b.beta, b.limb)
         if key not in refs:
-            wn_i, wn_d, _, _ = grid(P)
+            wn_i, wn_d, _, _ = pc.grid(P)
             ref = broaden.reference(spec, wn_i, wn_d, b)
             refs[key] = (ref, broaden.bound(spec, wn_i, wn_d, b, ref=ref))
         return refs[key]
@@ -67,7 +64,7 @@ def case(tmp_path_factory):
 
 def margin(P, beta):
     """the smallest distance of a d_i / wn_d from an integer, and the half-widths"""
-    wn_i, wn_d, n, _ = grid(P)
+    wn_i, wn_d, n, _ = pc.grid(P)
     h, d = broaden._halves(wn_i, wn_d, n, beta)
     q = d / wn_d
     return float(np.min(np.abs(q - np.round(q)))), h
@@ -98,7 +95,7 @@ def test_broadened_runs_keep_the_spectrum_and_match_the_definition(case, solutio
     assert m >= 1e-9 and (h[0], h[-1]) == HALVES[name] and np.all(np.diff(h) >= 0), (m, h[0], h[-1])
     plain, E = Engine(P.static), Engine(P.static)
     E.set_broadening(b)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         ref = plain.run(atm, P.opts)["spectrum"]
         got, spec = E.run_broadened(atm, P.opts, spectrum=True)
@@ -112,20 +109,20 @@ def test_broadened_runs_keep_the_spectrum_and_match_the_definition(case, solutio
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_pixels_moments_and_filter_sample_the_broadened_spectrum(case, solution):
     P = case(solution)
-    wn_i, wn_d, n, _ = grid(P)
+    wn_i, wn_d, n, _ = pc.grid(P)
     b = broaden.Rotation.from_beta(BETAS["h25-26"], 0.6)
     assert margin(P, b.beta)[0] >= 1e-9
-    px = tp.joined(tp.set_a(P), tp.set_b(P))
-    tol = tp.tolerance(px, SHIFTS)
+    px = pc.joined(pc.set_a(P), pc.set_b(P))
+    tol = pc.tolerance(px, SHIFTS)
     E, U = Engine(P.static), Engine(P.static)
     E.set_pixels(px); U.set_pixels(px)
     E.set_broadening(b)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     for k, atm in enumerate((P.atm, deep)):
         B, spec = E.run_broadened(atm, P.opts, spectrum=True)
         pairs, spec2 = E.run_pixels(atm, P.opts, SHIFTS, spectrum=True)
         assert np.array_equal(spec2, spec)                # the plain spectrum, never the broadened one
-        tp.check_close(pairs, pixels.reference(B, wn_i, wn_d, n, px, SHIFTS), tol, "%s run %d pairs vs reference over B" % (solution, k))
+        pc.check_close(pairs, pixels.reference(B, wn_i, wn_d, n, px, SHIFTS), tol, "%s run %d pairs vs reference over B" % (solution, k))
         plain_pairs = U.run_pixels(atm, P.opts, SHIFTS)
         moved = float(np.max(np.abs(pixels.value(pairs) - pixels.value(plain_pairs)) / np.abs(pixels.value(plain_pairs))))
         print("%s run %d: broadening moves the pixel values by up to %.3e (tolerance %.3e)" % (solution, k, moved, tol))
@@ -133,15 +130,15 @@ def test_pixels_moments_and_filter_sample_the_broadened_spectrum(case, solution)
         assert np.array_equal(pairs[..., 1], plain_pairs[..., 1])      # the weights' sums know nothing of the spectrum
     # moments and filtered moments on the same handle: over those pairs, at those files' own bounds
     pairs = E.run_pixels(P.atm, P.opts, SHIFTS)
-    ob = tm.observed(len(px), float(np.mean(spec)))
+    ob = xc.observed(len(px), float(np.mean(spec)))
     E.set_observed(ob)
     mom = E.run_moments(P.atm, P.opts, SHIFTS)
-    tm.check_moments(mom, pairs, ob, "%s moments over broadened pairs" % solution)
+    xc.check_moments(mom, pairs, ob, "%s moments over broadened pairs" % solution)
     F = xcor.svd_filter(ob.data, ob.seg_first, 3)
     E.set_filter(F)
     fmom, val = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
-    tf.check_values(val, pairs, ob, F, "%s filtered values over broadened pairs" % solution)
-    tf.check_moments(fmom, val, ob, "%s filtered moments" % solution)
+    xc.check_values(val, pairs, ob, F, "%s filtered values over broadened pairs" % solution)
+    xc.check_filtered_moments(fmom, val, ob, "%s filtered moments" % solution)
     assert not np.isnan(val).any()
     U.set_observed(ob)
     assert not np.array_equal(U.run_moments(P.atm, P.opts, SHIFTS), mom)
@@ -152,8 +149,8 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
     P = case("eclipse")
     b = broaden.Rotation.from_beta(BETAS["h325-333"], 0.6)
     assert margin(P, b.beta)[0] >= 1e-9
-    px = tp.joined(tp.set_a(P), tp.set_b(P))
-    bs = band_set(P)
+    px = pc.joined(pc.set_a(P), pc.set_b(P))
+    bs = pc.band_set(P)
     E, U, fresh = Engine(P.static), Engine(P.static), Engine(P.static)
     for X in (E, U, fresh):
         X.set_pixels(px)
@@ -171,7 +168,7 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
     # the runs that stay as they are, whatever is installed
     plain = U.run_pixels(P.atm, P.opts, SHIFTS)
     assert not np.array_equal(want, plain)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     for atm in (P.atm, deep):
         assert np.array_equal(E.run(atm, P.opts)["spectrum"], U.run(atm, P.opts)["spectrum"])
         se, sp_e = E.run_bands(atm, P.opts, spectrum=True)
@@ -192,15 +189,15 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
 
 def test_batch_outputs_are_the_single_handle_outputs(case):
     P = case("eclipse", nlines=30_000, seed=33)
-    px = tp.joined(tp.set_a(P), tp.set_b(P))
+    px = pc.joined(pc.set_a(P), pc.set_b(P))
     K = 5
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     bl = [broaden.Rotation.from_beta(beta, limb) for beta, limb in
           ((1.037e-4, 0.6), (1.3037e-3, 0.0), (3.95e-6, 1.0), (2e-6, 0.3), (5.2037e-4, 0.85))]
     for b in bl:
         assert margin(P, b.beta)[0] >= 1e-9
     shifts = np.stack([np.roll(SHIFTS, j)[:5] * (1.0 + 1e-6 * j) for j in range(K)])
-    ob = tm.observed(len(px), 1.0, nexp=5)
+    ob = xc.observed(len(px), 1.0, nexp=5)
     F = xcor.svd_filter(ob.data, ob.seg_first, 2)
     one = Engine(P.static)
     one.set_pixels(px); one.set_observed(ob); one.set_filter(F)
@@ -262,7 +259,7 @@ def test_opacity_grid_handle(tmp_path, case):
     builder.build_opacity_grid(P)
     builder.close()
     assert P.static.ogrid
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     b = broaden.Rotation.from_beta(5.37 * wn_d / float(wn[-1]), 0.6)
     m, h = margin(P, b.beta)
     assert m >= 1e-9 and h[-1] == 5 and 2 * h[-1] < n < 256, (m, h[0], h[-1], n)      # one ragged block, clipped at both ends
@@ -279,7 +276,7 @@ def test_opacity_grid_handle(tmp_path, case):
 
 def test_refusals_and_lifetime(case):
     P = case("eclipse", nlines=10_000)
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     E = Engine(P.static)
     lib = E._lib
     with pytest.raises(EngineError) as ei:              # nothing installed

@@ -12,9 +12,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import pixel_cases as pc
 from cases import golden
-from test_gpu_bands import band_bins, band_set, grid, make, thinner
-from test_gpu_batch import atmospheres
 from transit_amd import _abi, bands, contrib
 from transit_amd.engine import Batch, Engine, EngineError
 
@@ -51,7 +50,7 @@ def ceiling_per_bin(P, atm, n, lo=0):
 
 def shard_bins(P, b, lo, n):
     """(local bins, weights) of band b inside shard [lo, lo + n)"""
-    i, w = band_bins(P, b)
+    i, w = pc.band_bins(P, b)
     m = (i >= lo) & (i < lo + n)
     return i[m] - lo, w[m]
 
@@ -83,15 +82,15 @@ def debug_run(E, atm, opts):
 
 
 def sequence(P):
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     return [("fresh", P.atm), ("hinted", P.atm), ("deeper", deep), ("hinted again", P.atm)], keep
 
 
 @pytest.mark.parametrize("solution", GEOMETRIES)
 def test_own_optical_depths_closure_and_untouched_run(tmp_path, solution):
     """tests 5, 6, 8 and 9 (a)-(c) of the issue on the band tests' problem and band set"""
-    P = make(tmp_path, solution)
-    bs = band_set(P)
+    P = pc.make_band_case(tmp_path, solution)
+    bs = pc.band_set(P)
     n, nl = P.nwn, P.nlayer
     dbg, plain, E = Engine(P.static), Engine(P.static), Engine(P.static)
     plain.set_bands(bs)
@@ -151,8 +150,8 @@ def test_own_optical_depths_closure_and_untouched_run(tmp_path, solution):
 @pytest.mark.parametrize("solution", GEOMETRIES)
 def test_one_order_of_summation_across_run_forms(tmp_path, solution):
     """test 9 (d), (e): the rows do not depend on the kernels that made the optical depths or on the step plan"""
-    P = make(tmp_path, solution)
-    bs = band_set(P)
+    P = pc.make_band_case(tmp_path, solution)
+    bs = pc.band_set(P)
     seq, keep = sequence(P)
 
     def rows(E):
@@ -190,10 +189,10 @@ def test_one_order_of_summation_across_run_forms(tmp_path, solution):
 @pytest.mark.parametrize("solution", GEOMETRIES)
 def test_batch_rows_are_the_single_handle_rows(tmp_path, solution):
     """test 9 (f)"""
-    P = make(tmp_path, solution, nlines=60_000, seed=33)
-    bs = band_set(P, seed=3)
+    P = pc.make_band_case(tmp_path, solution, nlines=60_000, seed=33)
+    bs = pc.band_set(P, seed=3)
     K = 8
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     one = Engine(P.static)
     one.set_bands(bs)
     pairs = [one.run_contrib(atms[j], P.opts) for j in range(K)]
@@ -235,8 +234,8 @@ def test_against_the_oracle_on_goldens(name):
 @pytest.mark.parametrize("solution", GEOMETRIES)
 def test_shards_combined_in_rank_order(tmp_path, solution):
     """test 10"""
-    P = make(tmp_path, solution, nlines=60_000, nlayers=80)
-    bs = band_set(P, seed=5)
+    P = pc.make_band_case(tmp_path, solution, nlines=60_000, nlayers=80)
+    bs = pc.band_set(P, seed=5)
     n = P.nwn
     dbg, whole = Engine(P.static), Engine(P.static)
     out = debug_run(dbg, P.atm, P.opts)
@@ -255,7 +254,7 @@ def test_shards_combined_in_rank_order(tmp_path, solution):
             cf = E.run_contrib(P.atm, P.opts)[1]
             E.close()
             for k, b in enumerate(bs):
-                i, _ = band_bins(P, b)
+                i, _ = pc.band_bins(P, b)
                 if not np.any((i >= cuts[r]) & (i < cuts[r + 1])):
                     assert np.all(cf[k] == 0) and not np.any(np.signbit(cf[k])), (r, k)
             parts.append(cf)
@@ -266,8 +265,8 @@ def test_shards_combined_in_rank_order(tmp_path, solution):
 
 def test_refusals_and_a_change_of_nlayer(tmp_path):
     """test 11"""
-    P = make(tmp_path / "a", "eclipse", nlines=20_000, wnhigh=2600, nlayers=60)
-    Q = make(tmp_path / "b", "eclipse", nlines=20_000, wnhigh=2600, nlayers=90)      # the same lines, another atmosphere
+    P = pc.make_band_case(tmp_path / "a", "eclipse", nlines=20_000, wnhigh=2600, nlayers=60)
+    Q = pc.make_band_case(tmp_path / "b", "eclipse", nlines=20_000, wnhigh=2600, nlayers=90)      # the same lines, another atmosphere
     n = P.nwn
     assert Q.nwn == n and Q.nlayer != P.nlayer
     E = Engine(P.static)
@@ -278,13 +277,13 @@ def test_refusals_and_a_change_of_nlayer(tmp_path):
     E.set_bands(bs)
     lib = E._lib
     sums, cf = np.zeros((3, 2)), np.zeros((3, P.nlayer))
-    ps, pc = sums.ctypes.data_as(_abi.c_double_p), cf.ctypes.data_as(_abi.c_double_p)
+    ps, pcf = sums.ctypes.data_as(_abi.c_double_p), cf.ctypes.data_as(_abi.c_double_p)
     lib.trx_last_error.argtypes, lib.trx_last_error.restype = [C.c_void_p], C.c_char_p
     assert lib.trx_run_contrib(E._h, C.byref(P.atm), C.byref(P.opts), None, ps, None, None) == -1
     assert b"contrib" in lib.trx_last_error(E._h)
-    assert lib.trx_run_contrib(E._h, C.byref(P.atm), C.byref(P.opts), None, None, pc, None) == -1
+    assert lib.trx_run_contrib(E._h, C.byref(P.atm), C.byref(P.opts), None, None, pcf, None) == -1
     assert b"sums" in lib.trx_last_error(E._h)
-    assert lib.trx_run_contrib(E._h, C.byref(P.atm), C.byref(P.opts), None, ps, pc, None) == 0      # still runs
+    assert lib.trx_run_contrib(E._h, C.byref(P.atm), C.byref(P.opts), None, ps, pcf, None) == 0      # still runs
     dbg = Engine(P.static)
     # atmospheres of different nlayer one after the other on the same handles: rows of the new length
     for what, X in (("60 layers", P), ("90 layers", Q), ("60 layers again", P)):
@@ -304,8 +303,8 @@ def test_refusals_and_a_change_of_nlayer(tmp_path):
 @pytest.mark.parametrize("solution", GEOMETRIES)
 def test_large_grid_many_pieces(tmp_path, solution):
     """test 12: more than 64 pieces per band, the k_emission_rows side of the spectrum kernels"""
-    P = make(tmp_path, solution, nlines=10_000, wnlow=2500, wnhigh=2800, wndelt=0.004, wnosamp=1, nlayers=60)
-    wn_i, wn_d, n, wn = grid(P)
+    P = pc.make_band_case(tmp_path, solution, nlines=10_000, wnlow=2500, wnhigh=2800, wndelt=0.004, wnosamp=1, nlayers=60)
+    wn_i, wn_d, n, wn = pc.grid(P)
     nl = P.nlayer
     assert n >= 70_000 and n > 64 * 1024
     bs = [bands.weights(0, 1.0 + 0.25 * np.cos(np.arange(n) * 1e-3))]

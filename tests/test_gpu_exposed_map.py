@@ -1,10 +1,10 @@
 """The detrended Kp-Vsys map under the exposure table, on the device (trx_run_exposed_map / trx_run_batch_exposed_map,
 include/transit_hip.h).
 
-The case is test_gpu_filtered_map's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels, 7 exposures, the segments
+The case is xcor_checks': pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels, 7 exposures, the segments
 [1, 63, 64, 65, 200, 0, 7, 400], the 55 lags -81 .. 81 km/s, the 7 x 5 map with its seven outside cells, the 13 x 11 map of
 three chunks with a ragged last one, the filter xcor.svd_filter(ob.data, ob.seg_first, 3) and the pixel (PIXEL) at the grid's
-upper edge whose column is live in some cells only.  On top of it the table of test_gpu_exposures: scales with 1, 0 and a
+upper edge whose column is live in some cells only.  On top of it the table xcor_checks.SCALE and SMEAR: scales with 1, 0 and a
 negative value, smears that mix exact 0 with half-widths up to 1.3e-5 (7.8 km/s across the exposure).
 
 THE CONTRACT (test 1): a cell's value is xcor.cell_value of the moments run_filtered_moments returns on the same handle,
@@ -12,37 +12,31 @@ table installed, at the shifts LAGS[lag_index[cell]], within xcor.cell_bound -- 
 practice (printed).
 
 AGAINST NUMPY ALONE (test 3): the map against xcor.exposed_map_reference of pairs_lv, run_exposed's pairs at a constant shift
-per lag.  The tolerance is the one derived in test_gpu_filtered_map's docstring, applied to each cell's own rows
+per lag.  The tolerance is the one derived in xcor_checks.row_bounds' docstring, applied to each cell's own rows
 pairs_lv[lag_index[cell][v]][v]; nothing in it is measured, and the relative changes it rests on are asserted below 1e-3."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import test_gpu_exposures as te
-import test_gpu_filtered_map as tfm
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
+import pixel_cases as pc
 import wfilter_cases as wc
-from test_gpu_bands import thinner
-from test_gpu_batch import atmospheres
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, bands, broaden, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.exposures import Exposures
 
 pytestmark = pytest.mark.gpu
 
-STATS = tv.STATS
-LAG_KMS, LAGS = tfm.LAG_KMS, tfm.LAGS
-OUTSIDE = tfm.OUTSIDE
-KP2, VSYS2 = tfm.KP2, tfm.VSYS2
-CHUNK = tfm.CHUNK
-PIXEL, LIVE_UP_TO = tfm.PIXEL, tfm.LIVE_UP_TO
-EPS = 2.0 ** -52
-SCALE, SMEAR = te.SCALE, te.SMEAR
-the_map = tfm.the_map
+STATS = xc.STATS
+LAG_KMS, LAGS = xc.LAG_KMS, xc.LAGS
+OUTSIDE = xc.OUTSIDE
+KP2, VSYS2 = xc.FMAP_KP2, xc.FMAP_VSYS2
+CHUNK = xc.CHUNK
+PIXEL, LIVE_UP_TO = xc.PIXEL, xc.LIVE_UP_TO
+SCALE, SMEAR = xc.SCALE, xc.SMEAR
+the_map = xc.the_filtered_map
 
 
 def table():
@@ -50,17 +44,12 @@ def table():
 
 
 def handle(case, filt=True, ex=True):
-    E = tt.handle(case.P, case.px, case.ob)
+    E = xc.handle(case.P, case.px, case.ob)
     if filt:
         E.set_filter(case.F)
     if ex is not None and ex is not False:
         E.set_exposures(table() if ex is True else ex)
     return E
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)])
 
 
 class Case:
@@ -85,16 +74,16 @@ class Case:
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("expmap"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    # (test_gpu_filtered_map's pixel: its window leaves the grid between the lags of +30 and +33 km/s)
+    P = pc.make(tmp_path_factory.mktemp("expmap"), "eclipse", nlines=20_000)
+    px = xc.pixel_set(P)
+    # (xcor_checks.PIXEL: its window leaves the grid between the lags of +30 and +33 km/s)
     wn_i, wn_d, n = float(P.static.wn_i), float(P.static.wn_d), int(P.static.nwn)
     half = px.cut * px.fwhm[PIXEL] / bands.FWHM_PER_SIGMA
     px.centre[PIXEL] = (wn_i + (n - 0.5) * wn_d) * pixels.shift(LIVE_UP_TO + 1.5) + half
     plain = Engine(P.static)
     scale = float(np.mean(plain.run(P.atm, P.opts)["spectrum"]))
     plain.close()
-    ob = tm.observed(len(px), scale)
+    ob = xc.observed(len(px), scale)
     assert ob.seg_first[2] <= PIXEL < ob.seg_first[3] and (ob.nexp, ob.nseg) == (7, 8)
     assert SCALE.size == SMEAR.size == 7 and 0.0 in SCALE and 1.0 in SCALE and SCALE.min() < 0 and 0.0 in SMEAR and SMEAR.max() > 1e-5
     c = Case(P, px, ob, xcor.svd_filter(ob.data, ob.seg_first, 3))
@@ -137,7 +126,7 @@ def test_a_cell_is_the_filtered_moments_under_the_table(case, stat):
             # the table matters: no inside cell has the filtered map's value
             plain = E.run_filtered_map(case.P.atm, case.P.opts, vm)
             assert np.array_equal(np.isnan(plain), outside) and np.all(plain[~outside] != m[~outside])
-            differ = tfm.check_contract(case, E, vm, m, idx, key="table", what="%d cells, R = %d%s" % (m.size, R, ", offset" if offset else ""))
+            differ = xc.check_contract(case, E, vm, m, idx, key="table", what="%d cells, R = %d%s" % (m.size, R, ", offset" if offset else ""))
             if stat != "loglike_bl19":                             # (the expectation, printed; the assertion is the bound)
                 print("%s: the map has the bits of the host's points 5: %s" % (stat, differ == 0))
     E.close()
@@ -158,22 +147,6 @@ def test_a_table_that_changes_nothing_gives_the_filtered_map(case):
     E.close()
 
 
-def moment_differences(case, pr):
-    """test_gpu_filtered_map.moment_differences for a cell's own rows pr [nexp, npix, 2]"""
-    ob, F = case.ob, case.F
-    val, A = xcor.filter_reference(pr, ob, F), xcor.filter_abs_reference(pr, ob, F)
-    mom, S = xcor.reference_values(val, ob), xcor.abs_reference_values(val, ob)
-    tA = (ob.nexp + F.ncomp + 8) * EPS * A
-    lin = xcor.abs_reference_values(tA, ob)
-    cross = xcor.abs_reference_values(np.sqrt(np.abs(val) * tA), ob)
-    D = (int(np.max(np.diff(ob.seg_first))) + 16) * EPS * S
-    D[..., 0] = 0.0
-    D[..., 2] += lin[..., 2]
-    D[..., 3] += 2.0 * cross[..., 3] + lin[..., 3]
-    D[..., 5] += lin[..., 5]
-    return mom, D
-
-
 @pytest.mark.parametrize("stat", STATS)
 def test_the_map_is_the_definition_in_numpy(case, stat):
     E = handle(case)
@@ -184,9 +157,9 @@ def test_the_map_is_the_definition_in_numpy(case, stat):
     assert np.array_equal(np.isnan(m), OUTSIDE) and np.array_equal(np.isnan(ref), OUTSIDE)
     worst, ve = 0.0, np.arange(7)
     for i, j in np.argwhere(~OUTSIDE):
-        mom, D = moment_differences(case, case.pairs_lv[idx[i, j], ve])
+        mom, D = xc.moment_differences(case, case.pairs_lv[idx[i, j], ve])
         assert xcor.cell_value(mom, vm) == ref[i, j]
-        rows, small = tfm.row_bounds(mom, D, vm)
+        rows, small = xc.row_bounds(mom, D, vm)
         print("%s cell (%d, %d): largest relative change %.3e" % (stat, i, j, small))
         assert small < 1e-3, (stat, i, j, small)
         tol = 2.0 * float(np.sum(rows)) + xcor.cell_bound(mom, vm)
@@ -201,19 +174,19 @@ def test_cells_do_not_depend_on_the_rest_of_the_call_or_on_the_handles_history(c
     plain = Engine(P.static)
     spec_ref = plain.run(P.atm, P.opts)["spectrum"]
     plain.close()
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     for stat in STATS:
         vm = the_map(stat, offset=True)
         m, idx, R = run(E, case, vm)
         # one cell alone: spans of one lag, R = 7, its rows numbered 0 .. 6
         for i, j in ((2, 3), (5, 2), (0, 0)):
-            one, _, r1 = run(E, case, the_map(stat, offset=True, kp=tv.KP[i:i + 1], vsys=tv.VSYS[j:j + 1]))
+            one, _, r1 = run(E, case, the_map(stat, offset=True, kp=xc.KP[i:i + 1], vsys=xc.VSYS[j:j + 1]))
             assert r1 == 7 and one.shape == (1, 1) and same_bits(one[0, 0], m[i, j]), (stat, i, j)
         # a sub-map: other spans, other bases
-        sub, _, rs = run(E, case, the_map(stat, offset=True, kp=tv.KP[1:4], vsys=tv.VSYS[2:]))
+        sub, _, rs = run(E, case, the_map(stat, offset=True, kp=xc.KP[1:4], vsys=xc.VSYS[2:]))
         assert 7 < rs < R and same_bits(sub, m[1:4, 2:]), stat
         # the axes reversed: the same spans, every cell at another place of its chunk -- and, in the 143-cell map, in another chunk
-        rev, _, rr = run(E, case, the_map(stat, offset=True, kp=tv.KP[::-1], vsys=tv.VSYS[::-1]))
+        rev, _, rr = run(E, case, the_map(stat, offset=True, kp=xc.KP[::-1], vsys=xc.VSYS[::-1]))
         assert rr == R and same_bits(rev[::-1, ::-1], m), stat
         vm2 = the_map(stat, second=True)
         m2, _, R2 = run(E, case, vm2)
@@ -252,22 +225,22 @@ def test_with_a_weighted_filter_a_highpass_and_a_broadening_installed(case):
         W.set_exposures(table())
         for v in (vm, vm2):
             m, idx, R = run(W, case, v)
-            tfm.check_contract(case, W, v, m, idx, key="weighted %d" % ncomp, what="weighted filter, %d components" % ncomp)
+            xc.check_contract(case, W, v, m, idx, key="weighted %d" % ncomp, what="weighted filter, %d components" % ncomp)
         W.close()
     E.set_highpass(xcor.gaussian_highpass(6.0))
     for v in (vm, vm2):
         m, idx, R = run(E, case, v)
-        tfm.check_contract(case, E, v, m, idx, key="highpass", what="high-pass")
+        xc.check_contract(case, E, v, m, idx, key="highpass", what="high-pass")
     assert np.all(run(E, case, vm)[0][~OUTSIDE] != plain[~OUTSIDE])
     E.set_highpass(None)
     E.set_broadening(broaden.Rotation(4.0, 0.4))
     for v in (vm, vm2):
         m, idx, R = run(E, case, v)
-        tfm.check_contract(case, E, v, m, idx, key="broadening", what="broadening")
+        xc.check_contract(case, E, v, m, idx, key="broadening", what="broadening")
     assert np.all(run(E, case, vm)[0][~OUTSIDE] != plain[~OUTSIDE])
     E.set_highpass(xcor.gaussian_highpass(6.0))
     m, idx, R = run(E, case, vm)
-    tfm.check_contract(case, E, vm, m, idx, key="highpass and broadening", what="high-pass and broadening")
+    xc.check_contract(case, E, vm, m, idx, key="highpass and broadening", what="high-pass and broadening")
     E.set_highpass(None)
     E.set_broadening(None)
     assert same_bits(run(E, case, vm)[0], plain)
@@ -282,7 +255,7 @@ def test_nothing_else_moves(case):
     def neighbours(E, table_runs):
         out = [E.run_filtered_map(P.atm, P.opts, vm), E.run_trail(P.atm, P.opts, LAGS)] + list(E.run_velocity_map(P.atm, P.opts, vm, per=True))
         if table_runs:
-            out += list(E.run_filtered_moments(P.atm, P.opts, LAGS[cell], values=True)) + [E.run_exposed(P.atm, P.opts, tp.SHIFTS), E.run_moments(P.atm, P.opts, tp.SHIFTS)]
+            out += list(E.run_filtered_moments(P.atm, P.opts, LAGS[cell], values=True)) + [E.run_exposed(P.atm, P.opts, pc.SHIFTS), E.run_moments(P.atm, P.opts, pc.SHIFTS)]
         return out
 
     def same(a, b):
@@ -316,7 +289,7 @@ def test_a_map_with_every_cell_outside(case):
     plain.close()
     vm = the_map("ccf", offset=True)
     before = E.run_exposed_map(P.atm, P.opts, vm)
-    far = the_map("ccf", offset=True, vsys=tv.VSYS + 200.0)
+    far = the_map("ccf", offset=True, vsys=xc.VSYS + 200.0)
     m, idx, R, spec = E.run_exposed_map(P.atm, P.opts, far, lag_index=True, nrows=True, spectrum=True)
     assert R == 0 == xcor.exposed_map_rows(far)[3] and np.all(np.isnan(m)) and np.array_equal(spec, spec_ref)
     assert np.array_equal(idx, xcor.nearest_lags(far)) and np.all(np.any(idx < 0, axis=-1))
@@ -345,7 +318,7 @@ def test_refusals(case):
     assert "trx_run_exposed_map: no filter installed (trx_set_filter)" in refusal(E)
     E.set_exposures(table())
     assert "trx_run_exposed_map: no filter installed (trx_set_filter)" in refusal(E)              # no filter, a table
-    assert E.run_exposed(P.atm, P.opts, tp.SHIFTS).shape == (7, 800, 2)
+    assert E.run_exposed(P.atm, P.opts, pc.SHIFTS).shape == (7, 800, 2)
     E.set_exposures(None)
     E.set_filter(case.F)
     assert "trx_run_exposed_map: no exposure table installed (trx_set_exposures)" in refusal(E)   # a filter, no table
@@ -381,7 +354,7 @@ def test_refusals(case):
     # its own: the pairs' bytes.  Two cells at rest at the two ends of a grid of 100 000 lags: every exposure's span is the
     # whole grid, R = 700 000 rows of 800 pixels -- refused behind the tracks, ahead of the pixel pass
     kms = np.linspace(-50.0, 50.0, 100_000)
-    wide = xcor.VelocityMap(kms, [0.0], [kms[0], kms[-1]], tv.ORBIT, stat="chi2")
+    wide = xcor.VelocityMap(kms, [0.0], [kms[0], kms[-1]], xc.ORBIT, stat="chi2")
     assert xcor.exposed_map_rows(wide)[3] == 700_000 and 700_000 * 800 * 16 > _abi.EXPOSED_MAP_PAIR_BYTES
     two = np.full((1, 2), -7.0)
     rc = lib.trx_run_exposed_map(E._h, C.byref(P.atm), C.byref(P.opts), None, C.byref(wide.to_c()), two.ctypes.data_as(dp), None, C.byref(nr), None)
@@ -403,7 +376,7 @@ def test_refusals(case):
         S.set_observed(xcor.Observed([0, 1, 4], np.ones((7, 4))))
         S.set_exposures(table())
         assert "trx_run_exposed_map: this handle's shard is not the whole grid" in refusal(S, code=-6)
-        assert S.run_exposed(P.atm, P.opts, tp.SHIFTS).shape == (7, 4, 2)
+        assert S.run_exposed(P.atm, P.opts, pc.SHIFTS).shape == (7, 4, 2)
         S.close()
     finally:
         P.set_shard(0, n)
@@ -413,7 +386,7 @@ def test_the_batch_form(case):
     P, px, ob = case.P, case.px, case.ob
     dp = _abi.c_double_p
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     rot = [broaden.Rotation(4.0, 0.4), broaden.Rotation(2.5, 0.1), broaden.Rotation(6.0, 0.8)]
     tables = [table(), Exposures(scale=SCALE[::-1].copy()), Exposures(smear=np.roll(SMEAR, 2))]
     vm2 = the_map("loglike_bl19", second=True, offset=True)

@@ -2,12 +2,12 @@
 scale and a Doppler-smear half-width per exposure, applied in the pixel stage, against transit_amd.exposures, the numpy
 statement of the same definition.
 
-The case is test_gpu_pixels' (6001 bins, 60 layers), the exposures its seven shifts, the pixels three sets of 400: its
+The case is pixel_cases.make's (6001 bins, 60 layers), the exposures its seven shifts, the pixels three sets of 400: its
 set A (lane windows of 42-44 bins), its set B (wave windows of 283-290 bins) and a set C at R = 4575 whose plain windows are
 186-190 bins, so that the smear carries some exposures over kPixWaveFrom = 192 bins and others not; three segments, one
 per set.  smear = [0, 2e-9, 1e-6, 3e-6, 1.3e-5, 0, 1e-5], scale = [1, 0.5, 0, -0.25, 1, 3, 1e-3].
 
-Tolerance of the accuracy checks, per component, relative: test_gpu_pixels.tolerance + E * n_max * wn_d / (4 d_min) over the
+Tolerance of the accuracy checks, per component, relative: pixel_cases.tolerance + E * n_max * wn_d / (4 d_min) over the
 rows with eta > 0: the sum of the weights is about 4 d / wn_d, each of the n_max weights carries an absolute error of at
 most E = 2^-50 -- the host's and the device's erf within 2^-51 each (the host's is within 1.5 ulp(1) of 40-digit
 arithmetic; the device's is what test_the_weight_itself measures)."""
@@ -16,20 +16,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_filter as tf
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_velocity_map as tv
-from test_gpu_bands import grid, thinner
-from test_gpu_batch import atmospheres
+import pixel_cases as pc
+import xcor_checks as xc
 from transit_amd import _abi, bands, exposures, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-SMEAR = np.array([0.0, 2e-9, 1e-6, 3e-6, 1.3e-5, 0.0, 1e-5])
-SCALE = np.array([1.0, 0.5, 0.0, -0.25, 1.0, 3.0, 1e-3])
+SHIFTS = pc.SHIFTS
 LENGTHS = [400, 400, 400]
 WAVE_FROM = 192                                  # kPixWaveFrom
 E_ERF = 2.0 ** -50
@@ -37,7 +31,7 @@ EPS = 2.0 ** -52
 
 
 def table():
-    return exposures.Exposures(SCALE, SMEAR)
+    return exposures.Exposures(xc.SCALE, xc.SMEAR)
 
 
 def set_c(P):
@@ -47,13 +41,13 @@ def set_c(P):
 
 
 def pixel_set(P):
-    return tp.joined(tp.set_a(P), tp.set_b(P), set_c(P))
+    return pc.joined(pc.set_a(P), pc.set_b(P), set_c(P))
 
 
 def windows(P, px, shifts, ex):
     """[nexp, npix] whole-grid window lengths by exposures.exposed_range, and the smallest distance (in bins) of a window
     edge from a grid point"""
-    wn_i, wn_d, n, _ = grid(P)
+    wn_i, wn_d, n, _ = pc.grid(P)
     lens, margin = np.zeros((len(shifts), len(px)), dtype=np.int64), np.inf
     for v, s in enumerate(shifts):
         eta = ex.eta(v)
@@ -71,11 +65,11 @@ def tolerance(P, px, shifts, ex, lens):
     wn_d = float(P.static.wn_d)
     smeared = [v for v in range(len(shifts)) if ex.eta(v) > 0]
     d_min = min(float(np.min(px.centre)) / float(shifts[v]) * ex.eta(v) for v in smeared)
-    return tp.tolerance(px, shifts) + E_ERF * int(lens[smeared].max()) * wn_d / (4.0 * d_min)
+    return pc.tolerance(px, shifts) + E_ERF * int(lens[smeared].max()) * wn_d / (4.0 * d_min)
 
 
 def check_sums(mom, ref, scale, ob, what=""):
-    """moments against the reference's and the sums of its absolute terms, with test_gpu_moments' bound: the count exactly,
+    """moments against the reference's and the sums of its absolute terms, with xcor_checks.check_moments' bound: the count exactly,
     every other moment within (n_max + 16) * 2^-52 of the scale (exactly where the scale is 0)"""
     assert mom.shape == ref.shape == scale.shape
     assert np.array_equal(mom[..., 0], ref[..., 0]), what
@@ -105,13 +99,13 @@ def case(tmp_path_factory):
     """the eclipse case at 20 000 lines, the 1200 pixels, the observed set of 7 exposures by 3 segments, the table, the
     window lengths, and -- made once, shared and left unchanged -- the spectrum, the plain pairs and the exposed pairs"""
     c = Case()
-    c.P = tp.make(tmp_path_factory.mktemp("exposures"), "eclipse", nlines=20_000)
+    c.P = pc.make(tmp_path_factory.mktemp("exposures"), "eclipse", nlines=20_000)
     c.px, c.ex = pixel_set(c.P), table()
     c.lens, c.margin = windows(c.P, c.px, SHIFTS, c.ex)
     plain = Engine(c.P.static)
     c.spec = plain.run(c.P.atm, c.P.opts)["spectrum"]
     plain.close()
-    c.ob = tm.observed(len(c.px), float(np.mean(c.spec)), lengths=LENGTHS)
+    c.ob = xc.observed(len(c.px), float(np.mean(c.spec)), lengths=LENGTHS)
     E = handle(c.P, c.px, c.ob)
     c.plain = E.run_pixels(c.P.atm, c.P.opts, SHIFTS)
     E.set_exposures(c.ex)
@@ -127,7 +121,7 @@ def test_the_three_sets_take_both_forms_in_one_call(case):
     plain_lens, plain_margin = windows(P, px, SHIFTS, exposures.Exposures(smear=np.zeros(7)))
     a, b, c = plain_lens[:, :400], plain_lens[:, 400:800], plain_lens[:, 800:]
     assert 42 <= a.min() and a.max() <= 44 and 283 <= b.min() and b.max() <= 290 and 186 <= c.min() and c.max() <= 190
-    assert np.array_equal(plain_lens, np.array(tp.window_lengths_and_margin(P, px, SHIFTS)[0]).reshape(7, -1))
+    assert np.array_equal(plain_lens, np.array(pc.window_lengths_and_margin(P, px, SHIFTS)[0]).reshape(7, -1))
     assert min(case.margin, plain_margin) >= 1e-6, (case.margin, plain_margin)
     lens = case.lens
     # set C: lanes without smear, the wave at eta = 1.3e-5, and both forms in the one row at eta = 1e-5
@@ -140,18 +134,18 @@ def test_the_three_sets_take_both_forms_in_one_call(case):
 # ---- 1. accuracy -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_exposed_pairs_are_the_definition(tmp_path, solution):
-    P = tp.make(tmp_path, solution)
+    P = pc.make(tmp_path, solution)
     assert P.nwn == 6001
-    wn_i, wn_d, n, _ = grid(P)
+    wn_i, wn_d, n, _ = pc.grid(P)
     px, ex = pixel_set(P), table()
     lens, margin = windows(P, px, SHIFTS, ex)
     assert margin >= 1e-6
     tol = tolerance(P, px, SHIFTS, ex, lens)
-    assert tp.tolerance(px, SHIFTS) < tol < 2e-10
+    assert pc.tolerance(px, SHIFTS) < tol < 2e-10
     plain = Engine(P.static)
-    ob = tm.observed(len(px), 1.0, lengths=LENGTHS)
+    ob = xc.observed(len(px), 1.0, lengths=LENGTHS)
     E = handle(P, px, ob, ex)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     refs = {}
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         what = "%s run %d" % (solution, k)
@@ -161,7 +155,7 @@ def test_exposed_pairs_are_the_definition(tmp_path, solution):
         key = spec.tobytes()
         if key not in refs:
             refs[key] = exposures.reference(spec, wn_i, wn_d, n, px, SHIFTS, ex)
-        tp.check_close(out, refs[key], tol, what + " vs reference")
+        pc.check_close(out, refs[key], tol, what + " vs reference")
         assert np.all(out[..., 1] > 0) and np.all(out[2, :, 0] == 0)
     assert len(refs) == 2
     plain.close(); E.close()
@@ -177,10 +171,10 @@ def test_rows_without_smear_are_the_plain_rows(case):
         E.set_exposures(ex)
         assert np.array_equal(E.run_exposed(P.atm, P.opts, SHIFTS), case.plain)
     # smear = NULL: b is the plain b, a the one product
-    E.set_exposures(exposures.Exposures(scale=SCALE))
+    E.set_exposures(exposures.Exposures(scale=xc.SCALE))
     got, spec = E.run_exposed(P.atm, P.opts, SHIFTS, spectrum=True)
     assert np.array_equal(got[..., 1], case.plain[..., 1])
-    assert np.array_equal(got[..., 0], SCALE[:, None] * case.plain[..., 0])
+    assert np.array_equal(got[..., 0], xc.SCALE[:, None] * case.plain[..., 0])
     assert np.array_equal(spec, case.spec)
     # eta == 0 with a scale (exposure 5): the same
     assert np.array_equal(case.pairs[5, :, 1], case.plain[5, :, 1]) and np.array_equal(case.pairs[5, :, 0], 3.0 * case.plain[5, :, 0])
@@ -199,7 +193,7 @@ def test_the_weight_itself(case):
     (a == b * S_i in the same bits: a is that one product, rounded once.  a / b is S_i to an ulp, not always in the same
     bits: a quotient of a rounded product by its factor need not return the other factor.)"""
     P = case.P
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     sigma = 0.9 * wn_d / 12.0
     bins = np.arange(300, 5700, 27)
     off = np.linspace(0.0, 0.45, bins.size) * np.where(np.arange(bins.size) % 2, -1.0, 1.0)
@@ -245,8 +239,8 @@ def test_moments_filter_and_highpass_take_the_exposed_pairs(case):
     F = xcor.svd_filter(ob.data, ob.seg_first, 3)
     E.set_filter(F)
     fmom, fval = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
-    tf.check_values(fval, pairs, ob, F, "filter behind the exposed pairs")
-    tf.check_moments(fmom, fval, ob, "filtered moments of the exposed pairs")
+    xc.check_values(fval, pairs, ob, F, "filter behind the exposed pairs")
+    xc.check_filtered_moments(fmom, fval, ob, "filtered moments of the exposed pairs")
     assert np.array_equal(E.run_moments(P.atm, P.opts, SHIFTS), mom)
     # with a high-pass as well: its definition over the exposed pairs, then the same two
     hp = xcor.gaussian_highpass(12.0)
@@ -257,8 +251,8 @@ def test_moments_filter_and_highpass_take_the_exposed_pairs(case):
     check_sums(hmom, xcor.reference_values(hval, ob), xcor.abs_reference_values(hval, ob), ob, "high-passed moments of the exposed pairs")
     gain_free = xcor.Observed(ob.seg_first, ob.data, ob.weight, None)
     hfmom, hfval = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
-    tf.check_values(hfval, xcor.highpass_pairs(hval), gain_free, F, "filter behind the high-pass of the exposed pairs")
-    tf.check_moments(hfmom, hfval, ob, "filtered high-passed moments of the exposed pairs")
+    xc.check_values(hfval, xcor.highpass_pairs(hval), gain_free, F, "filter behind the high-pass of the exposed pairs")
+    xc.check_filtered_moments(hfmom, hfval, ob, "filtered high-passed moments of the exposed pairs")
     assert not np.array_equal(hmom, mom) and not np.array_equal(hfmom, fmom)
     E.close(); bare.close()
 
@@ -271,16 +265,16 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
         assert np.array_equal(E.run_exposed(P.atm, P.opts, SHIFTS), first)
     assert np.array_equal(E.run_exposed(P.atm, P.opts, SHIFTS, spectrum=True)[0], first)
     # the other rows' smear and scale change: rows 1 and 4 keep theirs
-    smear, scale = SMEAR[::-1].copy(), (SCALE * -2.0 + 0.125)[::-1].copy()
+    smear, scale = xc.SMEAR[::-1].copy(), (xc.SCALE * -2.0 + 0.125)[::-1].copy()
     for v in (1, 4):
-        smear[v], scale[v] = SMEAR[v], SCALE[v]
+        smear[v], scale[v] = xc.SMEAR[v], xc.SCALE[v]
     E.set_exposures(exposures.Exposures(scale, smear))
     got = E.run_exposed(P.atm, P.opts, SHIFTS)
     assert np.array_equal(got[[1, 4]], first[[1, 4]])
     assert all(not np.array_equal(got[v], first[v]) for v in (0, 2, 3, 5, 6))
     # the exposures permuted, with their shifts
     perm = [4, 0, 6, 2, 5, 1, 3]
-    E.set_exposures(exposures.Exposures(SCALE[perm], SMEAR[perm]))
+    E.set_exposures(exposures.Exposures(xc.SCALE[perm], xc.SMEAR[perm]))
     assert np.array_equal(E.run_exposed(P.atm, P.opts, SHIFTS[perm]), first[perm])
     E.close()
 
@@ -288,9 +282,9 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
 def test_batch_pairs_are_the_single_handle_pairs(case):
     P, px, ob = case.P, case.px, case.ob
     K = 4
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     shifts = np.stack([np.roll(SHIFTS, j) * (1.0 + 1e-6 * j) for j in range(K)])
-    tables = [exposures.Exposures(np.roll(SCALE, j) + 0.25 * j, np.roll(SMEAR, 2 * j)) for j in range(K)]
+    tables = [exposures.Exposures(np.roll(xc.SCALE, j) + 0.25 * j, np.roll(xc.SMEAR, 2 * j)) for j in range(K)]
     one = handle(P, px, ob)
     ref, ref1, mom = [], [], []
     for j in range(K):
@@ -326,7 +320,7 @@ def test_batch_pairs_are_the_single_handle_pairs(case):
     assert np.array_equal(B.run_exposed(atms[:3], P.opts, shifts[:3]), ref[:3])
     # all entries are checked before any is kept
     with pytest.raises(EngineError) as ei:
-        B.set_exposures([tables[0], exposures.Exposures(SCALE, np.where(np.arange(7) == 4, 0.5, SMEAR))])
+        B.set_exposures([tables[0], exposures.Exposures(xc.SCALE, np.where(np.arange(7) == 4, 0.5, xc.SMEAR))])
     assert ei.value.code == -1 and "entry 1" in str(ei.value) and "exposure 4" in str(ei.value)
     assert np.array_equal(B.run_exposed(atms[:3], P.opts, shifts[:3]), ref[:3])
     B.set_exposures(None)                               # cleared: the plain moments again
@@ -342,7 +336,7 @@ def test_batch_pairs_are_the_single_handle_pairs(case):
 def test_the_other_runs_do_not_know_of_the_table(case):
     P, px, ob = case.P, case.px, case.ob
     E, bare = handle(P, px, ob, case.ex), handle(P, px, ob)
-    hp, F, vm = xcor.gaussian_highpass(12.0), xcor.svd_filter(ob.data, ob.seg_first, 3), tv.the_map("ccf")
+    hp, F, vm = xcor.gaussian_highpass(12.0), xcor.svd_filter(ob.data, ob.seg_first, 3), xc.the_map("ccf")
     bs = pixels.as_bands(pixels.Pixels(px.centre[::100], px.fwhm[::100], px.cut), SHIFTS[:2])
     for X in (E, bare):
         X.set_highpass(hp)
@@ -388,7 +382,7 @@ def test_refusals_and_lifetimes(case):
     assert np.array_equal(E.run_exposed(P.atm, P.opts, SHIFTS), case.pairs)
 
     def with_exposure_3(scale=-0.25, smear=3e-6):
-        sc, sm = SCALE.copy(), SMEAR.copy()
+        sc, sm = xc.SCALE.copy(), xc.SMEAR.copy()
         sc[3], sm[3] = scale, smear
         return exposures.Exposures(sc, sm)
 
@@ -402,7 +396,7 @@ def test_refusals_and_lifetimes(case):
         assert np.array_equal(E.run_exposed(P.atm, P.opts, SHIFTS), case.pairs), what      # the previous table acts
     E.set_exposures(with_exposure_3(smear=exposures.SMEAR_MAX))                            # the cap itself is taken
     E.set_exposures(case.ex)
-    for what, ex in (("6", exposures.Exposures(SCALE[:6], SMEAR[:6])), ("8", exposures.Exposures(np.ones(8)))):
+    for what, ex in (("6", exposures.Exposures(xc.SCALE[:6], xc.SMEAR[:6])), ("8", exposures.Exposures(np.ones(8)))):
         with pytest.raises(EngineError) as ei:
             E.set_exposures(ex)
         assert ei.value.code == -1 and "nexp " + what in str(ei.value) and "nexp 7" in str(ei.value)
@@ -467,10 +461,10 @@ def test_refusals_and_lifetimes(case):
 # ---- 8. shards ----------------------------------------------------------------------------------------------------
 def test_shards_combined_in_rank_order(case):
     P, px, ob, ex = case.P, case.px, case.ob, case.ex
-    wn_i, wn_d, n, _ = grid(P)
+    wn_i, wn_d, n, _ = pc.grid(P)
     tol = tolerance(P, px, SHIFTS, ex, case.lens)
     ref = exposures.reference(case.spec, wn_i, wn_d, n, px, SHIFTS, ex)
-    tp.check_close(np.array(case.pairs), ref, tol, "whole grid")
+    pc.check_close(np.array(case.pairs), ref, tol, "whole grid")
     cuts = [0, 1500, 3777, n]
     parts, empties, negative = [], 0, 0
     try:
@@ -483,16 +477,16 @@ def test_shards_combined_in_rank_order(case):
             assert ei.value.code == -6
             E.close()
             assert sp.shape == (cuts[r + 1] - cuts[r],)
-            tp.check_close(s, exposures.reference(sp, wn_i, wn_d, n, px, SHIFTS, ex, lo=cuts[r]), tol, "shard %d" % r)
+            pc.check_close(s, exposures.reference(sp, wn_i, wn_d, n, px, SHIFTS, ex, lo=cuts[r]), tol, "shard %d" % r)
             for v in range(7):
                 for p in range(len(px)):
                     a, z = exposures.exposed_range(wn_i, wn_d, n, float(px.centre[p]) / float(SHIFTS[v]), float(px.fwhm[p]) / float(SHIFTS[v]), px.cut, ex.eta(v))
                     if max(a, cuts[r]) >= min(z, cuts[r + 1]):
                         empties += 1
-                        negative += SCALE[v] < 0
+                        negative += xc.SCALE[v] < 0
                         assert s[v, p, 0] == 0 and s[v, p, 1] == 0 and not np.signbit(s[v, p, 0]) and not np.signbit(s[v, p, 1]), (r, v, p)
             parts.append(s)
     finally:
         P.set_shard(0, n)
     assert empties > 1000 and negative > 100
-    tp.check_close(pixels.combine(parts), ref, tol, "shards added in rank order")
+    pc.check_close(pixels.combine(parts), ref, tol, "shards added in rank order")

@@ -2,8 +2,8 @@
 trx_run_filtered_moments and the batch forms, include/transit_hip.h) against transit_amd.xcor, the numpy statement of
 the same definition.
 
-The case is test_gpu_pixels' (6001 bins, 60 layers; 20 000 lines where only bits are compared), the seven shifts its
-own, the pixel set the 800-pixel set of test_gpu_moments with its two off-grid pixels -- and one further pixel of set A
+The case is pixel_cases.make's (6001 bins, 60 layers; 20 000 lines where only bits are compared), the seven shifts its
+own, the pixel set the 800-pixel set of xcor_checks with its two off-grid pixels -- and one further pixel of set A
 moved to 2561.0 cm-1: at these shifts its window is on the grid at -150 km/s only, so its pairs have b > 0 at one
 exposure and its column is dead all the same.  Segment lengths [1, 63, 64, 65, 200, 0, 7, 400]: tiles of 1, 63, 64 and
 64 + 1 pixels, an empty segment, and 400 = 6 tiles + 16.
@@ -13,7 +13,7 @@ Values, per element, relative to xcor.filter_abs_reference A = |g| + |back| (|fw
 two roundings in g, nexp products and sums in a coefficient, ncomp in the projection, one subtraction, doubled to leave
 room for the reference's own rounding.
 Moments: compared with xcor.reference_values over the VALUES THE DEVICE RETURNED (so that the cancellation inside g'
-does not enter), by the rule of test_gpu_moments: (n_max + 16) * 2^-52 of the sums of absolute terms, the count exact."""
+does not enter), by the rule of xcor_checks.check_moments: (n_max + 16) * 2^-52 of the sums of absolute terms, the count exact."""
 import ctypes as C
 import math
 import os
@@ -22,113 +22,60 @@ import shutil
 import numpy as np
 import pytest
 
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
+import pixel_cases as pc
+import xcor_checks as xc
 from cases import GOLDEN
-from test_gpu_bands import grid, thinner
-from test_gpu_batch import atmospheres
 from transit_amd import _abi, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-LENGTHS = tm.LENGTHS
-STRADDLE = {100: 2561.0}                        # pixel (of set A) -> centre (cm-1): on the grid at the first shift only
-DEAD = sorted(list(tm.OFF_GRID) + list(STRADDLE))
-EPS = 2.0 ** -52
-
-
-def pixel_set(P, straddle=True):
-    px = tm.pixel_set(P)
-    if straddle:
-        for p, c in STRADDLE.items():
-            px.centre[p] = c
-    return px
-
-
-def random_filter(nseg, ncomp, nexp, seed):
-    """matrices of both signs, scaled to 1 / nexp"""
-    rng = np.random.default_rng(seed)
-    return xcor.Filter(rng.uniform(-1.0, 1.0, (nseg, ncomp, nexp)) / nexp, rng.uniform(-1.0, 1.0, (nseg, nexp, ncomp)) / nexp)
-
-
-def check_values(val, pairs, ob, F, what=""):
-    """NaN exactly where the definition has it, every other value to (nexp + ncomp + 8) * 2^-52 of A"""
-    ref, scale = xcor.filter_reference(pairs, ob, F), xcor.filter_abs_reference(pairs, ob, F)
-    assert val.shape == ref.shape == (ob.nexp, ob.npix)
-    dead = np.isnan(ref)
-    assert np.array_equal(np.isnan(val), dead), what
-    tol = (ob.nexp + F.ncomp + 8) * EPS
-    err, size = np.abs(val - ref)[~dead], scale[~dead]
-    worst = float(np.max(err[size > 0] / size[size > 0]))
-    print("%s: worst |value - ref| / A %.3e = %.2f * 2^-52 (tolerance %.3e)" % (what, worst, worst / EPS, tol))
-    assert np.all(err <= tol * size), (what, worst, tol)
-    return ref
-
-
-def check_moments(mom, val, ob, what=""):
-    """the count exactly, every other moment to (n_max + 16) * 2^-52 of the sum of its absolute terms over the values
-    the device returned; an empty row is seven +0"""
-    ref, scale = xcor.reference_values(val, ob), xcor.abs_reference_values(val, ob)
-    assert mom.shape == ref.shape == (ob.nexp, ob.nseg, 7)
-    assert np.array_equal(mom[..., 0], ref[..., 0]), what
-    w = ob.weight if ob.weight is not None else np.ones_like(ob.data)
-    full = np.diff(ob.seg_first) > 0
-    want_n = np.add.reduceat((~np.isnan(val) & (w > 0)).astype(float), ob.seg_first[:-1][full], axis=1)
-    assert np.array_equal(mom[..., 0][:, full], want_n), what
-    tol = (int(np.max(np.diff(ob.seg_first))) + 16) * EPS
-    empty = ref[..., 0] == 0
-    assert np.all(mom[empty] == 0) and not np.any(np.signbit(mom[empty])), what
-    ratio = np.abs(mom - ref)[~empty][:, 1:] / scale[~empty][:, 1:]
-    worst = float(ratio.max())
-    print("%s: worst |mom - ref| / abs_ref %.3e = %.2f * 2^-52 (tolerance %.3e)" % (what, worst, worst / EPS, tol))
-    assert worst <= tol, (what, worst, tol)
+SHIFTS = pc.SHIFTS
 
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_filtered_values_and_moments_are_the_definition(tmp_path, solution):
-    P = tp.make(tmp_path, solution)
+    P = pc.make(tmp_path, solution)
     assert P.nwn == 6001
-    px = pixel_set(P)
+    px = xc.straddle_pixel_set(P)
     plain, E = Engine(P.static), Engine(P.static)
-    ob = tm.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])))
     F = xcor.svd_filter(ob.data, ob.seg_first, 3)
     assert (F.nseg, F.ncomp, F.nexp) == (8, 3, 7)
     E.set_pixels(px)
     E.set_observed(ob)
     E.set_filter(F)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         what = "%s run %d" % (solution, k)
         spec_ref = plain.run(atm, P.opts)["spectrum"]
         pairs = E.run_pixels(atm, P.opts, SHIFTS)
         mom, spec, val = E.run_filtered_moments(atm, P.opts, SHIFTS, spectrum=True, values=True)
         assert np.array_equal(spec, spec_ref), what
-        for p in STRADDLE:                             # on the grid at exactly one shift
+        for p in xc.STRADDLE:                             # on the grid at exactly one shift
             assert np.count_nonzero(pairs[:, p, 1] > 0) == 1 and pairs[0, p, 1] > 0
-        for p in tm.OFF_GRID:
+        for p in xc.OFF_GRID:
             assert np.all(pairs[:, p, 1] == 0)
-        check_values(val, pairs, ob, F, what)
-        assert np.flatnonzero(np.isnan(val).any(axis=0)).tolist() == DEAD and np.isnan(val[:, DEAD]).all(), what
-        check_moments(mom, val, ob, what)
+        xc.check_values(val, pairs, ob, F, what)
+        assert np.flatnonzero(np.isnan(val).any(axis=0)).tolist() == xc.DEAD and np.isnan(val[:, xc.DEAD]).all(), what
+        xc.check_filtered_moments(mom, val, ob, what)
         # without the values, without the spectrum: the same moments
         assert np.array_equal(E.run_filtered_moments(atm, P.opts, SHIFTS), mom), what
     plain.close(); E.close()
 
 
 def test_an_all_zero_filter_gives_the_unfiltered_bits(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=20_000)
-    px = pixel_set(P, straddle=False)
+    P = pc.make(tmp_path, "eclipse", nlines=20_000)
+    px = xc.straddle_pixel_set(P, straddle=False)
     E = Engine(P.static)
     E.set_pixels(px)
-    ob = tm.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])))
     E.set_observed(ob)
     E.set_filter(xcor.Filter(np.zeros((ob.nseg, 1, ob.nexp)), np.zeros((ob.nseg, ob.nexp, 1))))
     pairs = E.run_pixels(P.atm, P.opts, SHIFTS)
     mom, val = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
-    off = sorted(tm.OFF_GRID)
+    off = sorted(xc.OFF_GRID)
     on = np.ones(len(px), dtype=bool)
     on[off] = False
     assert np.all(pairs[:, on, 1] > 0) and np.all(pairs[:, off, 1] == 0)
@@ -141,20 +88,20 @@ def test_an_all_zero_filter_gives_the_unfiltered_bits(tmp_path):
 @pytest.mark.parametrize("ncomp", [1, 5, 16])
 def test_random_filters_of_every_register_size(tmp_path, ncomp):
     """ncomp 1, 5 and 16 take the kernel's instantiations for 4, 8 and 16 components"""
-    P = tp.make(tmp_path, "transit", nlines=20_000)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "transit", nlines=20_000)
+    px = xc.straddle_pixel_set(P)
     E = Engine(P.static)
     E.set_pixels(px)
-    ob = tm.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])), seed=5)
+    ob = xc.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])), seed=5)
     E.set_observed(ob)
-    F = random_filter(ob.nseg, ncomp, ob.nexp, seed=ncomp)
+    F = xc.random_filter(ob.nseg, ncomp, ob.nexp, seed=ncomp)
     assert F.fwd.min() < 0 < F.fwd.max() and F.back.min() < 0 < F.back.max()
     E.set_filter(F)
     pairs = E.run_pixels(P.atm, P.opts, SHIFTS)
     mom, val = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
-    check_values(val, pairs, ob, F, "ncomp %d" % ncomp)
-    assert np.flatnonzero(np.isnan(val).any(axis=0)).tolist() == DEAD
-    check_moments(mom, val, ob, "ncomp %d" % ncomp)
+    xc.check_values(val, pairs, ob, F, "ncomp %d" % ncomp)
+    assert np.flatnonzero(np.isnan(val).any(axis=0)).tolist() == xc.DEAD
+    xc.check_filtered_moments(mom, val, ob, "ncomp %d" % ncomp)
     # the same filter padded with zero components to the next instantiation: the same bits
     if ncomp < 16:
         wide = {1: 5, 5: 9}[ncomp]
@@ -167,13 +114,13 @@ def test_random_filters_of_every_register_size(tmp_path, ncomp):
 
 
 def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=20_000)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "eclipse", nlines=20_000)
+    px = xc.straddle_pixel_set(P)
     E = Engine(P.static)
     E.set_pixels(px)
-    ob = tm.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])))
     E.set_observed(ob)
-    F = random_filter(ob.nseg, 3, ob.nexp, seed=1)
+    F = xc.random_filter(ob.nseg, 3, ob.nexp, seed=1)
     E.set_filter(F)
     mom, val = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
     assert np.all(mom[:, 5] == 0) and np.all(mom[:, [0, 1, 2, 3, 4, 6, 7], 0] > 0)
@@ -185,7 +132,7 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
     lengths = [1, 30, 33, 64, 65, 100, 100, 0, 0, 7, 150, 250]
     again = xcor.Observed(xcor.segments(lengths), ob.data, ob.weight, ob.gain)
     same = {0: 0, 3: 2, 4: 3, 7: 5, 8: 5, 9: 6}              # new segment -> the old one of the same pixels
-    G = random_filter(again.nseg, 3, again.nexp, seed=2)
+    G = xc.random_filter(again.nseg, 3, again.nexp, seed=2)
     for new, old in same.items():
         assert again.seg_first[new:new + 2].tolist() == ob.seg_first[old:old + 2].tolist()
         G.fwd[new], G.back[new] = F.fwd[old], F.back[old]
@@ -203,7 +150,7 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
         assert np.all(val2[:, a:z][:, live] != val[:, a:z][:, live]), new
     # through a batch of two ways: each atmosphere's bits are the single handle's
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     shifts = np.stack([np.roll(SHIFTS, j) * (1.0 + 1e-6 * j) for j in range(K)])
     E.set_observed(ob)
     E.set_filter(F)
@@ -221,14 +168,14 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
 
 
 def test_the_other_runs_do_not_know_of_the_filter(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=20_000)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "eclipse", nlines=20_000)
+    px = xc.straddle_pixel_set(P)
     E, bare = Engine(P.static), Engine(P.static)
-    ob = tm.observed(len(px), float(np.mean(bare.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(bare.run(P.atm, P.opts)["spectrum"])))
     for X in (E, bare):
         X.set_pixels(px)
         X.set_observed(ob)
-    E.set_filter(random_filter(ob.nseg, 8, ob.nexp, seed=4))
+    E.set_filter(xc.random_filter(ob.nseg, 8, ob.nexp, seed=4))
     for k in range(2):
         E.run_filtered_moments(P.atm, P.opts, SHIFTS)
         assert np.array_equal(E.run_pixels(P.atm, P.opts, SHIFTS), bare.run_pixels(P.atm, P.opts, SHIFTS)), k
@@ -241,11 +188,11 @@ def test_likelihood_end_to_end(tmp_path):
     """xcor.loglike_bl19_sum of the filtered moments against the direct evaluation (means subtracted first) on the
     values the device returned, row by row to the 1e-10 of test_gpu_moments, the sum to 1e-10 of the sum of the rows'
     absolute values"""
-    P = tp.make(tmp_path, "transit", nlines=20_000)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "transit", nlines=20_000)
+    px = xc.straddle_pixel_set(P)
     E = Engine(P.static)
     E.set_pixels(px)
-    ob = tm.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])), seed=9)
+    ob = xc.observed(len(px), float(np.mean(E.run(P.atm, P.opts)["spectrum"])), seed=9)
     E.set_observed(ob)
     E.set_filter(xcor.svd_filter(ob.data, ob.seg_first, 3))
     mom, val = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
@@ -286,13 +233,13 @@ def test_opacity_grid_handle(tmp_path):
     builder.build_opacity_grid(P)
     builder.close()
     assert P.static.ogrid
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     centres = np.linspace(wn[0] + 1.0, wn[-1] - 1.0, 25) + 0.37 * wn_d
-    px = tp.joined(pixels.resolving_power(centres, 1000.0), pixels.resolving_power(centres, 100.0))
+    px = pc.joined(pixels.resolving_power(centres, 1000.0), pixels.resolving_power(centres, 100.0))
     shifts = np.array([1.0, 1.0 - 150.0 / 299792.458, 1.0 + 150.0 / 299792.458, 0.9991])
     plain, E = Engine(P.static), Engine(P.static)
     E.set_pixels(px)
-    ob = tm.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])), lengths=[10, 0, 15, 25], nexp=4)
+    ob = xc.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])), lengths=[10, 0, 15, 25], nexp=4)
     E.set_observed(ob)
     F = xcor.svd_filter(ob.data, ob.seg_first, 2)
     E.set_filter(F)
@@ -301,20 +248,20 @@ def test_opacity_grid_handle(tmp_path):
         pairs = E.run_pixels(P.atm, P.opts, shifts)
         mom, spec, val = E.run_filtered_moments(P.atm, P.opts, shifts, spectrum=True, values=True)
         assert np.array_equal(spec, ref)
-        check_values(val, pairs, ob, F, "opacity grid run %d" % k)
-        check_moments(mom, val, ob, "opacity grid run %d" % k)
+        xc.check_values(val, pairs, ob, F, "opacity grid run %d" % k)
+        xc.check_filtered_moments(mom, val, ob, "opacity grid run %d" % k)
         assert np.array_equal(E.run(P.atm, P.opts)["spectrum"], ref)
     plain.close(); E.close()
 
 
 def test_refusals_and_lifetimes(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=10_000)
+    P = pc.make(tmp_path, "eclipse", nlines=10_000)
     sh = np.ascontiguousarray(SHIFTS[:3])
     good_px = pixels.Pixels([2510.0, 2520.0, 2530.0, 2540.0], [0.2, 0.3, 1.5, 0.4], 4.0)
     rng = np.random.default_rng(2)
     f, w, gain = rng.standard_normal((3, 4)), rng.uniform(0.5, 2.0, (3, 4)), rng.uniform(0.5, 1.5, 4)
     good_ob = xcor.Observed([0, 1, 4], f, w, gain)
-    good = random_filter(2, 2, 3, seed=6)
+    good = xc.random_filter(2, 2, 3, seed=6)
     E = Engine(P.static)
     lib = E._lib
     dp = _abi.c_double_p
@@ -349,7 +296,7 @@ def test_refusals_and_lifetimes(tmp_path):
                              ("fwd inf", changed("fwd", (0, 1, 0), np.inf), "segment 0"),
                              ("back nan", changed("back", (0, 2, 1), np.nan), "segment 0"),
                              ("back -inf", changed("back", (1, 0, 0), -np.inf), "segment 1"),
-                             ("17 components", random_filter(2, 17, 3, seed=7), "TRX_FILTER_MAX")):
+                             ("17 components", xc.random_filter(2, 17, 3, seed=7), "TRX_FILTER_MAX")):
         assert name in refusal(E, filt), what
         unchanged(what)
     assert "fwd" in refusal(E, changed("fwd", (1, 0, 2), np.nan)) and "back" in refusal(E, changed("back", (1, 0, 0), np.nan))

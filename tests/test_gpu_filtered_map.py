@@ -1,7 +1,7 @@
 """The Kp-Vsys detection map with the detrending filter applied to every cell's own model matrix, on the device
 (trx_run_filtered_map / trx_run_batch_filtered_map, include/transit_hip.h).
 
-The case is test_gpu_velocity_map's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels, 7 exposures, the
+The case is xcor_checks': pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels, 7 exposures, the
 segments [1, 63, 64, 65, 200, 0, 7, 400], the 55 lags -81 .. 81 km/s, the 7 x 5 map with its seven outside cells and the
 13 x 11 map -- 143 cells, three chunks of _abi.CELLMAP_CHUNK = 64 cells with a ragged last one (second_axes enlarges the grid
 should the cap ever grow).  The filter is xcor.svd_filter(ob.data, ob.seg_first, 3).  One pixel (PIXEL, of segment 2) is moved
@@ -13,70 +13,27 @@ run_filtered_moments returns on the same handle at the shifts LAGS[lag_index[cel
 docstring), and in the same bits for ccf and chi2 in practice (printed).
 
 AGAINST NUMPY ALONE (test 2): the map against xcor.filtered_map_reference of run_pixels' pairs at the lags.  The tolerance is
-test_gpu_filter's tolerance of the VALUES carried through the moments and the statistic; nothing in it is measured.
-  - values: the device's g' lies within tau * A of filter_reference's, tau = (nexp + ncomp + 8) 2^-52 and
-    A = xcor.filter_abs_reference (test_gpu_filter's rule), with NaN in the same columns;
-  - moments: the exact sums over two value matrices that differ by at most tau A per element differ by at most
-    E2 = sum w tau A in m2, E5 = sum w |f| tau A in m5 and E3 = sum w (2 |g'| tau A + (tau A)^2) in m3; m1, m4 and m6 do not
-    contain g.  On top of that each side's sum is not exact: the device's moments lie within (n_max + 16) 2^-52 of the sums
-    S_k of their absolute terms (test_gpu_filter's rule for the moments, which leaves room for the reference's fsum), so
-    moment k of the two sides differs by at most D_k = E_k + (n_max + 16) 2^-52 S_k; the count m0 is exact;
-  - the statistic of a row, to first order in the D_k, by the triangle inequality over its definition (s = m1):
-        d<f> = (D4 + |<f>| D1) / s                       d<g> = (D2 + |<g>| D1) / s
-        dsf2 = (D6 + (m6 / s) D1) / s + 2 |<f>| d<f>     dsg2 = (D3 + (m3 / s) D1) / s + 2 |<g>| d<g>
-        dR   = (D5 + |m5 / s| D1) / s + |<f>| d<g> + |<g>| d<f>
-        ccf           dR / sqrt(sf2 sg2) + (|ccf| / 2) (dsf2 / sf2 + dsg2 / sg2)
-        loglike_bl19  (n / 2) (dsf2 + 2 |p0| dR + p0^2 dsg2) / arg
-        chi2          D6 + 2 |p0| D5 + 2 |p1| D4 + p0^2 D3 + 2 |p0 p1| D2 + p1^2 D1          (exact: it is linear)
-    doubled for the terms of second order, which needs the relative changes dsf2 / sf2, dsg2 / sg2 and d(arg) / arg to be
-    small: the test asserts that they are below 1e-3;
-  - the cell: the sum of its rows' bounds, plus xcor.cell_bound of the reference's moments for the two evaluations of
-    points 5 themselves."""
+the plain filter's tolerance of the VALUES carried through the moments and the statistic, derived in the docstring of
+xcor_checks.row_bounds; nothing in it is measured, and the relative changes it rests on are asserted below 1e-3."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
-from test_gpu_bands import thinner
-from test_gpu_batch import atmospheres
+import pixel_cases as pc
+import xcor_checks as xc
 from transit_amd import _abi, bands, broaden, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-STATS = tv.STATS
-LAG_KMS, LAGS = tv.LAG_KMS, tv.LAGS
-OUTSIDE = tv.OUTSIDE
-EPS = 2.0 ** -52
-CHUNK = _abi.CELLMAP_CHUNK
-PIXEL = 100                                      # of set A, in segment 2
-LIVE_UP_TO = 30.0                                # km/s: the last lag at which PIXEL's window is on the grid
-
-
-def second_axes():
-    """the 13 x 11 grid of test_gpu_velocity_map -- with more Kp rows, should 143 cells not span three chunks with a ragged
-    last one"""
-    n = tv.KP2.size
-    while n * tv.VSYS2.size <= 2 * CHUNK or (n * tv.VSYS2.size) % CHUNK == 0:
-        n += 1
-    return (tv.KP2 if n == tv.KP2.size else np.linspace(30.0, 210.0, n)), tv.VSYS2
-
-
-KP2, VSYS2 = second_axes()
-
-
-def the_map(stat="ccf", second=False, offset=False, **over):
-    kw = dict(kp=KP2, vsys=VSYS2) if second else {}
-    kw.update(over)
-    return tv.the_map(stat, second, offset, **kw)
+STATS = xc.STATS
+LAG_KMS, LAGS = xc.LAG_KMS, xc.LAGS
+OUTSIDE = xc.OUTSIDE
 
 
 def handle(case, filt=True):
-    E = tt.handle(case.P, case.px, case.ob)
+    E = xc.handle(case.P, case.px, case.ob)
     if filt:
         E.set_filter(case.F)
     return E
@@ -103,38 +60,22 @@ class Case:
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("fmap"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
+    P = pc.make(tmp_path_factory.mktemp("fmap"), "eclipse", nlines=20_000)
+    px = xc.pixel_set(P)
     # PIXEL's window [c - h, c + h] / lag leaves the grid (its last point: wn_i + (n - 1) wn_d) between the lags of
     # +30 and +33 km/s: its lower edge, at the lag of +31.5 km/s, sits half a bin above the last grid point
     wn_i, wn_d, n = float(P.static.wn_i), float(P.static.wn_d), int(P.static.nwn)
-    half = px.cut * px.fwhm[PIXEL] / bands.FWHM_PER_SIGMA
-    px.centre[PIXEL] = (wn_i + (n - 0.5) * wn_d) * pixels.shift(LIVE_UP_TO + 1.5) + half
+    half = px.cut * px.fwhm[xc.PIXEL] / bands.FWHM_PER_SIGMA
+    px.centre[xc.PIXEL] = (wn_i + (n - 0.5) * wn_d) * pixels.shift(xc.LIVE_UP_TO + 1.5) + half
     plain = Engine(P.static)
     scale = float(np.mean(plain.run(P.atm, P.opts)["spectrum"]))
     plain.close()
-    ob = tm.observed(len(px), scale)
-    assert ob.seg_first[2] <= PIXEL < ob.seg_first[3]
+    ob = xc.observed(len(px), scale)
+    assert ob.seg_first[2] <= xc.PIXEL < ob.seg_first[3]
     c = Case(P, px, ob, xcor.svd_filter(ob.data, ob.seg_first, 3))
     assert c.pairs.shape == (55, 800, 2)
-    assert np.array_equal(c.pairs[:, PIXEL, 1] > 0, LAG_KMS <= LIVE_UP_TO)
+    assert np.array_equal(c.pairs[:, xc.PIXEL, 1] > 0, LAG_KMS <= xc.LIVE_UP_TO)
     return c
-
-
-def check_contract(case, E, vm, m, idx, key="plain", cells=None, what=""):
-    """every inside cell (or the cells given) of m against cell_value of run_filtered_moments at its lags, within
-    cell_bound; returns the number of cells that differ in bits"""
-    differ, worst, n = 0, 0.0, 0
-    for i, j in (cells if cells is not None else np.argwhere(np.all(idx >= 0, axis=-1))):
-        mom = case.moments(E, idx[i, j], key)
-        want, bound = xcor.cell_value(mom, vm), xcor.cell_bound(mom, vm)
-        assert np.isfinite(m[i, j]) and bound > 0, (what, vm.stat, i, j)
-        assert abs(m[i, j] - want) <= bound, (what, vm.stat, i, j, m[i, j], want, bound)
-        differ += m[i, j] != want
-        worst = max(worst, abs(m[i, j] - want) / bound)
-        n += 1
-    print("%s %s: %d of %d cells differ in bits from cell_value(run_filtered_moments), worst |map - ref| / cell_bound %.4f" % (what, vm.stat, differ, n, worst))
-    return differ
 
 
 @pytest.mark.parametrize("stat", STATS)
@@ -142,7 +83,7 @@ def test_a_cell_is_the_filtered_moments_at_its_nearest_lags(case, stat):
     E = handle(case)
     for second in (False, True):
         for offset in ((False, True) if not second else (True,)):
-            vm = the_map(stat, second, offset)
+            vm = xc.the_filtered_map(stat, second, offset)
             m, idx = E.run_filtered_map(case.P.atm, case.P.opts, vm, lag_index=True)
             want_idx = xcor.nearest_lags(vm)
             assert idx.dtype == np.int32 and idx.shape == want_idx.shape == (vm.nkp, vm.nvsys, 7)
@@ -152,73 +93,29 @@ def test_a_cell_is_the_filtered_moments_at_its_nearest_lags(case, stat):
             if not second:
                 assert np.array_equal(outside, OUTSIDE)
             else:
-                assert m.size > 2 * CHUNK and m.size % CHUNK != 0 and 0 < np.count_nonzero(outside) < m.size // 2
+                assert m.size > 2 * xc.CHUNK and m.size % xc.CHUNK != 0 and 0 < np.count_nonzero(outside) < m.size // 2
             # the moved pixel's column is live in some inside cells and dead in others
-            live = np.array([[np.all(case.pairs[np.maximum(idx[i, j], 0), PIXEL, 1] > 0) for j in range(vm.nvsys)] for i in range(vm.nkp)])
+            live = np.array([[np.all(case.pairs[np.maximum(idx[i, j], 0), xc.PIXEL, 1] > 0) for j in range(vm.nvsys)] for i in range(vm.nkp)])
             assert np.any(live & ~outside) and np.any(~live & ~outside)
-            differ = check_contract(case, E, vm, m, idx, what="%d cells%s" % (m.size, ", offset" if offset else ""))
+            differ = xc.check_contract(case, E, vm, m, idx, what="%d cells%s" % (m.size, ", offset" if offset else ""))
             if stat != "loglike_bl19":                             # (the expectation, printed; the assertion is the bound)
                 print("%s: the map has the bits of the host's points 5: %s" % (stat, differ == 0))
     E.close()
 
 
-def moment_differences(case, idx):
-    """(mom, D) of a cell for the docstring's propagation: the reference's moments [nexp, nseg, 7] and the most by which the
-    device's can differ from them"""
-    ob, F = case.ob, case.F
-    pr = case.pairs[idx]
-    val, A = xcor.filter_reference(pr, ob, F), xcor.filter_abs_reference(pr, ob, F)
-    mom, S = xcor.reference_values(val, ob), xcor.abs_reference_values(val, ob)
-    tA = (ob.nexp + F.ncomp + 8) * EPS * A
-    lin = xcor.abs_reference_values(tA, ob)                       # sum w tA, sum w tA^2, sum w |f| tA
-    cross = xcor.abs_reference_values(np.sqrt(np.abs(val) * tA), ob)      # sum w |g'| tA
-    D = (int(np.max(np.diff(ob.seg_first))) + 16) * EPS * S
-    D[..., 0] = 0.0
-    D[..., 2] += lin[..., 2]
-    D[..., 3] += 2.0 * cross[..., 3] + lin[..., 3]
-    D[..., 5] += lin[..., 5]
-    return mom, D
-
-
-def row_bounds(mom, D, vm):
-    """[nexp, nseg]: the docstring's first-order bound of the statistic of every row (0 for a row the statistic skips), and the
-    largest relative change of a variance or of the logarithm's argument it rests on"""
-    p0, p1 = vm.params
-    if vm.stat == "chi2":
-        return D[..., 6] + 2 * abs(p0) * D[..., 5] + 2 * abs(p1) * D[..., 4] + p0 * p0 * D[..., 3] + 2 * abs(p0 * p1) * D[..., 2] + p1 * p1 * D[..., 1], 0.0
-    n, sf2, sg2, r, ok = xcor.central(mom)
-    with np.errstate(all="ignore"):
-        s = mom[..., 1]
-        mf, mg = mom[..., 4] / s, mom[..., 2] / s
-        dmf, dmg = (D[..., 4] + np.abs(mf) * D[..., 1]) / s, (D[..., 2] + np.abs(mg) * D[..., 1]) / s
-        dsf2 = (D[..., 6] + mom[..., 6] / s * D[..., 1]) / s + 2 * np.abs(mf) * dmf
-        dsg2 = (D[..., 3] + mom[..., 3] / s * D[..., 1]) / s + 2 * np.abs(mg) * dmg
-        dr = (D[..., 5] + np.abs(mom[..., 5] / s) * D[..., 1]) / s + np.abs(mf) * dmg + np.abs(mg) * dmf
-        small = np.maximum(dsf2 / sf2, dsg2 / sg2)
-        if vm.stat == "ccf":
-            b = dr / np.sqrt(sf2 * sg2) + 0.5 * np.abs(r / np.sqrt(sf2 * sg2)) * (dsf2 / sf2 + dsg2 / sg2)
-        else:
-            arg = sf2 - 2 * p0 * r + p0 * p0 * sg2
-            darg = dsf2 + 2 * abs(p0) * dr + p0 * p0 * dsg2
-            ok = ok & (arg > 0)
-            b = 0.5 * n * darg / arg
-            small = np.maximum(small, darg / arg)
-    return np.where(ok, b, 0.0), float(np.max(np.where(ok, small, 0.0)))
-
-
 @pytest.mark.parametrize("stat", STATS)
 def test_the_map_is_the_definition_in_numpy(case, stat):
     E = handle(case)
-    vm = the_map(stat, offset=True)
+    vm = xc.the_filtered_map(stat, offset=True)
     m, idx = E.run_filtered_map(case.P.atm, case.P.opts, vm, lag_index=True)
     E.close()
     ref = xcor.filtered_map_reference(case.pairs, case.ob, case.F, vm)
     assert np.array_equal(np.isnan(m), OUTSIDE) and np.array_equal(np.isnan(ref), OUTSIDE)
     worst = 0.0
     for i, j in np.argwhere(~OUTSIDE):
-        mom, D = moment_differences(case, idx[i, j])
+        mom, D = xc.moment_differences(case, case.pairs[idx[i, j]])
         assert xcor.cell_value(mom, vm) == ref[i, j]
-        rows, small = row_bounds(mom, D, vm)
+        rows, small = xc.row_bounds(mom, D, vm)
         assert small < 1e-3, (stat, i, j, small)
         tol = 2.0 * float(np.sum(rows)) + xcor.cell_bound(mom, vm)
         assert tol > 0 and abs(m[i, j] - ref[i, j]) <= tol, (stat, i, j, m[i, j], ref[i, j], tol)
@@ -233,18 +130,18 @@ def test_cells_do_not_depend_on_the_rest_of_the_call_or_on_the_handles_history(c
     spec_ref = plain.run(P.atm, P.opts)["spectrum"]
     plain.close()
     for stat in STATS:
-        vm = the_map(stat, offset=True)
+        vm = xc.the_filtered_map(stat, offset=True)
         m = E.run_filtered_map(P.atm, P.opts, vm)
         # one cell alone: another launch, the first place of the only chunk
         for i, j in ((2, 3), (5, 2), (0, 0)):
-            one = E.run_filtered_map(P.atm, P.opts, the_map(stat, offset=True, kp=tv.KP[i:i + 1], vsys=tv.VSYS[j:j + 1]))
+            one = E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map(stat, offset=True, kp=xc.KP[i:i + 1], vsys=xc.VSYS[j:j + 1]))
             assert one.shape == (1, 1) and one[0, 0] == m[i, j], (stat, i, j)
         # the axes reversed: every cell at another place of its chunk -- and, in the 143-cell map, in another chunk
-        rev = E.run_filtered_map(P.atm, P.opts, the_map(stat, offset=True, kp=tv.KP[::-1], vsys=tv.VSYS[::-1]))
+        rev = E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map(stat, offset=True, kp=xc.KP[::-1], vsys=xc.VSYS[::-1]))
         assert np.array_equal(rev[::-1, ::-1], m, equal_nan=True), stat
-        vm2 = the_map(stat, second=True)
+        vm2 = xc.the_filtered_map(stat, second=True)
         m2 = E.run_filtered_map(P.atm, P.opts, vm2)
-        rev2 = E.run_filtered_map(P.atm, P.opts, the_map(stat, second=True, kp=KP2[::-1], vsys=VSYS2[::-1]))
+        rev2 = E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map(stat, second=True, kp=xc.FMAP_KP2[::-1], vsys=xc.FMAP_VSYS2[::-1]))
         assert np.array_equal(rev2[::-1, ::-1], m2, equal_nan=True), stat
         # with and without the table, with and without the spectrum
         a, idx = E.run_filtered_map(P.atm, P.opts, vm, lag_index=True)
@@ -256,8 +153,8 @@ def test_cells_do_not_depend_on_the_rest_of_the_call_or_on_the_handles_history(c
     E.close()
     # fresh, hinted, resuming deeper, hinted again -- the moments from a second handle at the same atmosphere
     E, T = handle(case), handle(case)
-    deep, keep = thinner(P, 1e-3)
-    vm = the_map("loglike_bl19", offset=True)
+    deep, keep = pc.thinner(P, 1e-3)
+    vm = xc.the_filtered_map("loglike_bl19", offset=True)
     seen = set()
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):
         m, idx, spec = E.run_filtered_map(atm, P.opts, vm, lag_index=True, spectrum=True)
@@ -274,26 +171,26 @@ def test_cells_do_not_depend_on_the_rest_of_the_call_or_on_the_handles_history(c
 def test_with_a_highpass_and_a_broadening_installed(case):
     P = case.P
     E = handle(case)
-    plain = {stat: E.run_filtered_map(P.atm, P.opts, the_map(stat)) for stat in STATS}
+    plain = {stat: E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map(stat)) for stat in STATS}
     E.set_highpass(xcor.gaussian_highpass(6.0))
     E.set_broadening(broaden.Rotation(4.0, 0.4))
     for stat in STATS:
-        vm = the_map(stat)
+        vm = xc.the_filtered_map(stat)
         m, idx = E.run_filtered_map(P.atm, P.opts, vm, lag_index=True)
         assert np.array_equal(idx, xcor.nearest_lags(vm)) and np.array_equal(np.isnan(m), OUTSIDE)
         assert np.all(m[~OUTSIDE] != plain[stat][~OUTSIDE])
-        check_contract(case, E, vm, m, idx, key="highpass and broadening", what="high-pass and broadening")
+        xc.check_contract(case, E, vm, m, idx, key="highpass and broadening", what="high-pass and broadening")
     E.set_highpass(None)
     E.set_broadening(None)
     for stat in STATS:
-        assert np.array_equal(E.run_filtered_map(P.atm, P.opts, the_map(stat)), plain[stat], equal_nan=True)
+        assert np.array_equal(E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map(stat)), plain[stat], equal_nan=True)
     E.close()
 
 
 def test_the_trail_and_the_velocity_map_are_unchanged(case):
     P = case.P
     E = handle(case, filt=False)
-    vm = the_map("ccf", offset=True)
+    vm = xc.the_filtered_map("ccf", offset=True)
 
     def neighbours():
         return (E.run_trail(P.atm, P.opts, LAGS),) + E.run_velocity_map(P.atm, P.opts, vm, per=True)
@@ -321,7 +218,7 @@ def test_an_all_zero_filter_on_lag_nodes_is_the_velocity_map(case):
     E.set_filter(xcor.Filter(np.zeros((8, 1, 7)), np.zeros((8, 7, 1))))
     nodes = LAG_KMS[[0, 10, 27, 38, 53]]
     for stat in STATS:
-        vm = the_map(stat, kp=[100.0, 50.0], vsys=nodes, orbit=np.zeros(7))
+        vm = xc.the_filtered_map(stat, kp=[100.0, 50.0], vsys=nodes, orbit=np.zeros(7))
         assert np.array_equal(xcor.nearest_lags(vm)[0, :, 3], [0, 10, 27, 38, 53])
         m, want = E.run_filtered_map(P.atm, P.opts, vm), E.run_velocity_map(P.atm, P.opts, vm)
         assert np.all(np.isfinite(m)) and np.array_equal(m[0], m[1])
@@ -337,7 +234,7 @@ def test_refusals_and_the_batch_form(case):
     dp = _abi.c_double_p
     E = Engine(P.static)
     lib = E._lib
-    vm = the_map("chi2", offset=True)
+    vm = xc.the_filtered_map("chi2", offset=True)
     with pytest.raises(EngineError) as ei:                     # no pixel set, no observed set
         E.run_filtered_map(P.atm, P.opts, vm)
     assert ei.value.code == -1 and "trx_run_filtered_map: no observed set installed (trx_set_observed)" in str(ei.value)
@@ -375,7 +272,7 @@ def test_refusals_and_the_batch_form(case):
     refused(changed(nlag=2 ** 30), "nlag * npix above what one pixel launch takes")
     lag = vm.lag.copy()
     lag[1] = np.nan
-    refused(the_map("chi2", lag=lag).to_c(), "lag 1 must be finite and > 0")
+    refused(xc.the_filtered_map("chi2", lag=lag).to_c(), "lag 1 must be finite and > 0")
     refused(changed(stat=4), "unknown stat 4")
     refused(changed(nkp=0), "nkp < 1 or nvsys < 1")
     refused(changed(nkp=2 ** 16, nvsys=2 ** 15), "nkp * nvsys above 2^31 - 1")
@@ -384,10 +281,10 @@ def test_refusals_and_the_batch_form(case):
     refused(changed(p0=np.nan), "p0 must be finite")
     worse = vm.orbit.copy()
     worse[2] = np.inf
-    refused(the_map("chi2", offset=True, orbit=worse).to_c(), "orbit 2 must be finite")
+    refused(xc.the_filtered_map("chi2", offset=True, orbit=worse).to_c(), "orbit 2 must be finite")
     kms = LAG_KMS.copy()
     kms[3] = kms[2]
-    refused(the_map("chi2", offset=True, lag_kms=kms, lag=vm.lag).to_c(), "lag_kms 3 must be finite and above the one before it (strictly increasing)")
+    refused(xc.the_filtered_map("chi2", offset=True, lag_kms=kms, lag=vm.lag).to_c(), "lag_kms 3 must be finite and above the one before it (strictly increasing)")
     # its own: the index table's size (2^15 x 2^14 cells pass the map's limit; seven exposures of them do not)
     long_kp, long_vsys = np.full(2 ** 15, 100.0), np.zeros(2 ** 14)
     refused(changed(nkp=2 ** 15, nvsys=2 ** 14, kp=long_kp.ctypes.data_as(dp), vsys=long_vsys.ctypes.data_as(dp)), "nkp * nvsys * nexp above 2^31 - 1")
@@ -412,9 +309,9 @@ def test_refusals_and_the_batch_form(case):
         P.set_shard(0, n)
     # the batch form: three atmospheres on two ways, a broadening each
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     rot = [broaden.Rotation(4.0, 0.4), broaden.Rotation(2.5, 0.1), broaden.Rotation(6.0, 0.8)]
-    vm2 = the_map("loglike_bl19", second=True, offset=True)
+    vm2 = xc.the_filtered_map("loglike_bl19", second=True, offset=True)
     ref = []
     for j in range(K):
         E.set_broadening(rot[j])

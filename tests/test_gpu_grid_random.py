@@ -23,7 +23,7 @@ import pytest
 import oracle_lib as ol
 import random_cases
 from cases import rel_err
-from test_gpu_random import check_against_oracle, oracle
+from tolerances import check_against_oracle, oracle
 from transit_amd import _abi, engine, synth
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem

@@ -2,50 +2,34 @@
 trx_batch_set_highpass, include/transit_hip.h) against transit_amd.xcor.highpass_reference, the numpy statement of the
 same definition: BIT EQUALITY, NaN in the same places.
 
-The case is test_gpu_filter's: 6001 bins, 60 layers (20 000 lines where only bits are compared), the seven SHIFTS, the
+The case is xcor_checks' with its straddling pixel: 6001 bins, 60 layers (20 000 lines where only bits are compared), the seven SHIFTS, the
 800-pixel set with its two off-grid pixels and the straddling one, segment lengths [1, 63, 64, 65, 200, 0, 7, 400].  A
 second pixel set has ONE segment of 2 kHpTile + 17 pixels: two full tiles and a ragged one, halos that cross tile borders
 inside a segment, a dead pixel within `half` of a tile border.  Halves 0, 1, 5, 70 (wider than the 63, 64 and 65 pixel
 segments), 450 (wider than every segment of the first set) and 1024 (the cap: the kernel's largest LDS tile).
 
-Downstream the moments are held against xcor over the VALUES THE DEVICE RETURNED, by the rule of test_gpu_filter's
-check_moments -- the count exact, every other moment to (n_max + 16) * 2^-52 of the sum of its absolute terms -- written
+Downstream the moments are held against xcor over the VALUES THE DEVICE RETURNED, by the rule of
+xcor_checks.check_filtered_moments -- the count exact, every other moment to (n_max + 16) * 2^-52 of the sum of its absolute terms -- written
 here as |mom - ref| <= tolerance * scale: a one-pixel segment's g' is exactly 0, its sums of absolute terms with it, and
-such a row must then be exact (the quotient of test_gpu_filter's form is 0 / 0 there).  The filtered values by
-test_gpu_filter.check_values; trail rows and maps against their own contracts, bit for bit."""
+such a row must then be exact (the quotient of that check's form is 0 / 0 there).  The filtered values by
+xcor_checks.check_values; trail rows and maps against their own contracts, bit for bit."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import test_gpu_filter as tf
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_velocity_map as tv
-from test_gpu_bands import band_set, thinner
-from test_gpu_batch import atmospheres
+import pixel_cases as pc
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, broaden, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
+SHIFTS = pc.SHIFTS
 TILE = 512                                             # kHpTile
 LONG = 2 * TILE + 17
 LONG_DEAD = {TILE - 12: 2400.0, 2 * TILE + 3: 2700.0}   # pixel -> centre (cm-1), off the grid: 12 below a tile border, 3 above one
-
-
-def tables(half, seed=0):
-    """a boxcar, a Gaussian and a random table (a fifth of its taps zero) of this half"""
-    rng = np.random.default_rng(1000 + half + seed)
-    rnd = np.concatenate([[0.7], rng.uniform(0.0, 2.0, half) * (rng.random(half) > 0.2)])
-    gauss = np.exp(-(np.arange(half + 1.0) ** 2) / (2.0 * max(half / 3.0, 0.5) ** 2))
-    return {"boxcar": xcor.boxcar_highpass(2 * half + 1), "gauss": xcor.HighPass(gauss), "random": xcor.HighPass(rnd)}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and \
-        np.array_equal(np.where(np.isnan(a), 0.0, a).view(np.uint64), np.where(np.isnan(b), 0.0, b).view(np.uint64))
 
 
 def check_sums(mom, ref, scale, ob, what=""):
@@ -53,12 +37,12 @@ def check_sums(mom, ref, scale, ob, what=""):
     moment within (n_max + 16) * 2^-52 of the scale (exactly where the scale is 0), an empty row seven +0"""
     assert mom.shape == ref.shape == scale.shape
     assert np.array_equal(mom[..., 0], ref[..., 0]), what
-    tol = (int(np.max(np.diff(ob.seg_first))) + 16) * tf.EPS
+    tol = (int(np.max(np.diff(ob.seg_first))) + 16) * xc.EPS
     empty = ref[..., 0] == 0
     assert np.any(empty) and np.all(mom[empty] == 0) and not np.any(np.signbit(mom[empty])), what
     err, size = np.abs(mom - ref)[..., 1:], scale[..., 1:]
     worst = float(np.max(err[size > 0] / size[size > 0]))
-    print("%s: worst |mom - ref| / abs_ref %.3e = %.2f * 2^-52 (tolerance %.3e); %d sums of scale 0" % (what, worst, worst / tf.EPS, tol, np.count_nonzero(size == 0)))
+    print("%s: worst |mom - ref| / abs_ref %.3e = %.2f * 2^-52 (tolerance %.3e); %d sums of scale 0" % (what, worst, worst / xc.EPS, tol, np.count_nonzero(size == 0)))
     assert np.all(err <= tol * size), (what, worst, tol)
 
 
@@ -81,12 +65,12 @@ def long_pixel_set(P):
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
     """(P, px, ob): the eclipse case at 20 000 lines, the 800 pixels with the straddling one, the observed set"""
-    P = tp.make(tmp_path_factory.mktemp("highpass"), "eclipse", nlines=20_000)
-    px = tf.pixel_set(P)
+    P = pc.make(tmp_path_factory.mktemp("highpass"), "eclipse", nlines=20_000)
+    px = xc.straddle_pixel_set(P)
     plain = Engine(P.static)
     scale = float(np.mean(plain.run(P.atm, P.opts)["spectrum"]))
     plain.close()
-    return P, px, tm.observed(len(px), scale)
+    return P, px, xc.observed(len(px), scale)
 
 
 def handle(P, px, ob, hp=None):
@@ -101,14 +85,14 @@ def handle(P, px, ob, hp=None):
 # ---- 1. the values are the definition --------------------------------------------------------------------
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_values_are_the_definition_bit_for_bit(tmp_path, solution):
-    P = tp.make(tmp_path, solution)
+    P = pc.make(tmp_path, solution)
     assert P.nwn == 6001
-    px = tf.pixel_set(P)
+    px = xc.straddle_pixel_set(P)
     plain = Engine(P.static)
-    ob = tm.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])))
     E = handle(P, px, ob)
-    deep, keep = thinner(P, 1e-3)
-    first = tables(5)["gauss"]
+    deep, keep = pc.thinner(P, 1e-3)
+    first = xc.highpass_tables(5)["gauss"]
     seen = set()
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         what = "%s run %d" % (solution, k)
@@ -116,13 +100,13 @@ def test_values_are_the_definition_bit_for_bit(tmp_path, solution):
         val, spec = E.run_highpassed(atm, P.opts, SHIFTS, spectrum=True)      # (the run that meets the handle in that state)
         assert np.array_equal(spec, plain.run(atm, P.opts)["spectrum"]), what
         pairs = E.run_pixels(atm, P.opts, SHIFTS)
-        for p in tf.STRADDLE:                          # on the grid at exactly one shift: dead in six rows, live in one
+        for p in xc.STRADDLE:                          # on the grid at exactly one shift: dead in six rows, live in one
             assert np.count_nonzero(pairs[:, p, 1] > 0) == 1 and pairs[0, p, 1] > 0
         assert same_bits(val, xcor.highpass_reference(pairs, ob, first)), what
         assert np.array_equal(np.isnan(val), ~(pairs[..., 1] > 0)), what
-        assert np.flatnonzero(np.isnan(val).all(axis=0)).tolist() == sorted(tm.OFF_GRID), what
+        assert np.flatnonzero(np.isnan(val).all(axis=0)).tolist() == sorted(xc.OFF_GRID), what
         for half in (0, 1, 5, 70, 450):
-            for name, hp in tables(half, seed=k).items():
+            for name, hp in xc.highpass_tables(half, seed=k).items():
                 assert hp.half == half
                 E.set_highpass(hp)
                 got = E.run_highpassed(atm, P.opts, SHIFTS)
@@ -146,7 +130,7 @@ def test_one_long_segment_of_two_tiles_and_a_ragged_one(case, half):
     shifts = SHIFTS[1:6]                                # (5 rows: not the set's 3 exposures)
     pairs = E.run_pixels(P.atm, P.opts, shifts)
     assert np.all(pairs[:, sorted(LONG_DEAD), 1] == 0) and np.count_nonzero(pairs[..., 1] > 0) == 5 * (LONG - 2)
-    for name, hp in tables(half).items():
+    for name, hp in xc.highpass_tables(half).items():
         E.set_highpass(hp)
         got = E.run_highpassed(P.atm, P.opts, shifts)
         ref = xcor.highpass_reference(pairs, ob, hp)
@@ -158,11 +142,11 @@ def test_one_long_segment_of_two_tiles_and_a_ragged_one(case, half):
 # ---- 2. downstream -----------------------------------------------------------------------------------------
 def test_moments_filter_trail_and_map_take_the_high_passed_model(case):
     P, px, ob = case
-    hp = tables(70)["gauss"]
+    hp = xc.highpass_tables(70)["gauss"]
     E = handle(P, px, ob, hp)
     val = E.run_highpassed(P.atm, P.opts, SHIFTS)
     dead = np.flatnonzero(np.isnan(val).any(axis=0)).tolist()
-    assert dead == tf.DEAD
+    assert dead == xc.DEAD
     # the moments of the values the device returned
     mom = E.run_moments(P.atm, P.opts, SHIFTS)
     check_moments(mom, val, ob, "high-passed moments")
@@ -172,7 +156,7 @@ def test_moments_filter_trail_and_map_take_the_high_passed_model(case):
     F = xcor.svd_filter(ob.data, ob.seg_first, 3)
     E.set_filter(F)
     fmom, fval = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
-    tf.check_values(fval, xcor.highpass_pairs(val), gain_free(ob), F, "filter behind the high-pass")
+    xc.check_values(fval, xcor.highpass_pairs(val), gain_free(ob), F, "filter behind the high-pass")
     assert np.flatnonzero(np.isnan(fval).any(axis=0)).tolist() == dead and np.isnan(fval[:, dead]).all()
     check_moments(fmom, fval, ob, "filtered high-passed moments")
     assert np.array_equal(E.run_moments(P.atm, P.opts, SHIFTS), mom)      # (the filter is the filtered run's alone)
@@ -188,11 +172,11 @@ def test_moments_filter_trail_and_map_take_the_high_passed_model(case):
     tpairs = xcor.highpass_pairs(tval)
     check_sums(trail, xcor.trail_reference(tpairs, gain_free(ob)), xcor.trail_abs_reference(tpairs, gain_free(ob)), ob, "high-passed trail")
     # the map of its own per, bit for bit; per is the statistic of the high-passed trail
-    vm = tv.the_map("ccf")
+    vm = xc.the_map("ccf")
     m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
     assert np.array_equal(m, xcor.map_from_per(per, vm), equal_nan=True)
-    assert np.array_equal(np.isnan(m), tv.OUTSIDE)
-    tv.check_per(per, E.run_trail(P.atm, P.opts, vm.lag), vm, "high-passed trail")
+    assert np.array_equal(np.isnan(m), xc.OUTSIDE)
+    xc.check_per(per, E.run_trail(P.atm, P.opts, vm.lag), vm, "high-passed trail")
     assert not np.array_equal(per, bare.run_velocity_map(P.atm, P.opts, vm, per=True)[1])
     # half = 0, tap 1: g' is +0 at every live pixel -- the three moments with a factor g are +0 in every row
     E.set_highpass(xcor.boxcar_highpass(1))
@@ -206,7 +190,7 @@ def test_moments_filter_trail_and_map_take_the_high_passed_model(case):
 # ---- 3. independence -----------------------------------------------------------------------------------------
 def test_bits_do_not_depend_on_the_rest_of_the_call(case):
     P, px, ob = case
-    hp = tables(70)["random"]
+    hp = xc.highpass_tables(70)["random"]
     E = handle(P, px, ob, hp)
     val = E.run_highpassed(P.atm, P.opts, SHIFTS)
     for _ in range(2):
@@ -240,7 +224,7 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
         assert np.any(val2[0, a:z][live] != val[0, a:z][live]), new
     # through a batch of two ways: each atmosphere's moments are the single handle's
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     shifts = np.stack([np.roll(SHIFTS, j) * (1.0 + 1e-6 * j) for j in range(K)])
     E.set_observed(ob)
     E.set_highpass(hp)
@@ -265,8 +249,8 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
 # ---- 4. nobody else knows --------------------------------------------------------------------------------------
 def test_the_other_runs_do_not_know_of_the_high_pass(case):
     P, px, ob = case
-    E, bare = handle(P, px, ob, tables(5)["boxcar"]), handle(P, px, ob)
-    bs = band_set(P)
+    E, bare = handle(P, px, ob, xc.highpass_tables(5)["boxcar"]), handle(P, px, ob)
+    bs = pc.band_set(P)
     rot = broaden.Rotation.from_beta(1.037e-4)
     lags = SHIFTS[2:5]
     for X in (E, bare):
@@ -281,7 +265,7 @@ def test_the_other_runs_do_not_know_of_the_high_pass(case):
         assert np.array_equal(E.run_broadened(P.atm, P.opts), bare.run_broadened(P.atm, P.opts)), k
         assert not np.array_equal(E.run_moments(P.atm, P.opts, SHIFTS), bare.run_moments(P.atm, P.opts, SHIFTS)), k
     # the broadening is upstream of the high-pass: the values are the definition over the broadened pairs
-    assert same_bits(E.run_highpassed(P.atm, P.opts, SHIFTS), xcor.highpass_reference(bare.run_pixels(P.atm, P.opts, SHIFTS), ob, tables(5)["boxcar"]))
+    assert same_bits(E.run_highpassed(P.atm, P.opts, SHIFTS), xcor.highpass_reference(bare.run_pixels(P.atm, P.opts, SHIFTS), ob, xc.highpass_tables(5)["boxcar"]))
     # cleared: the parent's bits, those of a handle that never had one
     E.set_highpass(None)
     assert np.array_equal(E.run_moments(P.atm, P.opts, SHIFTS), bare.run_moments(P.atm, P.opts, SHIFTS))
@@ -294,7 +278,7 @@ def test_the_other_runs_do_not_know_of_the_high_pass(case):
 
 # ---- 5. refusals and lifetimes ---------------------------------------------------------------------------------
 def test_refusals_and_lifetimes(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=10_000)
+    P = pc.make(tmp_path, "eclipse", nlines=10_000)
     sh = np.ascontiguousarray(SHIFTS[:3])
     good_px = pixels.Pixels([2510.0, 2520.0, 2530.0, 2540.0], [0.2, 0.3, 1.5, 0.4], 4.0)
     rng = np.random.default_rng(2)
@@ -394,7 +378,7 @@ def test_refusals_and_lifetimes(tmp_path):
     E.set_highpass(good)
     unchanged("after set_pixels")
     # independent of the filter: installing or clearing one keeps the high-pass
-    E.set_filter(tf.random_filter(2, 2, 3, seed=6))
+    E.set_filter(xc.random_filter(2, 2, 3, seed=6))
     unchanged("with a filter")
     E.set_filter(None)
     unchanged("filter cleared")

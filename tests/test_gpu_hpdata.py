@@ -3,7 +3,7 @@ transit_amd.xcor.highpass_observed_reference, the numpy mirror of the same defin
 the model side's own kernel (run_highpassed), and, for what the call leaves installed, against a fresh handle that gets the
 same data, weights, basis and high-pass through set_observed, set_weighted_filter and set_highpass.
 
-The case is test_gpu_scatter's: tp.make("eclipse", 20 000 lines), the 800 pixels, 7 and 12 exposures, scatter_cases.the_set at
+The case is observed_cases.build_case's: pixel_cases.make("eclipse", 20 000 lines), the 800 pixels, 7 and 12 exposures, scatter_cases.the_set at
 the model's scale -- over two segmentations (hpdata_cases.SEGS: the eight orders, and one segment of 736 pixels over two
 tiles of 512 with a ragged second one); tests/test_hpdata_host.py holds their preconditions."""
 import ctypes as C
@@ -13,58 +13,31 @@ import numpy as np
 import pytest
 
 import hpdata_cases as hc
-import scatter_cases as cs
-import test_gpu_highpass as th
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
+import observed_cases as oc
+import pixel_cases as pc
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, pixels, xcor
 from transit_amd.engine import Engine, EngineError
 from transit_amd.exposures import Exposures
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
+SHIFTS = pc.SHIFTS
 SHIFTS12 = np.concatenate([SHIFTS, SHIFTS[1:6] * (1.0 + 1e-5)])
 V = xcor.SCATTER_VARIANCE
-same_bits = hc.same_bits
 HP = hc.tables(70)["gauss"]
 
 
-class Case:
-    def __init__(self, P, px, scale):
-        self.P, self.px, self.scale = P, px, scale
-        self.sets = {}
-
-    def observed(self, nexp=7, weighted=True, seg_name="orders"):
-        """the raw observed set, made once"""
-        key = (nexp, weighted, seg_name)
-        if key not in self.sets:
-            gain = np.random.default_rng(60 + nexp).uniform(0.5, 1.5, cs.NPIX)
-            data, w, _ = cs.the_set(nexp, weighted, self.scale)
-            self.sets[key] = xcor.Observed(hc.SEGS[seg_name], data, w, gain)
-        return self.sets[key]
-
-    def handle(self, ob, hp=None):
-        E = Engine(self.P.static)
-        E.set_pixels(self.px)
-        if ob is not None:
-            E.set_observed(ob)
-        if hp is not None:
-            E.set_highpass(hp)
-        return E
+class Case(oc.ScatterCase):
+    def make_observed(self, nexp, weighted, seg_name="orders"):
+        """scatter_cases.the_set cut into the segments of this name"""
+        return super().make_observed(nexp, weighted, hc.SEGS[seg_name])
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("hpdata"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    assert cs.LENGTHS == tm.LENGTHS and len(px) == cs.NPIX
-    E = Engine(P.static)
-    spec = E.run(P.atm, P.opts)["spectrum"]
-    E.close()
-    return Case(P, px, float(np.mean(spec)))
+    return oc.build_case(tmp_path_factory.mktemp("hpdata"), Case)
 
 
 def runs(E, P, shifts=SHIFTS):
@@ -75,13 +48,9 @@ def same_runs(a, b):
     return len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))
 
 
-def same_detrend(a, b):
-    return same_bits(a.basis, b.basis) and same_bits(a.coef, b.coef) and same_bits(a.data, b.data) and a.nsingular == b.nsingular
-
-
 def test_the_tables_are_the_model_sides():
     for half in hc.HALVES:
-        for name, hp in th.tables(half).items():
+        for name, hp in xc.highpass_tables(half).items():
             assert same_bits(hp.taps, hc.tables(half)[name].taps)
 
 
@@ -118,7 +87,7 @@ def test_two_kernels_one_definition(case, nexp, seg_name):
     pairs = M.run_pixels(P.atm, P.opts, shifts)
     a, b = pairs[..., 0], pairs[..., 1]
     live = b > 0
-    assert not live[:, list(tm.OFF_GRID)].any() and np.count_nonzero(live.all(axis=0)) > 700
+    assert not live[:, list(xc.OFF_GRID)].any() and np.count_nonzero(live.all(axis=0)) > 700
     with np.errstate(all="ignore"):
         g = np.where(live, ob.gain[None, :] * (a / np.where(live, b, 1.0)), 0.0)
     D = case.handle(xcor.Observed(ob.seg_first, g, live.astype(np.float64), None))
@@ -140,7 +109,7 @@ def test_two_kernels_one_definition(case, nexp, seg_name):
 def test_what_is_installed(case, seg_name):
     P = case.P
     ob = case.observed(7, True, seg_name)
-    E = case.handle(ob, HP)
+    E = case.handle(ob, hp=HP)
     D = E.detrend_observed(3, niter=2)
     before = runs(E, P)
     R = E.highpass_observed()
@@ -164,7 +133,7 @@ def test_what_is_installed(case, seg_name):
 def test_from_the_detrends_data_and_the_undo(case, weighted):
     P = case.P
     ob = case.observed(7, weighted)
-    E = case.handle(ob, HP)
+    E = case.handle(ob, hp=HP)
     raw_runs = E.run_moments(P.atm, P.opts, SHIFTS)
     undo = E.highpass_observed(apply=False)                  # nothing had been high-passed: TRX_OK
     assert undo.data is None and undo.ndead == 0 and same_bits(E.run_moments(P.atm, P.opts, SHIFTS), raw_runs)
@@ -197,9 +166,9 @@ def test_from_the_detrends_data_and_the_undo(case, weighted):
     # detrend, high-pass, detrend: the second detrend is a fresh handle's single one, and so is what follows it
     E.highpass_observed()
     D2 = E.detrend_observed(3, niter=2)
-    F = case.handle(ob, HP)
+    F = case.handle(ob, hp=HP)
     DF = F.detrend_observed(3, niter=2)
-    assert same_detrend(D2, DF) and same_detrend(D2, D1)
+    assert oc.same_detrend(D2, DF) and oc.same_detrend(D2, D1)
     assert same_runs(runs(E, P), runs(F, P)) and same_runs(runs(E, P), resid)
     F.close()
     # a high-pass over the residuals, then the detrend's undo: the raw set, and the high-pass gone with it
@@ -238,7 +207,7 @@ def test_from_the_detrends_data_and_the_undo(case, weighted):
 def test_the_weigh_reads_the_high_passed_data_and_keeps_its_weights(case):
     P = case.P
     ob = case.observed(7, True)
-    E = case.handle(ob, HP)
+    E = case.handle(ob, hp=HP)
     D = E.detrend_observed(3, niter=2)
     R = E.highpass_observed()
     # detrend, high-pass, weigh: the scatter of r' under W
@@ -256,19 +225,19 @@ def test_the_weigh_reads_the_high_passed_data_and_keeps_its_weights(case):
     assert same_bits(again.data, R.data) and again.ndead == R.ndead and same_runs(runs(E, P), weighed)
     # the weigh's undo does not touch the data
     E.weigh_observed(xcor.SCATTER_NONE)
-    G = case.handle(xcor.Observed(ob.seg_first, R.data, ob.weight, ob.gain), HP)
+    G = case.handle(xcor.Observed(ob.seg_first, R.data, ob.weight, ob.gain), hp=HP)
     G.set_weighted_filter(xcor.WeightedFilter(D.basis))
     assert same_runs(runs(E, P), runs(G, P))
     G.close()
     E.close()
     # weigh, then high-pass, under a plain filter over the raw set: weights and filter stay as they were
     filt = xcor.svd_filter(ob.data, ob.seg_first, 2)
-    E = case.handle(ob, HP)
+    E = case.handle(ob, hp=HP)
     E.set_filter(filt)
     W0 = E.weigh_observed(V, clip=3.0)
     R0 = E.highpass_observed()
     assert same_bits(R0.data, xcor.highpass_observed_reference(ob.data, ob.weight, ob.seg_first, HP)[0])
-    H = case.handle(xcor.Observed(ob.seg_first, R0.data, W0.weight, ob.gain), HP)
+    H = case.handle(xcor.Observed(ob.seg_first, R0.data, W0.weight, ob.gain), hp=HP)
     H.set_filter(filt)
     assert same_runs(runs(E, P), runs(H, P))
     H.close()
@@ -279,7 +248,7 @@ def test_the_weigh_reads_the_high_passed_data_and_keeps_its_weights(case):
 def test_refusals_leave_everything_as_it_was(case):
     P = case.P
     ob = case.observed(7, True)
-    E = case.handle(ob, HP)
+    E = case.handle(ob, hp=HP)
     E.detrend_observed(3, niter=2)
     good = E.highpass_observed()
     ref = runs(E, P)
@@ -350,12 +319,12 @@ def test_injection_high_pass_weights_and_recovery_end_to_end(case):
     w[rng.random((7, 800)) < 0.02] = 0.0
     ob = xcor.Observed(seg, raw, w, rng.uniform(0.5, 1.5, 800))
     hp = xcor.gaussian_highpass(25.0)
-    vm = tv.the_map("ccf", kp=tt.KP, vsys=tt.VSYS)
-    cell = (int(np.argmin(np.abs(tt.KP - tt.KP_TRUE))), int(np.argmin(np.abs(tt.VSYS - tt.VSYS_TRUE))))
+    vm = xc.the_map("ccf", kp=xc.TRAIL_KP, vsys=xc.TRAIL_VSYS)
+    cell = (int(np.argmin(np.abs(xc.TRAIL_KP - xc.KP_TRUE))), int(np.argmin(np.abs(xc.TRAIL_VSYS - xc.VSYS_TRUE))))
     assert cell == (2, 3) and (vm.nkp, vm.nvsys) == (5, 5)
-    shifts = np.array([pixels.shift(v) for v in tt.VSYS_TRUE + tt.KP_TRUE * tv.ORBIT])
+    shifts = np.array([pixels.shift(v) for v in xc.VSYS_TRUE + xc.KP_TRUE * xc.ORBIT])
     p0 = 0.1 / case.scale
-    E = case.handle(ob, hp)
+    E = case.handle(ob, hp=hp)
     E.set_exposures(Exposures(np.ones(7), np.full(7, 2e-6)))
 
     def peak(m):
@@ -370,7 +339,7 @@ def test_injection_high_pass_weights_and_recovery_end_to_end(case):
     # the precondition, on the host from the device's pairs: the numpy chain alone -- inject, SYSREM, high-pass, weigh, map --
     # finds the injected cell, and does not without the injection
     injected = E.run_exposed(P.atm, P.opts, shifts)
-    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in tv.LAGS])
+    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in xc.LAGS])
 
     def host_map(data):
         basis, coef, resid = xcor.sysrem_reference(data, w, seg, 2, 10)
@@ -399,7 +368,7 @@ def test_injection_high_pass_weights_and_recovery_end_to_end(case):
     # every cell has the bits of the same handle's filtered moments at the cell's lags
     for i in range(5):
         for j in range(5):
-            mom = E.run_filtered_moments(P.atm, P.opts, tv.LAGS[idx[i, j]])
+            mom = E.run_filtered_moments(P.atm, P.opts, xc.LAGS[idx[i, j]])
             want = xcor.cell_value(mom, vm)
             assert same_bits(m[i, j], want), (i, j, m[i, j], want)
     E.close()

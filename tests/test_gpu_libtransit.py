@@ -10,7 +10,7 @@ import pytest
 
 import oracle_lib as ol
 from cases import GOLDEN, rel_err
-from test_libtransit import build_driver, copy_case, probes, run_driver
+from host_check import build_driver, copy_case, probes, run_driver
 from transit_amd import build
 
 pytestmark = pytest.mark.gpu

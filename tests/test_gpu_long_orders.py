@@ -2,7 +2,7 @@
 per-cell maps, SYSREM, PCA, the scatter weights, the data-side high-pass and the normalisation (include/transit_hip.h) against
 transit_amd.xcor at many_cases.long_set -- 12 exposures of 1024, 1025, 0, 2049 and 7 pixels.
 
-Every other device test of this chain borrows test_gpu_moments' 800 pixels, whose longest segment is 400 (736 in
+Every other device test of this chain borrows xcor_checks.pixel_set's 800 pixels, whose longest segment is 400 (736 in
 hpdata_cases' "long" cut); the kernels have structure on the pixel axis that only shows at a detector's 2048:
   - k_scatter_median stages a segment's variances kScatLds = 1024 at a time: 1024 is one trip exactly, 1025 a second trip of
     one value padded to kScatTrip = 8 with +infinity, 2049 three trips; the ranks are carried from trip to trip, and the ties
@@ -15,11 +15,11 @@ hpdata_cases' "long" cut); the kernels have structure on the pixel axis that onl
   - k_norm_rowscale selects from a staging array of kNormCap = 2048 keys: 2049 is one above it.
 
 No tolerance here is this file's own.  Every comparison is "the same bits" or one of the derived rules of the tests this file
-borrows its checkers from, evaluated at the set's own nexp, ncomp and longest segment (2049): test_gpu_moments.check_moments
-and test_gpu_trail.check_trail ((n_max + 16) * 2^-52 of the absolute sums), test_gpu_velocity_map.check_per (xcor.per_bound),
-test_gpu_filter.check_values and check_moments, test_gpu_filtered_map.check_contract (xcor.cell_bound) and the propagation of
-its docstring, test_gpu_sysrem.check_outputs, test_gpu_pca.check_outputs, test_gpu_scatter.check_outputs,
-test_gpu_normalise.check_normalised and test_gpu_hpdata's rules (bits).  tests/test_many_cases_host.py holds the set's
+borrows its checkers from, evaluated at the set's own nexp, ncomp and longest segment (2049): xcor_checks.check_moments
+and xcor_checks.check_trail ((n_max + 16) * 2^-52 of the absolute sums), xcor_checks.check_per (xcor.per_bound),
+xcor_checks.check_values and check_filtered_moments, xcor_checks.check_contract (xcor.cell_bound) and the propagation of
+xcor_checks.row_bounds, observed_cases.check_sysrem_outputs, observed_cases.check_pca_outputs, observed_cases.check_scatter_outputs,
+observed_cases.check_normalised and test_gpu_hpdata's rules (bits).  tests/test_many_cases_host.py holds the set's
 preconditions; the *_host.py tests run the kernels' own source on the CPU over the same set against the same mirrors."""
 import numpy as np
 import pytest
@@ -27,28 +27,23 @@ import pytest
 import hpdata_cases as hc
 import many_cases as mc
 import normalise_cases as nc
+import observed_cases as oc
+import pixel_cases as pc
 import scatter_cases as cs
-import test_gpu_filter as tf
-import test_gpu_many_exposures as tme
-import test_gpu_normalise as tn
-import test_gpu_pca as tpc
-import test_gpu_pixels as tp
-import test_gpu_scatter as tsc
-import test_gpu_sysrem as ts
-import test_gpu_wfilter as twf
 import wfilter_cases as wc
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import pixels, xcor
 from transit_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-same_bits = mc.same_bits
 V = xcor.SCATTER_VARIANCE
 HALVES = mc.LONG_HALVES                                  # 0, 5, 70 and 600: more than kHpTile
-HP, RECIPES = tme.HP, tme.RECIPES                        # the Gaussian table of half 70; MEDIAN_RATIO, and quantile 0.9 + divide + clip 3
+HP, RECIPES = oc.HP, oc.RECIPES                          # the Gaussian table of half 70; MEDIAN_RATIO, and quantile 0.9 + divide + clip 3
 
 
-class Case(tme.Case):
+class Case(oc.ManyCase):
     def long(self, weighted=True):
         """(set, planted, pixels, observed set): the long set whose ties are planted with or without the weights, the observed
         set with or without them; the pixel centres as test_gpu_normalise makes its edge set's, one of them off the grid"""
@@ -63,7 +58,7 @@ class Case(tme.Case):
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("long"), "eclipse", nlines=20_000)
+    P = pc.make(tmp_path_factory.mktemp("long"), "eclipse", nlines=20_000)
     E = Engine(P.static)
     spec = E.run(P.atm, P.opts)["spectrum"]
     E.close()
@@ -79,9 +74,9 @@ def long_of(case):
 def test_moments_trail_and_velocity_map(case):
     ms, px, ob = long_of(case)
     E = case.handle(px, ob)
-    trail = tme.check_moments_and_trail(case, E, ms, ob)
-    got = tme.check_velocity_map(case, E, ms, trail)
-    assert all(np.isfinite(got[stat][1]).all() for stat in tme.STATS)
+    trail = oc.check_moments_and_trail(case, E, ms, ob)
+    got = oc.check_velocity_map(case, E, ms, trail)
+    assert all(np.isfinite(got[stat][1]).all() for stat in xc.STATS)
     E.close()
 
 
@@ -90,14 +85,14 @@ def test_plain_filter(case, ncomp):
     P = case.P
     ms, px, ob = long_of(case)
     E = case.handle(px, ob)
-    F = tf.random_filter(ob.nseg, ncomp, ms.nexp, seed=ncomp)
+    F = xc.random_filter(ob.nseg, ncomp, ms.nexp, seed=ncomp)
     E.set_filter(F)
     what = "%s, plain filter of %d" % (ms.name, ncomp)
     pairs = E.run_pixels(P.atm, P.opts, ms.shifts)
     mom, val = E.run_filtered_moments(P.atm, P.opts, ms.shifts, values=True)
-    tf.check_values(val, pairs, ob, F, what)
+    xc.check_values(val, pairs, ob, F, what)
     assert np.flatnonzero(np.isnan(val).any(axis=0)).tolist() == sorted(ms.off_grid) and np.isnan(val[:, sorted(ms.off_grid)]).all()
-    tf.check_moments(mom, val, ob, what)
+    xc.check_filtered_moments(mom, val, ob, what)
     E.close()
 
 
@@ -115,13 +110,13 @@ def test_weighted_filter(case):
     dead[list(ms.off_grid)] = True
     assert np.array_equal(np.isnan(val).any(axis=0), dead) and np.isnan(val[:, dead]).all() and dead[ms.masked_col]
     assert np.count_nonzero(dead) < ms.npix // 4
-    twf.check_moments(mom, val, ob, "%s, weighted filter of 8" % ms.name)
+    xc.check_weighted_moments(mom, val, ob, "%s, weighted filter of 8" % ms.name)
     E.close()
 
 
 @pytest.mark.parametrize("which", ["plain 6", "plain 16", "weighted 8"])
 def test_filtered_map(case, which):
-    tme.check_filtered_map(case, *long_of(case), which)
+    oc.check_filtered_map(case, *long_of(case), which)
 
 
 # ---- SYSREM and PCA ---------------------------------------------------------------------------------------------------
@@ -133,7 +128,7 @@ def test_sysrem(case, ncomp, niter, weighted):
     E = case.handle(px, ob)
     what = "%s, %d components of %d alternations, %s" % (ms.name, ncomp, niter, "edge weights" if weighted else "no weights")
     D = E.detrend_observed(ncomp, niter)
-    ts.check_outputs(D, xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, ncomp, niter), ob, what)
+    oc.check_sysrem_outputs(D, xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, ncomp, niter), ob, what)
     assert np.all(D.basis[2] == 0) and not np.signbit(D.basis[2]).any() and np.all(np.any(D.basis[[0, 1, 3, 4], :, 0] != 0, axis=1)), what
     if weighted:
         row = D.basis[ms.masked_seg, ms.masked_exp]
@@ -155,7 +150,7 @@ def test_sysrem_with_injection(case):
     on = pairs[..., 1] > 0
     assert np.count_nonzero(on) == ms.nexp * (ms.npix - 1) and np.all(f0[on] != ob.data[on])
     D = E.detrend_observed(8, 10, inject=(P.atm, P.opts, ms.shifts, p0, p1))
-    ts.check_outputs(D, xcor.sysrem_reference(f0, ob.weight, ob.seg_first, 8, 10), ob, "%s, injected" % ms.name)
+    oc.check_sysrem_outputs(D, xcor.sysrem_reference(f0, ob.weight, ob.seg_first, 8, 10), ob, "%s, injected" % ms.name)
     assert np.array_equal(D.spectrum, case.spec)
     E.close()
 
@@ -168,7 +163,7 @@ def test_pca(case, ncomp, weighted):
     E = case.handle(px, ob)
     what = "%s, PCA of %d components, %s" % (ms.name, ncomp, "edge weights" if weighted else "no weights")
     D = E.pca_observed(ncomp, 8)
-    tpc.check_outputs(D, xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, 8), ob, what)
+    oc.check_pca_outputs(D, xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, 8), ob, what)
     assert np.all(D.basis[2] == 0) and not np.signbit(D.basis[2]).any() and D.nwhole[2] == 0, what
     for s in mc.LONG_SEGS:
         assert (0 < D.nwhole[s] < ms.lengths[s]) if weighted else (D.nwhole[s] == ms.lengths[s]), what
@@ -198,8 +193,8 @@ def test_weigh_observed(case, weighted):
                     what = "%s, %s, %s, kind %d, clip %g, min_live %d" % (ms.name, "edge weights" if weighted else "no weights", stage, kind, clip, min_live)
                     mirror = xcor.scatter_reference(data, ob.weight, ob.seg_first, kind, clip, min_live)
                     R = E.weigh_observed(kind, clip=clip, min_live=min_live)
-                    tsc.check_outputs(R, mirror, what)
-                    assert R.nsingular == (tsc.nsingular_of(ob, data, mirror[3], D.basis) if D else 0), what
+                    oc.check_scatter_outputs(R, mirror, what)
+                    assert R.nsingular == (oc.nsingular_of(ob, D.basis, data, mirror[3]) if D else 0), what
                     var, med, keep, _ = mirror
                     assert R.median[2] == 0 and not np.signbit(R.median[2]), what
                     if stage == "raw" and min_live == 2:
@@ -265,13 +260,13 @@ def test_normalise_then_detrend_and_pca(case, nm):
     E.set_normalise(nm)
     norm = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm)
     N = E.normalise_observed()
-    tn.check_normalised(N, norm, what)
+    oc.check_normalised(N, norm, what)
     assert np.isfinite(N.data).all() and N.rowscale[ms.masked_exp, ms.masked_seg] == 0 and np.all(N.rowscale[:, 2] == 0) and np.all(N.rowscale[:, 3] > 0), what
     basis, coef, resid = xcor.sysrem_reference(norm[0], ob.weight, ob.seg_first, 3, 10)
     D = E.detrend_observed(3, 10)
-    ts.check_outputs(D, (basis, coef, resid), ob, what)
+    oc.check_sysrem_outputs(D, (basis, coef, resid), ob, what)
     D = E.pca_observed(3, 8)
-    tpc.check_outputs(D, xcor.pca_reference(norm[0], ob.weight, ob.seg_first, 3, 8), ob, what)
+    oc.check_pca_outputs(D, xcor.pca_reference(norm[0], ob.weight, ob.seg_first, 3, 8), ob, what)
     E.set_normalise(None)
     assert not same_bits(E.detrend_observed(3, 10).data, resid)
     print("%s: %d entries clipped, %d bad; SYSREM and PCA of the normalised data are the mirrors'" % (what, N.nclipped, N.nbad))
@@ -288,23 +283,23 @@ def test_the_pipeline_in_order_on_one_handle(case):
     E = case.handle(px, ob)
     pairs = E.run_pixels(P.atm, P.opts, ms.shifts)
     E.set_highpass(HP)
-    E.set_normalise(tn.MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
     fresh = E.run_moments(P.atm, P.opts, ms.shifts)
     p0, p1 = 0.05 / case.scale, 0.9
     f0 = xcor.inject_reference(pairs, ob, p0, p1)
-    norm = xcor.normalise_reference(f0, ob.weight, ob.seg_first, tn.MEDIAN_RATIO)[0]
+    norm = xcor.normalise_reference(f0, ob.weight, ob.seg_first, oc.MEDIAN_RATIO)[0]
     basis, coef, resid = xcor.sysrem_reference(norm, ob.weight, ob.seg_first, 5, 10)
     D = E.detrend_observed(5, 10, inject=(P.atm, P.opts, ms.shifts, p0, p1))
-    ts.check_outputs(D, (basis, coef, resid), ob, "the pipeline's detrend")
+    oc.check_sysrem_outputs(D, (basis, coef, resid), ob, "the pipeline's detrend")
     hpd, ndead = xcor.highpass_observed_reference(resid, ob.weight, ob.seg_first, HP)
     H = E.highpass_observed()
     assert same_bits(H.data, hpd) and H.ndead == ndead
     mirror = xcor.scatter_reference(hpd, ob.weight, ob.seg_first, V, 3.0, 2)
     R = E.weigh_observed(V, clip=3.0)
-    tsc.check_outputs(R, mirror, "the pipeline's weigh")
+    oc.check_scatter_outputs(R, mirror, "the pipeline's weigh")
     vm = ms.the_map("ccf")
     m, idx = E.run_filtered_map(P.atm, P.opts, vm, lag_index=True)
-    assert np.array_equal(idx, xcor.nearest_lags(vm)) and np.array_equal(np.isnan(m), tme.OUTSIDE)
+    assert np.array_equal(idx, xcor.nearest_lags(vm)) and np.array_equal(np.isnan(m), oc.MANY_OUTSIDE)
     F = case.handle(px, xcor.Observed(ob.seg_first, hpd, mirror[3], ob.gain))
     assert F.set_weighted_filter(xcor.WeightedFilter(basis)) == R.nsingular
     F.set_highpass(HP)

@@ -2,9 +2,9 @@
 weighted filter, the per-cell maps, SYSREM, PCA, the scatter weights, the data-side high-pass and the normalisation
 (include/transit_hip.h) against transit_amd.xcor at the sets of many_cases.py.
 
-The other device tests of this chain run at 4 to 12 exposures and at most 12 segments, on test_gpu_moments' 800 pixels in
+The other device tests of this chain run at 4 to 12 exposures and at most 12 segments, on xcor_checks.pixel_set's 800 pixels in
 segments of at most 400; orders of a detector's length -- 1024, 1025 and 2049 pixels -- are tests/test_gpu_long_orders.py's,
-on many_cases.long_set under the same checkers.  Here the pixel set and the segments stay test_gpu_moments' and the other two
+on many_cases.long_set under the same checkers.  Here the pixel set and the segments stay xcor_checks' and the other two
 axes grow:
   - 64, 65 and 130 exposures.  A wave takes the exposures 64 at a time in k_velocity_map and k_cell_stat (the in-order sum
     carried from trip to trip) and in k_sysrem_close's store of the basis; the column kernels take them 4 at a time
@@ -22,11 +22,11 @@ orders sets, where the empty segments on both sides of index 64 and the dead seg
 a sign bit, nwhole 0 and untouched data.
 
 No tolerance here is this file's own.  Every comparison is "the same bits" or one of the derived rules of the tests this
-file borrows its checkers from, evaluated at the set's nexp, ncomp and longest segment: test_gpu_moments.check_moments and
-test_gpu_trail.check_trail ((n_max + 16) * 2^-52 of the absolute sums), test_gpu_velocity_map.check_per (xcor.per_bound),
-test_gpu_filter.check_values and check_moments ((nexp + ncomp + 8) * 2^-52 of A), test_gpu_filtered_map.check_contract
-(xcor.cell_bound), the propagation of test_gpu_filtered_map's docstring for the maps against numpy alone, and
-test_gpu_sysrem.check_outputs, test_gpu_pca.check_outputs, test_gpu_scatter.check_outputs, test_gpu_normalise.check_normalised
+file borrows its checkers from, evaluated at the set's nexp, ncomp and longest segment: xcor_checks.check_moments and
+xcor_checks.check_trail ((n_max + 16) * 2^-52 of the absolute sums), xcor_checks.check_per (xcor.per_bound),
+xcor_checks.check_values and check_filtered_moments ((nexp + ncomp + 8) * 2^-52 of A), xcor_checks.check_contract
+(xcor.cell_bound), the propagation of xcor_checks.row_bounds' docstring for the maps against numpy alone, and
+observed_cases.check_sysrem_outputs, observed_cases.check_pca_outputs, observed_cases.check_scatter_outputs, observed_cases.check_normalised
 and test_gpu_hpdata's rule (bits).  tests/test_many_cases_host.py holds the preconditions of the sets on the host."""
 import numpy as np
 import pytest
@@ -34,201 +34,28 @@ import pytest
 import hpdata_cases as hc
 import many_cases as mc
 import normalise_cases as nc
+import observed_cases as oc
+import pixel_cases as pc
 import scatter_cases as cs
-import test_gpu_exposed_map as tem
-import test_gpu_filter as tf
-import test_gpu_filtered_map as tfm
-import test_gpu_moments as tm
-import test_gpu_normalise as tn
-import test_gpu_pca as tpc
-import test_gpu_pixels as tp
-import test_gpu_scatter as tsc
-import test_gpu_sysrem as ts
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
-import test_gpu_wfilter as twf
 import wfilter_cases as wc
-from test_gpu_batch import atmospheres
-from transit_amd import pixels, xcor
+import xcor_checks as xc
+from bits import same_bits
+from transit_amd import xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-STATS = tv.STATS
-HP = hc.tables(70)["gauss"]
-RECIPES = [tn.MEDIAN_RATIO, xcor.Normalise(xcor.NORM_ROW_QUANTILE, xcor.NORM_COL_DIVIDE, 0.9, 3.0)]
-EPS = 2.0 ** -52
+STATS = xc.STATS
 LAGS = mc.LAGS
-OUTSIDE = np.zeros((3, 4), dtype=bool)
-OUTSIDE[mc.OUTSIDE_CELL] = True
-INSIDE = [(int(i), int(j)) for i, j in np.argwhere(~OUTSIDE)]
-same_bits = mc.same_bits
-
-
-class Case:
-    """the problem, its spectrum's scale, and -- made once, on first use -- the pixel set and the observed set of every set"""
-
-    def __init__(self, P, scale, spec):
-        self.P, self.scale, self.spec = P, scale, spec
-        self.made = {}
-
-    def exposures(self, nexp):
-        """(set, pixels, observed set) of nexp exposures over test_gpu_moments' 800 pixels"""
-        if ("exp", nexp) not in self.made:
-            ms = mc.exposures_set(nexp)
-            assert ms.lengths == tm.LENGTHS and ms.off_grid == tm.OFF_GRID
-            self.made["exp", nexp] = (ms, tm.pixel_set(self.P), ms.observed(self.scale))
-        return self.made["exp", nexp]
-
-    def orders(self, nseg):
-        """(set, pixels, observed set) of nseg segments: pixels of test_gpu_pixels' two kinds (R = 20 000 on the same centres
-        as R = 3000, windows of a lane and of a wave), cut down to the set's, one of them off the grid"""
-        if ("seg", nseg) not in self.made:
-            ms = mc.orders_set(nseg)
-            half = (ms.npix + 1) // 2
-            centres = np.linspace(2503, 2557, half) + 0.37 * float(self.P.static.wn_d)
-            both = tp.joined(pixels.resolving_power(centres, 20000.0, 4.0), pixels.resolving_power(centres, 3000.0, 4.0))
-            px = pixels.Pixels(both.centre[:ms.npix].copy(), both.fwhm[:ms.npix].copy(), both.cut)
-            for p, c in ms.off_grid.items():
-                px.centre[p] = c
-            self.made["seg", nseg] = (ms, px, ms.observed(self.scale))
-        return self.made["seg", nseg]
-
-    def handle(self, px, ob):
-        E = Engine(self.P.static)
-        E.set_pixels(px)
-        E.set_observed(ob)
-        return E
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("many"), "eclipse", nlines=20_000)
+    P = pc.make(tmp_path_factory.mktemp("many"), "eclipse", nlines=20_000)
     E = Engine(P.static)
     spec = E.run(P.atm, P.opts)["spectrum"]
     E.close()
-    return Case(P, float(np.mean(spec)), spec)
-
-
-class Cells:
-    """what test_gpu_filtered_map's checkers take for a case: the observed set, the filter, the pairs at the lags, and the
-    filtered moments of every distinct lag row a map's cells take, made once per handle"""
-
-    def __init__(self, P, ob, F, pairs=None, pairs_lv=None):
-        self.P, self.ob, self.F, self.pairs, self.pairs_lv = P, ob, F, pairs, pairs_lv
-        self.moms, self.refs = {}, {}
-
-    def moments(self, E, idx, key="plain"):
-        k = (key, np.asarray(idx, dtype=np.int64).tobytes())
-        if k not in self.moms:
-            self.moms[k] = E.run_filtered_moments(self.P.atm, self.P.opts, LAGS[idx])
-        return self.moms[k]
-
-    def rows(self, idx):
-        """the pair rows [nexp, npix, 2] of a cell"""
-        return self.pairs[idx] if self.pairs is not None else self.pairs_lv[idx, np.arange(self.ob.nexp)]
-
-    def reference(self, idx):
-        """(mom, D) of a cell by test_gpu_filtered_map's docstring: numpy's moments and the most the device's may differ from
-        them.  Behind a weighted filter the values are the mirror's bit for bit (test_weighted_filter asserts it), so the
-        docstring's tau is 0 and only the moments' own rule is left in D"""
-        k = np.asarray(idx, dtype=np.int64).tobytes()
-        if k not in self.refs:
-            if isinstance(self.F, xcor.WeightedFilter):
-                val = xcor.weighted_filter_reference(self.rows(idx), self.ob, self.F)
-                mom, S = xcor.reference_values(val, self.ob), xcor.abs_reference_values(val, self.ob)
-                D = (int(np.max(np.diff(self.ob.seg_first))) + 16) * EPS * S
-                D[..., 0] = 0.0
-                self.refs[k] = (mom, D)
-            else:
-                self.refs[k] = tem.moment_differences(self, self.rows(idx))
-        return self.refs[k]
-
-
-# ---- what the two kinds of sets share ---------------------------------------------------------------------------
-def check_moments_and_trail(case, E, ms, ob):
-    """run_moments against the definition; run_trail bit for bit against run_moments at three lags and against the definition;
-    returns the trail"""
-    P = case.P
-    pairs = E.run_pixels(P.atm, P.opts, ms.shifts)
-    for p in ms.off_grid:
-        assert np.all(pairs[:, p, 1] == 0)
-    assert np.count_nonzero(pairs[..., 1] > 0) == ms.nexp * (ms.npix - len(ms.off_grid))
-    mom = E.run_moments(P.atm, P.opts, ms.shifts)
-    tm.check_moments(mom, pairs, ob, ms.name)
-    rows = [mom[ms.masked_exp, ms.masked_seg]] + ([mom[:, ms.dead_seg]] if ms.dead_seg is not None else [])
-    for row in rows:                                           # masked over the segment: seven +0, no sign bit
-        assert np.all(row == 0) and not np.signbit(row).any()
-    others = np.delete(np.arange(ms.nexp), ms.masked_exp)
-    assert np.all(mom[others, ms.masked_seg, 0] > 0)
-    trail = E.run_trail(P.atm, P.opts, LAGS)
-    assert trail.shape == (LAGS.size, ms.nexp, ms.nseg, 7)
-    for l in (0, LAGS.size // 2, LAGS.size - 1):
-        assert np.array_equal(trail[l], E.run_moments(P.atm, P.opts, np.full(ms.nexp, LAGS[l]))), (ms.name, l)
-    tt.check_trail(trail, E.run_pixels(P.atm, P.opts, LAGS), ob, "%s, %d lags" % (ms.name, LAGS.size))
-    return trail
-
-
-def check_velocity_map(case, E, ms, trail):
-    """per against trail_statistic of the trail (ccf and chi2 in bits), the map bit for bit map_from_per of that per, NaN in
-    the one outside cell; returns {stat: (map, per)}"""
-    P = case.P
-    out = {}
-    for stat in STATS:
-        vm = ms.the_map(stat)
-        m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
-        want = tv.check_per(per, trail, vm, ms.name)
-        if stat != "loglike_bl19":
-            assert same_bits(per, want), (ms.name, stat)
-        assert same_bits(m, xcor.map_from_per(per, vm)), (ms.name, stat)
-        assert np.array_equal(np.isnan(m), OUTSIDE), (ms.name, stat)
-        out[stat] = (m, per)
-    return out
-
-
-def check_map(E, C, ms, vm, m, idx, what, key="plain"):
-    """a per-cell map: every inside cell against cell_value of run_filtered_moments at its lags within cell_bound, and
-    against numpy alone by the propagation of test_gpu_filtered_map's docstring"""
-    assert np.array_equal(idx, xcor.nearest_lags(vm)) and np.array_equal(np.isnan(m), OUTSIDE), what
-    tfm.check_contract(C, E, vm, m, idx, key=key, what=what)
-    worst = 0.0
-    for i, j in INSIDE:
-        mom, D = C.reference(idx[i, j])
-        ref = xcor.cell_value(mom, vm)
-        rows, small = tfm.row_bounds(mom, D, vm)
-        assert small < 1e-3, (what, vm.stat, i, j, small)
-        tol = 2.0 * float(np.sum(rows)) + xcor.cell_bound(mom, vm)
-        assert tol > 0 and abs(m[i, j] - ref) <= tol, (what, vm.stat, i, j, m[i, j], ref, tol)
-        worst = max(worst, abs(m[i, j] - ref) / tol)
-    print("%s %s: worst |map - numpy| / tolerance %.3e over the %d inside cells" % (what, vm.stat, worst, len(INSIDE)))
-
-
-def install(E, ob, which):
-    """'plain N': tf.random_filter; 'weighted N': a weighted filter of wfilter_cases.random_basis, whose dead count is the
-    mirror's"""
-    kind, ncomp = which.split()
-    if kind == "plain":
-        F = tf.random_filter(ob.nseg, int(ncomp), ob.nexp, seed=20 + int(ncomp))
-        E.set_filter(F)
-    else:
-        F = xcor.WeightedFilter(wc.random_basis(ob.nseg, ob.nexp, int(ncomp), seed=50 + int(ncomp)))
-        assert E.set_weighted_filter(F) == np.count_nonzero(~xcor.weighted_factor(ob, F)[2])
-    return F
-
-
-def check_filtered_map(case, ms, px, ob, which):
-    P = case.P
-    E = case.handle(px, ob)
-    F = install(E, ob, which)
-    C = Cells(P, ob, F, pairs=E.run_pixels(P.atm, P.opts, LAGS))
-    for stat in STATS:
-        vm = ms.the_map(stat)
-        m, idx = E.run_filtered_map(P.atm, P.opts, vm, lag_index=True)
-        check_map(E, C, ms, vm, m, idx, "%s, %s, filtered map" % (ms.name, which))
-        if stat == "ccf":                                      # the cells' references are the definition's own
-            ref = xcor.filtered_map_reference(C.pairs, ob, F, vm)
-            assert np.array_equal(np.isnan(ref), OUTSIDE) and all(ref[c] == xcor.cell_value(C.reference(idx[c])[0], vm) for c in INSIDE)
-    E.close()
+    return oc.ManyCase(P, float(np.mean(spec)), spec)
 
 
 # ---- many exposures ------------------------------------------------------------------------------------------------
@@ -236,7 +63,7 @@ def check_filtered_map(case, ms, px, ob, which):
 def test_moments_and_trail(case, nexp):
     ms, px, ob = case.exposures(nexp)
     E = case.handle(px, ob)
-    check_moments_and_trail(case, E, ms, ob)
+    oc.check_moments_and_trail(case, E, ms, ob)
     E.close()
 
 
@@ -245,7 +72,7 @@ def test_velocity_map(case, nexp):
     P = case.P
     ms, px, ob = case.exposures(nexp)
     E = case.handle(px, ob)
-    got = check_velocity_map(case, E, ms, E.run_trail(P.atm, P.opts, LAGS))
+    got = oc.check_velocity_map(case, E, ms, E.run_trail(P.atm, P.opts, LAGS))
     if nexp > 64:
         # an exposure below 64 exchanged with one above it, orbit and data together: the same terms in another order, other bits
         a, b = 10, {65: 64, 130: 100}[nexp]
@@ -256,8 +83,8 @@ def test_velocity_map(case, nexp):
         vm = sw.the_map("ccf")
         m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
         assert same_bits(per, got["ccf"][1][:, perm])
-        assert same_bits(m, xcor.map_from_per(per, vm)) and np.array_equal(np.isnan(m), OUTSIDE)
-        differ = np.count_nonzero(m[~OUTSIDE] != got["ccf"][0][~OUTSIDE])
+        assert same_bits(m, xcor.map_from_per(per, vm)) and np.array_equal(np.isnan(m), oc.MANY_OUTSIDE)
+        differ = np.count_nonzero(m[~oc.MANY_OUTSIDE] != got["ccf"][0][~oc.MANY_OUTSIDE])
         print("%s: exposures %d and %d exchanged: %d of 11 cells change their bits" % (ms.name, a, b, differ))
         assert differ > 0
     E.close()
@@ -269,14 +96,14 @@ def test_plain_filter(case, nexp, ncomp):
     P = case.P
     ms, px, ob = case.exposures(nexp)
     E = case.handle(px, ob)
-    F = tf.random_filter(ob.nseg, ncomp, nexp, seed=ncomp)
+    F = xc.random_filter(ob.nseg, ncomp, nexp, seed=ncomp)
     E.set_filter(F)
     what = "%s, plain filter of %d" % (ms.name, ncomp)
     pairs = E.run_pixels(P.atm, P.opts, ms.shifts)
     mom, val = E.run_filtered_moments(P.atm, P.opts, ms.shifts, values=True)
-    tf.check_values(val, pairs, ob, F, what)
+    xc.check_values(val, pairs, ob, F, what)
     assert np.flatnonzero(np.isnan(val).any(axis=0)).tolist() == sorted(ms.off_grid) and np.isnan(val[:, sorted(ms.off_grid)]).all()
-    tf.check_moments(mom, val, ob, what)
+    xc.check_filtered_moments(mom, val, ob, what)
     E.close()
 
 
@@ -296,14 +123,14 @@ def test_weighted_filter(case, nexp, ncomp):
     dead[list(ms.off_grid)] = True
     assert np.array_equal(np.isnan(val).any(axis=0), dead) and np.isnan(val[:, dead]).all() and dead[ms.masked_col]
     assert np.count_nonzero(dead) < ms.npix // 4
-    twf.check_moments(mom, val, ob, "%s, weighted filter of %d" % (ms.name, ncomp))
+    xc.check_weighted_moments(mom, val, ob, "%s, weighted filter of %d" % (ms.name, ncomp))
     E.close()
 
 
 @pytest.mark.parametrize("which", ["plain 6", "plain 16", "weighted 8"])
 @pytest.mark.parametrize("nexp", mc.NEXPS)
 def test_filtered_map(case, nexp, which):
-    check_filtered_map(case, *case.exposures(nexp), which)
+    oc.check_filtered_map(case, *case.exposures(nexp), which)
 
 
 @pytest.mark.parametrize("which", ["plain 6", "plain 16", "weighted 8"])
@@ -313,21 +140,21 @@ def test_exposed_map(case, nexp, which):
     P = case.P
     ms, px, ob = case.exposures(nexp)
     E = case.handle(px, ob)
-    F = install(E, ob, which)
+    F = oc.install(E, ob, which)
     E.set_exposures(ms.table())
-    C = Cells(P, ob, F, pairs_lv=np.stack([E.run_exposed(P.atm, P.opts, np.full(nexp, s)) for s in LAGS]))
+    C = oc.Cells(P, ob, F, pairs_lv=np.stack([E.run_exposed(P.atm, P.opts, np.full(nexp, s)) for s in LAGS]))
     zero = np.flatnonzero(ms.scale == 0)
     assert np.all(C.pairs_lv[:, zero, :, 0] == 0) and np.all(C.pairs_lv[:, np.flatnonzero(ms.scale != 0)][:, :, 0, 0] != 0)
     for stat in STATS:
         vm = ms.the_map(stat)
         m, idx, R = E.run_exposed_map(P.atm, P.opts, vm, lag_index=True, nrows=True)
         assert R == xcor.exposed_map_rows(vm)[3] and nexp <= R < nexp * LAGS.size
-        check_map(E, C, ms, vm, m, idx, "%s, %s, exposed map" % (ms.name, which), key="table")
+        oc.check_map(E, C, ms, vm, m, idx, "%s, %s, exposed map" % (ms.name, which), key="table")
         if stat == "ccf":
             ref = xcor.exposed_map_reference(C.pairs_lv, ob, F, vm)
-            assert np.array_equal(np.isnan(ref), OUTSIDE) and all(ref[c] == xcor.cell_value(C.reference(idx[c])[0], vm) for c in INSIDE)
+            assert np.array_equal(np.isnan(ref), oc.MANY_OUTSIDE) and all(ref[c] == xcor.cell_value(C.reference(idx[c])[0], vm) for c in oc.MANY_INSIDE)
             plain = E.run_filtered_map(P.atm, P.opts, vm)      # the table matters
-            assert np.all(plain[~OUTSIDE] != m[~OUTSIDE])
+            assert np.all(plain[~oc.MANY_OUTSIDE] != m[~oc.MANY_OUTSIDE])
     E.close()
 
 
@@ -341,7 +168,7 @@ def test_sysrem(case, nexp, ncomp, niter, weighted):
     what = "%s, %d components of %d alternations, %s" % (ms.name, ncomp, niter, "edge weights" if weighted else "no weights")
     D = E.detrend_observed(ncomp, niter)
     mirror = xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, ncomp, niter)
-    ts.check_outputs(D, mirror, ob, what)
+    oc.check_sysrem_outputs(D, mirror, ob, what)
     assert np.all(D.basis[5] == 0) and np.all(np.any(D.basis[[0, 1, 2, 3, 4, 6, 7], :, 0] != 0, axis=1)), what
     if weighted:
         row = D.basis[ms.masked_seg, ms.masked_exp]
@@ -367,7 +194,7 @@ def test_sysrem_with_injection_and_what_it_installs(case, nexp):
     assert np.count_nonzero(on) == nexp * 798 and np.all(f0[on] != ob.data[on])
     basis, coef, resid = xcor.sysrem_reference(f0, ob.weight, ob.seg_first, 8, 10)
     D = E.detrend_observed(8, 10, inject=(P.atm, P.opts, ms.shifts, p0, p1))
-    ts.check_outputs(D, (basis, coef, resid), ob, "%s, injected under the table" % ms.name)
+    oc.check_sysrem_outputs(D, (basis, coef, resid), ob, "%s, injected under the table" % ms.name)
     assert np.array_equal(D.spectrum, case.spec)
     got = E.run_filtered_moments(P.atm, P.opts, ms.shifts, values=True)
     E.close()
@@ -391,8 +218,8 @@ def weigh_raw_and_detrended(E, ob, ncomp, niter, what):
         for kind in cs.KINDS:
             mirror = xcor.scatter_reference(data, ob.weight, ob.seg_first, kind, 3.0, 2)
             R = E.weigh_observed(kind, clip=3.0)
-            tsc.check_outputs(R, mirror, "%s, %s, kind %d" % (what, stage, kind))
-            assert R.nsingular == (tsc.nsingular_of(ob, data, mirror[3], D.basis) if D else 0), (what, stage, kind)
+            oc.check_scatter_outputs(R, mirror, "%s, %s, kind %d" % (what, stage, kind))
+            assert R.nsingular == (oc.nsingular_of(ob, D.basis, data, mirror[3]) if D else 0), (what, stage, kind)
             if not D:
                 raw.append(R)
     return raw
@@ -413,10 +240,10 @@ def highpass_raw_and_detrended(E, ob, ncomp, niter, what):
 
 
 def normalise_both_recipes(E, ob, what):
-    for nm in RECIPES:
+    for nm in oc.RECIPES:
         E.set_normalise(nm)
         N = E.normalise_observed()
-        tn.check_normalised(N, xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm), "%s, %s" % (what, nc.name(nm)))
+        oc.check_normalised(N, xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm), "%s, %s" % (what, nc.name(nm)))
         assert np.isfinite(N.data).all()
     E.set_normalise(None)
 
@@ -457,7 +284,7 @@ def test_pca(case, nexp, ncomp, weighted):
     what = "%s, PCA of %d components, %s" % (ms.name, ncomp, "edge weights" if weighted else "no weights")
     mirror = xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, 8)
     D = E.pca_observed(ncomp, 8)
-    tpc.check_outputs(D, mirror, ob, what)
+    oc.check_pca_outputs(D, mirror, ob, what)
     nwhole = mirror[5]
     assert np.array_equal(D.nwhole, nwhole) and (weighted or np.array_equal(nwhole, ms.lengths)), what
     for s in range(ms.nseg):
@@ -484,14 +311,14 @@ def test_pca_above_its_cap_is_refused(case):
 def test_orders_moments_trail_and_velocity_map(case, nseg):
     ms, px, ob = case.orders(nseg)
     E = case.handle(px, ob)
-    trail = check_moments_and_trail(case, E, ms, ob)
+    trail = oc.check_moments_and_trail(case, E, ms, ob)
     # the dead segment's statistic is undefined in the mirror and skipped on the device: per is finite all the same
     empty = np.flatnonzero(np.array(ms.lengths) == 0)
     for stat in ("ccf", "loglike_bl19"):
         st = ms.the_map(stat).statistic(trail)
         assert np.isnan(st[:, :, ms.dead_seg]).all() and np.isnan(st[:, :, empty]).all()
         assert np.isfinite(st[:, 0, 5]).all() and np.isnan(st[:, ms.masked_exp, ms.masked_seg]).all()
-    got = check_velocity_map(case, E, ms, trail)
+    got = oc.check_velocity_map(case, E, ms, trail)
     for stat in STATS:
         assert np.isfinite(got[stat][1]).all()
     E.close()
@@ -499,7 +326,7 @@ def test_orders_moments_trail_and_velocity_map(case, nseg):
 
 @pytest.mark.parametrize("nseg", mc.NSEGS)
 def test_orders_filtered_map(case, nseg):
-    check_filtered_map(case, *case.orders(nseg), "plain %d" % mc.ORDERS_NCOMP)
+    oc.check_filtered_map(case, *case.orders(nseg), "plain %d" % mc.ORDERS_NCOMP)
 
 
 @pytest.mark.parametrize("nseg", mc.NSEGS)
@@ -507,7 +334,7 @@ def test_orders_sysrem(case, nseg):
     ms, px, ob = case.orders(nseg)
     E = case.handle(px, ob)
     D = E.detrend_observed(mc.ORDERS_NCOMP, 10)
-    ts.check_outputs(D, xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 10), ob, ms.name)
+    oc.check_sysrem_outputs(D, xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 10), ob, ms.name)
     lengths = np.array(ms.lengths)
     empty = np.flatnonzero(lengths == 0)
     assert empty.min() < 64 and (nseg < 130 or empty.max() > 64)
@@ -534,7 +361,7 @@ def test_orders_pca(case, nseg):
     E = case.handle(px, ob)
     mirror = xcor.pca_reference(ob.data, ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 8)
     D = E.pca_observed(mc.ORDERS_NCOMP, 8)
-    tpc.check_outputs(D, mirror, ob, ms.name)
+    oc.check_pca_outputs(D, mirror, ob, ms.name)
     empty, dead = orders_edges(ms, nseg)
     for s in list(empty) + [ms.dead_seg]:
         assert np.all(D.basis[s] == 0) and not np.signbit(D.basis[s]).any() and D.nwhole[s] == 0 and np.all(D.eigen[s] == 0) and D.offdiag[s] == 0, s
@@ -566,7 +393,7 @@ def test_orders_highpass_observed(case, nseg):
     ms, px, ob = case.orders(nseg)
     E = case.handle(px, ob)
     highpass_raw_and_detrended(E, ob, mc.ORDERS_NCOMP, 10, ms.name)
-    E.set_highpass(HP)
+    E.set_highpass(oc.HP)
     R = E.highpass_observed()
     empty, dead = orders_edges(ms, nseg)
     assert np.all(R.data[:, dead] == 0) and not np.signbit(R.data[:, dead]).any()      # dead entries are +0
@@ -579,14 +406,14 @@ def test_orders_normalise_observed(case, nseg):
     ms, px, ob = case.orders(nseg)
     E = case.handle(px, ob)
     normalise_both_recipes(E, ob, ms.name)
-    E.set_normalise(tn.MEDIAN_RATIO)
-    norm = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, tn.MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
+    norm = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, oc.MEDIAN_RATIO)
     empty, dead = orders_edges(ms, nseg)
     assert np.all(norm[1][:, list(empty) + [ms.dead_seg]] == 0) and np.all(norm[0][:, dead] == 0) and not np.signbit(norm[0][:, dead]).any()
     D = E.detrend_observed(mc.ORDERS_NCOMP, 10)
-    ts.check_outputs(D, xcor.sysrem_reference(norm[0], ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 10), ob, ms.name)
+    oc.check_sysrem_outputs(D, xcor.sysrem_reference(norm[0], ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 10), ob, ms.name)
     D = E.pca_observed(mc.ORDERS_NCOMP, 8)
-    tpc.check_outputs(D, xcor.pca_reference(norm[0], ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 8), ob, ms.name)
+    oc.check_pca_outputs(D, xcor.pca_reference(norm[0], ob.weight, ob.seg_first, mc.ORDERS_NCOMP, 8), ob, ms.name)
     E.close()
 
 
@@ -594,7 +421,7 @@ def test_orders_batch_of_two_ways(case):
     P = case.P
     ms, px, ob = case.orders(130)
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     vm = ms.the_map("loglike_bl19")
     one = case.handle(px, ob)
     ref = [one.run_velocity_map(atms[j], P.opts, vm, per=True) for j in range(K)]

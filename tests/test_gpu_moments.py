@@ -2,7 +2,7 @@
 trx_run_moments and the batch forms, include/transit_hip.h) against transit_amd.xcor, the numpy statement of the
 same definition.
 
-The case is test_gpu_pixels' (40 000 lines, 6001 bins, 60 layers), the pixel set its 800-pixel joined set A + B
+The case is pixel_cases.make's (40 000 lines, 6001 bins, 60 layers), the pixel set its 800-pixel joined set A + B
 (windows of 42-44 and of 283-290 bins: both forms of the pair kernel), the shifts its seven.  Two of the 800 pixels
 (one in A, one in B) are moved off the grid, to 2400 and 2700 cm-1: their pairs have b = 0 and count in no moment.
 Segment lengths [1, 63, 64, 65, 200, 0, 7, 400]: one lane, a wave less one, a wave, a wave plus one, several
@@ -24,82 +24,41 @@ import shutil
 import numpy as np
 import pytest
 
-import test_gpu_pixels as tp
+import pixel_cases as pc
+import xcor_checks as xc
 from cases import GOLDEN
-from test_gpu_bands import grid, thinner
-from test_gpu_batch import atmospheres
 from transit_amd import _abi, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-LENGTHS = [1, 63, 64, 65, 200, 0, 7, 400]
-OFF_GRID = {250: 2400.0, 700: 2700.0}          # pixel -> centre (cm-1): one of set A, one of set B
-EPS = 2.0 ** -52
-
-
-def pixel_set(P):
-    px = tp.joined(tp.set_a(P), tp.set_b(P))
-    assert len(px) == 800 == sum(LENGTHS)
-    for p, c in OFF_GRID.items():
-        px.centre[p] = c
-    return px
-
-
-def observed(npix, scale, lengths=LENGTHS, nexp=len(SHIFTS), seed=3):
-    """data around the model's scale, less their mean (so that sum w f g has both signs), weights in [0.5, 2] with
-    5 % exact zeros, gains in [0.5, 1.5]"""
-    rng = np.random.default_rng(seed)
-    f = scale * (1.0 + 0.1 * rng.standard_normal((nexp, npix)))
-    f -= f.mean()
-    w = rng.uniform(0.5, 2.0, (nexp, npix))
-    w[rng.random((nexp, npix)) < 0.05] = 0.0
-    return xcor.Observed(xcor.segments(lengths), f, w, rng.uniform(0.5, 1.5, npix))
-
-
-def check_moments(mom, pairs, ob, what=""):
-    """the count exactly, every other moment to (n_max + 16) * 2^-52 of the sum of its absolute terms; an empty row is
-    seven +0"""
-    ref, scale = xcor.reference(pairs, ob), xcor.abs_reference(pairs, ob)
-    assert mom.shape == ref.shape == (ob.nexp, ob.nseg, 7)
-    assert np.array_equal(mom[..., 0], ref[..., 0]), what
-    n_max = int(np.max(np.diff(ob.seg_first)))
-    tol = (n_max + 16) * EPS
-    empty = ref[..., 0] == 0
-    assert np.all(mom[empty] == 0) and not np.any(np.signbit(mom[empty])), what
-    err = np.abs(mom - ref)[~empty][:, 1:]
-    ratio = err / scale[~empty][:, 1:]
-    worst = float(ratio.max())
-    print("%s: worst |mom - ref| / abs_ref %.3e = %.2f * 2^-52 (tolerance %.3e)" % (what, worst, worst / EPS, tol))
-    assert worst <= tol, (what, worst, tol)
-    return ref
+SHIFTS = pc.SHIFTS
 
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_moments_are_the_definition_over_the_pixel_pairs(tmp_path, solution):
-    P = tp.make(tmp_path, solution)
+    P = pc.make(tmp_path, solution)
     assert P.nwn == 6001
-    px = pixel_set(P)
+    px = xc.pixel_set(P)
     plain, E, only = Engine(P.static), Engine(P.static), Engine(P.static)
     scale = float(np.mean(plain.run(P.atm, P.opts)["spectrum"]))
-    ob = observed(len(px), scale)
+    ob = xc.observed(len(px), scale)
     assert (ob.nexp, ob.nseg) == (7, 8) and np.count_nonzero(ob.weight == 0) > 100
     for X in (E, only):
         X.set_pixels(px)
         X.set_observed(ob)
-    deep, keep = thinner(P, 1e-3)
+    deep, keep = pc.thinner(P, 1e-3)
     signs = set()
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         spec_ref = plain.run(atm, P.opts)["spectrum"]
         pairs = E.run_pixels(atm, P.opts, SHIFTS)
         mom, spec = E.run_moments(atm, P.opts, SHIFTS, spectrum=True)
         assert np.array_equal(spec, spec_ref)
-        for p in OFF_GRID:
+        for p in xc.OFF_GRID:
             assert np.all(pairs[:, p, 1] == 0)
         assert np.count_nonzero(pairs[..., 1] > 0) == 7 * 798
-        ref = check_moments(mom, pairs, ob, "%s run %d" % (solution, k))
+        ref = xc.check_moments(mom, pairs, ob, "%s run %d" % (solution, k))
         want_n = np.add.reduceat(((pairs[..., 1] > 0) & (ob.weight > 0)).astype(float), ob.seg_first[:-1][np.diff(ob.seg_first) > 0], axis=1)
         assert np.array_equal(mom[..., 0][:, np.diff(ob.seg_first) > 0], want_n)
         signs |= set(np.sign(ref[..., xcor.WFG]).ravel().tolist())
@@ -110,18 +69,18 @@ def test_moments_are_the_definition_over_the_pixel_pairs(tmp_path, solution):
     ob2 = xcor.Observed(xcor.segments([300, 200, 300]), ob.data)
     E.set_observed(ob2)
     mom = E.run_moments(P.atm, P.opts, SHIFTS)
-    check_moments(mom, E.run_pixels(P.atm, P.opts, SHIFTS), ob2, "%s [300, 200, 300], w = gain = 1" % solution)
+    xc.check_moments(mom, E.run_pixels(P.atm, P.opts, SHIFTS), ob2, "%s [300, 200, 300], w = gain = 1" % solution)
     assert mom[0, :, 0].tolist() == [299.0, 200.0, 299.0] and np.array_equal(mom[..., 1], mom[..., 0])
     plain.close(); E.close(); only.close()
 
 
 def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=20_000)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "eclipse", nlines=20_000)
+    px = xc.pixel_set(P)
     E = Engine(P.static)
     E.set_pixels(px)
     scale = float(np.mean(E.run(P.atm, P.opts)["spectrum"]))
-    ob = observed(len(px), scale)
+    ob = xc.observed(len(px), scale)
     E.set_observed(ob)
     first = E.run_moments(P.atm, P.opts, SHIFTS)
     assert np.all(first[:, 5] == 0) and np.all(first[:, [1, 2, 3, 4, 7], 0] > 0)
@@ -157,12 +116,12 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
 
 
 def test_chi_square_and_likelihood_end_to_end(tmp_path):
-    P = tp.make(tmp_path, "transit", nlines=20_000)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "transit", nlines=20_000)
+    px = xc.pixel_set(P)
     E = Engine(P.static)
     E.set_pixels(px)
     scale = float(np.mean(E.run(P.atm, P.opts)["spectrum"]))
-    ob = observed(len(px), scale, seed=9)
+    ob = xc.observed(len(px), scale, seed=9)
     E.set_observed(ob)
     pairs = E.run_pixels(P.atm, P.opts, SHIFTS)
     mom = E.run_moments(P.atm, P.opts, SHIFTS)
@@ -170,7 +129,7 @@ def test_chi_square_and_likelihood_end_to_end(tmp_path):
     with np.errstate(invalid="ignore", divide="ignore"):
         g = ob.gain[None, :] * pixels.value(pairs)
     f, w = ob.data, ob.weight
-    tol = (max(LENGTHS) + 32) * EPS
+    tol = (max(xc.LENGTHS) + 32) * xc.EPS
     for a, b in ((1.0, 0.0), (0.8, 0.05 * scale)):
         got = xcor.chi2(mom, a, b)
         worst = 0.0
@@ -211,14 +170,14 @@ def test_chi_square_and_likelihood_end_to_end(tmp_path):
 
 
 def test_batch_moments_are_the_single_handle_moments(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=30_000, seed=33)
-    px = pixel_set(P)
+    P = pc.make(tmp_path, "eclipse", nlines=30_000, seed=33)
+    px = xc.pixel_set(P)
     K = 4
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     shifts = np.stack([np.roll(SHIFTS, j) * (1.0 + 1e-6 * j) for j in range(K)])
     one = Engine(P.static)
     one.set_pixels(px)
-    ob = observed(len(px), float(np.mean(one.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(one.run(P.atm, P.opts)["spectrum"])))
     one.set_observed(ob)
     ref = np.stack([one.run_moments(atms[j], P.opts, shifts[j]) for j in range(K)])
     one.close()
@@ -241,26 +200,26 @@ def test_opacity_grid_handle(tmp_path):
     builder.build_opacity_grid(P)
     builder.close()
     assert P.static.ogrid
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     centres = np.linspace(wn[0] + 1.0, wn[-1] - 1.0, 25) + 0.37 * wn_d
-    px = tp.joined(pixels.resolving_power(centres, 1000.0), pixels.resolving_power(centres, 100.0))
+    px = pc.joined(pixels.resolving_power(centres, 1000.0), pixels.resolving_power(centres, 100.0))
     shifts = np.array([1.0, 1.0 - 150.0 / 299792.458, 1.0 + 150.0 / 299792.458, 0.9991])
     plain, E = Engine(P.static), Engine(P.static)
     E.set_pixels(px)
-    ob = observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])), lengths=[10, 0, 15, 25], nexp=4)
+    ob = xc.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])), lengths=[10, 0, 15, 25], nexp=4)
     E.set_observed(ob)
     for k in range(2):
         ref = plain.run(P.atm, P.opts)["spectrum"]
         pairs = E.run_pixels(P.atm, P.opts, shifts)
         mom, spec = E.run_moments(P.atm, P.opts, shifts, spectrum=True)
         assert np.array_equal(spec, ref)
-        check_moments(mom, pairs, ob, "opacity grid run %d" % k)
+        xc.check_moments(mom, pairs, ob, "opacity grid run %d" % k)
         assert np.array_equal(E.run(P.atm, P.opts)["spectrum"], ref)
     plain.close(); E.close()
 
 
 def test_refusals_and_lifetimes(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=10_000)
+    P = pc.make(tmp_path, "eclipse", nlines=10_000)
     sh = np.ascontiguousarray(SHIFTS[:3])
     good_px = pixels.Pixels([2510.0, 2520.0, 2530.0, 2540.0], [0.2, 0.3, 1.5, 0.4], 4.0)
     rng = np.random.default_rng(2)

@@ -7,7 +7,7 @@ all-equal row, negative values, a masked row, rows whose quantile is <= 0) at 1,
 with a recipe installed against sysrem_reference and pca_reference of the mirror's data, with and without injection; the
 state the three calls share; and the refusals by code and message.
 
-The problem is test_gpu_sysrem's: tp.make("eclipse", 20 000 lines, 6001 bins) and its 800 pixels.  The refusals of
+The problem is observed_cases.build_case's: pixel_cases.make("eclipse", 20 000 lines, 6001 bins) and its 800 pixels.  The refusals of
 trx_normalise_observed's injection arguments are trx_detrend_observed's own code path (detrend_inject_checks), and its
 refusal of a shard cannot be reached on a device -- no recipe can be installed on a shard, and "no recipe" is checked
 first --: tests/normalise_check.cpp holds their text and their order on the host."""
@@ -17,60 +17,34 @@ import numpy as np
 import pytest
 
 import normalise_cases as nc
+import observed_cases as oc
+import pixel_cases as pc
 import sysrem_cases as sc
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
+from bits import same_bits
 from transit_amd import _abi, pixels, xcor
 from transit_amd.engine import Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-same_bits = sc.same_bits
+SHIFTS = pc.SHIFTS
 Q, NONE = xcor.NORM_ROW_QUANTILE, xcor.NORM_ROW_NONE
-RATIO, DIVIDE, SUBTRACT = xcor.NORM_COL_RATIO, xcor.NORM_COL_DIVIDE, xcor.NORM_COL_SUBTRACT
-MEDIAN_RATIO = xcor.Normalise(Q, RATIO, 0.5, 0.0)
+DIVIDE, SUBTRACT = xcor.NORM_COL_DIVIDE, xcor.NORM_COL_SUBTRACT
 
 
-class Case:
-    def __init__(self, P, px, scale, spec):
-        self.P, self.px, self.scale, self.spec = P, px, scale, spec
+class Case(oc.SysremCase):
+    def __init__(self, *a):
+        super().__init__(*a)
         self.edge_px = pixels.resolving_power(np.linspace(2503.0, 2557.0, nc.NPIX), 20000.0, 4.0)
-        self.sets = {}
 
-    def observed(self, nexp=7, weighted=True):
-        """test_gpu_sysrem's raw observed set (at the model's scale, with a gain), made once"""
-        if (nexp, weighted) not in self.sets:
-            gain = np.random.default_rng(60 + nexp).uniform(0.5, 1.5, sc.NPIX)
-            w = sc.edge_weights(max(nexp, 3), 80 + nexp)[:nexp].copy() if weighted else None
-            self.sets[(nexp, weighted)] = xcor.Observed(sc.SEG, self.scale * sc.data_set(nexp, 70 + nexp), w, gain)
-        return self.sets[(nexp, weighted)]
-
-    def handle(self, ob, px=None):
-        E = Engine(self.P.static)
-        E.set_pixels(self.px if px is None else px)
-        if ob is not None:
-            E.set_observed(ob)
-        return E
+    def make_observed(self, nexp, weighted):
+        """the SYSREM tests' raw set, with edge weights down to one exposure"""
+        w = sc.edge_weights(max(nexp, 3), 80 + nexp)[:nexp].copy() if weighted else None
+        return xcor.Observed(sc.SEG, self.scale * sc.data_set(nexp, 70 + nexp), w, self.gain(nexp))
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("normalise"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    assert sc.LENGTHS == tm.LENGTHS and len(px) == sc.NPIX
-    E = Engine(P.static)
-    spec = E.run(P.atm, P.opts)["spectrum"]
-    E.close()
-    return Case(P, px, float(np.mean(spec)), spec)
-
-
-def check_normalised(N, mirror, what):
-    data, scale, centre, nclipped, nbad = mirror
-    assert same_bits(N.rowscale, scale), what
-    assert same_bits(N.centre, centre), what
-    assert same_bits(N.data, data), what
-    assert (N.nclipped, N.nbad) == (nclipped, nbad), what
+    return oc.build_case(tmp_path_factory.mktemp("normalise"), Case)
 
 
 # ---- 1. every recipe corner, bit for bit -------------------------------------------------------------------------
@@ -89,12 +63,12 @@ def test_every_recipe_corner_is_the_mirrors_bit_for_bit(case, which, nexp):
         E.set_normalise(nm)
         N = E.normalise_observed()
         mirror = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm)
-        check_normalised(N, mirror, what)
+        oc.check_normalised(N, mirror, what)
         assert N.spectrum is None and np.isfinite(N.data).all() and not np.signbit(N.rowscale).any(), what
         clipped, bad = clipped + N.nclipped, bad + N.nbad
     if which.startswith("edge"):
         # the edges took part: bad rows (a quantile <= 0) at every exposure count, the masked row, the all-equal row
-        scale = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, MEDIAN_RATIO)[1]
+        scale = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, oc.MEDIAN_RATIO)[1]
         assert bad > 0 and scale[nexp - 1, nc.MASKED_SEG] == 0 and scale[0, nc.ODD_SEG] == 2.5 and np.all(scale[:, nc.OVER_SEG] > 0)
     if nexp == 65:
         assert clipped > 0, which                            # (a clip of 3 sigma takes entries of 65)
@@ -113,17 +87,13 @@ def test_bits_about_a_whole_number_of_trips(case, nexp, weighted):
     E.set_normalise(nm)
     mirror = xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, nm)
     assert np.isfinite(mirror[0]).all()
-    check_normalised(E.normalise_observed(), mirror, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
+    oc.check_normalised(E.normalise_observed(), mirror, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
     E.close()
 
 
 # ---- 2. the detrending calls with a recipe installed -------------------------------------------------------------
-def nsingular_of(ob, basis):
-    return int(np.count_nonzero(~xcor.weighted_factor(ob, xcor.WeightedFilter(basis))[2]))
-
-
 @pytest.mark.parametrize("injected", [False, True])
-@pytest.mark.parametrize("nm", [MEDIAN_RATIO, xcor.Normalise(Q, DIVIDE, 0.9, 3.0), xcor.Normalise(NONE, SUBTRACT, 0.5, 0.0)], ids=nc.name)
+@pytest.mark.parametrize("nm", [oc.MEDIAN_RATIO, xcor.Normalise(Q, DIVIDE, 0.9, 3.0), xcor.Normalise(NONE, SUBTRACT, 0.5, 0.0)], ids=nc.name)
 def test_detrend_and_pca_run_step_1b(case, nm, injected):
     P = case.P
     ob = case.observed(12, True)
@@ -139,14 +109,14 @@ def test_detrend_and_pca_run_step_1b(case, nm, injected):
     norm = xcor.normalise_reference(f0, ob.weight, ob.seg_first, nm)
     what = nc.name(nm) + (", injected" if injected else "")
     N = E.normalise_observed(inject=inject)
-    check_normalised(N, norm, what)
+    oc.check_normalised(N, norm, what)
     assert (N.spectrum is None) == (not injected) and (not injected or np.array_equal(N.spectrum, case.spec))
     # SYSREM of the normalised data
     basis, coef, resid = xcor.sysrem_reference(norm[0], ob.weight, ob.seg_first, 3, 10)
     D = E.detrend_observed(3, 10, inject=inject)
     assert np.isfinite(basis).all() and np.isfinite(resid).all(), what
     assert same_bits(D.basis, basis) and same_bits(D.coef, coef) and same_bits(D.data, resid), what
-    assert D.nsingular == nsingular_of(ob, basis), what
+    assert D.nsingular == oc.nsingular_of(ob, basis), what
     # PCA of the same
     basis, coef, resid, eigen, offdiag, nwhole = xcor.pca_reference(norm[0], ob.weight, ob.seg_first, 3, 8)
     D = E.pca_observed(3, 8, inject=inject)
@@ -164,10 +134,10 @@ def test_the_three_calls_undo_one_another_and_start_from_raw(case):
     ob = case.observed(7, True)
     E = case.handle(ob)
     fresh = E.run_moments(P.atm, P.opts, SHIFTS)
-    E.set_normalise(MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
     assert same_bits(E.run_moments(P.atm, P.opts, SHIFTS), fresh)        # installing the recipe changes nothing in force
     N1 = E.normalise_observed()
-    check_normalised(N1, xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, MEDIAN_RATIO), "first call")
+    oc.check_normalised(N1, xcor.normalise_reference(ob.data, ob.weight, ob.seg_first, oc.MEDIAN_RATIO), "first call")
     normalised = E.run_moments(P.atm, P.opts, SHIFTS)
     assert not same_bits(normalised, fresh)
     with pytest.raises(EngineError) as ei:                               # no filter after it
@@ -201,13 +171,13 @@ def test_the_three_calls_undo_one_another_and_start_from_raw(case):
     assert same_bits(got.basis, want.basis) and same_bits(got.data, want.data) and same_bits(got.eigen, want.eigen)
     F.close()
     # set_observed drops the recipe
-    E.set_normalise(MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
     E.set_observed(ob)
     with pytest.raises(EngineError) as ei:
         E.normalise_observed()
     assert ei.value.code == -1 and "trx_normalise_observed: no recipe installed (trx_set_normalise)" in str(ei.value)
     assert same_bits(E.detrend_observed(3, 10).data, resid)
-    E.set_normalise(MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
     E.set_pixels(case.px)                                                # and so does set_pixels, with the observed set
     E.set_observed(ob)
     assert same_bits(E.detrend_observed(3, 10).data, resid)
@@ -250,7 +220,7 @@ def test_refusals_by_code_and_message_leave_everything_untouched(case):
     P = case.P
     ob = case.observed(7, True)
     E = case.handle(ob)
-    E.set_normalise(MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
     D = E.detrend_observed(3, 10)
     ref = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
     who = "trx_set_normalise: "
@@ -290,7 +260,7 @@ def test_refusals_by_code_and_message_leave_everything_untouched(case):
     run = "trx_normalise_observed: "
     assert raw() == (-1, run + "no recipe installed (trx_set_normalise)")
     assert raw(inject=2, p0=nan) == (-1, run + "no recipe installed (trx_set_normalise)")
-    E.set_normalise(MEDIAN_RATIO)
+    E.set_normalise(oc.MEDIAN_RATIO)
     assert raw(inject=2, p0=nan) == (-1, run + "inject must be 0 or 1")
     assert raw(inject=1, p0=nan) == (-1, run + "p0 must be finite")
     assert raw(inject=1) == (-1, run + "a is NULL")
@@ -299,7 +269,7 @@ def test_refusals_by_code_and_message_leave_everything_untouched(case):
     E.close()
     # no observed set
     N = case.handle(None)
-    for nm in (MEDIAN_RATIO, None):
+    for nm in (oc.MEDIAN_RATIO, None):
         with pytest.raises(EngineError) as ei:
             N.set_normalise(nm)
         assert ei.value.code == -1 and who + "no observed set installed (trx_set_observed)" in str(ei.value)
@@ -314,7 +284,7 @@ def test_refusals_by_code_and_message_leave_everything_untouched(case):
         S = Engine(P.static)
         S.set_pixels(pixels.Pixels([2510.0, 2520.0, 2530.0, 2540.0], [0.2, 0.3, 1.5, 0.4], 4.0))
         S.set_observed(xcor.Observed([0, 1, 4], np.ones((7, 4))))
-        for nm in (MEDIAN_RATIO, None):
+        for nm in (oc.MEDIAN_RATIO, None):
             with pytest.raises(EngineError) as ei:
                 S.set_normalise(nm)
             assert ei.value.code == -6 and who + "this handle's shard is not the whole grid" in str(ei.value)

@@ -2,7 +2,7 @@
 include/transit_hip.h), against transit_amd.xcor's mirrors of the same definition -- inject_reference, pca_reference and, for
 what the call installs, weighted_factor -- BIT FOR BIT: basis, coef, data, eigen, offdiag, nwhole and nsingular.
 
-The case is test_gpu_sysrem's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid ones,
+The case is observed_cases.build_case's: pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid ones,
 the segments [1, 63, 64, 65, 200, 0, 7, 400], 7 and 12 exposures, sysrem_cases' data and edge weights.  Past one wave of
 Jacobi pairs and at the cap -- 65, 100 and 128 exposures -- the set is two short segments of 130 and 64 pixels."""
 import ctypes as C
@@ -11,88 +11,36 @@ import time
 import numpy as np
 import pytest
 
+import observed_cases as oc
+import pixel_cases as pc
 import sysrem_cases as sc
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, broaden, pixels, xcor
 from transit_amd.engine import Engine, EngineError
 from transit_amd.exposures import Exposures
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-SCALE0 = np.array([1.0, 0.5, 0.0, -0.25, 0.0, 3.0, 1e-3])          # the table's scales: 0 at two exposures
-SMEAR = np.array([0.0, 2e-9, 1e-6, 3e-6, 1.3e-5, 0.0, 1e-5])
+SHIFTS = pc.SHIFTS
 V = xcor.SCATTER_VARIANCE
-same_bits = sc.same_bits
 
 
-class Case:
-    def __init__(self, P, px, scale, spec):
-        self.P, self.px, self.scale, self.spec = P, px, scale, spec
-        self.sets, self.mirrors = {}, {}
-
-    def observed(self, nexp=7, weighted=True):
-        """the raw observed set, made once"""
-        if (nexp, weighted) not in self.sets:
-            gain = np.random.default_rng(60 + nexp).uniform(0.5, 1.5, sc.NPIX)
-            w = sc.edge_weights(nexp, 80 + nexp) if weighted else None
-            self.sets[(nexp, weighted)] = xcor.Observed(sc.SEG, self.scale * sc.data_set(nexp, 70 + nexp), w, gain)
-        return self.sets[(nexp, weighted)]
-
+class Case(oc.SysremCase):
     def mirror(self, nexp, weighted, ncomp, nsweep):
         """xcor.pca_reference of the raw set, made once"""
-        key = (nexp, weighted, ncomp, nsweep)
-        if key not in self.mirrors:
-            ob = self.observed(nexp, weighted)
-            self.mirrors[key] = xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, nsweep)
-        return self.mirrors[key]
-
-    def handle(self, ob, px=None):
-        E = Engine(self.P.static)
-        E.set_pixels(self.px if px is None else px)
-        if ob is not None:
-            E.set_observed(ob)
-        return E
+        ob = self.observed(nexp, weighted)
+        return self.memo((nexp, weighted, ncomp, nsweep), lambda: xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, nsweep))
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("pca"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    assert sc.LENGTHS == tm.LENGTHS and len(px) == sc.NPIX
-    E = Engine(P.static)
-    spec = E.run(P.atm, P.opts)["spectrum"]
-    E.close()
-    return Case(P, px, float(np.mean(spec)), spec)
-
-
-def nsingular_of(ob, basis):
-    """the dead columns of the weighted filter of `basis` over ob's weights: the mirror of the install step"""
-    return int(np.count_nonzero(~xcor.weighted_factor(ob, xcor.WeightedFilter(basis))[2]))
-
-
-def check_outputs(D, mirror, ob, what):
-    basis, coef, resid, eigen, offdiag, nwhole = mirror
-    assert np.isfinite(basis).all() and np.isfinite(resid).all(), what
-    assert same_bits(D.basis, basis), what
-    assert same_bits(D.coef, coef), what
-    assert same_bits(D.data, resid), what
-    assert same_bits(D.eigen, eigen), what
-    assert same_bits(D.offdiag, offdiag), what
-    assert D.nwhole.dtype == np.int64 and np.array_equal(D.nwhole, nwhole), what
-    assert D.nsingular == nsingular_of(ob, basis), what
+    return oc.build_case(tmp_path_factory.mktemp("pca"), Case)
 
 
 def same_result(a, b):
     return (same_bits(a.basis, b.basis) and same_bits(a.coef, b.coef) and same_bits(a.data, b.data) and same_bits(a.eigen, b.eigen) and
             same_bits(a.offdiag, b.offdiag) and np.array_equal(a.nwhole, b.nwhole) and a.nsingular == b.nsingular)
-
-
-def same_detrend(a, b):
-    return same_bits(a.basis, b.basis) and same_bits(a.coef, b.coef) and same_bits(a.data, b.data) and a.nsingular == b.nsingular
 
 
 # ---- 1. bits without injection --------------------------------------------------------------------------------
@@ -106,7 +54,7 @@ def test_bits_without_injection(case, nexp, ncomp, weighted):
         what = "nexp %d, ncomp %d, nsweep %d, %s" % (nexp, ncomp, nsweep, "edge weights" if weighted else "no weights")
         D = E.pca_observed(ncomp, nsweep)
         mirror = case.mirror(nexp, weighted, ncomp, nsweep)
-        check_outputs(D, mirror, ob, what)
+        oc.check_pca_outputs(D, mirror, ob, what)
         assert D.spectrum is None
         basis = mirror[0]
         # the edges: the empty segment's vectors are zero, every other segment has a first component
@@ -151,7 +99,7 @@ def test_many_exposures(case, nexp, ncomp):
     E = case.handle(ob, px)
     D = E.pca_observed(ncomp, 8)
     mirror = xcor.pca_reference(ob.data, ob.weight, ob.seg_first, ncomp, 8)
-    check_outputs(D, mirror, ob, "nexp %d" % nexp)
+    oc.check_pca_outputs(D, mirror, ob, "nexp %d" % nexp)
     assert np.all(D.basis[1, 3] == 0) and not np.signbit(D.basis[1, 3]).any() and np.all(D.coef[:, 40] == 0)
     assert 0 < D.nwhole[0] < 130 and 0 < D.nwhole[1] < 64 and np.all(D.eigen[:, 0] > 0)
     print("nexp %d, %d components: the mirror's; nwhole %s, offdiag / eigen[:, 0] %s" % (nexp, ncomp, D.nwhole, D.offdiag / D.eigen[:, 0]))
@@ -176,7 +124,7 @@ def test_bits_with_injection(case, setup):
     ob = case.observed(7, True)
     E = case.handle(ob)
     if setup != "pixels":
-        E.set_exposures(Exposures(SCALE0.copy(), SMEAR.copy()))
+        E.set_exposures(Exposures(xc.SCALE0.copy(), xc.SMEAR.copy()))
     if "broadening" in setup:
         E.set_broadening(broaden.Rotation(4.0, 0.4))
     # a high-pass takes no part in the injection: the pairs are the ones ahead of it
@@ -190,13 +138,13 @@ def test_bits_with_injection(case, setup):
     # (test_the_injected_data_are_inject_references reads them off a whole set)
     mirror = xcor.pca_reference(f0, ob.weight, ob.seg_first, 3, 8)
     D = E.pca_observed(3, 8, inject=(P.atm, P.opts, SHIFTS, p0, p1))
-    check_outputs(D, mirror, ob, setup)
+    oc.check_pca_outputs(D, mirror, ob, setup)
     assert np.array_equal(D.spectrum, case.spec)             # run()'s bits, never the broadened spectrum
     assert same_bits(D.data[:, sc.MASKED_COL], f0[:, sc.MASKED_COL])     # a masked column keeps the injected data
     assert not same_bits(D.data, case.mirror(7, True, 3, 8)[2])
     # p0 = 0, p1 = 1 injects nothing
     D0 = E.pca_observed(3, 8, inject=(P.atm, P.opts, SHIFTS, 0.0, 1.0))
-    check_outputs(D0, case.mirror(7, True, 3, 8), ob, setup + ", p0 = 0 and p1 = 1")
+    oc.check_pca_outputs(D0, case.mirror(7, True, 3, 8), ob, setup + ", p0 = 0 and p1 = 1")
     E.close()
 
 
@@ -214,7 +162,7 @@ def test_the_injected_data_are_inject_references(case):
     f0 = xcor.inject_reference(pairs, ob, 0.05 / case.scale, 0.9)
     D = E.pca_observed(3, 2, inject=(P.atm, P.opts, SHIFTS, 0.05 / case.scale, 0.9))
     assert np.all(D.nwhole[1:] == 0) and np.all(D.basis[1:] == 0) and same_bits(D.data[:, 1:], f0[:, 1:])
-    check_outputs(D, xcor.pca_reference(f0, w, sc.SEG, 3, 2), ob, "every column with a hole")
+    oc.check_pca_outputs(D, xcor.pca_reference(f0, w, sc.SEG, 3, 2), ob, "every column with a hole")
     E.close()
 
 
@@ -227,14 +175,14 @@ def test_sequences_with_detrend_observed(case):
     undo = E.pca_observed(0)                                 # nothing had been detrended: TRX_OK
     assert undo.data is None and undo.eigen is None and undo.nsingular == 0 and same_bits(E.run_moments(P.atm, P.opts, SHIFTS), fresh)
     P1 = E.pca_observed(3, 8)
-    check_outputs(P1, case.mirror(7, True, 3, 8), ob, "first call")
+    oc.check_pca_outputs(P1, case.mirror(7, True, 3, 8), ob, "first call")
     assert not same_bits(E.run_moments(P.atm, P.opts, SHIFTS), fresh)
     assert same_result(E.pca_observed(3, 8), P1)             # twice
     mom = E.run_filtered_moments(P.atm, P.opts, SHIFTS)
     S1 = E.detrend_observed(3, 10)                           # pca -> detrend: a fresh detrend's bits
     F = case.handle(ob)
     S0 = F.detrend_observed(3, 10)
-    assert same_detrend(S1, S0) and S1.eigen is None
+    assert oc.same_detrend(S1, S0) and S1.eigen is None
     assert same_result(F.pca_observed(3, 8), P1)             # detrend -> pca: a fresh pca's bits
     F.close()
     assert same_result(E.pca_observed(3, 8), P1)
@@ -259,7 +207,7 @@ def test_sequences_with_detrend_observed(case):
 def test_highpass_weigh_and_what_is_installed(case):
     P = case.P
     ob = case.observed(7, True)
-    hp, ex = xcor.gaussian_highpass(6.0), Exposures(SCALE0.copy(), SMEAR.copy())
+    hp, ex = xcor.gaussian_highpass(6.0), Exposures(xc.SCALE0.copy(), xc.SMEAR.copy())
     E = case.handle(ob)
     E.set_filter(xcor.svd_filter(ob.data, ob.seg_first, 2))  # a plain filter in the slot: replaced
     E.set_highpass(hp)
@@ -267,7 +215,7 @@ def test_highpass_weigh_and_what_is_installed(case):
     E.highpass_observed()                                    # a high-pass over the raw data: the PCA uncovers it
     D = E.pca_observed(3, 8)
     basis, coef, resid, eigen, offdiag, nwhole = case.mirror(7, True, 3, 8)
-    check_outputs(D, case.mirror(7, True, 3, 8), ob, "behind a high-pass and a table")
+    oc.check_pca_outputs(D, case.mirror(7, True, 3, 8), ob, "behind a high-pass and a table")
     # run_filtered_moments is a fresh handle's under the same residuals, weights and basis
     got = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
     F = case.handle(xcor.Observed(ob.seg_first, resid, ob.weight, ob.gain))
@@ -386,17 +334,17 @@ def test_injection_and_recovery_end_to_end(case):
     w = rng.uniform(0.5, 2.0, (7, 800))
     w[rng.random((7, 800)) < 0.02] = 0.0
     ob = xcor.Observed(seg, raw, w, rng.uniform(0.5, 1.5, 800))
-    vm = tv.the_map("ccf", kp=tt.KP, vsys=tt.VSYS)
-    cell = (int(np.argmin(np.abs(tt.KP - tt.KP_TRUE))), int(np.argmin(np.abs(tt.VSYS - tt.VSYS_TRUE))))
+    vm = xc.the_map("ccf", kp=xc.TRAIL_KP, vsys=xc.TRAIL_VSYS)
+    cell = (int(np.argmin(np.abs(xc.TRAIL_KP - xc.KP_TRUE))), int(np.argmin(np.abs(xc.TRAIL_VSYS - xc.VSYS_TRUE))))
     assert cell == (2, 3) and (vm.nkp, vm.nvsys) == (5, 5)
-    shifts = np.array([pixels.shift(v) for v in tt.VSYS_TRUE + tt.KP_TRUE * tv.ORBIT])
+    shifts = np.array([pixels.shift(v) for v in xc.VSYS_TRUE + xc.KP_TRUE * xc.ORBIT])
     p0 = 0.1 / case.scale
     E = case.handle(ob)
     E.set_exposures(Exposures(np.ones(7), np.full(7, 2e-6)))
     D = E.pca_observed(3, 8, inject=(P.atm, P.opts, shifts, p0, 1.0))
     f0 = xcor.inject_reference(E.run_exposed(P.atm, P.opts, shifts), ob, p0, 1.0)
     mirror = xcor.pca_reference(f0, w, seg, 3, 8)
-    check_outputs(D, mirror, ob, "end to end")
+    oc.check_pca_outputs(D, mirror, ob, "end to end")
     R = E.weigh_observed(V, clip=3.0)
     var, med, keep, w1 = xcor.scatter_reference(mirror[2], w, seg, V, 3.0, 2)
     assert same_bits(R.weight, w1)
@@ -407,7 +355,7 @@ def test_injection_and_recovery_end_to_end(case):
     # every cell has the bits of the same handle's filtered moments at the cell's lags
     for i in range(5):
         for j in range(5):
-            mom = E.run_filtered_moments(P.atm, P.opts, tv.LAGS[idx[i, j]])
+            mom = E.run_filtered_moments(P.atm, P.opts, xc.LAGS[idx[i, j]])
             want = xcor.cell_value(mom, vm)
             assert same_bits(m[i, j], want), (i, j, m[i, j], want)
     E.close()

@@ -7,9 +7,8 @@ and against trx_run_bands with pixels.as_bands on a second handle; for bit indep
 spectrum, inside a larger set, subsets and permutations of the shifts, through a batch); over shards; on an
 opacity-grid handle; and for its refusals.
 
-Tolerance of the two accuracy checks, per component, relative: 1e-12 + 2 * 2^-52 * nu_max / sigma_min.  1e-12 is the
-figure of test_gpu_bands for GAUSS bands (summation order and exp); the second term bounds what a one-ulp difference
-in nu_i does to the weights: dx <= 2 ulp(nu) / sigma, and the Gaussian-weighted mean of |x| is below 1."""
+Tolerance of the two accuracy checks, per component, relative: pixel_cases.tolerance, 1e-12 + 2 * 2^-52 * nu_max / sigma_min,
+derived in that module's docstring."""
 import ctypes as C
 import os
 import shutil
@@ -17,103 +16,39 @@ import shutil
 import numpy as np
 import pytest
 
+import pixel_cases as pc
 from cases import GOLDEN
-from test_gpu_bands import grid, thinner
-from test_gpu_batch import atmospheres
-from transit_amd import _abi, bands, pixels, synth
+from transit_amd import _abi, bands, pixels
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
 
 pytestmark = pytest.mark.gpu
 
-V_KMS = (-150.0, -37.5, -3.1, 0.0, 3.1, 37.5, 150.0)
-SHIFTS = np.array([1.0 - v / 299792.458 for v in V_KMS])
-
-
-def make(tmp_path, solution, **kw):
-    d = str(tmp_path / solution)
-    args = dict(nlines=40_000, wnlow=2500, wnhigh=2560, wndelt=0.01, wnosamp=1, nlayers=60, solution=solution,
-                toomuch=10.0, ethresh=1e-50, seed=41, ncia=2 if solution == "transit" else 1)
-    args.update(kw)
-    synth.make_case(d, **args)
-    return Problem.from_cfg(os.path.join(d, "case.cfg"))
-
-
-def set_a(P):
-    """400 pixels at R = 20000: windows of 42-44 bins (a lane each)"""
-    wn_d = float(P.static.wn_d)
-    return pixels.resolving_power(np.linspace(2503, 2557, 400) + 0.37 * wn_d, 20000.0, 4.0)
-
-
-def set_b(P):
-    """the same centres at R = 3000: windows of 283-290 bins (a wave each)"""
-    wn_d = float(P.static.wn_d)
-    return pixels.resolving_power(np.linspace(2503, 2557, 400) + 0.37 * wn_d, 3000.0, 4.0)
-
-
-def joined(*sets):
-    return pixels.Pixels(np.concatenate([s.centre for s in sets]), np.concatenate([s.fwhm for s in sets]), sets[0].cut)
-
-
-def window_lengths_and_margin(P, px, shifts):
-    """the whole-grid window length of every pair, and the smallest distance (in bins) of a window edge from a grid
-    point: a one-bin disagreement about a range cannot hide behind rounding when it is far above an ulp"""
-    wn_i, wn_d, n, _ = grid(P)
-    lens, margin = [], np.inf
-    for b in pixels.as_bands(px, shifts):
-        a, z = bands.gauss_range(wn_i, wn_d, n, b.centre, b.fwhm, b.cut)
-        lens.append(z - a)
-        sigma = b.fwhm / bands.FWHM_PER_SIGMA
-        for edge in ((b.centre - b.cut * sigma - wn_i) / wn_d, (b.centre + b.cut * sigma - wn_i) / wn_d):
-            margin = min(margin, abs(edge - round(edge)))
-    return np.array(lens), margin
-
-
-def tolerance(px, shifts):
-    nu_max = float(np.max(px.centre)) / float(np.min(shifts))
-    sigma_min = float(np.min(px.fwhm)) / float(np.max(shifts)) / bands.FWHM_PER_SIGMA
-    return 1e-12 + 2.0 * 2.0 ** -52 * nu_max / sigma_min
-
-
-def check_close(got, ref, tol, what=""):
-    assert got.shape == ref.shape
-    zero = ref == 0
-    assert np.all(got[zero] == 0), what
-    err = np.abs(got[~zero] - ref[~zero]) / np.abs(ref[~zero])
-    worst = float(err.max()) if err.size else 0.0
-    print("%s: max rel err %.3e (tolerance %.3e)" % (what, worst, tol))
-    assert worst <= tol, (what, worst, tol)
-
-
-def check_accuracy(P, px, shifts, out, spec, tol, lo=0, what=""):
-    wn_i, wn_d, n, _ = grid(P)
-    check_close(out, pixels.reference(spec, wn_i, wn_d, n, px, shifts, lo=lo), tol, what)
-
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_pixel_runs_keep_the_spectrum_and_match_the_bands(tmp_path, solution):
-    P = make(tmp_path, solution)
+    P = pc.make(tmp_path, solution)
     assert P.nwn == 6001
-    A, B = set_a(P), set_b(P)
-    la, ma = window_lengths_and_margin(P, A, SHIFTS)
-    lb, mb = window_lengths_and_margin(P, B, SHIFTS)
+    A, B = pc.set_a(P), pc.set_b(P)
+    la, ma = pc.window_lengths_and_margin(P, A, pc.SHIFTS)
+    lb, mb = pc.window_lengths_and_margin(P, B, pc.SHIFTS)
     assert 42 <= la.min() and la.max() <= 44 and 283 <= lb.min() and lb.max() <= 290
     assert min(ma, mb) >= 1e-6, (ma, mb)
-    px = joined(A, B)
-    tol = tolerance(px, SHIFTS)
+    px = pc.joined(A, B)
+    tol = pc.tolerance(px, pc.SHIFTS)
     assert 1.5e-11 < tol < 3e-11
     plain, pix, banded = Engine(P.static), Engine(P.static), Engine(P.static)
     pix.set_pixels(px)
-    banded.set_bands(pixels.as_bands(px, SHIFTS))
-    deep, keep = thinner(P, 1e-3)
+    banded.set_bands(pixels.as_bands(px, pc.SHIFTS))
+    deep, keep = pc.thinner(P, 1e-3)
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         ref = plain.run(atm, P.opts)["spectrum"]
-        out, spec = pix.run_pixels(atm, P.opts, SHIFTS, spectrum=True)
-        assert out.shape == (len(SHIFTS), len(px), 2)
+        out, spec = pix.run_pixels(atm, P.opts, pc.SHIFTS, spectrum=True)
+        assert out.shape == (len(pc.SHIFTS), len(px), 2)
         assert np.array_equal(spec, ref)
-        check_accuracy(P, px, SHIFTS, out, spec, tol, what="%s run %d vs reference" % (solution, k))
+        pc.check_accuracy(P, px, pc.SHIFTS, out, spec, tol, what="%s run %d vs reference" % (solution, k))
         sums = banded.run_bands(atm, P.opts).reshape(out.shape)
-        check_close(out, sums, tol, "%s run %d vs run_bands" % (solution, k))
+        pc.check_close(out, sums, tol, "%s run %d vs run_bands" % (solution, k))
         assert np.all(out[..., 1] > 0)
     # trx_run on a handle with pixels installed: the plain spectrum
     for atm in (P.atm, deep):
@@ -122,8 +57,8 @@ def test_pixel_runs_keep_the_spectrum_and_match_the_bands(tmp_path, solution):
 
 
 def test_one_bin_window_is_the_spectrum_value(tmp_path):
-    P = make(tmp_path, "eclipse", nlines=10_000)
-    wn_i, wn_d, n, wn = grid(P)
+    P = pc.make(tmp_path, "eclipse", nlines=10_000)
+    wn_i, wn_d, n, wn = pc.grid(P)
     px = pixels.Pixels([float(wn[n // 2])], [wn_d / 2], 1.0)
     assert bands.gauss_range(wn_i, wn_d, n, float(wn[n // 2]), wn_d / 2, 1.0) == (n // 2, n // 2 + 1)
     E = Engine(P.static)
@@ -135,35 +70,35 @@ def test_one_bin_window_is_the_spectrum_value(tmp_path):
 
 
 def test_bits_do_not_depend_on_the_rest_of_the_call(tmp_path):
-    P = make(tmp_path, "eclipse", nlines=20_000)
-    px = joined(set_a(P), set_b(P))
+    P = pc.make(tmp_path, "eclipse", nlines=20_000)
+    px = pc.joined(pc.set_a(P), pc.set_b(P))
     E = Engine(P.static)
     E.set_pixels(px)
-    first = E.run_pixels(P.atm, P.opts, SHIFTS)
+    first = E.run_pixels(P.atm, P.opts, pc.SHIFTS)
     for _ in range(2):
-        assert np.array_equal(E.run_pixels(P.atm, P.opts, SHIFTS), first)
-    assert np.array_equal(E.run_pixels(P.atm, P.opts, SHIFTS, spectrum=True)[0], first)
+        assert np.array_equal(E.run_pixels(P.atm, P.opts, pc.SHIFTS), first)
+    assert np.array_equal(E.run_pixels(P.atm, P.opts, pc.SHIFTS, spectrum=True)[0], first)
     # subsets and a permutation of the shifts
     for idx in ([3], [0, 6], [5, 2, 4], [6, 5, 4, 3, 2, 1, 0], [1, 1, 0]):
-        got = E.run_pixels(P.atm, P.opts, SHIFTS[idx])
+        got = E.run_pixels(P.atm, P.opts, pc.SHIFTS[idx])
         assert np.array_equal(got, first[idx]), idx
     # the set between 300 other pixels (every lane and wave now holds other pairs)
     rng = np.random.default_rng(5)
     front = pixels.resolving_power(rng.uniform(2501, 2559, 137), 9000.0)
     back = pixels.resolving_power(rng.uniform(2490, 2570, 163), 2000.0)
-    E.set_pixels(joined(front, px, back))
-    got = E.run_pixels(P.atm, P.opts, SHIFTS)
-    assert got.shape == (len(SHIFTS), len(px) + 300, 2)
+    E.set_pixels(pc.joined(front, px, back))
+    got = E.run_pixels(P.atm, P.opts, pc.SHIFTS)
+    assert got.shape == (len(pc.SHIFTS), len(px) + 300, 2)
     assert np.array_equal(got[:, 137:137 + len(px)], first)
     E.close()
 
 
 def test_batch_pairs_are_the_single_handle_pairs(tmp_path):
-    P = make(tmp_path, "eclipse", nlines=30_000, seed=33)
-    px = joined(set_a(P), set_b(P))
+    P = pc.make(tmp_path, "eclipse", nlines=30_000, seed=33)
+    px = pc.joined(pc.set_a(P), pc.set_b(P))
     K = 7
-    atms, keep = atmospheres(P, K)
-    shifts = np.stack([np.roll(SHIFTS, j)[:5] * (1.0 + 1e-6 * j) for j in range(K)])
+    atms, keep = pc.atmospheres(P, K)
+    shifts = np.stack([np.roll(pc.SHIFTS, j)[:5] * (1.0 + 1e-6 * j) for j in range(K)])
     one = Engine(P.static)
     one.set_pixels(px)
     ref = np.stack([one.run_pixels(atms[j], P.opts, shifts[j]) for j in range(K)])
@@ -180,16 +115,16 @@ def test_batch_pairs_are_the_single_handle_pairs(tmp_path):
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_shards_combined_in_rank_order(tmp_path, solution):
-    P = make(tmp_path, solution, nlines=20_000)
-    px = joined(set_a(P), set_b(P))
-    tol = tolerance(px, SHIFTS)
-    wn_i, wn_d, n, _ = grid(P)
+    P = pc.make(tmp_path, solution, nlines=20_000)
+    px = pc.joined(pc.set_a(P), pc.set_b(P))
+    tol = pc.tolerance(px, pc.SHIFTS)
+    wn_i, wn_d, n, _ = pc.grid(P)
     whole = Engine(P.static)
     whole.set_pixels(px)
-    total, spec = whole.run_pixels(P.atm, P.opts, SHIFTS, spectrum=True)
+    total, spec = whole.run_pixels(P.atm, P.opts, pc.SHIFTS, spectrum=True)
     whole.close()
-    check_accuracy(P, px, SHIFTS, total, spec, tol, what="whole grid")
-    ranges = [bands.gauss_range(wn_i, wn_d, n, b.centre, b.fwhm, b.cut) for b in pixels.as_bands(px, SHIFTS)]
+    pc.check_accuracy(P, px, pc.SHIFTS, total, spec, tol, what="whole grid")
+    ranges = [bands.gauss_range(wn_i, wn_d, n, b.centre, b.fwhm, b.cut) for b in pixels.as_bands(px, pc.SHIFTS)]
     cuts = [0, 1500, 3777, n]
     parts, empties = [], 0
     try:
@@ -197,10 +132,10 @@ def test_shards_combined_in_rank_order(tmp_path, solution):
             P.set_shard(cuts[r], cuts[r + 1])
             E = Engine(P.static)
             E.set_pixels(px)
-            s, sp = E.run_pixels(P.atm, P.opts, SHIFTS, spectrum=True)
+            s, sp = E.run_pixels(P.atm, P.opts, pc.SHIFTS, spectrum=True)
             E.close()
             assert sp.shape == (cuts[r + 1] - cuts[r],)
-            check_accuracy(P, px, SHIFTS, s, sp, tol, lo=cuts[r], what="shard %d" % r)
+            pc.check_accuracy(P, px, pc.SHIFTS, s, sp, tol, lo=cuts[r], what="shard %d" % r)
             flat = s.reshape(-1, 2)
             for k, (a, z) in enumerate(ranges):
                 if max(a, cuts[r]) >= min(z, cuts[r + 1]):
@@ -223,13 +158,13 @@ def test_opacity_grid_handle(tmp_path):
     builder.build_opacity_grid(P)
     builder.close()
     assert P.static.ogrid
-    wn_i, wn_d, n, wn = grid(P)
+    wn_i, wn_d, n, wn = pc.grid(P)
     centres = np.linspace(wn[0] + 1.0, wn[-1] - 1.0, 25) + 0.37 * wn_d
-    px = joined(pixels.resolving_power(centres, 1000.0), pixels.resolving_power(centres, 100.0))      # windows of 3-4 bins, and of the whole grid
+    px = pc.joined(pixels.resolving_power(centres, 1000.0), pixels.resolving_power(centres, 100.0))      # windows of 3-4 bins, and of the whole grid
     shifts = np.array([1.0, 1.0 - 150.0 / 299792.458, 1.0 + 150.0 / 299792.458, 0.9991])
-    lens, margin = window_lengths_and_margin(P, px, shifts)
+    lens, margin = pc.window_lengths_and_margin(P, px, shifts)
     assert margin >= 1e-6 and lens.min() >= 2 and lens.max() == n
-    tol = tolerance(px, shifts)
+    tol = pc.tolerance(px, shifts)
     plain, pix, banded = Engine(P.static), Engine(P.static), Engine(P.static)
     pix.set_pixels(px)
     banded.set_bands(pixels.as_bands(px, shifts))
@@ -237,14 +172,14 @@ def test_opacity_grid_handle(tmp_path):
         ref = plain.run(P.atm, P.opts)["spectrum"]
         out, spec = pix.run_pixels(P.atm, P.opts, shifts, spectrum=True)
         assert np.array_equal(spec, ref)
-        check_accuracy(P, px, shifts, out, spec, tol, what="opacity grid run %d vs reference" % k)
-        check_close(out, banded.run_bands(P.atm, P.opts).reshape(out.shape), tol, "opacity grid run %d vs run_bands" % k)
+        pc.check_accuracy(P, px, shifts, out, spec, tol, what="opacity grid run %d vs reference" % k)
+        pc.check_close(out, banded.run_bands(P.atm, P.opts).reshape(out.shape), tol, "opacity grid run %d vs run_bands" % k)
         assert np.array_equal(pix.run(P.atm, P.opts)["spectrum"], ref)
     plain.close(); pix.close(); banded.close()
 
 
 def test_refusals_keep_the_previous_set(tmp_path):
-    P = make(tmp_path, "eclipse", nlines=10_000)
+    P = pc.make(tmp_path, "eclipse", nlines=10_000)
     E = Engine(P.static)
     lib = E._lib
     dp = _abi.c_double_p
@@ -253,7 +188,7 @@ def test_refusals_keep_the_previous_set(tmp_path):
     assert ei.value.code == -1
     good = pixels.Pixels([2510.0, 2520.0, 2530.0], [0.2, 0.3, 1.5], 4.0)
     E.set_pixels(good)
-    before = E.run_pixels(P.atm, P.opts, SHIFTS)
+    before = E.run_pixels(P.atm, P.opts, pc.SHIFTS)
     assert np.all(before[..., 1] > 0)
 
     def with_pixel_2(centre=2530.0, fwhm=1.5, cut=4.0):
@@ -269,7 +204,7 @@ def test_refusals_keep_the_previous_set(tmp_path):
         with pytest.raises(EngineError) as ei:
             E.set_pixels(px)
         assert ei.value.code == -1 and "pixel 2" in str(ei.value), what
-        assert np.array_equal(E.run_pixels(P.atm, P.opts, SHIFTS), before), what
+        assert np.array_equal(E.run_pixels(P.atm, P.opts, pc.SHIFTS), before), what
     for what, cut in (("cut 0", 0.0), ("cut < 0", -4.0), ("cut nan", np.nan), ("cut inf", np.inf)):
         with pytest.raises(EngineError) as ei:
             E.set_pixels(with_pixel_2(cut=cut))
@@ -283,10 +218,10 @@ def test_refusals_keep_the_previous_set(tmp_path):
     c = pixels.to_c(good)
     c.centre = None
     assert lib.trx_set_pixels(E._h, C.byref(c)) == -1
-    assert np.array_equal(E.run_pixels(P.atm, P.opts, SHIFTS), before)
+    assert np.array_equal(E.run_pixels(P.atm, P.opts, pc.SHIFTS), before)
     # the run's own refusals
     out = np.zeros_like(before)
-    sh = np.ascontiguousarray(SHIFTS)
+    sh = np.ascontiguousarray(pc.SHIFTS)
 
     def run(nshift, shift, dest):
         return lib.trx_run_pixels(E._h, C.byref(P.atm), C.byref(P.opts), None, nshift,
@@ -309,15 +244,15 @@ def test_refusals_keep_the_previous_set(tmp_path):
         E.run_bands(P.atm, P.opts)
     E.set_pixels(None)                                 # cleared: refused again
     with pytest.raises(EngineError):
-        E.run_pixels(P.atm, P.opts, SHIFTS)
+        E.run_pixels(P.atm, P.opts, pc.SHIFTS)
     E.set_pixels(good)
     E.set_pixels(pixels.Pixels([], []))                # npix = 0 clears too
     with pytest.raises(EngineError):
-        E.run_pixels(P.atm, P.opts, SHIFTS)
+        E.run_pixels(P.atm, P.opts, pc.SHIFTS)
     E.close()
     # a batch installs a set on every handle or on none
     B = Batch(P.static, ways=2)
-    three = np.stack([SHIFTS] * 3)
+    three = np.stack([pc.SHIFTS] * 3)
     with pytest.raises(EngineError):
         B.run_pixels([P.atm], P.opts, three[:1])
     B.set_pixels(good)

@@ -15,14 +15,12 @@ import os
 import numpy as np
 import pytest
 
-import oracle_lib as ol
 import random_cases
 from cases import rel_err
-from test_gpu_tail import KEYS, assert_same
+from tolerances import KEYS, assert_same, check_against_oracle, oracle
 from transit_amd import _abi, engine, synth
 from transit_amd.engine import Batch, Engine, EngineError
 from transit_amd.host import Problem
-from tolerances import DEBUG_KEYS, assert_tau_close
 
 pytestmark = pytest.mark.gpu
 
@@ -43,38 +41,6 @@ def make_problem(tmp_path, seed):
     d = str(tmp_path / "r")
     synth.make_case(d, **kw)
     return Problem.from_cfg(os.path.join(d, "case.cfg")), random_cases.summary(kw)
-
-
-def oracle(P):
-    ora = ol.OracleEngine(P.static)
-    try:
-        return ora.run(P.atm, P.opts, debug=DEBUG_KEYS)
-    except EngineError as e:                     # e.g. fewer than three points for the modulation
-        return e
-    finally:
-        ora.close()
-
-
-def check_against_oracle(P, hip, ref, note):
-    """One run of the handle against the oracle's result for the same atmosphere; returns the run."""
-    if isinstance(ref, Exception):
-        with pytest.raises(EngineError) as ei:
-            hip.run(P.atm, P.opts, debug=True)
-        assert ei.value.code == ref.code, note
-        return None
-    got = hip.run(P.atm, P.opts, debug=True)
-    assert np.array_equal(got["last"], ref["last"]), note
-    # optical depth: the arithmetic's 1e-9 plus the rounding steps of the reference's
-    # absolute-radius parabola where they apply (tests/tolerances.py) -- nothing else
-    noisy = assert_tau_close(P, got, ref, note)
-    # spectrum: 1e-8; rays whose optical depth carries parabola noise pass it on (in the
-    # modulation of a 3-4-layer atmosphere R^2 - 2*integral cancels on top of it)
-    assert rel_err(got["spectrum"][~noisy], ref["spectrum"][~noisy]) < 1e-8, note
-    assert rel_err(got["spectrum"], ref["spectrum"]) < 1e-7, note
-    sw = got["computed"].astype(bool) & ref["computed"].astype(bool)
-    assert rel_err(got["e"][sw], ref["e"][sw]) < 1e-9, note
-    assert rel_err(got["e_cs"], ref["e_cs"]) < 1e-12, note
-    return got
 
 
 def scaled_atmosphere(P, dens, f):

@@ -3,7 +3,7 @@ include/transit_hip.h), against transit_amd.xcor's mirrors of the same definitio
 it inject_reference, normalise_reference, sysrem_reference, weighted_factor, highpass_observed_reference and
 scatter_reference -- BIT FOR BIT.
 
-The problem is test_gpu_sysrem's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid ones,
+The problem is observed_cases.build_case's: pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid ones,
 the segments [1, 63, 64, 65, 200, 0, 7, 400], sysrem_cases' data at the model's scale and its edge weights (5 % single
 masked entries, a column masked at every exposure, an exposure masked over a whole segment); the long orders are
 many_cases.long_set's.  The vectors are regress_cases': the time basis of a synthetic airmass, seeded vectors behind it, and
@@ -17,65 +17,30 @@ import numpy as np
 import pytest
 
 import many_cases as mc
+import observed_cases as oc
+import pixel_cases as pc
 import regress_cases as rc
 import sysrem_cases as sc
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, broaden, pixels, xcor
 from transit_amd.engine import Engine, EngineError
 from transit_amd.exposures import Exposures
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-SCALE0 = np.array([1.0, 0.5, 0.0, -0.25, 0.0, 3.0, 1e-3])          # test_gpu_sysrem's table: 0 at two exposures
-SMEAR = np.array([0.0, 2e-9, 1e-6, 3e-6, 1.3e-5, 0.0, 1e-5])
-same_bits = sc.same_bits
+SHIFTS = pc.SHIFTS
 NSEG = len(sc.LENGTHS)
 V = xcor.SCATTER_VARIANCE
 
 
-class Case:
-    def __init__(self, P, px, scale, spec):
-        self.P, self.px, self.scale, self.spec = P, px, scale, spec
-        self.sets = {}
-
-    def observed(self, nexp=7, weighted=True):
-        """test_gpu_sysrem's raw observed set, made once"""
-        if (nexp, weighted) not in self.sets:
-            gain = np.random.default_rng(60 + nexp).uniform(0.5, 1.5, sc.NPIX)
-            w = sc.edge_weights(nexp, 80 + nexp) if weighted else None
-            self.sets[(nexp, weighted)] = xcor.Observed(sc.SEG, self.scale * sc.data_set(nexp, 70 + nexp), w, gain)
-        return self.sets[(nexp, weighted)]
-
-    def handle(self, ob, px=None):
-        E = Engine(self.P.static)
-        E.set_pixels(self.px if px is None else px)
-        if ob is not None:
-            E.set_observed(ob)
-        return E
-
-
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("regress"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    assert sc.LENGTHS == tm.LENGTHS and len(px) == sc.NPIX
-    E = Engine(P.static)
-    spec = E.run(P.atm, P.opts)["spectrum"]
-    E.close()
-    return Case(P, px, float(np.mean(spec)), spec)
+    return oc.build_case(tmp_path_factory.mktemp("regress"), oc.SysremCase)
 
 
 def everywhere(vec, nseg=NSEG):
     return np.ascontiguousarray(np.broadcast_to(vec[None, :, :], (nseg,) + vec.shape))
-
-
-def nsingular_of(ob, basis):
-    """the dead columns of the weighted filter of `basis` over ob's weights: the mirror of the install step"""
-    return int(np.count_nonzero(~xcor.weighted_factor(ob, xcor.WeightedFilter(basis))[2]))
 
 
 def mirror_of(f0, ob, vec, nfit=0, niter=10):
@@ -87,7 +52,7 @@ def mirror_of(f0, ob, vec, nfit=0, niter=10):
     if nfit:
         U, c, resid = xcor.sysrem_reference(resid, ob.weight, ob.seg_first, nfit, niter)
         basis, coef = np.concatenate([vec, U], axis=2), np.concatenate([coef, c], axis=0)
-    return basis, coef, resid, nfs, nsingular_of(ob, basis)
+    return basis, coef, resid, nfs, oc.nsingular_of(ob, basis)
 
 
 def check_outputs(D, mirror, what):
@@ -183,7 +148,7 @@ def test_the_injected_data(case, setup):
     ob = case.observed(7, True)
     E = case.handle(ob)
     if setup != "pixels":
-        E.set_exposures(Exposures(SCALE0.copy(), SMEAR.copy()))
+        E.set_exposures(Exposures(xc.SCALE0.copy(), xc.SMEAR.copy()))
     if "broadening" in setup:
         E.set_broadening(broaden.Rotation(4.0, 0.4))
     E.set_highpass(xcor.gaussian_highpass(6.0))                # a high-pass takes no part in the injection
@@ -463,10 +428,10 @@ def test_injection_and_recovery_end_to_end(case):
     seg = rc.E2E_SEG
     ob = xcor.Observed(seg, case.scale * data, w, gain)
     vec = xcor.time_basis(rc.airmass(7), 2)
-    vm = tv.the_map("ccf", kp=tt.KP, vsys=tt.VSYS)
-    cell = (int(np.argmin(np.abs(tt.KP - tt.KP_TRUE))), int(np.argmin(np.abs(tt.VSYS - tt.VSYS_TRUE))))
+    vm = xc.the_map("ccf", kp=xc.TRAIL_KP, vsys=xc.TRAIL_VSYS)
+    cell = (int(np.argmin(np.abs(xc.TRAIL_KP - xc.KP_TRUE))), int(np.argmin(np.abs(xc.TRAIL_VSYS - xc.VSYS_TRUE))))
     assert cell == (2, 3) and (vm.nkp, vm.nvsys) == (5, 5)
-    shifts = np.array([pixels.shift(v) for v in tt.VSYS_TRUE + tt.KP_TRUE * tv.ORBIT])
+    shifts = np.array([pixels.shift(v) for v in xc.VSYS_TRUE + xc.KP_TRUE * xc.ORBIT])
     p0 = 0.1 / case.scale
     E = case.handle(ob)
     E.set_exposures(Exposures(np.ones(7), np.full(7, 2e-6)))
@@ -476,7 +441,7 @@ def test_injection_and_recovery_end_to_end(case):
         return tuple(int(i) for i in np.unravel_index(np.argmax(m), m.shape))
 
     injected = E.run_exposed(P.atm, P.opts, shifts)
-    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in tv.LAGS])
+    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in xc.LAGS])
 
     def host_map(f0):
         basis, coef, resid, nfs, nsing = mirror_of(f0, ob, vec, 2, 10)
@@ -499,7 +464,7 @@ def test_injection_and_recovery_end_to_end(case):
     assert peak(m) == cell
     for i in range(5):
         for j in range(5):
-            mom = E.run_filtered_moments(P.atm, P.opts, tv.LAGS[idx[i, j]])
+            mom = E.run_filtered_moments(P.atm, P.opts, xc.LAGS[idx[i, j]])
             want = xcor.cell_value(mom, vm)
             assert same_bits(m[i, j], want), (i, j, m[i, j], want)
     E.close()

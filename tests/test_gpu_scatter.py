@@ -3,7 +3,7 @@ transit_amd.xcor.scatter_reference, the numpy mirror of the same definition -- B
 leaves installed, against a fresh handle that gets the same data, weights and basis through set_observed and
 set_weighted_filter.
 
-The case is test_gpu_sysrem's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels, the segments [1, 63, 64, 65,
+The case is observed_cases.build_case's: pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels, the segments [1, 63, 64, 65,
 200, 0, 7, 400], 7 and 12 exposures.  The data are scatter_cases.the_set at the model's scale: faint trends plus seeded
 noise with the planted columns (the ties at the median rank of the 65- and the 200-pixel segment, a constant column, a
 column masked at every exposure, five columns of 10 x the noise); tests/test_scatter_host.py holds their preconditions."""
@@ -13,74 +13,29 @@ import time
 import numpy as np
 import pytest
 
+import observed_cases as oc
+import pixel_cases as pc
 import scatter_cases as cs
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, pixels, xcor
 from transit_amd.engine import Engine, EngineError
 from transit_amd.exposures import Exposures
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
+SHIFTS = pc.SHIFTS
 V, M = xcor.SCATTER_VARIANCE, xcor.SCATTER_MASK
-same_bits = cs.same_bits
-
-
-class Case:
-    def __init__(self, P, px, scale):
-        self.P, self.px, self.scale = P, px, scale
-        self.sets = {}
-
-    def observed(self, nexp=7, weighted=True):
-        """the raw observed set, made once"""
-        if (nexp, weighted) not in self.sets:
-            gain = np.random.default_rng(60 + nexp).uniform(0.5, 1.5, cs.NPIX)
-            data, w, _ = cs.the_set(nexp, weighted, self.scale)
-            self.sets[(nexp, weighted)] = xcor.Observed(cs.SEG, data, w, gain)
-        return self.sets[(nexp, weighted)]
-
-    def handle(self, ob):
-        E = Engine(self.P.static)
-        E.set_pixels(self.px)
-        if ob is not None:
-            E.set_observed(ob)
-        return E
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("scatter"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    assert cs.LENGTHS == tm.LENGTHS and len(px) == cs.NPIX
-    E = Engine(P.static)
-    spec = E.run(P.atm, P.opts)["spectrum"]
-    E.close()
-    return Case(P, px, float(np.mean(spec)))
-
-
-def nsingular_of(ob, data, weight, basis):
-    """the dead columns of the weighted filter of `basis` under `weight`: the mirror of the factor step"""
-    return int(np.count_nonzero(~xcor.weighted_factor(xcor.Observed(ob.seg_first, data, weight, ob.gain), xcor.WeightedFilter(basis))[2]))
-
-
-def check_outputs(R, mirror, what):
-    var, med, keep, w = mirror
-    assert same_bits(R.variance, var), what
-    assert same_bits(R.median, med), what
-    assert same_bits(R.weight, w), what
-    assert R.nmasked == np.count_nonzero((var > 0) & ~keep), what
+    return oc.build_case(tmp_path_factory.mktemp("scatter"), oc.ScatterCase)
 
 
 def same_result(a, b):
     return same_bits(a.variance, b.variance) and same_bits(a.median, b.median) and same_bits(a.weight, b.weight) and \
         (a.nmasked, a.nsingular) == (b.nmasked, b.nsingular)
-
-
-def same_detrend(a, b):
-    return same_bits(a.basis, b.basis) and same_bits(a.coef, b.coef) and same_bits(a.data, b.data) and a.nsingular == b.nsingular
 
 
 # ---- 1. the outputs' bits, on the raw data and on the residuals of a detrend ---------------------------------
@@ -98,8 +53,8 @@ def test_bits(case, nexp, weighted):
                     what = "nexp %d, %s, %s, kind %d, clip %g, min_live %d" % (nexp, "edge weights" if weighted else "no weights", stage, kind, clip, min_live)
                     mirror = xcor.scatter_reference(data, ob.weight, ob.seg_first, kind, clip, min_live)
                     R = E.weigh_observed(kind, clip=clip, min_live=min_live)
-                    check_outputs(R, mirror, what)
-                    assert R.nsingular == (nsingular_of(ob, data, mirror[3], D.basis) if D else 0), what
+                    oc.check_scatter_outputs(R, mirror, what)
+                    assert R.nsingular == (oc.nsingular_of(ob, D.basis, data, mirror[3]) if D else 0), what
                     if clip:
                         clipped, margin = cs.clip_margin(*mirror[:3])
                         print("%s: clipped %s, nearest var / (9 med) %.3f away from 1, nsingular %d" % (what, clipped, margin, R.nsingular))
@@ -117,7 +72,7 @@ def test_bits_about_a_whole_number_of_trips(case, nexp, weighted):
     E = case.handle(ob)
     mirror = xcor.scatter_reference(ob.data, ob.weight, ob.seg_first, V, 3.0, 2)
     assert np.isfinite(mirror[0]).all() and np.isfinite(mirror[3]).all()
-    check_outputs(E.weigh_observed(V, clip=3.0, min_live=2), mirror, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
+    oc.check_scatter_outputs(E.weigh_observed(V, clip=3.0, min_live=2), mirror, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
     E.close()
 
 
@@ -166,7 +121,7 @@ def test_from_raw_and_the_undo(case, weighted):
     D1 = E.detrend_observed(3, niter=2)
     mom, fmom = E.run_moments(P.atm, P.opts, SHIFTS), E.run_filtered_moments(P.atm, P.opts, SHIFTS)
     R1 = E.weigh_observed(V, clip=3.0)
-    check_outputs(R1, xcor.scatter_reference(D1.data, ob.weight, ob.seg_first, V, 3.0, 2), "first call")
+    oc.check_scatter_outputs(R1, xcor.scatter_reference(D1.data, ob.weight, ob.seg_first, V, 3.0, 2), "first call")
     wmom, wfmom = E.run_moments(P.atm, P.opts, SHIFTS), E.run_filtered_moments(P.atm, P.opts, SHIFTS)
     assert not same_bits(wmom, mom) and not same_bits(wfmom, fmom)
     assert same_result(E.weigh_observed(V, clip=3.0), R1)    # twice: W is never an earlier call's result
@@ -187,7 +142,7 @@ def test_from_raw_and_the_undo(case, weighted):
     D2 = E.detrend_observed(3, niter=2)
     F = case.handle(ob)
     DF = F.detrend_observed(3, niter=2)
-    assert same_detrend(D2, DF) and same_detrend(D2, D1)
+    assert oc.same_detrend(D2, DF) and oc.same_detrend(D2, D1)
     assert same_bits(E.run_moments(P.atm, P.opts, SHIFTS), F.run_moments(P.atm, P.opts, SHIFTS))
     assert same_bits(E.run_filtered_moments(P.atm, P.opts, SHIFTS), F.run_filtered_moments(P.atm, P.opts, SHIFTS))
     assert same_bits(E.run_filtered_moments(P.atm, P.opts, SHIFTS), fmom)
@@ -200,7 +155,7 @@ def test_from_raw_and_the_undo(case, weighted):
     E.weigh_observed(V, clip=3.0)
     ob12 = case.observed(12, weighted)
     E.set_observed(ob12)
-    check_outputs(E.weigh_observed(M, clip=3.0, min_live=12), xcor.scatter_reference(ob12.data, ob12.weight, ob12.seg_first, M, 3.0, 12), "after set_observed")
+    oc.check_scatter_outputs(E.weigh_observed(M, clip=3.0, min_live=12), xcor.scatter_reference(ob12.data, ob12.weight, ob12.seg_first, M, 3.0, 12), "after set_observed")
     E.close()
 
 
@@ -305,10 +260,10 @@ def test_injection_weights_and_recovery_end_to_end(case):
     w = rng.uniform(0.5, 2.0, (7, 800))
     w[rng.random((7, 800)) < 0.02] = 0.0
     ob = xcor.Observed(seg, raw, w, rng.uniform(0.5, 1.5, 800))
-    vm = tv.the_map("ccf", kp=tt.KP, vsys=tt.VSYS)
-    cell = (int(np.argmin(np.abs(tt.KP - tt.KP_TRUE))), int(np.argmin(np.abs(tt.VSYS - tt.VSYS_TRUE))))
+    vm = xc.the_map("ccf", kp=xc.TRAIL_KP, vsys=xc.TRAIL_VSYS)
+    cell = (int(np.argmin(np.abs(xc.TRAIL_KP - xc.KP_TRUE))), int(np.argmin(np.abs(xc.TRAIL_VSYS - xc.VSYS_TRUE))))
     assert cell == (2, 3) and (vm.nkp, vm.nvsys) == (5, 5)
-    shifts = np.array([pixels.shift(v) for v in tt.VSYS_TRUE + tt.KP_TRUE * tv.ORBIT])
+    shifts = np.array([pixels.shift(v) for v in xc.VSYS_TRUE + xc.KP_TRUE * xc.ORBIT])
     p0 = 0.1 / case.scale
     E = case.handle(ob)
     E.set_exposures(Exposures(np.ones(7), np.full(7, 2e-6)))
@@ -320,7 +275,7 @@ def test_injection_weights_and_recovery_end_to_end(case):
     # the precondition, on the host from the device's pairs: the numpy chain alone -- inject, SYSREM, weigh, map -- finds the
     # injected cell, and does not without the injection
     injected = E.run_exposed(P.atm, P.opts, shifts)
-    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in tv.LAGS])
+    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in xc.LAGS])
 
     def host_map(data):
         basis, coef, resid = xcor.sysrem_reference(data, w, seg, 2, 10)
@@ -334,7 +289,7 @@ def test_injection_weights_and_recovery_end_to_end(case):
     # the device
     E.detrend_observed(2, 10, inject=(P.atm, P.opts, shifts, p0, 1.0), outputs=False)
     R = E.weigh_observed(V, clip=3.0)
-    check_outputs(R, mirror, "end to end")
+    oc.check_scatter_outputs(R, mirror, "end to end")
     print("%d columns clipped (%s of the five noisy ones among them), %d dead in the filter"
           % (R.nmasked, sum(R.weight[:, p].max() == 0 for p in noisy), R.nsingular))
     assert 5 <= R.nmasked < 400
@@ -345,7 +300,7 @@ def test_injection_weights_and_recovery_end_to_end(case):
     # every cell has the bits of the same handle's filtered moments at the cell's lags
     for i in range(5):
         for j in range(5):
-            mom = E.run_filtered_moments(P.atm, P.opts, tv.LAGS[idx[i, j]])
+            mom = E.run_filtered_moments(P.atm, P.opts, xc.LAGS[idx[i, j]])
             want = xcor.cell_value(mom, vm)
             assert same_bits(m[i, j], want), (i, j, m[i, j], want)
     E.close()
@@ -384,7 +339,7 @@ def test_size_and_time(case):
     t0 = time.perf_counter()
     mirror = xcor.scatter_reference(D.data, w, seg, V, 3.0, 2)
     t_host = time.perf_counter() - t0
-    check_outputs(first, mirror, "40 x 2048")
+    oc.check_scatter_outputs(first, mirror, "40 x 2048")
     assert same_result(E.weigh_observed(V, clip=3.0), first)
     E.close()
     print("40 x 2048 pixels, 100 exposures:")

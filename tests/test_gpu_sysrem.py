@@ -2,7 +2,7 @@
 against transit_amd.xcor's mirrors of the same definition -- inject_reference, sysrem_reference and, for what the call
 installs, weighted_factor -- BIT FOR BIT.
 
-The case is test_gpu_wfilter's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid ones
+The case is observed_cases.build_case's: pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid ones
 (b = 0 at every exposure), the segments [1, 63, 64, 65, 200, 0, 7, 400], 7 exposures, and a set of 12 exposures for 9
 components.  The data are sysrem_cases.data_set (smooth trends plus seeded noise) at the model's scale; the edge weights are
 sysrem_cases.edge_weights: 5 % single masked entries, a column masked at every exposure and an exposure masked over a whole
@@ -17,80 +17,30 @@ import time
 import numpy as np
 import pytest
 
+import observed_cases as oc
+import pixel_cases as pc
 import sysrem_cases as sc
-import test_gpu_filtered_map as tfm
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-import test_gpu_velocity_map as tv
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import _abi, bands, broaden, pixels, xcor
 from transit_amd.engine import Engine, EngineError
 from transit_amd.exposures import Exposures
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-SCALE0 = np.array([1.0, 0.5, 0.0, -0.25, 0.0, 3.0, 1e-3])          # the table's scales: 0 at two exposures
-SMEAR = np.array([0.0, 2e-9, 1e-6, 3e-6, 1.3e-5, 0.0, 1e-5])
-same_bits = sc.same_bits
+SHIFTS = pc.SHIFTS
 
 
-class Case:
-    def __init__(self, P, px, scale, spec):
-        self.P, self.px, self.scale, self.spec = P, px, scale, spec
-        self.sets, self.mirrors = {}, {}
-
-    def observed(self, nexp=7, weighted=True):
-        """the raw observed set, made once"""
-        if (nexp, weighted) not in self.sets:
-            gain = np.random.default_rng(60 + nexp).uniform(0.5, 1.5, sc.NPIX)
-            w = sc.edge_weights(nexp, 80 + nexp) if weighted else None
-            self.sets[(nexp, weighted)] = xcor.Observed(sc.SEG, self.scale * sc.data_set(nexp, 70 + nexp), w, gain)
-        return self.sets[(nexp, weighted)]
-
+class Case(oc.SysremCase):
     def mirror(self, nexp, weighted, ncomp, niter):
         """xcor.sysrem_reference of the raw set, made once"""
-        key = (nexp, weighted, ncomp, niter)
-        if key not in self.mirrors:
-            ob = self.observed(nexp, weighted)
-            self.mirrors[key] = xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, ncomp, niter)
-        return self.mirrors[key]
-
-    def handle(self, ob):
-        E = Engine(self.P.static)
-        E.set_pixels(self.px)
-        if ob is not None:
-            E.set_observed(ob)
-        return E
+        ob = self.observed(nexp, weighted)
+        return self.memo((nexp, weighted, ncomp, niter), lambda: xcor.sysrem_reference(ob.data, ob.weight, ob.seg_first, ncomp, niter))
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("sysrem"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
-    assert sc.LENGTHS == tm.LENGTHS and len(px) == sc.NPIX
-    E = Engine(P.static)
-    spec = E.run(P.atm, P.opts)["spectrum"]
-    E.close()
-    return Case(P, px, float(np.mean(spec)), spec)
-
-
-def nsingular_of(ob, basis):
-    """the dead columns of the weighted filter of `basis` over ob's weights: the mirror of the install step"""
-    return int(np.count_nonzero(~xcor.weighted_factor(ob, xcor.WeightedFilter(basis))[2]))
-
-
-def check_outputs(D, mirror, ob, what):
-    basis, coef, resid = mirror
-    assert np.isfinite(basis).all() and np.isfinite(resid).all(), what
-    assert same_bits(D.basis, basis), what
-    assert same_bits(D.coef, coef), what
-    assert same_bits(D.data, resid), what
-    assert D.nsingular == nsingular_of(ob, basis), what
-
-
-def same_result(a, b):
-    return same_bits(a.basis, b.basis) and same_bits(a.coef, b.coef) and same_bits(a.data, b.data) and a.nsingular == b.nsingular
+    return oc.build_case(tmp_path_factory.mktemp("sysrem"), Case)
 
 
 # ---- 1. bits without injection --------------------------------------------------------------------------------
@@ -103,7 +53,7 @@ def test_bits_without_injection(case, nexp, ncomp, weighted):
         what = "nexp %d, ncomp %d, niter %d, %s" % (nexp, ncomp, niter, "edge weights" if weighted else "no weights")
         D = E.detrend_observed(ncomp, niter)
         mirror = case.mirror(nexp, weighted, ncomp, niter)
-        check_outputs(D, mirror, ob, what)
+        oc.check_sysrem_outputs(D, mirror, ob, what)
         assert D.spectrum is None
         basis, coef, resid = mirror
         # the edges: the empty segment's vectors are zero, every other segment has a first component
@@ -124,7 +74,7 @@ def test_bits_about_a_whole_number_of_trips(case, nexp, weighted):
     """the column kernels take 8 exposures a trip (kSysTrips): one and two whole trips, and one exposure past each"""
     ob = case.observed(nexp, weighted)
     E = case.handle(ob)
-    check_outputs(E.detrend_observed(2, 2), case.mirror(nexp, weighted, 2, 2), ob, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
+    oc.check_sysrem_outputs(E.detrend_observed(2, 2), case.mirror(nexp, weighted, 2, 2), ob, "%d exposures, %s" % (nexp, "edge weights" if weighted else "no weights"))
     E.close()
 
 
@@ -135,7 +85,7 @@ def test_bits_with_injection(case, setup):
     ob = case.observed(7, True)
     E = case.handle(ob)
     if setup != "pixels":
-        E.set_exposures(Exposures(SCALE0.copy(), SMEAR.copy()))
+        E.set_exposures(Exposures(xc.SCALE0.copy(), xc.SMEAR.copy()))
     if "broadening" in setup:
         E.set_broadening(broaden.Rotation(4.0, 0.4))
     # a high-pass takes no part in the injection: the pairs are the ones ahead of it
@@ -146,17 +96,17 @@ def test_bits_with_injection(case, setup):
     p0, p1 = 0.05 / case.scale, 0.9
     f0 = xcor.inject_reference(pairs, ob, p0, p1)
     on = pairs[..., 1] > 0
-    for p in tm.OFF_GRID:                                    # the off-grid pixels keep F
+    for p in xc.OFF_GRID:                                    # the off-grid pixels keep F
         assert not on[:, p].any() and same_bits(f0[:, p], ob.data[:, p])
     assert np.count_nonzero(on) > 7 * 700 and np.all(f0[on] != ob.data[on])
     mirror = xcor.sysrem_reference(f0, ob.weight, ob.seg_first, 3, 10)
     D = E.detrend_observed(3, 10, inject=(P.atm, P.opts, SHIFTS, p0, p1))
-    check_outputs(D, mirror, ob, setup)
+    oc.check_sysrem_outputs(D, mirror, ob, setup)
     assert np.array_equal(D.spectrum, case.spec)             # run()'s bits, never the broadened spectrum
     assert not same_bits(D.data, case.mirror(7, True, 3, 10)[2])
     # p0 = 0, p1 = 1 injects nothing
     D0 = E.detrend_observed(3, 10, inject=(P.atm, P.opts, SHIFTS, 0.0, 1.0))
-    check_outputs(D0, case.mirror(7, True, 3, 10), ob, setup + ", p0 = 0 and p1 = 1")
+    oc.check_sysrem_outputs(D0, case.mirror(7, True, 3, 10), ob, setup + ", p0 = 0 and p1 = 1")
     E.close()
 
 
@@ -169,14 +119,14 @@ def test_from_raw_and_the_undo(case):
     undo = E.detrend_observed(0)                             # nothing had been detrended: TRX_OK
     assert undo.data is None and undo.nsingular == 0 and same_bits(E.run_moments(P.atm, P.opts, SHIFTS), fresh)
     D1 = E.detrend_observed(3, 10)
-    check_outputs(D1, case.mirror(7, True, 3, 10), ob, "first call")
+    oc.check_sysrem_outputs(D1, case.mirror(7, True, 3, 10), ob, "first call")
     assert not same_bits(E.run_moments(P.atm, P.opts, SHIFTS), fresh)
-    assert same_result(E.detrend_observed(3, 10), D1)        # two identical calls
+    assert oc.same_detrend(E.detrend_observed(3, 10), D1)        # two identical calls
     inject = (P.atm, P.opts, SHIFTS, 0.05 / case.scale, 1.0)
     other = E.detrend_observed(5, 2, inject=inject)
     assert other.basis.shape == (8, 7, 5) and not same_bits(other.data, D1.data)
-    assert same_result(E.detrend_observed(3, 10), D1)        # after a different call: a fresh handle's call
-    assert same_result(E.detrend_observed(5, 2, inject=inject), other)
+    assert oc.same_detrend(E.detrend_observed(3, 10), D1)        # after a different call: a fresh handle's call
+    assert oc.same_detrend(E.detrend_observed(5, 2, inject=inject), other)
     quiet = E.detrend_observed(3, 10, outputs=False)
     assert quiet.basis is None and quiet.data is None and quiet.nsingular == D1.nsingular
     mom = E.run_filtered_moments(P.atm, P.opts, SHIFTS)
@@ -188,7 +138,7 @@ def test_from_raw_and_the_undo(case):
         E.run_filtered_moments(P.atm, P.opts, SHIFTS)
     assert ei.value.code == -1 and "no filter installed" in str(ei.value)
     assert E.detrend_observed(0).nsingular == 0              # twice
-    assert same_result(E.detrend_observed(3, 10), D1)
+    assert oc.same_detrend(E.detrend_observed(3, 10), D1)
     assert same_bits(E.run_filtered_moments(P.atm, P.opts, SHIFTS), mom)
     # the undo also clears a filter the caller installed; set_observed drops the raw copy with the set
     E.detrend_observed(0)
@@ -199,7 +149,7 @@ def test_from_raw_and_the_undo(case):
     E.detrend_observed(3, 10)
     ob12 = case.observed(12, True)
     E.set_observed(ob12)
-    check_outputs(E.detrend_observed(9, 1), case.mirror(12, True, 9, 1), ob12, "after set_observed")
+    oc.check_sysrem_outputs(E.detrend_observed(9, 1), case.mirror(12, True, 9, 1), ob12, "after set_observed")
     E.close()
 
 
@@ -207,7 +157,7 @@ def test_from_raw_and_the_undo(case):
 def test_what_is_installed(case):
     P = case.P
     ob = case.observed(7, True)
-    hp, ex, vm = xcor.gaussian_highpass(6.0), Exposures(SCALE0.copy(), SMEAR.copy()), tfm.the_map("ccf", offset=True)
+    hp, ex, vm = xcor.gaussian_highpass(6.0), Exposures(xc.SCALE0.copy(), xc.SMEAR.copy()), xc.the_filtered_map("ccf", offset=True)
     E = case.handle(ob)
     E.set_filter(xcor.svd_filter(ob.data, ob.seg_first, 2))  # a plain filter in the slot: replaced
     E.set_highpass(hp)
@@ -216,7 +166,7 @@ def test_what_is_installed(case):
     exposed, highpassed = E.run_exposed(P.atm, P.opts, SHIFTS), E.run_highpassed(P.atm, P.opts, SHIFTS)
     D = E.detrend_observed(3, 10)
     basis, coef, resid = case.mirror(7, True, 3, 10)
-    check_outputs(D, (basis, coef, resid), ob, "behind a high-pass, a table and a broadening")
+    oc.check_sysrem_outputs(D, (basis, coef, resid), ob, "behind a high-pass, a table and a broadening")
     got = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
     got_map = E.run_exposed_map(P.atm, P.opts, vm)
     F = case.handle(xcor.Observed(ob.seg_first, resid, ob.weight, ob.gain))
@@ -228,7 +178,7 @@ def test_what_is_installed(case):
     want_map = F.run_exposed_map(P.atm, P.opts, vm)
     F.close()
     assert same_bits(got[0], want[0]) and same_bits(got[1], want[1])
-    assert same_bits(got_map, want_map) and np.array_equal(np.isnan(got_map), tfm.OUTSIDE)
+    assert same_bits(got_map, want_map) and np.array_equal(np.isnan(got_map), xc.OUTSIDE)
     assert np.count_nonzero(np.isfinite(got[1]).all(axis=0)) > 700 and np.isnan(got[1][:, sc.MASKED_COL]).all()
     # the high-pass, the table and the broadening survive the call
     assert same_bits(E.run_exposed(P.atm, P.opts, SHIFTS), exposed) and same_bits(E.run_highpassed(P.atm, P.opts, SHIFTS), highpassed)
@@ -295,7 +245,7 @@ def test_no_trace_and_refusals(case):
     # after the refusals: the data and the filter of the last good call
     after = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
     assert same_bits(after[0], ref[0]) and same_bits(after[1], ref[1])
-    assert same_result(E.detrend_observed(3, 10, inject=(P.atm, P.opts, SHIFTS, p0, 1.0)), D)
+    assert oc.same_detrend(E.detrend_observed(3, 10, inject=(P.atm, P.opts, SHIFTS, p0, 1.0)), D)
     E.close()
     # no observed set
     N = case.handle(None)
@@ -335,17 +285,17 @@ def test_injection_and_recovery_end_to_end(case):
     w = rng.uniform(0.5, 2.0, (7, 800))
     w[rng.random((7, 800)) < 0.02] = 0.0
     ob = xcor.Observed(seg, raw, w, rng.uniform(0.5, 1.5, 800))
-    vm = tv.the_map("ccf", kp=tt.KP, vsys=tt.VSYS)
-    cell = (int(np.argmin(np.abs(tt.KP - tt.KP_TRUE))), int(np.argmin(np.abs(tt.VSYS - tt.VSYS_TRUE))))
+    vm = xc.the_map("ccf", kp=xc.TRAIL_KP, vsys=xc.TRAIL_VSYS)
+    cell = (int(np.argmin(np.abs(xc.TRAIL_KP - xc.KP_TRUE))), int(np.argmin(np.abs(xc.TRAIL_VSYS - xc.VSYS_TRUE))))
     assert cell == (2, 3) and (vm.nkp, vm.nvsys) == (5, 5)
-    shifts = np.array([pixels.shift(v) for v in tt.VSYS_TRUE + tt.KP_TRUE * tv.ORBIT])
+    shifts = np.array([pixels.shift(v) for v in xc.VSYS_TRUE + xc.KP_TRUE * xc.ORBIT])
     p0 = 0.1 / case.scale
     E = case.handle(ob)
     E.set_exposures(Exposures(np.ones(7), np.full(7, 2e-6)))
     # the precondition, on the host from the device's pairs: the numpy chain alone finds the injected cell, and does not
     # without the injection
     injected = E.run_exposed(P.atm, P.opts, shifts)
-    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in tv.LAGS])
+    pairs_lv = np.stack([E.run_exposed(P.atm, P.opts, np.full(7, s)) for s in xc.LAGS])
 
     def host_map(data):
         basis, coef, resid = xcor.sysrem_reference(data, w, seg, 2, 10)
@@ -369,7 +319,7 @@ def test_injection_and_recovery_end_to_end(case):
     differ = 0
     for i in range(5):
         for j in range(5):
-            mom = E.run_filtered_moments(P.atm, P.opts, tv.LAGS[idx[i, j]])
+            mom = E.run_filtered_moments(P.atm, P.opts, xc.LAGS[idx[i, j]])
             want, bound = xcor.cell_value(mom, vm), xcor.cell_bound(mom, vm)
             assert bound > 0 and abs(m[i, j] - want) <= bound, (i, j, m[i, j], want, bound)
             differ += m[i, j] != want
@@ -408,7 +358,7 @@ def test_size_and_time(case):
         t0 = time.perf_counter()
         again = E.detrend_observed(ncomp, niter, inject=inject)
         out[name + ", outputs copied"] = time.perf_counter() - t0
-        assert same_result(first, again), name
+        assert oc.same_detrend(first, again), name
         assert np.isfinite(first.basis).all() and np.isfinite(first.coef).all() and np.isfinite(first.data).all(), name
         assert first.basis.shape == (nseg, nexp, ncomp) and np.all(np.abs(np.linalg.norm(first.basis, axis=1) - 1.0) < 1e-12), name
     t0 = time.perf_counter()

@@ -10,13 +10,12 @@ import numpy as np
 import pytest
 
 from cases import GOLDEN
+from tolerances import KEYS, assert_same
 from transit_amd import engine, synth
 from transit_amd.engine import Engine
 from transit_amd.host import Problem
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("e", "e_cs", "tau", "last", "intens", "computed", "er", "e_scat", "e_cloud")
 
 
 def engines(P):
@@ -26,26 +25,6 @@ def engines(P):
     finally:
         os.environ.pop("TRX_RAY_TAIL", None)
     return Engine(P.static), ref
-
-
-def assert_same(ra, rb, note=None):
-    sw = ra["computed"].astype(bool) if "computed" in ra else slice(None)
-    assert set(ra) == set(rb)
-    for k in ra:
-        if k in ("e", "e_cs", "e_scat", "e_cloud"):
-            assert np.array_equal(ra[k][sw], rb[k][sw]), (k, note)
-        elif k == "er":
-            # (edited extinction: written down to the ray's stopping height only)
-            nl = ra[k].shape[0]
-            used = (nl - 1 - np.arange(nl))[:, None] <= ra["last"][None, :]
-            assert np.array_equal(ra[k][used], rb[k][used]), (k, note)
-        elif k == "tau":
-            # heights a ray never reached hold whatever an earlier run left: compare what the ray used
-            last = ra["last"]
-            used = np.arange(ra[k].shape[1])[None, :] <= last[:, None]
-            assert np.array_equal(ra[k][used], rb[k][used]), (k, note)
-        else:
-            assert np.array_equal(ra[k], rb[k]), (k, note)
 
 
 def tail_runs(msgs):

@@ -1,7 +1,7 @@
 """The cross-correlation trail on the device (trx_run_trail / trx_run_batch_trail, include/transit_hip.h): every
 exposure of the observed set against the model at every lag of a grid.
 
-The case is test_gpu_moments': tp.make (20 000-40 000 lines, 6001 bins, 60 layers), its 800-pixel set with the two
+The case is xcor_checks': pixel_cases.make (20 000-40 000 lines, 6001 bins, 60 layers), its 800-pixel set with the two
 off-grid pixels, observed() with segment lengths [1, 63, 64, 65, 200, 0, 7, 400], 7 exposures, 5 % zero weights.  The
 lags are its seven SHIFTS followed by the first two again, 9 in all: ragged for a lag tile of 2 or 4 (the last tile has
 one lag), as the 7 exposures are for a tile of 4, and lags 7 and 8 repeat lags 0 and 1.
@@ -9,7 +9,7 @@ one lag), as the 7 exposures are for a tile of 4, and lags 7 and 8 repeat lags 0
 THE CONTRACT: trail[l] is, bit for bit, what run_moments gives on the same handle when all seven shifts equal lag l.
 
 Tolerance of the accuracy check, per moment, relative to xcor.trail_abs_reference: (n_max + 16) * 2^-52 with n_max = 400
-the longest segment -- the bound test_gpu_moments derives for the same sum in the same order (a double sum of n terms,
+the longest segment -- the bound xcor_checks' docstring derives for the same sum in the same order (a double sum of n terms,
 (n - 1) * 2^-53 each way it is ordered, each term of at most four correctly rounded operations); the count is exact.
 
 The end-to-end test: the data are the model's own pixel values at the shifts of a planet with (Kp, Vsys) = (100, 6) km/s
@@ -26,24 +26,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-from test_gpu_bands import thinner
-from test_gpu_batch import atmospheres
+import pixel_cases as pc
+import xcor_checks as xc
 from transit_amd import _abi, broaden, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tm.SHIFTS
+SHIFTS = pc.SHIFTS
 LAGS = np.concatenate([SHIFTS, SHIFTS[:2]])
-EPS = 2.0 ** -52
-NEXP = len(SHIFTS)
-
-KP_TRUE, VSYS_TRUE = 100.0, 6.0
-PHASE = np.linspace(-0.06, 0.06, NEXP)
-KP, VSYS = np.array([40.0, 70.0, 100.0, 130.0, 160.0]), np.array([-12.0, -6.0, 0.0, 6.0, 12.0])
-LAG_STEP = 3.0
 
 
 def by_moments(E, atm, opts, lags):
@@ -51,50 +42,27 @@ def by_moments(E, atm, opts, lags):
     return np.stack([E.run_moments(atm, opts, [lag] * E.mom_shape[0]) for lag in lags])
 
 
-def check_trail(trail, pairs, ob, what=""):
-    """the count exactly, every other moment to (n_max + 16) * 2^-52 of the sum of its absolute terms; an empty row is
-    seven +0"""
-    ref, scale = xcor.trail_reference(pairs, ob), xcor.trail_abs_reference(pairs, ob)
-    assert trail.shape == ref.shape == (pairs.shape[0], ob.nexp, ob.nseg, 7)
-    assert np.array_equal(trail[..., 0], ref[..., 0]), what
-    tol = (int(np.max(np.diff(ob.seg_first))) + 16) * EPS
-    empty = ref[..., 0] == 0
-    assert np.all(trail[empty] == 0) and not np.any(np.signbit(trail[empty])), what
-    ratio = np.abs(trail - ref)[~empty][:, 1:] / scale[~empty][:, 1:]
-    worst = float(ratio.max())
-    print("%s: worst |trail - ref| / abs_ref %.3e = %.2f * 2^-52 (tolerance %.3e)" % (what, worst, worst / EPS, tol))
-    assert worst <= tol, (what, worst, tol)
-    return ref
-
-
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
     """(P, px, ob): the eclipse case at 20 000 lines, the 800 pixels, the observed set"""
-    P = tp.make(tmp_path_factory.mktemp("trail"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
+    P = pc.make(tmp_path_factory.mktemp("trail"), "eclipse", nlines=20_000)
+    px = xc.pixel_set(P)
     plain = Engine(P.static)
     scale = float(np.mean(plain.run(P.atm, P.opts)["spectrum"]))
     plain.close()
-    return P, px, tm.observed(len(px), scale)
-
-
-def handle(P, px, ob):
-    E = Engine(P.static)
-    E.set_pixels(px)
-    E.set_observed(ob)
-    return E
+    return P, px, xc.observed(len(px), scale)
 
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
 def test_trail_is_the_moments_of_every_lag_bit_for_bit(tmp_path, solution):
-    P = tp.make(tmp_path, solution)
+    P = pc.make(tmp_path, solution)
     assert P.nwn == 6001
-    px = tm.pixel_set(P)
+    px = xc.pixel_set(P)
     plain = Engine(P.static)
-    ob = tm.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(plain.run(P.atm, P.opts)["spectrum"])))
     assert (ob.nexp, ob.nseg) == (7, 8)
-    E = handle(P, px, ob)
-    deep, keep = thinner(P, 1e-3)
+    E = xc.handle(P, px, ob)
+    deep, keep = pc.thinner(P, 1e-3)
     seen = set()
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):      # fresh, hinted, resuming deeper, hinted again
         trail, spec = E.run_trail(atm, P.opts, LAGS, spectrum=True)
@@ -113,14 +81,14 @@ def test_trail_is_the_moments_of_every_lag_bit_for_bit(tmp_path, solution):
 
 def test_trail_is_the_definition_over_the_pixel_pairs(case):
     P, px, ob = case
-    E = handle(P, px, ob)
+    E = xc.handle(P, px, ob)
     assert np.count_nonzero(ob.weight == 0) > 100
     pairs = E.run_pixels(P.atm, P.opts, LAGS)
     trail = E.run_trail(P.atm, P.opts, LAGS)
-    for p in tm.OFF_GRID:                                      # the off-grid pixels count nowhere
+    for p in xc.OFF_GRID:                                      # the off-grid pixels count nowhere
         assert np.all(pairs[:, p, 1] == 0)
     assert np.count_nonzero(pairs[..., 1] > 0) == 9 * 798
-    ref = check_trail(trail, pairs, ob, "9 lags x 7 exposures x 8 segments")
+    ref = xc.check_trail(trail, pairs, ob, "9 lags x 7 exposures x 8 segments")
     some = np.diff(ob.seg_first) > 0
     want_n = np.add.reduceat(((pairs[:, None, :, 1] > 0) & (ob.weight[None] > 0)).astype(float), ob.seg_first[:-1][some], axis=2)
     assert np.array_equal(trail[..., 0][:, :, some], want_n)
@@ -131,7 +99,7 @@ def test_trail_is_the_definition_over_the_pixel_pairs(case):
 
 def test_bits_do_not_depend_on_the_rest_of_the_call(case):
     P, px, ob = case
-    E = handle(P, px, ob)
+    E = xc.handle(P, px, ob)
     first = E.run_trail(P.atm, P.opts, LAGS)
     # one lag; a permuted subset of the lags
     for l in (0, 4, 8):
@@ -152,7 +120,7 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
     ob2 = xcor.Observed(xcor.segments([300, 200, 300]), ob.data)
     E.set_observed(ob2)
     trail = E.run_trail(P.atm, P.opts, LAGS)
-    check_trail(trail, E.run_pixels(P.atm, P.opts, LAGS), ob2, "[300, 200, 300], w = gain = 1")
+    xc.check_trail(trail, E.run_pixels(P.atm, P.opts, LAGS), ob2, "[300, 200, 300], w = gain = 1")
     assert trail[0, 0, :, 0].tolist() == [299.0, 200.0, 299.0] and np.array_equal(trail[..., 1], trail[..., 0])
     assert np.array_equal(trail, by_moments(E, P.atm, P.opts, LAGS))
     E.close()
@@ -160,7 +128,7 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(case):
 
 def test_broadening_applies_and_the_filter_does_not(case):
     P, px, ob = case
-    E = handle(P, px, ob)
+    E = xc.handle(P, px, ob)
     bare = E.run_trail(P.atm, P.opts, LAGS)
     # what the neighbours give before any trail with the other sets installed
     F = xcor.svd_filter(ob.data, ob.seg_first, 2)
@@ -172,7 +140,7 @@ def test_broadening_applies_and_the_filter_does_not(case):
     after = (E.run_moments(P.atm, P.opts, SHIFTS), E.run_filtered_moments(P.atm, P.opts, SHIFTS), E.run_pixels(P.atm, P.opts, SHIFTS))
     for a, b in zip(before, after):
         assert np.array_equal(a, b, equal_nan=True)
-    assert np.array_equal(before[0], np.stack([bare[v, v] for v in range(NEXP)]))      # the trail's diagonal IS the moment run
+    assert np.array_equal(before[0], np.stack([bare[v, v] for v in range(xc.NEXP)]))      # the trail's diagonal IS the moment run
     # with a broadening installed: the contract, against run_moments under the same broadening
     E.set_broadening(broaden.Rotation(4.0, 0.4))
     broad = E.run_trail(P.atm, P.opts, LAGS)
@@ -185,14 +153,14 @@ def test_broadening_applies_and_the_filter_does_not(case):
 
 
 def test_batch_trails_are_the_single_handle_trails(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=30_000, seed=33)
-    px = tm.pixel_set(P)
+    P = pc.make(tmp_path, "eclipse", nlines=30_000, seed=33)
+    px = xc.pixel_set(P)
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     lags = np.stack([np.roll(LAGS, j) * (1.0 + 1e-6 * j) for j in range(K)])
     one = Engine(P.static)
     one.set_pixels(px)
-    ob = tm.observed(len(px), float(np.mean(one.run(P.atm, P.opts)["spectrum"])))
+    ob = xc.observed(len(px), float(np.mean(one.run(P.atm, P.opts)["spectrum"])))
     one.set_observed(ob)
     ref = np.stack([one.run_trail(atms[j], P.opts, lags[j]) for j in range(K)])
     one.close()
@@ -207,28 +175,6 @@ def test_batch_trails_are_the_single_handle_trails(tmp_path):
     B.close()
 
 
-def end_to_end_map(px, run_pixels, trail_of):
-    """(map [5, 5], the injected cell): the data are the model's own pixel values at the planet's shifts times the gain,
-    unit weights, two segments (the pixels at R = 20 000 and those at R = 3000); run_pixels(shifts) gives the pairs,
-    trail_of(lags, ob) the trail of the observed set"""
-    sin = np.sin(2 * np.pi * PHASE)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        value = pixels.value(run_pixels(np.array([pixels.shift(v) for v in VSYS_TRUE + KP_TRUE * sin])))
-    gain = np.random.default_rng(4).uniform(0.5, 1.5, len(px))
-    data = np.where(np.isfinite(value), gain[None, :] * value, 0.0)           # (the off-grid pixels: any finite datum)
-    ob = xcor.Observed(xcor.segments([400, 400]), data, None, gain)
-    # the lag step is at most a quarter of the narrowest pixel's FWHM in velocity
-    assert LAG_STEP <= 0.25 * pixels.C_KMS * float(np.min(px.fwhm / px.centre))
-    lag_kms, lags = xcor.lag_grid(-81.0, 81.0, LAG_STEP)
-    assert lag_kms.size == 55
-    trail = trail_of(lags, ob)
-    assert trail.shape == (55, NEXP, 2, 7)
-    vp = VSYS[None, :, None] + KP[:, None, None] * sin[None, None, :]
-    m = xcor.velocity_map(trail, lag_kms, vp, stat=xcor.ccf)
-    assert m.shape == (5, 5) and np.all(np.isfinite(m))
-    return m, (int(np.argmin(np.abs(KP - KP_TRUE))), int(np.argmin(np.abs(VSYS - VSYS_TRUE))))
-
-
 def test_velocity_map_of_the_models_own_data_peaks_at_the_injected_cell(case):
     P, px, _ = case
     E = Engine(P.static)
@@ -238,16 +184,16 @@ def test_velocity_map_of_the_models_own_data_peaks_at_the_injected_cell(case):
         E.set_observed(ob)
         return E.run_trail(P.atm, P.opts, lags)
 
-    m, cell = end_to_end_map(px, lambda sh: E.run_pixels(P.atm, P.opts, sh), trail_of)
+    m, cell = xc.end_to_end_map(px, lambda sh: E.run_pixels(P.atm, P.opts, sh), trail_of)
     peak = tuple(int(i) for i in np.unravel_index(np.argmax(m), m.shape))
     print("map (rows Kp, columns Vsys):\n%s\npeak at %s, injected at %s" % (np.array2string(m, precision=4), peak, cell))
     assert cell == (2, 3) and peak == cell
-    assert m[cell] <= 2 * NEXP * (1 + 1e-12)                   # a correlation coefficient per exposure and segment
+    assert m[cell] <= 2 * xc.NEXP * (1 + 1e-12)                   # a correlation coefficient per exposure and segment
     E.close()
 
 
 def test_refusals(tmp_path):
-    P = tp.make(tmp_path, "eclipse", nlines=10_000)
+    P = pc.make(tmp_path, "eclipse", nlines=10_000)
     lag = np.ascontiguousarray(LAGS[:5])
     good_px = pixels.Pixels([2510.0, 2520.0, 2530.0, 2540.0], [0.2, 0.3, 1.5, 0.4], 4.0)
     rng = np.random.default_rng(2)
@@ -288,7 +234,7 @@ def test_refusals(tmp_path):
     assert run(5, lag, out)[0] == 0 and np.array_equal(out, before)
     assert np.array_equal(E.run_trail(P.atm, P.opts, lag), before)
     # 2^31 - 1 lags x 800 pixels: more pairs than one pixel launch takes (one exposure, one segment: the rows fit)
-    px = tm.pixel_set(P)
+    px = xc.pixel_set(P)
     E.set_pixels(px)
     E.set_observed(xcor.Observed([0, 800], np.zeros((1, 800))))
     rc, msg = run(2 ** 31 - 1, lag, out)

@@ -2,11 +2,11 @@
 trx_run_trail followed there by the statistic of every trail row added over the segments in order (per [nlag, nexp])
 and by the map, per interpolated along every cell's velocity track and added over the exposures in order.
 
-The case is test_gpu_trail's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800-pixel set, 7 exposures at
+The case is xcor_checks': pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800-pixel set, 7 exposures at
 PHASE = linspace(-0.06, 0.06, 7), the lag grid -81 .. 81 km/s in steps of 3 (55 lags; 55 x 7 = 385 rows is no multiple of
-the 4 rows of a block), and two observed sets: tm.observed() with the segments [1, 63, 64, 65, 200, 0, 7, 400] -- the
+the 4 rows of a block), and two observed sets: xcor_checks.observed() with the segments [1, 63, 64, 65, 200, 0, 7, 400] -- the
 1-pixel and the empty segment are rows ccf and loglike_bl19 skip -- and the two-segment own-data set of
-test_gpu_trail.end_to_end_map.  The map is Kp = 40, 70, 100, 130, 160, 190, 250 by Vsys = -12 .. 12 in steps of 6: with
+xcor_checks.end_to_end_map.  The map is Kp = 40, 70, 100, 130, 160, 190, 250 by Vsys = -12 .. 12 in steps of 6: with
 sin(2 pi 0.06) = 0.36812 the Kp = 250 row is outside the lag grid everywhere (92.0 + |Vsys| > 81), the Kp = 190 row at
 Vsys = +-12 only (81.9), everything else inside; the middle exposure has orbit = 0 and sits on lag nodes.  A second grid
 of 13 x 11 = 143 cells is more than one block and ends in a ragged one.  More than one trip of a wave over the exposures
@@ -21,72 +21,41 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_trail as tt
-from test_gpu_bands import thinner
-from test_gpu_batch import atmospheres
+import pixel_cases as pc
+import xcor_checks as xc
 from transit_amd import _abi, broaden, pixels, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
-
-STATS = ("ccf", "loglike_bl19", "chi2")
-PHASE = tt.PHASE
-ORBIT = np.sin(2 * np.pi * PHASE)
-LAG_KMS, LAGS = xcor.lag_grid(-81.0, 81.0, tt.LAG_STEP)
-KP, VSYS = np.array([40.0, 70.0, 100.0, 130.0, 160.0, 190.0, 250.0]), np.arange(-12.0, 13.0, 6.0)
-KP2, VSYS2 = np.linspace(30.0, 210.0, 13), np.linspace(-15.0, 15.0, 11)
-OFFSET = 0.3 * np.cos(np.arange(len(PHASE)))
-OUTSIDE = np.zeros((7, 5), dtype=bool)
-OUTSIDE[6], OUTSIDE[5, [0, 4]] = True, True
-
-
-def the_map(stat="ccf", second=False, offset=False, **over):
-    kw = dict(lag_kms=LAG_KMS, kp=KP2 if second else KP, vsys=VSYS2 if second else VSYS, orbit=ORBIT,
-              offset=OFFSET if offset is True else None if offset is False else offset,
-              stat=stat, scale=0.9, a=1.1, b=0.2)
-    kw.update(over)
-    return xcor.VelocityMap(**kw)
 
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
     """(P, px, ob, trail): the eclipse case at 20 000 lines, the 800 pixels, the 8-segment observed set and run_trail's
     trail of it at the 55 lags"""
-    P = tp.make(tmp_path_factory.mktemp("vmap"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
+    P = pc.make(tmp_path_factory.mktemp("vmap"), "eclipse", nlines=20_000)
+    px = xc.pixel_set(P)
     plain = Engine(P.static)
     scale = float(np.mean(plain.run(P.atm, P.opts)["spectrum"]))
     plain.close()
-    ob = tm.observed(len(px), scale)
-    E = tt.handle(P, px, ob)
-    trail = E.run_trail(P.atm, P.opts, LAGS)
+    ob = xc.observed(len(px), scale)
+    E = xc.handle(P, px, ob)
+    trail = E.run_trail(P.atm, P.opts, xc.LAGS)
     E.close()
-    assert trail.shape == (55, 7, 8, 7) and LAG_KMS.size == 55
+    assert trail.shape == (55, 7, 8, 7) and xc.LAG_KMS.size == 55
     return P, px, ob, trail
-
-
-def check_per(per, trail, vm, what):
-    """per against trail_statistic of the trail within per_bound; the count of differing rows and the worst ratio"""
-    want, tol = xcor.trail_statistic(trail, vm), xcor.per_bound(trail, vm)
-    assert per.shape == want.shape and np.all(np.isfinite(per)) and np.all(tol > 0)
-    ratio = float(np.max(np.abs(per - want) / tol))
-    print("%s %s: %d of %d rows differ from numpy, worst |per - ref| / per_bound %.4f" % (what, vm.stat, np.count_nonzero(per != want), per.size, ratio))
-    assert ratio <= 1.0, (what, vm.stat, ratio)
-    return want
 
 
 def test_per_is_the_statistic_added_over_the_segments_in_order(case):
     P, px, ob, trail = case
-    E = tt.handle(P, px, ob)
+    E = xc.handle(P, px, ob)
     # the 1-pixel and the empty segment are skipped by ccf and loglike_bl19; chi-square has a value for every row
     assert np.all(np.isnan(xcor.ccf(trail)[:, :, [0, 5]])) and np.all(np.isfinite(xcor.ccf(trail)[:, :, [1, 2, 3, 4, 6, 7]]))
     assert np.all(trail[:, :, 5] == 0) and np.all(trail[:, :, 0, 0] <= 1)
-    for stat in STATS:
-        vm = the_map(stat)
+    for stat in xc.STATS:
+        vm = xc.the_map(stat)
         m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
-        want = check_per(per, trail, vm, "8 segments")
+        want = xc.check_per(per, trail, vm, "8 segments")
         if stat != "loglike_bl19":                             # (the expectation, printed above; the assertion is the bound)
             print("%s: per has numpy's bits: %s" % (stat, np.array_equal(per, want)))
         if stat == "ccf":                                       # skipped, not counted: six coefficients at the most
@@ -94,19 +63,19 @@ def test_per_is_the_statistic_added_over_the_segments_in_order(case):
     E.close()
 
 
-@pytest.mark.parametrize("stat", STATS)
+@pytest.mark.parametrize("stat", xc.STATS)
 def test_map_is_map_from_per_bit_for_bit(case, stat):
     P, px, ob, trail = case
-    E = tt.handle(P, px, ob)
+    E = xc.handle(P, px, ob)
     pers = []
     for second in (False, True):
         for offset in (False, True):
-            vm = the_map(stat, second, offset)
+            vm = xc.the_map(stat, second, offset)
             m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
             assert m.shape == ((13, 11) if second else (7, 5))
             assert np.array_equal(m, xcor.map_from_per(per, vm), equal_nan=True), (stat, second, offset)
             if not second:
-                assert np.array_equal(np.isnan(m), OUTSIDE), (stat, offset)
+                assert np.array_equal(np.isnan(m), xc.OUTSIDE), (stat, offset)
             else:
                 assert 0 < np.count_nonzero(np.isnan(m)) < m.size // 2
             pers.append(per)
@@ -125,19 +94,19 @@ def test_own_data_map_peaks_at_the_injected_cell(case):
     def trail_of(lags, ob):
         E.set_observed(ob)
         seen["ob"], seen["trail"] = ob, E.run_trail(P.atm, P.opts, lags)
-        assert np.array_equal(lags, LAGS)
+        assert np.array_equal(lags, xc.LAGS)
         return seen["trail"]
 
-    m5, cell = tt.end_to_end_map(px, lambda sh: E.run_pixels(P.atm, P.opts, sh), trail_of)
+    m5, cell = xc.end_to_end_map(px, lambda sh: E.run_pixels(P.atm, P.opts, sh), trail_of)
     assert cell == (2, 3) and seen["ob"].nseg == 2
-    vm = the_map("ccf")
+    vm = xc.the_map("ccf")
     m = E.run_velocity_map(P.atm, P.opts, vm)                  # (the own-data set is still installed)
-    vp = VSYS[None, :, None] + KP[:, None, None] * ORBIT[None, None, :]
-    old = xcor.velocity_map(seen["trail"], LAG_KMS, vp, stat=xcor.ccf)
+    vp = xc.VSYS[None, :, None] + xc.KP[:, None, None] * xc.ORBIT[None, None, :]
+    old = xcor.velocity_map(seen["trail"], xc.LAG_KMS, vp, stat=xcor.ccf)
     bound = xcor.map_bound(seen["trail"], vm)
-    assert np.array_equal(np.isnan(m), OUTSIDE) and np.array_equal(np.isnan(old), OUTSIDE)
+    assert np.array_equal(np.isnan(m), xc.OUTSIDE) and np.array_equal(np.isnan(old), xc.OUTSIDE)
     ratio = float(np.nanmax(np.abs(m - old) / bound))
-    print("own data: worst |map - velocity_map(run_trail)| / map_bound %.4f; %d of 28 cells differ" % (ratio, np.count_nonzero(m[~OUTSIDE] != old[~OUTSIDE])))
+    print("own data: worst |map - velocity_map(run_trail)| / map_bound %.4f; %d of 28 cells differ" % (ratio, np.count_nonzero(m[~xc.OUTSIDE] != old[~xc.OUTSIDE])))
     assert ratio <= 1.0
     assert np.array_equal(m[:5], m5) or float(np.max(np.abs(m[:5] - m5) / bound[:5])) <= 1.0
     peak = tuple(int(i) for i in np.unravel_index(np.nanargmax(m), m.shape))
@@ -151,28 +120,28 @@ def test_own_data_map_peaks_at_the_injected_cell(case):
 
 def test_cells_do_not_depend_on_the_rest_of_the_call_or_on_the_handles_history(case):
     P, px, ob, trail = case
-    E = tt.handle(P, px, ob)
-    for stat in STATS:
-        vm = the_map(stat, offset=True)
+    E = xc.handle(P, px, ob)
+    for stat in xc.STATS:
+        vm = xc.the_map(stat, offset=True)
         m = E.run_velocity_map(P.atm, P.opts, vm)
         rows, cols = [4, 1, 6, 3], [3, 0]
-        sub = E.run_velocity_map(P.atm, P.opts, the_map(stat, offset=True, kp=KP[rows], vsys=VSYS[cols]))
+        sub = E.run_velocity_map(P.atm, P.opts, xc.the_map(stat, offset=True, kp=xc.KP[rows], vsys=xc.VSYS[cols]))
         assert np.array_equal(sub, m[np.ix_(rows, cols)], equal_nan=True), stat
-        one = E.run_velocity_map(P.atm, P.opts, the_map(stat, offset=True, kp=KP[2:3], vsys=VSYS[3:4]))
+        one = E.run_velocity_map(P.atm, P.opts, xc.the_map(stat, offset=True, kp=xc.KP[2:3], vsys=xc.VSYS[3:4]))
         assert one.shape == (1, 1) and one[0, 0] == m[2, 3]
         assert np.array_equal(E.run_velocity_map(P.atm, P.opts, vm), m, equal_nan=True)
     E.close()
     # fresh, hinted, resuming deeper, hinted again -- against a second handle's trail of the same atmosphere
-    E, T = tt.handle(P, px, ob), tt.handle(P, px, ob)
-    deep, keep = thinner(P, 1e-3)
-    vm = the_map("loglike_bl19")
+    E, T = xc.handle(P, px, ob), xc.handle(P, px, ob)
+    deep, keep = pc.thinner(P, 1e-3)
+    vm = xc.the_map("loglike_bl19")
     seen = set()
     for k, atm in enumerate((P.atm, P.atm, deep, P.atm)):
         m, per, spec = E.run_velocity_map(atm, P.opts, vm, per=True, spectrum=True)
-        tr, want_spec = T.run_trail(atm, P.opts, LAGS, spectrum=True)
+        tr, want_spec = T.run_trail(atm, P.opts, xc.LAGS, spectrum=True)
         assert np.array_equal(spec, want_spec), k
         assert np.array_equal(m, xcor.map_from_per(per, vm), equal_nan=True), k
-        check_per(per, tr, vm, "atmosphere %d" % k)
+        xc.check_per(per, tr, vm, "atmosphere %d" % k)
         seen.add(per.tobytes())
     assert len(seen) == 2
     E.close(); T.close()
@@ -180,12 +149,12 @@ def test_cells_do_not_depend_on_the_rest_of_the_call_or_on_the_handles_history(c
 
 def test_neighbours_on_the_handle_filter_and_broadening(case):
     P, px, ob, trail = case
-    E = tt.handle(P, px, ob)
-    vm = the_map("ccf")
-    before = (E.run_trail(P.atm, P.opts, LAGS), E.run_moments(P.atm, P.opts, tm.SHIFTS), E.run_pixels(P.atm, P.opts, tm.SHIFTS))
+    E = xc.handle(P, px, ob)
+    vm = xc.the_map("ccf")
+    before = (E.run_trail(P.atm, P.opts, xc.LAGS), E.run_moments(P.atm, P.opts, pc.SHIFTS), E.run_pixels(P.atm, P.opts, pc.SHIFTS))
     assert np.array_equal(before[0], trail)
     m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
-    after = (E.run_trail(P.atm, P.opts, LAGS), E.run_moments(P.atm, P.opts, tm.SHIFTS), E.run_pixels(P.atm, P.opts, tm.SHIFTS))
+    after = (E.run_trail(P.atm, P.opts, xc.LAGS), E.run_moments(P.atm, P.opts, pc.SHIFTS), E.run_pixels(P.atm, P.opts, pc.SHIFTS))
     for a, b in zip(before, after):
         assert np.array_equal(a, b, equal_nan=True)
     # a filter takes no part
@@ -195,12 +164,12 @@ def test_neighbours_on_the_handle_filter_and_broadening(case):
     E.set_filter(None)
     # a broadening applies: the trail under it is run_trail's under it
     E.set_broadening(broaden.Rotation(4.0, 0.4))
-    for stat in STATS:
-        vb = the_map(stat)
+    for stat in xc.STATS:
+        vb = xc.the_map(stat)
         mb, pb = E.run_velocity_map(P.atm, P.opts, vb, per=True)
-        broad = E.run_trail(P.atm, P.opts, LAGS)
+        broad = E.run_trail(P.atm, P.opts, xc.LAGS)
         assert np.array_equal(mb, xcor.map_from_per(pb, vb), equal_nan=True)
-        check_per(pb, broad, vb, "broadened")
+        xc.check_per(pb, broad, vb, "broadened")
         if stat == "ccf":
             assert np.all(pb != per)
     E.set_broadening(None)
@@ -211,9 +180,9 @@ def test_neighbours_on_the_handle_filter_and_broadening(case):
 def test_batch_maps_are_the_single_handle_maps(case):
     P, px, ob, _ = case
     K = 3
-    atms, keep = atmospheres(P, K)
-    vm = the_map("loglike_bl19", second=True, offset=True)
-    one = tt.handle(P, px, ob)
+    atms, keep = pc.atmospheres(P, K)
+    vm = xc.the_map("loglike_bl19", second=True, offset=True)
+    one = xc.handle(P, px, ob)
     ref = [one.run_velocity_map(atms[j], P.opts, vm, per=True) for j in range(K)]
     one.close()
     assert len({r[1].tobytes() for r in ref}) == K
@@ -231,12 +200,12 @@ def test_batch_maps_are_the_single_handle_maps(case):
 
 def test_one_lag(case):
     P, px, ob, _ = case
-    E = tt.handle(P, px, ob)
-    for stat in STATS:
-        vm = the_map(stat, lag_kms=[6.0], kp=[100.0, 50.0], vsys=[6.0, 7.0], orbit=np.zeros(7))      # x = vsys: on the lag, or outside
+    E = xc.handle(P, px, ob)
+    for stat in xc.STATS:
+        vm = xc.the_map(stat, lag_kms=[6.0], kp=[100.0, 50.0], vsys=[6.0, 7.0], orbit=np.zeros(7))      # x = vsys: on the lag, or outside
         m, per = E.run_velocity_map(P.atm, P.opts, vm, per=True)
         assert per.shape == (1, 7) and m.shape == (2, 2)
-        check_per(per, E.run_trail(P.atm, P.opts, vm.lag), vm, "one lag")
+        xc.check_per(per, E.run_trail(P.atm, P.opts, vm.lag), vm, "one lag")
         assert np.array_equal(m, xcor.map_from_per(per, vm), equal_nan=True)
         assert np.array_equal(np.isnan(m), [[False, True], [False, True]]) and m[0, 0] == m[1, 0]
     E.close()
@@ -247,7 +216,7 @@ def test_refusals(case):
     dp = _abi.c_double_p
     E = Engine(P.static)
     lib = E._lib
-    vm = the_map("chi2", offset=True)
+    vm = xc.the_map("chi2", offset=True)
     with pytest.raises(EngineError) as ei:                     # no pixel set, no observed set
         E.run_velocity_map(P.atm, P.opts, vm)
     assert ei.value.code == -1 and "observed" in str(ei.value)
@@ -284,7 +253,7 @@ def test_refusals(case):
     for bad in (np.nan, np.inf, 0.0, -1.0):
         lag = vm.lag.copy()
         lag[1] = bad
-        refused(the_map("chi2", lag=lag).to_c(), "lag 1 must be finite and > 0")
+        refused(xc.the_map("chi2", lag=lag).to_c(), "lag 1 must be finite and > 0")
     # the map's own
     refused(changed(stat=0), "unknown stat 0")
     refused(changed(stat=4), "unknown stat 4")
@@ -299,11 +268,11 @@ def test_refusals(case):
         for bad in (np.nan, np.inf):
             arr = np.array(getattr(vm, name), dtype=float)
             arr[at] = bad
-            refused(the_map("chi2", **{"offset": True, name: arr}).to_c(), "%s %d must be finite" % (name, at))
-    for at, bad in ((0, np.nan), (54, np.inf), (2, LAG_KMS[1]), (3, LAG_KMS[1])):
-        kms = LAG_KMS.copy()
+            refused(xc.the_map("chi2", **{"offset": True, name: arr}).to_c(), "%s %d must be finite" % (name, at))
+    for at, bad in ((0, np.nan), (54, np.inf), (2, xc.LAG_KMS[1]), (3, xc.LAG_KMS[1])):
+        kms = xc.LAG_KMS.copy()
         kms[at] = bad
-        refused(the_map("chi2", offset=True, lag_kms=kms, lag=vm.lag).to_c(), "lag_kms %d must be finite and above" % at)
+        refused(xc.the_map("chi2", offset=True, lag_kms=kms, lag=vm.lag).to_c(), "lag_kms %d must be finite and above" % at)
     # the handle is usable and the next run's bits are unchanged; per may be NULL
     alone = np.zeros((7, 5))
     assert lib.trx_run_velocity_map(E._h, C.byref(P.atm), C.byref(P.opts), None, C.byref(vm.to_c()), alone.ctypes.data_as(dp), None, None) == 0
@@ -352,7 +321,7 @@ def test_refusals(case):
     worse = vm.orbit.copy()
     worse[5] = np.nan
     with pytest.raises(EngineError) as ei:
-        B.run_velocity_map([P.atm, P.atm], P.opts, the_map("chi2", offset=True, orbit=worse))
+        B.run_velocity_map([P.atm, P.atm], P.opts, xc.the_map("chi2", offset=True, orbit=worse))
     assert ei.value.code == -1 and "orbit 5 must be finite" in str(ei.value)
     again = B.run_velocity_map([P.atm, P.atm], P.opts, vm, per=True)
     assert np.array_equal(again[0], ref[0], equal_nan=True) and np.array_equal(again[1], ref[1])

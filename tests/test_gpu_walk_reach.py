@@ -18,8 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_random import check_against_oracle, oracle
-from test_gpu_tail import KEYS, assert_same
+from tolerances import KEYS, assert_same, check_against_oracle, oracle
 from transit_amd import engine, synth
 from transit_amd.engine import Engine
 from transit_amd.host import Problem
@@ -90,7 +89,7 @@ def handles(P, env=None):
     return out
 
 
-def same_bits(P, env=None, scales=(1.0, 1.0, 0.03, 1.0), note=None):
+def runs_give_the_same_bits(P, env=None, scales=(1.0, 1.0, 0.03, 1.0), note=None):
     """Unhinted, hinted, resumed (the atmosphere thinner under the remembered depth) and hinted again, with every
     debug array; then a production run (finished rays' ranges skipped)."""
     a, b = handles(P, env)
@@ -136,7 +135,7 @@ def test_64_layer_step_same_bits(problems, solution, two_queues):
     fr = frames_of(P) if two_queues == "1" else None
     if fr is not None:
         assert fr[:40].count(2) >= 30, fr              # the upper layers reach less than a cell: the zone exists
-    same_bits(P, env={"TRX_TWO_QUEUES": two_queues}, note=(solution, two_queues))
+    runs_give_the_same_bits(P, env={"TRX_TWO_QUEUES": two_queues}, note=(solution, two_queues))
 
 
 @pytest.mark.parametrize("solution", ["eclipse", "transit"])
@@ -151,7 +150,7 @@ def test_against_the_oracle(problems, solution):
             check_against_oracle(P, hip, ref, (solution, rep))
     finally:
         hip.close()
-    same_bits(P, note=solution)
+    runs_give_the_same_bits(P, note=solution)
 
 
 @pytest.mark.parametrize("nlayers,chunk", [(24, 1), (24, 5), (16, 8), (8, 0)])
@@ -165,7 +164,7 @@ def test_every_step_through_k_line_walk(problems, nlayers, chunk):
     assert 2 in fr, fr                               # the upper layers reach less than a cell
     P.opts.eager, P.opts.layer_chunk = (1, chunk) if chunk else (0, 0)
     try:
-        same_bits(P, env=env, scales=(1.0, 1.0), note=(nlayers, chunk))
+        runs_give_the_same_bits(P, env=env, scales=(1.0, 1.0), note=(nlayers, chunk))
     finally:
         P.opts.eager, P.opts.layer_chunk = 0, 0
 
@@ -173,8 +172,8 @@ def test_every_step_through_k_line_walk(problems, nlayers, chunk):
 def test_threshold_that_drops_groups(problems):
     """ethresh 1e-4: most groups fall below the layer's limit (their weight is zero, their frame moves all the same)."""
     P = problems(24, "eclipse", 1e-4)
-    same_bits(P, note="ethresh")
-    same_bits(P, env={"TRX_LANES_WALK": "0", "TRX_NO_PACKED_WALK": "1"}, scales=(1.0, 1.0), note="ethresh, k_line_walk")
+    runs_give_the_same_bits(P, note="ethresh")
+    runs_give_the_same_bits(P, env={"TRX_LANES_WALK": "0", "TRX_NO_PACKED_WALK": "1"}, scales=(1.0, 1.0), note="ethresh, k_line_walk")
 
 
 @pytest.mark.parametrize("lo,hi", [(3, 20), (13, 811), (795, 1600), (1589, 1599)])
@@ -184,7 +183,7 @@ def test_ragged_shards(problems, lo, hi):
     P = problems(24, "eclipse")
     P.set_shard(lo, hi)
     try:
-        same_bits(P, scales=(1.0, 1.0), note=(lo, hi))
-        same_bits(P, env={"TRX_LANES_WALK": "0", "TRX_NO_PACKED_WALK": "1"}, scales=(1.0,), note=(lo, hi, "k_line_walk"))
+        runs_give_the_same_bits(P, scales=(1.0, 1.0), note=(lo, hi))
+        runs_give_the_same_bits(P, env={"TRX_LANES_WALK": "0", "TRX_NO_PACKED_WALK": "1"}, scales=(1.0,), note=(lo, hi, "k_line_walk"))
     finally:
         P.set_shard(0, P.nwn)

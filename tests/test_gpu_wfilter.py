@@ -1,7 +1,7 @@
 """The weighted detrending filter on the device (trx_set_weighted_filter / trx_batch_set_weighted_filter and the filtered
 runs behind it, include/transit_hip.h) against transit_amd.xcor's mirror of the same definition, BIT FOR BIT.
 
-The case is test_gpu_filtered_map's: tp.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid
+The case is xcor_checks': pixel_cases.make("eclipse", 20 000 lines, 6001 bins), the 800 pixels with their two off-grid
 ones (b = 0 at every exposure), 7 exposures, the segments [1, 63, 64, 65, 200, 0, 7, 400] -- a tile of one lane, 64 + 1, an
 empty segment, ordinary ones -- and ncomp 1, 3, 5 and 9: the kernels' paddings 4, 8 and 16.  The weights are
 wfilter_cases.edge_weights: a column masked at every exposure (MASKED), one with exactly ncomp - 1 positive weights (SHORT,
@@ -10,27 +10,24 @@ components and 7 exposures every column is singular: the <16> kernels are held o
 exposures.  Before any device call every test asserts wfilter_cases.decisive on the host: no pivot of the case lies between
 2^-40 and 2^-12 of its diagonal entry, so that no live/dead decision hinges on a pivot's last bits.
 
-Values and flags are compared in bits.  The moments follow test_gpu_filter's rule over the values the device returned;
-the map follows test_gpu_filtered_map's contract, xcor.cell_value of the moments within xcor.cell_bound."""
+Values and flags are compared in bits.  The moments follow xcor_checks.check_filtered_moments' rule over the values the device returned;
+the map follows xcor_checks.check_contract, xcor.cell_value of the moments within xcor.cell_bound."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import test_gpu_filter as tf
-import test_gpu_filtered_map as tfm
-import test_gpu_moments as tm
-import test_gpu_pixels as tp
-import test_gpu_velocity_map as tv
+import pixel_cases as pc
 import wfilter_cases as wc
-from test_gpu_batch import atmospheres
+import xcor_checks as xc
+from bits import same_bits
 from transit_amd import exposures, xcor
 from transit_amd.engine import Batch, Engine, EngineError
 
 pytestmark = pytest.mark.gpu
 
-SHIFTS = tp.SHIFTS
-LAGS = tfm.LAGS
+SHIFTS = pc.SHIFTS
+LAGS = xc.LAGS
 MASKED, SHORT, EXACT = 200, 210, 220             # edge columns, in the segment of 200 pixels
 NCOMPS = (1, 3, 5, 9)
 EPS = 2.0 ** -52
@@ -45,7 +42,7 @@ class Case:
         """(observed set, weighted filter, the mirror's live flags) for ncomp components, made once; the precondition
         is asserted here, on the host, before anything of it reaches the device"""
         if (ncomp, nexp) not in self.sets:
-            base = tm.observed(len(self.px), self.scale, nexp=nexp)
+            base = xc.observed(len(self.px), self.scale, nexp=nexp)
             ob = xcor.Observed(base.seg_first, base.data, wc.edge_weights(nexp, len(self.px), ncomp, MASKED, SHORT, EXACT, seed=0), base.gain)
             wf = xcor.WeightedFilter(wc.random_basis(ob.nseg, nexp, ncomp, seed=50))
             self.sets[(ncomp, nexp)] = (ob, wf, wc.decisive(ob, wf))
@@ -63,45 +60,23 @@ class Case:
 
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    P = tp.make(tmp_path_factory.mktemp("wfilter"), "eclipse", nlines=20_000)
-    px = tm.pixel_set(P)
+    P = pc.make(tmp_path_factory.mktemp("wfilter"), "eclipse", nlines=20_000)
+    px = xc.pixel_set(P)
     E = Engine(P.static)
     scale = float(np.mean(E.run(P.atm, P.opts)["spectrum"]))
     E.set_pixels(px)
     pairs = E.run_pixels(P.atm, P.opts, SHIFTS)
     E.close()
     assert pairs.shape == (7, 800, 2)
-    for p in tm.OFF_GRID:
+    for p in xc.OFF_GRID:
         assert np.all(pairs[:, p, 1] == 0)
     return Case(P, px, scale, pairs)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)])
-
-
-def check_moments(mom, val, ob, what=""):
-    """tf.check_moments' rule -- the count exactly, every other moment within (n_max + 16) * 2^-52 of the sum of its absolute
-    terms over the values the device returned -- as an inequality, for rows whose sums of absolute terms are exact zeros
-    (behind a high-pass the one pixel of a segment of one is g - g = 0) and for sets whose rows are all empty (9 components
-    of 7 exposures: every column is dead)"""
-    ref, scale = xcor.reference_values(val, ob), xcor.abs_reference_values(val, ob)
-    assert mom.shape == ref.shape == (ob.nexp, ob.nseg, 7)
-    assert np.array_equal(mom[..., 0], ref[..., 0]), what
-    tol = (int(np.max(np.diff(ob.seg_first))) + 16) * EPS
-    empty = ref[..., 0] == 0
-    assert np.all(mom[empty] == 0) and not np.any(np.signbit(mom[empty])), what
-    assert np.all(np.abs(mom - ref) <= tol * scale), what
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(scale > 0, np.abs(mom - ref) / scale, 0.0)
-    print("%s: worst |mom - ref| / abs_ref %.2f * 2^-52 (tolerance %.0f * 2^-52)" % (what, float(ratio.max()) / EPS, tol / EPS))
 
 
 def check_edges(val, ob, live, ncomp):
     """the NaN pattern: the pivot rule's dead columns and the off-grid pixels, nothing else"""
     dead = ~live
-    dead[list(tm.OFF_GRID)] = True
+    dead[list(xc.OFF_GRID)] = True
     assert np.array_equal(np.isnan(val).any(axis=0), dead) and np.isnan(val[:, dead]).all()
     assert not live[MASKED] and not live[SHORT] and bool(live[EXACT]) == (ncomp <= ob.nexp)
     assert np.count_nonzero(ob.weight[:, SHORT] > 0) == (ncomp - 1 if ncomp - 1 <= ob.nexp else 0)
@@ -123,7 +98,7 @@ def test_values_flags_and_moments_are_the_mirrors(case, ncomp):
     ref = xcor.weighted_filter_reference(case.pairs, ob, wf)
     assert same_bits(val, ref), "ncomp %d" % ncomp
     check_edges(val, ob, live, ncomp)
-    check_moments(mom, val, ob, "weighted, ncomp %d" % ncomp)
+    xc.check_weighted_moments(mom, val, ob, "weighted, ncomp %d" % ncomp)
     assert np.array_equal(E.run_filtered_moments(P.atm, P.opts, SHIFTS), mom)
     # behind an exposure table and a high-pass: the mirror over their pairs
     ex = exposures.Exposures(np.array([1.0, 0.5, 2.0, -0.25, 1.0, 3.0, 1e-3]), np.array([0.0, 2e-9, 1e-6, 3e-6, 1.3e-5, 0.0, 1e-5]))
@@ -136,7 +111,7 @@ def test_values_flags_and_moments_are_the_mirrors(case, ncomp):
     gain_free = xcor.Observed(ob.seg_first, ob.data, ob.weight, None)
     mom2, val2 = E.run_filtered_moments(P.atm, P.opts, SHIFTS, values=True)
     assert same_bits(val2, xcor.weighted_filter_reference(xcor.highpass_pairs(hval), gain_free, wf)), "ncomp %d, exposed and high-passed" % ncomp
-    check_moments(mom2, val2, ob, "weighted behind the exposure table and the high-pass, ncomp %d" % ncomp)
+    xc.check_weighted_moments(mom2, val2, ob, "weighted behind the exposure table and the high-pass, ncomp %d" % ncomp)
     if ncomp <= 7:
         assert not np.array_equal(mom2, mom)
     E.set_exposures(None)
@@ -159,13 +134,13 @@ def test_nine_components_of_twelve_exposures_are_live(case):
     mom, val = E.run_filtered_moments(P.atm, P.opts, shifts, values=True)
     assert same_bits(val, xcor.weighted_filter_reference(pairs, ob, wf))
     check_edges(val, ob, live, 9)
-    check_moments(mom, val, ob, "weighted, 9 components of 12 exposures")
+    xc.check_weighted_moments(mom, val, ob, "weighted, 9 components of 12 exposures")
     E.close()
 
 
 def test_a_masked_entry_matters_and_equal_weights_are_the_plain_filter(case):
     P = case.P
-    base = tm.observed(len(case.px), case.scale)
+    base = xc.observed(len(case.px), case.scale)
     seg = base.seg_first
     w = np.ones_like(base.data)
     w[:, seg[4]:seg[5]] = 0.75                           # a segment whose weights are all equal, and not 1
@@ -187,7 +162,7 @@ def test_a_masked_entry_matters_and_equal_weights_are_the_plain_filter(case):
     assert same_bits(weighted, xcor.weighted_filter_reference(case.pairs, ob, wf))
     tol = xcor.weighted_filter_bound(case.pairs, ob, wf) + (ob.nexp + F.ncomp + 8) * EPS * xcor.filter_abs_reference(case.pairs, ob, F)
     same = np.ones(ob.npix, dtype=bool)
-    same[[0, col] + list(tm.OFF_GRID)] = False
+    same[[0, col] + list(xc.OFF_GRID)] = False
     diff = np.abs(weighted - plain)
     assert np.all(diff[:, same] <= tol[:, same])
     print("equal weights: worst |weighted - plain| / (sum of the two bounds) %.4f" % float(np.max(diff[:, same] / tol[:, same])))
@@ -208,12 +183,12 @@ def test_filtered_map_cells_are_the_filtered_moments(case, ncomp):
             moms[key] = E.run_filtered_moments(P.atm, P.opts, LAGS[idx])
         return moms[key]
 
-    for stat in tv.STATS:
-        vm = tfm.the_map(stat, offset=True)
+    for stat in xc.STATS:
+        vm = xc.the_filtered_map(stat, offset=True)
         m, idx = E.run_filtered_map(P.atm, P.opts, vm, lag_index=True)
-        assert np.array_equal(idx, xcor.nearest_lags(vm)) and np.array_equal(np.isnan(m), tfm.OUTSIDE)
+        assert np.array_equal(idx, xcor.nearest_lags(vm)) and np.array_equal(np.isnan(m), xc.OUTSIDE)
         differ = 0
-        for i, j in np.argwhere(~tfm.OUTSIDE):
+        for i, j in np.argwhere(~xc.OUTSIDE):
             mom = moments(idx[i, j])
             want, bound = xcor.cell_value(mom, vm), xcor.cell_bound(mom, vm)
             if ncomp <= 7:
@@ -224,22 +199,22 @@ def test_filtered_map_cells_are_the_filtered_moments(case, ncomp):
         print("ncomp %d, %s: %d of 28 cells differ in bits from cell_value(run_filtered_moments)" % (ncomp, stat, differ))
         # a cell's bits do not depend on its chunk or its place there: one cell alone, and the axes reversed
         for i, j in ((2, 3), (0, 0)):
-            one = E.run_filtered_map(P.atm, P.opts, tfm.the_map(stat, offset=True, kp=tv.KP[i:i + 1], vsys=tv.VSYS[j:j + 1]))
+            one = E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map(stat, offset=True, kp=xc.KP[i:i + 1], vsys=xc.VSYS[j:j + 1]))
             assert one.shape == (1, 1) and same_bits(one[0, 0], m[i, j]), (stat, i, j)
     if ncomp == 3:
         # the definition in numpy, moments by fsum: on the pairs of the lags, to the cell bound and the moments' rule
-        vm = tfm.the_map("chi2", offset=True)
+        vm = xc.the_filtered_map("chi2", offset=True)
         lag_pairs = E.run_pixels(P.atm, P.opts, LAGS)
         m, idx = E.run_filtered_map(P.atm, P.opts, vm, lag_index=True)
         i, j = 2, 3
         val = xcor.weighted_filter_reference(lag_pairs[idx[i, j]], ob, wf)
-        check_moments(moments(idx[i, j]), val, ob, "the cell (2, 3): moments of the mirror's values")
+        xc.check_weighted_moments(moments(idx[i, j]), val, ob, "the cell (2, 3): moments of the mirror's values")
         # 143 cells: three chunks with a ragged last one; reversed, every cell sits in another chunk
-        vm2 = tfm.the_map("ccf", second=True)
+        vm2 = xc.the_filtered_map("ccf", second=True)
         m2 = E.run_filtered_map(P.atm, P.opts, vm2)
-        rev2 = E.run_filtered_map(P.atm, P.opts, tfm.the_map("ccf", second=True, kp=tfm.KP2[::-1], vsys=tfm.VSYS2[::-1]))
-        assert m2.size > 2 * tfm.CHUNK and m2.size % tfm.CHUNK != 0
-        assert same_bits(rev2[::-1, ::-1], m2) and np.count_nonzero(np.isfinite(m2)) > tfm.CHUNK
+        rev2 = E.run_filtered_map(P.atm, P.opts, xc.the_filtered_map("ccf", second=True, kp=xc.FMAP_KP2[::-1], vsys=xc.FMAP_VSYS2[::-1]))
+        assert m2.size > 2 * xc.CHUNK and m2.size % xc.CHUNK != 0
+        assert same_bits(rev2[::-1, ::-1], m2) and np.count_nonzero(np.isfinite(m2)) > xc.CHUNK
     E.close()
 
 
@@ -247,9 +222,9 @@ def test_batch_moments_and_maps_are_the_single_handles(case):
     P = case.P
     ob, wf, live = case.the_set(5)
     K = 3
-    atms, keep = atmospheres(P, K)
+    atms, keep = pc.atmospheres(P, K)
     shifts = np.stack([np.roll(SHIFTS, j) * (1.0 + 1e-6 * j) for j in range(K)])
-    vm = tfm.the_map("loglike_bl19", offset=True)
+    vm = xc.the_filtered_map("loglike_bl19", offset=True)
     E = case.handle(5)
     ref = np.stack([E.run_filtered_moments(atms[j], P.opts, shifts[j]) for j in range(K)])
     maps = np.stack([E.run_filtered_map(atms[j], P.opts, vm) for j in range(K)])
@@ -284,7 +259,7 @@ def test_batch_moments_and_maps_are_the_single_handles(case):
 def test_lifetimes_and_refusals(case):
     P = case.P
     ob, wf, live = case.the_set(3)
-    F = tf.random_filter(ob.nseg, 3, ob.nexp, seed=1)
+    F = xc.random_filter(ob.nseg, 3, ob.nexp, seed=1)
     E = Engine(P.static)
     lib = E._lib
 
@@ -350,14 +325,14 @@ def test_lifetimes_and_refusals(case):
     unchanged("without nsingular")
     # a refused plain filter leaves the weighted one in force too
     with pytest.raises(EngineError):
-        E.set_filter(tf.random_filter(ob.nseg, 17, ob.nexp, seed=2))
+        E.set_filter(xc.random_filter(ob.nseg, 17, ob.nexp, seed=2))
     unchanged("a refused plain filter")
     # and a refused weighted filter leaves a plain one in force
     E.set_filter(F)
     assert "segment 1" in refusal(changed((1, 0, 2), np.nan))
     assert np.array_equal(E.run_filtered_moments(P.atm, P.opts, SHIFTS), plain[0])
     # cleared, by None and by ncomp = 0; dropped by set_observed and by set_pixels
-    vm = tfm.the_map("ccf", offset=True)
+    vm = xc.the_filtered_map("ccf", offset=True)
     for clear in ("none", "ncomp 0", "set_observed", "set_pixels"):
         assert E.set_weighted_filter(wf) == nsing
         if clear == "none":
@@ -392,8 +367,8 @@ def test_no_leak_into_other_runs(case):
     new calls -- with a weighted filter installed, run and cleared on them in between, and one installed elsewhere"""
     P = case.P
     ob, wf, live = case.the_set(5)
-    F = tf.random_filter(ob.nseg, 5, ob.nexp, seed=3)
-    vm = tfm.the_map("ccf", offset=True)
+    F = xc.random_filter(ob.nseg, 5, ob.nexp, seed=3)
+    vm = xc.the_filtered_map("ccf", offset=True)
     elsewhere = case.handle(5)
     elsewhere.run_filtered_moments(P.atm, P.opts, SHIFTS)
 

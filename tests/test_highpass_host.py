@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 from transit_amd import xcor
@@ -58,11 +59,6 @@ def program_values(check_exe, tmp_path, pairs, ob, hp, name):
     assert out.returncode == 0 and out.stderr == "", out.stdout[-3000:] + out.stderr[-4000:]
     assert "0 differ from the literal definition" in out.stdout
     return np.fromfile(dst, dtype=np.float64).reshape(pairs.shape[0], ob.npix)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and \
-        np.array_equal(np.where(np.isnan(a), 0.0, a).view(np.uint64), np.where(np.isnan(b), 0.0, b).view(np.uint64))
 
 
 @pytest.mark.parametrize("half", [0, 1, 5, 70])

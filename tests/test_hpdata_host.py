@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 import hpdata_cases as hc
@@ -21,7 +22,6 @@ import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-same_bits = hc.same_bits
 SETS = [(nexp, weighted, stage, seg) for nexp in (7, 12) for weighted in (False, True) for stage in hc.STAGES for seg in hc.SEGS]
 
 

@@ -3,18 +3,15 @@ tests/libtransit_driver.c: the symbols it exports, the header, the prototypes ag
 reference's, and what it does when it cannot initialise."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from cases import GOLDEN
+from host_check import INCLUDE, build_driver, copy_case, probes, run_driver
 from transit_amd import build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-DRIVER = os.path.join(ROOT, "tests", "libtransit_driver.c")
 # where oracle/Makefile finds the reference's sources (its REF)
 REF_TRANSIT_C = os.path.join(os.environ.get("REF", "/root/reference"), "transit", "src", "transit.c")
 
@@ -22,40 +19,6 @@ API = ["transit_init", "get_no_samples", "get_waveno_arr", "set_radius", "set_cl
        "run_transit", "free_memory"]
 EXTRA = ["transit_status", "transit_error"]
 TRX_E_NODEVICE = -4
-
-
-def build_driver(directory) -> str:
-    """The test driver, compiled against the header and linked with -ltransit alone."""
-    lib = build.build_lib()
-    exe = os.path.join(str(directory), "libtransit_driver")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", INCLUDE, DRIVER, "-o", exe,
-                    "-L", os.path.dirname(lib), "-ltransit", "-Wl,-rpath," + os.path.dirname(lib)],
-                   check=True, capture_output=True, text=True, timeout=120)
-    return exe
-
-
-def run_driver(exe, work, script, timeout=600):
-    """Runs the driver on `script` (text) in `work`; run k's out goes to work/drv_out<k>.dat."""
-    with open(os.path.join(str(work), "script.txt"), "w") as f:
-        f.write(script)
-    return subprocess.run([exe, "script.txt", "drv_out"], cwd=str(work), capture_output=True, text=True,
-                          timeout=timeout)
-
-
-def copy_case(tmp_path, case, name=None):
-    work = tmp_path / (name or case)
-    shutil.copytree(os.path.join(GOLDEN, case), work)
-    return work
-
-
-def probes(stdout):
-    """The driver's probe lines: (status, samples, wn[3], out0)."""
-    out = []
-    for ln in stdout.splitlines():
-        w = ln.split()
-        if w and w[0] == "probe":
-            out.append((int(w[2]), int(w[4]), [float(x) for x in w[6:9]], float(w[10])))
-    return out
 
 
 def test_library_exports_exactly_the_ten_functions():

@@ -13,6 +13,7 @@ import many_cases as mc
 import scatter_cases as cs
 import sysrem_cases as sc
 import wfilter_cases as wc
+from bits import same_bits
 from transit_amd import xcor
 
 EXPOSURES = [("exp", n) for n in mc.NEXPS]
@@ -147,10 +148,10 @@ def test_a_random_basis_leaves_columns_live(kind, n, ncomp):
 def test_data_set_without_a_trends_factor_is_sysrem_cases_bit_for_bit():
     """long_set scales data_set's trends; at the default factor of 1 the other sets keep sysrem_cases.data_set's bits"""
     for nexp, seed in ((5, 3), (12, 52), (65, 165)):
-        assert mc.same_bits(mc.data_set(nexp, sc.NPIX, seed), sc.data_set(nexp, seed))
-        assert mc.same_bits(mc.data_set(nexp, sc.NPIX, seed, noise=0.0, nterms=2), sc.data_set(nexp, seed, noise=0.0, nterms=2))
-    assert not mc.same_bits(mc.data_set(12, sc.NPIX, 52, trends=mc.LONG_TRENDS), sc.data_set(12, 52))
-    assert mc.same_bits(mc.exposures_set(64).data, sc.data_set(64, 164))
+        assert same_bits(mc.data_set(nexp, sc.NPIX, seed), sc.data_set(nexp, seed))
+        assert same_bits(mc.data_set(nexp, sc.NPIX, seed, noise=0.0, nterms=2), sc.data_set(nexp, seed, noise=0.0, nterms=2))
+    assert not same_bits(mc.data_set(12, sc.NPIX, 52, trends=mc.LONG_TRENDS), sc.data_set(12, 52))
+    assert same_bits(mc.exposures_set(64).data, sc.data_set(64, 164))
 
 
 # ---- the long orders -------------------------------------------------------------------------------------------------
@@ -205,9 +206,9 @@ def test_the_long_sets_ties_straddle_the_median_rank_across_staging_trips(weight
         order = [int(p) for p in mc.ranked(var, seg, s)]
         m = len(order)
         r = (m - 1) // 2
-        assert a != b and mc.same_bits(ms.data[:, a], ms.data[:, b]) and mc.same_bits(ms.weight[:, a], ms.weight[:, b])
-        assert mc.same_bits(var[a], var[b]) and var[a] > 0 and np.count_nonzero(var[ms.segment(s)] == var[a]) == 2
-        assert order[r:r + 2] == sorted((a, b)) and mc.same_bits(med[s], var[a])     # the ranks r and r + 1, the lower pixel first
+        assert a != b and same_bits(ms.data[:, a], ms.data[:, b]) and same_bits(ms.weight[:, a], ms.weight[:, b])
+        assert same_bits(var[a], var[b]) and var[a] > 0 and np.count_nonzero(var[ms.segment(s)] == var[a]) == 2
+        assert order[r:r + 2] == sorted((a, b)) and same_bits(med[s], var[a])     # the ranks r and r + 1, the lower pixel first
         assert mc.trip_of(seg, s, a) != mc.trip_of(seg, s, b)
         after.append(b > a)
         if not weighted:

@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 import many_cases as mc
@@ -21,7 +22,6 @@ import sysrem_cases as sc
 from transit_amd import _abi, build, xcor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-same_bits = nc.same_bits
 
 
 @pytest.fixture(scope="module")

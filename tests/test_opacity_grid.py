@@ -14,17 +14,6 @@ from transit_amd.host import Problem
 CASE = os.path.join(GOLDEN, "opacity_grid")
 
 
-def read_grid(path):
-    with open(path, "rb") as f:
-        nmol, ntemp, nlayer, nwave = np.fromfile(f, dtype=np.int64, count=4)
-        ids = np.fromfile(f, dtype=np.int32, count=nmol)
-        temp = np.fromfile(f, dtype=np.float64, count=ntemp)
-        press = np.fromfile(f, dtype=np.float64, count=nlayer)
-        wns = np.fromfile(f, dtype=np.float64, count=nwave)
-        o = np.fromfile(f, dtype=np.float64).reshape(nlayer, ntemp, nmol, nwave)
-    return ids, temp, press, wns, o
-
-
 def workdir(tmp_path, with_file):
     d = tmp_path / "og"
     shutil.copytree(CASE, d)
@@ -33,7 +22,7 @@ def workdir(tmp_path, with_file):
     return str(d)
 
 
-REF = read_grid(os.path.join(CASE, "opacity_ref.dat"))
+REF = ol.read_grid(os.path.join(CASE, "opacity_ref.dat"))
 REF_SPEC = ol.read_spectrum(os.path.join(CASE, "spectrum.dat"))[:, 1]
 
 
@@ -44,7 +33,7 @@ def check_build(engine_cls, d, tol):
     o = eng.build_opacity_grid(P)
     eng.close()
     assert not P.needs_opacity_build and P.static.ogrid
-    ids, temp, press, wns, og = read_grid(os.path.join(d, "opac.dat"))
+    ids, temp, press, wns, og = ol.read_grid(os.path.join(d, "opac.dat"))
     rids, rtemp, rpress, rwns, rog = REF
     assert np.array_equal(ids, rids) and np.array_equal(temp, rtemp) and np.array_equal(wns, rwns)
     assert rel_err(press, rpress) < 1e-14

@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from cases import GOLDEN, golden, rel_err
+from cases import GOLDEN, check_savefiles, golden, rel_err
 from transit_amd import _abi, build
 from transit_amd.host import HostError, Problem, option_table
 
@@ -278,27 +278,6 @@ def test_detail_writer_on_the_reference_dumps(workdir):
         got, ref = open(d / "detail_cia.dat").read().split("\n"), open(os.path.join(GOLDEN, case, "detail_cia.dat")).read().split("\n")
         assert got[0] == ref[0] and len(got) == len(ref)
         assert [l.split()[0] for l in got[1:] if l] == [l.split()[0] for l in ref[1:] if l]
-
-
-SAVEFILES = (("tau.dat", "wavenumber"), ("CIA.dat", "wavenumber"), ("mol_extion.dat", "radius"),
-             ("total_extion.dat", "wavenumber"), ("cloud_extion.dat", "wavenumber"), ("scatt_extion.dat", "wavenumber"))
-
-
-def check_savefiles(got_dir, case, tol):
-    """The six dumps of `savefiles yes` against the reference's own: same text skeleton (header,
-    row keys, line count), same zeros (layers the reference's lazy sweep never reached; heights
-    past the toomuch cut), values to `tol`."""
-    import oracle_lib as ol
-    for name, key in SAVEFILES:
-        ref_path = os.path.join(GOLDEN, case, name)
-        got_lines, ref_lines = open(os.path.join(got_dir, name)).read().split("\n"), open(ref_path).read().split("\n")
-        assert got_lines[:4] == ref_lines[:4], name
-        assert len(got_lines) == len(ref_lines), name
-        gk, gv = ol.read_rows_dump(os.path.join(got_dir, name), key)
-        rk, rv = ol.read_rows_dump(ref_path, key)
-        assert np.array_equal(gk, rk), name
-        assert np.array_equal(gv == 0, rv == 0), name
-        assert rel_err(gv, rv) < tol, name
 
 
 @pytest.mark.parametrize("case", ["qscale_eclipse", "dumps_transit", "cloud_opa", "cloud_b17", "cloud_f18", "cloud_p19"])

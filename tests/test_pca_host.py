@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 import many_cases as mc
@@ -80,11 +81,11 @@ def run_program(check_exe, path, nexp, ncomp, nsweep, seg, data, w):
 
 def same_as_mirror(got, want):
     basis, coef, resid, eigen, offdiag, nwhole = want
-    assert sc.same_bits(got["U"].reshape(basis.shape), basis)
-    assert sc.same_bits(got["coef"].reshape(coef.shape), coef)
-    assert sc.same_bits(got["r"].reshape(resid.shape), resid)
-    assert sc.same_bits(got["eigen"].reshape(eigen.shape), eigen)
-    assert sc.same_bits(got["offdiag"], offdiag)
+    assert same_bits(got["U"].reshape(basis.shape), basis)
+    assert same_bits(got["coef"].reshape(coef.shape), coef)
+    assert same_bits(got["r"].reshape(resid.shape), resid)
+    assert same_bits(got["eigen"].reshape(eigen.shape), eigen)
+    assert same_bits(got["offdiag"], offdiag)
     assert np.array_equal(got["nwhole"], nwhole)
 
 
@@ -156,7 +157,7 @@ def test_weights_none_are_weights_one(nexp, ncomp, nsweep):
     data, _, got = mirror(nexp, False, ncomp, nsweep)
     ones = xcor.pca_reference(data, np.ones_like(data), sc.SEG, ncomp, nsweep)
     for a, b in zip(got, ones):
-        assert sc.same_bits(a, b)
+        assert same_bits(a, b)
 
 
 def prototype_set(nexp=7, seed=2, noise=1e-3, fall=0.3, npix=sc.NPIX):

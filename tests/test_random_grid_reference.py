@@ -17,11 +17,10 @@ import pytest
 import oracle_lib as ol
 import random_cases
 from cases import rel_err
-from test_opacity_grid import read_grid
+from tolerances import DEBUG_KEYS, assert_tau_close
 from transit_amd import synth
 from transit_amd.engine import EngineError
 from transit_amd.host import Problem
-from tolerances import DEBUG_KEYS, assert_tau_close
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
@@ -47,8 +46,8 @@ def test_oracle_grid_against_the_reference_binary(tmp_path, seed):
         o = ora.build_opacity_grid(P)
     finally:
         ora.close()
-    ids, temp, press, wns, og = read_grid(os.path.join(d, "opac.dat"))
-    rids, rtemp, rpress, rwns, rog = read_grid(os.path.join(d, "opac_ref.dat"))
+    ids, temp, press, wns, og = ol.read_grid(os.path.join(d, "opac.dat"))
+    rids, rtemp, rpress, rwns, rog = ol.read_grid(os.path.join(d, "opac_ref.dat"))
     e = kw["extra"]
     assert np.array_equal(temp, np.arange(e["tlow"], e["thigh"] + 0.5, e["tempdelt"], dtype=float)), note
     assert np.array_equal(ids, rids) and np.array_equal(temp, rtemp) and np.array_equal(wns, rwns), note

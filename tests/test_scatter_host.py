@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 import many_cases as mc
@@ -19,7 +20,6 @@ import scatter_cases as cs
 from transit_amd import _abi, build, xcor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-same_bits = cs.same_bits
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 import many_cases as mc
@@ -60,9 +61,9 @@ def program_is_the_mirror(check_exe, path, data, w, seg, ncomp, niter, want):
     lines = {w_[0]: w_[1:] for w_ in (line.split() for line in out.stdout.splitlines())}
     assert "FAILED" not in lines
     got = {k: np.array([float.fromhex(x) for x in lines[k]]) for k in ("U", "coef", "r")}
-    assert sc.same_bits(got["U"].reshape(basis.shape), basis)
-    assert sc.same_bits(got["coef"].reshape(coef.shape), coef)
-    assert sc.same_bits(got["r"].reshape(resid.shape), resid)
+    assert same_bits(got["U"].reshape(basis.shape), basis)
+    assert same_bits(got["coef"].reshape(coef.shape), coef)
+    assert same_bits(got["r"].reshape(resid.shape), resid)
 
 
 @pytest.mark.parametrize("weighted", [False, True])
@@ -108,7 +109,7 @@ def test_weights_none_are_weights_one(nexp, ncomp, niter):
     data, _, got = mirror(nexp, False, ncomp, niter)
     ones = xcor.sysrem_reference(data, np.ones_like(data), sc.SEG, ncomp, niter)
     for a, b in zip(got, ones):
-        assert sc.same_bits(a, b)
+        assert same_bits(a, b)
 
 
 @pytest.mark.parametrize("weighted", [False, True])
@@ -196,15 +197,15 @@ def test_injection_fixed_points():
     pairs[4, :5, 1] = 0.0
     out = xcor.inject_reference(pairs, obs, 1e-2, 1.0)
     dead = pairs[..., 1] <= 0
-    assert dead.sum() == 7 and sc.same_bits(out[dead], F[dead])
+    assert dead.sum() == 7 and same_bits(out[dead], F[dead])
     assert np.all(out[~dead] != F[~dead])
     # p0 = 0, p1 = 1: m = 0 g + 1 = 1, F * 1 = F
-    assert sc.same_bits(xcor.inject_reference(pairs, obs, 0.0, 1.0), F)
+    assert same_bits(xcor.inject_reference(pairs, obs, 0.0, 1.0), F)
     # the operations, one at a time
     g = obs.gain[None, :] * (pairs[..., 0] / np.where(dead, 1.0, pairs[..., 1]))
     m = 1e-2 * g
     m = m + 1.0
-    assert sc.same_bits(out[~dead], (F * m)[~dead])
+    assert same_bits(out[~dead], (F * m)[~dead])
 
 
 def test_abi_struct_constant_symbol_and_kernels():

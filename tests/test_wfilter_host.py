@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import same_bits
 from host_check import build_check
 
 import wfilter_cases as wc
@@ -45,11 +46,6 @@ def the_set(nexp, ncomp, seed):
     obs = xcor.Observed(xcor.segments(LENGTHS), rng.standard_normal((nexp, npix)), w)
     wf = xcor.WeightedFilter(wc.random_basis(obs.nseg, nexp, ncomp, seed + 2))
     return obs, wf, np.stack([g, np.ones_like(g)], axis=-1)
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)]) and np.array_equal(np.isnan(a), np.isnan(b))
 
 
 @pytest.mark.parametrize("nexp,ncomp", [(7, 1), (7, 3), (7, 5), (7, 9), (12, 4), (12, 8), (12, 9), (20, 16)])

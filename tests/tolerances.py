@@ -27,6 +27,11 @@ A difference that is large but NOT of this form -- at a height whose parabola is
 quanta wide -- fails.
 """
 import numpy as np
+import pytest
+
+import oracle_lib as ol
+from cases import rel_err
+from transit_amd.engine import EngineError
 
 STRICT = 1e-9      # the arithmetic's own tolerance (fp64, sums associated differently)
 NQ = 4.0           # rounding steps allowed per parabola value (3 cancelling terms, 2 results compared)
@@ -112,3 +117,60 @@ def assert_tau_close(problem, got, ref, note=None):
 
 
 DEBUG_KEYS = ("e", "e_cs", "tau", "last", "intens", "computed", "e_scat", "e_cloud")
+
+
+# ---- two runs of the device against each other: the same bits, wherever a run wrote ------------------------------
+KEYS = ("e", "e_cs", "tau", "last", "intens", "computed", "er", "e_scat", "e_cloud")
+
+
+def assert_same(ra, rb, note=None):
+    sw = ra["computed"].astype(bool) if "computed" in ra else slice(None)
+    assert set(ra) == set(rb), (sorted(ra), sorted(rb), note)
+    for k in ra:
+        if k in ("e", "e_cs", "e_scat", "e_cloud"):
+            assert np.array_equal(ra[k][sw], rb[k][sw]), (k, note)
+        elif k == "er":
+            # (edited extinction: written down to the ray's stopping height only)
+            nl = ra[k].shape[0]
+            used = (nl - 1 - np.arange(nl))[:, None] <= ra["last"][None, :]
+            assert np.array_equal(ra[k][used], rb[k][used]), (k, note)
+        elif k == "tau":
+            # heights a ray never reached hold whatever an earlier run left: compare what the ray used
+            last = ra["last"]
+            used = np.arange(ra[k].shape[1])[None, :] <= last[:, None]
+            assert np.array_equal(ra[k][used], rb[k][used]), (k, note)
+        else:
+            assert np.array_equal(ra[k], rb[k]), (k, note)
+
+
+# ---- a run of the device against the oracle ---------------------------------------------------------------------
+def oracle(P):
+    ora = ol.OracleEngine(P.static)
+    try:
+        return ora.run(P.atm, P.opts, debug=DEBUG_KEYS)
+    except EngineError as e:                     # e.g. fewer than three points for the modulation
+        return e
+    finally:
+        ora.close()
+
+
+def check_against_oracle(P, hip, ref, note):
+    """One run of the handle against the oracle's result for the same atmosphere; returns the run."""
+    if isinstance(ref, Exception):
+        with pytest.raises(EngineError) as ei:
+            hip.run(P.atm, P.opts, debug=True)
+        assert ei.value.code == ref.code, (note, ei.value.code, ref.code)
+        return None
+    got = hip.run(P.atm, P.opts, debug=True)
+    assert np.array_equal(got["last"], ref["last"]), (note, "last differs at", np.flatnonzero(got["last"] != ref["last"])[:4].tolist())
+    # optical depth: the arithmetic's 1e-9 plus the rounding steps of the reference's
+    # absolute-radius parabola where they apply (tests/tolerances.py) -- nothing else
+    noisy = assert_tau_close(P, got, ref, note)
+    # spectrum: 1e-8; rays whose optical depth carries parabola noise pass it on (in the
+    # modulation of a 3-4-layer atmosphere R^2 - 2*integral cancels on top of it)
+    assert rel_err(got["spectrum"][~noisy], ref["spectrum"][~noisy]) < 1e-8, (note, rel_err(got["spectrum"][~noisy], ref["spectrum"][~noisy]))
+    assert rel_err(got["spectrum"], ref["spectrum"]) < 1e-7, (note, rel_err(got["spectrum"], ref["spectrum"]))
+    sw = got["computed"].astype(bool) & ref["computed"].astype(bool)
+    assert rel_err(got["e"][sw], ref["e"][sw]) < 1e-9, (note, rel_err(got["e"][sw], ref["e"][sw]))
+    assert rel_err(got["e_cs"], ref["e_cs"]) < 1e-12, (note, rel_err(got["e_cs"], ref["e_cs"]))
+    return got
