@@ -26,23 +26,7 @@ def oracle_library():
         if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
             subprocess.check_call(["make", "-C", ORACLE_DIR, "oracle"], stdout=subprocess.DEVNULL)
         lib = C.CDLL(so)
-        _abi.bind_engine_api(lib, "trxo_")
-        lib.trxo_voigt_profile.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, _abi.c_float_p, C.c_int]
-        lib.trxo_voigt_profile.restype = C.c_int
-        lib.trxo_parab3.argtypes = [_abi.c_double_p, _abi.c_double_p, C.c_double]
-        lib.trxo_parab3.restype = C.c_double
-        lib.trxo_simpson.argtypes = [_abi.c_double_p, _abi.c_double_p, C.c_int]
-        lib.trxo_simpson.restype = C.c_double
-        lib.trxo_tau_slant.argtypes = [_abi.c_double_p, C.c_long, C.c_double, _abi.c_double_p]
-        lib.trxo_tau_slant.restype = C.c_double
-        lib.trxo_modulation.argtypes = [_abi.c_double_p, C.c_long, C.c_double, _abi.c_double_p, C.c_long, C.c_double, C.c_double, C.c_int]
-        lib.trxo_modulation.restype = C.c_double
-        lib.trxo_nearest.argtypes = [_abi.c_double_p, C.c_double, C.c_int, C.c_int]
-        lib.trxo_nearest.restype = C.c_int
-        lib.trxo_spline_init.argtypes = [_abi.c_double_p, _abi.c_double_p, _abi.c_double_p, C.c_long]
-        lib.trxo_spline_init.restype = None
-        lib.trxo_spline_eval.argtypes = [_abi.c_double_p, C.c_long, _abi.c_double_p, _abi.c_double_p, C.c_double]
-        lib.trxo_spline_eval.restype = C.c_double
+        _abi.bind(lib, os.path.join(ORACLE_DIR, "trx_oracle.h"), "trxo_")
         _lib = lib
     return _lib
 

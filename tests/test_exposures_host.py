@@ -181,5 +181,5 @@ def test_abi_struct_and_symbols():
     assert lib.trx_abi_version() == 5
     assert b"k_pixel_pairs_exposed" in open(path, "rb").read()
     # refused without a handle, before anything is touched
-    _abi.bind_exposures_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_set_exposures(None, None) == -1

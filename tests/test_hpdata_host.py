@@ -205,5 +205,5 @@ def test_abi_symbol_and_kernel():
     blob = open(path, "rb").read()
     assert b"k_data_highpass" in blob and b"k_pixel_highpass" in blob
     # refused without a handle, before anything is touched
-    _abi.bind_hpdata_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_highpass_observed(None, 1, None, None) == -1

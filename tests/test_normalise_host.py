@@ -243,6 +243,6 @@ def test_abi_struct_constants_symbols_and_kernels():
     for k in (b"k_norm_rowscale", b"k_norm_cols"):
         assert k in blob, k
     # refused without a handle, before anything is touched
-    _abi.bind_normalise_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_set_normalise(None, None) == -1
     assert lib.trx_normalise_observed(None, None, None, None, 0, None, 0, 0.0, 0.0, None, None, None, None, None, None) == -1

@@ -283,5 +283,5 @@ def test_abi_struct_constants_symbol_and_kernels():
     for k in (b"k_pca_live", b"k_pca_whole", b"k_pca_gram", b"k_pca_jacobi", b"k_pca_project"):
         assert k in blob, k
     # refused without a handle, before anything is touched
-    _abi.bind_pca_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_pca_observed(None, None, None, None, 0, None, None, None, None, None, None, None, None, None, None) == -1

@@ -97,7 +97,7 @@ def test_library_exports_and_refuses_without_a_handle():
     lib = C.CDLL(path)
     for name in ("trx_set_pixels", "trx_run_pixels", "trx_batch_set_pixels", "trx_run_batch_pixels"):
         assert hasattr(lib, name), name
-    _abi.bind_pixels_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     px = pixels.resolving_power([2510.0, 2520.0], 20000.0)
     assert lib.trx_set_pixels(None, C.byref(pixels.to_c(px))) == -1
     assert lib.trx_set_pixels(None, None) == -1

@@ -233,5 +233,5 @@ def test_abi_struct_constants_symbol_and_kernels():
     for nc in (4, 8, 16):
         assert b"k_regress_colsILi%dEE" % nc in blob, nc
     # refused without a handle, before anything is touched
-    _abi.bind_regress_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_regress_observed(None, None, None, None, 0, None, None, None, None, None, None, None, None) == -1

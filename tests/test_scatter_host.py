@@ -245,5 +245,5 @@ def test_abi_struct_constants_symbol_and_kernels():
     for k in (b"k_scatter_cols", b"k_scatter_median", b"k_scatter_weights"):
         assert k in blob, k
     # refused without a handle, before anything is touched
-    _abi.bind_scatter_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_weigh_observed(None, None, None, None, None, None, None) == -1

@@ -224,5 +224,5 @@ def test_abi_struct_constant_symbol_and_kernels():
     for k in (b"k_sysrem_inject", b"k_sysrem_cols", b"k_sysrem_rows", b"k_sysrem_close", b"k_sysrem_subtract"):
         assert k in blob, k
     # refused without a handle, before anything is touched
-    _abi.bind_sysrem_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_detrend_observed(None, None, None, None, 0, None, None, None, None, None, None, None) == -1

@@ -150,7 +150,7 @@ def test_header_prototypes_and_abi_signatures_agree():
     lib = C.CDLL(path)
     for name in ("trx_run_trail", "trx_run_batch_trail"):
         assert hasattr(lib, name), name
-    _abi.bind_trail_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert prototype("trx_run_moments") == list(lib.trx_run_trail.argtypes)      # (the parser, on a call bound before)
     for name in ("trx_run_trail", "trx_run_batch_trail"):
         f = getattr(lib, name)

@@ -197,6 +197,6 @@ def test_abi_struct_constant_and_symbols():
     for k in (b"k_wfilter_factor", b"k_pixel_wfilter", b"k_cell_wfilter"):
         assert k in blob, k
     # refused without a handle, before anything is touched
-    _abi.bind_filter_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     assert lib.trx_set_weighted_filter(None, None, None) == -1
     assert lib.trx_batch_set_weighted_filter(None, None) == -1

@@ -169,7 +169,7 @@ def test_library_exports_and_refuses_without_a_handle():
     lib = C.CDLL(path)
     for name in ("trx_set_filter", "trx_run_filtered_moments", "trx_batch_set_filter", "trx_run_batch_filtered_moments"):
         assert hasattr(lib, name), name
-    _abi.bind_filter_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     F = xcor.Filter(np.zeros((1, 1, 1)), np.zeros((1, 1, 1)))
     assert lib.trx_set_filter(None, C.byref(F.to_c())) == -1
     assert lib.trx_set_filter(None, None) == -1

@@ -161,7 +161,7 @@ def test_library_exports_and_refuses_without_a_handle():
     lib = C.CDLL(path)
     for name in ("trx_set_observed", "trx_run_moments", "trx_batch_set_observed", "trx_run_batch_moments"):
         assert hasattr(lib, name), name
-    _abi.bind_moments_api(lib)
+    _abi.bind(lib, _abi.HIP_HEADER, "trx_")
     ob = xcor.Observed([0, 2], [[1.0, 2.0]])
     assert lib.trx_set_observed(None, C.byref(ob.to_c())) == -1
     assert lib.trx_set_observed(None, None) == -1

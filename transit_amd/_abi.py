@@ -2,6 +2,10 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
+import re
+
+from .build import ROOT
 
 ABI_VERSION = 5
 
@@ -197,248 +201,78 @@ class TrxStats(C.Structure):
                 for name, _ in self._fields_}
 
 
-def bind_engine_api(lib, prefix: str = "trx_"):
-    """Declare argtypes/restypes of the create/run/destroy family on *lib*.
-    The same struct layouts serve any library exporting this ABI shape."""
-    f = lambda n: getattr(lib, prefix + n)
-    f("create").argtypes = [C.POINTER(TrxStatic), C.POINTER(C.c_void_p)]
-    f("create").restype = C.c_int
-    f("run").argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p,
-                         C.POINTER(TrxDebug)]
-    f("run").restype = C.c_int
-    f("destroy").argtypes = [C.c_void_p]
-    f("destroy").restype = None
-    f("get_stats").argtypes = [C.c_void_p, C.POINTER(TrxStats)]
-    f("get_stats").restype = C.c_int
-    f("table_info").argtypes = [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]
-    f("table_info").restype = C.c_int
-    f("table_copy").argtypes = [C.c_void_p, c_float_p]
-    f("table_copy").restype = C.c_int
-    f("width_grids").argtypes = [C.c_void_p, c_double_p, c_double_p]
-    f("width_grids").restype = C.c_int
-    f("sweep_permol").argtypes = [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, C.c_double,
-                                  C.c_int32, c_int32_p, c_double_p]
-    f("sweep_permol").restype = C.c_int
-    return lib
-
-
-def bind_bands_api(lib):
-    """argtypes/restypes of the band entry points (trx_set_bands, trx_run_bands and their batch forms)."""
-    lib.trx_set_bands.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxBand)]
-    lib.trx_set_bands.restype = C.c_int
-    lib.trx_run_bands.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, c_double_p,
-                                  C.POINTER(TrxDebug)]
-    lib.trx_run_bands.restype = C.c_int
-    lib.trx_batch_set_bands.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxBand)]
-    lib.trx_batch_set_bands.restype = C.c_int
-    lib.trx_run_batch_bands.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
-                                        C.POINTER(c_double_p)]
-    lib.trx_run_batch_bands.restype = C.c_int
-    return lib
-
-
-def bind_contrib_api(lib):
-    """argtypes/restypes of the contribution-function entry points (trx_run_contrib, trx_run_batch_contrib)."""
-    lib.trx_run_contrib.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, c_double_p,
-                                    c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_contrib.restype = C.c_int
-    lib.trx_run_batch_contrib.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
-                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_contrib.restype = C.c_int
-    return lib
-
-
-def bind_pixels_api(lib):
-    """argtypes/restypes of the detector-pixel entry points (trx_set_pixels, trx_run_pixels and their batch forms)."""
-    lib.trx_set_pixels.argtypes = [C.c_void_p, C.POINTER(TrxPixels)]
-    lib.trx_set_pixels.restype = C.c_int
-    lib.trx_run_pixels.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                   c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_pixels.restype = C.c_int
-    lib.trx_batch_set_pixels.argtypes = [C.c_void_p, C.POINTER(TrxPixels)]
-    lib.trx_batch_set_pixels.restype = C.c_int
-    lib.trx_run_batch_pixels.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
-                                         C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_pixels.restype = C.c_int
-    return lib
-
-
-def bind_moments_api(lib):
-    """argtypes/restypes of the moment entry points (trx_set_observed, trx_run_moments and their batch forms)."""
-    lib.trx_set_observed.argtypes = [C.c_void_p, C.POINTER(TrxObserved)]
-    lib.trx_set_observed.restype = C.c_int
-    lib.trx_run_moments.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                    c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_moments.restype = C.c_int
-    lib.trx_batch_set_observed.argtypes = [C.c_void_p, C.POINTER(TrxObserved)]
-    lib.trx_batch_set_observed.restype = C.c_int
-    lib.trx_run_batch_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
-                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_moments.restype = C.c_int
-    return lib
-
-
-def bind_trail_api(lib):
-    """argtypes/restypes of the trail entry points (trx_run_trail and its batch form)."""
-    lib.trx_run_trail.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                  c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_trail.restype = C.c_int
-    lib.trx_run_batch_trail.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
-                                        C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_trail.restype = C.c_int
-    return lib
-
-
-def bind_vmap_api(lib):
-    """argtypes/restypes of the detection-map entry points (trx_run_velocity_map and its batch form)."""
-    lib.trx_run_velocity_map.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.POINTER(TrxVmap),
-                                         c_double_p, c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_velocity_map.restype = C.c_int
-    lib.trx_run_batch_velocity_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.POINTER(TrxVmap),
-                                               C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_velocity_map.restype = C.c_int
-    return lib
-
-
 CELLMAP_CHUNK = 64      # kCellMapChunk (csrc/hip/trx_device.h): the most cells of a filtered map that go through the device at once
-
-
-def bind_cellmap_api(lib):
-    """argtypes/restypes of the filtered-map entry points (trx_run_filtered_map and its batch form)."""
-    lib.trx_run_filtered_map.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.POINTER(TrxVmap),
-                                         c_double_p, c_int32_p, C.POINTER(TrxDebug)]
-    lib.trx_run_filtered_map.restype = C.c_int
-    lib.trx_run_batch_filtered_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.POINTER(TrxVmap),
-                                               C.POINTER(c_double_p)]
-    lib.trx_run_batch_filtered_map.restype = C.c_int
-    return lib
-
-
 EXPOSED_MAP_PAIR_BYTES = 1 << 33      # kExposedMapPairBytes (csrc/hip/trx_device.h): the most bytes of pixel pairs [R][npix][2] an exposed map makes
 
 
-def bind_expmap_api(lib):
-    """argtypes/restypes of the exposed-map entry points (trx_run_exposed_map and its batch form)."""
-    lib.trx_run_exposed_map.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.POINTER(TrxVmap),
-                                        c_double_p, c_int32_p, C.POINTER(C.c_int64), C.POINTER(TrxDebug)]
-    lib.trx_run_exposed_map.restype = C.c_int
-    lib.trx_run_batch_exposed_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.POINTER(TrxVmap),
-                                              C.POINTER(c_double_p)]
-    lib.trx_run_batch_exposed_map.restype = C.c_int
+LOG_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)     # trx_log_fn
+
+HIP_HEADER = os.path.join(ROOT, "include", "transit_hip.h")
+HOST_HEADER = os.path.join(ROOT, "include", "transit_host.h")
+
+# a C type as a header writes it -> its ctypes: `const` and the parameter's name dropped, no blank at a star
+CTYPES = {
+    "void": None, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "long": C.c_long, "double": C.c_double,
+    "int*": C.POINTER(C.c_int), "int32_t*": c_int32_p, "int64_t*": c_int64_p, "float*": c_float_p, "double*": c_double_p,
+    "uint8_t*": c_uint8_p, "unsigned char*": c_uint8_p, "char*": C.c_char_p, "void*": C.c_void_p,
+    "int32_t**": C.POINTER(c_int32_p), "double**": C.POINTER(c_double_p), "char**": C.POINTER(C.c_char_p),
+    "void**": C.POINTER(C.c_void_p), "trx_log_fn": LOG_FN,
+}
+
+_prototypes = {}
+
+
+def _ctype(decl: str, named: bool, opaque, where: str):
+    """the ctypes of one declared type: CTYPES, a handle the header only names (`T *`: c_void_p, `T **`: a pointer to one)
+    or `trx_<name> *`, a pointer to the structure Trx<Name> of this module"""
+    t = re.sub(r"\bconst\b", " ", decl).strip()
+    if named and re.search(r"[\s*]\w+$", t):
+        t = re.sub(r"\w+$", "", t)
+    t = re.sub(r"\s*\*\s*", "*", re.sub(r"\s+", " ", t)).strip()
+    if t in CTYPES:
+        return CTYPES[t]
+    base, stars = t.rstrip("*"), len(t) - len(t.rstrip("*"))
+    if base in opaque and stars in (1, 2):
+        return C.c_void_p if stars == 1 else C.POINTER(C.c_void_p)
+    struct = globals().get("".join(w.capitalize() for w in base.split("_")))      # trx_opacity_grid: TrxOpacityGrid
+    if base.startswith("trx_") and stars == 1 and isinstance(struct, type) and issubclass(struct, C.Structure):
+        return C.POINTER(struct)
+    raise ValueError("%s: no ctypes for the C type '%s'" % (where, " ".join(decl.split())))
+
+
+def parse(text: str, prefix: str):
+    """{name: (restype, argtypes)} of every `<ret> <prefix>name(args);` of a header's text"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    opaque = set(re.findall(r"\btypedef\s+struct\s+(\w+)\s+\1\s*;", text))
+    out = {}
+    for ret, name, args in re.findall(r"^[ \t]*([\w \t*]+?)\s*\b(%s\w+)\s*\(([^()]*)\)\s*;" % re.escape(prefix), text, flags=re.M):
+        pars = [] if args.strip() in ("", "void") else args.split(",")
+        out[name] = (_ctype(ret, False, opaque, name + ", the return type"),
+                     [_ctype(p, True, opaque, "%s, argument %d" % (name, i + 1)) for i, p in enumerate(pars)])
+    return out
+
+
+def prototypes(header_path: str, prefix: str):
+    """parse() of a header file, read once per path and prefix"""
+    key = (header_path, prefix)
+    if key not in _prototypes:
+        with open(header_path) as f:
+            _prototypes[key] = parse(f.read(), prefix)
+    return _prototypes[key]
+
+
+def bind(lib, header_path: str, prefix: str, exported: str = ""):
+    """Set argtypes and restype, as the header declares them, on every `<prefix>name` of it that *lib* exports (as
+    `<exported>name`, where the library has the same family under a prefix of its own).  The header is the one place a
+    signature is written: a type this module cannot turn into ctypes raises ValueError."""
+    for name, (restype, argtypes) in prototypes(header_path, prefix).items():
+        fn = getattr(lib, exported + name[len(prefix):] if exported else name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = argtypes, restype
     return lib
 
 
-def bind_filter_api(lib):
-    """argtypes/restypes of the filter entry points (trx_set_filter, trx_run_filtered_moments and their batch forms)."""
-    lib.trx_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]
-    lib.trx_set_filter.restype = C.c_int
-    lib.trx_run_filtered_moments.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32,
-                                             c_double_p, c_double_p, c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_filtered_moments.restype = C.c_int
-    lib.trx_batch_set_filter.argtypes = [C.c_void_p, C.POINTER(TrxFilter)]
-    lib.trx_batch_set_filter.restype = C.c_int
-    lib.trx_set_weighted_filter.argtypes = [C.c_void_p, C.POINTER(TrxWfilter), C.POINTER(C.c_int64)]
-    lib.trx_set_weighted_filter.restype = C.c_int
-    lib.trx_batch_set_weighted_filter.argtypes = [C.c_void_p, C.POINTER(TrxWfilter)]
-    lib.trx_batch_set_weighted_filter.restype = C.c_int
-    lib.trx_run_batch_filtered_moments.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
-                                                   C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_filtered_moments.restype = C.c_int
-    return lib
-
-
-def bind_highpass_api(lib):
-    """argtypes/restypes of the high-pass entry points (trx_set_highpass, trx_run_highpassed, trx_batch_set_highpass)."""
-    lib.trx_set_highpass.argtypes = [C.c_void_p, C.POINTER(TrxHighpass)]
-    lib.trx_set_highpass.restype = C.c_int
-    lib.trx_run_highpassed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32,
-                                       c_double_p, c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_highpassed.restype = C.c_int
-    lib.trx_batch_set_highpass.argtypes = [C.c_void_p, C.POINTER(TrxHighpass)]
-    lib.trx_batch_set_highpass.restype = C.c_int
-    return lib
-
-
-def bind_broaden_api(lib):
-    """argtypes/restypes of the broadening entry points (trx_set_broadening, trx_run_broadened and their batch forms)."""
-    lib.trx_set_broadening.argtypes = [C.c_void_p, C.POINTER(TrxBroadening)]
-    lib.trx_set_broadening.restype = C.c_int
-    lib.trx_run_broadened.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, c_double_p,
-                                      C.POINTER(TrxDebug)]
-    lib.trx_run_broadened.restype = C.c_int
-    lib.trx_batch_set_broadening.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxBroadening)]
-    lib.trx_batch_set_broadening.restype = C.c_int
-    lib.trx_run_batch_broadened.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts),
-                                            C.POINTER(c_double_p)]
-    lib.trx_run_batch_broadened.restype = C.c_int
-    return lib
-
-
-def bind_exposures_api(lib):
-    """argtypes/restypes of the exposure-table entry points (trx_set_exposures, trx_run_exposed and their batch forms)."""
-    lib.trx_set_exposures.argtypes = [C.c_void_p, C.POINTER(TrxExposures)]
-    lib.trx_set_exposures.restype = C.c_int
-    lib.trx_run_exposed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                    c_double_p, C.POINTER(TrxDebug)]
-    lib.trx_run_exposed.restype = C.c_int
-    lib.trx_batch_set_exposures.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxExposures)]
-    lib.trx_batch_set_exposures.restype = C.c_int
-    lib.trx_run_batch_exposed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TrxAtm), C.POINTER(TrxOpts), C.c_int32,
-                                          C.POINTER(c_double_p), C.POINTER(c_double_p)]
-    lib.trx_run_batch_exposed.restype = C.c_int
-    return lib
-
-
-def bind_sysrem_api(lib):
-    """argtypes/restypes of the detrending entry point (trx_detrend_observed)."""
-    lib.trx_detrend_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                         C.POINTER(TrxDetrend), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int64),
-                                         C.POINTER(TrxDebug)]
-    lib.trx_detrend_observed.restype = C.c_int
-    return lib
-
-
-def bind_pca_api(lib):
-    """argtypes/restypes of the principal-component entry point (trx_pca_observed)."""
-    i64p = C.POINTER(C.c_int64)
-    lib.trx_pca_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                     C.POINTER(TrxPca), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, i64p, i64p,
-                                     C.POINTER(TrxDebug)]
-    lib.trx_pca_observed.restype = C.c_int
-    return lib
-
-
-def bind_regress_api(lib):
-    """argtypes/restypes of the regression entry point (trx_regress_observed)."""
-    i64p = C.POINTER(C.c_int64)
-    lib.trx_regress_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                         C.POINTER(TrxRegress), c_double_p, c_double_p, c_double_p, i64p, i64p, C.POINTER(TrxDebug)]
-    lib.trx_regress_observed.restype = C.c_int
-    return lib
-
-
-def bind_scatter_api(lib):
-    """argtypes/restypes of the column-scatter entry point (trx_weigh_observed)."""
-    lib.trx_weigh_observed.argtypes = [C.c_void_p, C.POINTER(TrxScatter), c_double_p, c_double_p, c_double_p,
-                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.trx_weigh_observed.restype = C.c_int
-    return lib
-
-
-def bind_hpdata_api(lib):
-    """argtypes/restypes of the observed set's own high-pass (trx_highpass_observed)."""
-    lib.trx_highpass_observed.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.POINTER(C.c_int64)]
-    lib.trx_highpass_observed.restype = C.c_int
-    return lib
-
-
-def bind_normalise_api(lib):
-    """argtypes/restypes of the normalisation entry points (trx_set_normalise, trx_normalise_observed)."""
-    i64p = C.POINTER(C.c_int64)
-    lib.trx_set_normalise.argtypes = [C.c_void_p, C.POINTER(TrxNormalise)]
-    lib.trx_set_normalise.restype = C.c_int
-    lib.trx_normalise_observed.argtypes = [C.c_void_p, C.POINTER(TrxAtm), C.POINTER(TrxOpts), c_double_p, C.c_int32, c_double_p,
-                                           C.c_int32, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p, i64p, i64p,
-                                           C.POINTER(TrxDebug)]
-    lib.trx_normalise_observed.restype = C.c_int
-    return lib
+def bind_engine_api(lib, prefix: str = "trx_"):
+    """transit_hip.h's signatures on a library of the same ABI shape that exports them as <prefix>name and has no header
+    of its own (CEngine serves any such library)."""
+    return bind(lib, HIP_HEADER, "trx_", prefix)

@@ -26,10 +26,6 @@ def create_comm(world: int, rank: int, device: int, broadcast: Optional[Callable
     ships the unique id; by default torch.distributed does it."""
     from .engine import hip_library, EngineError
     lib = hip_library()
-    lib.trx_comm_unique_id.argtypes = [C.c_void_p]
-    lib.trx_comm_unique_id.restype = C.c_int
-    lib.trx_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    lib.trx_comm_create.restype = C.c_int
     buf = C.create_string_buffer(COMM_ID_BYTES)
     if rank == 0:
         rc = lib.trx_comm_unique_id(buf)
@@ -42,7 +38,6 @@ def create_comm(world: int, rank: int, device: int, broadcast: Optional[Callable
     comm = C.c_void_p()
     rc = lib.trx_comm_create(idbuf, world, rank, device, C.byref(comm))
     if rc != 0:
-        lib.trx_last_error.argtypes, lib.trx_last_error.restype = [C.c_void_p], C.c_char_p
         raise EngineError(rc, "trx_comm_create", (lib.trx_last_error(None) or b"").decode(errors="replace"))
     return comm
 
@@ -50,8 +45,6 @@ def create_comm(world: int, rank: int, device: int, broadcast: Optional[Callable
 def destroy_comm(comm):
     from .engine import hip_library
     lib = hip_library()
-    lib.trx_comm_destroy.argtypes = [C.c_void_p]
-    lib.trx_comm_destroy.restype = None
     if comm:
         lib.trx_comm_destroy(comm)
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import numpy as np
@@ -43,11 +44,16 @@ class CEngine:
     def _f(self, name):
         return getattr(self._lib, self._p + name)
 
+    def _call(self, name, *args):
+        """<prefix>name(handle, *args), a non-zero status raised with the handle's last error"""
+        rc = self._f(name)(self._h, *args)
+        if rc != 0:
+            raise EngineError(rc, self._p + name, self._last_error())
+
     def _last_error(self) -> str:
         fn = getattr(self._lib, self._p + "last_error", None)
         if fn is None or not self._h:
             return ""
-        fn.argtypes, fn.restype = [C.c_void_p], C.c_char_p
         v = fn(self._h)
         return v.decode(errors="replace") if v else ""
 
@@ -82,11 +88,7 @@ class CEngine:
             ptr = lambda k: out[k].ctypes.data_as(types.get(k, _abi.c_double_p)) if k in out else None
             dbg = _abi.TrxDebug(ptr("e"), ptr("e_cs"), ptr("tau"), ptr("last"), ptr("intens"), ptr("computed"),
                                 ptr("er"), ptr("e_scat"), ptr("e_cloud"))
-        rc = self._f("run")(self._h, C.byref(atm), C.byref(opts),
-                            out["spectrum"].ctypes.data_as(_abi.c_double_p),
-                            C.byref(dbg) if dbg is not None else None)
-        if rc != 0:
-            raise EngineError(rc, self._p + "run", self._last_error())
+        self._call("run", C.byref(atm), C.byref(opts), _dp(out["spectrum"]), C.byref(dbg) if dbg is not None else None)
         return out
 
     def run_into(self, atm: _abi.TrxAtm, opts: _abi.TrxOpts, spectrum: np.ndarray) -> None:
@@ -94,17 +96,12 @@ class CEngine:
         (retrieval loops, bench.py's timed step)."""
         if spectrum.dtype != np.float64 or not spectrum.flags.c_contiguous or spectrum.size < self.nwn:
             raise ValueError("spectrum: a C-contiguous float64 array of at least %d elements" % self.nwn)
-        rc = self._f("run")(self._h, C.byref(atm), C.byref(opts), spectrum.ctypes.data_as(_abi.c_double_p), None)
-        if rc != 0:
-            raise EngineError(rc, self._p + "run", self._last_error())
+        self._call("run", C.byref(atm), C.byref(opts), _dp(spectrum), None)
 
     def sweep_permol(self, nv, temp, density, zpart, ethresh, nslot, iso_slot) -> np.ndarray:
         """computemolext(permol=1) for nv states: returns o[nv][nslot][nwn]."""
         out = np.zeros((nv, nslot, self.nwn))
-        rc = self._f("sweep_permol")(self._h, nv, temp, density, zpart, float(ethresh), nslot, iso_slot,
-                                     out.ctypes.data_as(_abi.c_double_p))
-        if rc != 0:
-            raise EngineError(rc, self._p + "sweep_permol", self._last_error())
+        self._call("sweep_permol", nv, temp, density, zpart, float(ethresh), nslot, iso_slot, _dp(out))
         return out
 
     def build_opacity_grid(self, problem) -> np.ndarray:
@@ -117,21 +114,15 @@ class CEngine:
 
     def restore_extinction(self, e: Optional[np.ndarray], computed: Optional[np.ndarray] = None):
         """trx_restore_extinction: e [nlayer][nwn_shard] and one flag per layer (None: forget them)."""
-        fn = self._f("restore_extinction")
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_int32, _abi.c_double_p, _abi.c_uint8_p], C.c_int
         if e is None:
-            rc = fn(self._h, 0, None, None)
+            self._call("restore_extinction", 0, None, None)
         else:
             e = np.ascontiguousarray(e, dtype=np.float64); c = np.ascontiguousarray(computed, dtype=np.uint8)
-            rc = fn(self._h, e.shape[0], e.ctypes.data_as(_abi.c_double_p), c.ctypes.data_as(_abi.c_uint8_p))
-        if rc != 0:
-            raise EngineError(rc, self._p + "restore_extinction", self._last_error())
+            self._call("restore_extinction", e.shape[0], _dp(e), c.ctypes.data_as(_abi.c_uint8_p))
 
     def stats(self) -> Dict[str, float]:
         s = _abi.TrxStats()
-        rc = self._f("get_stats")(self._h, C.byref(s))
-        if rc != 0:
-            raise EngineError(rc, self._p + "get_stats")
+        self._call("get_stats", C.byref(s))
         return s.as_dict()
 
     def table(self):
@@ -139,22 +130,14 @@ class CEngine:
         n = self.ndop * self.nlor
         ps, off = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
         tot = C.c_int64()
-        rc = self._f("table_info")(self._h, ps.ctypes.data_as(_abi.c_int64_p),
-                                   off.ctypes.data_as(_abi.c_int64_p), C.byref(tot))
-        if rc != 0:
-            raise EngineError(rc, self._p + "table_info")
+        self._call("table_info", ps.ctypes.data_as(_abi.c_int64_p), off.ctypes.data_as(_abi.c_int64_p), C.byref(tot))
         tab = np.zeros(tot.value, dtype=np.float32)
-        rc = self._f("table_copy")(self._h, tab.ctypes.data_as(_abi.c_float_p))
-        if rc != 0:
-            raise EngineError(rc, self._p + "table_copy")
+        self._call("table_copy", tab.ctypes.data_as(_abi.c_float_p))
         return ps.reshape(self.ndop, self.nlor), off.reshape(self.ndop, self.nlor), tab
 
     def width_grids(self):
         d, l = np.zeros(self.ndop), np.zeros(self.nlor)
-        rc = self._f("width_grids")(self._h, d.ctypes.data_as(_abi.c_double_p),
-                                    l.ctypes.data_as(_abi.c_double_p))
-        if rc != 0:
-            raise EngineError(rc, self._p + "width_grids")
+        self._call("width_grids", _dp(d), _dp(l))
         return d, l
 
 
@@ -197,36 +180,12 @@ def hip_library():
                                "`python -m transit_amd.build` (hipcc --offload-arch=gfx950)" % path)
         _one_hip_runtime()
         lib = C.CDLL(path)
-        _abi.bind_engine_api(lib, "trx_")
-        lib.trx_run_device.argtypes = [C.c_void_p, C.POINTER(_abi.TrxAtm), C.POINTER(_abi.TrxOpts),
-                                       C.c_void_p, C.POINTER(_abi.TrxDebug)]
-        lib.trx_run_device.restype = C.c_int
-        _abi.bind_bands_api(lib)
-        _abi.bind_contrib_api(lib)
-        _abi.bind_pixels_api(lib)
-        _abi.bind_moments_api(lib)
-        _abi.bind_trail_api(lib)
-        _abi.bind_vmap_api(lib)
-        _abi.bind_filter_api(lib)
-        _abi.bind_cellmap_api(lib)
-        _abi.bind_highpass_api(lib)
-        _abi.bind_broaden_api(lib)
-        _abi.bind_exposures_api(lib)
-        _abi.bind_expmap_api(lib)
-        _abi.bind_sysrem_api(lib)
-        _abi.bind_pca_api(lib)
-        _abi.bind_regress_api(lib)
-        _abi.bind_scatter_api(lib)
-        _abi.bind_hpdata_api(lib)
-        _abi.bind_normalise_api(lib)
-        lib.trx_device_count.restype = C.c_int
-        lib.trx_abi_version.restype = C.c_int
+        _abi.bind(lib, _abi.HIP_HEADER, "trx_")
         if lib.trx_abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("libtransit_hip.so ABI %d != binding %d" % (lib.trx_abi_version(), _abi.ABI_VERSION))
         # the runtime in this process may be the copy a PyTorch wheel bundles, not the toolchain's the
         # library was compiled against: a different MAJOR version is refused, a different minor one told
         built, running = C.c_int(0), C.c_int(0)
-        lib.trx_hip_versions.argtypes, lib.trx_hip_versions.restype = [C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int
         if lib.trx_hip_versions(C.byref(built), C.byref(running)) == 0 and built.value and running.value:
             if built.value // 10000000 != running.value // 10000000:
                 raise RuntimeError("libtransit_hip.so was built with HIP %d but runs on runtime %d (set "
@@ -242,6 +201,23 @@ def _dp(x):
     return x.ctypes.data_as(_abi.c_double_p) if x is not None else None
 
 
+def _vec(x) -> np.ndarray:
+    """x (shifts, lags) as a flat C-contiguous double array"""
+    return np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+
+
+def _zeros(give, *shapes):
+    """one zeroed double array per shape, or one None per shape where the caller does not want the outputs"""
+    return [np.zeros(shape) if give else None for shape in shapes]
+
+
+def _some(*pairs):
+    """(value, wanted) pairs: the wanted values as a tuple, or the only one by itself"""
+    out = tuple(v for v, wanted in pairs if wanted)
+    return out if len(out) > 1 else out[0]
+
+
+@dataclass(eq=False)
 class Detrended:
     """What Engine.detrend_observed returns: basis [nseg, nexp, ncomp] the fitted time vectors U, coef [ncomp, npix] their
     column vectors, data [nexp, npix] the residuals now installed as the observed data (None after the undo), nsingular the
@@ -252,133 +228,137 @@ class Detrended:
     nsingular_fit, the columns whose fit of the given vectors had a singular pivot (None from the other two calls); its basis
     [nseg, nexp, nvec + nfit] holds the given vectors ahead of the fitted ones, its coef [nvec + nfit, npix] likewise."""
 
-    def __init__(self, basis, coef, data, nsingular, spectrum=None, eigen=None, offdiag=None, nwhole=None, nsingular_fit=None):
-        self.basis, self.coef, self.data, self.nsingular, self.spectrum = basis, coef, data, nsingular, spectrum
-        self.eigen, self.offdiag, self.nwhole, self.nsingular_fit = eigen, offdiag, nwhole, nsingular_fit
+    basis: Optional[np.ndarray]
+    coef: Optional[np.ndarray]
+    data: Optional[np.ndarray]
+    nsingular: int
+    spectrum: Optional[np.ndarray] = None
+    eigen: Optional[np.ndarray] = None
+    offdiag: Optional[np.ndarray] = None
+    nwhole: Optional[np.ndarray] = None
+    nsingular_fit: Optional[int] = None
 
 
+@dataclass(eq=False)
 class Weighed:
     """What Engine.weigh_observed returns: variance [npix] every column's variance in time (+0: a dead column), median [nseg]
     every segment's median variance, weight [nexp, npix] the weights now in force (all three None after the undo or with
     outputs=False), nmasked the live columns the clip removed, nsingular the columns the installed weighted filter's pivot
     rule makes dead under the new weights (0 without a weighted filter)."""
 
-    def __init__(self, variance, median, weight, nmasked, nsingular):
-        self.variance, self.median, self.weight, self.nmasked, self.nsingular = variance, median, weight, nmasked, nsingular
+    variance: Optional[np.ndarray]
+    median: Optional[np.ndarray]
+    weight: Optional[np.ndarray]
+    nmasked: int
+    nsingular: int
 
 
+@dataclass(eq=False)
 class Highpassed:
     """What Engine.highpass_observed returns: data [nexp, npix] the high-passed data now installed (+0 at the dead entries;
     None after the undo or with outputs=False), ndead the entries whose weight as set_observed installed it is not > 0."""
 
-    def __init__(self, data, ndead):
-        self.data, self.ndead = data, ndead
+    data: Optional[np.ndarray]
+    ndead: int
 
 
+@dataclass(eq=False)
 class Normalised:
     """What Engine.normalise_observed returns: data [nexp, npix] the normalised data now installed (+0 at the dead entries and
     in bad rows and columns), rowscale [nexp, nseg] every row's scale (+0: a bad row), centre [npix] every column's mean in
     time (+0: a bad column) -- the three None with outputs=False --, nclipped the entries the clip replaced, nbad the live
     entries that got +0, spectrum the injection run's spectrum (None without)."""
 
-    def __init__(self, data, rowscale, centre, nclipped, nbad, spectrum=None):
-        self.data, self.rowscale, self.centre, self.nclipped, self.nbad, self.spectrum = data, rowscale, centre, nclipped, nbad, spectrum
+    data: Optional[np.ndarray]
+    rowscale: Optional[np.ndarray]
+    centre: Optional[np.ndarray]
+    nclipped: int
+    nbad: int
+    spectrum: Optional[np.ndarray] = None
 
 
 class Engine(CEngine):
     """MI355X engine: one handle = one GPU = one wavenumber shard."""
 
     def __init__(self, static: _abi.TrxStatic):
+        self.nbands, self.npix, self.mom_shape = 0, 0, (0, 0)       # of the sets installed: none yet
         super().__init__(hip_library(), "trx_", static)
 
     def run_device(self, atm, opts, d_spectrum_ptr: int):
-        rc = self._lib.trx_run_device(self._h, C.byref(atm), C.byref(opts), C.c_void_p(d_spectrum_ptr), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_device", self._last_error())
+        self._call("run_device", C.byref(atm), C.byref(opts), C.c_void_p(d_spectrum_ptr), None)
+
+    def _run_at(self, name, atm, opts, sh, out, spectrum: bool):
+        """the run `name` at the shifts (or lags) sh into out: out, or (out, spectrum) with spectrum=True"""
+        spec = np.zeros(self.nwn) if spectrum else None
+        self._call(name, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(out), None)
+        return (out, spec) if spectrum else out
+
+    def _inject(self, inject):
+        """inject=(atm, opts, shifts, p0, p1) of an observed-set call, or None: the five leading arguments of its C
+        signature (atm, opts, spectrum, nshift, shift), the flag, p0, p1 and the spectrum's buffer (None without)"""
+        if inject is None:
+            return (None, None, None, 0, None), 0, 0.0, 0.0, None
+        atm, opts, shifts, p0, p1 = inject
+        sh, spec = _vec(shifts), np.zeros(self.nwn)
+        return (C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh)), 1, float(p0), float(p1), spec
 
     def set_bands(self, bands):
         """trx_set_bands: install a band set (a list of transit_amd.bands.Band; empty: clear it)."""
         arr = _bands.to_c(bands)
-        rc = self._lib.trx_set_bands(self._h, len(bands), arr)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_bands", self._last_error())
+        self._call("set_bands", len(bands), arr)
         self.nbands = len(bands)
 
     def run_bands(self, atm, opts, spectrum: bool = False):
         """trx_run_bands: the band sums [nbands, 2] of this shard -- and, with spectrum=True, (sums, spectrum),
         the spectrum bit for bit what run() gives."""
-        sums = np.zeros((getattr(self, "nbands", 0), 2))
+        sums = np.zeros((self.nbands, 2))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_bands(self._h, C.byref(atm), C.byref(opts), _dp(spec), _dp(sums), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_bands", self._last_error())
+        self._call("run_bands", C.byref(atm), C.byref(opts), _dp(spec), _dp(sums), None)
         return (sums, spec) if spectrum else sums
 
     def run_contrib(self, atm, opts, spectrum: bool = False):
         """trx_run_contrib: (sums [nbands, 2], contrib [nbands, nlayer]) of this shard -- the band sums run_bands gives
         and the contribution function (eclipse) or transmittance profile (transit) of every band, rows in the
         atmosphere's layer order; with spectrum=True, (sums, contrib, spectrum)."""
-        nb = getattr(self, "nbands", 0)
+        nb = self.nbands
         sums = np.zeros((nb, 2))
         contrib = np.zeros((nb, int(atm.nlayer)))
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_contrib(self._h, C.byref(atm), C.byref(opts), _dp(spec), _dp(sums), _dp(contrib), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_contrib", self._last_error())
+        self._call("run_contrib", C.byref(atm), C.byref(opts), _dp(spec), _dp(sums), _dp(contrib), None)
         return (sums, contrib, spec) if spectrum else (sums, contrib)
 
     def set_pixels(self, pixels):
         """trx_set_pixels: install a detector (a transit_amd.pixels.Pixels; None or an empty one: clear it)."""
         n = len(pixels) if pixels is not None else 0
-        rc = self._lib.trx_set_pixels(self._h, C.byref(_pixels.to_c(pixels)) if n else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_pixels", self._last_error())
+        self._call("set_pixels", C.byref(_pixels.to_c(pixels)) if n else None)
         self.npix = n
         self.mom_shape = (0, 0)
 
     def run_pixels(self, atm, opts, shifts, spectrum: bool = False):
         """trx_run_pixels: the pairs [nshift, npix, 2] of this shard at the Doppler shifts given (nu_observed / nu_rest)
         -- and, with spectrum=True, (pairs, spectrum), the spectrum bit for bit what run() gives."""
-        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-        out = np.zeros((sh.size, getattr(self, "npix", 0), 2))
-        spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_pixels(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(out), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_pixels", self._last_error())
-        return (out, spec) if spectrum else out
+        sh = _vec(shifts)
+        return self._run_at("run_pixels", atm, opts, sh, np.zeros((sh.size, self.npix, 2)), spectrum)
 
     def set_observed(self, observed):
         """trx_set_observed: install the observed exposures (a transit_amd.xcor.Observed; None: clear them) over the
         pixel set in force.  set_pixels drops them."""
-        rc = self._lib.trx_set_observed(self._h, C.byref(observed.to_c()) if observed is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_observed", self._last_error())
+        self._call("set_observed", C.byref(observed.to_c()) if observed is not None else None)
         self.mom_shape = (observed.nexp, observed.nseg) if observed is not None else (0, 0)
 
     def run_moments(self, atm, opts, shifts, spectrum: bool = False):
         """trx_run_moments: the moments [nexp, nseg, 7] of the pixels at the exposures' Doppler shifts against the
         observed set (transit_amd.xcor) -- and, with spectrum=True, (moments, spectrum), the spectrum bit for bit what
         run() gives.  The pixel pairs stay on the device."""
-        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-        mom = np.zeros(getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
-        spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_moments(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(mom), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_moments", self._last_error())
-        return (mom, spec) if spectrum else mom
+        return self._run_at("run_moments", atm, opts, _vec(shifts), np.zeros(self.mom_shape + (_abi.NMOMENT,)), spectrum)
 
     def run_trail(self, atm, opts, lags, spectrum: bool = False):
         """trx_run_trail: the trail [nlag, nexp, nseg, 7] -- the moments of every exposure of the observed set against
         the model at every lag (nu_observed / nu_rest, as shifts are; transit_amd.xcor.lag_grid), row l bit for bit
         run_moments(atm, opts, [lags[l]] * nexp) -- and, with spectrum=True, (trail, spectrum), the spectrum bit for bit
         what run() gives.  An installed filter takes no part; the pixel pairs stay on the device."""
-        lg = np.ascontiguousarray(lags, dtype=np.float64).reshape(-1)
-        trail = np.zeros((lg.size,) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
-        spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_trail(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(lg.size), _dp(lg), _dp(trail), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_trail", self._last_error())
-        return (trail, spec) if spectrum else trail
+        lg = _vec(lags)
+        return self._run_at("run_trail", atm, opts, lg, np.zeros((lg.size,) + self.mom_shape + (_abi.NMOMENT,)), spectrum)
 
     def run_velocity_map(self, atm, opts, vm, per: bool = False, spectrum: bool = False):
         """trx_run_velocity_map: the Kp-Vsys map [nkp, nvsys] of a transit_amd.xcor.VelocityMap -- run_trail at vm.lag and,
@@ -386,20 +366,15 @@ class Engine(CEngine):
         spectrum=True a tuple (map[, per][, spectrum]): per [nlag, nexp] the statistic the map was made from (the map is
         xcor.map_from_per(per, vm) bit for bit), the spectrum bit for bit what run() gives."""
         m = np.zeros((vm.nkp, vm.nvsys))
-        pr = np.zeros((vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
+        pr = np.zeros((vm.nlag, self.mom_shape[0])) if per else None
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_velocity_map(self._h, C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m), _dp(pr), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_velocity_map", self._last_error())
-        out = (m,) + ((pr,) if per else ()) + ((spec,) if spectrum else ())
-        return out if len(out) > 1 else m
+        self._call("run_velocity_map", C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m), _dp(pr), None)
+        return _some((m, True), (pr, per), (spec, spectrum))
 
     def set_filter(self, filt):
         """trx_set_filter: install a detrending filter (a transit_amd.xcor.Filter; None: clear it) over the observed
         set in force.  set_observed and set_pixels drop it."""
-        rc = self._lib.trx_set_filter(self._h, C.byref(filt.to_c()) if filt is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_filter", self._last_error())
+        self._call("set_filter", C.byref(filt.to_c()) if filt is not None else None)
 
     def set_weighted_filter(self, wf) -> int:
         """trx_set_weighted_filter: install a weighted detrending filter (a transit_amd.xcor.WeightedFilter; None: clear
@@ -407,9 +382,7 @@ class Engine(CEngine):
         squares under its own weights.  Returns the number of columns the pivot rule makes dead.  run_filtered_moments
         and run_filtered_map then take it where they took the plain filter."""
         nsing = C.c_int64(0)
-        rc = self._lib.trx_set_weighted_filter(self._h, C.byref(wf.to_c()) if wf is not None else None, C.byref(nsing))
-        if rc != 0:
-            raise EngineError(rc, "trx_set_weighted_filter", self._last_error())
+        self._call("set_weighted_filter", C.byref(wf.to_c()) if wf is not None else None, C.byref(nsing))
         return int(nsing.value)
 
     def run_filtered_moments(self, atm, opts, shifts, spectrum: bool = False, values: bool = False):
@@ -417,16 +390,12 @@ class Engine(CEngine):
         observed set; with spectrum=True and/or values=True a tuple (moments[, spectrum][, values]) -- the spectrum
         bit for bit what run() gives, the values [nexp, npix] the filtered model g' (NaN in dead columns).  Without
         values=True neither the pairs nor the values leave the device."""
-        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-        mom = np.zeros(getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        sh = _vec(shifts)
+        mom = np.zeros(self.mom_shape + (_abi.NMOMENT,))
         spec = np.zeros(self.nwn) if spectrum else None
-        val = np.zeros((mom.shape[0], getattr(self, "npix", 0))) if values else None
-        rc = self._lib.trx_run_filtered_moments(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(val),
-                                                _dp(mom), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_filtered_moments", self._last_error())
-        out = (mom,) + ((spec,) if spectrum else ()) + ((val,) if values else ())
-        return out if len(out) > 1 else mom
+        val = np.zeros((mom.shape[0], self.npix)) if values else None
+        self._call("run_filtered_moments", C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(val), _dp(mom), None)
+        return _some((mom, True), (spec, spectrum), (val, values))
 
     def run_filtered_map(self, atm, opts, vm, lag_index: bool = False, spectrum: bool = False):
         """trx_run_filtered_map: the Kp-Vsys map [nkp, nvsys] of a transit_amd.xcor.VelocityMap with the installed filter
@@ -436,50 +405,36 @@ class Engine(CEngine):
         (map[, lag_index][, spectrum]): lag_index [nkp, nvsys, nexp] int32 the lags taken (-1: outside), the spectrum
         bit for bit what run() gives.  One spectrum and one pixel pass, whatever the number of cells."""
         m = np.zeros((vm.nkp, vm.nvsys))
-        idx = np.zeros((vm.nkp, vm.nvsys, getattr(self, "mom_shape", (0, 0))[0]), dtype=np.int32) if lag_index else None
+        idx = np.zeros((vm.nkp, vm.nvsys, self.mom_shape[0]), dtype=np.int32) if lag_index else None
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_filtered_map(self._h, C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m),
-                                            idx.ctypes.data_as(_abi.c_int32_p) if lag_index else None, None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_filtered_map", self._last_error())
-        out = (m,) + ((idx,) if lag_index else ()) + ((spec,) if spectrum else ())
-        return out if len(out) > 1 else m
+        self._call("run_filtered_map", C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m),
+                   idx.ctypes.data_as(_abi.c_int32_p) if lag_index else None, None)
+        return _some((m, True), (idx, lag_index), (spec, spectrum))
 
     def set_highpass(self, hp):
         """trx_set_highpass: install a high-pass along the pixel axis (a transit_amd.xcor.HighPass; None: clear it) over
         the observed set in force.  run_moments, run_filtered_moments, run_trail and run_velocity_map then take the
         high-passed model; set_observed and set_pixels drop it."""
-        rc = self._lib.trx_set_highpass(self._h, C.byref(hp.to_c()) if hp is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_highpass", self._last_error())
+        self._call("set_highpass", C.byref(hp.to_c()) if hp is not None else None)
 
     def run_highpassed(self, atm, opts, shifts, spectrum: bool = False):
         """trx_run_highpassed: the high-passed model values [nshift, npix] (transit_amd.xcor.highpass_reference of
         run_pixels' pairs, bit for bit; NaN where the pixel is dead) at any number of shifts -- and, with
         spectrum=True, (values, spectrum), the spectrum bit for bit what run() gives."""
-        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-        val = np.zeros((sh.size, getattr(self, "npix", 0)))
-        spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_highpassed(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(val), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_highpassed", self._last_error())
-        return (val, spec) if spectrum else val
+        sh = _vec(shifts)
+        return self._run_at("run_highpassed", atm, opts, sh, np.zeros((sh.size, self.npix)), spectrum)
 
     def set_broadening(self, b):
         """trx_set_broadening: install a rotational broadening (a transit_amd.broaden.Rotation; None: clear it).  The
         pixel, moment and filtered-moment runs then sample the broadened spectrum; set_pixels does not drop it."""
-        rc = self._lib.trx_set_broadening(self._h, C.byref(_broaden.to_c(b)) if b is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_broadening", self._last_error())
+        self._call("set_broadening", C.byref(_broaden.to_c(b)) if b is not None else None)
 
     def run_broadened(self, atm, opts, spectrum: bool = False):
         """trx_run_broadened: the broadened spectrum [nwn] -- and, with spectrum=True, (broadened, spectrum), the
         spectrum bit for bit what run() gives (never the broadened one)."""
         out = np.zeros(self.nwn)
         spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_broadened(self._h, C.byref(atm), C.byref(opts), _dp(spec), _dp(out), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_broadened", self._last_error())
+        self._call("run_broadened", C.byref(atm), C.byref(opts), _dp(spec), _dp(out), None)
         return (out, spec) if spectrum else out
 
     def set_exposures(self, ex):
@@ -488,21 +443,14 @@ class Engine(CEngine):
         run_filtered_moments and run_exposed_map then take it; set_observed and set_pixels drop it.  No device work: cheap per likelihood
         call."""
         n = len(ex) if ex is not None else 0
-        rc = self._lib.trx_set_exposures(self._h, C.byref(ex.to_c()) if n else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_exposures", self._last_error())
+        self._call("set_exposures", C.byref(ex.to_c()) if n else None)
 
     def run_exposed(self, atm, opts, shifts, spectrum: bool = False):
         """trx_run_exposed: the pairs [nexp, npix, 2] of this shard at the exposures' Doppler shifts with the installed
         exposure table (transit_amd.exposures.reference) -- and, with spectrum=True, (pairs, spectrum), the spectrum bit
         for bit what run() gives."""
-        sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-        out = np.zeros((sh.size, getattr(self, "npix", 0), 2))
-        spec = np.zeros(self.nwn) if spectrum else None
-        rc = self._lib.trx_run_exposed(self._h, C.byref(atm), C.byref(opts), _dp(spec), int(sh.size), _dp(sh), _dp(out), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_exposed", self._last_error())
-        return (out, spec) if spectrum else out
+        sh = _vec(shifts)
+        return self._run_at("run_exposed", atm, opts, sh, np.zeros((sh.size, self.npix, 2)), spectrum)
 
     def run_exposed_map(self, atm, opts, vm, lag_index: bool = False, nrows: bool = False, spectrum: bool = False):
         """trx_run_exposed_map: run_filtered_map UNDER the installed exposure table -- the model of exposure v scaled and
@@ -513,15 +461,12 @@ class Engine(CEngine):
         the (lag, exposure) pixel rows the call made (xcor.exposed_map_rows(vm)[3]), the spectrum bit for bit what run()
         gives.  One spectrum and one pixel pass, whatever the number of cells."""
         m = np.zeros((vm.nkp, vm.nvsys))
-        idx = np.zeros((vm.nkp, vm.nvsys, getattr(self, "mom_shape", (0, 0))[0]), dtype=np.int32) if lag_index else None
+        idx = np.zeros((vm.nkp, vm.nvsys, self.mom_shape[0]), dtype=np.int32) if lag_index else None
         spec = np.zeros(self.nwn) if spectrum else None
         nr = C.c_int64(-1)
-        rc = self._lib.trx_run_exposed_map(self._h, C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m),
-                                           idx.ctypes.data_as(_abi.c_int32_p) if lag_index else None, C.byref(nr), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_run_exposed_map", self._last_error())
-        out = (m,) + ((idx,) if lag_index else ()) + ((int(nr.value),) if nrows else ()) + ((spec,) if spectrum else ())
-        return out if len(out) > 1 else m
+        self._call("run_exposed_map", C.byref(atm), C.byref(opts), _dp(spec), C.byref(vm.to_c()), _dp(m),
+                   idx.ctypes.data_as(_abi.c_int32_p) if lag_index else None, C.byref(nr), None)
+        return _some((m, True), (idx, lag_index), (int(nr.value), nrows), (spec, spectrum))
 
     def detrend_observed(self, ncomp: int, niter: int = 10, inject=None, outputs: bool = True) -> "Detrended":
         """trx_detrend_observed: SYSREM on the observed exposures themselves, on the device, always from the RAW data of
@@ -534,23 +479,14 @@ class Engine(CEngine):
         [nexp, npix] (the residuals now installed), nsingular, and spectrum (None without an injection).  outputs=False
         leaves basis, coef and data on the device (None in the result): the loop of an injection-recovery test needs
         only the map that follows."""
-        nexp, nseg = getattr(self, "mom_shape", (0, 0))
-        npix = getattr(self, "npix", 0)
-        dt = _abi.TrxDetrend(int(ncomp), int(niter), 0 if inject is None else 1, 0, 0.0, 0.0)
-        atm = opts = sh = spec = None
-        if inject is not None:
-            atm, opts, shifts, dt.p0, dt.p1 = inject
-            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-            spec = np.zeros(self.nwn)
+        (nexp, nseg), npix = self.mom_shape, self.npix
+        run, flag, p0, p1, spec = self._inject(inject)
+        dt = _abi.TrxDetrend(int(ncomp), int(niter), flag, 0, p0, p1)
         n = max(int(ncomp), 0) if outputs else 0
-        basis, coef, data = np.zeros((nseg, nexp, n)), np.zeros((n, npix)), np.zeros((nexp, npix))
+        basis, coef, data = _zeros(n, (nseg, nexp, n), (n, npix), (nexp, npix))
         nsing = C.c_int64(0)
-        rc = self._lib.trx_detrend_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
-                                            _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), C.byref(dt),
-                                            _dp(basis) if n else None, _dp(coef) if n else None, _dp(data) if n else None, C.byref(nsing), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_detrend_observed", self._last_error())
-        return Detrended(basis if n else None, coef if n else None, data if n else None, int(nsing.value), spec)
+        self._call("detrend_observed", *run, C.byref(dt), _dp(basis), _dp(coef), _dp(data), C.byref(nsing), None)
+        return Detrended(basis, coef, data, int(nsing.value), spec)
 
     def pca_observed(self, ncomp: int, nsweep: int = 8, inject=None, outputs: bool = True) -> "Detrended":
         """trx_pca_observed: detrend_observed with a principal-component analysis in time in SYSREM's place, on the device,
@@ -560,27 +496,15 @@ class Engine(CEngine):
         detrend_observed's; either call undoes either.  Scattered masks keep a column out of the fit: SYSREM is the tool
         for those.  Returns a Detrended with eigen [nseg, ncomp], offdiag [nseg] and nwhole [nseg] beside basis, coef and
         data (all None after the undo or with outputs=False)."""
-        nexp, nseg = getattr(self, "mom_shape", (0, 0))
-        npix = getattr(self, "npix", 0)
-        pc = _abi.TrxPca(int(ncomp), int(nsweep), 0 if inject is None else 1, 0, 0.0, 0.0)
-        atm = opts = sh = spec = None
-        if inject is not None:
-            atm, opts, shifts, pc.p0, pc.p1 = inject
-            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-            spec = np.zeros(self.nwn)
+        (nexp, nseg), npix = self.mom_shape, self.npix
+        run, flag, p0, p1, spec = self._inject(inject)
+        pc = _abi.TrxPca(int(ncomp), int(nsweep), flag, 0, p0, p1)
         n = max(int(ncomp), 0) if outputs else 0
-        basis, coef, data = np.zeros((nseg, nexp, n)), np.zeros((n, npix)), np.zeros((nexp, npix))
-        eigen, offdiag, nwhole = np.zeros((nseg, n)), np.zeros(nseg), np.zeros(nseg, dtype=np.int64)
+        basis, coef, data, eigen, offdiag = _zeros(n, (nseg, nexp, n), (n, npix), (nexp, npix), (nseg, n), nseg)
+        nwhole = np.zeros(nseg, dtype=np.int64) if n else None
         nsing = C.c_int64(0)
-        rc = self._lib.trx_pca_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
-                                        _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), C.byref(pc),
-                                        _dp(basis) if n else None, _dp(coef) if n else None, _dp(data) if n else None,
-                                        _dp(eigen) if n else None, _dp(offdiag) if n else None,
-                                        nwhole.ctypes.data_as(C.POINTER(C.c_int64)) if n else None, C.byref(nsing), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_pca_observed", self._last_error())
-        if not n:
-            return Detrended(None, None, None, int(nsing.value), spec)
+        self._call("pca_observed", *run, C.byref(pc), _dp(basis), _dp(coef), _dp(data), _dp(eigen), _dp(offdiag),
+                   nwhole.ctypes.data_as(_abi.c_int64_p) if n else None, C.byref(nsing), None)
         return Detrended(basis, coef, data, int(nsing.value), spec, eigen, offdiag, nwhole)
 
     def regress_observed(self, vectors, nfit: int = 0, niter: int = 10, inject=None, outputs: bool = True) -> "Detrended":
@@ -593,8 +517,7 @@ class Engine(CEngine):
         The residuals become the observed data and the weighted filter of the merged basis the filter -- with nfit = 0 by
         the very factor the fit used.  Returns a Detrended with nsingular_fit beside basis [nseg, nexp, nvec + nfit], coef
         [nvec + nfit, npix], data, nsingular and spectrum."""
-        nexp, nseg = getattr(self, "mom_shape", (0, 0))
-        npix = getattr(self, "npix", 0)
+        (nexp, nseg), npix = self.mom_shape, self.npix
         vec = None
         if vectors is not None:
             vec = np.asarray(vectors, dtype=np.float64)
@@ -604,22 +527,13 @@ class Engine(CEngine):
                 raise ValueError("Engine.regress_observed: vectors of shape [nseg][nexp][nvec] or [nexp][nvec]")
             vec = np.ascontiguousarray(vec)
         nvec = int(vec.shape[2]) if vec is not None else 0
-        rg = _abi.TrxRegress(nvec, int(nfit), int(niter), 0 if inject is None else 1, 0.0, 0.0, _dp(vec) if nvec else None)
-        atm = opts = sh = spec = None
-        if inject is not None:
-            atm, opts, shifts, rg.p0, rg.p1 = inject
-            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-            spec = np.zeros(self.nwn)
+        run, flag, p0, p1, spec = self._inject(inject)
+        rg = _abi.TrxRegress(nvec, int(nfit), int(niter), flag, p0, p1, _dp(vec) if nvec else None)
         n = nvec + max(int(nfit), 0) if outputs and nvec else 0
-        basis, coef, data = np.zeros((nseg, nexp, n)), np.zeros((n, npix)), np.zeros((nexp, npix))
+        basis, coef, data = _zeros(n, (nseg, nexp, n), (n, npix), (nexp, npix))
         nfs, nsing = C.c_int64(0), C.c_int64(0)
-        rc = self._lib.trx_regress_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
-                                            _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), C.byref(rg),
-                                            _dp(basis) if n else None, _dp(coef) if n else None, _dp(data) if n else None,
-                                            C.byref(nfs), C.byref(nsing), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_regress_observed", self._last_error())
-        return Detrended(basis if n else None, coef if n else None, data if n else None, int(nsing.value), spec, nsingular_fit=int(nfs.value))
+        self._call("regress_observed", *run, C.byref(rg), _dp(basis), _dp(coef), _dp(data), C.byref(nfs), C.byref(nsing), None)
+        return Detrended(basis, coef, data, int(nsing.value), spec, nsingular_fit=int(nfs.value))
 
     def weigh_observed(self, kind: int, clip: float = 0.0, min_live: int = 2, outputs: bool = True) -> "Weighed":
         """trx_weigh_observed: the column-scatter weights of the observed set, on the device, from the data installed (the
@@ -631,17 +545,12 @@ class Engine(CEngine):
         factorised again against them; run_filtered_moments, run_filtered_map and run_exposed_map then run under them.
         Returns a Weighed: variance [npix], median [nseg], weight [nexp, npix], nmasked, nsingular.  outputs=False leaves the
         three arrays on the device (None in the result)."""
-        nexp, nseg = getattr(self, "mom_shape", (0, 0))
-        npix = getattr(self, "npix", 0)
+        (nexp, nseg), npix = self.mom_shape, self.npix
         sc = _abi.TrxScatter(int(kind), int(min_live), float(clip))
-        give = bool(outputs) and int(kind) != _abi.SCATTER_NONE
-        var, med, w = np.zeros(npix), np.zeros(nseg), np.zeros((nexp, npix))
+        var, med, w = _zeros(bool(outputs) and int(kind) != _abi.SCATTER_NONE, npix, nseg, (nexp, npix))
         nm, nsing = C.c_int64(0), C.c_int64(0)
-        rc = self._lib.trx_weigh_observed(self._h, C.byref(sc), _dp(var) if give else None, _dp(med) if give else None,
-                                          _dp(w) if give else None, C.byref(nm), C.byref(nsing))
-        if rc != 0:
-            raise EngineError(rc, "trx_weigh_observed", self._last_error())
-        return Weighed(var if give else None, med if give else None, w if give else None, int(nm.value), int(nsing.value))
+        self._call("weigh_observed", C.byref(sc), _dp(var), _dp(med), _dp(w), C.byref(nm), C.byref(nsing))
+        return Weighed(var, med, w, int(nm.value), int(nsing.value))
 
     def highpass_observed(self, apply: bool = True, outputs: bool = True) -> "Highpassed":
         """trx_highpass_observed: the observed set's own data through the installed high-pass (set_highpass), on the device
@@ -650,13 +559,9 @@ class Engine(CEngine):
         bit for bit).  The result becomes the observed data; weights, filter, high-pass, exposure table and gain stay.
         apply=False is the undo.  Every successful detrend_observed discards the high-pass: the order is detrend, high-pass,
         weigh, map.  Returns a Highpassed: data [nexp, npix] and ndead.  outputs=False leaves the data on the device."""
-        nexp = getattr(self, "mom_shape", (0, 0))[0]
-        give = bool(outputs) and bool(apply)
-        data = np.zeros((nexp, getattr(self, "npix", 0))) if give else None
+        data, = _zeros(bool(outputs) and bool(apply), (self.mom_shape[0], self.npix))
         nd = C.c_int64(0)
-        rc = self._lib.trx_highpass_observed(self._h, 1 if apply else 0, _dp(data), C.byref(nd))
-        if rc != 0:
-            raise EngineError(rc, "trx_highpass_observed", self._last_error())
+        self._call("highpass_observed", 1 if apply else 0, _dp(data), C.byref(nd))
         return Highpassed(data, int(nd.value))
 
     def set_normalise(self, nm):
@@ -665,9 +570,7 @@ class Engine(CEngine):
         divided by or reduced by its mean in time, single entries clipped.  No device work, and nothing in force changes:
         detrend_observed, pca_observed and normalise_observed take the recipe from their next call on, between the
         injection and the fit.  set_observed and set_pixels drop it."""
-        rc = self._lib.trx_set_normalise(self._h, C.byref(nm.to_c()) if nm is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_set_normalise", self._last_error())
+        self._call("set_normalise", C.byref(nm.to_c()) if nm is not None else None)
 
     def normalise_observed(self, inject=None, outputs: bool = True) -> "Normalised":
         """trx_normalise_observed: "the detrend of zero components" -- the installed recipe (set_normalise) over the RAW data
@@ -677,34 +580,18 @@ class Engine(CEngine):
         call undo one another.  The weights are NOT changed: rows with rowscale == 0, bad columns and columns of a low
         centre are for the driver to mask in set_observed.  Returns a Normalised: data [nexp, npix], rowscale [nexp, nseg],
         centre [npix], nclipped, nbad and spectrum.  outputs=False leaves the three arrays on the device."""
-        nexp, nseg = getattr(self, "mom_shape", (0, 0))
-        npix = getattr(self, "npix", 0)
-        atm = opts = sh = spec = None
-        p0 = p1 = 0.0
-        if inject is not None:
-            atm, opts, shifts, p0, p1 = inject
-            sh = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-            spec = np.zeros(self.nwn)
-        give = bool(outputs)
-        data, scale, centre = np.zeros((nexp, npix)), np.zeros((nexp, nseg)), np.zeros(npix)
+        (nexp, nseg), npix = self.mom_shape, self.npix
+        run, flag, p0, p1, spec = self._inject(inject)
+        data, scale, centre = _zeros(outputs, (nexp, npix), (nexp, nseg), npix)
         nc, nb = C.c_int64(0), C.c_int64(0)
-        rc = self._lib.trx_normalise_observed(self._h, C.byref(atm) if atm is not None else None, C.byref(opts) if opts is not None else None,
-                                              _dp(spec), int(sh.size) if sh is not None else 0, _dp(sh), 0 if inject is None else 1,
-                                              float(p0), float(p1), _dp(data) if give else None, _dp(scale) if give else None,
-                                              _dp(centre) if give else None, C.byref(nc), C.byref(nb), None)
-        if rc != 0:
-            raise EngineError(rc, "trx_normalise_observed", self._last_error())
-        return Normalised(data if give else None, scale if give else None, centre if give else None, int(nc.value), int(nb.value), spec)
+        self._call("normalise_observed", *run, flag, p0, p1, _dp(data), _dp(scale), _dp(centre), C.byref(nc), C.byref(nb), None)
+        return Normalised(data, scale, centre, int(nc.value), int(nb.value), spec)
 
     def gather(self, d_slice_ptr: int, d_all_ptr: int, count: int):
         """trx_gather: the one exchange of a sharded job -- every rank's `count` doubles (device
         memory) into d_all in rank order, ncclAllGather over the handle's communicator (a device
         copy without one)."""
-        self._lib.trx_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        self._lib.trx_gather.restype = C.c_int
-        rc = self._lib.trx_gather(self._h, C.c_void_p(d_slice_ptr), C.c_void_p(d_all_ptr), int(count))
-        if rc != 0:
-            raise EngineError(rc, "trx_gather", self._last_error())
+        self._call("gather", C.c_void_p(d_slice_ptr), C.c_void_p(d_all_ptr), int(count))
 
 
 def _rows(a):
@@ -727,17 +614,9 @@ class Batch:
 
     def __init__(self, static: _abi.TrxStatic, ways: int = 3):
         lib = hip_library()
-        lib.trx_batch_create.argtypes = [C.POINTER(_abi.TrxStatic), C.c_int32, C.POINTER(C.c_void_p)]
-        lib.trx_batch_create.restype = C.c_int
-        lib.trx_run_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.TrxAtm), C.POINTER(_abi.TrxOpts),
-                                      C.POINTER(_abi.c_double_p)]
-        lib.trx_run_batch.restype = C.c_int
-        lib.trx_batch_destroy.argtypes = [C.c_void_p]
-        lib.trx_batch_destroy.restype = None
-        lib.trx_last_error.argtypes = [C.c_void_p]
-        lib.trx_last_error.restype = C.c_char_p
         self._lib, self._b = lib, C.c_void_p()
         self.nwn = int(static.wn_hi - static.wn_lo)
+        self.nbands, self.npix, self.mom_shape = 0, 0, (0, 0)       # of the sets installed: none yet
         rc = lib.trx_batch_create(C.byref(static), int(ways), C.byref(self._b))
         if rc != 0:
             raise EngineError(rc, "trx_batch_create", self._err())
@@ -745,13 +624,16 @@ class Batch:
     def _err(self) -> str:
         return (self._lib.trx_last_error(None) or b"").decode(errors="replace")
 
+    def _set(self, name: str, *args):
+        """the batch function `name` on the batch, a non-zero status raised with the batch's last error"""
+        rc = getattr(self._lib, name)(self._b, *args)
+        if rc != 0:
+            raise EngineError(rc, name, self._err())
+
     def _call(self, name: str, atms, opts: _abi.TrxOpts, *args):
         """the batch function `name` over the atmospheres: args are what follows opts in its C signature"""
         k = len(atms)
-        arr = (_abi.TrxAtm * max(k, 1))(*atms)
-        rc = getattr(self._lib, name)(self._b, k, arr, C.byref(opts), *args)
-        if rc != 0:
-            raise EngineError(rc, name, self._err())
+        self._set(name, k, (_abi.TrxAtm * max(k, 1))(*atms), C.byref(opts), *args)
 
     def run(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
         out = np.zeros((len(atms), self.nwn))
@@ -761,14 +643,12 @@ class Batch:
     def set_bands(self, bands):
         """trx_batch_set_bands: the same band set on every handle of the batch, or on none."""
         arr = _bands.to_c(bands)
-        rc = self._lib.trx_batch_set_bands(self._b, len(bands), arr)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_bands", self._err())
+        self._set("trx_batch_set_bands", len(bands), arr)
         self.nbands = len(bands)
 
     def run_bands(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
         """trx_run_batch_bands: [K, nbands, 2], each atmosphere's sums what Engine.run_bands gives, bit for bit."""
-        out = np.zeros((len(atms), getattr(self, "nbands", 0), 2))
+        out = np.zeros((len(atms), self.nbands, 2))
         self._call("trx_run_batch_bands", atms, opts, _rows(out))
         return out
 
@@ -776,7 +656,7 @@ class Batch:
         """trx_run_batch_contrib: ([K, nbands, 2], [K, nbands, nlayer]), each atmosphere's pair what
         Engine.run_contrib gives, bit for bit (the atmospheres of one call share nlayer here)."""
         k = len(atms)
-        nb = getattr(self, "nbands", 0)
+        nb = self.nbands
         nl = int(atms[0].nlayer) if k else 0
         if any(int(a.nlayer) != nl for a in atms):
             raise ValueError("Batch.run_contrib: atmospheres of different nlayer; call it once per nlayer")
@@ -787,9 +667,7 @@ class Batch:
     def set_pixels(self, pixels):
         """trx_batch_set_pixels: the same detector on every handle of the batch, or on none."""
         n = len(pixels) if pixels is not None else 0
-        rc = self._lib.trx_batch_set_pixels(self._b, C.byref(_pixels.to_c(pixels)) if n else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_pixels", self._err())
+        self._set("trx_batch_set_pixels", C.byref(_pixels.to_c(pixels)) if n else None)
         self.npix = n
         self.mom_shape = (0, 0)
 
@@ -797,22 +675,20 @@ class Batch:
         """trx_run_batch_pixels: [K, nshift, npix, 2] for shifts of shape [K][nshift] (atmosphere j at its own shifts),
         each atmosphere's pairs what Engine.run_pixels gives, bit for bit."""
         sh = _per_atmosphere("run_pixels", "shifts of shape [K][nshift]", shifts, len(atms))
-        out = np.zeros((len(atms), sh.shape[1], getattr(self, "npix", 0), 2))
+        out = np.zeros((len(atms), sh.shape[1], self.npix, 2))
         self._call("trx_run_batch_pixels", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
     def set_observed(self, observed):
         """trx_batch_set_observed: the same observed set on every handle of the batch, or on none."""
-        rc = self._lib.trx_batch_set_observed(self._b, C.byref(observed.to_c()) if observed is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_observed", self._err())
+        self._set("trx_batch_set_observed", C.byref(observed.to_c()) if observed is not None else None)
         self.mom_shape = (observed.nexp, observed.nseg) if observed is not None else (0, 0)
 
     def run_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp] (atmosphere j at its own shifts),
         each atmosphere's moments what Engine.run_moments gives, bit for bit."""
         sh = _per_atmosphere("run_moments", "shifts of shape [K][nexp]", shifts, len(atms))
-        out = np.zeros((len(atms),) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        out = np.zeros((len(atms),) + self.mom_shape + (_abi.NMOMENT,))
         self._call("trx_run_batch_moments", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
@@ -820,7 +696,7 @@ class Batch:
         """trx_run_batch_trail: [K, nlag, nexp, nseg, 7] for lags of shape [K][nlag] (atmosphere j at its own lags), each
         atmosphere's trail what Engine.run_trail gives, bit for bit."""
         lg = _per_atmosphere("run_trail", "lags of shape [K][nlag]", lags, len(atms))
-        out = np.zeros((len(atms), lg.shape[1]) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        out = np.zeros((len(atms), lg.shape[1]) + self.mom_shape + (_abi.NMOMENT,))
         self._call("trx_run_batch_trail", atms, opts, int(lg.shape[1]), _rows(lg), _rows(out))
         return out
 
@@ -829,33 +705,27 @@ class Batch:
         -- with per=True, (maps, per [K, nlag, nexp]) --, each atmosphere's what Engine.run_velocity_map gives, bit for
         bit."""
         m = np.zeros((len(atms), vm.nkp, vm.nvsys))
-        pr = np.zeros((len(atms), vm.nlag, getattr(self, "mom_shape", (0, 0))[0])) if per else None
+        pr = np.zeros((len(atms), vm.nlag, self.mom_shape[0])) if per else None
         self._call("trx_run_batch_velocity_map", atms, opts, C.byref(vm.to_c()), _rows(m), _rows(pr))
         return (m, pr) if per else m
 
     def set_filter(self, filt):
         """trx_batch_set_filter: the same filter on every handle of the batch, or on none."""
-        rc = self._lib.trx_batch_set_filter(self._b, C.byref(filt.to_c()) if filt is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_filter", self._err())
+        self._set("trx_batch_set_filter", C.byref(filt.to_c()) if filt is not None else None)
 
     def set_weighted_filter(self, wf):
         """trx_batch_set_weighted_filter: the same weighted filter on every handle of the batch, or on none."""
-        rc = self._lib.trx_batch_set_weighted_filter(self._b, C.byref(wf.to_c()) if wf is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_weighted_filter", self._err())
+        self._set("trx_batch_set_weighted_filter", C.byref(wf.to_c()) if wf is not None else None)
 
     def set_highpass(self, hp):
         """trx_batch_set_highpass: the same high-pass on every handle of the batch, or on none."""
-        rc = self._lib.trx_batch_set_highpass(self._b, C.byref(hp.to_c()) if hp is not None else None)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_highpass", self._err())
+        self._set("trx_batch_set_highpass", C.byref(hp.to_c()) if hp is not None else None)
 
     def run_filtered_moments(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_filtered_moments: [K, nexp, nseg, 7] for shifts of shape [K][nexp], each atmosphere's moments
         what Engine.run_filtered_moments gives, bit for bit."""
         sh = _per_atmosphere("run_filtered_moments", "shifts of shape [K][nexp]", shifts, len(atms))
-        out = np.zeros((len(atms),) + getattr(self, "mom_shape", (0, 0)) + (_abi.NMOMENT,))
+        out = np.zeros((len(atms),) + self.mom_shape + (_abi.NMOMENT,))
         self._call("trx_run_batch_filtered_moments", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
@@ -872,9 +742,7 @@ class Batch:
         all entries are accepted, or none is kept."""
         bs = [] if b is None else list(b) if isinstance(b, (list, tuple)) else [b]
         arr = (_abi.TrxBroadening * max(len(bs), 1))(*[_broaden.to_c(x) for x in bs])
-        rc = self._lib.trx_batch_set_broadening(self._b, len(bs), arr)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_broadening", self._err())
+        self._set("trx_batch_set_broadening", len(bs), arr)
 
     def run_broadened(self, atms, opts: _abi.TrxOpts) -> np.ndarray:
         """trx_run_batch_broadened: [K, nwn], each atmosphere's broadened spectrum what Engine.run_broadened gives with
@@ -889,15 +757,13 @@ class Batch:
         are accepted, or none is kept.  The arrays are copied."""
         xs = [] if ex is None else list(ex) if isinstance(ex, (list, tuple)) else [ex]
         arr = (_abi.TrxExposures * max(len(xs), 1))(*[x.to_c() for x in xs])
-        rc = self._lib.trx_batch_set_exposures(self._b, len(xs), arr)
-        if rc != 0:
-            raise EngineError(rc, "trx_batch_set_exposures", self._err())
+        self._set("trx_batch_set_exposures", len(xs), arr)
 
     def run_exposed(self, atms, opts: _abi.TrxOpts, shifts) -> np.ndarray:
         """trx_run_batch_exposed: [K, nexp, npix, 2] for shifts of shape [K][nexp] (atmosphere j at its own shifts and
         with its own table), each atmosphere's pairs what Engine.run_exposed gives, bit for bit."""
         sh = _per_atmosphere("run_exposed", "shifts of shape [K][nexp]", shifts, len(atms))
-        out = np.zeros((len(atms), sh.shape[1], getattr(self, "npix", 0), 2))
+        out = np.zeros((len(atms), sh.shape[1], self.npix, 2))
         self._call("trx_run_batch_exposed", atms, opts, int(sh.shape[1]), _rows(sh), _rows(out))
         return out
 
@@ -921,7 +787,7 @@ class Batch:
             pass
 
 
-LOG_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
+LOG_FN = _abi.LOG_FN
 _log_keep = None
 
 
@@ -929,8 +795,6 @@ def set_log(callback, max_level: int = 3):
     """Route the library's messages (trx_set_log) to callback(level, text); None = silent."""
     global _log_keep
     lib = hip_library()
-    lib.trx_set_log.argtypes = [LOG_FN, C.c_void_p, C.c_int]
-    lib.trx_set_log.restype = None
     if callback is None:
         _log_keep = LOG_FN(0)
     else:

@@ -25,57 +25,7 @@ def _load():
         if not os.path.exists(path):
             raise RuntimeError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % path)
         lib = C.CDLL(path)
-        lib.trh_load.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
-        lib.trh_load.restype = C.c_int
-        lib.trh_free.argtypes = [C.c_void_p]
-        lib.trh_free.restype = None
-        for name, res in (("trh_static", C.POINTER(_abi.TrxStatic)), ("trh_atm", C.POINTER(_abi.TrxAtm)),
-                          ("trh_opts", C.POINTER(_abi.TrxOpts))):
-            getattr(lib, name).argtypes = [C.c_void_p]
-            getattr(lib, name).restype = res
-        lib.trh_nwn.argtypes = [C.c_void_p]
-        lib.trh_nwn.restype = C.c_int64
-        lib.trh_wavenumbers.argtypes = [C.c_void_p, _abi.c_double_p]
-        lib.trh_wavenumbers.restype = None
-        lib.trh_set_shard.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
-        lib.trh_set_shard.restype = None
-        lib.trh_reload_atm.argtypes = [C.c_void_p, _abi.c_double_p, C.c_int]
-        lib.trh_reload_atm.restype = C.c_int
-        lib.trh_set_radius.argtypes = [C.c_void_p, C.c_double]
-        lib.trh_set_cloudtop.argtypes = [C.c_void_p, C.c_double]
-        lib.trh_set_scattering.argtypes = [C.c_void_p, C.c_int, C.c_double]
-        lib.trh_write_spectrum.argtypes = [C.c_void_p, _abi.c_double_p, C.c_char_p]
-        lib.trh_write_spectrum.restype = C.c_int
-        lib.trh_write_toomuch.argtypes = [C.c_void_p, _abi.c_double_p, _abi.c_int64_p, C.c_char_p]
-        lib.trh_write_toomuch.restype = C.c_int
-        lib.trh_needs_opacity_build.argtypes = [C.c_void_p]
-        lib.trh_needs_opacity_build.restype = C.c_int
-        lib.trh_grid_request.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(_abi.c_double_p),
-                                         C.POINTER(_abi.c_double_p), C.POINTER(_abi.c_double_p),
-                                         C.POINTER(C.c_int32), C.POINTER(_abi.c_int32_p)]
-        lib.trh_grid_request.restype = C.c_int
-        lib.trh_install_opacity.argtypes = [C.c_void_p, _abi.c_double_p]
-        lib.trh_install_opacity.restype = C.c_int
-        lib.trh_option.argtypes = [C.c_void_p, C.c_char_p]
-        lib.trh_option.restype = C.c_char_p
-        lib.trh_messages.argtypes = [C.c_void_p]
-        lib.trh_messages.restype = C.c_char_p
-        lib.trh_output_plan.argtypes = [C.c_void_p]
-        lib.trh_output_plan.restype = C.c_char_p
-        lib.trh_option_table.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_char)]
-        lib.trh_option_table.restype = C.c_int
-        lib.trh_wants_detail.argtypes = [C.c_void_p, C.c_int]
-        lib.trh_wants_detail.restype = C.c_int
-        lib.trh_write_detail.argtypes = [C.c_void_p, C.c_int, _abi.c_double_p]
-        lib.trh_write_detail.restype = C.c_int
-        lib.trh_write_sample.argtypes = [C.c_void_p, C.c_char_p]
-        lib.trh_write_sample.restype = C.c_int
-        lib.trh_write_dumps_masked.argtypes = [C.c_void_p, _abi.c_double_p, _abi.c_double_p, _abi.c_double_p,
-                                               _abi.c_int64_p, C.c_char_p]
-        lib.trh_write_dumps_masked.restype = C.c_int
-        lib.trh_write_ext_dumps.argtypes = [C.c_void_p, _abi.c_double_p, _abi.c_double_p, _abi.c_int64_p,
-                                            _abi.c_double_p, _abi.c_double_p, _abi.c_double_p, C.c_char_p]
-        lib.trh_write_ext_dumps.restype = C.c_int
+        _abi.bind(lib, _abi.HOST_HEADER, "trh_")
         _lib = lib
     return _lib
 
@@ -182,8 +132,6 @@ class Problem:
         """--saveext: (e [nlayer][nwn], computed [nlayer]) of the file, or None when there is no valid one
         (restfile_extinct, extinction.c:97-137)."""
         lib = _load()
-        lib.trh_saveext_read.argtypes = [C.c_void_p, _abi.c_double_p, _abi.c_uint8_p]
-        lib.trh_saveext_read.restype = C.c_int
         e = np.zeros((self.nlayer, self.nwn)); c = np.zeros(self.nlayer, dtype=np.uint8)
         old = os.getcwd()
         try:
@@ -197,8 +145,6 @@ class Problem:
 
     def saveext_write(self, e: np.ndarray, computed: np.ndarray):
         lib = _load()
-        lib.trh_saveext_write.argtypes = [C.c_void_p, _abi.c_double_p, _abi.c_uint8_p]
-        lib.trh_saveext_write.restype = C.c_int
         e = np.ascontiguousarray(e, dtype=np.float64); c = np.ascontiguousarray(computed, dtype=np.uint8)
         old = os.getcwd()
         try:
